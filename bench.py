@@ -10,13 +10,20 @@ the whole front end on one GPU: ORB extract (8-level pyramid, per-cell FAST, oct
 driver's 20 steps make a timed region of ~2 s.  One agent (= one frame stream) per GPU, no data-path
 collective: `value` = frames processed by all ranks / max-over-ranks wall time ("weak" scaling).
 
-Rank 0 prints, as the LAST stdout line, ONE compact JSON object (a few KB: compact()).  Besides the contract keys it carries
+Rank 0 prints, as the LAST stdout line, ONE compact JSON object (a few KB: compact()).  A plain run sets up, warms up, times the
+steps, writes its outputs (--dump-outputs DIR) and prints the contract keys; nothing else runs.  With --full the line also carries
   roofline      -- dominant kernel (FAST cells): algorithmic bytes per launch / HIP-event duration
   cpu_baseline  -- the CPU oracle (port of the reference path) timed single-threaded on this host
   ba            -- bundle-adjustment iterations/s (second half of BASELINE.json's metric): ring map + loop-closed map, summary only
-The complete record (per-stage event spans, VALU issue model, schedules ...) is written to gpurun_out/bench_full.json (--full-json).
+  config_legs, pcie_inclusive, ba_sharded (N > 1), sanity_matches_le_TH_HIGH_last_step
+and the complete record (per-stage event spans, VALU issue model, schedules ...) is written to the --full-json file.
 With --legs (N = 1) the per-call costs of configs 2, 3 and 4 through the drop-in boundary (bench_legs.py: batch_sweep, low_texture,
 latency, online_agents, lba, lba_batch, merge, ba_cold) run too; each prints its own `{"leg": ...}` stdout line BEFORE the contract line.
+
+--dump-outputs DIR: after the timed steps, what the last step computed for a fixed, seeded sample of the frames of its final launch
+groups (one per pipeline lane), as .npy files: keypoints, descriptors, counts and the frame-to-frame matches (float32), and which frames
+they are (frame_index, float64: the frame's place in launch order; the image it read is frame_index % config.resident_stream_frames of
+the agent's stream).  See dump_outputs().
 """
 from __future__ import annotations
 
@@ -58,7 +65,84 @@ def parse():
     ap.add_argument("--no-legs", action="store_true", help="(default since round 5; accepted for old command lines)")
     ap.add_argument("--full-json", default=None, help="where the complete (uncompacted) record goes; default gpurun_out/bench_full.json")
     ap.add_argument("--texture", choices=("rich", "low"), default="rich", help="synthetic stream: the BASELINE corner-rich one, or the weakly textured second workload")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: roofline (HIP events, exclusive pass), PCIe leg, BA legs, "
+                                                       "config legs, CPU baseline, sharded BA (N > 1), the complete record")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed (a fixed sample) to DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+def frame_stream(n, start=0, texture="rich", workers=None):
+    """synth.frame_stream(n, start=start, texture=texture), the frames warped on a few threads (numpy releases the GIL inside each
+    frame's array operations): the same bits, a fraction of the start-up time."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from dvm_slam_amd import synth
+    if workers is None:
+        workers = min(16, len(os.sched_getaffinity(0)), int(os.environ.get("OMP_NUM_THREADS") or 16))
+        workers = max(1, workers // int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
+    tex = synth.base_texture(synth.SEED_FRAMES) if texture == "rich" else synth.low_texture(synth.SEED_FRAMES)
+    out = np.empty((n, synth.HEIGHT, synth.WIDTH), np.uint8)
+
+    def one(t):
+        out[t] = synth._warp(tex, synth.frame_homography(start + t), synth.HEIGHT, synth.WIDTH)
+
+    with ThreadPoolExecutor(max(1, workers)) as ex:
+        list(ex.map(one, range(n)))
+    return out
+
+
+DUMP_MAX_FRAMES = 256      # 178 KB per frame (cap 1 032 keypoints): 46 MB at most
+DUMP_SEED = 0xD0E5
+
+
+def dump_outputs(path, lanes, frame_ids, cap):
+    """What the timed path hands its caller for a fixed, seeded sample (at most DUMP_MAX_FRAMES) of the frames of the given lanes' last
+    launch groups: per frame the keypoint count, the keypoints (x, y, size, angle, response, octave, class_id), the 32-byte descriptors,
+    the frame-to-frame match count (queries = the previous frame's keypoints) and the matches (best_idx, best_dist, second_dist,
+    best_level, second_level).  Rows past a frame's count are zero.  float32 (every integer here is < 2^24), except frame_index: float64,
+    the frame's place in launch order (launch group x batch + slot; the frame before it supplied the match queries), which reads image
+    frame_index % resident_stream_frames of the agent's stream."""
+    import torch
+
+    from dvm_slam_amd import capi
+    avail = [(li, b) for li in range(len(lanes)) for b in range(len(frame_ids[li]))]
+    rng = np.random.default_rng(DUMP_SEED)
+    pick_ = np.sort(rng.choice(len(avail), size=min(DUMP_MAX_FRAMES, len(avail)), replace=False))
+    F = len(pick_)
+    # copy_result writes every row and the count on the extractor's own (non-blocking) stream: no fill kernel on torch's stream may race
+    # it, and whatever torch's stream last did with this memory is finished before the copies start
+    kps = torch.empty((F, cap, 7), dtype=torch.int32, device="cuda")
+    desc = torch.empty((F, cap, 32), dtype=torch.uint8, device="cuda")
+    nk = torch.empty(F, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    for j, p in enumerate(pick_):
+        li, b = avail[p]
+        lanes[li]["ext"].copy_result(b, kps[j].data_ptr(), desc[j].data_ptr(), nk[j:j + 1].data_ptr())
+    for ln in lanes:
+        ln["ext"].sync()
+    torch.cuda.synchronize()
+    kps, desc, nk = kps.cpu().numpy(), desc.cpu().numpy(), nk.cpu().numpy()
+    lane_m = [ln["matches"].cpu().numpy() for ln in lanes]
+    lane_nq = [ln["nq"].cpu().numpy() for ln in lanes]
+    m = np.ascontiguousarray(np.stack([lane_m[avail[p][0]][avail[p][1], :cap] for p in pick_]))
+    nq = np.array([lane_nq[avail[p][0]][avail[p][1]] for p in pick_], np.int64)
+
+    def fields(rec, dtype, n):
+        r = rec.view(dtype).reshape(F, cap)
+        v = np.stack([r[f].astype(np.float32) for f in dtype.names], axis=-1)
+        return np.where((np.arange(cap)[None, :] < n[:, None])[..., None], v, np.float32(0))
+
+    keypoints = fields(kps, capi.KP_DTYPE, nk)
+    descriptors = np.where((np.arange(cap)[None, :] < nk[:, None])[..., None], desc.astype(np.float32), np.float32(0))
+    matches = fields(m, capi.MATCH_DTYPE, nq)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("frame_index", np.array([frame_ids[avail[p][0]][avail[p][1]] for p in pick_], np.float64)),
+                      ("n_keypoints", nk.astype(np.float32)), ("keypoints", keypoints), ("descriptors", descriptors),
+                      ("n_match_queries", nq.astype(np.float32)), ("matches", matches)):
+        np.save(os.path.join(path, f"{name}.npy"), arr)
 
 
 def cpu_all_cores(libpath, seconds=3.0, max_procs=64):
@@ -201,7 +285,7 @@ def compact(out):
         except Exception:   # noqa: BLE001
             cr["valu_busy"] = None
         c["roofline"] = cr
-    else:
+    elif "roofline" in out:     # (a plain run has none: --full)
         c["roofline"] = None
     cb = out.get("cpu_baseline")
     if cb:
@@ -240,7 +324,8 @@ def compact(out):
             c["ba_sharded"]["replicas"] = pick(sh["replicas"], "value", "ranks")
     if isinstance(out.get("pcie_inclusive"), dict):
         c["pcie_inclusive"] = pick(out["pcie_inclusive"], "value", "unit", "h2d_gbps")
-    c["sanity_matches_le_TH_HIGH_last_step"] = out.get("sanity_matches_le_TH_HIGH_last_step")
+    if "sanity_matches_le_TH_HIGH_last_step" in out:
+        c["sanity_matches_le_TH_HIGH_last_step"] = out["sanity_matches_le_TH_HIGH_last_step"]
     cl = {}
     try:
         lat = out["latency"]
@@ -274,9 +359,10 @@ def emit(out, a):
     file (gpurun_out/bench_full.json travels back from the GPU box) so that nothing the old one-line form carried is lost."""
     path = a.full_json or os.path.join(ROOT, "gpurun_out", "bench_full.json")
     try:
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(out, f)
+        if a.full or a.full_json:       # a plain run writes no record unless --full-json names one
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "w") as f:
+                json.dump(out, f)
     except OSError as ex:
         print(f"bench.py: full record not written ({ex})", file=sys.stderr)
     for k in LEG_KEYS:
@@ -357,7 +443,7 @@ def main():
     nstream = max(a.stream_frames, B)
     nstream = (nstream + B - 1) // B * B
     # every rank is its own agent: a different segment of the camera path
-    frames = synth.frame_stream(nstream, start=exchange.agent_stream_segment(rank, nstream), texture=a.texture)
+    frames = frame_stream(nstream, start=exchange.agent_stream_segment(rank, nstream), texture=a.texture)
     d_frames = torch.from_numpy(frames).cuda()
     H, W = frames.shape[1:]
 
@@ -415,8 +501,9 @@ def main():
         step(i)
     for ln in lanes:
         ln["ext"].sync()
-        ln["ext"].profiling(2)          # HIP events around the dominant kernel only: the roofline's live launch duration.  Events around
-        ln["ext"].profile_reset()       # all six stages are twelve marker packets per launch group = 1-2 % of the timed region
+        if a.full:
+            ln["ext"].profiling(2)      # HIP events around the dominant kernel only: the roofline's live launch duration.  Events around
+            ln["ext"].profile_reset()   # all six stages are twelve marker packets per launch group = 1-2 % of the timed region
     barrier()
     t0 = time.perf_counter()
     for i in range(a.steps):
@@ -425,6 +512,11 @@ def main():
     dt = time.perf_counter() - t0
     for ln in lanes:
         ln["ext"].profiling(False)
+    if a.dump_outputs and rank == 0:
+        # each lane still holds its last launch group: those of the last step, before anything below launches more
+        last_chunk = (a.warmup + a.steps) * chunks - 1
+        idx = [i for i in range(last_chunk - nl + 1, last_chunk + 1) if i >= (a.warmup + a.steps - 1) * chunks and i >= 0]
+        dump_outputs(a.dump_outputs, [lanes[i % nl] for i in idx], [[i * B + b for b in range(B)] for i in idx], cap)
     dt = exchange.max_over_ranks(dt, device="cuda" if backend == "nccl" else "cpu")
     # which GPU every rank ran on, gathered over the same process group the timing used (the line reports what was launched, not what was asked for)
     rank_devices = [local]
@@ -433,40 +525,42 @@ def main():
         got = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(got, mine)
         rank_devices = [int(g[2].item()) for g in sorted(got, key=lambda g: int(g[0].item()))]
-    prof = {}
-    parts = [ln["ext"].profile_get("fast") for ln in lanes]
-    prof["fast"] = (sum(p[0] for p in parts), sum(p[1] for p in parts))
-    # the other stages' event spans from two further, untimed steps with events around everything (not part of `value`)
-    for ln in lanes:
-        ln["ext"].profiling(True)
-        ln["ext"].profile_reset()
-    for i in range(min(2, a.steps)):
-        step(a.warmup + a.steps + i)
-    barrier()
-    for ln in lanes:
-        ln["ext"].profiling(False)
-    for k in ("pyramid", "octree", "assemble", "blur", "orient_desc"):
-        parts = [ln["ext"].profile_get(k) for ln in lanes]
-        prof[k] = (sum(p[0] for p in parts), sum(p[1] for p in parts))
-    last = lanes[((a.warmup + a.steps) * chunks - 1) % nl]
-    valid = torch.arange(last["matches"].shape[1], device="cuda")[None, :] < last["nq"][:, None]     # rows beyond a pair's query count are stale
-    nmatched = int(((last["matches"][:, :, 1] <= 100) & valid).sum().item())  # TH_HIGH gate, sanity only
-    ext, grid = lanes[0]["ext"], lanes[0]["grid"]
-    # k_fast_cells alone on the chip (one lane, nothing overlapping it): the kernel-quality figure next to the one the
-    # pipelined timed region yields; same live HIP-event measurement, 8 further steps, not part of `value`
-    excl = None
-    if nl > 1 and not a.no_exclusive:
-        ext.profiling(True); ext.profile_reset()
-        for i in range(8):
-            ext.extract_batch_device(d_frames.data_ptr() + (i % nbatches) * B * H * W, B, H, W)
-        ext.sync()
-        ext.profiling(False)
-        excl = ext.profile_get("fast")
+    # --full: the roofline's event spans, two untimed steps with events around every stage, the sanity count, the exclusive pass
+    prof, nmatched, excl = {"fast": (0.0, 0)}, None, None
+    if a.full:
+        prof = {}
+        parts = [ln["ext"].profile_get("fast") for ln in lanes]
+        prof["fast"] = (sum(p[0] for p in parts), sum(p[1] for p in parts))
+        # the other stages' event spans from two further, untimed steps with events around everything (not part of `value`)
+        for ln in lanes:
+            ln["ext"].profiling(True)
+            ln["ext"].profile_reset()
+        for i in range(min(2, a.steps)):
+            step(a.warmup + a.steps + i)
+        barrier()
+        for ln in lanes:
+            ln["ext"].profiling(False)
+        for k in ("pyramid", "octree", "assemble", "blur", "orient_desc"):
+            parts = [ln["ext"].profile_get(k) for ln in lanes]
+            prof[k] = (sum(p[0] for p in parts), sum(p[1] for p in parts))
+        last = lanes[((a.warmup + a.steps) * chunks - 1) % nl]
+        valid = torch.arange(last["matches"].shape[1], device="cuda")[None, :] < last["nq"][:, None]     # rows beyond a pair's query count are stale
+        nmatched = int(((last["matches"][:, :, 1] <= 100) & valid).sum().item())  # TH_HIGH gate, sanity only
+        ext, grid = lanes[0]["ext"], lanes[0]["grid"]
+        # k_fast_cells alone on the chip (one lane, nothing overlapping it): the kernel-quality figure next to the one the
+        # pipelined timed region yields; same live HIP-event measurement, 8 further steps, not part of `value`
+        if nl > 1 and not a.no_exclusive:
+            ext.profiling(True); ext.profile_reset()
+            for i in range(8):
+                ext.extract_batch_device(d_frames.data_ptr() + (i % nbatches) * B * H * W, B, H, W)
+            ext.sync()
+            ext.profiling(False)
+            excl = ext.profile_get("fast")
 
     # BASELINE config 5: the 500-keyframe global BA landmark-sharded over all ranks (dvm_slam_amd/sharded_ba.py), reported beside
     # the one-GPU number of the `ba` leg.  Every rank takes part; a watchdog bounds the damage if a collective wedges.
     sharded_rec = None
-    if use_dist and not a.no_ba:
+    if a.full and use_dist and not a.no_ba:
         import threading
         box = {}
 
@@ -618,16 +712,17 @@ def main():
                        "ranks": {"count": world, "backend": ("rccl" if backend == "nccl" else backend) if use_dist else "none (single process)",
                                  "cuda_device_of_rank": rank_devices, "launched_by": "bench.py itself (--gpus N without a launcher)"
                                  if os.environ.get("DVM_BENCH_RELAUNCHED") == "1" else ("torch.distributed.run" if "WORLD_SIZE" in os.environ else "python")}},
-            "roofline": roof, "sanity_matches_le_TH_HIGH_last_step": nmatched,
         }
-        if world == 1 and not a.no_pcie:
+        if a.full:
+            out["roofline"], out["sanity_matches_le_TH_HIGH_last_step"] = roof, nmatched
+        if a.full and world == 1 and not a.no_pcie:
             for ln in lanes:             # a handle owns two streams; more than four per process share hardware queues
                 ln["ext"].close(); ln["grid"].close()
             out["pcie_inclusive"] = pcie_inclusive_leg(capi, frames, B, max(16, a.steps * chunks // 8), local)
         # BA leg first, while the GPU is still in its operating power state from the extract leg: the LM loop alone
         # (host-synchronised, mostly single-workgroup kernels) does not lift an idle MI355X off its 584 MHz idle clock
         # (measured: 315 it/s cold vs 1050 it/s hot); the CPU baseline below leaves the GPU idle for ~12 s.
-        if not a.no_ba:
+        if a.full and not a.no_ba:
             try:
                 import ba_bench
                 out["ba"] = ba_bench.run(local, a.ba_iters, cpu_seconds=6.0 if a.cpu_seconds > 0 else 0.0)
@@ -656,8 +751,8 @@ def main():
                     out[name] = fn()
                 except Exception as ex:   # noqa: BLE001 -- a leg that fails must not take the contract line with it
                     out[name] = {"error": repr(ex)}
-        if world == 1 and not a.no_config_legs:
-            # configs 2 / 3 in every default run (short forms of the --legs records, no CPU legs): per-call latencies of the tracked frame,
+        if a.full and world == 1 and not a.no_config_legs:
+            # configs 2 / 3 in every --full run (short forms of the --legs records, no CPU legs): per-call latencies of the tracked frame,
             # the local-BA window call and the merge chain through the drop-in boundary -> `config_legs` of the contract line
             import bench_legs
             for name, fn in (("latency", lambda: bench_legs.latency(capi, frames[:64], local, calls=200, cpu_calls=0)),
@@ -670,7 +765,7 @@ def main():
                     out[name] = fn()
                 except Exception as ex:   # noqa: BLE001
                     out[name] = {"error": repr(ex)}
-        if a.cpu_seconds > 0:
+        if a.full and a.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(frames, a.cpu_seconds)
         flush_c_stdio()
         emit(out, a)

@@ -142,11 +142,11 @@ def batch_sweep(batches=(1, 8, 32), steps=3, frames_per_step=4096):
     import json
     import subprocess
     out = {"unit": "frames/s (device-resident frames, two pipeline lanes)", "by_batch": {},
-           "note": "bench.py --batch B --no-ba --no-legs --no-pcie --no-exclusive --cpu-seconds 0; launch-group latency = ms_per_launch_group"}
+           "note": "bench.py --full --batch B --no-ba --no-legs --no-pcie --no-exclusive --cpu-seconds 0; launch-group latency = ms_per_launch_group"}
     for B in batches:
         chunks = max(2, min(frames_per_step // B, 1024))
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--batch", str(B), "--chunks-per-step", str(chunks), "--steps", str(steps), "--warmup", "1",
-               "--stream-frames", str(max(256, 4 * B)), "--no-ba", "--no-legs", "--no-pcie", "--no-exclusive", "--cpu-seconds", "0"]
+               "--stream-frames", str(max(256, 4 * B)), "--full", "--no-ba", "--no-legs", "--no-pcie", "--no-exclusive", "--cpu-seconds", "0"]
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
@@ -168,7 +168,7 @@ def low_texture(capi, device, cpu=True, steps=3):
     from dvm_slam_amd import synth
     out = {"unit": "frames/s", "stream": "synth.low_texture through the same camera path; bench.py --texture low (256-frame launch groups, two lanes, frames resident in HBM)"}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--texture", "low", "--steps", str(steps), "--warmup", "1", "--stream-frames", "512", "--no-ba", "--no-legs",
-           "--no-pcie", "--cpu-seconds", "0"]
+           "--full", "--no-pcie", "--cpu-seconds", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, env=env)
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

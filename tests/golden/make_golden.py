@@ -187,9 +187,39 @@ def triangulation():
     print("triangulation", np.bincount(st, minlength=10))
 
 
+def ref_dutils():
+    """DUtils::Random as the reference's own object code draws (oracle/_ref/libdutils_ref.so, `make -C oracle _ref`): what
+    tests/test_ref_dutils.py checks the restatements against where that library was not built.  Run in a fresh process."""
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    from ref_dutils import draw_minimal_sets, load_reference
+    from test_ref_dutils import RANGES, SEEDS
+    ref = load_reference()
+    assert ref is not None, "build oracle/_ref first (make -C oracle _ref)"
+    ref.lib._ZN6DUtils6Random12SeedRandOnceEi(77)         # the first call of the process seeds
+    once_first = [ref.random_int(0, 1000) for _ in range(20)]
+    ref.seed(5)
+    ref.lib._ZN6DUtils6Random12SeedRandOnceEi(99)         # a later one leaves the stream alone
+    once_later = [ref.random_int(0, 1000) for _ in range(20)]
+    streams = np.zeros((len(SEEDS), len(RANGES), 500), np.int64)
+    for i, seed in enumerate(SEEDS):
+        for j, (lo, hi) in enumerate(RANGES):
+            ref.seed(seed)
+            streams[i, j] = [ref.random_int(lo, hi) for _ in range(500)]
+    sets = []
+    for n in (3, 4, 20, 137):
+        ref.seed(42)
+        sets.append(draw_minimal_sets(ref.random_int, n, 200))
+    np.savez_compressed(os.path.join(HERE, "ref_dutils_random.npz"), seeds=np.array(SEEDS, np.int64), ranges=np.array(RANGES, np.int64),
+                        streams=streams, once_first=np.array(once_first, np.int64), once_later=np.array(once_later, np.int64),
+                        minimal_sets_n=np.array([3, 4, 20, 137], np.int64), minimal_sets=np.array(sets, np.int64))
+    print("ref_dutils", streams.shape, once_first[:4], once_later[:4])
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "tri":
         triangulation()
+    elif len(sys.argv) > 1 and sys.argv[1] == "dutils":
+        ref_dutils()
     elif len(sys.argv) > 1 and sys.argv[1] == "db":
         db_wire()
     elif len(sys.argv) > 1 and sys.argv[1] == "more":

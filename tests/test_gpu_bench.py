@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def _contract_line(stdout):
 def _run(*extra, tmp):
     full = os.path.join(str(tmp), "full.json")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "64", "--stream-frames", "128",
-                          "--chunks-per-step", "3", "--full-json", full, *extra], capture_output=True, text=True, timeout=600)
+                          "--chunks-per-step", "3", "--full", "--full-json", full, *extra], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d, before = _contract_line(out.stdout)
     assert before == [], out.stdout[-2000:]          # no --legs: the contract line is the only JSON on stdout
@@ -69,7 +70,7 @@ def test_bench_two_ranks_control_flow(tmp_path):
     env = dict(os.environ, DVM_BENCH_SHARE_GPU="1", DVM_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29577",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "32", "--stream-frames", "64",
-           "--chunks-per-step", "2", "--ba-iters", "3", "--cpu-seconds", "0", "--full-json", str(tmp_path / "full.json")]
+           "--chunks-per-step", "2", "--ba-iters", "3", "--cpu-seconds", "0", "--full", "--full-json", str(tmp_path / "full.json")]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d, before = _contract_line(out.stdout)
@@ -109,3 +110,58 @@ def test_bench_plain_command_honours_gpus():
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"], capture_output=True, text=True,
                          timeout=120, env=dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"))
     assert bad.returncode != 0 and "must agree" in (bad.stderr + bad.stdout)
+
+
+DUMPED = ("frame_index", "n_keypoints", "keypoints", "descriptors", "n_match_queries", "matches")
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path, oracle):
+    """A plain run (no --full) prints the contract keys and nothing that needs a run of its own; --steps sets the timed steps; and
+    --dump-outputs writes what the last timed step computed: the same arrays on a second run, the CPU oracle's keypoints and descriptors
+    for the frames they name."""
+    from dvm_slam_amd import exchange, synth
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32",
+                              "--stream-frames", "64", "--chunks-per-step", "2", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line, before = _contract_line(out.stdout)
+        assert before == [], out.stdout[-2000:]
+        return line, {n: np.load(d / f"{n}.npy") for n in DUMPED}
+
+    d, o = run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "config"):
+        assert k in d, k
+    for k in ("roofline", "cpu_baseline", "ba", "pcie_inclusive", "config_legs", "sanity_matches_le_TH_HIGH_last_step"):
+        assert k not in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    assert abs(d["value"] - 3 * 2 * 32 / (d["ms_per_step"] * 3 / 1e3)) < 1e-6 * d["value"]
+    assert all(a.dtype in (np.float32, np.float64) for a in o.values()) and sum(a.nbytes for a in o.values()) <= 64 << 20
+    # 1 + 3 steps of 2 launch groups: the last step is launch groups 6 and 7 (one per lane), 64 frames, all of them dumped
+    fi = o["frame_index"].astype(np.int64)
+    assert sorted(fi) == list(range(6 * 32, 8 * 32))
+    assert o["keypoints"].shape[:1] == o["descriptors"].shape[:1] == o["matches"].shape[:1] == (64,)
+    assert (o["n_keypoints"] > 500).all() and (o["matches"][:, :, 1][o["matches"][:, :, 0] >= 0] <= 256).all()
+    d2, o2 = run(tmp_path / "b")
+    for n in DUMPED:
+        assert np.array_equal(o[n], o2[n]), n
+    stream = synth.frame_stream(64, start=exchange.agent_stream_segment(0, 64))
+    orc = oracle.OrbOracle()
+    scale = orc.tables()["scale"]
+    for j in (0, 31, 32, 63):     # 0 and 32: the first pair of a launch group (its queries = the previous group's last frame)
+        n, k, desc, _ = orc.extract(stream[fi[j] % 64])
+        assert int(o["n_keypoints"][j]) == n
+        for c, f in enumerate(("x", "y", "size", "angle", "response", "octave")):
+            assert np.array_equal(o["keypoints"][j, :n, c], k[f].astype(np.float32)), f
+        assert np.array_equal(o["descriptors"][j, :n], desc.astype(np.float32))
+        assert not o["keypoints"][j, n:].any() and not o["descriptors"][j, n:].any()
+        # the frame-to-frame match of this frame (train) against the frame launched before it (queries), as the oracle's window search
+        nq, kq, dq, _ = orc.extract(stream[(fi[j] - 1) % 64])
+        assert int(o["n_match_queries"][j]) == nq
+        ref = oracle.Grid(k).match_window(desc, dq, kq["x"], kq["y"], (np.float32(15) * scale[kq["octave"]]).astype(np.float32),
+                                          kq["octave"] - 1, kq["octave"] + 1)
+        for c, f in enumerate(("best_idx", "best_dist", "second_dist", "best_level", "second_level")):
+            assert np.array_equal(o["matches"][j, :nq, c], ref[f].astype(np.float32)), f
+        assert not o["matches"][j, nq:].any()
+        if fi[j] % 64:            # neighbours on the camera path (image 0's queries come from image 63, where the stream wraps)
+            assert (ref["best_dist"] <= 50).mean() > 0.5

@@ -39,7 +39,7 @@ def test_exchange_and_sharded_ba_over_rccl():
 
 def test_bench_distributed_control_flow_over_rccl(tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--chunks-per-step", "2",
-           "--stream-frames", "256", "--cpu-seconds", "0", "--no-pcie", "--no-exclusive", "--ba-iters", "3", "--full-json", str(tmp_path / "full.json")]
+           "--stream-frames", "256", "--cpu-seconds", "0", "--no-pcie", "--no-exclusive", "--ba-iters", "3", "--full", "--full-json", str(tmp_path / "full.json")]
     env = _env(29656)
     env["DVM_BENCH_FORCE_DIST"] = "1"
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
