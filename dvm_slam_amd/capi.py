@@ -956,6 +956,48 @@ class Tracker:
         return out
 
 
+    def reserve_local_map(self, n):
+        """dvm_tracker_reserve_local_map: the second half's working set for tables of up to n points (allocated once)."""
+        f = self.L.dvm_tracker_reserve_local_map
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32]
+        check(f(self.t, int(n)))
+
+    def track_local_map(self, pts, frame_mp, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
+        """dvm_track_local_map: Tracking::TrackLocalMap of the frame the last track() call tracked (reference src/Tracking.cc:2668-2740) as
+        ONE device chain.  pts: LOCAL_POINT_DTYPE array (the local map); frame_mp [n]: per keypoint the index into pts of the point the
+        frame holds, or -1.  Returns a dict: mp (mvpMapPoints after the search), outlier (mvbOutlier), track_pts (TRACK_DTYPE per entry,
+        if asked), the counters of dvm_track_local_result, pose (7 doubles: t, q) and Tcw (7 floats: q, t)."""
+        pts = np.ascontiguousarray(pts, LOCAL_POINT_DTYPE)
+        frame_mp = np.ascontiguousarray(frame_mp, np.int32)
+        n_kp = len(frame_mp)
+        mp = np.empty(max(n_kp, 1), np.int32); outl = np.empty(max(n_kp, 1), np.uint8)
+        tp = np.zeros(max(len(pts), 1), TRACK_DTYPE) if want_track_points else None
+        res = TrackLocalResult()
+        f = self.L.dvm_track_local_map
+        f.restype = C.c_int32
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                      C.c_void_p, C.POINTER(TrackLocalResult)]
+        check(f(self.t, self.ext.h, _p(pts) if len(pts) else None, len(pts), _p(frame_mp), float(th), int(bool(far_points)), float(th_far),
+                _p(mp), _p(outl), _p(tp), C.byref(res)))
+        out = {k: getattr(res, k) for k in ("n_to_match", "nmatches", "n_requeried", "n_cleared_bad", "n_edges", "n_inliers", "matches_inliers")}
+        out.update(mp=mp[:n_kp], outlier=outl[:n_kp], pose=np.array(res.pose[:], np.float64), Tcw=np.array(res.Tcw[:], np.float32))
+        if want_track_points:
+            out["track_pts"] = tp[:len(pts)]
+        return out
+
+
+# dvm_local_point (include/dvmslam_hip.h): one mvpLocalMapPoints entry -- GetWorldPos, GetNormal, mfMinDistance / mfMaxDistance,
+# GetDescriptor, Observations, isBad
+LOCAL_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_dist", "<f4"), ("max_dist", "<f4"), ("desc", "u1", (32,)),
+                              ("n_obs", "<i4"), ("bad", "<i4")])
+
+
+class TrackLocalResult(C.Structure):
+    """dvm_track_local_result (include/dvmslam_hip.h)"""
+    _fields_ = [(k, C.c_int32) for k in ("n_to_match", "nmatches", "n_requeried", "n_cleared_bad", "n_edges", "n_inliers", "matches_inliers",
+                                         "reserved")] + [("pose", C.c_double * 7), ("Tcw", C.c_float * 7), ("reserved2", C.c_int32)]
+
+
 class TrackIn(C.Structure):
     """dvmh_track_in (include/dvmslam_host.h)"""
     _fields_ = [("Tcw_pred", C.c_void_p), ("Nl", C.c_int32), ("kps_l", C.c_void_p), ("mp_l", C.c_void_p), ("outlier_l", C.c_void_p), ("mps", C.c_void_p)]

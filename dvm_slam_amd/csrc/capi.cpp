@@ -45,6 +45,7 @@ struct dvm_frame {
 };
 
 namespace dvm { FrameView frame_view_of(const ::dvm_frame* f) { return f->view; } }
+namespace dvm { uint64_t orb_result_serial(const dvm_orb* h) { return h->serial; } }
 
 static int need_device(int device) {
   int n = 0;

@@ -10,6 +10,7 @@
 // tie" becomes "smallest sorted position wins", an associative rule a wavefront can reduce.
 #include <hip/hip_runtime.h>
 
+#include "frustum_point.h"
 #include "match_kernels.h"
 #include "pose_f32.h"
 #include "undistort_f64.h"
@@ -567,38 +568,14 @@ __global__ void __launch_bounds__(256) k_bowdb_query(const int64_t* __restrict__
 }
 
 // Frame::isInFrustum, mono branch (reference src/Frame.cc:575-636) + MapPoint::PredictScale
-// (src/MapPoint.cc:573-587): thread per map point, float arithmetic in the reference's order.
+// (src/MapPoint.cc:573-587): thread per map point, float arithmetic in the reference's order (frustum_point.h).
 __global__ void __launch_bounds__(256) k_is_in_frustum(FrustumFrame F, const float* __restrict__ P, const float* __restrict__ normal,
                                                        const float* __restrict__ min_dist, const float* __restrict__ max_dist,
                                                        int n, float cos_limit, TrackPoint* __restrict__ out) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  TrackPoint o;
-  o.in_view = 0; o.proj_x = -1; o.proj_y = -1; o.proj_xr = 0; o.depth = 0; o.level = -1; o.view_cos = 0;
-  const float p0 = P[3 * i], p1 = P[3 * i + 1], p2 = P[3 * i + 2];
-  // Pc = mRcw * P + mtcw (Frame.cc:585): Eigen's 3x3 * 3x1 coefficient is a0 + (a1 + a2)
-  const float X = dvm_pose::sum3(F.Rcw[0] * p0, F.Rcw[1] * p1, F.Rcw[2] * p2) + F.tcw[0];
-  const float Y = dvm_pose::sum3(F.Rcw[3] * p0, F.Rcw[4] * p1, F.Rcw[5] * p2) + F.tcw[1];
-  const float Z = dvm_pose::sum3(F.Rcw[6] * p0, F.Rcw[7] * p1, F.Rcw[8] * p2) + F.tcw[2];
-  const float Pc_dist = sqrtf(dvm_pose::sum3(X * X, Y * Y, Z * Z));
-  const float invz = 1.0f / Z;
-  bool ok = !(Z < 0.0f);
-  const float u = F.fx * X / Z + F.cx, v = F.fy * Y / Z + F.cy;
-  ok = ok && !(u < F.min_x || u > F.max_x) && !(v < F.min_y || v > F.max_y);
-  if (ok) {
-    o.proj_x = u; o.proj_y = v;
-    const float maxDistance = 1.2f * max_dist[i], minDistance = 0.8f * min_dist[i];
-    const float q0 = p0 - F.Ow[0], q1 = p1 - F.Ow[1], q2 = p2 - F.Ow[2];
-    const float dist = sqrtf(dvm_pose::sum3(q0 * q0, q1 * q1, q2 * q2));
-    if (!(dist < minDistance || dist > maxDistance)) {
-      const float viewCos = dvm_pose::sum3(q0 * normal[3 * i], q1 * normal[3 * i + 1], q2 * normal[3 * i + 2]) / dist;
-      if (!(viewCos < cos_limit)) {
-        const int nScale = dvm_pose::predict_scale(max_dist[i], dist, F.log_scale_factor, F.n_levels);
-        o.in_view = 1; o.proj_xr = u - F.bf * invz; o.depth = Pc_dist; o.level = nScale; o.view_cos = viewCos;
-      }
-    }
-  }
-  out[i] = o;
+  out[i] = frustum_point(F, P[3 * i], P[3 * i + 1], P[3 * i + 2], normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], min_dist[i], max_dist[i],
+                         cos_limit);
 }
 
 // LocalMapping::CreateNewMapPoints, the geometry of one neighbour keyframe's matches (reference src/LocalMapping.cc:598-741, monocular

@@ -14,6 +14,7 @@
 // Tracking.cc:2616-2624: call dvm_track_finish again with the wider queries -- no new extraction), and a query whose four ranked
 // candidates were all taken by earlier queries (the list may go on: the caller replays the epilogue from the ranked lists on the host).
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +29,17 @@
 #include "track_kernels.h"
 
 using namespace dvm;
+
+// what the second half (dvm_track_local_map) runs on: set by a dvm_track_finish of one frame that returned DVM_TRACK_COMPLETE, cleared by
+// any begin / finish and by the second half itself
+struct LocalFrame {
+  int ready = 0;
+  dvm_orb* h = nullptr; uint64_t serial = 0;     // the extractor and which of its extractions the frame is
+  int n = 0, ocap = 0, nlevels = 0;
+  const dvm_keypoint_pod* d_un = nullptr; const int32_t* d_n = nullptr;   // mvKeysUn on the device, the keypoint count
+  float bounds[4] = {0, 0, 0, 0}, inv_sigma2[64] = {};
+  dvm_ba_camera cam{};
+};
 
 struct dvm_tracker {
   int device = 0, kp_cap = 0, q_cap = 0, max_frames = 1;
@@ -53,7 +65,17 @@ struct dvm_tracker {
   template <class T> T* qdev(T* host_ptr) const { return reinterpret_cast<T*>(d_q + (reinterpret_cast<uint8_t*>(host_ptr) - hm)); }
   int begun = 0;                   // frames of the batch whose extraction is queued
   int rows = 0, cols = 0;
+  // ---- the second half (dvm_track_local_map): working set of dvm_tracker_reserve_local_map, and what the last finish left for it
+  int lm_cap = 0;                  // table entries reserved (a multiple of 64)
+  uint8_t* d_lm = nullptr;         // device: [upload][per-entry arrays][query arrays][ranked lists][counters]
+  uint8_t *hm_lm = nullptr, *hm_lm_dev = nullptr;   // mapped: [upload staging][results]
+  size_t lm_up_bytes = 0;          // the upload region's capacity (device copy at the start of d_lm)
+  struct LocalMapped { int32_t* mp; uint8_t* outlier; TrackPoint* tp; int32_t* res; double* pose; int32_t *n_inl, *fin, *nedges; } lm;
+  LocalFrame lf;
+  template <class T> T* lmdev(T* host_ptr) const { return reinterpret_cast<T*>(hm_lm_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm_lm)); }
 };
+
+namespace dvm { uint64_t orb_result_serial(const dvm_orb* h); }   // capi.cpp: which extraction the handle's result holds
 
 namespace {
 size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -121,6 +143,8 @@ void dvm_tracker_destroy(dvm_tracker* t) {
   if (t->grid) dvm_frame_destroy(t->grid);
   if (t->d_buf) hipFree(t->d_buf);
   if (t->d_q) hipFree(t->d_q);
+  if (t->d_lm) hipFree(t->d_lm);
+  if (t->hm_lm) hipHostFree(t->hm_lm);
   if (t->cev) hipEventDestroy(t->cev);
   if (t->cstream) hipStreamDestroy(t->cstream);
   if (t->hm) hipHostFree(t->hm);
@@ -130,7 +154,7 @@ void dvm_tracker_destroy(dvm_tracker* t) {
 int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_batch: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0;
+  t->begun = 0; t->lf.ready = 0;
   const int rc = dvm_orb_extract_batch_host(h, imgs, count, rows, cols, stride, frame_stride, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
@@ -139,7 +163,7 @@ int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int c
 int dvm_track_begin_staged(dvm_tracker* t, dvm_orb* h, int count, int rows, int cols, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_staged: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0;
+  t->begun = 0; t->lf.ready = 0;
   const int rc = dvm_orb_extract_staged(h, count, rows, cols, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
@@ -151,6 +175,7 @@ int dvm_track_begin(dvm_tracker* t, dvm_orb* h, const uint8_t* img, int rows, in
 
 int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* qs, const dvm_track_frame_out* outs, dvm_track_result* res) {
   if (!t || !h || !qs || !outs || !res || count < 1) return DVM_ERR_INVALID;
+  t->lf.ready = 0;
   if (t->begun != count) { set_error("dvm_track_finish: no matching dvm_track_begin on this tracker"); return DVM_ERR_STATE; }
   const dvm_track_queries& q0 = qs[0];
   int nq_max = 0;
@@ -268,6 +293,12 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
     r.n_edges = m.nedges[b]; r.n_inliers = m.n_inl[b]; r.nmatches_map = m.fin[4 * b]; r.nmatches_after = m.fin[4 * b + 1];
     std::memcpy(r.pose, m.pose_out + 7 * (size_t)b, 56);
   }
+  if (count == 1 && res[0].status == DVM_TRACK_COMPLETE) {     // what the second half runs on: this frame's grid (slot 0) and mvKeysUn
+    LocalFrame& f = t->lf;
+    f.ready = 1; f.h = h; f.serial = orb_result_serial(h); f.n = res[0].n; f.ocap = ocap; f.nlevels = q0.nlevels;
+    f.d_un = reinterpret_cast<const dvm_keypoint_pod*>(d_un); f.d_n = d_n;
+    std::memcpy(f.bounds, q0.bounds, 16); std::memcpy(f.inv_sigma2, q0.inv_level_sigma2, (size_t)q0.nlevels * 4); f.cam = q0.cam;
+  }
   return DVM_OK;
 }
 
@@ -276,6 +307,138 @@ int dvm_track_finish(dvm_tracker* t, dvm_orb* h, const dvm_track_queries* q, dvm
   if (!q || !res) return DVM_ERR_INVALID;
   dvm_track_frame_out o{kps, desc, cap, kps_un, assign, outlier, ranked};
   return dvm_track_finish_batch(t, h, 1, q, &o, res);
+}
+
+// ---- the second half: Tracking::TrackLocalMap (src/Tracking.cc:2668-2740) behind the first
+namespace {
+// the upload block of one call, carved in the mapped staging buffer and at the same offsets in the device copy:
+// [first half's pose 7 doubles][mvScaleFactors 64][mvInvLevelSigma2 64][table: n records][frame_mp: N]
+struct LocalUpload { double* pose; float *scale, *inv_sigma2; LocalPointPod* pts; int32_t* frame_mp; size_t bytes; };
+LocalUpload carve_upload(uint8_t* base, int n, int N) {
+  LocalUpload u;
+  uint8_t* p = base;
+  u.pose = carve<double>(p, 7); u.scale = carve<float>(p, 64); u.inv_sigma2 = carve<float>(p, 64);
+  u.pts = carve<LocalPointPod>(p, (size_t)n); u.frame_mp = carve<int32_t>(p, (size_t)N);
+  u.bytes = (size_t)(p - base);
+  return u;
+}
+}  // namespace
+
+int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points) {
+  if (!t || max_points < 1) return DVM_ERR_INVALID;
+  // (the prologue is one workgroup per frame: beyond 1 << 20 points it would dominate the chain, so such a table is refused)
+  if (max_points > (1 << 20)) { set_error("dvm_tracker_reserve_local_map: more than 1 048 576 local map points"); return DVM_ERR_CAPACITY; }
+  DVM_HIP(hipSetDevice(t->device));
+  if (t->d_lm) { hipFree(t->d_lm); t->d_lm = nullptr; }
+  if (t->hm_lm) { hipHostFree(t->hm_lm); t->hm_lm = nullptr; }
+  t->lm_cap = 0; t->lf.ready = 0;
+  const size_t P = ((size_t)max_points + 63) & ~(size_t)63, K = (size_t)t->kp_cap;
+  t->lm_up_bytes = pad256(56) + 2 * pad256(256) + pad256(P * sizeof(LocalPointPod)) + pad256(K * 4);
+  // device: upload copy, per-entry arrays (seen, pos, claims), per-keypoint arrays (frame_mp, skip), pose seed, query arrays at any stride
+  // up to P, ranked lists, counters
+  const size_t dbytes = t->lm_up_bytes + pad256(P) + pad256(P * 12) + pad256(P) + pad256(K * 4) + pad256(K) + pad256(56) +
+                        pad256(P * 32) + 5 * pad256(P * 4) + pad256(P) + pad256(P * 4) + pad256(P * 16) + 2 * pad256(32);
+  const size_t mbytes = t->lm_up_bytes + pad256(K * 4) + pad256(K) + pad256(P * sizeof(TrackPoint)) + pad256(64) + pad256(56) + 3 * pad256(16);
+  if (hipMalloc(reinterpret_cast<void**>(&t->d_lm), dbytes) != hipSuccess) {
+    t->d_lm = nullptr; set_error("dvm_tracker_reserve_local_map: hipMalloc"); return DVM_ERR_CAPACITY;
+  }
+  if (hipHostMalloc(reinterpret_cast<void**>(&t->hm_lm), mbytes, hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer(reinterpret_cast<void**>(&t->hm_lm_dev), t->hm_lm, 0) != hipSuccess) {
+    if (t->hm_lm) hipHostFree(t->hm_lm);
+    t->hm_lm = nullptr; hipFree(t->d_lm); t->d_lm = nullptr;
+    set_error("dvm_tracker_reserve_local_map: mapped host memory"); return DVM_ERR_CAPACITY;
+  }
+  std::memset(t->hm_lm, 0, mbytes);
+  uint8_t* p = t->hm_lm + t->lm_up_bytes;
+  auto& r = t->lm;
+  r.mp = carve<int32_t>(p, K); r.outlier = carve<uint8_t>(p, K); r.tp = carve<TrackPoint>(p, P); r.res = carve<int32_t>(p, 16);
+  r.pose = carve<double>(p, 7); r.n_inl = carve<int32_t>(p, 4); r.fin = carve<int32_t>(p, 4); r.nedges = carve<int32_t>(p, 4);
+  t->lm_cap = (int)P;
+  return DVM_OK;
+}
+
+int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, int n, const int32_t* frame_mp, float th, int far_points,
+                        float th_far, int32_t* mp_out, uint8_t* outlier, dvm_track_point* track_pts, dvm_track_local_result* res) {
+  if (!t || !h || !mp_out || !outlier || !res || n < 0 || (n && !pts)) return DVM_ERR_INVALID;
+  LocalFrame& f = t->lf;
+  if (!f.ready || f.h != h || orb_result_serial(h) != f.serial) {
+    set_error("dvm_track_local_map: not right after a dvm_track_finish of one frame that returned DVM_TRACK_COMPLETE (same tracker and extractor)");
+    return DVM_ERR_STATE;
+  }
+  if (!t->d_lm) { set_error("dvm_track_local_map: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
+  if (n > t->lm_cap) { set_error("dvm_track_local_map: more local map points than reserved"); return DVM_ERR_CAPACITY; }
+  const int N = f.n;
+  if (N && !frame_mp) return DVM_ERR_INVALID;
+  for (int j = 0; j < N; j++)
+    if (frame_mp[j] < -1 || frame_mp[j] >= n) { set_error("dvm_track_local_map: frame_mp names a point outside the table"); return DVM_ERR_INVALID; }
+  std::memset(res, 0, sizeof(*res));
+  DVM_HIP(hipSetDevice(t->device));
+  hipStream_t s = (hipStream_t)dvm_orb_stream(h);
+  // 1. the table, the frame's points and the level tables: ONE asynchronous copy from the mapped staging block
+  const LocalUpload up = carve_upload(t->hm_lm, n, N);
+  std::memcpy(up.pose, t->m.pose_out, 56);          // the first half's pose (the device casts it to the float pose the frame stores)
+  std::vector<float> scale(256, 1.0f);
+  int rc = dvm_orb_tables(h, scale.data(), nullptr, nullptr, nullptr, nullptr);
+  if (rc != DVM_OK) return rc;
+  std::memcpy(up.scale, scale.data(), 64 * 4);
+  std::memcpy(up.inv_sigma2, f.inv_sigma2, 64 * 4);
+  if (n) std::memcpy(up.pts, pts, (size_t)n * sizeof(LocalPointPod));
+  if (N) std::memcpy(up.frame_mp, frame_mp, (size_t)N * 4);
+  DVM_HIP(hipMemcpyAsync(t->d_lm, t->hm_lm, up.bytes, hipMemcpyHostToDevice, s));
+  const LocalUpload dup = carve_upload(t->d_lm, n, N);
+  // 2. device arrays of this call: per entry at the table's stride, per keypoint at the frame slot's capacity
+  const int Qs = (std::max(n, 1) + 63) & ~63;
+  const size_t K = (size_t)t->kp_cap;
+  LocalQueries LQ;
+  uint8_t* p = t->d_lm + t->lm_up_bytes;
+  LQ.seen = carve<uint8_t>(p, Qs); LQ.pos = carve<float>(p, (size_t)Qs * 3); LQ.claims = carve<uint8_t>(p, Qs);
+  LQ.frame_mp = carve<int32_t>(p, K); LQ.skip = carve<uint8_t>(p, K); LQ.pose_in = carve<double>(p, 7);
+  LQ.qdesc = carve<uint8_t>(p, (size_t)Qs * 32); LQ.qx = carve<float>(p, Qs); LQ.qy = carve<float>(p, Qs); LQ.qr = carve<float>(p, Qs);
+  LQ.qmin = carve<int32_t>(p, Qs); LQ.qmax = carve<int32_t>(p, Qs); LQ.q_claims = carve<uint8_t>(p, Qs); LQ.q_tab = carve<int32_t>(p, Qs);
+  uint32_t* d_ranked = carve<uint32_t>(p, (size_t)Qs * 4);
+  int32_t* d_lres = carve<int32_t>(p, 8);
+  LQ.nq = carve<int32_t>(p, 8);
+  LocalMapArgs A;
+  A.fx = (float)f.cam.fx; A.fy = (float)f.cam.fy; A.cx = (float)f.cam.cx; A.cy = (float)f.cam.cy;
+  A.min_x = f.bounds[0]; A.max_x = f.bounds[1]; A.min_y = f.bounds[2]; A.max_y = f.bounds[3];
+  A.log_scale_factor = f.nlevels > 1 ? (float)std::log((double)scale[1]) : 0.0f;     // Frame::mfLogScaleFactor = log(mfScaleFactor)
+  A.th = th; A.th_far = th_far; A.n_levels = f.nlevels; A.far_points = far_points ? 1 : 0; A.n = n;
+  const TrackBatch TB{1, Qs, (int64_t)f.ocap, LQ.nq};
+  auto& r = t->lm;
+  // 3. SearchLocalPoints up to the queries
+  launch_track_local_prologue(s, dup.pts, dup.frame_mp, dup.pose, dup.scale, f.d_n, f.ocap, A, LQ, track_pts ? t->lmdev(r.tp) : nullptr, t->lmdev(r.res), TB);
+  // 4. the ranked window search on the frame's grid (slot 0, built by the finish), the keypoints with observed points skipped
+  const FrameView FV = frame_view_of(t->grid);
+  launch_match_window_ranked_batch(s, FV, 0, 1, LQ.skip, nullptr, 0, LQ.qdesc, LQ.qx, LQ.qy, LQ.qr, LQ.qmin, LQ.qmax, LQ.nq, Qs, d_ranked);
+  // 5. SearchByProjection(F, points)'s claim replay: mvpMapPoints after the search (device copy for the gather, mapped copy for the host)
+  TrackRequery rq{};
+  rq.F = FV;
+  rq.qdesc = LQ.qdesc; rq.qx = LQ.qx; rq.qy = LQ.qy; rq.qr = LQ.qr; rq.qmin = LQ.qmin; rq.qmax = LQ.qmax;
+  launch_track_claims_local(s, d_ranked, LQ, rq, f.d_un, f.d_n, f.ocap, 100 /* TH_HIGH */, 0.8f, t->d_assign, d_lres, t->lmdev(r.mp),
+                            t->lmdev(r.res) + 8, TB);
+  // 6. PoseOptimization's edges in keypoint order (positions from the table; no min_matches gate: below 3 edges the pose stays), the pose
+  //    seeded from the first half's float pose, the outlier flags and mnMatchesInliers
+  const TrackBatch TE{1, 0, (int64_t)f.ocap, nullptr};
+  launch_track_gather(s, t->d_assign, f.d_un, f.d_n, f.ocap, LQ.pos, dup.inv_sigma2, f.nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp,
+                      t->d_nedges, d_lres, 0, t->lmdev(r.nedges), TE);
+  ba_launch_pose_optimize(s, LQ.pose_in, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, f.ocap, 1, f.cam.fx, f.cam.fy, f.cam.cx, f.cam.cy,
+                          t->lmdev(r.pose), t->d_edge_out, t->lmdev(r.n_inl), t->d_chi);
+  launch_track_finish(s, t->d_assign, f.d_n, f.ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmdev(r.outlier), t->lmdev(r.fin),
+                      d_lres, TE);
+  f.ready = 0;                      // once per finish
+  rc = hip_check(hipGetLastError(), "local map chain launch");
+  if (rc != DVM_OK) return rc;
+  // 7. ONE synchronisation: everything the host reads was written to mapped memory by the kernels
+  DVM_HIP(hipStreamSynchronize(s));
+  if (N) { std::memcpy(mp_out, r.mp, (size_t)N * 4); std::memcpy(outlier, r.outlier, (size_t)N); }
+  if (track_pts && n) std::memcpy(track_pts, r.tp, (size_t)n * sizeof(dvm_track_point));
+  res->n_to_match = r.res[0]; res->n_cleared_bad = r.res[1]; res->nmatches = r.res[8]; res->n_requeried = r.res[11];
+  res->n_edges = r.nedges[0]; res->n_inliers = r.n_inl[0]; res->matches_inliers = r.fin[0];
+  std::memcpy(res->pose, r.pose, 56);
+  // Sophus::SE3f(SE3quat_recov.rotation().cast<float>(), SE3quat_recov.translation().cast<float>()) (Optimizer.cc:1023-1025)
+  for (int k = 0; k < 3; k++) res->Tcw.t[k] = (float)res->pose[k];
+  for (int k = 0; k < 4; k++) res->Tcw.q[k] = (float)res->pose[3 + k];
+  return DVM_OK;
 }
 
 }  // extern "C"

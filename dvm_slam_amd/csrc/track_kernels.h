@@ -16,6 +16,36 @@ struct TrackRequery {
 // a batch of frames through the same launches: frame b's per-query arrays at b * qstride elements (nq_arr[b] of them), its keypoints at
 // b * kps_stride; count = 1, nq_arr = nullptr: one frame (nq given directly)
 struct TrackBatch { int count; int qstride; int64_t kps_stride; const int32_t* nq_arr; };
+// ---- the second half (dvm_track_local_map): SearchLocalPoints -> SearchByProjection(F, points) -> PoseOptimization
+struct LocalPointPod {  // == dvm_local_point
+  float pos[3], normal[3], min_dist, max_dist;
+  uint8_t desc[32];
+  int32_t n_obs, bad;
+};
+struct LocalMapArgs {   // the call's constants: camera, bounds, level count, SearchByProjection's th / far-point filter, table size
+  float fx, fy, cx, cy, min_x, max_x, min_y, max_y, log_scale_factor, th, th_far;
+  int32_t n_levels, far_points, n;
+};
+// what k_track_local_prologue leaves for the search (device arrays; the query arrays at the call's stride)
+struct LocalQueries {
+  uint8_t* qdesc; float *qx, *qy, *qr; int32_t *qmin, *qmax; uint8_t* q_claims; int32_t* q_tab;   // [stride] in table order
+  int32_t* nq;                 // [1] queries
+  uint8_t* seen;               // [n] the frame holds the entry
+  int32_t* frame_mp;           // [kp_cap] the frame's points after the bad ones were cleared
+  uint8_t* skip;               // [kp_cap] keypoint holds a point with Observations() > 0
+  float* pos;                  // [n][3] GetWorldPos() of every entry (the edge gather's positions)
+  uint8_t* claims;             // [n] Observations() > 0 of every entry
+  double* pose_in;             // [7] the first half's float pose widened: PoseOptimization's seed
+};
+// pose_first: the first half's optimised pose (t, q doubles); scale: mvScaleFactors [64]; B: count = 1, qstride = the table's stride
+void launch_track_local_prologue(hipStream_t s, const LocalPointPod* pts, const int32_t* frame_mp_in, const double* pose_first, const float* scale,
+                                 const int32_t* d_n, int kp_cap, const LocalMapArgs& A, const LocalQueries& LQ, TrackPoint* track_pts_host,
+                                 int32_t* res_host, const TrackBatch& B);
+// the claim replay of SearchByProjection(F, points) (k_track_claims<true>): assign[j] = the table entry keypoint j holds at the end (the
+// matched query's entry, else frame_mp[j]); res[0] = nmatches, res[3] = queries searched again
+void launch_track_claims_local(hipStream_t s, const uint32_t* ranked, const LocalQueries& LQ, const TrackRequery& rq, const dvm_keypoint_pod* kps,
+                               const int32_t* d_n, int kp_cap, int th_high, float nnratio, int32_t* assign, int32_t* res, int32_t* assign_host,
+                               int32_t* res_host, const TrackBatch& B);
 void launch_track_claims(hipStream_t s, const uint32_t* ranked, const uint8_t* q_claims, const float* q_angle, int nq, const TrackRequery& rq,
                          const dvm_keypoint_pod* kps, const int32_t* d_n, int kp_cap, int th_high, int check_ori, int32_t* assign, int32_t* res,
                          int32_t* assign_host, int32_t* res_host, const TrackBatch& B);

@@ -7,10 +7,16 @@
 //   k_track_gather   Optimizer::PoseOptimization's edge list (src/Optimizer.cc:768-838): the matched keypoints in keypoint order
 //   k_track_finish   the outlier flags back in keypoint order, Tracking.cc:2636-2660 (outlier matches dropped, nmatchesMap)
 // The pose itself is k_pose_optimize (ba_kernels.hip), launched between the last two.
+// The second half, Tracking::TrackLocalMap (dvm_track_local_map), runs on the grid and mvKeysUn the first half left:
+//   k_track_local_prologue  SearchLocalPoints (Tracking.cc:3041-3106) up to the matcher's queries
+//   k_track_claims<true>    SearchByProjection(F, vpMapPoints)'s epilogue (ORBmatcher.cc:75-131)
+// followed by k_track_gather, k_pose_optimize and k_track_finish as in the first half.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "frustum_point.h"
 #include "match_kernels.h"
+#include "pose_f32.h"
 #include "track_kernels.h"
 
 namespace dvm {
@@ -34,11 +40,18 @@ constexpr int kHisto = 30;   // HISTO_LENGTH, ORBmatcher.cc:38
 // rotation check, res[3] = queries searched again.
 // blockIdx.x = frame of a batch (dvm_track_finish_batch: K agents' frames in one chain): frame b's per-query arrays lie at b * B.qstride
 // elements, its keypoints at b * B.kps_stride, its grid in slot b, its results at b * kp_cap / b * 8; a single frame is the batch of one.
+// kLocal: the same replay for SearchByProjection(F, vpMapPoints) of the second half (ORBmatcher.cc:75-131, dvm_track_local_map): no
+// rotation check; the ratio test (best > nnratio * second, both on one level) needs the best AND the second free candidate, so a lane
+// takes the first two free entries of its list, a query with fewer than two free among four whose list may go on has its window scanned
+// again (best two by (distance, scan position)), and a lane waits while an earlier lane of its round takes either of the two.  The
+// keypoints whose frame point has Observations() > 0 start taken (LQ.skip).  Per-query state stays in global memory (the next block's
+// lists are loaded while the current one is decided): the number of points in view is not bounded by LDS.  LDS: 10 B per keypoint.
+template <bool kLocal>
 __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict__ ranked, const uint8_t* __restrict__ q_claims,
                                                       const float* __restrict__ q_angle, int nq, TrackRequery RQ, const dvm_keypoint_pod* __restrict__ kps,
-                                                      const int32_t* __restrict__ d_n, int kp_cap, int th_high, int check_ori,
-                                                      int32_t* __restrict__ assign, int32_t* __restrict__ res, int32_t* __restrict__ assign_host,
-                                                      int32_t* __restrict__ res_host, TrackBatch B) {
+                                                      const int32_t* __restrict__ d_n, int kp_cap, int th_high, int check_ori, float nnratio,
+                                                      LocalQueries LQ, int32_t* __restrict__ assign, int32_t* __restrict__ res,
+                                                      int32_t* __restrict__ assign_host, int32_t* __restrict__ res_host, TrackBatch B) {
   extern __shared__ __attribute__((aligned(16))) uint8_t track_smem[];
   {
     const int b = blockIdx.x;
@@ -49,40 +62,65 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
     if (RQ.F.skp) RQ.F = RQ.F.slot(b);
     kps += (size_t)b * B.kps_stride; d_n += b;
     assign += (size_t)b * kp_cap; assign_host += (size_t)b * kp_cap; res += 8 * b; res_host += 8 * b;
+    if constexpr (kLocal) { LQ.q_tab += qo; LQ.frame_mp += (size_t)b * kp_cap; LQ.skip += (size_t)b * kp_cap; }
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int N = min(*d_n, kp_cap);
-  const int nq_pad = (nq + 63) & ~63;
+  const int nq_pad = kLocal ? 0 : (nq + 63) & ~63;
   uint4* s_keys = reinterpret_cast<uint4*>(track_smem);                    // [nq_pad] the ranked lists
   int32_t* s_assign = reinterpret_cast<int32_t*>(s_keys + nq_pad);         // [kp_cap]
   uint32_t* s_owner = reinterpret_cast<uint32_t*>(s_assign + kp_cap);      // [kp_cap]
   uint32_t* s_qres = s_owner + kp_cap;                                     // [nq_pad]: keypoint | bin << 16, or 0xFFFFFFFF
   uint8_t* s_claimed = reinterpret_cast<uint8_t*>(s_qres + nq_pad);        // [kp_cap]
   uint8_t* s_qcl = s_claimed + kp_cap;                                     // [nq_pad] the query takes its keypoint
+  int8_t* s_oct = reinterpret_cast<int8_t*>(s_claimed + kp_cap);           // kLocal: [kp_cap] octave of each keypoint
   __shared__ int s_rot[kHisto];
   __shared__ int s_ind[3];
   __shared__ int s_cnt[4];
   // ---- parallel prologue (four waves): everything the sequential part reads comes to LDS -- a global load inside a round would put its
   // latency on the chain of ~50 rounds per frame
-  for (int j = tid; j < kp_cap; j += 256) { s_assign[j] = -1; s_owner[j] = 0xFFFFFFFFu; s_claimed[j] = 0; }
-  for (int q = tid; q < nq_pad; q += 256) {
-    s_qres[q] = 0xFFFFFFFFu;
-    s_keys[q] = q < nq ? *reinterpret_cast<const uint4*>(ranked + 4 * (size_t)q) : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    s_qcl[q] = q < nq ? q_claims[q] : 0;
+  if constexpr (kLocal) {
+    for (int j = tid; j < kp_cap; j += 256) {
+      s_assign[j] = -1; s_owner[j] = 0xFFFFFFFFu;
+      s_claimed[j] = j < N ? LQ.skip[j] : 0;
+      s_oct[j] = j < N ? (int8_t)kps[j].octave : (int8_t)0;
+    }
+  } else {
+    for (int j = tid; j < kp_cap; j += 256) { s_assign[j] = -1; s_owner[j] = 0xFFFFFFFFu; s_claimed[j] = 0; }
+    for (int q = tid; q < nq_pad; q += 256) {
+      s_qres[q] = 0xFFFFFFFFu;
+      s_keys[q] = q < nq ? *reinterpret_cast<const uint4*>(ranked + 4 * (size_t)q) : make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+      s_qcl[q] = q < nq ? q_claims[q] : 0;
+    }
   }
   if (tid < kHisto) s_rot[tid] = 0;
   if (tid < 4) s_cnt[tid] = 0;
   __syncthreads();
   // ---- sequential part: wave 0 alone (the other waves wait at the barrier below; inside one wave LDS operations complete in order,
   // so the rounds need no barrier)
-  int exhausted_any = 0, n_requeried = 0, n_rounds = 0;
+  int exhausted_any = 0, n_requeried = 0, n_rounds = 0, n_matched = 0;
   if (wave == 0) {
+    const uint4 none4 = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    uint4 next4 = none4;
+    uint8_t next_cl = 0;
+    if constexpr (kLocal) {
+      if (lane < nq) { next4 = *reinterpret_cast<const uint4*>(ranked + 4 * (size_t)lane); next_cl = q_claims[lane]; }
+    }
     for (int q0 = 0; q0 < nq; q0 += 64) {
       const int q = q0 + lane;
       bool decided = q >= nq;
-      const uint4 k4 = s_keys[q];
+      uint4 k4;
+      bool claims;
+      if constexpr (kLocal) {
+        k4 = next4; claims = !decided && next_cl != 0;
+        const int qn = q + 64;        // the next block's lists, in flight while this block is decided
+        next4 = none4; next_cl = 0;
+        if (qn < nq) { next4 = *reinterpret_cast<const uint4*>(ranked + 4 * (size_t)qn); next_cl = q_claims[qn]; }
+      } else {
+        k4 = s_keys[q];
+        claims = !decided && s_qcl[q] != 0;
+      }
       const uint32_t key0 = k4.x, key1 = k4.y, key2 = k4.z, key3 = k4.w;   // (selected by compares: an indexed array would live in scratch)
-      const bool claims = !decided && s_qcl[q] != 0;
       // list entries: distance >= 256 ends the list; an index >= N cannot occur (the grid holds N keypoints), guarded all the same
       const int i0 = (int)(key0 & 0xFFFFu), i1 = (int)(key1 & 0xFFFFu), i2 = (int)(key2 & 0xFFFFu), i3 = (int)(key3 & 0xFFFFu);
       const bool v0 = (key0 >> 16) < 256u && i0 < N, v1 = v0 && (key1 >> 16) < 256u && i1 < N, v2 = v1 && (key2 >> 16) < 256u && i2 < N,
@@ -92,14 +130,24 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
         // first candidate of the list no earlier query has taken (the four flags are read side by side: one LDS latency per round)
         const bool f0 = v0 && !s_claimed[v0 ? i0 : 0], f1 = v1 && !s_claimed[v1 ? i1 : 0], f2 = v2 && !s_claimed[v2 ? i2 : 0],
                    f3 = v3 && !s_claimed[v3 ? i3 : 0];
-        int prop = -1, pdist = 256;
+        int prop = -1, pdist = 256, sec = -1, sdist = 256;
         if (!decided) {
-          if (f0) { prop = i0; pdist = (int)(key0 >> 16); }
-          else if (f1) { prop = i1; pdist = (int)(key1 >> 16); }
-          else if (f2) { prop = i2; pdist = (int)(key2 >> 16); }
-          else if (f3) { prop = i3; pdist = (int)(key3 >> 16); }
+          if constexpr (kLocal) {     // the first two free entries: best and second of what is left
+            auto put = [&](bool f, int i, uint32_t key) {
+              if (!f) return;
+              if (prop < 0) { prop = i; pdist = (int)(key >> 16); }
+              else if (sec < 0) { sec = i; sdist = (int)(key >> 16); }
+            };
+            put(f0, i0, key0); put(f1, i1, key1); put(f2, i2, key2); put(f3, i3, key3);
+          } else {
+            if (f0) { prop = i0; pdist = (int)(key0 >> 16); }
+            else if (f1) { prop = i1; pdist = (int)(key1 >> 16); }
+            else if (f2) { prop = i2; pdist = (int)(key2 >> 16); }
+            else if (f3) { prop = i3; pdist = (int)(key3 >> 16); }
+          }
         }
-        bool exhausted = !decided && v3 && prop < 0;     // all four taken, the list may go on
+        // all four taken (kLocal: fewer than two free), the list may go on
+        bool exhausted = !decided && v3 && (kLocal ? sec < 0 : prop < 0);
         // A query whose four ranked candidates are all taken waits until every query in front of it is final -- it blocks the lanes behind
         // it meanwhile --, then the whole wave scans its window again, skipping what is taken by now: the reference's loop of
         // ORBmatcher.cc:1613-1650 at that query's turn (smallest (distance, scan position) among the free ones)
@@ -111,7 +159,7 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
           const float x = RQ.qx[qf], y = RQ.qy[qf], r = RQ.qr[qf];
           const int minLevel = RQ.qmin[qf], maxLevel = RQ.qmax[qf];
           const FrameView& F = RQ.F;
-          uint32_t best = (256u << 16) | 0xFFFFu;
+          uint32_t best = (256u << 16) | 0xFFFFu, best2 = best;
           const int nMinCellX = max(0, (int)floorf((x - F.minX - r) * F.wInv));
           const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - F.minX + r) * F.wInv));
           const int nMinCellY = max(0, (int)floorf((y - F.minY - r) * F.hInv));
@@ -141,19 +189,44 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
               if (idx >= N || s_claimed[idx]) continue;
               const int d = __popc(a.x ^ w[0]) + __popc(a.y ^ w[1]) + __popc(a.z ^ w[2]) + __popc(a.w ^ w[3]) +
                             __popc(b.x ^ w[4]) + __popc(b.y ^ w[5]) + __popc(b.z ^ w[6]) + __popc(b.w ^ w[7]);
-              best = min(best, ((uint32_t)d << 16) | ((uint32_t)p & 0xFFFFu));
+              const uint32_t key = ((uint32_t)d << 16) | ((uint32_t)p & 0xFFFFu);
+              if constexpr (kLocal) {
+                if (key < best) { best2 = best; best = key; }
+                else if (key < best2) best2 = key;
+              } else {
+                best = min(best, key);
+              }
             }
           }
+          if constexpr (kLocal) {     // the best two of two ascending pairs (disjoint): min(a1, b1), min(max(a1, b1), min(a2, b2))
 #pragma unroll
-          for (int o = 32; o >= 1; o >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, o));
+            for (int o = 32; o >= 1; o >>= 1) {
+              const uint32_t ob = (uint32_t)__shfl_xor((int)best, o), ob2 = (uint32_t)__shfl_xor((int)best2, o);
+              best2 = min(max(best, ob), min(best2, ob2));
+              best = min(best, ob);
+            }
+          } else {
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, o));
+          }
           const int bd = (int)(best >> 16);
           const int bidx = bd < 256 ? F.sidx[best & 0xFFFFu] : -1;
           if (lane == first_und) { exhausted = false; pdist = bd; prop = bidx; n_requeried++; }
+          if constexpr (kLocal) {
+            const int bd2 = (int)(best2 >> 16);
+            const int bidx2 = bd2 < 256 ? F.sidx[best2 & 0xFFFFu] : -1;
+            if (lane == first_und) { sdist = bd2; sec = bidx2; }
+          }
         }
-        const bool matched = prop >= 0 && pdist <= th_high;
+        bool matched = prop >= 0 && pdist <= th_high;
+        if constexpr (kLocal) {       // ORBmatcher.cc:100-104: the ratio test only when best and second lie on one level
+          const int plev = prop >= 0 ? (int)s_oct[prop] : -1, slev = sec >= 0 ? (int)s_oct[sec] : -1;
+          matched = matched && !(plev == slev && (float)pdist > nnratio * (float)sdist);
+        }
         const bool takes = matched && claims;
         if (!decided && takes) atomicMin(&s_owner[prop], (uint32_t)lane);
-        const bool blocked = !decided && ((prop >= 0 && s_owner[prop] < (uint32_t)lane) || (exhausted && RQ.F.skp != nullptr));
+        bool blocked = !decided && ((prop >= 0 && s_owner[prop] < (uint32_t)lane) || (exhausted && RQ.F.skp != nullptr));
+        if constexpr (kLocal) blocked = blocked || (!decided && sec >= 0 && s_owner[sec] < (uint32_t)lane);
         const unsigned long long bm = __ballot(blocked);
         const int first_blocked = bm ? (int)__builtin_ctzll(bm) : 64;
         if (!decided && takes) s_owner[prop] = 0xFFFFFFFFu;
@@ -163,7 +236,8 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
           if (matched) {
             atomicMax(&s_assign[prop], q);              // the last writer in query order stays (:1651: CurrentFrame.mvpMapPoints[bestIdx2] = pMP)
             if (takes) s_claimed[prop] = 1;
-            s_qres[q] = (uint32_t)prop;
+            if constexpr (kLocal) n_matched++;
+            else s_qres[q] = (uint32_t)prop;
           }
         }
       }
@@ -172,9 +246,27 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
     int nrq = n_requeried;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) nrq += __shfl_xor(nrq, o);
-    if (lane == 0) { s_cnt[0] = any_exhausted; s_cnt[1] = nrq; s_cnt[2] = n_rounds; }
+    if constexpr (kLocal) {
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) n_matched += __shfl_xor(n_matched, o);
+    }
+    if (lane == 0) { s_cnt[0] = any_exhausted; s_cnt[1] = nrq; s_cnt[2] = n_rounds; s_cnt[3] = n_matched; }
   }
   __syncthreads();
+  if constexpr (kLocal) {
+    // mvpMapPoints after the search: the last matching query's table entry, else what the frame held (bad points cleared)
+    for (int j = tid; j < kp_cap; j += 256) {
+      int a = -1;
+      if (j < N) { const int qa = s_assign[j]; a = qa >= 0 ? LQ.q_tab[qa] : LQ.frame_mp[j]; }
+      assign[j] = a;
+      if (j < N) assign_host[j] = a;
+    }
+    if (tid == 0) {
+      res[0] = s_cnt[3]; res[1] = s_cnt[0]; res[2] = s_cnt[3]; res[3] = s_cnt[1];
+      res_host[0] = s_cnt[3]; res_host[1] = s_cnt[0]; res_host[2] = s_cnt[3]; res_host[3] = s_cnt[1]; res_host[4] = s_cnt[2];
+    }
+    return;
+  }
   // ---- parallel epilogue.  Rotation histogram of the matches (:1652-1663): counts only, so the order of the additions is free
   if (check_ori) {
     for (int q = tid; q < nq; q += 256) {
@@ -307,15 +399,135 @@ __global__ void __launch_bounds__(256) k_track_finish(int32_t* __restrict__ assi
   if (tid == 0) { out[0] = s_cnt[0]; out[1] = res[0] - s_cnt[1]; }
 }
 
+// SearchLocalPoints (Tracking.cc:3041-3106) up to the queries of SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints)
+// (ORBmatcher.cc:50-73).  One workgroup per frame, in the reference's order:
+//   the frame's points: a bad one is cleared (counted), the others mark their table entry seen (mnLastFrameSeen) -- skipped below and
+//     not counted in nToMatch; a keypoint whose point has Observations() > 0 is skipped by the search (LQ.skip)
+//   Frame::UpdatePoseMatrices of the first half's float pose (Optimizer.cc:1023-1025: the double pose cast to float), pose_f32.h
+//   isInFrustum(pMP, 0.5) of every entry (frustum_point.h); mbTrackInView false for seen and bad entries; nToMatch
+//   the far-point filter (:52-53), radius RadiusByViewingCos(viewCos) * (th != 1 ? th : 1) * mvScaleFactors[level], levels
+//     [level - 1, level]; the in-view points compacted into the query arrays IN TABLE ORDER (the claim replay's order)
+// tables: scale[64] = mvScaleFactors.  res_host[0] = nToMatch, res_host[1] = frame points cleared as bad.
+__global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointPod* __restrict__ pts, const int32_t* __restrict__ frame_mp_in,
+                                                               const double* __restrict__ pose_first, const float* __restrict__ scale,
+                                                               const int32_t* __restrict__ d_n, int kp_cap, LocalMapArgs A, LocalQueries LQ,
+                                                               TrackPoint* __restrict__ tp_host, int32_t* __restrict__ res_host, TrackBatch B) {
+  __shared__ int s_wave[16];
+  __shared__ int s_cnt[2];
+  __shared__ float s_scale[64];
+  {
+    const int b = blockIdx.x;
+    const size_t qo = (size_t)b * B.qstride, ko = (size_t)b * kp_cap;
+    pts += qo; frame_mp_in += ko; pose_first += 7 * b; d_n += b; res_host += 8 * b;
+    if (tp_host) tp_host += qo;
+    LQ.qdesc += qo * 32; LQ.qx += qo; LQ.qy += qo; LQ.qr += qo; LQ.qmin += qo; LQ.qmax += qo; LQ.q_claims += qo; LQ.q_tab += qo; LQ.nq += b;
+    LQ.seen += qo; LQ.frame_mp += ko; LQ.skip += ko; LQ.pos += qo * 3; LQ.claims += qo; LQ.pose_in += 7 * b;
+  }
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int N = min(*d_n, kp_cap), n = A.n;
+  if (tid < 2) s_cnt[tid] = 0;
+  if (tid < 64) s_scale[tid] = tid < A.n_levels ? scale[tid] : 1.0f;
+  for (int i = tid; i < n; i += 1024) LQ.seen[i] = 0;
+  __syncthreads();
+  int cleared = 0;
+  for (int j = tid; j < kp_cap; j += 1024) {
+    int fm = j < N ? frame_mp_in[j] : -1;      // (the host checked fm < n)
+    uint8_t sk = 0;
+    if (fm >= 0) {
+      if (pts[fm].bad) { fm = -1; cleared++; }
+      else { LQ.seen[fm] = 1; sk = pts[fm].n_obs > 0 ? 1 : 0; }
+    }
+    LQ.frame_mp[j] = fm;
+    LQ.skip[j] = sk;
+  }
+  if (cleared) atomicAdd(&s_cnt[0], cleared);
+  // Frame::UpdatePoseMatrices: mRcw = R(q), mtcw = t, mOw = Tcw.inverse().translation() (each thread the same float operations)
+  float q[4], t[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) t[k] = (float)pose_first[k];
+#pragma unroll
+  for (int k = 0; k < 4; k++) q[k] = (float)pose_first[3 + k];
+  FrustumFrame F;
+  dvm_pose::quat_matrix(q, F.Rcw);
+  F.tcw[0] = t[0]; F.tcw[1] = t[1]; F.tcw[2] = t[2];
+  {
+    float qi[4];
+    dvm_pose::se3_inverse(q, t, qi, F.Ow);
+  }
+  F.fx = A.fx; F.fy = A.fy; F.cx = A.cx; F.cy = A.cy; F.min_x = A.min_x; F.max_x = A.max_x; F.min_y = A.min_y; F.max_y = A.max_y;
+  F.bf = 0.0f; F.log_scale_factor = A.log_scale_factor; F.n_levels = A.n_levels;
+  if (tid < 7) LQ.pose_in[tid] = (double)(float)pose_first[tid];   // g2o::SE3Quat of the SE3f (Optimizer.cc:759-760)
+  __syncthreads();
+  int base = 0, n_view = 0;
+  for (int c = 0; c < n; c += 1024) {
+    const int i = c + tid;
+    bool query = false;
+    TrackPoint o{};
+    if (i < n) {
+      const LocalPointPod& P = pts[i];
+      o = frustum_point(F, P.pos[0], P.pos[1], P.pos[2], P.normal[0], P.normal[1], P.normal[2], P.min_dist, P.max_dist, 0.5f);
+      if (LQ.seen[i] || P.bad) o.in_view = 0;
+      n_view += o.in_view;
+      if (tp_host) tp_host[i] = o;
+      LQ.pos[3 * (size_t)i] = P.pos[0]; LQ.pos[3 * (size_t)i + 1] = P.pos[1]; LQ.pos[3 * (size_t)i + 2] = P.pos[2];
+      LQ.claims[i] = P.n_obs > 0 ? 1 : 0;
+      query = o.in_view && !(A.far_points && o.depth > A.th_far);
+    }
+    const unsigned long long m = __ballot(query);
+    if (lane == 0) s_wave[wv] = __popcll(m);
+    __syncthreads();
+    int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    int total = 0;
+#pragma unroll
+    for (int w = 0; w < 16; w++) {
+      const int cw = s_wave[w];
+      if (w < wv) pos += cw;
+      total += cw;
+    }
+    if (query) {
+      const LocalPointPod& P = pts[i];
+      float r = o.view_cos > 0.998 ? 2.5f : 4.0f;            // RadiusByViewingCos (ORBmatcher.cc:207-212)
+      if (A.th != 1.0f) r *= A.th;
+      LQ.qx[pos] = o.proj_x; LQ.qy[pos] = o.proj_y; LQ.qr[pos] = r * s_scale[min(max(o.level, 0), 63)];
+      LQ.qmin[pos] = o.level - 1; LQ.qmax[pos] = o.level;
+      LQ.q_claims[pos] = P.n_obs > 0 ? 1 : 0; LQ.q_tab[pos] = i;
+      const uint2* sd = reinterpret_cast<const uint2*>(P.desc);
+      uint2* dd = reinterpret_cast<uint2*>(LQ.qdesc + (size_t)pos * 32);
+#pragma unroll
+      for (int k = 0; k < 4; k++) dd[k] = sd[k];
+    }
+    base += total;
+    __syncthreads();
+  }
+  for (int off = 32; off >= 1; off >>= 1) n_view += __shfl_xor(n_view, off);
+  if (lane == 0 && n_view) atomicAdd(&s_cnt[1], n_view);
+  __syncthreads();
+  if (tid == 0) { LQ.nq[0] = base; res_host[0] = s_cnt[1]; res_host[1] = s_cnt[0]; }
+}
+
 size_t track_claims_lds(int kp_cap, int nq) { const size_t qp = ((size_t)nq + 63) & ~(size_t)63; return qp * 16 + (size_t)kp_cap * 9 + qp * 5 + 16; }
 
 void launch_track_claims(hipStream_t s, const uint32_t* ranked, const uint8_t* q_claims, const float* q_angle, int nq, const TrackRequery& rq,
                          const dvm_keypoint_pod* kps, const int32_t* d_n, int kp_cap, int th_high, int check_ori, int32_t* assign, int32_t* res,
                          int32_t* assign_host, int32_t* res_host, const TrackBatch& B) {
   const size_t lds = track_claims_lds(kp_cap, B.count > 1 || B.nq_arr ? B.qstride : nq);
-  if (lds > 48 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_track_claims), (int)lds);
-  hipLaunchKernelGGL(k_track_claims, dim3(B.count), dim3(256), lds, s, ranked, q_claims, q_angle, nq, rq, kps, d_n, kp_cap, th_high,
-                     check_ori, assign, res, assign_host, res_host, B);
+  if (lds > 48 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_track_claims<false>), (int)lds);
+  hipLaunchKernelGGL(k_track_claims<false>, dim3(B.count), dim3(256), lds, s, ranked, q_claims, q_angle, nq, rq, kps, d_n, kp_cap, th_high,
+                     check_ori, 0.0f, LocalQueries{}, assign, res, assign_host, res_host, B);
+}
+void launch_track_claims_local(hipStream_t s, const uint32_t* ranked, const LocalQueries& LQ, const TrackRequery& rq, const dvm_keypoint_pod* kps,
+                               const int32_t* d_n, int kp_cap, int th_high, float nnratio, int32_t* assign, int32_t* res, int32_t* assign_host,
+                               int32_t* res_host, const TrackBatch& B) {
+  const size_t lds = (size_t)kp_cap * 10 + 16;
+  if (lds > 48 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_track_claims<true>), (int)lds);
+  hipLaunchKernelGGL(k_track_claims<true>, dim3(B.count), dim3(256), lds, s, ranked, LQ.q_claims, nullptr, 0, rq, kps, d_n, kp_cap, th_high, 0,
+                     nnratio, LQ, assign, res, assign_host, res_host, B);
+}
+void launch_track_local_prologue(hipStream_t s, const LocalPointPod* pts, const int32_t* frame_mp_in, const double* pose_first, const float* scale,
+                                 const int32_t* d_n, int kp_cap, const LocalMapArgs& A, const LocalQueries& LQ, TrackPoint* track_pts_host,
+                                 int32_t* res_host, const TrackBatch& B) {
+  hipLaunchKernelGGL(k_track_local_prologue, dim3(B.count), dim3(1024), 0, s, pts, frame_mp_in, pose_first, scale, d_n, kp_cap, A, LQ, track_pts_host,
+                     res_host, B);
 }
 void launch_track_gather(hipStream_t s, const int32_t* assign, const dvm_keypoint_pod* kps_un, const int32_t* d_n, int kp_cap, const float* q_pos,
                          const float* inv_sigma2, int nlevels, double* Xw, double* obs, double* info, int32_t* edge_kp, int32_t* n_edges,

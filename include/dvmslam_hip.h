@@ -631,6 +631,48 @@ int dvm_track_finish(dvm_tracker* t, dvm_orb* h, const dvm_track_queries* q, dvm
  * DVM_TRACK_FEW_MATCHES; the call may be repeated (all frames, the wider queries for those) after one begin. */
 int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* qs, const dvm_track_frame_out* outs, dvm_track_result* res);
 
+/* ---- The second half of the tracked frame, Tracking::TrackLocalMap (src/Tracking.cc:2668-2740), as ONE device chain behind the first:
+ * SearchLocalPoints (:3041-3106: the frame's bad points cleared, Frame::isInFrustum(pMP, 0.5) over the local map, the points the frame
+ * holds skipped) -> ORBmatcher::SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) (src/ORBmatcher.cc:44-205, mono: ratio
+ * 0.8 when best and second share a level, TH_HIGH, no rotation check) -> Optimizer::PoseOptimization (src/Optimizer.cc:744-1028) seeded
+ * from the first half's float pose -> mnMatchesInliers (mbOnlyTracking = false).  It runs on the frame's grid and mvKeysUn the first half
+ * left on the device (no re-upload of the frame); the table goes up in one asynchronous copy; one synchronisation at the end.
+ * UpdateLocalMap (which points form the table) stays with the caller.  Results equal dvm_is_in_frustum + dvmh_search_by_projection_points
+ * + dvm_pose_optimize composed in that order, bit for bit. */
+typedef struct {
+  float pos[3];                    /* GetWorldPos() */
+  float normal[3];                 /* GetNormal() */
+  float min_dist, max_dist;        /* mfMinDistance, mfMaxDistance as dvm_is_in_frustum takes them (GetMin/MaxDistanceInvariance() are
+                                      0.8 / 1.2 times these; PredictScale needs mfMaxDistance itself) */
+  uint8_t desc[32];                /* GetDescriptor() */
+  int32_t n_obs;                   /* Observations() */
+  int32_t bad;                     /* isBad() */
+} dvm_local_point;                 /* 72 bytes, one record per mvpLocalMapPoints entry */
+typedef struct {
+  int32_t n_to_match;              /* nToMatch of SearchLocalPoints (Tracking.cc:3073): in view, not bad, not held by the frame */
+  int32_t nmatches;                /* SearchByProjection's return value: every match event */
+  int32_t n_requeried;             /* queries whose window the device searched again (fewer than two of four ranked candidates free) */
+  int32_t n_cleared_bad;           /* frame points found bad and cleared (Tracking.cc:3047-3049) */
+  int32_t n_edges;                 /* PoseOptimization's nInitialCorrespondences */
+  int32_t n_inliers;               /* PoseOptimization's return value (0 below 3 edges: the pose is left as it was) */
+  int32_t matches_inliers;         /* mnMatchesInliers (mbOnlyTracking = false) */
+  int32_t reserved;
+  double pose[7];                  /* the optimised Tcw (tx ty tz qx qy qz qw) */
+  dvm_se3f Tcw;                    /* the same as the frame stores it (Optimizer.cc:1023-1025) */
+  int32_t reserved2;
+} dvm_track_local_result;          /* 120 bytes */
+/* Allocates the second half's working set for tables of up to max_points entries (at least 16 384 supported; no growth in the hot path).
+ * DVM_ERR_CAPACITY for what it cannot hold.  Called again, it replaces the working set; dvm_tracker_destroy frees it. */
+int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points);
+/* Right after a dvm_track_finish of ONE frame that returned DVM_TRACK_COMPLETE, on the same tracker and extractor, before the next begin
+ * (otherwise DVM_ERR_STATE); once per finish.  pts [n]: the local map (n <= the reservation, else DVM_ERR_CAPACITY); frame_mp [N] (N = the
+ * frame's keypoint count): the index into pts of the map point keypoint j holds after the first half, or -1 (every point the frame holds
+ * is in the table).  Outputs: mp_out [N] mvpMapPoints after the search (before any outlier drop: monocular TrackLocalMap keeps them);
+ * outlier [N] mvbOutlier of the second PoseOptimization (0 where no map point); track_pts (may be NULL) [n]: Frame::isInFrustum's mTrack*
+ * fields per entry, in_view = mbTrackInView after SearchLocalPoints (0 for bad entries and those the frame holds). */
+int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, int n, const int32_t* frame_mp, float th, int far_points,
+                        float th_far, int32_t* mp_out, uint8_t* outlier, dvm_track_point* track_pts /* may be NULL */, dvm_track_local_result* res);
+
 /* Optimizer::OptimizeSim3 (Optimizer.cc:1960-2212), numerics for N correspondences gathered by the caller:
  * P1c / P2c = the matched map points in their own key frame's camera frame (R1w*P+t1w, R2w*P+t2w), obs1 / obs2 =
  * undistorted keypoints in KF1 / KF2, w1 / w2 = mvInvLevelSigma2[octave], K1 / K2 = (fx,fy,cx,cy) of both pinhole
