@@ -1073,6 +1073,59 @@ class TrackerBatch:
             out.append(d)
         return out
 
+    def reserve_local_map(self, total):
+        """dvm_tracker_reserve_local_map: the batched second half's working set for `total` table entries per call (the sum over the
+        frames of each table's size rounded up to 64), per-keypoint arrays for max_frames frames."""
+        f = self.L.dvm_tracker_reserve_local_map
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32]
+        check(f(self.t, int(total)))
+
+    def track_local_map(self, tables, frame_mps, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
+        """dvm_track_local_map_batch: Tracking::TrackLocalMap of every frame the last track() call tracked, as ONE device chain.  tables [count]:
+        LOCAL_POINT_DTYPE arrays; frame_mps [count]: per keypoint the index into that frame's table, or -1; th / far_points / th_far: one value
+        for all frames or one per frame.  Returns one dict per frame: status (DVM_TRACK_COMPLETE = 0, else the first half's status and the
+        frame was skipped: zero counters, no arrays) and, for completed frames, what Tracker.track_local_map returns."""
+        count = len(tables)
+        per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * count
+        ths, fars, thfs = per(th), per(far_points), per(th_far)
+        assert len(frame_mps) == count and len(ths) == count and len(fars) == count and len(thfs) == count
+        ins = (LocalMapIn * count)(); outs = (LocalMapOut * count)(); res = (TrackLocalResult * count)(); status = np.zeros(count, np.int32)
+        keep = []
+        for b in range(count):
+            pts = np.ascontiguousarray(tables[b], LOCAL_POINT_DTYPE); fm = np.ascontiguousarray(frame_mps[b], np.int32)
+            mp = np.full(max(len(fm), 1), -1, np.int32); outl = np.zeros(max(len(fm), 1), np.uint8)
+            tp = np.zeros(max(len(pts), 1), TRACK_DTYPE) if want_track_points else None
+            keep.append((pts, fm, mp, outl, tp))
+            ins[b].pts, ins[b].n, ins[b].frame_mp = (pts.ctypes.data if len(pts) else None), len(pts), fm.ctypes.data
+            ins[b].th, ins[b].far_points, ins[b].th_far = float(ths[b]), int(bool(fars[b])), float(thfs[b])
+            outs[b].mp_out, outs[b].outlier, outs[b].track_pts = mp.ctypes.data, outl.ctypes.data, None if tp is None else tp.ctypes.data
+        f = self.L.dvm_track_local_map_batch
+        f.restype = C.c_int32
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(f(self.t, self.ext.h, count, ins, outs, res, _p(status)))
+        out = []
+        for b in range(count):
+            r = res[b]
+            d = {k: getattr(r, k) for k in ("n_to_match", "nmatches", "n_requeried", "n_cleared_bad", "n_edges", "n_inliers", "matches_inliers")}
+            d["status"] = int(status[b])
+            if status[b] == 0:
+                pts, fm, mp, outl, tp = keep[b]
+                d.update(mp=mp[:len(fm)], outlier=outl[:len(fm)], pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
+                if want_track_points:
+                    d["track_pts"] = tp[:len(pts)]
+            out.append(d)
+        return out
+
+
+class LocalMapIn(C.Structure):
+    """dvm_local_map_in (include/dvmslam_hip.h)"""
+    _fields_ = [("pts", C.c_void_p), ("n", C.c_int32), ("frame_mp", C.c_void_p), ("th", C.c_float), ("far_points", C.c_int32), ("th_far", C.c_float)]
+
+
+class LocalMapOut(C.Structure):
+    """dvm_local_map_out (include/dvmslam_hip.h)"""
+    _fields_ = [("mp_out", C.c_void_p), ("outlier", C.c_void_p), ("track_pts", C.c_void_p)]
+
 
 TRACKED_POINT_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
                                 ("in_view", "u1"), ("bad", "u1"), ("pad", "u1", (2,)), ("desc", "u1", (32,)), ("n_obs", "<i4")])

@@ -14,6 +14,8 @@
 // Tracking.cc:2616-2624: call dvm_track_finish again with the wider queries -- no new extraction), and a query whose four ranked
 // candidates were all taken by earlier queries (the list may go on: the caller replays the epilogue from the ranked lists on the host).
 #include <algorithm>
+#include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -30,19 +32,22 @@
 
 using namespace dvm;
 
-// what the second half (dvm_track_local_map) runs on: set by a dvm_track_finish of one frame that returned DVM_TRACK_COMPLETE, cleared by
-// any begin / finish and by the second half itself
+// what the second half runs on: set by a dvm_track_finish[_batch] that returned DVM_OK, cleared by any begin / finish and by the second
+// half itself.  ready: one frame that returned DVM_TRACK_COMPLETE (dvm_track_local_map); batch_ready: any finish (dvm_track_local_map_batch)
 struct LocalFrame {
-  int ready = 0;
+  int ready = 0, batch_ready = 0;
   dvm_orb* h = nullptr; uint64_t serial = 0;     // the extractor and which of its extractions the frame is
   int n = 0, ocap = 0, nlevels = 0;
   const dvm_keypoint_pod* d_un = nullptr; const int32_t* d_n = nullptr;   // mvKeysUn on the device, the keypoint count
   float bounds[4] = {0, 0, 0, 0}, inv_sigma2[64] = {};
   dvm_ba_camera cam{};
+  int count = 0; int64_t kps_stride = 0;          // the finish's frames: frame b's mvKeysUn at b * kps_stride, its count at d_n[b]
+  std::vector<int32_t> ns, status;                // per frame: keypoints, the first half's status
 };
 
 struct dvm_tracker {
   int device = 0, kp_cap = 0, q_cap = 0, max_frames = 1;
+  int q_rcap = 0;                  // q_cap rounded up to 64: the per-frame query capacity of d_q / d_ranked
   dvm_frame* grid = nullptr;       // max_frames slots
   uint8_t* d_buf = nullptr;        // device working set (one allocation)
   uint8_t *hm = nullptr, *hm_dev = nullptr;   // mapped page-locked buffer: queries in (staging of the one copy), results out
@@ -66,11 +71,11 @@ struct dvm_tracker {
   int begun = 0;                   // frames of the batch whose extraction is queued
   int rows = 0, cols = 0;
   // ---- the second half (dvm_track_local_map): working set of dvm_tracker_reserve_local_map, and what the last finish left for it
-  int lm_cap = 0;                  // table entries reserved (a multiple of 64)
+  int lm_cap = 0;                  // table entries reserved (a multiple of 64; a batch: all frames' tables, each rounded up to 64)
   uint8_t* d_lm = nullptr;         // device: [upload][per-entry arrays][query arrays][ranked lists][counters]
   uint8_t *hm_lm = nullptr, *hm_lm_dev = nullptr;   // mapped: [upload staging][results]
   size_t lm_up_bytes = 0;          // the upload region's capacity (device copy at the start of d_lm)
-  struct LocalMapped { int32_t* mp; uint8_t* outlier; TrackPoint* tp; int32_t* res; double* pose; int32_t *n_inl, *fin, *nedges; } lm;
+  struct LocalMapped { int32_t* mp; uint8_t* outlier; TrackPoint* tp; int32_t* res; double* pose; int32_t *n_inl, *fin, *nedges; } lm;   // [max_frames]
   LocalFrame lf;
   template <class T> T* lmdev(T* host_ptr) const { return reinterpret_cast<T*>(hm_lm_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm_lm)); }
 };
@@ -97,10 +102,11 @@ int dvm_tracker_create_batch(int device, int max_frames, int max_keypoints, int 
   DVM_HIP(hipSetDevice(device));
   dvm_tracker* t = new (std::nothrow) dvm_tracker();
   if (!t) return DVM_ERR_INVALID;
-  t->device = device; t->kp_cap = max_keypoints; t->q_cap = max_queries; t->max_frames = max_frames;
+  t->device = device; t->kp_cap = max_keypoints; t->q_cap = max_queries; t->max_frames = max_frames; t->q_rcap = (max_queries + 63) & ~63;
   int rc = dvm_frame_create(device, max_keypoints, max_frames, &t->grid);
   if (rc != DVM_OK) { delete t; return rc; }
-  const size_t K = (size_t)max_keypoints, Q = (size_t)max_queries, B = (size_t)max_frames;
+  // (Q rounded up to 64: dvm_track_finish_batch strides the per-query arrays by the call's largest nq rounded up to 64)
+  const size_t K = (size_t)max_keypoints, Q = ((size_t)max_queries + 63) & ~(size_t)63, B = (size_t)max_frames;
   // device working set
   size_t dbytes = pad256(B * Q * 16) + pad256(B * K * 4) + pad256(B * 32) + pad256(B * K * 24) + pad256(B * K * 16) + 2 * pad256(B * K * 8) + pad256(B * K * 4) +
                   pad256(B * 4) + pad256(B * K) + pad256(B * K * sizeof(dvm_keypoint_pod));
@@ -154,7 +160,7 @@ void dvm_tracker_destroy(dvm_tracker* t) {
 int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_batch: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0; t->lf.ready = 0;
+  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0;
   const int rc = dvm_orb_extract_batch_host(h, imgs, count, rows, cols, stride, frame_stride, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
@@ -163,7 +169,7 @@ int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int c
 int dvm_track_begin_staged(dvm_tracker* t, dvm_orb* h, int count, int rows, int cols, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_staged: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0; t->lf.ready = 0;
+  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0;
   const int rc = dvm_orb_extract_staged(h, count, rows, cols, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
@@ -175,7 +181,7 @@ int dvm_track_begin(dvm_tracker* t, dvm_orb* h, const uint8_t* img, int rows, in
 
 int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* qs, const dvm_track_frame_out* outs, dvm_track_result* res) {
   if (!t || !h || !qs || !outs || !res || count < 1) return DVM_ERR_INVALID;
-  t->lf.ready = 0;
+  t->lf.ready = 0; t->lf.batch_ready = 0;
   if (t->begun != count) { set_error("dvm_track_finish: no matching dvm_track_begin on this tracker"); return DVM_ERR_STATE; }
   const dvm_track_queries& q0 = qs[0];
   int nq_max = 0;
@@ -215,6 +221,11 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
     m.qdesc = carve<uint8_t>(p, Qn * 32); m.qx = carve<float>(p, Qn); m.qy = carve<float>(p, Qn); m.qr = carve<float>(p, Qn);
     m.qmin = carve<int32_t>(p, Qn); m.qmax = carve<int32_t>(p, Qn); m.q_claims = carve<uint8_t>(p, Qn); m.q_angle = carve<float>(p, Qn);
     m.q_pos = carve<float>(p, Qn * 3); m.pose_in = carve<double>(p, (size_t)count * 7); m.nq_arr = carve<int32_t>(p, count); m.inv_sigma2 = carve<float>(p, 64);
+    // (the block's end and the ranked lists' inside what create sized: refused before anything is written)
+    if ((size_t)(p - t->hm) > t->q_bytes || Qn > (size_t)t->max_frames * t->q_rcap) {
+      set_error("dvm_track_finish: the query block exceeds what the tracker was created for");
+      return DVM_ERR_CAPACITY;
+    }
   }
   HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {       // (a batch's query blocks: 2.4 MB for 32 frames)
     const dvm_track_queries& q = qs[b];
@@ -293,11 +304,14 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
     r.n_edges = m.nedges[b]; r.n_inliers = m.n_inl[b]; r.nmatches_map = m.fin[4 * b]; r.nmatches_after = m.fin[4 * b + 1];
     std::memcpy(r.pose, m.pose_out + 7 * (size_t)b, 56);
   }
-  if (count == 1 && res[0].status == DVM_TRACK_COMPLETE) {     // what the second half runs on: this frame's grid (slot 0) and mvKeysUn
+  {     // what the second half runs on: the frames' grids (slots 0..count-1) and mvKeysUn
     LocalFrame& f = t->lf;
-    f.ready = 1; f.h = h; f.serial = orb_result_serial(h); f.n = res[0].n; f.ocap = ocap; f.nlevels = q0.nlevels;
+    f.ready = count == 1 && res[0].status == DVM_TRACK_COMPLETE; f.batch_ready = 1;
+    f.h = h; f.serial = orb_result_serial(h); f.n = res[0].n; f.ocap = ocap; f.nlevels = q0.nlevels;
     f.d_un = reinterpret_cast<const dvm_keypoint_pod*>(d_un); f.d_n = d_n;
     std::memcpy(f.bounds, q0.bounds, 16); std::memcpy(f.inv_sigma2, q0.inv_level_sigma2, (size_t)q0.nlevels * 4); f.cam = q0.cam;
+    f.count = count; f.kps_stride = kps_stride; f.ns.resize((size_t)count); f.status.resize((size_t)count);
+    for (int b = 0; b < count; b++) { f.ns[b] = res[b].n; f.status[b] = res[b].status; }
   }
   return DVM_OK;
 }
@@ -322,23 +336,45 @@ LocalUpload carve_upload(uint8_t* base, int n, int N) {
   u.bytes = (size_t)(p - base);
   return u;
 }
+// the batch's upload block (dvm_track_local_map_batch), the same way: [mvScaleFactors 64][mvInvLevelSigma2 64][per frame: the first half's
+// pose 7 doubles, LocalFrameArgs, table offset, skip-flag switch][tables: T records, frame b's at qoff[b]][frame_mp: count x kstride].
+// For one frame it is no larger than LocalUpload's block.
+struct LocalUploadBatch {
+  float *scale, *inv_sigma2; double* pose; LocalFrameArgs* fa; int32_t *qoff, *skip_on; LocalPointPod* pts; int32_t* frame_mp; size_t bytes;
+};
+constexpr size_t kFrameRec = 7 * 8 + sizeof(LocalFrameArgs) + 8;     // per frame bytes of the frame block
+LocalUploadBatch carve_upload_batch(uint8_t* base, int count, size_t T, size_t kstride) {
+  LocalUploadBatch u;
+  uint8_t* p = base;
+  u.scale = carve<float>(p, 64); u.inv_sigma2 = carve<float>(p, 64);
+  uint8_t* fb = carve<uint8_t>(p, (size_t)count * kFrameRec);
+  u.pose = reinterpret_cast<double*>(fb); u.fa = reinterpret_cast<LocalFrameArgs*>(fb + (size_t)count * 56);
+  u.qoff = reinterpret_cast<int32_t*>(u.fa + count); u.skip_on = u.qoff + count;
+  u.pts = carve<LocalPointPod>(p, T); u.frame_mp = carve<int32_t>(p, (size_t)count * kstride);
+  u.bytes = (size_t)(p - base);
+  return u;
+}
 }  // namespace
 
 int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points) {
   if (!t || max_points < 1) return DVM_ERR_INVALID;
-  // (the prologue is one workgroup per frame: beyond 1 << 20 points it would dominate the chain, so such a table is refused)
-  if (max_points > (1 << 20)) { set_error("dvm_tracker_reserve_local_map: more than 1 048 576 local map points"); return DVM_ERR_CAPACITY; }
+  // (the prologue is one workgroup per frame: beyond 1 << 20 points per frame it would dominate the chain, so such a table is refused)
+  if ((int64_t)max_points > ((int64_t)t->max_frames << 20)) {
+    set_error("dvm_tracker_reserve_local_map: more than 1 048 576 local map points per frame"); return DVM_ERR_CAPACITY;
+  }
   DVM_HIP(hipSetDevice(t->device));
   if (t->d_lm) { hipFree(t->d_lm); t->d_lm = nullptr; }
   if (t->hm_lm) { hipHostFree(t->hm_lm); t->hm_lm = nullptr; }
-  t->lm_cap = 0; t->lf.ready = 0;
-  const size_t P = ((size_t)max_points + 63) & ~(size_t)63, K = (size_t)t->kp_cap;
-  t->lm_up_bytes = pad256(56) + 2 * pad256(256) + pad256(P * sizeof(LocalPointPod)) + pad256(K * 4);
-  // device: upload copy, per-entry arrays (seen, pos, claims), per-keypoint arrays (frame_mp, skip), pose seed, query arrays at any stride
+  t->lm_cap = 0; t->lf.ready = 0; t->lf.batch_ready = 0;
+  // P: table entries of one call (a batch: all frames' tables, each rounded up to 64); per keypoint and per frame: max_frames frames
+  const size_t P = ((size_t)max_points + 63) & ~(size_t)63, K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
+  t->lm_up_bytes = pad256(B * kFrameRec) + 2 * pad256(256) + pad256(P * sizeof(LocalPointPod)) + pad256(B * K * 4);
+  // device: upload copy, per-entry arrays (seen, pos, claims), per-keypoint arrays (frame_mp, skip), pose seeds, query arrays at any stride
   // up to P, ranked lists, counters
-  const size_t dbytes = t->lm_up_bytes + pad256(P) + pad256(P * 12) + pad256(P) + pad256(K * 4) + pad256(K) + pad256(56) +
-                        pad256(P * 32) + 5 * pad256(P * 4) + pad256(P) + pad256(P * 4) + pad256(P * 16) + 2 * pad256(32);
-  const size_t mbytes = t->lm_up_bytes + pad256(K * 4) + pad256(K) + pad256(P * sizeof(TrackPoint)) + pad256(64) + pad256(56) + 3 * pad256(16);
+  const size_t dbytes = t->lm_up_bytes + pad256(P) + pad256(P * 12) + pad256(P) + pad256(B * K * 4) + pad256(B * K) + pad256(B * 56) +
+                        pad256(P * 32) + 5 * pad256(P * 4) + pad256(P) + pad256(P * 4) + pad256(P * 16) + 2 * pad256(B * 32);
+  const size_t mbytes = t->lm_up_bytes + pad256(B * K * 4) + pad256(B * K) + pad256(P * sizeof(TrackPoint)) + pad256(B * 64) + pad256(B * 56) +
+                        3 * pad256(B * 16);
   if (hipMalloc(reinterpret_cast<void**>(&t->d_lm), dbytes) != hipSuccess) {
     t->d_lm = nullptr; set_error("dvm_tracker_reserve_local_map: hipMalloc"); return DVM_ERR_CAPACITY;
   }
@@ -351,8 +387,8 @@ int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points) {
   std::memset(t->hm_lm, 0, mbytes);
   uint8_t* p = t->hm_lm + t->lm_up_bytes;
   auto& r = t->lm;
-  r.mp = carve<int32_t>(p, K); r.outlier = carve<uint8_t>(p, K); r.tp = carve<TrackPoint>(p, P); r.res = carve<int32_t>(p, 16);
-  r.pose = carve<double>(p, 7); r.n_inl = carve<int32_t>(p, 4); r.fin = carve<int32_t>(p, 4); r.nedges = carve<int32_t>(p, 4);
+  r.mp = carve<int32_t>(p, B * K); r.outlier = carve<uint8_t>(p, B * K); r.tp = carve<TrackPoint>(p, P); r.res = carve<int32_t>(p, B * 16);
+  r.pose = carve<double>(p, B * 7); r.n_inl = carve<int32_t>(p, B * 4); r.fin = carve<int32_t>(p, B * 4); r.nedges = carve<int32_t>(p, B * 4);
   t->lm_cap = (int)P;
   return DVM_OK;
 }
@@ -402,7 +438,7 @@ int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, 
   A.fx = (float)f.cam.fx; A.fy = (float)f.cam.fy; A.cx = (float)f.cam.cx; A.cy = (float)f.cam.cy;
   A.min_x = f.bounds[0]; A.max_x = f.bounds[1]; A.min_y = f.bounds[2]; A.max_y = f.bounds[3];
   A.log_scale_factor = f.nlevels > 1 ? (float)std::log((double)scale[1]) : 0.0f;     // Frame::mfLogScaleFactor = log(mfScaleFactor)
-  A.th = th; A.th_far = th_far; A.n_levels = f.nlevels; A.far_points = far_points ? 1 : 0; A.n = n;
+  A.th = th; A.th_far = th_far; A.n_levels = f.nlevels; A.far_points = far_points ? 1 : 0; A.n = n; A.per_frame = nullptr;
   const TrackBatch TB{1, Qs, (int64_t)f.ocap, LQ.nq};
   auto& r = t->lm;
   // 3. SearchLocalPoints up to the queries
@@ -425,7 +461,7 @@ int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, 
                           t->lmdev(r.pose), t->d_edge_out, t->lmdev(r.n_inl), t->d_chi);
   launch_track_finish(s, t->d_assign, f.d_n, f.ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmdev(r.outlier), t->lmdev(r.fin),
                       d_lres, TE);
-  f.ready = 0;                      // once per finish
+  f.ready = 0; f.batch_ready = 0;   // once per finish
   rc = hip_check(hipGetLastError(), "local map chain launch");
   if (rc != DVM_OK) return rc;
   // 7. ONE synchronisation: everything the host reads was written to mapped memory by the kernels
@@ -438,6 +474,132 @@ int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, 
   // Sophus::SE3f(SE3quat_recov.rotation().cast<float>(), SE3quat_recov.translation().cast<float>()) (Optimizer.cc:1023-1025)
   for (int k = 0; k < 3; k++) res->Tcw.t[k] = (float)res->pose[k];
   for (int k = 0; k < 4; k++) res->Tcw.q[k] = (float)res->pose[3 + k];
+  return DVM_OK;
+}
+
+int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_out* out,
+                              dvm_track_local_result* res, int32_t* status) {
+  if (!t || !h || !in || !out || !res || !status || count < 1) return DVM_ERR_INVALID;
+  LocalFrame& f = t->lf;
+  if (!f.batch_ready || f.h != h || orb_result_serial(h) != f.serial || f.count != count) {
+    set_error("dvm_track_local_map_batch: not right after a dvm_track_finish[_batch] of `count` frames (same tracker and extractor)");
+    return DVM_ERR_STATE;
+  }
+  if (!t->d_lm) { set_error("dvm_track_local_map_batch: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
+  static const bool timing = std::getenv("DVM_TRACK_BATCH_TIMING") != nullptr;       // host-side phase times on stderr
+  using clk = std::chrono::steady_clock;
+  const clk::time_point tp0 = clk::now();
+  // the frames' table offsets: each frame's span rounded up to 64, back to back; a frame the first half did not complete gets none
+  std::vector<int32_t> qoff((size_t)count), nb((size_t)count, 0);
+  size_t T = 0, span_max = 64;
+  int live = 0;
+  for (int b = 0; b < count; b++) {
+    qoff[b] = (int32_t)std::min(T, (size_t)INT32_MAX);
+    if (f.status[b] != DVM_TRACK_COMPLETE) continue;
+    const dvm_local_map_in& q = in[b];
+    const int N = f.ns[b];
+    if (q.n < 0 || (q.n && !q.pts) || (N && !q.frame_mp) || !out[b].mp_out || !out[b].outlier) return DVM_ERR_INVALID;
+    for (int j = 0; j < N; j++)
+      if (q.frame_mp[j] < -1 || q.frame_mp[j] >= q.n) { set_error("dvm_track_local_map_batch: frame_mp names a point outside the table"); return DVM_ERR_INVALID; }
+    const size_t span = ((size_t)q.n + 63) & ~(size_t)63;
+    nb[b] = q.n; T += span; span_max = std::max(span_max, span); live++;
+  }
+  if (T > (size_t)t->lm_cap) { set_error("dvm_track_local_map_batch: more local map points than reserved (each frame's rounded up to 64)"); return DVM_ERR_CAPACITY; }
+  for (int b = 0; b < count; b++) { std::memset(&res[b], 0, sizeof(res[b])); status[b] = f.status[b]; }
+  if (!live) { f.ready = 0; f.batch_ready = 0; return DVM_OK; }
+  const int ocap = f.ocap;
+  const size_t Tc = std::max(T, (size_t)64);
+  const LocalUploadBatch up = carve_upload_batch(t->hm_lm, count, Tc, (size_t)ocap);
+  if (up.bytes > t->lm_up_bytes) { set_error("dvm_track_local_map_batch: the upload block exceeds the reservation"); return DVM_ERR_CAPACITY; }
+  DVM_HIP(hipSetDevice(t->device));
+  hipStream_t s = (hipStream_t)dvm_orb_stream(h);
+  // 1. the tables, the frames' points, poses and parameters packed into the mapped staging block by the pool threads: ONE copy
+  std::vector<float> scale(256, 1.0f);
+  int rc = dvm_orb_tables(h, scale.data(), nullptr, nullptr, nullptr, nullptr);
+  if (rc != DVM_OK) return rc;
+  std::memcpy(up.scale, scale.data(), 64 * 4);
+  std::memcpy(up.inv_sigma2, f.inv_sigma2, 64 * 4);
+  HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {       // (32 tables of 3 000 points: 7 MB)
+    const bool go = f.status[b] == DVM_TRACK_COMPLETE;
+    int32_t* fm = up.frame_mp + b * (size_t)ocap;
+    std::memcpy(up.pose + 7 * b, t->m.pose_out + 7 * b, 56);
+    up.fa[b] = LocalFrameArgs{nb[b], go && in[b].far_points ? 1 : 0, go ? in[b].th : 1.0f, go ? in[b].th_far : 0.0f};
+    up.qoff[b] = qoff[b]; up.skip_on[b] = 1;
+    if (go) {
+      if (nb[b]) std::memcpy(up.pts + qoff[b], in[b].pts, (size_t)nb[b] * sizeof(LocalPointPod));
+      if (f.ns[b]) std::memcpy(fm, in[b].frame_mp, (size_t)f.ns[b] * 4);
+    } else {
+      for (int j = 0; j < ocap; j++) fm[j] = -1;        // a skipped frame holds nothing and searches nothing
+    }
+  });
+  DVM_HIP(hipMemcpyAsync(t->d_lm, t->hm_lm, up.bytes, hipMemcpyHostToDevice, s));
+  const clk::time_point tp1 = clk::now();
+  const LocalUploadBatch dup = carve_upload_batch(t->d_lm, count, Tc, (size_t)ocap);
+  // 2. device arrays of this call: per entry at the frames' offsets, per keypoint at b * ocap
+  const size_t Kb = (size_t)count * ocap;
+  LocalQueries LQ;
+  uint8_t* p = t->d_lm + t->lm_up_bytes;
+  LQ.seen = carve<uint8_t>(p, Tc); LQ.pos = carve<float>(p, Tc * 3); LQ.claims = carve<uint8_t>(p, Tc);
+  LQ.frame_mp = carve<int32_t>(p, Kb); LQ.skip = carve<uint8_t>(p, Kb); LQ.pose_in = carve<double>(p, (size_t)count * 7);
+  LQ.qdesc = carve<uint8_t>(p, Tc * 32); LQ.qx = carve<float>(p, Tc); LQ.qy = carve<float>(p, Tc); LQ.qr = carve<float>(p, Tc);
+  LQ.qmin = carve<int32_t>(p, Tc); LQ.qmax = carve<int32_t>(p, Tc); LQ.q_claims = carve<uint8_t>(p, Tc); LQ.q_tab = carve<int32_t>(p, Tc);
+  uint32_t* d_ranked = carve<uint32_t>(p, Tc * 4);
+  int32_t* d_lres = carve<int32_t>(p, (size_t)count * 8);
+  LQ.nq = carve<int32_t>(p, (size_t)count * 8);
+  LocalMapArgs A;
+  A.fx = (float)f.cam.fx; A.fy = (float)f.cam.fy; A.cx = (float)f.cam.cx; A.cy = (float)f.cam.cy;
+  A.min_x = f.bounds[0]; A.max_x = f.bounds[1]; A.min_y = f.bounds[2]; A.max_y = f.bounds[3];
+  A.log_scale_factor = f.nlevels > 1 ? (float)std::log((double)scale[1]) : 0.0f;
+  A.th = 1.0f; A.th_far = 0.0f; A.n_levels = f.nlevels; A.far_points = 0; A.n = 0; A.per_frame = dup.fa;
+  const TrackBatch TB{count, (int)span_max, f.kps_stride, LQ.nq, dup.qoff};
+  auto& r = t->lm;
+  // 3. the chain of dvm_track_local_map, a workgroup (row of workgroups) per frame on grid slots 0..count-1
+  bool want_tp = false;
+  for (int b = 0; b < count; b++) want_tp = want_tp || (f.status[b] == DVM_TRACK_COMPLETE && out[b].track_pts);
+  launch_track_local_prologue(s, dup.pts, dup.frame_mp, dup.pose, dup.scale, f.d_n, ocap, A, LQ, want_tp ? t->lmdev(r.tp) : nullptr, t->lmdev(r.res),
+                              TB);
+  const FrameView FV = frame_view_of(t->grid);
+  launch_match_window_ranked_batch(s, FV, 0, count, LQ.skip, dup.skip_on, ocap, LQ.qdesc, LQ.qx, LQ.qy, LQ.qr, LQ.qmin, LQ.qmax, LQ.nq,
+                                   (int)span_max, d_ranked, dup.qoff);
+  TrackRequery rq{};
+  rq.F = FV;
+  rq.qdesc = LQ.qdesc; rq.qx = LQ.qx; rq.qy = LQ.qy; rq.qr = LQ.qr; rq.qmin = LQ.qmin; rq.qmax = LQ.qmax;
+  launch_track_claims_local(s, d_ranked, LQ, rq, f.d_un, f.d_n, ocap, 100 /* TH_HIGH */, 0.8f, t->d_assign, d_lres, t->lmdev(r.mp),
+                            t->lmdev(r.res) + 8 * count, TB);
+  const TrackBatch TE{count, 0, f.kps_stride, nullptr, dup.qoff};
+  launch_track_gather(s, t->d_assign, f.d_un, f.d_n, ocap, LQ.pos, dup.inv_sigma2, f.nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp,
+                      t->d_nedges, d_lres, 0, t->lmdev(r.nedges), TE);
+  ba_launch_pose_optimize(s, LQ.pose_in, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, f.cam.fx, f.cam.fy, f.cam.cx, f.cam.cy,
+                          t->lmdev(r.pose), t->d_edge_out, t->lmdev(r.n_inl), t->d_chi);
+  launch_track_finish(s, t->d_assign, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmdev(r.outlier), t->lmdev(r.fin),
+                      d_lres, TE);
+  f.ready = 0; f.batch_ready = 0;   // once per finish
+  rc = hip_check(hipGetLastError(), "batched local map chain launch");
+  if (rc != DVM_OK) return rc;
+  // 4. ONE synchronisation, then every completed frame's outputs copied out of mapped memory by the pool threads
+  DVM_HIP(hipStreamSynchronize(s));
+  const clk::time_point tp2 = clk::now();
+  HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {
+    if (f.status[b] != DVM_TRACK_COMPLETE) return;
+    const int N = f.ns[b], n = nb[b];
+    const size_t ko = b * (size_t)ocap;
+    const dvm_local_map_out& o = out[b];
+    if (N) { std::memcpy(o.mp_out, r.mp + ko, (size_t)N * 4); std::memcpy(o.outlier, r.outlier + ko, (size_t)N); }
+    if (o.track_pts && n) std::memcpy(o.track_pts, r.tp + qoff[b], (size_t)n * sizeof(dvm_track_point));
+    dvm_track_local_result& q = res[b];
+    const int32_t* pr = r.res + 8 * b;
+    const int32_t* cr = r.res + 8 * ((size_t)count + b);
+    q.n_to_match = pr[0]; q.n_cleared_bad = pr[1]; q.nmatches = cr[0]; q.n_requeried = cr[3];
+    q.n_edges = r.nedges[b]; q.n_inliers = r.n_inl[b]; q.matches_inliers = r.fin[4 * b];
+    std::memcpy(q.pose, r.pose + 7 * b, 56);
+    for (int k = 0; k < 3; k++) q.Tcw.t[k] = (float)q.pose[k];
+    for (int k = 0; k < 4; k++) q.Tcw.q[k] = (float)q.pose[3 + k];
+  });
+  if (timing) {
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    std::fprintf(stderr, "track local map batch of %d (%zu entries): pack + enqueue %.3f  wait %.3f  results out %.3f ms\n", count, T, ms(tp0, tp1),
+                 ms(tp1, tp2), ms(tp2, clk::now()));
+  }
   return DVM_OK;
 }
 

@@ -14,17 +14,23 @@ struct TrackRequery {
   const uint8_t* qdesc; const float *qx, *qy, *qr; const int32_t *qmin, *qmax;
 };
 // a batch of frames through the same launches: frame b's per-query arrays at b * qstride elements (nq_arr[b] of them), its keypoints at
-// b * kps_stride; count = 1, nq_arr = nullptr: one frame (nq given directly)
-struct TrackBatch { int count; int qstride; int64_t kps_stride; const int32_t* nq_arr; };
+// b * kps_stride; count = 1, nq_arr = nullptr: one frame (nq given directly).  qoff (device, may be null): frame b's per-query arrays at
+// qoff[b] elements instead (dvm_track_local_map_batch: tables of different sizes packed back to back)
+struct TrackBatch {
+  int count; int qstride; int64_t kps_stride; const int32_t* nq_arr; const int32_t* qoff;
+  __host__ __device__ size_t qo(int b) const { return qoff ? (size_t)qoff[b] : (size_t)b * qstride; }
+};
 // ---- the second half (dvm_track_local_map): SearchLocalPoints -> SearchByProjection(F, points) -> PoseOptimization
 struct LocalPointPod {  // == dvm_local_point
   float pos[3], normal[3], min_dist, max_dist;
   uint8_t desc[32];
   int32_t n_obs, bad;
 };
+struct LocalFrameArgs { int32_t n, far_points; float th, th_far; };   // one frame's table size and SearchByProjection's th / far-point filter
 struct LocalMapArgs {   // the call's constants: camera, bounds, level count, SearchByProjection's th / far-point filter, table size
   float fx, fy, cx, cy, min_x, max_x, min_y, max_y, log_scale_factor, th, th_far;
   int32_t n_levels, far_points, n;
+  const LocalFrameArgs* per_frame;   // device, may be null: frame b's n / th / far_points / th_far from per_frame[b] instead of the above
 };
 // what k_track_local_prologue leaves for the search (device arrays; the query arrays at the call's stride)
 struct LocalQueries {
@@ -37,7 +43,8 @@ struct LocalQueries {
   uint8_t* claims;             // [n] Observations() > 0 of every entry
   double* pose_in;             // [7] the first half's float pose widened: PoseOptimization's seed
 };
-// pose_first: the first half's optimised pose (t, q doubles); scale: mvScaleFactors [64]; B: count = 1, qstride = the table's stride
+// pose_first: the first half's optimised pose (t, q doubles); scale: mvScaleFactors [64]; B: count = 1, qstride = the table's stride, or
+// count frames with B.qoff (frame b's table, per-entry and query arrays at qoff[b], its per-keypoint arrays at b * kp_cap, A.per_frame)
 void launch_track_local_prologue(hipStream_t s, const LocalPointPod* pts, const int32_t* frame_mp_in, const double* pose_first, const float* scale,
                                  const int32_t* d_n, int kp_cap, const LocalMapArgs& A, const LocalQueries& LQ, TrackPoint* track_pts_host,
                                  int32_t* res_host, const TrackBatch& B);

@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
   {
     const int b = blockIdx.x;
     if (B.nq_arr) nq = B.nq_arr[b];
-    const size_t qo = (size_t)b * B.qstride;
+    const size_t qo = B.qo(b);
     ranked += qo * 4; q_claims += qo; q_angle += qo;
     RQ.qdesc += qo * 32; RQ.qx += qo; RQ.qy += qo; RQ.qr += qo; RQ.qmin += qo; RQ.qmax += qo;
     if (RQ.F.skp) RQ.F = RQ.F.slot(b);
@@ -336,7 +336,7 @@ __global__ void __launch_bounds__(256) k_track_gather(const int32_t* __restrict_
   __shared__ int s_base;
   {
     const int b = blockIdx.x;
-    assign += (size_t)b * kp_cap; kps_un += (size_t)b * B.kps_stride; d_n += b; q_pos += (size_t)b * B.qstride * 3;
+    assign += (size_t)b * kp_cap; kps_un += (size_t)b * B.kps_stride; d_n += b; q_pos += B.qo(b) * 3;
     Xw += (size_t)b * kp_cap * 3; obs += (size_t)b * kp_cap * 2; info += (size_t)b * kp_cap; edge_kp += (size_t)b * kp_cap;
     n_edges += b; n_edges_host += b; res += 8 * b;
   }
@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(256) k_track_finish(int32_t* __restrict__ assi
   {
     const int b = blockIdx.x;
     assign += (size_t)b * kp_cap; d_n += b; edge_kp += (size_t)b * kp_cap; n_edges += b; edge_outlier += (size_t)b * kp_cap;
-    q_claims += (size_t)b * B.qstride; outlier += (size_t)b * kp_cap; out += 4 * b; res += 8 * b;
+    q_claims += B.qo(b); outlier += (size_t)b * kp_cap; out += 4 * b; res += 8 * b;
   }
   const int tid = threadIdx.x;
   const int N = min(*d_n, kp_cap), E = n_edges[0];
@@ -407,7 +407,8 @@ __global__ void __launch_bounds__(256) k_track_finish(int32_t* __restrict__ assi
 //   isInFrustum(pMP, 0.5) of every entry (frustum_point.h); mbTrackInView false for seen and bad entries; nToMatch
 //   the far-point filter (:52-53), radius RadiusByViewingCos(viewCos) * (th != 1 ? th : 1) * mvScaleFactors[level], levels
 //     [level - 1, level]; the in-view points compacted into the query arrays IN TABLE ORDER (the claim replay's order)
-// tables: scale[64] = mvScaleFactors.  res_host[0] = nToMatch, res_host[1] = frame points cleared as bad.
+// tables: scale[64] = mvScaleFactors.  res_host[0] = nToMatch, res_host[1] = frame points cleared as bad.  A batch (B.qoff) reads each
+// frame's table size, th and far-point filter from A.per_frame[b]; an empty table with no frame points leaves nothing to search.
 __global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointPod* __restrict__ pts, const int32_t* __restrict__ frame_mp_in,
                                                                const double* __restrict__ pose_first, const float* __restrict__ scale,
                                                                const int32_t* __restrict__ d_n, int kp_cap, LocalMapArgs A, LocalQueries LQ,
@@ -417,7 +418,8 @@ __global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointP
   __shared__ float s_scale[64];
   {
     const int b = blockIdx.x;
-    const size_t qo = (size_t)b * B.qstride, ko = (size_t)b * kp_cap;
+    const size_t qo = B.qo(b), ko = (size_t)b * kp_cap;
+    if (A.per_frame) { const LocalFrameArgs fa = A.per_frame[b]; A.n = fa.n; A.far_points = fa.far_points; A.th = fa.th; A.th_far = fa.th_far; }
     pts += qo; frame_mp_in += ko; pose_first += 7 * b; d_n += b; res_host += 8 * b;
     if (tp_host) tp_host += qo;
     LQ.qdesc += qo * 32; LQ.qx += qo; LQ.qy += qo; LQ.qr += qo; LQ.qmin += qo; LQ.qmax += qo; LQ.q_claims += qo; LQ.q_tab += qo; LQ.nq += b;

@@ -662,6 +662,8 @@ typedef struct {
   int32_t reserved2;
 } dvm_track_local_result;          /* 120 bytes */
 /* Allocates the second half's working set for tables of up to max_points entries (at least 16 384 supported; no growth in the hot path).
+ * On a tracker of dvm_tracker_create_batch(max_frames = B), max_points is the TOTAL of one dvm_track_local_map_batch call: the sum over
+ * its frames of n_b, each rounded up to 64 (at least B x 16 384 supported); the per-keypoint arrays are reserved for B frames.
  * DVM_ERR_CAPACITY for what it cannot hold.  Called again, it replaces the working set; dvm_tracker_destroy frees it. */
 int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points);
 /* Right after a dvm_track_finish of ONE frame that returned DVM_TRACK_COMPLETE, on the same tracker and extractor, before the next begin
@@ -672,6 +674,27 @@ int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points);
  * fields per entry, in_view = mbTrackInView after SearchLocalPoints (0 for bad entries and those the frame holds). */
 int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, int n, const int32_t* frame_mp, float th, int far_points,
                         float th_far, int32_t* mp_out, uint8_t* outlier, dvm_track_point* track_pts /* may be NULL */, dvm_track_local_result* res);
+/* The same for the `count` frames of a dvm_track_finish_batch (or a dvm_track_finish: count = 1) -- several agents' frames of one camera
+ * tick: ONE upload of all tables, ONE chain of batched launches on the finish's grids, ONE synchronisation.  Accepted right after that
+ * finish on the same tracker and extractor with the finish's count, before the next begin, once per finish (otherwise DVM_ERR_STATE);
+ * where the finish ran twice (the wider window), the last one counts.  in / out / res / status: `count` entries.
+ *   frame b with first-half status DVM_TRACK_COMPLETE: res[b] and out[b] are exactly what dvm_track_local_map gives on that frame alone;
+ *     status[b] = DVM_TRACK_COMPLETE.  Its table size n_b may be 0 and differs per frame, as do th, far_points and th_far (th = 5 after a
+ *     relocalisation, 15 when lost: Tracking.cc:3083-3106).
+ *   any other frame b: skipped -- status[b] = the first half's status, res[b] zeroed, out[b] not written, in[b] not read.
+ * frame_mp entries outside [-1, n_b): DVM_ERR_INVALID; the tables' total (each n_b rounded up to 64) beyond the reservation:
+ * DVM_ERR_CAPACITY.  DVM_TRACK_BATCH_TIMING=1 prints the call's host phases on stderr. */
+typedef struct {
+  const dvm_local_point* pts; int32_t n;          /* this agent's mvpLocalMapPoints; n may be 0 */
+  const int32_t* frame_mp;                        /* [N_b] index into pts of the point keypoint j holds after the first half, or -1 */
+  float th; int32_t far_points; float th_far;     /* SearchByProjection's th (1 / 5 / 15 ...), mbFarPoints, mThFarPoints */
+} dvm_local_map_in;                               /* 40 bytes */
+typedef struct {
+  int32_t* mp_out; uint8_t* outlier;              /* [N_b] as dvm_track_local_map */
+  dvm_track_point* track_pts;                     /* [n_b] or NULL */
+} dvm_local_map_out;                              /* 24 bytes */
+int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_out* out,
+                              dvm_track_local_result* res, int32_t* status);
 
 /* Optimizer::OptimizeSim3 (Optimizer.cc:1960-2212), numerics for N correspondences gathered by the caller:
  * P1c / P2c = the matched map points in their own key frame's camera frame (R1w*P+t1w, R2w*P+t2w), obs1 / obs2 =
