@@ -985,6 +985,74 @@ class Tracker:
             out["track_pts"] = tp[:len(pts)]
         return out
 
+    def reserve_reference_keyframe(self, n):
+        """dvm_tracker_reserve_reference_keyframe: the reference-keyframe chain's working set for keyframes of up to n keypoints."""
+        f = self.L.dvm_tracker_reserve_reference_keyframe
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32]
+        check(f(self.t, int(n)))
+
+    def track_reference_keyframe(self, voc, kf, pose_last, img=None, K=None, bounds=None, inv_sigma2=None, dist=None, nnratio=0.7, check_ori=True,
+                                 th_low=50, min_matches=15, min_map=10, levelsup=4, lap=(0, 1000)):
+        """dvm_track_reference_keyframe: Tracking::TrackReferenceKeyFrame (reference src/Tracking.cc:2461-2520) as ONE device chain.
+        voc: a Vocabulary; kf: dict(kps (mvKeysUn), desc, mp (map-point ids or -1), pos [n, 3], n_obs, bad (optional), fv (mFeatVec as
+        vocab_transform_host returns it)); pose_last: mLastFrame.GetPose() as 7 floats (qx, qy, qz, qw, t).  With img: dvm_track_begin on it,
+        then the chain (form a: the no-motion-model case); without: the chain on the frame of the last track() (form b: the motion model
+        failed).  K: fx fy cx cy; bounds, dist: form (a).  Returns a dict: the counters of dvm_track_refkf_result, mp (mvpMapPoints after the
+        outlier drop), dropped, outlier, bow_ids / bow_vals / fv_nodes / fv_off / fv_feat (ComputeBoW), pose (7 doubles: t, q), Tcw (7 floats:
+        q, t) and, in form (a), kps / desc / kps_un."""
+        cap = self.ext.cap
+        vp = C.c_void_p
+        if img is not None:
+            img = np.ascontiguousarray(img, np.uint8)
+            fb = self.L.dvm_track_begin
+            fb.restype = C.c_int32
+            fb.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+            check(fb(self.t, self.ext.h, img.ctypes.data, img.shape[0], img.shape[1], img.strides[0], int(lap[0]), int(lap[1])))
+        kps_kf = np.ascontiguousarray(kf["kps"], KP_DTYPE)
+        n = len(kps_kf)
+        keep = [kps_kf, np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32), np.ascontiguousarray(kf["mp"], np.int32),
+                np.ascontiguousarray(kf["pos"], np.float32).reshape(-1, 3), np.ascontiguousarray(kf["n_obs"], np.int32)]
+        bad = None if kf.get("bad") is None else np.ascontiguousarray(kf["bad"], np.uint8)
+        fv = [np.ascontiguousarray(kf["fv"][k], np.int32) for k in ("fv_nodes", "fv_off", "fv_feat")]
+        rk = RefKeyframe()
+        rk.n = n
+        rk.kps_un, rk.desc, rk.mp, rk.mp_pos, rk.mp_nobs = (a.ctypes.data if len(a) else None for a in keep)
+        rk.mp_bad = None if bad is None or not len(bad) else bad.ctypes.data
+        rk.fv_n = len(fv[0])
+        rk.fv_node, rk.fv_off, rk.fv_feat = (a.ctypes.data if len(a) else None for a in fv)
+        T = np.asarray(pose_last, np.float32).reshape(7)
+        pr = TrackRefKfParams()
+        pr.pose_in[:] = [float(v) for v in np.concatenate([T[4:7], T[0:4]]).astype(np.float64)]
+        pr.nnratio, pr.check_ori, pr.th_low, pr.min_matches, pr.min_map, pr.levelsup = float(nnratio), int(check_ori), int(th_low), int(min_matches), int(min_map), int(levelsup)
+        if bounds is not None:
+            pr.bounds[:] = [float(v) for v in np.asarray(bounds, np.float32)]
+        pr.dist = None if dist is None else C.cast(C.pointer(dist), vp)
+        s2 = np.ascontiguousarray(inv_sigma2, np.float32)
+        pr.inv_level_sigma2, pr.nlevels = s2.ctypes.data, len(s2)
+        Kf = np.asarray(K, np.float32)
+        pr.cam = BaCamera(*[float(v) for v in Kf[:4]], 0.0)
+        kps = np.empty(cap, KP_DTYPE); kun = np.empty(cap, KP_DTYPE); desc = np.empty((cap, 32), np.uint8)
+        mp = np.empty(cap, np.int32); dropped = np.empty(cap, np.int32); outl = np.empty(cap, np.uint8)
+        bi = np.empty(cap, np.int32); bv = np.empty(cap, np.float64); fn = np.empty(cap, np.int32); fo = np.empty(cap + 1, np.int32)
+        ff = np.empty(cap, np.int32)
+        o = TrackRefKfOut()
+        o.kps, o.desc, o.cap, o.kps_un = kps.ctypes.data, desc.ctypes.data, cap, kun.ctypes.data
+        o.mp_out, o.dropped, o.outlier = mp.ctypes.data, dropped.ctypes.data, outl.ctypes.data
+        o.bow_ids, o.bow_vals, o.fv_node, o.fv_off, o.fv_feat = bi.ctypes.data, bv.ctypes.data, fn.ctypes.data, fo.ctypes.data, ff.ctypes.data
+        res = TrackRefKfResult()
+        f = self.L.dvm_track_reference_keyframe
+        f.restype = C.c_int32
+        f.argtypes = [vp, vp, vp, C.POINTER(RefKeyframe), C.POINTER(TrackRefKfParams), C.POINTER(TrackRefKfOut), C.POINTER(TrackRefKfResult)]
+        check(f(self.t, self.ext.h, voc.h, C.byref(rk), C.byref(pr), C.byref(o), C.byref(res)))
+        N = res.n
+        out = {k: getattr(res, k) for k in ("n", "mono_index", "status", "nmatches", "nmatches_before_rotation", "n_edges", "n_inliers",
+                                            "nmatches_after", "nmatches_map", "n_bow", "n_fv")}
+        out.update(mp=mp[:N], dropped=dropped[:N], outlier=outl[:N], bow_ids=bi[:res.n_bow], bow_vals=bv[:res.n_bow], fv_nodes=fn[:res.n_fv],
+                   fv_off=fo[:res.n_fv + 1], fv_feat=ff[:fo[res.n_fv]], pose=np.array(res.pose[:], np.float64), Tcw=np.array(res.Tcw[:], np.float32))
+        if img is not None:
+            out.update(kps=kps[:N], desc=desc[:N], kps_un=kun[:N])
+        return out
+
 
 # dvm_local_point (include/dvmslam_hip.h): one mvpLocalMapPoints entry -- GetWorldPos, GetNormal, mfMinDistance / mfMaxDistance,
 # GetDescriptor, Observations, isBad
@@ -996,6 +1064,37 @@ class TrackLocalResult(C.Structure):
     """dvm_track_local_result (include/dvmslam_hip.h)"""
     _fields_ = [(k, C.c_int32) for k in ("n_to_match", "nmatches", "n_requeried", "n_cleared_bad", "n_edges", "n_inliers", "matches_inliers",
                                          "reserved")] + [("pose", C.c_double * 7), ("Tcw", C.c_float * 7), ("reserved2", C.c_int32)]
+
+
+# dvm_track_refkf_* (include/dvmslam_hip.h): the reference-keyframe chain's keyframe, parameters, outputs and result; DVM_TRACK_* statuses
+DVM_TRACK_COMPLETE, DVM_TRACK_FEW_MATCHES, DVM_TRACK_FEW_MAP_MATCHES = 0, 1, 3
+
+
+class RefKeyframe(C.Structure):
+    """dvm_ref_keyframe (include/dvmslam_hip.h)"""
+    _fields_ = [("n", C.c_int32), ("kps_un", C.c_void_p), ("desc", C.c_void_p), ("mp", C.c_void_p), ("mp_pos", C.c_void_p), ("mp_nobs", C.c_void_p),
+                ("mp_bad", C.c_void_p), ("fv_n", C.c_int32), ("fv_node", C.c_void_p), ("fv_off", C.c_void_p), ("fv_feat", C.c_void_p)]
+
+
+class TrackRefKfParams(C.Structure):
+    """dvm_track_refkf_params (include/dvmslam_hip.h)"""
+    _fields_ = [("pose_in", C.c_double * 7), ("nnratio", C.c_float), ("check_ori", C.c_int32), ("th_low", C.c_int32), ("min_matches", C.c_int32),
+                ("min_map", C.c_int32), ("levelsup", C.c_int32), ("bounds", C.c_float * 4), ("dist", C.c_void_p), ("inv_level_sigma2", C.c_void_p),
+                ("nlevels", C.c_int32), ("cam", BaCamera)]
+
+
+class TrackRefKfOut(C.Structure):
+    """dvm_track_refkf_out (include/dvmslam_hip.h)"""
+    _fields_ = [("kps", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int32), ("kps_un", C.c_void_p), ("mp_out", C.c_void_p), ("dropped", C.c_void_p),
+                ("outlier", C.c_void_p), ("bow_ids", C.c_void_p), ("bow_vals", C.c_void_p), ("fv_node", C.c_void_p), ("fv_off", C.c_void_p),
+                ("fv_feat", C.c_void_p)]
+
+
+class TrackRefKfResult(C.Structure):
+    """dvm_track_refkf_result (include/dvmslam_hip.h)"""
+    _fields_ = [(k, C.c_int32) for k in ("n", "mono_index", "status", "nmatches", "nmatches_before_rotation", "n_edges", "n_inliers",
+                                         "nmatches_after", "nmatches_map", "n_bow", "n_fv", "reserved")] + \
+               [("pose", C.c_double * 7), ("Tcw", C.c_float * 7), ("reserved2", C.c_int32)]
 
 
 class TrackIn(C.Structure):

@@ -938,6 +938,17 @@ int dvm_vocab_create(int device, int n_nodes, const int32_t* child_off, const in
   return DVM_OK;
 }
 
+}  // extern "C"
+// for the chains of other translation units (track.cpp): the transform of the device features [cap][32] whose count is on the device
+namespace dvm {
+int vocab_device(const dvm_vocab* v) { return v->device; }
+void vocab_launch_transform(const dvm_vocab* v, hipStream_t s, const uint8_t* d_feat, int cap, const int32_t* d_n, int levelsup, int32_t* word_id,
+                            int32_t* node_id, double* weight) {
+  launch_vocab_transform(s, v->child_off, v->children, v->desc, v->weight, v->word_id, v->L, d_feat, cap, levelsup, word_id, node_id, weight, d_n);
+}
+}  // namespace dvm
+extern "C" {
+
 int dvm_vocab_transform(const dvm_vocab* v, const uint8_t* features, int n, int levelsup, int32_t* word_id, int32_t* node_id,
                         double* weight, int on_device, void* stream) {
   if (!v || n < 0) return DVM_ERR_INVALID;

@@ -825,9 +825,11 @@ __global__ void __launch_bounds__(256) k_vocab_transform(const int32_t* __restri
                                                          const uint8_t* __restrict__ node_desc, const double* __restrict__ weight,
                                                          const int32_t* __restrict__ word_id, int L, const uint8_t* __restrict__ feat,
                                                          int n, int levelsup, int32_t* __restrict__ out_word,
-                                                         int32_t* __restrict__ out_node, double* __restrict__ out_weight) {
+                                                         int32_t* __restrict__ out_node, double* __restrict__ out_weight,
+                                                         const int32_t* __restrict__ d_n) {
   const int lane = threadIdx.x & 15;
   const int f = blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (d_n) n = min(n, *d_n);     // (a count still on the device: n is then the capacity the grid covers)
   if (f >= n) return;
   uint32_t w[8];
   {
@@ -866,10 +868,10 @@ __global__ void __launch_bounds__(256) k_vocab_transform(const int32_t* __restri
 }
 void launch_vocab_transform(hipStream_t s, const int32_t* child_off, const int32_t* children, const uint8_t* node_desc,
                             const double* weight, const int32_t* word_id, int L, const uint8_t* feat, int n, int levelsup,
-                            int32_t* out_word, int32_t* out_node, double* out_weight) {
+                            int32_t* out_word, int32_t* out_node, double* out_weight, const int32_t* d_n) {
   if (n > 0)
     hipLaunchKernelGGL(k_vocab_transform, dim3((n + 15) / 16), dim3(256), 0, s, child_off, children, node_desc, weight, word_id, L,
-                       feat, n, levelsup, out_word, out_node, out_weight);
+                       feat, n, levelsup, out_word, out_node, out_weight, d_n);
 }
 
 }  // namespace dvm

@@ -43,6 +43,7 @@ struct LocalFrame {
   dvm_ba_camera cam{};
   int count = 0; int64_t kps_stride = 0;          // the finish's frames: frame b's mvKeysUn at b * kps_stride, its count at d_n[b]
   std::vector<int32_t> ns, status;                // per frame: keypoints, the first half's status
+  double pose[7] = {};                            // ready: the pose dvm_track_local_map starts from (the finish's, or the reference-keyframe chain's)
 };
 
 struct dvm_tracker {
@@ -78,9 +79,25 @@ struct dvm_tracker {
   struct LocalMapped { int32_t* mp; uint8_t* outlier; TrackPoint* tp; int32_t* res; double* pose; int32_t *n_inl, *fin, *nedges; } lm;   // [max_frames]
   LocalFrame lf;
   template <class T> T* lmdev(T* host_ptr) const { return reinterpret_cast<T*>(hm_lm_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm_lm)); }
+  // ---- TrackReferenceKeyFrame (dvm_track_reference_keyframe): working set of dvm_tracker_reserve_reference_keyframe, and when it may run
+  int rk_state = 0;                // 1: right after a single-frame begin (form a), 2: right after that frame's finish (form b), else 0
+  dvm_orb* rk_h = nullptr; uint64_t rk_serial = 0;   // the extractor and which of its extractions the frame is
+  int rk_cap = 0;                  // keyframe keypoints reserved
+  uint8_t* d_rk = nullptr;         // device: [upload copy][the frame's transform, FeatureVector and match state]
+  uint8_t *hm_rk = nullptr, *hm_rk_dev = nullptr;   // mapped: [upload staging][results]
+  size_t rk_up_bytes = 0;          // the upload region's capacity
+  struct RefKfMapped {
+    int32_t *bow_ids, *fv_node, *fv_off, *fv_feat, *match, *cnt, *nedges, *n_inl, *fin; double *bow_vals, *pose; uint8_t* outlier;
+  } rk;
+  template <class T> T* rkdev(T* host_ptr) const { return reinterpret_cast<T*>(hm_rk_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm_rk)); }
 };
 
-namespace dvm { uint64_t orb_result_serial(const dvm_orb* h); }   // capi.cpp: which extraction the handle's result holds
+namespace dvm {
+uint64_t orb_result_serial(const dvm_orb* h);   // capi.cpp: which extraction the handle's result holds
+int vocab_device(const dvm_vocab* v);           // capi.cpp: the vocabulary's device and its transform of device features (count on the device)
+void vocab_launch_transform(const dvm_vocab* v, hipStream_t s, const uint8_t* d_feat, int cap, const int32_t* d_n, int levelsup, int32_t* word_id,
+                            int32_t* node_id, double* weight);
+}
 
 namespace {
 size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -151,6 +168,8 @@ void dvm_tracker_destroy(dvm_tracker* t) {
   if (t->d_q) hipFree(t->d_q);
   if (t->d_lm) hipFree(t->d_lm);
   if (t->hm_lm) hipHostFree(t->hm_lm);
+  if (t->d_rk) hipFree(t->d_rk);
+  if (t->hm_rk) hipHostFree(t->hm_rk);
   if (t->cev) hipEventDestroy(t->cev);
   if (t->cstream) hipStreamDestroy(t->cstream);
   if (t->hm) hipHostFree(t->hm);
@@ -160,19 +179,21 @@ void dvm_tracker_destroy(dvm_tracker* t) {
 int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_batch: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0;
+  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0; t->rk_state = 0;
   const int rc = dvm_orb_extract_batch_host(h, imgs, count, rows, cols, stride, frame_stride, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
+  if (count == 1 && t->max_frames == 1) { t->rk_state = 1; t->rk_h = h; t->rk_serial = orb_result_serial(h); }
   return DVM_OK;
 }
 int dvm_track_begin_staged(dvm_tracker* t, dvm_orb* h, int count, int rows, int cols, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_staged: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0;
+  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0; t->rk_state = 0;
   const int rc = dvm_orb_extract_staged(h, count, rows, cols, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
+  if (count == 1 && t->max_frames == 1) { t->rk_state = 1; t->rk_h = h; t->rk_serial = orb_result_serial(h); }
   return DVM_OK;
 }
 int dvm_track_begin(dvm_tracker* t, dvm_orb* h, const uint8_t* img, int rows, int cols, int stride, int lap0, int lap1) {
@@ -181,7 +202,7 @@ int dvm_track_begin(dvm_tracker* t, dvm_orb* h, const uint8_t* img, int rows, in
 
 int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* qs, const dvm_track_frame_out* outs, dvm_track_result* res) {
   if (!t || !h || !qs || !outs || !res || count < 1) return DVM_ERR_INVALID;
-  t->lf.ready = 0; t->lf.batch_ready = 0;
+  t->lf.ready = 0; t->lf.batch_ready = 0; t->rk_state = 0;
   if (t->begun != count) { set_error("dvm_track_finish: no matching dvm_track_begin on this tracker"); return DVM_ERR_STATE; }
   const dvm_track_queries& q0 = qs[0];
   int nq_max = 0;
@@ -312,7 +333,9 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
     std::memcpy(f.bounds, q0.bounds, 16); std::memcpy(f.inv_sigma2, q0.inv_level_sigma2, (size_t)q0.nlevels * 4); f.cam = q0.cam;
     f.count = count; f.kps_stride = kps_stride; f.ns.resize((size_t)count); f.status.resize((size_t)count);
     for (int b = 0; b < count; b++) { f.ns[b] = res[b].n; f.status[b] = res[b].status; }
+    std::memcpy(f.pose, m.pose_out, 56);
   }
+  if (count == 1 && t->max_frames == 1) { t->rk_state = 2; t->rk_h = h; t->rk_serial = orb_result_serial(h); }   // (whatever the status)
   return DVM_OK;
 }
 
@@ -412,7 +435,7 @@ int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, 
   hipStream_t s = (hipStream_t)dvm_orb_stream(h);
   // 1. the table, the frame's points and the level tables: ONE asynchronous copy from the mapped staging block
   const LocalUpload up = carve_upload(t->hm_lm, n, N);
-  std::memcpy(up.pose, t->m.pose_out, 56);          // the first half's pose (the device casts it to the float pose the frame stores)
+  std::memcpy(up.pose, f.pose, 56);                 // the first half's pose (the device casts it to the float pose the frame stores)
   std::vector<float> scale(256, 1.0f);
   int rc = dvm_orb_tables(h, scale.data(), nullptr, nullptr, nullptr, nullptr);
   if (rc != DVM_OK) return rc;
@@ -461,7 +484,7 @@ int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, 
                           t->lmdev(r.pose), t->d_edge_out, t->lmdev(r.n_inl), t->d_chi);
   launch_track_finish(s, t->d_assign, f.d_n, f.ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmdev(r.outlier), t->lmdev(r.fin),
                       d_lres, TE);
-  f.ready = 0; f.batch_ready = 0;   // once per finish
+  f.ready = 0; f.batch_ready = 0; t->rk_state = 0;   // once per finish
   rc = hip_check(hipGetLastError(), "local map chain launch");
   if (rc != DVM_OK) return rc;
   // 7. ONE synchronisation: everything the host reads was written to mapped memory by the kernels
@@ -573,7 +596,7 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
                           t->lmdev(r.pose), t->d_edge_out, t->lmdev(r.n_inl), t->d_chi);
   launch_track_finish(s, t->d_assign, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmdev(r.outlier), t->lmdev(r.fin),
                       d_lres, TE);
-  f.ready = 0; f.batch_ready = 0;   // once per finish
+  f.ready = 0; f.batch_ready = 0; t->rk_state = 0;   // once per finish
   rc = hip_check(hipGetLastError(), "batched local map chain launch");
   if (rc != DVM_OK) return rc;
   // 4. ONE synchronisation, then every completed frame's outputs copied out of mapped memory by the pool threads
@@ -600,6 +623,216 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
     std::fprintf(stderr, "track local map batch of %d (%zu entries): pack + enqueue %.3f  wait %.3f  results out %.3f ms\n", count, T, ms(tp0, tp1),
                  ms(tp1, tp2), ms(tp2, clk::now()));
   }
+  return DVM_OK;
+}
+
+// ---- the other way into the second half: Tracking::TrackReferenceKeyFrame (src/Tracking.cc:2461-2520)
+namespace {
+// the upload block of one call, carved in the mapped staging buffer and at the same offsets in the device copy:
+// [pose_in 7 doubles][mvInvLevelSigma2 64][keyframe: desc n x 32, angle n, use n, claims n, pos n x 3][its mFeatVec: nodes, offsets, features]
+struct RefKfUpload {
+  double* pose; float* inv_sigma2; uint8_t* desc; float* angle; uint8_t *use, *claims; float* pos; int32_t *fv_node, *fv_off, *fv_feat; size_t bytes;
+};
+RefKfUpload carve_refkf_upload(uint8_t* base, int n, int nf, int nfeat) {
+  RefKfUpload u;
+  uint8_t* p = base;
+  u.pose = carve<double>(p, 7); u.inv_sigma2 = carve<float>(p, 64);
+  u.desc = carve<uint8_t>(p, (size_t)n * 32); u.angle = carve<float>(p, (size_t)n); u.use = carve<uint8_t>(p, (size_t)n);
+  u.claims = carve<uint8_t>(p, (size_t)n); u.pos = carve<float>(p, (size_t)n * 3);
+  u.fv_node = carve<int32_t>(p, (size_t)nf); u.fv_off = carve<int32_t>(p, (size_t)nf + 1); u.fv_feat = carve<int32_t>(p, (size_t)nfeat);
+  u.bytes = (size_t)(p - base);
+  return u;
+}
+}  // namespace
+
+int dvm_tracker_reserve_reference_keyframe(dvm_tracker* t, int max_kf_keypoints) {
+  if (!t || max_kf_keypoints < 1) return DVM_ERR_INVALID;
+  if (t->max_frames != 1) { set_error("dvm_tracker_reserve_reference_keyframe: a single-frame tracker (dvm_tracker_create)"); return DVM_ERR_STATE; }
+  if (max_kf_keypoints > kFrameCap) { set_error("dvm_tracker_reserve_reference_keyframe: more than 8 192 keyframe keypoints"); return DVM_ERR_CAPACITY; }
+  DVM_HIP(hipSetDevice(t->device));
+  if (t->d_rk) { hipFree(t->d_rk); t->d_rk = nullptr; }
+  if (t->hm_rk) { hipHostFree(t->hm_rk); t->hm_rk = nullptr; }
+  t->rk_cap = 0;
+  const size_t R = (size_t)max_kf_keypoints, K = (size_t)t->kp_cap;
+  t->rk_up_bytes = carve_refkf_upload(nullptr, (int)R, (int)R, (int)R).bytes;
+  // device: upload copy, the transform (word, node, weight), the FeatureVector CSR, counters, match, bin, res
+  const size_t dbytes = t->rk_up_bytes + 2 * pad256(K * 4) + pad256(K * 8) + 2 * pad256(K * 4) + pad256((K + 1) * 4) + pad256(kRefKfCnt * 4) +
+                        2 * pad256(K * 4) + pad256(8 * 4);
+  // mapped: upload staging, BowVector, FeatureVector, match, counters, outlier flags, edges / inliers / nmatchesMap, pose
+  const size_t mbytes = t->rk_up_bytes + pad256(K * 4) + pad256(K * 8) + 2 * pad256(K * 4) + pad256((K + 1) * 4) + pad256(K * 4) + pad256(8 * 4) +
+                        pad256(K) + 3 * pad256(4 * 4) + pad256(7 * 8);
+  if (hipMalloc(reinterpret_cast<void**>(&t->d_rk), dbytes) != hipSuccess) {
+    t->d_rk = nullptr; set_error("dvm_tracker_reserve_reference_keyframe: hipMalloc"); return DVM_ERR_CAPACITY;
+  }
+  if (hipHostMalloc(reinterpret_cast<void**>(&t->hm_rk), mbytes, hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer(reinterpret_cast<void**>(&t->hm_rk_dev), t->hm_rk, 0) != hipSuccess) {
+    if (t->hm_rk) hipHostFree(t->hm_rk);
+    t->hm_rk = nullptr; hipFree(t->d_rk); t->d_rk = nullptr;
+    set_error("dvm_tracker_reserve_reference_keyframe: mapped host memory"); return DVM_ERR_CAPACITY;
+  }
+  std::memset(t->hm_rk, 0, mbytes);
+  uint8_t* p = t->hm_rk + t->rk_up_bytes;
+  auto& r = t->rk;
+  r.bow_ids = carve<int32_t>(p, K); r.bow_vals = carve<double>(p, K); r.fv_node = carve<int32_t>(p, K); r.fv_feat = carve<int32_t>(p, K);
+  r.fv_off = carve<int32_t>(p, K + 1); r.match = carve<int32_t>(p, K); r.cnt = carve<int32_t>(p, 8); r.outlier = carve<uint8_t>(p, K);
+  r.nedges = carve<int32_t>(p, 4); r.n_inl = carve<int32_t>(p, 4); r.fin = carve<int32_t>(p, 4); r.pose = carve<double>(p, 7);
+  t->rk_cap = (int)R;
+  return DVM_OK;
+}
+
+int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, const dvm_ref_keyframe* kf, const dvm_track_refkf_params* p,
+                                 dvm_track_refkf_out* out, dvm_track_refkf_result* res) {
+  if (!t || !h || !voc || !kf || !p || !out || !res) return DVM_ERR_INVALID;
+  if (t->max_frames != 1 || !t->rk_state || t->rk_h != h || orb_result_serial(h) != t->rk_serial) {
+    set_error("dvm_track_reference_keyframe: not right after a dvm_track_begin or dvm_track_finish of one frame (single-frame tracker, same "
+              "extractor), or already run on that frame");
+    return DVM_ERR_STATE;
+  }
+  if (!t->d_rk) { set_error("dvm_track_reference_keyframe: no dvm_tracker_reserve_reference_keyframe on this tracker"); return DVM_ERR_STATE; }
+  const int form = t->rk_state;
+  if (!out->mp_out || !out->dropped || !out->outlier) return DVM_ERR_INVALID;
+  if (p->nlevels < 1 || p->nlevels > 64 || !p->inv_level_sigma2 || p->th_low < 0 || p->th_low > 255 || p->levelsup < 0 || p->min_matches < 0 ||
+      !(p->nnratio >= 0.0f)) {
+    set_error("dvm_track_reference_keyframe: bad parameters"); return DVM_ERR_INVALID;
+  }
+  if (form == 1 && !(p->bounds[1] > p->bounds[0] && p->bounds[3] > p->bounds[2])) {
+    set_error("dvm_track_reference_keyframe: form (a) builds the grid: empty frame bounds"); return DVM_ERR_INVALID;
+  }
+  if (vocab_device(voc) != t->device) { set_error("dvm_track_reference_keyframe: the vocabulary lives on another device"); return DVM_ERR_INVALID; }
+  // the keyframe: every index the device follows is checked here
+  const int n = kf->n, nf = kf->fv_n;
+  if (n < 0 || nf < 0) return DVM_ERR_INVALID;
+  if (n > t->rk_cap || nf > t->rk_cap) { set_error("dvm_track_reference_keyframe: more keyframe keypoints than reserved"); return DVM_ERR_CAPACITY; }
+  if (n && (!kf->kps_un || !kf->desc || !kf->mp || !kf->mp_pos || !kf->mp_nobs)) return DVM_ERR_INVALID;
+  if (nf && (!kf->fv_node || !kf->fv_off || !kf->fv_feat)) return DVM_ERR_INVALID;
+  const int nfeat = nf ? kf->fv_off[nf] : 0;
+  if (nf && kf->fv_off[0] != 0) return DVM_ERR_INVALID;
+  for (int a = 0; a < nf; a++) {
+    if (kf->fv_off[a + 1] < kf->fv_off[a] || (a && (uint32_t)kf->fv_node[a] <= (uint32_t)kf->fv_node[a - 1])) {
+      set_error("dvm_track_reference_keyframe: mFeatVec offsets must not decrease and its nodes must ascend (as unsigned)"); return DVM_ERR_INVALID;
+    }
+  }
+  if (nfeat > n) { set_error("dvm_track_reference_keyframe: mFeatVec lists more features than the keyframe has"); return DVM_ERR_INVALID; }
+  for (int k = 0; k < nfeat; k++)
+    if (kf->fv_feat[k] < 0 || kf->fv_feat[k] >= n) { set_error("dvm_track_reference_keyframe: mFeatVec names a keypoint outside the keyframe"); return DVM_ERR_INVALID; }
+  std::memset(res, 0, sizeof(*res));
+  t->rk_state = 0; t->lf.ready = 0; t->lf.batch_ready = 0;        // once per begin; the second half waits for this call's status
+  DVM_HIP(hipSetDevice(t->device));
+  hipStream_t s = (hipStream_t)dvm_orb_stream(h);
+  const dvm_keypoint* d_kps = nullptr; const uint8_t* d_desc = nullptr; const int32_t* d_n = nullptr; int ocap = 0;
+  int rc = dvm_orb_result_device(h, 0, &d_kps, &d_desc, &d_n, &ocap);
+  if (rc != DVM_OK) return rc;
+  if (ocap > t->kp_cap) { set_error("dvm_track_reference_keyframe: the extractor's keypoint capacity exceeds the tracker's"); return DVM_ERR_CAPACITY; }
+  // 1. the keyframe as the matcher and the optimiser read it: ONE asynchronous copy from the mapped staging block
+  const RefKfUpload up = carve_refkf_upload(t->hm_rk, n, nf, nfeat);
+  std::memcpy(up.pose, p->pose_in, 56);
+  std::memset(up.inv_sigma2, 0, 64 * 4);
+  std::memcpy(up.inv_sigma2, p->inv_level_sigma2, (size_t)p->nlevels * 4);
+  if (n) std::memcpy(up.desc, kf->desc, (size_t)n * 32);
+  for (int i = 0; i < n; i++) {
+    const int id = kf->mp[i];
+    const bool use = id >= 0 && !(kf->mp_bad && kf->mp_bad[i]);      // SearchByBoW: no map point or a bad one -> skipped (:247-252)
+    up.angle[i] = kf->kps_un[i].angle; up.use[i] = use ? 1 : 0;
+    up.claims[i] = id >= 0 && kf->mp_nobs[i] > 0 ? 1 : 0;
+    for (int k = 0; k < 3; k++) up.pos[3 * i + k] = id >= 0 ? kf->mp_pos[3 * i + k] : 0.0f;
+  }
+  if (nf) {
+    std::memcpy(up.fv_node, kf->fv_node, (size_t)nf * 4); std::memcpy(up.fv_off, kf->fv_off, ((size_t)nf + 1) * 4);
+    std::memcpy(up.fv_feat, kf->fv_feat, (size_t)nfeat * 4);
+  } else {
+    up.fv_off[0] = 0;
+  }
+  DVM_HIP(hipMemcpyAsync(t->d_rk, t->hm_rk, up.bytes, hipMemcpyHostToDevice, s));
+  const RefKfUpload dup = carve_refkf_upload(t->d_rk, n, nf, nfeat);
+  // 2. form (a): what dvm_track_finish does before its search -- mvKeysUn (Frame.cc:791-818) and AssignFeaturesToGrid
+  LocalFrame& f = t->lf;
+  const bool undist = form == 1 && p->dist && p->dist->k1 != 0.0f;
+  const dvm_keypoint_pod* d_un = f.d_un;
+  if (form == 1) {
+    const dvm_keypoint* un = d_kps;
+    if (undist) {
+      rc = dvm_undistort_keypoints(p->dist, d_kps, reinterpret_cast<dvm_keypoint*>(t->d_kps_un), ocap, 1, s);
+      if (rc != DVM_OK) return rc;
+      un = reinterpret_cast<const dvm_keypoint*>(t->d_kps_un);
+      if (out->kps_un) DVM_HIP(hipMemcpyAsync(t->m.kps_un, t->d_kps_un, (size_t)ocap * sizeof(dvm_keypoint_pod), hipMemcpyDeviceToHost, s));
+    }
+    rc = dvm_frame_build_batch(t->grid, 0, 1, un, ocap, d_desc, (int64_t)ocap * 32, d_n, p->bounds[0], p->bounds[1], p->bounds[2], p->bounds[3], s);
+    if (rc != DVM_OK) return rc;
+    d_un = reinterpret_cast<const dvm_keypoint_pod*>(un);
+  }
+  // 3. the chain: ComputeBoW (transform, then the BowVector / FeatureVector in LDS) -> SearchByBoW -> rotation check -> PoseOptimization's
+  //    edges in keypoint order -> k_pose_optimize seeded from pose_in -> outlier flags and nmatchesMap
+  uint8_t* q = t->d_rk + t->rk_up_bytes;
+  const size_t K = (size_t)t->kp_cap;
+  RefKfArgs A;
+  int32_t* word = carve<int32_t>(q, K); int32_t* node = carve<int32_t>(q, K); double* w = carve<double>(q, K);
+  A.word = word; A.node = node; A.w = w;
+  A.fv_node = carve<int32_t>(q, K); A.fv_feat = carve<int32_t>(q, K); A.fv_off = carve<int32_t>(q, K + 1); A.cnt = carve<int32_t>(q, kRefKfCnt);
+  A.match = carve<int32_t>(q, K); A.bin = carve<int32_t>(q, K); A.res = carve<int32_t>(q, 8);
+  auto& r = t->rk;
+  A.h_bow_ids = t->rkdev(r.bow_ids); A.h_bow_vals = t->rkdev(r.bow_vals); A.h_fv_node = t->rkdev(r.fv_node); A.h_fv_off = t->rkdev(r.fv_off);
+  A.h_fv_feat = t->rkdev(r.fv_feat); A.h_match = t->rkdev(r.match); A.h_cnt = t->rkdev(r.cnt);
+  A.kdesc = dup.desc; A.kangle = dup.angle; A.kuse = dup.use; A.kfv_node = dup.fv_node; A.kfv_off = dup.fv_off; A.kfv_feat = dup.fv_feat; A.kfv_n = nf;
+  vocab_launch_transform(voc, s, d_desc, ocap, d_n, p->levelsup, word, node, w);
+  launch_refkf_bow(s, A, d_n, ocap);
+  launch_refkf_search(s, A, d_un, d_desc, d_n, ocap, p->th_low, p->nnratio);
+  launch_refkf_settle(s, A, d_n, ocap, p->check_ori);
+  const TrackBatch TE{1, 0, (int64_t)ocap, nullptr, nullptr};
+  launch_track_gather(s, A.match, d_un, d_n, ocap, dup.pos, dup.inv_sigma2, p->nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges, A.res,
+                      p->min_matches, t->rkdev(r.nedges), TE);
+  ba_launch_pose_optimize(s, dup.pose, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, 1, p->cam.fx, p->cam.fy, p->cam.cx, p->cam.cy,
+                          t->rkdev(r.pose), t->d_edge_out, t->rkdev(r.n_inl), t->d_chi);
+  launch_track_finish(s, A.match, d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, dup.claims, t->rkdev(r.outlier), t->rkdev(r.fin), A.res, TE);
+  rc = hip_check(hipGetLastError(), "reference keyframe chain launch");
+  if (rc != DVM_OK) return rc;
+  // 4. ONE synchronisation (behind the download of the extraction in form (a))
+  int N = 0, mono = 0;
+  {
+    // (form (a) without kps but with kps_un and no distortion: mvKeysUn = mvKeys is downloaded into kps_un directly)
+    dvm_keypoint* kp = form != 1 ? nullptr : out->kps ? out->kps : undist ? nullptr : out->kps_un;
+    uint8_t* dp = form == 1 ? out->desc : nullptr;
+    const int cap = kp || dp ? out->cap : ocap;
+    rc = dvm_orb_download_batch(h, 1, &kp, &dp, &cap, &N, &mono);
+    if (rc != DVM_OK) return rc;
+    if (form == 1 && out->kps_un && kp != out->kps_un)
+      std::memcpy(out->kps_un, undist ? reinterpret_cast<const dvm_keypoint*>(t->m.kps_un) : out->kps, (size_t)N * sizeof(dvm_keypoint));
+  }
+  res->n = N; res->mono_index = mono;
+  res->n_bow = r.cnt[0]; res->n_fv = r.cnt[1]; res->nmatches_before_rotation = r.cnt[2]; res->nmatches = r.cnt[3];
+  if (out->bow_ids) std::memcpy(out->bow_ids, r.bow_ids, (size_t)res->n_bow * 4);
+  if (out->bow_vals) std::memcpy(out->bow_vals, r.bow_vals, (size_t)res->n_bow * 8);
+  if (out->fv_node) std::memcpy(out->fv_node, r.fv_node, (size_t)res->n_fv * 4);
+  if (out->fv_off) std::memcpy(out->fv_off, r.fv_off, ((size_t)res->n_fv + 1) * 4);
+  if (out->fv_feat) std::memcpy(out->fv_feat, r.fv_feat, (size_t)r.fv_off[res->n_fv] * 4);
+  // mvpMapPoints: SearchByBoW's matches, those PoseOptimization rejected dropped (Tracking.cc:2486-2516)
+  const bool few = res->nmatches < p->min_matches;
+  for (int j = 0; j < N; j++) {
+    const int a = r.match[j];
+    const int id = a >= 0 ? kf->mp[a] : -1;
+    const bool o = !few && id >= 0 && r.outlier[j];
+    out->mp_out[j] = o ? -1 : id; out->dropped[j] = o ? id : -1; out->outlier[j] = o ? 1 : 0;
+  }
+  if (few) {
+    res->status = DVM_TRACK_FEW_MATCHES;
+    std::memcpy(res->pose, p->pose_in, 56);
+  } else {
+    res->n_edges = r.nedges[0]; res->n_inliers = r.n_inl[0]; res->nmatches_map = r.fin[0]; res->nmatches_after = r.fin[1];
+    std::memcpy(res->pose, r.pose, 56);
+    res->status = res->nmatches_map < p->min_map ? DVM_TRACK_FEW_MAP_MATCHES : DVM_TRACK_COMPLETE;
+  }
+  for (int k = 0; k < 3; k++) res->Tcw.t[k] = (float)res->pose[k];
+  for (int k = 0; k < 4; k++) res->Tcw.q[k] = (float)res->pose[3 + k];
+  // what dvm_track_local_map runs on: the grid (slot 0) and mvKeysUn of the frame, this call's pose
+  if (form == 1) {
+    f.h = h; f.serial = orb_result_serial(h); f.n = N; f.ocap = ocap; f.nlevels = p->nlevels;
+    f.d_un = d_un; f.d_n = d_n;
+    std::memcpy(f.bounds, p->bounds, 16); std::memset(f.inv_sigma2, 0, sizeof(f.inv_sigma2));
+    std::memcpy(f.inv_sigma2, p->inv_level_sigma2, (size_t)p->nlevels * 4); f.cam = p->cam;
+    f.count = 1; f.kps_stride = ocap; f.ns.assign(1, N);
+  }
+  f.status.assign(1, res->status);
+  std::memcpy(f.pose, res->pose, 56);
+  f.ready = res->status == DVM_TRACK_COMPLETE; f.batch_ready = 0;
   return DVM_OK;
 }
 

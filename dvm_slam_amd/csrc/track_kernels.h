@@ -61,4 +61,27 @@ void launch_track_gather(hipStream_t s, const int32_t* assign, const dvm_keypoin
                          const int32_t* res, int min_matches, int32_t* n_edges_host, const TrackBatch& B);
 void launch_track_finish(hipStream_t s, int32_t* assign, const int32_t* d_n, int kp_cap, const int32_t* edge_kp, const int32_t* n_edges,
                          const uint8_t* edge_outlier, const uint8_t* q_claims, uint8_t* outlier, int32_t* out, const int32_t* res, const TrackBatch& B);
+
+// ---- the reference-keyframe chain (dvm_track_reference_keyframe): Frame::ComputeBoW -> SearchByBoW(KF, F) -> PoseOptimization
+constexpr int kRefKfCnt = 40;   // RefKfArgs::cnt entries: [0] n_bow [1] n_fv [2] matches before the rotation check [8, 38) rotation histogram
+struct RefKfArgs {
+  // the frame: k_vocab_transform's per-feature word / node / weight [cap]
+  const int32_t* word; const int32_t* node; const double* w;
+  int32_t *fv_node, *fv_off, *fv_feat;   // device: mFeatVec as CSR ([cap], [cap + 1], [cap])
+  int32_t* cnt;                          // device [kRefKfCnt]
+  int32_t* match;                        // device [cap]: the keyframe keypoint matched to frame keypoint j, or -1 (k_track_gather's assign)
+  int32_t* bin;                          // device [cap]: its rotation bin
+  int32_t* res;                          // device [8]: res[0] = nmatches, res[1] = 0 (what k_track_gather / k_track_finish read)
+  // mapped host memory: what the host reads after the one synchronisation
+  int32_t* h_bow_ids; double* h_bow_vals; int32_t *h_fv_node, *h_fv_off, *h_fv_feat; int32_t* h_match; int32_t* h_cnt;
+  // the keyframe (device copy of the upload)
+  const uint8_t* kdesc; const float* kangle; const uint8_t* kuse;   // [n]: descriptor, mvKeysUn angle, has a good map point
+  const int32_t *kfv_node, *kfv_off, *kfv_feat; int32_t kfv_n;      // its mFeatVec
+};
+// one workgroup: the frame's BowVector (mapped) and FeatureVector (device + mapped); the match state reset
+void launch_refkf_bow(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap);
+// SearchByBoW's matching: one wave per keyframe node; then the rotation check and res[] for the edge gather
+void launch_refkf_search(hipStream_t s, const RefKfArgs& A, const dvm_keypoint_pod* kps_un, const uint8_t* desc, const int32_t* d_n, int cap, int th_low,
+                         float nnratio);
+void launch_refkf_settle(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap, int check_ori);
 }  // namespace dvm

@@ -17,12 +17,28 @@
 #include "frustum_point.h"
 #include "match_kernels.h"
 #include "pose_f32.h"
+#include "rot_bin.h"
 #include "track_kernels.h"
 
 namespace dvm {
 
 namespace {
-constexpr int kHisto = 30;   // HISTO_LENGTH, ORBmatcher.cc:38
+constexpr int kHisto = kRotHisto;   // HISTO_LENGTH, ORBmatcher.cc:38
+
+// ComputeThreeMaxima (ORBmatcher.cc:1750-1802) over the bin counts, on one lane: the three fullest bins, the second and third dropped
+// below a tenth of the first
+__device__ void three_maxima(const int* hist, int* ind) {
+  int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+  for (int i = 0; i < kHisto; i++) {
+    const int sv = hist[i];
+    if (sv > max1) { max3 = max2; max2 = max1; max1 = sv; ind3 = ind2; ind2 = ind1; ind1 = i; }
+    else if (sv > max2) { max3 = max2; max2 = sv; ind3 = ind2; ind2 = i; }
+    else if (sv > max3) { max3 = sv; ind3 = i; }
+  }
+  if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+  else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
+  ind[0] = ind1; ind[1] = ind2; ind[2] = ind3;
+}
 }
 
 // One wave.  Queries are decided in blocks of 64, one per lane.  Inside a block a lane's choice depends on what the lanes before it
@@ -272,28 +288,14 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
     for (int q = tid; q < nq; q += 256) {
       const uint32_t r = s_qres[q];
       if (r == 0xFFFFFFFFu) continue;
-      float rot = q_angle[q] - kps[r].angle;
-      if (rot < 0.0f) rot += 360.0f;
-      int bin = (int)roundf(rot * (1.0f / (float)kHisto));
-      if (bin == kHisto) bin = 0;
+      const int bin = rot_bin(q_angle[q], kps[r].angle);
       atomicAdd(&s_rot[bin], 1);
       s_qres[q] = r | ((uint32_t)bin << 16);
     }
   }
   __syncthreads();
   // ComputeThreeMaxima (ORBmatcher.cc:1750-1802) on one lane, then the matches of the other bins are taken back (:1730-1745)
-  if (tid == 0) {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < kHisto; i++) {
-      const int sv = s_rot[i];
-      if (sv > max1) { max3 = max2; max2 = max1; max1 = sv; ind3 = ind2; ind2 = ind1; ind1 = i; }
-      else if (sv > max2) { max3 = max2; max2 = sv; ind3 = ind2; ind2 = i; }
-      else if (sv > max3) { max3 = sv; ind3 = i; }
-    }
-    if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
-    s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-  }
+  if (tid == 0) three_maxima(s_rot, s_ind);
   __syncthreads();
   int nmatched = 0, ndropped = 0;
   for (int q = tid; q < nq; q += 256) {
@@ -507,6 +509,237 @@ __global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointP
   if (tid == 0) { LQ.nq[0] = base; res_host[0] = s_cnt[1]; res_host[1] = s_cnt[0]; }
 }
 
+// ---- the reference-keyframe chain: Tracking::TrackReferenceKeyFrame (Tracking.cc:2461-2520) behind the extraction of the frame
+
+namespace {
+// exclusive prefix sum of v over the 1024 threads of a workgroup; *total = the sum.  s_wave: 16 ints of LDS (free again on return)
+__device__ int block_scan_1024(int v, int* s_wave, int* total) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int x = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(x, o);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) s_wave[wv] = x;
+  __syncthreads();
+  int base = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < 16; w++) {
+    const int c = s_wave[w];
+    if (w < wv) base += c;
+    all += c;
+  }
+  __syncthreads();
+  *total = all;
+  return base + x - v;
+}
+// ascending bitonic sort of keys[0 .. P) (P a power of two) by the whole workgroup
+__device__ void bitonic_sort(uint64_t* keys, int P) {
+  for (int k = 2; k <= P; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < P; i += blockDim.x) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const uint64_t a = keys[i], b = keys[ixj];
+          if ((a > b) == ((i & k) == 0)) { keys[i] = b; keys[ixj] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+// the runs of equal (key >> 32) among the first M sorted keys: run r starts at sorted position start and is run number r (ascending).
+// Each thread owns a contiguous chunk of positions and calls f(r, start) for the runs that start in it.  Returns the number of runs.
+template <class Fn>
+__device__ int for_each_run(const uint64_t* keys, int M, int* s_wave, Fn f) {
+  const int chunk = (M + 1023) / 1024;
+  const int b = min((int)threadIdx.x * chunk, M), e = min(b + chunk, M);
+  int heads = 0;
+  for (int i = b; i < e; i++) heads += (i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32)) ? 1 : 0;
+  int total = 0;
+  int r = block_scan_1024(heads, s_wave, &total);
+  for (int i = b; i < e; i++)
+    if (i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32)) f(r++, i);
+  return total;
+}
+}  // namespace
+
+// Frame::ComputeBoW's bookkeeping (TemplatedVocabulary::transform's TF_IDF branch, DBoW2 TemplatedVocabulary.h:1098-1138, as the host
+// mirror dvm_slam_amd/host/orb_vocabulary.cpp keeps it) on k_vocab_transform's per-feature results, in LDS by one workgroup:
+//   the features with weight > 0 only (a stopped word adds nothing, not even its node entry);
+//   BowVector: sort (word << 32 | feature); each word's weight is the sum of its features' weights added in feature order, the L1 norm
+//     the sum of |value| in ascending word order -- both sequential double additions, the order std::map gives the host -- then each
+//     value divided by the norm (correctly rounded double division);
+//   FeatureVector: sort ((unsigned)node << 32 | feature): nodes ascending as unsigned (node -1 last), features ascending inside a node.
+// It also resets the match state of the search behind it.  LDS: 16 B per entry of the sort (the capacity rounded up to a power of two).
+__global__ void __launch_bounds__(1024) k_refkf_bow(RefKfArgs A, const int32_t* __restrict__ d_n, int cap, int P) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t refkf_smem[];
+  uint64_t* keys = reinterpret_cast<uint64_t*>(refkf_smem);    // [P]
+  double* vals = reinterpret_cast<double*>(keys + P);          // [P]
+  __shared__ int s_wave[16];
+  __shared__ int s_m;
+  __shared__ double s_norm;
+  const int tid = threadIdx.x;
+  const int N = min(*d_n, cap);
+  for (int j = tid; j < cap; j += 1024) { A.match[j] = -1; A.bin[j] = -1; }
+  if (tid < kRefKfCnt) A.cnt[tid] = 0;
+  if (tid == 0) s_m = 0;
+  __syncthreads();
+  int m = 0;
+  for (int i = tid; i < P; i += 1024) {
+    const bool keep = i < N && A.w[i] > 0.0;
+    keys[i] = keep ? ((uint64_t)(uint32_t)A.word[i] << 32) | (uint32_t)i : ~0ull;
+    m += keep ? 1 : 0;
+  }
+  if (m) atomicAdd(&s_m, m);
+  __syncthreads();
+  const int M = s_m;
+  bitonic_sort(keys, P);
+  // BowVector: one thread per word adds its features' weights in feature order
+  const int n_bow = for_each_run(keys, M, s_wave, [&](int r, int start) {
+    const uint32_t word = (uint32_t)(keys[start] >> 32);
+    double v = A.w[(uint32_t)keys[start]];
+    for (int i = start + 1; i < M && (uint32_t)(keys[i] >> 32) == word; i++) v += A.w[(uint32_t)keys[i]];
+    vals[r] = v;
+    A.h_bow_ids[r] = (int32_t)word;
+  });
+  __syncthreads();
+  if (tid == 0) {
+    double norm = 0.0;
+    for (int r = 0; r < n_bow; r++) norm += fabs(vals[r]);
+    s_norm = norm;
+  }
+  __syncthreads();
+  const double norm = s_norm;
+  for (int r = tid; r < n_bow; r += 1024) A.h_bow_vals[r] = norm > 0.0 ? vals[r] / norm : vals[r];
+  __syncthreads();
+  // FeatureVector
+  for (int i = tid; i < P; i += 1024) {
+    const bool keep = i < N && A.w[i] > 0.0;
+    keys[i] = keep ? ((uint64_t)(uint32_t)A.node[i] << 32) | (uint32_t)i : ~0ull;
+  }
+  __syncthreads();
+  bitonic_sort(keys, P);
+  const int n_fv = for_each_run(keys, M, s_wave, [&](int r, int start) {
+    const int32_t nd = (int32_t)(uint32_t)(keys[start] >> 32);
+    A.fv_node[r] = nd; A.fv_off[r] = start;
+    A.h_fv_node[r] = nd; A.h_fv_off[r] = start;
+  });
+  for (int i = tid; i < M; i += 1024) {
+    const int32_t f = (int32_t)(uint32_t)keys[i];
+    A.fv_feat[i] = f; A.h_fv_feat[i] = f;
+  }
+  if (tid == 0) {
+    A.fv_off[n_fv] = M; A.h_fv_off[n_fv] = M;
+    A.cnt[0] = n_bow; A.cnt[1] = n_fv;
+  }
+}
+
+// ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) (ORBmatcher.cc:214-393, monocular) without a serial replay.  The reference walks the
+// nodes both FeatureVectors share in ascending order; inside a node it takes the keyframe's features in order (those without a map point
+// or with a bad one skipped), scans the node's frame features that no earlier match has taken (:265-266), keeps the smallest distance
+// (first in scan order wins) and the second smallest (duplicates counted), and takes the best when best <= TH_LOW and best < nnratio *
+// second.  A frame feature lies in exactly ONE node of the frame's FeatureVector, so what one node's matches take is never a candidate
+// of another node: the nodes are independent, and the reference's sequential walk is one sequential walk per node in any node order.
+// One wave per keyframe node: the node is found in the frame's list by binary search, the wave walks the node's keyframe features in
+// order and scans the frame features across its lanes (min of (distance << 20 | scan position); per lane the two smallest distances,
+// merged), so every decision sees exactly the claims the reference's walk has made by then.  The rotation histogram only counts, so its
+// global atomics may come in any order.  LDS: the claim flag of every frame keypoint (1 B each).
+// Known limit: a vocabulary with L - levelsup <= 0 puts every feature into node 0: one wave then walks the whole frame.
+__global__ void __launch_bounds__(256) k_refkf_search(RefKfArgs A, const dvm_keypoint_pod* __restrict__ kps_un, const uint8_t* __restrict__ desc,
+                                                      const int32_t* __restrict__ d_n, int cap, int th_low, float nnratio) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t refkf_smem[];
+  uint8_t* s_claim = refkf_smem;   // [cap]
+  for (int j = threadIdx.x; j < cap; j += 256) s_claim[j] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int a = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (a >= A.kfv_n) return;
+  const int N = min(*d_n, cap), n_fv = A.cnt[1];
+  const uint32_t node = (uint32_t)A.kfv_node[a];
+  int lo = 0, hi = n_fv;                  // the frame's nodes ascend as unsigned
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((uint32_t)A.fv_node[mid] < node) lo = mid + 1; else hi = mid;
+  }
+  if (lo >= n_fv || (uint32_t)A.fv_node[lo] != node) return;
+  const int fb = A.fv_off[lo], fe = A.fv_off[lo + 1];
+  for (int k = A.kfv_off[a]; k < A.kfv_off[a + 1]; k++) {
+    const int r = A.kfv_feat[k];          // (the host checked 0 <= r < n)
+    if (!A.kuse[r]) continue;
+    uint32_t w[8];
+    {
+      const uint4* q = reinterpret_cast<const uint4*>(A.kdesc + (size_t)r * 32);
+      const uint4 q0 = q[0], q1 = q[1];
+      w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w; w[4] = q1.x; w[5] = q1.y; w[6] = q1.z; w[7] = q1.w;
+    }
+    uint32_t best = 0xFFFFFFFFu;
+    int d1 = 256, d2 = 256;
+    for (int p = fb + lane; p < fe; p += 64) {
+      const int j = A.fv_feat[p];
+      if (j >= N || s_claim[j]) continue;
+      const uint4* td = reinterpret_cast<const uint4*>(desc + (size_t)j * 32);
+      const uint4 x = td[0], y = td[1];
+      const int d = __popc(x.x ^ w[0]) + __popc(x.y ^ w[1]) + __popc(x.z ^ w[2]) + __popc(x.w ^ w[3]) + __popc(y.x ^ w[4]) + __popc(y.y ^ w[5]) +
+                    __popc(y.z ^ w[6]) + __popc(y.w ^ w[7]);
+      best = min(best, ((uint32_t)d << 20) | (uint32_t)(p - fb));
+      if (d < d1) { d2 = d1; d1 = d; }
+      else if (d < d2) d2 = d;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {     // the two smallest of two ascending pairs: min(a1, b1), min(max(a1, b1), min(a2, b2))
+      best = min(best, (uint32_t)__shfl_xor((int)best, o));
+      const int od1 = __shfl_xor(d1, o), od2 = __shfl_xor(d2, o);
+      d2 = min(max(d1, od1), min(d2, od2));
+      d1 = min(d1, od1);
+    }
+    const int bd = (int)(best >> 20);
+    if (bd <= th_low && (float)bd < nnratio * (float)d2) {
+      const int j = A.fv_feat[fb + (int)(best & 0xFFFFFu)];
+      if (lane == 0) {
+        s_claim[j] = 1;
+        const int bin = rot_bin(A.kangle[r], kps_un[j].angle);
+        A.match[j] = r; A.bin[j] = bin;
+        if (bin >= 0 && bin < kHisto) atomicAdd(&A.cnt[8 + bin], 1);     // (angles outside [0, 360) fall outside the histogram)
+        atomicAdd(&A.cnt[2], 1);
+      }
+    }
+  }
+}
+
+// the rotation check of SearchByBoW (:372-387): ComputeThreeMaxima, the matches of the other bins taken back; res[0] = nmatches for the
+// edge gather, the final matches to mapped memory.  One workgroup.
+__global__ void __launch_bounds__(256) k_refkf_settle(RefKfArgs A, const int32_t* __restrict__ d_n, int cap, int check_ori) {
+  __shared__ int s_rot[kHisto];
+  __shared__ int s_ind[3];
+  __shared__ int s_nd[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int N = min(*d_n, cap);
+  if (tid < kHisto) s_rot[tid] = A.cnt[8 + tid];
+  __syncthreads();
+  if (tid == 0) three_maxima(s_rot, s_ind);
+  __syncthreads();
+  int nd = 0;
+  for (int j = tid; j < cap; j += 256) {
+    int m = j < N ? A.match[j] : -1;
+    if (m >= 0 && check_ori) {
+      const int bin = A.bin[j];
+      if (bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) { m = -1; nd++; A.match[j] = -1; }
+    }
+    if (j < N) A.h_match[j] = m;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) nd += __shfl_xor(nd, o);
+  if (lane == 0) s_nd[wave] = nd;
+  __syncthreads();
+  if (tid == 0) {
+    const int nm = A.cnt[2], nmatches = nm - (s_nd[0] + s_nd[1] + s_nd[2] + s_nd[3]);
+    A.res[0] = nmatches; A.res[1] = 0;
+    A.h_cnt[0] = A.cnt[0]; A.h_cnt[1] = A.cnt[1]; A.h_cnt[2] = nm; A.h_cnt[3] = nmatches;
+  }
+}
+
 size_t track_claims_lds(int kp_cap, int nq) { const size_t qp = ((size_t)nq + 63) & ~(size_t)63; return qp * 16 + (size_t)kp_cap * 9 + qp * 5 + 16; }
 
 void launch_track_claims(hipStream_t s, const uint32_t* ranked, const uint8_t* q_claims, const float* q_angle, int nq, const TrackRequery& rq,
@@ -540,6 +773,22 @@ void launch_track_gather(hipStream_t s, const int32_t* assign, const dvm_keypoin
 void launch_track_finish(hipStream_t s, int32_t* assign, const int32_t* d_n, int kp_cap, const int32_t* edge_kp, const int32_t* n_edges,
                          const uint8_t* edge_outlier, const uint8_t* q_claims, uint8_t* outlier, int32_t* out, const int32_t* res, const TrackBatch& B) {
   hipLaunchKernelGGL(k_track_finish, dim3(B.count), dim3(256), 0, s, assign, d_n, kp_cap, edge_kp, n_edges, edge_outlier, q_claims, outlier, out, res, B);
+}
+
+void launch_refkf_bow(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap) {
+  int P = 1;
+  while (P < cap) P <<= 1;
+  const size_t lds = (size_t)P * 16;
+  if (lds > 48 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_refkf_bow), (int)lds);
+  hipLaunchKernelGGL(k_refkf_bow, dim3(1), dim3(1024), lds, s, A, d_n, cap, P);
+}
+void launch_refkf_search(hipStream_t s, const RefKfArgs& A, const dvm_keypoint_pod* kps_un, const uint8_t* desc, const int32_t* d_n, int cap, int th_low,
+                         float nnratio) {
+  if (A.kfv_n < 1) return;
+  hipLaunchKernelGGL(k_refkf_search, dim3((A.kfv_n + 3) / 4), dim3(256), (size_t)cap, s, A, kps_un, desc, d_n, cap, th_low, nnratio);
+}
+void launch_refkf_settle(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap, int check_ori) {
+  hipLaunchKernelGGL(k_refkf_settle, dim3(1), dim3(256), 0, s, A, d_n, cap, check_ori);
 }
 
 }  // namespace dvm

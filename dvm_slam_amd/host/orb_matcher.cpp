@@ -2,6 +2,7 @@
 #include "orb_matcher.h"
 
 #include "../csrc/pose_f32.h"
+#include "../csrc/rot_bin.h"
 
 #include <algorithm>
 #include <atomic>
@@ -387,14 +388,8 @@ int ORBmatcher::SearchByProjection(FrameView& F, const TrackedPointPOD* MPs, int
 // query claimed meanwhile is re-evaluated over its (short) candidate list.
 // --------------------------------------------------------------------------------------------------------------------
 namespace {
-int RotBin(float a1, float a2) {
-  const float factor = 1.0f / ORBmatcher::HISTO_LENGTH;
-  float rot = a1 - a2;
-  if (rot < 0.0) rot += 360.0f;
-  int bin = (int)std::round(rot * factor);
-  if (bin == ORBmatcher::HISTO_LENGTH) bin = 0;
-  return bin;
-}
+static_assert(ORBmatcher::HISTO_LENGTH == dvm::kRotHisto, "one histogram length");
+int RotBin(float a1, float a2) { return dvm::rot_bin(a1, a2); }   // (csrc/rot_bin.h: the device chains evaluate the same expression)
 int LowerBound(const FeatureVectorView& fv, int from, int key) { return (int)(std::lower_bound(fv.node + from, fv.node + fv.n, key) - fv.node); }
 
 // Walk two FeatureVectors like the while loops of :232-364 / :735-818 / :890-1031 and call f(a, b) for every common node.

@@ -590,7 +590,7 @@ typedef struct {
   int32_t th_high, check_ori;      /* ORBmatcher::TH_HIGH (100), mbCheckOrientation */
   int32_t min_matches;             /* 20 (Tracking.cc:2616) */
 } dvm_track_queries;
-enum { DVM_TRACK_COMPLETE = 0, DVM_TRACK_FEW_MATCHES = 1, DVM_TRACK_REPLAY_ON_HOST = 2 };
+enum { DVM_TRACK_COMPLETE = 0, DVM_TRACK_FEW_MATCHES = 1, DVM_TRACK_REPLAY_ON_HOST = 2, DVM_TRACK_FEW_MAP_MATCHES = 3 };
 typedef struct {
   int32_t n, mono_index;           /* the extraction's keypoint count and monoIndex */
   int32_t status;                  /* DVM_TRACK_COMPLETE; FEW_MATCHES: nmatches < min_matches, no pose (search again with the doubled window:
@@ -695,6 +695,77 @@ typedef struct {
 } dvm_local_map_out;                              /* 24 bytes */
 int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_out* out,
                               dvm_track_local_result* res, int32_t* status);
+
+/* ---- The other way into TrackLocalMap, Tracking::TrackReferenceKeyFrame (src/Tracking.cc:2461-2520), as ONE device chain: taken by
+ * Tracking::Track (:1756-1765) when there is no motion model (no velocity yet, or within two frames of a relocalisation) or when
+ * TrackWithMotionModel failed.  Frame::ComputeBoW (DBoW2 transform, levelsup 4) -> ORBmatcher(0.7, true).SearchByBoW(mpReferenceKF, F)
+ * (src/ORBmatcher.cc:214-393) -> Optimizer::PoseOptimization seeded from mLastFrame.GetPose() (src/Optimizer.cc:744-1028) -> outlier
+ * matches dropped, nmatchesMap (:2486-2516).  The frame's descriptors and grid stay on the device; the keyframe goes up in one
+ * asynchronous copy; one synchronisation at the end.  Results equal dvm_orb_extract + dvmh_vocab_transform +
+ * dvmh_search_by_bow_kf_frame + dvm_pose_optimize composed in that order, bit for bit. */
+typedef struct {
+  int32_t n;                       /* mpReferenceKF->N */
+  const dvm_keypoint* kps_un;      /* [n] mvKeysUn (the angle is what SearchByBoW reads) */
+  const uint8_t* desc;             /* [n][32] mDescriptors */
+  const int32_t* mp;               /* [n] the caller's map-point id from GetMapPointMatches(), or -1 */
+  const float* mp_pos;             /* [n][3] GetWorldPos() of that point (read where mp >= 0) */
+  const int32_t* mp_nobs;          /* [n] Observations() */
+  const uint8_t* mp_bad;           /* [n] isBad(), or NULL */
+  int32_t fv_n;                    /* mFeatVec flattened as dvmh_feature_vector_view: fv_n nodes, ascending as unsigned */
+  const int32_t *fv_node, *fv_off, *fv_feat;   /* [fv_n], [fv_n + 1], [fv_off[fv_n]] */
+} dvm_ref_keyframe;                /* 88 bytes */
+typedef struct {
+  double pose_in[7];               /* mLastFrame.GetPose() widened to double (tx ty tz qx qy qz qw), as dvm_track_queries::pose_in */
+  float nnratio;                   /* 0.7 */
+  int32_t check_ori;               /* 1 */
+  int32_t th_low;                  /* ORBmatcher::TH_LOW (50) */
+  int32_t min_matches;             /* 15 (Tracking.cc:2470) */
+  int32_t min_map;                 /* 10 (Tracking.cc:2519) */
+  int32_t levelsup;                /* ComputeBoW's levelsup (4) */
+  float bounds[4];                 /* as dvm_track_queries: form (a) builds the grid with them */
+  const dvm_distortion* dist;      /* NULL or k1 == 0: mvKeysUn = mvKeys (form (a)) */
+  const float* inv_level_sigma2;   /* mvInvLevelSigma2, nlevels entries */
+  int32_t nlevels;
+  dvm_ba_camera cam;               /* fx fy cx cy of PoseOptimization's edges */
+} dvm_track_refkf_params;          /* 160 bytes */
+typedef struct {
+  dvm_keypoint* kps; uint8_t* desc; int32_t cap;   /* [cap] form (a): the extraction (as dvm_orb_extract); may be NULL in form (b) */
+  dvm_keypoint* kps_un;                            /* [cap] or NULL: mvKeysUn (form (a)) */
+  int32_t* mp_out;                                 /* [N] mvpMapPoints after the outlier drop: the caller's ids, or -1 */
+  int32_t* dropped;                                /* [N] the id whose match PoseOptimization rejected, or -1 (mbTrackInView /
+                                                      mnLastFrameSeen of :2491-2503) */
+  uint8_t* outlier;                                /* [N] mvbOutlier as PoseOptimization leaves it (before the drop resets it) */
+  int32_t* bow_ids; double* bow_vals;              /* [N] or NULL: mBowVec (n_bow entries, ascending word) */
+  int32_t *fv_node, *fv_off, *fv_feat;             /* [N], [N + 1], [N] or NULL: mFeatVec (n_fv nodes), as dvmh_vocab_transform */
+} dvm_track_refkf_out;             /* 96 bytes */
+typedef struct {
+  int32_t n, mono_index;           /* the extraction's keypoint count and monoIndex */
+  int32_t status;                  /* DVM_TRACK_COMPLETE; FEW_MATCHES: nmatches < min_matches (no optimisation, pose = pose_in);
+                                      FEW_MAP_MATCHES: nmatchesMap < min_map */
+  int32_t nmatches;                /* SearchByBoW's return value */
+  int32_t nmatches_before_rotation;
+  int32_t n_edges, n_inliers;      /* PoseOptimization: nInitialCorrespondences and its return value */
+  int32_t nmatches_after;          /* nmatches after the outlier drop */
+  int32_t nmatches_map;            /* nmatchesMap */
+  int32_t n_bow, n_fv;             /* entries of mBowVec, nodes of mFeatVec */
+  int32_t reserved;
+  double pose[7];                  /* the optimised Tcw (tx ty tz qx qy qz qw) */
+  dvm_se3f Tcw;                    /* the same as SetPose receives it */
+  int32_t reserved2;
+} dvm_track_refkf_result;          /* 136 bytes */
+/* Allocates the chain's working set for reference keyframes of up to max_kf_keypoints keypoints (the keyframe upload, the frame's BoW
+ * arrays, the match state), once; a single-frame tracker of at most 8 192 keypoints.  Called again, it replaces the working set;
+ * dvm_tracker_destroy frees it. */
+int dvm_tracker_reserve_reference_keyframe(dvm_tracker* t, int max_kf_keypoints);
+/* Accepted once per dvm_track_begin on a single-frame tracker (dvm_tracker_create), same tracker and extractor (otherwise DVM_ERR_STATE):
+ *   (a) right after dvm_track_begin, no finish: the no-motion-model case.  The call does what dvm_track_finish does before its search
+ *       (undistortion when k1 != 0, the grid) and returns kps / desc / kps_un as dvm_track_finish does;
+ *   (b) right after a dvm_track_finish of that frame, whatever its status: the motion-model-failed case.  Nothing of the first half's
+ *       matches or pose carries over.
+ * kf->n beyond the reservation: DVM_ERR_CAPACITY.  After DVM_TRACK_COMPLETE, dvm_track_local_map is accepted on the frame (the grid and
+ * mvKeysUn this call left, seeded from this call's pose); after any other status it is refused. */
+int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, const dvm_ref_keyframe* kf, const dvm_track_refkf_params* p,
+                                 dvm_track_refkf_out* out, dvm_track_refkf_result* res);
 
 /* Optimizer::OptimizeSim3 (Optimizer.cc:1960-2212), numerics for N correspondences gathered by the caller:
  * P1c / P2c = the matched map points in their own key frame's camera frame (R1w*P+t1w, R2w*P+t2w), obs1 / obs2 =
