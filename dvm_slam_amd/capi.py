@@ -1008,47 +1008,21 @@ class Tracker:
             fb.restype = C.c_int32
             fb.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
             check(fb(self.t, self.ext.h, img.ctypes.data, img.shape[0], img.shape[1], img.strides[0], int(lap[0]), int(lap[1])))
-        kps_kf = np.ascontiguousarray(kf["kps"], KP_DTYPE)
-        n = len(kps_kf)
-        keep = [kps_kf, np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32), np.ascontiguousarray(kf["mp"], np.int32),
-                np.ascontiguousarray(kf["pos"], np.float32).reshape(-1, 3), np.ascontiguousarray(kf["n_obs"], np.int32)]
-        bad = None if kf.get("bad") is None else np.ascontiguousarray(kf["bad"], np.uint8)
-        fv = [np.ascontiguousarray(kf["fv"][k], np.int32) for k in ("fv_nodes", "fv_off", "fv_feat")]
-        rk = RefKeyframe()
-        rk.n = n
-        rk.kps_un, rk.desc, rk.mp, rk.mp_pos, rk.mp_nobs = (a.ctypes.data if len(a) else None for a in keep)
-        rk.mp_bad = None if bad is None or not len(bad) else bad.ctypes.data
-        rk.fv_n = len(fv[0])
-        rk.fv_node, rk.fv_off, rk.fv_feat = (a.ctypes.data if len(a) else None for a in fv)
-        T = np.asarray(pose_last, np.float32).reshape(7)
-        pr = TrackRefKfParams()
-        pr.pose_in[:] = [float(v) for v in np.concatenate([T[4:7], T[0:4]]).astype(np.float64)]
-        pr.nnratio, pr.check_ori, pr.th_low, pr.min_matches, pr.min_map, pr.levelsup = float(nnratio), int(check_ori), int(th_low), int(min_matches), int(min_map), int(levelsup)
+        rk, keep = _ref_keyframe(kf)
+        pr, s2 = _refkf_params(pose_last, K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
         if bounds is not None:
             pr.bounds[:] = [float(v) for v in np.asarray(bounds, np.float32)]
         pr.dist = None if dist is None else C.cast(C.pointer(dist), vp)
-        s2 = np.ascontiguousarray(inv_sigma2, np.float32)
-        pr.inv_level_sigma2, pr.nlevels = s2.ctypes.data, len(s2)
-        Kf = np.asarray(K, np.float32)
-        pr.cam = BaCamera(*[float(v) for v in Kf[:4]], 0.0)
         kps = np.empty(cap, KP_DTYPE); kun = np.empty(cap, KP_DTYPE); desc = np.empty((cap, 32), np.uint8)
-        mp = np.empty(cap, np.int32); dropped = np.empty(cap, np.int32); outl = np.empty(cap, np.uint8)
-        bi = np.empty(cap, np.int32); bv = np.empty(cap, np.float64); fn = np.empty(cap, np.int32); fo = np.empty(cap + 1, np.int32)
-        ff = np.empty(cap, np.int32)
-        o = TrackRefKfOut()
+        o, arrs = _refkf_out(cap)
         o.kps, o.desc, o.cap, o.kps_un = kps.ctypes.data, desc.ctypes.data, cap, kun.ctypes.data
-        o.mp_out, o.dropped, o.outlier = mp.ctypes.data, dropped.ctypes.data, outl.ctypes.data
-        o.bow_ids, o.bow_vals, o.fv_node, o.fv_off, o.fv_feat = bi.ctypes.data, bv.ctypes.data, fn.ctypes.data, fo.ctypes.data, ff.ctypes.data
         res = TrackRefKfResult()
         f = self.L.dvm_track_reference_keyframe
         f.restype = C.c_int32
         f.argtypes = [vp, vp, vp, C.POINTER(RefKeyframe), C.POINTER(TrackRefKfParams), C.POINTER(TrackRefKfOut), C.POINTER(TrackRefKfResult)]
         check(f(self.t, self.ext.h, voc.h, C.byref(rk), C.byref(pr), C.byref(o), C.byref(res)))
         N = res.n
-        out = {k: getattr(res, k) for k in ("n", "mono_index", "status", "nmatches", "nmatches_before_rotation", "n_edges", "n_inliers",
-                                            "nmatches_after", "nmatches_map", "n_bow", "n_fv")}
-        out.update(mp=mp[:N], dropped=dropped[:N], outlier=outl[:N], bow_ids=bi[:res.n_bow], bow_vals=bv[:res.n_bow], fv_nodes=fn[:res.n_fv],
-                   fv_off=fo[:res.n_fv + 1], fv_feat=ff[:fo[res.n_fv]], pose=np.array(res.pose[:], np.float64), Tcw=np.array(res.Tcw[:], np.float32))
+        out = _refkf_result(res, arrs)
         if img is not None:
             out.update(kps=kps[:N], desc=desc[:N], kps_un=kun[:N])
         return out
@@ -1095,6 +1069,56 @@ class TrackRefKfResult(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n", "mono_index", "status", "nmatches", "nmatches_before_rotation", "n_edges", "n_inliers",
                                          "nmatches_after", "nmatches_map", "n_bow", "n_fv", "reserved")] + \
                [("pose", C.c_double * 7), ("Tcw", C.c_float * 7), ("reserved2", C.c_int32)]
+
+
+def _ref_keyframe(kf):
+    """dvm_ref_keyframe of a keyframe dict (Tracker.track_reference_keyframe's kf); returns it and the arrays it points into."""
+    keep = [np.ascontiguousarray(kf["kps"], KP_DTYPE), np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32), np.ascontiguousarray(kf["mp"], np.int32),
+            np.ascontiguousarray(kf["pos"], np.float32).reshape(-1, 3), np.ascontiguousarray(kf["n_obs"], np.int32)]
+    bad = None if kf.get("bad") is None else np.ascontiguousarray(kf["bad"], np.uint8)
+    fv = [np.ascontiguousarray(kf["fv"][k], np.int32) for k in ("fv_nodes", "fv_off", "fv_feat")]
+    rk = RefKeyframe()
+    rk.n = len(keep[0])
+    rk.kps_un, rk.desc, rk.mp, rk.mp_pos, rk.mp_nobs = (a.ctypes.data if len(a) else None for a in keep)
+    rk.mp_bad = None if bad is None or not len(bad) else bad.ctypes.data
+    rk.fv_n = len(fv[0])
+    rk.fv_node, rk.fv_off, rk.fv_feat = (a.ctypes.data if len(a) else None for a in fv)
+    return rk, (keep, bad, fv)
+
+
+def _refkf_params(pose_last, K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup):
+    """dvm_track_refkf_params (bounds zero, no distortion); returns it and the level table it points into."""
+    T = np.asarray(pose_last, np.float32).reshape(7)
+    pr = TrackRefKfParams()
+    pr.pose_in[:] = [float(v) for v in np.concatenate([T[4:7], T[0:4]]).astype(np.float64)]
+    pr.nnratio, pr.check_ori, pr.th_low, pr.min_matches, pr.min_map, pr.levelsup = float(nnratio), int(check_ori), int(th_low), int(min_matches), int(min_map), int(levelsup)
+    s2 = np.ascontiguousarray(inv_sigma2, np.float32)
+    pr.inv_level_sigma2, pr.nlevels = s2.ctypes.data, len(s2)
+    Kf = np.asarray(K, np.float32)
+    pr.cam = BaCamera(*[float(v) for v in Kf[:4]], 0.0)
+    return pr, s2
+
+
+def _refkf_out(cap):
+    """dvm_track_refkf_out for a frame of up to cap keypoints (kps / desc / kps_un unset) and the arrays it points into."""
+    arrs = dict(mp=np.empty(cap, np.int32), dropped=np.empty(cap, np.int32), outlier=np.empty(cap, np.uint8), bow_ids=np.empty(cap, np.int32),
+                bow_vals=np.empty(cap, np.float64), fv_nodes=np.empty(cap, np.int32), fv_off=np.empty(cap + 1, np.int32), fv_feat=np.empty(cap, np.int32))
+    o = TrackRefKfOut()
+    o.mp_out, o.dropped, o.outlier = arrs["mp"].ctypes.data, arrs["dropped"].ctypes.data, arrs["outlier"].ctypes.data
+    o.bow_ids, o.bow_vals = arrs["bow_ids"].ctypes.data, arrs["bow_vals"].ctypes.data
+    o.fv_node, o.fv_off, o.fv_feat = arrs["fv_nodes"].ctypes.data, arrs["fv_off"].ctypes.data, arrs["fv_feat"].ctypes.data
+    return o, arrs
+
+
+def _refkf_result(res, arrs):
+    """dvm_track_refkf_result and the outputs _refkf_out's arrays hold, as Tracker.track_reference_keyframe returns them."""
+    N, fo = res.n, arrs["fv_off"]
+    out = {k: getattr(res, k) for k in ("n", "mono_index", "status", "nmatches", "nmatches_before_rotation", "n_edges", "n_inliers",
+                                        "nmatches_after", "nmatches_map", "n_bow", "n_fv")}
+    out.update(mp=arrs["mp"][:N], dropped=arrs["dropped"][:N], outlier=arrs["outlier"][:N], bow_ids=arrs["bow_ids"][:res.n_bow],
+               bow_vals=arrs["bow_vals"][:res.n_bow], fv_nodes=arrs["fv_nodes"][:res.n_fv], fv_off=fo[:res.n_fv + 1], fv_feat=arrs["fv_feat"][:fo[res.n_fv]],
+               pose=np.array(res.pose[:], np.float64), Tcw=np.array(res.Tcw[:], np.float32))
+    return out
 
 
 class TrackIn(C.Structure):
@@ -1212,6 +1236,50 @@ class TrackerBatch:
                 d.update(mp=mp[:len(fm)], outlier=outl[:len(fm)], pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
                 if want_track_points:
                     d["track_pts"] = tp[:len(pts)]
+            out.append(d)
+        return out
+
+    def reserve_reference_keyframe(self, total):
+        """dvm_tracker_reserve_reference_keyframe_batch: the batched reference-keyframe chain's working set for `total` keyframe keypoints
+        per call (the sum over its keyframes of each one's size rounded up to 64), per-frame arrays for max_frames frames."""
+        f = self.L.dvm_tracker_reserve_reference_keyframe_batch
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32]
+        check(f(self.t, int(total)))
+
+    def track_reference_keyframe(self, voc, kfs, poses_last, K, inv_sigma2, nnratio=0.7, check_ori=True, th_low=50, min_matches=15, min_map=10,
+                                 levelsup=4):
+        """dvm_track_reference_keyframe_batch: Tracking::TrackReferenceKeyFrame of the frames of the last track() call that need it, as ONE
+        device chain.  kfs [count]: a keyframe dict as Tracker.track_reference_keyframe takes it, or None for a frame that does not run;
+        poses_last [count]: mLastFrame.GetPose() as 7 floats (qx, qy, qz, qw, t), read where kfs[b] is not None.  Returns one dict per frame:
+        status (the chain's for a frame that ran, else the first half's: zero counters, no arrays) and, for a frame that ran, what
+        Tracker.track_reference_keyframe returns in form (b)."""
+        count = len(kfs)
+        assert len(poses_last) == count
+        cap = self.ext.cap
+        kfp = (C.POINTER(RefKeyframe) * count)(); prs = (TrackRefKfParams * count)(); outs = (TrackRefKfOut * count)()
+        res = (TrackRefKfResult * count)(); status = np.zeros(count, np.int32)
+        keep = []
+        for b in range(count):
+            if kfs[b] is None:
+                keep.append(None)
+                continue
+            rk, ka = _ref_keyframe(kfs[b])
+            pr, s2 = _refkf_params(poses_last[b], K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
+            o, arrs = _refkf_out(cap)
+            kfp[b] = C.pointer(rk); prs[b] = pr; outs[b] = o
+            keep.append((rk, ka, s2, arrs))
+        f = self.L.dvm_track_reference_keyframe_batch
+        f.restype = C.c_int32
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(f(self.t, self.ext.h, voc.h, count, kfp, prs, outs, res, _p(status)))
+        out = []
+        for b in range(count):
+            if keep[b] is None:
+                d = {k: getattr(res[b], k) for k in ("n", "mono_index", "nmatches", "nmatches_before_rotation", "n_edges", "n_inliers",
+                                                     "nmatches_after", "nmatches_map", "n_bow", "n_fv")}
+            else:
+                d = _refkf_result(res[b], keep[b][3])
+            d["status"] = int(status[b])
             out.append(d)
         return out
 

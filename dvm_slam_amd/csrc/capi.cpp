@@ -940,11 +940,13 @@ int dvm_vocab_create(int device, int n_nodes, const int32_t* child_off, const in
 
 }  // extern "C"
 // for the chains of other translation units (track.cpp): the transform of the device features [cap][32] whose count is on the device
+// (run: a batch -- frame run[r] for r < nrun, its features at b * feat_stride bytes, its outputs at b * cap, its count at d_n[b])
 namespace dvm {
 int vocab_device(const dvm_vocab* v) { return v->device; }
 void vocab_launch_transform(const dvm_vocab* v, hipStream_t s, const uint8_t* d_feat, int cap, const int32_t* d_n, int levelsup, int32_t* word_id,
-                            int32_t* node_id, double* weight) {
-  launch_vocab_transform(s, v->child_off, v->children, v->desc, v->weight, v->word_id, v->L, d_feat, cap, levelsup, word_id, node_id, weight, d_n);
+                            int32_t* node_id, double* weight, const int32_t* run, int nrun, int64_t feat_stride) {
+  launch_vocab_transform(s, v->child_off, v->children, v->desc, v->weight, v->word_id, v->L, d_feat, cap, levelsup, word_id, node_id, weight, d_n,
+                         run, nrun, feat_stride);
 }
 }  // namespace dvm
 extern "C" {

@@ -826,9 +826,14 @@ __global__ void __launch_bounds__(256) k_vocab_transform(const int32_t* __restri
                                                          const int32_t* __restrict__ word_id, int L, const uint8_t* __restrict__ feat,
                                                          int n, int levelsup, int32_t* __restrict__ out_word,
                                                          int32_t* __restrict__ out_node, double* __restrict__ out_weight,
-                                                         const int32_t* __restrict__ d_n) {
+                                                         const int32_t* __restrict__ d_n, const int32_t* __restrict__ run,
+                                                         int64_t feat_stride) {
   const int lane = threadIdx.x & 15;
   const int f = blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (run) {     // a batch: frame run[blockIdx.y], its features at b * feat_stride bytes, its outputs and count at b * n / b
+    const int b = run[blockIdx.y];
+    feat += (size_t)b * feat_stride; out_word += (size_t)b * n; out_node += (size_t)b * n; out_weight += (size_t)b * n; d_n += b;
+  }
   if (d_n) n = min(n, *d_n);     // (a count still on the device: n is then the capacity the grid covers)
   if (f >= n) return;
   uint32_t w[8];
@@ -868,10 +873,11 @@ __global__ void __launch_bounds__(256) k_vocab_transform(const int32_t* __restri
 }
 void launch_vocab_transform(hipStream_t s, const int32_t* child_off, const int32_t* children, const uint8_t* node_desc,
                             const double* weight, const int32_t* word_id, int L, const uint8_t* feat, int n, int levelsup,
-                            int32_t* out_word, int32_t* out_node, double* out_weight, const int32_t* d_n) {
-  if (n > 0)
-    hipLaunchKernelGGL(k_vocab_transform, dim3((n + 15) / 16), dim3(256), 0, s, child_off, children, node_desc, weight, word_id, L,
-                       feat, n, levelsup, out_word, out_node, out_weight, d_n);
+                            int32_t* out_word, int32_t* out_node, double* out_weight, const int32_t* d_n, const int32_t* run, int nrun,
+                            int64_t feat_stride) {
+  if (n > 0 && nrun > 0)
+    hipLaunchKernelGGL(k_vocab_transform, dim3((n + 15) / 16, run ? nrun : 1), dim3(256), 0, s, child_off, children, node_desc, weight, word_id, L,
+                       feat, n, levelsup, out_word, out_node, out_weight, d_n, run, feat_stride);
 }
 
 }  // namespace dvm

@@ -33,9 +33,10 @@
 using namespace dvm;
 
 // what the second half runs on: set by a dvm_track_finish[_batch] that returned DVM_OK, cleared by any begin / finish and by the second
-// half itself.  ready: one frame that returned DVM_TRACK_COMPLETE (dvm_track_local_map); batch_ready: any finish (dvm_track_local_map_batch)
+// half itself.  ready: one frame that returned DVM_TRACK_COMPLETE (dvm_track_local_map); batch_ready: any finish (dvm_track_local_map_batch);
+// rkb_ready: any finish, until dvm_track_reference_keyframe_batch, the single call or the second half runs on it
 struct LocalFrame {
-  int ready = 0, batch_ready = 0;
+  int ready = 0, batch_ready = 0, rkb_ready = 0;
   dvm_orb* h = nullptr; uint64_t serial = 0;     // the extractor and which of its extractions the frame is
   int n = 0, ocap = 0, nlevels = 0;
   const dvm_keypoint_pod* d_un = nullptr; const int32_t* d_n = nullptr;   // mvKeysUn on the device, the keypoint count
@@ -44,6 +45,9 @@ struct LocalFrame {
   int count = 0; int64_t kps_stride = 0;          // the finish's frames: frame b's mvKeysUn at b * kps_stride, its count at d_n[b]
   std::vector<int32_t> ns, status;                // per frame: keypoints, the first half's status
   double pose[7] = {};                            // ready: the pose dvm_track_local_map starts from (the finish's, or the reference-keyframe chain's)
+  std::vector<double> poses;                      // [count][7]: the poses dvm_track_local_map_batch starts from (the same choice per frame)
+  std::vector<int32_t> monos;                     // per frame: monoIndex of the extraction
+  const uint8_t* d_desc = nullptr; int64_t desc_stride = 0;   // the frames' descriptors on the device: frame b's at b * desc_stride
 };
 
 struct dvm_tracker {
@@ -90,13 +94,21 @@ struct dvm_tracker {
     int32_t *bow_ids, *fv_node, *fv_off, *fv_feat, *match, *cnt, *nedges, *n_inl, *fin; double *bow_vals, *pose; uint8_t* outlier;
   } rk;
   template <class T> T* rkdev(T* host_ptr) const { return reinterpret_cast<T*>(hm_rk_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm_rk)); }
+  // ---- the same for the frames of a batched finish (dvm_track_reference_keyframe_batch): working set of
+  //      dvm_tracker_reserve_reference_keyframe_batch; per-frame arrays for max_frames frames at the extractor's capacity
+  int rkb_cap = 0;                 // keyframe keypoints of one call reserved (each keyframe's rounded up to 64)
+  uint8_t* d_rkb = nullptr;        // device: [upload copy][the frames' transforms, FeatureVectors and match state]
+  uint8_t *hm_rkb = nullptr, *hm_rkb_dev = nullptr;   // mapped: [upload staging][results]
+  size_t rkb_up_bytes = 0;
+  RefKfMapped rkb;                 // [max_frames] slices (fv_off: kp_cap + 1 per frame, cnt: 8 per frame)
+  template <class T> T* rkbdev(T* host_ptr) const { return reinterpret_cast<T*>(hm_rkb_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm_rkb)); }
 };
 
 namespace dvm {
 uint64_t orb_result_serial(const dvm_orb* h);   // capi.cpp: which extraction the handle's result holds
 int vocab_device(const dvm_vocab* v);           // capi.cpp: the vocabulary's device and its transform of device features (count on the device)
 void vocab_launch_transform(const dvm_vocab* v, hipStream_t s, const uint8_t* d_feat, int cap, const int32_t* d_n, int levelsup, int32_t* word_id,
-                            int32_t* node_id, double* weight);
+                            int32_t* node_id, double* weight, const int32_t* run = nullptr, int nrun = 1, int64_t feat_stride = 0);
 }
 
 namespace {
@@ -170,6 +182,8 @@ void dvm_tracker_destroy(dvm_tracker* t) {
   if (t->hm_lm) hipHostFree(t->hm_lm);
   if (t->d_rk) hipFree(t->d_rk);
   if (t->hm_rk) hipHostFree(t->hm_rk);
+  if (t->d_rkb) hipFree(t->d_rkb);
+  if (t->hm_rkb) hipHostFree(t->hm_rkb);
   if (t->cev) hipEventDestroy(t->cev);
   if (t->cstream) hipStreamDestroy(t->cstream);
   if (t->hm) hipHostFree(t->hm);
@@ -179,7 +193,7 @@ void dvm_tracker_destroy(dvm_tracker* t) {
 int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_batch: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0; t->rk_state = 0;
+  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0; t->lf.rkb_ready = 0; t->rk_state = 0;
   const int rc = dvm_orb_extract_batch_host(h, imgs, count, rows, cols, stride, frame_stride, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
@@ -189,7 +203,7 @@ int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int c
 int dvm_track_begin_staged(dvm_tracker* t, dvm_orb* h, int count, int rows, int cols, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_staged: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0; t->rk_state = 0;
+  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0; t->lf.rkb_ready = 0; t->rk_state = 0;
   const int rc = dvm_orb_extract_staged(h, count, rows, cols, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
@@ -202,7 +216,7 @@ int dvm_track_begin(dvm_tracker* t, dvm_orb* h, const uint8_t* img, int rows, in
 
 int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* qs, const dvm_track_frame_out* outs, dvm_track_result* res) {
   if (!t || !h || !qs || !outs || !res || count < 1) return DVM_ERR_INVALID;
-  t->lf.ready = 0; t->lf.batch_ready = 0; t->rk_state = 0;
+  t->lf.ready = 0; t->lf.batch_ready = 0; t->lf.rkb_ready = 0; t->rk_state = 0;
   if (t->begun != count) { set_error("dvm_track_finish: no matching dvm_track_begin on this tracker"); return DVM_ERR_STATE; }
   const dvm_track_queries& q0 = qs[0];
   int nq_max = 0;
@@ -327,13 +341,15 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
   }
   {     // what the second half runs on: the frames' grids (slots 0..count-1) and mvKeysUn
     LocalFrame& f = t->lf;
-    f.ready = count == 1 && res[0].status == DVM_TRACK_COMPLETE; f.batch_ready = 1;
+    f.ready = count == 1 && res[0].status == DVM_TRACK_COMPLETE; f.batch_ready = 1; f.rkb_ready = 1;
     f.h = h; f.serial = orb_result_serial(h); f.n = res[0].n; f.ocap = ocap; f.nlevels = q0.nlevels;
     f.d_un = reinterpret_cast<const dvm_keypoint_pod*>(d_un); f.d_n = d_n;
     std::memcpy(f.bounds, q0.bounds, 16); std::memcpy(f.inv_sigma2, q0.inv_level_sigma2, (size_t)q0.nlevels * 4); f.cam = q0.cam;
     f.count = count; f.kps_stride = kps_stride; f.ns.resize((size_t)count); f.status.resize((size_t)count);
-    for (int b = 0; b < count; b++) { f.ns[b] = res[b].n; f.status[b] = res[b].status; }
+    f.monos.resize((size_t)count); f.poses.assign(m.pose_out, m.pose_out + 7 * (size_t)count);
+    for (int b = 0; b < count; b++) { f.ns[b] = res[b].n; f.status[b] = res[b].status; f.monos[b] = res[b].mono_index; }
     std::memcpy(f.pose, m.pose_out, 56);
+    f.d_desc = d_desc; f.desc_stride = desc_stride;
   }
   if (count == 1 && t->max_frames == 1) { t->rk_state = 2; t->rk_h = h; t->rk_serial = orb_result_serial(h); }   // (whatever the status)
   return DVM_OK;
@@ -484,7 +500,7 @@ int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, 
                           t->lmdev(r.pose), t->d_edge_out, t->lmdev(r.n_inl), t->d_chi);
   launch_track_finish(s, t->d_assign, f.d_n, f.ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmdev(r.outlier), t->lmdev(r.fin),
                       d_lres, TE);
-  f.ready = 0; f.batch_ready = 0; t->rk_state = 0;   // once per finish
+  f.ready = 0; f.batch_ready = 0; f.rkb_ready = 0; t->rk_state = 0;   // once per finish
   rc = hip_check(hipGetLastError(), "local map chain launch");
   if (rc != DVM_OK) return rc;
   // 7. ONE synchronisation: everything the host reads was written to mapped memory by the kernels
@@ -529,7 +545,7 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
   }
   if (T > (size_t)t->lm_cap) { set_error("dvm_track_local_map_batch: more local map points than reserved (each frame's rounded up to 64)"); return DVM_ERR_CAPACITY; }
   for (int b = 0; b < count; b++) { std::memset(&res[b], 0, sizeof(res[b])); status[b] = f.status[b]; }
-  if (!live) { f.ready = 0; f.batch_ready = 0; return DVM_OK; }
+  if (!live) { f.ready = 0; f.batch_ready = 0; f.rkb_ready = 0; return DVM_OK; }
   const int ocap = f.ocap;
   const size_t Tc = std::max(T, (size_t)64);
   const LocalUploadBatch up = carve_upload_batch(t->hm_lm, count, Tc, (size_t)ocap);
@@ -545,7 +561,7 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
   HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {       // (32 tables of 3 000 points: 7 MB)
     const bool go = f.status[b] == DVM_TRACK_COMPLETE;
     int32_t* fm = up.frame_mp + b * (size_t)ocap;
-    std::memcpy(up.pose + 7 * b, t->m.pose_out + 7 * b, 56);
+    std::memcpy(up.pose + 7 * b, f.poses.data() + 7 * b, 56);    // the finish's pose, or the reference-keyframe chain's
     up.fa[b] = LocalFrameArgs{nb[b], go && in[b].far_points ? 1 : 0, go ? in[b].th : 1.0f, go ? in[b].th_far : 0.0f};
     up.qoff[b] = qoff[b]; up.skip_on[b] = 1;
     if (go) {
@@ -596,7 +612,7 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
                           t->lmdev(r.pose), t->d_edge_out, t->lmdev(r.n_inl), t->d_chi);
   launch_track_finish(s, t->d_assign, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmdev(r.outlier), t->lmdev(r.fin),
                       d_lres, TE);
-  f.ready = 0; f.batch_ready = 0; t->rk_state = 0;   // once per finish
+  f.ready = 0; f.batch_ready = 0; f.rkb_ready = 0; t->rk_state = 0;   // once per finish
   rc = hip_check(hipGetLastError(), "batched local map chain launch");
   if (rc != DVM_OK) return rc;
   // 4. ONE synchronisation, then every completed frame's outputs copied out of mapped memory by the pool threads
@@ -642,6 +658,34 @@ RefKfUpload carve_refkf_upload(uint8_t* base, int n, int nf, int nfeat) {
   u.fv_node = carve<int32_t>(p, (size_t)nf); u.fv_off = carve<int32_t>(p, (size_t)nf + 1); u.fv_feat = carve<int32_t>(p, (size_t)nfeat);
   u.bytes = (size_t)(p - base);
   return u;
+}
+// the checks of dvm_track_reference_keyframe on one frame's keyframe, parameters and outputs (form (b)); cap: keypoints per keyframe
+int check_refkf_frame(const char* fn, const dvm_ref_keyframe* kf, const dvm_track_refkf_params* p, const dvm_track_refkf_out* out, int cap) {
+  char msg[256];
+  if (!out->mp_out || !out->dropped || !out->outlier) return DVM_ERR_INVALID;
+  if (p->nlevels < 1 || p->nlevels > 64 || !p->inv_level_sigma2 || p->th_low < 0 || p->th_low > 255 || p->levelsup < 0 || p->min_matches < 0 ||
+      !(p->nnratio >= 0.0f)) {
+    std::snprintf(msg, sizeof msg, "%s: bad parameters", fn); set_error(msg); return DVM_ERR_INVALID;
+  }
+  const int n = kf->n, nf = kf->fv_n;
+  if (n < 0 || nf < 0) return DVM_ERR_INVALID;
+  if (n > cap || nf > cap) { std::snprintf(msg, sizeof msg, "%s: more keyframe keypoints than reserved", fn); set_error(msg); return DVM_ERR_CAPACITY; }
+  if (n && (!kf->kps_un || !kf->desc || !kf->mp || !kf->mp_pos || !kf->mp_nobs)) return DVM_ERR_INVALID;
+  if (nf && (!kf->fv_node || !kf->fv_off || !kf->fv_feat)) return DVM_ERR_INVALID;
+  const int nfeat = nf ? kf->fv_off[nf] : 0;
+  if (nf && kf->fv_off[0] != 0) return DVM_ERR_INVALID;
+  for (int a = 0; a < nf; a++) {
+    if (kf->fv_off[a + 1] < kf->fv_off[a] || (a && (uint32_t)kf->fv_node[a] <= (uint32_t)kf->fv_node[a - 1])) {
+      std::snprintf(msg, sizeof msg, "%s: mFeatVec offsets must not decrease and its nodes must ascend (as unsigned)", fn); set_error(msg);
+      return DVM_ERR_INVALID;
+    }
+  }
+  if (nfeat > n) { std::snprintf(msg, sizeof msg, "%s: mFeatVec lists more features than the keyframe has", fn); set_error(msg); return DVM_ERR_INVALID; }
+  for (int k = 0; k < nfeat; k++)
+    if (kf->fv_feat[k] < 0 || kf->fv_feat[k] >= n) {
+      std::snprintf(msg, sizeof msg, "%s: mFeatVec names a keypoint outside the keyframe", fn); set_error(msg); return DVM_ERR_INVALID;
+    }
+  return DVM_OK;
 }
 }  // namespace
 
@@ -690,37 +734,19 @@ int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* vo
   }
   if (!t->d_rk) { set_error("dvm_track_reference_keyframe: no dvm_tracker_reserve_reference_keyframe on this tracker"); return DVM_ERR_STATE; }
   const int form = t->rk_state;
-  if (!out->mp_out || !out->dropped || !out->outlier) return DVM_ERR_INVALID;
-  if (p->nlevels < 1 || p->nlevels > 64 || !p->inv_level_sigma2 || p->th_low < 0 || p->th_low > 255 || p->levelsup < 0 || p->min_matches < 0 ||
-      !(p->nnratio >= 0.0f)) {
-    set_error("dvm_track_reference_keyframe: bad parameters"); return DVM_ERR_INVALID;
-  }
+  int rc = check_refkf_frame("dvm_track_reference_keyframe", kf, p, out, t->rk_cap);
+  if (rc != DVM_OK) return rc;
   if (form == 1 && !(p->bounds[1] > p->bounds[0] && p->bounds[3] > p->bounds[2])) {
     set_error("dvm_track_reference_keyframe: form (a) builds the grid: empty frame bounds"); return DVM_ERR_INVALID;
   }
   if (vocab_device(voc) != t->device) { set_error("dvm_track_reference_keyframe: the vocabulary lives on another device"); return DVM_ERR_INVALID; }
-  // the keyframe: every index the device follows is checked here
-  const int n = kf->n, nf = kf->fv_n;
-  if (n < 0 || nf < 0) return DVM_ERR_INVALID;
-  if (n > t->rk_cap || nf > t->rk_cap) { set_error("dvm_track_reference_keyframe: more keyframe keypoints than reserved"); return DVM_ERR_CAPACITY; }
-  if (n && (!kf->kps_un || !kf->desc || !kf->mp || !kf->mp_pos || !kf->mp_nobs)) return DVM_ERR_INVALID;
-  if (nf && (!kf->fv_node || !kf->fv_off || !kf->fv_feat)) return DVM_ERR_INVALID;
-  const int nfeat = nf ? kf->fv_off[nf] : 0;
-  if (nf && kf->fv_off[0] != 0) return DVM_ERR_INVALID;
-  for (int a = 0; a < nf; a++) {
-    if (kf->fv_off[a + 1] < kf->fv_off[a] || (a && (uint32_t)kf->fv_node[a] <= (uint32_t)kf->fv_node[a - 1])) {
-      set_error("dvm_track_reference_keyframe: mFeatVec offsets must not decrease and its nodes must ascend (as unsigned)"); return DVM_ERR_INVALID;
-    }
-  }
-  if (nfeat > n) { set_error("dvm_track_reference_keyframe: mFeatVec lists more features than the keyframe has"); return DVM_ERR_INVALID; }
-  for (int k = 0; k < nfeat; k++)
-    if (kf->fv_feat[k] < 0 || kf->fv_feat[k] >= n) { set_error("dvm_track_reference_keyframe: mFeatVec names a keypoint outside the keyframe"); return DVM_ERR_INVALID; }
+  const int n = kf->n, nf = kf->fv_n, nfeat = nf ? kf->fv_off[nf] : 0;
   std::memset(res, 0, sizeof(*res));
-  t->rk_state = 0; t->lf.ready = 0; t->lf.batch_ready = 0;        // once per begin; the second half waits for this call's status
+  t->rk_state = 0; t->lf.ready = 0; t->lf.batch_ready = 0; t->lf.rkb_ready = 0;   // once per begin; the second half waits for this call's status
   DVM_HIP(hipSetDevice(t->device));
   hipStream_t s = (hipStream_t)dvm_orb_stream(h);
   const dvm_keypoint* d_kps = nullptr; const uint8_t* d_desc = nullptr; const int32_t* d_n = nullptr; int ocap = 0;
-  int rc = dvm_orb_result_device(h, 0, &d_kps, &d_desc, &d_n, &ocap);
+  rc = dvm_orb_result_device(h, 0, &d_kps, &d_desc, &d_n, &ocap);
   if (rc != DVM_OK) return rc;
   if (ocap > t->kp_cap) { set_error("dvm_track_reference_keyframe: the extractor's keypoint capacity exceeds the tracker's"); return DVM_ERR_CAPACITY; }
   // 1. the keyframe as the matcher and the optimiser read it: ONE asynchronous copy from the mapped staging block
@@ -764,7 +790,7 @@ int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* vo
   //    edges in keypoint order -> k_pose_optimize seeded from pose_in -> outlier flags and nmatchesMap
   uint8_t* q = t->d_rk + t->rk_up_bytes;
   const size_t K = (size_t)t->kp_cap;
-  RefKfArgs A;
+  RefKfArgs A{};
   int32_t* word = carve<int32_t>(q, K); int32_t* node = carve<int32_t>(q, K); double* w = carve<double>(q, K);
   A.word = word; A.node = node; A.w = w;
   A.fv_node = carve<int32_t>(q, K); A.fv_feat = carve<int32_t>(q, K); A.fv_off = carve<int32_t>(q, K + 1); A.cnt = carve<int32_t>(q, kRefKfCnt);
@@ -833,6 +859,246 @@ int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* vo
   f.status.assign(1, res->status);
   std::memcpy(f.pose, res->pose, 56);
   f.ready = res->status == DVM_TRACK_COMPLETE; f.batch_ready = 0;
+  return DVM_OK;
+}
+
+
+// ---- TrackReferenceKeyFrame for the frames of a batched finish (dvm_track_reference_keyframe_batch)
+namespace {
+// the upload block of one call: [mvInvLevelSigma2 64][per frame: pose_in 7 doubles, keyframe offset, node count, res 8][run list][wg_base]
+// [keyframes: T entries, frame b's at qoff[b] -- desc x 32, angle, use, claims, pos x 3, mFeatVec nodes, features][mFeatVec offsets: T + count,
+// frame b's at qoff[b] + b]
+struct RefKfUploadBatch {
+  float* inv_sigma2; double* pose; int32_t *qoff, *kfv_n, *res, *run, *wg_base;
+  uint8_t* desc; float* angle; uint8_t *use, *claims; float* pos; int32_t *fv_node, *fv_feat, *fv_off; size_t bytes;
+};
+RefKfUploadBatch carve_refkf_upload_batch(uint8_t* base, int count, size_t T) {
+  RefKfUploadBatch u;
+  uint8_t* p = base;
+  const size_t B = (size_t)count;
+  u.inv_sigma2 = carve<float>(p, 64); u.pose = carve<double>(p, B * 7); u.qoff = carve<int32_t>(p, B); u.kfv_n = carve<int32_t>(p, B);
+  u.res = carve<int32_t>(p, B * 8); u.run = carve<int32_t>(p, B); u.wg_base = carve<int32_t>(p, B + 1);
+  u.desc = carve<uint8_t>(p, T * 32); u.angle = carve<float>(p, T); u.use = carve<uint8_t>(p, T); u.claims = carve<uint8_t>(p, T);
+  u.pos = carve<float>(p, T * 3); u.fv_node = carve<int32_t>(p, T); u.fv_feat = carve<int32_t>(p, T); u.fv_off = carve<int32_t>(p, T + B);
+  u.bytes = (size_t)(p - base);
+  return u;
+}
+// the device working set behind the upload, per frame at the call's capacity stride (cap <= kp_cap, count <= max_frames)
+struct RefKfWork { int32_t *word, *node; double* w; int32_t *fv_node, *fv_feat, *fv_off, *cnt, *match, *bin; size_t bytes; };
+RefKfWork carve_refkf_work(uint8_t* base, size_t B, size_t K) {
+  RefKfWork r;
+  uint8_t* p = base;
+  r.word = carve<int32_t>(p, B * K); r.node = carve<int32_t>(p, B * K); r.w = carve<double>(p, B * K);
+  r.fv_node = carve<int32_t>(p, B * K); r.fv_feat = carve<int32_t>(p, B * K); r.fv_off = carve<int32_t>(p, B * (K + 1));
+  r.cnt = carve<int32_t>(p, B * kRefKfCnt); r.match = carve<int32_t>(p, B * K); r.bin = carve<int32_t>(p, B * K);
+  r.bytes = (size_t)(p - base);
+  return r;
+}
+}  // namespace
+
+int dvm_tracker_reserve_reference_keyframe_batch(dvm_tracker* t, int max_total_kf_keypoints) {
+  if (!t || max_total_kf_keypoints < 1) return DVM_ERR_INVALID;
+  if ((int64_t)max_total_kf_keypoints > (int64_t)t->max_frames * kFrameCap) {
+    set_error("dvm_tracker_reserve_reference_keyframe_batch: more than 8 192 keyframe keypoints per frame"); return DVM_ERR_CAPACITY;
+  }
+  DVM_HIP(hipSetDevice(t->device));
+  if (t->d_rkb) { hipFree(t->d_rkb); t->d_rkb = nullptr; }
+  if (t->hm_rkb) { hipHostFree(t->hm_rkb); t->hm_rkb = nullptr; }
+  t->rkb_cap = 0;
+  const size_t R = ((size_t)max_total_kf_keypoints + 63) & ~(size_t)63, K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
+  t->rkb_up_bytes = carve_refkf_upload_batch(nullptr, (int)B, R).bytes;
+  const size_t dbytes = t->rkb_up_bytes + carve_refkf_work(nullptr, B, K).bytes;
+  // mapped: upload staging, BowVector, FeatureVector, match, counters, outlier flags, edges / inliers / nmatchesMap, pose
+  const size_t mbytes = t->rkb_up_bytes + pad256(B * K * 4) + pad256(B * K * 8) + pad256(B * K * 4) + pad256(B * K * 4) + pad256(B * (K + 1) * 4) +
+                        pad256(B * K * 4) + pad256(B * 8 * 4) + pad256(B * K) + 3 * pad256(B * 4 * 4) + pad256(B * 7 * 8);
+  if (hipMalloc(reinterpret_cast<void**>(&t->d_rkb), dbytes) != hipSuccess) {
+    t->d_rkb = nullptr; set_error("dvm_tracker_reserve_reference_keyframe_batch: hipMalloc"); return DVM_ERR_CAPACITY;
+  }
+  if (hipHostMalloc(reinterpret_cast<void**>(&t->hm_rkb), mbytes, hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer(reinterpret_cast<void**>(&t->hm_rkb_dev), t->hm_rkb, 0) != hipSuccess) {
+    if (t->hm_rkb) hipHostFree(t->hm_rkb);
+    t->hm_rkb = nullptr; hipFree(t->d_rkb); t->d_rkb = nullptr;
+    set_error("dvm_tracker_reserve_reference_keyframe_batch: mapped host memory"); return DVM_ERR_CAPACITY;
+  }
+  std::memset(t->hm_rkb, 0, mbytes);
+  uint8_t* p = t->hm_rkb + t->rkb_up_bytes;
+  auto& r = t->rkb;
+  r.bow_ids = carve<int32_t>(p, B * K); r.bow_vals = carve<double>(p, B * K); r.fv_node = carve<int32_t>(p, B * K); r.fv_feat = carve<int32_t>(p, B * K);
+  r.fv_off = carve<int32_t>(p, B * (K + 1)); r.match = carve<int32_t>(p, B * K); r.cnt = carve<int32_t>(p, B * 8); r.outlier = carve<uint8_t>(p, B * K);
+  r.nedges = carve<int32_t>(p, B * 4); r.n_inl = carve<int32_t>(p, B * 4); r.fin = carve<int32_t>(p, B * 4); r.pose = carve<double>(p, B * 7);
+  t->rkb_cap = (int)R;
+  return DVM_OK;
+}
+
+int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, int count, const dvm_ref_keyframe* const* kfs,
+                                       const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status) {
+  if (!t || !h || !voc || !kfs || !ps || !outs || !res || !status || count < 1) return DVM_ERR_INVALID;
+  LocalFrame& f = t->lf;
+  if (!f.rkb_ready || f.h != h || orb_result_serial(h) != f.serial || f.count != count) {
+    set_error("dvm_track_reference_keyframe_batch: not right after a dvm_track_finish[_batch] of `count` frames (same tracker and extractor), "
+              "or already run on that finish");
+    return DVM_ERR_STATE;
+  }
+  if (!t->d_rkb) { set_error("dvm_track_reference_keyframe_batch: no dvm_tracker_reserve_reference_keyframe_batch on this tracker"); return DVM_ERR_STATE; }
+  static const bool timing = std::getenv("DVM_TRACK_BATCH_TIMING") != nullptr;       // host-side phase times on stderr
+  using clk = std::chrono::steady_clock;
+  const clk::time_point tp0 = clk::now();
+  // every keyframe checked as the single call checks it, the shared parameters equal across the frames that run; nothing enqueued before
+  std::vector<int32_t> qoff((size_t)count, 0), run;
+  size_t T = 0;
+  const dvm_track_refkf_params* p0 = nullptr;
+  for (int b = 0; b < count; b++) {
+    qoff[b] = (int32_t)std::min(T, (size_t)INT32_MAX);
+    const dvm_ref_keyframe* kf = kfs[b];
+    if (!kf) continue;
+    const dvm_track_refkf_params* p = &ps[b];
+    const int rc = check_refkf_frame("dvm_track_reference_keyframe_batch", kf, p, &outs[b], kFrameCap);
+    if (rc != DVM_OK) return rc;
+    if (!p0) {
+      p0 = p;
+    } else if (p->nnratio != p0->nnratio || p->check_ori != p0->check_ori || p->th_low != p0->th_low || p->min_matches != p0->min_matches ||
+               p->min_map != p0->min_map || p->levelsup != p0->levelsup || p->nlevels != p0->nlevels ||
+               std::memcmp(p->inv_level_sigma2, p0->inv_level_sigma2, (size_t)p->nlevels * 4) != 0 || std::memcmp(&p->cam, &p0->cam, sizeof(p->cam)) != 0) {
+      set_error("dvm_track_reference_keyframe_batch: the frames that run share camera, level table and matcher thresholds");
+      return DVM_ERR_INVALID;
+    }
+    T += ((size_t)std::max(kf->n, kf->fv_n) + 63) & ~(size_t)63;
+    run.push_back(b);
+  }
+  if (p0 && vocab_device(voc) != t->device) { set_error("dvm_track_reference_keyframe_batch: the vocabulary lives on another device"); return DVM_ERR_INVALID; }
+  if (T > (size_t)t->rkb_cap) {
+    set_error("dvm_track_reference_keyframe_batch: more keyframe keypoints than reserved (each keyframe's rounded up to 64)"); return DVM_ERR_CAPACITY;
+  }
+  const int ocap = f.ocap;
+  const RefKfUploadBatch up = carve_refkf_upload_batch(t->hm_rkb, count, std::max(T, (size_t)64));
+  if (up.bytes > t->rkb_up_bytes || ocap > t->kp_cap) {
+    set_error("dvm_track_reference_keyframe_batch: the upload block exceeds the reservation"); return DVM_ERR_CAPACITY;
+  }
+  // accepted: once per finish, and the single call no longer runs on it
+  for (int b = 0; b < count; b++) { std::memset(&res[b], 0, sizeof(res[b])); status[b] = f.status[b]; }
+  f.rkb_ready = 0; t->rk_state = 0;
+  const int nrun = (int)run.size();
+  if (!nrun) return DVM_OK;
+  const dvm_track_refkf_params& P0 = *p0;
+  DVM_HIP(hipSetDevice(t->device));
+  hipStream_t s = (hipStream_t)dvm_orb_stream(h);
+  // 1. the keyframes packed back to back into the mapped staging block by the pool threads: ONE asynchronous copy
+  std::memset(up.inv_sigma2, 0, 64 * 4);
+  std::memcpy(up.inv_sigma2, P0.inv_level_sigma2, (size_t)P0.nlevels * 4);
+  int nwg = 0;
+  for (int r = 0; r < nrun; r++) { up.run[r] = run[r]; up.wg_base[r] = nwg; nwg += (kfs[run[r]]->fv_n + 3) / 4; }
+  up.wg_base[nrun] = nwg;
+  HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {
+    const dvm_ref_keyframe* kf = kfs[b];
+    const size_t o = (size_t)qoff[b];
+    up.qoff[b] = qoff[b];
+    int32_t* rs = up.res + 8 * b;
+    for (int k = 0; k < 8; k++) rs[k] = 0;
+    if (!kf) {                            // a frame that does not run: no edges (k_track_gather reads res[1] != 0), the pose left alone
+      rs[1] = 1; up.kfv_n[b] = 0;
+      std::memcpy(up.pose + 7 * b, f.poses.data() + 7 * b, 56);
+      return;
+    }
+    const int n = kf->n, nf = kf->fv_n, nfeat = nf ? kf->fv_off[nf] : 0;
+    std::memcpy(up.pose + 7 * b, ps[b].pose_in, 56);
+    up.kfv_n[b] = nf;
+    if (n) std::memcpy(up.desc + o * 32, kf->desc, (size_t)n * 32);
+    for (int i = 0; i < n; i++) {
+      const int id = kf->mp[i];
+      const bool use = id >= 0 && !(kf->mp_bad && kf->mp_bad[i]);      // SearchByBoW: no map point or a bad one -> skipped (:247-252)
+      up.angle[o + i] = kf->kps_un[i].angle; up.use[o + i] = use ? 1 : 0;
+      up.claims[o + i] = id >= 0 && kf->mp_nobs[i] > 0 ? 1 : 0;
+      for (int k = 0; k < 3; k++) up.pos[3 * (o + i) + k] = id >= 0 ? kf->mp_pos[3 * i + k] : 0.0f;
+    }
+    int32_t* fo = up.fv_off + o + b;
+    if (nf) {
+      std::memcpy(up.fv_node + o, kf->fv_node, (size_t)nf * 4); std::memcpy(fo, kf->fv_off, ((size_t)nf + 1) * 4);
+      std::memcpy(up.fv_feat + o, kf->fv_feat, (size_t)nfeat * 4);
+    } else {
+      fo[0] = 0;
+    }
+  });
+  DVM_HIP(hipMemcpyAsync(t->d_rkb, t->hm_rkb, up.bytes, hipMemcpyHostToDevice, s));
+  const clk::time_point tp1 = clk::now();
+  const RefKfUploadBatch dup = carve_refkf_upload_batch(t->d_rkb, count, std::max(T, (size_t)64));
+  // 2. the chain of dvm_track_reference_keyframe on the finish's frames: the transform of all frames that run in one launch, a workgroup
+  //    per frame for the BoW and the rotation check, each frame's keyframe nodes on their own workgroups, then the edge gather, the pose
+  //    and the outlier flags as the batched first half runs them (a frame that does not run: an empty workgroup in each)
+  const RefKfWork W = carve_refkf_work(t->d_rkb + t->rkb_up_bytes, (size_t)t->max_frames, (size_t)t->kp_cap);
+  auto& r = t->rkb;
+  RefKfArgs A{};
+  A.word = W.word; A.node = W.node; A.w = W.w; A.fv_node = W.fv_node; A.fv_feat = W.fv_feat; A.fv_off = W.fv_off; A.cnt = W.cnt;
+  A.match = W.match; A.bin = W.bin; A.res = dup.res;
+  A.h_bow_ids = t->rkbdev(r.bow_ids); A.h_bow_vals = t->rkbdev(r.bow_vals); A.h_fv_node = t->rkbdev(r.fv_node); A.h_fv_off = t->rkbdev(r.fv_off);
+  A.h_fv_feat = t->rkbdev(r.fv_feat); A.h_match = t->rkbdev(r.match); A.h_cnt = t->rkbdev(r.cnt);
+  A.kdesc = dup.desc; A.kangle = dup.angle; A.kuse = dup.use; A.kfv_node = dup.fv_node; A.kfv_off = dup.fv_off; A.kfv_feat = dup.fv_feat; A.kfv_n = 0;
+  A.run = dup.run; A.kqoff = dup.qoff; A.kfv_nb = dup.kfv_n; A.wg_base = dup.wg_base; A.nrun = nrun; A.nwg = nwg;
+  A.kps_stride = f.kps_stride; A.desc_stride = f.desc_stride;
+  vocab_launch_transform(voc, s, f.d_desc, ocap, f.d_n, P0.levelsup, W.word, W.node, W.w, dup.run, nrun, f.desc_stride);
+  launch_refkf_bow(s, A, f.d_n, ocap);
+  launch_refkf_search(s, A, f.d_un, f.d_desc, f.d_n, ocap, P0.th_low, P0.nnratio);
+  launch_refkf_settle(s, A, f.d_n, ocap, P0.check_ori);
+  const TrackBatch TE{count, 0, f.kps_stride, nullptr, dup.qoff};
+  launch_track_gather(s, W.match, f.d_un, f.d_n, ocap, dup.pos, dup.inv_sigma2, P0.nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges,
+                      dup.res, P0.min_matches, t->rkbdev(r.nedges), TE);
+  ba_launch_pose_optimize(s, dup.pose, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, P0.cam.fx, P0.cam.fy, P0.cam.cx, P0.cam.cy,
+                          t->rkbdev(r.pose), t->d_edge_out, t->rkbdev(r.n_inl), t->d_chi);
+  launch_track_finish(s, W.match, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, dup.claims, t->rkbdev(r.outlier), t->rkbdev(r.fin), dup.res, TE);
+  int rc = hip_check(hipGetLastError(), "batched reference keyframe chain launch");
+  if (rc != DVM_OK) return rc;
+  // 3. ONE synchronisation, then every frame that ran copied out of mapped memory by the pool threads
+  DVM_HIP(hipStreamSynchronize(s));
+  const clk::time_point tp2 = clk::now();
+  HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {
+    const dvm_ref_keyframe* kf = kfs[b];
+    if (!kf) return;
+    const dvm_track_refkf_params* p = &ps[b];
+    const dvm_track_refkf_out* out = &outs[b];
+    dvm_track_refkf_result* q = &res[b];
+    const size_t K = (size_t)ocap;
+    const int N = f.ns[b];
+    const int32_t* cnt = r.cnt + 8 * b;
+    q->n = N; q->mono_index = f.monos[b];
+    q->n_bow = cnt[0]; q->n_fv = cnt[1]; q->nmatches_before_rotation = cnt[2]; q->nmatches = cnt[3];
+    const int32_t* fo = r.fv_off + b * (K + 1);
+    if (out->bow_ids) std::memcpy(out->bow_ids, r.bow_ids + b * K, (size_t)q->n_bow * 4);
+    if (out->bow_vals) std::memcpy(out->bow_vals, r.bow_vals + b * K, (size_t)q->n_bow * 8);
+    if (out->fv_node) std::memcpy(out->fv_node, r.fv_node + b * K, (size_t)q->n_fv * 4);
+    if (out->fv_off) std::memcpy(out->fv_off, fo, ((size_t)q->n_fv + 1) * 4);
+    if (out->fv_feat) std::memcpy(out->fv_feat, r.fv_feat + b * K, (size_t)fo[q->n_fv] * 4);
+    // mvpMapPoints: SearchByBoW's matches, those PoseOptimization rejected dropped (Tracking.cc:2486-2516)
+    const bool few = q->nmatches < p->min_matches;
+    const int32_t* match = r.match + b * K;
+    const uint8_t* outl = r.outlier + b * K;
+    for (int j = 0; j < N; j++) {
+      const int a = match[j];
+      const int id = a >= 0 ? kf->mp[a] : -1;
+      const bool o = !few && id >= 0 && outl[j];
+      out->mp_out[j] = o ? -1 : id; out->dropped[j] = o ? id : -1; out->outlier[j] = o ? 1 : 0;
+    }
+    if (few) {
+      q->status = DVM_TRACK_FEW_MATCHES;
+      std::memcpy(q->pose, p->pose_in, 56);
+    } else {
+      q->n_edges = r.nedges[b]; q->n_inliers = r.n_inl[b]; q->nmatches_map = r.fin[4 * b]; q->nmatches_after = r.fin[4 * b + 1];
+      std::memcpy(q->pose, r.pose + 7 * b, 56);
+      q->status = q->nmatches_map < p->min_map ? DVM_TRACK_FEW_MAP_MATCHES : DVM_TRACK_COMPLETE;
+    }
+    for (int k = 0; k < 3; k++) q->Tcw.t[k] = (float)q->pose[k];
+    for (int k = 0; k < 4; k++) q->Tcw.q[k] = (float)q->pose[3 + k];
+    // what dvm_track_local_map_batch runs on: this frame complete or not by this call's status, seeded from its pose
+    status[b] = q->status; f.status[b] = q->status;
+    std::memcpy(f.poses.data() + 7 * b, q->pose, 56);
+  });
+  if (count == 1) {       // and dvm_track_local_map, as after dvm_track_reference_keyframe
+    std::memcpy(f.pose, f.poses.data(), 56);
+    f.ready = f.status[0] == DVM_TRACK_COMPLETE;
+  }
+  if (timing) {
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    std::fprintf(stderr, "track reference keyframe batch of %d (%d run, %zu entries): pack + enqueue %.3f  wait %.3f  results out %.3f ms\n", count,
+                 nrun, T, ms(tp0, tp1), ms(tp1, tp2), ms(tp2, clk::now()));
+  }
   return DVM_OK;
 }
 

@@ -77,10 +77,20 @@ struct RefKfArgs {
   // the keyframe (device copy of the upload)
   const uint8_t* kdesc; const float* kangle; const uint8_t* kuse;   // [n]: descriptor, mvKeysUn angle, has a good map point
   const int32_t *kfv_node, *kfv_off, *kfv_feat; int32_t kfv_n;      // its mFeatVec
+  // a batch (dvm_track_reference_keyframe_batch; null for one frame): frame b's per-frame arrays above at b * cap (fv_off at b * (cap + 1),
+  // cnt at b * kRefKfCnt, res at 8 b, h_cnt at 8 b), its keyframe at kqoff[b] entries of the upload (kfv_off at kqoff[b] + b), its frame
+  // inputs at b * kps_stride / b * desc_stride
+  const int32_t* run;       // device [nrun]: the frames that run; workgroup r of the bow / settle kernels works on frame run[r]
+  const int32_t* kqoff;     // device [count]
+  const int32_t* kfv_nb;    // device [count]: the keyframes' node counts
+  const int32_t* wg_base;   // device [nrun + 1]: run r's first workgroup of k_refkf_search (its nodes, 4 per workgroup)
+  int32_t nrun, nwg;        // frames that run, k_refkf_search's workgroups (host values)
+  int64_t kps_stride, desc_stride;
 };
-// one workgroup: the frame's BowVector (mapped) and FeatureVector (device + mapped); the match state reset
+// one workgroup (per frame that runs): the frame's BowVector (mapped) and FeatureVector (device + mapped); the match state reset
 void launch_refkf_bow(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap);
-// SearchByBoW's matching: one wave per keyframe node; then the rotation check and res[] for the edge gather
+// SearchByBoW's matching: one wave per keyframe node (a batch: each frame its own range of workgroups, A.wg_base); then the rotation
+// check and res[] for the edge gather, one workgroup per frame that runs
 void launch_refkf_search(hipStream_t s, const RefKfArgs& A, const dvm_keypoint_pod* kps_un, const uint8_t* desc, const int32_t* d_n, int cap, int th_low,
                          float nnratio);
 void launch_refkf_settle(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap, int check_ori);

@@ -565,6 +565,16 @@ __device__ int for_each_run(const uint64_t* keys, int M, int* s_wave, Fn f) {
 }
 }  // namespace
 
+// a batch's frame b: every per-frame pointer of A moved to that frame's slice (RefKfArgs); one frame (A.run null) stays as it is
+__device__ __forceinline__ void refkf_at(RefKfArgs& A, int b, int cap) {
+  const size_t o = (size_t)b * cap;
+  A.word += o; A.node += o; A.w += o; A.fv_node += o; A.fv_feat += o; A.fv_off += o + b; A.cnt += (size_t)b * kRefKfCnt; A.match += o; A.bin += o;
+  A.res += 8 * b;
+  A.h_bow_ids += o; A.h_bow_vals += o; A.h_fv_node += o; A.h_fv_off += o + b; A.h_fv_feat += o; A.h_match += o; A.h_cnt += 8 * b;
+  const size_t k = (size_t)A.kqoff[b];
+  A.kdesc += k * 32; A.kangle += k; A.kuse += k; A.kfv_node += k; A.kfv_off += k + b; A.kfv_feat += k; A.kfv_n = A.kfv_nb[b];
+}
+
 // Frame::ComputeBoW's bookkeeping (TemplatedVocabulary::transform's TF_IDF branch, DBoW2 TemplatedVocabulary.h:1098-1138, as the host
 // mirror dvm_slam_amd/host/orb_vocabulary.cpp keeps it) on k_vocab_transform's per-feature results, in LDS by one workgroup:
 //   the features with weight > 0 only (a stopped word adds nothing, not even its node entry);
@@ -573,7 +583,9 @@ __device__ int for_each_run(const uint64_t* keys, int M, int* s_wave, Fn f) {
 //     value divided by the norm (correctly rounded double division);
 //   FeatureVector: sort ((unsigned)node << 32 | feature): nodes ascending as unsigned (node -1 last), features ascending inside a node.
 // It also resets the match state of the search behind it.  LDS: 16 B per entry of the sort (the capacity rounded up to a power of two).
+// A batch: one workgroup per frame that runs (A.run).
 __global__ void __launch_bounds__(1024) k_refkf_bow(RefKfArgs A, const int32_t* __restrict__ d_n, int cap, int P) {
+  if (A.run) { const int b = A.run[blockIdx.x]; refkf_at(A, b, cap); d_n += b; }
   extern __shared__ __attribute__((aligned(16))) uint8_t refkf_smem[];
   uint64_t* keys = reinterpret_cast<uint64_t*>(refkf_smem);    // [P]
   double* vals = reinterpret_cast<double*>(keys + P);          // [P]
@@ -647,14 +659,28 @@ __global__ void __launch_bounds__(1024) k_refkf_bow(RefKfArgs A, const int32_t* 
 // merged), so every decision sees exactly the claims the reference's walk has made by then.  The rotation histogram only counts, so its
 // global atomics may come in any order.  LDS: the claim flag of every frame keypoint (1 B each).
 // Known limit: a vocabulary with L - levelsup <= 0 puts every feature into node 0: one wave then walks the whole frame.
+// A batch: each frame that runs has its own range of workgroups (A.wg_base), so a workgroup's claim flags -- indexed by the frame's
+// keypoint -- never mix two frames.
 __global__ void __launch_bounds__(256) k_refkf_search(RefKfArgs A, const dvm_keypoint_pod* __restrict__ kps_un, const uint8_t* __restrict__ desc,
                                                       const int32_t* __restrict__ d_n, int cap, int th_low, float nnratio) {
   extern __shared__ __attribute__((aligned(16))) uint8_t refkf_smem[];
   uint8_t* s_claim = refkf_smem;   // [cap]
+  int wg = blockIdx.x;
+  if (A.run) {
+    int lo = 0, hi = A.nrun - 1;            // the run r with wg_base[r] <= blockIdx.x < wg_base[r + 1]
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (A.wg_base[mid] <= wg) lo = mid; else hi = mid - 1;
+    }
+    const int b = A.run[lo];
+    wg -= A.wg_base[lo];
+    refkf_at(A, b, cap);
+    kps_un += (size_t)b * A.kps_stride; desc += (size_t)b * A.desc_stride; d_n += b;
+  }
   for (int j = threadIdx.x; j < cap; j += 256) s_claim[j] = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const int a = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int a = wg * 4 + (threadIdx.x >> 6);
   if (a >= A.kfv_n) return;
   const int N = min(*d_n, cap), n_fv = A.cnt[1];
   const uint32_t node = (uint32_t)A.kfv_node[a];
@@ -709,8 +735,9 @@ __global__ void __launch_bounds__(256) k_refkf_search(RefKfArgs A, const dvm_key
 }
 
 // the rotation check of SearchByBoW (:372-387): ComputeThreeMaxima, the matches of the other bins taken back; res[0] = nmatches for the
-// edge gather, the final matches to mapped memory.  One workgroup.
+// edge gather, the final matches to mapped memory.  One workgroup (per frame that runs).
 __global__ void __launch_bounds__(256) k_refkf_settle(RefKfArgs A, const int32_t* __restrict__ d_n, int cap, int check_ori) {
+  if (A.run) { const int b = A.run[blockIdx.x]; refkf_at(A, b, cap); d_n += b; }
   __shared__ int s_rot[kHisto];
   __shared__ int s_ind[3];
   __shared__ int s_nd[4];
@@ -780,15 +807,18 @@ void launch_refkf_bow(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int
   while (P < cap) P <<= 1;
   const size_t lds = (size_t)P * 16;
   if (lds > 48 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_refkf_bow), (int)lds);
-  hipLaunchKernelGGL(k_refkf_bow, dim3(1), dim3(1024), lds, s, A, d_n, cap, P);
+  if (A.run && A.nrun < 1) return;
+  hipLaunchKernelGGL(k_refkf_bow, dim3(A.run ? A.nrun : 1), dim3(1024), lds, s, A, d_n, cap, P);
 }
 void launch_refkf_search(hipStream_t s, const RefKfArgs& A, const dvm_keypoint_pod* kps_un, const uint8_t* desc, const int32_t* d_n, int cap, int th_low,
                          float nnratio) {
-  if (A.kfv_n < 1) return;
-  hipLaunchKernelGGL(k_refkf_search, dim3((A.kfv_n + 3) / 4), dim3(256), (size_t)cap, s, A, kps_un, desc, d_n, cap, th_low, nnratio);
+  const int nwg = A.run ? A.nwg : (A.kfv_n + 3) / 4;
+  if (nwg < 1) return;
+  hipLaunchKernelGGL(k_refkf_search, dim3(nwg), dim3(256), (size_t)cap, s, A, kps_un, desc, d_n, cap, th_low, nnratio);
 }
 void launch_refkf_settle(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap, int check_ori) {
-  hipLaunchKernelGGL(k_refkf_settle, dim3(1), dim3(256), 0, s, A, d_n, cap, check_ori);
+  if (A.run && A.nrun < 1) return;
+  hipLaunchKernelGGL(k_refkf_settle, dim3(A.run ? A.nrun : 1), dim3(256), 0, s, A, d_n, cap, check_ori);
 }
 
 }  // namespace dvm

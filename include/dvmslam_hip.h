@@ -766,6 +766,28 @@ int dvm_tracker_reserve_reference_keyframe(dvm_tracker* t, int max_kf_keypoints)
  * mvKeysUn this call left, seeded from this call's pose); after any other status it is refused. */
 int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, const dvm_ref_keyframe* kf, const dvm_track_refkf_params* p,
                                  dvm_track_refkf_out* out, dvm_track_refkf_result* res);
+/* The working set of dvm_track_reference_keyframe_batch, separate from dvm_tracker_reserve_reference_keyframe's and accepted on any tracker:
+ * max_total_kf_keypoints is the TOTAL of one call, the sum over its keyframes of n (of fv_n where that is larger), each rounded up to 64
+ * (up to max_frames x 8 192); the per-frame arrays are reserved for max_frames frames.  DVM_ERR_CAPACITY for what it cannot hold.  Called
+ * again, it replaces the working set; dvm_tracker_destroy frees it. */
+int dvm_tracker_reserve_reference_keyframe_batch(dvm_tracker* t, int max_total_kf_keypoints);
+/* TrackReferenceKeyFrame for the frames of one camera tick (several agents on one GPU) that need it: after the batched first half, the
+ * frames whose motion model failed or that had none (the caller passed nq = 0 queries: DVM_TRACK_FEW_MATCHES) run ComputeBoW ->
+ * SearchByBoW -> PoseOptimization as ONE chain of batched launches: one upload of all keyframes, one synchronisation.  Accepted right after a
+ * dvm_track_finish_batch of `count` frames (or a dvm_track_finish: count = 1) on the same tracker and extractor, once per finish (otherwise
+ * DVM_ERR_STATE; where the finish ran twice, the last one counts).  kfs / ps / outs / res / status: `count` entries.
+ *   kfs[b] != NULL: form (b) of dvm_track_reference_keyframe on frame b whatever its first-half status -- res[b] and outs[b] exactly what
+ *     that call gives on the frame alone; status[b] = res[b].status.  outs[b].kps / desc / kps_un are not written (the finish returned them).
+ *   kfs[b] == NULL: status[b] = the first half's status, res[b] zeroed, outs[b] not written, ps[b] not read.
+ * ps[b].pose_in is per frame; nnratio, check_ori, th_low, min_matches, min_map, levelsup, the level table and cam must be equal across the
+ * frames that run (DVM_ERR_INVALID); bounds and dist are not read.  Every keyframe is checked as the single call checks it before anything
+ * runs; the keyframes' total beyond the reservation: DVM_ERR_CAPACITY.  A refused call leaves the finish for a corrected one.  Afterwards
+ * dvm_track_local_map_batch (count frames) treats a frame as complete when status[b] == DVM_TRACK_COMPLETE, seeded from this call's pose
+ * where the frame ran; with count = 1, dvm_track_local_map is accepted as after dvm_track_reference_keyframe.  DVM_TRACK_BATCH_TIMING=1
+ * prints the call's host phases on stderr. */
+int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, int count, const dvm_ref_keyframe* const* kfs,
+                                       const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res,
+                                       int32_t* status);
 
 /* Optimizer::OptimizeSim3 (Optimizer.cc:1960-2212), numerics for N correspondences gathered by the caller:
  * P1c / P2c = the matched map points in their own key frame's camera frame (R1w*P+t1w, R2w*P+t2w), obs1 / obs2 =
