@@ -13,6 +13,8 @@
 // unfinished, flagged in dvm_track_result::status: fewer than min_matches matches (the reference searches again with a doubled window,
 // Tracking.cc:2616-2624: call dvm_track_finish again with the wider queries -- no new extraction), and a query whose four ranked
 // candidates were all taken by earlier queries (the list may go on: the caller replays the epilogue from the ranked lists on the host).
+// The second half (dvm_track_local_map, dvm_track_reference_keyframe) runs as the batch of one frame: the single calls keep their own
+// checks and run the chains of dvm_track_local_map_batch / dvm_track_reference_keyframe_batch.
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -21,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "../../include/dvmslam_hip.h"
@@ -38,16 +41,52 @@ using namespace dvm;
 struct LocalFrame {
   int ready = 0, batch_ready = 0, rkb_ready = 0;
   dvm_orb* h = nullptr; uint64_t serial = 0;     // the extractor and which of its extractions the frame is
-  int n = 0, ocap = 0, nlevels = 0;
+  int ocap = 0, nlevels = 0;
   const dvm_keypoint_pod* d_un = nullptr; const int32_t* d_n = nullptr;   // mvKeysUn on the device, the keypoint count
   float bounds[4] = {0, 0, 0, 0}, inv_sigma2[64] = {};
   dvm_ba_camera cam{};
   int count = 0; int64_t kps_stride = 0;          // the finish's frames: frame b's mvKeysUn at b * kps_stride, its count at d_n[b]
   std::vector<int32_t> ns, status;                // per frame: keypoints, the first half's status
-  double pose[7] = {};                            // ready: the pose dvm_track_local_map starts from (the finish's, or the reference-keyframe chain's)
-  std::vector<double> poses;                      // [count][7]: the poses dvm_track_local_map_batch starts from (the same choice per frame)
+  std::vector<double> poses;                      // [count][7]: the poses the second half starts from (the finish's, or the reference-keyframe chain's)
   std::vector<int32_t> monos;                     // per frame: monoIndex of the extraction
   const uint8_t* d_desc = nullptr; int64_t desc_stride = 0;   // the frames' descriptors on the device: frame b's at b * desc_stride
+};
+
+// the memory of one reservation: a device block and a mapped page-locked block, each beginning with the upload region (built in the
+// mapped block, copied to the same offsets of the device block by one asynchronous copy)
+struct WorkingSet {
+  uint8_t* d = nullptr;                           // device
+  uint8_t *hm = nullptr, *hm_dev = nullptr;       // mapped: host address, device address
+  size_t up_bytes = 0;                            // the upload region's capacity
+  // replaces what it holds by dbytes of device memory and mbytes of zeroed mapped memory; on failure it holds nothing and names what failed
+  const char* alloc(size_t dbytes, size_t mbytes) {
+    free();
+    if (hipMalloc(reinterpret_cast<void**>(&d), dbytes) != hipSuccess) { d = nullptr; return "hipMalloc"; }
+    if (hipHostMalloc(reinterpret_cast<void**>(&hm), mbytes, hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer(reinterpret_cast<void**>(&hm_dev), hm, 0) != hipSuccess) {
+      free();
+      return "mapped host memory";
+    }
+    std::memset(hm, 0, mbytes);
+    return nullptr;
+  }
+  void free() {
+    if (d) hipFree(d);
+    if (hm) hipHostFree(hm);
+    d = hm = hm_dev = nullptr; up_bytes = 0;
+  }
+  template <class T> T* dev(T* host_ptr) const { return reinterpret_cast<T*>(hm_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm)); }
+};
+
+// a TrackReferenceKeyFrame working set: per-frame arrays for the tracker's max_frames frames at its keypoint capacity, keyframes of up to
+// `cap` entries per call (each keyframe's rounded up to 64)
+struct RefKfMapped {
+  int32_t *bow_ids, *fv_node, *fv_off, *fv_feat, *match, *cnt, *nedges, *n_inl, *fin; double *bow_vals, *pose; uint8_t* outlier;
+};
+struct RefKf {
+  WorkingSet ws;                   // device: [upload copy][the frames' transforms, FeatureVectors and match state]; mapped: [upload staging][results]
+  int cap = 0;
+  RefKfMapped r;                   // [max_frames] slices of the results (fv_off: kp_cap + 1 per frame, cnt: 8 per frame)
 };
 
 struct dvm_tracker {
@@ -75,33 +114,19 @@ struct dvm_tracker {
   template <class T> T* qdev(T* host_ptr) const { return reinterpret_cast<T*>(d_q + (reinterpret_cast<uint8_t*>(host_ptr) - hm)); }
   int begun = 0;                   // frames of the batch whose extraction is queued
   int rows = 0, cols = 0;
-  // ---- the second half (dvm_track_local_map): working set of dvm_tracker_reserve_local_map, and what the last finish left for it
+  // ---- the second half (dvm_track_local_map[_batch]): working set of dvm_tracker_reserve_local_map, and what the last finish left for it
   int lm_cap = 0;                  // table entries reserved (a multiple of 64; a batch: all frames' tables, each rounded up to 64)
-  uint8_t* d_lm = nullptr;         // device: [upload][per-entry arrays][query arrays][ranked lists][counters]
-  uint8_t *hm_lm = nullptr, *hm_lm_dev = nullptr;   // mapped: [upload staging][results]
-  size_t lm_up_bytes = 0;          // the upload region's capacity (device copy at the start of d_lm)
+  WorkingSet lmw;                  // device: [upload][per-entry arrays][query arrays][ranked lists][counters]; mapped: [upload staging][results]
   struct LocalMapped { int32_t* mp; uint8_t* outlier; TrackPoint* tp; int32_t* res; double* pose; int32_t *n_inl, *fin, *nedges; } lm;   // [max_frames]
   LocalFrame lf;
-  template <class T> T* lmdev(T* host_ptr) const { return reinterpret_cast<T*>(hm_lm_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm_lm)); }
-  // ---- TrackReferenceKeyFrame (dvm_track_reference_keyframe): working set of dvm_tracker_reserve_reference_keyframe, and when it may run
+  // ---- TrackReferenceKeyFrame: the working sets of dvm_tracker_reserve_reference_keyframe (rk, one frame) and of
+  //      dvm_tracker_reserve_reference_keyframe_batch (rkb), and when the single call dvm_track_reference_keyframe may run
   int rk_state = 0;                // 1: right after a single-frame begin (form a), 2: right after that frame's finish (form b), else 0
   dvm_orb* rk_h = nullptr; uint64_t rk_serial = 0;   // the extractor and which of its extractions the frame is
-  int rk_cap = 0;                  // keyframe keypoints reserved
-  uint8_t* d_rk = nullptr;         // device: [upload copy][the frame's transform, FeatureVector and match state]
-  uint8_t *hm_rk = nullptr, *hm_rk_dev = nullptr;   // mapped: [upload staging][results]
-  size_t rk_up_bytes = 0;          // the upload region's capacity
-  struct RefKfMapped {
-    int32_t *bow_ids, *fv_node, *fv_off, *fv_feat, *match, *cnt, *nedges, *n_inl, *fin; double *bow_vals, *pose; uint8_t* outlier;
-  } rk;
-  template <class T> T* rkdev(T* host_ptr) const { return reinterpret_cast<T*>(hm_rk_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm_rk)); }
-  // ---- the same for the frames of a batched finish (dvm_track_reference_keyframe_batch): working set of
-  //      dvm_tracker_reserve_reference_keyframe_batch; per-frame arrays for max_frames frames at the extractor's capacity
-  int rkb_cap = 0;                 // keyframe keypoints of one call reserved (each keyframe's rounded up to 64)
-  uint8_t* d_rkb = nullptr;        // device: [upload copy][the frames' transforms, FeatureVectors and match state]
-  uint8_t *hm_rkb = nullptr, *hm_rkb_dev = nullptr;   // mapped: [upload staging][results]
-  size_t rkb_up_bytes = 0;
-  RefKfMapped rkb;                 // [max_frames] slices (fv_off: kp_cap + 1 per frame, cnt: 8 per frame)
-  template <class T> T* rkbdev(T* host_ptr) const { return reinterpret_cast<T*>(hm_rkb_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm_rkb)); }
+  int rk_cap = 0;                  // keyframe keypoints the single call takes (rk.cap: this rounded up to 64)
+  RefKf rk, rkb;
+  // nothing of the second half may run until the next finish (or begin, for the single reference-keyframe call)
+  void clear_next() { lf.ready = 0; lf.batch_ready = 0; lf.rkb_ready = 0; rk_state = 0; }
 };
 
 namespace dvm {
@@ -114,6 +139,8 @@ void vocab_launch_transform(const dvm_vocab* v, hipStream_t s, const uint8_t* d_
 namespace {
 size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 template <class T> T* carve(uint8_t*& p, size_t count) { T* r = reinterpret_cast<T*>(p); p += pad256(count * sizeof(T)); return r; }
+// a reservation that could not be allocated: "<fn>: <what failed>"
+int reserve_failed(const char* fn, const char* what) { set_error(std::string(fn) + ": " + what); return DVM_ERR_CAPACITY; }
 }  // namespace
 
 extern "C" {
@@ -178,12 +205,7 @@ void dvm_tracker_destroy(dvm_tracker* t) {
   if (t->grid) dvm_frame_destroy(t->grid);
   if (t->d_buf) hipFree(t->d_buf);
   if (t->d_q) hipFree(t->d_q);
-  if (t->d_lm) hipFree(t->d_lm);
-  if (t->hm_lm) hipHostFree(t->hm_lm);
-  if (t->d_rk) hipFree(t->d_rk);
-  if (t->hm_rk) hipHostFree(t->hm_rk);
-  if (t->d_rkb) hipFree(t->d_rkb);
-  if (t->hm_rkb) hipHostFree(t->hm_rkb);
+  t->lmw.free(); t->rk.ws.free(); t->rkb.ws.free();
   if (t->cev) hipEventDestroy(t->cev);
   if (t->cstream) hipStreamDestroy(t->cstream);
   if (t->hm) hipHostFree(t->hm);
@@ -193,7 +215,7 @@ void dvm_tracker_destroy(dvm_tracker* t) {
 int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_batch: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0; t->lf.rkb_ready = 0; t->rk_state = 0;
+  t->begun = 0; t->clear_next();
   const int rc = dvm_orb_extract_batch_host(h, imgs, count, rows, cols, stride, frame_stride, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
@@ -203,7 +225,7 @@ int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int c
 int dvm_track_begin_staged(dvm_tracker* t, dvm_orb* h, int count, int rows, int cols, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_staged: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0; t->lf.ready = 0; t->lf.batch_ready = 0; t->lf.rkb_ready = 0; t->rk_state = 0;
+  t->begun = 0; t->clear_next();
   const int rc = dvm_orb_extract_staged(h, count, rows, cols, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
@@ -216,7 +238,7 @@ int dvm_track_begin(dvm_tracker* t, dvm_orb* h, const uint8_t* img, int rows, in
 
 int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* qs, const dvm_track_frame_out* outs, dvm_track_result* res) {
   if (!t || !h || !qs || !outs || !res || count < 1) return DVM_ERR_INVALID;
-  t->lf.ready = 0; t->lf.batch_ready = 0; t->lf.rkb_ready = 0; t->rk_state = 0;
+  t->clear_next();
   if (t->begun != count) { set_error("dvm_track_finish: no matching dvm_track_begin on this tracker"); return DVM_ERR_STATE; }
   const dvm_track_queries& q0 = qs[0];
   int nq_max = 0;
@@ -314,6 +336,7 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
     if (rc != DVM_OK) return rc;
     for (int b = 0; b < count; b++) { res[b].n = ns[b]; res[b].mono_index = monos[b]; }
   }
+  static const bool debug = std::getenv("DVM_TRACK_DEBUG") != nullptr;       // per-frame counters on stderr
   for (int b = 0; b < count; b++) {
     const dvm_track_queries& q = qs[b];
     const dvm_track_frame_out& o = outs[b];
@@ -326,7 +349,7 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
     r.nmatches = rs[0];
     r.nmatches_before_rotation = rs[2];
     r.n_requeried = rs[3];
-    if (std::getenv("DVM_TRACK_DEBUG")) std::fprintf(stderr, "track: frame %d nq %d rounds %d requeried %d\n", b, q.nq, rs[4], rs[3]);
+    if (debug) std::fprintf(stderr, "track: frame %d nq %d rounds %d requeried %d\n", b, q.nq, rs[4], rs[3]);
     if (rs[1]) {                        // a query ran out of ranked candidates and could not be searched again on the device (DVM_TRACK_NO_REQUERY)
       r.status = DVM_TRACK_REPLAY_ON_HOST;
       if (o.ranked && q.nq) DVM_HIP(hipMemcpy(o.ranked, t->d_ranked + (size_t)b * Qs * 4, (size_t)q.nq * 16, hipMemcpyDeviceToHost));
@@ -342,13 +365,12 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
   {     // what the second half runs on: the frames' grids (slots 0..count-1) and mvKeysUn
     LocalFrame& f = t->lf;
     f.ready = count == 1 && res[0].status == DVM_TRACK_COMPLETE; f.batch_ready = 1; f.rkb_ready = 1;
-    f.h = h; f.serial = orb_result_serial(h); f.n = res[0].n; f.ocap = ocap; f.nlevels = q0.nlevels;
+    f.h = h; f.serial = orb_result_serial(h); f.ocap = ocap; f.nlevels = q0.nlevels;
     f.d_un = reinterpret_cast<const dvm_keypoint_pod*>(d_un); f.d_n = d_n;
     std::memcpy(f.bounds, q0.bounds, 16); std::memcpy(f.inv_sigma2, q0.inv_level_sigma2, (size_t)q0.nlevels * 4); f.cam = q0.cam;
     f.count = count; f.kps_stride = kps_stride; f.ns.resize((size_t)count); f.status.resize((size_t)count);
     f.monos.resize((size_t)count); f.poses.assign(m.pose_out, m.pose_out + 7 * (size_t)count);
     for (int b = 0; b < count; b++) { f.ns[b] = res[b].n; f.status[b] = res[b].status; f.monos[b] = res[b].mono_index; }
-    std::memcpy(f.pose, m.pose_out, 56);
     f.d_desc = d_desc; f.desc_stride = desc_stride;
   }
   if (count == 1 && t->max_frames == 1) { t->rk_state = 2; t->rk_h = h; t->rk_serial = orb_result_serial(h); }   // (whatever the status)
@@ -364,26 +386,15 @@ int dvm_track_finish(dvm_tracker* t, dvm_orb* h, const dvm_track_queries* q, dvm
 
 // ---- the second half: Tracking::TrackLocalMap (src/Tracking.cc:2668-2740) behind the first
 namespace {
-// the upload block of one call, carved in the mapped staging buffer and at the same offsets in the device copy:
-// [first half's pose 7 doubles][mvScaleFactors 64][mvInvLevelSigma2 64][table: n records][frame_mp: N]
-struct LocalUpload { double* pose; float *scale, *inv_sigma2; LocalPointPod* pts; int32_t* frame_mp; size_t bytes; };
-LocalUpload carve_upload(uint8_t* base, int n, int N) {
-  LocalUpload u;
-  uint8_t* p = base;
-  u.pose = carve<double>(p, 7); u.scale = carve<float>(p, 64); u.inv_sigma2 = carve<float>(p, 64);
-  u.pts = carve<LocalPointPod>(p, (size_t)n); u.frame_mp = carve<int32_t>(p, (size_t)N);
-  u.bytes = (size_t)(p - base);
-  return u;
-}
-// the batch's upload block (dvm_track_local_map_batch), the same way: [mvScaleFactors 64][mvInvLevelSigma2 64][per frame: the first half's
-// pose 7 doubles, LocalFrameArgs, table offset, skip-flag switch][tables: T records, frame b's at qoff[b]][frame_mp: count x kstride].
-// For one frame it is no larger than LocalUpload's block.
-struct LocalUploadBatch {
+// the upload block of one call, carved in the mapped staging buffer and at the same offsets in the device copy: [mvScaleFactors 64]
+// [mvInvLevelSigma2 64][per frame: the first half's pose 7 doubles, LocalFrameArgs, table offset, skip-flag switch][tables: T records,
+// frame b's at qoff[b]][frame_mp: count x kstride]
+struct LocalMapUpload {
   float *scale, *inv_sigma2; double* pose; LocalFrameArgs* fa; int32_t *qoff, *skip_on; LocalPointPod* pts; int32_t* frame_mp; size_t bytes;
 };
 constexpr size_t kFrameRec = 7 * 8 + sizeof(LocalFrameArgs) + 8;     // per frame bytes of the frame block
-LocalUploadBatch carve_upload_batch(uint8_t* base, int count, size_t T, size_t kstride) {
-  LocalUploadBatch u;
+LocalMapUpload carve_local_map_upload(uint8_t* base, int count, size_t T, size_t kstride) {
+  LocalMapUpload u;
   uint8_t* p = base;
   u.scale = carve<float>(p, 64); u.inv_sigma2 = carve<float>(p, 64);
   uint8_t* fb = carve<uint8_t>(p, (size_t)count * kFrameRec);
@@ -402,29 +413,19 @@ int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points) {
     set_error("dvm_tracker_reserve_local_map: more than 1 048 576 local map points per frame"); return DVM_ERR_CAPACITY;
   }
   DVM_HIP(hipSetDevice(t->device));
-  if (t->d_lm) { hipFree(t->d_lm); t->d_lm = nullptr; }
-  if (t->hm_lm) { hipHostFree(t->hm_lm); t->hm_lm = nullptr; }
   t->lm_cap = 0; t->lf.ready = 0; t->lf.batch_ready = 0;
   // P: table entries of one call (a batch: all frames' tables, each rounded up to 64); per keypoint and per frame: max_frames frames
   const size_t P = ((size_t)max_points + 63) & ~(size_t)63, K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
-  t->lm_up_bytes = pad256(B * kFrameRec) + 2 * pad256(256) + pad256(P * sizeof(LocalPointPod)) + pad256(B * K * 4);
+  const size_t up = pad256(B * kFrameRec) + 2 * pad256(256) + pad256(P * sizeof(LocalPointPod)) + pad256(B * K * 4);
   // device: upload copy, per-entry arrays (seen, pos, claims), per-keypoint arrays (frame_mp, skip), pose seeds, query arrays at any stride
   // up to P, ranked lists, counters
-  const size_t dbytes = t->lm_up_bytes + pad256(P) + pad256(P * 12) + pad256(P) + pad256(B * K * 4) + pad256(B * K) + pad256(B * 56) +
+  const size_t dbytes = up + pad256(P) + pad256(P * 12) + pad256(P) + pad256(B * K * 4) + pad256(B * K) + pad256(B * 56) +
                         pad256(P * 32) + 5 * pad256(P * 4) + pad256(P) + pad256(P * 4) + pad256(P * 16) + 2 * pad256(B * 32);
-  const size_t mbytes = t->lm_up_bytes + pad256(B * K * 4) + pad256(B * K) + pad256(P * sizeof(TrackPoint)) + pad256(B * 64) + pad256(B * 56) +
+  const size_t mbytes = up + pad256(B * K * 4) + pad256(B * K) + pad256(P * sizeof(TrackPoint)) + pad256(B * 64) + pad256(B * 56) +
                         3 * pad256(B * 16);
-  if (hipMalloc(reinterpret_cast<void**>(&t->d_lm), dbytes) != hipSuccess) {
-    t->d_lm = nullptr; set_error("dvm_tracker_reserve_local_map: hipMalloc"); return DVM_ERR_CAPACITY;
-  }
-  if (hipHostMalloc(reinterpret_cast<void**>(&t->hm_lm), mbytes, hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&t->hm_lm_dev), t->hm_lm, 0) != hipSuccess) {
-    if (t->hm_lm) hipHostFree(t->hm_lm);
-    t->hm_lm = nullptr; hipFree(t->d_lm); t->d_lm = nullptr;
-    set_error("dvm_tracker_reserve_local_map: mapped host memory"); return DVM_ERR_CAPACITY;
-  }
-  std::memset(t->hm_lm, 0, mbytes);
-  uint8_t* p = t->hm_lm + t->lm_up_bytes;
+  if (const char* what = t->lmw.alloc(dbytes, mbytes)) return reserve_failed("dvm_tracker_reserve_local_map", what);
+  t->lmw.up_bytes = up;
+  uint8_t* p = t->lmw.hm + up;
   auto& r = t->lm;
   r.mp = carve<int32_t>(p, B * K); r.outlier = carve<uint8_t>(p, B * K); r.tp = carve<TrackPoint>(p, P); r.res = carve<int32_t>(p, B * 16);
   r.pose = carve<double>(p, B * 7); r.n_inl = carve<int32_t>(p, B * 4); r.fin = carve<int32_t>(p, B * 4); r.nedges = carve<int32_t>(p, B * 4);
@@ -432,99 +433,13 @@ int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points) {
   return DVM_OK;
 }
 
-int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, int n, const int32_t* frame_mp, float th, int far_points,
-                        float th_far, int32_t* mp_out, uint8_t* outlier, dvm_track_point* track_pts, dvm_track_local_result* res) {
-  if (!t || !h || !mp_out || !outlier || !res || n < 0 || (n && !pts)) return DVM_ERR_INVALID;
+namespace {
+// TrackLocalMap on the `count` frames of the last finish (t->lf), behind the entry points' state checks: the tables, the frames' points,
+// poses and parameters in ONE upload, ONE chain of batched launches, a workgroup (row of workgroups) per frame on grid slots 0..count-1,
+// ONE synchronisation.  A frame the first half did not complete is skipped.
+int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_out* out, dvm_track_local_result* res,
+                  int32_t* status) {
   LocalFrame& f = t->lf;
-  if (!f.ready || f.h != h || orb_result_serial(h) != f.serial) {
-    set_error("dvm_track_local_map: not right after a dvm_track_finish of one frame that returned DVM_TRACK_COMPLETE (same tracker and extractor)");
-    return DVM_ERR_STATE;
-  }
-  if (!t->d_lm) { set_error("dvm_track_local_map: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
-  if (n > t->lm_cap) { set_error("dvm_track_local_map: more local map points than reserved"); return DVM_ERR_CAPACITY; }
-  const int N = f.n;
-  if (N && !frame_mp) return DVM_ERR_INVALID;
-  for (int j = 0; j < N; j++)
-    if (frame_mp[j] < -1 || frame_mp[j] >= n) { set_error("dvm_track_local_map: frame_mp names a point outside the table"); return DVM_ERR_INVALID; }
-  std::memset(res, 0, sizeof(*res));
-  DVM_HIP(hipSetDevice(t->device));
-  hipStream_t s = (hipStream_t)dvm_orb_stream(h);
-  // 1. the table, the frame's points and the level tables: ONE asynchronous copy from the mapped staging block
-  const LocalUpload up = carve_upload(t->hm_lm, n, N);
-  std::memcpy(up.pose, f.pose, 56);                 // the first half's pose (the device casts it to the float pose the frame stores)
-  std::vector<float> scale(256, 1.0f);
-  int rc = dvm_orb_tables(h, scale.data(), nullptr, nullptr, nullptr, nullptr);
-  if (rc != DVM_OK) return rc;
-  std::memcpy(up.scale, scale.data(), 64 * 4);
-  std::memcpy(up.inv_sigma2, f.inv_sigma2, 64 * 4);
-  if (n) std::memcpy(up.pts, pts, (size_t)n * sizeof(LocalPointPod));
-  if (N) std::memcpy(up.frame_mp, frame_mp, (size_t)N * 4);
-  DVM_HIP(hipMemcpyAsync(t->d_lm, t->hm_lm, up.bytes, hipMemcpyHostToDevice, s));
-  const LocalUpload dup = carve_upload(t->d_lm, n, N);
-  // 2. device arrays of this call: per entry at the table's stride, per keypoint at the frame slot's capacity
-  const int Qs = (std::max(n, 1) + 63) & ~63;
-  const size_t K = (size_t)t->kp_cap;
-  LocalQueries LQ;
-  uint8_t* p = t->d_lm + t->lm_up_bytes;
-  LQ.seen = carve<uint8_t>(p, Qs); LQ.pos = carve<float>(p, (size_t)Qs * 3); LQ.claims = carve<uint8_t>(p, Qs);
-  LQ.frame_mp = carve<int32_t>(p, K); LQ.skip = carve<uint8_t>(p, K); LQ.pose_in = carve<double>(p, 7);
-  LQ.qdesc = carve<uint8_t>(p, (size_t)Qs * 32); LQ.qx = carve<float>(p, Qs); LQ.qy = carve<float>(p, Qs); LQ.qr = carve<float>(p, Qs);
-  LQ.qmin = carve<int32_t>(p, Qs); LQ.qmax = carve<int32_t>(p, Qs); LQ.q_claims = carve<uint8_t>(p, Qs); LQ.q_tab = carve<int32_t>(p, Qs);
-  uint32_t* d_ranked = carve<uint32_t>(p, (size_t)Qs * 4);
-  int32_t* d_lres = carve<int32_t>(p, 8);
-  LQ.nq = carve<int32_t>(p, 8);
-  LocalMapArgs A;
-  A.fx = (float)f.cam.fx; A.fy = (float)f.cam.fy; A.cx = (float)f.cam.cx; A.cy = (float)f.cam.cy;
-  A.min_x = f.bounds[0]; A.max_x = f.bounds[1]; A.min_y = f.bounds[2]; A.max_y = f.bounds[3];
-  A.log_scale_factor = f.nlevels > 1 ? (float)std::log((double)scale[1]) : 0.0f;     // Frame::mfLogScaleFactor = log(mfScaleFactor)
-  A.th = th; A.th_far = th_far; A.n_levels = f.nlevels; A.far_points = far_points ? 1 : 0; A.n = n; A.per_frame = nullptr;
-  const TrackBatch TB{1, Qs, (int64_t)f.ocap, LQ.nq};
-  auto& r = t->lm;
-  // 3. SearchLocalPoints up to the queries
-  launch_track_local_prologue(s, dup.pts, dup.frame_mp, dup.pose, dup.scale, f.d_n, f.ocap, A, LQ, track_pts ? t->lmdev(r.tp) : nullptr, t->lmdev(r.res), TB);
-  // 4. the ranked window search on the frame's grid (slot 0, built by the finish), the keypoints with observed points skipped
-  const FrameView FV = frame_view_of(t->grid);
-  launch_match_window_ranked_batch(s, FV, 0, 1, LQ.skip, nullptr, 0, LQ.qdesc, LQ.qx, LQ.qy, LQ.qr, LQ.qmin, LQ.qmax, LQ.nq, Qs, d_ranked);
-  // 5. SearchByProjection(F, points)'s claim replay: mvpMapPoints after the search (device copy for the gather, mapped copy for the host)
-  TrackRequery rq{};
-  rq.F = FV;
-  rq.qdesc = LQ.qdesc; rq.qx = LQ.qx; rq.qy = LQ.qy; rq.qr = LQ.qr; rq.qmin = LQ.qmin; rq.qmax = LQ.qmax;
-  launch_track_claims_local(s, d_ranked, LQ, rq, f.d_un, f.d_n, f.ocap, 100 /* TH_HIGH */, 0.8f, t->d_assign, d_lres, t->lmdev(r.mp),
-                            t->lmdev(r.res) + 8, TB);
-  // 6. PoseOptimization's edges in keypoint order (positions from the table; no min_matches gate: below 3 edges the pose stays), the pose
-  //    seeded from the first half's float pose, the outlier flags and mnMatchesInliers
-  const TrackBatch TE{1, 0, (int64_t)f.ocap, nullptr};
-  launch_track_gather(s, t->d_assign, f.d_un, f.d_n, f.ocap, LQ.pos, dup.inv_sigma2, f.nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp,
-                      t->d_nedges, d_lres, 0, t->lmdev(r.nedges), TE);
-  ba_launch_pose_optimize(s, LQ.pose_in, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, f.ocap, 1, f.cam.fx, f.cam.fy, f.cam.cx, f.cam.cy,
-                          t->lmdev(r.pose), t->d_edge_out, t->lmdev(r.n_inl), t->d_chi);
-  launch_track_finish(s, t->d_assign, f.d_n, f.ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmdev(r.outlier), t->lmdev(r.fin),
-                      d_lres, TE);
-  f.ready = 0; f.batch_ready = 0; f.rkb_ready = 0; t->rk_state = 0;   // once per finish
-  rc = hip_check(hipGetLastError(), "local map chain launch");
-  if (rc != DVM_OK) return rc;
-  // 7. ONE synchronisation: everything the host reads was written to mapped memory by the kernels
-  DVM_HIP(hipStreamSynchronize(s));
-  if (N) { std::memcpy(mp_out, r.mp, (size_t)N * 4); std::memcpy(outlier, r.outlier, (size_t)N); }
-  if (track_pts && n) std::memcpy(track_pts, r.tp, (size_t)n * sizeof(dvm_track_point));
-  res->n_to_match = r.res[0]; res->n_cleared_bad = r.res[1]; res->nmatches = r.res[8]; res->n_requeried = r.res[11];
-  res->n_edges = r.nedges[0]; res->n_inliers = r.n_inl[0]; res->matches_inliers = r.fin[0];
-  std::memcpy(res->pose, r.pose, 56);
-  // Sophus::SE3f(SE3quat_recov.rotation().cast<float>(), SE3quat_recov.translation().cast<float>()) (Optimizer.cc:1023-1025)
-  for (int k = 0; k < 3; k++) res->Tcw.t[k] = (float)res->pose[k];
-  for (int k = 0; k < 4; k++) res->Tcw.q[k] = (float)res->pose[3 + k];
-  return DVM_OK;
-}
-
-int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_out* out,
-                              dvm_track_local_result* res, int32_t* status) {
-  if (!t || !h || !in || !out || !res || !status || count < 1) return DVM_ERR_INVALID;
-  LocalFrame& f = t->lf;
-  if (!f.batch_ready || f.h != h || orb_result_serial(h) != f.serial || f.count != count) {
-    set_error("dvm_track_local_map_batch: not right after a dvm_track_finish[_batch] of `count` frames (same tracker and extractor)");
-    return DVM_ERR_STATE;
-  }
-  if (!t->d_lm) { set_error("dvm_track_local_map_batch: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
   static const bool timing = std::getenv("DVM_TRACK_BATCH_TIMING") != nullptr;       // host-side phase times on stderr
   using clk = std::chrono::steady_clock;
   const clk::time_point tp0 = clk::now();
@@ -548,8 +463,8 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
   if (!live) { f.ready = 0; f.batch_ready = 0; f.rkb_ready = 0; return DVM_OK; }
   const int ocap = f.ocap;
   const size_t Tc = std::max(T, (size_t)64);
-  const LocalUploadBatch up = carve_upload_batch(t->hm_lm, count, Tc, (size_t)ocap);
-  if (up.bytes > t->lm_up_bytes) { set_error("dvm_track_local_map_batch: the upload block exceeds the reservation"); return DVM_ERR_CAPACITY; }
+  const LocalMapUpload up = carve_local_map_upload(t->lmw.hm, count, Tc, (size_t)ocap);
+  if (up.bytes > t->lmw.up_bytes) { set_error("dvm_track_local_map_batch: the upload block exceeds the reservation"); return DVM_ERR_CAPACITY; }
   DVM_HIP(hipSetDevice(t->device));
   hipStream_t s = (hipStream_t)dvm_orb_stream(h);
   // 1. the tables, the frames' points, poses and parameters packed into the mapped staging block by the pool threads: ONE copy
@@ -571,13 +486,13 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
       for (int j = 0; j < ocap; j++) fm[j] = -1;        // a skipped frame holds nothing and searches nothing
     }
   });
-  DVM_HIP(hipMemcpyAsync(t->d_lm, t->hm_lm, up.bytes, hipMemcpyHostToDevice, s));
+  DVM_HIP(hipMemcpyAsync(t->lmw.d, t->lmw.hm, up.bytes, hipMemcpyHostToDevice, s));
   const clk::time_point tp1 = clk::now();
-  const LocalUploadBatch dup = carve_upload_batch(t->d_lm, count, Tc, (size_t)ocap);
+  const LocalMapUpload dup = carve_local_map_upload(t->lmw.d, count, Tc, (size_t)ocap);
   // 2. device arrays of this call: per entry at the frames' offsets, per keypoint at b * ocap
   const size_t Kb = (size_t)count * ocap;
   LocalQueries LQ;
-  uint8_t* p = t->d_lm + t->lm_up_bytes;
+  uint8_t* p = t->lmw.d + t->lmw.up_bytes;
   LQ.seen = carve<uint8_t>(p, Tc); LQ.pos = carve<float>(p, Tc * 3); LQ.claims = carve<uint8_t>(p, Tc);
   LQ.frame_mp = carve<int32_t>(p, Kb); LQ.skip = carve<uint8_t>(p, Kb); LQ.pose_in = carve<double>(p, (size_t)count * 7);
   LQ.qdesc = carve<uint8_t>(p, Tc * 32); LQ.qx = carve<float>(p, Tc); LQ.qy = carve<float>(p, Tc); LQ.qr = carve<float>(p, Tc);
@@ -588,34 +503,38 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
   LocalMapArgs A;
   A.fx = (float)f.cam.fx; A.fy = (float)f.cam.fy; A.cx = (float)f.cam.cx; A.cy = (float)f.cam.cy;
   A.min_x = f.bounds[0]; A.max_x = f.bounds[1]; A.min_y = f.bounds[2]; A.max_y = f.bounds[3];
-  A.log_scale_factor = f.nlevels > 1 ? (float)std::log((double)scale[1]) : 0.0f;
-  A.th = 1.0f; A.th_far = 0.0f; A.n_levels = f.nlevels; A.far_points = 0; A.n = 0; A.per_frame = dup.fa;
+  A.log_scale_factor = f.nlevels > 1 ? (float)std::log((double)scale[1]) : 0.0f;     // Frame::mfLogScaleFactor = log(mfScaleFactor)
+  A.n_levels = f.nlevels; A.per_frame = dup.fa;
   const TrackBatch TB{count, (int)span_max, f.kps_stride, LQ.nq, dup.qoff};
   auto& r = t->lm;
-  // 3. the chain of dvm_track_local_map, a workgroup (row of workgroups) per frame on grid slots 0..count-1
+  // 3. SearchLocalPoints up to the queries
   bool want_tp = false;
   for (int b = 0; b < count; b++) want_tp = want_tp || (f.status[b] == DVM_TRACK_COMPLETE && out[b].track_pts);
-  launch_track_local_prologue(s, dup.pts, dup.frame_mp, dup.pose, dup.scale, f.d_n, ocap, A, LQ, want_tp ? t->lmdev(r.tp) : nullptr, t->lmdev(r.res),
+  launch_track_local_prologue(s, dup.pts, dup.frame_mp, dup.pose, dup.scale, f.d_n, ocap, A, LQ, want_tp ? t->lmw.dev(r.tp) : nullptr, t->lmw.dev(r.res),
                               TB);
+  // 4. the ranked window search on the frames' grids (built by the finish), the keypoints with observed points skipped
   const FrameView FV = frame_view_of(t->grid);
   launch_match_window_ranked_batch(s, FV, 0, count, LQ.skip, dup.skip_on, ocap, LQ.qdesc, LQ.qx, LQ.qy, LQ.qr, LQ.qmin, LQ.qmax, LQ.nq,
                                    (int)span_max, d_ranked, dup.qoff);
+  // 5. SearchByProjection(F, points)'s claim replay: mvpMapPoints after the search (device copy for the gather, mapped copy for the host)
   TrackRequery rq{};
   rq.F = FV;
   rq.qdesc = LQ.qdesc; rq.qx = LQ.qx; rq.qy = LQ.qy; rq.qr = LQ.qr; rq.qmin = LQ.qmin; rq.qmax = LQ.qmax;
-  launch_track_claims_local(s, d_ranked, LQ, rq, f.d_un, f.d_n, ocap, 100 /* TH_HIGH */, 0.8f, t->d_assign, d_lres, t->lmdev(r.mp),
-                            t->lmdev(r.res) + 8 * count, TB);
+  launch_track_claims_local(s, d_ranked, LQ, rq, f.d_un, f.d_n, ocap, 100 /* TH_HIGH */, 0.8f, t->d_assign, d_lres, t->lmw.dev(r.mp),
+                            t->lmw.dev(r.res) + 8 * count, TB);
+  // 6. PoseOptimization's edges in keypoint order (positions from the table; no min_matches gate: below 3 edges the pose stays), the pose
+  //    seeded from the first half's float pose, the outlier flags and mnMatchesInliers
   const TrackBatch TE{count, 0, f.kps_stride, nullptr, dup.qoff};
   launch_track_gather(s, t->d_assign, f.d_un, f.d_n, ocap, LQ.pos, dup.inv_sigma2, f.nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp,
-                      t->d_nedges, d_lres, 0, t->lmdev(r.nedges), TE);
+                      t->d_nedges, d_lres, 0, t->lmw.dev(r.nedges), TE);
   ba_launch_pose_optimize(s, LQ.pose_in, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, f.cam.fx, f.cam.fy, f.cam.cx, f.cam.cy,
-                          t->lmdev(r.pose), t->d_edge_out, t->lmdev(r.n_inl), t->d_chi);
-  launch_track_finish(s, t->d_assign, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmdev(r.outlier), t->lmdev(r.fin),
+                          t->lmw.dev(r.pose), t->d_edge_out, t->lmw.dev(r.n_inl), t->d_chi);
+  launch_track_finish(s, t->d_assign, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmw.dev(r.outlier), t->lmw.dev(r.fin),
                       d_lres, TE);
-  f.ready = 0; f.batch_ready = 0; f.rkb_ready = 0; t->rk_state = 0;   // once per finish
-  rc = hip_check(hipGetLastError(), "batched local map chain launch");
+  t->clear_next();   // once per finish
+  rc = hip_check(hipGetLastError(), "local map chain launch");
   if (rc != DVM_OK) return rc;
-  // 4. ONE synchronisation, then every completed frame's outputs copied out of mapped memory by the pool threads
+  // 7. ONE synchronisation, then every completed frame's outputs copied out of mapped memory by the pool threads
   DVM_HIP(hipStreamSynchronize(s));
   const clk::time_point tp2 = clk::now();
   HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {
@@ -631,6 +550,7 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
     q.n_to_match = pr[0]; q.n_cleared_bad = pr[1]; q.nmatches = cr[0]; q.n_requeried = cr[3];
     q.n_edges = r.nedges[b]; q.n_inliers = r.n_inl[b]; q.matches_inliers = r.fin[4 * b];
     std::memcpy(q.pose, r.pose + 7 * b, 56);
+    // Sophus::SE3f(SE3quat_recov.rotation().cast<float>(), SE3quat_recov.translation().cast<float>()) (Optimizer.cc:1023-1025)
     for (int k = 0; k < 3; k++) q.Tcw.t[k] = (float)q.pose[k];
     for (int k = 0; k < 4; k++) q.Tcw.q[k] = (float)q.pose[3 + k];
   });
@@ -641,24 +561,44 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
   }
   return DVM_OK;
 }
+}  // namespace
 
-// ---- the other way into the second half: Tracking::TrackReferenceKeyFrame (src/Tracking.cc:2461-2520)
-namespace {
-// the upload block of one call, carved in the mapped staging buffer and at the same offsets in the device copy:
-// [pose_in 7 doubles][mvInvLevelSigma2 64][keyframe: desc n x 32, angle n, use n, claims n, pos n x 3][its mFeatVec: nodes, offsets, features]
-struct RefKfUpload {
-  double* pose; float* inv_sigma2; uint8_t* desc; float* angle; uint8_t *use, *claims; float* pos; int32_t *fv_node, *fv_off, *fv_feat; size_t bytes;
-};
-RefKfUpload carve_refkf_upload(uint8_t* base, int n, int nf, int nfeat) {
-  RefKfUpload u;
-  uint8_t* p = base;
-  u.pose = carve<double>(p, 7); u.inv_sigma2 = carve<float>(p, 64);
-  u.desc = carve<uint8_t>(p, (size_t)n * 32); u.angle = carve<float>(p, (size_t)n); u.use = carve<uint8_t>(p, (size_t)n);
-  u.claims = carve<uint8_t>(p, (size_t)n); u.pos = carve<float>(p, (size_t)n * 3);
-  u.fv_node = carve<int32_t>(p, (size_t)nf); u.fv_off = carve<int32_t>(p, (size_t)nf + 1); u.fv_feat = carve<int32_t>(p, (size_t)nfeat);
-  u.bytes = (size_t)(p - base);
-  return u;
+int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, int n, const int32_t* frame_mp, float th, int far_points,
+                        float th_far, int32_t* mp_out, uint8_t* outlier, dvm_track_point* track_pts, dvm_track_local_result* res) {
+  if (!t || !h || !mp_out || !outlier || !res || n < 0 || (n && !pts)) return DVM_ERR_INVALID;
+  LocalFrame& f = t->lf;
+  if (!f.ready || f.h != h || orb_result_serial(h) != f.serial) {
+    set_error("dvm_track_local_map: not right after a dvm_track_finish of one frame that returned DVM_TRACK_COMPLETE (same tracker and extractor)");
+    return DVM_ERR_STATE;
+  }
+  if (!t->lmw.d) { set_error("dvm_track_local_map: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
+  if (n > t->lm_cap) { set_error("dvm_track_local_map: more local map points than reserved"); return DVM_ERR_CAPACITY; }
+  const int N = f.ns[0];
+  if (N && !frame_mp) return DVM_ERR_INVALID;
+  for (int j = 0; j < N; j++)
+    if (frame_mp[j] < -1 || frame_mp[j] >= n) { set_error("dvm_track_local_map: frame_mp names a point outside the table"); return DVM_ERR_INVALID; }
+  // the batch of one frame (ready: its first-half status is DVM_TRACK_COMPLETE)
+  const dvm_local_map_in in{pts, n, frame_mp, th, far_points, th_far};
+  const dvm_local_map_out out{mp_out, outlier, track_pts};
+  int32_t status = 0;
+  return local_map_run(t, h, 1, &in, &out, res, &status);
 }
+
+int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_out* out,
+                              dvm_track_local_result* res, int32_t* status) {
+  if (!t || !h || !in || !out || !res || !status || count < 1) return DVM_ERR_INVALID;
+  LocalFrame& f = t->lf;
+  if (!f.batch_ready || f.h != h || orb_result_serial(h) != f.serial || f.count != count) {
+    set_error("dvm_track_local_map_batch: not right after a dvm_track_finish[_batch] of `count` frames (same tracker and extractor)");
+    return DVM_ERR_STATE;
+  }
+  if (!t->lmw.d) { set_error("dvm_track_local_map_batch: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
+  return local_map_run(t, h, count, in, out, res, status);
+}
+
+// ---- the other way into the second half: Tracking::TrackReferenceKeyFrame (src/Tracking.cc:2461-2520) on the frames of a finish, or on
+//      the one frame of a single-frame begin / finish
+namespace {
 // the checks of dvm_track_reference_keyframe on one frame's keyframe, parameters and outputs (form (b)); cap: keypoints per keyframe
 int check_refkf_frame(const char* fn, const dvm_ref_keyframe* kf, const dvm_track_refkf_params* p, const dvm_track_refkf_out* out, int cap) {
   char msg[256];
@@ -687,193 +627,16 @@ int check_refkf_frame(const char* fn, const dvm_ref_keyframe* kf, const dvm_trac
     }
   return DVM_OK;
 }
-}  // namespace
 
-int dvm_tracker_reserve_reference_keyframe(dvm_tracker* t, int max_kf_keypoints) {
-  if (!t || max_kf_keypoints < 1) return DVM_ERR_INVALID;
-  if (t->max_frames != 1) { set_error("dvm_tracker_reserve_reference_keyframe: a single-frame tracker (dvm_tracker_create)"); return DVM_ERR_STATE; }
-  if (max_kf_keypoints > kFrameCap) { set_error("dvm_tracker_reserve_reference_keyframe: more than 8 192 keyframe keypoints"); return DVM_ERR_CAPACITY; }
-  DVM_HIP(hipSetDevice(t->device));
-  if (t->d_rk) { hipFree(t->d_rk); t->d_rk = nullptr; }
-  if (t->hm_rk) { hipHostFree(t->hm_rk); t->hm_rk = nullptr; }
-  t->rk_cap = 0;
-  const size_t R = (size_t)max_kf_keypoints, K = (size_t)t->kp_cap;
-  t->rk_up_bytes = carve_refkf_upload(nullptr, (int)R, (int)R, (int)R).bytes;
-  // device: upload copy, the transform (word, node, weight), the FeatureVector CSR, counters, match, bin, res
-  const size_t dbytes = t->rk_up_bytes + 2 * pad256(K * 4) + pad256(K * 8) + 2 * pad256(K * 4) + pad256((K + 1) * 4) + pad256(kRefKfCnt * 4) +
-                        2 * pad256(K * 4) + pad256(8 * 4);
-  // mapped: upload staging, BowVector, FeatureVector, match, counters, outlier flags, edges / inliers / nmatchesMap, pose
-  const size_t mbytes = t->rk_up_bytes + pad256(K * 4) + pad256(K * 8) + 2 * pad256(K * 4) + pad256((K + 1) * 4) + pad256(K * 4) + pad256(8 * 4) +
-                        pad256(K) + 3 * pad256(4 * 4) + pad256(7 * 8);
-  if (hipMalloc(reinterpret_cast<void**>(&t->d_rk), dbytes) != hipSuccess) {
-    t->d_rk = nullptr; set_error("dvm_tracker_reserve_reference_keyframe: hipMalloc"); return DVM_ERR_CAPACITY;
-  }
-  if (hipHostMalloc(reinterpret_cast<void**>(&t->hm_rk), mbytes, hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&t->hm_rk_dev), t->hm_rk, 0) != hipSuccess) {
-    if (t->hm_rk) hipHostFree(t->hm_rk);
-    t->hm_rk = nullptr; hipFree(t->d_rk); t->d_rk = nullptr;
-    set_error("dvm_tracker_reserve_reference_keyframe: mapped host memory"); return DVM_ERR_CAPACITY;
-  }
-  std::memset(t->hm_rk, 0, mbytes);
-  uint8_t* p = t->hm_rk + t->rk_up_bytes;
-  auto& r = t->rk;
-  r.bow_ids = carve<int32_t>(p, K); r.bow_vals = carve<double>(p, K); r.fv_node = carve<int32_t>(p, K); r.fv_feat = carve<int32_t>(p, K);
-  r.fv_off = carve<int32_t>(p, K + 1); r.match = carve<int32_t>(p, K); r.cnt = carve<int32_t>(p, 8); r.outlier = carve<uint8_t>(p, K);
-  r.nedges = carve<int32_t>(p, 4); r.n_inl = carve<int32_t>(p, 4); r.fin = carve<int32_t>(p, 4); r.pose = carve<double>(p, 7);
-  t->rk_cap = (int)R;
-  return DVM_OK;
-}
-
-int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, const dvm_ref_keyframe* kf, const dvm_track_refkf_params* p,
-                                 dvm_track_refkf_out* out, dvm_track_refkf_result* res) {
-  if (!t || !h || !voc || !kf || !p || !out || !res) return DVM_ERR_INVALID;
-  if (t->max_frames != 1 || !t->rk_state || t->rk_h != h || orb_result_serial(h) != t->rk_serial) {
-    set_error("dvm_track_reference_keyframe: not right after a dvm_track_begin or dvm_track_finish of one frame (single-frame tracker, same "
-              "extractor), or already run on that frame");
-    return DVM_ERR_STATE;
-  }
-  if (!t->d_rk) { set_error("dvm_track_reference_keyframe: no dvm_tracker_reserve_reference_keyframe on this tracker"); return DVM_ERR_STATE; }
-  const int form = t->rk_state;
-  int rc = check_refkf_frame("dvm_track_reference_keyframe", kf, p, out, t->rk_cap);
-  if (rc != DVM_OK) return rc;
-  if (form == 1 && !(p->bounds[1] > p->bounds[0] && p->bounds[3] > p->bounds[2])) {
-    set_error("dvm_track_reference_keyframe: form (a) builds the grid: empty frame bounds"); return DVM_ERR_INVALID;
-  }
-  if (vocab_device(voc) != t->device) { set_error("dvm_track_reference_keyframe: the vocabulary lives on another device"); return DVM_ERR_INVALID; }
-  const int n = kf->n, nf = kf->fv_n, nfeat = nf ? kf->fv_off[nf] : 0;
-  std::memset(res, 0, sizeof(*res));
-  t->rk_state = 0; t->lf.ready = 0; t->lf.batch_ready = 0; t->lf.rkb_ready = 0;   // once per begin; the second half waits for this call's status
-  DVM_HIP(hipSetDevice(t->device));
-  hipStream_t s = (hipStream_t)dvm_orb_stream(h);
-  const dvm_keypoint* d_kps = nullptr; const uint8_t* d_desc = nullptr; const int32_t* d_n = nullptr; int ocap = 0;
-  rc = dvm_orb_result_device(h, 0, &d_kps, &d_desc, &d_n, &ocap);
-  if (rc != DVM_OK) return rc;
-  if (ocap > t->kp_cap) { set_error("dvm_track_reference_keyframe: the extractor's keypoint capacity exceeds the tracker's"); return DVM_ERR_CAPACITY; }
-  // 1. the keyframe as the matcher and the optimiser read it: ONE asynchronous copy from the mapped staging block
-  const RefKfUpload up = carve_refkf_upload(t->hm_rk, n, nf, nfeat);
-  std::memcpy(up.pose, p->pose_in, 56);
-  std::memset(up.inv_sigma2, 0, 64 * 4);
-  std::memcpy(up.inv_sigma2, p->inv_level_sigma2, (size_t)p->nlevels * 4);
-  if (n) std::memcpy(up.desc, kf->desc, (size_t)n * 32);
-  for (int i = 0; i < n; i++) {
-    const int id = kf->mp[i];
-    const bool use = id >= 0 && !(kf->mp_bad && kf->mp_bad[i]);      // SearchByBoW: no map point or a bad one -> skipped (:247-252)
-    up.angle[i] = kf->kps_un[i].angle; up.use[i] = use ? 1 : 0;
-    up.claims[i] = id >= 0 && kf->mp_nobs[i] > 0 ? 1 : 0;
-    for (int k = 0; k < 3; k++) up.pos[3 * i + k] = id >= 0 ? kf->mp_pos[3 * i + k] : 0.0f;
-  }
-  if (nf) {
-    std::memcpy(up.fv_node, kf->fv_node, (size_t)nf * 4); std::memcpy(up.fv_off, kf->fv_off, ((size_t)nf + 1) * 4);
-    std::memcpy(up.fv_feat, kf->fv_feat, (size_t)nfeat * 4);
-  } else {
-    up.fv_off[0] = 0;
-  }
-  DVM_HIP(hipMemcpyAsync(t->d_rk, t->hm_rk, up.bytes, hipMemcpyHostToDevice, s));
-  const RefKfUpload dup = carve_refkf_upload(t->d_rk, n, nf, nfeat);
-  // 2. form (a): what dvm_track_finish does before its search -- mvKeysUn (Frame.cc:791-818) and AssignFeaturesToGrid
-  LocalFrame& f = t->lf;
-  const bool undist = form == 1 && p->dist && p->dist->k1 != 0.0f;
-  const dvm_keypoint_pod* d_un = f.d_un;
-  if (form == 1) {
-    const dvm_keypoint* un = d_kps;
-    if (undist) {
-      rc = dvm_undistort_keypoints(p->dist, d_kps, reinterpret_cast<dvm_keypoint*>(t->d_kps_un), ocap, 1, s);
-      if (rc != DVM_OK) return rc;
-      un = reinterpret_cast<const dvm_keypoint*>(t->d_kps_un);
-      if (out->kps_un) DVM_HIP(hipMemcpyAsync(t->m.kps_un, t->d_kps_un, (size_t)ocap * sizeof(dvm_keypoint_pod), hipMemcpyDeviceToHost, s));
-    }
-    rc = dvm_frame_build_batch(t->grid, 0, 1, un, ocap, d_desc, (int64_t)ocap * 32, d_n, p->bounds[0], p->bounds[1], p->bounds[2], p->bounds[3], s);
-    if (rc != DVM_OK) return rc;
-    d_un = reinterpret_cast<const dvm_keypoint_pod*>(un);
-  }
-  // 3. the chain: ComputeBoW (transform, then the BowVector / FeatureVector in LDS) -> SearchByBoW -> rotation check -> PoseOptimization's
-  //    edges in keypoint order -> k_pose_optimize seeded from pose_in -> outlier flags and nmatchesMap
-  uint8_t* q = t->d_rk + t->rk_up_bytes;
-  const size_t K = (size_t)t->kp_cap;
-  RefKfArgs A{};
-  int32_t* word = carve<int32_t>(q, K); int32_t* node = carve<int32_t>(q, K); double* w = carve<double>(q, K);
-  A.word = word; A.node = node; A.w = w;
-  A.fv_node = carve<int32_t>(q, K); A.fv_feat = carve<int32_t>(q, K); A.fv_off = carve<int32_t>(q, K + 1); A.cnt = carve<int32_t>(q, kRefKfCnt);
-  A.match = carve<int32_t>(q, K); A.bin = carve<int32_t>(q, K); A.res = carve<int32_t>(q, 8);
-  auto& r = t->rk;
-  A.h_bow_ids = t->rkdev(r.bow_ids); A.h_bow_vals = t->rkdev(r.bow_vals); A.h_fv_node = t->rkdev(r.fv_node); A.h_fv_off = t->rkdev(r.fv_off);
-  A.h_fv_feat = t->rkdev(r.fv_feat); A.h_match = t->rkdev(r.match); A.h_cnt = t->rkdev(r.cnt);
-  A.kdesc = dup.desc; A.kangle = dup.angle; A.kuse = dup.use; A.kfv_node = dup.fv_node; A.kfv_off = dup.fv_off; A.kfv_feat = dup.fv_feat; A.kfv_n = nf;
-  vocab_launch_transform(voc, s, d_desc, ocap, d_n, p->levelsup, word, node, w);
-  launch_refkf_bow(s, A, d_n, ocap);
-  launch_refkf_search(s, A, d_un, d_desc, d_n, ocap, p->th_low, p->nnratio);
-  launch_refkf_settle(s, A, d_n, ocap, p->check_ori);
-  const TrackBatch TE{1, 0, (int64_t)ocap, nullptr, nullptr};
-  launch_track_gather(s, A.match, d_un, d_n, ocap, dup.pos, dup.inv_sigma2, p->nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges, A.res,
-                      p->min_matches, t->rkdev(r.nedges), TE);
-  ba_launch_pose_optimize(s, dup.pose, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, 1, p->cam.fx, p->cam.fy, p->cam.cx, p->cam.cy,
-                          t->rkdev(r.pose), t->d_edge_out, t->rkdev(r.n_inl), t->d_chi);
-  launch_track_finish(s, A.match, d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, dup.claims, t->rkdev(r.outlier), t->rkdev(r.fin), A.res, TE);
-  rc = hip_check(hipGetLastError(), "reference keyframe chain launch");
-  if (rc != DVM_OK) return rc;
-  // 4. ONE synchronisation (behind the download of the extraction in form (a))
-  int N = 0, mono = 0;
-  {
-    // (form (a) without kps but with kps_un and no distortion: mvKeysUn = mvKeys is downloaded into kps_un directly)
-    dvm_keypoint* kp = form != 1 ? nullptr : out->kps ? out->kps : undist ? nullptr : out->kps_un;
-    uint8_t* dp = form == 1 ? out->desc : nullptr;
-    const int cap = kp || dp ? out->cap : ocap;
-    rc = dvm_orb_download_batch(h, 1, &kp, &dp, &cap, &N, &mono);
-    if (rc != DVM_OK) return rc;
-    if (form == 1 && out->kps_un && kp != out->kps_un)
-      std::memcpy(out->kps_un, undist ? reinterpret_cast<const dvm_keypoint*>(t->m.kps_un) : out->kps, (size_t)N * sizeof(dvm_keypoint));
-  }
-  res->n = N; res->mono_index = mono;
-  res->n_bow = r.cnt[0]; res->n_fv = r.cnt[1]; res->nmatches_before_rotation = r.cnt[2]; res->nmatches = r.cnt[3];
-  if (out->bow_ids) std::memcpy(out->bow_ids, r.bow_ids, (size_t)res->n_bow * 4);
-  if (out->bow_vals) std::memcpy(out->bow_vals, r.bow_vals, (size_t)res->n_bow * 8);
-  if (out->fv_node) std::memcpy(out->fv_node, r.fv_node, (size_t)res->n_fv * 4);
-  if (out->fv_off) std::memcpy(out->fv_off, r.fv_off, ((size_t)res->n_fv + 1) * 4);
-  if (out->fv_feat) std::memcpy(out->fv_feat, r.fv_feat, (size_t)r.fv_off[res->n_fv] * 4);
-  // mvpMapPoints: SearchByBoW's matches, those PoseOptimization rejected dropped (Tracking.cc:2486-2516)
-  const bool few = res->nmatches < p->min_matches;
-  for (int j = 0; j < N; j++) {
-    const int a = r.match[j];
-    const int id = a >= 0 ? kf->mp[a] : -1;
-    const bool o = !few && id >= 0 && r.outlier[j];
-    out->mp_out[j] = o ? -1 : id; out->dropped[j] = o ? id : -1; out->outlier[j] = o ? 1 : 0;
-  }
-  if (few) {
-    res->status = DVM_TRACK_FEW_MATCHES;
-    std::memcpy(res->pose, p->pose_in, 56);
-  } else {
-    res->n_edges = r.nedges[0]; res->n_inliers = r.n_inl[0]; res->nmatches_map = r.fin[0]; res->nmatches_after = r.fin[1];
-    std::memcpy(res->pose, r.pose, 56);
-    res->status = res->nmatches_map < p->min_map ? DVM_TRACK_FEW_MAP_MATCHES : DVM_TRACK_COMPLETE;
-  }
-  for (int k = 0; k < 3; k++) res->Tcw.t[k] = (float)res->pose[k];
-  for (int k = 0; k < 4; k++) res->Tcw.q[k] = (float)res->pose[3 + k];
-  // what dvm_track_local_map runs on: the grid (slot 0) and mvKeysUn of the frame, this call's pose
-  if (form == 1) {
-    f.h = h; f.serial = orb_result_serial(h); f.n = N; f.ocap = ocap; f.nlevels = p->nlevels;
-    f.d_un = d_un; f.d_n = d_n;
-    std::memcpy(f.bounds, p->bounds, 16); std::memset(f.inv_sigma2, 0, sizeof(f.inv_sigma2));
-    std::memcpy(f.inv_sigma2, p->inv_level_sigma2, (size_t)p->nlevels * 4); f.cam = p->cam;
-    f.count = 1; f.kps_stride = ocap; f.ns.assign(1, N);
-  }
-  f.status.assign(1, res->status);
-  std::memcpy(f.pose, res->pose, 56);
-  f.ready = res->status == DVM_TRACK_COMPLETE; f.batch_ready = 0;
-  return DVM_OK;
-}
-
-
-// ---- TrackReferenceKeyFrame for the frames of a batched finish (dvm_track_reference_keyframe_batch)
-namespace {
 // the upload block of one call: [mvInvLevelSigma2 64][per frame: pose_in 7 doubles, keyframe offset, node count, res 8][run list][wg_base]
 // [keyframes: T entries, frame b's at qoff[b] -- desc x 32, angle, use, claims, pos x 3, mFeatVec nodes, features][mFeatVec offsets: T + count,
 // frame b's at qoff[b] + b]
-struct RefKfUploadBatch {
+struct KeyframeUpload {
   float* inv_sigma2; double* pose; int32_t *qoff, *kfv_n, *res, *run, *wg_base;
   uint8_t* desc; float* angle; uint8_t *use, *claims; float* pos; int32_t *fv_node, *fv_feat, *fv_off; size_t bytes;
 };
-RefKfUploadBatch carve_refkf_upload_batch(uint8_t* base, int count, size_t T) {
-  RefKfUploadBatch u;
+KeyframeUpload carve_keyframe_upload(uint8_t* base, int count, size_t T) {
+  KeyframeUpload u;
   uint8_t* p = base;
   const size_t B = (size_t)count;
   u.inv_sigma2 = carve<float>(p, 64); u.pose = carve<double>(p, B * 7); u.qoff = carve<int32_t>(p, B); u.kfv_n = carve<int32_t>(p, B);
@@ -894,56 +657,39 @@ RefKfWork carve_refkf_work(uint8_t* base, size_t B, size_t K) {
   r.bytes = (size_t)(p - base);
   return r;
 }
-}  // namespace
-
-int dvm_tracker_reserve_reference_keyframe_batch(dvm_tracker* t, int max_total_kf_keypoints) {
-  if (!t || max_total_kf_keypoints < 1) return DVM_ERR_INVALID;
-  if ((int64_t)max_total_kf_keypoints > (int64_t)t->max_frames * kFrameCap) {
-    set_error("dvm_tracker_reserve_reference_keyframe_batch: more than 8 192 keyframe keypoints per frame"); return DVM_ERR_CAPACITY;
-  }
-  DVM_HIP(hipSetDevice(t->device));
-  if (t->d_rkb) { hipFree(t->d_rkb); t->d_rkb = nullptr; }
-  if (t->hm_rkb) { hipHostFree(t->hm_rkb); t->hm_rkb = nullptr; }
-  t->rkb_cap = 0;
-  const size_t R = ((size_t)max_total_kf_keypoints + 63) & ~(size_t)63, K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
-  t->rkb_up_bytes = carve_refkf_upload_batch(nullptr, (int)B, R).bytes;
-  const size_t dbytes = t->rkb_up_bytes + carve_refkf_work(nullptr, B, K).bytes;
-  // mapped: upload staging, BowVector, FeatureVector, match, counters, outlier flags, edges / inliers / nmatchesMap, pose
-  const size_t mbytes = t->rkb_up_bytes + pad256(B * K * 4) + pad256(B * K * 8) + pad256(B * K * 4) + pad256(B * K * 4) + pad256(B * (K + 1) * 4) +
-                        pad256(B * K * 4) + pad256(B * 8 * 4) + pad256(B * K) + 3 * pad256(B * 4 * 4) + pad256(B * 7 * 8);
-  if (hipMalloc(reinterpret_cast<void**>(&t->d_rkb), dbytes) != hipSuccess) {
-    t->d_rkb = nullptr; set_error("dvm_tracker_reserve_reference_keyframe_batch: hipMalloc"); return DVM_ERR_CAPACITY;
-  }
-  if (hipHostMalloc(reinterpret_cast<void**>(&t->hm_rkb), mbytes, hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&t->hm_rkb_dev), t->hm_rkb, 0) != hipSuccess) {
-    if (t->hm_rkb) hipHostFree(t->hm_rkb);
-    t->hm_rkb = nullptr; hipFree(t->d_rkb); t->d_rkb = nullptr;
-    set_error("dvm_tracker_reserve_reference_keyframe_batch: mapped host memory"); return DVM_ERR_CAPACITY;
-  }
-  std::memset(t->hm_rkb, 0, mbytes);
-  uint8_t* p = t->hm_rkb + t->rkb_up_bytes;
-  auto& r = t->rkb;
+// the mapped results behind the upload staging: BowVector, FeatureVector, match, counters, outlier flags, edges / inliers / nmatchesMap,
+// pose, B slices each; returns their bytes
+size_t carve_refkf_results(uint8_t* base, size_t B, size_t K, RefKfMapped& r) {
+  uint8_t* p = base;
   r.bow_ids = carve<int32_t>(p, B * K); r.bow_vals = carve<double>(p, B * K); r.fv_node = carve<int32_t>(p, B * K); r.fv_feat = carve<int32_t>(p, B * K);
   r.fv_off = carve<int32_t>(p, B * (K + 1)); r.match = carve<int32_t>(p, B * K); r.cnt = carve<int32_t>(p, B * 8); r.outlier = carve<uint8_t>(p, B * K);
   r.nedges = carve<int32_t>(p, B * 4); r.n_inl = carve<int32_t>(p, B * 4); r.fin = carve<int32_t>(p, B * 4); r.pose = carve<double>(p, B * 7);
-  t->rkb_cap = (int)R;
+  return (size_t)(p - base);
+}
+
+// (re)allocates w for keyframes of R entries per call (a multiple of 64) and the tracker's max_frames frames; fn names the caller's errors
+int reserve_refkf(dvm_tracker* t, RefKf& w, size_t R, const char* fn) {
+  DVM_HIP(hipSetDevice(t->device));
+  w.cap = 0;
+  const size_t K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
+  const size_t up = carve_keyframe_upload(nullptr, (int)B, R).bytes;
+  RefKfMapped sized;
+  if (const char* what = w.ws.alloc(up + carve_refkf_work(nullptr, B, K).bytes, up + carve_refkf_results(nullptr, B, K, sized))) return reserve_failed(fn, what);
+  w.ws.up_bytes = up;
+  carve_refkf_results(w.ws.hm + up, B, K, w.r);
+  w.cap = (int)R;
   return DVM_OK;
 }
 
-int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, int count, const dvm_ref_keyframe* const* kfs,
-                                       const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status) {
-  if (!t || !h || !voc || !kfs || !ps || !outs || !res || !status || count < 1) return DVM_ERR_INVALID;
+// dvm_track_reference_keyframe_batch's chain up to its synchronisation, on the frames of the last finish (t->lf) and the working set w.
+// Every keyframe is checked as the single call checks it and the shared parameters equal across the frames that run before anything is
+// enqueued (a refused call leaves the finish for a corrected one); then the keyframes packed back to back into w's staging block by the pool
+// threads, ONE asynchronous copy, and the chain on the extractor's stream.  *nrun_out: the frames that run (none: nothing enqueued),
+// *T_out: their keyframe entries.
+int refkf_enqueue(dvm_tracker* t, RefKf& w, dvm_orb* h, const dvm_vocab* voc, int count, const dvm_ref_keyframe* const* kfs,
+                  const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status, int* nrun_out,
+                  size_t* T_out) {
   LocalFrame& f = t->lf;
-  if (!f.rkb_ready || f.h != h || orb_result_serial(h) != f.serial || f.count != count) {
-    set_error("dvm_track_reference_keyframe_batch: not right after a dvm_track_finish[_batch] of `count` frames (same tracker and extractor), "
-              "or already run on that finish");
-    return DVM_ERR_STATE;
-  }
-  if (!t->d_rkb) { set_error("dvm_track_reference_keyframe_batch: no dvm_tracker_reserve_reference_keyframe_batch on this tracker"); return DVM_ERR_STATE; }
-  static const bool timing = std::getenv("DVM_TRACK_BATCH_TIMING") != nullptr;       // host-side phase times on stderr
-  using clk = std::chrono::steady_clock;
-  const clk::time_point tp0 = clk::now();
-  // every keyframe checked as the single call checks it, the shared parameters equal across the frames that run; nothing enqueued before
   std::vector<int32_t> qoff((size_t)count, 0), run;
   size_t T = 0;
   const dvm_track_refkf_params* p0 = nullptr;
@@ -966,18 +712,19 @@ int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_voc
     run.push_back(b);
   }
   if (p0 && vocab_device(voc) != t->device) { set_error("dvm_track_reference_keyframe_batch: the vocabulary lives on another device"); return DVM_ERR_INVALID; }
-  if (T > (size_t)t->rkb_cap) {
+  if (T > (size_t)w.cap) {
     set_error("dvm_track_reference_keyframe_batch: more keyframe keypoints than reserved (each keyframe's rounded up to 64)"); return DVM_ERR_CAPACITY;
   }
   const int ocap = f.ocap;
-  const RefKfUploadBatch up = carve_refkf_upload_batch(t->hm_rkb, count, std::max(T, (size_t)64));
-  if (up.bytes > t->rkb_up_bytes || ocap > t->kp_cap) {
+  const KeyframeUpload up = carve_keyframe_upload(w.ws.hm, count, std::max(T, (size_t)64));
+  if (up.bytes > w.ws.up_bytes || ocap > t->kp_cap) {
     set_error("dvm_track_reference_keyframe_batch: the upload block exceeds the reservation"); return DVM_ERR_CAPACITY;
   }
   // accepted: once per finish, and the single call no longer runs on it
   for (int b = 0; b < count; b++) { std::memset(&res[b], 0, sizeof(res[b])); status[b] = f.status[b]; }
   f.rkb_ready = 0; t->rk_state = 0;
   const int nrun = (int)run.size();
+  *nrun_out = nrun; *T_out = T;
   if (!nrun) return DVM_OK;
   const dvm_track_refkf_params& P0 = *p0;
   DVM_HIP(hipSetDevice(t->device));
@@ -1018,20 +765,20 @@ int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_voc
       fo[0] = 0;
     }
   });
-  DVM_HIP(hipMemcpyAsync(t->d_rkb, t->hm_rkb, up.bytes, hipMemcpyHostToDevice, s));
-  const clk::time_point tp1 = clk::now();
-  const RefKfUploadBatch dup = carve_refkf_upload_batch(t->d_rkb, count, std::max(T, (size_t)64));
-  // 2. the chain of dvm_track_reference_keyframe on the finish's frames: the transform of all frames that run in one launch, a workgroup
-  //    per frame for the BoW and the rotation check, each frame's keyframe nodes on their own workgroups, then the edge gather, the pose
-  //    and the outlier flags as the batched first half runs them (a frame that does not run: an empty workgroup in each)
-  const RefKfWork W = carve_refkf_work(t->d_rkb + t->rkb_up_bytes, (size_t)t->max_frames, (size_t)t->kp_cap);
-  auto& r = t->rkb;
+  DVM_HIP(hipMemcpyAsync(w.ws.d, w.ws.hm, up.bytes, hipMemcpyHostToDevice, s));
+  const KeyframeUpload dup = carve_keyframe_upload(w.ws.d, count, std::max(T, (size_t)64));
+  // 2. the chain: ComputeBoW (the transform of all frames that run in one launch, then the BowVector / FeatureVector in LDS, a workgroup per
+  //    frame) -> SearchByBoW (each frame's keyframe nodes on their own workgroups) -> rotation check -> PoseOptimization's edges in keypoint
+  //    order -> k_pose_optimize seeded from pose_in -> outlier flags and nmatchesMap, as the batched first half runs them (a frame that
+  //    does not run: an empty workgroup in each)
+  const RefKfWork W = carve_refkf_work(w.ws.d + w.ws.up_bytes, (size_t)t->max_frames, (size_t)t->kp_cap);
+  const RefKfMapped& r = w.r;
   RefKfArgs A{};
   A.word = W.word; A.node = W.node; A.w = W.w; A.fv_node = W.fv_node; A.fv_feat = W.fv_feat; A.fv_off = W.fv_off; A.cnt = W.cnt;
   A.match = W.match; A.bin = W.bin; A.res = dup.res;
-  A.h_bow_ids = t->rkbdev(r.bow_ids); A.h_bow_vals = t->rkbdev(r.bow_vals); A.h_fv_node = t->rkbdev(r.fv_node); A.h_fv_off = t->rkbdev(r.fv_off);
-  A.h_fv_feat = t->rkbdev(r.fv_feat); A.h_match = t->rkbdev(r.match); A.h_cnt = t->rkbdev(r.cnt);
-  A.kdesc = dup.desc; A.kangle = dup.angle; A.kuse = dup.use; A.kfv_node = dup.fv_node; A.kfv_off = dup.fv_off; A.kfv_feat = dup.fv_feat; A.kfv_n = 0;
+  A.h_bow_ids = w.ws.dev(r.bow_ids); A.h_bow_vals = w.ws.dev(r.bow_vals); A.h_fv_node = w.ws.dev(r.fv_node); A.h_fv_off = w.ws.dev(r.fv_off);
+  A.h_fv_feat = w.ws.dev(r.fv_feat); A.h_match = w.ws.dev(r.match); A.h_cnt = w.ws.dev(r.cnt);
+  A.kdesc = dup.desc; A.kangle = dup.angle; A.kuse = dup.use; A.kfv_node = dup.fv_node; A.kfv_off = dup.fv_off; A.kfv_feat = dup.fv_feat;
   A.run = dup.run; A.kqoff = dup.qoff; A.kfv_nb = dup.kfv_n; A.wg_base = dup.wg_base; A.nrun = nrun; A.nwg = nwg;
   A.kps_stride = f.kps_stride; A.desc_stride = f.desc_stride;
   vocab_launch_transform(voc, s, f.d_desc, ocap, f.d_n, P0.levelsup, W.word, W.node, W.w, dup.run, nrun, f.desc_stride);
@@ -1040,22 +787,26 @@ int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_voc
   launch_refkf_settle(s, A, f.d_n, ocap, P0.check_ori);
   const TrackBatch TE{count, 0, f.kps_stride, nullptr, dup.qoff};
   launch_track_gather(s, W.match, f.d_un, f.d_n, ocap, dup.pos, dup.inv_sigma2, P0.nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges,
-                      dup.res, P0.min_matches, t->rkbdev(r.nedges), TE);
+                      dup.res, P0.min_matches, w.ws.dev(r.nedges), TE);
   ba_launch_pose_optimize(s, dup.pose, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, P0.cam.fx, P0.cam.fy, P0.cam.cx, P0.cam.cy,
-                          t->rkbdev(r.pose), t->d_edge_out, t->rkbdev(r.n_inl), t->d_chi);
-  launch_track_finish(s, W.match, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, dup.claims, t->rkbdev(r.outlier), t->rkbdev(r.fin), dup.res, TE);
-  int rc = hip_check(hipGetLastError(), "batched reference keyframe chain launch");
-  if (rc != DVM_OK) return rc;
-  // 3. ONE synchronisation, then every frame that ran copied out of mapped memory by the pool threads
-  DVM_HIP(hipStreamSynchronize(s));
-  const clk::time_point tp2 = clk::now();
+                          w.ws.dev(r.pose), t->d_edge_out, w.ws.dev(r.n_inl), t->d_chi);
+  launch_track_finish(s, W.match, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, dup.claims, w.ws.dev(r.outlier), w.ws.dev(r.fin), dup.res, TE);
+  return hip_check(hipGetLastError(), "reference keyframe chain launch");
+}
+
+// after refkf_enqueue's chain is through: every frame that ran copied out of w's mapped results by the pool threads, and what the second
+// half runs on -- such a frame complete or not by this call's status, seeded from its pose
+void refkf_copy_out(dvm_tracker* t, const RefKf& w, int count, const dvm_ref_keyframe* const* kfs, const dvm_track_refkf_params* ps,
+                    const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status) {
+  LocalFrame& f = t->lf;
+  const RefKfMapped& r = w.r;
+  const size_t K = (size_t)f.ocap;
   HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {
     const dvm_ref_keyframe* kf = kfs[b];
     if (!kf) return;
     const dvm_track_refkf_params* p = &ps[b];
     const dvm_track_refkf_out* out = &outs[b];
     dvm_track_refkf_result* q = &res[b];
-    const size_t K = (size_t)ocap;
     const int N = f.ns[b];
     const int32_t* cnt = r.cnt + 8 * b;
     q->n = N; q->mono_index = f.monos[b];
@@ -1086,14 +837,120 @@ int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_voc
     }
     for (int k = 0; k < 3; k++) q->Tcw.t[k] = (float)q->pose[k];
     for (int k = 0; k < 4; k++) q->Tcw.q[k] = (float)q->pose[3 + k];
-    // what dvm_track_local_map_batch runs on: this frame complete or not by this call's status, seeded from its pose
     status[b] = q->status; f.status[b] = q->status;
     std::memcpy(f.poses.data() + 7 * b, q->pose, 56);
   });
-  if (count == 1) {       // and dvm_track_local_map, as after dvm_track_reference_keyframe
-    std::memcpy(f.pose, f.poses.data(), 56);
-    f.ready = f.status[0] == DVM_TRACK_COMPLETE;
+  if (count == 1) f.ready = f.status[0] == DVM_TRACK_COMPLETE;     // and dvm_track_local_map on the one frame
+}
+}  // namespace
+
+int dvm_tracker_reserve_reference_keyframe(dvm_tracker* t, int max_kf_keypoints) {
+  if (!t || max_kf_keypoints < 1) return DVM_ERR_INVALID;
+  if (t->max_frames != 1) { set_error("dvm_tracker_reserve_reference_keyframe: a single-frame tracker (dvm_tracker_create)"); return DVM_ERR_STATE; }
+  if (max_kf_keypoints > kFrameCap) { set_error("dvm_tracker_reserve_reference_keyframe: more than 8 192 keyframe keypoints"); return DVM_ERR_CAPACITY; }
+  t->rk_cap = 0;
+  const int rc = reserve_refkf(t, t->rk, ((size_t)max_kf_keypoints + 63) & ~(size_t)63, "dvm_tracker_reserve_reference_keyframe");
+  if (rc == DVM_OK) t->rk_cap = max_kf_keypoints;
+  return rc;
+}
+
+int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, const dvm_ref_keyframe* kf, const dvm_track_refkf_params* p,
+                                 dvm_track_refkf_out* out, dvm_track_refkf_result* res) {
+  if (!t || !h || !voc || !kf || !p || !out || !res) return DVM_ERR_INVALID;
+  if (t->max_frames != 1 || !t->rk_state || t->rk_h != h || orb_result_serial(h) != t->rk_serial) {
+    set_error("dvm_track_reference_keyframe: not right after a dvm_track_begin or dvm_track_finish of one frame (single-frame tracker, same "
+              "extractor), or already run on that frame");
+    return DVM_ERR_STATE;
   }
+  if (!t->rk.ws.d) { set_error("dvm_track_reference_keyframe: no dvm_tracker_reserve_reference_keyframe on this tracker"); return DVM_ERR_STATE; }
+  const int form = t->rk_state;
+  int rc = check_refkf_frame("dvm_track_reference_keyframe", kf, p, out, t->rk_cap);
+  if (rc != DVM_OK) return rc;
+  if (form == 1 && !(p->bounds[1] > p->bounds[0] && p->bounds[3] > p->bounds[2])) {
+    set_error("dvm_track_reference_keyframe: form (a) builds the grid: empty frame bounds"); return DVM_ERR_INVALID;
+  }
+  if (vocab_device(voc) != t->device) { set_error("dvm_track_reference_keyframe: the vocabulary lives on another device"); return DVM_ERR_INVALID; }
+  std::memset(res, 0, sizeof(*res));
+  t->clear_next();   // once per begin; the second half waits for this call's status
+  DVM_HIP(hipSetDevice(t->device));
+  hipStream_t s = (hipStream_t)dvm_orb_stream(h);
+  LocalFrame& f = t->lf;
+  const bool undist = form == 1 && p->dist && p->dist->k1 != 0.0f;
+  if (form == 1) {
+    // what dvm_track_finish does before its search -- mvKeysUn (Frame.cc:791-818) and AssignFeaturesToGrid -- and what it leaves for the
+    // second half, as a finish of one frame (the keypoint count and monoIndex from the download below)
+    const dvm_keypoint* d_kps = nullptr; const uint8_t* d_desc = nullptr; const int32_t* d_n = nullptr; int ocap = 0;
+    rc = dvm_orb_result_device(h, 0, &d_kps, &d_desc, &d_n, &ocap);
+    if (rc != DVM_OK) return rc;
+    if (ocap > t->kp_cap) { set_error("dvm_track_reference_keyframe: the extractor's keypoint capacity exceeds the tracker's"); return DVM_ERR_CAPACITY; }
+    const dvm_keypoint* un = d_kps;
+    if (undist) {
+      rc = dvm_undistort_keypoints(p->dist, d_kps, reinterpret_cast<dvm_keypoint*>(t->d_kps_un), ocap, 1, s);
+      if (rc != DVM_OK) return rc;
+      un = reinterpret_cast<const dvm_keypoint*>(t->d_kps_un);
+      if (out->kps_un) DVM_HIP(hipMemcpyAsync(t->m.kps_un, t->d_kps_un, (size_t)ocap * sizeof(dvm_keypoint_pod), hipMemcpyDeviceToHost, s));
+    }
+    rc = dvm_frame_build_batch(t->grid, 0, 1, un, ocap, d_desc, (int64_t)ocap * 32, d_n, p->bounds[0], p->bounds[1], p->bounds[2], p->bounds[3], s);
+    if (rc != DVM_OK) return rc;
+    f.h = h; f.serial = orb_result_serial(h); f.ocap = ocap; f.nlevels = p->nlevels;
+    f.d_un = reinterpret_cast<const dvm_keypoint_pod*>(un); f.d_n = d_n;
+    std::memcpy(f.bounds, p->bounds, 16); std::memset(f.inv_sigma2, 0, sizeof(f.inv_sigma2));
+    std::memcpy(f.inv_sigma2, p->inv_level_sigma2, (size_t)p->nlevels * 4); f.cam = p->cam;
+    f.count = 1; f.kps_stride = ocap; f.d_desc = d_desc; f.desc_stride = (int64_t)ocap * 32;
+    f.ns.assign(1, 0); f.status.assign(1, 0); f.monos.assign(1, 0); f.poses.assign(7, 0.0);
+  }
+  // the batched chain on the one frame
+  int32_t status = 0;
+  int nrun = 0;
+  size_t T = 0;
+  rc = refkf_enqueue(t, t->rk, h, voc, 1, &kf, p, out, res, &status, &nrun, &T);
+  if (rc != DVM_OK) return rc;
+  // ONE synchronisation (behind the download of the extraction in form (a))
+  if (form == 1) {
+    // (without kps but with kps_un and no distortion: mvKeysUn = mvKeys is downloaded into kps_un directly)
+    dvm_keypoint* kp = out->kps ? out->kps : undist ? nullptr : out->kps_un;
+    uint8_t* dp = out->desc;
+    const int cap = kp || dp ? out->cap : f.ocap;
+    rc = dvm_orb_download_batch(h, 1, &kp, &dp, &cap, f.ns.data(), f.monos.data());
+    if (rc != DVM_OK) return rc;
+    if (out->kps_un && kp != out->kps_un)
+      std::memcpy(out->kps_un, undist ? reinterpret_cast<const dvm_keypoint*>(t->m.kps_un) : out->kps, (size_t)f.ns[0] * sizeof(dvm_keypoint));
+  } else {
+    DVM_HIP(hipStreamSynchronize(s));
+  }
+  refkf_copy_out(t, t->rk, 1, &kf, p, out, res, &status);
+  return DVM_OK;
+}
+
+int dvm_tracker_reserve_reference_keyframe_batch(dvm_tracker* t, int max_total_kf_keypoints) {
+  if (!t || max_total_kf_keypoints < 1) return DVM_ERR_INVALID;
+  if ((int64_t)max_total_kf_keypoints > (int64_t)t->max_frames * kFrameCap) {
+    set_error("dvm_tracker_reserve_reference_keyframe_batch: more than 8 192 keyframe keypoints per frame"); return DVM_ERR_CAPACITY;
+  }
+  return reserve_refkf(t, t->rkb, ((size_t)max_total_kf_keypoints + 63) & ~(size_t)63, "dvm_tracker_reserve_reference_keyframe_batch");
+}
+
+int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, int count, const dvm_ref_keyframe* const* kfs,
+                                       const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status) {
+  if (!t || !h || !voc || !kfs || !ps || !outs || !res || !status || count < 1) return DVM_ERR_INVALID;
+  LocalFrame& f = t->lf;
+  if (!f.rkb_ready || f.h != h || orb_result_serial(h) != f.serial || f.count != count) {
+    set_error("dvm_track_reference_keyframe_batch: not right after a dvm_track_finish[_batch] of `count` frames (same tracker and extractor), "
+              "or already run on that finish");
+    return DVM_ERR_STATE;
+  }
+  if (!t->rkb.ws.d) { set_error("dvm_track_reference_keyframe_batch: no dvm_tracker_reserve_reference_keyframe_batch on this tracker"); return DVM_ERR_STATE; }
+  static const bool timing = std::getenv("DVM_TRACK_BATCH_TIMING") != nullptr;       // host-side phase times on stderr
+  using clk = std::chrono::steady_clock;
+  const clk::time_point tp0 = clk::now();
+  int nrun = 0;
+  size_t T = 0;
+  int rc = refkf_enqueue(t, t->rkb, h, voc, count, kfs, ps, outs, res, status, &nrun, &T);
+  if (rc != DVM_OK || !nrun) return rc;
+  const clk::time_point tp1 = clk::now();
+  DVM_HIP(hipStreamSynchronize((hipStream_t)dvm_orb_stream(h)));
+  const clk::time_point tp2 = clk::now();
+  refkf_copy_out(t, t->rkb, count, kfs, ps, outs, res, status);
   if (timing) {
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::fprintf(stderr, "track reference keyframe batch of %d (%d run, %zu entries): pack + enqueue %.3f  wait %.3f  results out %.3f ms\n", count,

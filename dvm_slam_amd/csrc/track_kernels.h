@@ -27,10 +27,10 @@ struct LocalPointPod {  // == dvm_local_point
   int32_t n_obs, bad;
 };
 struct LocalFrameArgs { int32_t n, far_points; float th, th_far; };   // one frame's table size and SearchByProjection's th / far-point filter
-struct LocalMapArgs {   // the call's constants: camera, bounds, level count, SearchByProjection's th / far-point filter, table size
-  float fx, fy, cx, cy, min_x, max_x, min_y, max_y, log_scale_factor, th, th_far;
-  int32_t n_levels, far_points, n;
-  const LocalFrameArgs* per_frame;   // device, may be null: frame b's n / th / far_points / th_far from per_frame[b] instead of the above
+struct LocalMapArgs {   // the call's constants: camera, bounds, level count; per frame its table size and SearchByProjection's th / far-point filter
+  float fx, fy, cx, cy, min_x, max_x, min_y, max_y, log_scale_factor;
+  int32_t n_levels;
+  const LocalFrameArgs* per_frame;   // device [count]
 };
 // what k_track_local_prologue leaves for the search (device arrays; the query arrays at the call's stride)
 struct LocalQueries {
@@ -43,8 +43,8 @@ struct LocalQueries {
   uint8_t* claims;             // [n] Observations() > 0 of every entry
   double* pose_in;             // [7] the first half's float pose widened: PoseOptimization's seed
 };
-// pose_first: the first half's optimised pose (t, q doubles); scale: mvScaleFactors [64]; B: count = 1, qstride = the table's stride, or
-// count frames with B.qoff (frame b's table, per-entry and query arrays at qoff[b], its per-keypoint arrays at b * kp_cap, A.per_frame)
+// pose_first: the first half's optimised poses (t, q doubles); scale: mvScaleFactors [64]; B: count frames with B.qoff (frame b's table,
+// per-entry and query arrays at qoff[b], its per-keypoint arrays at b * kp_cap, A.per_frame[b])
 void launch_track_local_prologue(hipStream_t s, const LocalPointPod* pts, const int32_t* frame_mp_in, const double* pose_first, const float* scale,
                                  const int32_t* d_n, int kp_cap, const LocalMapArgs& A, const LocalQueries& LQ, TrackPoint* track_pts_host,
                                  int32_t* res_host, const TrackBatch& B);
@@ -76,10 +76,10 @@ struct RefKfArgs {
   int32_t* h_bow_ids; double* h_bow_vals; int32_t *h_fv_node, *h_fv_off, *h_fv_feat; int32_t* h_match; int32_t* h_cnt;
   // the keyframe (device copy of the upload)
   const uint8_t* kdesc; const float* kangle; const uint8_t* kuse;   // [n]: descriptor, mvKeysUn angle, has a good map point
-  const int32_t *kfv_node, *kfv_off, *kfv_feat; int32_t kfv_n;      // its mFeatVec
-  // a batch (dvm_track_reference_keyframe_batch; null for one frame): frame b's per-frame arrays above at b * cap (fv_off at b * (cap + 1),
-  // cnt at b * kRefKfCnt, res at 8 b, h_cnt at 8 b), its keyframe at kqoff[b] entries of the upload (kfv_off at kqoff[b] + b), its frame
-  // inputs at b * kps_stride / b * desc_stride
+  const int32_t *kfv_node, *kfv_off, *kfv_feat;                     // its mFeatVec
+  // the frames (one frame is a batch of one): frame b's per-frame arrays above at b * cap (fv_off at b * (cap + 1), cnt at b * kRefKfCnt,
+  // res at 8 b, h_cnt at 8 b), its keyframe at kqoff[b] entries of the upload (kfv_off at kqoff[b] + b), its frame inputs at
+  // b * kps_stride / b * desc_stride
   const int32_t* run;       // device [nrun]: the frames that run; workgroup r of the bow / settle kernels works on frame run[r]
   const int32_t* kqoff;     // device [count]
   const int32_t* kfv_nb;    // device [count]: the keyframes' node counts
@@ -89,8 +89,8 @@ struct RefKfArgs {
 };
 // one workgroup (per frame that runs): the frame's BowVector (mapped) and FeatureVector (device + mapped); the match state reset
 void launch_refkf_bow(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap);
-// SearchByBoW's matching: one wave per keyframe node (a batch: each frame its own range of workgroups, A.wg_base); then the rotation
-// check and res[] for the edge gather, one workgroup per frame that runs
+// SearchByBoW's matching: one wave per keyframe node (each frame its own range of workgroups, A.wg_base); then the rotation check and
+// res[] for the edge gather, one workgroup per frame that runs
 void launch_refkf_search(hipStream_t s, const RefKfArgs& A, const dvm_keypoint_pod* kps_un, const uint8_t* desc, const int32_t* d_n, int cap, int th_low,
                          float nnratio);
 void launch_refkf_settle(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap, int check_ori);

@@ -409,8 +409,8 @@ __global__ void __launch_bounds__(256) k_track_finish(int32_t* __restrict__ assi
 //   isInFrustum(pMP, 0.5) of every entry (frustum_point.h); mbTrackInView false for seen and bad entries; nToMatch
 //   the far-point filter (:52-53), radius RadiusByViewingCos(viewCos) * (th != 1 ? th : 1) * mvScaleFactors[level], levels
 //     [level - 1, level]; the in-view points compacted into the query arrays IN TABLE ORDER (the claim replay's order)
-// tables: scale[64] = mvScaleFactors.  res_host[0] = nToMatch, res_host[1] = frame points cleared as bad.  A batch (B.qoff) reads each
-// frame's table size, th and far-point filter from A.per_frame[b]; an empty table with no frame points leaves nothing to search.
+// tables: scale[64] = mvScaleFactors.  res_host[0] = nToMatch, res_host[1] = frame points cleared as bad.  Each frame's table size, th
+// and far-point filter from A.per_frame[b]; an empty table with no frame points leaves nothing to search.
 __global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointPod* __restrict__ pts, const int32_t* __restrict__ frame_mp_in,
                                                                const double* __restrict__ pose_first, const float* __restrict__ scale,
                                                                const int32_t* __restrict__ d_n, int kp_cap, LocalMapArgs A, LocalQueries LQ,
@@ -418,17 +418,17 @@ __global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointP
   __shared__ int s_wave[16];
   __shared__ int s_cnt[2];
   __shared__ float s_scale[64];
+  const LocalFrameArgs fa = A.per_frame[blockIdx.x];
   {
     const int b = blockIdx.x;
     const size_t qo = B.qo(b), ko = (size_t)b * kp_cap;
-    if (A.per_frame) { const LocalFrameArgs fa = A.per_frame[b]; A.n = fa.n; A.far_points = fa.far_points; A.th = fa.th; A.th_far = fa.th_far; }
     pts += qo; frame_mp_in += ko; pose_first += 7 * b; d_n += b; res_host += 8 * b;
     if (tp_host) tp_host += qo;
     LQ.qdesc += qo * 32; LQ.qx += qo; LQ.qy += qo; LQ.qr += qo; LQ.qmin += qo; LQ.qmax += qo; LQ.q_claims += qo; LQ.q_tab += qo; LQ.nq += b;
     LQ.seen += qo; LQ.frame_mp += ko; LQ.skip += ko; LQ.pos += qo * 3; LQ.claims += qo; LQ.pose_in += 7 * b;
   }
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int N = min(*d_n, kp_cap), n = A.n;
+  const int N = min(*d_n, kp_cap), n = fa.n;
   if (tid < 2) s_cnt[tid] = 0;
   if (tid < 64) s_scale[tid] = tid < A.n_levels ? scale[tid] : 1.0f;
   for (int i = tid; i < n; i += 1024) LQ.seen[i] = 0;
@@ -475,7 +475,7 @@ __global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointP
       if (tp_host) tp_host[i] = o;
       LQ.pos[3 * (size_t)i] = P.pos[0]; LQ.pos[3 * (size_t)i + 1] = P.pos[1]; LQ.pos[3 * (size_t)i + 2] = P.pos[2];
       LQ.claims[i] = P.n_obs > 0 ? 1 : 0;
-      query = o.in_view && !(A.far_points && o.depth > A.th_far);
+      query = o.in_view && !(fa.far_points && o.depth > fa.th_far);
     }
     const unsigned long long m = __ballot(query);
     if (lane == 0) s_wave[wv] = __popcll(m);
@@ -491,7 +491,7 @@ __global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointP
     if (query) {
       const LocalPointPod& P = pts[i];
       float r = o.view_cos > 0.998 ? 2.5f : 4.0f;            // RadiusByViewingCos (ORBmatcher.cc:207-212)
-      if (A.th != 1.0f) r *= A.th;
+      if (fa.th != 1.0f) r *= fa.th;
       LQ.qx[pos] = o.proj_x; LQ.qy[pos] = o.proj_y; LQ.qr[pos] = r * s_scale[min(max(o.level, 0), 63)];
       LQ.qmin[pos] = o.level - 1; LQ.qmax[pos] = o.level;
       LQ.q_claims[pos] = P.n_obs > 0 ? 1 : 0; LQ.q_tab[pos] = i;
@@ -565,14 +565,14 @@ __device__ int for_each_run(const uint64_t* keys, int M, int* s_wave, Fn f) {
 }
 }  // namespace
 
-// a batch's frame b: every per-frame pointer of A moved to that frame's slice (RefKfArgs); one frame (A.run null) stays as it is
+// frame b: every per-frame pointer of A moved to that frame's slice (RefKfArgs)
 __device__ __forceinline__ void refkf_at(RefKfArgs& A, int b, int cap) {
   const size_t o = (size_t)b * cap;
   A.word += o; A.node += o; A.w += o; A.fv_node += o; A.fv_feat += o; A.fv_off += o + b; A.cnt += (size_t)b * kRefKfCnt; A.match += o; A.bin += o;
   A.res += 8 * b;
   A.h_bow_ids += o; A.h_bow_vals += o; A.h_fv_node += o; A.h_fv_off += o + b; A.h_fv_feat += o; A.h_match += o; A.h_cnt += 8 * b;
   const size_t k = (size_t)A.kqoff[b];
-  A.kdesc += k * 32; A.kangle += k; A.kuse += k; A.kfv_node += k; A.kfv_off += k + b; A.kfv_feat += k; A.kfv_n = A.kfv_nb[b];
+  A.kdesc += k * 32; A.kangle += k; A.kuse += k; A.kfv_node += k; A.kfv_off += k + b; A.kfv_feat += k;
 }
 
 // Frame::ComputeBoW's bookkeeping (TemplatedVocabulary::transform's TF_IDF branch, DBoW2 TemplatedVocabulary.h:1098-1138, as the host
@@ -583,9 +583,9 @@ __device__ __forceinline__ void refkf_at(RefKfArgs& A, int b, int cap) {
 //     value divided by the norm (correctly rounded double division);
 //   FeatureVector: sort ((unsigned)node << 32 | feature): nodes ascending as unsigned (node -1 last), features ascending inside a node.
 // It also resets the match state of the search behind it.  LDS: 16 B per entry of the sort (the capacity rounded up to a power of two).
-// A batch: one workgroup per frame that runs (A.run).
+// One workgroup per frame that runs (A.run).
 __global__ void __launch_bounds__(1024) k_refkf_bow(RefKfArgs A, const int32_t* __restrict__ d_n, int cap, int P) {
-  if (A.run) { const int b = A.run[blockIdx.x]; refkf_at(A, b, cap); d_n += b; }
+  { const int b = A.run[blockIdx.x]; refkf_at(A, b, cap); d_n += b; }
   extern __shared__ __attribute__((aligned(16))) uint8_t refkf_smem[];
   uint64_t* keys = reinterpret_cast<uint64_t*>(refkf_smem);    // [P]
   double* vals = reinterpret_cast<double*>(keys + P);          // [P]
@@ -659,14 +659,14 @@ __global__ void __launch_bounds__(1024) k_refkf_bow(RefKfArgs A, const int32_t* 
 // merged), so every decision sees exactly the claims the reference's walk has made by then.  The rotation histogram only counts, so its
 // global atomics may come in any order.  LDS: the claim flag of every frame keypoint (1 B each).
 // Known limit: a vocabulary with L - levelsup <= 0 puts every feature into node 0: one wave then walks the whole frame.
-// A batch: each frame that runs has its own range of workgroups (A.wg_base), so a workgroup's claim flags -- indexed by the frame's
-// keypoint -- never mix two frames.
+// Each frame that runs has its own range of workgroups (A.wg_base), so a workgroup's claim flags -- indexed by the frame's keypoint --
+// never mix two frames.
 __global__ void __launch_bounds__(256) k_refkf_search(RefKfArgs A, const dvm_keypoint_pod* __restrict__ kps_un, const uint8_t* __restrict__ desc,
                                                       const int32_t* __restrict__ d_n, int cap, int th_low, float nnratio) {
   extern __shared__ __attribute__((aligned(16))) uint8_t refkf_smem[];
   uint8_t* s_claim = refkf_smem;   // [cap]
-  int wg = blockIdx.x;
-  if (A.run) {
+  int wg = blockIdx.x, kfv_n;
+  {
     int lo = 0, hi = A.nrun - 1;            // the run r with wg_base[r] <= blockIdx.x < wg_base[r + 1]
     while (lo < hi) {
       const int mid = (lo + hi + 1) >> 1;
@@ -674,6 +674,7 @@ __global__ void __launch_bounds__(256) k_refkf_search(RefKfArgs A, const dvm_key
     }
     const int b = A.run[lo];
     wg -= A.wg_base[lo];
+    kfv_n = A.kfv_nb[b];
     refkf_at(A, b, cap);
     kps_un += (size_t)b * A.kps_stride; desc += (size_t)b * A.desc_stride; d_n += b;
   }
@@ -681,7 +682,7 @@ __global__ void __launch_bounds__(256) k_refkf_search(RefKfArgs A, const dvm_key
   __syncthreads();
   const int lane = threadIdx.x & 63;
   const int a = wg * 4 + (threadIdx.x >> 6);
-  if (a >= A.kfv_n) return;
+  if (a >= kfv_n) return;
   const int N = min(*d_n, cap), n_fv = A.cnt[1];
   const uint32_t node = (uint32_t)A.kfv_node[a];
   int lo = 0, hi = n_fv;                  // the frame's nodes ascend as unsigned
@@ -735,9 +736,9 @@ __global__ void __launch_bounds__(256) k_refkf_search(RefKfArgs A, const dvm_key
 }
 
 // the rotation check of SearchByBoW (:372-387): ComputeThreeMaxima, the matches of the other bins taken back; res[0] = nmatches for the
-// edge gather, the final matches to mapped memory.  One workgroup (per frame that runs).
+// edge gather, the final matches to mapped memory.  One workgroup per frame that runs.
 __global__ void __launch_bounds__(256) k_refkf_settle(RefKfArgs A, const int32_t* __restrict__ d_n, int cap, int check_ori) {
-  if (A.run) { const int b = A.run[blockIdx.x]; refkf_at(A, b, cap); d_n += b; }
+  { const int b = A.run[blockIdx.x]; refkf_at(A, b, cap); d_n += b; }
   __shared__ int s_rot[kHisto];
   __shared__ int s_ind[3];
   __shared__ int s_nd[4];
@@ -807,18 +808,17 @@ void launch_refkf_bow(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int
   while (P < cap) P <<= 1;
   const size_t lds = (size_t)P * 16;
   if (lds > 48 * 1024) raise_dynamic_lds(reinterpret_cast<const void*>(k_refkf_bow), (int)lds);
-  if (A.run && A.nrun < 1) return;
-  hipLaunchKernelGGL(k_refkf_bow, dim3(A.run ? A.nrun : 1), dim3(1024), lds, s, A, d_n, cap, P);
+  if (A.nrun < 1) return;
+  hipLaunchKernelGGL(k_refkf_bow, dim3(A.nrun), dim3(1024), lds, s, A, d_n, cap, P);
 }
 void launch_refkf_search(hipStream_t s, const RefKfArgs& A, const dvm_keypoint_pod* kps_un, const uint8_t* desc, const int32_t* d_n, int cap, int th_low,
                          float nnratio) {
-  const int nwg = A.run ? A.nwg : (A.kfv_n + 3) / 4;
-  if (nwg < 1) return;
-  hipLaunchKernelGGL(k_refkf_search, dim3(nwg), dim3(256), (size_t)cap, s, A, kps_un, desc, d_n, cap, th_low, nnratio);
+  if (A.nwg < 1) return;
+  hipLaunchKernelGGL(k_refkf_search, dim3(A.nwg), dim3(256), (size_t)cap, s, A, kps_un, desc, d_n, cap, th_low, nnratio);
 }
 void launch_refkf_settle(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap, int check_ori) {
-  if (A.run && A.nrun < 1) return;
-  hipLaunchKernelGGL(k_refkf_settle, dim3(A.run ? A.nrun : 1), dim3(256), 0, s, A, d_n, cap, check_ori);
+  if (A.nrun < 1) return;
+  hipLaunchKernelGGL(k_refkf_settle, dim3(A.nrun), dim3(256), 0, s, A, d_n, cap, check_ori);
 }
 
 }  // namespace dvm
