@@ -1916,3 +1916,158 @@ class HostKeyFrameDatabase:
         nl = C.c_int32(0); nm = C.c_int32(0)
         self._f("detect_n_best", C.c_int32)(self.h, C.c_int32(slot), C.c_int32(n_num), _p(lo), C.byref(nl), _p(me), C.byref(nm))
         return lo[:nl.value].copy(), me[:nm.value].copy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# LocalMapping::CreateNewMapPoints as one device chain (dvm_create_new_map_points / dvmh_create_new_map_points).  Keyframes are the
+# dicts keyframe_view() takes (kps, desc, mp, fv, Tcw, K, bounds, scale_factors, level_sigma2).
+class _NpKeyFrame(C.Structure):   # == dvm_np_keyframe
+    _fields_ = [("n", C.c_int32), ("kps", C.c_void_p), ("desc", C.c_void_p), ("mp", C.c_void_p), ("fv_n", C.c_int32), ("fv_node", C.c_void_p),
+                ("fv_off", C.c_void_p), ("fv_feat", C.c_void_p), ("Tcw", C.c_float * 7), ("Twc", C.c_float * 7), ("Ow", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("scale_factors", C.c_void_p),
+                ("level_sigma2", C.c_void_p), ("n_levels", C.c_int32)]
+
+
+class _NpNeighbour(C.Structure):   # == dvm_np_neighbour
+    _fields_ = [("kf", _NpKeyFrame), ("median_depth", C.c_float), ("ep", C.c_float * 2), ("F12", C.c_float * 9)]
+
+
+class _NpParams(C.Structure):   # == dvm_np_params
+    _fields_ = [("cos_parallax_max", C.c_double), ("ratio_factor", C.c_float), ("th_far", C.c_float), ("far_points", C.c_int32),
+                ("coarse", C.c_int32), ("check_ori", C.c_int32), ("monocular", C.c_int32)]
+
+
+class _NpOut(C.Structure):   # == dvm_np_out
+    _fields_ = [("nb_status", C.c_void_p), ("nb_matches", C.c_void_p), ("pair_off", C.c_void_p), ("pairs", C.c_void_p), ("status", C.c_void_p),
+                ("x3D", C.c_void_p), ("new_point", C.c_void_p), ("record_cap", C.c_int32)]
+
+
+def _np_params(cur, coarse=False, check_ori=False, cos_parallax_max=0.9998, ratio_factor=None, far_points=False, th_far=0.0, monocular=1):
+    """check_ori = False is what CreateNewMapPoints' matcher has (ORBmatcher(0.6f, false), LocalMapping.cc:467); ratio_factor defaults to
+    1.5f * the current keyframe's mfScaleFactor (:483)."""
+    p = _NpParams()
+    if ratio_factor is None:
+        ratio_factor = np.float32(1.5) * np.float32(np.asarray(cur["scale_factors"], np.float32)[1])
+    p.cos_parallax_max, p.ratio_factor, p.th_far = float(cos_parallax_max), float(ratio_factor), float(th_far)
+    p.far_points, p.coarse, p.check_ori, p.monocular = int(far_points), int(coarse), int(check_ori), int(monocular)
+    return p
+
+
+class _NpResult:
+    """The caller memory of dvm_np_out, and the dict handed back."""
+
+    def __init__(self, n1, n_nb, record_cap):
+        self.nb_status = np.zeros(max(n_nb, 1), np.int32); self.nb_matches = np.zeros(max(n_nb, 1), np.int32)
+        self.pair_off = np.zeros(n_nb + 1, np.int32)
+        self.pairs = np.zeros((max(record_cap, 1), 2), np.int32); self.status = np.zeros(max(record_cap, 1), np.int32)
+        self.x3D = np.zeros((max(record_cap, 1), 3), np.float32); self.new_point = np.zeros(max(n1, 1), np.int32)
+        self.n1, self.n_nb = n1, n_nb
+        o = self.out = _NpOut()
+        o.nb_status, o.nb_matches, o.pair_off, o.pairs = (a.ctypes.data for a in (self.nb_status, self.nb_matches, self.pair_off, self.pairs))
+        o.status, o.x3D, o.new_point, o.record_cap = self.status.ctypes.data, self.x3D.ctypes.data, self.new_point.ctypes.data, int(record_cap)
+
+    def result(self):
+        m = int(self.pair_off[self.n_nb])
+        return dict(nb_status=self.nb_status[:self.n_nb].copy(), nb_matches=self.nb_matches[:self.n_nb].copy(), pair_off=self.pair_off.copy(),
+                    pairs=self.pairs[:m].copy(), status=self.status[:m].copy(), x3D=self.x3D[:m].copy(), new_point=self.new_point[:self.n1].copy())
+
+
+def _np_record_cap(cur, n_nb, record_cap):
+    return int(record_cap) if record_cap is not None else int((np.asarray(cur["mp"]) < 0).sum()) * n_nb
+
+
+class NewPoints:
+    """dvm_new_points: LocalMapping::CreateNewMapPoints for all neighbour keyframes as one device chain."""
+
+    def __init__(self, device=0):
+        self.L = lib()
+        vp, i32 = C.c_void_p, C.c_int32
+        self.L.dvm_new_points_create.argtypes = [i32, C.POINTER(vp)]
+        self.L.dvm_new_points_destroy.argtypes = [vp]; self.L.dvm_new_points_destroy.restype = None
+        self.L.dvm_new_points_reserve.argtypes = [vp, i32, i32, i32]
+        self.L.dvm_create_new_map_points.argtypes = [vp, vp, i32, vp, vp, vp]
+        self.L.dvm_new_points_profiling.argtypes = [vp, i32]
+        self.L.dvm_new_points_last_kernel_ms.argtypes = [vp, vp]
+        self.h = vp()
+        check(self.L.dvm_new_points_create(device, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.dvm_new_points_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def reserve(self, max_kf1_keypoints, max_neighbours, max_total_neighbour_keypoints):
+        check(self.L.dvm_new_points_reserve(self.h, int(max_kf1_keypoints), int(max_neighbours), int(max_total_neighbour_keypoints)))
+
+    def profiling(self, enable=True):
+        check(self.L.dvm_new_points_profiling(self.h, int(enable)))
+
+    def last_kernel_ms(self):
+        """(search, geometry, settle) milliseconds of the last call that ran with profiling on."""
+        ms = np.zeros(3, np.float32)
+        check(self.L.dvm_new_points_last_kernel_ms(self.h, _p(ms)))
+        return ms
+
+    @staticmethod
+    def _keyframe(kf, keep):
+        """dict -> dvm_np_keyframe; Twc / Ow as KeyFrame::SetPose derives them (Ow = Twc's translation)."""
+        v, k = keyframe_view(kf)
+        keep.append(k)
+        s = _NpKeyFrame()
+        s.n, s.kps, s.desc, s.mp = v.N, v.mvKeysUn, v.mDescriptors, v.mvpMapPoints
+        s.fv_n, s.fv_node, s.fv_off, s.fv_feat = v.mFeatVec.n, v.mFeatVec.node, v.mFeatVec.off, v.mFeatVec.feat
+        s.Tcw = v.Tcw; s.Twc = v.Twc
+        s.Ow = (C.c_float * 3)(*v.Twc[4:7])
+        s.fx, s.fy, s.cx, s.cy = v.fx, v.fy, v.cx, v.cy
+        s.scale_factors, s.level_sigma2, s.n_levels = v.mvScaleFactors, v.mvLevelSigma2, v.nLevels
+        return s, v
+
+    def prepare(self, cur, neighbours, median_depth, record_cap=None, **params):
+        """The argument structs of a call built once (views, pair geometry, result arrays): returns run() -> result dict, for a caller
+        that repeats the call on the same keyframes (a timing loop).  The arrays of `cur` / `neighbours` are read in place at run()."""
+        keep = []
+        c, cv = self._keyframe(cur, keep)
+        n_nb = len(neighbours)
+        nbs = (_NpNeighbour * max(n_nb, 1))()
+        for j, kf in enumerate(neighbours):
+            s, v = self._keyframe(kf, keep)
+            nbs[j].kf = s
+            nbs[j].median_depth = float(median_depth[j])
+            _, _, ep, F12 = triangulation_geometry((cv, None), (v, None))
+            nbs[j].ep = (C.c_float * 2)(*ep); nbs[j].F12 = (C.c_float * 9)(*F12)
+        p = _np_params(cur, **params)
+        R = _NpResult(c.n, n_nb, _np_record_cap(cur, n_nb, record_cap))
+
+        def run():
+            keep  # noqa: B018 (the views' arrays live as long as the closure)
+            check(self.L.dvm_create_new_map_points(self.h, C.addressof(c), n_nb, C.addressof(nbs), C.addressof(p), C.addressof(R.out)))
+            return R.result()
+        return run
+
+    def create_new_map_points(self, cur, neighbours, median_depth, record_cap=None, **params):
+        """cur / neighbours: keyframe dicts; median_depth[j] = ComputeSceneMedianDepth(2) of neighbour j.  params: coarse, check_ori,
+        cos_parallax_max, ratio_factor, far_points, th_far, monocular.  Returns dict(nb_status, nb_matches, pair_off, pairs[m, 2],
+        status[m], x3D[m, 3], new_point[n1])."""
+        return self.prepare(cur, neighbours, median_depth, record_cap=record_cap, **params)()
+
+
+def create_new_map_points(cur, neighbours, median_depth, device=0, record_cap=None, **params):
+    """dvmh_create_new_map_points: the host entry (pair geometry, camera centres and the calling thread's chain handle inside).
+    Arguments and result as NewPoints.create_new_map_points."""
+    keep = []
+    cv, k = keyframe_view(cur); keep.append(k)
+    n_nb = len(neighbours)
+    views = (_KeyFrameView * max(n_nb, 1))()
+    for j, kf in enumerate(neighbours):
+        v, k = keyframe_view(kf); keep.append(k)
+        views[j] = v
+    md = np.ascontiguousarray(median_depth, np.float32)
+    p = _np_params(cur, **params)
+    R = _NpResult(cv.N, n_nb, _np_record_cap(cur, n_nb, record_cap))
+    rc = _hcall("dvmh_create_new_map_points", C.c_int32, C.c_int32(device), C.byref(cv), C.c_int32(n_nb), C.byref(views), C.c_void_p(md.ctypes.data if md.size else None),
+                C.byref(p), C.byref(R.out))
+    check(rc)
+    return R.result()

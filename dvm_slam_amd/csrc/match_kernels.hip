@@ -15,6 +15,7 @@
 #include "pose_f32.h"
 #include "undistort_f64.h"
 #include "jacobi4.h"
+#include "tri_device.h"
 
 namespace dvm {
 
@@ -468,45 +469,20 @@ __global__ void __launch_bounds__(256) k_match_triangulation(const uint8_t* __re
   const int lane = threadIdx.x & 15;
   const int q = blockIdx.x * 16 + (threadIdx.x >> 4);
   if (q >= nq) return;
-  const int idx1 = qidx[q];
-  const uint32_t* qd = reinterpret_cast<const uint32_t*>(desc1 + (size_t)idx1 * 32);
-  uint32_t w[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) w[i] = qd[i];
-  const float x1 = kps1[idx1].x, y1 = kps1[idx1].y;
-  // epipolar line in the second image l = x1' F12 = [a b c]
-  const float a = __fadd_rn(__fadd_rn(__fmul_rn(x1, G.F12[0]), __fmul_rn(y1, G.F12[3])), G.F12[6]);
-  const float b = __fadd_rn(__fadd_rn(__fmul_rn(x1, G.F12[1]), __fmul_rn(y1, G.F12[4])), G.F12[7]);
-  const float c = __fadd_rn(__fadd_rn(__fmul_rn(x1, G.F12[2]), __fmul_rn(y1, G.F12[5])), G.F12[8]);
-  const float den = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
+  const TriQuery Q = tri_query(desc1, kps1, qidx[q], G.F12);
   const int beg = off[q], end = off[q + 1];
   uint32_t k = 0xFFFFFFFFu;
   for (int p = beg + lane; p < end; p += 16) {
     const int idx2 = cand[p];
     if (idx2 < 0) continue;
-    const uint4* td = reinterpret_cast<const uint4*>(desc2 + (size_t)idx2 * 32);
-    const uint4 A = td[0], B = td[1];
-    const int d = __popc(A.x ^ w[0]) + __popc(A.y ^ w[1]) + __popc(A.z ^ w[2]) + __popc(A.w ^ w[3]) +
-                  __popc(B.x ^ w[4]) + __popc(B.y ^ w[5]) + __popc(B.z ^ w[6]) + __popc(B.w ^ w[7]);
-    if (d > G.th_low) continue;
-    const dvm_keypoint_pod kp2 = kps2[idx2];
-    const float distex = __fsub_rn(G.ep[0], kp2.x), distey = __fsub_rn(G.ep[1], kp2.y);
-    if (__fadd_rn(__fmul_rn(distex, distex), __fmul_rn(distey, distey)) < __fmul_rn(100.f, scale_factors2[kp2.octave])) continue;
-    if (!G.coarse) {
-      const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, kp2.x), __fmul_rn(b, kp2.y)), c);
-      if (den == 0.f) continue;
-      const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
-      if (!((double)dsqr < 3.84 * (double)level_sigma2_2[kp2.octave])) continue;
-    }
-    k = min(k, ((uint32_t)d << 16) | (uint32_t)(0xFFFF - (p - beg)));
+    const int d = tri_candidate(Q, desc2, kps2, idx2, G, scale_factors2, level_sigma2_2);
+    if (d < 0) continue;
+    k = min(k, tri_key(d, p - beg));
   }
-  k = min(k, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k, 0xB1, 0xF, 0xF, false));
-  k = min(k, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k, 0x4E, 0xF, 0xF, false));
-  k = min(k, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k, 0x141, 0xF, 0xF, false));
-  k = min(k, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k, 0x140, 0xF, 0xF, false));
+  k = tri_row_min(k);
   if (lane == 0) {
     const bool hit = k != 0xFFFFFFFFu;
-    best_idx[q] = hit ? cand[beg + (0xFFFF - (int)(k & 0xFFFFu))] : -1;
+    best_idx[q] = hit ? cand[beg + tri_key_pos(k)] : -1;
     best_dist[q] = hit ? (int)(k >> 16) : 256;
   }
 }
@@ -593,81 +569,12 @@ __global__ void __launch_bounds__(128) k_triangulate_matches(TriPair P, const dv
                                                              int32_t* __restrict__ status) {
   const int m = blockIdx.x * 128 + threadIdx.x;
   if (m >= n) return;
-  using dvm_pose::sum3;
   float* X = x3D_out + 3 * (int64_t)m;
-  X[0] = X[1] = X[2] = 0.0f;
   const int i1 = pairs[2 * m], i2 = pairs[2 * m + 1];
-  if (i1 < 0 || i1 >= n1 || i2 < 0 || i2 >= n2) { status[m] = -1; return; }
-  const dvm_keypoint_pod kp1 = kps1[i1], kp2 = kps2[i2];
-  if (kp1.octave < 0 || kp1.octave >= P.n_levels || kp2.octave < 0 || kp2.octave >= P.n_levels) { status[m] = -1; return; }
-  const float* T1w = P.T1w;
-  const float* T2w = P.T2w;
-  const float xn1[3] = {(kp1.x - P.K1[2]) / P.K1[0], (kp1.y - P.K1[3]) / P.K1[1], 1.0f};
-  const float xn2[3] = {(kp2.x - P.K2[2]) / P.K2[0], (kp2.y - P.K2[3]) / P.K2[1], 1.0f};
-  float r1[3], r2[3];
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    r1[i] = sum3(T1w[i] * xn1[0], T1w[4 + i] * xn1[1], T1w[8 + i] * xn1[2]);
-    r2[i] = sum3(T2w[i] * xn2[0], T2w[4 + i] * xn2[1], T2w[8 + i] * xn2[2]);
-  }
-  const float nr1 = sqrtf(sum3(r1[0] * r1[0], r1[1] * r1[1], r1[2] * r1[2])), nr2 = sqrtf(sum3(r2[0] * r2[0], r2[1] * r2[1], r2[2] * r2[2]));
-  const float cosParallaxRays = sum3(r1[0] * r2[0], r1[1] * r2[1], r1[2] * r2[2]) / (nr1 * nr2);
-  const float cosParallaxStereo = cosParallaxRays + 1;
-  if (!(cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0 && (double)cosParallaxRays < P.cos_parallax_max)) { status[m] = 1; return; }
-  float A[4][4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    A[0][k] = xn1[0] * T1w[8 + k] - T1w[k];
-    A[1][k] = xn1[1] * T1w[8 + k] - T1w[4 + k];
-    A[2][k] = xn2[0] * T2w[8 + k] - T2w[k];
-    A[3][k] = xn2[1] * T2w[8 + k] - T2w[4 + k];
-  }
-  double B[4][4], V[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      double acc = 0.0;
-#pragma unroll
-      for (int k = 0; k < 4; k++) acc += (double)A[k][i] * (double)A[k][j];
-      B[i][j] = acc;
-    }
-  jacobi4_dev(B, V);
-  int mi = 0;
-#pragma unroll
-  for (int k = 1; k < 4; k++) if (B[k][k] < B[mi][mi]) mi = k;
-  float vh[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) vh[k] = (float)(mi == 0 ? V[k][0] : mi == 1 ? V[k][1] : mi == 2 ? V[k][2] : V[k][3]);
-  if (vh[3] == 0) { status[m] = 2; return; }
-  const float x3D[3] = {vh[0] / vh[3], vh[1] / vh[3], vh[2] / vh[3]};
-  X[0] = x3D[0]; X[1] = x3D[1]; X[2] = x3D[2];
-  const float z1 = sum3(T1w[8] * x3D[0], T1w[9] * x3D[1], T1w[10] * x3D[2]) + T1w[11];
-  if (z1 <= 0) { status[m] = 3; return; }
-  const float z2 = sum3(T2w[8] * x3D[0], T2w[9] * x3D[1], T2w[10] * x3D[2]) + T2w[11];
-  if (z2 <= 0) { status[m] = 4; return; }
-  {
-    const float x1 = sum3(T1w[0] * x3D[0], T1w[1] * x3D[1], T1w[2] * x3D[2]) + T1w[3];
-    const float y1 = sum3(T1w[4] * x3D[0], T1w[5] * x3D[1], T1w[6] * x3D[2]) + T1w[7];
-    const float u = P.K1[0] * x1 / z1 + P.K1[2], v = P.K1[1] * y1 / z1 + P.K1[3];
-    const float ex = u - kp1.x, ey = v - kp1.y;
-    if ((double)(ex * ex + ey * ey) > 5.991 * (double)sigma2_1[kp1.octave]) { status[m] = 5; return; }
-  }
-  {
-    const float x2 = sum3(T2w[0] * x3D[0], T2w[1] * x3D[1], T2w[2] * x3D[2]) + T2w[3];
-    const float y2 = sum3(T2w[4] * x3D[0], T2w[5] * x3D[1], T2w[6] * x3D[2]) + T2w[7];
-    const float u = P.K2[0] * x2 / z2 + P.K2[2], v = P.K2[1] * y2 / z2 + P.K2[3];
-    const float ex = u - kp2.x, ey = v - kp2.y;
-    if ((double)(ex * ex + ey * ey) > 5.991 * (double)sigma2_2[kp2.octave]) { status[m] = 6; return; }
-  }
-  const float d1[3] = {x3D[0] - P.Ow1[0], x3D[1] - P.Ow1[1], x3D[2] - P.Ow1[2]}, d2[3] = {x3D[0] - P.Ow2[0], x3D[1] - P.Ow2[1], x3D[2] - P.Ow2[2]};
-  const float dist1 = sqrtf(sum3(d1[0] * d1[0], d1[1] * d1[1], d1[2] * d1[2])), dist2 = sqrtf(sum3(d2[0] * d2[0], d2[1] * d2[1], d2[2] * d2[2]));
-  if (dist1 == 0 || dist2 == 0) { status[m] = 7; return; }
-  if (P.far_points && (dist1 >= P.th_far || dist2 >= P.th_far)) { status[m] = 8; return; }
-  const float ratioDist = dist2 / dist1;
-  const float ratioOctave = sf1[kp1.octave] / sf2[kp2.octave];
-  if (ratioDist * P.ratio_factor < ratioOctave || ratioDist > ratioOctave * P.ratio_factor) { status[m] = 9; return; }
-  status[m] = 0;
+  if (i1 < 0 || i1 >= n1 || i2 < 0 || i2 >= n2) { X[0] = X[1] = X[2] = 0.0f; status[m] = -1; return; }
+  float x[3];
+  status[m] = tri_pair_geometry(P, kps1[i1], kps2[i2], sigma2_1, sigma2_2, sf1, sf2, x);
+  X[0] = x[0]; X[1] = x[1]; X[2] = x[2];
 }
 void launch_triangulate_matches(hipStream_t s, const TriPair& P, const dvm_keypoint_pod* kps1, int n1, const dvm_keypoint_pod* kps2, int n2,
                                 const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2, const float* sf1,

@@ -1,0 +1,294 @@
+// dvm_slam_amd/csrc/new_points.cpp -- dvm_new_points: LocalMapping::CreateNewMapPoints for all neighbours of a keyframe as one chain
+// (include/dvmslam_hip.h; kernels in new_points_kernels.hip).  The handle owns a stream and one reserved working set: a device block
+// [packed upload][speculative results] and a mapped page-locked block [upload staging][results].  A call validates everything, packs both
+// keyframe sets back to back into the staging region, sends it with ONE copy, queues the three launches, synchronises ONCE and copies the
+// records out of the mapped block.  Host arithmetic here is index-free: the baseline test of each neighbour and the 3x4 pose matrices.
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/dvmslam_hip.h"
+#include "new_points_kernels.h"
+#include "orb_pipeline.h"
+#include "pose_f32.h"
+
+using namespace dvm;
+
+struct dvm_new_points {
+  int device = 0;
+  hipStream_t s = nullptr;
+  uint8_t *d = nullptr, *hm = nullptr, *hm_dev = nullptr;
+  size_t up_bytes = 0, spec_bytes = 0;          // device block: [up_bytes][spec]; mapped block: [up_bytes][results]
+  int max_n1 = 0, max_nb = 0, max_total = 0;
+  size_t rec_cap = 0;                           // records the mapped block holds: max_nb * max_n1
+  int profiling = 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  float last_ms[3] = {0, 0, 0};
+  void release() {
+    if (d) hipFree(d);
+    if (hm) hipHostFree(hm);
+    d = hm = hm_dev = nullptr; up_bytes = spec_bytes = 0; max_n1 = max_nb = max_total = 0; rec_cap = 0;
+  }
+};
+
+namespace {
+constexpr size_t kAlign = 64;
+size_t al(size_t b) { return (b + kAlign - 1) & ~(kAlign - 1); }
+// bytes a keyframe of n keypoints takes in the packed upload at most: per keypoint its cv::KeyPoint, descriptor, map point, and -- fv_n <= n
+// nodes, at most n features -- a node id, an offset and a feature; per keyframe the last offset, two level tables of 64 and the rounding of
+// its eight arrays.  Linear in n, so the neighbours' sum is bounded by their total.
+constexpr size_t kKfPerKeypoint = sizeof(dvm_keypoint_pod) + 32 + 4 * 4, kKfFixed = 4 + 2 * 64 * 4 + 8 * kAlign;
+
+int fail(int rc, const std::string& msg) { set_error("dvm_create_new_map_points: " + msg); return rc; }
+
+int check_keyframe(const dvm_np_keyframe& k, const char* who, int n_levels) {
+  const std::string w(who);
+  if (k.n < 0 || k.n > kFrameCap) return fail(DVM_ERR_INVALID, w + ": n outside [0, 8192]");
+  if (k.n_levels != n_levels) return fail(DVM_ERR_INVALID, w + ": level tables of another length than the current keyframe's");
+  if (!k.scale_factors || !k.level_sigma2) return fail(DVM_ERR_INVALID, w + ": missing level table");
+  if (!(k.fx != 0.0f) || !(k.fy != 0.0f)) return fail(DVM_ERR_INVALID, w + ": zero focal length");
+  if (k.n > 0 && (!k.kps || !k.desc || !k.mp)) return fail(DVM_ERR_INVALID, w + ": missing keypoint array");
+  if (k.fv_n < 0 || k.fv_n > k.n) return fail(DVM_ERR_INVALID, w + ": more FeatureVector nodes than keypoints");
+  if (k.fv_n > 0) {
+    if (!k.fv_node || !k.fv_off || !k.fv_feat) return fail(DVM_ERR_INVALID, w + ": missing FeatureVector array");
+    if (k.fv_off[0] != 0) return fail(DVM_ERR_INVALID, w + ": FeatureVector offsets do not start at 0");
+    for (int a = 0; a < k.fv_n; a++) {
+      if (k.fv_off[a + 1] < k.fv_off[a]) return fail(DVM_ERR_INVALID, w + ": FeatureVector offsets not monotone");
+      if (a > 0 && k.fv_node[a] <= k.fv_node[a - 1]) return fail(DVM_ERR_INVALID, w + ": FeatureVector nodes not ascending");
+    }
+    const int nf = k.fv_off[k.fv_n];
+    if (nf > k.n) return fail(DVM_ERR_INVALID, w + ": more FeatureVector features than keypoints");
+    for (int f = 0; f < nf; f++)
+      if (k.fv_feat[f] < 0 || k.fv_feat[f] >= k.n) return fail(DVM_ERR_INVALID, w + ": FeatureVector feature index out of range");
+  }
+  return DVM_OK;
+}
+
+// packs one keyframe at *off of the staging block and returns its device view
+NpKfDev pack_keyframe(const dvm_np_keyframe& k, uint8_t* stage, const uint8_t* dev, size_t* off) {
+  NpKfDev v{};
+  auto put = [&](const void* src, size_t bytes) {
+    const size_t o = *off;
+    if (bytes) std::memcpy(stage + o, src, bytes);
+    *off = o + al(bytes);
+    return dev + o;
+  };
+  const size_t n = (size_t)k.n, nf = k.fv_n > 0 ? (size_t)k.fv_off[k.fv_n] : 0;
+  v.kps = reinterpret_cast<const dvm_keypoint_pod*>(put(k.kps, n * sizeof(dvm_keypoint_pod)));
+  v.desc = put(k.desc, n * 32);
+  v.mp = reinterpret_cast<const int32_t*>(put(k.mp, n * 4));
+  v.fv_node = reinterpret_cast<const int32_t*>(put(k.fv_node, (size_t)k.fv_n * 4));
+  v.fv_off = reinterpret_cast<const int32_t*>(put(k.fv_off, k.fv_n > 0 ? ((size_t)k.fv_n + 1) * 4 : 0));
+  v.fv_feat = reinterpret_cast<const int32_t*>(put(k.fv_feat, nf * 4));
+  v.sf = reinterpret_cast<const float*>(put(k.scale_factors, (size_t)k.n_levels * 4));
+  v.sigma2 = reinterpret_cast<const float*>(put(k.level_sigma2, (size_t)k.n_levels * 4));
+  v.n = k.n; v.fv_n = k.fv_n;
+  return v;
+}
+
+// KeyFrame::GetPose().matrix3x4(), row-major (the rotation matrix of the unit quaternion | translation)
+void pose_3x4(const dvm_se3f& T, float* out) {
+  float R[9];
+  dvm_pose::quat_matrix(T.q, R);
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) out[4 * r + c] = R[3 * r + c];
+    out[4 * r + 3] = T.t[r];
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int dvm_new_points_create(int device, dvm_new_points** out) {
+  if (!out) return DVM_ERR_INVALID;
+  *out = nullptr;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  if (device < 0 || device >= n) { set_error("device index out of range"); return DVM_ERR_INVALID; }
+  DVM_HIP(hipSetDevice(device));
+  dvm_new_points* h = new (std::nothrow) dvm_new_points;
+  if (!h) return DVM_ERR_INVALID;
+  h->device = device;
+  int rc = hip_check(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking), "hipStreamCreate");
+  if (rc != DVM_OK) { delete h; return rc; }
+  *out = h;
+  return DVM_OK;
+}
+
+void dvm_new_points_destroy(dvm_new_points* h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  if (h->s) { hipStreamSynchronize(h->s); hipStreamDestroy(h->s); }
+  for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
+  h->release();
+  delete h;
+}
+
+int dvm_new_points_reserve(dvm_new_points* h, int max_kf1_keypoints, int max_neighbours, int max_total_neighbour_keypoints) {
+  if (!h || max_kf1_keypoints < 0 || max_kf1_keypoints > kFrameCap || max_neighbours < 0 || max_total_neighbour_keypoints < 0 ||
+      (int64_t)max_total_neighbour_keypoints > (int64_t)max_neighbours * kFrameCap) {
+    set_error("dvm_new_points_reserve: bad sizes");
+    return DVM_ERR_INVALID;
+  }
+  if (max_kf1_keypoints <= h->max_n1 && max_neighbours <= h->max_nb && max_total_neighbour_keypoints <= h->max_total) return DVM_OK;
+  DVM_HIP(hipSetDevice(h->device));
+  DVM_HIP(hipStreamSynchronize(h->s));
+  const int n1 = std::max(max_kf1_keypoints, h->max_n1), nb = std::max(max_neighbours, h->max_nb), tot = std::max(max_total_neighbour_keypoints, h->max_total);
+  h->release();
+  const size_t n1p = ((size_t)n1 + 63) & ~(size_t)63;
+  const size_t up = al(((size_t)n1 + (size_t)tot) * kKfPerKeypoint + ((size_t)nb + 1) * kKfFixed + al((size_t)nb * sizeof(NpNbDev)));
+  const size_t spec = (size_t)nb * n1p * 20 + kAlign;
+  const size_t rec = (size_t)nb * (size_t)n1;
+  const size_t res = al(((size_t)nb + 1) * 4) * 2 + al(rec * 8) + al(rec * 4) + al(rec * 12) + al((size_t)n1 * 4) + kAlign;
+  if (hipMalloc(reinterpret_cast<void**>(&h->d), up + spec) != hipSuccess) { h->d = nullptr; set_error("dvm_new_points_reserve: hipMalloc failed"); return DVM_ERR_HIP; }
+  if (hipHostMalloc(reinterpret_cast<void**>(&h->hm), up + res, hipHostMallocMapped) != hipSuccess ||
+      hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hm_dev), h->hm, 0) != hipSuccess) {
+    h->release();
+    set_error("dvm_new_points_reserve: mapped host memory failed");
+    return DVM_ERR_HIP;
+  }
+  h->up_bytes = up; h->spec_bytes = spec; h->max_n1 = n1; h->max_nb = nb; h->max_total = tot; h->rec_cap = rec;
+  return DVM_OK;
+}
+
+int dvm_new_points_profiling(dvm_new_points* h, int enable) {
+  if (!h) return DVM_ERR_INVALID;
+  DVM_HIP(hipSetDevice(h->device));
+  if (enable)
+    for (hipEvent_t& e : h->ev) if (!e) DVM_HIP(hipEventCreate(&e));
+  h->profiling = enable != 0;
+  return DVM_OK;
+}
+int dvm_new_points_last_kernel_ms(dvm_new_points* h, float* ms) {
+  if (!h || !ms) return DVM_ERR_INVALID;
+  for (int i = 0; i < 3; i++) ms[i] = h->last_ms[i];
+  return DVM_OK;
+}
+
+int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int n_neighbours, const dvm_np_neighbour* nbs,
+                              const dvm_np_params* p, dvm_np_out* out) {
+  static_assert(sizeof(dvm_keypoint) == sizeof(dvm_keypoint_pod), "layout");
+  if (!h || !cur || !p || !out || n_neighbours < 0 || (n_neighbours > 0 && !nbs)) return fail(DVM_ERR_INVALID, "missing argument");
+  if (p->monocular != 1) return fail(DVM_ERR_INVALID, "only monocular keyframes (the stereo branches are outside the accelerated path)");
+  if (!out->nb_status || !out->nb_matches || !out->pair_off || (cur->n > 0 && !out->new_point) || out->record_cap < 0 ||
+      (out->record_cap > 0 && (!out->pairs || !out->status || !out->x3D)))
+    return fail(DVM_ERR_INVALID, "missing output array");
+  if (cur->n_levels < 1 || cur->n_levels > 64) return fail(DVM_ERR_INVALID, "n_levels outside [1, 64]");
+  int rc = check_keyframe(*cur, "current keyframe", cur->n_levels);
+  if (rc != DVM_OK) return rc;
+  int64_t total = 0;
+  for (int j = 0; j < n_neighbours; j++) {
+    rc = check_keyframe(nbs[j].kf, ("neighbour " + std::to_string(j)).c_str(), cur->n_levels);
+    if (rc != DVM_OK) return rc;
+    total += nbs[j].kf.n;
+  }
+  if (cur->n > h->max_n1 || n_neighbours > h->max_nb || total > h->max_total)
+    return fail(DVM_ERR_CAPACITY, "beyond the reservation (dvm_new_points_reserve): " + std::to_string(cur->n) + " keypoints, " + std::to_string(n_neighbours) +
+                                      " neighbours with " + std::to_string(total) + " keypoints");
+  int64_t nq0 = 0;
+  for (int i = 0; i < cur->n; i++) nq0 += cur->mp[i] < 0 ? 1 : 0;
+  if ((int64_t)out->record_cap < nq0 * n_neighbours) return fail(DVM_ERR_CAPACITY, "record_cap below n_neighbours x keypoints without a point");
+
+  // the baseline test (LocalMapping.cc:497-512), float, one operation per statement
+  std::vector<int> run;
+  for (int j = 0; j < n_neighbours; j++) {
+    const float dx = nbs[j].kf.Ow[0] - cur->Ow[0], dy = nbs[j].kf.Ow[1] - cur->Ow[1], dz = nbs[j].kf.Ow[2] - cur->Ow[2];
+    float s = dx * dx;
+    const float yy = dy * dy, zz = dz * dz;
+    s = s + yy;
+    s = s + zz;
+    const float baseline = sqrtf(s);
+    const float ratio = baseline / nbs[j].median_depth;
+    const bool skip = (double)ratio < 0.01;
+    out->nb_status[j] = skip ? 1 : 0;
+    out->nb_matches[j] = 0;
+    if (!skip) run.push_back(j);
+  }
+  const int nrun = (int)run.size(), n1 = cur->n;
+  const size_t n1p = ((size_t)n1 + 63) & ~(size_t)63;
+  for (int i = 0; i < n1; i++) out->new_point[i] = -1;
+  for (int j = 0; j <= n_neighbours; j++) out->pair_off[j] = 0;
+  if (nrun == 0 || n1 == 0) return DVM_OK;
+
+  DVM_HIP(hipSetDevice(h->device));
+  // pack: [NpNbDev x nrun][current keyframe][neighbours that run]
+  size_t off = al((size_t)nrun * sizeof(NpNbDev));
+  NpNbDev* nb_stage = reinterpret_cast<NpNbDev*>(h->hm);
+  NpArgs A{};
+  A.cur = pack_keyframe(*cur, h->hm, h->d, &off);
+  float T1w[12];
+  pose_3x4(cur->Tcw, T1w);
+  for (int r = 0; r < nrun; r++) {
+    const dvm_np_neighbour& nb = nbs[run[r]];
+    NpNbDev& D = nb_stage[r];
+    std::memset(&D, 0, sizeof(D));
+    D.kf = pack_keyframe(nb.kf, h->hm, h->d, &off);
+    TriPair& P = D.P;
+    P.cos_parallax_max = p->cos_parallax_max;
+    P.K1[0] = cur->fx; P.K1[1] = cur->fy; P.K1[2] = cur->cx; P.K1[3] = cur->cy;
+    P.K2[0] = nb.kf.fx; P.K2[1] = nb.kf.fy; P.K2[2] = nb.kf.cx; P.K2[3] = nb.kf.cy;
+    std::memcpy(P.T1w, T1w, sizeof(T1w));
+    pose_3x4(nb.kf.Tcw, P.T2w);
+    std::memcpy(P.Ow1, cur->Ow, 12); std::memcpy(P.Ow2, nb.kf.Ow, 12);
+    P.ratio_factor = p->ratio_factor; P.th_far = p->th_far; P.far_points = p->far_points ? 1 : 0; P.n_levels = cur->n_levels;
+    std::memcpy(D.G.F12, nb.F12, 36); D.G.ep[0] = nb.ep[0]; D.G.ep[1] = nb.ep[1];
+    D.G.coarse = p->coarse != 0; D.G.th_low = 50;   // ORBmatcher::TH_LOW
+  }
+  if (off > h->up_bytes) return fail(DVM_ERR_CAPACITY, "packed keyframes exceed the reserved upload region");   // (cannot happen: kKfPerKeypoint / kKfFixed bound every keyframe)
+  A.nb = reinterpret_cast<const NpNbDev*>(h->d);
+  A.nrun = nrun; A.n1 = n1; A.n1p = (int32_t)n1p; A.nfeat1 = cur->fv_n > 0 ? cur->fv_off[cur->fv_n] : 0;
+  A.n_levels = cur->n_levels; A.check_ori = p->check_ori != 0;
+  uint8_t* spec = h->d + h->up_bytes;
+  A.best = reinterpret_cast<int32_t*>(spec);
+  A.st = A.best + (size_t)nrun * n1p;
+  A.X = reinterpret_cast<float*>(A.st + (size_t)nrun * n1p);
+  // results in the mapped block (sized for the reservation)
+  size_t ro = h->up_bytes;
+  auto carve = [&](size_t bytes) { uint8_t* q = h->hm + ro; ro += al(bytes); return q; };
+  int32_t* r_matches = reinterpret_cast<int32_t*>(carve(((size_t)h->max_nb + 1) * 4));
+  int32_t* r_off = reinterpret_cast<int32_t*>(carve(((size_t)h->max_nb + 1) * 4));
+  int32_t* r_pairs = reinterpret_cast<int32_t*>(carve(h->rec_cap * 8));
+  int32_t* r_status = reinterpret_cast<int32_t*>(carve(h->rec_cap * 4));
+  float* r_x3D = reinterpret_cast<float*>(carve(h->rec_cap * 12));
+  int32_t* r_new = reinterpret_cast<int32_t*>(carve((size_t)h->max_n1 * 4));
+  auto dev = [&](auto* q) { return reinterpret_cast<decltype(q)>(h->hm_dev + (reinterpret_cast<uint8_t*>(q) - h->hm)); };
+  A.h_matches = dev(r_matches); A.h_pair_off = dev(r_off); A.h_pairs = dev(r_pairs); A.h_status = dev(r_status); A.h_x3D = dev(r_x3D);
+  A.h_new_point = dev(r_new);
+
+  DVM_HIP(hipMemcpyAsync(h->d, h->hm, off, hipMemcpyHostToDevice, h->s));
+  DVM_HIP(hipMemsetAsync(A.best, 0xFF, (size_t)nrun * n1p * 4, h->s));
+  const bool prof = h->profiling != 0;
+  if (prof) DVM_HIP(hipEventRecord(h->ev[0], h->s));
+  launch_np_search(h->s, A);
+  if (prof) DVM_HIP(hipEventRecord(h->ev[1], h->s));
+  launch_np_geometry(h->s, A);
+  if (prof) DVM_HIP(hipEventRecord(h->ev[2], h->s));
+  launch_np_settle(h->s, A);
+  if (prof) DVM_HIP(hipEventRecord(h->ev[3], h->s));
+  rc = hip_check(hipGetLastError(), "dvm_create_new_map_points launch");
+  const int rs = hip_check(hipStreamSynchronize(h->s), "dvm_create_new_map_points sync");
+  if (rc != DVM_OK) return rc;
+  if (rs != DVM_OK) return rs;
+  if (prof)
+    for (int i = 0; i < 3; i++) DVM_HIP(hipEventElapsedTime(&h->last_ms[i], h->ev[i], h->ev[i + 1]));
+
+  const size_t nrec = (size_t)r_off[nrun];
+  if (nrec > (size_t)out->record_cap || nrec > h->rec_cap) return fail(DVM_ERR_STATE, "more records than the bound allows");   // (an internal error)
+  for (int r = 0; r < nrun; r++) out->nb_matches[run[r]] = r_matches[r];
+  for (int j = 0, r = 0; j < n_neighbours; j++) {     // a skipped neighbour's range is empty
+    out->pair_off[j] = r_off[r];
+    if (r < nrun && run[r] == j) r++;
+  }
+  out->pair_off[n_neighbours] = (int32_t)nrec;
+  if (nrec) {
+    std::memcpy(out->pairs, r_pairs, nrec * 8);
+    std::memcpy(out->status, r_status, nrec * 4);
+    std::memcpy(out->x3D, r_x3D, nrec * 12);
+  }
+  std::memcpy(out->new_point, r_new, (size_t)n1 * 4);
+  return DVM_OK;
+}
+
+}  // extern "C"

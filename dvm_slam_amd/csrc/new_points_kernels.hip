@@ -1,0 +1,154 @@
+// dvm_slam_amd/csrc/new_points_kernels.hip -- LocalMapping::CreateNewMapPoints (reference src/LocalMapping.cc:446-760, monocular) for all
+// neighbour keyframes of the current keyframe as three launches behind one upload (dvm_create_new_map_points, include/dvmslam_hip.h):
+//   k_np_search     ORBmatcher::SearchForTriangulation's search (src/ORBmatcher.cc:890-960) for every (neighbour, KF1 keypoint without a
+//                   point AT ENTRY), speculatively: the reference never sets vbMatched2, so a keypoint's best candidate in a neighbour
+//                   depends on nothing the loop over the neighbours changes
+//   k_np_geometry   the per-match body of CreateNewMapPoints (:598-741) for every best candidate found
+//   k_np_settle     ONE workgroup walks the neighbours in order: the matches of keypoints that still have no point vote in the rotation
+//                   histogram (:961-1031), the survivors are compacted in ascending idx1 with their precomputed status and point, and the
+//                   keypoints of accepted pairs are marked (what pKF->AddMapPoint does to the table, :744)
+// The launches' order carries the dependency; no workgroup waits for another inside a kernel.  The per-candidate test and the per-pair
+// geometry are the functions the single calls run (tri_device.h).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "new_points_kernels.h"
+#include "rot_bin.h"
+#include "tri_device.h"
+
+namespace dvm {
+
+// One DPP row (16 lanes) per (KF1 feature position k, neighbour blockIdx.y).  The row finds k's vocabulary node (the last node whose
+// offset is <= k), looks the node up in the neighbour's FeatureVector (node ids ascend) and scans that node's KF2 features across its
+// lanes, those with a map point skipped; a tie goes to the last candidate in the node's order, as in k_match_triangulation.
+__global__ void __launch_bounds__(256) k_np_search(NpArgs A) {
+  const int lane = threadIdx.x & 15;
+  const int k = blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (k >= A.nfeat1) return;
+  const NpKfDev& C = A.cur;
+  const int idx1 = C.fv_feat[k];
+  if (C.mp[idx1] >= 0) return;                       // already a MapPoint at entry: never asked
+  const NpNbDev& N = A.nb[blockIdx.y];
+  int lo = 0, hi = C.fv_n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (C.fv_off[mid] <= k) lo = mid; else hi = mid - 1;
+  }
+  const int node = C.fv_node[lo];
+  lo = 0; hi = N.kf.fv_n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (N.kf.fv_node[mid] < node) lo = mid + 1; else hi = mid;
+  }
+  if (lo >= N.kf.fv_n || N.kf.fv_node[lo] != node) return;
+  const int fb = N.kf.fv_off[lo], fe = N.kf.fv_off[lo + 1];
+  const TriQuery Q = tri_query(C.desc, C.kps, idx1, N.G.F12);
+  uint32_t key = 0xFFFFFFFFu;
+  for (int p = fb + lane; p < fe; p += 16) {
+    const int idx2 = N.kf.fv_feat[p];
+    if (N.kf.mp[idx2] >= 0) continue;
+    if ((unsigned)N.kf.kps[idx2].octave >= (unsigned)A.n_levels) continue;   // outside the tables: no candidate, nothing read
+    const int d = tri_candidate(Q, N.kf.desc, N.kf.kps, idx2, N.G, N.kf.sf, N.kf.sigma2);
+    if (d < 0) continue;
+    key = min(key, tri_key(d, p - fb));
+  }
+  key = tri_row_min(key);
+  if (lane == 0 && key != 0xFFFFFFFFu) A.best[(size_t)blockIdx.y * A.n1p + idx1] = N.kf.fv_feat[fb + tri_key_pos(key)];
+}
+
+// thread per (KF1 keypoint, neighbour blockIdx.y) with a best candidate
+__global__ void __launch_bounds__(128) k_np_geometry(NpArgs A) {
+  const int i = blockIdx.x * 128 + threadIdx.x;
+  if (i >= A.n1) return;
+  const size_t o = (size_t)blockIdx.y * A.n1p + i;
+  const int m = A.best[o];
+  if (m < 0) return;
+  const NpNbDev& N = A.nb[blockIdx.y];
+  float x[3];
+  A.st[o] = tri_pair_geometry(N.P, A.cur.kps[i], N.kf.kps[m], A.cur.sigma2, N.kf.sigma2, A.cur.sf, N.kf.sf, x);
+  A.X[3 * o] = x[0]; A.X[3 * o + 1] = x[1]; A.X[3 * o + 2] = x[2];
+}
+
+// One workgroup; thread t owns the keypoints [t * chunk, (t + 1) * chunk) (chunk <= 8: 8192 keypoints), so the table in LDS is only ever
+// touched by its owner and the records of a neighbour come out in ascending idx1 from an exclusive scan of the per-thread counts.
+__global__ void __launch_bounds__(1024) k_np_settle(NpArgs A) {
+  __shared__ uint8_t s_has[kFrameCap];
+  __shared__ int s_hist[kRotHisto];
+  __shared__ int s_ind[3];
+  __shared__ int s_wave[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const NpKfDev& C = A.cur;
+  const int chunk = (A.n1 + 1023) / 1024;
+  const int b = min(tid * chunk, A.n1), e = min(b + chunk, A.n1);
+  for (int i = b; i < e; i++) { s_has[i] = C.mp[i] >= 0 ? 1 : 0; A.h_new_point[i] = -1; }
+  if (tid == 0) A.h_pair_off[0] = 0;
+  int base = 0;
+  for (int r = 0; r < A.nrun; r++) {
+    const NpNbDev& N = A.nb[r];
+    const int32_t* best = A.best + (size_t)r * A.n1p;
+    if (tid < kRotHisto) s_hist[tid] = 0;
+    __syncthreads();
+    int bins[8];
+    unsigned live = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const int i = b + j;
+      bins[j] = -1;
+      if (i >= e) continue;
+      const int m = best[i];
+      if (m < 0 || s_has[i]) continue;               // no match, or a point from an earlier neighbour: the reference does not ask (:897-902)
+      live |= 1u << j;
+      const int bin = rot_bin(C.kps[i].angle, N.kf.kps[m].angle);
+      if (bin >= 0 && bin < kRotHisto) { bins[j] = bin; if (A.check_ori) atomicAdd(&s_hist[bin], 1); }
+    }
+    __syncthreads();
+    if (tid == 0) three_maxima(s_hist, s_ind);
+    __syncthreads();
+    unsigned keep = live;
+    if (A.check_ori) {
+#pragma unroll
+      for (int j = 0; j < 8; j++)
+        if (!(bins[j] >= 0 && (bins[j] == s_ind[0] || bins[j] == s_ind[1] || bins[j] == s_ind[2]))) keep &= ~(1u << j);
+    }
+    const int cnt = __popc(keep);
+    int incl = cnt;                                   // inclusive scan inside the wave, then over the 16 waves
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 16; w++) { const int v = s_wave[w]; if (w < wave) before += v; total += v; }
+    int rec = base + before + incl - cnt;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      if (!(keep >> j & 1u)) continue;
+      const int i = b + j;
+      const size_t o = (size_t)r * A.n1p + i;
+      const int st = A.st[o];
+      A.h_pairs[2 * (size_t)rec] = i; A.h_pairs[2 * (size_t)rec + 1] = best[i];
+      A.h_status[rec] = st;
+      A.h_x3D[3 * (size_t)rec] = A.X[3 * o]; A.h_x3D[3 * (size_t)rec + 1] = A.X[3 * o + 1]; A.h_x3D[3 * (size_t)rec + 2] = A.X[3 * o + 2];
+      if (st == 0) { s_has[i] = 1; A.h_new_point[i] = rec; }
+      rec++;
+    }
+    base += total;
+    if (tid == 0) { A.h_matches[r] = total; A.h_pair_off[r + 1] = base; }
+    __syncthreads();                                  // s_wave and s_hist are rewritten by the next neighbour
+  }
+}
+
+void launch_np_search(hipStream_t s, const NpArgs& A) {
+  if (A.nrun < 1 || A.nfeat1 < 1) return;
+  hipLaunchKernelGGL(k_np_search, dim3((A.nfeat1 + 15) / 16, A.nrun), dim3(256), 0, s, A);
+}
+void launch_np_geometry(hipStream_t s, const NpArgs& A) {
+  if (A.nrun < 1 || A.n1 < 1) return;
+  hipLaunchKernelGGL(k_np_geometry, dim3((A.n1 + 127) / 128, A.nrun), dim3(128), 0, s, A);
+}
+void launch_np_settle(hipStream_t s, const NpArgs& A) { hipLaunchKernelGGL(k_np_settle, dim3(1), dim3(1024), 0, s, A); }
+
+}  // namespace dvm

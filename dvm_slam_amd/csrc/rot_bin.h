@@ -1,5 +1,6 @@
 // dvm_slam_amd/csrc/rot_bin.h -- the rotation-histogram bin of ORBmatcher (HISTO_LENGTH = 30, e.g. src/ORBmatcher.cc:324-329): the one
-// float expression the host mirror (host/orb_matcher.cpp) and the device chains (track_kernels.hip) both evaluate.
+// float expression the host mirror (host/orb_matcher.cpp) and the device chains (track_kernels.hip, new_points_kernels.hip) both evaluate,
+// and ComputeThreeMaxima as the device chains run it.
 #pragma once
 #include <math.h>
 
@@ -19,5 +20,19 @@ DVM_ROT_HD inline int rot_bin(float a1, float a2) {
   int bin = (int)roundf(rot * factor);
   if (bin == kRotHisto) bin = 0;
   return bin;
+}
+// ComputeThreeMaxima (ORBmatcher.cc:1750-1802) over the bin counts: the three fullest bins, the second and third dropped below a
+// tenth of the first (on the device: one lane)
+DVM_ROT_HD inline void three_maxima(const int* hist, int* ind) {
+  int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+  for (int i = 0; i < kRotHisto; i++) {
+    const int sv = hist[i];
+    if (sv > max1) { max3 = max2; max2 = max1; max1 = sv; ind3 = ind2; ind2 = ind1; ind1 = i; }
+    else if (sv > max2) { max3 = max2; max2 = sv; ind3 = ind2; ind2 = i; }
+    else if (sv > max3) { max3 = sv; ind3 = i; }
+  }
+  if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+  else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
+  ind[0] = ind1; ind[1] = ind2; ind[2] = ind3;
 }
 }  // namespace dvm

@@ -23,22 +23,7 @@
 namespace dvm {
 
 namespace {
-constexpr int kHisto = kRotHisto;   // HISTO_LENGTH, ORBmatcher.cc:38
-
-// ComputeThreeMaxima (ORBmatcher.cc:1750-1802) over the bin counts, on one lane: the three fullest bins, the second and third dropped
-// below a tenth of the first
-__device__ void three_maxima(const int* hist, int* ind) {
-  int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-  for (int i = 0; i < kHisto; i++) {
-    const int sv = hist[i];
-    if (sv > max1) { max3 = max2; max2 = max1; max1 = sv; ind3 = ind2; ind2 = ind1; ind1 = i; }
-    else if (sv > max2) { max3 = max2; max2 = sv; ind3 = ind2; ind2 = i; }
-    else if (sv > max3) { max3 = sv; ind3 = i; }
-  }
-  if ((float)max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-  else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
-  ind[0] = ind1; ind[1] = ind2; ind[2] = ind3;
-}
+constexpr int kHisto = kRotHisto;   // HISTO_LENGTH, ORBmatcher.cc:38 (three_maxima: rot_bin.h)
 }
 
 // One wave.  Queries are decided in blocks of 64, one per lane.  Inside a block a lane's choice depends on what the lanes before it

@@ -1011,6 +1011,56 @@ int dvmh_search_for_triangulation(int device, const dvmh_keyframe_view* KF1, con
   dvm_host::ORBmatcher m(0.6f, check_ori != 0, device);
   return m.SearchForTriangulation(KeyFrameView(*KF1), KeyFrameView(*KF2), pairs, false, coarse != 0);
 }
+namespace {
+// the calling thread's chain handle (one per device it has used): created on first use, reserved on growth, never per call
+struct NewPointsSlot {
+  int device = -1;
+  dvm_new_points* h = nullptr;
+  int n1 = 0, nb = 0, total = 0;
+  ~NewPointsSlot() { if (h) dvm_new_points_destroy(h); }
+};
+dvm_np_keyframe NpKeyFrame(const dvmh_keyframe_view& K) {
+  dvm_np_keyframe k;
+  std::memset(&k, 0, sizeof(k));
+  k.n = K.N; k.kps = K.mvKeysUn; k.desc = K.mDescriptors; k.mp = K.mvpMapPoints;
+  k.fv_n = K.mFeatVec.n; k.fv_node = K.mFeatVec.node; k.fv_off = K.mFeatVec.off; k.fv_feat = K.mFeatVec.feat;
+  k.Tcw = K.Tcw; k.Twc = K.Twc;
+  std::memcpy(k.Ow, K.Twc.t, 12);                 // KeyFrame::GetCameraCenter() = mTwc.translation()
+  k.fx = K.fx; k.fy = K.fy; k.cx = K.cx; k.cy = K.cy;
+  k.scale_factors = K.mvScaleFactors; k.level_sigma2 = K.mvLevelSigma2; k.n_levels = K.nLevels;
+  return k;
+}
+}  // namespace
+int dvmh_create_new_map_points(int device, const dvmh_keyframe_view* cur, int n_neighbours, const dvmh_keyframe_view* neighbours,
+                               const float* median_depth, const dvm_np_params* p, dvm_np_out* out) {
+  if (!cur || n_neighbours < 0 || (n_neighbours > 0 && (!neighbours || !median_depth)) || !p || !out) return DVM_ERR_INVALID;
+  thread_local NewPointsSlot slot;
+  if (slot.h && slot.device != device) { dvm_new_points_destroy(slot.h); slot = NewPointsSlot(); }
+  if (!slot.h) {
+    const int rc = dvm_new_points_create(device, &slot.h);
+    if (rc != DVM_OK) { slot.h = nullptr; return rc; }
+    slot.device = device;
+  }
+  std::vector<dvm_np_neighbour> nbs((size_t)n_neighbours);
+  int64_t total = 0;
+  for (int j = 0; j < n_neighbours; j++) {
+    nbs[j].kf = NpKeyFrame(neighbours[j]);
+    nbs[j].median_depth = median_depth[j];
+    float R12[9], t12[3];
+    dvm_host::ORBmatcher::TriangulationGeometry(KeyFrameView(*cur), KeyFrameView(neighbours[j]), R12, t12, nbs[j].ep, nbs[j].F12);
+    total += std::max(neighbours[j].N, 0);
+  }
+  const dvm_np_keyframe c = NpKeyFrame(*cur);
+  // growth only, with headroom; sizes no reservation can hold are left to the call's own checks (they name the offending keyframe)
+  if (c.n >= 0 && c.n <= 8192 && total <= (int64_t)n_neighbours * 8192 && (c.n > slot.n1 || n_neighbours > slot.nb || total > slot.total)) {
+    const int n1 = std::max(slot.n1, c.n), nb = std::max(slot.nb, n_neighbours);
+    const int tot = (int)std::min<int64_t>(std::max<int64_t>(slot.total, total + total / 4), (int64_t)nb * 8192);
+    const int rc = dvm_new_points_reserve(slot.h, n1, nb, tot);
+    if (rc != DVM_OK) return rc;
+    slot.n1 = n1; slot.nb = nb; slot.total = tot;
+  }
+  return dvm_create_new_map_points(slot.h, &c, n_neighbours, nbs.data(), p, out);
+}
 int dvmh_fuse(int device, const dvmh_keyframe_view* KF, const dvmh_map_points_view* P, const uint8_t* inKF, float th, int32_t* best_idx) {
   dvm_host::ORBmatcher m(0.6f, true, device);
   return m.Fuse(KeyFrameView(*KF), MapPointsView(*P), inKF, th, best_idx);

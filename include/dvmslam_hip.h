@@ -339,6 +339,92 @@ int dvm_match_triangulation(const uint8_t* desc1, const dvm_keypoint* kps1, int 
                             const float* level_sigma2_2, int nlevels, int32_t* best_idx, int32_t* best_dist, int on_device,
                             void* stream);
 
+/* LocalMapping::CreateNewMapPoints (LocalMapping.cc:446-760, monocular pinhole) for ALL neighbour keyframes of the current keyframe as
+ * ONE device chain: one upload, three launches whatever n_neighbours is, one synchronisation.  Per neighbour, in the order given:
+ *   1. baseline test (:497-512): baseline = ||Ow2 - Ow1|| in float, summed as x^2 + y^2 + z^2; ratio = baseline / median_depth in float;
+ *      the neighbour is skipped when (double)ratio < 0.01 -- plain arithmetic, no special case: a negative median depth (what
+ *      ComputeSceneMedianDepth returns without points) skips, a zero one gives +inf and does not;
+ *   2. ORBmatcher::SearchForTriangulation (what dvm_match_triangulation + the host's node walk and rotation check do today) against the
+ *      current keyframe's map-point table AS THE EARLIER NEIGHBOURS LEFT IT;
+ *   3. the geometry of dvm_triangulate_matches for every pair the search returned (same codes, same zero-filling);
+ *   4. every KF1 keypoint of a status-0 pair is marked as having a point.
+ * The reference never sets vbMatched2 (ORBmatcher.cc:878,927), so the best KF2 candidate of a KF1 keypoint depends on that keypoint and the
+ * neighbour only: the search and the geometry of all (neighbour, keypoint without a point at entry) run speculatively in two launches, and
+ * one workgroup then walks the neighbours in order -- live matches (no point so far), rotation histogram + ComputeThreeMaxima over them,
+ * compaction in ascending idx1, table update.  The results equal the loop of the separate calls bit for bit.
+ *
+ * dvm_np_keyframe: what the two separate calls read of a keyframe.  mp[i] = map point id of keypoint i, -1 = none (of a neighbour: KF2
+ * features with a point are no candidates).  fv_*: the flattened DBoW2::FeatureVector (dvmh_feature_vector_view): node ids strictly
+ * ascending, features of node k = fv_feat[fv_off[k] .. fv_off[k+1]), fv_off[0] = 0, at most n features in all.  A neighbour also carries
+ * median_depth = ComputeSceneMedianDepth(2) (the map points live with the caller) and the pair geometry ep / F12 as
+ * dvmh_triangulation_geometry(cur, neighbour) computes it (index-free host arithmetic; dvmh_create_new_map_points fills it in).
+ * PRECONDITION: the neighbours are distinct keyframes (GetBestCovisibilityKeyFrames returns each once; a data-only check cannot see it).
+ *
+ * dvm_np_out (caller memory, written once after the synchronisation):
+ *   nb_status[n_neighbours]   0 ran, 1 skipped by the baseline test
+ *   nb_matches[n_neighbours]  SearchForTriangulation's return value for that neighbour (0 when skipped)
+ *   pair_off[n_neighbours+1]  neighbour j's records are [pair_off[j], pair_off[j+1])
+ *   pairs[2 m], status[m], x3D[3 m]   flat records in neighbour order, inside a neighbour by ascending idx1 -- exactly vMatchedIndices;
+ *                             ALL pairs are recorded, not only the accepted ones; record_cap = records the three arrays hold
+ *   new_point[cur->n]         the record that gave KF1 keypoint i its point, -1 none
+ * How a caller that honours CheckNewKeyFrames() (:490) uses it: the records of neighbour j do not depend on later neighbours, so it applies
+ * the records neighbour by neighbour and stops at the neighbour at which the reference would have returned; the rest is dropped.  Two records
+ * of one neighbour may name the same idx2 (both status 0): they come in idx1 order and the caller's pKF2->AddMapPoint overwrites, as the
+ * reference's does.
+ *
+ * Errors, all reported before anything runs and leaving the handle usable: DVM_ERR_CAPACITY -- cur->n, n_neighbours or the neighbours'
+ * total keypoints beyond the reservation, or record_cap < n_neighbours x (keypoints of cur without a point); DVM_ERR_INVALID -- a keyframe
+ * with n > 8192, non-monotone fv_off, a feature index outside [0, n), nodes not ascending, level tables of unequal length or outside
+ * [1, 64], a zero focal length, a missing array, p->monocular != 1 (the stereo branches are outside the project's scope, as in the
+ * separate calls).  A KF2 candidate whose octave lies outside the tables is no candidate; a KF1 keypoint whose octave does gives status -1
+ * with nothing read.  dvm_new_points_create returns DVM_ERR_NO_DEVICE without a GPU. */
+typedef struct {
+  int32_t n;
+  const dvm_keypoint* kps;      /* mvKeysUn */
+  const uint8_t* desc;          /* n x 32 */
+  const int32_t* mp;            /* n */
+  int32_t fv_n;
+  const int32_t *fv_node, *fv_off, *fv_feat;
+  dvm_se3f Tcw, Twc;            /* GetPose(), GetPoseInverse() */
+  float Ow[3];                  /* GetCameraCenter() */
+  float fx, fy, cx, cy;
+  const float* scale_factors;   /* mvScaleFactors */
+  const float* level_sigma2;    /* mvLevelSigma2 */
+  int32_t n_levels;
+} dvm_np_keyframe;
+typedef struct {
+  dvm_np_keyframe kf;
+  float median_depth;
+  float ep[2], F12[9];
+} dvm_np_neighbour;
+typedef struct {
+  double cos_parallax_max;      /* 0.9998, 0.9996 inertial (:655-656) */
+  float ratio_factor;           /* 1.5f * mpCurrentKeyFrame->mfScaleFactor (:483) */
+  float th_far;                 /* mThFarPoints */
+  int32_t far_points;           /* mbFarPoints */
+  int32_t coarse, check_ori;    /* bCoarse; the matcher's mbCheckOrientation */
+  int32_t monocular;            /* must be 1 */
+} dvm_np_params;
+typedef struct {
+  int32_t *nb_status, *nb_matches, *pair_off;
+  int32_t* pairs;
+  int32_t* status;
+  float* x3D;
+  int32_t* new_point;
+  int32_t record_cap;
+} dvm_np_out;
+typedef struct dvm_new_points dvm_new_points;
+int dvm_new_points_create(int device, dvm_new_points** out);
+void dvm_new_points_destroy(dvm_new_points* h);
+/* the working set for calls up to these sizes (grow-only; a call never allocates) */
+int dvm_new_points_reserve(dvm_new_points* h, int max_kf1_keypoints, int max_neighbours, int max_total_neighbour_keypoints);
+int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int n_neighbours, const dvm_np_neighbour* nbs,
+                              const dvm_np_params* p, dvm_np_out* out);
+/* HIP-event timing of the three launches (measurement only): enable != 0 makes every call record events; ms[3] = search, geometry,
+ * settle of the last call that ran */
+int dvm_new_points_profiling(dvm_new_points* h, int enable);
+int dvm_new_points_last_kernel_ms(dvm_new_points* h, float* ms);
+
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:384-453), batched: map point p owns the descriptors
  * desc[off[p] .. off[p+1]) (32 B each, its observations in the reference's iteration order); best_idx[p] = index
  * inside that range of the descriptor with the least median Hamming distance to the others (median =

@@ -153,6 +153,12 @@ int dvmh_search_by_bow_kf_kf(int device, const dvmh_keyframe_view* KF1, const dv
 int dvmh_search_for_triangulation(int device, const dvmh_keyframe_view* KF1, const dvmh_keyframe_view* KF2, int coarse, int check_ori, int32_t* pairs);
 /* the geometry it derives from the two poses (:841-862, CameraModels/Pinhole.cpp:106-110): R12 [9], t12 [3], epipole [2], F12 [9] */
 void dvmh_triangulation_geometry(const dvmh_keyframe_view* KF1, const dvmh_keyframe_view* KF2, float* R12, float* t12, float* ep, float* F12);
+/* LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:446-760) for all neighbours as ONE device chain: dvm_create_new_map_points
+ * (include/dvmslam_hip.h describes the steps, the records and the errors) on the views the matcher functions take.  median_depth[j] =
+ * neighbours[j]->ComputeSceneMedianDepth(2).  The pair geometry of every neighbour (dvmh_triangulation_geometry) is computed here; the
+ * camera centres are Twc's translations; the chain handle belongs to the calling thread and is reserved on growth only. */
+int dvmh_create_new_map_points(int device, const dvmh_keyframe_view* cur, int n_neighbours, const dvmh_keyframe_view* neighbours,
+                               const float* median_depth, const dvm_np_params* p, dvm_np_out* out);
 /* Fuse(pKF, vpMapPoints, th), :1060-1234, search part: best_idx[i] = keypoint the i-th point would fuse into (-1: none) */
 int dvmh_fuse(int device, const dvmh_keyframe_view* KF, const dvmh_map_points_view* P, const uint8_t* inKF, float th, int32_t* best_idx);
 /* Fuse(pKF, Scw, vpPoints, th, vpReplacePoint), :1236-1345: KF->mvpMapPoints receives the added points, replace[i] the id to replace */
