@@ -2071,3 +2071,111 @@ def create_new_map_points(cur, neighbours, median_depth, device=0, record_cap=No
                 C.byref(p), C.byref(R.out))
     check(rc)
     return R.result()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dvm_fuse_targets: the Fuse searches of LocalMapping::SearchInNeighbors against all target keyframes as one chain
+class _FtTarget(C.Structure):   # == dvm_ft_target
+    _fields_ = [("n", C.c_int32), ("kps", C.c_void_p), ("desc", C.c_void_p), ("Tcw", C.c_float * 7), ("Ow", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("scale_factors", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("log_scale_factor", C.c_float), ("n_levels", C.c_int32)]
+
+
+class _FtPoints(C.Structure):   # == dvm_ft_points
+    _fields_ = [("n", C.c_int32), ("pos", C.c_void_p), ("normal", C.c_void_p), ("min_dist", C.c_void_p), ("max_dist", C.c_void_p),
+                ("desc", C.c_void_p), ("valid", C.c_void_p)]
+
+
+class FuseTargets:
+    """dvm_fuse_targets: set() the target keyframes once (one upload, all grids in one launch), run() point tables against them."""
+
+    def __init__(self, device=0):
+        self.L = lib()
+        vp, i32 = C.c_void_p, C.c_int32
+        self.L.dvm_fuse_targets_create.argtypes = [i32, C.POINTER(vp)]
+        self.L.dvm_fuse_targets_destroy.argtypes = [vp]; self.L.dvm_fuse_targets_destroy.restype = None
+        self.L.dvm_fuse_targets_reserve.argtypes = [vp, i32, i32, i32]
+        self.L.dvm_fuse_targets_set.argtypes = [vp, i32, vp]
+        self.L.dvm_fuse_targets_run.argtypes = [vp, vp, vp, C.c_float, vp, vp]
+        self.L.dvm_fuse_targets_profiling.argtypes = [vp, i32]
+        self.L.dvm_fuse_targets_last_kernel_ms.argtypes = [vp, vp]
+        self.h = vp()
+        self.n_targets = 0
+        check(self.L.dvm_fuse_targets_create(device, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.dvm_fuse_targets_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def reserve(self, max_points, max_targets, max_total_target_keypoints):
+        check(self.L.dvm_fuse_targets_reserve(self.h, int(max_points), int(max_targets), int(max_total_target_keypoints)))
+
+    def profiling(self, enable=True):
+        check(self.L.dvm_fuse_targets_profiling(self.h, int(enable)))
+
+    def last_kernel_ms(self):
+        """(grid build of the last set, search of the last run) in milliseconds, with profiling on."""
+        ms = np.zeros(2, np.float32)
+        check(self.L.dvm_fuse_targets_last_kernel_ms(self.h, _p(ms)))
+        return ms
+
+    @staticmethod
+    def targets(kfs):
+        """Keyframe dicts (kps, desc, Tcw, K, bounds, scale_factors, inv_level_sigma2, log_scale_factor) -> (dvm_ft_target array, keepalive).
+        Ow is derived as KeyFrame::SetPose does (Twc's translation)."""
+        keep = []
+        arr = (_FtTarget * max(len(kfs), 1))()
+        for t, kf in enumerate(kfs):
+            v, k = keyframe_view(kf)
+            keep.append(k)
+            s = arr[t]
+            s.n, s.kps, s.desc = v.N, v.mvKeysUn, v.mDescriptors
+            s.Tcw = v.Tcw
+            s.Ow = (C.c_float * 3)(*v.Twc[4:7])
+            s.fx, s.fy, s.cx, s.cy = v.fx, v.fy, v.cx, v.cy
+            s.min_x, s.max_x, s.min_y, s.max_y = v.mnMinX, v.mnMaxX, v.mnMinY, v.mnMaxY
+            s.scale_factors, s.inv_level_sigma2 = v.mvScaleFactors, v.mvInvLevelSigma2
+            s.log_scale_factor, s.n_levels = v.mfLogScaleFactor, v.nLevels
+        return arr, keep
+
+    def set(self, kfs):
+        arr, keep = self.targets(kfs)
+        self.set_raw(arr, len(kfs))
+
+    def set_raw(self, arr, n):
+        check(self.L.dvm_fuse_targets_set(self.h, int(n), C.addressof(arr)))
+        self.n_targets = int(n)
+
+    def run(self, pts, th=3.0, skip=None, want_dist=True):
+        """pts: dict(pos, normal, min_dist, max_dist, desc[, valid]); skip: [T, n] uint8 or None.  Returns (best_idx[T, n], best_dist[T, n])
+        (best_dist None with want_dist = False)."""
+        P, keep = map_points_view(pts)
+        n, T = P.n, self.n_targets
+        s = _FtPoints()
+        s.n, s.pos, s.normal, s.min_dist, s.max_dist, s.desc = n, P.pos, P.normal, P.min_dist, P.max_dist, P.desc
+        va = None if pts.get("valid") is None else np.ascontiguousarray(pts["valid"], np.uint8)
+        s.valid = _ptr(va)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(T, n)
+        bi = np.full((T, n), -7, np.int32); bd = np.full((T, n), -7, np.int32) if want_dist else None
+        check(self.L.dvm_fuse_targets_run(self.h, C.addressof(s), _ptr(sk), float(th), _ptr(bi), _ptr(bd)))
+        return bi, bd
+
+
+def fuse_targets(kfs, P, in_kf, th, device=0):
+    """dvmh_fuse_targets: kfs = keyframe_view() results, P = map_points_view() result, in_kf [T, n] or None.
+    Returns (count, best_idx[T, n])."""
+    T, n = len(kfs), P[0].n
+    views = (_KeyFrameView * max(T, 1))()
+    for t, kv in enumerate(kfs):
+        views[t] = kv[0]
+    bi = np.full((T, n), -7, np.int32)
+    ik = None if in_kf is None else np.ascontiguousarray(in_kf, np.uint8).reshape(T, n)
+    rc = _hcall("dvmh_fuse_targets", C.c_int32, C.c_int32(device), C.c_int32(T), C.byref(views), C.byref(P[0]), C.c_void_p(_ptr(ik)), C.c_float(th),
+                C.c_void_p(_ptr(bi)))
+    check(min(rc, 0))
+    return rc, bi

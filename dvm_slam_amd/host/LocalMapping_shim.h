@@ -34,12 +34,30 @@
 //
 // (bCoarse is computed once in front of the loop; the matcher of :467 is ORBmatcher(0.6f, false), so the rotation check is off.)
 //
+// SearchInNeighborsChain does the same for LocalMapping::SearchInNeighbors (src/LocalMapping.cc:757-865): both Fuse directions (:812-849)
+// on dvm_fuse_targets -- all target keyframes uploaded once, their grids built in one launch, all (target, point) searches in one launch,
+// one synchronisation per direction -- where the reference's loop makes one blocking Fuse call per target.  The function then reads
+//
+//   ... the target selection of :759-810, unchanged, fills vpTargetKFs ...
+//   const SearchInNeighborsCounts fused = SearchInNeighborsChain(keyFrame, vpTargetKFs, &mbAbortBA);
+//   if (fused.aborted) return;                               // mbAbortBA was set between the two directions (:823)
+//   vpMapPointMatches = keyFrame->GetMapPointMatches();      // the point update of :851-861 and UpdateConnections (:864): as before
+//
+// The searches are speculative: they read the descriptors as they are at entry, and the rows are replayed target by target exactly as
+// ORBmatcher::Fuse applies them (isBad() / IsInKeyFrame() tested again at each row).  MapPoint::Replace ends in
+// ComputeDistinctiveDescriptors, so the survivor of a Replace may carry a new descriptor for the later targets: its descriptor is compared
+// with the bytes that were uploaded, and before a row of such a point is applied ONE further run refreshes the rows of all points stale at
+// that moment against the targets not yet finished.  No row of a stale point is applied unrefreshed.
+//
 // Not covered: the stereo / two-camera-rig branches (bStereo1 / bStereo2, mpCamera2) -- DVM-SLAM's agents are monocular.
 // Parity: float arithmetic in Eigen's evaluation order; the homogeneous point comes from a double Jacobi diagonalisation of
 // A^T A where the reference runs Eigen::JacobiSVD<Matrix4f> -- the same vector up to float SVD error (tolerance parity, as for
 // Sim3Solver's eigen-decomposition; decisions equal away from the thresholds).
 #pragma once
+#include <cstring>
 #include <stdexcept>
+#include <unordered_map>
+#include <unordered_set>
 #include <utility>
 #include <vector>
 
@@ -173,6 +191,194 @@ inline NewPointRecords CreateNewMapPointsChain(KeyFrame* pKF1, const std::vector
     R.pairs[m] = std::make_pair((size_t)pairs[2 * m], (size_t)pairs[2 * m + 1]);
     for (int k = 0; k < 3; k++) R.x3D[m](k) = X[3 * m + k];
   }
+  return R;
+}
+
+// ---- LocalMapping::SearchInNeighbors (:812-849) on dvm_fuse_targets
+namespace dvm_fuse_detail {
+// the calling thread's chain handle: created on first use, reserved on growth, never per call
+struct Handle {
+  dvm_fuse_targets* h = nullptr;
+  int device = -1, np = 0, nt = 0, total = 0;
+  ~Handle() { if (h) dvm_fuse_targets_destroy(h); }
+  void ensure(int dev, int n_points, int n_targets, long total_keypoints) {
+    if (h && device != dev) { dvm_fuse_targets_destroy(h); h = nullptr; np = nt = total = 0; }
+    if (!h) {
+      if (dvm_fuse_targets_create(dev, &h) != DVM_OK) { h = nullptr; throw std::runtime_error(dvm_last_error()); }
+      device = dev;
+    }
+    if (n_points <= np && n_targets <= nt && total_keypoints <= total) return;
+    const int p = std::max(np, n_points + n_points / 4), t = std::max(nt, n_targets);
+    const int tot = (int)std::min<long>(std::max<long>(total, total_keypoints + total_keypoints / 4), (long)t * 8192);
+    if (dvm_fuse_targets_reserve(h, p, t, tot) != DVM_OK) throw std::runtime_error(dvm_last_error());
+    np = p; nt = t; total = tot;
+  }
+};
+inline Handle& handle() {
+  thread_local Handle H;
+  return H;
+}
+inline void read_descriptor(MapPoint* p, uint8_t* dst) {
+  const cv::Mat d = p->GetDescriptor();
+  std::memcpy(dst, d.ptr<uint8_t>(), 32);
+}
+// LocalMapping.cc:840-842: a point is a fuse candidate once per keyframe, `pMP->mnFuseCandidateForKF == keyFrame->mnId` says it has been
+// taken.  The first overload is the reference's test and mark; it is chosen wherever the point class has the member.  A point class
+// without it (a reduced MapPoint) gets the same answer from a set that lives for the call.  Returns true the first time a point is seen.
+template <class MP>
+inline auto MarkFuseCandidate(MP* pMP, long unsigned int kfId, std::unordered_set<MP*>&, int) -> decltype(pMP->mnFuseCandidateForKF == kfId) {
+  if (pMP->mnFuseCandidateForKF == kfId) return false;
+  pMP->mnFuseCandidateForKF = kfId;
+  return true;
+}
+template <class MP>
+inline bool MarkFuseCandidate(MP* pMP, long unsigned int, std::unordered_set<MP*>& seen, long) {
+  return seen.insert(pMP).second;
+}
+struct NoSeam {
+  void operator()(MapPoint*, MapPoint*) const {}
+};
+
+// ORBmatcher::Fuse(pKF, vpPoints, th) for every pKF of vpKFs in order (ORBmatcher.cc:1060-1234): nFused[t] = its return value
+template <class AfterReplace>
+inline void FusePass(const std::vector<KeyFrame*>& vpKFs, const std::vector<MapPoint*>& vpPoints, float th, AfterReplace& afterReplace,
+                     std::vector<int>& nFused, int& nDeviceCalls) {
+  static_assert(sizeof(cv::KeyPoint) == sizeof(dvm_keypoint), "cv::KeyPoint is passed as dvm_keypoint");
+  const size_t T = vpKFs.size(), n = vpPoints.size();
+  nFused.assign(T, 0);
+  if (T == 0 || n == 0) return;
+  std::vector<dvm_ft_target> targets(T);
+  long total = 0;
+  for (size_t t = 0; t < T; t++) {
+    KeyFrame* kf = vpKFs[t];
+    if (kf->NLeft != -1) throw std::runtime_error("SearchInNeighborsChain: stereo / fisheye pairs (NLeft != -1) are outside the accelerated path");
+    if (kf->mvScaleFactors.size() != kf->mvInvLevelSigma2.size()) throw std::invalid_argument("SearchInNeighborsChain: a keyframe's pyramid tables differ in length");
+    dvm_ft_target& k = targets[t];
+    std::memset(&k, 0, sizeof(k));
+    k.n = kf->N; k.kps = reinterpret_cast<const dvm_keypoint*>(kf->mvKeysUn.data()); k.desc = kf->mDescriptors.data;
+    const Sophus::SE3f Tcw = kf->GetPose();
+    const Eigen::Vector3f Ow = kf->GetCameraCenter();
+    for (int i = 0; i < 4; i++) k.Tcw.q[i] = Tcw.unit_quaternion().coeffs()(i);
+    for (int i = 0; i < 3; i++) { k.Tcw.t[i] = Tcw.translation()(i); k.Ow[i] = Ow(i); }
+    k.fx = kf->fx; k.fy = kf->fy; k.cx = kf->cx; k.cy = kf->cy;
+    k.min_x = (float)kf->mnMinX; k.max_x = (float)kf->mnMaxX; k.min_y = (float)kf->mnMinY; k.max_y = (float)kf->mnMaxY;
+    k.scale_factors = kf->mvScaleFactors.data(); k.inv_level_sigma2 = kf->mvInvLevelSigma2.data();
+    k.log_scale_factor = kf->mfLogScaleFactor; k.n_levels = (int32_t)kf->mvScaleFactors.size();
+    total += kf->N;
+  }
+  // the point table as it is at entry: position, normal and distance range do not move inside the loop; the descriptor may
+  std::vector<float> pos(3 * n, 0.f), normal(3 * n, 0.f), mind(n, 1.f), maxd(n, 1.f);
+  std::vector<uint8_t> desc(32 * n, 0), valid(n, 0), skip(T * n, 0);
+  std::unordered_map<MapPoint*, std::vector<size_t>> where;             // a point may sit at two keypoints
+  for (size_t i = 0; i < n; i++) {
+    MapPoint* p = vpPoints[i];
+    if (!p || p->isBad()) continue;
+    valid[i] = 1;
+    const Eigen::Vector3f X = p->GetWorldPos(), Nn = p->GetNormal();
+    for (int c = 0; c < 3; c++) { pos[3 * i + c] = X(c); normal[3 * i + c] = Nn(c); }
+    mind[i] = p->GetMinDistance(); maxd[i] = p->GetMaxDistance();
+    read_descriptor(p, &desc[32 * i]);
+    where[p].push_back(i);
+    for (size_t t = 0; t < T; t++) skip[t * n + i] = p->IsInKeyFrame(vpKFs[t]) ? 1 : 0;
+  }
+  dvm_ft_points P;
+  P.n = (int32_t)n; P.pos = pos.data(); P.normal = normal.data(); P.min_dist = mind.data(); P.max_dist = maxd.data(); P.desc = desc.data();
+  P.valid = valid.data();
+  Handle& H = handle();
+  dvm_host::use_device();
+  H.ensure(dvm_host::device(), (int)n, (int)T, total);
+  if (dvm_fuse_targets_set(H.h, (int)T, targets.data()) != DVM_OK) throw std::runtime_error(dvm_last_error());
+  std::vector<int32_t> best(T * n, -1), fresh;
+  if (dvm_fuse_targets_run(H.h, &P, skip.data(), th, best.data(), nullptr) != DVM_OK) throw std::runtime_error(dvm_last_error());
+  nDeviceCalls++;
+
+  std::vector<uint8_t> stale(n, 0);
+  size_t nStale = 0;
+  // rows (t.., i) of every stale point, searched again with the descriptors the points carry now
+  auto refresh = [&](size_t t0) {
+    std::vector<uint8_t> mask(T * n, 1);
+    for (size_t i = 0; i < n; i++) {
+      if (!stale[i]) continue;
+      MapPoint* p = vpPoints[i];
+      read_descriptor(p, &desc[32 * i]);
+      for (size_t t = t0; t < T; t++) mask[t * n + i] = (p->isBad() || p->IsInKeyFrame(vpKFs[t])) ? 1 : 0;
+    }
+    fresh.assign(T * n, -1);
+    if (dvm_fuse_targets_run(H.h, &P, mask.data(), th, fresh.data(), nullptr) != DVM_OK) throw std::runtime_error(dvm_last_error());
+    nDeviceCalls++;
+    for (size_t i = 0; i < n; i++) {
+      if (!stale[i]) continue;
+      for (size_t t = t0; t < T; t++) best[t * n + i] = fresh[t * n + i];
+      stale[i] = 0;
+    }
+    nStale = 0;
+  };
+  // the descriptor of a Replace's survivor against the bytes the device holds
+  auto check_survivor = [&](MapPoint* s) {
+    const auto it = where.find(s);
+    if (it == where.end()) return;
+    uint8_t now[32];
+    read_descriptor(s, now);
+    for (size_t i : it->second)
+      if (!stale[i] && std::memcmp(now, &desc[32 * i], 32) != 0) { stale[i] = 1; nStale++; }
+  };
+  for (size_t t = 0; t < T; t++) {
+    KeyFrame* pKF = vpKFs[t];
+    for (size_t i = 0; i < n; i++) {
+      MapPoint* pMP = vpPoints[i];
+      if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;      // state may have changed through an earlier Replace
+      if (nStale && stale[i]) refresh(t);
+      const int32_t idx = best[t * n + i];
+      if (idx < 0) continue;
+      MapPoint* pMPinKF = pKF->GetMapPoint(idx);
+      if (pMPinKF) {
+        if (!pMPinKF->isBad()) {
+          if (pMPinKF->Observations() > pMP->Observations()) { pMP->Replace(pMPinKF); afterReplace(pMPinKF, pMP); check_survivor(pMPinKF); }
+          else { pMPinKF->Replace(pMP); afterReplace(pMP, pMPinKF); check_survivor(pMP); }
+        }
+      } else {
+        pMP->AddObservation(pKF, idx);
+        pKF->AddMapPoint(pMP, idx);
+      }
+      nFused[t]++;
+    }
+  }
+}
+}  // namespace dvm_fuse_detail
+
+// what SearchInNeighborsChain hands back: ORBmatcher::Fuse's return value per target keyframe (first direction) and for the current
+// keyframe (second direction), the blocking device calls made (two without a stale descriptor), and whether *pbAbort ended it in between
+struct SearchInNeighborsCounts {
+  std::vector<int> nFused;
+  int nFusedCurrent = 0;
+  int nDeviceCalls = 0;
+  bool aborted = false;
+};
+
+// LocalMapping.cc:812-849.  afterReplace(survivor, replaced) is called after each MapPoint::Replace: a seam for tests whose mock Replace
+// does not recompute descriptors; it does nothing in production (MapPoint::Replace itself ends in ComputeDistinctiveDescriptors).
+template <class AfterReplace = dvm_fuse_detail::NoSeam>
+inline SearchInNeighborsCounts SearchInNeighborsChain(KeyFrame* keyFrame, const std::vector<KeyFrame*>& vpTargetKFs, const bool* pbAbort,
+                                                      AfterReplace afterReplace = AfterReplace(), const float th = 3.0f) {
+  SearchInNeighborsCounts R;
+  // Search matches by projection from current KF in target KFs
+  const std::vector<MapPoint*> vpMapPointMatches = keyFrame->GetMapPointMatches();
+  dvm_fuse_detail::FusePass(vpTargetKFs, vpMapPointMatches, th, afterReplace, R.nFused, R.nDeviceCalls);
+  if (pbAbort && *pbAbort) { R.aborted = true; return R; }
+  // Search matches by projection from target KFs in current KF
+  std::vector<MapPoint*> vpFuseCandidates;
+  vpFuseCandidates.reserve(vpTargetKFs.size() * vpMapPointMatches.size());
+  std::unordered_set<MapPoint*> seen;                                  // (only read where MapPoint has no mnFuseCandidateForKF)
+  for (KeyFrame* pKFi : vpTargetKFs) {
+    for (MapPoint* pMP : pKFi->GetMapPointMatches()) {
+      if (!pMP) continue;
+      if (pMP->isBad() || !dvm_fuse_detail::MarkFuseCandidate(pMP, keyFrame->mnId, seen, 0)) continue;
+      vpFuseCandidates.push_back(pMP);
+    }
+  }
+  std::vector<int> nCur;
+  dvm_fuse_detail::FusePass(std::vector<KeyFrame*>(1, keyFrame), vpFuseCandidates, th, afterReplace, nCur, R.nDeviceCalls);
+  R.nFusedCurrent = nCur.empty() ? 0 : nCur[0];
   return R;
 }
 

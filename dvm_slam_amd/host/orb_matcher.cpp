@@ -1065,6 +1065,64 @@ int dvmh_fuse(int device, const dvmh_keyframe_view* KF, const dvmh_map_points_vi
   dvm_host::ORBmatcher m(0.6f, true, device);
   return m.Fuse(KeyFrameView(*KF), MapPointsView(*P), inKF, th, best_idx);
 }
+namespace {
+struct FuseTargetsSlot {
+  int device = -1;
+  dvm_fuse_targets* h = nullptr;
+  int np = 0, nt = 0, total = 0;
+  ~FuseTargetsSlot() { if (h) dvm_fuse_targets_destroy(h); }
+};
+}  // namespace
+int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targets, const dvmh_map_points_view* P, const uint8_t* inKF, float th,
+                      int32_t* best_idx) {
+  if (n_targets < 0 || (n_targets > 0 && !targets) || !P || P->n < 0) return DVM_ERR_INVALID;
+  thread_local FuseTargetsSlot slot;
+  if (slot.h && slot.device != device) { dvm_fuse_targets_destroy(slot.h); slot = FuseTargetsSlot(); }
+  if (!slot.h) {
+    const int rc = dvm_fuse_targets_create(device, &slot.h);
+    if (rc != DVM_OK) { slot.h = nullptr; return rc; }
+    slot.device = device;
+  }
+  std::vector<dvm_ft_target> tg((size_t)n_targets);
+  int64_t total = 0;
+  for (int t = 0; t < n_targets; t++) {
+    const dvmh_keyframe_view& K = targets[t];
+    dvm_ft_target& k = tg[t];
+    std::memset(&k, 0, sizeof(k));
+    k.n = K.N; k.kps = K.mvKeysUn; k.desc = K.mDescriptors;
+    k.Tcw = K.Tcw;
+    std::memcpy(k.Ow, K.Twc.t, 12);                 // KeyFrame::GetCameraCenter() = mTwc.translation()
+    k.fx = K.fx; k.fy = K.fy; k.cx = K.cx; k.cy = K.cy;
+    k.min_x = K.mnMinX; k.max_x = K.mnMaxX; k.min_y = K.mnMinY; k.max_y = K.mnMaxY;
+    k.scale_factors = K.mvScaleFactors; k.inv_level_sigma2 = K.mvInvLevelSigma2;
+    k.log_scale_factor = K.mfLogScaleFactor; k.n_levels = K.nLevels;
+    total += std::max(K.N, 0);
+  }
+  // growth only, with headroom; sizes no reservation can hold are left to the calls' own checks (they name the offending target)
+  if (n_targets <= 65535 && total <= (int64_t)n_targets * 8192 && (int64_t)std::max(P->n, slot.np) * std::max(n_targets, slot.nt) <= ((int64_t)1 << 27) &&
+      (P->n > slot.np || n_targets > slot.nt || total > slot.total)) {
+    const int np = std::max(slot.np, P->n), nt = std::max(slot.nt, n_targets);
+    const int tot = (int)std::min<int64_t>(std::max<int64_t>(slot.total, total + total / 4), (int64_t)nt * 8192);
+    const int rc = dvm_fuse_targets_reserve(slot.h, np, nt, tot);
+    if (rc != DVM_OK) return rc;
+    slot.np = np; slot.nt = nt; slot.total = tot;
+  }
+  int rc = dvm_fuse_targets_set(slot.h, n_targets, tg.data());
+  if (rc != DVM_OK) return rc;
+  const size_t n = (size_t)P->n, E = n * (size_t)n_targets;
+  if (E == 0) return 0;
+  std::vector<uint8_t> valid(n, 1);
+  for (size_t i = 0; i < n; i++)
+    if ((P->id && P->id[i] < 0) || (P->bad && P->bad[i])) valid[i] = 0;   // !pMP, isBad(); IsInKeyFrame(pKF) is the mask
+  dvm_ft_points pts;
+  pts.n = P->n; pts.pos = P->pos; pts.normal = P->normal; pts.min_dist = P->min_dist; pts.max_dist = P->max_dist; pts.desc = P->desc;
+  pts.valid = valid.data();
+  rc = dvm_fuse_targets_run(slot.h, &pts, inKF, th, best_idx, nullptr);
+  if (rc != DVM_OK) return rc;
+  int nFused = 0;
+  for (size_t e = 0; e < E; e++) nFused += best_idx[e] >= 0 ? 1 : 0;
+  return nFused;
+}
 int dvmh_fuse_sim3(int device, dvmh_keyframe_view* KF, const dvm_sim3f* Scw, const dvmh_map_points_view* P, float th, int32_t* replace) {
   dvm_host::ORBmatcher m(0.6f, true, device);
   KeyFrameView K(*KF);                    // (the function writes through K.mvpMapPoints, the caller's array)

@@ -425,6 +425,63 @@ int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int
 int dvm_new_points_profiling(dvm_new_points* h, int enable);
 int dvm_new_points_last_kernel_ms(dvm_new_points* h, float* ms);
 
+/* The first half of LocalMapping::SearchInNeighbors (LocalMapping.cc:812-821): ORBmatcher::Fuse(pKFi, vpMapPointMatches) once per target
+ * keyframe -- its search part (ORBmatcher.cc:1089-1210) for ALL targets as ONE chain.  The search reads the target keyframe, the point's
+ * position, normal, distance range and descriptor, and two skip conditions (isBad(), IsInKeyFrame(pKF)); everything the loop mutates is in
+ * the apply step (:1213-1228), which stays with the caller.  Walking the targets in order moves only three things: isBad() and
+ * IsInKeyFrame(target) can only turn true (a host-side skip when the row is applied), and MapPoint::Replace ends in
+ * ComputeDistinctiveDescriptors (MapPoint.cc:356), so a surviving point may carry a new descriptor for the later targets.  All T x n searches
+ * therefore run speculatively in one launch, and the caller runs again -- masked -- the rows of points whose descriptor really changed.
+ *
+ *   set   uploads all targets in one staged copy and builds all their grids in one launch (the order dvm_frame_build produces, the spans
+ *         back to back).  It does not wait.  The targets stay resident until the next set (or a reserve that grows the working set).
+ *   run   uploads the point table and the mask once, launches ONE kernel over (target, point) -- one 16-lane row per pair -- and copies the
+ *         two result arrays back behind one synchronisation.  It may be called again on the same targets with other points or masks.
+ *
+ * Contract: best_idx / best_dist [T * n], entry (t, i) at t * n + i, equals bit for bit what dvm_project_search returns for target t alone
+ * with gate_inv_sigma2 = inv_level_sigma2, gate = 5.99 and valid[i] && !skip[t * n + i]; then dvmh_fuse's rule: best_idx = -1 unless
+ * best_dist <= 50 (ORBmatcher::TH_LOW).  best_dist (may be NULL) is the raw distance, 256 without a candidate.  A masked entry costs its
+ * row's early exit and reads best_idx = -1, best_dist = 256.
+ *
+ * Errors, all reported before anything runs and leaving the handle (and the resident targets) usable: DVM_ERR_CAPACITY -- targets, their
+ * total keypoints or the points beyond the reservation; DVM_ERR_INVALID -- a target with n > 8192, n_levels outside [1, 64], a zero focal
+ * length, empty image bounds, a keypoint whose octave lies outside the level tables (the gate indexes them), a missing array, run before
+ * set.  dvm_fuse_targets_create returns DVM_ERR_NO_DEVICE without a GPU.  A target with n = 0 is legal (all its entries are -1 / 256);
+ * n_targets = 0 and P->n = 0 are legal and write nothing.  sizeof(dvm_ft_target) == 120, sizeof(dvm_ft_points) == 56 (LP64). */
+typedef struct {
+  int32_t n;
+  const dvm_keypoint* kps;          /* mvKeysUn */
+  const uint8_t* desc;              /* n x 32 */
+  dvm_se3f Tcw;                     /* GetPose() */
+  float Ow[3];                      /* GetCameraCenter() */
+  float fx, fy, cx, cy;
+  float min_x, max_x, min_y, max_y; /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+  const float* scale_factors;       /* mvScaleFactors */
+  const float* inv_level_sigma2;    /* mvInvLevelSigma2 */
+  float log_scale_factor;           /* mfLogScaleFactor */
+  int32_t n_levels;
+} dvm_ft_target;
+typedef struct {
+  int32_t n;
+  const float* pos;                 /* 3n  GetWorldPos() */
+  const float* normal;              /* 3n  GetNormal() */
+  const float* min_dist;            /* mfMinDistance, mfMaxDistance: the search applies the factors 0.8f / 1.2f */
+  const float* max_dist;
+  const uint8_t* desc;              /* 32n GetDescriptor() */
+  const uint8_t* valid;             /* n; may be NULL (all valid) */
+} dvm_ft_points;
+typedef struct dvm_fuse_targets dvm_fuse_targets;
+int dvm_fuse_targets_create(int device, dvm_fuse_targets** out);
+void dvm_fuse_targets_destroy(dvm_fuse_targets* h);
+/* the working set for calls up to these sizes (grow-only; set and run never allocate).  Growing it drops the resident targets. */
+int dvm_fuse_targets_reserve(dvm_fuse_targets* h, int max_points, int max_targets, int max_total_target_keypoints);
+int dvm_fuse_targets_set(dvm_fuse_targets* h, int n_targets, const dvm_ft_target* targets);
+int dvm_fuse_targets_run(dvm_fuse_targets* h, const dvm_ft_points* P, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist);
+/* HIP-event timing (measurement only): enable != 0 makes set and run record events; ms[2] = grid build of the last set, search of the
+ * last run (read after a run) */
+int dvm_fuse_targets_profiling(dvm_fuse_targets* h, int enable);
+int dvm_fuse_targets_last_kernel_ms(dvm_fuse_targets* h, float* ms);
+
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:384-453), batched: map point p owns the descriptors
  * desc[off[p] .. off[p+1]) (32 B each, its observations in the reference's iteration order); best_idx[p] = index
  * inside that range of the descriptor with the least median Hamming distance to the others (median =

@@ -161,6 +161,12 @@ int dvmh_create_new_map_points(int device, const dvmh_keyframe_view* cur, int n_
                                const float* median_depth, const dvm_np_params* p, dvm_np_out* out);
 /* Fuse(pKF, vpMapPoints, th), :1060-1234, search part: best_idx[i] = keypoint the i-th point would fuse into (-1: none) */
 int dvmh_fuse(int device, const dvmh_keyframe_view* KF, const dvmh_map_points_view* P, const uint8_t* inKF, float th, int32_t* best_idx);
+/* The same search against n_targets keyframes as ONE device chain (dvm_fuse_targets_set + dvm_fuse_targets_run, include/dvmslam_hip.h) --
+ * the first half of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:812-821).  inKF [n_targets * P->n] (may be NULL), best_idx likewise:
+ * row t equals dvmh_fuse(device, &targets[t], P, inKF + t * P->n, th, best_idx + t * P->n).  Returns the number of entries >= 0.  The
+ * chain handle belongs to the calling thread and is reserved on growth only. */
+int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targets, const dvmh_map_points_view* P, const uint8_t* inKF, float th,
+                      int32_t* best_idx);
 /* Fuse(pKF, Scw, vpPoints, th, vpReplacePoint), :1236-1345: KF->mvpMapPoints receives the added points, replace[i] the id to replace */
 int dvmh_fuse_sim3(int device, dvmh_keyframe_view* KF, const dvm_sim3f* Scw, const dvmh_map_points_view* P, float th, int32_t* replace);
 /* SearchByProjection(pKF, Scw, vpPoints, [vpPointsKFs,] vpMatched, [vpMatchedKF,] th, ratioHamming), :395-603; point_kf / matched_kf may be NULL */
