@@ -1976,40 +1976,57 @@ def _np_record_cap(cur, n_nb, record_cap):
     return int(record_cap) if record_cap is not None else int((np.asarray(cur["mp"]) < 0).sum()) * n_nb
 
 
-class NewPoints:
-    """dvm_new_points: LocalMapping::CreateNewMapPoints for all neighbour keyframes as one device chain."""
+class _Chain:
+    """A device-chain handle over <prefix>_create / _destroy / _reserve / _profiling / _last_kernel_ms, bound once at construction."""
 
-    def __init__(self, device=0):
+    def __init__(self, prefix, n_kernel_ms, device=0):
         self.L = lib()
         vp, i32 = C.c_void_p, C.c_int32
-        self.L.dvm_new_points_create.argtypes = [i32, C.POINTER(vp)]
-        self.L.dvm_new_points_destroy.argtypes = [vp]; self.L.dvm_new_points_destroy.restype = None
-        self.L.dvm_new_points_reserve.argtypes = [vp, i32, i32, i32]
-        self.L.dvm_create_new_map_points.argtypes = [vp, vp, i32, vp, vp, vp]
-        self.L.dvm_new_points_profiling.argtypes = [vp, i32]
-        self.L.dvm_new_points_last_kernel_ms.argtypes = [vp, vp]
+        create, self._destroy, self._reserve_fn, self._profiling, self._last_ms = (
+            getattr(self.L, f"{prefix}_{name}") for name in ("create", "destroy", "reserve", "profiling", "last_kernel_ms"))
+        create.argtypes = [i32, C.POINTER(vp)]
+        self._destroy.argtypes = [vp]; self._destroy.restype = None
+        self._reserve_fn.argtypes = [vp, i32, i32, i32]
+        self._profiling.argtypes = [vp, i32]
+        self._last_ms.argtypes = [vp, vp]
+        self._n_kernel_ms = n_kernel_ms
         self.h = vp()
-        check(self.L.dvm_new_points_create(device, C.byref(self.h)))
+        check(create(device, C.byref(self.h)))
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.dvm_new_points_destroy(self.h)
+            self._destroy(self.h)
             self.h = None
 
     def __del__(self):
         self.close()
 
-    def reserve(self, max_kf1_keypoints, max_neighbours, max_total_neighbour_keypoints):
-        check(self.L.dvm_new_points_reserve(self.h, int(max_kf1_keypoints), int(max_neighbours), int(max_total_neighbour_keypoints)))
+    def _reserve(self, a, b, c):
+        check(self._reserve_fn(self.h, int(a), int(b), int(c)))
 
     def profiling(self, enable=True):
-        check(self.L.dvm_new_points_profiling(self.h, int(enable)))
+        check(self._profiling(self.h, int(enable)))
+
+    def _last_kernel_ms(self):
+        ms = np.zeros(self._n_kernel_ms, np.float32)
+        check(self._last_ms(self.h, _p(ms)))
+        return ms
+
+
+class NewPoints(_Chain):
+    """dvm_new_points: LocalMapping::CreateNewMapPoints for all neighbour keyframes as one device chain."""
+
+    def __init__(self, device=0):
+        super().__init__("dvm_new_points", 3, device)
+        vp = C.c_void_p
+        self.L.dvm_create_new_map_points.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
+
+    def reserve(self, max_kf1_keypoints, max_neighbours, max_total_neighbour_keypoints):
+        self._reserve(max_kf1_keypoints, max_neighbours, max_total_neighbour_keypoints)
 
     def last_kernel_ms(self):
         """(search, geometry, settle) milliseconds of the last call that ran with profiling on."""
-        ms = np.zeros(3, np.float32)
-        check(self.L.dvm_new_points_last_kernel_ms(self.h, _p(ms)))
-        return ms
+        return self._last_kernel_ms()
 
     @staticmethod
     def _keyframe(kf, keep):
@@ -2087,42 +2104,22 @@ class _FtPoints(C.Structure):   # == dvm_ft_points
                 ("desc", C.c_void_p), ("valid", C.c_void_p)]
 
 
-class FuseTargets:
+class FuseTargets(_Chain):
     """dvm_fuse_targets: set() the target keyframes once (one upload, all grids in one launch), run() point tables against them."""
 
     def __init__(self, device=0):
-        self.L = lib()
-        vp, i32 = C.c_void_p, C.c_int32
-        self.L.dvm_fuse_targets_create.argtypes = [i32, C.POINTER(vp)]
-        self.L.dvm_fuse_targets_destroy.argtypes = [vp]; self.L.dvm_fuse_targets_destroy.restype = None
-        self.L.dvm_fuse_targets_reserve.argtypes = [vp, i32, i32, i32]
-        self.L.dvm_fuse_targets_set.argtypes = [vp, i32, vp]
-        self.L.dvm_fuse_targets_run.argtypes = [vp, vp, vp, C.c_float, vp, vp]
-        self.L.dvm_fuse_targets_profiling.argtypes = [vp, i32]
-        self.L.dvm_fuse_targets_last_kernel_ms.argtypes = [vp, vp]
-        self.h = vp()
         self.n_targets = 0
-        check(self.L.dvm_fuse_targets_create(device, C.byref(self.h)))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.dvm_fuse_targets_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
+        super().__init__("dvm_fuse_targets", 2, device)
+        vp = C.c_void_p
+        self.L.dvm_fuse_targets_set.argtypes = [vp, C.c_int32, vp]
+        self.L.dvm_fuse_targets_run.argtypes = [vp, vp, vp, C.c_float, vp, vp]
 
     def reserve(self, max_points, max_targets, max_total_target_keypoints):
-        check(self.L.dvm_fuse_targets_reserve(self.h, int(max_points), int(max_targets), int(max_total_target_keypoints)))
-
-    def profiling(self, enable=True):
-        check(self.L.dvm_fuse_targets_profiling(self.h, int(enable)))
+        self._reserve(max_points, max_targets, max_total_target_keypoints)
 
     def last_kernel_ms(self):
         """(grid build of the last set, search of the last run) in milliseconds, with profiling on."""
-        ms = np.zeros(2, np.float32)
-        check(self.L.dvm_fuse_targets_last_kernel_ms(self.h, _p(ms)))
-        return ms
+        return self._last_kernel_ms()
 
     @staticmethod
     def targets(kfs):

@@ -25,6 +25,7 @@
 #include "ba_kernels.h"
 #include "f64_spec.h"
 #include "ba_ordering.h"
+#include "chain.h"
 #include "host_stage.h"
 #include "orb_pipeline.h"  // set_error / hip_check / DVM_HIP
 
@@ -190,10 +191,7 @@ extern "C" {
 int dvm_ba_create(int device, dvm_ba** out) {
   if (!out) return DVM_ERR_INVALID;
   *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
-  if (device < 0 || device >= n) { set_error("device index out of range"); return DVM_ERR_INVALID; }
-  DVM_HIP(hipSetDevice(device));
+  { const int rc = need_device(device); if (rc != DVM_OK) return rc; }
   dvm_ba* h = new dvm_ba;
   h->device = device;
   int rc = hip_check(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking), "stream");
@@ -1150,7 +1148,7 @@ int dvm_pose_optimize(int device, const double* pose_in, const double* Xw, const
     return DVM_ERR_INVALID;
   }
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(&ndev); if (rc != DVM_OK) return rc; }
   if (device < 0 || device >= ndev) return DVM_ERR_INVALID;
   for (int f = 0; f < batch; f++) if (n[f] < 0 || n[f] > stride) { set_error("n[f] out of range"); return DVM_ERR_INVALID; }
   DVM_HIP(hipSetDevice(device));
@@ -1188,7 +1186,7 @@ int dvm_optimize_sim3(int device, double* S12, int fix_scale, const double* P1c,
     return DVM_ERR_INVALID;
   }
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(&ndev); if (rc != DVM_OK) return rc; }
   if (device < 0 || device >= ndev) return DVM_ERR_INVALID;
   DVM_HIP(hipSetDevice(device));
   const size_t n = (size_t)N;
@@ -1218,7 +1216,7 @@ int dvm_sim3_hypotheses(int device, const float* P1c, const float* P2c, const fl
   }
   for (int i = 0; i < 3 * H; i++) if (triples[i] < 0 || triples[i] >= N) { set_error("dvm_sim3_hypotheses: sample index out of range"); return DVM_ERR_INVALID; }
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(&ndev); if (rc != DVM_OK) return rc; }
   if (device < 0 || device >= ndev) return DVM_ERR_INVALID;
   DVM_HIP(hipSetDevice(device));
   const size_t n = (size_t)N, hh = (size_t)H;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/dvmslam_hip.h"
+#include "chain.h"
 #include "match_kernels.h"
 #include "orb_pipeline.h"
 
@@ -46,19 +47,6 @@ struct dvm_frame {
 
 namespace dvm { FrameView frame_view_of(const ::dvm_frame* f) { return f->view; } }
 namespace dvm { uint64_t orb_result_serial(const dvm_orb* h) { return h->serial; } }
-
-static int need_device(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-    set_error("no HIP device visible (libdvmslam_hip has no CPU path)");
-    return DVM_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= n) {
-    set_error("device index out of range");
-    return DVM_ERR_INVALID;
-  }
-  return hip_check(hipSetDevice(device), "hipSetDevice");
-}
 
 #include "group_commit.h"
 #include "host_stage.h"
@@ -316,8 +304,7 @@ int dvm_hamming_matrix(const uint8_t* A, int nA, const uint8_t* B, int nB, uint1
   if (!D) return DVM_ERR_INVALID;
   int rc = need_device(0);
   if (on_device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return DVM_ERR_NO_DEVICE;
+    if (rc == DVM_ERR_NO_DEVICE) return rc;
     launch_hamming_matrix((hipStream_t)stream, A, nA, B, nB, D);
     return hip_check(hipGetLastError(), "hamming launch");
   }
@@ -526,8 +513,7 @@ int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const floa
   if (!frame || n < 0) return DVM_ERR_INVALID;
   if (n == 0) return DVM_OK;
   if (!P || !normal || !min_dist || !max_dist || !out) return DVM_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(); if (rc != DVM_OK) return rc; }
   FrustumFrame F;
   std::memcpy(&F, frame, sizeof(F));
   if (on_device) {
@@ -558,8 +544,7 @@ int dvm_triangulate_matches(const dvm_tri_pair* pair, const dvm_keypoint* kps1, 
     set_error("dvm_triangulate_matches: zero focal length");
     return DVM_ERR_INVALID;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(); if (rc != DVM_OK) return rc; }
   TriPair P;
   std::memcpy(&P, pair, sizeof(P));
   if (on_device) {
@@ -591,8 +576,7 @@ int dvm_undistort_keypoints(const dvm_distortion* cam, const dvm_keypoint* kps_i
   if (n == 0) return DVM_OK;
   if (!kps_in || !kps_out) return DVM_ERR_INVALID;
   if (!(cam->fx != 0.0f) || !(cam->fy != 0.0f)) { set_error("dvm_undistort_keypoints: zero focal length"); return DVM_ERR_INVALID; }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(); if (rc != DVM_OK) return rc; }
   dvm_undistort::Camera C;
   std::memcpy(&C, cam, sizeof(C));
   if (on_device) {
@@ -629,8 +613,7 @@ int dvm_match_lists(const uint8_t* tdesc, int nt, const uint8_t* qdesc, int nq, 
   if (nq < 0 || nt < 0) return DVM_ERR_INVALID;
   if (nq == 0) return DVM_OK;
   if (!tdesc || !qdesc || !off || !cand || !out) return DVM_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(); if (rc != DVM_OK) return rc; }
   if (on_device) {
     launch_match_lists((hipStream_t)stream, tdesc, qdesc, off, cand, nq, reinterpret_cast<dvm_match_pod*>(out));
     return hip_check(hipGetLastError(), "match_lists launch");
@@ -690,8 +673,7 @@ int dvm_match_triangulation(const uint8_t* desc1, const dvm_keypoint* kps1, int 
   if (!desc1 || !kps1 || !qidx || !desc2 || !kps2 || !off || !cand || !F12 || !ep || !scale_factors2 || !level_sigma2_2 || !best_idx ||
       !best_dist)
     return DVM_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(); if (rc != DVM_OK) return rc; }
   TriGeom G;
   std::memcpy(G.F12, F12, 36);
   G.ep[0] = ep[0]; G.ep[1] = ep[1];
@@ -872,8 +854,7 @@ int dvm_distinctive_descriptors(const uint8_t* desc, const int32_t* off, int n_p
   if (n_points < 0) return DVM_ERR_INVALID;
   if (n_points == 0) return DVM_OK;
   if (!desc || !off || !best_idx || !best_median) return DVM_ERR_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(); if (rc != DVM_OK) return rc; }
   if (on_device) {
     launch_distinctive((hipStream_t)stream, desc, off, n_points, best_idx, best_median);
     return hip_check(hipGetLastError(), "distinctive launch");
@@ -911,7 +892,7 @@ int dvm_vocab_create(int device, int n_nodes, const int32_t* child_off, const in
   *out = nullptr;
   if (n_nodes < 1 || !child_off || !children || !desc || !weight || !word_id || L < 0) return DVM_ERR_INVALID;
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(&ndev); if (rc != DVM_OK) return rc; }
   if (device < 0 || device >= ndev) return DVM_ERR_INVALID;
   const int nch = child_off[n_nodes];
   if (child_off[0] != 0 || nch < 0) { set_error("vocabulary: bad child_off"); return DVM_ERR_INVALID; }

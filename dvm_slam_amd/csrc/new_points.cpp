@@ -1,6 +1,6 @@
 // dvm_slam_amd/csrc/new_points.cpp -- dvm_new_points: LocalMapping::CreateNewMapPoints for all neighbours of a keyframe as one chain
-// (include/dvmslam_hip.h; kernels in new_points_kernels.hip).  The handle owns a stream and one reserved working set: a device block
-// [packed upload][speculative results] and a mapped page-locked block [upload staging][results].  A call validates everything, packs both
+// (include/dvmslam_hip.h; kernels in new_points_kernels.hip; the handle's stream, working set, packing cursor and kernel times: chain.h).
+// The working set: a device block [packed upload][speculative results] and a mapped block [upload staging][results].  A call validates everything, packs both
 // keyframe sets back to back into the staging region, sends it with ONE copy, queues the three launches, synchronises ONCE and copies the
 // records out of the mapped block.  Host arithmetic here is index-free: the baseline test of each neighbour and the 3x4 pose matrices.
 #include <cmath>
@@ -10,36 +10,25 @@
 #include <vector>
 
 #include "../../include/dvmslam_hip.h"
+#include "chain.h"
 #include "new_points_kernels.h"
 #include "orb_pipeline.h"
 #include "pose_f32.h"
 
 using namespace dvm;
 
-struct dvm_new_points {
-  int device = 0;
-  hipStream_t s = nullptr;
-  uint8_t *d = nullptr, *hm = nullptr, *hm_dev = nullptr;
-  size_t up_bytes = 0, spec_bytes = 0;          // device block: [up_bytes][spec]; mapped block: [up_bytes][results]
+struct dvm_new_points : Chain {                 // ws: device block [up_bytes][spec]; mapped block [up_bytes][results]
   int max_n1 = 0, max_nb = 0, max_total = 0;
   size_t rec_cap = 0;                           // records the mapped block holds: max_nb * max_n1
-  int profiling = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   float last_ms[3] = {0, 0, 0};
-  void release() {
-    if (d) hipFree(d);
-    if (hm) hipHostFree(hm);
-    d = hm = hm_dev = nullptr; up_bytes = spec_bytes = 0; max_n1 = max_nb = max_total = 0; rec_cap = 0;
-  }
 };
 
 namespace {
-constexpr size_t kAlign = 64;
-size_t al(size_t b) { return (b + kAlign - 1) & ~(kAlign - 1); }
+using Cursor64 = Cursor<64>;                    // every item of the upload and of the results starts at a multiple of 64 bytes
 // bytes a keyframe of n keypoints takes in the packed upload at most: per keypoint its cv::KeyPoint, descriptor, map point, and -- fv_n <= n
 // nodes, at most n features -- a node id, an offset and a feature; per keyframe the last offset, two level tables of 64 and the rounding of
 // its eight arrays.  Linear in n, so the neighbours' sum is bounded by their total.
-constexpr size_t kKfPerKeypoint = sizeof(dvm_keypoint_pod) + 32 + 4 * 4, kKfFixed = 4 + 2 * 64 * 4 + 8 * kAlign;
+constexpr size_t kKfPerKeypoint = sizeof(dvm_keypoint_pod) + 32 + 4 * 4, kKfFixed = 4 + 2 * 64 * 4 + 8 * 64;
 
 int fail(int rc, const std::string& msg) { set_error("dvm_create_new_map_points: " + msg); return rc; }
 
@@ -66,24 +55,18 @@ int check_keyframe(const dvm_np_keyframe& k, const char* who, int n_levels) {
   return DVM_OK;
 }
 
-// packs one keyframe at *off of the staging block and returns its device view
-NpKfDev pack_keyframe(const dvm_np_keyframe& k, uint8_t* stage, const uint8_t* dev, size_t* off) {
+// packs one keyframe at the cursor (staging block -> device block) and returns its device view
+NpKfDev pack_keyframe(const dvm_np_keyframe& k, Cursor64& c) {
   NpKfDev v{};
-  auto put = [&](const void* src, size_t bytes) {
-    const size_t o = *off;
-    if (bytes) std::memcpy(stage + o, src, bytes);
-    *off = o + al(bytes);
-    return dev + o;
-  };
   const size_t n = (size_t)k.n, nf = k.fv_n > 0 ? (size_t)k.fv_off[k.fv_n] : 0;
-  v.kps = reinterpret_cast<const dvm_keypoint_pod*>(put(k.kps, n * sizeof(dvm_keypoint_pod)));
-  v.desc = put(k.desc, n * 32);
-  v.mp = reinterpret_cast<const int32_t*>(put(k.mp, n * 4));
-  v.fv_node = reinterpret_cast<const int32_t*>(put(k.fv_node, (size_t)k.fv_n * 4));
-  v.fv_off = reinterpret_cast<const int32_t*>(put(k.fv_off, k.fv_n > 0 ? ((size_t)k.fv_n + 1) * 4 : 0));
-  v.fv_feat = reinterpret_cast<const int32_t*>(put(k.fv_feat, nf * 4));
-  v.sf = reinterpret_cast<const float*>(put(k.scale_factors, (size_t)k.n_levels * 4));
-  v.sigma2 = reinterpret_cast<const float*>(put(k.level_sigma2, (size_t)k.n_levels * 4));
+  v.kps = reinterpret_cast<const dvm_keypoint_pod*>(c.put(k.kps, n * sizeof(dvm_keypoint_pod)));
+  v.desc = c.put(k.desc, n * 32);
+  v.mp = reinterpret_cast<const int32_t*>(c.put(k.mp, n * 4));
+  v.fv_node = reinterpret_cast<const int32_t*>(c.put(k.fv_node, (size_t)k.fv_n * 4));
+  v.fv_off = reinterpret_cast<const int32_t*>(c.put(k.fv_off, k.fv_n > 0 ? ((size_t)k.fv_n + 1) * 4 : 0));
+  v.fv_feat = reinterpret_cast<const int32_t*>(c.put(k.fv_feat, nf * 4));
+  v.sf = reinterpret_cast<const float*>(c.put(k.scale_factors, (size_t)k.n_levels * 4));
+  v.sigma2 = reinterpret_cast<const float*>(c.put(k.level_sigma2, (size_t)k.n_levels * 4));
   v.n = k.n; v.fv_n = k.fv_n;
   return v;
 }
@@ -101,30 +84,8 @@ void pose_3x4(const dvm_se3f& T, float* out) {
 
 extern "C" {
 
-int dvm_new_points_create(int device, dvm_new_points** out) {
-  if (!out) return DVM_ERR_INVALID;
-  *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
-  if (device < 0 || device >= n) { set_error("device index out of range"); return DVM_ERR_INVALID; }
-  DVM_HIP(hipSetDevice(device));
-  dvm_new_points* h = new (std::nothrow) dvm_new_points;
-  if (!h) return DVM_ERR_INVALID;
-  h->device = device;
-  int rc = hip_check(hipStreamCreateWithFlags(&h->s, hipStreamNonBlocking), "hipStreamCreate");
-  if (rc != DVM_OK) { delete h; return rc; }
-  *out = h;
-  return DVM_OK;
-}
-
-void dvm_new_points_destroy(dvm_new_points* h) {
-  if (!h) return;
-  hipSetDevice(h->device);
-  if (h->s) { hipStreamSynchronize(h->s); hipStreamDestroy(h->s); }
-  for (hipEvent_t e : h->ev) if (e) hipEventDestroy(e);
-  h->release();
-  delete h;
-}
+int dvm_new_points_create(int device, dvm_new_points** out) { return chain_create(device, out); }
+void dvm_new_points_destroy(dvm_new_points* h) { chain_destroy(h); }
 
 int dvm_new_points_reserve(dvm_new_points* h, int max_kf1_keypoints, int max_neighbours, int max_total_neighbour_keypoints) {
   if (!h || max_kf1_keypoints < 0 || max_kf1_keypoints > kFrameCap || max_neighbours < 0 || max_total_neighbour_keypoints < 0 ||
@@ -136,30 +97,24 @@ int dvm_new_points_reserve(dvm_new_points* h, int max_kf1_keypoints, int max_nei
   DVM_HIP(hipSetDevice(h->device));
   DVM_HIP(hipStreamSynchronize(h->s));
   const int n1 = std::max(max_kf1_keypoints, h->max_n1), nb = std::max(max_neighbours, h->max_nb), tot = std::max(max_total_neighbour_keypoints, h->max_total);
-  h->release();
+  h->max_n1 = h->max_nb = h->max_total = 0; h->rec_cap = 0;       // (a failed allocation leaves the handle holding nothing)
   const size_t n1p = ((size_t)n1 + 63) & ~(size_t)63;
-  const size_t up = al(((size_t)n1 + (size_t)tot) * kKfPerKeypoint + ((size_t)nb + 1) * kKfFixed + al((size_t)nb * sizeof(NpNbDev)));
-  const size_t spec = (size_t)nb * n1p * 20 + kAlign;
+  const size_t up = pad<64>(((size_t)n1 + (size_t)tot) * kKfPerKeypoint + ((size_t)nb + 1) * kKfFixed + pad<64>((size_t)nb * sizeof(NpNbDev)));
+  const size_t spec = (size_t)nb * n1p * 20 + 64;
   const size_t rec = (size_t)nb * (size_t)n1;
-  const size_t res = al(((size_t)nb + 1) * 4) * 2 + al(rec * 8) + al(rec * 4) + al(rec * 12) + al((size_t)n1 * 4) + kAlign;
-  if (hipMalloc(reinterpret_cast<void**>(&h->d), up + spec) != hipSuccess) { h->d = nullptr; set_error("dvm_new_points_reserve: hipMalloc failed"); return DVM_ERR_HIP; }
-  if (hipHostMalloc(reinterpret_cast<void**>(&h->hm), up + res, hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hm_dev), h->hm, 0) != hipSuccess) {
-    h->release();
-    set_error("dvm_new_points_reserve: mapped host memory failed");
+  const size_t res = pad<64>(((size_t)nb + 1) * 4) * 2 + pad<64>(rec * 8) + pad<64>(rec * 4) + pad<64>(rec * 12) + pad<64>((size_t)n1 * 4) + 64;
+  if (const char* what = h->ws.alloc(up + spec, up + res, up, /*mapped*/ true, /*zeroed*/ false)) {
+    set_error(std::string("dvm_new_points_reserve: ") + what + " failed");
     return DVM_ERR_HIP;
   }
-  h->up_bytes = up; h->spec_bytes = spec; h->max_n1 = n1; h->max_nb = nb; h->max_total = tot; h->rec_cap = rec;
+  h->max_n1 = n1; h->max_nb = nb; h->max_total = tot; h->rec_cap = rec;
   return DVM_OK;
 }
 
 int dvm_new_points_profiling(dvm_new_points* h, int enable) {
   if (!h) return DVM_ERR_INVALID;
   DVM_HIP(hipSetDevice(h->device));
-  if (enable)
-    for (hipEvent_t& e : h->ev) if (!e) DVM_HIP(hipEventCreate(&e));
-  h->profiling = enable != 0;
-  return DVM_OK;
+  return h->timer.enable(enable != 0);
 }
 int dvm_new_points_last_kernel_ms(dvm_new_points* h, float* ms) {
   if (!h || !ms) return DVM_ERR_INVALID;
@@ -214,17 +169,18 @@ int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int
 
   DVM_HIP(hipSetDevice(h->device));
   // pack: [NpNbDev x nrun][current keyframe][neighbours that run]
-  size_t off = al((size_t)nrun * sizeof(NpNbDev));
-  NpNbDev* nb_stage = reinterpret_cast<NpNbDev*>(h->hm);
+  WorkingSet& ws = h->ws;
+  Cursor64 up{ws.hm, ws.d};
+  NpNbDev* nb_stage = up.carve<NpNbDev>((size_t)nrun);
   NpArgs A{};
-  A.cur = pack_keyframe(*cur, h->hm, h->d, &off);
+  A.cur = pack_keyframe(*cur, up);
   float T1w[12];
   pose_3x4(cur->Tcw, T1w);
   for (int r = 0; r < nrun; r++) {
     const dvm_np_neighbour& nb = nbs[run[r]];
     NpNbDev& D = nb_stage[r];
     std::memset(&D, 0, sizeof(D));
-    D.kf = pack_keyframe(nb.kf, h->hm, h->d, &off);
+    D.kf = pack_keyframe(nb.kf, up);
     TriPair& P = D.P;
     P.cos_parallax_max = p->cos_parallax_max;
     P.K1[0] = cur->fx; P.K1[1] = cur->fy; P.K1[2] = cur->cx; P.K1[3] = cur->cy;
@@ -236,43 +192,41 @@ int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int
     std::memcpy(D.G.F12, nb.F12, 36); D.G.ep[0] = nb.ep[0]; D.G.ep[1] = nb.ep[1];
     D.G.coarse = p->coarse != 0; D.G.th_low = 50;   // ORBmatcher::TH_LOW
   }
-  if (off > h->up_bytes) return fail(DVM_ERR_CAPACITY, "packed keyframes exceed the reserved upload region");   // (cannot happen: kKfPerKeypoint / kKfFixed bound every keyframe)
-  A.nb = reinterpret_cast<const NpNbDev*>(h->d);
+  if (up.used() > ws.up_bytes) return fail(DVM_ERR_CAPACITY, "packed keyframes exceed the reserved upload region");   // (cannot happen: kKfPerKeypoint / kKfFixed bound every keyframe)
+  A.nb = reinterpret_cast<const NpNbDev*>(ws.d);
   A.nrun = nrun; A.n1 = n1; A.n1p = (int32_t)n1p; A.nfeat1 = cur->fv_n > 0 ? cur->fv_off[cur->fv_n] : 0;
   A.n_levels = cur->n_levels; A.check_ori = p->check_ori != 0;
-  uint8_t* spec = h->d + h->up_bytes;
+  uint8_t* spec = ws.d + ws.up_bytes;
   A.best = reinterpret_cast<int32_t*>(spec);
   A.st = A.best + (size_t)nrun * n1p;
   A.X = reinterpret_cast<float*>(A.st + (size_t)nrun * n1p);
   // results in the mapped block (sized for the reservation)
-  size_t ro = h->up_bytes;
-  auto carve = [&](size_t bytes) { uint8_t* q = h->hm + ro; ro += al(bytes); return q; };
-  int32_t* r_matches = reinterpret_cast<int32_t*>(carve(((size_t)h->max_nb + 1) * 4));
-  int32_t* r_off = reinterpret_cast<int32_t*>(carve(((size_t)h->max_nb + 1) * 4));
-  int32_t* r_pairs = reinterpret_cast<int32_t*>(carve(h->rec_cap * 8));
-  int32_t* r_status = reinterpret_cast<int32_t*>(carve(h->rec_cap * 4));
-  float* r_x3D = reinterpret_cast<float*>(carve(h->rec_cap * 12));
-  int32_t* r_new = reinterpret_cast<int32_t*>(carve((size_t)h->max_n1 * 4));
-  auto dev = [&](auto* q) { return reinterpret_cast<decltype(q)>(h->hm_dev + (reinterpret_cast<uint8_t*>(q) - h->hm)); };
-  A.h_matches = dev(r_matches); A.h_pair_off = dev(r_off); A.h_pairs = dev(r_pairs); A.h_status = dev(r_status); A.h_x3D = dev(r_x3D);
-  A.h_new_point = dev(r_new);
+  Cursor64 res{ws.hm + ws.up_bytes};
+  int32_t* r_matches = res.carve<int32_t>((size_t)h->max_nb + 1);
+  int32_t* r_off = res.carve<int32_t>((size_t)h->max_nb + 1);
+  int32_t* r_pairs = res.carve<int32_t>(h->rec_cap * 2);
+  int32_t* r_status = res.carve<int32_t>(h->rec_cap);
+  float* r_x3D = res.carve<float>(h->rec_cap * 3);
+  int32_t* r_new = res.carve<int32_t>((size_t)h->max_n1);
+  A.h_matches = ws.dev(r_matches); A.h_pair_off = ws.dev(r_off); A.h_pairs = ws.dev(r_pairs); A.h_status = ws.dev(r_status); A.h_x3D = ws.dev(r_x3D);
+  A.h_new_point = ws.dev(r_new);
 
-  DVM_HIP(hipMemcpyAsync(h->d, h->hm, off, hipMemcpyHostToDevice, h->s));
+  DVM_HIP(hipMemcpyAsync(ws.d, ws.hm, up.used(), hipMemcpyHostToDevice, h->s));
   DVM_HIP(hipMemsetAsync(A.best, 0xFF, (size_t)nrun * n1p * 4, h->s));
-  const bool prof = h->profiling != 0;
-  if (prof) DVM_HIP(hipEventRecord(h->ev[0], h->s));
+  const EventTimer& tm = h->timer;
+  DVM_HIP(tm.mark(0, h->s));
   launch_np_search(h->s, A);
-  if (prof) DVM_HIP(hipEventRecord(h->ev[1], h->s));
+  DVM_HIP(tm.mark(1, h->s));
   launch_np_geometry(h->s, A);
-  if (prof) DVM_HIP(hipEventRecord(h->ev[2], h->s));
+  DVM_HIP(tm.mark(2, h->s));
   launch_np_settle(h->s, A);
-  if (prof) DVM_HIP(hipEventRecord(h->ev[3], h->s));
+  DVM_HIP(tm.mark(3, h->s));
   rc = hip_check(hipGetLastError(), "dvm_create_new_map_points launch");
   const int rs = hip_check(hipStreamSynchronize(h->s), "dvm_create_new_map_points sync");
   if (rc != DVM_OK) return rc;
   if (rs != DVM_OK) return rs;
-  if (prof)
-    for (int i = 0; i < 3; i++) DVM_HIP(hipEventElapsedTime(&h->last_ms[i], h->ev[i], h->ev[i + 1]));
+  if (tm.on)
+    for (int i = 0; i < 3; i++) DVM_HIP(tm.elapsed(i, i + 1, &h->last_ms[i]));
 
   const size_t nrec = (size_t)r_off[nrun];
   if (nrec > (size_t)out->record_cap || nrec > h->rec_cap) return fail(DVM_ERR_STATE, "more records than the bound allows");   // (an internal error)

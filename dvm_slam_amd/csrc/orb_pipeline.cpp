@@ -7,6 +7,7 @@
 //   operator()              :876-955                -> extract_device (stage order, output placement)
 // Everything runs in HIP kernels (orb_kernels.hip, octree_kernel.hip); the host only sequences launches.
 #include "orb_pipeline.h"
+#include "chain.h"       // need_device
 #include "host_stage.h"   // HostPool
 
 #include <algorithm>
@@ -273,16 +274,7 @@ OrbPipeline::~OrbPipeline() {
 }
 
 int OrbPipeline::init() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device visible (libdvmslam_hip has no CPU path)");
-    return DVM_ERR_NO_DEVICE;
-  }
-  if (device < 0 || device >= ndev) {
-    set_error("device index out of range");
-    return DVM_ERR_INVALID;
-  }
-  DVM_HIP(hipSetDevice(device));
+  { const int rc = need_device(device); if (rc != DVM_OK) return rc; }
   DVM_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
   lane_main[0] = stream;
   if (const char* e = getenv("DVM_BLUR_EARLY")) blur_early = (e[0] == '1');

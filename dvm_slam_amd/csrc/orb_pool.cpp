@@ -13,6 +13,7 @@
 
 #include "../../include/dvmslam_hip.h"
 #include "ba_kernels.h"
+#include "chain.h"
 #include "group_commit.h"
 #include "orb_pipeline.h"
 
@@ -189,7 +190,7 @@ extern "C" int dvm_pose_pool_create(int device, int max_batch, int window_us, dv
   if (!out || max_batch < 1 || max_batch > 256) { set_error("dvm_pose_pool_create: bad parameters"); return DVM_ERR_INVALID; }
   *out = nullptr;
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(&ndev); if (rc != DVM_OK) return rc; }
   if (device < 0 || device >= ndev) return DVM_ERR_INVALID;
   DVM_HIP(hipSetDevice(device));
   dvm_pose_pool* pool = new (std::nothrow) dvm_pose_pool();

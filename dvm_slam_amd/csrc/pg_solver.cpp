@@ -16,6 +16,7 @@
 #include "../../include/dvmslam_hip.h"
 #include "ba_kernels.h"
 #include "ba_ordering.h"
+#include "chain.h"
 #include "orb_pipeline.h"  // set_error / hip_check / DVM_HIP
 
 using namespace dvm;
@@ -45,7 +46,7 @@ extern "C" int dvm_pose_graph_optimize(int device, double* S, const uint8_t* fix
                                        int fix_scale, int iterations, dvm_pg_stats* st) {
   if (!S || !fixed || !edges || n < 1 || E < 1 || iterations < 0) { set_error("dvm_pose_graph_optimize: bad arguments"); return DVM_ERR_INVALID; }
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = need_any_device(&ndev); if (rc != DVM_OK) return rc; }
   if (device < 0 || device >= ndev) return DVM_ERR_INVALID;
   DVM_HIP(hipSetDevice(device));
   if (st) std::memset(st, 0, sizeof(*st));

@@ -15,6 +15,7 @@
 // candidates were all taken by earlier queries (the list may go on: the caller replays the epilogue from the ranked lists on the host).
 // The second half (dvm_track_local_map, dvm_track_reference_keyframe) runs as the batch of one frame: the single calls keep their own
 // checks and run the chains of dvm_track_local_map_batch / dvm_track_reference_keyframe_batch.
+// Every reservation here is a WorkingSet carved by a Cursor<256> (chain.h, shared with the other chains): items start at multiples of 256 bytes.
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -28,6 +29,7 @@
 
 #include "../../include/dvmslam_hip.h"
 #include "ba_kernels.h"
+#include "chain.h"
 #include "match_kernels.h"
 #include "orb_pipeline.h"
 #include "host_stage.h"   // HostPool
@@ -52,32 +54,6 @@ struct LocalFrame {
   const uint8_t* d_desc = nullptr; int64_t desc_stride = 0;   // the frames' descriptors on the device: frame b's at b * desc_stride
 };
 
-// the memory of one reservation: a device block and a mapped page-locked block, each beginning with the upload region (built in the
-// mapped block, copied to the same offsets of the device block by one asynchronous copy)
-struct WorkingSet {
-  uint8_t* d = nullptr;                           // device
-  uint8_t *hm = nullptr, *hm_dev = nullptr;       // mapped: host address, device address
-  size_t up_bytes = 0;                            // the upload region's capacity
-  // replaces what it holds by dbytes of device memory and mbytes of zeroed mapped memory; on failure it holds nothing and names what failed
-  const char* alloc(size_t dbytes, size_t mbytes) {
-    free();
-    if (hipMalloc(reinterpret_cast<void**>(&d), dbytes) != hipSuccess) { d = nullptr; return "hipMalloc"; }
-    if (hipHostMalloc(reinterpret_cast<void**>(&hm), mbytes, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void**>(&hm_dev), hm, 0) != hipSuccess) {
-      free();
-      return "mapped host memory";
-    }
-    std::memset(hm, 0, mbytes);
-    return nullptr;
-  }
-  void free() {
-    if (d) hipFree(d);
-    if (hm) hipHostFree(hm);
-    d = hm = hm_dev = nullptr; up_bytes = 0;
-  }
-  template <class T> T* dev(T* host_ptr) const { return reinterpret_cast<T*>(hm_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm)); }
-};
-
 // a TrackReferenceKeyFrame working set: per-frame arrays for the tracker's max_frames frames at its keypoint capacity, keyframes of up to
 // `cap` entries per call (each keyframe's rounded up to 64)
 struct RefKfMapped {
@@ -93,25 +69,23 @@ struct dvm_tracker {
   int device = 0, kp_cap = 0, q_cap = 0, max_frames = 1;
   int q_rcap = 0;                  // q_cap rounded up to 64: the per-frame query capacity of d_q / d_ranked
   dvm_frame* grid = nullptr;       // max_frames slots
-  uint8_t* d_buf = nullptr;        // device working set (one allocation)
-  uint8_t *hm = nullptr, *hm_dev = nullptr;   // mapped page-locked buffer: queries in (staging of the one copy), results out
-  size_t hm_bytes = 0;
+  WorkingSet ws;                   // first half.  device: the arrays below; mapped: queries in (staging of the one copy), results out
   // device, [frame][...]
   uint32_t* d_ranked; int32_t* d_assign; int32_t* d_res; double *d_Xw, *d_obs, *d_info, *d_chi; int32_t *d_edge_kp, *d_nedges;
   uint8_t* d_edge_out; dvm_keypoint_pod* d_kps_un;
-  // mapped (host address; device address = hm_dev + (p - hm)).  The query block is carved per call (stride = the call's largest nq).
+  // mapped (host address; device address: ws.dev(p)).  The query block is carved per call (stride = the call's largest nq).
   struct Mapped {
     uint8_t* qdesc; float *qx, *qy, *qr; int32_t *qmin, *qmax; uint8_t* q_claims; float *q_angle, *q_pos; double* pose_in; int32_t* nq_arr;
     float* inv_sigma2;
     int32_t* assign; uint8_t* outlier; int32_t* res; int32_t* fin; int32_t* nedges; double* pose_out; int32_t* n_inl;
     dvm_keypoint_pod* kps_un;
   } m;
-  template <class T> T* dev(T* host_ptr) const { return reinterpret_cast<T*>(hm_dev + (reinterpret_cast<uint8_t*>(host_ptr) - hm)); }
   // the query block: built in the mapped buffer (page-locked), copied to the device by ONE asynchronous copy on a side stream while the
   // extraction runs; the kernels read the device copy (the one-wave claim replay walks it serially: a PCIe read per step would be its chain)
+  // d_q has no allocation of its own: it is the last item of ws.d (carved at create, freed with ws)
   uint8_t* d_q = nullptr; size_t q_bytes = 0;
   hipStream_t cstream = nullptr; hipEvent_t cev = nullptr;
-  template <class T> T* qdev(T* host_ptr) const { return reinterpret_cast<T*>(d_q + (reinterpret_cast<uint8_t*>(host_ptr) - hm)); }
+  template <class T> T* qdev(T* host_ptr) const { return rebase(host_ptr, ws.hm, d_q); }
   int begun = 0;                   // frames of the batch whose extraction is queued
   int rows = 0, cols = 0;
   // ---- the second half (dvm_track_local_map[_batch]): working set of dvm_tracker_reserve_local_map, and what the last finish left for it
@@ -137,8 +111,7 @@ void vocab_launch_transform(const dvm_vocab* v, hipStream_t s, const uint8_t* d_
 }
 
 namespace {
-size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-template <class T> T* carve(uint8_t*& p, size_t count) { T* r = reinterpret_cast<T*>(p); p += pad256(count * sizeof(T)); return r; }
+using Cursor256 = Cursor<256>;
 // a reservation that could not be allocated: "<fn>: <what failed>"
 int reserve_failed(const char* fn, const char* what) { set_error(std::string(fn) + ": " + what); return DVM_ERR_CAPACITY; }
 }  // namespace
@@ -152,10 +125,7 @@ int dvm_tracker_create_batch(int device, int max_frames, int max_keypoints, int 
     set_error("dvm_tracker_create: capacity beyond what the claim replay keeps in LDS (9 B per keypoint + 21 B per query <= 150 KB)");
     return DVM_ERR_CAPACITY;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
-  if (device < 0 || device >= ndev) { set_error("device index out of range"); return DVM_ERR_INVALID; }
-  DVM_HIP(hipSetDevice(device));
+  { const int rc = need_device(device); if (rc != DVM_OK) return rc; }
   dvm_tracker* t = new (std::nothrow) dvm_tracker();
   if (!t) return DVM_ERR_INVALID;
   t->device = device; t->kp_cap = max_keypoints; t->q_cap = max_queries; t->max_frames = max_frames; t->q_rcap = (max_queries + 63) & ~63;
@@ -164,31 +134,28 @@ int dvm_tracker_create_batch(int device, int max_frames, int max_keypoints, int 
   // (Q rounded up to 64: dvm_track_finish_batch strides the per-query arrays by the call's largest nq rounded up to 64)
   const size_t K = (size_t)max_keypoints, Q = ((size_t)max_queries + 63) & ~(size_t)63, B = (size_t)max_frames;
   // device working set
-  size_t dbytes = pad256(B * Q * 16) + pad256(B * K * 4) + pad256(B * 32) + pad256(B * K * 24) + pad256(B * K * 16) + 2 * pad256(B * K * 8) + pad256(B * K * 4) +
-                  pad256(B * 4) + pad256(B * K) + pad256(B * K * sizeof(dvm_keypoint_pod));
-  if (hipMalloc(reinterpret_cast<void**>(&t->d_buf), dbytes) != hipSuccess) { dvm_tracker_destroy(t); set_error("dvm_tracker_create: hipMalloc"); return DVM_ERR_HIP; }
-  uint8_t* p = t->d_buf;
-  t->d_ranked = carve<uint32_t>(p, B * Q * 4); t->d_assign = carve<int32_t>(p, B * K); t->d_res = carve<int32_t>(p, B * 8);
-  t->d_Xw = carve<double>(p, B * K * 3); t->d_obs = carve<double>(p, B * K * 2); t->d_info = carve<double>(p, B * K); t->d_chi = carve<double>(p, B * K);
-  t->d_edge_kp = carve<int32_t>(p, B * K); t->d_nedges = carve<int32_t>(p, B); t->d_edge_out = carve<uint8_t>(p, B * K);
-  t->d_kps_un = carve<dvm_keypoint_pod>(p, B * K);
+  const size_t dbytes = pad<256>(B * Q * 16) + pad<256>(B * K * 4) + pad<256>(B * 32) + pad<256>(B * K * 24) + pad<256>(B * K * 16) + 2 * pad<256>(B * K * 8) + pad<256>(B * K * 4) +
+                        pad<256>(B * 4) + pad<256>(B * K) + pad<256>(B * K * sizeof(dvm_keypoint_pod));
   // mapped buffer: [query block: carved per call] [results]
-  t->q_bytes = pad256(B * Q * 32) + 3 * pad256(B * Q * 4) + 2 * pad256(B * Q * 4) + pad256(B * Q) + pad256(B * Q * 4) + pad256(B * Q * 12) + pad256(B * 56) +
-               pad256(B * 4) + pad256(64 * 4);
-  const size_t mbytes = t->q_bytes + pad256(B * K * 4) + pad256(B * K) + pad256(B * 32) + pad256(B * 16) + pad256(B * 4) + pad256(B * 56) + pad256(B * 4) +
-                        pad256(K * sizeof(dvm_keypoint_pod));
-  if (hipHostMalloc(reinterpret_cast<void**>(&t->hm), mbytes, hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&t->hm_dev), t->hm, 0) != hipSuccess) {
-    dvm_tracker_destroy(t); set_error("dvm_tracker_create: mapped host memory"); return DVM_ERR_HIP;
+  t->q_bytes = pad<256>(B * Q * 32) + 3 * pad<256>(B * Q * 4) + 2 * pad<256>(B * Q * 4) + pad<256>(B * Q) + pad<256>(B * Q * 4) + pad<256>(B * Q * 12) + pad<256>(B * 56) +
+               pad<256>(B * 4) + pad<256>(64 * 4);
+  const size_t mbytes = t->q_bytes + pad<256>(B * K * 4) + pad<256>(B * K) + pad<256>(B * 32) + pad<256>(B * 16) + pad<256>(B * 4) + pad<256>(B * 56) + pad<256>(B * 4) +
+                        pad<256>(K * sizeof(dvm_keypoint_pod));
+  // (the query block's device copy d_q: the device block's last item)
+  if (const char* what = t->ws.alloc(dbytes + t->q_bytes, mbytes, t->q_bytes, /*mapped*/ true, /*zeroed*/ true)) {
+    dvm_tracker_destroy(t); set_error(std::string("dvm_tracker_create: ") + what); return DVM_ERR_HIP;
   }
-  t->hm_bytes = mbytes;
-  std::memset(t->hm, 0, mbytes);
-  p = t->hm + t->q_bytes;
+  Cursor256 c{t->ws.d};
+  t->d_ranked = c.carve<uint32_t>(B * Q * 4); t->d_assign = c.carve<int32_t>(B * K); t->d_res = c.carve<int32_t>(B * 8);
+  t->d_Xw = c.carve<double>(B * K * 3); t->d_obs = c.carve<double>(B * K * 2); t->d_info = c.carve<double>(B * K); t->d_chi = c.carve<double>(B * K);
+  t->d_edge_kp = c.carve<int32_t>(B * K); t->d_nedges = c.carve<int32_t>(B); t->d_edge_out = c.carve<uint8_t>(B * K);
+  t->d_kps_un = c.carve<dvm_keypoint_pod>(B * K); t->d_q = c.carve<uint8_t>(t->q_bytes);
+  c = Cursor256{t->ws.hm + t->q_bytes};
   auto& m = t->m;
-  m.assign = carve<int32_t>(p, B * K); m.outlier = carve<uint8_t>(p, B * K);
-  m.res = carve<int32_t>(p, B * 8); m.fin = carve<int32_t>(p, B * 4); m.nedges = carve<int32_t>(p, B); m.pose_out = carve<double>(p, B * 7);
-  m.n_inl = carve<int32_t>(p, B); m.kps_un = carve<dvm_keypoint_pod>(p, K);
-  if (hipMalloc(reinterpret_cast<void**>(&t->d_q), t->q_bytes) != hipSuccess || hipStreamCreateWithFlags(&t->cstream, hipStreamNonBlocking) != hipSuccess ||
+  m.assign = c.carve<int32_t>(B * K); m.outlier = c.carve<uint8_t>(B * K);
+  m.res = c.carve<int32_t>(B * 8); m.fin = c.carve<int32_t>(B * 4); m.nedges = c.carve<int32_t>(B); m.pose_out = c.carve<double>(B * 7);
+  m.n_inl = c.carve<int32_t>(B); m.kps_un = c.carve<dvm_keypoint_pod>(K);
+  if (hipStreamCreateWithFlags(&t->cstream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&t->cev, hipEventDisableTiming) != hipSuccess) {
     dvm_tracker_destroy(t); set_error("dvm_tracker_create: query block"); return DVM_ERR_HIP;
   }
@@ -203,12 +170,10 @@ void dvm_tracker_destroy(dvm_tracker* t) {
   if (!t) return;
   hipSetDevice(t->device);
   if (t->grid) dvm_frame_destroy(t->grid);
-  if (t->d_buf) hipFree(t->d_buf);
-  if (t->d_q) hipFree(t->d_q);
   t->lmw.free(); t->rk.ws.free(); t->rkb.ws.free();
   if (t->cev) hipEventDestroy(t->cev);
   if (t->cstream) hipStreamDestroy(t->cstream);
-  if (t->hm) hipHostFree(t->hm);
+  t->ws.free();
   delete t;
 }
 
@@ -272,14 +237,16 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
   }
   const int Qs = (std::max(nq_max, 1) + 63) & ~63;      // the per-query arrays' stride for this call
   auto& m = t->m;
+  size_t q_used = 0;
   {   // the query block of THIS call, packed: one copy (~75 KB per frame of 1 000 queries)
-    uint8_t* p = t->hm;
+    Cursor256 c{t->ws.hm};
     const size_t Qn = (size_t)count * Qs;
-    m.qdesc = carve<uint8_t>(p, Qn * 32); m.qx = carve<float>(p, Qn); m.qy = carve<float>(p, Qn); m.qr = carve<float>(p, Qn);
-    m.qmin = carve<int32_t>(p, Qn); m.qmax = carve<int32_t>(p, Qn); m.q_claims = carve<uint8_t>(p, Qn); m.q_angle = carve<float>(p, Qn);
-    m.q_pos = carve<float>(p, Qn * 3); m.pose_in = carve<double>(p, (size_t)count * 7); m.nq_arr = carve<int32_t>(p, count); m.inv_sigma2 = carve<float>(p, 64);
+    m.qdesc = c.carve<uint8_t>(Qn * 32); m.qx = c.carve<float>(Qn); m.qy = c.carve<float>(Qn); m.qr = c.carve<float>(Qn);
+    m.qmin = c.carve<int32_t>(Qn); m.qmax = c.carve<int32_t>(Qn); m.q_claims = c.carve<uint8_t>(Qn); m.q_angle = c.carve<float>(Qn);
+    m.q_pos = c.carve<float>(Qn * 3); m.pose_in = c.carve<double>((size_t)count * 7); m.nq_arr = c.carve<int32_t>(count); m.inv_sigma2 = c.carve<float>(64);
     // (the block's end and the ranked lists' inside what create sized: refused before anything is written)
-    if ((size_t)(p - t->hm) > t->q_bytes || Qn > (size_t)t->max_frames * t->q_rcap) {
+    q_used = c.used();
+    if (q_used > t->q_bytes || Qn > (size_t)t->max_frames * t->q_rcap) {
       set_error("dvm_track_finish: the query block exceeds what the tracker was created for");
       return DVM_ERR_CAPACITY;
     }
@@ -295,8 +262,7 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
   });
   std::memcpy(m.inv_sigma2, q0.inv_level_sigma2, (size_t)q0.nlevels * 4);
   {
-    const size_t used = (size_t)(reinterpret_cast<uint8_t*>(m.inv_sigma2) - t->hm) + pad256(64 * 4);
-    DVM_HIP(hipMemcpyAsync(t->d_q, t->hm, used, hipMemcpyHostToDevice, t->cstream));   // beside the extraction, not behind it
+    DVM_HIP(hipMemcpyAsync(t->d_q, t->ws.hm, q_used, hipMemcpyHostToDevice, t->cstream));   // beside the extraction, not behind it
     DVM_HIP(hipEventRecord(t->cev, t->cstream));
     DVM_HIP(hipStreamWaitEvent(s, t->cev, 0));
   }
@@ -320,12 +286,12 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
   { static const bool no_rq = std::getenv("DVM_TRACK_NO_REQUERY") != nullptr; if (no_rq) rq.F.skp = nullptr; }   /* timing experiment only */
   rq.qdesc = t->qdev(m.qdesc); rq.qx = t->qdev(m.qx); rq.qy = t->qdev(m.qy); rq.qr = t->qdev(m.qr); rq.qmin = t->qdev(m.qmin); rq.qmax = t->qdev(m.qmax);
   launch_track_claims(s, t->d_ranked, t->qdev(m.q_claims), t->qdev(m.q_angle), 0, rq, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, q0.th_high,
-                      q0.check_ori, t->d_assign, t->d_res, t->dev(m.assign), t->dev(m.res), TB);
+                      q0.check_ori, t->d_assign, t->d_res, t->ws.dev(m.assign), t->ws.dev(m.res), TB);
   launch_track_gather(s, t->d_assign, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, t->qdev(m.q_pos), t->qdev(m.inv_sigma2), q0.nlevels, t->d_Xw,
-                      t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges, t->d_res, q0.min_matches, t->dev(m.nedges), TB);
+                      t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges, t->d_res, q0.min_matches, t->ws.dev(m.nedges), TB);
   ba_launch_pose_optimize(s, t->qdev(m.pose_in), t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, q0.cam.fx, q0.cam.fy, q0.cam.cx, q0.cam.cy,
-                          t->dev(m.pose_out), t->d_edge_out, t->dev(m.n_inl), t->d_chi);
-  launch_track_finish(s, t->d_assign, d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, t->qdev(m.q_claims), t->dev(m.outlier), t->dev(m.fin), t->d_res, TB);
+                          t->ws.dev(m.pose_out), t->d_edge_out, t->ws.dev(m.n_inl), t->d_chi);
+  launch_track_finish(s, t->d_assign, d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, t->qdev(m.q_claims), t->ws.dev(m.outlier), t->ws.dev(m.fin), t->d_res, TB);
   // (what the host wants back is written to mapped memory by the kernels themselves: no copy command behind the chain)
   rc = hip_check(hipGetLastError(), "tracking chain launch");
   if (rc != DVM_OK) return rc;
@@ -395,13 +361,13 @@ struct LocalMapUpload {
 constexpr size_t kFrameRec = 7 * 8 + sizeof(LocalFrameArgs) + 8;     // per frame bytes of the frame block
 LocalMapUpload carve_local_map_upload(uint8_t* base, int count, size_t T, size_t kstride) {
   LocalMapUpload u;
-  uint8_t* p = base;
-  u.scale = carve<float>(p, 64); u.inv_sigma2 = carve<float>(p, 64);
-  uint8_t* fb = carve<uint8_t>(p, (size_t)count * kFrameRec);
+  Cursor256 c{base};
+  u.scale = c.carve<float>(64); u.inv_sigma2 = c.carve<float>(64);
+  uint8_t* fb = c.carve<uint8_t>((size_t)count * kFrameRec);
   u.pose = reinterpret_cast<double*>(fb); u.fa = reinterpret_cast<LocalFrameArgs*>(fb + (size_t)count * 56);
   u.qoff = reinterpret_cast<int32_t*>(u.fa + count); u.skip_on = u.qoff + count;
-  u.pts = carve<LocalPointPod>(p, T); u.frame_mp = carve<int32_t>(p, (size_t)count * kstride);
-  u.bytes = (size_t)(p - base);
+  u.pts = c.carve<LocalPointPod>(T); u.frame_mp = c.carve<int32_t>((size_t)count * kstride);
+  u.bytes = c.used();
   return u;
 }
 }  // namespace
@@ -416,19 +382,18 @@ int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points) {
   t->lm_cap = 0; t->lf.ready = 0; t->lf.batch_ready = 0;
   // P: table entries of one call (a batch: all frames' tables, each rounded up to 64); per keypoint and per frame: max_frames frames
   const size_t P = ((size_t)max_points + 63) & ~(size_t)63, K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
-  const size_t up = pad256(B * kFrameRec) + 2 * pad256(256) + pad256(P * sizeof(LocalPointPod)) + pad256(B * K * 4);
+  const size_t up = pad<256>(B * kFrameRec) + 2 * pad<256>(256) + pad<256>(P * sizeof(LocalPointPod)) + pad<256>(B * K * 4);
   // device: upload copy, per-entry arrays (seen, pos, claims), per-keypoint arrays (frame_mp, skip), pose seeds, query arrays at any stride
   // up to P, ranked lists, counters
-  const size_t dbytes = up + pad256(P) + pad256(P * 12) + pad256(P) + pad256(B * K * 4) + pad256(B * K) + pad256(B * 56) +
-                        pad256(P * 32) + 5 * pad256(P * 4) + pad256(P) + pad256(P * 4) + pad256(P * 16) + 2 * pad256(B * 32);
-  const size_t mbytes = up + pad256(B * K * 4) + pad256(B * K) + pad256(P * sizeof(TrackPoint)) + pad256(B * 64) + pad256(B * 56) +
-                        3 * pad256(B * 16);
-  if (const char* what = t->lmw.alloc(dbytes, mbytes)) return reserve_failed("dvm_tracker_reserve_local_map", what);
-  t->lmw.up_bytes = up;
-  uint8_t* p = t->lmw.hm + up;
+  const size_t dbytes = up + pad<256>(P) + pad<256>(P * 12) + pad<256>(P) + pad<256>(B * K * 4) + pad<256>(B * K) + pad<256>(B * 56) +
+                        pad<256>(P * 32) + 5 * pad<256>(P * 4) + pad<256>(P) + pad<256>(P * 4) + pad<256>(P * 16) + 2 * pad<256>(B * 32);
+  const size_t mbytes = up + pad<256>(B * K * 4) + pad<256>(B * K) + pad<256>(P * sizeof(TrackPoint)) + pad<256>(B * 64) + pad<256>(B * 56) +
+                        3 * pad<256>(B * 16);
+  if (const char* what = t->lmw.alloc(dbytes, mbytes, up, /*mapped*/ true, /*zeroed*/ true)) return reserve_failed("dvm_tracker_reserve_local_map", what);
+  Cursor256 c{t->lmw.hm + up};
   auto& r = t->lm;
-  r.mp = carve<int32_t>(p, B * K); r.outlier = carve<uint8_t>(p, B * K); r.tp = carve<TrackPoint>(p, P); r.res = carve<int32_t>(p, B * 16);
-  r.pose = carve<double>(p, B * 7); r.n_inl = carve<int32_t>(p, B * 4); r.fin = carve<int32_t>(p, B * 4); r.nedges = carve<int32_t>(p, B * 4);
+  r.mp = c.carve<int32_t>(B * K); r.outlier = c.carve<uint8_t>(B * K); r.tp = c.carve<TrackPoint>(P); r.res = c.carve<int32_t>(B * 16);
+  r.pose = c.carve<double>(B * 7); r.n_inl = c.carve<int32_t>(B * 4); r.fin = c.carve<int32_t>(B * 4); r.nedges = c.carve<int32_t>(B * 4);
   t->lm_cap = (int)P;
   return DVM_OK;
 }
@@ -492,14 +457,14 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
   // 2. device arrays of this call: per entry at the frames' offsets, per keypoint at b * ocap
   const size_t Kb = (size_t)count * ocap;
   LocalQueries LQ;
-  uint8_t* p = t->lmw.d + t->lmw.up_bytes;
-  LQ.seen = carve<uint8_t>(p, Tc); LQ.pos = carve<float>(p, Tc * 3); LQ.claims = carve<uint8_t>(p, Tc);
-  LQ.frame_mp = carve<int32_t>(p, Kb); LQ.skip = carve<uint8_t>(p, Kb); LQ.pose_in = carve<double>(p, (size_t)count * 7);
-  LQ.qdesc = carve<uint8_t>(p, Tc * 32); LQ.qx = carve<float>(p, Tc); LQ.qy = carve<float>(p, Tc); LQ.qr = carve<float>(p, Tc);
-  LQ.qmin = carve<int32_t>(p, Tc); LQ.qmax = carve<int32_t>(p, Tc); LQ.q_claims = carve<uint8_t>(p, Tc); LQ.q_tab = carve<int32_t>(p, Tc);
-  uint32_t* d_ranked = carve<uint32_t>(p, Tc * 4);
-  int32_t* d_lres = carve<int32_t>(p, (size_t)count * 8);
-  LQ.nq = carve<int32_t>(p, (size_t)count * 8);
+  Cursor256 c{t->lmw.d + t->lmw.up_bytes};
+  LQ.seen = c.carve<uint8_t>(Tc); LQ.pos = c.carve<float>(Tc * 3); LQ.claims = c.carve<uint8_t>(Tc);
+  LQ.frame_mp = c.carve<int32_t>(Kb); LQ.skip = c.carve<uint8_t>(Kb); LQ.pose_in = c.carve<double>((size_t)count * 7);
+  LQ.qdesc = c.carve<uint8_t>(Tc * 32); LQ.qx = c.carve<float>(Tc); LQ.qy = c.carve<float>(Tc); LQ.qr = c.carve<float>(Tc);
+  LQ.qmin = c.carve<int32_t>(Tc); LQ.qmax = c.carve<int32_t>(Tc); LQ.q_claims = c.carve<uint8_t>(Tc); LQ.q_tab = c.carve<int32_t>(Tc);
+  uint32_t* d_ranked = c.carve<uint32_t>(Tc * 4);
+  int32_t* d_lres = c.carve<int32_t>((size_t)count * 8);
+  LQ.nq = c.carve<int32_t>((size_t)count * 8);
   LocalMapArgs A;
   A.fx = (float)f.cam.fx; A.fy = (float)f.cam.fy; A.cx = (float)f.cam.cx; A.cy = (float)f.cam.cy;
   A.min_x = f.bounds[0]; A.max_x = f.bounds[1]; A.min_y = f.bounds[2]; A.max_y = f.bounds[3];
@@ -637,34 +602,34 @@ struct KeyframeUpload {
 };
 KeyframeUpload carve_keyframe_upload(uint8_t* base, int count, size_t T) {
   KeyframeUpload u;
-  uint8_t* p = base;
+  Cursor256 c{base};
   const size_t B = (size_t)count;
-  u.inv_sigma2 = carve<float>(p, 64); u.pose = carve<double>(p, B * 7); u.qoff = carve<int32_t>(p, B); u.kfv_n = carve<int32_t>(p, B);
-  u.res = carve<int32_t>(p, B * 8); u.run = carve<int32_t>(p, B); u.wg_base = carve<int32_t>(p, B + 1);
-  u.desc = carve<uint8_t>(p, T * 32); u.angle = carve<float>(p, T); u.use = carve<uint8_t>(p, T); u.claims = carve<uint8_t>(p, T);
-  u.pos = carve<float>(p, T * 3); u.fv_node = carve<int32_t>(p, T); u.fv_feat = carve<int32_t>(p, T); u.fv_off = carve<int32_t>(p, T + B);
-  u.bytes = (size_t)(p - base);
+  u.inv_sigma2 = c.carve<float>(64); u.pose = c.carve<double>(B * 7); u.qoff = c.carve<int32_t>(B); u.kfv_n = c.carve<int32_t>(B);
+  u.res = c.carve<int32_t>(B * 8); u.run = c.carve<int32_t>(B); u.wg_base = c.carve<int32_t>(B + 1);
+  u.desc = c.carve<uint8_t>(T * 32); u.angle = c.carve<float>(T); u.use = c.carve<uint8_t>(T); u.claims = c.carve<uint8_t>(T);
+  u.pos = c.carve<float>(T * 3); u.fv_node = c.carve<int32_t>(T); u.fv_feat = c.carve<int32_t>(T); u.fv_off = c.carve<int32_t>(T + B);
+  u.bytes = c.used();
   return u;
 }
 // the device working set behind the upload, per frame at the call's capacity stride (cap <= kp_cap, count <= max_frames)
 struct RefKfWork { int32_t *word, *node; double* w; int32_t *fv_node, *fv_feat, *fv_off, *cnt, *match, *bin; size_t bytes; };
 RefKfWork carve_refkf_work(uint8_t* base, size_t B, size_t K) {
   RefKfWork r;
-  uint8_t* p = base;
-  r.word = carve<int32_t>(p, B * K); r.node = carve<int32_t>(p, B * K); r.w = carve<double>(p, B * K);
-  r.fv_node = carve<int32_t>(p, B * K); r.fv_feat = carve<int32_t>(p, B * K); r.fv_off = carve<int32_t>(p, B * (K + 1));
-  r.cnt = carve<int32_t>(p, B * kRefKfCnt); r.match = carve<int32_t>(p, B * K); r.bin = carve<int32_t>(p, B * K);
-  r.bytes = (size_t)(p - base);
+  Cursor256 c{base};
+  r.word = c.carve<int32_t>(B * K); r.node = c.carve<int32_t>(B * K); r.w = c.carve<double>(B * K);
+  r.fv_node = c.carve<int32_t>(B * K); r.fv_feat = c.carve<int32_t>(B * K); r.fv_off = c.carve<int32_t>(B * (K + 1));
+  r.cnt = c.carve<int32_t>(B * kRefKfCnt); r.match = c.carve<int32_t>(B * K); r.bin = c.carve<int32_t>(B * K);
+  r.bytes = c.used();
   return r;
 }
 // the mapped results behind the upload staging: BowVector, FeatureVector, match, counters, outlier flags, edges / inliers / nmatchesMap,
 // pose, B slices each; returns their bytes
 size_t carve_refkf_results(uint8_t* base, size_t B, size_t K, RefKfMapped& r) {
-  uint8_t* p = base;
-  r.bow_ids = carve<int32_t>(p, B * K); r.bow_vals = carve<double>(p, B * K); r.fv_node = carve<int32_t>(p, B * K); r.fv_feat = carve<int32_t>(p, B * K);
-  r.fv_off = carve<int32_t>(p, B * (K + 1)); r.match = carve<int32_t>(p, B * K); r.cnt = carve<int32_t>(p, B * 8); r.outlier = carve<uint8_t>(p, B * K);
-  r.nedges = carve<int32_t>(p, B * 4); r.n_inl = carve<int32_t>(p, B * 4); r.fin = carve<int32_t>(p, B * 4); r.pose = carve<double>(p, B * 7);
-  return (size_t)(p - base);
+  Cursor256 c{base};
+  r.bow_ids = c.carve<int32_t>(B * K); r.bow_vals = c.carve<double>(B * K); r.fv_node = c.carve<int32_t>(B * K); r.fv_feat = c.carve<int32_t>(B * K);
+  r.fv_off = c.carve<int32_t>(B * (K + 1)); r.match = c.carve<int32_t>(B * K); r.cnt = c.carve<int32_t>(B * 8); r.outlier = c.carve<uint8_t>(B * K);
+  r.nedges = c.carve<int32_t>(B * 4); r.n_inl = c.carve<int32_t>(B * 4); r.fin = c.carve<int32_t>(B * 4); r.pose = c.carve<double>(B * 7);
+  return c.used();
 }
 
 // (re)allocates w for keyframes of R entries per call (a multiple of 64) and the tracker's max_frames frames; fn names the caller's errors
@@ -674,8 +639,8 @@ int reserve_refkf(dvm_tracker* t, RefKf& w, size_t R, const char* fn) {
   const size_t K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
   const size_t up = carve_keyframe_upload(nullptr, (int)B, R).bytes;
   RefKfMapped sized;
-  if (const char* what = w.ws.alloc(up + carve_refkf_work(nullptr, B, K).bytes, up + carve_refkf_results(nullptr, B, K, sized))) return reserve_failed(fn, what);
-  w.ws.up_bytes = up;
+  if (const char* what = w.ws.alloc(up + carve_refkf_work(nullptr, B, K).bytes, up + carve_refkf_results(nullptr, B, K, sized), up, /*mapped*/ true, /*zeroed*/ true))
+    return reserve_failed(fn, what);
   carve_refkf_results(w.ws.hm + up, B, K, w.r);
   w.cap = (int)R;
   return DVM_OK;

@@ -4,6 +4,7 @@
 #include <string>
 
 #include "../../include/dvmslam_wire.h"
+#include "chain.h"   // need_any_device
 #include "wire_kernels.h"
 
 namespace dvm { void set_error(const std::string& s); }
@@ -124,8 +125,7 @@ int dvm_wire_gather_keypoints(void* d_block, int first_kf, int count, const dvm_
                               const uint8_t* d_desc, int64_t desc_stride, void* stream) {
   if (!d_block || first_kf < 0 || count < 0 || (count > 0 && (!d_kps || !d_desc))) return DVM_ERR_INVALID;
   if (count == 0) return DVM_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { dvm::set_error("no HIP device visible (libdvmslam_hip has no CPU path)"); return DVM_ERR_NO_DEVICE; }
+  { const int rc = dvm::need_any_device(); if (rc != DVM_OK) return rc; }
   dvm::launch_wire_gather((hipStream_t)stream, static_cast<uint8_t*>(d_block), first_kf, count, reinterpret_cast<const uint32_t*>(d_kps), kps_stride,
                           d_desc, desc_stride);
   if (hipGetLastError() != hipSuccess) { dvm::set_error("wire gather launch failed"); return DVM_ERR_HIP; }

@@ -62,6 +62,7 @@
 #include <vector>
 
 #include "KeyFrame.h"
+#include "chain_handle.h"
 #include "dvm_device.h"
 #include "dvmslam_host.h"
 
@@ -196,26 +197,17 @@ inline NewPointRecords CreateNewMapPointsChain(KeyFrame* pKF1, const std::vector
 
 // ---- LocalMapping::SearchInNeighbors (:812-849) on dvm_fuse_targets
 namespace dvm_fuse_detail {
-// the calling thread's chain handle: created on first use, reserved on growth, never per call
-struct Handle {
-  dvm_fuse_targets* h = nullptr;
-  int device = -1, np = 0, nt = 0, total = 0;
-  ~Handle() { if (h) dvm_fuse_targets_destroy(h); }
-  void ensure(int dev, int n_points, int n_targets, long total_keypoints) {
-    if (h && device != dev) { dvm_fuse_targets_destroy(h); h = nullptr; np = nt = total = 0; }
-    if (!h) {
-      if (dvm_fuse_targets_create(dev, &h) != DVM_OK) { h = nullptr; throw std::runtime_error(dvm_last_error()); }
-      device = dev;
-    }
-    if (n_points <= np && n_targets <= nt && total_keypoints <= total) return;
-    const int p = std::max(np, n_points + n_points / 4), t = std::max(nt, n_targets);
-    const int tot = (int)std::min<long>(std::max<long>(total, total_keypoints + total_keypoints / 4), (long)t * 8192);
-    if (dvm_fuse_targets_reserve(h, p, t, tot) != DVM_OK) throw std::runtime_error(dvm_last_error());
-    np = p; nt = t; total = tot;
-  }
-};
-inline Handle& handle() {
+// the calling thread's chain handle (chain_handle.h), cap: {points, targets, their keypoints}; growth with headroom on the points and on
+// the keypoints
+using Handle = dvm_host::ChainHandle<dvm_fuse_targets, dvm_fuse_targets_create, dvm_fuse_targets_destroy, dvm_fuse_targets_reserve>;
+inline Handle& handle(int dev, int n_points, int n_targets, long total_keypoints) {
   thread_local Handle H;
+  if (H.open(dev) != DVM_OK) throw std::runtime_error(dvm_last_error());
+  if (!H.holds(n_points, n_targets, total_keypoints)) {
+    const int p = std::max(H.cap[0], n_points + n_points / 4), t = std::max(H.cap[1], n_targets);
+    const int tot = (int)std::min<long>(std::max<long>(H.cap[2], total_keypoints + total_keypoints / 4), (long)t * 8192);
+    if (H.reserve(p, t, tot) != DVM_OK) throw std::runtime_error(dvm_last_error());
+  }
   return H;
 }
 inline void read_descriptor(MapPoint* p, uint8_t* dst) {
@@ -284,9 +276,8 @@ inline void FusePass(const std::vector<KeyFrame*>& vpKFs, const std::vector<MapP
   dvm_ft_points P;
   P.n = (int32_t)n; P.pos = pos.data(); P.normal = normal.data(); P.min_dist = mind.data(); P.max_dist = maxd.data(); P.desc = desc.data();
   P.valid = valid.data();
-  Handle& H = handle();
   dvm_host::use_device();
-  H.ensure(dvm_host::device(), (int)n, (int)T, total);
+  Handle& H = handle(dvm_host::device(), (int)n, (int)T, total);
   if (dvm_fuse_targets_set(H.h, (int)T, targets.data()) != DVM_OK) throw std::runtime_error(dvm_last_error());
   std::vector<int32_t> best(T * n, -1), fresh;
   if (dvm_fuse_targets_run(H.h, &P, skip.data(), th, best.data(), nullptr) != DVM_OK) throw std::runtime_error(dvm_last_error());

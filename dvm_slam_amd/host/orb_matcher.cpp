@@ -1,5 +1,6 @@
 // dvm_slam_amd/host/orb_matcher.cpp -- see orb_matcher.h.  Host C++ (g++), links libdvmslam_hip.so.
 #include "orb_matcher.h"
+#include "chain_handle.h"
 
 #include "../csrc/pose_f32.h"
 #include "../csrc/rot_bin.h"
@@ -1012,13 +1013,9 @@ int dvmh_search_for_triangulation(int device, const dvmh_keyframe_view* KF1, con
   return m.SearchForTriangulation(KeyFrameView(*KF1), KeyFrameView(*KF2), pairs, false, coarse != 0);
 }
 namespace {
-// the calling thread's chain handle (one per device it has used): created on first use, reserved on growth, never per call
-struct NewPointsSlot {
-  int device = -1;
-  dvm_new_points* h = nullptr;
-  int n1 = 0, nb = 0, total = 0;
-  ~NewPointsSlot() { if (h) dvm_new_points_destroy(h); }
-};
+// the calling thread's chain handles; cap: {current keyframe's keypoints, neighbours, their keypoints} / {points, targets, their keypoints}
+using NewPointsSlot = dvm_host::ChainHandle<dvm_new_points, dvm_new_points_create, dvm_new_points_destroy, dvm_new_points_reserve>;
+using FuseTargetsSlot = dvm_host::ChainHandle<dvm_fuse_targets, dvm_fuse_targets_create, dvm_fuse_targets_destroy, dvm_fuse_targets_reserve>;
 dvm_np_keyframe NpKeyFrame(const dvmh_keyframe_view& K) {
   dvm_np_keyframe k;
   std::memset(&k, 0, sizeof(k));
@@ -1035,12 +1032,7 @@ int dvmh_create_new_map_points(int device, const dvmh_keyframe_view* cur, int n_
                                const float* median_depth, const dvm_np_params* p, dvm_np_out* out) {
   if (!cur || n_neighbours < 0 || (n_neighbours > 0 && (!neighbours || !median_depth)) || !p || !out) return DVM_ERR_INVALID;
   thread_local NewPointsSlot slot;
-  if (slot.h && slot.device != device) { dvm_new_points_destroy(slot.h); slot = NewPointsSlot(); }
-  if (!slot.h) {
-    const int rc = dvm_new_points_create(device, &slot.h);
-    if (rc != DVM_OK) { slot.h = nullptr; return rc; }
-    slot.device = device;
-  }
+  { const int rc = slot.open(device); if (rc != DVM_OK) return rc; }
   std::vector<dvm_np_neighbour> nbs((size_t)n_neighbours);
   int64_t total = 0;
   for (int j = 0; j < n_neighbours; j++) {
@@ -1052,12 +1044,11 @@ int dvmh_create_new_map_points(int device, const dvmh_keyframe_view* cur, int n_
   }
   const dvm_np_keyframe c = NpKeyFrame(*cur);
   // growth only, with headroom; sizes no reservation can hold are left to the call's own checks (they name the offending keyframe)
-  if (c.n >= 0 && c.n <= 8192 && total <= (int64_t)n_neighbours * 8192 && (c.n > slot.n1 || n_neighbours > slot.nb || total > slot.total)) {
-    const int n1 = std::max(slot.n1, c.n), nb = std::max(slot.nb, n_neighbours);
-    const int tot = (int)std::min<int64_t>(std::max<int64_t>(slot.total, total + total / 4), (int64_t)nb * 8192);
-    const int rc = dvm_new_points_reserve(slot.h, n1, nb, tot);
+  if (c.n >= 0 && c.n <= 8192 && total <= (int64_t)n_neighbours * 8192 && !slot.holds(c.n, n_neighbours, total)) {
+    const int n1 = std::max(slot.cap[0], c.n), nb = std::max(slot.cap[1], n_neighbours);
+    const int tot = (int)std::min<int64_t>(std::max<int64_t>(slot.cap[2], total + total / 4), (int64_t)nb * 8192);
+    const int rc = slot.reserve(n1, nb, tot);
     if (rc != DVM_OK) return rc;
-    slot.n1 = n1; slot.nb = nb; slot.total = tot;
   }
   return dvm_create_new_map_points(slot.h, &c, n_neighbours, nbs.data(), p, out);
 }
@@ -1065,24 +1056,11 @@ int dvmh_fuse(int device, const dvmh_keyframe_view* KF, const dvmh_map_points_vi
   dvm_host::ORBmatcher m(0.6f, true, device);
   return m.Fuse(KeyFrameView(*KF), MapPointsView(*P), inKF, th, best_idx);
 }
-namespace {
-struct FuseTargetsSlot {
-  int device = -1;
-  dvm_fuse_targets* h = nullptr;
-  int np = 0, nt = 0, total = 0;
-  ~FuseTargetsSlot() { if (h) dvm_fuse_targets_destroy(h); }
-};
-}  // namespace
 int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targets, const dvmh_map_points_view* P, const uint8_t* inKF, float th,
                       int32_t* best_idx) {
   if (n_targets < 0 || (n_targets > 0 && !targets) || !P || P->n < 0) return DVM_ERR_INVALID;
   thread_local FuseTargetsSlot slot;
-  if (slot.h && slot.device != device) { dvm_fuse_targets_destroy(slot.h); slot = FuseTargetsSlot(); }
-  if (!slot.h) {
-    const int rc = dvm_fuse_targets_create(device, &slot.h);
-    if (rc != DVM_OK) { slot.h = nullptr; return rc; }
-    slot.device = device;
-  }
+  { const int rc = slot.open(device); if (rc != DVM_OK) return rc; }
   std::vector<dvm_ft_target> tg((size_t)n_targets);
   int64_t total = 0;
   for (int t = 0; t < n_targets; t++) {
@@ -1099,13 +1077,11 @@ int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targe
     total += std::max(K.N, 0);
   }
   // growth only, with headroom; sizes no reservation can hold are left to the calls' own checks (they name the offending target)
-  if (n_targets <= 65535 && total <= (int64_t)n_targets * 8192 && (int64_t)std::max(P->n, slot.np) * std::max(n_targets, slot.nt) <= ((int64_t)1 << 27) &&
-      (P->n > slot.np || n_targets > slot.nt || total > slot.total)) {
-    const int np = std::max(slot.np, P->n), nt = std::max(slot.nt, n_targets);
-    const int tot = (int)std::min<int64_t>(std::max<int64_t>(slot.total, total + total / 4), (int64_t)nt * 8192);
-    const int rc = dvm_fuse_targets_reserve(slot.h, np, nt, tot);
+  const int np = std::max(slot.cap[0], P->n), nt = std::max(slot.cap[1], n_targets);
+  if (n_targets <= 65535 && total <= (int64_t)n_targets * 8192 && (int64_t)np * nt <= ((int64_t)1 << 27) && !slot.holds(P->n, n_targets, total)) {
+    const int tot = (int)std::min<int64_t>(std::max<int64_t>(slot.cap[2], total + total / 4), (int64_t)nt * 8192);
+    const int rc = slot.reserve(np, nt, tot);
     if (rc != DVM_OK) return rc;
-    slot.np = np; slot.nt = nt; slot.total = tot;
   }
   int rc = dvm_fuse_targets_set(slot.h, n_targets, tg.data());
   if (rc != DVM_OK) return rc;
