@@ -113,25 +113,29 @@ def test_match_window_ties(capi, oracle):
 
 
 def test_grid_edge_cases(capi, oracle):
-    # empty frame, single keypoint, keypoints outside the grid (dropped by PosInGrid), ragged n
-    for n in (0, 1, 63, 65, 1025):
-        rng = np.random.default_rng(n)
-        kps = np.zeros(n, oracle.KP_DTYPE)
-        kps["x"] = rng.uniform(-5, 645, n).astype(np.float32)  # some round to column 64 -> not indexed
-        kps["y"] = rng.uniform(-5, 485, n).astype(np.float32)
-        kps["octave"] = rng.integers(0, 8, n)
-        desc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
-        g = capi.FrameGrid(capacity=2048)
-        g.build(kps, desc)
-        o = oracle.Grid(kps)
-        nq = 64
-        qd = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
-        qx = rng.uniform(0, 640, nq).astype(np.float32)
-        qy = rng.uniform(0, 480, nq).astype(np.float32)
-        qr = np.full(nq, 700, np.float32)
-        neg = np.full(nq, -1, np.int32)
-        _check_matches(g.match_window(qd, qx, qy, qr, neg, neg), o.match_window(desc, qd, qx, qy, qr, neg, neg))
-        g.close()
+    # empty frame, single keypoint, keypoints outside the grid (dropped by PosInGrid), ragged n -- on a handle of 2 048 and on one of the
+    # full 8 192 (few keys in a full-capacity slot, the 8 192-entry skip buffer)
+    for cap in (2048, 8192):
+        for n in (0, 1, 63, 65, 1025):
+            rng = np.random.default_rng(n)
+            kps = np.zeros(n, oracle.KP_DTYPE)
+            kps["x"] = rng.uniform(-5, 645, n).astype(np.float32)  # some round to column 64 -> not indexed
+            kps["y"] = rng.uniform(-5, 485, n).astype(np.float32)
+            kps["octave"] = rng.integers(0, 8, n)
+            desc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+            g = capi.FrameGrid(capacity=cap)
+            g.build(kps, desc)
+            o = oracle.Grid(kps)
+            nq = 64
+            qd = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
+            qx = rng.uniform(0, 640, nq).astype(np.float32)
+            qy = rng.uniform(0, 480, nq).astype(np.float32)
+            qr = np.full(nq, 700, np.float32)
+            neg = np.full(nq, -1, np.int32)
+            _check_matches(g.match_window(qd, qx, qy, qr, neg, neg), o.match_window(desc, qd, qx, qy, qr, neg, neg))
+            skip = (rng.random(n) < 0.3).astype(np.uint8)
+            _check_matches(g.match_window(qd, qx, qy, qr, neg, neg, skip=skip), o.match_window(desc, qd, qx, qy, qr, neg, neg, skip=skip))
+            g.close()
 
 
 def test_match_frames_batch(capi, oracle, frames):
