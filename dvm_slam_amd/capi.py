@@ -2176,3 +2176,78 @@ def fuse_targets(kfs, P, in_kf, th, device=0):
                 C.c_void_p(_ptr(bi)))
     check(min(rc, 0))
     return rc, bi
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dvm_search_by_bow_targets: the SearchByBoW calls of LoopClosing::DetectCommonRegionsFromBoW against all candidates and covisibles as one chain
+class _BtKeyFrame(C.Structure):   # == dvm_bt_keyframe
+    _fields_ = [("n", C.c_int32), ("fv_n", C.c_int32), ("kps", C.c_void_p), ("desc", C.c_void_p), ("mp", C.c_void_p), ("bad", C.c_void_p),
+                ("fv_node", C.c_void_p), ("fv_off", C.c_void_p), ("fv_feat", C.c_void_p)]
+
+
+class BowTargets(_Chain):
+    """dvm_bow_targets: SearchByBoW(cur, target) (ORBmatcher.cc:709-834) for all target keyframes behind one upload and one synchronisation."""
+
+    def __init__(self, device=0):
+        super().__init__("dvm_bow_targets", 2, device)
+        vp = C.c_void_p
+        self.L.dvm_search_by_bow_targets.argtypes = [vp, vp, C.c_int32, vp, C.c_float, C.c_int32, vp, vp]
+
+    def reserve(self, max_cur_keypoints, max_targets, max_total_target_keypoints):
+        self._reserve(max_cur_keypoints, max_targets, max_total_target_keypoints)
+
+    def last_kernel_ms(self):
+        """(search, settle) milliseconds of the last call that ran with profiling on."""
+        return self._last_kernel_ms()
+
+    @staticmethod
+    def _keyframe(kf, s, keep):
+        """dict(kps, desc, mp[, bad], fv) -> dvm_bt_keyframe; a key that is missing or None is a NULL array."""
+        kps = np.ascontiguousarray(kf["kps"], KP_DTYPE)
+        arrs = [kps, None if kf.get("desc") is None else np.ascontiguousarray(kf["desc"], np.uint8),
+                None if kf.get("mp") is None else np.ascontiguousarray(kf["mp"], np.int32),
+                None if kf.get("bad") is None else np.ascontiguousarray(kf["bad"], np.uint8)]
+        fv = kf.get("fv") or {}
+        arrs += [None if fv.get(k) is None else np.ascontiguousarray(fv[k], np.int32) for k in ("fv_nodes", "fv_off", "fv_feat")]
+        keep.append(arrs)
+        s.n = int(kf.get("n", len(kps)))
+        s.fv_n = 0 if arrs[4] is None else len(arrs[4])
+        s.kps, s.desc, s.mp, s.bad, s.fv_node, s.fv_off, s.fv_feat = (None if a is None else a.ctypes.data for a in arrs)
+
+    def prepare(self, cur, targets, nnratio=0.9, check_ori=True):
+        """The argument structs of a call built once: returns run() -> (match_idx2[T, n], nmatches[T]), for a caller that repeats the call
+        on the same keyframes (a timing loop).  The arrays are read in place at run()."""
+        keep = []
+        c = _BtKeyFrame()
+        self._keyframe(cur, c, keep)
+        T = len(targets)
+        arr = (_BtKeyFrame * max(T, 1))()
+        for t, kf in enumerate(targets):
+            self._keyframe(kf, arr[t], keep)
+        n1 = max(int(c.n), 0)
+        idx = np.full((T, n1), -7, np.int32); nm = np.full(T, -7, np.int32)
+
+        def run():
+            keep  # noqa: B018 (the arrays live as long as the closure)
+            check(self.L.dvm_search_by_bow_targets(self.h, C.addressof(c), T, C.addressof(arr), float(nnratio), int(check_ori),
+                                                   idx.ctypes.data, nm.ctypes.data))
+            return idx, nm
+        return run
+
+    def search(self, cur, targets, nnratio=0.9, check_ori=True):
+        """cur / targets: keyframe dicts (kps, desc, mp[, bad], fv).  Returns (match_idx2[T, n], nmatches[T])."""
+        return self.prepare(cur, targets, nnratio, check_ori)()
+
+
+def search_by_bow_targets(KF1, kfs, nnratio=0.9, check_ori=True, device=0, want_idx2=True):
+    """dvmh_search_by_bow_targets: KF1 / kfs = keyframe_view() results.  Returns (sum of nmatches, matches12[T, N] map-point ids,
+    idx2[T, N] or None, nmatches[T])."""
+    T, n = len(kfs), KF1[0].N
+    views = (_KeyFrameView * max(T, 1))()
+    for t, kv in enumerate(kfs):
+        views[t] = kv[0]
+    m12 = np.full((T, n), -7, np.int32); idx2 = np.full((T, n), -7, np.int32) if want_idx2 else None; nm = np.full(T, -7, np.int32)
+    rc = _hcall("dvmh_search_by_bow_targets", C.c_int32, C.c_int32(device), C.byref(KF1[0]), C.c_int32(T), C.byref(views), C.c_float(nnratio),
+                C.c_int32(int(check_ori)), C.c_void_p(m12.ctypes.data), C.c_void_p(None if idx2 is None else idx2.ctypes.data), C.c_void_p(nm.ctypes.data))
+    check(min(rc, 0))
+    return rc, m12, idx2, nm

@@ -1,0 +1,147 @@
+// dvm_slam_amd/csrc/bow_targets_kernels.hip -- ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (ORBmatcher.cc:709-834) of one current
+// keyframe against many target keyframes: the searches LoopClosing::DetectCommonRegionsFromBoW runs per candidate and covisible
+// (LoopClosing.cc:722-731), all in one launch plus one launch for the rotation checks.
+#include "bow_targets_kernels.h"
+#include "rot_bin.h"
+
+namespace dvm {
+
+// The reference walks the nodes both FeatureVectors share in ascending order; inside a node it takes KF1's features in list order (those
+// without a map point or with a bad one skipped, :742-748), scans the node's KF2 features that have a good map point and that no earlier
+// match has taken (vbMatched2, :759-767), keeps the smallest distance (first in scan order wins) and the second smallest (duplicates
+// counted), and takes the best when best < TH_LOW -- STRICT, :785; the KeyFrame -> Frame form (k_refkf_search) has <= -- and
+// best < nnratio * second.  A keypoint of KF2 lies in exactly ONE node of KF2's FeatureVector (the host checks it while packing), so
+// vbMatched2 never couples two nodes, and targets never share anything: every (target, node of KF1) pair is one independent sequential
+// walk.  One wave per pair: the node is found in the target's list by binary search, the wave walks the node's KF1 features in order and
+// scans the target's features across its lanes (min of (distance << 20 | scan position); per lane the two smallest distances, merged as
+// k_refkf_search merges them), so every decision sees exactly the claims the reference's walk has made by then.
+// Claims: lane l scans the positions l, l + 64, l + 128, ... of the node and no other lane ever reads them, so the claim flag of position
+// p is bit p / 64 of a 128-bit mask in lane p % 64's registers (a node holds at most 8192 features).  Nothing is shared between pairs,
+// whichever target the four waves of a workgroup belong to.
+// The wave writes match (-1 included) for every KF1 feature of its node, so the rows need no initialisation; KF1 features that no node
+// lists are the host's.  The histogram only counts, so its global atomics may come in any order.
+__global__ void __launch_bounds__(256) k_bt_search(const BtKfDev* __restrict__ tab, int n_targets, int n1, int fv_n1, float nnratio,
+                                                  int32_t* __restrict__ match, int8_t* __restrict__ bin, int32_t* __restrict__ cnt) {
+  const int lane = threadIdx.x & 63;
+  const int64_t pair = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (pair >= (int64_t)n_targets * fv_n1) return;
+  const int t = (int)(pair / fv_n1), a = (int)(pair - (int64_t)t * fv_n1);
+  const BtKfDev C = tab[0], K = tab[1 + t];
+  int32_t* row = match + (size_t)t * n1;
+  int8_t* brow = bin + (size_t)t * n1;
+  const int kb = C.fv_off[a], ke = C.fv_off[a + 1];
+  int fb = 0, fe = 0;
+  {
+    const uint32_t node = (uint32_t)C.fv_node[a];
+    int lo = 0, hi = K.fv_n;                // the target's nodes ascend as unsigned
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if ((uint32_t)K.fv_node[mid] < node) lo = mid + 1; else hi = mid;
+    }
+    if (lo < K.fv_n && (uint32_t)K.fv_node[lo] == node) { fb = K.fv_off[lo]; fe = K.fv_off[lo + 1]; }
+  }
+  if (fe <= fb) {                           // the target does not have the node: nothing of it matches
+    for (int k = kb + lane; k < ke; k += 64) row[C.fv_feat[k]] = -1;
+    return;
+  }
+  uint64_t claim0 = 0, claim1 = 0;          // bit s: this lane's position lane + 64 * s (claim1: s - 64) is taken
+  for (int k = kb; k < ke; k++) {
+    const int r = C.fv_feat[k];             // (the host checked 0 <= r < n1)
+    if (!C.use[r]) {
+      if (lane == 0) row[r] = -1;
+      continue;
+    }
+    uint32_t w[8];
+    {
+      const uint4* q = reinterpret_cast<const uint4*>(C.desc + (size_t)r * 32);
+      const uint4 q0 = q[0], q1 = q[1];
+      w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w; w[4] = q1.x; w[5] = q1.y; w[6] = q1.z; w[7] = q1.w;
+    }
+    uint32_t best = 0xFFFFFFFFu;
+    int d1 = 256, d2 = 256;
+    int s = 0;
+    for (int p = fb + lane; p < fe; p += 64, s++) {
+      const bool taken = ((s < 64 ? claim0 >> s : claim1 >> (s - 64)) & 1) != 0;
+      const int j = K.fv_feat[p];           // (the host checked 0 <= j < n)
+      if (taken || !K.use[j]) continue;
+      const uint4* td = reinterpret_cast<const uint4*>(K.desc + (size_t)j * 32);
+      const uint4 x = td[0], y = td[1];
+      const int d = __popc(x.x ^ w[0]) + __popc(x.y ^ w[1]) + __popc(x.z ^ w[2]) + __popc(x.w ^ w[3]) + __popc(y.x ^ w[4]) + __popc(y.y ^ w[5]) +
+                    __popc(y.z ^ w[6]) + __popc(y.w ^ w[7]);
+      best = min(best, ((uint32_t)d << 20) | (uint32_t)(p - fb));
+      if (d < d1) { d2 = d1; d1 = d; }
+      else if (d < d2) d2 = d;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {     // the two smallest of two ascending pairs: min(a1, b1), min(max(a1, b1), min(a2, b2))
+      best = min(best, (uint32_t)__shfl_xor((int)best, o));
+      const int od1 = __shfl_xor(d1, o), od2 = __shfl_xor(d2, o);
+      d2 = min(max(d1, od1), min(d2, od2));
+      d1 = min(d1, od1);
+    }
+    const int bd = (int)(best >> 20);
+    const bool take = bd < 50 && (float)bd < nnratio * (float)d2;     // TH_LOW, strict (:785-786)
+    if (take) {
+      const int pos = (int)(best & 0xFFFFFu);
+      if (lane == (pos & 63)) {
+        const int sb = pos >> 6;
+        if (sb < 64) claim0 |= 1ull << sb; else claim1 |= 1ull << (sb - 64);
+      }
+      if (lane == 0) {
+        const int j = K.fv_feat[fb + pos];
+        const int b = rot_bin(C.angle[r], K.angle[j]);
+        const bool in = b >= 0 && b < kRotHisto;                      // (angles outside [0, 360) fall outside the histogram)
+        row[r] = j; brow[r] = (int8_t)(in ? b : -2);
+        if (in) atomicAdd(&cnt[t * kBtCnt + b], 1);
+        atomicAdd(&cnt[t * kBtCnt + 30], 1);
+      }
+    } else if (lane == 0) {
+      row[r] = -1;
+    }
+  }
+}
+
+// the rotation check (:813-831): ComputeThreeMaxima on the target's histogram, the matches of the other bins taken back, nmatches.  It
+// walks the features KF1's FeatureVector lists: the others hold no match.  One workgroup per target.
+__global__ void __launch_bounds__(256) k_bt_settle(const BtKfDev* __restrict__ tab, int n1, int check_ori, int32_t* __restrict__ match,
+                                                  const int8_t* __restrict__ bin, const int32_t* __restrict__ cnt, int32_t* __restrict__ nmatches) {
+  __shared__ int s_rot[kRotHisto];
+  __shared__ int s_ind[3];
+  __shared__ int s_nd[4];
+  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const BtKfDev C = tab[0];
+  if (tid < kRotHisto) s_rot[tid] = cnt[t * kBtCnt + tid];
+  __syncthreads();
+  if (tid == 0) three_maxima(s_rot, s_ind);
+  __syncthreads();
+  int nd = 0;
+  if (check_ori) {
+    int32_t* row = match + (size_t)t * n1;
+    const int8_t* brow = bin + (size_t)t * n1;
+    const int m1 = C.fv_off[C.fv_n];
+    for (int p = tid; p < m1; p += 256) {
+      const int i = C.fv_feat[p];
+      if (row[i] < 0) continue;
+      const int b = brow[i];
+      if (b != s_ind[0] && b != s_ind[1] && b != s_ind[2]) { row[i] = -1; nd++; }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) nd += __shfl_xor(nd, o);
+  if (lane == 0) s_nd[wave] = nd;
+  __syncthreads();
+  if (tid == 0) nmatches[t] = cnt[t * kBtCnt + 30] - (s_nd[0] + s_nd[1] + s_nd[2] + s_nd[3]);
+}
+
+void launch_bt_search(hipStream_t s, const BtKfDev* tab, int n_targets, int n1, int fv_n1, float nnratio, int32_t* match, int8_t* bin, int32_t* cnt) {
+  const int64_t pairs = (int64_t)n_targets * fv_n1;
+  if (pairs < 1) return;
+  hipLaunchKernelGGL(k_bt_search, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, s, tab, n_targets, n1, fv_n1, nnratio, match, bin, cnt);
+}
+void launch_bt_settle(hipStream_t s, const BtKfDev* tab, int n_targets, int n1, int check_ori, int32_t* match, const int8_t* bin, const int32_t* cnt,
+                      int32_t* nmatches) {
+  if (n_targets < 1) return;
+  hipLaunchKernelGGL(k_bt_settle, dim3(n_targets), dim3(256), 0, s, tab, n1, check_ori, match, bin, cnt, nmatches);
+}
+
+}  // namespace dvm

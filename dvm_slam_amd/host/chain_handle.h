@@ -1,4 +1,4 @@
-// dvm_slam_amd/host/chain_handle.h -- the calling thread's handle of a device chain (dvm_new_points, dvm_fuse_targets): created on first
+// dvm_slam_amd/host/chain_handle.h -- the calling thread's handle of a device chain (dvm_new_points, dvm_fuse_targets, dvm_bow_targets): created on first
 // use, dropped and created again when the device changes, reserved on growth only -- never per call.  The caller decides what to reserve
 // (its own headroom, its own pre-checks) and how to report a status that is not DVM_OK.
 #pragma once

@@ -1016,6 +1016,15 @@ namespace {
 // the calling thread's chain handles; cap: {current keyframe's keypoints, neighbours, their keypoints} / {points, targets, their keypoints}
 using NewPointsSlot = dvm_host::ChainHandle<dvm_new_points, dvm_new_points_create, dvm_new_points_destroy, dvm_new_points_reserve>;
 using FuseTargetsSlot = dvm_host::ChainHandle<dvm_fuse_targets, dvm_fuse_targets_create, dvm_fuse_targets_destroy, dvm_fuse_targets_reserve>;
+// cap: {current keyframe's keypoints, targets, their keypoints}
+using BowTargetsSlot = dvm_host::ChainHandle<dvm_bow_targets, dvm_bow_targets_create, dvm_bow_targets_destroy, dvm_bow_targets_reserve>;
+dvm_bt_keyframe BtKeyFrame(const dvmh_keyframe_view& K) {
+  dvm_bt_keyframe k;
+  std::memset(&k, 0, sizeof(k));
+  k.n = K.N; k.kps = K.mvKeysUn; k.desc = K.mDescriptors; k.mp = K.mvpMapPoints; k.bad = K.mpBad;
+  k.fv_n = K.mFeatVec.n; k.fv_node = K.mFeatVec.node; k.fv_off = K.mFeatVec.off; k.fv_feat = K.mFeatVec.feat;
+  return k;
+}
 dvm_np_keyframe NpKeyFrame(const dvmh_keyframe_view& K) {
   dvm_np_keyframe k;
   std::memset(&k, 0, sizeof(k));
@@ -1098,6 +1107,42 @@ int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targe
   int nFused = 0;
   for (size_t e = 0; e < E; e++) nFused += best_idx[e] >= 0 ? 1 : 0;
   return nFused;
+}
+int dvmh_search_by_bow_targets(int device, const dvmh_keyframe_view* KF1, int n_targets, const dvmh_keyframe_view* targets, float nnratio,
+                               int check_ori, int32_t* matches12, int32_t* idx2, int32_t* nmatches) {
+  if (!KF1 || n_targets < 0 || (n_targets > 0 && (!targets || !nmatches || (KF1->N > 0 && !matches12)))) return DVM_ERR_INVALID;
+  thread_local BowTargetsSlot slot;
+  { const int rc = slot.open(device); if (rc != DVM_OK) return rc; }
+  std::vector<dvm_bt_keyframe> tg((size_t)n_targets);
+  int64_t total = 0;
+  for (int t = 0; t < n_targets; t++) {
+    tg[t] = BtKeyFrame(targets[t]);
+    total += std::max(targets[t].N, 0);
+  }
+  const dvm_bt_keyframe c = BtKeyFrame(*KF1);
+  // growth only, with headroom; sizes no reservation can hold are left to the call's own checks (they name the offending keyframe)
+  const int n1 = std::max(slot.cap[0], c.n), nt = std::max(slot.cap[1], n_targets);
+  if (c.n >= 0 && c.n <= 8192 && n_targets <= 65535 && total <= (int64_t)n_targets * 8192 && (int64_t)n1 * nt <= ((int64_t)1 << 27) &&
+      !slot.holds(c.n, n_targets, total)) {
+    const int tot = (int)std::min<int64_t>(std::max<int64_t>(slot.cap[2], total + total / 4), (int64_t)nt * 8192);
+    const int rc = slot.reserve(n1, nt, tot);
+    if (rc != DVM_OK) return rc;
+  }
+  const size_t N = (size_t)std::max(c.n, 0), E = N * (size_t)n_targets;
+  std::vector<int32_t> own;
+  if (!idx2) { own.resize(std::max<size_t>(E, 1)); idx2 = own.data(); }
+  const int rc = dvm_search_by_bow_targets(slot.h, &c, n_targets, tg.data(), nnratio, check_ori, idx2, nmatches);
+  if (rc != DVM_OK) return rc;
+  int sum = 0;
+  for (int t = 0; t < n_targets; t++) {
+    const int32_t* mp2 = targets[t].mvpMapPoints;
+    for (size_t i = 0; i < N; i++) {
+      const int32_t j = idx2[(size_t)t * N + i];
+      matches12[(size_t)t * N + i] = j >= 0 ? mp2[j] : -1;     // vpMatches12[idx1] = vpMapPoints2[bestIdx2] (:787)
+    }
+    sum += nmatches[t];
+  }
+  return sum;
 }
 int dvmh_fuse_sim3(int device, dvmh_keyframe_view* KF, const dvm_sim3f* Scw, const dvmh_map_points_view* P, float th, int32_t* replace) {
   dvm_host::ORBmatcher m(0.6f, true, device);

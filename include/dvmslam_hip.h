@@ -482,6 +482,47 @@ int dvm_fuse_targets_run(dvm_fuse_targets* h, const dvm_ft_points* P, const uint
 int dvm_fuse_targets_profiling(dvm_fuse_targets* h, int enable);
 int dvm_fuse_targets_last_kernel_ms(dvm_fuse_targets* h, float* ms);
 
+/* The BoW searches of LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:722-731): ORBmatcher::SearchByBoW(mpCurrentKF, vpCovKFi[j],
+ * vvpMatchedMPs[j]) (ORBmatcher.cc:709-834) once per candidate and covisible keyframe -- up to 11 per candidate, 33 per candidate list --
+ * for ALL target keyframes as ONE chain.  The search of one pair walks the vocabulary nodes both FeatureVectors share; a keypoint of the
+ * target lies in exactly one node, so the claims of one node (vbMatched2) never reach another, and targets share nothing: every
+ * (target, node of cur) pair is an independent sequential walk, one wave each.
+ *
+ *   one packed upload of cur and all targets (keypoint angles, descriptors, a has-good-map-point flag, the FeatureVectors; every target's
+ *   span rounded up), TWO launches -- the search over (target, node) pairs, the rotation check (ComputeThreeMaxima, :813-831) per target --
+ *   and ONE copy back behind ONE synchronisation.  The call never allocates after dvm_bow_targets_reserve.
+ *
+ * Contract: match_idx2[t * cur->n + i] is the keypoint of target t that SearchByBoW(cur, targets[t]) leaves matched to keypoint i of cur
+ * (vpMatches12[i] == targets[t]'s map point of that keypoint), -1 where it leaves NULL; nmatches[t] is that call's return value.  Both
+ * equal the reference's sequential walk bit for bit, with its acceptance rule best < TH_LOW = 50 (strict, :785) and
+ * (float)best < nnratio * (float)second.  Row t does not depend on the other targets.
+ *
+ * Errors, all reported before anything runs and leaving the handle usable: DVM_ERR_CAPACITY -- cur's keypoints, the targets or their
+ * total keypoints beyond the reservation; DVM_ERR_INVALID -- a keyframe with n > 8192, a missing array, node ids not strictly ascending
+ * as unsigned, fv_off not non-decreasing from 0, an fv_feat entry outside [0, n), an fv_feat entry listed twice within one keyframe (the
+ * independence of the nodes rests on it).  dvm_bow_targets_create returns DVM_ERR_NO_DEVICE without a GPU.  Legal: n_targets = 0 (writes
+ * nothing), cur->n = 0 or cur->fv_n = 0 (nmatches all 0), a target with n = 0 or fv_n = 0 (its row is -1, its count 0).
+ * sizeof(dvm_bt_keyframe) == 64 (LP64). */
+typedef struct {
+  int32_t n, fv_n;                  /* keypoints; nodes of mFeatVec */
+  const dvm_keypoint* kps;          /* mvKeysUn (the search reads .angle only) */
+  const uint8_t* desc;              /* n x 32 */
+  const int32_t* mp;                /* n: >= 0 where GetMapPointMatches()[i] != NULL */
+  const uint8_t* bad;               /* n: isBad() of that point; may be NULL */
+  const int32_t *fv_node, *fv_off, *fv_feat;   /* mFeatVec flattened, nodes ascending as unsigned (dvm_ref_keyframe's convention) */
+} dvm_bt_keyframe;
+typedef struct dvm_bow_targets dvm_bow_targets;
+int dvm_bow_targets_create(int device, dvm_bow_targets** out);
+void dvm_bow_targets_destroy(dvm_bow_targets* h);
+/* the working set for calls up to these sizes (grow-only; the search never allocates) */
+int dvm_bow_targets_reserve(dvm_bow_targets* h, int max_cur_keypoints, int max_targets, int max_total_target_keypoints);
+/* match_idx2 [n_targets * cur->n], nmatches [n_targets] */
+int dvm_search_by_bow_targets(dvm_bow_targets* h, const dvm_bt_keyframe* cur, int n_targets, const dvm_bt_keyframe* targets, float nnratio,
+                              int check_ori, int32_t* match_idx2, int32_t* nmatches);
+/* HIP-event timing (measurement only): enable != 0 makes the search record events; ms[2] = search kernel, settle kernel of the last call */
+int dvm_bow_targets_profiling(dvm_bow_targets* h, int enable);
+int dvm_bow_targets_last_kernel_ms(dvm_bow_targets* h, float* ms);
+
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:384-453), batched: map point p owns the descriptors
  * desc[off[p] .. off[p+1]) (32 B each, its observations in the reference's iteration order); best_idx[p] = index
  * inside that range of the descriptor with the least median Hamming distance to the others (median =

@@ -149,6 +149,13 @@ int dvmh_search_by_bow_kf_frame(int device, const dvmh_keyframe_view* KF, const 
                                 int check_ori, int32_t* matches, int* requeried);
 int dvmh_search_by_bow_kf_kf(int device, const dvmh_keyframe_view* KF1, const dvmh_keyframe_view* KF2, float nnratio, int check_ori, int32_t* matches12,
                              int* requeried);
+/* SearchByBoW(pKF1, pKF2, vpMatches12) of one keyframe against n_targets keyframes as ONE device chain (dvm_search_by_bow_targets,
+ * include/dvmslam_hip.h) -- the searches of LoopClosing::DetectCommonRegionsFromBoW (src/LoopClosing.cc:722-731) for every candidate and
+ * covisible at once.  matches12 [n_targets * KF1->N] map-point ids, idx2 likewise (the matched keypoint of the target; may be NULL),
+ * nmatches [n_targets]: row t and nmatches[t] equal dvmh_search_by_bow_kf_kf(device, KF1, &targets[t], nnratio, check_ori, ...) bit for
+ * bit.  Returns the sum of nmatches.  The chain handle belongs to the calling thread and is reserved on growth only. */
+int dvmh_search_by_bow_targets(int device, const dvmh_keyframe_view* KF1, int n_targets, const dvmh_keyframe_view* targets, float nnratio,
+                               int check_ori, int32_t* matches12, int32_t* idx2, int32_t* nmatches);
 /* SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo = false, bCoarse), :836-1058; pairs: up to KF1->N (idx1, idx2) */
 int dvmh_search_for_triangulation(int device, const dvmh_keyframe_view* KF1, const dvmh_keyframe_view* KF2, int coarse, int check_ori, int32_t* pairs);
 /* the geometry it derives from the two poses (:841-862, CameraModels/Pinhole.cpp:106-110): R12 [9], t12 [3], epipole [2], F12 [9] */
