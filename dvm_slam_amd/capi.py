@@ -58,6 +58,48 @@ class FrustumFrame(C.Structure):
                 ("max_y", C.c_float), ("bf", C.c_float), ("log_scale_factor", C.c_float), ("n_levels", C.c_int32)]
 
 
+class CameraModel(C.Structure):   # == dvm_camera_model
+    """A camera model of the reference's GeometricCamera: model 0 pinhole, 1 KannalaBrandt8; p = fx, fy, cx, cy, k1, k2, k3, k4."""
+    _fields_ = [("model", C.c_int32), ("p", C.c_float * 8)]
+    PINHOLE, KANNALA_BRANDT8 = 0, 1
+
+    @classmethod
+    def make(cls, model, params):
+        v = [float(x) for x in params] + [0.0] * (8 - len(params))
+        return cls(int(model), (C.c_float * 8)(*v))
+
+    @classmethod
+    def pinhole(cls, fx, fy, cx, cy):
+        return cls.make(cls.PINHOLE, [fx, fy, cx, cy])
+
+    @classmethod
+    def robomaster(cls):
+        """The real robot's camera (Camera.type: "KannalaBrandt8"): calibrated at 1920 x 1080 and used at 960 x 540, so fx, fy, cx, cy are
+        the calibration's times 0.5, as the reference's Settings scale them for the resized image."""
+        return cls.make(cls.KANNALA_BRANDT8, [0.5 * 495.1139105110322, 0.5 * 494.58353174914896, 0.5 * 960.3182783342162, 0.5 * 555.0427286112108,
+                                              -0.027058405982580736, 0.025005319766890292, -0.02255121102967952, 0.006475379139360301])
+
+    @classmethod
+    def tum(cls):
+        """The 512 x 512 fisheye camera of the TUM-VI sequences (Camera.type: "KannalaBrandt8")."""
+        return cls.make(cls.KANNALA_BRANDT8, [190.978477, 190.973307, 254.931706, 256.897442, 0.003482389402, 0.000715034845, -0.002053236141, 0.000202936736])
+
+    @property
+    def params(self):
+        return np.array(list(self.p), np.float32)
+
+    def project(self, Xc):
+        """Pixels of camera-frame points [n, 3] in float64 (for building scenes; the device code is csrc/camera_model.h)."""
+        p = self.params.astype(np.float64); X = np.asarray(Xc, np.float64).reshape(-1, 3)
+        if self.model == self.PINHOLE:
+            return np.stack([p[0] * X[:, 0] / X[:, 2] + p[2], p[1] * X[:, 1] / X[:, 2] + p[3]], axis=1)
+        rho = np.hypot(X[:, 0], X[:, 1]); th = np.arctan2(rho, X[:, 2])
+        r = th * (1 + th ** 2 * (p[4] + th ** 2 * (p[5] + th ** 2 * (p[6] + th ** 2 * p[7]))))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c, s = np.where(rho > 0, X[:, 0] / rho, 1.0), np.where(rho > 0, X[:, 1] / rho, 0.0)
+        return np.stack([p[0] * r * c + p[2], p[1] * r * s + p[3]], axis=1)
+
+
 class TriPair(C.Structure):   # == dvm_tri_pair
     _fields_ = [("cos_parallax_max", C.c_double), ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("T1w", C.c_float * 12), ("T2w", C.c_float * 12),
                 ("Ow1", C.c_float * 3), ("Ow2", C.c_float * 3), ("ratio_factor", C.c_float), ("th_far", C.c_float), ("far_points", C.c_int32),
@@ -774,6 +816,37 @@ def pose_optimize(poses, Xw, obs, inv_sigma2, n, intrinsics, device=0):
     return out, outl, nin
 
 
+def pose_optimize_cam(poses, Xw, obs, inv_sigma2, n, model, device=0):
+    """dvm_pose_optimize_cam: pose_optimize on a CameraModel (model 0: the pinhole kernel on its four floats)."""
+    poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+    B = len(poses)
+    Xw = np.ascontiguousarray(Xw, np.float64).reshape(B, -1, 3)
+    S = Xw.shape[1]
+    obs = np.ascontiguousarray(obs, np.float64).reshape(B, S, 2)
+    inv_sigma2 = np.ascontiguousarray(inv_sigma2, np.float64).reshape(B, S)
+    n = np.ascontiguousarray(n, np.int32).reshape(B)
+    out = np.zeros((B, 7), np.float64)
+    outl = np.zeros((B, S), np.uint8)
+    nin = np.zeros(B, np.int32)
+    fn = lib().dvm_pose_optimize_cam
+    fn.restype = C.c_int32; fn.argtypes = None
+    check(fn(C.c_int32(device), _p(poses), _p(Xw), _p(obs), _p(inv_sigma2), _p(n), C.c_int32(S), C.c_int32(B), None if model is None else C.byref(model),
+             _p(out), _p(outl), _p(nin)))
+    return out, outl, nin
+
+
+def is_in_frustum_cam(F: "FrustumFrame", model, P, normal, min_dist, max_dist, viewing_cos_limit=0.5):
+    """dvm_is_in_frustum_cam: is_in_frustum with the projection of a CameraModel (F.fx, fy, cx, cy are not read)."""
+    P = np.ascontiguousarray(P, np.float32); normal = np.ascontiguousarray(normal, np.float32)
+    min_dist = np.ascontiguousarray(min_dist, np.float32); max_dist = np.ascontiguousarray(max_dist, np.float32)
+    out = np.zeros(len(P), TRACK_DTYPE)
+    fn = lib().dvm_is_in_frustum_cam
+    fn.restype = C.c_int32; fn.argtypes = None
+    check(fn(C.byref(F), None if model is None else C.byref(model), _p(P), _p(normal), _p(min_dist), _p(max_dist), C.c_int32(len(P)),
+             C.c_float(float(viewing_cos_limit)), _p(out), C.c_int32(0), None))
+    return out
+
+
 def is_in_frustum(F: "FrustumFrame", P, normal, min_dist, max_dist, viewing_cos_limit=0.5):
     """Frame::isInFrustum for an array of map points; returns a TRACK_DTYPE array."""
     P = np.ascontiguousarray(P, np.float32); normal = np.ascontiguousarray(normal, np.float32)
@@ -890,6 +963,30 @@ def search_by_projection_frames(kps_c, desc_c, mp_c, Tcw, K, bounds, scale_facto
     n = H.dvmh_search_by_projection_frames(device, len(kps_c), _p(kps_c), _p(desc_c), _p(mp), *[_p(a) for a in f],
                                            len(f[3]), len(kps_l), _p(kps_l), _p(mp_l), None if outl is None else _p(outl),
                                            _p(mps), float(th), int(check_ori), C.byref(req))
+    if n < 0:
+        check(n)
+    return n, mp, req.value
+
+
+def search_by_projection_frames_cam(kps_c, desc_c, mp_c, Tcw, model, bounds, scale_factors, kps_l, mp_l, outlier_l, mps, th,
+                                    check_ori=True, device=0):
+    """dvmh_search_by_projection_frames_cam: search_by_projection_frames with the query projection of a CameraModel in place of K.
+    Returns (nmatches, updated mvpMapPoints of the current frame, #host re-queries)."""
+    H = host_lib()
+    kps_c = np.ascontiguousarray(kps_c, KP_DTYPE); kps_l = np.ascontiguousarray(kps_l, KP_DTYPE)
+    desc_c = np.ascontiguousarray(desc_c, np.uint8)
+    mp = np.array(mp_c, np.int32, copy=True)
+    mp_l = np.ascontiguousarray(mp_l, np.int32)
+    outl = None if outlier_l is None else np.ascontiguousarray(outlier_l, np.uint8)
+    T, b, sf = [np.ascontiguousarray(a, np.float32) for a in (Tcw, bounds, scale_factors)]
+    assert T.shape == (7,)
+    mps = np.ascontiguousarray(mps, MAP_POINT_DTYPE)
+    req = C.c_int32(0)
+    fn = H.dvmh_search_by_projection_frames_cam
+    fn.restype = C.c_int32; fn.argtypes = None
+    n = fn(C.c_int32(device), C.c_int32(len(kps_c)), _p(kps_c), _p(desc_c), _p(mp), _p(T), None if model is None else C.byref(model), _p(b), _p(sf),
+           C.c_int32(len(sf)), C.c_int32(len(kps_l)), _p(kps_l), _p(mp_l), None if outl is None else _p(outl), _p(mps), C.c_float(float(th)),
+           C.c_int32(int(check_ori)), C.byref(req))
     if n < 0:
         check(n)
     return n, mp, req.value
@@ -1731,19 +1828,20 @@ def search_by_sim3(KF1, KF2, P1, P2, matches12, idx_in_kf2, S12, th, device=0):
     return n, m
 
 
-def project_search(grid, cam, pts, th, scale_factors, skip=None, gate_inv_sigma2=None, gate=5.99, valid=None):
-    """dvm_project_search on a FrameGrid slot 0.  cam: dict(Tcw (7-float SE3f), Ow, K, bounds, log_scale_factor[, sim3_pair, S2]).
-    Returns (matches, proj)."""
-    class _Cam(C.Structure):
-        _fields_ = [("Tcw", C.c_float * 7), ("Ow", C.c_float * 3), ("K", C.c_float * 4), ("b", C.c_float * 4),
-                    ("lsf", C.c_float), ("nl", C.c_int32), ("sim3_pair", C.c_int32), ("S2", C.c_float * 7)]
+class _KfCamera(C.Structure):   # == dvm_kf_camera
+    _fields_ = [("Tcw", C.c_float * 7), ("Ow", C.c_float * 3), ("K", C.c_float * 4), ("b", C.c_float * 4),
+                ("lsf", C.c_float), ("nl", C.c_int32), ("sim3_pair", C.c_int32), ("S2", C.c_float * 7)]
+
+
+def _project_search_call(fn, grid, cam, model_args, pts, th, scale_factors, skip, gate_inv_sigma2, gate, valid):
+    """dvm_project_search / dvm_project_search_cam on a FrameGrid slot 0: packs the camera dict and the points; model_args goes behind cam."""
     sf = np.ascontiguousarray(scale_factors, np.float32)
-    c = _Cam()
+    c = _KfCamera()
     c.Tcw = (C.c_float * 7)(*np.asarray(cam["Tcw"], np.float32).reshape(7))
     c.sim3_pair = int(cam.get("sim3_pair", 0))
     if cam.get("S2") is not None:
         c.S2 = (C.c_float * 7)(*np.asarray(cam["S2"], np.float32).reshape(7))
-    c.Ow = (C.c_float * 3)(*np.asarray(cam["Ow"], np.float32)); c.K = (C.c_float * 4)(*np.asarray(cam["K"], np.float32))
+    c.Ow = (C.c_float * 3)(*np.asarray(cam["Ow"], np.float32)); c.K = (C.c_float * 4)(*np.asarray(cam.get("K", (0, 0, 0, 0)), np.float32))
     c.b = (C.c_float * 4)(*np.asarray(cam["bounds"], np.float32)); c.lsf = float(cam["log_scale_factor"]); c.nl = len(sf)
     P, keep = map_points_view(pts)
     n = P.n
@@ -1753,12 +1851,23 @@ def project_search(grid, cam, pts, th, scale_factors, skip=None, gate_inv_sigma2
         sk = np.zeros(grid.capacity, np.uint8); sk[:len(skip)] = skip
     gi = None if gate_inv_sigma2 is None else np.ascontiguousarray(gate_inv_sigma2, np.float32)
     va = None if valid is None else np.ascontiguousarray(valid, np.uint8)
-    fn = lib().dvm_project_search
     fn.restype = C.c_int32; fn.argtypes = None
     vp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
-    check(fn(grid.h, C.c_int32(0), vp(sk), C.byref(c), C.c_void_p(P.pos), C.c_void_p(P.normal), C.c_void_p(P.min_dist), C.c_void_p(P.max_dist),
+    check(fn(grid.h, C.c_int32(0), vp(sk), C.byref(c), *model_args, C.c_void_p(P.pos), C.c_void_p(P.normal), C.c_void_p(P.min_dist), C.c_void_p(P.max_dist),
              C.c_void_p(P.desc), vp(va), C.c_int32(n), C.c_float(th), vp(sf), vp(gi), C.c_double(gate), vp(out), vp(proj), C.c_int32(0), None))
     return out[:n], proj[:n]
+
+
+def project_search(grid, cam, pts, th, scale_factors, skip=None, gate_inv_sigma2=None, gate=5.99, valid=None):
+    """dvm_project_search on a FrameGrid slot 0.  cam: dict(Tcw (7-float SE3f), Ow, K, bounds, log_scale_factor[, sim3_pair, S2]).
+    Returns (matches, proj)."""
+    return _project_search_call(lib().dvm_project_search, grid, cam, (), pts, th, scale_factors, skip, gate_inv_sigma2, gate, valid)
+
+
+def project_search_cam(grid, cam, model, pts, th, scale_factors, skip=None, gate_inv_sigma2=None, gate=5.99, valid=None):
+    """dvm_project_search_cam: project_search with the projection of a CameraModel (cam["K"] is not read and may be absent)."""
+    return _project_search_call(lib().dvm_project_search_cam, grid, cam, (None if model is None else C.byref(model),), pts, th, scale_factors, skip,
+                                gate_inv_sigma2, gate, valid)
 
 
 def bowdb_query_raw(bows, q_ids, q_vals, erase=(), device=0):

@@ -198,6 +198,11 @@ void ba_launch_sim3_hypotheses(hipStream_t s, const float* P1c, const float* P2c
 void ba_launch_pose_optimize(hipStream_t s, const double* pose_in, const double* Xw, const double* obs, const double* info,
                              const int32_t* n_per_frame, int stride, int batch, double fx, double fy, double cx, double cy,
                              double* pose_out, uint8_t* outlier, int32_t* n_inliers, double* chi_scratch);
+// the same on a KannalaBrandt8 camera (p = mvParameters, camera_model.h): k_pose_optimize_kb8, which keeps 256 x 5 correspondences of a
+// frame in registers as the pinhole kernel does
+void ba_launch_pose_optimize_kb8(hipStream_t s, const double* pose_in, const double* Xw, const double* obs, const double* info,
+                                 const int32_t* n_per_frame, int stride, int batch, const float* p, double* pose_out, uint8_t* outlier,
+                                 int32_t* n_inliers, double* chi_scratch);
 
 }  // namespace dvm
 

@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "ba_kernels.h"
+#include "camera_model.h"
 #include "f64_spec.h"
 #include "jacobi4.h"
 
@@ -2531,18 +2532,41 @@ __device__ __forceinline__ double block_sum_one(double v, double* part4) {
 // Newton steps, as the tile Cholesky does) instead of 27 double-precision divisions and 6 square roots on a single lane.
 // (Measured, one frame of 300 matches: 363 us per call before, of which ~2.8 us per LM trial were the divisions.)
 constexpr int kPoseEdgesPerThread = 5;
+// KannalaBrandt8: its Jacobian needs 78 more registers than the pinhole's six values, and 5 still does not spill (docs/NOTEBOOK.md section 16)
+constexpr int kPoseEdgesPerThreadKB8 = 5;
 #ifdef DVM_POSE_PROF   // make EXTRA=-DDVM_POSE_PROF: per-phase clocks of workgroup 0 (dvm_debug_pose_prof), measurement builds only
 __device__ unsigned long long g_pose_prof[16];
 #define POSE_T(k) do { if (tid == 0 && blockIdx.x == 0) { const unsigned long long now_ = wall_clock64(); g_pose_prof[k] += now_ - pose_last_; pose_last_ = now_; } } while (0)
 #else
 #define POSE_T(k) do {} while (0)
 #endif
-__global__ void __launch_bounds__(256) k_pose_optimize(const double* __restrict__ pose_in, const double* __restrict__ Xw,
-                                                       const double* __restrict__ obs, const double* __restrict__ info,
-                                                       const int32_t* __restrict__ n_per_frame, int stride, double fx,
-                                                       double fy, double cx, double cy, double* __restrict__ pose_out,
-                                                       uint8_t* __restrict__ outlier, int32_t* __restrict__ n_inliers,
-                                                       double* __restrict__ chi_scratch) {
+// The camera of the frame: what the `edge` of k_pose_optimize asks of it is the projection (the residual) and MINUS the projection's
+// Jacobian (EdgeSE3ProjectXYZOnlyPose::linearizeOplus, OptimizableTypes.cpp:51-63: -projectJac(xyz_trans) * SE3deriv).
+struct PoseCamPinhole {   // Pinhole::project / projectJac: four doubles, laid out as the four scalar arguments they replace
+  double fx, fy, cx, cy;
+  __device__ __forceinline__ void project(double x, double y, double z, double& u, double& v) const { u = fx * x / z + cx; v = fy * y / z + cy; }
+  __device__ __forceinline__ void neg_jac(double x, double y, double z, double* J) const {
+    J[0] = -(fx / z); J[1] = 0; J[2] = fx * x / (z * z); J[3] = 0; J[4] = -(fy / z); J[5] = fy * y / (z * z);
+  }
+};
+struct PoseCamKB8 {       // KannalaBrandt8 (camera_model.h): mvParameters as the reference stores them
+  float p[8];
+  __device__ __forceinline__ void project(double x, double y, double z, double& u, double& v) const { dvm_cam::kb8_project(p, x, y, z, u, v); }
+  __device__ __forceinline__ void neg_jac(double x, double y, double z, double* J) const {
+    dvm_cam::kb8_project_jac(p, x, y, z, J);
+#pragma unroll
+    for (int i = 0; i < 6; i++) J[i] = -J[i];
+  }
+};
+// The body of k_pose_optimize, common to every camera: LM control, speculative linearisation, the 28-value reduction, the 6x6 solve and
+// the four rounds; the camera enters `edge` and `fresh` through project / neg_jac only.  EPT: correspondences a thread keeps in
+// registers (kPoseEdgesPerThread for the pinhole camera, kPoseEdgesPerThreadKB8 for KannalaBrandt8).
+template <class CAM, int EPT>
+__device__ __forceinline__ void pose_optimize_block(const double* __restrict__ pose_in, const double* __restrict__ Xw,
+                                                    const double* __restrict__ obs, const double* __restrict__ info,
+                                                    const int32_t* __restrict__ n_per_frame, int stride, const CAM cam,
+                                                    double* __restrict__ pose_out, uint8_t* __restrict__ outlier,
+                                                    int32_t* __restrict__ n_inliers, double* __restrict__ chi_scratch) {
   __shared__ double s_park[256 * 29];
   __shared__ double s_part[4 * 28];
   __shared__ double s_sum[28];
@@ -2561,7 +2585,6 @@ __global__ void __launch_bounds__(256) k_pose_optimize(const double* __restrict_
   double* last_chi = chi_scratch + (size_t)f * stride;  // e->chi2() as g2o reports it (last evaluation): edges beyond the register-resident ones
   const double delta = (double)sqrtf(5.991f);
   const float chi2Mono = 5.991f;
-  constexpr int EPT = kPoseEdgesPerThread;
   if (tid < 7) {
     double v = pose_in[7 * (size_t)f + tid];
     s_T0[tid] = v;
@@ -2595,13 +2618,16 @@ __global__ void __launch_bounds__(256) k_pose_optimize(const double* __restrict_
     mat3_vec(R, Xp, Xc);
     Xc[0] += T[0]; Xc[1] += T[1]; Xc[2] += T[2];
     const double x = Xc[0], y = Xc[1], z = Xc[2];
-    const double e0 = o0 - (fx * x / z + cx), e1 = o1 - (fy * y / z + cy);
+    double pu, pv;
+    cam.project(x, y, z, pu, pv);
+    const double e0 = o0 - pu, e1 = o1 - pv;
     const double chi2 = e0 * w0 * e0 + e1 * w0 * e1;
     double r0, r1;
     robustify(chi2, robust_on ? delta : 0.0, r0, r1);
     a.v[27] += r0;
     if (jac) {
-      const double J[6] = {-(fx / z), 0, fx * x / (z * z), 0, -(fy / z), fy * y / (z * z)};
+      double J[6];
+      cam.neg_jac(x, y, z, J);
       const double S[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
       double B[12];
 #pragma unroll
@@ -2786,7 +2812,9 @@ __global__ void __launch_bounds__(256) k_pose_optimize(const double* __restrict_
         double Xc[3];
         mat3_vec(R, Xp, Xc);
         Xc[0] += s_T[0]; Xc[1] += s_T[1]; Xc[2] += s_T[2];
-        const double e0 = o0 - (fx * Xc[0] / Xc[2] + cx), e1 = o1 - (fy * Xc[1] / Xc[2] + cy);
+        double pu, pv;
+        cam.project(Xc[0], Xc[1], Xc[2], pu, pv);
+        const double e0 = o0 - pu, e1 = o1 - pv;
         return e0 * w0 * e0 + e1 * w0 * e1;
       };
 #pragma unroll
@@ -2820,6 +2848,24 @@ __global__ void __launch_bounds__(256) k_pose_optimize(const double* __restrict_
   if (tid < 7) pose_out[7 * (size_t)f + tid] = s_T[tid];
   if (tid == 0) n_inliers[f] = N - s_nact;
 }
+// the pinhole camera: the four intrinsics travel as scalars
+__global__ void __launch_bounds__(256) k_pose_optimize(const double* __restrict__ pose_in, const double* __restrict__ Xw,
+                                                       const double* __restrict__ obs, const double* __restrict__ info,
+                                                       const int32_t* __restrict__ n_per_frame, int stride, double fx,
+                                                       double fy, double cx, double cy, double* __restrict__ pose_out,
+                                                       uint8_t* __restrict__ outlier, int32_t* __restrict__ n_inliers,
+                                                       double* __restrict__ chi_scratch) {
+  pose_optimize_block<PoseCamPinhole, kPoseEdgesPerThread>(pose_in, Xw, obs, info, n_per_frame, stride, PoseCamPinhole{fx, fy, cx, cy}, pose_out, outlier,
+                                                           n_inliers, chi_scratch);
+}
+// KannalaBrandt8 (dvm_pose_optimize_cam, model 1)
+__global__ void __launch_bounds__(256) k_pose_optimize_kb8(const double* __restrict__ pose_in, const double* __restrict__ Xw,
+                                                           const double* __restrict__ obs, const double* __restrict__ info,
+                                                           const int32_t* __restrict__ n_per_frame, int stride, PoseCamKB8 cam,
+                                                           double* __restrict__ pose_out, uint8_t* __restrict__ outlier,
+                                                           int32_t* __restrict__ n_inliers, double* __restrict__ chi_scratch) {
+  pose_optimize_block<PoseCamKB8, kPoseEdgesPerThreadKB8>(pose_in, Xw, obs, info, n_per_frame, stride, cam, pose_out, outlier, n_inliers, chi_scratch);
+}
 
 #ifdef DVM_POSE_PROF
 extern "C" int dvm_debug_pose_prof(unsigned long long* out, int reset) {
@@ -2835,6 +2881,15 @@ void ba_launch_pose_optimize(hipStream_t s, const double* pose_in, const double*
                              double* pose_out, uint8_t* outlier, int32_t* n_inliers, double* chi_scratch) {
   hipLaunchKernelGGL(k_pose_optimize, dim3(batch), dim3(256), 0, s, pose_in, Xw, obs, info, n_per_frame, stride, fx, fy, cx, cy,
                      pose_out, outlier, n_inliers, chi_scratch);
+}
+// k_pose_optimize_kb8: the same body on a KannalaBrandt8 camera, p = mvParameters (dvm_pose_optimize_cam, model 1)
+void ba_launch_pose_optimize_kb8(hipStream_t s, const double* pose_in, const double* Xw, const double* obs, const double* info,
+                                 const int32_t* n_per_frame, int stride, int batch, const float* p, double* pose_out, uint8_t* outlier,
+                                 int32_t* n_inliers, double* chi_scratch) {
+  PoseCamKB8 cam;
+  for (int i = 0; i < 8; i++) cam.p[i] = p[i];
+  hipLaunchKernelGGL(k_pose_optimize_kb8, dim3(batch), dim3(256), 0, s, pose_in, Xw, obs, info, n_per_frame, stride, cam, pose_out, outlier, n_inliers,
+                     chi_scratch);
 }
 
 // ---------------------------------------------------------------------------------------- B9

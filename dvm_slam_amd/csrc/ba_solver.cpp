@@ -25,6 +25,7 @@
 #include "ba_kernels.h"
 #include "f64_spec.h"
 #include "ba_ordering.h"
+#include "camera_model.h"
 #include "chain.h"
 #include "host_stage.h"
 #include "orb_pipeline.h"  // set_error / hip_check / DVM_HIP
@@ -1140,11 +1141,12 @@ int dvm_ba_edge_chi2(dvm_ba* h, double* chi2, uint8_t* depth_positive) {
 
 void* dvm_ba_stream(dvm_ba* h) { return h ? (void*)h->stream : nullptr; }
 
-int dvm_pose_optimize(int device, const double* pose_in, const double* Xw, const double* obs, const double* inv_sigma2,
-                      const int32_t* n, int stride, int batch, const dvm_ba_camera* cam, double* pose_out,
-                      uint8_t* outlier, int32_t* n_inliers) {
+// dvm_pose_optimize and dvm_pose_optimize_cam: kb8 == nullptr runs the pinhole kernel on cam, otherwise k_pose_optimize_kb8 on kb8[0..7]
+static int pose_optimize_impl(const char* who, int device, const double* pose_in, const double* Xw, const double* obs, const double* inv_sigma2,
+                              const int32_t* n, int stride, int batch, const dvm_ba_camera* cam, const float* kb8, double* pose_out,
+                              uint8_t* outlier, int32_t* n_inliers) {
   if (!pose_in || !Xw || !obs || !inv_sigma2 || !n || !cam || !pose_out || !outlier || !n_inliers || stride < 1 || batch < 1) {
-    set_error("dvm_pose_optimize: bad arguments");
+    set_error(std::string(who) + ": bad arguments");
     return DVM_ERR_INVALID;
   }
   int ndev = 0;
@@ -1156,7 +1158,7 @@ int dvm_pose_optimize(int device, const double* pose_in, const double* Xw, const
   Stage st;   // the calling thread's staging context: one upload, one download, one synchronisation (host_stage.h)
   // A frame or a few (Tracking's per-frame call): k_pose_optimize reads every correspondence ONCE, into registers, and writes the
   // results once at the end, so the arrays stay in mapped host memory and no copy command brackets the kernel.  Beyond
-  // kPoseEdgesPerThread x 256 correspondences per frame the kernel re-reads them every iteration: copied, as large batches are.
+  // kPoseEdgesPerThread x 256 correspondences per frame (either camera) the kernel re-reads them every iteration: copied, as large batches are.
   const bool direct = S <= 1280 && B * S <= 8192;
   int iP, iX, iO, iW, iN, oP, oL, oI;
   if (direct) {
@@ -1171,11 +1173,30 @@ int dvm_pose_optimize(int device, const double* pose_in, const double* Xw, const
   const int sC = st.scratch(B * S * 8);
   int rc = st.upload();
   if (rc != DVM_OK) return rc;
-  ba_launch_pose_optimize(st.stream(), st.ptr<double>(iP), st.ptr<double>(iX), st.ptr<double>(iO), st.ptr<double>(iW), st.ptr<int32_t>(iN), stride,
-                          batch, cam->fx, cam->fy, cam->cx, cam->cy, st.ptr<double>(oP), st.ptr<uint8_t>(oL), st.ptr<int32_t>(oI),
-                          st.ptr<double>(sC));
+  if (kb8)
+    ba_launch_pose_optimize_kb8(st.stream(), st.ptr<double>(iP), st.ptr<double>(iX), st.ptr<double>(iO), st.ptr<double>(iW), st.ptr<int32_t>(iN), stride,
+                                batch, kb8, st.ptr<double>(oP), st.ptr<uint8_t>(oL), st.ptr<int32_t>(oI), st.ptr<double>(sC));
+  else
+    ba_launch_pose_optimize(st.stream(), st.ptr<double>(iP), st.ptr<double>(iX), st.ptr<double>(iO), st.ptr<double>(iW), st.ptr<int32_t>(iN), stride,
+                            batch, cam->fx, cam->fy, cam->cx, cam->cy, st.ptr<double>(oP), st.ptr<uint8_t>(oL), st.ptr<int32_t>(oI),
+                            st.ptr<double>(sC));
   rc = hip_check(hipGetLastError(), "pose_optimize launch");
   return rc == DVM_OK ? st.download() : rc;
+}
+
+int dvm_pose_optimize(int device, const double* pose_in, const double* Xw, const double* obs, const double* inv_sigma2,
+                      const int32_t* n, int stride, int batch, const dvm_ba_camera* cam, double* pose_out,
+                      uint8_t* outlier, int32_t* n_inliers) {
+  return pose_optimize_impl("dvm_pose_optimize", device, pose_in, Xw, obs, inv_sigma2, n, stride, batch, cam, nullptr, pose_out, outlier, n_inliers);
+}
+
+int dvm_pose_optimize_cam(int device, const double* pose_in, const double* Xw, const double* obs, const double* inv_sigma2,
+                          const int32_t* n, int stride, int batch, const dvm_camera_model* model, double* pose_out,
+                          uint8_t* outlier, int32_t* n_inliers) {
+  if (!model || !dvm_cam::model_ok(model->model, model->p)) { set_error("dvm_pose_optimize_cam: NULL model, unknown model or zero focal length"); return DVM_ERR_INVALID; }
+  const dvm_ba_camera cam = {(double)model->p[0], (double)model->p[1], (double)model->p[2], (double)model->p[3], 0.0};
+  return pose_optimize_impl("dvm_pose_optimize_cam", device, pose_in, Xw, obs, inv_sigma2, n, stride, batch, &cam,
+                            model->model == dvm_cam::kKannalaBrandt8 ? model->p : nullptr, pose_out, outlier, n_inliers);
 }
 
 int dvm_optimize_sim3(int device, double* S12, int fix_scale, const double* P1c, const double* P2c, const double* obs1,

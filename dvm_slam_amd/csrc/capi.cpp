@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/dvmslam_hip.h"
+#include "camera_model.h"
 #include "chain.h"
 #include "match_kernels.h"
 #include "orb_pipeline.h"
@@ -507,17 +508,25 @@ int dvm_match_window(const dvm_frame* train, int slot, const uint8_t* skip, cons
   return dvm_match_window_top2(train, slot, skip, qdesc, qx, qy, qr, qmin, qmax, nq, d_nq, out, nullptr, on_device, stream);
 }
 
-int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const float* normal, const float* min_dist,
-                      const float* max_dist, int n, float viewing_cos_limit, dvm_track_point* out, int on_device, void* stream) {
+// dvm_is_in_frustum and dvm_is_in_frustum_cam: kb8 == nullptr launches the pinhole kernel on F's intrinsics, otherwise k_is_in_frustum_kb8
+static int is_in_frustum_impl(const dvm_frustum_frame* frame, const float* kb8, const float* P, const float* normal, const float* min_dist,
+                              const float* max_dist, int n, float viewing_cos_limit, dvm_track_point* out, int on_device, void* stream) {
   static_assert(sizeof(dvm_frustum_frame) == sizeof(FrustumFrame) && sizeof(dvm_track_point) == sizeof(TrackPoint), "layout");
+  static_assert(sizeof(dvm_camera_model) == 36 && sizeof(CamParams) == 32, "layout");
   if (!frame || n < 0) return DVM_ERR_INVALID;
   if (n == 0) return DVM_OK;
   if (!P || !normal || !min_dist || !max_dist || !out) return DVM_ERR_INVALID;
   { const int rc = need_any_device(); if (rc != DVM_OK) return rc; }
   FrustumFrame F;
   std::memcpy(&F, frame, sizeof(F));
+  CamParams K{};
+  if (kb8) std::memcpy(K.p, kb8, sizeof(K.p));
+  auto launch = [&](hipStream_t s, const float* dP, const float* dN, const float* dmin, const float* dmax, TrackPoint* dout) {
+    if (kb8) launch_is_in_frustum_kb8(s, F, K, dP, dN, dmin, dmax, n, viewing_cos_limit, dout);
+    else launch_is_in_frustum(s, F, dP, dN, dmin, dmax, n, viewing_cos_limit, dout);
+  };
   if (on_device) {
-    launch_is_in_frustum((hipStream_t)stream, F, P, normal, min_dist, max_dist, n, viewing_cos_limit, reinterpret_cast<TrackPoint*>(out));
+    launch((hipStream_t)stream, P, normal, min_dist, max_dist, reinterpret_cast<TrackPoint*>(out));
     return hip_check(hipGetLastError(), "is_in_frustum launch");
   }
   const size_t N = (size_t)n;
@@ -526,10 +535,23 @@ int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const floa
             oT = st.out(out, N * sizeof(TrackPoint));
   int rc = st.upload();
   if (rc != DVM_OK) return rc;
-  launch_is_in_frustum(nullptr, F, st.ptr<float>(iP), st.ptr<float>(iN), st.ptr<float>(imin), st.ptr<float>(imax), n, viewing_cos_limit,
-                       st.ptr<TrackPoint>(oT));
+  launch(nullptr, st.ptr<float>(iP), st.ptr<float>(iN), st.ptr<float>(imin), st.ptr<float>(imax), st.ptr<TrackPoint>(oT));
   rc = hip_check(hipGetLastError(), "launch");
   return rc == DVM_OK ? st.download() : rc;
+}
+int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const float* normal, const float* min_dist,
+                      const float* max_dist, int n, float viewing_cos_limit, dvm_track_point* out, int on_device, void* stream) {
+  return is_in_frustum_impl(frame, nullptr, P, normal, min_dist, max_dist, n, viewing_cos_limit, out, on_device, stream);
+}
+int dvm_is_in_frustum_cam(const dvm_frustum_frame* frame, const dvm_camera_model* model, const float* P, const float* normal,
+                          const float* min_dist, const float* max_dist, int n, float viewing_cos_limit, dvm_track_point* out, int on_device,
+                          void* stream) {
+  if (!frame || n < 0) return DVM_ERR_INVALID;
+  if (!model || !dvm_cam::model_ok(model->model, model->p)) { set_error("dvm_is_in_frustum_cam: NULL model, unknown model or zero focal length"); return DVM_ERR_INVALID; }
+  dvm_frustum_frame fr = *frame;   // the model's p[0..3] stand for the frame's fx, fy, cx, cy
+  fr.fx = model->p[0]; fr.fy = model->p[1]; fr.cx = model->p[2]; fr.cy = model->p[3];
+  return is_in_frustum_impl(&fr, model->model == dvm_cam::kKannalaBrandt8 ? model->p : nullptr, P, normal, min_dist, max_dist, n, viewing_cos_limit, out,
+                            on_device, stream);
 }
 
 int dvm_triangulate_matches(const dvm_tri_pair* pair, const dvm_keypoint* kps1, int n1, const dvm_keypoint* kps2, int n2,
@@ -630,10 +652,11 @@ int dvm_match_lists(const uint8_t* tdesc, int nt, const uint8_t* qdesc, int nq, 
   return rc == DVM_OK ? st.download() : rc;
 }
 
-int dvm_project_search(const dvm_frame* train, int slot, const uint8_t* skip, const dvm_kf_camera* cam, const float* P,
-                       const float* normal, const float* min_dist, const float* max_dist, const uint8_t* desc,
-                       const uint8_t* valid, int n, float th, const float* scale_factors, const float* gate_inv_sigma2,
-                       double gate, dvm_match* out, dvm_projection* proj, int on_device, void* stream) {
+// dvm_project_search and dvm_project_search_cam: kb8 == nullptr launches the pinhole kernel on cam's intrinsics, otherwise k_project_search_kb8
+static int project_search_impl(const dvm_frame* train, int slot, const uint8_t* skip, const dvm_kf_camera* cam, const float* kb8, const float* P,
+                               const float* normal, const float* min_dist, const float* max_dist, const uint8_t* desc,
+                               const uint8_t* valid, int n, float th, const float* scale_factors, const float* gate_inv_sigma2,
+                               double gate, dvm_match* out, dvm_projection* proj, int on_device, void* stream) {
   static_assert(sizeof(dvm_kf_camera) + 4 == sizeof(ProjectCam) && sizeof(dvm_projection) == sizeof(Projection), "layout");
   if (!train || slot < 0 || slot >= train->slots || !cam || n < 0) return DVM_ERR_INVALID;
   if (n == 0) return DVM_OK;
@@ -644,9 +667,16 @@ int dvm_project_search(const dvm_frame* train, int slot, const uint8_t* skip, co
   ProjectCam C;
   std::memcpy(&C, cam, sizeof(dvm_kf_camera));
   C.th = th;
+  CamParams K{};
+  if (kb8) std::memcpy(K.p, kb8, sizeof(K.p));
+  auto launch = [&](hipStream_t s, const uint8_t* dskip, const float* dP, const float* dN, const float* dmin, const float* dmax, const uint8_t* ddesc,
+                    const uint8_t* dvalid, const float* dsf, const float* dgate, dvm_match_pod* dout, Projection* dproj) {
+    if (kb8) launch_project_search_kb8(s, train->view, slot, dskip, C, K, dP, dN, dmin, dmax, ddesc, dvalid, n, dsf, dgate, gate, dout, dproj);
+    else launch_project_search(s, train->view, slot, dskip, C, dP, dN, dmin, dmax, ddesc, dvalid, n, dsf, dgate, gate, dout, dproj);
+  };
   if (on_device) {
-    launch_project_search((hipStream_t)stream, train->view, slot, skip, C, P, normal, min_dist, max_dist, desc, valid, n,
-                          scale_factors, gate_inv_sigma2, gate, reinterpret_cast<dvm_match_pod*>(out), reinterpret_cast<Projection*>(proj));
+    launch((hipStream_t)stream, skip, P, normal, min_dist, max_dist, desc, valid, scale_factors, gate_inv_sigma2, reinterpret_cast<dvm_match_pod*>(out),
+           reinterpret_cast<Projection*>(proj));
     return hip_check(hipGetLastError(), "project_search launch");
   }
   Stage st;
@@ -656,11 +686,28 @@ int dvm_project_search(const dvm_frame* train, int slot, const uint8_t* skip, co
             iK = st.in(skip, (size_t)train->cap), oM = st.out(out, N * sizeof(dvm_match)), oP = st.out(proj, N * sizeof(dvm_projection));
   rc = st.upload();
   if (rc != DVM_OK) return rc;
-  launch_project_search(nullptr, train->view, slot, st.ptr<uint8_t>(iK), C, st.ptr<float>(iP), st.ptr<float>(iN), st.ptr<float>(imin),
-                        st.ptr<float>(imax), st.ptr<uint8_t>(iD), st.ptr<uint8_t>(iV), n, st.ptr<float>(iS), st.ptr<float>(iG), gate,
-                        st.ptr<dvm_match_pod>(oM), st.ptr<Projection>(oP));
+  launch(nullptr, st.ptr<uint8_t>(iK), st.ptr<float>(iP), st.ptr<float>(iN), st.ptr<float>(imin), st.ptr<float>(imax), st.ptr<uint8_t>(iD),
+         st.ptr<uint8_t>(iV), st.ptr<float>(iS), st.ptr<float>(iG), st.ptr<dvm_match_pod>(oM), st.ptr<Projection>(oP));
   rc = hip_check(hipGetLastError(), "project_search launch");
   return rc == DVM_OK ? st.download() : rc;
+}
+int dvm_project_search(const dvm_frame* train, int slot, const uint8_t* skip, const dvm_kf_camera* cam, const float* P,
+                       const float* normal, const float* min_dist, const float* max_dist, const uint8_t* desc,
+                       const uint8_t* valid, int n, float th, const float* scale_factors, const float* gate_inv_sigma2,
+                       double gate, dvm_match* out, dvm_projection* proj, int on_device, void* stream) {
+  return project_search_impl(train, slot, skip, cam, nullptr, P, normal, min_dist, max_dist, desc, valid, n, th, scale_factors, gate_inv_sigma2, gate, out, proj,
+                             on_device, stream);
+}
+int dvm_project_search_cam(const dvm_frame* train, int slot, const uint8_t* skip, const dvm_kf_camera* cam, const dvm_camera_model* model,
+                           const float* P, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* desc,
+                           const uint8_t* valid, int n, float th, const float* scale_factors, const float* gate_inv_sigma2, double gate,
+                           dvm_match* out, dvm_projection* proj, int on_device, void* stream) {
+  if (!train || slot < 0 || slot >= train->slots || !cam || n < 0) return DVM_ERR_INVALID;
+  if (!model || !dvm_cam::model_ok(model->model, model->p)) { set_error("dvm_project_search_cam: NULL model, unknown model or zero focal length"); return DVM_ERR_INVALID; }
+  dvm_kf_camera kc = *cam;   // the model's p[0..3] stand for the keyframe's fx, fy, cx, cy
+  kc.fx = model->p[0]; kc.fy = model->p[1]; kc.cx = model->p[2]; kc.cy = model->p[3];
+  return project_search_impl(train, slot, skip, &kc, model->model == dvm_cam::kKannalaBrandt8 ? model->p : nullptr, P, normal, min_dist, max_dist, desc, valid, n,
+                             th, scale_factors, gate_inv_sigma2, gate, out, proj, on_device, stream);
 }
 
 int dvm_match_triangulation(const uint8_t* desc1, const dvm_keypoint* kps1, int n1, const int32_t* qidx, int nq,

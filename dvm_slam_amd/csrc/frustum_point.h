@@ -4,14 +4,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "camera_model.h"
 #include "match_kernels.h"   // FrustumFrame, TrackPoint
 #include "pose_f32.h"
 
 namespace dvm {
 
 // p = GetWorldPos(), n = GetNormal(), min_dist / max_dist = mfMinDistance / mfMaxDistance
+// MODEL: the camera behind mpCamera->project (Frame.cc:594).  The pinhole instantiation is what every chain calls; KannalaBrandt8
+// (k_is_in_frustum_kb8 only) reads mvParameters from kb8 (camera_model.h) and none of F.fx, fy, cx, cy.
+template <int MODEL = dvm_cam::kPinhole>
 __device__ __forceinline__ TrackPoint frustum_point(const FrustumFrame& F, float p0, float p1, float p2, float n0, float n1, float n2,
-                                                    float min_dist, float max_dist, float cos_limit) {
+                                                    float min_dist, float max_dist, float cos_limit, const float* kb8 = nullptr) {
   TrackPoint o;
   o.in_view = 0; o.proj_x = -1; o.proj_y = -1; o.proj_xr = 0; o.depth = 0; o.level = -1; o.view_cos = 0;
   // Pc = mRcw * P + mtcw (Frame.cc:585): Eigen's 3x3 * 3x1 coefficient is a0 + (a1 + a2)
@@ -21,7 +25,9 @@ __device__ __forceinline__ TrackPoint frustum_point(const FrustumFrame& F, float
   const float Pc_dist = sqrtf(dvm_pose::sum3(X * X, Y * Y, Z * Z));
   const float invz = 1.0f / Z;
   bool ok = !(Z < 0.0f);
-  const float u = F.fx * X / Z + F.cx, v = F.fy * Y / Z + F.cy;
+  float u, v;
+  if constexpr (MODEL == dvm_cam::kKannalaBrandt8) dvm_cam::kb8_project(kb8, X, Y, Z, u, v);
+  else { u = F.fx * X / Z + F.cx; v = F.fy * Y / Z + F.cy; }
   ok = ok && !(u < F.min_x || u > F.max_x) && !(v < F.min_y || v > F.max_y);
   if (ok) {
     o.proj_x = u; o.proj_y = v;

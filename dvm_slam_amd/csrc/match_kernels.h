@@ -82,6 +82,9 @@ struct Projection {  // == dvm_projection
   float u, v, radius;
   int32_t level;
 };
+struct CamParams {  // == dvm_camera_model::p: fx, fy, cx, cy, k1, k2, k3, k4 (camera_model.h)
+  float p[8];
+};
 struct TriGeom {
   float F12[9], ep[2];
   int32_t coarse, th_low;
@@ -100,6 +103,13 @@ void launch_triangulate_matches(hipStream_t s, const TriPair& P, const dvm_keypo
                                 const float* sf2, float* x3D, int32_t* status);
 void launch_is_in_frustum(hipStream_t s, const FrustumFrame& F, const float* P, const float* normal, const float* min_dist,
                           const float* max_dist, int n, float cos_limit, TrackPoint* out);
+// the two above for a KannalaBrandt8 camera (K = mvParameters): the pinhole intrinsics of F / C are not read
+void launch_is_in_frustum_kb8(hipStream_t s, const FrustumFrame& F, const CamParams& K, const float* P, const float* normal, const float* min_dist,
+                              const float* max_dist, int n, float cos_limit, TrackPoint* out);
+void launch_project_search_kb8(hipStream_t s, const FrameView& F, int slot, const uint8_t* skip, const ProjectCam& C, const CamParams& K, const float* P,
+                               const float* normal, const float* min_dist, const float* max_dist, const uint8_t* desc,
+                               const uint8_t* valid, int n, const float* scale_factors, const float* gate_inv_sigma2, double gate,
+                               dvm_match_pod* out, Projection* proj);
 void launch_frame_build(hipStream_t s, const dvm_keypoint_pod* kps, int64_t kps_stride, const uint8_t* desc,
                         int64_t desc_stride, int n, const int32_t* d_n, const FrameView& F, int first_slot, int count);
 void launch_match_window(hipStream_t s, const FrameView& F, int slot, const uint8_t* skip, const uint8_t* qdesc,

@@ -243,19 +243,20 @@ __global__ void __launch_bounds__(256) k_match_lists(const uint8_t* __restrict__
 // -- depth > 0, KeyFrame::IsInImage, distance inside the scale-invariance range, viewing angle < 60 deg
 // (PO.Pn >= 0.5 dist), MapPoint::PredictScale, radius = th * scaleFactor[level], candidates of octave [level-1, level],
 // optional per-candidate chi2 gate (Fuse).  One DPP row (16 lanes) per map point; every lane repeats the projection.
-__global__ void __launch_bounds__(256) k_project_search(FrameView FB, int slot, const uint8_t* __restrict__ skip, ProjectCam C,
-                                                        const float* __restrict__ P, const float* __restrict__ normal,
-                                                        const float* __restrict__ min_dist, const float* __restrict__ max_dist,
-                                                        const uint8_t* __restrict__ desc, const uint8_t* __restrict__ valid, int n,
-                                                        const float* __restrict__ scale_factors,
-                                                        const float* __restrict__ gate_inv_sigma2, double gate,
-                                                        dvm_match_pod* __restrict__ out, Projection* __restrict__ proj) {
+// MODEL: the camera behind pCamera->project (project_row<MODEL>); kb8 = mvParameters for KannalaBrandt8, unused for the pinhole camera.
+template <int MODEL>
+__device__ __forceinline__ void project_search_row(const FrameView& FB, int slot, const uint8_t* __restrict__ skip, const ProjectCam& C,
+                                                   const float* kb8, const float* __restrict__ P, const float* __restrict__ normal,
+                                                   const float* __restrict__ min_dist, const float* __restrict__ max_dist,
+                                                   const uint8_t* __restrict__ desc, const uint8_t* __restrict__ valid, int n,
+                                                   const float* __restrict__ scale_factors, const float* __restrict__ gate_inv_sigma2,
+                                                   double gate, dvm_match_pod* __restrict__ out, Projection* __restrict__ proj) {
   const int lane = threadIdx.x & 15;
   const int i = blockIdx.x * 16 + (threadIdx.x >> 4);
   if (i >= n) return;
   const FrameView F = FB.slot(slot);
-  const ProjectRow R = project_row(F, skip, C, C.th, P, normal, min_dist, max_dist, desc, valid == nullptr || valid[i] != 0, i, scale_factors,
-                                   gate_inv_sigma2, gate, lane);
+  const ProjectRow R = project_row<MODEL>(F, skip, C, C.th, P, normal, min_dist, max_dist, desc, valid == nullptr || valid[i] != 0, i, scale_factors,
+                                          gate_inv_sigma2, gate, lane, kb8);
   const uint32_t k1 = R.k1, k2 = R.k2;
   if (lane == 0) {
     dvm_match_pod m;
@@ -272,6 +273,26 @@ __global__ void __launch_bounds__(256) k_project_search(FrameView FB, int slot, 
       proj[i] = pr;
     }
   }
+}
+__global__ void __launch_bounds__(256) k_project_search(FrameView FB, int slot, const uint8_t* __restrict__ skip, ProjectCam C,
+                                                        const float* __restrict__ P, const float* __restrict__ normal,
+                                                        const float* __restrict__ min_dist, const float* __restrict__ max_dist,
+                                                        const uint8_t* __restrict__ desc, const uint8_t* __restrict__ valid, int n,
+                                                        const float* __restrict__ scale_factors,
+                                                        const float* __restrict__ gate_inv_sigma2, double gate,
+                                                        dvm_match_pod* __restrict__ out, Projection* __restrict__ proj) {
+  project_search_row<dvm_cam::kPinhole>(FB, slot, skip, C, nullptr, P, normal, min_dist, max_dist, desc, valid, n, scale_factors, gate_inv_sigma2, gate, out, proj);
+}
+// the same with pCamera->project of a KannalaBrandt8 camera (dvm_project_search_cam, model 1)
+__global__ void __launch_bounds__(256) k_project_search_kb8(FrameView FB, int slot, const uint8_t* __restrict__ skip, ProjectCam C, CamParams K,
+                                                            const float* __restrict__ P, const float* __restrict__ normal,
+                                                            const float* __restrict__ min_dist, const float* __restrict__ max_dist,
+                                                            const uint8_t* __restrict__ desc, const uint8_t* __restrict__ valid, int n,
+                                                            const float* __restrict__ scale_factors,
+                                                            const float* __restrict__ gate_inv_sigma2, double gate,
+                                                            dvm_match_pod* __restrict__ out, Projection* __restrict__ proj) {
+  project_search_row<dvm_cam::kKannalaBrandt8>(FB, slot, skip, C, K.p, P, normal, min_dist, max_dist, desc, valid, n, scale_factors, gate_inv_sigma2, gate, out,
+                                               proj);
 }
 
 // ORBmatcher::SearchForTriangulation inner loop (reference src/ORBmatcher.cc:905-998, monocular): query q = keypoint
@@ -377,6 +398,16 @@ __global__ void __launch_bounds__(256) k_is_in_frustum(FrustumFrame F, const flo
                          cos_limit);
 }
 
+// k_is_in_frustum with mpCamera->project of a KannalaBrandt8 camera (dvm_is_in_frustum_cam, model 1): frustum_point<KannalaBrandt8>
+__global__ void __launch_bounds__(256) k_is_in_frustum_kb8(FrustumFrame F, CamParams K, const float* __restrict__ P, const float* __restrict__ normal,
+                                                           const float* __restrict__ min_dist, const float* __restrict__ max_dist,
+                                                           int n, float cos_limit, TrackPoint* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = frustum_point<dvm_cam::kKannalaBrandt8>(F, P[3 * i], P[3 * i + 1], P[3 * i + 2], normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], min_dist[i],
+                                                   max_dist[i], cos_limit, K.p);
+}
+
 // LocalMapping::CreateNewMapPoints, the geometry of one neighbour keyframe's matches (reference src/LocalMapping.cc:598-741, monocular
 // pinhole branch; GeometricTools::Triangulate src/GeometricTools.cc:48-67): thread per match.  Parallax of the two rays, the
 // homogeneous point (null vector of the 4x4 system: eigenvector of the smallest eigenvalue of A^T A by cyclic Jacobi in double --
@@ -463,6 +494,17 @@ void launch_undistort_keypoints(hipStream_t s, const dvm_undistort::Camera& cam,
 void launch_is_in_frustum(hipStream_t s, const FrustumFrame& F, const float* P, const float* normal, const float* min_dist,
                           const float* max_dist, int n, float cos_limit, TrackPoint* out) {
   hipLaunchKernelGGL(k_is_in_frustum, dim3((n + 255) / 256), dim3(256), 0, s, F, P, normal, min_dist, max_dist, n, cos_limit, out);
+}
+void launch_is_in_frustum_kb8(hipStream_t s, const FrustumFrame& F, const CamParams& K, const float* P, const float* normal, const float* min_dist,
+                              const float* max_dist, int n, float cos_limit, TrackPoint* out) {
+  hipLaunchKernelGGL(k_is_in_frustum_kb8, dim3((n + 255) / 256), dim3(256), 0, s, F, K, P, normal, min_dist, max_dist, n, cos_limit, out);
+}
+void launch_project_search_kb8(hipStream_t s, const FrameView& F, int slot, const uint8_t* skip, const ProjectCam& C, const CamParams& K, const float* P,
+                               const float* normal, const float* min_dist, const float* max_dist, const uint8_t* desc,
+                               const uint8_t* valid, int n, const float* scale_factors, const float* gate_inv_sigma2, double gate,
+                               dvm_match_pod* out, Projection* proj) {
+  hipLaunchKernelGGL(k_project_search_kb8, dim3((n + 15) / 16), dim3(256), 0, s, F, slot, skip, C, K, P, normal, min_dist, max_dist, desc,
+                     valid, n, scale_factors, gate_inv_sigma2, gate, out, proj);
 }
 void launch_match_lists(hipStream_t s, const uint8_t* tdesc, const uint8_t* qdesc, const int32_t* off, const int32_t* cand,
                         int nq, dvm_match_pod* out) {

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "camera_model.h"
 #include "match_kernels.h"
 #include "pose_f32.h"
 
@@ -167,11 +168,16 @@ struct ProjectRow {
   float u, v, r;
   int level;
 };
+// MODEL: the camera behind pCamera->project.  The pinhole instantiation is what every chain calls; KannalaBrandt8 (k_project_search_kb8
+// only) reads mvParameters from kb8 (camera_model.h) and none of C.fx, fy, cx, cy -- except in the sim3_pair == 1 form, where the
+// reference writes the pinhole formula inline whatever the camera (ORBmatcher.cc:1401-1406) and kb8[0..3] stand for fx, fy, cx, cy.
+template <int MODEL = dvm_cam::kPinhole>
 __device__ __forceinline__ ProjectRow project_row(const FrameView& F, const uint8_t* __restrict__ skip, const ProjectCam& C, float th,
                                                   const float* __restrict__ P, const float* __restrict__ normal,
                                                   const float* __restrict__ min_dist, const float* __restrict__ max_dist,
                                                   const uint8_t* __restrict__ desc, bool ok, int i, const float* __restrict__ scale_factors,
-                                                  const float* __restrict__ gate_inv_sigma2, double gate, int lane) {
+                                                  const float* __restrict__ gate_inv_sigma2, double gate, int lane,
+                                                  const float* kb8 = nullptr) {
   float out_u = -1.f, out_v = -1.f, out_r = 0.f;
   int out_level = -1;
   const float p0 = P[3 * i], p1 = P[3 * i + 1], p2 = P[3 * i + 2];
@@ -186,8 +192,15 @@ __device__ __forceinline__ ProjectRow project_row(const FrameView& F, const uint
     dvm_pose::sim3_apply(C.q2, C.t2, pc, p2c);
     X = p2c[0]; Y = p2c[1]; Z = p2c[2];
     const float invz = (float)(1.0 / (double)Z);
-    u = C.fx * (X * invz) + C.cx;
-    v = C.fy * (Y * invz) + C.cy;
+    if constexpr (MODEL == dvm_cam::kKannalaBrandt8) {
+      u = kb8[0] * (X * invz) + kb8[2];
+      v = kb8[1] * (Y * invz) + kb8[3];
+    } else {
+      u = C.fx * (X * invz) + C.cx;
+      v = C.fy * (Y * invz) + C.cy;
+    }
+  } else if constexpr (MODEL == dvm_cam::kKannalaBrandt8) {
+    dvm_cam::kb8_project(kb8, X, Y, Z, u, v);
   } else {
     u = C.fx * X / Z + C.cx;
     v = C.fy * Y / Z + C.cy;

@@ -2,6 +2,7 @@
 #include "orb_matcher.h"
 #include "chain_handle.h"
 
+#include "../csrc/camera_model.h"
 #include "../csrc/pose_f32.h"
 #include "../csrc/rot_bin.h"
 
@@ -148,7 +149,9 @@ void BuildFrameQueries(const FrameView& Cur, const FrameView& Last, const MapPoi
     const float xc = x3Dc[0], yc = x3Dc[1], zc = x3Dc[2];
     const float invzc = (float)(1.0 / zc);
     if (invzc < 0) continue;
-    const float u = Cur.fx * xc / zc + Cur.cx, v = Cur.fy * yc / zc + Cur.cy;
+    float u, v;   // CurrentFrame.mpCamera->project(x3Dc) (:1586)
+    if (Cur.mpCamera && Cur.mpCamera->model == dvm_cam::kKannalaBrandt8) dvm_cam::kb8_project(Cur.mpCamera->p, xc, yc, zc, u, v);
+    else { u = Cur.fx * xc / zc + Cur.cx; v = Cur.fy * yc / zc + Cur.cy; }
     if (u < Cur.mnMinX || u > Cur.mnMaxX) continue;
     if (v < Cur.mnMinY || v > Cur.mnMaxY) continue;
     const int nLastOctave = Last.mvKeysUn[i].octave;
@@ -928,13 +931,16 @@ using dvm_host::KeyFrameView;
 using dvm_host::MapPointsView;
 extern "C" {
 void dvmh_set_match_pool(dvm_match_pool* pool) { dvm_host::set_match_pool(pool); }
-int dvmh_search_by_projection_frames(int device, int Nc, const dvm_keypoint* kps_c, const uint8_t* desc_c, int32_t* mp_c, const dvm_se3f* Tcw,
-                                     const float* K, const float* bounds, const float* scale_factors, int nlevels, int Nl, const dvm_keypoint* kps_l,
-                                     const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps, float th, int check_ori, int* requeried) {
+// dvmh_search_by_projection_frames and _cam: K = fx fy cx cy; model (may be NULL) sends the query projection through camera_model.h
+static int search_by_projection_frames_impl(int device, int Nc, const dvm_keypoint* kps_c, const uint8_t* desc_c, int32_t* mp_c, const dvm_se3f* Tcw,
+                                            const float* K, const dvm_camera_model* model, const float* bounds, const float* scale_factors, int nlevels,
+                                            int Nl, const dvm_keypoint* kps_l, const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps,
+                                            float th, int check_ori, int* requeried) {
   FrameView C, L;
   C.N = Nc; C.mvKeysUn = kps_c; C.mDescriptors = desc_c; C.mvpMapPoints = mp_c;
   C.Tcw = *Tcw;
   C.fx = K[0]; C.fy = K[1]; C.cx = K[2]; C.cy = K[3];
+  C.mpCamera = model;
   C.mnMinX = bounds[0]; C.mnMaxX = bounds[1]; C.mnMinY = bounds[2]; C.mnMaxY = bounds[3];
   C.mvScaleFactors = scale_factors; C.nLevels = nlevels;
   L = C;
@@ -943,6 +949,20 @@ int dvmh_search_by_projection_frames(int device, int Nc, const dvm_keypoint* kps
   const int n = m.SearchByProjection(C, L, mps, th, true);
   if (requeried) *requeried = m.last_requeried;
   return n;
+}
+int dvmh_search_by_projection_frames(int device, int Nc, const dvm_keypoint* kps_c, const uint8_t* desc_c, int32_t* mp_c, const dvm_se3f* Tcw,
+                                     const float* K, const float* bounds, const float* scale_factors, int nlevels, int Nl, const dvm_keypoint* kps_l,
+                                     const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps, float th, int check_ori, int* requeried) {
+  return search_by_projection_frames_impl(device, Nc, kps_c, desc_c, mp_c, Tcw, K, nullptr, bounds, scale_factors, nlevels, Nl, kps_l, mp_l, outlier_l, mps, th,
+                                          check_ori, requeried);
+}
+int dvmh_search_by_projection_frames_cam(int device, int Nc, const dvm_keypoint* kps_c, const uint8_t* desc_c, int32_t* mp_c, const dvm_se3f* Tcw,
+                                         const dvm_camera_model* model, const float* bounds, const float* scale_factors, int nlevels, int Nl,
+                                         const dvm_keypoint* kps_l, const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps, float th,
+                                         int check_ori, int* requeried) {
+  if (!model || !dvm_cam::model_ok(model->model, model->p)) return DVM_ERR_INVALID;
+  return search_by_projection_frames_impl(device, Nc, kps_c, desc_c, mp_c, Tcw, model->p, model->model == dvm_cam::kKannalaBrandt8 ? model : nullptr, bounds,
+                                          scale_factors, nlevels, Nl, kps_l, mp_l, outlier_l, mps, th, check_ori, requeried);
 }
 int dvmh_search_by_projection_frames_dev(int device, int Nc, const dvm_keypoint* kps_c, const uint8_t* desc_c, int32_t* mp_c, const dvm_se3f* Tcw,
                                          const float* K, const float* bounds, const float* scale_factors, int nlevels, int Nl, const dvm_keypoint* kps_l,

@@ -24,6 +24,9 @@ typedef dvmh_tracked_point TrackedPointPOD;  // a local map point as Tracking::S
 struct FrameView : dvmh_frame_view {
   FrameView() : dvmh_frame_view() { nLevels = 8; }
   FrameView(const dvmh_frame_view& v) : dvmh_frame_view(v) {}
+  // mpCamera, where it is not the pinhole camera of fx, fy, cx, cy: a KannalaBrandt8 model (model == 1) sends the query projection of
+  // SearchByProjection(CurrentFrame, LastFrame) through csrc/camera_model.h.  NULL (and model 0): fx, fy, cx, cy above.
+  const dvm_camera_model* mpCamera = nullptr;
 };
 // DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>) flattened: node ids ascending, the features of node k are
 // feat[off[k] .. off[k+1]) in insertion order (dvm_host::ORBVocabulary::transform produces exactly this).

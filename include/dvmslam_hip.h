@@ -12,6 +12,7 @@
  *   dvm_ba_*       <- Optimizer::{BundleAdjustment,LocalBundleAdjustment} + g2o BlockSolver_6_3/LM
  *                                                    src/Optimizer.cc:55-356,1030-1387
  *   dvm_pose_optimize <- Optimizer::PoseOptimization src/Optimizer.cc:744-1028
+ *   dvm_pose_optimize_cam, dvm_is_in_frustum_cam, dvm_project_search_cam <- the same on a GeometricCamera (CameraModels/KannalaBrandt8.cpp)
  *   dvm_pose_graph_optimize <- Optimizer::OptimizeEssentialGraph src/Optimizer.cc:1389-1652 (g2o part)
  *   dvm_sim3_hypotheses <- Sim3Solver::ComputeSim3 + CheckInliers src/Sim3Solver.cc:294-408
  *   dvm_distinctive_descriptors <- MapPoint::ComputeDistinctiveDescriptors src/MapPoint.cc:384-453
@@ -262,6 +263,23 @@ typedef struct { float proj_x, proj_y, proj_xr, depth, view_cos; int32_t level; 
 int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const float* normal, const float* min_dist,
                       const float* max_dist, int n, float viewing_cos_limit, dvm_track_point* out, int on_device, void* stream);
 
+/* A camera model of the reference's GeometricCamera (CameraModels/Pinhole.cpp, KannalaBrandt8.cpp), evaluated by csrc/camera_model.h.
+ * KannalaBrandt8: theta = atan2(sqrt(x^2 + y^2), z), r = theta + k1 theta^3 + k2 theta^5 + k3 theta^7 + k4 theta^9,
+ * u = fx r x / rho + cx, v = fy r y / rho + cy (rho = sqrt(x^2 + y^2); on the optical axis u = cx, v = cy).  Its Jacobian
+ * (projectJac, KannalaBrandt8.cpp:144-172) is 0 / 0 on the optical axis: NaN there, as in the reference.  sizeof(dvm_camera_model) == 36.
+ * Every *_cam entry returns DVM_ERR_INVALID, before anything runs, for a NULL model, a model outside {0, 1} or a zero focal length.
+ * What takes a model: dvm_pose_optimize_cam, dvm_is_in_frustum_cam, dvm_project_search_cam (and dvmh_search_by_projection_frames_cam,
+ * include/dvmslam_host.h).  The pools, the tracked-frame chains, the BA windows and OptimizeSim3 are pinhole-only. */
+typedef struct { int32_t model;   /* 0 pinhole, 1 KannalaBrandt8 */
+                 float p[8];      /* fx, fy, cx, cy, k1, k2, k3, k4: mvParameters, float as the reference stores them */
+} dvm_camera_model;
+/* dvm_is_in_frustum with uv = mpCamera->project(Pc) (Frame.cc:594) of `model`: model->p[0..3] replace frame->fx, fy, cx, cy, which are
+ * not read.  Everything else, proj_xr = u - bf * invz included, as in dvm_is_in_frustum; model 0 gives its results bit for bit.  A
+ * KannalaBrandt8 monocular frame has mvKeysUn = mvKeys and bounds 0 .. cols / 0 .. rows (mDistCoef is zero): the caller passes those. */
+int dvm_is_in_frustum_cam(const dvm_frustum_frame* frame, const dvm_camera_model* model, const float* P, const float* normal,
+                          const float* min_dist, const float* max_dist, int n, float viewing_cos_limit, dvm_track_point* out, int on_device,
+                          void* stream);
+
 /* LocalMapping::CreateNewMapPoints, the geometry of ONE neighbour keyframe (LocalMapping.cc:598-741, monocular pinhole branch) for
  * the index pairs ORBmatcher::SearchForTriangulation returned: unprojectEig, parallax of the two rays (cos > 0 and, in double,
  * < cos_parallax_max: 0.9998, 0.9996 inertial), GeometricTools::Triangulate (GeometricTools.cc:48-67), z > 0 in both cameras,
@@ -326,6 +344,14 @@ int dvm_project_search(const dvm_frame* train, int slot, const uint8_t* skip, co
                        const float* normal, const float* min_dist, const float* max_dist, const uint8_t* desc,
                        const uint8_t* valid, int n, float th, const float* scale_factors, const float* gate_inv_sigma2,
                        double gate, dvm_match* out, dvm_projection* proj, int on_device, void* stream);
+/* dvm_project_search with uv = pCamera->project(p3Dc) of `model` (ORBmatcher.cc:431, :1117, :1274, :1774): model->p[0..3] replace
+ * cam->fx, fy, cx, cy, which are not read.  The chi2 gate of Fuse(KF, vpMapPoints) takes its error from that u, v; nothing else about it
+ * changes.  cam->sim3_pair == 1 (SearchBySim3) keeps u = fx * (X * invz) + cx: the reference writes the pinhole formula inline there
+ * (ORBmatcher.cc:1401-1406) whatever the camera, so that form reads p[0..3] only.  Model 0 gives dvm_project_search's results bit for bit. */
+int dvm_project_search_cam(const dvm_frame* train, int slot, const uint8_t* skip, const dvm_kf_camera* cam, const dvm_camera_model* model,
+                           const float* P, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* desc,
+                           const uint8_t* valid, int n, float th, const float* scale_factors, const float* gate_inv_sigma2, double gate,
+                           dvm_match* out, dvm_projection* proj, int on_device, void* stream);
 
 /* ORBmatcher::SearchForTriangulation inner loop (ORBmatcher.cc:905-998, monocular): query q = keypoint qidx[q] of KF1
  * scans the KF2 keypoints cand[off[q] .. off[q+1]) (entries < 0 skipped); a candidate is kept if dist <= 50, dist <= best
@@ -735,6 +761,15 @@ int dvm_f64_spec_eval(int device, const double* x, int n, double* out);
 int dvm_pose_optimize(int device, const double* pose_in, const double* Xw, const double* obs, const double* inv_sigma2,
                       const int32_t* n, int stride, int batch, const dvm_ba_camera* cam, double* pose_out,
                       uint8_t* outlier, int32_t* n_inliers);
+/* The same on a camera model: the edge's error is obs - pCamera->project(Xc) and its Jacobian -pCamera->projectJac(Xc) * SE3deriv
+ * (OptimizableTypes.cpp:51-63) of `model`; LM control, rounds, classification and outputs as above.  Model 0 runs the pinhole kernel on
+ * (double)p[0..3] and returns what dvm_pose_optimize returns for those doubles, bit for bit.  KannalaBrandt8: the projection takes theta
+ * from the FLOAT atan2f, as the reference's Vector3d overload does (KannalaBrandt8.cpp:48-66), so the residual is quantised in theta and
+ * poses agree with a host evaluation to about 1e-5 (9.6e-6 measured, tests allow 9.6e-5), not to the 1e-6 of the pinhole kernel; a correspondence on the optical axis has a NaN Jacobian.  The kernel
+ * keeps up to 1 280 correspondences per frame (256 x 5) in registers for either model and re-reads the rest from memory every iteration. */
+int dvm_pose_optimize_cam(int device, const double* pose_in, const double* Xw, const double* obs, const double* inv_sigma2,
+                          const int32_t* n, int stride, int batch, const dvm_camera_model* model, double* pose_out,
+                          uint8_t* outlier, int32_t* n_inliers);
 
 /* The shared form for several agents on one GPU (as dvm_orb_pool for the extractor): dvm_pose_pool_optimize is dvm_pose_optimize for ONE
  * frame -- same arguments, same results bit for bit --, callable from any number of threads; calls that arrive within `window_us` of each

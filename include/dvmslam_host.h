@@ -76,6 +76,14 @@ typedef struct dvmh_tracked_point {
 int dvmh_search_by_projection_frames(int device, int Nc, const dvm_keypoint* kps_c, const uint8_t* desc_c, int32_t* mp_c, const dvm_se3f* Tcw,
                                      const float* K, const float* bounds, const float* scale_factors, int nlevels, int Nl, const dvm_keypoint* kps_l,
                                      const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps, float th, int check_ori, int* requeried);
+/* The same with CurrentFrame.mpCamera->project(x3Dc) (:1586) of a camera model (dvm_camera_model, include/dvmslam_hip.h) in place of K: a
+ * KannalaBrandt8 agent's TrackWithMotionModel search.  Model 0 is the call above on model->p[0..3], bit for bit.  A NULL model, a model
+ * outside {0, 1} or a zero focal length returns DVM_ERR_INVALID before anything runs.  kps_c are mvKeysUn = mvKeys for such a frame and
+ * bounds 0 .. cols / 0 .. rows (the caller's). */
+int dvmh_search_by_projection_frames_cam(int device, int Nc, const dvm_keypoint* kps_c, const uint8_t* desc_c, int32_t* mp_c, const dvm_se3f* Tcw,
+                                         const dvm_camera_model* model, const float* bounds, const float* scale_factors, int nlevels, int Nl,
+                                         const dvm_keypoint* kps_l, const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps, float th,
+                                         int check_ori, int* requeried);
 /* Several agents on one GPU: route the grid build + window search of every SearchByProjection(CurrentFrame, LastFrame) of this process
  * through a shared search service (dvm_match_pool_create, include/dvmslam_hip.h); NULL: back to one staged call per thread.  Frames beyond
  * the pool's capacity, and frames still in HBM, keep the per-thread call.  The pool must outlive the calls. */
