@@ -1560,6 +1560,37 @@ def pose_graph_optimize(S, fixed, edges_v, edges_meas, fix_scale=False, iteratio
     return So, d
 
 
+class PgTrialStats(C.Structure):
+    _fields_ = [("nfree", C.c_int32), ("failed", C.c_int32), ("levels", C.c_int32), ("reserved", C.c_int32),
+                ("chi2_before", C.c_double), ("chi2_after", C.c_double), ("scale_sum", C.c_double)]
+
+
+def pose_graph_debug_trial(S, fixed, edges_v, edges_meas, fix_scale=False, lam=1e-16, device=0):
+    """dvm_pose_graph_debug_trial: one LM trial of dvm_pose_graph_optimize at damping `lam`, stage by stage.  Returns a dict: e[E,7],
+    J[E,2,7,7] ([error row, dof]), H[7m,7m] (lower triangle of J^T J + lam I), b[7m], x[7m] in vertex-id order of the m free vertices,
+    vidx[n] (elimination position, -1 fixed), S[n,8] after oplus, chi2_before, chi2_after, scale_sum, failed, levels."""
+    L = lib()
+    vp, i32 = C.c_void_p, C.c_int32
+    L.dvm_pose_graph_debug_trial.restype = i32
+    L.dvm_pose_graph_debug_trial.argtypes = [i32, vp, vp, i32, vp, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.POINTER(PgTrialStats)]
+    So = np.array(S, np.float64, copy=True)
+    fx = np.ascontiguousarray(fixed, np.uint8)
+    ed = np.zeros(len(edges_v), PG_EDGE_DTYPE)
+    ev = np.asarray(edges_v)
+    ed["vi"] = ev[:, 0]; ed["vj"] = ev[:, 1]; ed["Sji"] = edges_meas
+    E, m = len(ed), int((fx == 0).sum())
+    e = np.zeros((E, 7)); J = np.zeros((E, 2, 7, 7))
+    H, b, x = (np.zeros(max(1, k))[:k] for k in (49 * m * m, 7 * m, 7 * m))     # (never a null pointer, m = 0 included)
+    H = H.reshape(7 * m, 7 * m)
+    vidx = np.full(len(So), -1, np.int32)
+    st = PgTrialStats()
+    check(L.dvm_pose_graph_debug_trial(device, _p(So), _p(fx), len(So), _p(ed), E, int(fix_scale), float(lam), _p(e), _p(J), _p(H), _p(b), _p(x),
+                                       _p(vidx), C.byref(st)))
+    assert st.nfree == m
+    return dict(e=e, J=J, H=H, b=b, x=x, vidx=vidx, S=So, chi2_before=st.chi2_before, chi2_after=st.chi2_after, scale_sum=st.scale_sum,
+                failed=int(st.failed), levels=int(st.levels), nfree=m)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # SURVEY.md 8(a) M4-M7: the remaining whole ORBmatcher functions (host mirrors in dvm_slam_amd/host/orb_matcher.cpp over
 # dvm_hamming_matrix / dvm_match_lists / dvm_project_search / dvm_match_triangulation).  The view structs of

@@ -3420,7 +3420,9 @@ __global__ void __launch_bounds__(256) k_pg_edge(PgView G) {
     sim3_load(G.emeas + 8 * (size_t)k, C); sim3_load(G.S + 8 * (size_t)vi, Si); sim3_load(G.S + 8 * (size_t)vj, Sj);
     double e[7];
     pg_edge_error(C, Si, Sj, e);
-    for (int a = 0; a < 7; a++) { G.e_err[7 * (size_t)k + a] = e[a]; chi += e[a] * e[a]; }
+    // e_err belongs to the linearisation: b = -J^T e is rebuilt from it in EVERY trial of the iteration (k_pg_rhs), so the chi2-only
+    // pass at a trial state must leave it alone -- g2o builds b once per iteration (a rejected trial used to leave its errors here)
+    for (int a = 0; a < 7; a++) { if (JAC) G.e_err[7 * (size_t)k + a] = e[a]; chi += e[a] * e[a]; }
     if (JAC) {
       for (int side = 0; side < 2; side++) {
         const int v = side ? vj : vi;

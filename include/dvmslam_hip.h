@@ -1034,6 +1034,23 @@ typedef struct {
 int dvm_pose_graph_optimize(int device, double* S, const uint8_t* fixed, int n, const dvm_pg_edge* edges, int E,
                             int fix_scale, int iterations, dvm_pg_stats* stats);
 
+/* Test hook (tests/test_gpu_pose_graph.py): ONE Levenberg-Marquardt trial of dvm_pose_graph_optimize at a caller-given lambda,
+ * through the same set-up and the same launches, with every stage handed back.  nfree = number of vertices with fixed[v] == 0;
+ * "free vertex a" = the a-th of them by vertex id.  Outputs (host, caller-allocated):
+ *   e[E][7], J[E][2][49] (side 0 = vertex i, side 1 = vertex j; row-major [error row][dof]) and chi2_before at the input state;
+ *   H[7 nfree][7 nfree] row-major: the lower triangle of J^T J + lambda I, b[7 nfree] = -J^T e (the augmented rhs row the
+ *   factorisation reads) and the solution x[7 nfree], all in vertex-id order of the free vertices (the elimination order and the
+ *   tile layout are undone here); vidx[n] = position of each vertex in the elimination order (-1 = fixed);
+ *   S = the estimates after oplus, scale_sum = computeScale's x^T (lambda x + b), chi2_after at the new estimates.
+ * failed != 0: the factorisation met a non-positive pivot; x keeps its initial zeros and S comes back as it was (normalised). */
+typedef struct {
+  int32_t nfree, failed, levels, reserved;
+  double chi2_before, chi2_after, scale_sum;
+} dvm_pg_trial_stats;
+int dvm_pose_graph_debug_trial(int device, double* S, const uint8_t* fixed, int n, const dvm_pg_edge* edges, int E, int fix_scale,
+                               double lambda, double* e, double* J, double* H, double* b, double* x, int32_t* vidx,
+                               dvm_pg_trial_stats* stats);
+
 /* Sim3Solver::ComputeSim3 + CheckInliers (src/Sim3Solver.cc:294-408) for H RANSAC hypotheses in one launch.
  * P1c / P2c: the N matched map points in the two keyframes' camera frames (mvX3Dc1 / mvX3Dc2, float[3N]);
  * max_err1/2: mvnMaxError1/2 as the reference stores them, (float)(size_t)(9.210 * sigma2); K1 / K2: fx, fy, cx, cy;

@@ -850,46 +850,49 @@ void orc_sim3_exp_log(const double* u, double* S8, double* log7) {
   sim3_log(S, log7);
 }
 
-int orc_pose_graph_optimize(double* Sio, const uint8_t* fixed, int n, const int32_t* ev, const double* emeas, int E, int fix_scale,
-                            int iterations, double* stats /*[6 + 64]: iterations, trials, chi2_initial, chi2_final, lambda_final, stop, chi2_per_iter[32], trials_per_iter[32]*/) {
-  std::vector<Sim3d> S(n);
-  for (int v = 0; v < n; v++) { std::memcpy(S[v].q, Sio + 8 * v, 32); std::memcpy(S[v].t, Sio + 8 * v + 4, 24); S[v].s = Sio[8 * v + 7]; }
-  std::vector<Sim3d> C(E);
-  for (int k = 0; k < E; k++) { std::memcpy(C[k].q, emeas + 8 * k, 32); std::memcpy(C[k].t, emeas + 8 * k + 4, 24); C[k].s = emeas[8 * k + 7]; }
-  std::vector<int> idx(n, -1);
-  int m = 0;
-  for (int v = 0; v < n; v++) if (!fixed[v]) idx[v] = m++;
-  const int dim = 7 * m;
-  auto chi_all = [&]() { double chi = 0; for (int k = 0; k < E; k++) { double e[7]; pg_edge_error(C[k], S[ev[2 * k]], S[ev[2 * k + 1]], e); for (int a = 0; a < 7; a++) chi += e[a] * e[a]; } return chi; };
-  auto oplus = [&](Sim3d& X, const double* u) {
+// The essential graph as orc_pose_graph_optimize and orc_pose_graph_trial share it: estimates, measurements, the dense system in
+// vertex-id order of the free vertices, and the two halves of one LM iteration (linearize, trial).
+namespace {
+struct PoseGraphOracle {
+  int n, E, fix_scale, dim;
+  const uint8_t* fixed;
+  const int32_t* ev;
+  std::vector<Sim3d> S, C;
+  std::vector<int> idx, first;   // free-vertex number per vertex (-1: fixed); envelope of the lower triangle
+  std::vector<double> H, Hl, b, x;
+  PoseGraphOracle(const double* Sio, const uint8_t* fixed_, int n_, const int32_t* ev_, const double* emeas, int E_, int fix_scale_)
+      : n(n_), E(E_), fix_scale(fix_scale_), fixed(fixed_), ev(ev_), S(n_), C(E_), idx(n_, -1) {
+    for (int v = 0; v < n; v++) { std::memcpy(S[v].q, Sio + 8 * v, 32); std::memcpy(S[v].t, Sio + 8 * v + 4, 24); S[v].s = Sio[8 * v + 7]; }
+    for (int k = 0; k < E; k++) { std::memcpy(C[k].q, emeas + 8 * k, 32); std::memcpy(C[k].t, emeas + 8 * k + 4, 24); C[k].s = emeas[8 * k + 7]; }
+    int m = 0;
+    for (int v = 0; v < n; v++) if (!fixed[v]) idx[v] = m++;
+    dim = 7 * m;
+    H.assign((size_t)dim * dim, 0.0); b.assign(dim, 0.0); x.assign(dim, 0.0);
+    first.resize(dim);
+    for (int r = 0; r < dim; r++) first[r] = r - r % 7;
+    for (int k = 0; k < E; k++) {
+      const int a = idx[ev[2 * k]], c = idx[ev[2 * k + 1]];
+      if (a < 0 || c < 0) continue;
+      const int hi = std::max(a, c), lo = std::min(a, c);
+      for (int r = 7 * hi; r < 7 * hi + 7; r++) first[r] = std::min(first[r], 7 * lo);
+    }
+  }
+  double chi_all() const { double chi = 0; for (int k = 0; k < E; k++) { double e[7]; pg_edge_error(C[k], S[ev[2 * k]], S[ev[2 * k + 1]], e); for (int a = 0; a < 7; a++) chi += e[a] * e[a]; } return chi; }
+  void oplus(Sim3d& X, const double* u) const {
     double uu[7]; for (int a = 0; a < 7; a++) uu[a] = u[a];
     if (fix_scale) uu[6] = 0;
     Sim3d Ex, Sn; sim3_exp(uu, Ex); sim3_mul(Ex, X, Sn); X = Sn;
-  };
-  double lambda = 1e-16, ni = 2;   // setUserLambdaInit(1e-16)
-  int nBad = 0, it_done = 0, trials = 0, stop = 0;
-  double chi_last = 0, chi_init = 0;
-  std::vector<double> H((size_t)dim * dim), Hl, b(dim), x(dim);
-  std::vector<int> first(dim);   // envelope of the lower triangle
-  for (int r = 0; r < dim; r++) first[r] = r - r % 7;
-  for (int k = 0; k < E; k++) {
-    const int a = idx[ev[2 * k]], c = idx[ev[2 * k + 1]];
-    if (a < 0 || c < 0) continue;
-    const int hi = std::max(a, c), lo = std::min(a, c);
-    for (int r = 7 * hi; r < 7 * hi + 7; r++) first[r] = std::min(first[r], 7 * lo);
   }
-  for (int it = 0; it < iterations; it++) {
-    double currentChi = chi_all(), tempChi = currentChi;
-    const double iniChi = currentChi;
-    if (it == 0) chi_init = currentChi;
+  // linearizeOplus (numeric) + constructQuadraticForm; e_out [E][7] / J_out [E][2][49] (zero for a fixed side) when asked for
+  void linearize(double* e_out, double* J_out) {
     std::fill(H.begin(), H.end(), 0.0); std::fill(b.begin(), b.end(), 0.0);
-    for (int k = 0; k < E; k++) {   // linearizeOplus (numeric) + constructQuadraticForm
+    for (int k = 0; k < E; k++) {
       const int vi = ev[2 * k], vj = ev[2 * k + 1];
       double e[7], J[2][49];
       pg_edge_error(C[k], S[vi], S[vj], e);
       for (int side = 0; side < 2; side++) {
         const int v = side ? vj : vi;
-        if (fixed[v]) continue;
+        if (fixed[v]) { if (J_out) for (int a = 0; a < 49; a++) J[side][a] = 0; continue; }
         for (int d = 0; d < 7; d++) {
           double u[7] = {0, 0, 0, 0, 0, 0, 0}, e1[7], e2[7];
           Sim3d bak = S[v];
@@ -898,6 +901,8 @@ int orc_pose_graph_optimize(double* Sio, const uint8_t* fixed, int n, const int3
           for (int a = 0; a < 7; a++) J[side][7 * a + d] = (1.0 / (2 * 1e-9)) * (e1[a] - e2[a]);
         }
       }
+      if (e_out) std::memcpy(e_out + 7 * (size_t)k, e, sizeof(e));
+      if (J_out) std::memcpy(J_out + 98 * (size_t)k, J, sizeof(J));
       for (int sa = 0; sa < 2; sa++) {
         const int va = sa ? vj : vi;
         if (fixed[va]) continue;
@@ -912,37 +917,61 @@ int orc_pose_graph_optimize(double* Sio, const uint8_t* fixed, int n, const int3
         }
       }
     }
+  }
+  // one trial at lambda: H + lambda I, Cholesky + solve, oplus.  false: the factorisation failed, x and S are as they were.
+  // H_out [dim][dim]: the damped matrix before the factorisation overwrites it
+  bool trial(double lambda, double* H_out) {
+    Hl = H;
+    for (int r = 0; r < dim; r++) Hl[(size_t)r * dim + r] += lambda;
+    if (H_out) std::memcpy(H_out, Hl.data(), Hl.size() * sizeof(double));
+    // Cholesky + solve on the ENVELOPE of H (row r starts at its first structurally non-zero column): the skipped
+    // products are exact zeros of the dense factorisation, every kept sum runs over ascending k as before -> same bits
+    bool ok = true;
+    for (int r = 0; r < dim && ok; r++) {
+      double* Lr = &Hl[(size_t)r * dim];
+      for (int j = first[r]; j < r; j++) {
+        const double* Lj = &Hl[(size_t)j * dim];
+        double v = Lr[j];
+        for (int k = std::max(first[r], first[j]); k < j; k++) v -= Lr[k] * Lj[k];
+        Lr[j] = v / Lj[j];
+      }
+      double dj = Lr[r];
+      for (int k = first[r]; k < r; k++) dj -= Lr[k] * Lr[k];
+      if (!(dj > 0)) { ok = false; break; }
+      Lr[r] = std::sqrt(dj);
+    }
+    if (ok) {
+      for (int r = 0; r < dim; r++) { double v = b[r]; for (int k = first[r]; k < r; k++) v -= Hl[(size_t)r * dim + k] * x[k]; x[r] = v / Hl[(size_t)r * dim + r]; }
+      for (int r = dim - 1; r >= 0; r--) { double v = x[r]; for (int k = r + 1; k < dim; k++) if (first[k] <= r) v -= Hl[(size_t)k * dim + r] * x[k]; x[r] = v / Hl[(size_t)r * dim + r]; }
+      for (int v = 0; v < n; v++) if (!fixed[v]) oplus(S[v], &x[7 * idx[v]]);
+    }
+    return ok;
+  }
+  double compute_scale(double lambda) const { double scale = 0; for (int r = 0; r < dim; r++) scale += x[r] * (lambda * x[r] + b[r]); return scale; }
+  void store(double* Sio) const { for (int v = 0; v < n; v++) { std::memcpy(Sio + 8 * v, S[v].q, 32); std::memcpy(Sio + 8 * v + 4, S[v].t, 24); Sio[8 * v + 7] = S[v].s; } }
+};
+}  // namespace
+
+int orc_pose_graph_optimize(double* Sio, const uint8_t* fixed, int n, const int32_t* ev, const double* emeas, int E, int fix_scale,
+                            int iterations, double* stats /*[6 + 64]: iterations, trials, chi2_initial, chi2_final, lambda_final, stop, chi2_per_iter[32], trials_per_iter[32]*/) {
+  PoseGraphOracle G(Sio, fixed, n, ev, emeas, E, fix_scale);
+  double lambda = 1e-16, ni = 2;   // setUserLambdaInit(1e-16)
+  int nBad = 0, it_done = 0, trials = 0, stop = 0;
+  double chi_last = 0, chi_init = 0;
+  for (int it = 0; it < iterations; it++) {
+    double currentChi = G.chi_all(), tempChi = currentChi;
+    const double iniChi = currentChi;
+    if (it == 0) chi_init = currentChi;
+    G.linearize(nullptr, nullptr);
     double rho = 0;
     int qmax = 0;
     do {
-      std::vector<Sim3d> bak = S;   // push()
-      Hl = H;
-      for (int r = 0; r < dim; r++) Hl[(size_t)r * dim + r] += lambda;
-      // Cholesky + solve on the ENVELOPE of H (row r starts at its first structurally non-zero column): the skipped
-      // products are exact zeros of the dense factorisation, every kept sum runs over ascending k as before -> same bits
-      bool ok = true;
-      for (int r = 0; r < dim && ok; r++) {
-        double* Lr = &Hl[(size_t)r * dim];
-        for (int j = first[r]; j < r; j++) {
-          const double* Lj = &Hl[(size_t)j * dim];
-          double v = Lr[j];
-          for (int k = std::max(first[r], first[j]); k < j; k++) v -= Lr[k] * Lj[k];
-          Lr[j] = v / Lj[j];
-        }
-        double dj = Lr[r];
-        for (int k = first[r]; k < r; k++) dj -= Lr[k] * Lr[k];
-        if (!(dj > 0)) { ok = false; break; }
-        Lr[r] = std::sqrt(dj);
-      }
-      if (ok) {
-        for (int r = 0; r < dim; r++) { double v = b[r]; for (int k = first[r]; k < r; k++) v -= Hl[(size_t)r * dim + k] * x[k]; x[r] = v / Hl[(size_t)r * dim + r]; }
-        for (int r = dim - 1; r >= 0; r--) { double v = x[r]; for (int k = r + 1; k < dim; k++) if (first[k] <= r) v -= Hl[(size_t)k * dim + r] * x[k]; x[r] = v / Hl[(size_t)r * dim + r]; }
-        for (int v = 0; v < n; v++) if (!fixed[v]) oplus(S[v], &x[7 * idx[v]]);
-      }
-      tempChi = ok ? chi_all() : std::numeric_limits<double>::max();
+      std::vector<Sim3d> bak = G.S;   // push()
+      const bool ok = G.trial(lambda, nullptr);
+      tempChi = ok ? G.chi_all() : std::numeric_limits<double>::max();
       rho = currentChi - tempChi;
       double scale = 0;
-      if (ok) for (int r = 0; r < dim; r++) scale += x[r] * (lambda * x[r] + b[r]);
+      if (ok) scale = G.compute_scale(lambda);
       scale += 1e-3;
       rho /= scale;
       if (rho > 0 && std::isfinite(tempChi)) {
@@ -953,7 +982,7 @@ int orc_pose_graph_optimize(double* Sio, const uint8_t* fixed, int n, const int3
         currentChi = tempChi;
       } else {
         lambda *= ni; ni *= 2;
-        S = bak;   // pop()
+        G.S = bak;   // pop()
       }
       qmax++; trials++;
     } while (rho < 0 && qmax < 10);
@@ -964,9 +993,25 @@ int orc_pose_graph_optimize(double* Sio, const uint8_t* fixed, int n, const int3
     if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
     if (nBad >= 3) { stop = 2; break; }
   }
-  for (int v = 0; v < n; v++) { std::memcpy(Sio + 8 * v, S[v].q, 32); std::memcpy(Sio + 8 * v + 4, S[v].t, 24); Sio[8 * v + 7] = S[v].s; }
+  G.store(Sio);
   if (stats) { stats[0] = it_done; stats[1] = trials; stats[2] = chi_init; stats[3] = chi_last; stats[4] = lambda; stats[5] = stop; }
   return 0;
+}
+
+// test hook: the body of one iteration of orc_pose_graph_optimize at a given lambda, every stage handed back from the dense form
+// (vertex-id order of the free vertices).  H = the damped matrix J^T J + lambda I, full and symmetric.  Returns the number of free
+// vertices.  out[4] = chi2 before, chi2 after (at the new estimates; at the old ones when the factorisation failed), computeScale's
+// x^T (lambda x + b), failed (0 / 1).  A failed factorisation leaves x zero and Sio unchanged.
+int orc_pose_graph_trial(double* Sio, const uint8_t* fixed, int n, const int32_t* ev, const double* emeas, int E, int fix_scale,
+                         double lambda, double* e, double* J, double* H, double* b, double* x, double* out) {
+  PoseGraphOracle G(Sio, fixed, n, ev, emeas, E, fix_scale);
+  out[0] = G.chi_all();
+  G.linearize(e, J);
+  const bool ok = G.trial(lambda, H);
+  out[1] = G.chi_all(); out[2] = G.compute_scale(lambda); out[3] = ok ? 0 : 1;
+  std::memcpy(b, G.b.data(), G.b.size() * sizeof(double)); std::memcpy(x, G.x.data(), G.x.size() * sizeof(double));
+  G.store(Sio);
+  return G.dim / 7;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -249,6 +249,11 @@ int orc_optimize_sim3(double* S12io, int fix_scale, const double* P1c, const dou
 void orc_sim3_exp_log(const double* u, double* S8, double* log7);
 int orc_pose_graph_optimize(double* S, const uint8_t* fixed, int n, const int32_t* ev, const double* emeas, int E, int fix_scale,
                             int iterations, double* stats);
+/* test hook: ONE iteration body of orc_pose_graph_optimize at a given lambda (linearise, damp, factorise, solve, oplus), every stage
+   handed back in vertex-id order of the free vertices: e[E][7], J[E][2][49] (zero for a fixed side), H[7m][7m] = J^T J + lambda I (full),
+   b[7m], x[7m]; S = the estimates after oplus; out[4] = chi2 before, chi2 after, x^T (lambda x + b), failed.  Returns m (free vertices). */
+int orc_pose_graph_trial(double* S, const uint8_t* fixed, int n, const int32_t* ev, const double* emeas, int E, int fix_scale,
+                         double lambda, double* e, double* J, double* H, double* b, double* x, double* out);
 
 /* Sim3Solver::ComputeSim3 + CheckInliers (src/Sim3Solver.cc:294-408) for H given minimal sets; T12 = [s, R row-major (9), t (3)] */
 void orc_sim3_hypotheses(const float* P1c, const float* P2c, const float* max_err1, const float* max_err2, int N, const float* K1,

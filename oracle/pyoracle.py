@@ -741,6 +741,23 @@ def pose_graph_optimize(S, fixed, edges_v, edges_meas, fix_scale=False, iteratio
     return So, st
 
 
+def pose_graph_trial(S, fixed, edges_v, edges_meas, fix_scale=False, lam=1e-16):
+    """orc_pose_graph_trial: one iteration body of pose_graph_optimize at damping `lam`, stage by stage.  Returns a dict: e[E,7],
+    J[E,2,7,7] ([error row, dof]; zero for a fixed side), H[7m,7m] = J^T J + lam I (full), b[7m], x[7m] in vertex-id order of the m free
+    vertices, S[n,8] after oplus, chi2_before, chi2_after, scale_sum, failed."""
+    L = lib()
+    vp, i32 = C.c_void_p, C.c_int32
+    L.orc_pose_graph_trial.restype = i32
+    L.orc_pose_graph_trial.argtypes = [vp, vp, i32, vp, vp, i32, i32, C.c_double] + [vp] * 6
+    So = np.array(S, np.float64, copy=True)
+    fx = np.ascontiguousarray(fixed, np.uint8); ev = np.ascontiguousarray(edges_v, np.int32); em = np.ascontiguousarray(edges_meas, np.float64)
+    E, m = len(ev), int((fx == 0).sum())
+    e = np.zeros((E, 7)); J = np.zeros((E, 2, 7, 7)); H = np.zeros((7 * m, 7 * m)); b = np.zeros(7 * m); x = np.zeros(7 * m); out = np.zeros(4)
+    got = L.orc_pose_graph_trial(_p(So), _p(fx), len(So), _p(ev), _p(em), E, int(fix_scale), float(lam), _p(e), _p(J), _p(H), _p(b), _p(x), _p(out))
+    assert got == m
+    return dict(e=e, J=J, H=H, b=b, x=x, S=So, chi2_before=out[0], chi2_after=out[1], scale_sum=out[2], failed=int(out[3]), nfree=m)
+
+
 class KeyFrameDatabase:
     """KeyFrameDatabase place-recognition queries (kfdb_oracle.cpp) on keyframe slots."""
     PREFIX = "orc_kfdb_"

@@ -65,6 +65,9 @@ def test_count_only_entry_points(L):
     _refused(L, L.dvm_triangulate_matches(_ptr(pair), *tri))
     # dvm_pose_graph_optimize(device, S, fixed, n, edges, E, fix_scale, iterations, stats)                        pg_solver.cpp
     _refused(L, L.dvm_pose_graph_optimize(i32(0), _ptr(z), _ptr(z), i32(2), _ptr(z), i32(1), i32(1), i32(1), vp(0)))
+    # dvm_pose_graph_debug_trial(device, S, fixed, n, edges, E, fix_scale, lambda, e, J, H, b, x, vidx, stats)      pg_solver.cpp
+    _refused(L, L.dvm_pose_graph_debug_trial(i32(0), _ptr(z), _ptr(z), i32(2), _ptr(z), i32(1), i32(1), C.c_double(1.0), _ptr(z), _ptr(z), _ptr(z),
+                                             _ptr(z), _ptr(z), _ptr(z), _ptr(z)))
     # dvm_wire_gather_keypoints(d_block, first_kf, count, d_kps, kps_stride, d_desc, desc_stride, stream)         wire.cpp
     _refused(L, L.dvm_wire_gather_keypoints(vp(64), i32(0), i32(1), vp(64), C.c_int64(1), vp(64), C.c_int64(32), vp(0)))
 
