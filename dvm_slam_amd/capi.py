@@ -605,6 +605,22 @@ class BundleAdjuster:
         check(self.L.dvm_ba_set_problem(self.h, _p(poses), _p(fixed), self.P, _p(points), self.Lm, _p(edges), self.E,
                                         C.byref(cam)))
 
+    def set_problem_cam(self, poses, fixed, points, edges, model, huber_delta):
+        """dvm_ba_set_problem_cam: the problem on a CameraModel.  KannalaBrandt8 runs the tile solver at every size; the pinhole model is
+        set_problem with (double)p[0..3]."""
+        poses = np.ascontiguousarray(poses, np.float64)
+        points = np.ascontiguousarray(points, np.float64)
+        fixed = np.ascontiguousarray(fixed, np.uint8)
+        edges = np.ascontiguousarray(edges, BA_EDGE_DTYPE)
+        assert isinstance(model, CameraModel)
+        f = self.L.dvm_ba_set_problem_cam
+        f.restype = C.c_int32; f.argtypes = None
+        rc = f(self.h, _p(poses), _p(fixed), C.c_int32(len(poses)), _p(points), C.c_int32(len(points)), _p(edges), C.c_int32(len(edges)),
+               C.byref(model), C.c_double(float(huber_delta)))
+        if rc == 0:
+            self.P, self.Lm, self.E = len(poses), len(points), len(edges)
+        check(rc)
+
     def set_problem_sharded(self, poses, fixed, points, edges, intrinsics, huber_delta, rank, world):
         """BASELINE config 5: the whole problem on every rank, the observations of the landmarks `point % world == rank`
         evaluated here (dvm_ba_set_problem_sharded).  Needs set_allreduce() before optimize()."""

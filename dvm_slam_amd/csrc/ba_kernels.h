@@ -117,6 +117,11 @@ struct BaView {
   double *poses_new, *points_new;   // trial state: k_update writes exp(dx) * poses -> poses_new, points + dx -> points_new; an
                                     // accepted trial swaps the pointers on the host, a rejected one leaves (poses, points) alone
                                     // -- g2o's push() / pop() / discardTop() without copies
+  // The camera model of the problem (camera_model.h), read by k_edge_eval alone.  Behind every older member, so that none of their offsets
+  // in the kernel argument moves.  0: pinhole, fx / fy / cx / cy above; 1: KannalaBrandt8, cam_p = mvParameters (fx .. cy above hold
+  // (double)cam_p[0..3] and are not read).
+  int32_t cam_model;
+  float cam_p[8];
 };
 
 // How a phase-ending kernel hands its scalar to the host without a D2H copy + stream synchronisation: the LAST workgroup to

@@ -235,6 +235,35 @@ __device__ __forceinline__ double wave_sum_lds(const double* v, double* park /* 
   return s;
 }
 
+// The camera of a projection edge: what an edge kernel (k_edge_eval here, the `edge` of k_pose_optimize below) asks of it is the projection
+// (the residual) and MINUS the projection's Jacobian (EdgeSE3ProjectXYZ::linearizeOplus, OptimizableTypes.cpp:147-154: -projectJac(xyz_trans) * R
+// and * SE3deriv; EdgeSE3ProjectXYZOnlyPose::linearizeOplus, :51-63).
+struct PoseCamPinhole {   // Pinhole::project / projectJac: four doubles, laid out as the four scalar arguments they replace
+  double fx, fy, cx, cy;
+  __device__ __forceinline__ void project(double x, double y, double z, double& u, double& v) const { u = fx * x / z + cx; v = fy * y / z + cy; }
+  __device__ __forceinline__ void neg_jac(double x, double y, double z, double* J) const {
+    J[0] = -(fx / z); J[1] = 0; J[2] = fx * x / (z * z); J[3] = 0; J[4] = -(fy / z); J[5] = fy * y / (z * z);
+  }
+};
+struct PoseCamKB8 {       // KannalaBrandt8 (camera_model.h): mvParameters as the reference stores them
+  float p[8];
+  __device__ __forceinline__ void project(double x, double y, double z, double& u, double& v) const { dvm_cam::kb8_project(p, x, y, z, u, v); }
+  __device__ __forceinline__ void neg_jac(double x, double y, double z, double* J) const {
+    dvm_cam::kb8_project_jac(p, x, y, z, J);
+#pragma unroll
+    for (int i = 0; i < 6; i++) J[i] = -J[i];
+  }
+};
+// the camera of a bundle-adjustment problem out of its view: the four doubles, or mvParameters (BaView::cam_p)
+template <class CAM> __device__ __forceinline__ CAM ba_view_cam(const BaView& V);
+template <> __device__ __forceinline__ PoseCamPinhole ba_view_cam<PoseCamPinhole>(const BaView& V) { return PoseCamPinhole{V.fx, V.fy, V.cx, V.cy}; }
+template <> __device__ __forceinline__ PoseCamKB8 ba_view_cam<PoseCamKB8>(const BaView& V) {
+  PoseCamKB8 c;
+#pragma unroll
+  for (int i = 0; i < 8; i++) c.p[i] = V.cam_p[i];
+  return c;
+}
+
 // ------------------------------------------------------------------------------------------ K8
 // JAC=false: residual / chi2 only (computeActiveErrors + activeRobustChi2 terms).
 // JAC=true : additionally Jacobians A (2x3, point), B (2x6, pose), weights and Hpl block W (6x3).
@@ -243,8 +272,11 @@ __device__ __forceinline__ double wave_sum_lds(const double* v, double* park /* 
 // the halves still shared a 192-byte row: ~10 of the kernel's 28 us).  A wave's 64 rows are one contiguous 8 KB / 8 KB / 9 KB image
 // in global memory: every lane parks its row in LDS (row pitch 18 doubles: 16-byte writes without bank conflicts), three times in
 // turn, and the wave copies the image out with 16-byte stores, 1 KB per instruction.
+// CAM: the problem's camera (PoseCamPinhole / PoseCamKB8), which enters through project and neg_jac only.  Under KannalaBrandt8 the residual's
+// theta is the float atan2f of project(Vector3d) and the Jacobian's the double atan2 (camera_model.h), the chi2-only pass evaluates no
+// Jacobian, and a point on the optical axis gets NaN rows as in the reference (an inactive edge exact zeros all the same).
 constexpr int kLinPitch = 18;
-template <bool JAC>
+template <bool JAC, class CAM>
 __global__ void __launch_bounds__(256) k_edge_eval(BaView V, BaPublish pub) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   __shared__ double2 s_rows[JAC ? 4 * 64 * kLinPitch / 2 : 1];
@@ -262,8 +294,11 @@ __global__ void __launch_bounds__(256) k_edge_eval(BaView V, BaPublish pub) {
     Xc[0] += T[0]; Xc[1] += T[1]; Xc[2] += T[2];
     const double x = Xc[0], y = Xc[1], z = Xc[2];
     const double info = V.e_info[k];
-    const double e0 = V.e_obs[2 * (size_t)k] - (V.fx * x / z + V.cx);
-    const double e1 = V.e_obs[2 * (size_t)k + 1] - (V.fy * y / z + V.cy);
+    const CAM cam = ba_view_cam<CAM>(V);
+    double pu, pv;
+    cam.project(x, y, z, pu, pv);
+    const double e0 = V.e_obs[2 * (size_t)k] - pu;
+    const double e1 = V.e_obs[2 * (size_t)k + 1] - pv;
     const double chi2 = e0 * info * e0 + e1 * info * e1;
     const unsigned fl = V.e_flags ? V.e_flags[k] : 3u;
     const bool active = (fl & 1u) != 0;                 // g2o: level 0.  A level-1 edge is outside the active set: no error evaluation
@@ -272,7 +307,8 @@ __global__ void __launch_bounds__(256) k_edge_eval(BaView V, BaPublish pub) {
     robustify(chi2, (fl & 2u) ? V.delta : 0.0, rho0, rho1);
     if (!active) { rho0 = 0; rho1 = 0; }
     if (JAC) {
-      const double J[6] = {-(V.fx / z), 0, V.fx * x / (z * z), 0, -(V.fy / z), V.fy * y / (z * z)};
+      double J[6];
+      cam.neg_jac(x, y, z, J);
       double A[6], B[12];
 #pragma unroll
       for (int r = 0; r < 2; r++)
@@ -2540,24 +2576,6 @@ __device__ unsigned long long g_pose_prof[16];
 #else
 #define POSE_T(k) do {} while (0)
 #endif
-// The camera of the frame: what the `edge` of k_pose_optimize asks of it is the projection (the residual) and MINUS the projection's
-// Jacobian (EdgeSE3ProjectXYZOnlyPose::linearizeOplus, OptimizableTypes.cpp:51-63: -projectJac(xyz_trans) * SE3deriv).
-struct PoseCamPinhole {   // Pinhole::project / projectJac: four doubles, laid out as the four scalar arguments they replace
-  double fx, fy, cx, cy;
-  __device__ __forceinline__ void project(double x, double y, double z, double& u, double& v) const { u = fx * x / z + cx; v = fy * y / z + cy; }
-  __device__ __forceinline__ void neg_jac(double x, double y, double z, double* J) const {
-    J[0] = -(fx / z); J[1] = 0; J[2] = fx * x / (z * z); J[3] = 0; J[4] = -(fy / z); J[5] = fy * y / (z * z);
-  }
-};
-struct PoseCamKB8 {       // KannalaBrandt8 (camera_model.h): mvParameters as the reference stores them
-  float p[8];
-  __device__ __forceinline__ void project(double x, double y, double z, double& u, double& v) const { dvm_cam::kb8_project(p, x, y, z, u, v); }
-  __device__ __forceinline__ void neg_jac(double x, double y, double z, double* J) const {
-    dvm_cam::kb8_project_jac(p, x, y, z, J);
-#pragma unroll
-    for (int i = 0; i < 6; i++) J[i] = -J[i];
-  }
-};
 // The body of k_pose_optimize, common to every camera: LM control, speculative linearisation, the 28-value reduction, the 6x6 solve and
 // the four rounds; the camera enters `edge` and `fresh` through project / neg_jac only.  EPT: correspondences a thread keeps in
 // registers (kPoseEdgesPerThread for the pinhole camera, kPoseEdgesPerThreadKB8 for KannalaBrandt8).
@@ -3525,8 +3543,13 @@ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 void ba_launch_edge_eval(hipStream_t s, const BaView& V, bool jac, const BaPublish& pub) {
   const int nb = cdiv(V.E, 256);
-  if (jac) hipLaunchKernelGGL(k_edge_eval<true>, dim3(nb), dim3(256), 0, s, V, pub);
-  else hipLaunchKernelGGL(k_edge_eval<false>, dim3(nb), dim3(256), 0, s, V, pub);
+  if (V.cam_model == dvm_cam::kKannalaBrandt8) {
+    if (jac) hipLaunchKernelGGL((k_edge_eval<true, PoseCamKB8>), dim3(nb), dim3(256), 0, s, V, pub);
+    else hipLaunchKernelGGL((k_edge_eval<false, PoseCamKB8>), dim3(nb), dim3(256), 0, s, V, pub);
+  } else {
+    if (jac) hipLaunchKernelGGL((k_edge_eval<true, PoseCamPinhole>), dim3(nb), dim3(256), 0, s, V, pub);
+    else hipLaunchKernelGGL((k_edge_eval<false, PoseCamPinhole>), dim3(nb), dim3(256), 0, s, V, pub);
+  }
 }
 void ba_launch_accum(hipStream_t s, const BaView& V, const double* spec, const BaPublish* max_pub) {
   const int nb_pose = V.nfree > 0 ? (V.schur_wide ? V.nfree : cdiv(V.nfree, 4)) : 0;   // (wide: a workgroup per camera)

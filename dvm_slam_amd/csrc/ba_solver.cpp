@@ -239,7 +239,8 @@ void dvm_ba_destroy(dvm_ba* h) {
 // workgroups) the level launches are ahead again (1 401 vs 1 313 it/s).
 static bool kFlowDefault(const BaTileSchedule& SC, int workgroups) { return SC.nlevels >= 5 && (int)(SC.flow_tasks.size() / 8) <= 4 * workgroups; }
 static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed, int P, const double* points, int L,
-                            const dvm_ba_edge* edges, int E, const dvm_ba_camera* cam, int rank, int world) {
+                            const dvm_ba_edge* edges, int E, const dvm_ba_camera* cam, int rank, int world,
+                            const dvm_camera_model* model = nullptr) {
   if (!h || !poses || !fixed || !points || !edges || !cam || P < 1 || L < 1 || E < 1 || world < 1 || rank < 0 || rank >= world) {
     set_error("dvm_ba_set_problem: bad arguments");
     return DVM_ERR_INVALID;
@@ -257,6 +258,13 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
   std::memset(&V, 0, sizeof(V));
   V.P = P; V.L = L; V.E = E;
   V.fx = cam->fx; V.fy = cam->fy; V.cx = cam->cx; V.cy = cam->cy; V.delta = cam->huber_delta;
+  // the camera model is set by every call (the memset above left it pinhole): a handle that goes from one camera to another and back
+  // gives what a fresh handle gives
+  const bool kb8 = model && model->model == dvm_cam::kKannalaBrandt8;
+  if (kb8) {
+    V.cam_model = dvm_cam::kKannalaBrandt8;
+    for (int i = 0; i < 8; i++) V.cam_p[i] = model->p[i];
+  }
   std::vector<int32_t> e_pose(E), e_point(E);
   std::vector<double> e_obs(2 * (size_t)E), e_info(E);
   std::vector<int32_t> pt_cnt(L + 1, 0), ps_cnt(P + 1, 0);
@@ -678,7 +686,8 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
   h->have_problem = true;
   {
     static const int max_free = [] { const char* e = std::getenv("DVM_BA_WINDOW_MAX_FREE"); return e ? std::atoi(e) : 6; }();
-    h->win_mode = world == 1 && V.nfree <= std::min(max_free, 30) && !std::getenv("DVM_BA_NO_WINDOW");
+    // (the sequential-order kernels of ba_window.hip are pinhole-only: what they promise is g2o's bits, and no two atan2f share those)
+    h->win_mode = world == 1 && !kb8 && V.nfree <= std::min(max_free, 30) && !std::getenv("DVM_BA_NO_WINDOW");
     h->win_device_stale = false;
     if (h->win_mode) {
       h->ws_poses = pn; h->ws_points.assign(points, points + 3 * (size_t)L); h->ws_fixed.assign(fixed, fixed + P);
@@ -692,6 +701,20 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
 int dvm_ba_set_problem(dvm_ba* h, const double* poses, const uint8_t* fixed, int P, const double* points, int L,
                        const dvm_ba_edge* edges, int E, const dvm_ba_camera* cam) {
   const int rc = set_problem_impl(h, poses, fixed, P, points, L, edges, E, cam, 0, 1);
+  if (rc == DVM_OK) h->sharded_api = false;
+  return rc;
+}
+// dvm_ba_set_problem on a camera model: KannalaBrandt8 goes to the tile solver with k_edge_eval's fisheye instantiation, whatever the
+// problem's size; the pinhole model IS dvm_ba_set_problem
+int dvm_ba_set_problem_cam(dvm_ba* h, const double* poses, const uint8_t* fixed, int P, const double* points, int L,
+                           const dvm_ba_edge* edges, int E, const dvm_camera_model* model, double huber_delta) {
+  if (!model || !dvm_cam::model_ok(model->model, model->p)) {
+    set_error("dvm_ba_set_problem_cam: NULL model, unknown model or zero focal length");
+    return DVM_ERR_INVALID;
+  }
+  const dvm_ba_camera cam{(double)model->p[0], (double)model->p[1], (double)model->p[2], (double)model->p[3], huber_delta};
+  if (model->model == dvm_cam::kPinhole) return dvm_ba_set_problem(h, poses, fixed, P, points, L, edges, E, &cam);
+  const int rc = set_problem_impl(h, poses, fixed, P, points, L, edges, E, &cam, 0, 1, model);
   if (rc == DVM_OK) h->sharded_api = false;
   return rc;
 }

@@ -268,8 +268,9 @@ int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const floa
  * u = fx r x / rho + cx, v = fy r y / rho + cy (rho = sqrt(x^2 + y^2); on the optical axis u = cx, v = cy).  Its Jacobian
  * (projectJac, KannalaBrandt8.cpp:144-172) is 0 / 0 on the optical axis: NaN there, as in the reference.  sizeof(dvm_camera_model) == 36.
  * Every *_cam entry returns DVM_ERR_INVALID, before anything runs, for a NULL model, a model outside {0, 1} or a zero focal length.
- * What takes a model: dvm_pose_optimize_cam, dvm_is_in_frustum_cam, dvm_project_search_cam (and dvmh_search_by_projection_frames_cam,
- * include/dvmslam_host.h).  The pools, the tracked-frame chains, the BA windows and OptimizeSim3 are pinhole-only. */
+ * What takes a model: dvm_pose_optimize_cam, dvm_is_in_frustum_cam, dvm_project_search_cam, dvm_ba_set_problem_cam (and
+ * dvmh_search_by_projection_frames_cam, include/dvmslam_host.h).  The pools, the tracked-frame chains, the batched BA windows
+ * (dvm_ba_optimize_windows) and OptimizeSim3 are pinhole-only. */
 typedef struct { int32_t model;   /* 0 pinhole, 1 KannalaBrandt8 */
                  float p[8];      /* fx, fy, cx, cy, k1, k2, k3, k4: mvParameters, float as the reference stores them */
 } dvm_camera_model;
@@ -628,6 +629,24 @@ void dvm_ba_destroy(dvm_ba* h);
 /* builds the graph (vertex order, incidence lists, reduced-camera block pattern) and uploads it */
 int dvm_ba_set_problem(dvm_ba* h, const double* poses, const uint8_t* fixed, int P, const double* points, int L,
                        const dvm_ba_edge* edges, int E, const dvm_ba_camera* cam);
+/* dvm_ba_set_problem on a camera model (dvm_camera_model above): every EdgeSE3ProjectXYZ of the problem takes its error from
+ * obs - pCamera->project(Xc) and its Jacobians from -pCamera->projectJac(Xc) * R and * SE3deriv (OptimizableTypes.h:102,
+ * OptimizableTypes.cpp:147-154) of that one camera.  DVM_ERR_INVALID, before anything runs, for a NULL model, a model outside {0, 1} or a
+ * zero focal length.  Every call sets the handle's model again; dvm_ba_optimize, dvm_ba_set_edge_flags, dvm_ba_get_result,
+ * dvm_ba_edge_chi2 and the measurement aids then work as on any problem.
+ *   model 0: forwards to dvm_ba_set_problem with (double)p[0..3] and huber_delta -- everything afterwards is that call's result bit for
+ *     bit, the sequential-order form of problems with <= 6 free cameras included.
+ *   model 1 (KannalaBrandt8): the residual's theta is the float atan2f(sqrtf((float)(x^2 + y^2)), (float)z) of project(Vector3d), the
+ *     Jacobian's the double atan2, as in the reference; a point on the optical axis has a NaN Jacobian, as in the reference.  The tile
+ *     solver handles EVERY problem size under this camera, the <= 6 free cameras of a local-BA window too: what the sequential-order
+ *     kernels promise is g2o's bits, and the residual is quantised by an atan2f whose last bit no two implementations share, so that
+ *     promise does not exist here.  ACCURACY CONTRACT (tests/test_gpu_ba_kb8.py, against the float64 restatement of the recipe in
+ *     tests/ba_kb8_scene.py): the LM accept / reject sequence and the stop reason are identical, and poses and landmarks agree within
+ *     10 x what the restatement itself moves by when every edge's theta is one float32 ulp off (measured per scene set, docs/NOTEBOOK.md
+ *     section 18; never less than 1e-6) -- on scenes whose trial sequence survives that ulp.
+ * Pinhole-only as before: dvm_ba_set_problem_sharded, dvm_ba_optimize_windows(_fast), dvm_ba_pool_*, dvm_ba_optimize_batch. */
+int dvm_ba_set_problem_cam(dvm_ba* h, const double* poses, const uint8_t* fixed, int P, const double* points, int L,
+                           const dvm_ba_edge* edges, int E, const dvm_camera_model* model, double huber_delta);
 /* optimizer.optimize(iterations); stop_flag (may be NULL) is g2o's forceStopFlag: polled between
  * iterations and trials, may be written by another thread (LocalMapping.cc:305,359).
  * ACCURACY CONTRACT (tests/test_gpu_ba_weak.py, tests/test_gpu_config_size.py, tests/test_gpu_ba_window.py), against the CPU
