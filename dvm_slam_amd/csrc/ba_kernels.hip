@@ -1,122 +1,34 @@
-// dvm_slam_amd/csrc/ba_kernels.hip -- FP64 bundle-adjustment kernels for gfx950.
+// dvm_slam_amd/csrc/ba_kernels.hip -- the FP64 tile solver of bundle adjustment for gfx950 (driver: ba_solver.cpp).
 //
 // One Levenberg-Marquardt iteration of the reference's BA (g2o BlockSolver_6_3 + Levenberg,
 // reference Thirdparty/g2o/g2o/core/{block_solver.hpp,optimization_algorithm_levenberg.cpp},
-// src/Optimizer.cc:55-356,1030-1387, src/OptimizableTypes.cpp:136-155, src/CameraModels/Pinhole.cpp):
-//   K8  k_edge_eval            per-edge residual, Huber weight, 2x3 / 2x6 Jacobians, Hpl block
-//       k_point_accum          Hll (3x3), bl per landmark       (gather over the landmark's edges)
-//       k_pose_accum           Hpp (6x6), bp per camera         (one wave per camera, fixed-order reduce)
-//   K9  k_dinv, k_schur_blocks Dinv = (Hll+lambda I)^-1 ; Hschur block = Hpp - sum W Dinv W^T
-//       k_schur_rhs            bschur = bp - sum W Dinv bl  (stored as the augmented row of S)
-//   K10 k_chol_diag / k_chol_trsm / k_chol_update   blocked dense Cholesky on v_mfma_f64_16x16x4
-//       k_chol_backsolve       L^T x = y
-//   K11 k_point_backsub, k_update      xl = Dinv (bl - W^T xp); T <- exp(d) T, X <- X + d
+// src/Optimizer.cc:55-356,1030-1387, src/OptimizableTypes.cpp:136-155, src/CameraModels/{Pinhole,KannalaBrandt8}.cpp):
+//   K8  k_edge_eval<JAC, CAM>  per-edge residual, Huber weight, 2x3 / 2x6 Jacobians, Hpl block (the edge itself: proj_edge.h)
+//       k_accum                Hll (3x3), bl per landmark and Hpp (6x6), bp per camera: fixed-order gathers; k_max_diag(_sharded)
+//   K9  k_dinv / k_trial_prologue   Dinv = (Hll + lambda I)^-1
+//       k_schur<NW>, k_schur_lm, k_schur_reduce, k_clear_tiles   S = Hpp - sum W Dinv W^T, bschur = bp - sum W Dinv bl (augmented row of S)
+//   K10 k_chol_diag / k_chol_trsm / k_chol_update / k_chol_trsm_update / k_chol_pair   blocked dense Cholesky on v_mfma_f64_16x16x4
+//       k_chol_backsolve       L^T x = y;  k_chol_flow: the whole factorisation and solve as one dataflow launch
+//   K11 k_point_backsub        xl = Dinv (bl - W^T xp); T <- exp(d) T, X <- X + d;  k_edge_depth
+//   sharded solve              k_pack_tiles, k_hpp_diag, k_points_exchange
 // All accumulations are gathers with a fixed order: results are run-to-run deterministic.
+// The other FP64 optimisers live in files of their own: pose_kernels.hip (PoseOptimization), sim3_kernels.hip (OptimizeSim3, Sim3Solver),
+// pg_kernels.hip (essential graph), ba_window.hip (small windows); the small algebra they share is se3_f64.h's.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 #include <cstring>
 
 #include "ba_kernels.h"
-#include "camera_model.h"
-#include "f64_spec.h"
-#include "jacobi4.h"
+#include "proj_edge.h"
+#include "se3_f64.h"
 
 namespace dvm {
-
-// ------------------------------------------------------------------------------- small algebra
-__device__ __forceinline__ void quat_to_R(const double* q, double* R) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y,
-               tyz = tz * y, tzz = tz * z;
-  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-__device__ __forceinline__ void R_to_quat(const double* R, double* q) {
-  double t = R[0] + R[4] + R[8];
-  if (t > 0) {
-    t = sqrt(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-  } else {
-    int i = 0;
-    if (R[4] > R[0]) i = 1;
-    if (R[8] > R[i * 4]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = sqrt(R[i * 4] - R[j * 4] - R[k * 4] + 1.0);
-    q[i] = 0.5 * t;
-    t = 0.5 / t;
-    q[3] = (R[k * 3 + j] - R[j * 3 + k]) * t;
-    q[j] = (R[j * 3 + i] + R[i * 3 + j]) * t;
-    q[k] = (R[k * 3 + i] + R[i * 3 + k]) * t;
-  }
-}
-__device__ __forceinline__ void quat_normalize(double* q) {
-  if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
-}
-__device__ __forceinline__ void mat3_vec(const double* R, const double* v, double* o) {
-  o[0] = R[0] * v[0] + R[1] * v[1] + R[2] * v[2];
-  o[1] = R[3] * v[0] + R[4] * v[1] + R[5] * v[2];
-  o[2] = R[6] * v[0] + R[7] * v[1] + R[8] * v[2];
-}
-
-// T <- exp(u) * T, u = (omega, upsilon): SE3Quat::exp + operator* + normalizeRotation
-// (reference Thirdparty/g2o/g2o/types/se3quat.h:212-266, types_six_dof_expmap.h:71-74)
-__device__ __forceinline__ void se3_oplus(double* T, const double* u) {
-  const double om0 = u[0], om1 = u[1], om2 = u[2];
-  const double theta = sqrt(om0 * om0 + om1 * om1 + om2 * om2);
-  const double O[9] = {0, -om2, om1, om2, 0, -om0, -om1, om0, 0};
-  double O2[9];
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) O2[3 * r + c] = O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c] + O[3 * r + 2] * O[6 + c];
-  double R[9], Vm[9];
-  if (theta < 0.00001) {
-#pragma unroll
-    for (int k = 0; k < 9; k++) { R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + O[k] + O2[k]; Vm[k] = R[k]; }
-  } else {
-    // sin / cos / pow(theta, 3) of SE3Quat::exp: the double-precision spec the oracle evaluates too (csrc/f64_spec.h), not the device libm
-    const double sn = f64_sin(theta), cs = f64_cos(theta);
-    const double a = sn / theta, bb = (1 - cs) / (theta * theta), c = (theta - sn) / f64_cube(theta);
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-      const double I = (k % 4 == 0) ? 1.0 : 0.0;
-      R[k] = I + a * O[k] + bb * O2[k];
-      Vm[k] = I + bb * O[k] + c * O2[k];
-    }
-  }
-  double dq[4], dt[3], Rd[9], rt[3], nq[4];
-  R_to_quat(R, dq);
-  quat_normalize(dq);
-  mat3_vec(Vm, u + 3, dt);
-  quat_to_R(dq, Rd);
-  mat3_vec(Rd, T, rt);
-  const double* q = T + 3;
-  nq[3] = dq[3] * q[3] - dq[0] * q[0] - dq[1] * q[1] - dq[2] * q[2];
-  nq[0] = dq[3] * q[0] + dq[0] * q[3] + dq[1] * q[2] - dq[2] * q[1];
-  nq[1] = dq[3] * q[1] + dq[1] * q[3] + dq[2] * q[0] - dq[0] * q[2];
-  nq[2] = dq[3] * q[2] + dq[2] * q[3] + dq[0] * q[1] - dq[1] * q[0];
-  quat_normalize(nq);
-  T[0] = dt[0] + rt[0]; T[1] = dt[1] + rt[1]; T[2] = dt[2] + rt[2];
-  T[3] = nq[0]; T[4] = nq[1]; T[5] = nq[2]; T[6] = nq[3];
-}
-
-// Huber (robust_kernel_impl.cpp:68-81); delta <= 0 means "no robust kernel"
-__device__ __forceinline__ void robustify(double e, double delta, double& rho0, double& rho1) {
-  if (delta <= 0 || e <= delta * delta) { rho0 = e; rho1 = 1.; }
-  else { const double s = sqrt(e); rho0 = 2 * s * delta - delta * delta; rho1 = delta / s; }
-}
 
 __device__ __forceinline__ double ba_lambda(const BaView& V) { return V.lambda ? *V.lambda : V.lambda_v; }
 
 // Block sum of `v` -> partial[blockIdx.x]; the last workgroup to arrive then reduces all partials exactly like
-// k_reduce_sum (thread-strided sums, then the same tree: identical bits) and hands the result to the host (BaPublish).
+// k_reduce_sum of pg_kernels.hip (thread-strided sums, then the same tree: identical bits) and hands the result to the host (BaPublish).
 template <bool MAX>
 __device__ __forceinline__ void block_reduce_publish(double v, double* __restrict__ partial, const BaPublish& pub, int nb_part = 0) {
   __shared__ double s_red[256];
@@ -193,30 +105,6 @@ __device__ __forceinline__ void block_reduce_publish(double v, double* __restric
   }
 }
 
-// Sums of N per-thread doubles over a 256-thread workgroup, THROUGH LDS: every thread parks its values (pitch N + 1), thread
-// (q, i) adds the 64 threads of wave q for value i in thread order, then the four wave sums are added -- a fixed order.  The
-// alternative, xor-butterflies of __shfl_xor, is ds_bpermute_b32 twice per double and step: 24 cycles of the CU's LDS unit
-// each (tools/valu_issue2.hip), 336 of them for 28 values -- 13 us per reduction with four waves sharing the unit.
-// park: 256 * (N + 1) doubles, part: 4 * N doubles, out: N doubles (all in LDS; out is valid for every thread on return).
-template <int N>
-__device__ __forceinline__ void block_sum_lds(const double* v, double* park, double* part, double* out) {
-  const int tid = threadIdx.x;
-  double* mine = park + (size_t)tid * (N + 1);
-#pragma unroll
-  for (int i = 0; i < N; i++) mine[i] = v[i];
-  __syncthreads();
-  if (tid < 4 * N) {
-    const int q = tid / N, i = tid - q * N;
-    const double* col = park + (size_t)(64 * q) * (N + 1) + i;
-    double s = 0;
-#pragma unroll 16
-    for (int l = 0; l < 64; l++) s += col[(size_t)l * (N + 1)];
-    part[q * N + i] = s;
-  }
-  __syncthreads();
-  if (tid < N) out[tid] = (part[tid] + part[N + tid]) + (part[2 * N + tid] + part[3 * N + tid]);
-  __syncthreads();
-}
 // the same for one wave (64 lanes), no workgroup barrier: lane i < N returns the sum of value i over the lanes, in lane order
 template <int N>
 __device__ __forceinline__ double wave_sum_lds(const double* v, double* park /* 64 * (N + 1) doubles of this wave */) {
@@ -235,25 +123,6 @@ __device__ __forceinline__ double wave_sum_lds(const double* v, double* park /* 
   return s;
 }
 
-// The camera of a projection edge: what an edge kernel (k_edge_eval here, the `edge` of k_pose_optimize below) asks of it is the projection
-// (the residual) and MINUS the projection's Jacobian (EdgeSE3ProjectXYZ::linearizeOplus, OptimizableTypes.cpp:147-154: -projectJac(xyz_trans) * R
-// and * SE3deriv; EdgeSE3ProjectXYZOnlyPose::linearizeOplus, :51-63).
-struct PoseCamPinhole {   // Pinhole::project / projectJac: four doubles, laid out as the four scalar arguments they replace
-  double fx, fy, cx, cy;
-  __device__ __forceinline__ void project(double x, double y, double z, double& u, double& v) const { u = fx * x / z + cx; v = fy * y / z + cy; }
-  __device__ __forceinline__ void neg_jac(double x, double y, double z, double* J) const {
-    J[0] = -(fx / z); J[1] = 0; J[2] = fx * x / (z * z); J[3] = 0; J[4] = -(fy / z); J[5] = fy * y / (z * z);
-  }
-};
-struct PoseCamKB8 {       // KannalaBrandt8 (camera_model.h): mvParameters as the reference stores them
-  float p[8];
-  __device__ __forceinline__ void project(double x, double y, double z, double& u, double& v) const { dvm_cam::kb8_project(p, x, y, z, u, v); }
-  __device__ __forceinline__ void neg_jac(double x, double y, double z, double* J) const {
-    dvm_cam::kb8_project_jac(p, x, y, z, J);
-#pragma unroll
-    for (int i = 0; i < 6; i++) J[i] = -J[i];
-  }
-};
 // the camera of a bundle-adjustment problem out of its view: the four doubles, or mvParameters (BaView::cam_p)
 template <class CAM> __device__ __forceinline__ CAM ba_view_cam(const BaView& V);
 template <> __device__ __forceinline__ PoseCamPinhole ba_view_cam<PoseCamPinhole>(const BaView& V) { return PoseCamPinhole{V.fx, V.fy, V.cx, V.cy}; }
@@ -288,45 +157,28 @@ __global__ void __launch_bounds__(256) k_edge_eval(BaView V, BaPublish pub) {
     const int p = V.e_pose[k], l = V.e_point[k];
     const double* T = (JAC ? V.poses : V.poses_new) + 7 * (size_t)p;     // chi2-only evaluations look at the TRIAL state
     const double* X = (JAC ? V.points : V.points_new) + 3 * (size_t)l;
-    double R[9], Xc[3];
+    double R[9];
     quat_to_R(T + 3, R);
-    mat3_vec(R, X, Xc);
-    Xc[0] += T[0]; Xc[1] += T[1]; Xc[2] += T[2];
-    const double x = Xc[0], y = Xc[1], z = Xc[2];
-    const double info = V.e_info[k];
     const CAM cam = ba_view_cam<CAM>(V);
-    double pu, pv;
-    cam.project(x, y, z, pu, pv);
-    const double e0 = V.e_obs[2 * (size_t)k] - pu;
-    const double e1 = V.e_obs[2 * (size_t)k + 1] - pv;
-    const double chi2 = e0 * info * e0 + e1 * info * e1;
+    const ProjEdge<CAM> e(cam, R, T, X, V.e_obs[2 * (size_t)k], V.e_obs[2 * (size_t)k + 1], V.e_info[k]);
     const unsigned fl = V.e_flags ? V.e_flags[k] : 3u;
     const bool active = (fl & 1u) != 0;                 // g2o: level 0.  A level-1 edge is outside the active set: no error evaluation
-    if (active) V.e_chi2[k] = chi2;                     // (its chi2() stays what it was), nothing in chi2 / H / b
+    if (active) V.e_chi2[k] = e.chi2;                   // (its chi2() stays what it was), nothing in chi2 / H / b
     double rho1;
-    robustify(chi2, (fl & 2u) ? V.delta : 0.0, rho0, rho1);
+    robustify(e.chi2, (fl & 2u) ? V.delta : 0.0, rho0, rho1);
     if (!active) { rho0 = 0; rho1 = 0; }
     if (JAC) {
-      double J[6];
-      cam.neg_jac(x, y, z, J);
       double A[6], B[12];
-#pragma unroll
-      for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) A[3 * r + c] = J[3 * r] * R[c] + J[3 * r + 1] * R[3 + c] + J[3 * r + 2] * R[6 + c];
-      const double S[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
-#pragma unroll
-      for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int c = 0; c < 6; c++) B[6 * r + c] = J[3 * r] * S[c] + J[3 * r + 1] * S[6 + c] + J[3 * r + 2] * S[12 + c];
+      e.jac_point(cam, R, A);
+      e.jac_pose(cam, B);
       if (!active) {                                    // exact zeros whatever the geometry (a point on the camera plane: inf / NaN rows)
 #pragma unroll
         for (int i = 0; i < 6; i++) A[i] = 0.0;
 #pragma unroll
         for (int i = 0; i < 12; i++) B[i] = 0.0;
       }
-      const double w = active ? rho1 * info : 0.0;
-      const double wr0 = active ? -info * e0 * rho1 : 0.0, wr1 = active ? -info * e1 * rho1 : 0.0;
+      const double w = active ? e.w(rho1) : 0.0;
+      const double wr0 = active ? e.wr0(rho1) : 0.0, wr1 = active ? e.wr1(rho1) : 0.0;
       double2* mine = reinterpret_cast<double2*>(park + (size_t)lane * kLinPitch);
 #pragma unroll
       for (int i = 0; i < 6; i++) mine[i] = make_double2(B[2 * i], B[2 * i + 1]);
@@ -338,7 +190,7 @@ __global__ void __launch_bounds__(256) k_edge_eval(BaView V, BaPublish pub) {
 #pragma unroll
       for (int a = 0; a < 6; a++)
 #pragma unroll
-        for (int b = 0; b < 3; b++) Wv[3 * a + b] = pose_free ? w * (B[a] * A[b] + B[6 + a] * A[3 + b]) : 0.0;
+        for (int b = 0; b < 3; b++) Wv[3 * a + b] = pose_free ? proj_edge_hpl(w, B, A, a, b) : 0.0;
     }
   }
   if (JAC) {
@@ -382,34 +234,14 @@ __global__ void __launch_bounds__(256) k_edge_eval(BaView V, BaPublish pub) {
   block_reduce_publish<false>(rho0, V.partial, pub);   // fixed-order sum of rho0 over all edges -> host
 }
 
-// Sum `n` partials in a fixed order into out[slot]; single workgroup.
-__global__ void __launch_bounds__(256) k_reduce_sum(const double* __restrict__ partial, int n, double* __restrict__ out, int slot) {
-  __shared__ double s[256];
-  double acc = 0;
-  for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-  s[threadIdx.x] = acc;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[slot] = s[0];
-}
-
 // (Hll + lambda I)^-1 and its product with bl for one landmark
 __device__ __forceinline__ void dinv_apply(const double* H, const double* bl, double lambda, double* __restrict__ D, double* __restrict__ db) {
-  const double a = H[0] + lambda, b = H[1], c = H[2], d = H[3], e = H[4] + lambda, f = H[5], g = H[6], h = H[7], i = H[8] + lambda;
-  const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
-  const double id = 1.0 / det;
+  const double M[9] = {H[0] + lambda, H[1], H[2], H[3], H[4] + lambda, H[5], H[6], H[7], H[8] + lambda};
   double o[9];
-  o[0] = (e * i - f * h) * id; o[1] = (c * h - b * i) * id; o[2] = (b * f - c * e) * id;
-  o[3] = (f * g - d * i) * id; o[4] = (a * i - c * g) * id; o[5] = (c * d - a * f) * id;
-  o[6] = (d * h - e * g) * id; o[7] = (b * g - a * h) * id; o[8] = (a * e - b * d) * id;
+  inv3(M, o);     // (the operations of ba_window.hip's w_dinv in the same order: the same bits)
 #pragma unroll
   for (int k = 0; k < 9; k++) D[k] = o[k];
-  db[0] = o[0] * bl[0] + o[1] * bl[1] + o[2] * bl[2];
-  db[1] = o[3] * bl[0] + o[4] * bl[1] + o[5] * bl[2];
-  db[2] = o[6] * bl[0] + o[7] * bl[1] + o[8] * bl[2];
+  mat3_vec(o, bl, db);
 }
 
 // a KEPT landmark (BaView::kept_slot) is not eliminated: it contributes nothing to the Schur complement or its right-hand side
@@ -935,25 +767,6 @@ __global__ void __launch_bounds__(256) k_schur_reduce(BaView V) {
   const int i1 = V.blk_i1[blk], i2 = V.blk_i2[blk];
   if (i1 == i2) v += V.Hpp[36 * (size_t)i1 + e] + (ra == cb ? ba_lambda(V) * V.damp_s : 0.0);
   V.S[(size_t)(ba_row(i1) + ra) * V.ldS + ba_row(i2) + cb] = v;
-}
-
-// clears the structurally non-zero tiles of S (a trial rebuilds them); everything else is never touched and stays zero
-// from the allocation-time memset: 197 of 1 326 tiles = 6 MB instead of 85 MB at 500 keyframes
-__global__ void __launch_bounds__(256) k_zero_tiles(double* __restrict__ S, int ldS, const int32_t* __restrict__ nz) {
-  const int ti = nz[2 * blockIdx.x], tj = nz[2 * blockIdx.x + 1];
-  double* base = S + (size_t)ti * 64 * ldS + tj * 64;
-  for (int i = threadIdx.x; i < 64 * 32; i += 256) {
-    const int r = i >> 5, c2 = i & 31;
-    reinterpret_cast<double2*>(base + (size_t)r * ldS)[c2] = make_double2(0.0, 0.0);
-  }
-}
-
-// identity on the padding rows of the tiled system (rows 60..63 of every tile, cameras beyond nfree in the last tile)
-__global__ void __launch_bounds__(256) k_pad_identity(BaView V) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r >= V.n_pad) return;
-  const int w = r & 63;
-  if (w >= V.per_tile * V.dof || (r >> 6) * V.per_tile + w / V.dof >= V.nfree) V.S[(size_t)r * V.ldS + r] = 1.0;
 }
 
 // Start of a BA trial: the damped landmark blocks are inverted (k_dinv); the Cholesky failure flag is reset on the way.  (The
@@ -2476,7 +2289,7 @@ __global__ void __launch_bounds__(256) k_point_backsub(BaView V, BaPublish pub, 
       double T[7];
 #pragma unroll
       for (int a = 0; a < 7; a++) T[a] = V.poses[7 * (size_t)p + a];
-      se3_oplus(T, u);
+      se3_oplus(T, u, T);
 #pragma unroll
       for (int a = 0; a < 7; a++) V.poses_new[7 * (size_t)p + a] = T[a];
     }
@@ -2540,1002 +2353,6 @@ __global__ void __launch_bounds__(256) k_edge_depth(BaView V, uint8_t* __restric
   quat_to_R(T + 3, R);
   const double z = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + T[2];
   out[k] = z > 0.0;
-}
-
-// ---------------------------------------------------------------------------------------- B1
-// Optimizer::PoseOptimization (reference src/Optimizer.cc:744-1028, mono edges
-// EdgeSE3ProjectXYZOnlyPose, src/OptimizableTypes.cpp:51-63): one camera, N unary reprojection edges,
-// 4 rounds x optimize(10) of g2o's Levenberg with a dense 6x6 solve, re-classifying inliers after every
-// round (chi2 > 5.991 as float), Huber removed after round 2.  ONE workgroup runs the whole thing for
-// one frame -- about 40 LM iterations with no host round trip; frames are batched over the grid.
-struct PoseAccum { double v[28]; };  // 21 upper-H + 6 b + 1 chi
-// One value over the workgroup in a fixed order: xor-butterfly inside each wave, then the four wave sums in wave order.
-// (What the chi2-only evaluation of a trial needs: running the 28-value reduction for it cost 2 us per LM trial.)
-__device__ __forceinline__ double block_sum_one(double v, double* part4) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) part4[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = (part4[0] + part4[1]) + (part4[2] + part4[3]);
-  __syncthreads();
-  return r;
-}
-// The kernel is a LATENCY path -- Tracking calls PoseOptimization two or three times per frame, one frame at a time, and a
-// workgroup runs ~40 dependent LM iterations -- so everything that repeats per iteration is kept off the memory system and off
-// the serial thread: a thread's correspondences (up to kPoseEdgesPerThread x 256 per frame; more fall back to global reads) live
-// in registers across all iterations together with their level flag and last chi2; the Jacobian pass reduces its 28 sums in one
-// pass through LDS; a trial's chi2-only pass reduces ONE value; the 6x6 solve forms 1 / L_ii once per row (v_rsq_f64 + two
-// Newton steps, as the tile Cholesky does) instead of 27 double-precision divisions and 6 square roots on a single lane.
-// (Measured, one frame of 300 matches: 363 us per call before, of which ~2.8 us per LM trial were the divisions.)
-constexpr int kPoseEdgesPerThread = 5;
-// KannalaBrandt8: its Jacobian needs 78 more registers than the pinhole's six values, and 5 still does not spill (docs/NOTEBOOK.md section 16)
-constexpr int kPoseEdgesPerThreadKB8 = 5;
-#ifdef DVM_POSE_PROF   // make EXTRA=-DDVM_POSE_PROF: per-phase clocks of workgroup 0 (dvm_debug_pose_prof), measurement builds only
-__device__ unsigned long long g_pose_prof[16];
-#define POSE_T(k) do { if (tid == 0 && blockIdx.x == 0) { const unsigned long long now_ = wall_clock64(); g_pose_prof[k] += now_ - pose_last_; pose_last_ = now_; } } while (0)
-#else
-#define POSE_T(k) do {} while (0)
-#endif
-// The body of k_pose_optimize, common to every camera: LM control, speculative linearisation, the 28-value reduction, the 6x6 solve and
-// the four rounds; the camera enters `edge` and `fresh` through project / neg_jac only.  EPT: correspondences a thread keeps in
-// registers (kPoseEdgesPerThread for the pinhole camera, kPoseEdgesPerThreadKB8 for KannalaBrandt8).
-template <class CAM, int EPT>
-__device__ __forceinline__ void pose_optimize_block(const double* __restrict__ pose_in, const double* __restrict__ Xw,
-                                                    const double* __restrict__ obs, const double* __restrict__ info,
-                                                    const int32_t* __restrict__ n_per_frame, int stride, const CAM cam,
-                                                    double* __restrict__ pose_out, uint8_t* __restrict__ outlier,
-                                                    int32_t* __restrict__ n_inliers, double* __restrict__ chi_scratch) {
-  __shared__ double s_park[256 * 29];
-  __shared__ double s_part[4 * 28];
-  __shared__ double s_sum[28];
-  __shared__ double s_T[7], s_Tbak[7], s_T0[7];
-  __shared__ double s_lambda, s_ni, s_cur, s_ini, s_rho;
-  __shared__ int s_ctl, s_qmax, s_nbad, s_nact, s_lin;
-  const int f = blockIdx.x, tid = threadIdx.x;
-#ifdef DVM_POSE_PROF
-  unsigned long long pose_last_ = wall_clock64();
-#endif
-  const int N = n_per_frame[f];
-  const double* X = Xw + (size_t)f * stride * 3;
-  const double* O = obs + (size_t)f * stride * 2;
-  const double* W = info + (size_t)f * stride;
-  uint8_t* outl = outlier + (size_t)f * stride;
-  double* last_chi = chi_scratch + (size_t)f * stride;  // e->chi2() as g2o reports it (last evaluation): edges beyond the register-resident ones
-  const double delta = (double)sqrtf(5.991f);
-  const float chi2Mono = 5.991f;
-  if (tid < 7) {
-    double v = pose_in[7 * (size_t)f + tid];
-    s_T0[tid] = v;
-  }
-  __syncthreads();
-  if (tid == 0) quat_normalize(&s_T0[3]);
-  // this thread's correspondences: registers for the first EPT, global memory beyond
-  double eX[EPT][3], eO[EPT][2], eW[EPT], eChi[EPT];
-  bool eOut[EPT];       // level(1) == outlier flag in the reference's bookkeeping
-#pragma unroll
-  for (int e = 0; e < EPT; e++) {
-    const int i = tid + 256 * e;
-    const bool in = i < N;
-    const int ii = in ? i : 0;
-    eX[e][0] = X[3 * ii]; eX[e][1] = X[3 * ii + 1]; eX[e][2] = X[3 * ii + 2];
-    eO[e][0] = O[2 * ii]; eO[e][1] = O[2 * ii + 1];
-    eW[e] = W[ii];
-    eChi[e] = 0; eOut[e] = false;
-  }
-  for (int i = tid + 256 * EPT; i < N; i += 256) { outl[i] = 0; last_chi[i] = 0; }
-  __syncthreads();
-  if (N < 3) {  // nInitialCorrespondences < 3: return 0, pose untouched (Optimizer.cc:904-905)
-    if (tid < 7) pose_out[7 * (size_t)f + tid] = pose_in[7 * (size_t)f + tid];
-    for (int i = tid; i < N; i += 256) outl[i] = 0;
-    if (tid == 0) n_inliers[f] = 0;
-    return;
-  }
-  // one active edge at pose (R, T): chi2 (always; returned), H / b terms (jac)
-  auto edge = [&](const double* R, const double* T, const double* Xp, double o0, double o1, double w0, bool jac, bool robust_on, PoseAccum& a) -> double {
-    double Xc[3];
-    mat3_vec(R, Xp, Xc);
-    Xc[0] += T[0]; Xc[1] += T[1]; Xc[2] += T[2];
-    const double x = Xc[0], y = Xc[1], z = Xc[2];
-    double pu, pv;
-    cam.project(x, y, z, pu, pv);
-    const double e0 = o0 - pu, e1 = o1 - pv;
-    const double chi2 = e0 * w0 * e0 + e1 * w0 * e1;
-    double r0, r1;
-    robustify(chi2, robust_on ? delta : 0.0, r0, r1);
-    a.v[27] += r0;
-    if (jac) {
-      double J[6];
-      cam.neg_jac(x, y, z, J);
-      const double S[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
-      double B[12];
-#pragma unroll
-      for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int c = 0; c < 6; c++) B[6 * r + c] = J[3 * r] * S[c] + J[3 * r + 1] * S[6 + c] + J[3 * r + 2] * S[12 + c];
-      const double w = r1 * w0, wr0 = -w0 * e0 * r1, wr1 = -w0 * e1 * r1;
-      int t = 0;
-#pragma unroll
-      for (int p = 0; p < 6; p++) {
-        a.v[21 + p] += B[p] * wr0 + B[6 + p] * wr1;
-#pragma unroll
-        for (int q = 0; q <= p; q++) a.v[t++] += w * (B[p] * B[q] + B[6 + p] * B[6 + q]);
-      }
-    }
-    return chi2;
-  };
-  // evaluates the active edges at pose T: chi (always), H / b (jac); updates the edges' last chi2.  Result in s_sum ([27] = chi2).
-  auto eval = [&](const double* T, bool jac, bool robust_on) {
-    PoseAccum a;
-#pragma unroll
-    for (int i = 0; i < 28; i++) a.v[i] = 0;
-    double R[9];
-    quat_to_R(T + 3, R);
-#pragma unroll
-    for (int e = 0; e < EPT; e++) {
-      if (tid + 256 * e < N && !eOut[e]) eChi[e] = edge(R, T, eX[e], eO[e][0], eO[e][1], eW[e], jac, robust_on, a);
-    }
-    for (int i = tid + 256 * EPT; i < N; i += 256) {
-      if (outl[i]) continue;
-      last_chi[i] = edge(R, T, X + 3 * i, O[2 * i], O[2 * i + 1], W[i], jac, robust_on, a);
-    }
-    if (jac) block_sum_lds<28>(a.v, s_park, s_part, s_sum);
-    else {
-      const double c = block_sum_one(a.v[27], s_part);
-      if (tid == 0) s_sum[27] = c;
-      __syncthreads();
-    }
-  };
-
-  bool robust_on = true;
-  for (int round = 0; round < 4; round++) {
-    if (tid < 7) s_T[tid] = s_T0[tid];  // vSE3->setEstimate(pFrame->GetPose()) every round
-    if (tid == 0) { s_nact = 0; s_ctl = 0; s_nbad = 0; s_lin = 0; }
-    __syncthreads();
-    int my = 0;
-#pragma unroll
-    for (int e = 0; e < EPT; e++) my += (tid + 256 * e < N && !eOut[e]) ? 1 : 0;
-    for (int i = tid + 256 * EPT; i < N; i += 256) my += outl[i] ? 0 : 1;
-    if (my) atomicAdd(&s_nact, my);
-    __syncthreads();
-    const int nact = s_nact;
-    POSE_T(0);
-    for (int it = 0; it < 10 && nact > 0; it++) {
-      // Speculative linearisation (as the tile solver's LM loop does it): an accepted trial has evaluated its state WITH the Jacobians, so
-      // the iteration that follows finds H, b and chi2 of its state in s_sum already -- one pass per accepted trial instead of two
-      // (chi2 only, then the same edges again with Jacobians); a rejected trial's sums are simply overwritten.
-      const bool have_lin = s_lin != 0;
-      __syncthreads();
-      if (tid == 0) s_lin = 0;
-      if (!have_lin) eval(s_T, true, robust_on);
-      POSE_T(1);
-      if (tid == 0) {
-        s_cur = s_sum[27]; s_ini = s_sum[27];
-        if (it == 0) {
-          double mx = 0;
-          int t = 0;
-          for (int p = 0; p < 6; p++) for (int q = 0; q <= p; q++) { if (p == q) mx = fmax(mx, fabs(s_sum[t])); t++; }
-          s_lambda = 1e-5 * mx; s_ni = 2; s_nbad = 0;
-        }
-        s_qmax = 0;
-      }
-      __syncthreads();
-      double Hs[21], bs[6];
-      if (tid == 0) {
-#pragma unroll
-        for (int i = 0; i < 21; i++) Hs[i] = s_sum[i];
-#pragma unroll
-        for (int i = 0; i < 6; i++) bs[i] = s_sum[21 + i];
-      }
-      POSE_T(2);
-      while (true) {
-        double xs[6];
-        bool ok = true;
-        if (tid == 0) {
-          for (int i = 0; i < 7; i++) s_Tbak[i] = s_T[i];
-          // dense 6x6 Cholesky of (H + lambda I), lower-packed Hs[p(p+1)/2 + q]; ri[j] = 1 / L_jj
-          double Lm[21], ri[6];
-#pragma unroll
-          for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = 0; j <= i; j++) {
-              double sacc = Hs[i * (i + 1) / 2 + j] + (i == j ? s_lambda : 0.0);
-#pragma unroll
-              for (int k = 0; k < j; k++) sacc -= Lm[i * (i + 1) / 2 + k] * Lm[j * (j + 1) / 2 + k];
-              if (i == j) {
-                if (!(sacc > 0)) ok = false;
-                const double dd = sacc > 0 ? sacc : 1.0;
-                double y = __builtin_amdgcn_rsq(dd);
-                y = __builtin_fma(0.5 * y, __builtin_fma(-dd * y, y, 1.0), y);
-                y = __builtin_fma(0.5 * y, __builtin_fma(-dd * y, y, 1.0), y);
-                double sq = dd * y;
-                sq = __builtin_fma(0.5 * y, __builtin_fma(-sq, sq, dd), sq);
-                Lm[i * (i + 1) / 2 + i] = sq; ri[i] = y;
-              } else Lm[i * (i + 1) / 2 + j] = sacc * ri[j];
-            }
-          if (ok) {
-#pragma unroll
-            for (int i = 0; i < 6; i++) {
-              double sacc = bs[i];
-#pragma unroll
-              for (int k = 0; k < i; k++) sacc -= Lm[i * (i + 1) / 2 + k] * xs[k];
-              xs[i] = sacc * ri[i];
-            }
-#pragma unroll
-            for (int i = 5; i >= 0; i--) {
-              double sacc = xs[i];
-#pragma unroll
-              for (int k = i + 1; k < 6; k++) sacc -= Lm[k * (k + 1) / 2 + i] * xs[k];
-              xs[i] = sacc * ri[i];
-            }
-            se3_oplus(s_T, xs);
-          }
-          s_ctl = ok ? 1 : 0;
-        }
-        __syncthreads();
-        POSE_T(3);
-        const bool okb = s_ctl != 0;
-        const bool spec = it + 1 < 10;        // (the last iteration of a round: nobody would use the linearisation)
-        if (okb) eval(s_T, spec, robust_on);
-        POSE_T(4);
-        if (tid == 0) {
-          const double tempChi = okb ? s_sum[27] : 1.7976931348623157e308;
-          double rho = s_cur - tempChi;
-          double scale = 0;
-          if (okb) for (int j = 0; j < 6; j++) scale += xs[j] * (s_lambda * xs[j] + bs[j]);
-          scale += 1e-3;
-          rho /= scale;
-          if (rho > 0 && isfinite(tempChi)) {
-            double alpha = 1. - f64_cube(2 * rho - 1);   // pow(2 rho - 1, 3) as the shared double-precision spec forms it (f64_spec.h)
-            alpha = fmin(alpha, 2. / 3.);
-            s_lambda *= fmax(1. / 3., alpha);
-            s_ni = 2;
-            s_cur = tempChi;
-            if (spec) s_lin = 1;                   // s_sum holds this state's linearisation
-          } else {
-            s_lambda *= s_ni; s_ni *= 2;
-            for (int i = 0; i < 7; i++) s_T[i] = s_Tbak[i];
-          }
-          s_qmax++;
-          s_rho = rho;
-          s_ctl = (rho < 0 && s_qmax < 10) ? 1 : 0;  // continue the trial loop?
-        }
-        __syncthreads();
-        POSE_T(5);
-        if (!s_ctl) break;
-        __syncthreads();
-      }
-      if (tid == 0) {
-        int stop = 0;
-        if (s_qmax == 10 || s_rho == 0) stop = 1;
-        else {
-          if ((s_ini - s_cur) * 1e3 < s_ini) s_nbad++; else s_nbad = 0;
-          if (s_nbad >= 3) stop = 1;
-        }
-        s_ctl = stop;
-      }
-      __syncthreads();
-      const int stop = s_ctl;
-      __syncthreads();
-      POSE_T(6);
-#ifdef DVM_POSE_PROF
-      if (tid == 0 && blockIdx.x == 0) g_pose_prof[15]++;
-#endif
-      if (stop) break;
-    }
-    // classification (Optimizer.cc:923-948): outliers recompute their error, inliers report the last evaluation
-    {
-      double R[9];
-      quat_to_R(s_T + 3, R);
-      auto fresh = [&](const double* Xp, double o0, double o1, double w0) {
-        double Xc[3];
-        mat3_vec(R, Xp, Xc);
-        Xc[0] += s_T[0]; Xc[1] += s_T[1]; Xc[2] += s_T[2];
-        double pu, pv;
-        cam.project(Xc[0], Xc[1], Xc[2], pu, pv);
-        const double e0 = o0 - pu, e1 = o1 - pv;
-        return e0 * w0 * e0 + e1 * w0 * e1;
-      };
-#pragma unroll
-      for (int e = 0; e < EPT; e++) {
-        if (tid + 256 * e < N) {
-          if (eOut[e]) eChi[e] = fresh(eX[e], eO[e][0], eO[e][1], eW[e]);
-          eOut[e] = (float)eChi[e] > chi2Mono;
-        }
-      }
-      for (int i = tid + 256 * EPT; i < N; i += 256) {
-        if (outl[i]) last_chi[i] = fresh(X + 3 * i, O[2 * i], O[2 * i + 1], W[i]);
-        outl[i] = (float)last_chi[i] > chi2Mono ? 1 : 0;
-      }
-    }
-    if (round == 2) robust_on = false;
-    __syncthreads();
-    POSE_T(7);
-    if (N < 10) break;  // optimizer.edges().size() < 10
-  }
-  if (tid == 0) s_nact = 0;
-  __syncthreads();
-  int bad = 0;
-#pragma unroll
-  for (int e = 0; e < EPT; e++) {
-    const int i = tid + 256 * e;
-    if (i < N) { outl[i] = eOut[e] ? 1 : 0; bad += eOut[e] ? 1 : 0; }
-  }
-  for (int i = tid + 256 * EPT; i < N; i += 256) bad += outl[i];
-  if (bad) atomicAdd(&s_nact, bad);
-  __syncthreads();
-  if (tid < 7) pose_out[7 * (size_t)f + tid] = s_T[tid];
-  if (tid == 0) n_inliers[f] = N - s_nact;
-}
-// the pinhole camera: the four intrinsics travel as scalars
-__global__ void __launch_bounds__(256) k_pose_optimize(const double* __restrict__ pose_in, const double* __restrict__ Xw,
-                                                       const double* __restrict__ obs, const double* __restrict__ info,
-                                                       const int32_t* __restrict__ n_per_frame, int stride, double fx,
-                                                       double fy, double cx, double cy, double* __restrict__ pose_out,
-                                                       uint8_t* __restrict__ outlier, int32_t* __restrict__ n_inliers,
-                                                       double* __restrict__ chi_scratch) {
-  pose_optimize_block<PoseCamPinhole, kPoseEdgesPerThread>(pose_in, Xw, obs, info, n_per_frame, stride, PoseCamPinhole{fx, fy, cx, cy}, pose_out, outlier,
-                                                           n_inliers, chi_scratch);
-}
-// KannalaBrandt8 (dvm_pose_optimize_cam, model 1)
-__global__ void __launch_bounds__(256) k_pose_optimize_kb8(const double* __restrict__ pose_in, const double* __restrict__ Xw,
-                                                           const double* __restrict__ obs, const double* __restrict__ info,
-                                                           const int32_t* __restrict__ n_per_frame, int stride, PoseCamKB8 cam,
-                                                           double* __restrict__ pose_out, uint8_t* __restrict__ outlier,
-                                                           int32_t* __restrict__ n_inliers, double* __restrict__ chi_scratch) {
-  pose_optimize_block<PoseCamKB8, kPoseEdgesPerThreadKB8>(pose_in, Xw, obs, info, n_per_frame, stride, cam, pose_out, outlier, n_inliers, chi_scratch);
-}
-
-#ifdef DVM_POSE_PROF
-extern "C" int dvm_debug_pose_prof(unsigned long long* out, int reset) {
-  unsigned long long h[16];
-  int rc = (int)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pose_prof), sizeof(h));
-  for (int i = 0; i < 16; i++) out[i] = h[i];
-  if (reset) { for (auto& v : h) v = 0; rc |= (int)hipMemcpyToSymbol(HIP_SYMBOL(g_pose_prof), h, sizeof(h)); }
-  return rc;
-}
-#endif
-void ba_launch_pose_optimize(hipStream_t s, const double* pose_in, const double* Xw, const double* obs, const double* info,
-                             const int32_t* n_per_frame, int stride, int batch, double fx, double fy, double cx, double cy,
-                             double* pose_out, uint8_t* outlier, int32_t* n_inliers, double* chi_scratch) {
-  hipLaunchKernelGGL(k_pose_optimize, dim3(batch), dim3(256), 0, s, pose_in, Xw, obs, info, n_per_frame, stride, fx, fy, cx, cy,
-                     pose_out, outlier, n_inliers, chi_scratch);
-}
-// k_pose_optimize_kb8: the same body on a KannalaBrandt8 camera, p = mvParameters (dvm_pose_optimize_cam, model 1)
-void ba_launch_pose_optimize_kb8(hipStream_t s, const double* pose_in, const double* Xw, const double* obs, const double* info,
-                                 const int32_t* n_per_frame, int stride, int batch, const float* p, double* pose_out, uint8_t* outlier,
-                                 int32_t* n_inliers, double* chi_scratch) {
-  PoseCamKB8 cam;
-  for (int i = 0; i < 8; i++) cam.p[i] = p[i];
-  hipLaunchKernelGGL(k_pose_optimize_kb8, dim3(batch), dim3(256), 0, s, pose_in, Xw, obs, info, n_per_frame, stride, cam, pose_out, outlier, n_inliers,
-                     chi_scratch);
-}
-
-// ---------------------------------------------------------------------------------------- B9
-// Optimizer::OptimizeSim3 (reference src/Optimizer.cc:1960-2212): one 7-DoF g2o::Sim3 vertex, two
-// reprojection edges per correspondence (EdgeSim3ProjectXYZ, EdgeInverseSim3ProjectXYZ) whose Jacobians
-// g2o takes NUMERICALLY (central differences, delta 1e-9, base_binary_edge.hpp:131-205) because the
-// analytic linearizeOplus is commented out (include/OptimizableTypes.h:186,205); dense 7x7 Levenberg,
-// optimize(5), inlier test chi2 <= th2, robust kernel off, optimize(5 or 10), final inlier count.
-// One workgroup runs everything; the 14 perturbed Sim3 states (and inverses) are shared by all edges.
-struct Sim3d { double q[4]; double t[3]; double s; };
-__device__ void sim3_exp(const double* u, Sim3d& S) {  // g2o::Sim3(const Vector7d&), sim3.h:62-125
-  const double om0 = u[0], om1 = u[1], om2 = u[2], sigma = u[6];
-  const double theta = sqrt(om0 * om0 + om1 * om1 + om2 * om2);
-  const double O[9] = {0, -om2, om1, om2, 0, -om0, -om1, om0, 0};
-  double O2[9];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
-  S.s = exp(sigma);
-  const double eps = 0.00001;
-  double A, B, C, R[9];
-  if (fabs(sigma) < eps) {
-    C = 1;
-    if (theta < eps) { A = 0.5; B = 1. / 6.; for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0) ? 1.0 : 0.0) + O[i] + O2[i]; }
-    else {
-      const double th2 = theta * theta;
-      A = (1 - cos(theta)) / th2; B = (theta - sin(theta)) / (th2 * theta);
-      for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0) ? 1.0 : 0.0) + sin(theta) / theta * O[i] + (1 - cos(theta)) / (theta * theta) * O2[i];
-    }
-  } else {
-    C = (S.s - 1) / sigma;
-    if (theta < eps) {
-      const double s2 = sigma * sigma;
-      A = ((sigma - 1) * S.s + 1) / s2; B = ((0.5 * s2 - sigma + 1) * S.s) / (s2 * sigma);
-      for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0) ? 1.0 : 0.0) + O[i] + O2[i];
-    } else {
-      for (int i = 0; i < 9; i++) R[i] = ((i % 4 == 0) ? 1.0 : 0.0) + sin(theta) / theta * O[i] + (1 - cos(theta)) / (theta * theta) * O2[i];
-      const double a = S.s * sin(theta), b = S.s * cos(theta), th2 = theta * theta, s2 = sigma * sigma, c = th2 + s2;
-      A = (a * sigma + (1 - b) * theta) / (theta * c);
-      B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / th2;
-    }
-  }
-  R_to_quat(R, S.q);
-  double W[9];
-  for (int i = 0; i < 9; i++) W[i] = A * O[i] + B * O2[i] + C * ((i % 4 == 0) ? 1.0 : 0.0);
-  mat3_vec(W, u + 3, S.t);
-}
-__device__ void sim3_mul(const Sim3d& a, const Sim3d& b, Sim3d& o) {
-  const double* p = a.q; const double* q = b.q;
-  o.q[3] = p[3] * q[3] - p[0] * q[0] - p[1] * q[1] - p[2] * q[2];
-  o.q[0] = p[3] * q[0] + p[0] * q[3] + p[1] * q[2] - p[2] * q[1];
-  o.q[1] = p[3] * q[1] + p[1] * q[3] + p[2] * q[0] - p[0] * q[2];
-  o.q[2] = p[3] * q[2] + p[2] * q[3] + p[0] * q[1] - p[1] * q[0];
-  double R[9], rt[3];
-  quat_to_R(a.q, R);
-  mat3_vec(R, b.t, rt);
-  for (int i = 0; i < 3; i++) o.t[i] = a.s * rt[i] + a.t[i];
-  o.s = a.s * b.s;
-}
-__device__ void sim3_inv(const Sim3d& a, Sim3d& o) {
-  o.q[0] = -a.q[0]; o.q[1] = -a.q[1]; o.q[2] = -a.q[2]; o.q[3] = a.q[3];
-  double R[9];
-  const double v[3] = {(-1. / a.s) * a.t[0], (-1. / a.s) * a.t[1], (-1. / a.s) * a.t[2]};
-  quat_to_R(o.q, R);
-  mat3_vec(R, v, o.t);
-  o.s = 1. / a.s;
-}
-struct Sim3M { double R[9]; double t[3]; double s; };  // map-ready form: x -> s R x + t
-__device__ __forceinline__ void sim3_to_map(const Sim3d& a, Sim3M& m) {
-  quat_to_R(a.q, m.R);
-  m.t[0] = a.t[0]; m.t[1] = a.t[1]; m.t[2] = a.t[2]; m.s = a.s;
-}
-__device__ __forceinline__ void sim3_proj(const Sim3M& m, const double* x, const double* K, double& u, double& v) {
-  double rx[3];
-  mat3_vec(m.R, x, rx);
-  const double X = m.s * rx[0] + m.t[0], Y = m.s * rx[1] + m.t[1], Z = m.s * rx[2] + m.t[2];
-  u = K[0] * X / Z + K[2];
-  v = K[1] * Y / Z + K[3];
-}
-
-__global__ void __launch_bounds__(256) k_optimize_sim3(double* __restrict__ S12io, int fix_scale, const double* __restrict__ P1c,
-                                                       const double* __restrict__ P2c, const double* __restrict__ obs1,
-                                                       const double* __restrict__ obs2, const double* __restrict__ w1,
-                                                       const double* __restrict__ w2, int N, const double* __restrict__ Kio,
-                                                       double th2, uint8_t* __restrict__ inlier, int32_t* __restrict__ nin_out,
-                                                       double* __restrict__ chi_scratch, uint8_t* __restrict__ flag_scratch) {
-  __shared__ double s_park[256 * 37];   // the 36 sums of a Jacobian pass in ONE pass through LDS
-  __shared__ double s_part[4 * 36];
-  __shared__ double s_sum[36];
-  __shared__ Sim3d s_S, s_bak;
-  __shared__ Sim3M s_M[30];   // [0] S, [1] S^-1, [2+2d] S+d, [3+2d] (S+d)^-1, [16+2d] S-d, [17+2d] (S-d)^-1
-  __shared__ double s_K[8];
-  __shared__ double s_lambda, s_ni, s_cur, s_ini, s_rho;
-  __shared__ int s_ctl, s_qmax, s_nbad, s_cnt;
-  const int tid = threadIdx.x;
-  double* chi12 = chi_scratch;
-  double* chi21 = chi_scratch + N;
-  uint8_t* alive = flag_scratch;
-  uint8_t* robust = flag_scratch + N;
-  if (tid < 8) s_K[tid] = Kio[tid];
-  if (tid == 0) {
-    for (int i = 0; i < 4; i++) s_S.q[i] = S12io[i];
-    for (int i = 0; i < 3; i++) s_S.t[i] = S12io[4 + i];
-    s_S.s = S12io[7];
-  }
-  for (int i = tid; i < N; i += 256) { alive[i] = 1; robust[i] = 1; inlier[i] = 0; chi12[i] = 0; chi21[i] = 0; }
-  __syncthreads();
-  const double deltaHuber = (double)sqrtf((float)th2);
-
-  // refreshes s_M[0..1] (jac=false) or all 30 maps (jac=true) from s_S
-  auto prepare = [&](bool jac) {
-    if (tid == 0) { sim3_to_map(s_S, s_M[0]); Sim3d Si; sim3_inv(s_S, Si); sim3_to_map(Si, s_M[1]); }
-    if (jac && tid >= 64 && tid < 78) {
-      const int k = tid - 64, d = k >> 1, sgn = k & 1;
-      double u[7] = {0, 0, 0, 0, 0, 0, 0};
-      u[d] = sgn ? -1e-9 : 1e-9;
-      if (fix_scale) u[6] = 0;
-      Sim3d E, Sx, Sxi;
-      sim3_exp(u, E);
-      sim3_mul(E, s_S, Sx);
-      sim3_inv(Sx, Sxi);
-      sim3_to_map(Sx, s_M[(sgn ? 16 : 2) + 2 * d]);
-      sim3_to_map(Sxi, s_M[(sgn ? 17 : 3) + 2 * d]);
-    }
-    __syncthreads();
-  };
-  auto eval = [&](bool jac) {
-    prepare(jac);
-    double acc[36];
-#pragma unroll
-    for (int i = 0; i < 36; i++) acc[i] = 0;
-    for (int i = tid; i < N; i += 256) {
-      if (!alive[i]) continue;
-      const double* x1 = P1c + 3 * i; const double* x2 = P2c + 3 * i;
-      double u, v;
-      sim3_proj(s_M[0], x2, s_K, u, v);
-      const double a0 = obs1[2 * i] - u, a1 = obs1[2 * i + 1] - v;
-      sim3_proj(s_M[1], x1, s_K + 4, u, v);
-      const double b0 = obs2[2 * i] - u, b1 = obs2[2 * i + 1] - v;
-      const double c12 = w1[i] * (a0 * a0 + a1 * a1), c21 = w2[i] * (b0 * b0 + b1 * b1);
-      chi12[i] = c12; chi21[i] = c21;
-      const double dl = robust[i] ? deltaHuber : 0.0;
-      double r0a, r1a, r0b, r1b;
-      robustify(c12, dl, r0a, r1a);
-      robustify(c21, dl, r0b, r1b);
-      acc[35] += r0a;
-      acc[35] += r0b;
-      if (jac) {
-        double J12[14], J21[14];
-#pragma unroll
-        for (int d = 0; d < 7; d++) {
-          double up, vp, um, vm;
-          sim3_proj(s_M[2 + 2 * d], x2, s_K, up, vp); sim3_proj(s_M[16 + 2 * d], x2, s_K, um, vm);
-          // e(+d) - e(-d) = (obs - proj+) - (obs - proj-)
-          J12[d] = 5e8 * ((obs1[2 * i] - up) - (obs1[2 * i] - um)); J12[7 + d] = 5e8 * ((obs1[2 * i + 1] - vp) - (obs1[2 * i + 1] - vm));
-          sim3_proj(s_M[3 + 2 * d], x1, s_K + 4, up, vp); sim3_proj(s_M[17 + 2 * d], x1, s_K + 4, um, vm);
-          J21[d] = 5e8 * ((obs2[2 * i] - up) - (obs2[2 * i] - um)); J21[7 + d] = 5e8 * ((obs2[2 * i + 1] - vp) - (obs2[2 * i + 1] - vm));
-        }
-#pragma unroll
-        for (int pass = 0; pass < 2; pass++) {
-          const double* J = pass ? J21 : J12;
-          const double e0 = pass ? b0 : a0, e1 = pass ? b1 : a1, w0 = pass ? w2[i] : w1[i], r1 = pass ? r1b : r1a;
-          const double w = r1 * w0, wr0 = -w0 * e0 * r1, wr1 = -w0 * e1 * r1;
-          int t = 0;
-#pragma unroll
-          for (int p = 0; p < 7; p++) {
-            acc[28 + p] += J[p] * wr0 + J[7 + p] * wr1;
-#pragma unroll
-            for (int q = 0; q <= p; q++) acc[t++] += w * (J[p] * J[q] + J[7 + p] * J[7 + q]);
-          }
-        }
-      }
-    }
-    if (jac) block_sum_lds<36>(acc, s_park, s_part, s_sum);
-    else {          // a trial's chi2: one value (the full reduction here cost ~2 us per LM trial)
-      const double c = block_sum_one(acc[35], s_part);
-      if (tid == 0) s_sum[35] = c;
-      __syncthreads();
-    }
-  };
-  auto optimize = [&](int iters) {
-    for (int it = 0; it < iters; it++) {
-      eval(true);
-      double Hs[28], bs[7], xs[7];
-      if (tid == 0) {
-        s_cur = s_sum[35]; s_ini = s_sum[35];
-        for (int i = 0; i < 28; i++) Hs[i] = s_sum[i];
-        for (int i = 0; i < 7; i++) bs[i] = s_sum[28 + i];
-        if (it == 0) {
-          double mx = 0;
-          for (int p = 0; p < 7; p++) mx = fmax(mx, fabs(Hs[p * (p + 1) / 2 + p]));
-          s_lambda = 1e-5 * mx; s_ni = 2; s_nbad = 0;
-        }
-        s_qmax = 0;
-      }
-      __syncthreads();
-      while (true) {
-        if (tid == 0) {
-          s_bak = s_S;
-          // dense 7x7 Cholesky; ri[j] = 1 / L_jj by v_rsq_f64 + two Newton steps: no double-precision division or square root on
-          // this single lane (35 of them before: ~3 us per LM trial)
-          double Lm[28], ri[7];
-          bool ok = true;
-#pragma unroll
-          for (int i = 0; i < 7; i++)
-#pragma unroll
-            for (int j = 0; j <= i; j++) {
-              double sacc = Hs[i * (i + 1) / 2 + j] + (i == j ? s_lambda : 0.0);
-#pragma unroll
-              for (int k = 0; k < j; k++) sacc -= Lm[i * (i + 1) / 2 + k] * Lm[j * (j + 1) / 2 + k];
-              if (i == j) {
-                if (!(sacc > 0)) ok = false;
-                const double dd = sacc > 0 ? sacc : 1.0;
-                double y = __builtin_amdgcn_rsq(dd);
-                y = __builtin_fma(0.5 * y, __builtin_fma(-dd * y, y, 1.0), y);
-                y = __builtin_fma(0.5 * y, __builtin_fma(-dd * y, y, 1.0), y);
-                double sq = dd * y;
-                sq = __builtin_fma(0.5 * y, __builtin_fma(-sq, sq, dd), sq);
-                Lm[i * (i + 1) / 2 + i] = sq; ri[i] = y;
-              } else Lm[i * (i + 1) / 2 + j] = sacc * ri[j];
-            }
-          if (ok) {
-#pragma unroll
-            for (int i = 0; i < 7; i++) {
-              double sacc = bs[i];
-#pragma unroll
-              for (int k = 0; k < i; k++) sacc -= Lm[i * (i + 1) / 2 + k] * xs[k];
-              xs[i] = sacc * ri[i];
-            }
-#pragma unroll
-            for (int i = 6; i >= 0; i--) {
-              double sacc = xs[i];
-#pragma unroll
-              for (int k = i + 1; k < 7; k++) sacc -= Lm[k * (k + 1) / 2 + i] * xs[k];
-              xs[i] = sacc * ri[i];
-            }
-            double u[7];
-            for (int i = 0; i < 7; i++) u[i] = xs[i];
-            if (fix_scale) u[6] = 0;
-            Sim3d E, Sn;
-            sim3_exp(u, E);
-            sim3_mul(E, s_S, Sn);
-            s_S = Sn;
-          }
-          s_ctl = ok ? 1 : 0;
-        }
-        __syncthreads();
-        const bool okb = s_ctl != 0;
-        if (okb) eval(false);
-        if (tid == 0) {
-          const double tempChi = okb ? s_sum[35] : 1.7976931348623157e308;
-          double rho = s_cur - tempChi;
-          double scale = 0;
-          if (okb) for (int j = 0; j < 7; j++) scale += xs[j] * (s_lambda * xs[j] + bs[j]);
-          scale += 1e-3;
-          rho /= scale;
-          if (rho > 0 && isfinite(tempChi)) {
-            double alpha = 1. - f64_cube(2 * rho - 1);   // pow(2 rho - 1, 3) as the shared double-precision spec forms it (f64_spec.h)
-            alpha = fmin(alpha, 2. / 3.);
-            s_lambda *= fmax(1. / 3., alpha);
-            s_ni = 2;
-            s_cur = tempChi;
-          } else {
-            s_lambda *= s_ni; s_ni *= 2;
-            s_S = s_bak;
-          }
-          s_qmax++;
-          s_rho = rho;
-          s_ctl = (rho < 0 && s_qmax < 10) ? 1 : 0;
-        }
-        __syncthreads();
-        const int again = s_ctl;
-        __syncthreads();
-        if (!again) break;
-      }
-      if (tid == 0) {
-        int stop = 0;
-        if (s_qmax == 10 || s_rho == 0) stop = 1;
-        else {
-          if ((s_ini - s_cur) * 1e3 < s_ini) s_nbad++; else s_nbad = 0;
-          if (s_nbad >= 3) stop = 1;
-        }
-        s_ctl = stop;
-      }
-      __syncthreads();
-      const int stop = s_ctl;
-      __syncthreads();
-      if (stop) break;
-    }
-  };
-
-  optimize(5);
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
-  int bad = 0;
-  for (int i = tid; i < N; i += 256) {
-    if (chi12[i] > th2 || chi21[i] > th2) { alive[i] = 0; bad++; } else robust[i] = 0;
-  }
-  if (bad) atomicAdd(&s_cnt, bad);
-  __syncthreads();
-  const int nBad = s_cnt;
-  __syncthreads();
-  if (N - nBad < 10) {
-    if (tid == 0) *nin_out = 0;
-    return;
-  }
-  optimize(nBad > 0 ? 10 : 5);
-  prepare(false);
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
-  int in = 0;
-  for (int i = tid; i < N; i += 256) {
-    if (!alive[i]) continue;
-    double u, v;
-    sim3_proj(s_M[0], P2c + 3 * i, s_K, u, v);
-    const double a0 = obs1[2 * i] - u, a1 = obs1[2 * i + 1] - v;
-    sim3_proj(s_M[1], P1c + 3 * i, s_K + 4, u, v);
-    const double b0 = obs2[2 * i] - u, b1 = obs2[2 * i + 1] - v;
-    const double c12 = w1[i] * (a0 * a0 + a1 * a1), c21 = w2[i] * (b0 * b0 + b1 * b1);
-    if (!(c12 > th2 || c21 > th2)) { inlier[i] = 1; in++; }
-  }
-  if (in) atomicAdd(&s_cnt, in);
-  __syncthreads();
-  if (tid == 0) {
-    *nin_out = s_cnt;
-    for (int i = 0; i < 4; i++) S12io[i] = s_S.q[i];
-    for (int i = 0; i < 3; i++) S12io[4 + i] = s_S.t[i];
-    S12io[7] = s_S.s;
-  }
-}
-
-void ba_launch_optimize_sim3(hipStream_t s, double* S12io, int fix_scale, const double* P1c, const double* P2c,
-                             const double* obs1, const double* obs2, const double* w1, const double* w2, int N,
-                             const double* K, double th2, uint8_t* inlier, int32_t* nin, double* chi_scratch, uint8_t* flag_scratch) {
-  hipLaunchKernelGGL(k_optimize_sim3, dim3(1), dim3(256), 0, s, S12io, fix_scale, P1c, P2c, obs1, obs2, w1, w2, N, K, th2, inlier,
-                     nin, chi_scratch, flag_scratch);
-}
-
-// ------------------------------------------------------------------------------------------ Sim3Solver
-// Sim3Solver::ComputeSim3 (Horn 1987 closed form, reference src/Sim3Solver.cc:294-385) + CheckInliers (:387-408) for
-// a batch of RANSAC hypotheses, one wavefront each: the 3-point solve is wave-uniform (every lane computes it, no
-// communication), the N correspondences are strided over the lanes, inliers counted by ballots.  The minimal sets are
-// input (the reference draws them with DUtils::Random).  float / double split as in the reference except the 4x4
-// eigen-decomposition: cyclic Jacobi in double ("Horn spec", same as the oracle) instead of Eigen::EigenSolver<float>.
-// (jacobi4_dev: jacobi4.h)
-
-__global__ void __launch_bounds__(64) k_sim3_hypotheses(const float* __restrict__ P1c, const float* __restrict__ P2c,
-                                                        const float* __restrict__ max_err1, const float* __restrict__ max_err2,
-                                                        int N, const float* __restrict__ K, const int32_t* __restrict__ triples,
-                                                        int H, int fix_scale, float* __restrict__ T12,
-                                                        int32_t* __restrict__ n_inliers, uint8_t* __restrict__ mask) {
-  const int h = blockIdx.x, lane = threadIdx.x;
-  if (h >= H) return;
-  float P1[3][3], P2[3][3];
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const int idx = triples[3 * h + c];
-#pragma unroll
-    for (int r = 0; r < 3; r++) { P1[r][c] = P1c[3 * idx + r]; P2[r][c] = P2c[3 * idx + r]; }
-  }
-  float O1[3], O2[3], Pr1[3][3], Pr2[3][3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    O1[r] = ((P1[r][0] + P1[r][1]) + P1[r][2]) / 3.0f; O2[r] = ((P2[r][0] + P2[r][1]) + P2[r][2]) / 3.0f;
-#pragma unroll
-    for (int c = 0; c < 3; c++) { Pr1[r][c] = P1[r][c] - O1[r]; Pr2[r][c] = P2[r][c] - O2[r]; }
-  }
-  float M[3][3];
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) M[r][c] = (Pr2[r][0] * Pr1[c][0] + Pr2[r][1] * Pr1[c][1]) + Pr2[r][2] * Pr1[c][2];
-  const float N11 = M[0][0] + M[1][1] + M[2][2], N12 = M[1][2] - M[2][1], N13 = M[2][0] - M[0][2], N14 = M[0][1] - M[1][0];
-  const float N22 = M[0][0] - M[1][1] - M[2][2], N23 = M[0][1] + M[1][0], N24 = M[2][0] + M[0][2];
-  const float N33 = -M[0][0] + M[1][1] - M[2][2], N34 = M[1][2] + M[2][1], N44 = -M[0][0] - M[1][1] + M[2][2];
-  double A[4][4] = {{N11, N12, N13, N14}, {N12, N22, N23, N24}, {N13, N23, N33, N34}, {N14, N24, N34, N44}}, V[4][4];
-  jacobi4_dev(A, V);
-  int mi = 0;
-#pragma unroll
-  for (int k = 1; k < 4; k++) if (A[k][k] > A[mi][mi]) mi = k;
-  double q0 = V[0][0], vx = V[1][0], vy = V[2][0], vz = V[3][0];
-#pragma unroll
-  for (int k = 1; k < 4; k++) if (mi == k) { q0 = V[0][k]; vx = V[1][k]; vy = V[2][k]; vz = V[3][k]; }
-  const double vn = sqrt(vx * vx + vy * vy + vz * vz);
-  const double ang = atan2(vn, q0);
-  float R[3][3];
-  {
-    double ax = 0, ay = 0, az = 0;
-    if (vn > 0) { ax = vx / vn; ay = vy / vn; az = vz / vn; }
-    const double w = cos(ang), sh = sin(ang), x = sh * ax, y = sh * ay, z = sh * az;
-    R[0][0] = (float)(1 - 2 * (y * y + z * z)); R[0][1] = (float)(2 * (x * y - z * w)); R[0][2] = (float)(2 * (x * z + y * w));
-    R[1][0] = (float)(2 * (x * y + z * w)); R[1][1] = (float)(1 - 2 * (x * x + z * z)); R[1][2] = (float)(2 * (y * z - x * w));
-    R[2][0] = (float)(2 * (x * z - y * w)); R[2][1] = (float)(2 * (y * z + x * w)); R[2][2] = (float)(1 - 2 * (x * x + y * y));
-  }
-  float P3[3][3];
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) P3[r][c] = (R[r][0] * Pr2[0][c] + R[r][1] * Pr2[1][c]) + R[r][2] * Pr2[2][c];
-  float sc = 1.0f;
-  if (!fix_scale) {
-    float nom = 0, den = 0;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-      for (int r = 0; r < 3; r++) { nom += Pr1[r][c] * P3[r][c]; den += P3[r][c] * P3[r][c]; }
-    sc = (float)((double)nom / (double)den);
-  }
-  float t[3], sR[3][3], sRi[3][3], ti[3];
-#pragma unroll
-  for (int r = 0; r < 3; r++) t[r] = O1[r] - ((sc * R[r][0]) * O2[0] + (sc * R[r][1]) * O2[1] + (sc * R[r][2]) * O2[2]);
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) { sR[r][c] = sc * R[r][c]; sRi[r][c] = (float)((1.0 / sc) * R[c][r]); }
-#pragma unroll
-  for (int r = 0; r < 3; r++) ti[r] = (-sRi[r][0] * t[0] + -sRi[r][1] * t[1]) + -sRi[r][2] * t[2];
-  if (lane == 0) {
-    float* out = T12 + 13 * (size_t)h;
-    out[0] = sc;
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) out[1 + 3 * r + c] = R[r][c];
-#pragma unroll
-    for (int r = 0; r < 3; r++) out[10 + r] = t[r];
-  }
-  const float fx1 = K[0], fy1 = K[1], cx1 = K[2], cy1 = K[3], fx2 = K[4], fy2 = K[5], cx2 = K[6], cy2 = K[7];
-  int nin = 0;
-  for (int base = 0; base < N; base += 64) {
-    const int i = base + lane;
-    bool in = false;
-    if (i < N) {
-      const float X1[3] = {P1c[3 * i], P1c[3 * i + 1], P1c[3 * i + 2]}, X2[3] = {P2c[3 * i], P2c[3 * i + 1], P2c[3 * i + 2]};
-      float a[3], b[3];
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        a[r] = ((sR[r][0] * X2[0] + sR[r][1] * X2[1]) + sR[r][2] * X2[2]) + t[r];
-        b[r] = ((sRi[r][0] * X1[0] + sRi[r][1] * X1[1]) + sRi[r][2] * X1[2]) + ti[r];
-      }
-      const float p1x = fx1 * X1[0] / X1[2] + cx1, p1y = fy1 * X1[1] / X1[2] + cy1;   // FromCameraToImage
-      const float p2x = fx2 * X2[0] / X2[2] + cx2, p2y = fy2 * X2[1] / X2[2] + cy2;
-      const float u1 = fx1 * a[0] / a[2] + cx1, v1 = fy1 * a[1] / a[2] + cy1;
-      const float u2 = fx2 * b[0] / b[2] + cx2, v2 = fy2 * b[1] / b[2] + cy2;
-      const float d1x = p1x - u1, d1y = p1y - v1, d2x = u2 - p2x, d2y = v2 - p2y;
-      const float err1 = d1x * d1x + d1y * d1y, err2 = d2x * d2x + d2y * d2y;
-      in = err1 < max_err1[i] && err2 < max_err2[i];
-      mask[(size_t)h * N + i] = in ? 1 : 0;
-    }
-    nin += __popcll(__ballot(in));
-  }
-  if (lane == 0) n_inliers[h] = nin;
-}
-
-void ba_launch_sim3_hypotheses(hipStream_t s, const float* P1c, const float* P2c, const float* e1, const float* e2, int N,
-                               const float* K, const int32_t* triples, int H, int fix_scale, float* T12, int32_t* nin, uint8_t* mask) {
-  if (H > 0) hipLaunchKernelGGL(k_sim3_hypotheses, dim3(H), dim3(64), 0, s, P1c, P2c, e1, e2, N, K, triples, H, fix_scale, T12, nin, mask);
-}
-
-// ---------------------------------------------------------------------------------- essential graph
-// Optimizer::OptimizeEssentialGraph numerics (reference src/Optimizer.cc:1389-1652): VertexSim3Expmap + EdgeSim3
-// (types_seven_dof_expmap.h:93-117), numeric Jacobians as g2o takes them (base_binary_edge.hpp:131-205).
-__device__ void sim3_log(const Sim3d& S, double* res) {   // g2o Sim3::log, sim3.h:128-197
-  const double sigma = log(S.s);
-  double R[9];
-  quat_to_R(S.q, R);
-  const double d = 0.5 * (R[0] + R[4] + R[8] - 1);
-  const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
-  double omega[3];
-  const double eps = 0.00001;
-  double A, B, C;
-  if (fabs(sigma) < eps) {
-    C = 1;
-    if (d > 1 - eps) { for (int i = 0; i < 3; i++) omega[i] = 0.5 * dR[i]; A = 1. / 2.; B = 1. / 6.; }
-    else {
-      const double theta = acos(d), theta2 = theta * theta;
-      for (int i = 0; i < 3; i++) omega[i] = theta / (2 * sqrt(1 - d * d)) * dR[i];
-      A = (1 - cos(theta)) / theta2; B = (theta - sin(theta)) / (theta2 * theta);
-    }
-  } else {
-    C = (S.s - 1) / sigma;
-    if (d > 1 - eps) {
-      const double sigma2 = sigma * sigma;
-      for (int i = 0; i < 3; i++) omega[i] = 0.5 * dR[i];
-      A = ((sigma - 1) * S.s + 1) / sigma2; B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);
-    } else {
-      const double theta = acos(d);
-      for (int i = 0; i < 3; i++) omega[i] = theta / (2 * sqrt(1 - d * d)) * dR[i];
-      const double theta2 = theta * theta, a = S.s * sin(theta), b = S.s * cos(theta), c = theta2 + sigma * sigma;
-      A = (a * sigma + (1 - b) * theta) / (theta * c);
-      B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
-    }
-  }
-  const double O[9] = {0, -omega[2], omega[1], omega[2], 0, -omega[0], -omega[1], omega[0], 0};
-  double W[9];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) {
-      const double o2 = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
-      W[3 * i + j] = A * O[3 * i + j] + B * o2 + C * (i == j ? 1.0 : 0.0);
-    }
-  const double c00 = W[4] * W[8] - W[5] * W[7], c01 = W[5] * W[6] - W[3] * W[8], c02 = W[3] * W[7] - W[4] * W[6];
-  const double det = W[0] * c00 + W[1] * c01 + W[2] * c02;
-  const double inv[9] = {c00, W[2] * W[7] - W[1] * W[8], W[1] * W[5] - W[2] * W[4],
-                         c01, W[0] * W[8] - W[2] * W[6], W[2] * W[3] - W[0] * W[5],
-                         c02, W[1] * W[6] - W[0] * W[7], W[0] * W[4] - W[1] * W[3]};
-  for (int i = 0; i < 3; i++) res[i] = omega[i];
-  for (int i = 0; i < 3; i++) res[3 + i] = (inv[3 * i] * S.t[0] + inv[3 * i + 1] * S.t[1] + inv[3 * i + 2] * S.t[2]) / det;
-  res[6] = sigma;
-}
-__device__ __forceinline__ void sim3_load(const double* p, Sim3d& S) {
-  S.q[0] = p[0]; S.q[1] = p[1]; S.q[2] = p[2]; S.q[3] = p[3]; S.t[0] = p[4]; S.t[1] = p[5]; S.t[2] = p[6]; S.s = p[7];
-}
-__device__ void pg_edge_error(const Sim3d& C, const Sim3d& Si, const Sim3d& Sj, double* e) {   // log(C * v1 * v2^-1)
-  Sim3d Sji, t1, t2;
-  sim3_inv(Sj, Sji);
-  sim3_mul(C, Si, t1);
-  sim3_mul(t1, Sji, t2);
-  sim3_log(t2, e);
-}
-// thread per edge: error, chi2 partial; JAC: the two 7x7 numeric Jacobians (14 columns x 2 perturbed error evaluations)
-template <bool JAC>
-__global__ void __launch_bounds__(256) k_pg_edge(PgView G) {
-  __shared__ double red[256];
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  double chi = 0;
-  if (k < G.E) {
-    const int vi = G.ev[2 * k], vj = G.ev[2 * k + 1];
-    Sim3d C, Si, Sj;
-    sim3_load(G.emeas + 8 * (size_t)k, C); sim3_load(G.S + 8 * (size_t)vi, Si); sim3_load(G.S + 8 * (size_t)vj, Sj);
-    double e[7];
-    pg_edge_error(C, Si, Sj, e);
-    // e_err belongs to the linearisation: b = -J^T e is rebuilt from it in EVERY trial of the iteration (k_pg_rhs), so the chi2-only
-    // pass at a trial state must leave it alone -- g2o builds b once per iteration (a rejected trial used to leave its errors here)
-    for (int a = 0; a < 7; a++) { if (JAC) G.e_err[7 * (size_t)k + a] = e[a]; chi += e[a] * e[a]; }
-    if (JAC) {
-      for (int side = 0; side < 2; side++) {
-        const int v = side ? vj : vi;
-        double* J = G.e_J + (size_t)k * 98 + 49 * side;
-        if (G.vidx[v] < 0) { for (int a = 0; a < 49; a++) J[a] = 0; continue; }
-        const Sim3d& X = side ? Sj : Si;
-        for (int d = 0; d < 7; d++) {
-          double e1[7], e2[7];
-          for (int sgn = 0; sgn < 2; sgn++) {
-            double u[7] = {0, 0, 0, 0, 0, 0, 0};
-            u[d] = sgn ? -1e-9 : 1e-9;
-            if (G.fix_scale) u[6] = 0;
-            Sim3d Ex, Xp;
-            sim3_exp(u, Ex);
-            sim3_mul(Ex, X, Xp);
-            pg_edge_error(C, side ? Si : Xp, side ? Xp : Sj, sgn ? e2 : e1);
-          }
-          for (int a = 0; a < 7; a++) J[7 * a + d] = (1.0 / (2 * 1e-9)) * (e1[a] - e2[a]);
-        }
-      }
-    }
-  }
-  red[threadIdx.x] = chi;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) G.partial[blockIdx.x] = red[0];
-}
-// 64 threads per non-zero 7x7 block (a >= b): H_ab = sum over its contributions J_a^T J_b (+ lambda on the diagonal),
-// fixed order, written into the tile-space matrix
-__global__ void __launch_bounds__(256) k_pg_blocks(PgView G, BaView T) {
-  const int blk = blockIdx.x * 4 + (threadIdx.x >> 6), t = threadIdx.x & 63;
-  if (blk >= G.nblk || t >= 49) return;
-  const int r = t / 7, c = t % 7;
-  const int a = G.blk_a[blk], b = G.blk_b[blk];
-  double acc = 0;
-  for (int i = G.blk_start[blk]; i < G.blk_start[blk + 1]; i++) {
-    const int w = G.blk_contrib[i];
-    const double* Ja = G.e_J + (size_t)(w >> 2) * 98 + 49 * ((w >> 1) & 1);
-    const double* Jb = G.e_J + (size_t)(w >> 2) * 98 + 49 * (w & 1);
-    double h = 0;
-#pragma unroll
-    for (int k = 0; k < 7; k++) h += Ja[7 * k + r] * Jb[7 * k + c];
-    acc += h;
-  }
-  if (a == b && r == c) acc += *T.lambda;
-  const int ra = (a / T.per_tile) * 64 + (a % T.per_tile) * T.dof, rb = (b / T.per_tile) * 64 + (b % T.per_tile) * T.dof;
-  T.S[(size_t)(ra + r) * T.ldS + rb + c] = acc;
-}
-// thread per free vertex: b_v = - sum J_v^T e  -> compact copy (computeScale) and the augmented rhs row
-__global__ void __launch_bounds__(256) k_pg_rhs(PgView G, BaView T) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= G.nfree) return;
-  double b[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int i = G.v_start[p]; i < G.v_start[p + 1]; i++) {
-    const int w = G.v_contrib[i];
-    const double* J = G.e_J + (size_t)(w >> 1) * 98 + 49 * (w & 1);
-    const double* e = G.e_err + 7 * (size_t)(w >> 1);
-    for (int r = 0; r < 7; r++) {
-      double g = 0;
-#pragma unroll
-      for (int a = 0; a < 7; a++) g += J[7 * a + r] * (-e[a]);
-      b[r] += g;
-    }
-  }
-  const int row = (p / T.per_tile) * 64 + (p % T.per_tile) * T.dof;
-  for (int r = 0; r < 7; r++) { G.bp[7 * (size_t)p + r] = b[r]; T.S[(size_t)T.n_pad * T.ldS + row + r] = b[r]; }
-  if (p == 0) T.S[(size_t)T.n_pad * T.ldS + T.n_pad] = 1e200;
-}
-// thread per free vertex: oplus (S <- Sim3(x) * S) and the computeScale partial sum x^T (lambda x + b)
-__global__ void __launch_bounds__(256) k_pg_update(PgView G, BaView T) {
-  __shared__ double red[256];
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  double sc = 0;
-  if (p < G.nfree) {
-    const double lambda = *T.lambda;
-    double u[7];
-    for (int r = 0; r < 7; r++) { u[r] = T.x[7 * (size_t)p + r]; sc += u[r] * (lambda * u[r] + G.bp[7 * (size_t)p + r]); }
-    if (G.fix_scale) u[6] = 0;
-    double* Sp = G.S + 8 * (size_t)G.free_v[p];
-    Sim3d X, Ex, Xn;
-    sim3_load(Sp, X);
-    sim3_exp(u, Ex);
-    sim3_mul(Ex, X, Xn);
-    Sp[0] = Xn.q[0]; Sp[1] = Xn.q[1]; Sp[2] = Xn.q[2]; Sp[3] = Xn.q[3]; Sp[4] = Xn.t[0]; Sp[5] = Xn.t[1]; Sp[6] = Xn.t[2]; Sp[7] = Xn.s;
-  }
-  red[threadIdx.x] = sc;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) G.partial[blockIdx.x] = red[0];
 }
 
 // ------------------------------------------------------------------------------------- launchers
@@ -3721,24 +2538,6 @@ void ba_launch_points_exchange(hipStream_t s, const BaView& V, double* buf, bool
 }
 void ba_launch_edge_depth(hipStream_t s, const BaView& V, uint8_t* d_out) {
   hipLaunchKernelGGL(k_edge_depth, dim3(cdiv(V.E, 256)), dim3(256), 0, s, V, d_out);
-}
-
-void pg_launch_edge_eval(hipStream_t s, const PgView& G, bool jac, double* d_scalars, int slot) {
-  const int nb = cdiv(G.E, 256);
-  if (jac) hipLaunchKernelGGL(k_pg_edge<true>, dim3(nb), dim3(256), 0, s, G);
-  else hipLaunchKernelGGL(k_pg_edge<false>, dim3(nb), dim3(256), 0, s, G);
-  hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(256), 0, s, G.partial, nb, d_scalars, slot);
-}
-void pg_launch_build(hipStream_t s, const PgView& G, const BaView& T) {
-  hipLaunchKernelGGL(k_zero_tiles, dim3(T.n_nz), dim3(256), 0, s, T.S, T.ldS, T.nz_tiles);
-  hipLaunchKernelGGL(k_pg_blocks, dim3(cdiv(G.nblk, 4)), dim3(256), 0, s, G, T);
-  hipLaunchKernelGGL(k_pg_rhs, dim3(cdiv(G.nfree, 256)), dim3(256), 0, s, G, T);
-  hipLaunchKernelGGL(k_pad_identity, dim3(cdiv(T.n_pad, 256)), dim3(256), 0, s, T);
-}
-void pg_launch_update(hipStream_t s, const PgView& G, const BaView& T, double* d_scalars, int slot_scale) {
-  const int nb = cdiv(G.nfree, 256);
-  hipLaunchKernelGGL(k_pg_update, dim3(nb), dim3(256), 0, s, G, T);
-  hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(256), 0, s, G.partial, nb, d_scalars, slot_scale);
 }
 
 }  // namespace dvm

@@ -47,11 +47,13 @@
 #include <vector>
 
 #include "../../include/dvmslam_hip.h"
-#include "f64_spec.h"
 #include "ba_kernels.h"
+#include "f64_spec.h"
 #include "group_commit.h"
 #include "host_stage.h"
 #include "orb_pipeline.h"   // set_error / hip_check / DVM_HIP
+#include "proj_edge.h"
+#include "se3_f64.h"       // the small algebra, in the oracle's sequences
 
 namespace dvm {
 
@@ -116,97 +118,6 @@ struct BaWin {
   double *cl_ctl;                         // [4] 0: the solve succeeded, 1: the stop word as the leader saw it
 };
 
-// ------------------------------------------------------------------------------------------------ small algebra (the oracle's sequences)
-__device__ __forceinline__ void w_quat_to_R(const double* q, double* R) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-  R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-  R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
-__device__ __forceinline__ void w_R_to_quat(const double* R, double* q) {      // Eigen's quaternion-from-matrix
-  double t = R[0] + R[4] + R[8];
-  if (t > 0) {
-    t = sqrt(t + 1.0);
-    q[3] = 0.5 * t;
-    t = 0.5 / t;
-    q[0] = (R[7] - R[5]) * t; q[1] = (R[2] - R[6]) * t; q[2] = (R[3] - R[1]) * t;
-  } else {
-    int i = 0;
-    if (R[4] > R[0]) i = 1;
-    if (R[8] > R[i * 4]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    t = sqrt(R[i * 4] - R[j * 4] - R[k * 4] + 1.0);
-    q[i] = 0.5 * t;
-    t = 0.5 / t;
-    q[3] = (R[k * 3 + j] - R[j * 3 + k]) * t;
-    q[j] = (R[j * 3 + i] + R[i * 3 + j]) * t;
-    q[k] = (R[k * 3 + i] + R[i * 3 + k]) * t;
-  }
-}
-__device__ __forceinline__ void w_quat_normalize(double* q) {      // SE3Quat::normalizeRotation, se3quat.h:261-266
-  if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
-  const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
-}
-__device__ __forceinline__ void w_mat3_vec(const double* R, const double* v, double* o) {
-  o[0] = R[0] * v[0] + R[1] * v[1] + R[2] * v[2];
-  o[1] = R[3] * v[0] + R[4] * v[1] + R[5] * v[2];
-  o[2] = R[6] * v[0] + R[7] * v[1] + R[8] * v[2];
-}
-// T' = exp(u) * T, u = (omega, upsilon): SE3Quat::exp + operator* + normalizeRotation with the libm calls taken from f64_spec.h
-__device__ void w_se3_oplus(const double* T, const double* u, double* Tn) {
-  const double om0 = u[0], om1 = u[1], om2 = u[2];
-  const double theta = sqrt(om0 * om0 + om1 * om1 + om2 * om2);
-  const double O[9] = {0, -om2, om1, om2, 0, -om0, -om1, om0, 0};
-  double O2[9];
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c < 3; c++) O2[3 * r + c] = O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c] + O[3 * r + 2] * O[6 + c];
-  double R[9], Vm[9];
-  if (theta < 0.00001) {
-#pragma unroll
-    for (int k = 0; k < 9; k++) { R[k] = ((k % 4 == 0) ? 1.0 : 0.0) + O[k] + O2[k]; Vm[k] = R[k]; }
-  } else {
-    const double sn = f64_sin(theta), cs = f64_cos(theta);
-    const double a = sn / theta, bb = (1 - cs) / (theta * theta), c = (theta - sn) / f64_cube(theta);
-#pragma unroll
-    for (int k = 0; k < 9; k++) {
-      const double I = (k % 4 == 0) ? 1.0 : 0.0;
-      R[k] = I + a * O[k] + bb * O2[k];
-      Vm[k] = I + bb * O[k] + c * O2[k];
-    }
-  }
-  double dq[4], dt[3], Rd[9], rt[3], nq[4];
-  w_R_to_quat(R, dq);
-  w_quat_normalize(dq);
-  w_mat3_vec(Vm, u + 3, dt);
-  w_quat_to_R(dq, Rd);
-  w_mat3_vec(Rd, T, rt);
-  const double* q = T + 3;
-  nq[3] = dq[3] * q[3] - dq[0] * q[0] - dq[1] * q[1] - dq[2] * q[2];
-  nq[0] = dq[3] * q[0] + dq[0] * q[3] + dq[1] * q[2] - dq[2] * q[1];
-  nq[1] = dq[3] * q[1] + dq[1] * q[3] + dq[2] * q[0] - dq[0] * q[2];
-  nq[2] = dq[3] * q[2] + dq[2] * q[3] + dq[0] * q[1] - dq[1] * q[0];
-  w_quat_normalize(nq);
-  Tn[0] = dt[0] + rt[0]; Tn[1] = dt[1] + rt[1]; Tn[2] = dt[2] + rt[2];
-  Tn[3] = nq[0]; Tn[4] = nq[1]; Tn[5] = nq[2]; Tn[6] = nq[3];
-}
-__device__ __forceinline__ void w_robustify(double e, double delta, double& rho0, double& rho1) {   // robust_kernel_impl.cpp:68-81
-  if (delta <= 0 || e <= delta * delta) { rho0 = e; rho1 = 1.; }
-  else { const double s = sqrt(e); rho0 = 2 * s * delta - delta * delta; rho1 = delta / s; }
-}
-__device__ __forceinline__ void w_inv3(const double* M, double* Inv) {
-  const double a = M[0], b = M[1], c = M[2], d = M[3], e = M[4], f = M[5], g = M[6], h = M[7], i = M[8];
-  const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
-  const double id = 1.0 / det;
-  Inv[0] = (e * i - f * h) * id; Inv[1] = (c * h - b * i) * id; Inv[2] = (b * f - c * e) * id;
-  Inv[3] = (f * g - d * i) * id; Inv[4] = (a * i - c * g) * id; Inv[5] = (c * d - a * f) * id;
-  Inv[6] = (d * h - e * g) * id; Inv[7] = (b * g - a * h) * id; Inv[8] = (a * e - b * d) * id;
-}
-
 // ------------------------------------------------------------------------------------------------ the sequential sum
 // sum of v[0..n) in index order, s = ((0 + v0) + v1) + ..., by ONE wave: 64 values at a time go lane -> LDS, every lane then adds them
 // with uniform-address (broadcast) reads -- the chain of dependent v_add_f64 is the cost (8 cycles per value), the next 64 values
@@ -246,40 +157,28 @@ __device__ double wave_sequential_sum(const double* __restrict__ v, int n, doubl
 // ------------------------------------------------------------------------------------------------ edge pass
 // JAC = false: computeActiveErrors -- chi2 and rho of every edge at the state (poses, pts).  JAC = true: additionally linearizeOplus +
 // the edge's part of constructQuadraticForm: A (2x3), B (2x6), w = rho' Omega, wr = -Omega e rho', W = w B^T A, each into the row its
-// consumer will stream.
-template <bool JAC>
+// consumer will stream.  CAM: the window's camera (proj_edge.h); the pinhole camera is the only one these kernels are instantiated for.
+template <class CAM> __device__ __forceinline__ CAM win_cam(const BaWin& W);
+template <> __device__ __forceinline__ PoseCamPinhole win_cam<PoseCamPinhole>(const BaWin& W) { return PoseCamPinhole{W.fx, W.fy, W.cx, W.cy}; }
+template <bool JAC, class CAM>
 __device__ void win_edge_pass(const BaWin& W, const double* __restrict__ poses, const double* __restrict__ pts) {
+  const CAM cam = win_cam<CAM>(W);
   for (int k = threadIdx.x; k < W.E; k += kWinThreads) {
     const int p = W.e_pose[k], l = W.e_point[k];
     const double* T = poses + 7 * (size_t)p;
     const double* X = pts + 3 * (size_t)l;
-    double R[9], Xc[3];
-    w_quat_to_R(T + 3, R);
-    w_mat3_vec(R, X, Xc);
-    Xc[0] += T[0]; Xc[1] += T[1]; Xc[2] += T[2];
-    const double x = Xc[0], y = Xc[1], z = Xc[2];
-    const double info = W.e_info[k];
-    const double e0 = W.e_obs[2 * k] - (W.fx * x / z + W.cx);
-    const double e1 = W.e_obs[2 * k + 1] - (W.fy * y / z + W.cy);
-    const double chi2 = e0 * info * e0 + e1 * info * e1;
+    double R[9];
+    quat_to_R(T + 3, R);
+    const ProjEdge<CAM> e(cam, R, T, X, W.e_obs[2 * k], W.e_obs[2 * k + 1], W.e_info[k]);
     double r0, r1;
-    w_robustify(chi2, W.delta, r0, r1);
-    W.e_chi2[k] = chi2;
+    robustify(e.chi2, W.delta, r0, r1);
+    W.e_chi2[k] = e.chi2;
     W.e_rho[k] = r0;
     if (!JAC) continue;
-    const double J[6] = {-(W.fx / z), 0, W.fx * x / (z * z), 0, -(W.fy / z), W.fy * y / (z * z)};
     double A[6], B[12];
-#pragma unroll
-    for (int r = 0; r < 2; r++)
-#pragma unroll
-      for (int c = 0; c < 3; c++) A[3 * r + c] = J[3 * r] * R[c] + J[3 * r + 1] * R[3 + c] + J[3 * r + 2] * R[6 + c];
-    const double S[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
-#pragma unroll
-    for (int r = 0; r < 2; r++)
-#pragma unroll
-      for (int c = 0; c < 6; c++) B[6 * r + c] = J[3 * r] * S[c] + J[3 * r + 1] * S[6 + c] + J[3 * r + 2] * S[12 + c];
-    const double w = r1 * info;
-    const double wr0 = -info * e0 * r1, wr1 = -info * e1 * r1;
+    e.jac_point(cam, R, A);
+    e.jac_pose(cam, B);
+    const double w = e.w(r1), wr0 = e.wr0(r1), wr1 = e.wr1(r1);
     double* oB = W.rowB + kRowB * (size_t)k;
     double* oA = W.rowA + kRowA * (size_t)W.lpos[k];
 #pragma unroll
@@ -294,7 +193,7 @@ __device__ void win_edge_pass(const BaWin& W, const double* __restrict__ poses, 
 #pragma unroll
       for (int a = 0; a < 6; a++)
 #pragma unroll
-        for (int b = 0; b < 3; b++) oW[3 * a + b] = w * (B[a] * A[b] + B[6 + a] * A[3 + b]);
+        for (int b = 0; b < 3; b++) oW[3 * a + b] = proj_edge_hpl(w, B, A, a, b);
     }
   }
 }
@@ -767,8 +666,8 @@ __device__ void win_schur(const BaWin& W, double* S, double* rhs, double* stage,
       for (int i = 0; i < 9; i++) D[i] = h[i];
       const double g[3] = {h[9], h[10], h[11]};
       D[0] += lambda; D[4] += lambda; D[8] += lambda;
-      w_inv3(D, Di);
-      w_mat3_vec(Di, g, d3);
+      inv3(D, Di);
+      mat3_vec(Di, g, d3);
       double* o = W.DD + kRowH * (size_t)(cur.la + tid);
 #pragma unroll
       for (int i = 0; i < 9; i++) { h[i] = Di[i]; o[i] = Di[i]; }
@@ -937,7 +836,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window(const BaWin* __restri
     // computeActiveErrors + robust chi2 + buildSystem at the accepted state.  (From the second iteration on g2o recomputes the chi2
     // of the state the last accepted trial has just evaluated: same state, same sums, same bits -- only the Jacobians are new.)
     lap(15);
-    win_edge_pass<true>(W, poses, pts);
+    win_edge_pass<true, PoseCamPinhole>(W, poses, pts);
     __syncthreads();
     lap(0);
     if (it == 0) {
@@ -997,7 +896,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window(const BaWin* __restri
           }
           const double c[3] = {c0, c1, c2};
           double xl[3];
-          w_mat3_vec(W.DD + kRowH * (size_t)li, c, xl);
+          mat3_vec(W.DD + kRowH * (size_t)li, c, xl);
           W.x[n + 3 * (size_t)li] = xl[0]; W.x[n + 3 * (size_t)li + 1] = xl[1]; W.x[n + 3 * (size_t)li + 2] = xl[2];
         }
       }
@@ -1007,7 +906,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window(const BaWin* __restri
       // successful solve, optimization_algorithm_levenberg.cpp:107-127); computeScale's terms x_j (lambda x_j + b_j)
       for (int i = tid; i < W.nfree; i += NT) {
         const int p = W.free_pose[i];
-        w_se3_oplus(poses + 7 * (size_t)p, W.x + 6 * (size_t)i, poses_t + 7 * (size_t)p);
+        se3_oplus(poses + 7 * (size_t)p, W.x + 6 * (size_t)i, poses_t + 7 * (size_t)p);
       }
       for (int t = tid; t < nl; t += NT) {
         const int l = W.act_pt[t / 3];
@@ -1017,7 +916,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window(const BaWin* __restri
       for (int j = tid; j < nl; j += NT) { const double xj = W.x[n + j]; W.terms[n + j] = xj * (lambda * xj + W.HB[kRowH * (size_t)(j / 3) + 9 + j % 3]); }
       __syncthreads();
       lap(8);
-      win_edge_pass<false>(W, poses_t, pts_t);
+      win_edge_pass<false, PoseCamPinhole>(W, poses_t, pts_t);
       __syncthreads();
       lap(9);
       if (wave == 0) { const double c = wave_sequential_sum(W.e_rho, W.E, seqbuf); if (tid == 0) ctl[1] = c; }
@@ -1061,7 +960,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window(const BaWin* __restri
   // caller downloads them (Optimizer_shim's LocalBundleAdjustment erases observations on chi2 > 5.991).  Evaluate the edges at the
   // unchanged input state, so that what leaves is the chi2 OF the state that leaves -- never the previous tenant of the buffer.
   if (it_done == 0) {
-    win_edge_pass<false>(W, poses, pts);
+    win_edge_pass<false, PoseCamPinhole>(W, poses, pts);
     __syncthreads();
     if (wave == 0) { const double c = wave_sequential_sum(W.e_rho, W.E, seqbuf); if (tid == 0) { st->chi2_initial = c; chi_last = c; } }
     __syncthreads();
@@ -1073,8 +972,8 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window(const BaWin* __restri
     const double* T = poses + 7 * (size_t)W.e_pose[k];
     const double* X = pts + 3 * (size_t)W.e_point[k];
     double R[9], Xc[3];
-    w_quat_to_R(T + 3, R);
-    w_mat3_vec(R, X, Xc);
+    quat_to_R(T + 3, R);
+    mat3_vec(R, X, Xc);
     W.e_depth[k] = (Xc[2] + T[2]) > 0.0 ? 1 : 0;
   }
   if (tid == 0) {
@@ -1160,12 +1059,13 @@ __device__ __forceinline__ void w_dinv(const double* __restrict__ h, double lamb
   for (int i = 0; i < 9; i++) D[i] = h[i];
   const double g3[3] = {h[9], h[10], h[11]};
   D[0] += lambda; D[4] += lambda; D[8] += lambda;
-  w_inv3(D, Di);
-  w_mat3_vec(Di, g3, d3);
+  inv3(D, Di);
+  mat3_vec(Di, g3, d3);
 }
 
-template <bool JAC>
+template <bool JAC, class CAM>
 __device__ void cl_edge_pass(const BaWin& W, const ClusterCtx& C, const double* __restrict__ poses, const double* __restrict__ pts) {
+  const CAM cam = win_cam<CAM>(W);
   const size_t Fp = (size_t)W.Fp;
   for (int p = C.g; p < kParts; p += C.G) {
     int lo, hi;
@@ -1174,44 +1074,29 @@ __device__ void cl_edge_pass(const BaWin& W, const ClusterCtx& C, const double* 
       const int pi = W.e_pose[k], l = W.e_point[k];
       const double* T = poses + 7 * (size_t)pi;
       const double* X = pts + 3 * (size_t)l;
-      double R[9], Xc[3];
-      w_quat_to_R(T + 3, R);
-      w_mat3_vec(R, X, Xc);
-      Xc[0] += T[0]; Xc[1] += T[1]; Xc[2] += T[2];
-      const double x = Xc[0], y = Xc[1], z = Xc[2];
-      const double info = W.e_info[k];
-      const double e0 = W.e_obs[2 * k] - (W.fx * x / z + W.cx);
-      const double e1 = W.e_obs[2 * k + 1] - (W.fy * y / z + W.cy);
-      const double chi2 = e0 * info * e0 + e1 * info * e1;
+      double R[9];
+      quat_to_R(T + 3, R);
+      const ProjEdge<CAM> e(cam, R, T, X, W.e_obs[2 * k], W.e_obs[2 * k + 1], W.e_info[k]);
       double r0, r1;
-      w_robustify(chi2, W.delta, r0, r1);
-      W.chi_s[k] = chi2;
+      robustify(e.chi2, W.delta, r0, r1);
+      W.chi_s[k] = e.chi2;
       W.e_rho[k] = r0;
       if (!JAC) continue;
-      const double J[6] = {-(W.fx / z), 0, W.fx * x / (z * z), 0, -(W.fy / z), W.fy * y / (z * z)};
       double A[6], B[12];
-#pragma unroll
-      for (int r = 0; r < 2; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) A[3 * r + c] = J[3 * r] * R[c] + J[3 * r + 1] * R[3 + c] + J[3 * r + 2] * R[6 + c];
-      const double w = r1 * info;
-      const double wr0 = -info * e0 * r1, wr1 = -info * e1 * r1;
+      e.jac_point(cam, R, A);
+      const double w = e.w(r1), wr0 = e.wr0(r1), wr1 = e.wr1(r1);
       double2* oA = reinterpret_cast<double2*>(W.rowA + kRowA * (size_t)k);
       oA[0] = make_double2(A[0], A[1]); oA[1] = make_double2(A[2], A[3]); oA[2] = make_double2(A[4], A[5]);
       oA[3] = make_double2(w, wr0); oA[4] = make_double2(wr1, 0.0);
       if (k < W.F) {
-        const double S[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
-#pragma unroll
-        for (int r = 0; r < 2; r++)
-#pragma unroll
-          for (int c = 0; c < 6; c++) B[6 * r + c] = J[3 * r] * S[c] + J[3 * r + 1] * S[6 + c] + J[3 * r + 2] * S[12 + c];
+        e.jac_pose(cam, B);     // (the pose half only for the rows that have one: a free camera's)
 #pragma unroll
         for (int i = 0; i < 12; i++) W.Bs[i * Fp + k] = B[i];
         W.Bs[12 * Fp + k] = w; W.Bs[13 * Fp + k] = wr0; W.Bs[14 * Fp + k] = wr1;
 #pragma unroll
         for (int a = 0; a < 6; a++)
 #pragma unroll
-          for (int b2 = 0; b2 < 3; b2++) W.Ws[(3 * a + b2) * Fp + k] = w * (B[a] * A[b2] + B[6 + a] * A[3 + b2]);
+          for (int b2 = 0; b2 < 3; b2++) W.Ws[(3 * a + b2) * Fp + k] = proj_edge_hpl(w, B, A, a, b2);
       }
     }
   }
@@ -1407,7 +1292,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window_cluster(const BaWin* 
     //  as the tile solver's loop and k_pose_optimize do -- was measured: 2.92 -> 3.27 ms for 32 windows.  The pass it saves is 15 us, but
     //  two sets of rows are 260 MB for 32 windows and no longer stay in the 256 MB memory-side cache: the accumulation behind it went from
     //  27 to 48 us, the W Dinv pass from 18 to 25.)
-    cl_edge_pass<true>(W, C, poses, pts);
+    cl_edge_pass<true, PoseCamPinhole>(W, C, poses, pts);
     if (it == 0) cluster_partial_sums(W, C, W.e_rho, W.E, 0, red);
     CL_BARRIER();
     ph = 1;
@@ -1509,7 +1394,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window_cluster(const BaWin* 
               c0 -= W.Cs[r]; c1 -= W.Cs[Fp + r]; c2 -= W.Cs[2 * Fp + r];
             }
             const double c[3] = {c0, c1, c2};
-            w_mat3_vec(Di, c, xl);
+            mat3_vec(Di, c, xl);
 #pragma unroll
             for (int a = 0; a < 3; a++) W.x[n + 3 * (size_t)li + a] = xl[a];
           } else {
@@ -1526,14 +1411,14 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window_cluster(const BaWin* 
         part_range(W.nfree, p, lo, hi);
         for (int i = lo + tid; i < hi; i += NT) {
           const int pp = W.free_pose[i];
-          w_se3_oplus(poses + 7 * (size_t)pp, W.x + 6 * (size_t)i, poses_t + 7 * (size_t)pp);
+          se3_oplus(poses + 7 * (size_t)pp, W.x + 6 * (size_t)i, poses_t + 7 * (size_t)pp);
 #pragma unroll
           for (int a = 0; a < 6; a++) { const double xj = W.x[6 * i + a]; W.terms[6 * i + a] = xj * (lambda * xj + W.bp[6 * i + a]); }
         }
       }
       CL_BARRIER();
       ph = 9;
-      cl_edge_pass<false>(W, C, poses_t, pts_t);
+      cl_edge_pass<false, PoseCamPinhole>(W, C, poses_t, pts_t);
       cluster_partial_sums(W, C, W.e_rho, W.E, 0, red);
       cluster_partial_sums(W, C, W.terms, n + nl, 1, red);
       CL_BARRIER();
@@ -1567,7 +1452,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window_cluster(const BaWin* 
     if (nBad >= 3) { stop_reason = 2; break; }
   }
   if (it_done == 0) {     // no iteration ran: the edges are evaluated at the unchanged input state (see k_ba_window)
-    cl_edge_pass<false>(W, C, poses, pts);
+    cl_edge_pass<false, PoseCamPinhole>(W, C, poses, pts);
     cluster_partial_sums(W, C, W.e_rho, W.E, 0, red);
     CL_BARRIER();
     chi_last = cluster_total(W, 0);
@@ -1586,8 +1471,8 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window_cluster(const BaWin* 
       const double* T = poses + 7 * (size_t)W.e_pose[k];
       const double* X = pts + 3 * (size_t)W.e_point[k];
       double R[9], Xc[3];
-      w_quat_to_R(T + 3, R);
-      w_mat3_vec(R, X, Xc);
+      quat_to_R(T + 3, R);
+      mat3_vec(R, X, Xc);
       const int ko = W.e_orig[k];
       W.e_depth[ko] = (Xc[2] + T[2]) > 0.0 ? 1 : 0;
       W.e_chi2[ko] = W.chi_s[k];

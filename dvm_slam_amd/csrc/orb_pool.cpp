@@ -162,7 +162,7 @@ extern "C" int dvm_orb_pool_extract(dvm_orb_pool* pool, const uint8_t* img, int 
 // writes its correspondences straight into its slot, the kernel reads them once (register-resident up to kPoolPoseMaxN per frame)
 // and writes pose, outlier flags and inlier count back in place -- no copy command around the launch.
 namespace {
-constexpr int kPoolPoseMaxN = 1280;   // correspondences per frame the kernel keeps in registers (ba_kernels.hip: kPoseEdgesPerThread x 256)
+constexpr int kPoolPoseMaxN = 1280;   // correspondences per frame the kernel keeps in registers (pose_kernels.hip: kPoseEdgesPerThread x 256)
 struct PoseLane {
   double *pose_in = nullptr, *X = nullptr, *obs = nullptr, *w = nullptr, *pose_out = nullptr, *chi = nullptr;   // mapped host (chi: device)
   int32_t *n = nullptr, *ninl = nullptr;

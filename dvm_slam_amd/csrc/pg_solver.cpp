@@ -4,7 +4,7 @@
 // "SE3 Pose Recovering": VertexSim3Expmap / EdgeSim3 with identity information, g2o's numeric Jacobians,
 // OptimizationAlgorithmLevenberg with setUserLambdaInit(1e-16), optimize(20).  The sparse 7x7-block system goes through
 // the same tile Cholesky as the bundle adjustment (nested-dissection order, elimination-tree level schedule; 9 Sim3
-// vertices per 64-row tile); the LM control flow runs here, every numerical step is a HIP kernel (ba_kernels.hip).
+// vertices per 64-row tile); the LM control flow runs here, every numerical step is a HIP kernel (pg_kernels.hip; the factorisation and solve are the tile solver's, ba_kernels.hip).
 #include <algorithm>
 #include <chrono>
 #include <cmath>

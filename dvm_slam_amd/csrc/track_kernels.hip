@@ -6,7 +6,7 @@
 //                    :1730-1745, replayed from the ranked candidate lists of k_match_window_ranked
 //   k_track_gather   Optimizer::PoseOptimization's edge list (src/Optimizer.cc:768-838): the matched keypoints in keypoint order
 //   k_track_finish   the outlier flags back in keypoint order, Tracking.cc:2636-2660 (outlier matches dropped, nmatchesMap)
-// The pose itself is k_pose_optimize (ba_kernels.hip), launched between the last two.
+// The pose itself is k_pose_optimize (pose_kernels.hip), launched between the last two.
 // The second half, Tracking::TrackLocalMap (dvm_track_local_map), runs on the grid and mvKeysUn the first half left:
 //   k_track_local_prologue  SearchLocalPoints (Tracking.cc:3041-3106) up to the matcher's queries
 //   k_track_claims<true>    SearchByProjection(F, vpMapPoints)'s epilogue (ORBmatcher.cc:75-131)

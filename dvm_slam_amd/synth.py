@@ -368,6 +368,15 @@ def small_window_problem(n_kf: int = 2, n_pts: int = 150, seed: int = 1, noise_p
                 inv_sigma2=inv_sigma2, intrinsics=np.array([FX, FY, CX, CY]))
 
 
+def with_fy(pr: dict, fy_new: float) -> dict:
+    """The scene of ba_problem() / small_window_problem() through a camera with fy = fy_new (fx != fy): every observation's v is rescaled
+    about cy by fy_new / fy, so the scene stays consistent with the new intrinsics.  Returns a new dict; `pr` is left as it is."""
+    fx, fy, cx, cy = pr["intrinsics"]
+    obs = pr["obs"].copy()
+    obs[:, 1] = cy + (obs[:, 1] - cy) * (fy_new / fy)
+    return dict(pr, obs=obs, intrinsics=np.array([fx, fy_new, cx, cy]))
+
+
 def vocabulary(k: int = 10, L: int = 3, seed: int = 0x0B0C, ragged: bool = True, stop_frac: float = 0.02):
     """Synthetic DBoW2 vocabulary tree (ORBvoc.txt is not shipped with the reference: .MISSING_LARGE_BLOBS).
     Breadth-first node ids, root = 0, depth L, fan-out k (6..k when `ragged`), random 256-bit node descriptors,

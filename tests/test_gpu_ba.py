@@ -34,7 +34,20 @@ def _run_both(capi, oracle, pr, delta, iters):
 def test_ba_matches_oracle(capi, oracle, n_kf, n_pts, delta, iters):
     from dvm_slam_amd import synth
     pr = synth.ba_problem(n_kf=n_kf, n_pts=n_pts, seed=n_kf * 31 + n_pts)
-    (po_, pto, so, chio), (pg, ptg, sg, chig, depth) = _run_both(capi, oracle, pr, delta, iters)
+    _assert_matches_oracle(*_run_both(capi, oracle, pr, delta, iters))
+
+
+def test_ba_matches_oracle_with_fx_ne_fy(capi, oracle):
+    """synth's camera has fx == fy: the smallest problem above on the tile solver (11 free cameras) through fy = 163, the observations' v
+    rescaled about cy, against the oracle on the same intrinsics -- the same assertions."""
+    from dvm_slam_amd import synth
+    pr = synth.with_fy(synth.ba_problem(n_kf=12, n_pts=300, seed=12 * 31 + 300), 163.0)
+    assert pr["intrinsics"][0] != pr["intrinsics"][1] and pr["intrinsics"][2] != pr["intrinsics"][3]
+    _assert_matches_oracle(*_run_both(capi, oracle, pr, np.sqrt(5.991), 10))
+
+
+def _assert_matches_oracle(o, g):
+    (po_, pto, so, chio), (pg, ptg, sg, chig, depth) = o, g
     assert sg["iterations"] == so["iterations"]
     assert sg["trials"] == so["trials"], "LM accept/reject sequence differs"
     assert sg["stop_reason"] == so["stop_reason"]

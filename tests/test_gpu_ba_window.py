@@ -82,6 +82,18 @@ def test_small_local_windows_are_bit_identical(oracle, n_kf, seed):
     _assert_identical(capi.ba_optimize_windows([w10])[0], _oracle(oracle, dict(w, poses=o5[0], points=o5[1], iterations=10)), "second round")
 
 
+@pytest.mark.parametrize("n_kf,seed", [(2, 0), (4, 1)])
+def test_windows_with_fx_ne_fy_are_bit_identical(oracle, n_kf, seed):
+    """synth's camera has fx == fy, under which a kernel that swapped the two focal lengths would pass every case above: the same scenes
+    through fy = 163 (the observations' v rescaled about cy; cx != cy as everywhere), against the oracle on the same intrinsics."""
+    pr = synth.with_fy(synth.small_window_problem(n_kf, 120, seed=250 + seed), 163.0)
+    assert pr["intrinsics"][0] != pr["intrinsics"][1] and pr["intrinsics"][2] != pr["intrinsics"][3]
+    w = _window(pr, DELTA, 10)
+    g = capi.ba_optimize_windows([w])[0]
+    _assert_identical(g, _oracle(oracle, w), f"kf {n_kf} seed {seed}")
+    assert g["stats"]["iterations"] >= 3
+
+
 def test_weak_gauge_problems_that_no_tolerance_covers(oracle):
     """The class the soak kept reporting: ring-scene toys with one free camera and two-view landmarks.  The oracle
     run on the SAME problem with its edges in another order lands up to 1e-1 away from itself -- and the window kernel lands on the

@@ -89,6 +89,18 @@ def test_fast_windows_small_and_degenerate(oracle):
     assert np.array_equal(g["points"], pr["points"])
 
 
+def test_fast_windows_with_fx_ne_fy(oracle):
+    """synth's camera has fx == fy: the smallest local window (four keyframes) through fy = 163, the observations' v rescaled about cy,
+    against the oracle on the same intrinsics.  Two fixed keyframes hold the gauge, so that the oracle itself does not move by more than
+    TOL when the order of its sums changes (tools/ba_sensitivity.py) and the general contract applies."""
+    pr = synth.with_fy(synth.small_window_problem(4, 150, seed=750), 163.0)
+    assert pr["intrinsics"][0] != pr["intrinsics"][1] and pr["intrinsics"][2] != pr["intrinsics"][3]
+    w = _window(pr, 10, n_fixed=2)
+    g = capi.ba_optimize_windows([w], fast=True)[0]
+    _check_vs_oracle(oracle, w, g, "fx != fy")
+    assert g["stats"]["iterations"] >= 3
+
+
 def test_fast_windows_capacity():
     pr = synth.ba_problem(n_kf=40, n_pts=600, k_obs=6, seed=0x3E0, radius=12.0)
     with pytest.raises(capi.DvmError):
