@@ -831,8 +831,11 @@ int orc_search_by_sim3(int N1, const orc_keypoint* kps1, const uint8_t* desc1, c
                        const float* min1, const float* max1, const uint8_t* mdesc1, const float* T1w7, int N2,
                        const orc_keypoint* kps2, const uint8_t* desc2, const int32_t* mp2, const uint8_t* bad2, const float* P2,
                        const float* min2, const float* max2, const uint8_t* mdesc2, const float* T2w7,
-                       const float* bounds, const float* K, const float* S12_7, float th,
-                       const float* scale_factors, float log_scale_factor, int n_levels, int32_t* matches12, const int32_t* idx_in_kf2) {
+                       const float* bounds1, const float* bounds2, const float* K1, const float* S12_7, float th,
+                       const float* scale_factors1, float log_scale_factor1, int n_levels1, const float* scale_factors2,
+                       float log_scale_factor2, int n_levels2, int32_t* matches12, const int32_t* idx_in_kf2) {
+  // pKF1's fx, fy, cx, cy in BOTH directions (:1349-1352, :1405, :1481); the image test, the grid, PredictScale's tables and the radius
+  // are those of the keyframe searched: pKF2's for the points of pKF1 (:1409, :1421-1426), pKF1's for the points of pKF2 (:1485, :1497-1502)
   const so::SE3 T1w = load_se3(T1w7), T2w = load_se3(T2w7);
   const so::Sim3 S12 = load_sim3(S12_7), S21 = so::sim3_inverse(S12);
   std::vector<uint8_t> am1(N1, 0), am2(N2, 0);
@@ -843,10 +846,10 @@ int orc_search_by_sim3(int N1, const orc_keypoint* kps1, const uint8_t* desc1, c
       if (idx2 >= 0 && idx2 < N2) am2[idx2] = 1;
     }
   std::vector<int> vnMatch1, vnMatch2;
-  sim3_direction(N1, mp1, bad1, am1.data(), P1, min1, max1, mdesc1, T1w, S21, N2, kps2, desc2, bounds, K, th, scale_factors,
-                 log_scale_factor, n_levels, vnMatch1);
-  sim3_direction(N2, mp2, bad2, am2.data(), P2, min2, max2, mdesc2, T2w, S12, N1, kps1, desc1, bounds, K, th, scale_factors,
-                 log_scale_factor, n_levels, vnMatch2);
+  sim3_direction(N1, mp1, bad1, am1.data(), P1, min1, max1, mdesc1, T1w, S21, N2, kps2, desc2, bounds2, K1, th, scale_factors2,
+                 log_scale_factor2, n_levels2, vnMatch1);
+  sim3_direction(N2, mp2, bad2, am2.data(), P2, min2, max2, mdesc2, T2w, S12, N1, kps1, desc1, bounds1, K1, th, scale_factors1,
+                 log_scale_factor1, n_levels1, vnMatch2);
   int nFound = 0;
   for (int i1 = 0; i1 < N1; i1++) {
     const int idx2 = vnMatch1[i1];

@@ -158,8 +158,9 @@ int orc_search_by_sim3(int N1, const orc_keypoint* kps1, const uint8_t* desc1, c
                        const float* min1, const float* max1, const uint8_t* mdesc1, const float* T1w7, int N2,
                        const orc_keypoint* kps2, const uint8_t* desc2, const int32_t* mp2, const uint8_t* bad2, const float* P2,
                        const float* min2, const float* max2, const uint8_t* mdesc2, const float* T2w7,
-                       const float* bounds, const float* K, const float* S12_7, float th,
-                       const float* scale_factors, float log_scale_factor, int n_levels, int32_t* matches12, const int32_t* idx_in_kf2);
+                       const float* bounds1, const float* bounds2, const float* K1, const float* S12_7, float th,
+                       const float* scale_factors1, float log_scale_factor1, int n_levels1, const float* scale_factors2,
+                       float log_scale_factor2, int n_levels2, int32_t* matches12, const int32_t* idx_in_kf2);
 
 int orc_search_by_projection_reloc(int Nc, const orc_keypoint* kps_c, const uint8_t* desc_c, int32_t* mp_c, const float* bounds,
                                    const float* Tcw7, const float* K, int Nk, const orc_keypoint* kps_k,

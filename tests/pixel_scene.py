@@ -23,23 +23,24 @@ def _tex_to_plane():
     return np.array([[M_PER_PX, 0, -M_PER_PX * TEX_W / 2], [0, M_PER_PX, -M_PER_PX * TEX_H / 2], [0, 0, 1.0]])
 
 
-def homography_pix_to_tex(R, t):
+def homography_pix_to_tex(R, t, K=K):
     Kmat = np.array([[K[0], 0, K[2]], [0, K[1], K[3]], [0, 0, 1.0]])
     G = np.column_stack([R[:, 0], R[:, 1], Z0 * R[:, 2] + t])        # plane coordinates (a, b, 1) -> camera
     return np.linalg.inv(Kmat @ G @ _tex_to_plane())
 
 
-def render(n_frames, seed=synth.SEED_FRAMES):
+def render(n_frames, seed=synth.SEED_FRAMES, K=K):
+    """K: the camera (fx, fy, cx, cy) the frames are rendered through."""
     tex = synth.base_texture(seed, h=TEX_H, w=TEX_W)
     frames, poses = [], []
     for t in range(n_frames):
         R, tt = pose_at(t)
-        frames.append(synth._warp(tex, homography_pix_to_tex(R, tt), 480, 640))
+        frames.append(synth._warp(tex, homography_pix_to_tex(R, tt, K), 480, 640))
         poses.append((R, tt))
     return np.stack(frames), poses
 
 
-def backproject(kps, R, t):
+def backproject(kps, R, t, K=K):
     """Keypoints of a frame with pose (R, t) -> their points on the plane, world coordinates [n, 3]."""
     rays = np.column_stack([(kps["x"] - K[2]) / K[0], (kps["y"] - K[3]) / K[1], np.ones(len(kps))])
     rw = rays @ R                       # R^T ray

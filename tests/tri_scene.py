@@ -9,9 +9,11 @@ from dvm_slam_amd import synth
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 
 
-def scene(seed=0, n=600, baseline=0.6, depth=(2.0, 12.0), noise_px=0.5, wrong_frac=0.15, far_frac=0.1, K=(458.0, 457.0, 367.0, 248.0)):
+def scene(seed=0, n=600, baseline=0.6, depth=(2.0, 12.0), noise_px=0.5, wrong_frac=0.15, far_frac=0.1, K=(458.0, 457.0, 367.0, 248.0), K2=None):
+    """K: the first keyframe's camera; K2: the second's (None: the same)."""
     rng = np.random.default_rng(seed)
     K = np.asarray(K, np.float32)
+    K2 = K if K2 is None else np.asarray(K2, np.float32)
     sf = (1.2 ** np.arange(8)).astype(np.float32)
     sigma2 = (sf * sf).astype(np.float32)
 
@@ -33,7 +35,7 @@ def scene(seed=0, n=600, baseline=0.6, depth=(2.0, 12.0), noise_px=0.5, wrong_fr
     Pw = (Pc1 - t1) @ R1                                             # R1^T (Pc - t)
     Pc2 = Pw @ R2.T + t2
     uv1 = np.stack([K[0] * Pc1[:, 0] / Pc1[:, 2] + K[2], K[1] * Pc1[:, 1] / Pc1[:, 2] + K[3]], 1)
-    uv2 = np.stack([K[0] * Pc2[:, 0] / Pc2[:, 2] + K[2], K[1] * Pc2[:, 1] / Pc2[:, 2] + K[3]], 1)
+    uv2 = np.stack([K2[0] * Pc2[:, 0] / Pc2[:, 2] + K2[2], K2[1] * Pc2[:, 1] / Pc2[:, 2] + K2[3]], 1)
     oct1 = rng.integers(0, 8, n)
     d1 = np.linalg.norm(Pw - Ow1, axis=1); d2 = np.linalg.norm(Pw - Ow2, axis=1)
     # the octave the other view would see the point at, +- 1, some inconsistent
@@ -49,7 +51,7 @@ def scene(seed=0, n=600, baseline=0.6, depth=(2.0, 12.0), noise_px=0.5, wrong_fr
     idx2[wrong] = rng.integers(0, n, wrong.sum())                    # mismatches: reprojection / depth failures
     perm = rng.permutation(n)
     pairs = np.stack([np.arange(n)[perm], idx2[perm]], 1).astype(np.int32)
-    return dict(K1=K, K2=K, T1w=T1, T2w=T2, Ow1=Ow1, Ow2=Ow2, kps1=kps1, kps2=kps2, pairs=pairs, sigma2_1=sigma2, sigma2_2=sigma2,
+    return dict(K1=K, K2=K2, T1w=T1, T2w=T2, Ow1=Ow1, Ow2=Ow2, kps1=kps1, kps2=kps2, pairs=pairs, sigma2_1=sigma2, sigma2_2=sigma2,
                 sf1=sf, sf2=sf, ratio_factor=np.float32(1.5) * sf[1])
 
 
