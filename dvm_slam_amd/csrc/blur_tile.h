@@ -16,6 +16,45 @@ __device__ __forceinline__ uint32_t udot2(uint32_t a, uint32_t b, uint32_t c) {
   return __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, a), __builtin_bit_cast(us2_t, b), c, false);
 }
 
+// The per-pixel arithmetic of both passes, shared by the tile blur below and the descriptor kernel's patch blur
+// (orb_kernels.hip: k_orient_desc_blur) so that the two cannot drift.
+// GA = g0 | g1 << 8 | g2 << 16 | g3 << 24, GB = g2 | g1 << 8 | g0 << 16: the 8.8 taps as v_dot4_u32_u8 operands.
+// h-pass of 4 columns x 2 rows: a0..a2 / b0..b2 = three consecutive dwords of the two raw rows, byte k of a0 = the leftmost
+// tap (x - 3) of output column k.  o[k] = row a's 8.8 sum | row b's << 16.  (a2 / b2 only reach columns 1..3.)
+__device__ __forceinline__ void blur_h4x2(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t b0, uint32_t b1, uint32_t b2, uint32_t GA,
+                                          uint32_t GB, uint32_t (&o)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t wa0 = k ? __builtin_amdgcn_alignbyte(a1, a0, k) : a0, wa1 = k ? __builtin_amdgcn_alignbyte(a2, a1, k) : a1;
+    const uint32_t wb0 = k ? __builtin_amdgcn_alignbyte(b1, b0, k) : b0, wb1 = k ? __builtin_amdgcn_alignbyte(b2, b1, k) : b1;
+    const uint32_t ha = __builtin_amdgcn_udot4(wa1, GB, __builtin_amdgcn_udot4(wa0, GA, 0u, false), false);
+    const uint32_t hb = __builtin_amdgcn_udot4(wb1, GB, __builtin_amdgcn_udot4(wb0, GA, 0u, false), false);
+    o[k] = ha | (hb << 16);
+  }
+}
+// v-pass of one pixel: w0..w3 = the h-pass sums of rows (0,1) (2,3) (4,5) (6,-) as u16 pairs -> the 16.16 sum with the rounding
+// constant added.  W01 = g0 | g1 << 16, W23 = g2 | g3 << 16, W21 = g2 | g1 << 16, W0 = g0.
+__device__ __forceinline__ uint32_t blur_v1(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t W01, uint32_t W23, uint32_t W21,
+                                            uint32_t W0) {
+  return udot2(w3, W0, udot2(w2, W21, udot2(w1, W23, udot2(w0, W01, 32768u))));
+}
+// v-pass of one column x 4 rows: P[j] = the h-pass sums of rows (2j, 2j + 1) as a u16 pair; r0..r3 = output rows 0..3 (taps on
+// rows r .. r + 6).  (P[5] only meets a zero weight: row 3's last tap is row 9.)
+__device__ __forceinline__ void blur_v1x4(const uint32_t (&P)[6], uint32_t W01, uint32_t W23, uint32_t W21, uint32_t W0, uint32_t& r0,
+                                          uint32_t& r1, uint32_t& r2, uint32_t& r3) {
+  uint32_t Q[5];
+#pragma unroll
+  for (int j = 0; j < 5; j++) Q[j] = __builtin_amdgcn_alignbyte(P[j + 1], P[j], 2);
+  r0 = blur_v1(P[0], P[1], P[2], P[3], W01, W23, W21, W0);
+  r1 = blur_v1(Q[0], Q[1], Q[2], Q[3], W01, W23, W21, W0);
+  r2 = blur_v1(P[1], P[2], P[3], P[4], W01, W23, W21, W0);
+  r3 = blur_v1(Q[1], Q[2], Q[3], Q[4], W01, W23, W21, W0);
+}
+// four 16.16 sums -> four blurred pixels: byte 2 of each accumulator = (acc >> 16) & 255 (the sum never reaches 256 << 16)
+__device__ __forceinline__ uint32_t blur_pack4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
+  return __builtin_amdgcn_perm(c1, c0, 0x0c0c0602u) | __builtin_amdgcn_perm(c3, c2, 0x06020c0cu);
+}
+
 constexpr int kRawPitch = 72;   // bytes: 64 + 6 halo, rounded to dwords (tile rows are dword aligned: x0 % 64 == 0)
 constexpr int kHtPitch = (kBlurTH / 2 + 4) | 1;   // dwords per COLUMN of the transposed h-pass buffer (row pairs), odd -> conflict-free
 // (64 x 32 tiles, tried for a smaller LDS footprint next to the concurrently running k_octree: blur 0.31 -> 0.36 ms)
@@ -63,14 +102,7 @@ __device__ __forceinline__ void blur_tile(const uint8_t* __restrict__ pyr, int p
     const uint32_t* ra = r32 + (2 * yp) * 18 + g;
     const uint32_t a0 = ra[0], a1 = ra[1], a2 = ra[2], b0 = ra[18], b1 = ra[19], b2 = ra[20];
     uint32_t o[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const uint32_t wa0 = k ? __builtin_amdgcn_alignbyte(a1, a0, k) : a0, wa1 = k ? __builtin_amdgcn_alignbyte(a2, a1, k) : a1;
-      const uint32_t wb0 = k ? __builtin_amdgcn_alignbyte(b1, b0, k) : b0, wb1 = k ? __builtin_amdgcn_alignbyte(b2, b1, k) : b1;
-      const uint32_t ha = __builtin_amdgcn_udot4(wa1, GB, __builtin_amdgcn_udot4(wa0, GA, 0u, false), false);
-      const uint32_t hb = __builtin_amdgcn_udot4(wb1, GB, __builtin_amdgcn_udot4(wb0, GA, 0u, false), false);
-      o[k] = ha | (hb << 16);
-    }
+    blur_h4x2(a0, a1, a2, b0, b1, b2, GA, GB, o);
 #pragma unroll
     for (int k = 0; k < 4; k++) hpt[(4 * g + k) * kHtPitch + yp] = o[k];
   }
@@ -84,25 +116,17 @@ __device__ __forceinline__ void blur_tile(const uint8_t* __restrict__ pyr, int p
 #pragma unroll
     for (int c = 0; c < 4; c++) {
       const uint32_t* col = hpt + (4 * gx + c) * kHtPitch + 2 * gy;
-      uint32_t P[6], Q[5];
+      uint32_t P[6];
 #pragma unroll
       for (int j = 0; j < 6; j++) P[j] = col[j];
-#pragma unroll
-      for (int j = 0; j < 5; j++) Q[j] = __builtin_amdgcn_alignbyte(P[j + 1], P[j], 2);
-      acc[0][c] = udot2(P[3], W0, udot2(P[2], W21, udot2(P[1], W23, udot2(P[0], W01, 32768u))));
-      acc[1][c] = udot2(Q[3], W0, udot2(Q[2], W21, udot2(Q[1], W23, udot2(Q[0], W01, 32768u))));
-      acc[2][c] = udot2(P[4], W0, udot2(P[3], W21, udot2(P[2], W23, udot2(P[1], W01, 32768u))));
-      acc[3][c] = udot2(Q[4], W0, udot2(Q[3], W21, udot2(Q[2], W23, udot2(Q[1], W01, 32768u))));
+      blur_v1x4(P, W01, W23, W21, W0, acc[0][c], acc[1][c], acc[2][c], acc[3][c]);
     }
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int y = 4 * gy + r;
       if (y < th) {
-        // byte 2 of each accumulator = (acc >> 16) & 255 (the sum never reaches 256 << 16)
-        const uint32_t lo = __builtin_amdgcn_perm(acc[r][1], acc[r][0], 0x0c0c0602u);
-        const uint32_t hi = __builtin_amdgcn_perm(acc[r][3], acc[r][2], 0x06020c0cu);
         // the blurred image's pitch is a multiple of 64, so a full dword store never leaves the row
-        *reinterpret_cast<uint32_t*>(dst + (int64_t)y * L.blur_stride + 4 * gx) = lo | hi;
+        *reinterpret_cast<uint32_t*>(dst + (int64_t)y * L.blur_stride + 4 * gx) = blur_pack4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
       }
     }
   }

@@ -208,7 +208,8 @@ int dvm_orb_debug_blurred(dvm_orb* h, int frame, int level, uint8_t* out) {
   if (!h || !h->p->configured || !out) return DVM_ERR_STATE;
   OrbPipeline& P = *h->p;
   if (level < 0 || level >= P.PD.nlevels || frame < 0 || frame >= P.last_batch) return DVM_ERR_INVALID;
-  int rc = P.sync();
+  int rc = P.refresh_blur();   // a batch whose descriptors blurred their own patches left no blurred pyramid: make it now
+  if (rc == DVM_OK) rc = P.sync();
   if (rc != DVM_OK) return rc;
   const LevelDesc& L = P.PD.lv[level];
   return hip_check(hipMemcpy2D(out, L.w, P.d_blur + (size_t)frame * P.PD.blur_frame_bytes + L.blur_off, L.blur_stride, L.w, L.h,

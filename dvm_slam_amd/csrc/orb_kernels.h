@@ -50,5 +50,8 @@ void launch_blur(hipStream_t s, const uint8_t* d_pyr, uint8_t* d_blur, const Til
 void launch_orient_desc(hipStream_t s, const uint8_t* d_pyr, const uint8_t* d_blur, const PipelineDesc& PD,
                         const KpAux* d_aux, const int32_t* d_n, dvm_keypoint_pod* d_kps, uint8_t* d_desc, int batch,
                         HostMirror hm = HostMirror());
+// IC_Angle + GaussianBlur of the keypoint's own 43 x 43 raw patch + descriptor: no blurred pyramid (batches on the throughput path)
+void launch_orient_desc_blur(hipStream_t s, const uint8_t* d_pyr, const PipelineDesc& PD, const KpAux* d_aux, const int32_t* d_n,
+                             dvm_keypoint_pod* d_kps, uint8_t* d_desc, int batch, HostMirror hm = HostMirror());
 
 }  // namespace dvm

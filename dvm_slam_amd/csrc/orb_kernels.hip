@@ -7,6 +7,7 @@
 //   ORBextractor.cc:919-920  GaussianBlur 7x7 sigma 2    -> k_blur7
 //   ORBextractor.cc:75-99    IC_Angle                    -> k_orient_desc (phase 1)
 //   ORBextractor.cc:102-143  computeOrbDescriptor        -> k_orient_desc (phase 2)
+//   batches of more than a handful of frames: k_orient_desc_blur = IC_Angle + the blur of the keypoint's own patch + descriptor
 // All integer results are bit-exact by construction; the few float ops (fastAtan2, rotation of the
 // BRIEF pattern, keypoint scaling) are compiled with FP contraction OFF so every operation is one
 // IEEE rounding, the same sequence the CPU oracle performs.
@@ -37,6 +38,8 @@ __constant__ int8_t c_circle[16][2] = {{0, 3},  {1, 3},   {2, 2},   {3, 1},   {3
 // orientation disc as dot4 weights: item (row v+15, dword c) of the 31 x 32-byte patch rows -> {WU, W1}: byte k of
 // WU = u+16 (u = 4c+k-15) inside the disc else 0, byte k of W1 = 1 inside else 0; filled by the host at init
 __device__ uint2 c_disc_w[256];
+// the same weights laid out for k_orient_desc_blur's raw patch: item (row v+21, dword c) of 44 rows x 11 dwords from column cx-21
+__device__ uint2 c_disc_w43[512];
 __constant__ int c_gauss7[7];
 
 // XCD-aware (block, frame) mapping for per-frame kernels launched as a 1-D grid of
@@ -1309,6 +1312,181 @@ __global__ void __launch_bounds__(256) k_orient_desc(const uint8_t* __restrict__
   }
 }
 
+// ------------------------------------------------------------------------------- K4 + K5 + K6
+// k_orient_desc with the blur inside (throughput path).  The descriptors read blurred pixels only within 18 px of a keypoint, and
+// a blurred pixel needs raw pixels within 3 px: everything a keypoint needs lies in the 43 x 43 raw patch around it, which contains
+// the 31 x 31 IC_Angle patch.  So the blurred pyramid -- one more launch per batch, written to HBM to be read once -- does not exist
+// on this path.  What that saves is not the bytes but k_blur7's workgroups.  Per keypoint, one wave:
+//   load   rows cy-21 .. cy+22 x 11 unaligned dwords from column cx-21 of the BORDERED level (8 per lane).  A keypoint lies
+//          >= 19 px inside its level, so the patch stays inside the 19-px REFLECT_101 frame: no clamping, and the mirrored
+//          pixels the blur wants at a level's edge are already there
+//   angle  moments from those registers against c_disc_w43 (the integer sums of k_orient_desc, other item layout)
+//   h-pass 22 row pairs x 5 groups of 8 columns (blur_h4x2 twice: 9 re-alignments per row instead of 12) -> column-major u16
+//          pairs, odd pitch (as blur_tile)
+//   rBRIEF the v-pass runs for the 512 sampled pixels only (blur_v1 on the sample's column of the h-pass buffer: the pair window
+//          is re-aligned by the row's parity), not for the 37 x 37 patch: no blurred patch in LDS either
+// The kernel is VALU-bound (0.90 busy at 113.6 M wave-instructions per 256 frames; with the v-pass over the whole 37 x 37 patch it was
+// 168 M at 0.97), so what counts is its instruction count.
+// The LDS of a wave is its own, so between the phases a wave only has to keep ITS accesses in order (LDS instructions of a wave
+// execute in order): a wavefront-scope fence for the compiler, no s_barrier -- the four waves drift apart and fill each other's
+// waits (workgroup barriers instead: 279.8 k frames/s against 282.7 k).  The workgroup meets twice, around the shared angle
+// computation.
+constexpr int kPbPerWave = 4;                // keypoints a wave walks one after the other (16 per workgroup): LDS holds one of them at a time,
+                                             // so more of them only cost the registers of their loads.  256-frame stream: 272.1 k frames/s
+                                             // with 1, 282.6-282.8 k with 2, 284.7 k with 4
+constexpr int kPbR = kDescR + 3;             // raw patch radius
+constexpr int kPbDw = 11;                    // dwords per raw row: columns cx-21 .. cx+22
+constexpr int kPbRows = 2 * kPbR + 2;        // 44 = 22 row pairs (row cy+22 only completes the last pair)
+constexpr int kPbItems = kPbRows * kPbDw;    // 484 dwords, 8 per lane
+constexpr int kPbLoads = (kPbItems + 63) / 64;
+constexpr int kPbPairs = kPbRows / 2;
+constexpr int kPbHtPitch = kPbPairs | 1;     // dwords per column of the h-pass buffer, odd -> conflict-free
+constexpr int kPbCols = 40;                  // h-pass columns cx-18 .. cx+21 (37 used; 37..39 are never read)
+// the disc's rows are 6 .. 36 of the raw patch: the loads whose items all lie outside carry no weight
+constexpr int kPbMomFirst = ((kPbR - kHalfPatch) * kPbDw) / 64, kPbMomLast = ((kPbR + kHalfPatch) * kPbDw + kPbDw - 1) / 64;
+static_assert(kPbLoads * 64 <= 512, "c_disc_w43");
+
+// orders a wave's own LDS accesses across its lanes (compiler only: the hardware runs a wave's LDS instructions in order)
+__device__ __forceinline__ void patch_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__global__ void __launch_bounds__(256) k_orient_desc_blur(const uint8_t* __restrict__ pyr, int pyr_frame_bytes, PipelineDesc PD,
+                                                          const KpAux* __restrict__ aux, const int32_t* __restrict__ n_kp,
+                                                          dvm_keypoint_pod* __restrict__ kps, uint8_t* __restrict__ desc, int batch,
+                                                          HostMirror hm) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_raw[4][kPbItems];
+  __shared__ __attribute__((aligned(16))) uint32_t s_hpt[4][kPbCols * kPbHtPitch];
+  __shared__ int s_mom[4 * kPbPerWave][2];
+  __shared__ float s_rot[4 * kPbPerWave][3];
+  int blk, f;
+  if (!xcd_frame_map((PD.kp_cap + 4 * kPbPerWave - 1) / (4 * kPbPerWave), batch, blk, f)) return;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g0 = (blk * 4 + wave) * kPbPerWave;
+  const int nkf = n_kp[f];
+  if (nkf - blk * 4 * kPbPerWave <= 0) return;           // the whole workgroup is past the frame's keypoints
+  const int nk = max(min(kPbPerWave, nkf - g0), 0);      // wave-uniform; a wave without keypoints stays for the two barriers
+  KpAux a[kPbPerWave];                                   // (and walks keypoint 0 of the workgroup: valid data, nothing stored)
+#pragma unroll
+  for (int q = 0; q < kPbPerWave; q++) a[q] = aux[(int64_t)f * PD.kp_cap + (nk > 0 ? g0 + min(q, nk - 1) : blk * 4 * kPbPerWave)];
+  // ---- raw patches -> registers: every keypoint's loads go out before anything waits for one
+  uint32_t rv[kPbPerWave][kPbLoads];
+#pragma unroll
+  for (int q = 0; q < kPbPerWave; q++) {
+    const LevelDesc& L = PD.lv[a[q].level];
+    const uint8_t* p0 = pyr + (int64_t)f * pyr_frame_bytes + L.pyr_off + (int64_t)(kEdge + a[q].cy - kPbR) * L.stride + kEdge + a[q].cx - kPbR;
+#pragma unroll
+    for (int i = 0; i < kPbLoads; i++) {
+      const int item = min(lane + 64 * i, kPbItems - 1);
+      const int r = item / kPbDw, c = item - kPbDw * r;
+      __builtin_memcpy(&rv[q][i], p0 + (uint32_t)(r * L.stride + 4 * c), 4);
+    }
+  }
+  // ---- IC_Angle moments from the registers
+  {
+    uint2 w[kPbLoads];
+#pragma unroll
+    for (int i = kPbMomFirst; i <= kPbMomLast; i++) w[i] = c_disc_w43[lane + 64 * i];
+#pragma unroll
+    for (int q = 0; q < kPbPerWave; q++) {
+      int s10 = 0, s01 = 0;
+#pragma unroll
+      for (int i = kPbMomFirst; i <= kPbMomLast; i++) {
+        const int r = (lane + 64 * i) / kPbDw;
+        const int s1 = (int)__builtin_amdgcn_udot4(rv[q][i], w[i].y, 0u, false);
+        const int su = (int)__builtin_amdgcn_udot4(rv[q][i], w[i].x, 0u, false);
+        s10 += su - 16 * s1;
+        s01 += (r - kPbR) * s1;
+      }
+      const int m10 = wave_sum_i32(s10), m01 = wave_sum_i32(s01);
+      if (lane == q) { s_mom[wave * kPbPerWave + q][0] = m10; s_mom[wave * kPbPerWave + q][1] = m01; }
+    }
+  }
+  __syncthreads();
+  // one wave computes the workgroup's angles, a lane each (see k_orient_desc); the others are already blurring
+  if (threadIdx.x < 4 * kPbPerWave) {
+    float ang, ca_, sb_;
+    ang = fast_atan2_deg((float)s_mom[threadIdx.x][1], (float)s_mom[threadIdx.x][0]);
+    sincos_deg(ang, ca_, sb_);
+    s_rot[threadIdx.x][0] = ang; s_rot[threadIdx.x][1] = ca_; s_rot[threadIdx.x][2] = sb_;
+  }
+  float px0[4], py0[4], px1[4], py1[4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int* pt = &c_pattern[(64 * i + lane) * 4];
+    px0[i] = (float)pt[0]; py0[i] = (float)pt[1]; px1[i] = (float)pt[2]; py1[i] = (float)pt[3];
+  }
+  const uint32_t t0 = (uint32_t)c_gauss7[0], t1 = (uint32_t)c_gauss7[1], t2 = (uint32_t)c_gauss7[2], t3 = (uint32_t)c_gauss7[3];
+  const uint32_t GA = t0 | (t1 << 8) | (t2 << 16) | (t3 << 24), GB = t2 | (t1 << 8) | (t0 << 16);
+  const uint32_t W01 = t0 | (t1 << 16), W23 = t2 | (t3 << 16), W21 = t2 | (t1 << 16), W0 = t0;
+  uint32_t* raw = s_raw[wave];
+  uint32_t* hpt = s_hpt[wave];
+  // the blurred pixel (x, y) relative to the keypoint, |x|, |y| <= 18: taps on rows y+18 .. y+24 of column x+18 of the h-pass buffer
+  auto blurred_at = [&](int x, int y) -> uint32_t {
+    const int r0 = y + kDescR;
+    const uint32_t* cp = hpt + (x + kDescR) * kPbHtPitch + (r0 >> 1);
+    const uint32_t sh = (uint32_t)(r0 & 1) * 2u;   // an odd first row: the pairs straddle the dwords
+    const uint32_t p0 = cp[0], p1 = cp[1], p2 = cp[2], p3 = cp[3], p4 = cp[4];
+    return blur_v1(__builtin_amdgcn_alignbyte(p1, p0, sh), __builtin_amdgcn_alignbyte(p2, p1, sh), __builtin_amdgcn_alignbyte(p3, p2, sh),
+                   __builtin_amdgcn_alignbyte(p4, p3, sh), W01, W23, W21, W0) >> 16;
+  };
+#pragma unroll
+  for (int q = 0; q < kPbPerWave; q++) {
+    const bool live = q < nk;                      // wave-uniform
+    if (q > 0 && !live) break;                     // (round 0 holds the workgroup's last barrier)
+    if (live) {
+#pragma unroll
+      for (int i = 0; i < kPbLoads; i++)
+        if (lane + 64 * i < kPbItems) raw[lane + 64 * i] = rv[q][i];
+    }
+    patch_sync();
+    if (live) {   // h-pass: item = row pair yp x columns 8g .. 8g+7
+#pragma unroll
+      for (int it = 0; it < (kPbPairs * 5 + 63) / 64; it++) {
+        const int i = lane + 64 * it;
+        if (i < kPbPairs * 5) {
+          const int yp = i / 5, g = i - 5 * yp;
+          const uint32_t* ra = raw + 2 * yp * kPbDw + 2 * g;
+          const uint32_t a0 = ra[0], a1 = ra[1], a2 = ra[2], b0 = ra[kPbDw], b1 = ra[kPbDw + 1], b2 = ra[kPbDw + 2];
+          uint32_t a3 = 0u, b3 = 0u;               // the row ends with dword 10: columns 37..39 of the last group are never read
+          if (g < 4) { a3 = ra[3]; b3 = ra[kPbDw + 3]; }
+          uint32_t o[4], p[4];
+          blur_h4x2(a0, a1, a2, b0, b1, b2, GA, GB, o);
+          blur_h4x2(a1, a2, a3, b1, b2, b3, GA, GB, p);
+#pragma unroll
+          for (int k = 0; k < 4; k++) hpt[(8 * g + k) * kPbHtPitch + yp] = o[k];
+#pragma unroll
+          for (int k = 0; k < 4; k++) hpt[(8 * g + 4 + k) * kPbHtPitch + yp] = p[k];
+        }
+      }
+    }
+    if (q == 0) __syncthreads(); else patch_sync();   // q == 0: s_rot too
+    if (live) {
+      const float angle = s_rot[wave * kPbPerWave + q][0], ca = s_rot[wave * kPbPerWave + q][1], sb = s_rot[wave * kPbPerWave + q][2];
+      unsigned long long words[4];
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const uint32_t v0 = blurred_at(__float2int_rn(px0[i] * ca - py0[i] * sb), __float2int_rn(px0[i] * sb + py0[i] * ca));
+        const uint32_t v1 = blurred_at(__float2int_rn(px1[i] * ca - py1[i] * sb), __float2int_rn(px1[i] * sb + py1[i] * ca));
+        words[i] = __ballot(v0 < v1);
+      }
+      if (lane == 0) {
+        kps[(int64_t)f * PD.kp_cap + a[q].out_pos].angle = angle;
+        unsigned long long* d = reinterpret_cast<unsigned long long*>(desc + ((int64_t)f * PD.kp_cap + a[q].out_pos) * 32);
+        d[0] = words[0]; d[1] = words[1]; d[2] = words[2]; d[3] = words[3];
+        if (hm.kps) {
+          hm.kps[(int64_t)f * PD.kp_cap + a[q].out_pos].angle = angle;
+          unsigned long long* h = reinterpret_cast<unsigned long long*>(hm.desc + ((int64_t)f * PD.kp_cap + a[q].out_pos) * 32);
+          h[0] = words[0]; h[1] = words[1]; h[2] = words[2]; h[3] = words[3];
+        }
+      }
+    }
+    // (the next round's h-pass comes behind the patch_sync that follows its raw store: the samples above have read hpt by then)
+  }
+}
+
 // ------------------------------------------------------------------------------------- launchers
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
@@ -1335,6 +1513,15 @@ void upload_constants(const int8_t* disc_u, const int8_t* disc_v, const int* gau
     w[item].y |= 1u << (8 * k);
   }
   hipMemcpyToSymbol(HIP_SYMBOL(c_disc_w), w, sizeof(w));
+  uint2 w43[512];
+  for (int i = 0; i < 512; i++) w43[i] = make_uint2(0u, 0u);
+  for (int p = 0; p < kDiscPixels; p++) {
+    const int u = disc_u[p], v = disc_v[p];
+    const int item = (v + kPbR) * kPbDw + ((u + kPbR) >> 2), k = (u + kPbR) & 3;
+    w43[item].x |= (uint32_t)(u + 16) << (8 * k);
+    w43[item].y |= 1u << (8 * k);
+  }
+  hipMemcpyToSymbol(HIP_SYMBOL(c_disc_w43), w43, sizeof(w43));
   hipMemcpyToSymbol(HIP_SYMBOL(c_gauss7), gauss7, 7 * sizeof(int));
 }
 
@@ -1449,6 +1636,12 @@ void launch_orient_desc(hipStream_t s, const uint8_t* d_pyr, const uint8_t* d_bl
                         const KpAux* d_aux, const int32_t* d_n, dvm_keypoint_pod* d_kps, uint8_t* d_desc, int batch, HostMirror hm) {
   hipLaunchKernelGGL(k_orient_desc, dim3(xcd_grid(cdiv(PD.kp_cap, 4 * kDescPerWave), batch)), dim3(256), 0, s, d_pyr, PD.pyr_frame_bytes,
                      d_blur, PD.blur_frame_bytes, PD, d_aux, d_n, d_kps, d_desc, batch, hm);
+}
+
+void launch_orient_desc_blur(hipStream_t s, const uint8_t* d_pyr, const PipelineDesc& PD, const KpAux* d_aux, const int32_t* d_n,
+                             dvm_keypoint_pod* d_kps, uint8_t* d_desc, int batch, HostMirror hm) {
+  hipLaunchKernelGGL(k_orient_desc_blur, dim3(xcd_grid(cdiv(PD.kp_cap, 4 * kPbPerWave), batch)), dim3(256), 0, s, d_pyr, PD.pyr_frame_bytes, PD,
+                     d_aux, d_n, d_kps, d_desc, batch, hm);
 }
 
 }  // namespace dvm

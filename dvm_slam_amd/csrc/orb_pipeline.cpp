@@ -307,6 +307,7 @@ int OrbPipeline::init() {
   if (const char* e = getenv("DVM_LAT_SPLIT")) lat_split = (e[0] != '0');
   if (const char* e = getenv("DVM_ZERO_COPY_IN")) zero_copy_in = (e[0] != '0');
   if (const char* e = getenv("DVM_SERIAL")) overlap_blur = (e[0] != '1');      // debug / A-B switch only
+  if (const char* e = getenv("DVM_PATCH_BLUR")) patch_blur = (e[0] != '0');    // A-B switch: 0 = k_blur7 + k_orient_desc for batches too
 #ifdef DVM_DEBUG
   if (const char* e = getenv("DVM_HOST_OCTREE")) host_octree_forced = (e[0] == '1');  // debug / A-B switch, debug builds only
 #endif
@@ -641,6 +642,8 @@ int OrbPipeline::extract_device(const uint8_t* d_imgs, int batch, int rows, int 
   if (small) {
     hm = mirror_dev;   // (device addresses of the mapped result buffers, looked up once per configuration)
   }
+  const bool fused = patch_blur && !small;   // throughput path: no blurred pyramid, k_orient_desc_blur
+  blur_stale = fused;
   const bool blur_first = blur_early && !small;
   const bool split0 = small && lat_split && overlap_blur && !host_octree && !tiny_levels && L > 1 && chunks == 1 && group_split[0] >= L;
   if (split0 && !lat_aux) DVM_HIP(hipStreamCreateWithFlags(&lat_aux, hipStreamNonBlocking));
@@ -678,7 +681,7 @@ int OrbPipeline::extract_device(const uint8_t* d_imgs, int batch, int rows, int 
     for (int l = 1; l < L; l++) launch_pyr_resize(st, pyr_f0, PD, l, d_tabs, nb);
     if (tiny_levels) launch_pyr_borders(st, pyr_f0, PD, nb);   // else: fused into the level kernels
     prof.end(st);
-    const bool blur_forked = overlap_blur && !host_octree && side != nullptr && !small;   // latency path: one chain, no events (below)
+    const bool blur_forked = overlap_blur && !host_octree && side != nullptr && !small && !fused;   // latency path: one chain, no events (below)
     if (blur_forked && blur_first) {   // blur needs the pyramid only: low-priority side stream, fills the idle slots of
       DVM_HIP(hipEventRecord(ev_fork[ck], st));               // FAST's tail, the small scan kernels and the octree
       DVM_HIP(hipStreamWaitEvent(side, ev_fork[ck], 0));
@@ -787,7 +790,9 @@ int OrbPipeline::extract_device(const uint8_t* d_imgs, int batch, int rows, int 
     prof.begin(st, "assemble");
     launch_assemble(st, (d_sel + (size_t)f0 * PD.sel_frame_slots), (d_nsel + (size_t)f0 * L), PD, lap0, lap1, (d_kps + (size_t)f0 * PD.kp_cap), (d_aux + (size_t)f0 * PD.kp_cap), (d_n + f0), (d_mono + f0), nb, hm);
     prof.end(st);
-    if (!blur_forked && !blur_done) {
+    if (fused) {
+      // nothing to launch or to wait for: the descriptor kernel blurs what it reads
+    } else if (!blur_forked && !blur_done) {
       prof.begin(st, "blur");
       launch_blur(st, (d_pyr + (size_t)f0 * PD.pyr_frame_bytes), (d_blur + (size_t)f0 * PD.blur_frame_bytes), d_tiles, PD, nullptr, nb);
       prof.end(st);
@@ -795,12 +800,15 @@ int OrbPipeline::extract_device(const uint8_t* d_imgs, int batch, int rows, int 
       DVM_HIP(hipStreamWaitEvent(st, ev_join[ck], 0));
     }
     prof.begin(st, "orient_desc");
-    launch_orient_desc(st, (d_pyr + (size_t)f0 * PD.pyr_frame_bytes), (d_blur + (size_t)f0 * PD.blur_frame_bytes), PD, (d_aux + (size_t)f0 * PD.kp_cap), (d_n + f0), (d_kps + (size_t)f0 * PD.kp_cap), (d_desc + (size_t)f0 * PD.kp_cap * 32), nb, hm);
+    if (fused)
+      launch_orient_desc_blur(st, (d_pyr + (size_t)f0 * PD.pyr_frame_bytes), PD, (d_aux + (size_t)f0 * PD.kp_cap), (d_n + f0), (d_kps + (size_t)f0 * PD.kp_cap), (d_desc + (size_t)f0 * PD.kp_cap * 32), nb, hm);
+    else
+      launch_orient_desc(st, (d_pyr + (size_t)f0 * PD.pyr_frame_bytes), (d_blur + (size_t)f0 * PD.blur_frame_bytes), PD, (d_aux + (size_t)f0 * PD.kp_cap), (d_n + f0), (d_kps + (size_t)f0 * PD.kp_cap), (d_desc + (size_t)f0 * PD.kp_cap * 32), nb, hm);
     prof.end(st);
 
     return DVM_OK;
   };
-  if (!small && !lane_side[0] && overlap_blur) DVM_HIP(hipStreamCreateWithPriority(&lane_side[0], hipStreamNonBlocking, side_priority));
+  if (!small && !fused && !lane_side[0] && overlap_blur) DVM_HIP(hipStreamCreateWithPriority(&lane_side[0], hipStreamNonBlocking, side_priority));
   if (nck == 1) {
     rc = run_half(stream, lane_side[0], 0, 0, batch);
     if (rc != DVM_OK) return rc;
@@ -820,6 +828,16 @@ int OrbPipeline::extract_device(const uint8_t* d_imgs, int batch, int rows, int 
     DVM_HIP(hipStreamWaitEvent(stream, ev_done, 0));
   }
   DVM_HIP(hipGetLastError());
+  return DVM_OK;
+}
+
+int OrbPipeline::refresh_blur() {
+  if (!blur_stale) return DVM_OK;
+  if (!configured || last_batch < 1) { set_error("no batch to blur"); return DVM_ERR_STATE; }
+  DVM_HIP(hipSetDevice(device));
+  launch_blur(stream, d_pyr, d_blur, d_tiles, PD, nullptr, last_batch);
+  DVM_HIP(hipGetLastError());
+  blur_stale = false;
   return DVM_OK;
 }
 

@@ -86,6 +86,11 @@ class OrbPipeline {
   bool blur_early = true;    // launch the blur right after the pyramid (all levels) instead of after the candidate counts
   bool overlap_blur = true;  // DVM_SERIAL=1 puts the blur back on `stream`
   int side_priority = 0;     // lowest stream priority of the device (the blur's side stream)
+  // DVM_PATCH_BLUR=0/1: batches of more than kLatencyBatch frames launch no blur and fork no side stream; the descriptor kernel
+  // blurs each keypoint's own patch on chip (k_orient_desc_blur).  d_blur then does not describe the batch: refresh_blur()
+  bool patch_blur = true;
+  bool blur_stale = false;   // d_blur is older than the last batch (dvm_orb_debug_blurred runs the blur on demand)
+  int refresh_blur();        // k_blur7 over the last batch's resident pyramid, on `stream`, if d_blur is stale
   Profiler prof;
   std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
   std::vector<int> nfeat;
