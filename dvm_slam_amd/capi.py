@@ -894,6 +894,68 @@ def triangulate_matches(K1, K2, T1w, T2w, Ow1, Ow2, kps1, kps2, pairs, sigma2_1,
     return X, st
 
 
+class PairPose(C.Structure):   # == dvm_pair_pose
+    """The relative pose of a keyframe pair (R12, t12 of T12 = T1w * Tw2) and R21 = R12^T, t21 = -R21 t12 (dvm_pair_pose_set)."""
+    _fields_ = [("R12", C.c_float * 9), ("t12", C.c_float * 3), ("R21", C.c_float * 9), ("t21", C.c_float * 3)]
+
+
+def pair_pose(R12, t12):
+    R12 = np.ascontiguousarray(R12, np.float32).reshape(9); t12 = np.ascontiguousarray(t12, np.float32).reshape(3)
+    out = PairPose()
+    fn = lib().dvm_pair_pose_set
+    fn.restype = None; fn.argtypes = None
+    fn(_p(R12), _p(t12), C.byref(out))
+    return out
+
+
+def _model_ref(m):
+    return None if m is None else C.byref(m)
+
+
+def triangulate_matches_cam(model1, model2, T1w, T2w, Ow1, Ow2, kps1, kps2, pairs, sigma2_1, sigma2_2, sf1, sf2, ratio_factor,
+                            cos_parallax_max=0.9998, far_points=False, th_far=0.0):
+    """dvm_triangulate_matches_cam: triangulate_matches with the rays and both reprojections through a CameraModel per keyframe (both of
+    one model type).  Returns (x3D[n,3] float32, status[n] int32)."""
+    P = TriPair()
+    P.cos_parallax_max = float(cos_parallax_max)
+    for name, v, k in (("T1w", T1w, 12), ("T2w", T2w, 12), ("Ow1", Ow1, 3), ("Ow2", Ow2, 3)):
+        setattr(P, name, (C.c_float * k)(*np.asarray(v, np.float32).reshape(-1)))
+    f = [np.ascontiguousarray(x, np.float32) for x in (sigma2_1, sigma2_2, sf1, sf2)]
+    P.ratio_factor = float(ratio_factor); P.th_far = float(th_far); P.far_points = int(far_points); P.n_levels = len(f[0])
+    k1 = np.ascontiguousarray(kps1); k2 = np.ascontiguousarray(kps2)
+    pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    n = len(pr)
+    X = np.zeros((n, 3), np.float32); st = np.zeros(n, np.int32)
+    fn = lib().dvm_triangulate_matches_cam
+    fn.restype = C.c_int32; fn.argtypes = None
+    check(fn(C.byref(P), _model_ref(model1), _model_ref(model2), _p(k1), C.c_int32(len(k1)), _p(k2), C.c_int32(len(k2)), _p(pr), C.c_int32(n), _p(f[0]), _p(f[1]),
+             _p(f[2]), _p(f[3]), _p(X), _p(st), C.c_int32(0), None))
+    return X, st
+
+
+def match_triangulation_cam(desc1, kps1, qidx, desc2, kps2, off, cand, model1, model2, pose, ep, coarse, level_sigma2_1, scale_factors2,
+                            level_sigma2_2, F12=None):
+    """dvm_match_triangulation_cam: SearchForTriangulation's inner loop on a CameraModel per keyframe.  Query q = keypoint qidx[q] of KF1
+    scans cand[off[q] .. off[q+1]).  pose: a PairPose (read under KannalaBrandt8), F12: read under model 0.  Returns (best_idx, best_dist)."""
+    d1 = np.ascontiguousarray(desc1, np.uint8); d2 = np.ascontiguousarray(desc2, np.uint8)
+    k1 = np.ascontiguousarray(kps1, KP_DTYPE); k2 = np.ascontiguousarray(kps2, KP_DTYPE)
+    qi = np.ascontiguousarray(qidx, np.int32); of = np.ascontiguousarray(off, np.int32)
+    cd = np.ascontiguousarray(cand, np.int32)
+    if cd.size == 0:
+        cd = np.full(1, -1, np.int32)
+    epf = np.ascontiguousarray(ep, np.float32)
+    s1 = np.ascontiguousarray(level_sigma2_1, np.float32); sf2 = np.ascontiguousarray(scale_factors2, np.float32); s2 = np.ascontiguousarray(level_sigma2_2, np.float32)
+    F = None if F12 is None else np.ascontiguousarray(F12, np.float32)
+    nq = len(qi)
+    bi = np.zeros(max(nq, 1), np.int32); bd = np.zeros(max(nq, 1), np.int32)
+    fn = lib().dvm_match_triangulation_cam
+    fn.restype = C.c_int32; fn.argtypes = None
+    check(fn(_p(d1), _p(k1), C.c_int32(len(k1)), _p(qi), C.c_int32(nq), _p(d2), _p(k2), C.c_int32(len(k2)), _p(of), _p(cd), _model_ref(model1), _model_ref(model2),
+             None if pose is None else C.byref(pose), None if F is None else _p(F), _p(epf), C.c_int32(int(coarse)), _p(s1), _p(sf2), _p(s2), C.c_int32(len(s2)),
+             _p(bi), _p(bd), C.c_int32(0), None))
+    return bi[:nq], bd[:nq]
+
+
 def undistort_keypoints(cam, kps, d_in=None, d_out=None, n=None, stream=None):
     """Frame::UndistortKeyPoints: cam = (fx, fy, cx, cy, k1, k2, p1, p2, k3) float32; kps a KP_DTYPE array (returns the
     undistorted copy), or device pointers d_in / d_out of n keypoints (asynchronous on `stream`)."""
@@ -1819,6 +1881,23 @@ def search_for_triangulation(KF1, KF2, coarse=False, check_ori=True, device=0):
     return n, pairs[:n]
 
 
+def triangulation_geometry_cam(KF1, KF2, model1, model2):
+    """dvmh_triangulation_geometry_cam: R12, t12, the epipole through model2, F12 (Pinhole's formula on p[0..3])."""
+    R12 = np.zeros(9, np.float32); t12 = np.zeros(3, np.float32); ep = np.zeros(2, np.float32); F12 = np.zeros(9, np.float32)
+    check(_hcall("dvmh_triangulation_geometry_cam", C.c_int32, C.byref(KF1[0]), C.byref(KF2[0]), _model_ref(model1), _model_ref(model2),
+                 *(C.c_void_p(a.ctypes.data) for a in (R12, t12, ep, F12))))
+    return R12, t12, ep, F12
+
+
+def search_for_triangulation_cam(KF1, KF2, model1, model2, coarse=False, check_ori=True, device=0):
+    """dvmh_search_for_triangulation_cam: SearchForTriangulation on a CameraModel per keyframe.  Returns (nmatches, pairs[nmatches, 2])."""
+    pairs = np.zeros((max(KF1[0].N, 1), 2), np.int32)
+    n = _hcall("dvmh_search_for_triangulation_cam", C.c_int32, C.c_int32(device), C.byref(KF1[0]), C.byref(KF2[0]), _model_ref(model1), _model_ref(model2),
+               C.c_int32(int(coarse)), C.c_int32(int(check_ori)), C.c_void_p(pairs.ctypes.data))
+    check(min(n, 0))
+    return n, pairs[:n]
+
+
 def fuse(KF, P, in_kf, th, device=0):
     """Fuse(KF, vpMapPoints, th) search part (:1060-1213).  Returns (count, vBestIdx)."""
     bi = np.zeros(max(P[0].n, 1), np.int32)
@@ -2176,6 +2255,7 @@ class NewPoints(_Chain):
         super().__init__("dvm_new_points", 3, device)
         vp = C.c_void_p
         self.L.dvm_create_new_map_points.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
+        self.L.dvm_create_new_map_points_cam.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
 
     def reserve(self, max_kf1_keypoints, max_neighbours, max_total_neighbour_keypoints):
         self._reserve(max_kf1_keypoints, max_neighbours, max_total_neighbour_keypoints)
@@ -2220,6 +2300,42 @@ class NewPoints(_Chain):
             return R.result()
         return run
 
+    def prepare_cam(self, cur, neighbours, median_depth, cur_model, nb_models, record_cap=None, **params):
+        """prepare() for dvm_create_new_map_points_cam: cur_model / nb_models[j] = the CameraModel of the current keyframe / neighbour j
+        (None is passed on as NULL).  The epipole goes through the neighbour's model; the relative poses come from dvm_pair_pose_set."""
+        keep = []
+        c, cv = self._keyframe(cur, keep)
+        n_nb = len(neighbours)
+        nbs = (_NpNeighbour * max(n_nb, 1))()
+        poses = (PairPose * max(n_nb, 1))()
+        models = (CameraModel * max(n_nb, 1))()
+        have_models = cur_model is not None and nb_models is not None and all(m is not None for m in nb_models)
+        for j, kf in enumerate(neighbours):
+            s, v = self._keyframe(kf, keep)
+            nbs[j].kf = s
+            nbs[j].median_depth = float(median_depth[j])
+            if have_models:
+                models[j] = nb_models[j]
+                ok = cur_model.model == nb_models[j].model and cur_model.model in (0, 1) and all(m.p[0] != 0 and m.p[1] != 0 for m in (cur_model, nb_models[j]))
+                if ok:
+                    R12, t12, ep, F12 = triangulation_geometry_cam((cv, None), (v, None), cur_model, nb_models[j])
+                    nbs[j].ep = (C.c_float * 2)(*ep); nbs[j].F12 = (C.c_float * 9)(*F12)
+                    poses[j] = pair_pose(R12, t12)
+        p = _np_params(cur, **params)
+        R = _NpResult(c.n, n_nb, _np_record_cap(cur, n_nb, record_cap))
+
+        def run():
+            keep  # noqa: B018 (the views' arrays live as long as the closure)
+            check(self.L.dvm_create_new_map_points_cam(self.h, C.addressof(c), None if cur_model is None else C.addressof(cur_model), n_nb, C.addressof(nbs),
+                                                       C.addressof(models) if have_models or cur_model is None else None, C.addressof(poses), C.addressof(p),
+                                                       C.addressof(R.out)))
+            return R.result()
+        return run
+
+    def create_new_map_points_cam(self, cur, neighbours, median_depth, cur_model, nb_models, record_cap=None, **params):
+        """dvm_create_new_map_points_cam; arguments as prepare_cam, result as create_new_map_points."""
+        return self.prepare_cam(cur, neighbours, median_depth, cur_model, nb_models, record_cap=record_cap, **params)()
+
     def create_new_map_points(self, cur, neighbours, median_depth, record_cap=None, **params):
         """cur / neighbours: keyframe dicts; median_depth[j] = ComputeSceneMedianDepth(2) of neighbour j.  params: coarse, check_ori,
         cos_parallax_max, ratio_factor, far_points, th_far, monocular.  Returns dict(nb_status, nb_matches, pair_off, pairs[m, 2],
@@ -2242,6 +2358,27 @@ def create_new_map_points(cur, neighbours, median_depth, device=0, record_cap=No
     R = _NpResult(cv.N, n_nb, _np_record_cap(cur, n_nb, record_cap))
     rc = _hcall("dvmh_create_new_map_points", C.c_int32, C.c_int32(device), C.byref(cv), C.c_int32(n_nb), C.byref(views), C.c_void_p(md.ctypes.data if md.size else None),
                 C.byref(p), C.byref(R.out))
+    check(rc)
+    return R.result()
+
+
+def create_new_map_points_cam(cur, neighbours, median_depth, cur_model, nb_models, device=0, record_cap=None, **params):
+    """dvmh_create_new_map_points_cam: the host entry on a CameraModel per keyframe.  Arguments and result as
+    NewPoints.create_new_map_points_cam."""
+    keep = []
+    cv, k = keyframe_view(cur); keep.append(k)
+    n_nb = len(neighbours)
+    views = (_KeyFrameView * max(n_nb, 1))()
+    models = (CameraModel * max(n_nb, 1))()
+    for j, kf in enumerate(neighbours):
+        v, k = keyframe_view(kf); keep.append(k)
+        views[j] = v
+        models[j] = nb_models[j]
+    md = np.ascontiguousarray(median_depth, np.float32)
+    p = _np_params(cur, **params)
+    R = _NpResult(cv.N, n_nb, _np_record_cap(cur, n_nb, record_cap))
+    rc = _hcall("dvmh_create_new_map_points_cam", C.c_int32, C.c_int32(device), C.byref(cv), _model_ref(cur_model), C.c_int32(n_nb), C.byref(views), C.byref(models),
+                C.c_void_p(md.ctypes.data if md.size else None), C.byref(p), C.byref(R.out))
     check(rc)
     return R.result()
 

@@ -555,9 +555,11 @@ int dvm_is_in_frustum_cam(const dvm_frustum_frame* frame, const dvm_camera_model
                             on_device, stream);
 }
 
-int dvm_triangulate_matches(const dvm_tri_pair* pair, const dvm_keypoint* kps1, int n1, const dvm_keypoint* kps2, int n2,
-                            const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2, const float* scale_factors_1,
-                            const float* scale_factors_2, float* x3D, int32_t* status, int on_device, void* stream) {
+// dvm_triangulate_matches and dvm_triangulate_matches_cam: kb8_1 == nullptr launches the pinhole kernel on the pair's intrinsics, otherwise
+// k_triangulate_matches_kb8 on the two cameras' parameters
+static int triangulate_matches_impl(const dvm_tri_pair* pair, const float* kb8_1, const float* kb8_2, const dvm_keypoint* kps1, int n1, const dvm_keypoint* kps2,
+                                    int n2, const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2, const float* scale_factors_1,
+                                    const float* scale_factors_2, float* x3D, int32_t* status, int on_device, void* stream) {
   static_assert(sizeof(dvm_tri_pair) == sizeof(TriPair) && sizeof(dvm_keypoint) == sizeof(dvm_keypoint_pod), "layout");
   if (!pair || n < 0 || n1 < 0 || n2 < 0) return DVM_ERR_INVALID;
   if (n == 0) return DVM_OK;
@@ -570,9 +572,16 @@ int dvm_triangulate_matches(const dvm_tri_pair* pair, const dvm_keypoint* kps1, 
   { const int rc = need_any_device(); if (rc != DVM_OK) return rc; }
   TriPair P;
   std::memcpy(&P, pair, sizeof(P));
+  CamParams C1{}, C2{};
+  if (kb8_1) { std::memcpy(C1.p, kb8_1, sizeof(C1.p)); std::memcpy(C2.p, kb8_2, sizeof(C2.p)); }
+  auto launch = [&](hipStream_t s, const dvm_keypoint_pod* dk1, const dvm_keypoint_pod* dk2, const int32_t* dpairs, const float* ds1, const float* ds2,
+                    const float* df1, const float* df2, float* dX, int32_t* dst) {
+    if (kb8_1) launch_triangulate_matches_kb8(s, P, C1, C2, dk1, n1, dk2, n2, dpairs, n, ds1, ds2, df1, df2, dX, dst);
+    else launch_triangulate_matches(s, P, dk1, n1, dk2, n2, dpairs, n, ds1, ds2, df1, df2, dX, dst);
+  };
   if (on_device) {
-    launch_triangulate_matches((hipStream_t)stream, P, reinterpret_cast<const dvm_keypoint_pod*>(kps1), n1, reinterpret_cast<const dvm_keypoint_pod*>(kps2), n2,
-                               pairs, n, sigma2_1, sigma2_2, scale_factors_1, scale_factors_2, x3D, status);
+    launch((hipStream_t)stream, reinterpret_cast<const dvm_keypoint_pod*>(kps1), reinterpret_cast<const dvm_keypoint_pod*>(kps2), pairs, sigma2_1, sigma2_2,
+           scale_factors_1, scale_factors_2, x3D, status);
     return hip_check(hipGetLastError(), "triangulate_matches launch");
   }
   for (int m = 0; m < n; m++)
@@ -587,10 +596,38 @@ int dvm_triangulate_matches(const dvm_tri_pair* pair, const dvm_keypoint* kps1, 
             oX = st.out(x3D, N * 12), oS = st.out(status, N * 4);
   int rc = st.upload();
   if (rc != DVM_OK) return rc;
-  launch_triangulate_matches(nullptr, P, st.ptr<dvm_keypoint_pod>(iK1), n1, st.ptr<dvm_keypoint_pod>(iK2), n2, st.ptr<int32_t>(iP), n, st.ptr<float>(iS1),
-                             st.ptr<float>(iS2), st.ptr<float>(iF1), st.ptr<float>(iF2), st.ptr<float>(oX), st.ptr<int32_t>(oS));
+  launch(nullptr, st.ptr<dvm_keypoint_pod>(iK1), st.ptr<dvm_keypoint_pod>(iK2), st.ptr<int32_t>(iP), st.ptr<float>(iS1), st.ptr<float>(iS2), st.ptr<float>(iF1),
+         st.ptr<float>(iF2), st.ptr<float>(oX), st.ptr<int32_t>(oS));
   rc = hip_check(hipGetLastError(), "launch");
   return rc == DVM_OK ? st.download() : rc;
+}
+int dvm_triangulate_matches(const dvm_tri_pair* pair, const dvm_keypoint* kps1, int n1, const dvm_keypoint* kps2, int n2,
+                            const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2, const float* scale_factors_1,
+                            const float* scale_factors_2, float* x3D, int32_t* status, int on_device, void* stream) {
+  return triangulate_matches_impl(pair, nullptr, nullptr, kps1, n1, kps2, n2, pairs, n, sigma2_1, sigma2_2, scale_factors_1, scale_factors_2, x3D, status,
+                                  on_device, stream);
+}
+// what every entry that takes the models of two keyframes asks of them before anything runs
+static bool model_pair_ok(const dvm_camera_model* a, const dvm_camera_model* b) {
+  return a && b && dvm_cam::model_ok(a->model, a->p) && dvm_cam::model_ok(b->model, b->p) && a->model == b->model;
+}
+void dvm_pair_pose_set(const float* R12, const float* t12, dvm_pair_pose* out) {
+  static_assert(sizeof(dvm_pair_pose) == sizeof(dvm_tri::PairPose), "layout");
+  if (R12 && t12 && out) dvm_tri::pair_pose(R12, t12, *reinterpret_cast<dvm_tri::PairPose*>(out));
+}
+int dvm_triangulate_matches_cam(const dvm_tri_pair* pair, const dvm_camera_model* model1, const dvm_camera_model* model2, const dvm_keypoint* kps1,
+                                int n1, const dvm_keypoint* kps2, int n2, const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2,
+                                const float* scale_factors_1, const float* scale_factors_2, float* x3D, int32_t* status, int on_device, void* stream) {
+  if (!pair || n < 0 || n1 < 0 || n2 < 0) return DVM_ERR_INVALID;
+  if (!model_pair_ok(model1, model2)) {
+    set_error("dvm_triangulate_matches_cam: NULL model, unknown model, zero focal length or two model types in one pair");
+    return DVM_ERR_INVALID;
+  }
+  dvm_tri_pair pr = *pair;   // the models' p[0..3] stand for the pair's K1, K2
+  std::memcpy(pr.K1, model1->p, 16); std::memcpy(pr.K2, model2->p, 16);
+  const bool kb8 = model1->model == dvm_cam::kKannalaBrandt8;
+  return triangulate_matches_impl(&pr, kb8 ? model1->p : nullptr, kb8 ? model2->p : nullptr, kps1, n1, kps2, n2, pairs, n, sigma2_1, sigma2_2, scale_factors_1,
+                                  scale_factors_2, x3D, status, on_device, stream);
 }
 
 int dvm_undistort_keypoints(const dvm_distortion* cam, const dvm_keypoint* kps_in, dvm_keypoint* kps_out, int n, int on_device, void* stream) {
@@ -711,24 +748,38 @@ int dvm_project_search_cam(const dvm_frame* train, int slot, const uint8_t* skip
                              th, scale_factors, gate_inv_sigma2, gate, out, proj, on_device, stream);
 }
 
-int dvm_match_triangulation(const uint8_t* desc1, const dvm_keypoint* kps1, int n1, const int32_t* qidx, int nq,
-                            const uint8_t* desc2, const dvm_keypoint* kps2, int n2, const int32_t* off, const int32_t* cand,
-                            const float* F12, const float* ep, int coarse, const float* scale_factors2,
-                            const float* level_sigma2_2, int nlevels, int32_t* best_idx, int32_t* best_dist, int on_device,
-                            void* stream) {
+// dvm_match_triangulation and dvm_match_triangulation_cam: kb8 == nullptr launches the pinhole kernel on F12, otherwise
+// k_match_triangulation_kb8 on kb8's cameras and relative pose (its ep, coarse and th_low are filled in here)
+static int match_triangulation_impl(const uint8_t* desc1, const dvm_keypoint* kps1, int n1, const int32_t* qidx, int nq,
+                                    const uint8_t* desc2, const dvm_keypoint* kps2, int n2, const int32_t* off, const int32_t* cand,
+                                    const TriGeomKB8* kb8, const float* F12, const float* ep, int coarse, const float* level_sigma2_1,
+                                    const float* scale_factors2, const float* level_sigma2_2, int nlevels, int32_t* best_idx, int32_t* best_dist,
+                                    int on_device, void* stream) {
   if (nq < 0 || n1 < 0 || n2 < 0 || nlevels < 1) return DVM_ERR_INVALID;
   if (nq == 0) return DVM_OK;
-  if (!desc1 || !kps1 || !qidx || !desc2 || !kps2 || !off || !cand || !F12 || !ep || !scale_factors2 || !level_sigma2_2 || !best_idx ||
-      !best_dist)
+  if (!desc1 || !kps1 || !qidx || !desc2 || !kps2 || !off || !cand || !ep || !scale_factors2 || !level_sigma2_2 || !best_idx || !best_dist)
     return DVM_ERR_INVALID;
+  if (kb8 ? !level_sigma2_1 : !F12) return DVM_ERR_INVALID;
   { const int rc = need_any_device(); if (rc != DVM_OK) return rc; }
-  TriGeom G;
-  std::memcpy(G.F12, F12, 36);
-  G.ep[0] = ep[0]; G.ep[1] = ep[1];
-  G.coarse = coarse != 0; G.th_low = 50;   // ORBmatcher::TH_LOW
+  TriGeom G{};
+  TriGeomKB8 GK{};
+  if (kb8) {
+    GK = *kb8;
+    GK.ep[0] = ep[0]; GK.ep[1] = ep[1];
+    GK.coarse = coarse != 0; GK.th_low = 50;
+  } else {
+    std::memcpy(G.F12, F12, 36);
+    G.ep[0] = ep[0]; G.ep[1] = ep[1];
+    G.coarse = coarse != 0; G.th_low = 50;   // ORBmatcher::TH_LOW
+  }
+  auto launch = [&](hipStream_t s, const uint8_t* d1, const dvm_keypoint_pod* k1, const int32_t* dq, const uint8_t* d2, const dvm_keypoint_pod* k2,
+                    const int32_t* doff, const int32_t* dcand, const float* dsig1, const float* dsf2, const float* dsig2, int32_t* dbi, int32_t* dbd) {
+    if (kb8) launch_match_triangulation_kb8(s, d1, k1, dq, nq, d2, k2, doff, dcand, GK, dsig1, dsf2, dsig2, nlevels, dbi, dbd);
+    else launch_match_triangulation(s, d1, k1, dq, nq, d2, k2, doff, dcand, G, dsf2, dsig2, dbi, dbd);
+  };
   if (on_device) {
-    launch_match_triangulation((hipStream_t)stream, desc1, reinterpret_cast<const dvm_keypoint_pod*>(kps1), qidx, nq, desc2,
-                               reinterpret_cast<const dvm_keypoint_pod*>(kps2), off, cand, G, scale_factors2, level_sigma2_2, best_idx, best_dist);
+    launch((hipStream_t)stream, desc1, reinterpret_cast<const dvm_keypoint_pod*>(kps1), qidx, desc2, reinterpret_cast<const dvm_keypoint_pod*>(kps2), off, cand,
+           level_sigma2_1, scale_factors2, level_sigma2_2, best_idx, best_dist);
     return hip_check(hipGetLastError(), "match_triangulation launch");
   }
   const int ncand = off[nq];
@@ -737,14 +788,40 @@ int dvm_match_triangulation(const uint8_t* desc1, const dvm_keypoint* kps1, int 
   const int i1 = st.in(desc1, (size_t)n1 * 32), k1 = st.in(kps1, (size_t)n1 * sizeof(dvm_keypoint)), iq = st.in(qidx, (size_t)nq * 4),
             i2 = st.in(desc2, (size_t)n2 * 32), k2 = st.in(kps2, (size_t)n2 * sizeof(dvm_keypoint)), io = st.in(off, (size_t)(nq + 1) * 4),
             ic = st.in(cand, (size_t)ncand * 4), is = st.in(scale_factors2, (size_t)nlevels * 4), iv = st.in(level_sigma2_2, (size_t)nlevels * 4),
-            oi = st.out(best_idx, (size_t)nq * 4), od = st.out(best_dist, (size_t)nq * 4);
+            iw = st.in(kb8 ? level_sigma2_1 : nullptr, (size_t)nlevels * 4), oi = st.out(best_idx, (size_t)nq * 4), od = st.out(best_dist, (size_t)nq * 4);
   int rc = st.upload();
   if (rc != DVM_OK) return rc;
-  launch_match_triangulation(nullptr, st.ptr<uint8_t>(i1), st.ptr<dvm_keypoint_pod>(k1), st.ptr<int32_t>(iq), nq, st.ptr<uint8_t>(i2),
-                             st.ptr<dvm_keypoint_pod>(k2), st.ptr<int32_t>(io), st.ptr<int32_t>(ic), G, st.ptr<float>(is), st.ptr<float>(iv),
-                             st.ptr<int32_t>(oi), st.ptr<int32_t>(od));
+  launch(nullptr, st.ptr<uint8_t>(i1), st.ptr<dvm_keypoint_pod>(k1), st.ptr<int32_t>(iq), st.ptr<uint8_t>(i2), st.ptr<dvm_keypoint_pod>(k2), st.ptr<int32_t>(io),
+         st.ptr<int32_t>(ic), st.ptr<float>(iw), st.ptr<float>(is), st.ptr<float>(iv), st.ptr<int32_t>(oi), st.ptr<int32_t>(od));
   rc = hip_check(hipGetLastError(), "match_triangulation launch");
   return rc == DVM_OK ? st.download() : rc;
+}
+int dvm_match_triangulation(const uint8_t* desc1, const dvm_keypoint* kps1, int n1, const int32_t* qidx, int nq,
+                            const uint8_t* desc2, const dvm_keypoint* kps2, int n2, const int32_t* off, const int32_t* cand,
+                            const float* F12, const float* ep, int coarse, const float* scale_factors2,
+                            const float* level_sigma2_2, int nlevels, int32_t* best_idx, int32_t* best_dist, int on_device,
+                            void* stream) {
+  return match_triangulation_impl(desc1, kps1, n1, qidx, nq, desc2, kps2, n2, off, cand, nullptr, F12, ep, coarse, nullptr, scale_factors2, level_sigma2_2, nlevels,
+                                  best_idx, best_dist, on_device, stream);
+}
+int dvm_match_triangulation_cam(const uint8_t* desc1, const dvm_keypoint* kps1, int n1, const int32_t* qidx, int nq, const uint8_t* desc2,
+                                const dvm_keypoint* kps2, int n2, const int32_t* off, const int32_t* cand, const dvm_camera_model* model1,
+                                const dvm_camera_model* model2, const dvm_pair_pose* pose, const float* F12, const float* ep, int coarse,
+                                const float* level_sigma2_1, const float* scale_factors2, const float* level_sigma2_2, int nlevels,
+                                int32_t* best_idx, int32_t* best_dist, int on_device, void* stream) {
+  if (!model_pair_ok(model1, model2)) {
+    set_error("dvm_match_triangulation_cam: NULL model, unknown model, zero focal length or two model types in one pair");
+    return DVM_ERR_INVALID;
+  }
+  if (model1->model != dvm_cam::kKannalaBrandt8)
+    return match_triangulation_impl(desc1, kps1, n1, qidx, nq, desc2, kps2, n2, off, cand, nullptr, F12, ep, coarse, nullptr, scale_factors2, level_sigma2_2,
+                                    nlevels, best_idx, best_dist, on_device, stream);
+  if (!pose || nlevels > 64) return DVM_ERR_INVALID;
+  TriGeomKB8 GK{};
+  std::memcpy(&GK.R, pose, sizeof(GK.R));
+  std::memcpy(GK.cam1, model1->p, 32); std::memcpy(GK.cam2, model2->p, 32);
+  return match_triangulation_impl(desc1, kps1, n1, qidx, nq, desc2, kps2, n2, off, cand, &GK, nullptr, ep, coarse, level_sigma2_1, scale_factors2, level_sigma2_2,
+                                  nlevels, best_idx, best_dist, on_device, stream);
 }
 
 struct dvm_bowdb {

@@ -2,11 +2,19 @@
 // rotations (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), exact zeros skipped.  On return A is (numerically) diagonal and the columns of
 // V are the eigenvectors.  Used where the reference calls Eigen's float eigen / singular value solvers on 4x4 matrices
 // (Sim3Solver::ComputeSim3, GeometricTools::Triangulate): tolerance parity there, the same operation sequence as the oracle here.
+// A device function in a HIP translation unit; a plain inline function where a host compiler includes it (tri_model.h's host build).
 #pragma once
+#include <math.h>
+
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define DVM_J4_HD __device__ __forceinline__
+#else
+#define DVM_J4_HD inline
+#endif
 
 namespace dvm {
-__device__ __forceinline__ void jacobi4_dev(double A[4][4], double V[4][4]) {
+DVM_J4_HD void jacobi4_dev(double A[4][4], double V[4][4]) {
 #pragma unroll
   for (int i = 0; i < 4; i++)
 #pragma unroll

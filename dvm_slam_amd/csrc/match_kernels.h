@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "orb_kernels.h"
+#include "tri_model.h"
 #include "undistort_f64.h"
 
 struct dvm_frame;
@@ -89,6 +90,12 @@ struct TriGeom {
   float F12[9], ep[2];
   int32_t coarse, th_low;
 };
+struct TriGeomKB8 {            // the search's geometry on a KannalaBrandt8 pair
+  float ep[2];                 // pKF2->mpCamera->project(T2w * Cw), the float KannalaBrandt8 projection
+  int32_t coarse, th_low;
+  dvm_tri::PairPose R;         // R12, t12 and R21, -R21 t12
+  float cam1[8], cam2[8];      // mvParameters of the two keyframes' cameras
+};
 void launch_project_search(hipStream_t s, const FrameView& F, int slot, const uint8_t* skip, const ProjectCam& C, const float* P,
                            const float* normal, const float* min_dist, const float* max_dist, const uint8_t* desc,
                            const uint8_t* valid, int n, const float* scale_factors, const float* gate_inv_sigma2, double gate,
@@ -101,6 +108,15 @@ void launch_undistort_keypoints(hipStream_t s, const dvm_undistort::Camera& cam,
 void launch_triangulate_matches(hipStream_t s, const TriPair& P, const dvm_keypoint_pod* kps1, int n1, const dvm_keypoint_pod* kps2, int n2,
                                 const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2, const float* sf1,
                                 const float* sf2, float* x3D, int32_t* status);
+// the two above for a KannalaBrandt8 pair (C1, C2 / G.cam1, G.cam2 = mvParameters): the pinhole intrinsics of P and F12 are not read;
+// level_sigma2_1 = KF1's mvLevelSigma2, which KannalaBrandt8::epipolarConstrain reads beside KF2's
+void launch_match_triangulation_kb8(hipStream_t s, const uint8_t* desc1, const dvm_keypoint_pod* kps1, const int32_t* qidx, int nq,
+                                    const uint8_t* desc2, const dvm_keypoint_pod* kps2, const int32_t* off, const int32_t* cand,
+                                    const TriGeomKB8& G, const float* level_sigma2_1, const float* scale_factors2, const float* level_sigma2_2,
+                                    int n_levels, int32_t* best_idx, int32_t* best_dist);
+void launch_triangulate_matches_kb8(hipStream_t s, const TriPair& P, const CamParams& C1, const CamParams& C2, const dvm_keypoint_pod* kps1, int n1,
+                                    const dvm_keypoint_pod* kps2, int n2, const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2,
+                                    const float* sf1, const float* sf2, float* x3D, int32_t* status);
 void launch_is_in_frustum(hipStream_t s, const FrustumFrame& F, const float* P, const float* normal, const float* min_dist,
                           const float* max_dist, int n, float cos_limit, TrackPoint* out);
 // the two above for a KannalaBrandt8 camera (K = mvParameters): the pinhole intrinsics of F / C are not read

@@ -329,6 +329,30 @@ __global__ void __launch_bounds__(256) k_match_triangulation(const uint8_t* __re
   }
 }
 
+// k_match_triangulation on a KannalaBrandt8 pair (dvm_match_triangulation_cam, model 1): the candidate test is
+// KannalaBrandt8::epipolarConstrain, run over the workgroup's survivors of the two cheap tests (tri_rows_kb8, tri_device.h).  A candidate
+// whose octave lies outside the tables is no candidate.
+__global__ void __launch_bounds__(256) k_match_triangulation_kb8(const uint8_t* __restrict__ desc1, const dvm_keypoint_pod* __restrict__ kps1,
+                                                                 const int32_t* __restrict__ qidx, int nq,
+                                                                 const uint8_t* __restrict__ desc2, const dvm_keypoint_pod* __restrict__ kps2,
+                                                                 const int32_t* __restrict__ off, const int32_t* __restrict__ cand, TriGeomKB8 G,
+                                                                 const float* __restrict__ level_sigma2_1, const float* __restrict__ scale_factors2,
+                                                                 const float* __restrict__ level_sigma2_2, int n_levels,
+                                                                 int32_t* __restrict__ best_idx, int32_t* __restrict__ best_dist) {
+  __shared__ TriBlockKB8 S;
+  const int lane = threadIdx.x & 15;
+  const int q = blockIdx.x * 16 + (threadIdx.x >> 4);
+  const bool active = q < nq;
+  const int beg = active ? off[q] : 0, end = active ? off[q + 1] : 0;
+  const uint32_t k = tri_rows_kb8(S, active, desc1, kps1, active ? qidx[q] : 0, beg, end, [&](int p) { return cand[p]; }, desc2, kps2, G, level_sigma2_1,
+                                  scale_factors2, level_sigma2_2, n_levels);
+  if (lane == 0 && active) {
+    const bool hit = k != 0xFFFFFFFFu;
+    best_idx[q] = hit ? cand[beg + tri_key_pos(k)] : -1;
+    best_dist[q] = hit ? (int)(k >> 16) : 256;
+  }
+}
+
 // KeyFrameDatabase place-recognition queries (reference src/KeyFrameDatabase.cc:224-808: DetectCandidates,
 // DetectNBestCandidates, CalculateMergeScore) walk an inverted file word -> keyframes to count, per keyframe, the words it
 // shares with the query BowVector, then score the survivors with L1Scoring::score (DBoW2/ScoringObject.cpp:23-63).
@@ -435,6 +459,30 @@ void launch_triangulate_matches(hipStream_t s, const TriPair& P, const dvm_keypo
                      x3D, status);
 }
 
+// k_triangulate_matches on a KannalaBrandt8 pair (dvm_triangulate_matches_cam, model 1): tri_pair_geometry<KannalaBrandt8>, the rays from
+// kb8_unproject and both reprojections through kb8_project; P.K1 / P.K2 are not read.
+__global__ void __launch_bounds__(128) k_triangulate_matches_kb8(TriPair P, CamParams C1, CamParams C2, const dvm_keypoint_pod* __restrict__ kps1, int n1,
+                                                                 const dvm_keypoint_pod* __restrict__ kps2, int n2,
+                                                                 const int32_t* __restrict__ pairs, int n, const float* __restrict__ sigma2_1,
+                                                                 const float* __restrict__ sigma2_2, const float* __restrict__ sf1,
+                                                                 const float* __restrict__ sf2, float* __restrict__ x3D_out,
+                                                                 int32_t* __restrict__ status) {
+  const int m = blockIdx.x * 128 + threadIdx.x;
+  if (m >= n) return;
+  float* X = x3D_out + 3 * (int64_t)m;
+  const int i1 = pairs[2 * m], i2 = pairs[2 * m + 1];
+  if (i1 < 0 || i1 >= n1 || i2 < 0 || i2 >= n2) { X[0] = X[1] = X[2] = 0.0f; status[m] = -1; return; }
+  float x[3];
+  status[m] = tri_pair_geometry<dvm_cam::kKannalaBrandt8>(P, kps1[i1], kps2[i2], sigma2_1, sigma2_2, sf1, sf2, x, C1.p, C2.p);
+  X[0] = x[0]; X[1] = x[1]; X[2] = x[2];
+}
+void launch_triangulate_matches_kb8(hipStream_t s, const TriPair& P, const CamParams& C1, const CamParams& C2, const dvm_keypoint_pod* kps1, int n1,
+                                    const dvm_keypoint_pod* kps2, int n2, const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2,
+                                    const float* sf1, const float* sf2, float* x3D, int32_t* status) {
+  hipLaunchKernelGGL(k_triangulate_matches_kb8, dim3((n + 127) / 128), dim3(128), 0, s, P, C1, C2, kps1, n1, kps2, n2, pairs, n, sigma2_1, sigma2_2, sf1,
+                     sf2, x3D, status);
+}
+
 // D[i][j] = Hamming(A[i], B[j]); one thread per pair, 64 columns x 4 rows per workgroup.
 __global__ void __launch_bounds__(256) k_hamming_matrix(const uint8_t* __restrict__ A, int nA,
                                                         const uint8_t* __restrict__ B, int nB, uint16_t* __restrict__ D) {
@@ -523,6 +571,13 @@ void launch_match_triangulation(hipStream_t s, const uint8_t* desc1, const dvm_k
                                 int32_t* best_dist) {
   hipLaunchKernelGGL(k_match_triangulation, dim3((nq + 15) / 16), dim3(256), 0, s, desc1, kps1, qidx, nq, desc2, kps2, off, cand, G,
                      scale_factors2, level_sigma2_2, best_idx, best_dist);
+}
+void launch_match_triangulation_kb8(hipStream_t s, const uint8_t* desc1, const dvm_keypoint_pod* kps1, const int32_t* qidx, int nq,
+                                    const uint8_t* desc2, const dvm_keypoint_pod* kps2, const int32_t* off, const int32_t* cand,
+                                    const TriGeomKB8& G, const float* level_sigma2_1, const float* scale_factors2, const float* level_sigma2_2,
+                                    int n_levels, int32_t* best_idx, int32_t* best_dist) {
+  hipLaunchKernelGGL(k_match_triangulation_kb8, dim3((nq + 15) / 16), dim3(256), 0, s, desc1, kps1, qidx, nq, desc2, kps2, off, cand, G,
+                     level_sigma2_1, scale_factors2, level_sigma2_2, n_levels, best_idx, best_dist);
 }
 void launch_bowdb_query(hipStream_t s, const int64_t* kf_off, const int32_t* kf_len, const int32_t* live, int n_live, const int32_t* ids,
                         const double* vals, const int32_t* qids, const double* qvals, int nq, int32_t* common, int32_t* first_word, float* score) {

@@ -13,6 +13,7 @@
 #include "chain.h"
 #include "new_points_kernels.h"
 #include "orb_pipeline.h"
+#include "camera_model.h"
 #include "pose_f32.h"
 
 using namespace dvm;
@@ -99,7 +100,9 @@ int dvm_new_points_reserve(dvm_new_points* h, int max_kf1_keypoints, int max_nei
   const int n1 = std::max(max_kf1_keypoints, h->max_n1), nb = std::max(max_neighbours, h->max_nb), tot = std::max(max_total_neighbour_keypoints, h->max_total);
   h->max_n1 = h->max_nb = h->max_total = 0; h->rec_cap = 0;       // (a failed allocation leaves the handle holding nothing)
   const size_t n1p = ((size_t)n1 + 63) & ~(size_t)63;
-  const size_t up = pad<64>(((size_t)n1 + (size_t)tot) * kKfPerKeypoint + ((size_t)nb + 1) * kKfFixed + pad<64>((size_t)nb * sizeof(NpNbDev)));
+  // (a KannalaBrandt8 call adds its per-neighbour geometry to the upload)
+  const size_t up = pad<64>(((size_t)n1 + (size_t)tot) * kKfPerKeypoint + ((size_t)nb + 1) * kKfFixed + pad<64>((size_t)nb * sizeof(NpNbDev)) +
+                            pad<64>((size_t)nb * sizeof(TriGeomKB8)));
   const size_t spec = (size_t)nb * n1p * 20 + 64;
   const size_t rec = (size_t)nb * (size_t)n1;
   const size_t res = pad<64>(((size_t)nb + 1) * 4) * 2 + pad<64>(rec * 8) + pad<64>(rec * 4) + pad<64>(rec * 12) + pad<64>((size_t)n1 * 4) + 64;
@@ -122,8 +125,14 @@ int dvm_new_points_last_kernel_ms(dvm_new_points* h, float* ms) {
   return DVM_OK;
 }
 
-int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int n_neighbours, const dvm_np_neighbour* nbs,
-                              const dvm_np_params* p, dvm_np_out* out) {
+}  // extern "C"
+
+namespace {
+// dvm_create_new_map_points and dvm_create_new_map_points_cam: kb8 == false runs the pinhole kernels on the keyframes' intrinsics; otherwise
+// cur_model / nb_models / nb_poses (validated by the caller) go to the KannalaBrandt8 kernels
+int create_new_map_points_impl(dvm_new_points* h, const dvm_np_keyframe* cur, int n_neighbours, const dvm_np_neighbour* nbs, const dvm_np_params* p,
+                               dvm_np_out* out, bool kb8, const dvm_camera_model* cur_model, const dvm_camera_model* nb_models,
+                               const dvm_pair_pose* nb_poses) {
   static_assert(sizeof(dvm_keypoint) == sizeof(dvm_keypoint_pod), "layout");
   if (!h || !cur || !p || !out || n_neighbours < 0 || (n_neighbours > 0 && !nbs)) return fail(DVM_ERR_INVALID, "missing argument");
   if (p->monocular != 1) return fail(DVM_ERR_INVALID, "only monocular keyframes (the stereo branches are outside the accelerated path)");
@@ -172,6 +181,8 @@ int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int
   WorkingSet& ws = h->ws;
   Cursor64 up{ws.hm, ws.d};
   NpNbDev* nb_stage = up.carve<NpNbDev>((size_t)nrun);
+  const size_t gk_off = up.used();
+  TriGeomKB8* gk_stage = kb8 ? up.carve<TriGeomKB8>((size_t)nrun) : nullptr;
   NpArgs A{};
   A.cur = pack_keyframe(*cur, up);
   float T1w[12];
@@ -191,6 +202,13 @@ int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int
     P.ratio_factor = p->ratio_factor; P.th_far = p->th_far; P.far_points = p->far_points ? 1 : 0; P.n_levels = cur->n_levels;
     std::memcpy(D.G.F12, nb.F12, 36); D.G.ep[0] = nb.ep[0]; D.G.ep[1] = nb.ep[1];
     D.G.coarse = p->coarse != 0; D.G.th_low = 50;   // ORBmatcher::TH_LOW
+    if (kb8) {
+      TriGeomKB8& GK = gk_stage[r];
+      GK.ep[0] = nb.ep[0]; GK.ep[1] = nb.ep[1];
+      GK.coarse = D.G.coarse; GK.th_low = D.G.th_low;
+      std::memcpy(&GK.R, &nb_poses[run[r]], sizeof(GK.R));
+      std::memcpy(GK.cam1, cur_model->p, 32); std::memcpy(GK.cam2, nb_models[run[r]].p, 32);
+    }
   }
   if (up.used() > ws.up_bytes) return fail(DVM_ERR_CAPACITY, "packed keyframes exceed the reserved upload region");   // (cannot happen: kKfPerKeypoint / kKfFixed bound every keyframe)
   A.nb = reinterpret_cast<const NpNbDev*>(ws.d);
@@ -215,9 +233,18 @@ int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int
   DVM_HIP(hipMemsetAsync(A.best, 0xFF, (size_t)nrun * n1p * 4, h->s));
   const EventTimer& tm = h->timer;
   DVM_HIP(tm.mark(0, h->s));
-  launch_np_search(h->s, A);
-  DVM_HIP(tm.mark(1, h->s));
-  launch_np_geometry(h->s, A);
+  if (kb8) {
+    NpArgsKB8 K{};
+    K.A = A;
+    K.G = reinterpret_cast<const TriGeomKB8*>(ws.d + gk_off);
+    launch_np_search_kb8(h->s, K);
+    DVM_HIP(tm.mark(1, h->s));
+    launch_np_geometry_kb8(h->s, K);
+  } else {
+    launch_np_search(h->s, A);
+    DVM_HIP(tm.mark(1, h->s));
+    launch_np_geometry(h->s, A);
+  }
   DVM_HIP(tm.mark(2, h->s));
   launch_np_settle(h->s, A);
   DVM_HIP(tm.mark(3, h->s));
@@ -243,6 +270,38 @@ int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int
   }
   std::memcpy(out->new_point, r_new, (size_t)n1 * 4);
   return DVM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int n_neighbours, const dvm_np_neighbour* nbs,
+                              const dvm_np_params* p, dvm_np_out* out) {
+  return create_new_map_points_impl(h, cur, n_neighbours, nbs, p, out, false, nullptr, nullptr, nullptr);
+}
+
+int dvm_create_new_map_points_cam(dvm_new_points* h, const dvm_np_keyframe* cur, const dvm_camera_model* cur_model, int n_neighbours,
+                                  const dvm_np_neighbour* nbs, const dvm_camera_model* nb_models, const dvm_pair_pose* nb_poses,
+                                  const dvm_np_params* p, dvm_np_out* out) {
+  if (!h || !cur || !p || !out || n_neighbours < 0 || (n_neighbours > 0 && !nbs)) return fail(DVM_ERR_INVALID, "missing argument");
+  if (!cur_model || (n_neighbours > 0 && !nb_models)) return fail(DVM_ERR_INVALID, "NULL camera model");
+  if (!dvm_cam::model_ok(cur_model->model, cur_model->p)) return fail(DVM_ERR_INVALID, "current keyframe: unknown camera model or zero focal length");
+  for (int j = 0; j < n_neighbours; j++) {
+    if (!dvm_cam::model_ok(nb_models[j].model, nb_models[j].p))
+      return fail(DVM_ERR_INVALID, "neighbour " + std::to_string(j) + ": unknown camera model or zero focal length");
+    if (nb_models[j].model != cur_model->model)
+      return fail(DVM_ERR_INVALID, "neighbour " + std::to_string(j) + ": another camera model than the current keyframe's (a mixed pair is out of scope)");
+  }
+  const bool kb8 = cur_model->model == dvm_cam::kKannalaBrandt8;
+  if (kb8 && n_neighbours > 0 && !nb_poses) return fail(DVM_ERR_INVALID, "missing relative poses");
+  // the models' p[0..3] stand for the keyframes' fx, fy, cx, cy
+  dvm_np_keyframe c = *cur;
+  c.fx = cur_model->p[0]; c.fy = cur_model->p[1]; c.cx = cur_model->p[2]; c.cy = cur_model->p[3];
+  std::vector<dvm_np_neighbour> nv(nbs, nbs + n_neighbours);
+  for (int j = 0; j < n_neighbours; j++) {
+    nv[j].kf.fx = nb_models[j].p[0]; nv[j].kf.fy = nb_models[j].p[1]; nv[j].kf.cx = nb_models[j].p[2]; nv[j].kf.cy = nb_models[j].p[3];
+  }
+  return create_new_map_points_impl(h, &c, n_neighbours, nv.data(), p, out, kb8, cur_model, nb_models, nb_poses);
 }
 
 }  // extern "C"

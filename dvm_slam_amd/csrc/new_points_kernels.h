@@ -36,6 +36,14 @@ struct NpArgs {
   int32_t *h_matches, *h_pair_off, *h_pairs, *h_status, *h_new_point;
   float* h_x3D;
 };
+// the chain on KannalaBrandt8 keyframes (dvm_create_new_map_points_cam, model 1): beside NpArgs, per running neighbour the search's
+// geometry on such a pair (the cameras' parameters, the relative pose, the epipole)
+struct NpArgsKB8 {
+  NpArgs A;
+  const TriGeomKB8* G;            // [nrun]
+};
+void launch_np_search_kb8(hipStream_t s, const NpArgsKB8& K);
+void launch_np_geometry_kb8(hipStream_t s, const NpArgsKB8& K);
 void launch_np_search(hipStream_t s, const NpArgs& A);
 void launch_np_geometry(hipStream_t s, const NpArgs& A);
 void launch_np_settle(hipStream_t s, const NpArgs& A);

@@ -141,6 +141,68 @@ __global__ void __launch_bounds__(1024) k_np_settle(NpArgs A) {
   }
 }
 
+// ---- KannalaBrandt8 keyframes.  k_np_settle reads no camera and serves both models.
+
+// k_np_search with KannalaBrandt8::epipolarConstrain as the candidate test, run over the workgroup's survivors of the two cheap tests
+// (tri_rows_kb8, tri_device.h): no row leaves before the workgroup's barriers
+__global__ void __launch_bounds__(256) k_np_search_kb8(NpArgsKB8 K) {
+  __shared__ TriBlockKB8 S;
+  const NpArgs& A = K.A;
+  const int lane = threadIdx.x & 15;
+  const int k = blockIdx.x * 16 + (threadIdx.x >> 4);
+  const NpKfDev& C = A.cur;
+  const NpNbDev& N = A.nb[blockIdx.y];
+  const TriGeomKB8& G = K.G[blockIdx.y];
+  bool active = k < A.nfeat1;
+  int idx1 = 0, fb = 0, fe = 0;
+  if (active) {
+    idx1 = C.fv_feat[k];
+    active = C.mp[idx1] < 0;                         // already a MapPoint at entry: never asked
+  }
+  if (active) {
+    int lo = 0, hi = C.fv_n - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (C.fv_off[mid] <= k) lo = mid; else hi = mid - 1;
+    }
+    const int node = C.fv_node[lo];
+    lo = 0; hi = N.kf.fv_n;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (N.kf.fv_node[mid] < node) lo = mid + 1; else hi = mid;
+    }
+    active = lo < N.kf.fv_n && N.kf.fv_node[lo] == node;
+    if (active) { fb = N.kf.fv_off[lo]; fe = N.kf.fv_off[lo + 1]; }
+  }
+  const uint32_t key = tri_rows_kb8(S, active, C.desc, C.kps, idx1, fb, fe,
+                                    [&](int p) { const int idx2 = N.kf.fv_feat[p]; return N.kf.mp[idx2] >= 0 ? -1 : idx2; }, N.kf.desc, N.kf.kps, G,
+                                    C.sigma2, N.kf.sf, N.kf.sigma2, A.n_levels);
+  if (lane == 0 && active && key != 0xFFFFFFFFu) A.best[(size_t)blockIdx.y * A.n1p + idx1] = N.kf.fv_feat[fb + tri_key_pos(key)];
+}
+
+// k_np_geometry with tri_pair_geometry<KannalaBrandt8>
+__global__ void __launch_bounds__(128) k_np_geometry_kb8(NpArgsKB8 K) {
+  const NpArgs& A = K.A;
+  const int i = blockIdx.x * 128 + threadIdx.x;
+  if (i >= A.n1) return;
+  const size_t o = (size_t)blockIdx.y * A.n1p + i;
+  const int m = A.best[o];
+  if (m < 0) return;
+  const NpNbDev& N = A.nb[blockIdx.y];
+  const TriGeomKB8& G = K.G[blockIdx.y];
+  float x[3];
+  A.st[o] = tri_pair_geometry<dvm_cam::kKannalaBrandt8>(N.P, A.cur.kps[i], N.kf.kps[m], A.cur.sigma2, N.kf.sigma2, A.cur.sf, N.kf.sf, x, G.cam1, G.cam2);
+  A.X[3 * o] = x[0]; A.X[3 * o + 1] = x[1]; A.X[3 * o + 2] = x[2];
+}
+
+void launch_np_search_kb8(hipStream_t s, const NpArgsKB8& K) {
+  if (K.A.nrun < 1 || K.A.nfeat1 < 1) return;
+  hipLaunchKernelGGL(k_np_search_kb8, dim3((K.A.nfeat1 + 15) / 16, K.A.nrun), dim3(256), 0, s, K);
+}
+void launch_np_geometry_kb8(hipStream_t s, const NpArgsKB8& K) {
+  if (K.A.nrun < 1 || K.A.n1 < 1) return;
+  hipLaunchKernelGGL(k_np_geometry_kb8, dim3((K.A.n1 + 127) / 128, K.A.nrun), dim3(128), 0, s, K);
+}
 void launch_np_search(hipStream_t s, const NpArgs& A) {
   if (A.nrun < 1 || A.nfeat1 < 1) return;
   hipLaunchKernelGGL(k_np_search, dim3((A.nfeat1 + 15) / 16, A.nrun), dim3(256), 0, s, A);

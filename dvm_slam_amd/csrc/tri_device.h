@@ -2,14 +2,16 @@
 // (k_match_triangulation, k_triangulate_matches: match_kernels.hip) and by the chain (new_points_kernels.hip), so that both evaluate ONE
 // operation sequence:
 //   TriQuery / tri_candidate   ORBmatcher::SearchForTriangulation's per-candidate test (reference src/ORBmatcher.cc:905-960, monocular)
-//   tri_pair_geometry          the per-match body of CreateNewMapPoints (src/LocalMapping.cc:598-741, GeometricTools.cc:48-67)
+//   tri_pair_geometry<MODEL>   the per-match body of CreateNewMapPoints (src/LocalMapping.cc:598-741, GeometricTools.cc:48-67)
+//   tri_rows_kb8               the same test for a workgroup of 16 queries on a KannalaBrandt8 pair (CameraModels/KannalaBrandt8.cpp:216-220, :304-374)
+// The arithmetic that depends on the camera lives in tri_model.h, which also compiles for the host.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "jacobi4.h"
 #include "match_kernels.h"
 #include "pose_f32.h"
+#include "tri_model.h"
 
 namespace dvm {
 
@@ -62,13 +64,122 @@ __device__ __forceinline__ uint32_t tri_row_min(uint32_t k) {
   return k;
 }
 
-// One match (kp1, kp2) of one neighbour: parallax of the two rays, the homogeneous point (null vector of the 4x4 system: eigenvector of
-// the smallest eigenvalue of A^T A by cyclic Jacobi in double -- the reference runs Eigen::JacobiSVD<Matrix4f>, tolerance parity), depth,
-// reprojection error and scale-consistency tests in float in Eigen's evaluation order, comparisons with double literals in double.
-// Returns the status (include/dvmslam_hip.h); X = the point, zeros when no triangulation was attempted.
+// ---- the same search on a KannalaBrandt8 pair (model 1 of camera_model.h): KannalaBrandt8::epipolarConstrain in place of the line test.
+// The search on such a pair costs a double Jacobi per candidate that passes the two cheap tests, and few candidates do: left where the
+// candidate is found, one lane of a row would run it while the other lanes of the wave wait (measured: the chain's search 0.52 ms against
+// 0.025 ms on a pinhole pair).  So a workgroup of 16 rows works in three steps on a list in LDS:
+//   1. every lane scans its candidates of its row's query: dist <= th_low, the epipole disc; a coarse search keeps the key at once,
+//      otherwise the candidate joins the workgroup's list of survivors;
+//   2. thread t takes survivor t -- its row's query (pixel, ray, KF1's sigma2: taken once per row by the row's first lane), its own
+//      ray, KannalaBrandt8::epipolarConstrain -- and a survivor that passes lowers its row's key with an LDS atomic minimum;
+//   3. the row's key is the minimum of what its lanes kept and what the list gave.
+// A list that is full (kTriListCap survivors in one workgroup) sends further survivors through the constraint where they stand.
+constexpr int kTriRows = 16, kTriListCap = 256;
+struct TriRowQuery {             // what the constraint reads of a KF1 keypoint
+  float u, v, rx, ry, sigma1;
+  int32_t ok;                    // its octave lies inside KF1's tables (otherwise sigma1 is not read and only a coarse search takes it)
+};
+struct TriBlockKB8 {
+  TriRowQuery q[kTriRows];
+  uint32_t key[kTriRows];
+  int32_t n;
+  int32_t idx2[kTriListCap];
+  uint32_t skey[kTriListCap];
+  uint8_t row[kTriListCap];
+};
+__device__ __forceinline__ TriRowQuery tri_row_query(const dvm_keypoint_pod& kp1, const float* cam1, const float* __restrict__ level_sigma2_1, int n_levels) {
+  TriRowQuery Q;
+  Q.u = kp1.x; Q.v = kp1.y;
+  Q.ok = (unsigned)kp1.octave < (unsigned)n_levels;
+  Q.sigma1 = Q.ok ? level_sigma2_1[kp1.octave] : 0.f;
+  float r[3];
+  dvm_tri::unproject<dvm_cam::kKannalaBrandt8>(cam1, kp1.x, kp1.y, r);
+  Q.rx = r[0]; Q.ry = r[1];
+  return Q;
+}
+// KannalaBrandt8::epipolarConstrain of a query and a KF2 keypoint
+__device__ __forceinline__ bool tri_constrain(const TriRowQuery& Q, const dvm_keypoint_pod& kp2, const TriGeomKB8& G, const float* __restrict__ level_sigma2_2) {
+  if (!Q.ok) return false;
+  const float r1[3] = {Q.rx, Q.ry, 1.f};
+  float r2[3];
+  dvm_tri::unproject<dvm_cam::kKannalaBrandt8>(G.cam2, kp2.x, kp2.y, r2);
+  return dvm_tri::kb8_epipolar_constrain(G.cam1, G.cam2, r1, r2, Q.u, Q.v, kp2.x, kp2.y, G.R, Q.sigma1, level_sigma2_2[kp2.octave]);
+}
+// The three steps for the calling workgroup of 256 threads (every thread calls it: it holds workgroup barriers).  The row of this thread
+// asks for KF1 keypoint idx1 over the candidate positions [beg, end) when `active`; cand_at(p) is the KF2 keypoint at position p or -1.
+// Returns the row's key in every lane of the row: tri_key of the best candidate, 0xFFFFFFFF without one.
+template <class CandAt>
+__device__ __forceinline__ uint32_t tri_rows_kb8(TriBlockKB8& S, bool active, const uint8_t* __restrict__ desc1, const dvm_keypoint_pod* __restrict__ kps1,
+                                                 int idx1, int beg, int end, CandAt cand_at, const uint8_t* __restrict__ desc2,
+                                                 const dvm_keypoint_pod* __restrict__ kps2, const TriGeomKB8& G, const float* __restrict__ level_sigma2_1,
+                                                 const float* __restrict__ scale_factors2, const float* __restrict__ level_sigma2_2, int n_levels) {
+  const int lane = threadIdx.x & 15, row = threadIdx.x >> 4;
+  if (threadIdx.x < kTriRows) S.key[threadIdx.x] = 0xFFFFFFFFu;
+  if (threadIdx.x == 0) S.n = 0;
+  __syncthreads();
+  uint32_t key = 0xFFFFFFFFu;
+  if (active && end > beg) {
+    uint32_t w[8];
+    const uint32_t* qd = reinterpret_cast<const uint32_t*>(desc1 + (size_t)idx1 * 32);
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = qd[i];
+    if (lane == 0 && !G.coarse) S.q[row] = tri_row_query(kps1[idx1], G.cam1, level_sigma2_1, n_levels);
+    for (int p = beg + lane; p < end; p += 16) {
+      const int idx2 = cand_at(p);
+      if (idx2 < 0) continue;
+      const uint4* td = reinterpret_cast<const uint4*>(desc2 + (size_t)idx2 * 32);
+      const uint4 A = td[0], B = td[1];
+      const int d = __popc(A.x ^ w[0]) + __popc(A.y ^ w[1]) + __popc(A.z ^ w[2]) + __popc(A.w ^ w[3]) +
+                    __popc(B.x ^ w[4]) + __popc(B.y ^ w[5]) + __popc(B.z ^ w[6]) + __popc(B.w ^ w[7]);
+      if (d > G.th_low) continue;
+      const dvm_keypoint_pod kp2 = kps2[idx2];
+      if ((unsigned)kp2.octave >= (unsigned)n_levels) continue;   // outside the tables: no candidate, nothing read
+      const float distex = G.ep[0] - kp2.x, distey = G.ep[1] - kp2.y;
+      if (distex * distex + distey * distey < 100.f * scale_factors2[kp2.octave]) continue;
+      const uint32_t k = tri_key(d, p - beg);
+      if (G.coarse) { key = min(key, k); continue; }
+      const int slot = atomicAdd(&S.n, 1);
+      if (slot < kTriListCap) {
+        S.idx2[slot] = idx2; S.skey[slot] = k; S.row[slot] = (uint8_t)row;
+      } else {                                                     // the list is full: this lane decides for itself
+        const TriRowQuery Q = tri_row_query(kps1[idx1], G.cam1, level_sigma2_1, n_levels);
+        if (tri_constrain(Q, kp2, G, level_sigma2_2)) key = min(key, k);
+      }
+    }
+  }
+  __syncthreads();
+  const int ns = min(S.n, kTriListCap);
+  for (int t = threadIdx.x; t < ns; t += 256) {
+    const int idx2 = S.idx2[t], r = S.row[t];
+    if (tri_constrain(S.q[r], kps2[idx2], G, level_sigma2_2)) atomicMin(&S.key[r], S.skey[t]);
+  }
+  __syncthreads();
+  return min(tri_row_min(key), S.key[row]);
+}
+
+// One match (kp1, kp2) of one neighbour under camera model MODEL (dvm_tri::pair_geometry, tri_model.h): the octave check, the two rays,
+// then the shared body.  cam1 / cam2 = the cameras' parameters (the pinhole instantiation reads P.K1 / P.K2 and ignores them).  Returns
+// the status (include/dvmslam_hip.h).
+template <int MODEL = dvm_cam::kPinhole>
 __device__ __forceinline__ int tri_pair_geometry(const TriPair& P, const dvm_keypoint_pod& kp1, const dvm_keypoint_pod& kp2,
                                                  const float* __restrict__ sigma2_1, const float* __restrict__ sigma2_2,
-                                                 const float* __restrict__ sf1, const float* __restrict__ sf2, float* X) {
+                                                 const float* __restrict__ sf1, const float* __restrict__ sf2, float* X,
+                                                 const float* cam1 = nullptr, const float* cam2 = nullptr) {
+  X[0] = X[1] = X[2] = 0.0f;
+  if (kp1.octave < 0 || kp1.octave >= P.n_levels || kp2.octave < 0 || kp2.octave >= P.n_levels) return -1;
+  if (MODEL == dvm_cam::kPinhole) { cam1 = P.K1; cam2 = P.K2; }
+  float xn1[3], xn2[3];
+  dvm_tri::unproject<MODEL>(cam1, kp1.x, kp1.y, xn1);
+  dvm_tri::unproject<MODEL>(cam2, kp2.x, kp2.y, xn2);
+  return dvm_tri::pair_geometry<MODEL>(P, kp1, kp2, xn1, xn2, cam1, cam2, sigma2_1, sigma2_2, sf1, sf2, X);
+}
+
+// The pinhole instantiation is the operation sequence the pinhole kernels have always compiled, statement for statement (dvm_tri::pair_geometry
+// <kPinhole> is the same arithmetic; tests/test_kb8_tri_model.py holds the host build of that one against the float64 statement).
+template <>
+__device__ __forceinline__ int tri_pair_geometry<dvm_cam::kPinhole>(const TriPair& P, const dvm_keypoint_pod& kp1, const dvm_keypoint_pod& kp2,
+                                                 const float* __restrict__ sigma2_1, const float* __restrict__ sigma2_2,
+                                                 const float* __restrict__ sf1, const float* __restrict__ sf2, float* X, const float*, const float*) {
   using dvm_pose::sum3;
   X[0] = X[1] = X[2] = 0.0f;
   if (kp1.octave < 0 || kp1.octave >= P.n_levels || kp2.octave < 0 || kp2.octave >= P.n_levels) return -1;

@@ -604,8 +604,12 @@ void ORBmatcher::TriangulationGeometry(const KeyFrameView& KF1, const KeyFrameVi
   // Cw = pKF1->GetCameraCenter(); C2 = T2w * Cw; ep = pKF2->mpCamera->project(C2)   (:842-848)
   float C2[3];
   dvm_pose::se3_apply(KF2.Tcw.q, KF2.Tcw.t, KF1.Twc.t, C2);
-  ep[0] = KF2.fx * C2[0] / C2[2] + KF2.cx;
-  ep[1] = KF2.fy * C2[1] / C2[2] + KF2.cy;
+  if (KF2.mpCamera && KF2.mpCamera->model == dvm_cam::kKannalaBrandt8) {
+    dvm_cam::kb8_project(KF2.mpCamera->p, C2[0], C2[1], C2[2], ep[0], ep[1]);
+  } else {
+    ep[0] = KF2.fx * C2[0] / C2[2] + KF2.cx;
+    ep[1] = KF2.fy * C2[1] / C2[2] + KF2.cy;
+  }
   // T12 = T1w * Tw2; R12 = T12.rotationMatrix(); t12 = T12.translation()   (:856-859)
   float q12[4];
   dvm_pose::se3_compose(KF1.Tcw.q, KF1.Tcw.t, KF2.Twc.q, KF2.Twc.t, q12, t12);
@@ -646,9 +650,18 @@ int ORBmatcher::SearchForTriangulation(const KeyFrameView& KF1, const KeyFrameVi
   if (cand.empty()) cand.push_back(-1);
   std::vector<int32_t> bi(nq), bd(nq);
   if (int rcd = dvm_set_device(device_)) return rcd;   // stateless entry point: runs on the calling thread's current device
-  int rc = dvm_match_triangulation(KF1.mDescriptors, KF1.mvKeysUn, KF1.N, qidx.data(), nq, KF2.mDescriptors, KF2.mvKeysUn, KF2.N,
-                                   off.data(), cand.data(), F12, ep, bCoarse ? 1 : 0, KF2.mvScaleFactors, KF2.mvLevelSigma2, KF2.nLevels,
-                                   bi.data(), bd.data(), 0, nullptr);
+  int rc;
+  if (KF1.mpCamera && KF2.mpCamera) {   // pCamera1->epipolarConstrain(pCamera2, ...) of the keyframes' own cameras (:992)
+    dvm_pair_pose pose;
+    dvm_pair_pose_set(R12, t12, &pose);
+    rc = dvm_match_triangulation_cam(KF1.mDescriptors, KF1.mvKeysUn, KF1.N, qidx.data(), nq, KF2.mDescriptors, KF2.mvKeysUn, KF2.N, off.data(), cand.data(),
+                                     KF1.mpCamera, KF2.mpCamera, &pose, F12, ep, bCoarse ? 1 : 0, KF1.mvLevelSigma2, KF2.mvScaleFactors, KF2.mvLevelSigma2,
+                                     KF2.nLevels, bi.data(), bd.data(), 0, nullptr);
+  } else {
+    rc = dvm_match_triangulation(KF1.mDescriptors, KF1.mvKeysUn, KF1.N, qidx.data(), nq, KF2.mDescriptors, KF2.mvKeysUn, KF2.N,
+                                 off.data(), cand.data(), F12, ep, bCoarse ? 1 : 0, KF2.mvScaleFactors, KF2.mvLevelSigma2, KF2.nLevels,
+                                 bi.data(), bd.data(), 0, nullptr);
+  }
   if (rc != DVM_OK) return rc;
   int nmatches = 0;
   std::vector<int> vMatches12(KF1.N, -1);
@@ -1033,6 +1046,30 @@ int dvmh_search_for_triangulation(int device, const dvmh_keyframe_view* KF1, con
   return m.SearchForTriangulation(KeyFrameView(*KF1), KeyFrameView(*KF2), pairs, false, coarse != 0);
 }
 namespace {
+// a keyframe view on a camera model: the model's p[0..3] stand for fx, fy, cx, cy, and the view carries the model
+KeyFrameView CamKeyFrame(const dvmh_keyframe_view& K, const dvm_camera_model* model) {
+  KeyFrameView v(K);
+  v.fx = model->p[0]; v.fy = model->p[1]; v.cx = model->p[2]; v.cy = model->p[3];
+  v.mpCamera = model;
+  return v;
+}
+bool ModelPairOk(const dvm_camera_model* a, const dvm_camera_model* b) {
+  return a && b && dvm_cam::model_ok(a->model, a->p) && dvm_cam::model_ok(b->model, b->p) && a->model == b->model;
+}
+}  // namespace
+int dvmh_triangulation_geometry_cam(const dvmh_keyframe_view* KF1, const dvmh_keyframe_view* KF2, const dvm_camera_model* model1,
+                                    const dvm_camera_model* model2, float* R12, float* t12, float* ep, float* F12) {
+  if (!KF1 || !KF2 || !R12 || !t12 || !ep || !F12 || !ModelPairOk(model1, model2)) return DVM_ERR_INVALID;
+  dvm_host::ORBmatcher::TriangulationGeometry(CamKeyFrame(*KF1, model1), CamKeyFrame(*KF2, model2), R12, t12, ep, F12);
+  return DVM_OK;
+}
+int dvmh_search_for_triangulation_cam(int device, const dvmh_keyframe_view* KF1, const dvmh_keyframe_view* KF2, const dvm_camera_model* model1,
+                                      const dvm_camera_model* model2, int coarse, int check_ori, int32_t* pairs) {
+  if (!KF1 || !KF2 || !pairs || !ModelPairOk(model1, model2)) return DVM_ERR_INVALID;
+  dvm_host::ORBmatcher m(0.6f, check_ori != 0, device);
+  return m.SearchForTriangulation(CamKeyFrame(*KF1, model1), CamKeyFrame(*KF2, model2), pairs, false, coarse != 0);
+}
+namespace {
 // the calling thread's chain handles; cap: {current keyframe's keypoints, neighbours, their keypoints} / {points, targets, their keypoints}
 using NewPointsSlot = dvm_host::ChainHandle<dvm_new_points, dvm_new_points_create, dvm_new_points_destroy, dvm_new_points_reserve>;
 using FuseTargetsSlot = dvm_host::ChainHandle<dvm_fuse_targets, dvm_fuse_targets_create, dvm_fuse_targets_destroy, dvm_fuse_targets_reserve>;
@@ -1057,18 +1094,26 @@ dvm_np_keyframe NpKeyFrame(const dvmh_keyframe_view& K) {
   return k;
 }
 }  // namespace
-int dvmh_create_new_map_points(int device, const dvmh_keyframe_view* cur, int n_neighbours, const dvmh_keyframe_view* neighbours,
-                               const float* median_depth, const dvm_np_params* p, dvm_np_out* out) {
+// dvmh_create_new_map_points and _cam: cur_model == NULL is the pinhole call; otherwise the models were validated by the caller
+static int create_new_map_points_impl(int device, const dvmh_keyframe_view* cur, const dvm_camera_model* cur_model, int n_neighbours,
+                                      const dvmh_keyframe_view* neighbours, const dvm_camera_model* nb_models, const float* median_depth,
+                                      const dvm_np_params* p, dvm_np_out* out) {
   if (!cur || n_neighbours < 0 || (n_neighbours > 0 && (!neighbours || !median_depth)) || !p || !out) return DVM_ERR_INVALID;
   thread_local NewPointsSlot slot;
   { const int rc = slot.open(device); if (rc != DVM_OK) return rc; }
   std::vector<dvm_np_neighbour> nbs((size_t)n_neighbours);
+  std::vector<dvm_pair_pose> poses((size_t)(cur_model ? n_neighbours : 0));
   int64_t total = 0;
   for (int j = 0; j < n_neighbours; j++) {
     nbs[j].kf = NpKeyFrame(neighbours[j]);
     nbs[j].median_depth = median_depth[j];
     float R12[9], t12[3];
-    dvm_host::ORBmatcher::TriangulationGeometry(KeyFrameView(*cur), KeyFrameView(neighbours[j]), R12, t12, nbs[j].ep, nbs[j].F12);
+    if (cur_model) {
+      dvm_host::ORBmatcher::TriangulationGeometry(CamKeyFrame(*cur, cur_model), CamKeyFrame(neighbours[j], &nb_models[j]), R12, t12, nbs[j].ep, nbs[j].F12);
+      dvm_pair_pose_set(R12, t12, &poses[j]);
+    } else {
+      dvm_host::ORBmatcher::TriangulationGeometry(KeyFrameView(*cur), KeyFrameView(neighbours[j]), R12, t12, nbs[j].ep, nbs[j].F12);
+    }
     total += std::max(neighbours[j].N, 0);
   }
   const dvm_np_keyframe c = NpKeyFrame(*cur);
@@ -1079,7 +1124,20 @@ int dvmh_create_new_map_points(int device, const dvmh_keyframe_view* cur, int n_
     const int rc = slot.reserve(n1, nb, tot);
     if (rc != DVM_OK) return rc;
   }
+  if (cur_model) return dvm_create_new_map_points_cam(slot.h, &c, cur_model, n_neighbours, nbs.data(), nb_models, poses.data(), p, out);
   return dvm_create_new_map_points(slot.h, &c, n_neighbours, nbs.data(), p, out);
+}
+int dvmh_create_new_map_points(int device, const dvmh_keyframe_view* cur, int n_neighbours, const dvmh_keyframe_view* neighbours,
+                               const float* median_depth, const dvm_np_params* p, dvm_np_out* out) {
+  return create_new_map_points_impl(device, cur, nullptr, n_neighbours, neighbours, nullptr, median_depth, p, out);
+}
+int dvmh_create_new_map_points_cam(int device, const dvmh_keyframe_view* cur, const dvm_camera_model* cur_model, int n_neighbours,
+                                   const dvmh_keyframe_view* neighbours, const dvm_camera_model* nb_models, const float* median_depth,
+                                   const dvm_np_params* p, dvm_np_out* out) {
+  if (!cur_model || (n_neighbours > 0 && !nb_models) || !dvm_cam::model_ok(cur_model->model, cur_model->p)) return DVM_ERR_INVALID;
+  for (int j = 0; j < n_neighbours; j++)
+    if (!ModelPairOk(cur_model, &nb_models[j])) return DVM_ERR_INVALID;
+  return create_new_map_points_impl(device, cur, cur_model, n_neighbours, neighbours, nb_models, median_depth, p, out);
 }
 int dvmh_fuse(int device, const dvmh_keyframe_view* KF, const dvmh_map_points_view* P, const uint8_t* inKF, float th, int32_t* best_idx) {
   dvm_host::ORBmatcher m(0.6f, true, device);

@@ -40,6 +40,9 @@ struct KeyFrameView : dvmh_keyframe_view {
   KeyFrameView() : dvmh_keyframe_view() { nLevels = 8; }
   KeyFrameView(const dvmh_keyframe_view& v) : dvmh_keyframe_view(v) {}
   void SetPose(const dvm_se3f& T);       // KeyFrame::SetPose: mTcw = T; mTwc = mTcw.inverse()
+  // mpCamera, as FrameView has it: a KannalaBrandt8 model (model == 1) sends SearchForTriangulation's epipole and candidate test through
+  // that camera (dvm_match_triangulation_cam).  NULL (and model 0): fx, fy, cx, cy above.  Both keyframes of a pair carry one model type.
+  const dvm_camera_model* mpCamera = nullptr;
 };
 // A list of map points as the projection searches read them (SoA): GetWorldPos, GetNormal, mfMinDistance / mfMaxDistance
 // (GetMin/MaxDistanceInvariance = 0.8 / 1.2 times these), GetDescriptor, isBad, and an id standing for the pointer.
@@ -113,7 +116,8 @@ class ORBmatcher {
   int SearchForTriangulation(const KeyFrameView& KF1, const KeyFrameView& KF2, int32_t* vMatchedPairs, bool bOnlyStereo = false,
                              bool bCoarse = false);
   // the geometry it derives from the two poses (:841-862, Pinhole.cpp:106-110) through Sophus' SE3 products and Eigen's
-  // 3x3 inverse / products: R12, t12, epipole in image 2, F12
+  // 3x3 inverse / products: R12, t12, epipole in image 2, F12.  The epipole is KF2.mpCamera->project(T2w * Cw): through the
+  // KannalaBrandt8 projection where KF2 carries such a model (F12 is then Pinhole's formula on p[0..3], which nothing reads)
   static void TriangulationGeometry(const KeyFrameView& KF1, const KeyFrameView& KF2, float* R12, float* t12, float* ep, float* F12);
 
   // int Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th, const bool bRight = false)   (:1060-1234),

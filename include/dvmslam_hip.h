@@ -13,6 +13,7 @@
  *                                                    src/Optimizer.cc:55-356,1030-1387
  *   dvm_pose_optimize <- Optimizer::PoseOptimization src/Optimizer.cc:744-1028
  *   dvm_pose_optimize_cam, dvm_is_in_frustum_cam, dvm_project_search_cam <- the same on a GeometricCamera (CameraModels/KannalaBrandt8.cpp)
+ *   dvm_match_triangulation_cam, dvm_triangulate_matches_cam, dvm_create_new_map_points_cam <- CreateNewMapPoints on such a camera
  *   dvm_pose_graph_optimize <- Optimizer::OptimizeEssentialGraph src/Optimizer.cc:1389-1652 (g2o part)
  *   dvm_sim3_hypotheses <- Sim3Solver::ComputeSim3 + CheckInliers src/Sim3Solver.cc:294-408
  *   dvm_distinctive_descriptors <- MapPoint::ComputeDistinctiveDescriptors src/MapPoint.cc:384-453
@@ -268,9 +269,12 @@ int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const floa
  * u = fx r x / rho + cx, v = fy r y / rho + cy (rho = sqrt(x^2 + y^2); on the optical axis u = cx, v = cy).  Its Jacobian
  * (projectJac, KannalaBrandt8.cpp:144-172) is 0 / 0 on the optical axis: NaN there, as in the reference.  sizeof(dvm_camera_model) == 36.
  * Every *_cam entry returns DVM_ERR_INVALID, before anything runs, for a NULL model, a model outside {0, 1} or a zero focal length.
- * What takes a model: dvm_pose_optimize_cam, dvm_is_in_frustum_cam, dvm_project_search_cam, dvm_ba_set_problem_cam (and
- * dvmh_search_by_projection_frames_cam, include/dvmslam_host.h).  The pools, the tracked-frame chains, the batched BA windows
- * (dvm_ba_optimize_windows) and OptimizeSim3 are pinhole-only. */
+ * What takes a model: dvm_pose_optimize_cam, dvm_is_in_frustum_cam, dvm_project_search_cam, dvm_ba_set_problem_cam,
+ * dvm_match_triangulation_cam, dvm_triangulate_matches_cam, dvm_create_new_map_points_cam (and dvmh_search_by_projection_frames_cam,
+ * dvmh_triangulation_geometry_cam, dvmh_search_for_triangulation_cam, dvmh_create_new_map_points_cam, include/dvmslam_host.h).  The
+ * entries that take the models of TWO keyframes want one model type for both (the parameters may differ per keyframe): a pair of a
+ * pinhole and a KannalaBrandt8 keyframe is DVM_ERR_INVALID -- the reference's mixed pair is out of scope.  The pools, the tracked-frame
+ * chains, the Fuse / BoW chains, the batched BA windows (dvm_ba_optimize_windows) and OptimizeSim3 are pinhole-only. */
 typedef struct { int32_t model;   /* 0 pinhole, 1 KannalaBrandt8 */
                  float p[8];      /* fx, fy, cx, cy, k1, k2, k3, k4: mvParameters, float as the reference stores them */
 } dvm_camera_model;
@@ -303,6 +307,22 @@ typedef struct {
 int dvm_triangulate_matches(const dvm_tri_pair* pair, const dvm_keypoint* kps1, int n1, const dvm_keypoint* kps2, int n2,
                             const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2, const float* scale_factors_1,
                             const float* scale_factors_2, float* x3D, int32_t* status, int on_device, void* stream);
+
+/* The relative pose of a keyframe pair as SearchForTriangulation holds it -- T12 = T1w * Tw2, R12 = T12.rotationMatrix(), t12 =
+ * T12.translation() (ORBmatcher.cc:856-859; dvmh_triangulation_geometry computes both) -- and what KannalaBrandt8::TriangulateMatches
+ * derives from it for every candidate (KannalaBrandt8.cpp:335-336): R21 = R12^T, t21 = -R21 t12.  dvm_pair_pose_set fills all four from
+ * R12 and t12, once per pair, on the host (index-free float arithmetic in Eigen's order). */
+typedef struct { float R12[9], t12[3], R21[9], t21[3]; } dvm_pair_pose;
+void dvm_pair_pose_set(const float* R12, const float* t12, dvm_pair_pose* out);
+
+/* dvm_triangulate_matches on a camera model per keyframe: xn = pCamera->unprojectEig(kp.pt) and both reprojection errors from
+ * pCamera->project(Point3f(x, y, z)) (LocalMapping.cc:608-609, :676, :700); the parallax gate, GeometricTools::Triangulate with its
+ * w == 0 test, the depth, distance and scale-consistency tests and the status codes are dvm_triangulate_matches'.  model1 / model2 = the
+ * cameras of kps1 / kps2; their p[0..3] replace pair->K1 / K2, which are not read.  Both models of one type (else DVM_ERR_INVALID);
+ * model 0 gives dvm_triangulate_matches' results bit for bit. */
+int dvm_triangulate_matches_cam(const dvm_tri_pair* pair, const dvm_camera_model* model1, const dvm_camera_model* model2, const dvm_keypoint* kps1,
+                                int n1, const dvm_keypoint* kps2, int n2, const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2,
+                                const float* scale_factors_1, const float* scale_factors_2, float* x3D, int32_t* status, int on_device, void* stream);
 
 /* Best / second best over an explicit candidate list per query -- the inner loop of the
  * vocabulary-node restricted searches (SearchByBoW ORBmatcher.cc:262-300,760-800; SearchForTriangulation
@@ -366,7 +386,22 @@ int dvm_match_triangulation(const uint8_t* desc1, const dvm_keypoint* kps1, int 
                             const float* level_sigma2_2, int nlevels, int32_t* best_idx, int32_t* best_dist, int on_device,
                             void* stream);
 
-/* LocalMapping::CreateNewMapPoints (LocalMapping.cc:446-760, monocular pinhole) for ALL neighbour keyframes of the current keyframe as
+/* dvm_match_triangulation on a camera model per keyframe.  Under KannalaBrandt8 the candidate test after dist <= 50 and the epipole disc
+ * is KannalaBrandt8::epipolarConstrain (KannalaBrandt8.cpp:216-220): TriangulateMatches (:304-374) > 0.0001f, all in float -- the two rays
+ * (unproject), their parallax against the double 0.9998, the point from the 4x4 system of cameras [I | 0] and [R21 | t21] (null vector by
+ * the double Jacobi of A^T A; division by the fourth component with no w == 0 test), z > 0 in both cameras, the reprojection error through
+ * project() of camera 1 against 5.991 * level_sigma2_1[kp1.octave] and of camera 2 against 5.991 * level_sigma2_2[kp2.octave]; the value
+ * is z1.  It reads KF1's level_sigma2 beside KF2's; F12 is not read (may be NULL) and `ep` is the caller's
+ * pKF2->mpCamera->project(T2w * Cw) (dvmh_triangulation_geometry_cam).  A candidate whose octave lies outside [0, nlevels) is no
+ * candidate; a query whose octave does finds nothing unless coarse != 0.  Under model 0 `pose` and level_sigma2_1 are not read (may be
+ * NULL) and the results are dvm_match_triangulation's bit for bit.  Both models of one type (else DVM_ERR_INVALID). */
+int dvm_match_triangulation_cam(const uint8_t* desc1, const dvm_keypoint* kps1, int n1, const int32_t* qidx, int nq, const uint8_t* desc2,
+                                const dvm_keypoint* kps2, int n2, const int32_t* off, const int32_t* cand, const dvm_camera_model* model1,
+                                const dvm_camera_model* model2, const dvm_pair_pose* pose, const float* F12, const float* ep, int coarse,
+                                const float* level_sigma2_1, const float* scale_factors2, const float* level_sigma2_2, int nlevels,
+                                int32_t* best_idx, int32_t* best_dist, int on_device, void* stream);
+
+/* LocalMapping::CreateNewMapPoints (LocalMapping.cc:446-760, monocular; pinhole here, any model through the _cam entry below) for ALL neighbour keyframes of the current keyframe as
  * ONE device chain: one upload, three launches whatever n_neighbours is, one synchronisation.  Per neighbour, in the order given:
  *   1. baseline test (:497-512): baseline = ||Ow2 - Ow1|| in float, summed as x^2 + y^2 + z^2; ratio = baseline / median_depth in float;
  *      the neighbour is skipped when (double)ratio < 0.01 -- plain arithmetic, no special case: a negative median depth (what
@@ -447,6 +482,18 @@ void dvm_new_points_destroy(dvm_new_points* h);
 int dvm_new_points_reserve(dvm_new_points* h, int max_kf1_keypoints, int max_neighbours, int max_total_neighbour_keypoints);
 int dvm_create_new_map_points(dvm_new_points* h, const dvm_np_keyframe* cur, int n_neighbours, const dvm_np_neighbour* nbs,
                               const dvm_np_params* p, dvm_np_out* out);
+/* dvm_create_new_map_points on a camera model per keyframe: cur_model = the current keyframe's camera, nb_models[j] / nb_poses[j] =
+ * neighbour j's camera and the pair's relative pose (dvm_pair_pose_set).  The models' p[0..3] replace the keyframes' fx, fy, cx, cy,
+ * which are not read.  Under KannalaBrandt8 the search is dvm_match_triangulation_cam's and the geometry dvm_triangulate_matches_cam's;
+ * nbs[j].ep is the epipole through neighbour j's model and nbs[j].F12 is not read.  Three launches, as the pinhole chain: every ray is
+ * taken where it is used (a pre-pass that wrote all rays into a table first was measured and was no faster).  The records equal the loop
+ * of the two _cam calls bit for bit.  Under model 0 nb_poses is not read (may be NULL) and the call is
+ * dvm_create_new_map_points.  All models of one type: a NULL model, a model outside {0, 1}, a zero focal length or a mixed pair is
+ * DVM_ERR_INVALID before anything runs, and the handle stays usable.  A KF1 keypoint whose octave lies outside the tables finds nothing
+ * in a KannalaBrandt8 search unless p->coarse (under model 0 it is matched and gets status -1). */
+int dvm_create_new_map_points_cam(dvm_new_points* h, const dvm_np_keyframe* cur, const dvm_camera_model* cur_model, int n_neighbours,
+                                  const dvm_np_neighbour* nbs, const dvm_camera_model* nb_models, const dvm_pair_pose* nb_poses,
+                                  const dvm_np_params* p, dvm_np_out* out);
 /* HIP-event timing of the three launches (measurement only): enable != 0 makes every call record events; ms[3] = search, geometry,
  * settle of the last call that ran */
 int dvm_new_points_profiling(dvm_new_points* h, int enable);

@@ -174,6 +174,21 @@ void dvmh_triangulation_geometry(const dvmh_keyframe_view* KF1, const dvmh_keyfr
  * camera centres are Twc's translations; the chain handle belongs to the calling thread and is reserved on growth only. */
 int dvmh_create_new_map_points(int device, const dvmh_keyframe_view* cur, int n_neighbours, const dvmh_keyframe_view* neighbours,
                                const float* median_depth, const dvm_np_params* p, dvm_np_out* out);
+/* The three above on a camera model per keyframe (dvm_camera_model, include/dvmslam_hip.h): a KannalaBrandt8 agent's CreateNewMapPoints.
+ * The models' p[0..3] stand for the views' fx, fy, cx, cy, which are not read.  Both keyframes of a pair carry one model type (the
+ * parameters may differ): a NULL model, a model outside {0, 1}, a zero focal length or a pair of two types returns DVM_ERR_INVALID before
+ * anything runs (the reference's mixed pair is out of scope).  Model 0 gives the call above bit for bit.
+ *   dvmh_triangulation_geometry_cam     R12, t12 as above; ep = pKF2->mpCamera->project(T2w * Cw) through model2 (:848); F12 is Pinhole's
+ *                                       formula on p[0..3] and is read under model 0 only
+ *   dvmh_search_for_triangulation_cam   the candidate test is pCamera1->epipolarConstrain(pCamera2, ...) (:992): dvm_match_triangulation_cam
+ *   dvmh_create_new_map_points_cam      dvm_create_new_map_points_cam; nb_models[j] = neighbours[j]'s camera */
+int dvmh_triangulation_geometry_cam(const dvmh_keyframe_view* KF1, const dvmh_keyframe_view* KF2, const dvm_camera_model* model1,
+                                    const dvm_camera_model* model2, float* R12, float* t12, float* ep, float* F12);
+int dvmh_search_for_triangulation_cam(int device, const dvmh_keyframe_view* KF1, const dvmh_keyframe_view* KF2, const dvm_camera_model* model1,
+                                      const dvm_camera_model* model2, int coarse, int check_ori, int32_t* pairs);
+int dvmh_create_new_map_points_cam(int device, const dvmh_keyframe_view* cur, const dvm_camera_model* cur_model, int n_neighbours,
+                                   const dvmh_keyframe_view* neighbours, const dvm_camera_model* nb_models, const float* median_depth,
+                                   const dvm_np_params* p, dvm_np_out* out);
 /* Fuse(pKF, vpMapPoints, th), :1060-1234, search part: best_idx[i] = keypoint the i-th point would fuse into (-1: none) */
 int dvmh_fuse(int device, const dvmh_keyframe_view* KF, const dvmh_map_points_view* P, const uint8_t* inKF, float th, int32_t* best_idx);
 /* The same search against n_targets keyframes as ONE device chain (dvm_fuse_targets_set + dvm_fuse_targets_run, include/dvmslam_hip.h) --
