@@ -2,6 +2,7 @@
 // keyframe against many target keyframes: the searches LoopClosing::DetectCommonRegionsFromBoW runs per candidate and covisible
 // (LoopClosing.cc:722-731), all in one launch plus one launch for the rotation checks.
 #include "bow_targets_kernels.h"
+#include "match_device.h"
 #include "rot_bin.h"
 
 namespace dvm {
@@ -13,8 +14,8 @@ namespace dvm {
 // best < nnratio * second.  A keypoint of KF2 lies in exactly ONE node of KF2's FeatureVector (the host checks it while packing), so
 // vbMatched2 never couples two nodes, and targets never share anything: every (target, node of KF1) pair is one independent sequential
 // walk.  One wave per pair: the node is found in the target's list by binary search, the wave walks the node's KF1 features in order and
-// scans the target's features across its lanes (min of (distance << 20 | scan position); per lane the two smallest distances, merged as
-// k_refkf_search merges them), so every decision sees exactly the claims the reference's walk has made by then.
+// scans the target's features across its lanes (bow_node_scan, match_device.h, which k_refkf_search calls too), so every decision sees
+// exactly the claims the reference's walk has made by then.
 // Claims: lane l scans the positions l, l + 64, l + 128, ... of the node and no other lane ever reads them, so the claim flag of position
 // p is bit p / 64 of a 128-bit mask in lane p % 64's registers (a node holds at most 8192 features).  Nothing is shared between pairs,
 // whichever target the four waves of a workgroup belong to.
@@ -32,13 +33,8 @@ __global__ void __launch_bounds__(256) k_bt_search(const BtKfDev* __restrict__ t
   const int kb = C.fv_off[a], ke = C.fv_off[a + 1];
   int fb = 0, fe = 0;
   {
-    const uint32_t node = (uint32_t)C.fv_node[a];
-    int lo = 0, hi = K.fv_n;                // the target's nodes ascend as unsigned
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if ((uint32_t)K.fv_node[mid] < node) lo = mid + 1; else hi = mid;
-    }
-    if (lo < K.fv_n && (uint32_t)K.fv_node[lo] == node) { fb = K.fv_off[lo]; fe = K.fv_off[lo + 1]; }
+    const int at = fv_find<uint32_t>(K.fv_node, K.fv_n, C.fv_node[a]);   // the target's nodes ascend as unsigned
+    if (at >= 0) { fb = K.fv_off[at]; fe = K.fv_off[at + 1]; }
   }
   if (fe <= fb) {                           // the target does not have the node: nothing of it matches
     for (int k = kb + lane; k < ke; k += 64) row[C.fv_feat[k]] = -1;
@@ -51,34 +47,11 @@ __global__ void __launch_bounds__(256) k_bt_search(const BtKfDev* __restrict__ t
       if (lane == 0) row[r] = -1;
       continue;
     }
-    uint32_t w[8];
-    {
-      const uint4* q = reinterpret_cast<const uint4*>(C.desc + (size_t)r * 32);
-      const uint4 q0 = q[0], q1 = q[1];
-      w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w; w[4] = q1.x; w[5] = q1.y; w[6] = q1.z; w[7] = q1.w;
-    }
-    uint32_t best = 0xFFFFFFFFu;
-    int d1 = 256, d2 = 256;
-    int s = 0;
-    for (int p = fb + lane; p < fe; p += 64, s++) {
-      const bool taken = ((s < 64 ? claim0 >> s : claim1 >> (s - 64)) & 1) != 0;
-      const int j = K.fv_feat[p];           // (the host checked 0 <= j < n)
-      if (taken || !K.use[j]) continue;
-      const uint4* td = reinterpret_cast<const uint4*>(K.desc + (size_t)j * 32);
-      const uint4 x = td[0], y = td[1];
-      const int d = __popc(x.x ^ w[0]) + __popc(x.y ^ w[1]) + __popc(x.z ^ w[2]) + __popc(x.w ^ w[3]) + __popc(y.x ^ w[4]) + __popc(y.y ^ w[5]) +
-                    __popc(y.z ^ w[6]) + __popc(y.w ^ w[7]);
-      best = min(best, ((uint32_t)d << 20) | (uint32_t)(p - fb));
-      if (d < d1) { d2 = d1; d1 = d; }
-      else if (d < d2) d2 = d;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {     // the two smallest of two ascending pairs: min(a1, b1), min(max(a1, b1), min(a2, b2))
-      best = min(best, (uint32_t)__shfl_xor((int)best, o));
-      const int od1 = __shfl_xor(d1, o), od2 = __shfl_xor(d2, o);
-      d2 = min(max(d1, od1), min(d2, od2));
-      d1 = min(d1, od1);
-    }
+    int d2;
+    const uint32_t best = bow_node_scan(C.desc, r, K.fv_feat, fb, fe, K.desc, lane, [&](int p, int j) {   // (the host checked 0 <= j < n)
+      const int s = (p - fb) >> 6;
+      return ((s < 64 ? claim0 >> s : claim1 >> (s - 64)) & 1) != 0 || !K.use[j];
+    }, d2);
     const int bd = (int)(best >> 20);
     const bool take = bd < 50 && (float)bd < nnratio * (float)d2;     // TH_LOW, strict (:785-786)
     if (take) {
@@ -108,7 +81,7 @@ __global__ void __launch_bounds__(256) k_bt_settle(const BtKfDev* __restrict__ t
   __shared__ int s_rot[kRotHisto];
   __shared__ int s_ind[3];
   __shared__ int s_nd[4];
-  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t = blockIdx.x, tid = threadIdx.x;
   const BtKfDev C = tab[0];
   if (tid < kRotHisto) s_rot[tid] = cnt[t * kBtCnt + tid];
   __syncthreads();
@@ -122,15 +95,12 @@ __global__ void __launch_bounds__(256) k_bt_settle(const BtKfDev* __restrict__ t
     for (int p = tid; p < m1; p += 256) {
       const int i = C.fv_feat[p];
       if (row[i] < 0) continue;
-      const int b = brow[i];
-      if (b != s_ind[0] && b != s_ind[1] && b != s_ind[2]) { row[i] = -1; nd++; }
+      if (rot_dropped(brow[i], s_ind)) { row[i] = -1; nd++; }
     }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) nd += __shfl_xor(nd, o);
-  if (lane == 0) s_nd[wave] = nd;
+  block_sum4_put(nd, s_nd);
   __syncthreads();
-  if (tid == 0) nmatches[t] = cnt[t * kBtCnt + 30] - (s_nd[0] + s_nd[1] + s_nd[2] + s_nd[3]);
+  if (tid == 0) nmatches[t] = cnt[t * kBtCnt + 30] - block_sum4(s_nd);
 }
 
 void launch_bt_search(hipStream_t s, const BtKfDev* tab, int n_targets, int n1, int fv_n1, float nnratio, int32_t* match, int8_t* bin, int32_t* cnt) {

@@ -1,0 +1,162 @@
+// dvm_slam_amd/csrc/match_device.h -- the inner steps every matcher kernel shares, one definition each (match_kernels.hip, track_kernels.hip,
+// bow_targets_kernels.hip, new_points_kernels.hip, proj_device.h, tri_device.h):
+//   desc_load / desc_distance        ORBmatcher::DescriptorDistance (reference src/ORBmatcher.cc:1900-1914): popcount over 8 dwords
+//   window_scan<LANES>               Frame::GetFeaturesInArea (src/Frame.cc:712-770) over a frame's sorted keypoints
+//   row_min / row_top2               reductions over a DPP row (16 lanes);  wave_min / wave_top2 / wave_sum: over the wave
+//   block_sum4_put / block_sum4      a count summed over a workgroup of four waves
+//   fv_find / fv_node_of             lookups in a DBoW2 FeatureVector stored as (fv_node[], fv_off[], fv_feat[])
+//   bow_node_scan                    the per-feature step of ORBmatcher::SearchByBoW inside one vocabulary node
+// The tie rules live in the callers' key encodings (window keys dist << 16 | sorted position, tri_key, BoW keys dist << 20 | scan
+// position): everything here only takes minima of keys.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "match_kernels.h"
+
+namespace dvm {
+
+// ---- descriptors: 32 bytes at base + 32 * idx, read as two 16-byte loads
+__device__ __forceinline__ void desc_load(const uint8_t* __restrict__ base, int idx, uint32_t (&w)[8]) {
+  const uint4* q = reinterpret_cast<const uint4*>(base + (size_t)idx * 32);
+  const uint4 a = q[0], b = q[1];
+  w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+}
+__device__ __forceinline__ int desc_distance(const uint32_t (&w)[8], const uint8_t* __restrict__ base, int idx) {
+  const uint4* td = reinterpret_cast<const uint4*>(base + (size_t)idx * 32);
+  const uint4 a = td[0], b = td[1];
+  return __popc(a.x ^ w[0]) + __popc(a.y ^ w[1]) + __popc(a.z ^ w[2]) + __popc(a.w ^ w[3]) +
+         __popc(b.x ^ w[4]) + __popc(b.y ^ w[5]) + __popc(b.z ^ w[6]) + __popc(b.w ^ w[7]);
+}
+
+// the two smallest keys seen so far, k1 <= k2 (an equal key counts again: it becomes the second).  Written with min / max: the form
+// "if (k < k1) { k2 = k1; k1 = k; } else if (k < k2) k2 = k;" on references compiles to a store through a selected address, which
+// keeps k1 and k2 in scratch memory.
+template <class T>
+__device__ __forceinline__ void top2_insert(T& k1, T& k2, T k) {
+  k2 = min(k2, max(k1, k));
+  k1 = min(k1, k);
+}
+
+// ---- GetFeaturesInArea(x, y, r, minLevel, maxLevel) of frame F: the cell rectangle with the reference's early-outs, then the sorted
+// positions of its grid columns across LANES lanes (16: one DPP row per query; 64: the whole wave); visit(p, oct, dx, dy) for every
+// position p that passes the row, level and radius tests (oct = its octave, dx / dy = its offset from the window's centre).
+template <int LANES, class Visit>
+__device__ __forceinline__ void window_scan(const FrameView& F, float x, float y, float r, int minLevel, int maxLevel, int lane, Visit visit) {
+  const int nMinCellX = max(0, (int)floorf((x - F.minX - r) * F.wInv));
+  const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - F.minX + r) * F.wInv));
+  const int nMinCellY = max(0, (int)floorf((y - F.minY - r) * F.hInv));
+  const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - F.minY + r) * F.hInv));
+  const bool empty = nMinCellX >= kGridCols || nMaxCellX < 0 || nMinCellY >= kGridRows || nMaxCellY < 0;
+  if (empty || nMinCellX > nMaxCellX) return;
+  const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
+  const int beg = F.cellx_start[nMinCellX], end = F.cellx_start[nMaxCellX + 1];
+  for (int p = beg + lane; p < end; p += LANES) {
+    const float4 kp = F.skp[p];
+    const int oct = __float_as_int(kp.z);
+    const int iy = __float_as_int(kp.w) % kGridRows;
+    if (iy < nMinCellY || iy > nMaxCellY) continue;
+    if (checkLevels) {
+      if (oct < minLevel) continue;
+      if (maxLevel >= 0 && oct > maxLevel) continue;
+    }
+    const float dx = kp.x - x, dy = kp.y - y;
+    if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
+    visit(p, oct, dx, dy);
+  }
+}
+
+// ---- reductions.  A DPP row: xor-1, xor-2 inside quads, then half-row and row mirrors; every lane of the row ends with the result.
+#define DVM_ROW_DPP(v, CTRL, OLD) (uint32_t)__builtin_amdgcn_update_dpp(OLD, (int)(v), CTRL, 0xF, 0xF, false)
+__device__ __forceinline__ uint32_t row_min(uint32_t k) {
+  k = min(k, DVM_ROW_DPP(k, 0xB1, -1));    // quad_perm [1,0,3,2]
+  k = min(k, DVM_ROW_DPP(k, 0x4E, -1));    // quad_perm [2,3,0,1]
+  k = min(k, DVM_ROW_DPP(k, 0x141, -1));   // row_half_mirror
+  k = min(k, DVM_ROW_DPP(k, 0x140, -1));   // row_mirror
+  return k;
+}
+// the two smallest of two ascending pairs (disjoint sets): min(a1, b1), min(max(a1, b1), min(a2, b2))
+template <class T>
+__device__ __forceinline__ void top2_merge(T& k1, T& k2, T o1, T o2) {
+  const T n1 = min(k1, o1), n2 = min(max(k1, o1), min(k2, o2));
+  k1 = n1; k2 = n2;
+}
+__device__ __forceinline__ void row_top2(uint32_t& k1, uint32_t& k2) {
+  top2_merge(k1, k2, DVM_ROW_DPP(k1, 0xB1, 0), DVM_ROW_DPP(k2, 0xB1, 0));
+  top2_merge(k1, k2, DVM_ROW_DPP(k1, 0x4E, 0), DVM_ROW_DPP(k2, 0x4E, 0));
+  top2_merge(k1, k2, DVM_ROW_DPP(k1, 0x141, 0), DVM_ROW_DPP(k2, 0x141, 0));
+  top2_merge(k1, k2, DVM_ROW_DPP(k1, 0x140, 0), DVM_ROW_DPP(k2, 0x140, 0));
+}
+#undef DVM_ROW_DPP
+__device__ __forceinline__ uint32_t wave_min(uint32_t k) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) k = min(k, (uint32_t)__shfl_xor((int)k, o));
+  return k;
+}
+template <class T>
+__device__ __forceinline__ void wave_top2(T& k1, T& k2) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const T o1 = __shfl_xor(k1, o), o2 = __shfl_xor(k2, o);
+    top2_merge(k1, k2, o1, o2);
+  }
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+// The sum of v over a workgroup of four waves in two halves: every thread calls block_sum4_put(v, s4) (s4: four ints of LDS), and
+// behind the caller's next barrier block_sum4(s4) is the sum.
+__device__ __forceinline__ void block_sum4_put(int v, int* s4) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+}
+__device__ __forceinline__ int block_sum4(const int* s4) { return s4[0] + s4[1] + s4[2] + s4[3]; }
+
+// ---- FeatureVector lookups.  fv_find: the index of `node` in the ascending list fv_node[0 .. fv_n) or -1; ORDER is the type the ids
+// ascend as -- uint32_t in the lists k_refkf_bow sorts and the BoW targets pack (node -1 last), int32_t in the new-points keyframes
+// (check_keyframe, new_points.cpp).
+template <class ORDER>
+__device__ __forceinline__ int fv_find(const int32_t* __restrict__ fv_node, int fv_n, int32_t node) {
+  int lo = 0, hi = fv_n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((ORDER)fv_node[mid] < (ORDER)node) lo = mid + 1; else hi = mid;
+  }
+  return lo < fv_n && fv_node[lo] == node ? lo : -1;
+}
+// the list index of the node that holds feature position k: the last node whose offset is <= k
+__device__ __forceinline__ int fv_node_of(const int32_t* __restrict__ fv_off, int fv_n, int k) {
+  int lo = 0, hi = fv_n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (fv_off[mid] <= k) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// ---- SearchByBoW inside one node, for one query feature, by one wave: the query qdesc[r] against the features fv_feat[fb .. fe) of
+// `desc`, scan position p across the 64 lanes, those skipped for which taken(p, j) holds (j = fv_feat[p]).  Returns, in every lane, the
+// smallest (distance << 20 | scan position - fb) -- first in scan order wins -- or 0xFFFFFFFF without a candidate; second = the second
+// smallest distance (duplicates counted), 256 without one.
+template <class Taken>
+__device__ __forceinline__ uint32_t bow_node_scan(const uint8_t* __restrict__ qdesc, int r, const int32_t* __restrict__ fv_feat, int fb, int fe,
+                                                  const uint8_t* __restrict__ desc, int lane, Taken taken, int& second) {
+  uint32_t w[8];
+  desc_load(qdesc, r, w);
+  uint32_t best = 0xFFFFFFFFu;
+  int d1 = 256, d2 = 256;
+  for (int p = fb + lane; p < fe; p += 64) {
+    const int j = fv_feat[p];
+    if (taken(p, j)) continue;
+    const int d = desc_distance(w, desc, j);
+    best = min(best, ((uint32_t)d << 20) | (uint32_t)(p - fb));
+    top2_insert(d1, d2, d);
+  }
+  wave_top2(d1, d2);
+  second = d2;
+  return wave_min(best);
+}
+
+}  // namespace dvm

@@ -1,10 +1,11 @@
 // dvm_slam_amd/csrc/match_kernels.hip -- gfx950 kernels of the matching path.
 //
-//   ORBmatcher::DescriptorDistance (reference src/ORBmatcher.cc:1900-1914) -> popcount over 8 dwords
+//   ORBmatcher::DescriptorDistance (reference src/ORBmatcher.cc:1900-1914) -> desc_distance (match_device.h)
 //   Frame::AssignFeaturesToGrid / PosInGrid (src/Frame.cc:481-506,773-782)  -> k_frame_build
 //   Frame::GetFeaturesInArea (src/Frame.cc:712-770) + the best / second-best loops of
 //   ORBmatcher::SearchByProjection (src/ORBmatcher.cc:70-115,1604-1639)      -> k_match_window
-// (the grid build, the window scan and the projection row are device functions of proj_device.h: fuse_targets_kernels.hip calls them too)
+// (the grid build, the best two of a window and the projection row are device functions of proj_device.h: fuse_targets_kernels.hip calls
+// them too; the window scan itself, the descriptor distance and the row / wave reductions are match_device.h's, shared with the chains)
 //
 // Layout: a frame's keypoints are stored SORTED by (grid column ix, grid row iy, keypoint index) --
 // exactly the order in which GetFeaturesInArea enumerates candidates -- so "first candidate wins a
@@ -12,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "frustum_point.h"
+#include "match_device.h"
 #include "match_kernels.h"
 #include "pose_f32.h"
 #include "proj_device.h"
@@ -140,38 +142,13 @@ __global__ void __launch_bounds__(256) k_match_window_ranked(FrameView FB, int s
   const int minLevel = qmin[q], maxLevel = qmax[q];
   const uint32_t none = (256u << 16) | 0xFFFFu;
   uint32_t k[4] = {none, none, none, none};
-  const int nMinCellX = max(0, (int)floorf((x - F.minX - r) * F.wInv));
-  const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - F.minX + r) * F.wInv));
-  const int nMinCellY = max(0, (int)floorf((y - F.minY - r) * F.hInv));
-  const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - F.minY + r) * F.hInv));
-  const bool empty = nMinCellX >= kGridCols || nMaxCellX < 0 || nMinCellY >= kGridRows || nMaxCellY < 0;
-  if (!empty && nMinCellX <= nMaxCellX) {
-    const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
-    const uint32_t* qd = reinterpret_cast<const uint32_t*>(qdesc + (size_t)q * 32);
-    uint32_t w[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) w[i] = qd[i];
-    const int beg = F.cellx_start[nMinCellX], end = F.cellx_start[nMaxCellX + 1];
-    for (int p = beg + lane; p < end; p += 16) {
-      const float4 kp = F.skp[p];
-      const int oct = __float_as_int(kp.z);
-      const int iy = __float_as_int(kp.w) % kGridRows;
-      if (iy < nMinCellY || iy > nMaxCellY) continue;
-      if (checkLevels) {
-        if (oct < minLevel) continue;
-        if (maxLevel >= 0 && oct > maxLevel) continue;
-      }
-      const float dx = kp.x - x, dy = kp.y - y;
-      if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
-      if (skip && skip[F.sidx[p]]) continue;
-      const uint4* td = reinterpret_cast<const uint4*>(F.sdesc + (size_t)p * 32);
-      const uint4 a = td[0], b = td[1];
-      const int d = __popc(a.x ^ w[0]) + __popc(a.y ^ w[1]) + __popc(a.z ^ w[2]) + __popc(a.w ^ w[3]) +
-                    __popc(b.x ^ w[4]) + __popc(b.y ^ w[5]) + __popc(b.z ^ w[6]) + __popc(b.w ^ w[7]);
-      const uint32_t key = ((uint32_t)d << 16) | (uint32_t)p;
-      if (key < k[3]) { k[3] = key; sort4(k); }
-    }
-  }
+  uint32_t w[8];
+  desc_load(qdesc, q, w);
+  window_scan<16>(F, x, y, r, minLevel, maxLevel, lane, [&](int p, int, float, float) {
+    if (skip && skip[F.sidx[p]]) return;
+    const uint32_t key = ((uint32_t)desc_distance(w, F.sdesc, p) << 16) | (uint32_t)p;
+    if (key < k[3]) { k[3] = key; sort4(k); }
+  });
   // the four smallest of two ascending 4-lists: min(a[i], b[3 - i]) (a bitonic half-cleaner), sorted again; the sets are disjoint
 #define DVM_TOP4_STEP(CTRL)                                                                                     \
   {                                                                                                             \
@@ -205,28 +182,17 @@ __global__ void __launch_bounds__(256) k_match_lists(const uint8_t* __restrict__
   const int lane = threadIdx.x & 63;
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= nq) return;
-  const uint32_t* qd = reinterpret_cast<const uint32_t*>(qdesc + (size_t)q * 32);
   uint32_t w[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) w[i] = qd[i];
+  desc_load(qdesc, q, w);
   const int beg = off[q], end = off[q + 1];
   unsigned long long k1 = (256ull << 32) | 0xFFFFFFFFull, k2 = k1;
   for (int p = beg + lane; p < end; p += 64) {
     const int idx = cand[p];
     if (idx < 0) continue;  // caller-masked candidate
-    const uint4* td = reinterpret_cast<const uint4*>(tdesc + (size_t)idx * 32);
-    const uint4 a = td[0], b = td[1];
-    const int d = __popc(a.x ^ w[0]) + __popc(a.y ^ w[1]) + __popc(a.z ^ w[2]) + __popc(a.w ^ w[3]) +
-                  __popc(b.x ^ w[4]) + __popc(b.y ^ w[5]) + __popc(b.z ^ w[6]) + __popc(b.w ^ w[7]);
-    const unsigned long long k = ((unsigned long long)d << 32) | (unsigned)(p - beg);
-    if (k < k1) { k2 = k1; k1 = k; } else if (k < k2) k2 = k;
+    const unsigned long long k = ((unsigned long long)desc_distance(w, tdesc, idx) << 32) | (unsigned)(p - beg);
+    if (k < k1) { k2 = k1; k1 = k; } else if (k < k2) k2 = k;     // (64-bit keys: the branch is cheaper than top2_insert's min / max)
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long o1 = __shfl_xor(k1, o), o2 = __shfl_xor(k2, o);
-    const unsigned long long n1 = min(k1, o1), n2 = min(max(k1, o1), min(k2, o2));
-    k1 = n1; k2 = n2;
-  }
+  wave_top2(k1, k2);
   if (lane == 0) {
     dvm_match_pod m;
     m.best_dist = (int)(k1 >> 32);
@@ -321,7 +287,7 @@ __global__ void __launch_bounds__(256) k_match_triangulation(const uint8_t* __re
     if (d < 0) continue;
     k = min(k, tri_key(d, p - beg));
   }
-  k = tri_row_min(k);
+  k = row_min(k);
   if (lane == 0) {
     const bool hit = k != 0xFFFFFFFFu;
     best_idx[q] = hit ? cand[beg + tri_key_pos(k)] : -1;
@@ -413,23 +379,26 @@ __global__ void __launch_bounds__(256) k_bowdb_query(const int64_t* __restrict__
 
 // Frame::isInFrustum, mono branch (reference src/Frame.cc:575-636) + MapPoint::PredictScale
 // (src/MapPoint.cc:573-587): thread per map point, float arithmetic in the reference's order (frustum_point.h).
+// MODEL: the camera behind mpCamera->project; kb8 = mvParameters for KannalaBrandt8, unused for the pinhole camera.
+template <int MODEL>
+__device__ __forceinline__ void is_in_frustum_thread(const FrustumFrame& F, const float* kb8, const float* __restrict__ P, const float* __restrict__ normal,
+                                                     const float* __restrict__ min_dist, const float* __restrict__ max_dist, int n, float cos_limit,
+                                                     TrackPoint* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = frustum_point<MODEL>(F, P[3 * i], P[3 * i + 1], P[3 * i + 2], normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], min_dist[i], max_dist[i],
+                                cos_limit, kb8);
+}
 __global__ void __launch_bounds__(256) k_is_in_frustum(FrustumFrame F, const float* __restrict__ P, const float* __restrict__ normal,
                                                        const float* __restrict__ min_dist, const float* __restrict__ max_dist,
                                                        int n, float cos_limit, TrackPoint* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  out[i] = frustum_point(F, P[3 * i], P[3 * i + 1], P[3 * i + 2], normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], min_dist[i], max_dist[i],
-                         cos_limit);
+  is_in_frustum_thread<dvm_cam::kPinhole>(F, nullptr, P, normal, min_dist, max_dist, n, cos_limit, out);
 }
-
-// k_is_in_frustum with mpCamera->project of a KannalaBrandt8 camera (dvm_is_in_frustum_cam, model 1): frustum_point<KannalaBrandt8>
+// the same with mpCamera->project of a KannalaBrandt8 camera (dvm_is_in_frustum_cam, model 1)
 __global__ void __launch_bounds__(256) k_is_in_frustum_kb8(FrustumFrame F, CamParams K, const float* __restrict__ P, const float* __restrict__ normal,
                                                            const float* __restrict__ min_dist, const float* __restrict__ max_dist,
                                                            int n, float cos_limit, TrackPoint* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  out[i] = frustum_point<dvm_cam::kKannalaBrandt8>(F, P[3 * i], P[3 * i + 1], P[3 * i + 2], normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], min_dist[i],
-                                                   max_dist[i], cos_limit, K.p);
+  is_in_frustum_thread<dvm_cam::kKannalaBrandt8>(F, K.p, P, normal, min_dist, max_dist, n, cos_limit, out);
 }
 
 // LocalMapping::CreateNewMapPoints, the geometry of one neighbour keyframe's matches (reference src/LocalMapping.cc:598-741, monocular
@@ -437,20 +406,38 @@ __global__ void __launch_bounds__(256) k_is_in_frustum_kb8(FrustumFrame F, CamPa
 // homogeneous point (null vector of the 4x4 system: eigenvector of the smallest eigenvalue of A^T A by cyclic Jacobi in double --
 // the reference runs Eigen::JacobiSVD<Matrix4f>, tolerance parity), depth, reprojection error and scale-consistency tests in float
 // in Eigen's evaluation order, comparisons with double literals in double.  status: include/dvmslam_hip.h.
-__global__ void __launch_bounds__(128) k_triangulate_matches(TriPair P, const dvm_keypoint_pod* __restrict__ kps1, int n1,
-                                                             const dvm_keypoint_pod* __restrict__ kps2, int n2,
-                                                             const int32_t* __restrict__ pairs, int n, const float* __restrict__ sigma2_1,
-                                                             const float* __restrict__ sigma2_2, const float* __restrict__ sf1,
-                                                             const float* __restrict__ sf2, float* __restrict__ x3D_out,
-                                                             int32_t* __restrict__ status) {
+// MODEL: tri_pair_geometry<MODEL>; for KannalaBrandt8 (dvm_triangulate_matches_cam, model 1) the rays come from kb8_unproject and both
+// reprojections go through kb8_project on cam1 / cam2, and P.K1 / P.K2 are not read.
+template <int MODEL>
+__device__ __forceinline__ void triangulate_match_thread(const TriPair& P, const float* cam1, const float* cam2, const dvm_keypoint_pod* __restrict__ kps1,
+                                                         int n1, const dvm_keypoint_pod* __restrict__ kps2, int n2, const int32_t* __restrict__ pairs,
+                                                         int n, const float* __restrict__ sigma2_1, const float* __restrict__ sigma2_2,
+                                                         const float* __restrict__ sf1, const float* __restrict__ sf2, float* __restrict__ x3D_out,
+                                                         int32_t* __restrict__ status) {
   const int m = blockIdx.x * 128 + threadIdx.x;
   if (m >= n) return;
   float* X = x3D_out + 3 * (int64_t)m;
   const int i1 = pairs[2 * m], i2 = pairs[2 * m + 1];
   if (i1 < 0 || i1 >= n1 || i2 < 0 || i2 >= n2) { X[0] = X[1] = X[2] = 0.0f; status[m] = -1; return; }
   float x[3];
-  status[m] = tri_pair_geometry(P, kps1[i1], kps2[i2], sigma2_1, sigma2_2, sf1, sf2, x);
+  status[m] = tri_pair_geometry<MODEL>(P, kps1[i1], kps2[i2], sigma2_1, sigma2_2, sf1, sf2, x, cam1, cam2);
   X[0] = x[0]; X[1] = x[1]; X[2] = x[2];
+}
+__global__ void __launch_bounds__(128) k_triangulate_matches(TriPair P, const dvm_keypoint_pod* __restrict__ kps1, int n1,
+                                                             const dvm_keypoint_pod* __restrict__ kps2, int n2,
+                                                             const int32_t* __restrict__ pairs, int n, const float* __restrict__ sigma2_1,
+                                                             const float* __restrict__ sigma2_2, const float* __restrict__ sf1,
+                                                             const float* __restrict__ sf2, float* __restrict__ x3D_out,
+                                                             int32_t* __restrict__ status) {
+  triangulate_match_thread<dvm_cam::kPinhole>(P, nullptr, nullptr, kps1, n1, kps2, n2, pairs, n, sigma2_1, sigma2_2, sf1, sf2, x3D_out, status);
+}
+__global__ void __launch_bounds__(128) k_triangulate_matches_kb8(TriPair P, CamParams C1, CamParams C2, const dvm_keypoint_pod* __restrict__ kps1, int n1,
+                                                                 const dvm_keypoint_pod* __restrict__ kps2, int n2,
+                                                                 const int32_t* __restrict__ pairs, int n, const float* __restrict__ sigma2_1,
+                                                                 const float* __restrict__ sigma2_2, const float* __restrict__ sf1,
+                                                                 const float* __restrict__ sf2, float* __restrict__ x3D_out,
+                                                                 int32_t* __restrict__ status) {
+  triangulate_match_thread<dvm_cam::kKannalaBrandt8>(P, C1.p, C2.p, kps1, n1, kps2, n2, pairs, n, sigma2_1, sigma2_2, sf1, sf2, x3D_out, status);
 }
 void launch_triangulate_matches(hipStream_t s, const TriPair& P, const dvm_keypoint_pod* kps1, int n1, const dvm_keypoint_pod* kps2, int n2,
                                 const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2, const float* sf1,
@@ -459,23 +446,6 @@ void launch_triangulate_matches(hipStream_t s, const TriPair& P, const dvm_keypo
                      x3D, status);
 }
 
-// k_triangulate_matches on a KannalaBrandt8 pair (dvm_triangulate_matches_cam, model 1): tri_pair_geometry<KannalaBrandt8>, the rays from
-// kb8_unproject and both reprojections through kb8_project; P.K1 / P.K2 are not read.
-__global__ void __launch_bounds__(128) k_triangulate_matches_kb8(TriPair P, CamParams C1, CamParams C2, const dvm_keypoint_pod* __restrict__ kps1, int n1,
-                                                                 const dvm_keypoint_pod* __restrict__ kps2, int n2,
-                                                                 const int32_t* __restrict__ pairs, int n, const float* __restrict__ sigma2_1,
-                                                                 const float* __restrict__ sigma2_2, const float* __restrict__ sf1,
-                                                                 const float* __restrict__ sf2, float* __restrict__ x3D_out,
-                                                                 int32_t* __restrict__ status) {
-  const int m = blockIdx.x * 128 + threadIdx.x;
-  if (m >= n) return;
-  float* X = x3D_out + 3 * (int64_t)m;
-  const int i1 = pairs[2 * m], i2 = pairs[2 * m + 1];
-  if (i1 < 0 || i1 >= n1 || i2 < 0 || i2 >= n2) { X[0] = X[1] = X[2] = 0.0f; status[m] = -1; return; }
-  float x[3];
-  status[m] = tri_pair_geometry<dvm_cam::kKannalaBrandt8>(P, kps1[i1], kps2[i2], sigma2_1, sigma2_2, sf1, sf2, x, C1.p, C2.p);
-  X[0] = x[0]; X[1] = x[1]; X[2] = x[2];
-}
 void launch_triangulate_matches_kb8(hipStream_t s, const TriPair& P, const CamParams& C1, const CamParams& C2, const dvm_keypoint_pod* kps1, int n1,
                                     const dvm_keypoint_pod* kps2, int n2, const int32_t* pairs, int n, const float* sigma2_1, const float* sigma2_2,
                                     const float* sf1, const float* sf2, float* x3D, int32_t* status) {
@@ -489,12 +459,9 @@ __global__ void __launch_bounds__(256) k_hamming_matrix(const uint8_t* __restric
   const int j = blockIdx.x * 64 + (threadIdx.x & 63);
   const int i = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (i >= nA || j >= nB) return;
-  const uint4* a = reinterpret_cast<const uint4*>(A + (size_t)i * 32);
-  const uint4* b = reinterpret_cast<const uint4*>(B + (size_t)j * 32);
-  const uint4 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
-  int d = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-          __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-  D[(size_t)i * nB + j] = (uint16_t)d;
+  uint32_t w[8];
+  desc_load(A, i, w);
+  D[(size_t)i * nB + j] = (uint16_t)desc_distance(w, B, j);
 }
 
 void launch_frame_build(hipStream_t s, const dvm_keypoint_pod* kps, int64_t kps_stride, const uint8_t* desc,
@@ -662,11 +629,7 @@ __global__ void __launch_bounds__(256) k_vocab_transform(const int32_t* __restri
   if (d_n) n = min(n, *d_n);     // (a count still on the device: n is then the capacity the grid covers)
   if (f >= n) return;
   uint32_t w[8];
-  {
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(feat + (size_t)f * 32);
-#pragma unroll
-    for (int i = 0; i < 8; i++) w[i] = q[i];
-  }
+  desc_load(feat, f, w);
   const int nid_level = L - levelsup;
   int nid = nid_level <= 0 ? 0 : -1;   // the reference leaves *nid unset if the walk ends above nid_level
   int cur = 0, level = 0;
@@ -677,19 +640,10 @@ __global__ void __launch_bounds__(256) k_vocab_transform(const int32_t* __restri
     for (int base = c0; base < c1; base += 16) {
       const int c = base + lane;
       uint32_t key = 0xFFFFFFFFu;
-      if (c < c1) {
-        const uint4* d = reinterpret_cast<const uint4*>(node_desc + (size_t)children[c] * 32);
-        const uint4 a = d[0], b = d[1];
-        const int dist = __popc(a.x ^ w[0]) + __popc(a.y ^ w[1]) + __popc(a.z ^ w[2]) + __popc(a.w ^ w[3]) +
-                         __popc(b.x ^ w[4]) + __popc(b.y ^ w[5]) + __popc(b.z ^ w[6]) + __popc(b.w ^ w[7]);
-        key = ((uint32_t)dist << 16) | (uint32_t)(c - c0);
-      }
+      if (c < c1) key = ((uint32_t)desc_distance(w, node_desc, children[c]) << 16) | (uint32_t)(c - c0);
       best = min(best, key);
     }
-    best = min(best, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)best, 0xB1, 0xF, 0xF, false));
-    best = min(best, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)best, 0x4E, 0xF, 0xF, false));
-    best = min(best, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)best, 0x141, 0xF, 0xF, false));
-    best = min(best, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)best, 0x140, 0xF, 0xF, false));
+    best = row_min(best);
     cur = children[c0 + (int)(best & 0xFFFFu)];
     if (level == nid_level) nid = cur;
     c0 = child_off[cur]; c1 = child_off[cur + 1];

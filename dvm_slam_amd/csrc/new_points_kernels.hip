@@ -8,7 +8,8 @@
 //                   histogram (:961-1031), the survivors are compacted in ascending idx1 with their precomputed status and point, and the
 //                   keypoints of accepted pairs are marked (what pKF->AddMapPoint does to the table, :744)
 // The launches' order carries the dependency; no workgroup waits for another inside a kernel.  The per-candidate test and the per-pair
-// geometry are the functions the single calls run (tri_device.h).
+// geometry are the functions the single calls run (tri_device.h); the FeatureVector lookups are match_device.h's.  The pinhole and the
+// KannalaBrandt8 kernels of a pair are one template body each.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -18,30 +19,29 @@
 
 namespace dvm {
 
-// One DPP row (16 lanes) per (KF1 feature position k, neighbour blockIdx.y).  The row finds k's vocabulary node (the last node whose
-// offset is <= k), looks the node up in the neighbour's FeatureVector (node ids ascend) and scans that node's KF2 features across its
-// lanes, those with a map point skipped; a tie goes to the last candidate in the node's order, as in k_match_triangulation.
+// What the row of KF1 feature position k asks of neighbour N: idx1 = the keypoint, [fb, fe) = the positions of k's vocabulary node in N's
+// FeatureVector (node ids ascend as signed).  false: nothing to search -- k past the list, a keypoint with a MapPoint at entry (never
+// asked), or a node the neighbour lacks.
+__device__ __forceinline__ bool np_node_range(const NpArgs& A, const NpNbDev& N, int k, int& idx1, int& fb, int& fe) {
+  const NpKfDev& C = A.cur;
+  if (k >= A.nfeat1) return false;
+  idx1 = C.fv_feat[k];
+  if (C.mp[idx1] >= 0) return false;
+  const int at = fv_find<int32_t>(N.kf.fv_node, N.kf.fv_n, C.fv_node[fv_node_of(C.fv_off, C.fv_n, k)]);
+  if (at < 0) return false;
+  fb = N.kf.fv_off[at]; fe = N.kf.fv_off[at + 1];
+  return true;
+}
+
+// One DPP row (16 lanes) per (KF1 feature position k, neighbour blockIdx.y).  The row scans the KF2 features of k's node (np_node_range)
+// across its lanes, those with a map point skipped; a tie goes to the last candidate in the node's order, as in k_match_triangulation.
 __global__ void __launch_bounds__(256) k_np_search(NpArgs A) {
   const int lane = threadIdx.x & 15;
   const int k = blockIdx.x * 16 + (threadIdx.x >> 4);
-  if (k >= A.nfeat1) return;
   const NpKfDev& C = A.cur;
-  const int idx1 = C.fv_feat[k];
-  if (C.mp[idx1] >= 0) return;                       // already a MapPoint at entry: never asked
   const NpNbDev& N = A.nb[blockIdx.y];
-  int lo = 0, hi = C.fv_n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (C.fv_off[mid] <= k) lo = mid; else hi = mid - 1;
-  }
-  const int node = C.fv_node[lo];
-  lo = 0; hi = N.kf.fv_n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (N.kf.fv_node[mid] < node) lo = mid + 1; else hi = mid;
-  }
-  if (lo >= N.kf.fv_n || N.kf.fv_node[lo] != node) return;
-  const int fb = N.kf.fv_off[lo], fe = N.kf.fv_off[lo + 1];
+  int idx1 = 0, fb = 0, fe = 0;
+  if (!np_node_range(A, N, k, idx1, fb, fe)) return;
   const TriQuery Q = tri_query(C.desc, C.kps, idx1, N.G.F12);
   uint32_t key = 0xFFFFFFFFu;
   for (int p = fb + lane; p < fe; p += 16) {
@@ -52,22 +52,27 @@ __global__ void __launch_bounds__(256) k_np_search(NpArgs A) {
     if (d < 0) continue;
     key = min(key, tri_key(d, p - fb));
   }
-  key = tri_row_min(key);
+  key = row_min(key);
   if (lane == 0 && key != 0xFFFFFFFFu) A.best[(size_t)blockIdx.y * A.n1p + idx1] = N.kf.fv_feat[fb + tri_key_pos(key)];
 }
 
-// thread per (KF1 keypoint, neighbour blockIdx.y) with a best candidate
-__global__ void __launch_bounds__(128) k_np_geometry(NpArgs A) {
+// thread per (KF1 keypoint, neighbour blockIdx.y) with a best candidate: tri_pair_geometry<MODEL>, for KannalaBrandt8 on the pair's
+// cameras G[blockIdx.y].cam1 / cam2 (G is not read for the pinhole camera)
+template <int MODEL>
+__device__ __forceinline__ void np_geometry_thread(const NpArgs& A, const TriGeomKB8* G) {
   const int i = blockIdx.x * 128 + threadIdx.x;
   if (i >= A.n1) return;
   const size_t o = (size_t)blockIdx.y * A.n1p + i;
   const int m = A.best[o];
   if (m < 0) return;
   const NpNbDev& N = A.nb[blockIdx.y];
+  const float *cam1 = nullptr, *cam2 = nullptr;
+  if constexpr (MODEL == dvm_cam::kKannalaBrandt8) { cam1 = G[blockIdx.y].cam1; cam2 = G[blockIdx.y].cam2; }
   float x[3];
-  A.st[o] = tri_pair_geometry(N.P, A.cur.kps[i], N.kf.kps[m], A.cur.sigma2, N.kf.sigma2, A.cur.sf, N.kf.sf, x);
+  A.st[o] = tri_pair_geometry<MODEL>(N.P, A.cur.kps[i], N.kf.kps[m], A.cur.sigma2, N.kf.sigma2, A.cur.sf, N.kf.sf, x, cam1, cam2);
   A.X[3 * o] = x[0]; A.X[3 * o + 1] = x[1]; A.X[3 * o + 2] = x[2];
 }
+__global__ void __launch_bounds__(128) k_np_geometry(NpArgs A) { np_geometry_thread<dvm_cam::kPinhole>(A, nullptr); }
 
 // One workgroup; thread t owns the keypoints [t * chunk, (t + 1) * chunk) (chunk <= 8: 8192 keypoints), so the table in LDS is only ever
 // touched by its owner and the records of a neighbour come out in ascending idx1 from an exclusive scan of the per-thread counts.
@@ -108,7 +113,7 @@ __global__ void __launch_bounds__(1024) k_np_settle(NpArgs A) {
     if (A.check_ori) {
 #pragma unroll
       for (int j = 0; j < 8; j++)
-        if (!(bins[j] >= 0 && (bins[j] == s_ind[0] || bins[j] == s_ind[1] || bins[j] == s_ind[2]))) keep &= ~(1u << j);
+        if (bins[j] < 0 || rot_dropped(bins[j], s_ind)) keep &= ~(1u << j);
     }
     const int cnt = __popc(keep);
     int incl = cnt;                                   // inclusive scan inside the wave, then over the 16 waves
@@ -153,47 +158,15 @@ __global__ void __launch_bounds__(256) k_np_search_kb8(NpArgsKB8 K) {
   const NpKfDev& C = A.cur;
   const NpNbDev& N = A.nb[blockIdx.y];
   const TriGeomKB8& G = K.G[blockIdx.y];
-  bool active = k < A.nfeat1;
   int idx1 = 0, fb = 0, fe = 0;
-  if (active) {
-    idx1 = C.fv_feat[k];
-    active = C.mp[idx1] < 0;                         // already a MapPoint at entry: never asked
-  }
-  if (active) {
-    int lo = 0, hi = C.fv_n - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (C.fv_off[mid] <= k) lo = mid; else hi = mid - 1;
-    }
-    const int node = C.fv_node[lo];
-    lo = 0; hi = N.kf.fv_n;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (N.kf.fv_node[mid] < node) lo = mid + 1; else hi = mid;
-    }
-    active = lo < N.kf.fv_n && N.kf.fv_node[lo] == node;
-    if (active) { fb = N.kf.fv_off[lo]; fe = N.kf.fv_off[lo + 1]; }
-  }
+  const bool active = np_node_range(A, N, k, idx1, fb, fe);
   const uint32_t key = tri_rows_kb8(S, active, C.desc, C.kps, idx1, fb, fe,
                                     [&](int p) { const int idx2 = N.kf.fv_feat[p]; return N.kf.mp[idx2] >= 0 ? -1 : idx2; }, N.kf.desc, N.kf.kps, G,
                                     C.sigma2, N.kf.sf, N.kf.sigma2, A.n_levels);
   if (lane == 0 && active && key != 0xFFFFFFFFu) A.best[(size_t)blockIdx.y * A.n1p + idx1] = N.kf.fv_feat[fb + tri_key_pos(key)];
 }
 
-// k_np_geometry with tri_pair_geometry<KannalaBrandt8>
-__global__ void __launch_bounds__(128) k_np_geometry_kb8(NpArgsKB8 K) {
-  const NpArgs& A = K.A;
-  const int i = blockIdx.x * 128 + threadIdx.x;
-  if (i >= A.n1) return;
-  const size_t o = (size_t)blockIdx.y * A.n1p + i;
-  const int m = A.best[o];
-  if (m < 0) return;
-  const NpNbDev& N = A.nb[blockIdx.y];
-  const TriGeomKB8& G = K.G[blockIdx.y];
-  float x[3];
-  A.st[o] = tri_pair_geometry<dvm_cam::kKannalaBrandt8>(N.P, A.cur.kps[i], N.kf.kps[m], A.cur.sigma2, N.kf.sigma2, A.cur.sf, N.kf.sf, x, G.cam1, G.cam2);
-  A.X[3 * o] = x[0]; A.X[3 * o + 1] = x[1]; A.X[3 * o + 2] = x[2];
-}
+__global__ void __launch_bounds__(128) k_np_geometry_kb8(NpArgsKB8 K) { np_geometry_thread<dvm_cam::kKannalaBrandt8>(K.A, K.G); }
 
 void launch_np_search_kb8(hipStream_t s, const NpArgsKB8& K) {
   if (K.A.nrun < 1 || K.A.nfeat1 < 1) return;

@@ -1,12 +1,14 @@
 // dvm_slam_amd/csrc/proj_device.h -- device code the searches over a feature grid share: the grid build of one frame (k_frame_build,
-// k_ft_build), the window scan of one DPP row (k_match_window, k_project_search, k_ft_search) and the projection of one map point into a
-// keyframe with its window search (k_project_search, k_ft_search).  One definition each: a kernel that batches the work of another calls
-// the function the other calls, so their results agree bit for bit.
+// k_ft_build), the best two of a window by one DPP row (window_top2: k_match_window, k_project_search, k_ft_search; the scan itself is
+// window_scan of match_device.h) and the projection of one map point into a keyframe with its window search (k_project_search,
+// k_ft_search).  One definition each: a kernel that batches the work of another calls the function the other calls, so their results
+// agree bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "camera_model.h"
+#include "match_device.h"
 #include "match_kernels.h"
 #include "pose_f32.h"
 
@@ -92,12 +94,7 @@ __device__ __forceinline__ void frame_build_block(const dvm_keypoint_pod* __rest
   }
 }
 
-__device__ __forceinline__ void top2_insert(uint32_t& k1, uint32_t& k2, uint32_t k) {
-  if (k < k1) { k2 = k1; k1 = k; }
-  else if (k < k2) k2 = k;
-}
-
-// GetFeaturesInArea(x, y, r, minLevel, maxLevel) of frame F scanned by one DPP row (16 lanes): best / second best
+// GetFeaturesInArea(x, y, r, minLevel, maxLevel) of frame F scanned by one DPP row (window_scan<16>, match_device.h): best / second best
 // (dist << 16 | sorted position) after the row reduction, identical on all 16 lanes.  gate_inv_sigma2 != nullptr adds the
 // per-candidate reprojection gate of ORBmatcher::Fuse (ORBmatcher.cc:1187-1196): skip if (ex^2 + ey^2) * invSigma2[octave]
 // > gate (the comparison is made in double there: 5.99 is a double literal).
@@ -106,56 +103,17 @@ __device__ __forceinline__ void window_top2(const FrameView& F, float x, float y
                                             const float* __restrict__ gate_inv_sigma2, double gate, int lane, uint32_t& k1_out,
                                             uint32_t& k2_out) {
   uint32_t k1 = (256u << 16) | 0xFFFFu, k2 = k1;
-  // GetFeaturesInArea cell rectangle (with the reference's early-outs)
-  const int nMinCellX = max(0, (int)floorf((x - F.minX - r) * F.wInv));
-  const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - F.minX + r) * F.wInv));
-  const int nMinCellY = max(0, (int)floorf((y - F.minY - r) * F.hInv));
-  const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - F.minY + r) * F.hInv));
-  const bool empty = nMinCellX >= kGridCols || nMaxCellX < 0 || nMinCellY >= kGridRows || nMaxCellY < 0;
-  if (!empty && nMinCellX <= nMaxCellX) {
-    const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
-    const uint32_t* qd = reinterpret_cast<const uint32_t*>(qdesc32);
-    uint32_t w[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) w[i] = qd[i];
-    const int beg = F.cellx_start[nMinCellX], end = F.cellx_start[nMaxCellX + 1];
-    for (int p = beg + lane; p < end; p += 16) {
-      const float4 kp = F.skp[p];
-      const int oct = __float_as_int(kp.z);
-      const int cell = __float_as_int(kp.w);
-      const int iy = cell % kGridRows;
-      if (iy < nMinCellY || iy > nMaxCellY) continue;
-      if (checkLevels) {
-        if (oct < minLevel) continue;
-        if (maxLevel >= 0 && oct > maxLevel) continue;
-      }
-      const float dx = kp.x - x, dy = kp.y - y;
-      if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
-      if (skip && skip[F.sidx[p]]) continue;
-      if (gate_inv_sigma2) {
-        const float e2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
-        if ((double)__fmul_rn(e2, gate_inv_sigma2[oct]) > gate) continue;
-      }
-      const uint4* td = reinterpret_cast<const uint4*>(F.sdesc + (size_t)p * 32);
-      const uint4 a = td[0], b = td[1];
-      int d = __popc(a.x ^ w[0]) + __popc(a.y ^ w[1]) + __popc(a.z ^ w[2]) + __popc(a.w ^ w[3]) +
-              __popc(b.x ^ w[4]) + __popc(b.y ^ w[5]) + __popc(b.z ^ w[6]) + __popc(b.w ^ w[7]);
-      top2_insert(k1, k2, ((uint32_t)d << 16) | (uint32_t)p);
+  uint32_t w[8];
+  desc_load(qdesc32, 0, w);
+  window_scan<16>(F, x, y, r, minLevel, maxLevel, lane, [&](int p, int oct, float dx, float dy) {
+    if (skip && skip[F.sidx[p]]) return;
+    if (gate_inv_sigma2) {
+      const float e2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+      if ((double)__fmul_rn(e2, gate_inv_sigma2[oct]) > gate) return;
     }
-  }
-  // top-2 of the row: xor-1, xor-2 inside quads, then half-row and row mirrors (the merged sets are disjoint)
-#define DVM_TOP2_STEP(CTRL)                                                              \
-  {                                                                                      \
-    const uint32_t o1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)k1, CTRL, 0xF, 0xF, false); \
-    const uint32_t o2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)k2, CTRL, 0xF, 0xF, false); \
-    const uint32_t n1 = min(k1, o1), n2 = min(max(k1, o1), min(k2, o2));                 \
-    k1 = n1; k2 = n2;                                                                    \
-  }
-  DVM_TOP2_STEP(0xB1)    // quad_perm [1,0,3,2]
-  DVM_TOP2_STEP(0x4E)    // quad_perm [2,3,0,1]
-  DVM_TOP2_STEP(0x141)   // row_half_mirror
-  DVM_TOP2_STEP(0x140)   // row_mirror
-#undef DVM_TOP2_STEP
+    top2_insert(k1, k2, ((uint32_t)desc_distance(w, F.sdesc, p) << 16) | (uint32_t)p);
+  });
+  row_top2(k1, k2);
   k1_out = k1; k2_out = k2;
 }
 

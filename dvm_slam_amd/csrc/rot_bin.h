@@ -1,6 +1,6 @@
 // dvm_slam_amd/csrc/rot_bin.h -- the rotation-histogram bin of ORBmatcher (HISTO_LENGTH = 30, e.g. src/ORBmatcher.cc:324-329): the one
 // float expression the host mirror (host/orb_matcher.cpp) and the device chains (track_kernels.hip, new_points_kernels.hip) both evaluate,
-// and ComputeThreeMaxima as the device chains run it.
+// and ComputeThreeMaxima with the test it ends in, as the device chains run them.
 #pragma once
 #include <math.h>
 
@@ -35,4 +35,6 @@ DVM_ROT_HD inline void three_maxima(const int* hist, int* ind) {
   else if ((float)max3 < 0.1f * (float)max1) ind3 = -1;
   ind[0] = ind1; ind[1] = ind2; ind[2] = ind3;
 }
+// the rotation check takes back a match whose bin is none of the three maxima (e.g. ORBmatcher.cc:1730-1745)
+DVM_ROT_HD inline bool rot_dropped(int bin, const int* ind) { return bin != ind[0] && bin != ind[1] && bin != ind[2]; }
 }  // namespace dvm

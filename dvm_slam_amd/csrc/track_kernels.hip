@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "frustum_point.h"
+#include "match_device.h"
 #include "match_kernels.h"
 #include "pose_f32.h"
 #include "rot_bin.h"
@@ -161,55 +162,17 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
           const int minLevel = RQ.qmin[qf], maxLevel = RQ.qmax[qf];
           const FrameView& F = RQ.F;
           uint32_t best = (256u << 16) | 0xFFFFu, best2 = best;
-          const int nMinCellX = max(0, (int)floorf((x - F.minX - r) * F.wInv));
-          const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - F.minX + r) * F.wInv));
-          const int nMinCellY = max(0, (int)floorf((y - F.minY - r) * F.hInv));
-          const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - F.minY + r) * F.hInv));
-          const bool empty = nMinCellX >= kGridCols || nMaxCellX < 0 || nMinCellY >= kGridRows || nMaxCellY < 0;
-          if (!empty && nMinCellX <= nMaxCellX) {
-            const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
-            const uint32_t* qd = reinterpret_cast<const uint32_t*>(RQ.qdesc + (size_t)qf * 32);
-            uint32_t w[8];
-#pragma unroll
-            for (int i = 0; i < 8; i++) w[i] = qd[i];
-            const int beg = F.cellx_start[nMinCellX], end = F.cellx_start[nMaxCellX + 1];
-            for (int p = beg + lane; p < end; p += 64) {
-              const float4 kp = F.skp[p];
-              const int idx = F.sidx[p];
-              const uint4* td = reinterpret_cast<const uint4*>(F.sdesc + (size_t)p * 32);
-              const uint4 a = td[0], b = td[1];
-              const int oct = __float_as_int(kp.z);
-              const int iy = __float_as_int(kp.w) % kGridRows;
-              if (iy < nMinCellY || iy > nMaxCellY) continue;
-              if (checkLevels) {
-                if (oct < minLevel) continue;
-                if (maxLevel >= 0 && oct > maxLevel) continue;
-              }
-              const float dx = kp.x - x, dy = kp.y - y;
-              if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
-              if (idx >= N || s_claimed[idx]) continue;
-              const int d = __popc(a.x ^ w[0]) + __popc(a.y ^ w[1]) + __popc(a.z ^ w[2]) + __popc(a.w ^ w[3]) +
-                            __popc(b.x ^ w[4]) + __popc(b.y ^ w[5]) + __popc(b.z ^ w[6]) + __popc(b.w ^ w[7]);
-              const uint32_t key = ((uint32_t)d << 16) | ((uint32_t)p & 0xFFFFu);
-              if constexpr (kLocal) {
-                if (key < best) { best2 = best; best = key; }
-                else if (key < best2) best2 = key;
-              } else {
-                best = min(best, key);
-              }
-            }
-          }
-          if constexpr (kLocal) {     // the best two of two ascending pairs (disjoint): min(a1, b1), min(max(a1, b1), min(a2, b2))
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-              const uint32_t ob = (uint32_t)__shfl_xor((int)best, o), ob2 = (uint32_t)__shfl_xor((int)best2, o);
-              best2 = min(max(best, ob), min(best2, ob2));
-              best = min(best, ob);
-            }
-          } else {
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, o));
-          }
+          uint32_t w[8];
+          desc_load(RQ.qdesc, qf, w);
+          window_scan<64>(F, x, y, r, minLevel, maxLevel, lane, [&](int p, int, float, float) {
+            const int idx = F.sidx[p];
+            if (idx >= N || s_claimed[idx]) return;
+            const uint32_t key = ((uint32_t)desc_distance(w, F.sdesc, p) << 16) | (uint32_t)p;
+            if constexpr (kLocal) top2_insert(best, best2, key);
+            else best = min(best, key);
+          });
+          if constexpr (kLocal) wave_top2(best, best2);     // best two by (distance, scan position)
+          else best = wave_min(best);
           const int bd = (int)(best >> 16);
           const int bidx = bd < 256 ? F.sidx[best & 0xFFFFu] : -1;
           if (lane == first_und) { exhausted = false; pdist = bd; prop = bidx; n_requeried++; }
@@ -244,13 +207,8 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
       }
     }
     const int any_exhausted = __ballot(exhausted_any != 0) != 0ull;
-    int nrq = n_requeried;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) nrq += __shfl_xor(nrq, o);
-    if constexpr (kLocal) {
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) n_matched += __shfl_xor(n_matched, o);
-    }
+    const int nrq = wave_sum(n_requeried);
+    if constexpr (kLocal) n_matched = wave_sum(n_matched);
     if (lane == 0) { s_cnt[0] = any_exhausted; s_cnt[1] = nrq; s_cnt[2] = n_rounds; s_cnt[3] = n_matched; }
   }
   __syncthreads();
@@ -288,14 +246,12 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
     if (r == 0xFFFFFFFFu) continue;
     nmatched++;
     if (check_ori) {
-      const int bin = (int)(r >> 16);
-      if (bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) { ndropped++; s_assign[r & 0xFFFFu] = -1; }
+      if (rot_dropped((int)(r >> 16), s_ind)) { ndropped++; s_assign[r & 0xFFFFu] = -1; }
     }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) { nmatched += __shfl_xor(nmatched, o); ndropped += __shfl_xor(ndropped, o); }
   __shared__ int s_nm[4], s_nd[4];
-  if (lane == 0) { s_nm[wave] = nmatched; s_nd[wave] = ndropped; }
+  block_sum4_put(nmatched, s_nm);
+  block_sum4_put(ndropped, s_nd);
   __syncthreads();
   // (both copies: the device one feeds k_track_gather, the mapped one is what the host reads after the chain's one synchronisation)
   for (int j = tid; j < kp_cap; j += 256) {
@@ -304,7 +260,7 @@ __global__ void __launch_bounds__(256) k_track_claims(const uint32_t* __restrict
     if (j < N) assign_host[j] = a;
   }
   if (tid == 0) {
-    const int nm = s_nm[0] + s_nm[1] + s_nm[2] + s_nm[3], nd = s_nd[0] + s_nd[1] + s_nd[2] + s_nd[3];
+    const int nm = block_sum4(s_nm), nd = block_sum4(s_nd);
     res[0] = nm - nd; res[1] = s_cnt[0]; res[2] = nm; res[3] = s_cnt[1];
     res_host[0] = nm - nd; res_host[1] = s_cnt[0]; res_host[2] = nm; res_host[3] = s_cnt[1]; res_host[4] = s_cnt[2];
   }
@@ -640,8 +596,8 @@ __global__ void __launch_bounds__(1024) k_refkf_bow(RefKfArgs A, const int32_t* 
 // second.  A frame feature lies in exactly ONE node of the frame's FeatureVector, so what one node's matches take is never a candidate
 // of another node: the nodes are independent, and the reference's sequential walk is one sequential walk per node in any node order.
 // One wave per keyframe node: the node is found in the frame's list by binary search, the wave walks the node's keyframe features in
-// order and scans the frame features across its lanes (min of (distance << 20 | scan position); per lane the two smallest distances,
-// merged), so every decision sees exactly the claims the reference's walk has made by then.  The rotation histogram only counts, so its
+// order and scans the frame features across its lanes (bow_node_scan, match_device.h: min of (distance << 20 | scan position) and the
+// two smallest distances), so every decision sees exactly the claims the reference's walk has made by then.  The rotation histogram only counts, so its
 // global atomics may come in any order.  LDS: the claim flag of every frame keypoint (1 B each).
 // Known limit: a vocabulary with L - levelsup <= 0 puts every feature into node 0: one wave then walks the whole frame.
 // Each frame that runs has its own range of workgroups (A.wg_base), so a workgroup's claim flags -- indexed by the frame's keypoint --
@@ -669,43 +625,14 @@ __global__ void __launch_bounds__(256) k_refkf_search(RefKfArgs A, const dvm_key
   const int a = wg * 4 + (threadIdx.x >> 6);
   if (a >= kfv_n) return;
   const int N = min(*d_n, cap), n_fv = A.cnt[1];
-  const uint32_t node = (uint32_t)A.kfv_node[a];
-  int lo = 0, hi = n_fv;                  // the frame's nodes ascend as unsigned
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if ((uint32_t)A.fv_node[mid] < node) lo = mid + 1; else hi = mid;
-  }
-  if (lo >= n_fv || (uint32_t)A.fv_node[lo] != node) return;
-  const int fb = A.fv_off[lo], fe = A.fv_off[lo + 1];
+  const int at = fv_find<uint32_t>(A.fv_node, n_fv, A.kfv_node[a]);     // the frame's nodes ascend as unsigned
+  if (at < 0) return;                     // the frame does not have the node
+  const int fb = A.fv_off[at], fe = A.fv_off[at + 1];
   for (int k = A.kfv_off[a]; k < A.kfv_off[a + 1]; k++) {
     const int r = A.kfv_feat[k];          // (the host checked 0 <= r < n)
     if (!A.kuse[r]) continue;
-    uint32_t w[8];
-    {
-      const uint4* q = reinterpret_cast<const uint4*>(A.kdesc + (size_t)r * 32);
-      const uint4 q0 = q[0], q1 = q[1];
-      w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w; w[4] = q1.x; w[5] = q1.y; w[6] = q1.z; w[7] = q1.w;
-    }
-    uint32_t best = 0xFFFFFFFFu;
-    int d1 = 256, d2 = 256;
-    for (int p = fb + lane; p < fe; p += 64) {
-      const int j = A.fv_feat[p];
-      if (j >= N || s_claim[j]) continue;
-      const uint4* td = reinterpret_cast<const uint4*>(desc + (size_t)j * 32);
-      const uint4 x = td[0], y = td[1];
-      const int d = __popc(x.x ^ w[0]) + __popc(x.y ^ w[1]) + __popc(x.z ^ w[2]) + __popc(x.w ^ w[3]) + __popc(y.x ^ w[4]) + __popc(y.y ^ w[5]) +
-                    __popc(y.z ^ w[6]) + __popc(y.w ^ w[7]);
-      best = min(best, ((uint32_t)d << 20) | (uint32_t)(p - fb));
-      if (d < d1) { d2 = d1; d1 = d; }
-      else if (d < d2) d2 = d;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {     // the two smallest of two ascending pairs: min(a1, b1), min(max(a1, b1), min(a2, b2))
-      best = min(best, (uint32_t)__shfl_xor((int)best, o));
-      const int od1 = __shfl_xor(d1, o), od2 = __shfl_xor(d2, o);
-      d2 = min(max(d1, od1), min(d2, od2));
-      d1 = min(d1, od1);
-    }
+    int d2;
+    const uint32_t best = bow_node_scan(A.kdesc, r, A.fv_feat, fb, fe, desc, lane, [&](int, int j) { return j >= N || s_claim[j]; }, d2);
     const int bd = (int)(best >> 20);
     if (bd <= th_low && (float)bd < nnratio * (float)d2) {
       const int j = A.fv_feat[fb + (int)(best & 0xFFFFFu)];
@@ -727,7 +654,7 @@ __global__ void __launch_bounds__(256) k_refkf_settle(RefKfArgs A, const int32_t
   __shared__ int s_rot[kHisto];
   __shared__ int s_ind[3];
   __shared__ int s_nd[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int N = min(*d_n, cap);
   if (tid < kHisto) s_rot[tid] = A.cnt[8 + tid];
   __syncthreads();
@@ -737,17 +664,14 @@ __global__ void __launch_bounds__(256) k_refkf_settle(RefKfArgs A, const int32_t
   for (int j = tid; j < cap; j += 256) {
     int m = j < N ? A.match[j] : -1;
     if (m >= 0 && check_ori) {
-      const int bin = A.bin[j];
-      if (bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) { m = -1; nd++; A.match[j] = -1; }
+      if (rot_dropped(A.bin[j], s_ind)) { m = -1; nd++; A.match[j] = -1; }
     }
     if (j < N) A.h_match[j] = m;
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) nd += __shfl_xor(nd, o);
-  if (lane == 0) s_nd[wave] = nd;
+  block_sum4_put(nd, s_nd);
   __syncthreads();
   if (tid == 0) {
-    const int nm = A.cnt[2], nmatches = nm - (s_nd[0] + s_nd[1] + s_nd[2] + s_nd[3]);
+    const int nm = A.cnt[2], nmatches = nm - block_sum4(s_nd);
     A.res[0] = nmatches; A.res[1] = 0;
     A.h_cnt[0] = A.cnt[0]; A.h_cnt[1] = A.cnt[1]; A.h_cnt[2] = nm; A.h_cnt[3] = nmatches;
   }

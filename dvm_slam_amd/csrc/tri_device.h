@@ -4,11 +4,13 @@
 //   TriQuery / tri_candidate   ORBmatcher::SearchForTriangulation's per-candidate test (reference src/ORBmatcher.cc:905-960, monocular)
 //   tri_pair_geometry<MODEL>   the per-match body of CreateNewMapPoints (src/LocalMapping.cc:598-741, GeometricTools.cc:48-67)
 //   tri_rows_kb8               the same test for a workgroup of 16 queries on a KannalaBrandt8 pair (CameraModels/KannalaBrandt8.cpp:216-220, :304-374)
-// The arithmetic that depends on the camera lives in tri_model.h, which also compiles for the host.
+// The arithmetic that depends on the camera lives in tri_model.h, which also compiles for the host; the descriptor distance and the row
+// minimum are match_device.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "match_device.h"
 #include "match_kernels.h"
 #include "pose_f32.h"
 #include "tri_model.h"
@@ -22,9 +24,7 @@ struct TriQuery {
 };
 __device__ __forceinline__ TriQuery tri_query(const uint8_t* __restrict__ desc1, const dvm_keypoint_pod* __restrict__ kps1, int idx1, const float* F12) {
   TriQuery Q;
-  const uint32_t* qd = reinterpret_cast<const uint32_t*>(desc1 + (size_t)idx1 * 32);
-#pragma unroll
-  for (int i = 0; i < 8; i++) Q.w[i] = qd[i];
+  desc_load(desc1, idx1, Q.w);
   const float x1 = kps1[idx1].x, y1 = kps1[idx1].y;
   Q.a = __fadd_rn(__fadd_rn(__fmul_rn(x1, F12[0]), __fmul_rn(y1, F12[3])), F12[6]);
   Q.b = __fadd_rn(__fadd_rn(__fmul_rn(x1, F12[1]), __fmul_rn(y1, F12[4])), F12[7]);
@@ -36,10 +36,7 @@ __device__ __forceinline__ TriQuery tri_query(const uint8_t* __restrict__ desc1,
 // Pinhole::epipolarConstrain (CameraModels/Pinhole.cpp:104-127); -1 otherwise.  Reads the tables at kps2[idx2].octave.
 __device__ __forceinline__ int tri_candidate(const TriQuery& Q, const uint8_t* __restrict__ desc2, const dvm_keypoint_pod* __restrict__ kps2, int idx2,
                                              const TriGeom& G, const float* __restrict__ scale_factors2, const float* __restrict__ level_sigma2_2) {
-  const uint4* td = reinterpret_cast<const uint4*>(desc2 + (size_t)idx2 * 32);
-  const uint4 A = td[0], B = td[1];
-  const int d = __popc(A.x ^ Q.w[0]) + __popc(A.y ^ Q.w[1]) + __popc(A.z ^ Q.w[2]) + __popc(A.w ^ Q.w[3]) +
-                __popc(B.x ^ Q.w[4]) + __popc(B.y ^ Q.w[5]) + __popc(B.z ^ Q.w[6]) + __popc(B.w ^ Q.w[7]);
+  const int d = desc_distance(Q.w, desc2, idx2);
   if (d > G.th_low) return -1;
   const dvm_keypoint_pod kp2 = kps2[idx2];
   const float distex = __fsub_rn(G.ep[0], kp2.x), distey = __fsub_rn(G.ep[1], kp2.y);
@@ -55,14 +52,6 @@ __device__ __forceinline__ int tri_candidate(const TriQuery& Q, const uint8_t* _
 // the sequential rule "dist > bestDist -> continue" = minimum distance, LAST position wins a tie = min over this key
 __device__ __forceinline__ uint32_t tri_key(int d, int pos) { return ((uint32_t)d << 16) | (uint32_t)(0xFFFF - pos); }
 __device__ __forceinline__ int tri_key_pos(uint32_t k) { return 0xFFFF - (int)(k & 0xFFFFu); }
-// min over the 16 lanes of a DPP row
-__device__ __forceinline__ uint32_t tri_row_min(uint32_t k) {
-  k = min(k, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k, 0xB1, 0xF, 0xF, false));
-  k = min(k, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k, 0x4E, 0xF, 0xF, false));
-  k = min(k, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k, 0x141, 0xF, 0xF, false));
-  k = min(k, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)k, 0x140, 0xF, 0xF, false));
-  return k;
-}
 
 // ---- the same search on a KannalaBrandt8 pair (model 1 of camera_model.h): KannalaBrandt8::epipolarConstrain in place of the line test.
 // The search on such a pair costs a double Jacobi per candidate that passes the two cheap tests, and few candidates do: left where the
@@ -120,17 +109,12 @@ __device__ __forceinline__ uint32_t tri_rows_kb8(TriBlockKB8& S, bool active, co
   uint32_t key = 0xFFFFFFFFu;
   if (active && end > beg) {
     uint32_t w[8];
-    const uint32_t* qd = reinterpret_cast<const uint32_t*>(desc1 + (size_t)idx1 * 32);
-#pragma unroll
-    for (int i = 0; i < 8; i++) w[i] = qd[i];
+    desc_load(desc1, idx1, w);
     if (lane == 0 && !G.coarse) S.q[row] = tri_row_query(kps1[idx1], G.cam1, level_sigma2_1, n_levels);
     for (int p = beg + lane; p < end; p += 16) {
       const int idx2 = cand_at(p);
       if (idx2 < 0) continue;
-      const uint4* td = reinterpret_cast<const uint4*>(desc2 + (size_t)idx2 * 32);
-      const uint4 A = td[0], B = td[1];
-      const int d = __popc(A.x ^ w[0]) + __popc(A.y ^ w[1]) + __popc(A.z ^ w[2]) + __popc(A.w ^ w[3]) +
-                    __popc(B.x ^ w[4]) + __popc(B.y ^ w[5]) + __popc(B.z ^ w[6]) + __popc(B.w ^ w[7]);
+      const int d = desc_distance(w, desc2, idx2);
       if (d > G.th_low) continue;
       const dvm_keypoint_pod kp2 = kps2[idx2];
       if ((unsigned)kp2.octave >= (unsigned)n_levels) continue;   // outside the tables: no candidate, nothing read
@@ -154,7 +138,7 @@ __device__ __forceinline__ uint32_t tri_rows_kb8(TriBlockKB8& S, bool active, co
     if (tri_constrain(S.q[r], kps2[idx2], G, level_sigma2_2)) atomicMin(&S.key[r], S.skey[t]);
   }
   __syncthreads();
-  return min(tri_row_min(key), S.key[row]);
+  return min(row_min(key), S.key[row]);
 }
 
 // One match (kp1, kp2) of one neighbour under camera model MODEL (dvm_tri::pair_geometry, tri_model.h): the octave check, the two rays,
