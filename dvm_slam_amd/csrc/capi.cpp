@@ -166,10 +166,11 @@ int dvm_orb_copy_result(dvm_orb* h, int frame, dvm_keypoint* d_kps_dst, uint8_t*
   if (!h || !h->p->configured || frame < 0 || frame >= h->p->max_batch || !d_kps_dst || !d_desc_dst || !d_n_dst) return DVM_ERR_STATE;
   OrbPipeline& P = *h->p;
   const size_t cap = (size_t)P.PD.kp_cap;
-  int rc = hip_check(hipMemcpyAsync(d_kps_dst, P.d_kps + (size_t)frame * cap, cap * sizeof(dvm_keypoint), hipMemcpyDeviceToDevice, P.stream), "copy kps");
-  if (rc == DVM_OK) rc = hip_check(hipMemcpyAsync(d_desc_dst, P.d_desc + (size_t)frame * cap * 32, cap * 32, hipMemcpyDeviceToDevice, P.stream), "copy desc");
-  if (rc == DVM_OK) rc = hip_check(hipMemcpyAsync(d_n_dst, P.d_n + frame, 4, hipMemcpyDeviceToDevice, P.stream), "copy n");
-  return rc;
+  int rc = hip_check(hipSetDevice(P.device), "hipSetDevice");
+  if (rc != DVM_OK) return rc;
+  launch_copy_result(P.stream, P.d_kps + (size_t)frame * cap, reinterpret_cast<dvm_keypoint_pod*>(d_kps_dst), P.d_desc + (size_t)frame * cap * 32, d_desc_dst,
+                     (int)cap, P.d_n + frame, d_n_dst);
+  return hip_check(hipGetLastError(), "copy_result launch");
 }
 const float* dvm_orb_scale_factors_device(dvm_orb* h) { return h ? h->d_scale : nullptr; }
 int dvm_orb_download(dvm_orb* h, int frame, dvm_keypoint* kps, uint8_t* desc, int cap, int* n, int* mono_index) {
@@ -336,12 +337,12 @@ int dvm_frame_create(int device, int capacity, int slots, dvm_frame** out) {
   rc = hip_check(hipMalloc(&V.skp, S * capacity * sizeof(float4)), "hipMalloc");
   if (rc == DVM_OK) rc = hip_check(hipMalloc(&V.sidx, S * capacity * 4), "hipMalloc");
   if (rc == DVM_OK) rc = hip_check(hipMalloc(&V.sdesc, S * capacity * 32), "hipMalloc");
-  if (rc == DVM_OK) rc = hip_check(hipMalloc(&V.cellx_start, S * 80 * 4), "hipMalloc");
+  if (rc == DVM_OK) rc = hip_check(hipMalloc(&V.cell_start, S * kCellStartStride * 4), "hipMalloc");
   if (rc == DVM_OK) rc = hip_check(hipMalloc(&V.n_sorted, S * 4), "hipMalloc");
   if (rc == DVM_OK) rc = hip_check(hipMalloc(&V.n_total, S * 4), "hipMalloc");
   if (rc == DVM_OK) rc = hip_check(hipMalloc(&V.n_overflow, 4), "hipMalloc");
   if (rc == DVM_OK) rc = hip_check(hipMemset(V.n_overflow, 0, 4), "memset");
-  if (rc == DVM_OK) rc = hip_check(hipMemset(V.cellx_start, 0, S * 80 * 4), "memset");
+  if (rc == DVM_OK) rc = hip_check(hipMemset(V.cell_start, 0, S * kCellStartStride * 4), "memset");
   if (rc == DVM_OK) rc = hip_check(hipMemset(V.n_sorted, 0, S * 4), "memset");
   if (rc == DVM_OK) rc = hip_check(hipMemset(V.n_total, 0, S * 4), "memset");
   if (rc != DVM_OK) {
@@ -357,7 +358,7 @@ void dvm_frame_destroy(dvm_frame* f) {
   if (V.skp) hipFree(V.skp);
   if (V.sidx) hipFree(V.sidx);
   if (V.sdesc) hipFree(V.sdesc);
-  if (V.cellx_start) hipFree(V.cellx_start);
+  if (V.cell_start) hipFree(V.cell_start);
   if (V.n_sorted) hipFree(V.n_sorted);
   if (V.n_total) hipFree(V.n_total);
   if (V.n_overflow) hipFree(V.n_overflow);

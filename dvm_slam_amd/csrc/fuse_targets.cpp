@@ -30,8 +30,8 @@ constexpr int kMaxTargets = 65535;              // gridDim.y
 constexpr int64_t kMaxEntries = (int64_t)1 << 27;   // target x point entries of one run
 // upload bytes of a target of n keypoints at most: keypoints, descriptors; two level tables of 64 and the rounding of its four arrays
 constexpr size_t kUpPerKeypoint = sizeof(dvm_keypoint_pod) + 32, kUpFixed = 2 * 64 * 4 + 4 * 64;
-// grid bytes: sorted keypoint, index, descriptor; cellx_start[80], the three counters and the rounding of its five arrays
-constexpr size_t kGridPerKeypoint = sizeof(float4) + 4 + 32, kGridFixed = 80 * 4 + 5 * 64;
+// grid bytes: sorted keypoint, index, descriptor; cell_start[kCellStartStride], the three counters and the rounding of its five arrays
+constexpr size_t kGridPerKeypoint = sizeof(float4) + 4 + 32, kGridFixed = (size_t)kCellStartStride * 4 + 5 * 64;
 constexpr size_t kPointBytes = 12 + 12 + 4 + 4 + 32 + 1;
 
 int fail(const char* fn, int rc, const std::string& msg) { set_error(std::string(fn) + ": " + msg); return rc; }
@@ -121,7 +121,7 @@ int dvm_fuse_targets_set(dvm_fuse_targets* h, int n_targets, const dvm_ft_target
     F.skp = grid.carve<float4>(n);
     F.sidx = grid.carve<int32_t>(n);
     F.sdesc = grid.carve<uint8_t>(n * 32);
-    F.cellx_start = grid.carve<int32_t>(80);
+    F.cell_start = grid.carve<int32_t>(kCellStartStride);
     F.n_sorted = grid.carve<int32_t>(2);
     F.n_total = F.n_sorted + 1;
     F.n_overflow = n_overflow;

@@ -38,9 +38,43 @@ __device__ __forceinline__ void top2_insert(T& k1, T& k2, T k) {
   k1 = min(k1, k);
 }
 
-// ---- GetFeaturesInArea(x, y, r, minLevel, maxLevel) of frame F: the cell rectangle with the reference's early-outs, then the sorted
-// positions of its grid columns across LANES lanes (16: one DPP row per query; 64: the whole wave); visit(p, oct, dx, dy) for every
-// position p that passes the row, level and radius tests (oct = its octave, dx / dy = its offset from the window's centre).
+// ---- sums across the lanes that share a window (window_scan).  lanes_prefix: the inclusive prefix sum of v over a DPP row (LANES = 16:
+// four row_shr steps, a lane without a source adds 0) or over the wave (LANES = 64: the row prefixes plus the totals of the rows in front,
+// read with v_readlane -- the caller is in wave-uniform control flow with all 64 lanes active); lanes_total: the last lane's prefix in
+// every lane.
+#define DVM_ROW_SHR(v, N) __builtin_amdgcn_update_dpp(0, v, 0x110 + N, 0xF, 0xF, false)
+template <int LANES>
+__device__ __forceinline__ int lanes_prefix(int v, int lane) {
+  static_assert(LANES == 16 || LANES == 64, "a DPP row or the wave");
+  v += DVM_ROW_SHR(v, 1);
+  v += DVM_ROW_SHR(v, 2);
+  v += DVM_ROW_SHR(v, 4);
+  v += DVM_ROW_SHR(v, 8);
+  if constexpr (LANES == 64) {
+    const int t0 = __builtin_amdgcn_readlane(v, 15), t1 = __builtin_amdgcn_readlane(v, 31), t2 = __builtin_amdgcn_readlane(v, 47);
+    v += (lane >= 16 ? t0 : 0) + (lane >= 32 ? t1 : 0) + (lane >= 48 ? t2 : 0);
+  }
+  return v;
+}
+#undef DVM_ROW_SHR
+template <int LANES>
+__device__ __forceinline__ int lanes_total(int incl) {
+  if constexpr (LANES == 64) return __builtin_amdgcn_readlane(incl, 63);
+  else return __builtin_amdgcn_update_dpp(0, incl, 0x15F, 0xF, 0xF, false);   // row_newbcast:15
+}
+
+// ---- GetFeaturesInArea(x, y, r, minLevel, maxLevel) of frame F: the cell rectangle with the reference's early-outs, then the keypoints
+// of the rectangle's cells alone across LANES lanes (16: one DPP row per query; 64: the whole wave); visit(p, oct, dx, dy) for every
+// sorted position p that passes the level and radius tests (oct = its octave, dx / dy = its offset from the window's centre), in no
+// particular order: the callers take minima of keys.
+// Rows nMinCellY .. nMaxCellY of grid column c are one span of sorted positions, cell_start[c * 48 + nMinCellY] .. cell_start[c * 48 +
+// nMaxCellY + 1).  The columns go LANES at a time: a lane owns one column's span, a prefix sum over the span lengths gives every span its
+// place in one flat range, and each owner writes its span's positions (uint16: < kFrameCap) to the window's LDS queue at that place.  The
+// lanes then walk the queue side by side, so a round of the loop tests LANES keypoints of the rectangle whatever the columns hold.  The
+// queue holds kWindowQueue * LANES positions and is filled again, pass by pass, where a group of columns holds more.  It is the window's
+// own (128 B per DPP row, 512 B per wave, workgroups of at most 256 threads) and one wave's LDS operations execute in order: between the
+// writes and the reads the compiler only has to keep that order (a wavefront-scope fence).
+constexpr int kWindowQueue = 4;
 template <int LANES, class Visit>
 __device__ __forceinline__ void window_scan(const FrameView& F, float x, float y, float r, int minLevel, int maxLevel, int lane, Visit visit) {
   const int nMinCellX = max(0, (int)floorf((x - F.minX - r) * F.wInv));
@@ -48,21 +82,42 @@ __device__ __forceinline__ void window_scan(const FrameView& F, float x, float y
   const int nMinCellY = max(0, (int)floorf((y - F.minY - r) * F.hInv));
   const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - F.minY + r) * F.hInv));
   const bool empty = nMinCellX >= kGridCols || nMaxCellX < 0 || nMinCellY >= kGridRows || nMaxCellY < 0;
-  if (empty || nMinCellX > nMaxCellX) return;
+  if (empty || nMinCellX > nMaxCellX || nMinCellY > nMaxCellY) return;
   const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
-  const int beg = F.cellx_start[nMinCellX], end = F.cellx_start[nMaxCellX + 1];
-  for (int p = beg + lane; p < end; p += LANES) {
-    const float4 kp = F.skp[p];
-    const int oct = __float_as_int(kp.z);
-    const int iy = __float_as_int(kp.w) % kGridRows;
-    if (iy < nMinCellY || iy > nMaxCellY) continue;
-    if (checkLevels) {
-      if (oct < minLevel) continue;
-      if (maxLevel >= 0 && oct > maxLevel) continue;
+  constexpr int kQueue = kWindowQueue * LANES;
+  __shared__ uint16_t s_queue[(256 / LANES) * kQueue];
+  uint16_t* queue = s_queue + (threadIdx.x / LANES) * kQueue;
+  for (int g = nMinCellX; g <= nMaxCellX; g += LANES) {
+    const int c = g + lane;
+    int beg = 0, len = 0;
+    if (c <= nMaxCellX) {
+      beg = F.cell_start[c * kGridRows + nMinCellY];
+      len = F.cell_start[c * kGridRows + nMaxCellY + 1] - beg;
     }
-    const float dx = kp.x - x, dy = kp.y - y;
-    if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
-    visit(p, oct, dx, dy);
+    const int incl = lanes_prefix<LANES>(len, lane), excl = incl - len;
+    const int total = lanes_total<LANES>(incl);
+    for (int base = 0; base < total; base += kQueue) {
+      const int hi = min(incl, base + kQueue);
+#pragma clang loop vectorize(disable) unroll(disable)
+      for (int f = max(excl, base); f < hi; f++) queue[f - base] = (uint16_t)(beg + (f - excl));
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      const int n = min(total - base, kQueue);
+      for (int j = lane; j < n; j += LANES) {
+        const int p = queue[j];
+        const float4 kp = F.skp[p];
+        const int oct = __float_as_int(kp.z);
+        if (checkLevels) {
+          if (oct < minLevel) continue;
+          if (maxLevel >= 0 && oct > maxLevel) continue;
+        }
+        const float dx = kp.x - x, dy = kp.y - y;
+        if (!(fabsf(dx) < r && fabsf(dy) < r)) continue;
+        visit(p, oct, dx, dy);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
   }
 }
 

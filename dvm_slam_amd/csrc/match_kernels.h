@@ -20,12 +20,14 @@ struct dvm_match_pod {  // == dvm_match
 
 // Device view of a set of frame slots, each `cap` keypoints, sorted in GetFeaturesInArea order.
 constexpr int kGridCols = 64, kGridRows = 48;  // Frame.h:44-45 (FRAME_GRID_COLS / FRAME_GRID_ROWS)
+constexpr int kGridCells = kGridCols * kGridRows;
+constexpr int kCellStartStride = kGridCells + 4;   // int32 entries of cell_start per slot: kGridCells + 1, rounded to 16 bytes
 
 struct FrameView {
   float4* skp;           // (x, y, octave bits, cell bits) per sorted position
   int32_t* sidx;         // original keypoint index
   uint8_t* sdesc;        // 32 B descriptors, sorted
-  int32_t* cellx_start;  // [65] first sorted position with grid column >= c
+  int32_t* cell_start;   // [kGridCells + 1] first sorted position whose cell ix * kGridRows + iy is >= c; the last entry is n_sorted
   int32_t* n_sorted;     // keypoints inside the grid
   int32_t* n_total;      // keypoints given
   int32_t* n_overflow;   // one per handle: device-side counts (d_n) that exceeded cap and were clamped (sticky; dvm_frame_overflows)
@@ -36,7 +38,7 @@ struct FrameView {
     v.skp += (int64_t)s * cap;
     v.sidx += (int64_t)s * cap;
     v.sdesc += (int64_t)s * cap * 32;
-    v.cellx_start += (int64_t)s * 80;
+    v.cell_start += (int64_t)s * kCellStartStride;
     v.n_sorted += s;
     v.n_total += s;
     return v;

@@ -40,9 +40,9 @@ __global__ void __launch_bounds__(1024) k_frame_build(const dvm_keypoint_pod* __
 }
 
 
-// Sixteen lanes (one DPP row) per query, four queries per wave: a window holds ~10 candidates out of the ~70 of its
-// grid columns, so a full wave per query left most lanes idle and paid a 6-step cross-lane reduction; a row reduces
-// its top-2 with four DPP steps and no LDS traffic.  QUERIES_FROM_KPS: queries are keypoints of another frame (frame-to-frame
+// Sixteen lanes (one DPP row) per query, four queries per wave: a window's cell rectangle holds ~25 keypoints (window_scan walks those
+// alone), so a full wave per query left most lanes idle and paid a 6-step cross-lane reduction; a row reduces its top-2 with four DPP
+// steps.  QUERIES_FROM_KPS: queries are keypoints of another frame (frame-to-frame
 // search, window th*scale[octave], octaves [o-1,o+1]); otherwise explicit query arrays.
 template <bool QUERIES_FROM_KPS>
 __global__ void __launch_bounds__(256) k_match_window(FrameView FB, int first_slot, const uint8_t* __restrict__ skip,

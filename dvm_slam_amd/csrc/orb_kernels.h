@@ -53,5 +53,8 @@ void launch_orient_desc(hipStream_t s, const uint8_t* d_pyr, const uint8_t* d_bl
 // IC_Angle + GaussianBlur of the keypoint's own 43 x 43 raw patch + descriptor: no blurred pyramid (batches on the throughput path)
 void launch_orient_desc_blur(hipStream_t s, const uint8_t* d_pyr, const PipelineDesc& PD, const KpAux* d_aux, const int32_t* d_n,
                              dvm_keypoint_pod* d_kps, uint8_t* d_desc, int batch, HostMirror hm = HostMirror());
+// one frame's result (all cap keypoint and descriptor rows, and the count) to the caller's device arrays in one launch
+void launch_copy_result(hipStream_t s, const dvm_keypoint_pod* kps_src, dvm_keypoint_pod* kps_dst, const uint8_t* desc_src, uint8_t* desc_dst, int cap,
+                        const int32_t* n_src, int32_t* n_dst);
 
 }  // namespace dvm

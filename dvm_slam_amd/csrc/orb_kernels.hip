@@ -1644,4 +1644,31 @@ void launch_orient_desc_blur(hipStream_t s, const uint8_t* d_pyr, const Pipeline
                      d_aux, d_n, d_kps, d_desc, batch, hm);
 }
 
+// dvm_orb_copy_result: a frame's keypoint rows, descriptor rows (all of them: a reader may rely on every row being written) and count to
+// the caller's arrays, one launch.  W = the widest word the four addresses and the two sizes allow.
+template <class W>
+__global__ void __launch_bounds__(256) k_copy_result(const W* __restrict__ kps_src, W* __restrict__ kps_dst, uint32_t n_kps,
+                                                     const W* __restrict__ desc_src, W* __restrict__ desc_dst, uint32_t n_desc,
+                                                     const int32_t* __restrict__ n_src, int32_t* __restrict__ n_dst) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_kps) kps_dst[i] = kps_src[i];
+  else if (i - n_kps < n_desc) desc_dst[i - n_kps] = desc_src[i - n_kps];
+  if (i == 0) *n_dst = *n_src;
+}
+template <class W>
+static void copy_result_as(hipStream_t s, const void* kps_src, void* kps_dst, size_t kps_bytes, const void* desc_src, void* desc_dst,
+                           size_t desc_bytes, const int32_t* n_src, int32_t* n_dst) {
+  const uint32_t nk = (uint32_t)(kps_bytes / sizeof(W)), nd = (uint32_t)(desc_bytes / sizeof(W));
+  hipLaunchKernelGGL(k_copy_result<W>, dim3(max(1, cdiv((int)(nk + nd), 256))), dim3(256), 0, s, static_cast<const W*>(kps_src), static_cast<W*>(kps_dst), nk,
+                     static_cast<const W*>(desc_src), static_cast<W*>(desc_dst), nd, n_src, n_dst);
+}
+void launch_copy_result(hipStream_t s, const dvm_keypoint_pod* kps_src, dvm_keypoint_pod* kps_dst, const uint8_t* desc_src, uint8_t* desc_dst, int cap,
+                        const int32_t* n_src, int32_t* n_dst) {
+  const size_t kb = (size_t)cap * sizeof(dvm_keypoint_pod), db = (size_t)cap * 32;
+  const uintptr_t a = (uintptr_t)kps_src | (uintptr_t)kps_dst | (uintptr_t)desc_src | (uintptr_t)desc_dst | kb | db;
+  if (a % 16 == 0) copy_result_as<uint4>(s, kps_src, kps_dst, kb, desc_src, desc_dst, db, n_src, n_dst);
+  else if (a % 4 == 0) copy_result_as<uint32_t>(s, kps_src, kps_dst, kb, desc_src, desc_dst, db, n_src, n_dst);
+  else copy_result_as<uint8_t>(s, kps_src, kps_dst, kb, desc_src, desc_dst, db, n_src, n_dst);
+}
+
 }  // namespace dvm

@@ -72,14 +72,22 @@ __device__ __forceinline__ void frame_build_block(const dvm_keypoint_pod* __rest
   }
   __syncthreads();
   const int m = s_m;
-  if (tid <= kGridCols) {  // cellx_start[c] = first sorted position whose column >= c
-    uint32_t want = (uint32_t)(tid * kGridRows) << 13;
-    int lo = 0, hi = m;
-    while (lo < hi) {
-      int mid = (lo + hi) >> 1;
-      if (keys[mid] < want) lo = mid + 1; else hi = mid;
+  {  // cell_start[c] = first sorted position whose cell >= c = the number of keys below c << 13, for all kGridCells + 1 entries on every
+     // build (nothing of an earlier build stays).  Three cells per thread, their lower bounds side by side in steps of falling powers of
+     // two over keys[0 .. P): an invalid key is above every cell's, so the search needs no m.
+    const uint32_t w0 = (uint32_t)tid << 13, w1 = (uint32_t)(tid + 1024) << 13, w2 = (uint32_t)(tid + 2048) << 13;
+    int l0 = 0, l1 = 0, l2 = 0;
+    for (int s = P; s > 0; s >>= 1) {
+      const bool in0 = l0 + s <= P, in1 = l1 + s <= P, in2 = l2 + s <= P;
+      const uint32_t k0 = keys[in0 ? l0 + s - 1 : 0], k1 = keys[in1 ? l1 + s - 1 : 0], k2 = keys[in2 ? l2 + s - 1 : 0];
+      if (in0 && k0 < w0) l0 += s;
+      if (in1 && k1 < w1) l1 += s;
+      if (in2 && k2 < w2) l2 += s;
     }
-    F.cellx_start[tid] = lo;
+    F.cell_start[tid] = l0;
+    F.cell_start[tid + 1024] = l1;
+    F.cell_start[tid + 2048] = l2;
+    if (tid == 0) F.cell_start[kGridCells] = m;
   }
   for (int p = tid; p < m; p += 1024) {
     const uint32_t key = keys[p];
