@@ -318,6 +318,14 @@ class OrbExtractor:
         check(self.L.dvm_orb_debug_level(self.h, frame, level, int(bordered), _p(out)))
         return out
 
+    def debug_pyr_path(self, level) -> int:
+        """1 if the last batch built this level with k_pyr_resize_direct, 0 for k_pyr_resize (dvm_orb_debug_pyr_path)."""
+        out = C.c_int(0)
+        f = self.L.dvm_orb_debug_pyr_path
+        f.restype = C.c_int32; f.argtypes = None
+        check(f(self.h, C.c_int32(level), C.byref(out)))
+        return out.value
+
     def debug_blurred(self, frame, level):
         _, r, c, _ = self.pyramid(frame, level)
         out = np.zeros((r, c), np.uint8)

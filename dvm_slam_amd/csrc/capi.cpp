@@ -205,6 +205,13 @@ int dvm_orb_debug_level(dvm_orb* h, int frame, int level, int bordered, uint8_t*
     return hip_check(hipMemcpy2D(out, L.w + 2 * kEdge, base, L.stride, L.w + 2 * kEdge, L.h + 2 * kEdge, hipMemcpyDeviceToHost), "memcpy2d");
   return hip_check(hipMemcpy2D(out, L.w, base + (size_t)kEdge * L.stride + kEdge, L.stride, L.w, L.h, hipMemcpyDeviceToHost), "memcpy2d");
 }
+int dvm_orb_debug_pyr_path(dvm_orb* h, int level, int* out) {
+  if (!h || !h->p->configured || !out) return DVM_ERR_STATE;
+  OrbPipeline& P = *h->p;
+  if (level < 0 || level >= P.PD.nlevels) return DVM_ERR_INVALID;
+  *out = P.pyr_path[level];
+  return DVM_OK;
+}
 int dvm_orb_debug_blurred(dvm_orb* h, int frame, int level, uint8_t* out) {
   if (!h || !h->p->configured || !out) return DVM_ERR_STATE;
   OrbPipeline& P = *h->p;

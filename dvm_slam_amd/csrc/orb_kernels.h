@@ -26,6 +26,10 @@ void upload_constants(const int8_t* disc_u, const int8_t* disc_v, const int* gau
 void launch_pyr_level0(hipStream_t s, const uint8_t* d_src, int rows, int cols, int sstride, int64_t frame_stride,
                        uint8_t* d_pyr, const PipelineDesc& PD, int batch);
 void launch_pyr_resize(hipStream_t s, uint8_t* d_pyr, const PipelineDesc& PD, int level, const int32_t* d_tabs, int batch);
+constexpr int kRzLatencyBatch = 8;   // batches up to this size build the pyramid with short tiles (k_pyr_resize<16>)
+// k_pyr_resize_direct (batches above kRzLatencyBatch): the strip height for a level from its resize tables, 0 = the level keeps k_pyr_resize
+int pyr_direct_strip_rows(const LevelDesc& P, const LevelDesc& L, const int32_t* xofs, const int32_t* yofs);
+void launch_pyr_resize_direct(hipStream_t s, uint8_t* d_pyr, const PipelineDesc& PD, int level, const int32_t* d_tabs, int batch, int strip_rows);
 void launch_pyr_borders(hipStream_t s, uint8_t* d_pyr, const PipelineDesc& PD, int batch);
 void launch_fast(hipStream_t s, const uint8_t* d_pyr, const CellDesc* d_cells, const PipelineDesc& PD, uint32_t* d_cand,
                  int32_t* d_cell_count, int batch, int max_rw, int max_rh, int cell_first, int cell_num, const CellDesc* h_cells);

@@ -285,6 +285,116 @@ __global__ void __launch_bounds__(256) k_pyr_resize(uint8_t* __restrict__ pyr, i
   pyr_resize_tile<TH>(pyr, pyr_frame_bytes, P, L, tabs, lds_pitch, blockIdx.z, blockIdx.x, blockIdx.y);
 }
 
+// level l = cv::resize(level l-1, INTER_LINEAR) WITH its REFLECT_101 frame, straight from global memory: no LDS tile, no barrier, one
+// global round trip for the tables and one for the pixels.  The throughput path's form of k_pyr_resize for the levels pyr_direct_strip_rows() accepts; it writes
+// the same bytes (interior, frame columns, strip rows stored twice, pad bytes of the last group).
+//   lane  = the four destination bytes at bordered column X4 of a STRIP of R consecutive interior rows; a wave = 64 consecutive
+//           groups of one strip, so rows are wave-uniform: row tables, vertical weights and the emit test are scalar.  The four
+//           waves of a workgroup take four consecutive strips.
+//   cols  : the sources sx[k], sx[k]+1 of the four pixels lie in a window of at most 8 bytes from base = min sx[k] (checked on the
+//           host for every group, mirrored and pad columns included), so ONE unaligned 8-byte load per source row holds them all
+//           (unaligned global loads are free on gfx950, NOTEBOOK 3); four v_perm selectors put bytes sx[k]-base, sx[k]+1-base
+//           into the halves of a dword for v_dot2_u32_u16 against the 11-bit weights -- the operands k_pyr_resize forms from LDS.
+//   rows  : the strip's source rows sya..syb (at most NS, by the host's choice of R) are all loaded before the first wait.  They are
+//           walked in a statically unrolled loop (register indices stay static: no scratch): row j's four horizontal values are
+//           formed once, row j-1's are kept, and the destination row whose second tap is row j is emitted.  yofs is strictly
+//           increasing, so a source row emits at most one destination row.  No tap is clamped: a level where sy < 0 or
+//           sy + 1 > P.h - 1 occurs (a level as large as its parent) is not accepted and keeps k_pyr_resize.
+//   vert  : (b * (h >> 4)) >> 16 as ONE v_mul_hi_u32_u24 of (b << 12) and (h & ~15): (b * 2^12 * (h >> 4) * 2^4) >> 32 is the same
+//           number, both factors fit 24 bits (b <= 2048, h <= 255 * 2048); tests/test_pyr_direct_model.py checks it for every pair.
+// The strip's row tables ride in a vector register (lane i = row y0 + i) and are read back with v_readlane: no scalar load, hence
+// no s_waitcnt lgkmcnt, inside the walk.  Lanes past the row end compute the last group again and store nothing.
+#ifndef DVM_PYR_NS
+#define DVM_PYR_NS 24   // (make EXTRA=-DDVM_PYR_NS=n: measurement builds)
+#endif
+#ifndef DVM_PYR_WAVES
+#define DVM_PYR_WAVES 4
+#endif
+constexpr int kRdNS = DVM_PYR_NS;   // source rows of a strip = 8-byte loads in flight per lane
+constexpr int kRdWaves = DVM_PYR_WAVES;   // strips (waves) per workgroup
+__device__ __forceinline__ uint32_t mul_hi_u24(uint32_t a, uint32_t b) {   // both < 2^24
+  return (uint32_t)(((uint64_t)(a & 0xFFFFFFu) * (uint64_t)(b & 0xFFFFFFu)) >> 32);
+}
+template <int NS>
+__global__ void __launch_bounds__(64 * kRdWaves) k_pyr_resize_direct(uint8_t* __restrict__ pyr, int pyr_frame_bytes, LevelDesc P, LevelDesc L,
+                                                           const int32_t* __restrict__ tabs, int R) {
+  const int f = blockIdx.z, tx = threadIdx.x & 63;
+  const int ty = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int w = L.w, bw = L.w + 2 * kEdge;
+  const int y0 = ((int)blockIdx.y * kRdWaves + ty) * R;   // first interior row of this wave's strip
+  if (y0 >= L.h) return;
+  const int yl = min(y0 + R - 1, L.h - 1);
+  const int Xt = ((int)blockIdx.x * 64 + tx) * 4;
+  const bool live = Xt < bw;
+  const int X4 = live ? Xt : ((bw - 1) & ~3);
+  const int32_t* xofs = tabs + L.tab_off;
+  const int32_t* xal = xofs + L.w;   // (a0 | a1 << 16)
+  const int32_t* yofs = xal + L.w;
+  const int32_t* ybe = yofs + L.h;   // (b0 | b1 << 16)
+  const int dyl = min(y0 + tx, yl);
+  const int yv = yofs[dyl];
+  const uint32_t bv = (uint32_t)ybe[dyl];
+  int sx[4];
+  uint32_t al[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int x = min(X4 + k, bw - 1) - kEdge;   // pad bytes beyond the frame repeat the last frame column
+    const int xm = x < 0 ? -x : (x >= w ? 2 * (w - 1) - x : x);   // REFLECT_101 (one bounce: w >= 40)
+    sx[k] = xofs[xm];
+    al[k] = (uint32_t)xal[xm];
+  }
+  const int base = min(min(sx[0], sx[1]), min(sx[2], sx[3]));
+  uint32_t sel[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) sel[k] = 0x0c000c00u | (uint32_t)(sx[k] - base) | ((uint32_t)(sx[k] + 1 - base) << 16);
+  const int sya = __builtin_amdgcn_readlane(yv, 0);   // (no tap of an accepted level is clamped: 0 <= sy, sy + 1 <= P.h - 1)
+  const int syb = __builtin_amdgcn_readlane(yv, (yl - y0) & 63) + 1;
+  const uint8_t* Sf = pyr + (int64_t)f * pyr_frame_bytes + P.pyr_off;
+  const uint32_t scol = (uint32_t)(kEdge + base);
+  uint2 win[NS];
+#pragma unroll
+  for (int j = 0; j < NS; j++) {
+    const uint8_t* Sr = Sf + (uint32_t)((kEdge + min(sya + j, syb)) * P.stride);   // (rows past syb: the last row again, not used)
+    __builtin_memcpy(&win[j], Sr + scol, 8);
+  }
+  uint8_t* Dl = pyr + (int64_t)f * pyr_frame_bytes + L.pyr_off;
+  int d = y0;   // the next destination row, its table entries and its second tap
+  int syd = __builtin_amdgcn_readlane(yv, 0);
+  uint32_t bbd = __builtin_amdgcn_readlane(bv, 0);
+  int r1 = syd + 1;
+  uint32_t prev[4] = {0u, 0u, 0u, 0u}, cur[4];
+#pragma unroll
+  for (int j = 0; j < NS; j++) {
+    if (sya + j > syb) break;
+#pragma unroll
+    for (int k = 0; k < 4; k++) cur[k] = udot2(__builtin_amdgcn_perm(win[j].y, win[j].x, sel[k]), al[k], 0u) & 0xFFFFF0u;
+    if (d <= yl && r1 == sya + j) {
+      const uint32_t b0 = (bbd & 0xFFFFu) << 12, b1 = (bbd >> 16) << 12;
+      uint32_t v = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        // ((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2; a convex combination, never above 255
+        const uint32_t r = (mul_hi_u24(b0, prev[k]) + mul_hi_u24(b1, cur[k]) + 2u) >> 2;
+        v |= r << (8 * k);
+      }
+      if (live) {
+        // row pitch is a multiple of 64 >= bw: a full dword store never leaves the row
+        *reinterpret_cast<uint32_t*>(Dl + (int64_t)(kEdge + d) * L.stride + X4) = v;
+        int top, bot;
+        mirror_rows(d, L.h, top, bot);
+        if (top >= 0) *reinterpret_cast<uint32_t*>(Dl + (int64_t)top * L.stride + X4) = v;
+        if (bot >= 0) *reinterpret_cast<uint32_t*>(Dl + (int64_t)bot * L.stride + X4) = v;
+      }
+      d++;
+      syd = __builtin_amdgcn_readlane(yv, (d - y0) & 63);
+      bbd = __builtin_amdgcn_readlane(bv, (d - y0) & 63);
+      r1 = syd + 1;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) prev[k] = cur[k];
+  }
+}
+
 // FALLBACK for tiny levels (w < 40 or h < 20, where the mirror bounces more than once): the level kernels above
 // already write the frame for every normal size, and this kernel is then not launched.
 // REFLECT_101 frame of every level in ONE launch.  Per level, "bordered row" R in [0, h+38):
@@ -1538,7 +1648,7 @@ void launch_pyr_resize(hipStream_t s, uint8_t* d_pyr, const PipelineDesc& PD, in
   // LDS for the source rectangle of a 256 x 16 destination tile (scale = P/L, +margins)
   const double sxs = (double)P.w / L.w, sys = (double)P.h / L.h;
   const int pitch = (((int)(kRzTW * sxs) + 16) + 3) & ~3;
-  if (batch <= 8) {   // latency path: short tiles
+  if (batch <= kRzLatencyBatch) {   // latency path: short tiles
     const int nrows = (int)(16 * sys) + 4;
     dim3 grid(cdiv(L.w + 2 * kEdge, kRzTW), cdiv(L.h, 16), batch);
     hipLaunchKernelGGL(k_pyr_resize<16>, grid, dim3(256), (size_t)pitch * nrows, s, d_pyr, PD.pyr_frame_bytes, P, L, d_tabs, pitch);
@@ -1547,6 +1657,41 @@ void launch_pyr_resize(hipStream_t s, uint8_t* d_pyr, const PipelineDesc& PD, in
   const int nrows = (int)(kRzTH * sys) + 4;
   dim3 grid(cdiv(L.w + 2 * kEdge, kRzTW), cdiv(L.h, kRzTH), batch);
   hipLaunchKernelGGL(k_pyr_resize<kRzTH>, grid, dim3(256), (size_t)pitch * nrows, s, d_pyr, PD.pyr_frame_bytes, P, L, d_tabs, pitch);
+}
+// Strip height R for k_pyr_resize_direct at level L (parent P), or 0 when the level must keep k_pyr_resize.  Decided from the
+// tables the kernel reads: both levels single-bounce sized, every group's window at most 8 bytes and inside the parent's row pitch,
+// yofs strictly increasing with both taps inside the parent unclamped, and R the largest height at which no strip spans more than
+// kRdNS source rows.
+int pyr_direct_strip_rows(const LevelDesc& P, const LevelDesc& L, const int32_t* xofs, const int32_t* yofs) {
+  if (L.w < 40 || L.h < 20 || P.w < 40 || P.h < 20) return 0;
+  const int w = L.w, bw = L.w + 2 * kEdge;
+  for (int X4 = 0; X4 < bw; X4 += 4) {
+    int lo = INT32_MAX, hi = INT32_MIN;
+    for (int k = 0; k < 4; k++) {
+      const int x = std::min(X4 + k, bw - 1) - kEdge;
+      const int xm = x < 0 ? -x : (x >= w ? 2 * (w - 1) - x : x);
+      if (xm < 0 || xm >= w) return 0;
+      lo = std::min(lo, xofs[xm]);
+      hi = std::max(hi, xofs[xm] + 1);
+    }
+    if (lo < 0 || hi - lo + 1 > 8 || kEdge + lo + 8 > P.stride) return 0;
+  }
+  for (int y = 0; y < L.h; y++) {
+    if (yofs[y] < 0 || yofs[y] + 1 > P.h - 1) return 0;
+    if (y > 0 && yofs[y] <= yofs[y - 1]) return 0;
+  }
+  for (int R = std::min(kRdNS, 63); R >= 1; R--) {
+    bool ok = true;
+    for (int y0 = 0; y0 < L.h && ok; y0 += R) ok = yofs[std::min(y0 + R - 1, L.h - 1)] + 1 - yofs[y0] + 1 <= kRdNS;
+    if (ok) return R;
+  }
+  return 0;
+}
+void launch_pyr_resize_direct(hipStream_t s, uint8_t* d_pyr, const PipelineDesc& PD, int level, const int32_t* d_tabs, int batch, int strip_rows) {
+  const LevelDesc& L = PD.lv[level];
+  const LevelDesc& P = PD.lv[level - 1];
+  dim3 grid(cdiv(cdiv(L.w + 2 * kEdge, 4), 64), cdiv(cdiv(L.h, strip_rows), kRdWaves), batch);
+  hipLaunchKernelGGL(k_pyr_resize_direct<kRdNS>, grid, dim3(64 * kRdWaves), 0, s, d_pyr, PD.pyr_frame_bytes, P, L, d_tabs, strip_rows);
 }
 void launch_pyr_borders(hipStream_t s, uint8_t* d_pyr, const PipelineDesc& PD, int batch) {
   int rows = 0, maxw = 0;

@@ -308,6 +308,7 @@ int OrbPipeline::init() {
   if (const char* e = getenv("DVM_ZERO_COPY_IN")) zero_copy_in = (e[0] != '0');
   if (const char* e = getenv("DVM_SERIAL")) overlap_blur = (e[0] != '1');      // debug / A-B switch only
   if (const char* e = getenv("DVM_PATCH_BLUR")) patch_blur = (e[0] != '0');    // A-B switch: 0 = k_blur7 + k_orient_desc for batches too
+  if (const char* e = getenv("DVM_PYR_DIRECT")) pyr_direct = (e[0] != '0');    // A-B switch: 0 = k_pyr_resize for every level of a batch
 #ifdef DVM_DEBUG
   if (const char* e = getenv("DVM_HOST_OCTREE")) host_octree_forced = (e[0] == '1');  // debug / A-B switch, debug builds only
 #endif
@@ -420,6 +421,7 @@ int OrbPipeline::configure(int rows, int cols) {
       tabs.insert(tabs.end(), xa.begin(), xa.end());
       tabs.insert(tabs.end(), yo.begin(), yo.end());
       tabs.insert(tabs.end(), yb.begin(), yb.end());
+      pyr_strip[l] = pyr_direct ? pyr_direct_strip_rows(PD.lv[l - 1], D, xo.data(), yo.data()) : 0;
     }
     // FAST cells, ORBextractor.cc:617-650
     D.cell_first = (int)cells.size();
@@ -678,7 +680,11 @@ int OrbPipeline::extract_device(const uint8_t* d_imgs, int batch, int rows, int 
       DVM_HIP(hipEventRecord(ev_stage_free, st));                   // H2D copy may overwrite it while this one computes
       stage_free_valid = true;
     }
-    for (int l = 1; l < L; l++) launch_pyr_resize(st, pyr_f0, PD, l, d_tabs, nb);
+    for (int l = 1; l < L; l++) {
+      pyr_path[l] = nb > kRzLatencyBatch && pyr_strip[l] > 0;
+      if (pyr_path[l]) launch_pyr_resize_direct(st, pyr_f0, PD, l, d_tabs, nb, pyr_strip[l]);
+      else launch_pyr_resize(st, pyr_f0, PD, l, d_tabs, nb);
+    }
     if (tiny_levels) launch_pyr_borders(st, pyr_f0, PD, nb);   // else: fused into the level kernels
     prof.end(st);
     const bool blur_forked = overlap_blur && !host_octree && side != nullptr && !small && !fused;   // latency path: one chain, no events (below)

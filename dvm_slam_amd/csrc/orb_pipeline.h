@@ -89,6 +89,11 @@ class OrbPipeline {
   // DVM_PATCH_BLUR=0/1: batches of more than kLatencyBatch frames launch no blur and fork no side stream; the descriptor kernel
   // blurs each keypoint's own patch on chip (k_orient_desc_blur).  d_blur then does not describe the batch: refresh_blur()
   bool patch_blur = true;
+  // DVM_PYR_DIRECT=0/1: batches of more than kRzLatencyBatch frames build every level that qualifies (pyr_direct_strip_rows) with
+  // k_pyr_resize_direct; 0 keeps k_pyr_resize everywhere (A-B switch)
+  bool pyr_direct = true;
+  int pyr_strip[kMaxLevels] = {};      // strip height of the direct kernel per level of the current image size, 0 = k_pyr_resize
+  uint8_t pyr_path[kMaxLevels] = {};   // 1 = the last batch built the level with k_pyr_resize_direct (dvm_orb_debug_pyr_path)
   bool blur_stale = false;   // d_blur is older than the last batch (dvm_orb_debug_blurred runs the blur on demand)
   int refresh_blur();        // k_blur7 over the last batch's resident pyramid, on `stream`, if d_blur is stale
   Profiler prof;

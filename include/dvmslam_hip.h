@@ -153,6 +153,8 @@ int dvm_orb_debug_blurred(dvm_orb* h, int frame, int level, uint8_t* out);
 int dvm_orb_debug_candidates(dvm_orb* h, int frame, int level, int32_t* xs, int32_t* ys, int32_t* scores,
                              int cap, int* n);
 int dvm_orb_debug_level_keypoints(dvm_orb* h, int frame, int level, dvm_keypoint* kps, int cap, int* n);
+/* *out = 1 if the last batch built pyramid level `level` with k_pyr_resize_direct, 0 for k_pyr_resize (and for level 0) */
+int dvm_orb_debug_pyr_path(dvm_orb* h, int level, int* out);
 
 /* per-kernel HIP-event timing on the handle's stream.  names: "pyramid","fast","octree",
  * "assemble","blur","orient_desc","grid_sort","match" ...  Returns accumulated milliseconds and launch count since
