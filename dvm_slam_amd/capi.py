@@ -1110,10 +1110,22 @@ class Tracker:
 
     __del__ = close
 
+    def set_camera_model(self, model):
+        """dvm_tracker_set_camera_model: the camera of the agent this tracker serves, for every chain of the tracker.  model: a CameraModel, or
+        None for the default (the pinhole K of each call).  Drops what the last begin / finish prepared for the second half."""
+        f = self.L.dvm_tracker_set_camera_model
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_void_p]
+        check(f(self.t, _model_ref(model)))
+
     def track(self, img, Tcw_pred, K, bounds, scale_factors, inv_sigma2, kps_l, mp_l, outlier_l, mps, th=15.0, check_ori=True, dist=None,
-              lap=(0, 1000)):
-        """Tcw_pred: 7 floats (qx, qy, qz, qw, t).  Returns a dict: n, kps, desc, kps_un, mp (mvpMapPoints after the outlier drop), dropped,
-        pose (7 doubles: t, q), and the counters of dvmh_track_result."""
+              lap=(0, 1000), model=None):
+        """Tcw_pred: 7 floats (qx, qy, qz, qw, t).  model: a CameraModel (dvmh_track_with_motion_model_cam: the tracker is set to it and K,
+        which may then be None, is not read), or None for the pinhole K.  Returns a dict: n, kps, desc, kps_un, mp (mvpMapPoints after the
+        outlier drop), dropped, pose (7 doubles: t, q), and the counters of dvmh_track_result."""
+        if K is None:
+            if model is None:
+                raise ValueError("K is needed without a camera model")
+            K = model.p[:4]
         img = np.ascontiguousarray(img, np.uint8)
         cap = self.ext.cap
         kps = np.empty(cap, KP_DTYPE); kun = np.empty(cap, KP_DTYPE); desc = np.empty((cap, 32), np.uint8)
@@ -1123,11 +1135,12 @@ class Tracker:
         f4 = [np.ascontiguousarray(a, np.float32) for a in (Tcw_pred, K, bounds, scale_factors, inv_sigma2)]
         mps = np.ascontiguousarray(mps, MAP_POINT_DTYPE)
         res = TrackResult()
-        fn = self.H.dvmh_track_with_motion_model
+        fn = self.H.dvmh_track_with_motion_model if model is None else self.H.dvmh_track_with_motion_model_cam
         fn.restype = C.c_int32; fn.argtypes = None
         vp = C.c_void_p
+        cam = () if model is None else (C.byref(model),)
         rc = fn(self.t, self.ext.h, C.c_int32(self.device), vp(img.ctypes.data), C.c_int32(img.shape[0]), C.c_int32(img.shape[1]), C.c_int32(img.strides[0]),
-                C.c_int32(lap[0]), C.c_int32(lap[1]), _p(f4[0]), _p(f4[1]), _p(f4[2]), None if dist is None else C.byref(dist), _p(f4[3]), _p(f4[4]),
+                C.c_int32(lap[0]), C.c_int32(lap[1]), _p(f4[0]), _p(f4[1]), *cam, _p(f4[2]), None if dist is None else C.byref(dist), _p(f4[3]), _p(f4[4]),
                 C.c_int32(len(f4[3])), C.c_int32(len(kps_l)), _p(kps_l), _p(mp_l), None if outl is None else _p(outl), _p(mps), C.c_float(float(th)),
                 C.c_int32(int(check_ori)), _p(kps), _p(desc), C.c_int32(cap), _p(kun), _p(mp), _p(dropped), C.byref(res))
         check(rc)
@@ -1175,16 +1188,21 @@ class Tracker:
         check(f(self.t, int(n)))
 
     def track_reference_keyframe(self, voc, kf, pose_last, img=None, K=None, bounds=None, inv_sigma2=None, dist=None, nnratio=0.7, check_ori=True,
-                                 th_low=50, min_matches=15, min_map=10, levelsup=4, lap=(0, 1000)):
+                                 th_low=50, min_matches=15, min_map=10, levelsup=4, lap=(0, 1000), model=None):
         """dvm_track_reference_keyframe: Tracking::TrackReferenceKeyFrame (reference src/Tracking.cc:2461-2520) as ONE device chain.
         voc: a Vocabulary; kf: dict(kps (mvKeysUn), desc, mp (map-point ids or -1), pos [n, 3], n_obs, bad (optional), fv (mFeatVec as
         vocab_transform_host returns it)); pose_last: mLastFrame.GetPose() as 7 floats (qx, qy, qz, qw, t).  With img: dvm_track_begin on it,
         then the chain (form a: the no-motion-model case); without: the chain on the frame of the last track() (form b: the motion model
-        failed).  K: fx fy cx cy; bounds, dist: form (a).  Returns a dict: the counters of dvm_track_refkf_result, mp (mvpMapPoints after the
+        failed).  K: fx fy cx cy; bounds, dist: form (a).  model: a CameraModel -- with img the tracker is set to it before the begin (form (b)
+        runs on the model of the frame's track() call); K may then be None (it is not read under KannalaBrandt8).  Returns a dict: the counters of dvm_track_refkf_result, mp (mvpMapPoints after the
         outlier drop), dropped, outlier, bow_ids / bow_vals / fv_nodes / fv_off / fv_feat (ComputeBoW), pose (7 doubles: t, q), Tcw (7 floats:
         q, t) and, in form (a), kps / desc / kps_un."""
         cap = self.ext.cap
         vp = C.c_void_p
+        if model is not None:
+            K = model.p[:4] if K is None else K
+            if img is not None:
+                self.set_camera_model(model)
         if img is not None:
             img = np.ascontiguousarray(img, np.uint8)
             fb = self.L.dvm_track_begin
@@ -1343,6 +1361,13 @@ class TrackerBatch:
 
     __del__ = close
 
+    def set_camera_model(self, model):
+        """dvm_tracker_set_camera_model: the camera of the agent this tracker serves, for every chain of the tracker.  model: a CameraModel, or
+        None for the default (the pinhole K of each call).  Drops what the last begin / finish prepared for the second half."""
+        f = self.L.dvm_tracker_set_camera_model
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_void_p]
+        check(f(self.t, _model_ref(model)))
+
     def prepare(self, Tcw_preds, lasts):
         """lasts: per agent (kps_l, mp_l, outlier_l or None, mps).  Returns the marshalled dvmh_track_in array (keep it alive with its arrays)."""
         n = len(lasts)
@@ -1356,16 +1381,22 @@ class TrackerBatch:
             i.Tcw_pred, i.Nl, i.kps_l, i.mp_l, i.outlier_l, i.mps = T.ctypes.data, len(kl), kl.ctypes.data, ml.ctypes.data, None if ol is None else ol.ctypes.data, mps.ctypes.data
         return ins, keep
 
-    def track(self, imgs, ins, K, bounds, scale_factors, inv_sigma2, th=15.0, check_ori=True, lap=(0, 1000)):
-        """imgs [count, rows, cols] u8; ins: prepare()'s array.  Returns one dict per frame (views into this object's arrays)."""
+    def track(self, imgs, ins, K, bounds, scale_factors, inv_sigma2, th=15.0, check_ori=True, lap=(0, 1000), model=None):
+        """imgs [count, rows, cols] u8; ins: prepare()'s array; model: as Tracker.track takes it, one for all frames
+        (dvmh_track_with_motion_model_batch_cam).  Returns one dict per frame (views into this object's arrays)."""
+        if K is None:
+            if model is None:
+                raise ValueError("K is needed without a camera model")
+            K = model.p[:4]
         imgs = np.ascontiguousarray(imgs, np.uint8)
         count = imgs.shape[0]
         f4 = [np.ascontiguousarray(a, np.float32) for a in (K, bounds, scale_factors, inv_sigma2)]
-        fn = self.H.dvmh_track_with_motion_model_batch
+        fn = self.H.dvmh_track_with_motion_model_batch if model is None else self.H.dvmh_track_with_motion_model_batch_cam
         fn.restype = C.c_int32; fn.argtypes = None
         vp = C.c_void_p
+        cam = () if model is None else (C.byref(model),)
         rc = fn(self.t, self.ext.h, C.c_int32(self.device), C.c_int32(count), vp(imgs.ctypes.data), C.c_int32(imgs.shape[1]), C.c_int32(imgs.shape[2]),
-                C.c_int32(imgs.strides[1]), C.c_int64(imgs.strides[0]), C.c_int32(lap[0]), C.c_int32(lap[1]), _p(f4[0]), _p(f4[1]), _p(f4[2]), _p(f4[3]),
+                C.c_int32(imgs.strides[1]), C.c_int64(imgs.strides[0]), C.c_int32(lap[0]), C.c_int32(lap[1]), _p(f4[0]), *cam, _p(f4[1]), _p(f4[2]), _p(f4[3]),
                 C.c_int32(len(f4[2])), C.c_float(float(th)), C.c_int32(int(check_ori)), ins[0] if isinstance(ins, tuple) else ins, self.outs, self.res)
         check(rc)
         out = []

@@ -29,6 +29,7 @@
 
 #include "../../include/dvmslam_hip.h"
 #include "ba_kernels.h"
+#include "camera_model.h"
 #include "chain.h"
 #include "match_kernels.h"
 #include "orb_pipeline.h"
@@ -47,6 +48,7 @@ struct LocalFrame {
   const dvm_keypoint_pod* d_un = nullptr; const int32_t* d_n = nullptr;   // mvKeysUn on the device, the keypoint count
   float bounds[4] = {0, 0, 0, 0}, inv_sigma2[64] = {};
   dvm_ba_camera cam{};
+  dvm_camera_model model{};                       // the camera model that finish ran on (dvm_tracker_set_camera_model): the second half runs on it
   int count = 0; int64_t kps_stride = 0;          // the finish's frames: frame b's mvKeysUn at b * kps_stride, its count at d_n[b]
   std::vector<int32_t> ns, status;                // per frame: keypoints, the first half's status
   std::vector<double> poses;                      // [count][7]: the poses the second half starts from (the finish's, or the reference-keyframe chain's)
@@ -87,6 +89,7 @@ struct dvm_tracker {
   hipStream_t cstream = nullptr; hipEvent_t cev = nullptr;
   template <class T> T* qdev(T* host_ptr) const { return rebase(host_ptr, ws.hm, d_q); }
   int begun = 0;                   // frames of the batch whose extraction is queued
+  dvm_camera_model model{};        // dvm_tracker_set_camera_model: 0 (a fresh tracker): the cam of the query / parameter structs; 1: KannalaBrandt8 on model.p
   int rows = 0, cols = 0;
   // ---- the second half (dvm_track_local_map[_batch]): working set of dvm_tracker_reserve_local_map, and what the last finish left for it
   int lm_cap = 0;                  // table entries reserved (a multiple of 64; a batch: all frames' tables, each rounded up to 64)
@@ -114,6 +117,17 @@ namespace {
 using Cursor256 = Cursor<256>;
 // a reservation that could not be allocated: "<fn>: <what failed>"
 int reserve_failed(const char* fn, const char* what) { set_error(std::string(fn) + ": " + what); return DVM_ERR_CAPACITY; }
+// PoseOptimization of a chain: k_pose_optimize on cam, or k_pose_optimize_kb8 on M.p under a KannalaBrandt8 model (cam is then not read)
+void launch_pose_optimize(hipStream_t s, const dvm_camera_model& M, const dvm_ba_camera& cam, const double* pose_in, const double* Xw, const double* obs,
+                          const double* info, const int32_t* n_per_frame, int stride, int batch, double* pose_out, uint8_t* outlier, int32_t* n_inliers,
+                          double* chi_scratch) {
+  if (M.model == dvm_cam::kKannalaBrandt8)
+    ba_launch_pose_optimize_kb8(s, pose_in, Xw, obs, info, n_per_frame, stride, batch, M.p, pose_out, outlier, n_inliers, chi_scratch);
+  else
+    ba_launch_pose_optimize(s, pose_in, Xw, obs, info, n_per_frame, stride, batch, cam.fx, cam.fy, cam.cx, cam.cy, pose_out, outlier, n_inliers, chi_scratch);
+}
+// a KannalaBrandt8 frame has mvKeysUn = mvKeys and a zero mDistCoef: distortion coefficients beside such a model are a caller's mistake
+bool kb8_with_distortion(const dvm_camera_model& M, const dvm_distortion* dist) { return M.model == dvm_cam::kKannalaBrandt8 && dist && dist->k1 != 0.0f; }
 }  // namespace
 
 extern "C" {
@@ -177,6 +191,15 @@ void dvm_tracker_destroy(dvm_tracker* t) {
   delete t;
 }
 
+int dvm_tracker_set_camera_model(dvm_tracker* t, const dvm_camera_model* model) {
+  if (!t) return DVM_ERR_INVALID;
+  if (model && !dvm_cam::model_ok(model->model, model->p)) { set_error("dvm_tracker_set_camera_model: unknown model or zero focal length"); return DVM_ERR_INVALID; }
+  dvm_camera_model M{};            // NULL and model 0: the default (the structs' cam fields; p is not kept)
+  if (model && model->model == dvm_cam::kKannalaBrandt8) M = *model;
+  t->model = M; t->clear_next();   // (a finish records the model it ran on: nothing prepared under the old one runs on the new)
+  return DVM_OK;
+}
+
 int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error("dvm_track_begin_batch: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
@@ -206,6 +229,8 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
   t->clear_next();
   if (t->begun != count) { set_error("dvm_track_finish: no matching dvm_track_begin on this tracker"); return DVM_ERR_STATE; }
   const dvm_track_queries& q0 = qs[0];
+  const dvm_camera_model M = t->model;
+  const bool kb8 = M.model == dvm_cam::kKannalaBrandt8;    // (the cam fields of the queries are then not read)
   int nq_max = 0;
   for (int b = 0; b < count; b++) {
     const dvm_track_queries& q = qs[b];
@@ -213,7 +238,11 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
     if (!o.kps || !o.desc || !o.assign || !o.outlier) return DVM_ERR_INVALID;
     if (q.nq < 0 || q.nq > t->q_cap || q.nlevels < 1 || q.nlevels > 64 || !q.inv_level_sigma2) { set_error("dvm_track_finish: bad query set"); return DVM_ERR_INVALID; }
     if (q.nq && (!q.qdesc || !q.qx || !q.qy || !q.qr || !q.qmin || !q.qmax || !q.q_claims || !q.q_angle || !q.q_pos)) return DVM_ERR_INVALID;
-    if (b && (std::memcmp(q.bounds, q0.bounds, 16) != 0 || std::memcmp(&q.cam, &q0.cam, sizeof(q.cam)) != 0 || q.th_high != q0.th_high || q.check_ori != q0.check_ori ||
+    if (kb8_with_distortion(M, q.dist)) {
+      set_error("dvm_track_finish: distortion coefficients under a KannalaBrandt8 camera model (such a frame has mvKeysUn = mvKeys, mDistCoef zero)");
+      return DVM_ERR_INVALID;
+    }
+    if (b && (std::memcmp(q.bounds, q0.bounds, 16) != 0 || (!kb8 && std::memcmp(&q.cam, &q0.cam, sizeof(q.cam)) != 0) || q.th_high != q0.th_high || q.check_ori != q0.check_ori ||
               q.min_matches != q0.min_matches || q.nlevels != q0.nlevels || std::memcmp(q.inv_level_sigma2, q0.inv_level_sigma2, (size_t)q.nlevels * 4) != 0)) {
       set_error("dvm_track_finish_batch: the frames of a batch share camera, bounds, level table and matcher thresholds");
       return DVM_ERR_INVALID;
@@ -289,8 +318,8 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
                       q0.check_ori, t->d_assign, t->d_res, t->ws.dev(m.assign), t->ws.dev(m.res), TB);
   launch_track_gather(s, t->d_assign, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, t->qdev(m.q_pos), t->qdev(m.inv_sigma2), q0.nlevels, t->d_Xw,
                       t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges, t->d_res, q0.min_matches, t->ws.dev(m.nedges), TB);
-  ba_launch_pose_optimize(s, t->qdev(m.pose_in), t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, q0.cam.fx, q0.cam.fy, q0.cam.cx, q0.cam.cy,
-                          t->ws.dev(m.pose_out), t->d_edge_out, t->ws.dev(m.n_inl), t->d_chi);
+  launch_pose_optimize(s, M, q0.cam, t->qdev(m.pose_in), t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, t->ws.dev(m.pose_out), t->d_edge_out,
+                       t->ws.dev(m.n_inl), t->d_chi);
   launch_track_finish(s, t->d_assign, d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, t->qdev(m.q_claims), t->ws.dev(m.outlier), t->ws.dev(m.fin), t->d_res, TB);
   // (what the host wants back is written to mapped memory by the kernels themselves: no copy command behind the chain)
   rc = hip_check(hipGetLastError(), "tracking chain launch");
@@ -333,7 +362,7 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
     f.ready = count == 1 && res[0].status == DVM_TRACK_COMPLETE; f.batch_ready = 1; f.rkb_ready = 1;
     f.h = h; f.serial = orb_result_serial(h); f.ocap = ocap; f.nlevels = q0.nlevels;
     f.d_un = reinterpret_cast<const dvm_keypoint_pod*>(d_un); f.d_n = d_n;
-    std::memcpy(f.bounds, q0.bounds, 16); std::memcpy(f.inv_sigma2, q0.inv_level_sigma2, (size_t)q0.nlevels * 4); f.cam = q0.cam;
+    std::memcpy(f.bounds, q0.bounds, 16); std::memcpy(f.inv_sigma2, q0.inv_level_sigma2, (size_t)q0.nlevels * 4); f.cam = q0.cam; f.model = M;
     f.count = count; f.kps_stride = kps_stride; f.ns.resize((size_t)count); f.status.resize((size_t)count);
     f.monos.resize((size_t)count); f.poses.assign(m.pose_out, m.pose_out + 7 * (size_t)count);
     for (int b = 0; b < count; b++) { f.ns[b] = res[b].n; f.status[b] = res[b].status; f.monos[b] = res[b].mono_index; }
@@ -470,12 +499,13 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
   A.min_x = f.bounds[0]; A.max_x = f.bounds[1]; A.min_y = f.bounds[2]; A.max_y = f.bounds[3];
   A.log_scale_factor = f.nlevels > 1 ? (float)std::log((double)scale[1]) : 0.0f;     // Frame::mfLogScaleFactor = log(mfScaleFactor)
   A.n_levels = f.nlevels; A.per_frame = dup.fa;
+  std::memcpy(A.kb8, f.model.p, sizeof(A.kb8));
   const TrackBatch TB{count, (int)span_max, f.kps_stride, LQ.nq, dup.qoff};
   auto& r = t->lm;
   // 3. SearchLocalPoints up to the queries
   bool want_tp = false;
   for (int b = 0; b < count; b++) want_tp = want_tp || (f.status[b] == DVM_TRACK_COMPLETE && out[b].track_pts);
-  launch_track_local_prologue(s, dup.pts, dup.frame_mp, dup.pose, dup.scale, f.d_n, ocap, A, LQ, want_tp ? t->lmw.dev(r.tp) : nullptr, t->lmw.dev(r.res),
+  launch_track_local_prologue(s, f.model.model, dup.pts, dup.frame_mp, dup.pose, dup.scale, f.d_n, ocap, A, LQ, want_tp ? t->lmw.dev(r.tp) : nullptr, t->lmw.dev(r.res),
                               TB);
   // 4. the ranked window search on the frames' grids (built by the finish), the keypoints with observed points skipped
   const FrameView FV = frame_view_of(t->grid);
@@ -492,8 +522,8 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
   const TrackBatch TE{count, 0, f.kps_stride, nullptr, dup.qoff};
   launch_track_gather(s, t->d_assign, f.d_un, f.d_n, ocap, LQ.pos, dup.inv_sigma2, f.nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp,
                       t->d_nedges, d_lres, 0, t->lmw.dev(r.nedges), TE);
-  ba_launch_pose_optimize(s, LQ.pose_in, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, f.cam.fx, f.cam.fy, f.cam.cx, f.cam.cy,
-                          t->lmw.dev(r.pose), t->d_edge_out, t->lmw.dev(r.n_inl), t->d_chi);
+  launch_pose_optimize(s, f.model, f.cam, LQ.pose_in, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, t->lmw.dev(r.pose), t->d_edge_out,
+                       t->lmw.dev(r.n_inl), t->d_chi);
   launch_track_finish(s, t->d_assign, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmw.dev(r.outlier), t->lmw.dev(r.fin),
                       d_lres, TE);
   t->clear_next();   // once per finish
@@ -669,7 +699,8 @@ int refkf_enqueue(dvm_tracker* t, RefKf& w, dvm_orb* h, const dvm_vocab* voc, in
       p0 = p;
     } else if (p->nnratio != p0->nnratio || p->check_ori != p0->check_ori || p->th_low != p0->th_low || p->min_matches != p0->min_matches ||
                p->min_map != p0->min_map || p->levelsup != p0->levelsup || p->nlevels != p0->nlevels ||
-               std::memcmp(p->inv_level_sigma2, p0->inv_level_sigma2, (size_t)p->nlevels * 4) != 0 || std::memcmp(&p->cam, &p0->cam, sizeof(p->cam)) != 0) {
+               std::memcmp(p->inv_level_sigma2, p0->inv_level_sigma2, (size_t)p->nlevels * 4) != 0 ||
+               (f.model.model != dvm_cam::kKannalaBrandt8 && std::memcmp(&p->cam, &p0->cam, sizeof(p->cam)) != 0)) {
       set_error("dvm_track_reference_keyframe_batch: the frames that run share camera, level table and matcher thresholds");
       return DVM_ERR_INVALID;
     }
@@ -753,8 +784,8 @@ int refkf_enqueue(dvm_tracker* t, RefKf& w, dvm_orb* h, const dvm_vocab* voc, in
   const TrackBatch TE{count, 0, f.kps_stride, nullptr, dup.qoff};
   launch_track_gather(s, W.match, f.d_un, f.d_n, ocap, dup.pos, dup.inv_sigma2, P0.nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges,
                       dup.res, P0.min_matches, w.ws.dev(r.nedges), TE);
-  ba_launch_pose_optimize(s, dup.pose, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, P0.cam.fx, P0.cam.fy, P0.cam.cx, P0.cam.cy,
-                          w.ws.dev(r.pose), t->d_edge_out, w.ws.dev(r.n_inl), t->d_chi);
+  launch_pose_optimize(s, f.model, P0.cam, dup.pose, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, w.ws.dev(r.pose), t->d_edge_out,
+                       w.ws.dev(r.n_inl), t->d_chi);
   launch_track_finish(s, W.match, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, dup.claims, w.ws.dev(r.outlier), w.ws.dev(r.fin), dup.res, TE);
   return hip_check(hipGetLastError(), "reference keyframe chain launch");
 }
@@ -835,6 +866,10 @@ int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* vo
     set_error("dvm_track_reference_keyframe: form (a) builds the grid: empty frame bounds"); return DVM_ERR_INVALID;
   }
   if (vocab_device(voc) != t->device) { set_error("dvm_track_reference_keyframe: the vocabulary lives on another device"); return DVM_ERR_INVALID; }
+  if (form == 1 && kb8_with_distortion(t->model, p->dist)) {
+    set_error("dvm_track_reference_keyframe: distortion coefficients under a KannalaBrandt8 camera model (such a frame has mvKeysUn = mvKeys, mDistCoef zero)");
+    return DVM_ERR_INVALID;
+  }
   std::memset(res, 0, sizeof(*res));
   t->clear_next();   // once per begin; the second half waits for this call's status
   DVM_HIP(hipSetDevice(t->device));
@@ -860,7 +895,7 @@ int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* vo
     f.h = h; f.serial = orb_result_serial(h); f.ocap = ocap; f.nlevels = p->nlevels;
     f.d_un = reinterpret_cast<const dvm_keypoint_pod*>(un); f.d_n = d_n;
     std::memcpy(f.bounds, p->bounds, 16); std::memset(f.inv_sigma2, 0, sizeof(f.inv_sigma2));
-    std::memcpy(f.inv_sigma2, p->inv_level_sigma2, (size_t)p->nlevels * 4); f.cam = p->cam;
+    std::memcpy(f.inv_sigma2, p->inv_level_sigma2, (size_t)p->nlevels * 4); f.cam = p->cam; f.model = t->model;
     f.count = 1; f.kps_stride = ocap; f.d_desc = d_desc; f.desc_stride = (int64_t)ocap * 32;
     f.ns.assign(1, 0); f.status.assign(1, 0); f.monos.assign(1, 0); f.poses.assign(7, 0.0);
   }

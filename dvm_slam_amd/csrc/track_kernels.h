@@ -31,6 +31,7 @@ struct LocalMapArgs {   // the call's constants: camera, bounds, level count; pe
   float fx, fy, cx, cy, min_x, max_x, min_y, max_y, log_scale_factor;
   int32_t n_levels;
   const LocalFrameArgs* per_frame;   // device [count]
+  float kb8[8];                      // mvParameters of a KannalaBrandt8 frame (camera_model.h): read by the model-1 prologue only, which reads none of fx, fy, cx, cy
 };
 // what k_track_local_prologue leaves for the search (device arrays; the query arrays at the call's stride)
 struct LocalQueries {
@@ -44,8 +45,9 @@ struct LocalQueries {
   double* pose_in;             // [7] the first half's float pose widened: PoseOptimization's seed
 };
 // pose_first: the first half's optimised poses (t, q doubles); scale: mvScaleFactors [64]; B: count frames with B.qoff (frame b's table,
-// per-entry and query arrays at qoff[b], its per-keypoint arrays at b * kp_cap, A.per_frame[b])
-void launch_track_local_prologue(hipStream_t s, const LocalPointPod* pts, const int32_t* frame_mp_in, const double* pose_first, const float* scale,
+// per-entry and query arrays at qoff[b], its per-keypoint arrays at b * kp_cap, A.per_frame[b]); model: dvm_cam::kPinhole or kKannalaBrandt8
+// (mpCamera->project of isInFrustum through A.kb8)
+void launch_track_local_prologue(hipStream_t s, int model, const LocalPointPod* pts, const int32_t* frame_mp_in, const double* pose_first, const float* scale,
                                  const int32_t* d_n, int kp_cap, const LocalMapArgs& A, const LocalQueries& LQ, TrackPoint* track_pts_host,
                                  int32_t* res_host, const TrackBatch& B);
 // the claim replay of SearchByProjection(F, points) (k_track_claims<true>): assign[j] = the table entry keypoint j holds at the end (the

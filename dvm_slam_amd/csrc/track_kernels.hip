@@ -352,6 +352,9 @@ __global__ void __launch_bounds__(256) k_track_finish(int32_t* __restrict__ assi
 //     [level - 1, level]; the in-view points compacted into the query arrays IN TABLE ORDER (the claim replay's order)
 // tables: scale[64] = mvScaleFactors.  res_host[0] = nToMatch, res_host[1] = frame points cleared as bad.  Each frame's table size, th
 // and far-point filter from A.per_frame[b]; an empty table with no frame points leaves nothing to search.
+// MODEL: the camera behind isInFrustum's mpCamera->project (frustum_point<MODEL>, what dvm_is_in_frustum[_cam] calls); KannalaBrandt8 reads
+// A.kb8 (78 VGPRs against the pinhole's 74, no scratch: both keep the 1024-thread workgroup).
+template <int MODEL>
 __global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointPod* __restrict__ pts, const int32_t* __restrict__ frame_mp_in,
                                                                const double* __restrict__ pose_first, const float* __restrict__ scale,
                                                                const int32_t* __restrict__ d_n, int kp_cap, LocalMapArgs A, LocalQueries LQ,
@@ -410,7 +413,7 @@ __global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointP
     TrackPoint o{};
     if (i < n) {
       const LocalPointPod& P = pts[i];
-      o = frustum_point(F, P.pos[0], P.pos[1], P.pos[2], P.normal[0], P.normal[1], P.normal[2], P.min_dist, P.max_dist, 0.5f);
+      o = frustum_point<MODEL>(F, P.pos[0], P.pos[1], P.pos[2], P.normal[0], P.normal[1], P.normal[2], P.min_dist, P.max_dist, 0.5f, A.kb8);
       if (LQ.seen[i] || P.bad) o.in_view = 0;
       n_view += o.in_view;
       if (tp_host) tp_host[i] = o;
@@ -695,11 +698,15 @@ void launch_track_claims_local(hipStream_t s, const uint32_t* ranked, const Loca
   hipLaunchKernelGGL(k_track_claims<true>, dim3(B.count), dim3(256), lds, s, ranked, LQ.q_claims, nullptr, 0, rq, kps, d_n, kp_cap, th_high, 0,
                      nnratio, LQ, assign, res, assign_host, res_host, B);
 }
-void launch_track_local_prologue(hipStream_t s, const LocalPointPod* pts, const int32_t* frame_mp_in, const double* pose_first, const float* scale,
-                                 const int32_t* d_n, int kp_cap, const LocalMapArgs& A, const LocalQueries& LQ, TrackPoint* track_pts_host,
-                                 int32_t* res_host, const TrackBatch& B) {
-  hipLaunchKernelGGL(k_track_local_prologue, dim3(B.count), dim3(1024), 0, s, pts, frame_mp_in, pose_first, scale, d_n, kp_cap, A, LQ, track_pts_host,
-                     res_host, B);
+void launch_track_local_prologue(hipStream_t s, int model, const LocalPointPod* pts, const int32_t* frame_mp_in, const double* pose_first,
+                                 const float* scale, const int32_t* d_n, int kp_cap, const LocalMapArgs& A, const LocalQueries& LQ,
+                                 TrackPoint* track_pts_host, int32_t* res_host, const TrackBatch& B) {
+  if (model == dvm_cam::kKannalaBrandt8)
+    hipLaunchKernelGGL((k_track_local_prologue<dvm_cam::kKannalaBrandt8>), dim3(B.count), dim3(1024), 0, s, pts, frame_mp_in, pose_first, scale, d_n,
+                       kp_cap, A, LQ, track_pts_host, res_host, B);
+  else
+    hipLaunchKernelGGL((k_track_local_prologue<dvm_cam::kPinhole>), dim3(B.count), dim3(1024), 0, s, pts, frame_mp_in, pose_first, scale, d_n, kp_cap,
+                       A, LQ, track_pts_host, res_host, B);
 }
 void launch_track_gather(hipStream_t s, const int32_t* assign, const dvm_keypoint_pod* kps_un, const int32_t* d_n, int kp_cap, const float* q_pos,
                          const float* inv_sigma2, int nlevels, double* Xw, double* obs, double* info, int32_t* edge_kp, int32_t* n_edges,

@@ -13,20 +13,30 @@
 
 #include "dvmslam_host.h"
 #include "orb_matcher.h"
+#include "../csrc/camera_model.h"
 
 using dvm_host::FrameQueries;
 using dvm_host::FrameView;
 
 namespace {
 constexpr int TH_HIGH = 100;   // ORBmatcher::TH_HIGH, ORBmatcher.cc:36
+
+// What the _cam entries do with their model before the shared body runs: checked as every *_cam entry checks it, the tracker set to it
+// (dvm_tracker_set_camera_model).  *K: fx fy cx cy of the model (the caller's K is not read); *cam: the model for FrameView::mpCamera and
+// dvm_pose_optimize_cam under KannalaBrandt8, NULL under model 0 -- the body is then the plain entry's, bit for bit.
+int use_camera_model(dvm_tracker* t, const dvm_camera_model* model, const float** K, const dvm_camera_model** cam) {
+  if (!t || !model || !dvm_cam::model_ok(model->model, model->p)) return DVM_ERR_INVALID;
+  *cam = model->model == dvm_cam::kKannalaBrandt8 ? model : nullptr;
+  *K = model->p;
+  return dvm_tracker_set_camera_model(t, *cam);
 }
 
-extern "C" int dvmh_track_with_motion_model(dvm_tracker* t, dvm_orb* h, int device, const uint8_t* img, int rows, int cols, int stride, int lap0,
-                                            int lap1, const dvm_se3f* Tcw_pred, const float* K, const float* bounds, const dvm_distortion* dist,
-                                            const float* scale_factors, const float* inv_level_sigma2, int nlevels, int Nl,
-                                            const dvm_keypoint* kps_l, const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps,
-                                            float th, int check_ori, dvm_keypoint* kps, uint8_t* desc, int cap, dvm_keypoint* kps_un,
-                                            int32_t* mp_c, int32_t* dropped, dvmh_track_result* out) {
+// dvmh_track_with_motion_model and _cam: model NULL: the pinhole camera K; else a KannalaBrandt8 model the tracker is set to, K = model->p
+int track_with_motion_model(dvm_tracker* t, dvm_orb* h, int device, const uint8_t* img, int rows, int cols, int stride, int lap0, int lap1,
+                            const dvm_se3f* Tcw_pred, const float* K, const dvm_camera_model* model, const float* bounds, const dvm_distortion* dist,
+                            const float* scale_factors, const float* inv_level_sigma2, int nlevels, int Nl, const dvm_keypoint* kps_l,
+                            const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps, float th, int check_ori, dvm_keypoint* kps,
+                            uint8_t* desc, int cap, dvm_keypoint* kps_un, int32_t* mp_c, int32_t* dropped, dvmh_track_result* out) {
   if (!t || !h || !img || !Tcw_pred || !K || !bounds || !scale_factors || !inv_level_sigma2 || !kps || !desc || !mp_c || !dropped || !out ||
       (Nl && (!kps_l || !mp_l || !mps)))
     return DVM_ERR_INVALID;
@@ -38,6 +48,7 @@ extern "C" int dvmh_track_with_motion_model(dvm_tracker* t, dvm_orb* h, int devi
   FrameView C, L;
   C.N = 0; C.Tcw = *Tcw_pred;
   C.fx = K[0]; C.fy = K[1]; C.cx = K[2]; C.cy = K[3];
+  C.mpCamera = model;            // CurrentFrame.mpCamera->project of LastFrame's points (ORBmatcher.cc:1586), both attempts
   C.mnMinX = bounds[0]; C.mnMaxX = bounds[1]; C.mnMinY = bounds[2]; C.mnMaxY = bounds[3];
   C.mvScaleFactors = scale_factors; C.nLevels = nlevels;
   L = C;
@@ -111,7 +122,8 @@ extern "C" int dvmh_track_with_motion_model(dvm_tracker* t, dvm_orb* h, int devi
     const int32_t ne = (int32_t)kp_of.size();
     std::vector<uint8_t> rej((size_t)ne);
     int32_t inl = 0;
-    rc = dvm_pose_optimize(device, tq.pose_in, Xw.data(), obs.data(), w.data(), &ne, ne, 1, &tq.cam, out->pose, rej.data(), &inl);
+    rc = model ? dvm_pose_optimize_cam(device, tq.pose_in, Xw.data(), obs.data(), w.data(), &ne, ne, 1, model, out->pose, rej.data(), &inl)
+               : dvm_pose_optimize(device, tq.pose_in, Xw.data(), obs.data(), w.data(), &ne, ne, 1, &tq.cam, out->pose, rej.data(), &inl);
     if (rc != DVM_OK) return rc;
     out->n_inliers = inl;
     int left = nm, nmap = 0;
@@ -142,6 +154,30 @@ extern "C" int dvmh_track_with_motion_model(dvm_tracker* t, dvm_orb* h, int devi
   for (int k = 0; k < 4; k++) out->Tcw.q[k] = (float)out->pose[3 + k];
   return DVM_OK;
 }
+}  // namespace
+
+extern "C" int dvmh_track_with_motion_model(dvm_tracker* t, dvm_orb* h, int device, const uint8_t* img, int rows, int cols, int stride, int lap0,
+                                            int lap1, const dvm_se3f* Tcw_pred, const float* K, const float* bounds, const dvm_distortion* dist,
+                                            const float* scale_factors, const float* inv_level_sigma2, int nlevels, int Nl,
+                                            const dvm_keypoint* kps_l, const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps,
+                                            float th, int check_ori, dvm_keypoint* kps, uint8_t* desc, int cap, dvm_keypoint* kps_un,
+                                            int32_t* mp_c, int32_t* dropped, dvmh_track_result* out) {
+  return track_with_motion_model(t, h, device, img, rows, cols, stride, lap0, lap1, Tcw_pred, K, nullptr, bounds, dist, scale_factors, inv_level_sigma2,
+                                 nlevels, Nl, kps_l, mp_l, outlier_l, mps, th, check_ori, kps, desc, cap, kps_un, mp_c, dropped, out);
+}
+extern "C" int dvmh_track_with_motion_model_cam(dvm_tracker* t, dvm_orb* h, int device, const uint8_t* img, int rows, int cols, int stride, int lap0,
+                                                int lap1, const dvm_se3f* Tcw_pred, const float* K, const dvm_camera_model* model, const float* bounds,
+                                                const dvm_distortion* dist, const float* scale_factors, const float* inv_level_sigma2, int nlevels,
+                                                int Nl, const dvm_keypoint* kps_l, const int32_t* mp_l, const uint8_t* outlier_l,
+                                                const dvmh_map_point* mps, float th, int check_ori, dvm_keypoint* kps, uint8_t* desc, int cap,
+                                                dvm_keypoint* kps_un, int32_t* mp_c, int32_t* dropped, dvmh_track_result* out) {
+  (void)K;
+  const float* Km = nullptr; const dvm_camera_model* cam = nullptr;
+  const int rc = use_camera_model(t, model, &Km, &cam);
+  if (rc != DVM_OK) return rc;
+  return track_with_motion_model(t, h, device, img, rows, cols, stride, lap0, lap1, Tcw_pred, Km, cam, bounds, dist, scale_factors, inv_level_sigma2,
+                                 nlevels, Nl, kps_l, mp_l, outlier_l, mps, th, check_ori, kps, desc, cap, kps_un, mp_c, dropped, out);
+}
 
 
 // ---- K agents' frames at one camera tick: dvmh_track_with_motion_model for `count` frames through ONE chain of batched launches
@@ -153,10 +189,11 @@ struct AgentQueries {
   std::vector<uint8_t> q_claims;
   std::vector<float> q_angle, q_pos;
   FrameView C, L;
-  void build(const dvmh_track_in& in, const float* K, const float* bounds, const float* scale_factors, int nlevels, float th) {
+  void build(const dvmh_track_in& in, const float* K, const dvm_camera_model* model, const float* bounds, const float* scale_factors, int nlevels, float th) {
     C = FrameView();
     C.N = 0; C.Tcw = *in.Tcw_pred;
     C.fx = K[0]; C.fy = K[1]; C.cx = K[2]; C.cy = K[3];
+    C.mpCamera = model;
     C.mnMinX = bounds[0]; C.mnMaxX = bounds[1]; C.mnMinY = bounds[2]; C.mnMaxY = bounds[3];
     C.mvScaleFactors = scale_factors; C.nLevels = nlevels;
     L = C;
@@ -240,10 +277,12 @@ class TickPool {
 };
 }  // namespace
 
-extern "C" int dvmh_track_with_motion_model_batch(dvm_tracker* t, dvm_orb* h, int device, int count, const uint8_t* imgs, int rows, int cols, int stride,
-                                                  int64_t frame_stride, int lap0, int lap1, const float* K, const float* bounds, const float* scale_factors,
-                                                  const float* inv_level_sigma2, int nlevels, float th, int check_ori, const dvmh_track_in* in,
-                                                  const dvmh_track_out* outs, dvmh_track_result* res) {
+namespace {
+// dvmh_track_with_motion_model_batch and _cam: model as in track_with_motion_model
+int track_with_motion_model_batch(dvm_tracker* t, dvm_orb* h, int device, int count, const uint8_t* imgs, int rows, int cols, int stride, int64_t frame_stride,
+                                  int lap0, int lap1, const float* K, const dvm_camera_model* model, const float* bounds, const float* scale_factors,
+                                  const float* inv_level_sigma2, int nlevels, float th, int check_ori, const dvmh_track_in* in, const dvmh_track_out* outs,
+                                  dvmh_track_result* res) {
   if (!t || !h || !K || !bounds || !scale_factors || !inv_level_sigma2 || !in || !outs || !res || count < 1) return DVM_ERR_INVALID;
   for (int b = 0; b < count; b++) {
     if (!in[b].Tcw_pred || (in[b].Nl && (!in[b].kps_l || !in[b].mp_l || !in[b].mps)) || !outs[b].kps || !outs[b].desc || !outs[b].mp_c || !outs[b].dropped) return DVM_ERR_INVALID;
@@ -260,7 +299,7 @@ extern "C" int dvmh_track_with_motion_model_batch(dvm_tracker* t, dvm_orb* h, in
   // (persistent workers: spawning eight threads per tick and giving each four agents' queries took 0.45 ms of a 1.6 ms tick of 32 frames --
   //  longer than the extraction it was meant to run under)
   auto build_all = [&](float scale, const std::vector<uint8_t>* only) {
-    TickPool::get().run(count, 24, [&](int b) { if (!only || (*only)[b]) AQ[b].build(in[b], K, bounds, scale_factors, nlevels, scale * th); });
+    TickPool::get().run(count, 24, [&](int b) { if (!only || (*only)[b]) AQ[b].build(in[b], K, model, bounds, scale_factors, nlevels, scale * th); });
   };
   build_all(1.0f, nullptr);
   tp2 = clk::now();
@@ -321,4 +360,25 @@ extern "C" int dvmh_track_with_motion_model_batch(dvm_tracker* t, dvm_orb* h, in
                  ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3), ms(tp3, tp4), ms(tp4, clk::now()));
   }
   return DVM_OK;
+}
+}  // namespace
+
+extern "C" int dvmh_track_with_motion_model_batch(dvm_tracker* t, dvm_orb* h, int device, int count, const uint8_t* imgs, int rows, int cols, int stride,
+                                                  int64_t frame_stride, int lap0, int lap1, const float* K, const float* bounds, const float* scale_factors,
+                                                  const float* inv_level_sigma2, int nlevels, float th, int check_ori, const dvmh_track_in* in,
+                                                  const dvmh_track_out* outs, dvmh_track_result* res) {
+  return track_with_motion_model_batch(t, h, device, count, imgs, rows, cols, stride, frame_stride, lap0, lap1, K, nullptr, bounds, scale_factors,
+                                       inv_level_sigma2, nlevels, th, check_ori, in, outs, res);
+}
+extern "C" int dvmh_track_with_motion_model_batch_cam(dvm_tracker* t, dvm_orb* h, int device, int count, const uint8_t* imgs, int rows, int cols,
+                                                      int stride, int64_t frame_stride, int lap0, int lap1, const float* K,
+                                                      const dvm_camera_model* model, const float* bounds, const float* scale_factors,
+                                                      const float* inv_level_sigma2, int nlevels, float th, int check_ori, const dvmh_track_in* in,
+                                                      const dvmh_track_out* outs, dvmh_track_result* res) {
+  (void)K;
+  const float* Km = nullptr; const dvm_camera_model* cam = nullptr;
+  const int rc = use_camera_model(t, model, &Km, &cam);
+  if (rc != DVM_OK) return rc;
+  return track_with_motion_model_batch(t, h, device, count, imgs, rows, cols, stride, frame_stride, lap0, lap1, Km, cam, bounds, scale_factors,
+                                       inv_level_sigma2, nlevels, th, check_ori, in, outs, res);
 }

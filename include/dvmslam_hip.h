@@ -275,8 +275,9 @@ int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const floa
  * dvm_match_triangulation_cam, dvm_triangulate_matches_cam, dvm_create_new_map_points_cam (and dvmh_search_by_projection_frames_cam,
  * dvmh_triangulation_geometry_cam, dvmh_search_for_triangulation_cam, dvmh_create_new_map_points_cam, include/dvmslam_host.h).  The
  * entries that take the models of TWO keyframes want one model type for both (the parameters may differ per keyframe): a pair of a
- * pinhole and a KannalaBrandt8 keyframe is DVM_ERR_INVALID -- the reference's mixed pair is out of scope.  The pools, the tracked-frame
- * chains, the Fuse / BoW chains, the batched BA windows (dvm_ba_optimize_windows) and OptimizeSim3 are pinhole-only. */
+ * pinhole and a KannalaBrandt8 keyframe is DVM_ERR_INVALID -- the reference's mixed pair is out of scope.  The tracked-frame
+ * chains take the agent's model as state of the tracker (dvm_tracker_set_camera_model below).  The pools (dvm_orb_pool_*, dvm_match_pool_*,
+ * dvm_pose_pool_*), the Fuse / BoW chains, the batched BA windows (dvm_ba_optimize_windows) and OptimizeSim3 are pinhole-only. */
 typedef struct { int32_t model;   /* 0 pinhole, 1 KannalaBrandt8 */
                  float p[8];      /* fx, fy, cx, cy, k1, k2, k3, k4: mvParameters, float as the reference stores them */
 } dvm_camera_model;
@@ -904,6 +905,18 @@ typedef struct {
   uint32_t* ranked;                                /* NULL, or [nq][4] (REPLAY_ON_HOST only) */
 } dvm_track_frame_out;
 int dvm_tracker_create_batch(int device, int max_frames, int max_keypoints, int max_queries, dvm_tracker** out);
+/* The camera of the agent this tracker serves (dvm_camera_model above), for every chain of the tracker: dvm_track_finish[_batch],
+ * dvm_track_local_map[_batch] and dvm_track_reference_keyframe[_batch], forms (a) and (b).  NULL or model 0 -- what a fresh tracker has --
+ * leaves every chain on the cam field of dvm_track_queries / dvm_track_refkf_params, as before.  Model 1 (KannalaBrandt8): isInFrustum's
+ * mpCamera->project and PoseOptimization's edges are evaluated on model->p (csrc/camera_model.h) and the structs' cam fields are not read;
+ * the frames of a batch share the model.  Such a frame has mvKeysUn = mvKeys and a zero mDistCoef: dist with k1 != 0 is then
+ * DVM_ERR_INVALID from dvm_track_finish and from form (a) of dvm_track_reference_keyframe, before anything is queued (the begin stays
+ * valid for a corrected call).  The caller's queries (qx, qy) are projections through the same model (dvmh_track_with_motion_model_cam
+ * builds them so).  An unknown model or a zero focal length: DVM_ERR_INVALID, the tracker keeps the model it had.  May be called at any
+ * time; what a begin or finish prepared before the call is dropped (the second half then returns DVM_ERR_STATE until the next finish): the
+ * second half always runs on the model of the finish that prepared it.  Out of scope: a model per frame of a batch, the stereo /
+ * two-camera fisheye rigs of the reference (its Nleft branches). */
+int dvm_tracker_set_camera_model(dvm_tracker* t, const dvm_camera_model* model);
 int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1);
 /* the same for `count` frames the caller has written into the extractor's page-locked input buffer (dvm_orb_staging): no host copy */
 int dvm_track_begin_staged(dvm_tracker* t, dvm_orb* h, int count, int rows, int cols, int lap0, int lap1);

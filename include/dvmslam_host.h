@@ -124,6 +124,19 @@ int dvmh_track_with_motion_model(dvm_tracker* t, dvm_orb* h, int device, const u
                                  const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps, float th, int check_ori,
                                  dvm_keypoint* kps, uint8_t* desc, int cap, dvm_keypoint* kps_un, int32_t* mp_c, int32_t* dropped,
                                  dvmh_track_result* out);
+/* The same for an agent whose camera is `model` (dvm_camera_model, include/dvmslam_hip.h): the tracker is set to it
+ * (dvm_tracker_set_camera_model -- it stays set for dvm_track_local_map / dvm_track_reference_keyframe behind this call and for later
+ * frames) and LastFrame's points are projected through it (FrameView::mpCamera), on the first attempt and on the doubled window.  Under
+ * KannalaBrandt8 K is not read (may be NULL), kps_un = kps, bounds are 0 .. cols / 0 .. rows and dist must be NULL or have k1 == 0
+ * (DVM_ERR_INVALID otherwise).  Results equal dvm_orb_extract + dvmh_search_by_projection_frames_cam + dvm_pose_optimize_cam + the
+ * outlier drop, bit for bit; model 0 is the call above on model->p[0..3], bit for bit.  A NULL model, a model outside {0, 1} or a zero
+ * focal length returns DVM_ERR_INVALID before anything runs, and the tracker keeps the model it had. */
+int dvmh_track_with_motion_model_cam(dvm_tracker* t, dvm_orb* h, int device, const uint8_t* img, int rows, int cols, int stride, int lap0, int lap1,
+                                     const dvm_se3f* Tcw_pred, const float* K, const dvm_camera_model* model, const float* bounds,
+                                     const dvm_distortion* dist, const float* scale_factors, const float* inv_level_sigma2, int nlevels, int Nl,
+                                     const dvm_keypoint* kps_l, const int32_t* mp_l, const uint8_t* outlier_l, const dvmh_map_point* mps, float th,
+                                     int check_ori, dvm_keypoint* kps, uint8_t* desc, int cap, dvm_keypoint* kps_un, int32_t* mp_c, int32_t* dropped,
+                                     dvmh_track_result* out);
 
 /* The same for `count` frames at once -- the frames of several agents sharing the GPU at one camera tick (dvm_tracker_create_batch with
  * max_frames >= count; an extractor handle with max_batch >= count): ONE chain of batched launches behind ONE synchronisation, the frames'
@@ -144,6 +157,12 @@ int dvmh_track_with_motion_model_batch(dvm_tracker* t, dvm_orb* h, int device, i
                                        int64_t frame_stride, int lap0, int lap1, const float* K, const float* bounds, const float* scale_factors,
                                        const float* inv_level_sigma2, int nlevels, float th, int check_ori, const dvmh_track_in* in,
                                        const dvmh_track_out* outs, dvmh_track_result* res);
+/* dvmh_track_with_motion_model_cam for `count` frames: the agents of a batch share the model, as they share K.  Frame b's outputs equal
+ * dvmh_track_with_motion_model_cam on that frame alone, bit for bit. */
+int dvmh_track_with_motion_model_batch_cam(dvm_tracker* t, dvm_orb* h, int device, int count, const uint8_t* imgs, int rows, int cols, int stride,
+                                           int64_t frame_stride, int lap0, int lap1, const float* K, const dvm_camera_model* model, const float* bounds,
+                                           const float* scale_factors, const float* inv_level_sigma2, int nlevels, float th, int check_ori,
+                                           const dvmh_track_in* in, const dvmh_track_out* outs, dvmh_track_result* res);
 
 /* SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints), :44-205.  claimed_obs[j] != 0 <=> F.mvpMapPoints[j]->Observations() > 0 */
 int dvmh_search_by_projection_points(int device, int N, const dvm_keypoint* kps, const uint8_t* desc, int32_t* mp, const uint8_t* claimed_obs,
