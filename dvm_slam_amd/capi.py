@@ -732,13 +732,23 @@ def ba_optimize_batch(problems, device=0, threads=0, stop_flag=None):
 class BaWindowBatch:
     """K bundle-adjustment windows marshalled ONCE into the dvm_ba_window array of the C ABI (input arrays referenced, output arrays allocated):
     what a C++ agent node holds anyway.  run() is then the bare library call -- the per-call Python work of ba_optimize_windows (~35 us per
-    window) stays out of a timed loop."""
+    window) stays out of a timed loop.  A problem may carry `model` (a CameraModel) instead of, or beside, `intrinsics`: run(fast=True) then
+    is dvm_ba_optimize_windows_fast_cam, with a window that has no model as the pinhole model of its intrinsics (rounded to float)."""
 
     def __init__(self, problems):
         K = len(problems)
         self.K = K
         self.wins = (BaWindow * max(K, 1))()
         self.stats = (BaStats * max(K, 1))()
+        self.models = None      # the dvm_camera_model array, when any window has a model
+        if any(pr.get("model") is not None for pr in problems):
+            self.models = (CameraModel * max(K, 1))()
+            for k, pr in enumerate(problems):
+                m = pr.get("model")
+                if m is None:
+                    m = CameraModel.pinhole(*[float(v) for v in pr["intrinsics"]])
+                assert isinstance(m, CameraModel)
+                self.models[k] = m
         self.keep, self.outs = [], []
         for k, pr in enumerate(problems):
             poses = np.ascontiguousarray(pr["poses"], np.float64); points = np.ascontiguousarray(pr["points"], np.float64)
@@ -749,7 +759,8 @@ class BaWindowBatch:
             w = self.wins[k]
             w.n_poses, w.n_points, w.n_edges, w.iterations = len(poses), len(points), len(edges), int(pr["iterations"])
             w.poses, w.fixed, w.points, w.edges = poses.ctypes.data, fixed.ctypes.data, points.ctypes.data, edges.ctypes.data
-            w.cam = BaCamera(*[float(v) for v in pr["intrinsics"]], float(pr["huber_delta"]))
+            intr = pr["intrinsics"] if pr.get("model") is None else list(pr["model"].p[:4])   # (under a model cam's fx, fy, cx, cy are not what counts)
+            w.cam = BaCamera(*[float(v) for v in intr], float(pr["huber_delta"]))
             w.poses_out, w.points_out, w.edge_chi2_out, w.depth_positive_out = (o["poses"].ctypes.data, o["points"].ctypes.data, o["edge_chi2"].ctypes.data,
                                                                                 o["depth_positive"].ctypes.data)
 
@@ -757,7 +768,13 @@ class BaWindowBatch:
         """One library call over the K windows; returns the per-window dicts (the output arrays are this object's: copy what must outlive the next run).
         collect=False: the bare call -- results() builds the dicts (ctypes slices of the statistics: ~5 us a window) when they are wanted."""
         sf = _p(stop_flag) if stop_flag is not None else None
-        if _batch:
+        if self.models is not None:
+            if _batch or not fast:
+                raise ValueError("a window with a camera model runs through run(fast=True) only: dvm_ba_optimize_windows and dvm_ba_optimize_batch are pinhole-only")
+            f = lib().dvm_ba_optimize_windows_fast_cam
+            f.restype = C.c_int32; f.argtypes = None
+            check(f(C.c_int32(device), self.wins, self.models, C.c_int32(self.K), sf, self.stats))
+        elif _batch:
             f = lib().dvm_ba_optimize_batch
             f.restype = C.c_int32; f.argtypes = None
             check(f(C.c_int32(device), self.wins, C.c_int32(self.K), C.c_int32(_threads), sf, self.stats))
@@ -798,6 +815,11 @@ class BaPool:
     def optimize(self, batch: "BaWindowBatch"):
         """batch: a BaWindowBatch of ONE window (marshalled by the caller's thread).  Returns (result dict, windows in the launch)."""
         n = C.c_int32(0)
+        if batch.models is not None:      # the window has a model: dvm_ba_pool_optimize_cam
+            f = lib().dvm_ba_pool_optimize_cam
+            f.restype = C.c_int32; f.argtypes = None
+            check(f(self.p, batch.wins, batch.models, batch.stats, C.byref(n)))
+            return batch.results()[0], n.value
         f = lib().dvm_ba_pool_optimize
         f.restype = C.c_int32; f.argtypes = None
         check(f(self.p, batch.wins, batch.stats, C.byref(n)))
@@ -806,7 +828,7 @@ class BaPool:
 
 def ba_optimize_windows(problems, device=0, stop_flag=None, _threads=0, _batch=False, fast=False):
     """dvm_ba_optimize_windows: K independent bundle adjustments in one launch.  problems: dicts with poses [P,7], fixed [P], points [L,3],
-    edges (BA_EDGE_DTYPE), intrinsics (fx, fy, cx, cy), huber_delta, iterations.  Returns one dict per window: poses, points, edge_chi2,
+    edges (BA_EDGE_DTYPE), intrinsics (fx, fy, cx, cy) or model (a CameraModel: fast=True only, see BaWindowBatch), huber_delta, iterations.  Returns one dict per window: poses, points, edge_chi2,
     depth_positive, stats (the keys of BundleAdjuster.optimize).  fast=True: dvm_ba_optimize_windows_fast (tree sums in a fixed order)."""
     return BaWindowBatch(problems).run(device, stop_flag, fast, _threads, _batch)
 

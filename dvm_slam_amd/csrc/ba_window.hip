@@ -33,6 +33,8 @@
 // camera-major with structure-of-arrays rows, a cluster of G = 1 / 2 / 4 / 8 workgroups per window separated by agent-scope phase
 // barriers, the reduced system solved in workgroup 0's LDS.  Deterministic, independent of G; equal to the oracle to the general
 // solver's contract (same LM trial sequence, 1e-6), not bit for bit (tests/test_gpu_ba_window_fast.py, tools/soak_r06.py).
+// dvm_ba_optimize_windows_fast_cam / dvm_ba_pool_optimize_cam: the same kernel as a template on the camera (proj_edge.h), a dvm_camera_model
+// per window, one launch per model type present in the call (tests/test_gpu_ba_window_fast_kb8.py).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -116,6 +118,9 @@ struct BaWin {
   double *Sblk, *rhsg;                    // [nblk][36] the blocks of the reduced system as their owner waves leave them, [6 nfree]
   double *cl_part;                        // [4][8] partial sums of the eight fixed parts: chi2, scale terms, max |diag|
   double *cl_ctl;                         // [4] 0: the solve succeeded, 1: the stop word as the leader saw it
+  // ---- k_ba_window_cluster<PoseCamKB8> only: mvParameters of the window's KannalaBrandt8 camera (fx, fy, cx, cy above are not read then).
+  // Behind everything else: no offset the pinhole instantiation reads has moved.
+  float kb8[8];
 };
 
 // ------------------------------------------------------------------------------------------------ the sequential sum
@@ -157,9 +162,13 @@ __device__ double wave_sequential_sum(const double* __restrict__ v, int n, doubl
 // ------------------------------------------------------------------------------------------------ edge pass
 // JAC = false: computeActiveErrors -- chi2 and rho of every edge at the state (poses, pts).  JAC = true: additionally linearizeOplus +
 // the edge's part of constructQuadraticForm: A (2x3), B (2x6), w = rho' Omega, wr = -Omega e rho', W = w B^T A, each into the row its
-// consumer will stream.  CAM: the window's camera (proj_edge.h); the pinhole camera is the only one these kernels are instantiated for.
+// consumer will stream.  CAM: the window's camera (proj_edge.h).  The sequential-order kernel (win_edge_pass) is instantiated for the pinhole
+// camera only -- its promise is g2o's bits, which a float atan2f does not have --, the cluster form (cl_edge_pass) for both.
 template <class CAM> __device__ __forceinline__ CAM win_cam(const BaWin& W);
 template <> __device__ __forceinline__ PoseCamPinhole win_cam<PoseCamPinhole>(const BaWin& W) { return PoseCamPinhole{W.fx, W.fy, W.cx, W.cy}; }
+template <> __device__ __forceinline__ PoseCamKB8 win_cam<PoseCamKB8>(const BaWin& W) {
+  return PoseCamKB8{{W.kb8[0], W.kb8[1], W.kb8[2], W.kb8[3], W.kb8[4], W.kb8[5], W.kb8[6], W.kb8[7]}};
+}
 template <bool JAC, class CAM>
 __device__ void win_edge_pass(const BaWin& W, const double* __restrict__ poses, const double* __restrict__ pts) {
   const CAM cam = win_cam<CAM>(W);
@@ -1185,7 +1194,9 @@ __device__ void cl_t_rows(const BaWin& W, const ClusterCtx& C, double lambda) {
   }
 }
 // the reduced right-hand side and the blocks of the reduced system, each formed completely by ONE wave of the cluster
-__device__ void cl_schur(const BaWin& W, const ClusterCtx& C, double* wred, double lambda) {
+// (inlined by force: with two instantiations of the kernel calling it the inliner would otherwise leave it a function, and a call costs the
+//  kernel the full register file and a stack)
+__device__ __forceinline__ void cl_schur(const BaWin& W, const ClusterCtx& C, double* wred, double lambda) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const size_t Fp = (size_t)W.Fp;
   double* wbuf = wred + wave * 4 * 36;
@@ -1235,6 +1246,8 @@ __device__ void cl_schur(const BaWin& W, const ClusterCtx& C, double* wred, doub
   }
 }
 
+// CAM: the camera of every window of the launch (a call's windows are grouped by model type on the host).  Only the three edge passes name it.
+template <class CAM>
 __global__ void __launch_bounds__(kWinThreads) k_ba_window_cluster(const BaWin* __restrict__ wins, const volatile int* __restrict__ stop, int K, int G) {
   extern __shared__ double lds[];
   constexpr int NT = kWinThreads;
@@ -1292,7 +1305,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window_cluster(const BaWin* 
     //  as the tile solver's loop and k_pose_optimize do -- was measured: 2.92 -> 3.27 ms for 32 windows.  The pass it saves is 15 us, but
     //  two sets of rows are 260 MB for 32 windows and no longer stay in the 256 MB memory-side cache: the accumulation behind it went from
     //  27 to 48 us, the W Dinv pass from 18 to 25.)
-    cl_edge_pass<true, PoseCamPinhole>(W, C, poses, pts);
+    cl_edge_pass<true, CAM>(W, C, poses, pts);
     if (it == 0) cluster_partial_sums(W, C, W.e_rho, W.E, 0, red);
     CL_BARRIER();
     ph = 1;
@@ -1418,7 +1431,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window_cluster(const BaWin* 
       }
       CL_BARRIER();
       ph = 9;
-      cl_edge_pass<false, PoseCamPinhole>(W, C, poses_t, pts_t);
+      cl_edge_pass<false, CAM>(W, C, poses_t, pts_t);
       cluster_partial_sums(W, C, W.e_rho, W.E, 0, red);
       cluster_partial_sums(W, C, W.terms, n + nl, 1, red);
       CL_BARRIER();
@@ -1452,7 +1465,7 @@ __global__ void __launch_bounds__(kWinThreads) k_ba_window_cluster(const BaWin* 
     if (nBad >= 3) { stop_reason = 2; break; }
   }
   if (it_done == 0) {     // no iteration ran: the edges are evaluated at the unchanged input state (see k_ba_window)
-    cl_edge_pass<false, PoseCamPinhole>(W, C, poses, pts);
+    cl_edge_pass<false, CAM>(W, C, poses, pts);
     cluster_partial_sums(W, C, W.e_rho, W.E, 0, red);
     CL_BARRIER();
     chi_last = cluster_total(W, 0);
@@ -1795,12 +1808,52 @@ struct StopWord {                      // a word of page-locked host memory the 
   }
 };
 
+// what build_window refuses, found without building anything: a call of two launches checks ALL its windows before the first launch
+int precheck_window(const dvm_ba_window& w) {
+  const int P = w.n_poses, L = w.n_points, E = w.n_edges;
+  if (P < 0 || L < 0 || E < 0 || (P && (!w.poses || !w.fixed)) || (L && !w.points) || (E && !w.edges)) { set_error("dvm_ba_optimize_windows: null array"); return DVM_ERR_INVALID; }
+  std::vector<uint8_t> pose_used(P, 0);
+  for (int k = 0; k < E; k++) {
+    const dvm_ba_edge& e = w.edges[k];
+    if (e.pose < 0 || e.pose >= P || e.point < 0 || e.point >= L) { set_error("dvm_ba_optimize_windows: edge index out of range"); return DVM_ERR_INVALID; }
+    pose_used[e.pose] = 1;
+  }
+  int nfree = 0;
+  for (int p = 0; p < P; p++) nfree += (!w.fixed[p] && pose_used[p]) ? 1 : 0;
+  if (nfree > kWinMaxFree) { set_error("dvm_ba_optimize_windows: more than 30 free cameras in one window (use dvm_ba_optimize)"); return DVM_ERR_CAPACITY; }
+  return DVM_OK;
+}
+
 }  // namespace
 
-int dvm_ba_optimize_windows_impl(int device, const dvm_ba_window* windows, int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats, bool normalize_input, bool fast, int cluster) {
+// models (the fast form only; NULL: pinhole windows): the camera model of every window.  Model 0: the window's cam.fx, fy, cx, cy, as without
+// models; model 1 (KannalaBrandt8): models[k].p, and cam.huber_delta.  The windows are grouped by model type and each type present runs as ONE
+// launch of its instantiation of k_ba_window_cluster, one after the other on the calling thread's staging stream, G chosen per launch from its
+// own window count: a homogeneous call is one launch, a mixed one two.  A window's result depends neither on its batch nor on G, hence not on
+// the other model types of the call either.
+int dvm_ba_optimize_windows_impl(int device, const dvm_ba_window* windows, int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats, bool normalize_input, bool fast, int cluster,
+                                 const dvm_camera_model* models) {
   if (K < 0 || (K && !windows)) { set_error("dvm_ba_optimize_windows: null windows"); return DVM_ERR_INVALID; }
   if (K == 0) return DVM_OK;
-  int rc = dvm_set_device(device);
+  if (models && !fast) { set_error("dvm_ba_optimize_windows: the sequential-order form is pinhole-only"); return DVM_ERR_INVALID; }
+  int n_kb8 = 0;
+  for (int k = 0; models && k < K; k++) n_kb8 += models[k].model == dvm_cam::kKannalaBrandt8 ? 1 : 0;
+  const bool kb8 = n_kb8 == K;
+  int rc = DVM_OK;
+  if (n_kb8 > 0 && n_kb8 < K) {
+    for (int k = 0; k < K; k++) if ((rc = precheck_window(windows[k])) != DVM_OK) return rc;
+    for (int type = 0; type < 2; type++) {
+      std::vector<int> idx;
+      std::vector<dvm_ba_window> gw;
+      std::vector<dvm_camera_model> gm;
+      for (int k = 0; k < K; k++) if ((models[k].model == dvm_cam::kKannalaBrandt8 ? 1 : 0) == type) { idx.push_back(k); gw.push_back(windows[k]); gm.push_back(models[k]); }
+      std::vector<dvm_ba_stats> gs(idx.size());
+      if ((rc = dvm_ba_optimize_windows_impl(device, gw.data(), (int)idx.size(), stop_flag, stats ? gs.data() : nullptr, normalize_input, true, cluster, gm.data())) != DVM_OK) return rc;
+      for (size_t j = 0; stats && j < idx.size(); j++) stats[idx[j]] = gs[j];
+    }
+    return DVM_OK;
+  }
+  rc = dvm_set_device(device);
   if (rc != DVM_OK) return rc;
   const auto t0 = std::chrono::steady_clock::now();
   // the cluster size: the largest of 8 / 4 / 2 / 1 workgroups per window whose grid (8 * ceil(K / 8) * G workgroups, one per CU: the
@@ -2000,6 +2053,7 @@ int dvm_ba_optimize_windows_impl(int device, const dvm_ba_window* windows, int K
     v.x = st.ptr<double>(s.x); v.terms = st.ptr<double>(s.terms);
     v.stats = st.ptr<dvm_ba_stats>(s.stats);
     v.prof = s.prof >= 0 ? st.ptr<unsigned long long>(s.prof) : nullptr;
+    if (kb8) std::memcpy(v.kb8, models[k].p, sizeof(v.kb8));
     const size_t n = 6 * (size_t)b.nfree;
     lds_doubles = std::max(lds_doubles, n * (n + 1) / 2 + 2 * n + 64 + 256 + (size_t)b.stage_doubles);
   }
@@ -2017,11 +2071,12 @@ int dvm_ba_optimize_windows_impl(int device, const dvm_ba_window* windows, int K
   thread_local KernelEvents kev;     // the launch's duration -> dvm_ba_stats::kernel_us (the fast form's roofline figure in bench_legs.lba_fast)
   if (fast) {
     const int groups = 8 * ((K + 7) / 8);
-    DVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ba_window_cluster), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    const auto kernel = kb8 ? k_ba_window_cluster<PoseCamKB8> : k_ba_window_cluster<PoseCamPinhole>;
+    DVM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     if (!kev.a) { DVM_HIP(hipEventCreate(&kev.a)); DVM_HIP(hipEventCreate(&kev.b)); }
     hipEventRecord(kev.a, st.stream());
     const bool scatter = std::getenv("DVM_BA_CLUSTER_SCATTER") != nullptr;     // (placement test: see the kernel)
-    hipLaunchKernelGGL(k_ba_window_cluster, dim3(groups * G), dim3(kWinThreads), lds_bytes, st.stream(), st.ptr<BaWin>(views_slot), sw.d, scatter ? -K : K, G);
+    hipLaunchKernelGGL(kernel, dim3(groups * G), dim3(kWinThreads), lds_bytes, st.stream(), st.ptr<BaWin>(views_slot), sw.d, scatter ? -K : K, G);
     hipEventRecord(kev.b, st.stream());
   }
   else hipLaunchKernelGGL(k_ba_window, dim3(K), dim3(kWinThreads), lds_bytes, st.stream(), st.ptr<BaWin>(views_slot), sw.d);
@@ -2044,7 +2099,7 @@ int dvm_ba_optimize_windows_impl(int device, const dvm_ba_window* windows, int K
     bool timed_out = std::getenv("DVM_BA_TEST_TIMEOUT") != nullptr;      // (test hook: take the repeat path without a real time-out)
     for (int k = 0; k < K; k++) timed_out = timed_out || sync_back[k][8] != 0u;
     if (timed_out)     // a cluster's workgroups were not all resident (other work held compute units): solve the batch again, one workgroup per window
-      return dvm_ba_optimize_windows_impl(device, windows, K, stop_flag, stats, normalize_input, true, 1);
+      return dvm_ba_optimize_windows_impl(device, windows, K, stop_flag, stats, normalize_input, true, 1, models);
   }
   const auto t2 = std::chrono::steady_clock::now();
   if (want_prof) {
@@ -2108,6 +2163,19 @@ int dvm_ba_optimize_windows_fast(int device, const dvm_ba_window* windows, int K
   }
   return dvm_ba_optimize_windows_impl(device, windows, K, stop_flag, stats, true, true, 0);
 }
+// dvm_ba_optimize_windows_fast with a camera model per window.  A model 0 window becomes the pinhole window of (double)p[0..3]: from there on it
+// IS a window of dvm_ba_optimize_windows_fast.  (DVM_BA_SPLIT is not honoured here.)
+int dvm_ba_optimize_windows_fast_cam(int device, const dvm_ba_window* windows, const dvm_camera_model* models, int K, const volatile uint8_t* stop_flag,
+                                     dvm_ba_stats* stats) {
+  if (K < 0 || (K && (!windows || !models))) { set_error("dvm_ba_optimize_windows_fast_cam: NULL windows or models"); return DVM_ERR_INVALID; }
+  for (int k = 0; k < K; k++)
+    if (!dvm_cam::model_ok(models[k].model, models[k].p)) { set_error("dvm_ba_optimize_windows_fast_cam: unknown model or zero focal length (window " + std::to_string(k) + ")"); return DVM_ERR_INVALID; }
+  if (K == 0) return DVM_OK;
+  std::vector<dvm_ba_window> w(windows, windows + K);
+  for (int k = 0; k < K; k++)
+    if (models[k].model == dvm_cam::kPinhole) { w[k].cam.fx = (double)models[k].p[0]; w[k].cam.fy = (double)models[k].p[1]; w[k].cam.cx = (double)models[k].p[2]; w[k].cam.cy = (double)models[k].p[3]; }
+  return dvm_ba_optimize_windows_impl(device, w.data(), K, stop_flag, stats, true, true, 0, models);
+}
 
 // ---- dvm_ba_pool_*: the LocalBundleAdjustment calls of several agents' LocalMapping threads (one per agent in the reference:
 // LocalMapping.cc:172 -> Optimizer.cc:1030-1387), each a BLOCKING call with its own window, batched behind the boundary into one launch
@@ -2119,6 +2187,7 @@ struct dvm_ba_pool {
   GroupCommit gc;
   std::vector<dvm_ba_window> win[GroupCommit::kLanes];
   std::vector<dvm_ba_stats> st[GroupCommit::kLanes];
+  std::vector<dvm_camera_model> mod[GroupCommit::kLanes];   // the windows' models (model 0 with cam as the window has it: a call without one)
 };
 int dvm_ba_pool_create(int device, int max_batch, int window_us, dvm_ba_pool** out) {
   if (!out || max_batch < 1 || max_batch > 256) return DVM_ERR_INVALID;
@@ -2130,12 +2199,14 @@ int dvm_ba_pool_create(int device, int max_batch, int window_us, dvm_ba_pool** o
   p->device = device;
   p->gc.max_batch = max_batch;
   p->gc.window_us = window_us >= 0 ? window_us : 300;     // a LocalBundleAdjustment call takes milliseconds: 0.3 ms of collecting costs little
-  for (int l = 0; l < GroupCommit::kLanes; l++) { p->win[l].resize((size_t)max_batch); p->st[l].resize((size_t)max_batch); }
+  for (int l = 0; l < GroupCommit::kLanes; l++) { p->win[l].resize((size_t)max_batch); p->st[l].resize((size_t)max_batch); p->mod[l].resize((size_t)max_batch); }
   *out = p;
   return DVM_OK;
 }
 void dvm_ba_pool_destroy(dvm_ba_pool* pool) { delete pool; }
-int dvm_ba_pool_optimize(dvm_ba_pool* pool, const dvm_ba_window* w, dvm_ba_stats* stats, int* batch_size) {
+// one window through the pool; model NULL: the pinhole camera of w->cam.  Calls of every model type collect in the same lane: the batch is one
+// call of the cluster form, which groups its windows by type
+static int ba_pool_optimize(dvm_ba_pool* pool, const dvm_ba_window* w, const dvm_camera_model* model, dvm_ba_stats* stats, int* batch_size) {
   if (!pool || !w) return DVM_ERR_INVALID;
   if (w->n_poses < 1 || w->n_points < 0 || w->n_edges < 0 || w->iterations < 0 || !w->poses || !w->fixed || (w->n_points && !w->points) || (w->n_edges && !w->edges)) {
     set_error("dvm_ba_pool_optimize: the window is incomplete");
@@ -2146,6 +2217,15 @@ int dvm_ba_pool_optimize(dvm_ba_pool* pool, const dvm_ba_window* w, dvm_ba_stats
   int rc = pool->gc.join(key, [](int) { return 0; }, li, slot);
   if (rc != 0) return rc;
   pool->win[li][(size_t)slot] = *w;                       // (the arrays stay the caller's: it is blocked here until the batch is through)
+  dvm_camera_model& sm = pool->mod[li][(size_t)slot];
+  std::memset(&sm, 0, sizeof(sm));
+  if (model) {
+    sm = *model;
+    if (model->model == dvm_cam::kPinhole) {
+      dvm_ba_camera& c = pool->win[li][(size_t)slot].cam;
+      c.fx = (double)model->p[0]; c.fy = (double)model->p[1]; c.cx = (double)model->p[2]; c.cy = (double)model->p[3];
+    }
+  }
   if (pool->gc.arrive(li, slot)) {
     const int count = pool->gc.batch_count(li);
     // the batch runs on the library's helper thread, whichever caller leads it: ONE set of page-locked / device staging buffers and
@@ -2157,7 +2237,11 @@ int dvm_ba_pool_optimize(dvm_ba_pool* pool, const dvm_ba_window* w, dvm_ba_stats
       std::lock_guard<std::mutex> user(H.use);
       H.submit([&] {
         brc = dvm_set_device(pool->device);
-        if (brc == DVM_OK) brc = dvm_ba_optimize_windows_fast(pool->device, pool->win[li].data(), count, nullptr, pool->st[li].data());
+        bool any_kb8 = false;
+        for (int k = 0; k < count; k++) any_kb8 = any_kb8 || pool->mod[li][(size_t)k].model == dvm_cam::kKannalaBrandt8;
+        if (brc == DVM_OK)
+          brc = any_kb8 ? dvm_ba_optimize_windows_impl(pool->device, pool->win[li].data(), count, nullptr, pool->st[li].data(), true, true, 0, pool->mod[li].data())
+                        : dvm_ba_optimize_windows_fast(pool->device, pool->win[li].data(), count, nullptr, pool->st[li].data());
         if (brc != DVM_OK) berr = last_error_cstr();
       });
       H.wait();
@@ -2172,6 +2256,14 @@ int dvm_ba_pool_optimize(dvm_ba_pool* pool, const dvm_ba_window* w, dvm_ba_stats
   pool->gc.finish(li);
   if (rc != DVM_OK) set_error("dvm_ba_pool_optimize: " + err);
   return rc;
+}
+
+int dvm_ba_pool_optimize(dvm_ba_pool* pool, const dvm_ba_window* w, dvm_ba_stats* stats, int* batch_size) {
+  return ba_pool_optimize(pool, w, nullptr, stats, batch_size);
+}
+int dvm_ba_pool_optimize_cam(dvm_ba_pool* pool, const dvm_ba_window* w, const dvm_camera_model* model, dvm_ba_stats* stats, int* batch_size) {
+  if (!model || !dvm_cam::model_ok(model->model, model->p)) { set_error("dvm_ba_pool_optimize_cam: NULL model, unknown model or zero focal length"); return DVM_ERR_INVALID; }
+  return ba_pool_optimize(pool, w, model, stats, batch_size);
 }
 
 int dvm_f64_spec_eval(int device, const double* x, int n, double* out) {

@@ -272,12 +272,13 @@ int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const floa
  * (projectJac, KannalaBrandt8.cpp:144-172) is 0 / 0 on the optical axis: NaN there, as in the reference.  sizeof(dvm_camera_model) == 36.
  * Every *_cam entry returns DVM_ERR_INVALID, before anything runs, for a NULL model, a model outside {0, 1} or a zero focal length.
  * What takes a model: dvm_pose_optimize_cam, dvm_is_in_frustum_cam, dvm_project_search_cam, dvm_ba_set_problem_cam,
- * dvm_match_triangulation_cam, dvm_triangulate_matches_cam, dvm_create_new_map_points_cam (and dvmh_search_by_projection_frames_cam,
+ * dvm_ba_optimize_windows_fast_cam, dvm_ba_pool_optimize_cam, dvm_match_triangulation_cam, dvm_triangulate_matches_cam, dvm_create_new_map_points_cam (and dvmh_search_by_projection_frames_cam,
  * dvmh_triangulation_geometry_cam, dvmh_search_for_triangulation_cam, dvmh_create_new_map_points_cam, include/dvmslam_host.h).  The
  * entries that take the models of TWO keyframes want one model type for both (the parameters may differ per keyframe): a pair of a
  * pinhole and a KannalaBrandt8 keyframe is DVM_ERR_INVALID -- the reference's mixed pair is out of scope.  The tracked-frame
  * chains take the agent's model as state of the tracker (dvm_tracker_set_camera_model below).  The pools (dvm_orb_pool_*, dvm_match_pool_*,
- * dvm_pose_pool_*), the Fuse / BoW chains, the batched BA windows (dvm_ba_optimize_windows) and OptimizeSim3 are pinhole-only. */
+ * dvm_pose_pool_*), the Fuse / BoW chains, the sequential-order BA windows (dvm_ba_optimize_windows), dvm_ba_optimize_batch,
+ * dvm_ba_set_problem_sharded and OptimizeSim3 are pinhole-only. */
 typedef struct { int32_t model;   /* 0 pinhole, 1 KannalaBrandt8 */
                  float p[8];      /* fx, fy, cx, cy, k1, k2, k3, k4: mvParameters, float as the reference stores them */
 } dvm_camera_model;
@@ -694,7 +695,8 @@ int dvm_ba_set_problem(dvm_ba* h, const double* poses, const uint8_t* fixed, int
  *     tests/ba_kb8_scene.py): the LM accept / reject sequence and the stop reason are identical, and poses and landmarks agree within
  *     10 x what the restatement itself moves by when every edge's theta is one float32 ulp off (measured per scene set, docs/NOTEBOOK.md
  *     section 18; never less than 1e-6) -- on scenes whose trial sequence survives that ulp.
- * Pinhole-only as before: dvm_ba_set_problem_sharded, dvm_ba_optimize_windows(_fast), dvm_ba_pool_*, dvm_ba_optimize_batch. */
+ * Pinhole-only as before: dvm_ba_set_problem_sharded, dvm_ba_optimize_windows (the sequential-order form), dvm_ba_optimize_batch.  The
+ * cluster form and the pool take a model per window: dvm_ba_optimize_windows_fast_cam, dvm_ba_pool_optimize_cam below. */
 int dvm_ba_set_problem_cam(dvm_ba* h, const double* poses, const uint8_t* fixed, int P, const double* points, int L,
                            const dvm_ba_edge* edges, int E, const dvm_camera_model* model, double huber_delta);
 /* optimizer.optimize(iterations); stop_flag (may be NULL) is g2o's forceStopFlag: polled between
@@ -808,6 +810,32 @@ typedef struct dvm_ba_pool dvm_ba_pool;
 int dvm_ba_pool_create(int device, int max_batch, int window_us, dvm_ba_pool** out);
 void dvm_ba_pool_destroy(dvm_ba_pool* pool);
 int dvm_ba_pool_optimize(dvm_ba_pool* pool, const dvm_ba_window* w, dvm_ba_stats* stats, int* batch_size);
+/* dvm_ba_optimize_windows_fast with a camera model PER WINDOW (dvm_camera_model above; models: K entries): the LocalBundleAdjustment windows
+ * of a fleet of fisheye agents -- or of a fleet of both kinds -- in one call.  Every EdgeSE3ProjectXYZ of window k takes its error and its
+ * Jacobians from models[k], as under dvm_ba_set_problem_cam.  DVM_ERR_INVALID, before anything runs and before the device is touched, for
+ * NULL models, any model outside {0, 1} or a zero focal length anywhere in the array; no output is written then.
+ *   model 0: the window is the pinhole window of (double)p[0..3] -- what dvm_ba_optimize_windows_fast returns for it with those four
+ *     doubles in cam, BIT FOR BIT, results and LM statistics.
+ *   model 1 (KannalaBrandt8): the window's cam.fx, fy, cx, cy are NOT read; cam.huber_delta is.  theta of the residual is the float atan2f
+ *     of project(Vector3d), the Jacobian's the double atan2, as in the reference; a point on the optical axis has a NaN Jacobian, as in
+ *     the reference.  ACCURACY CONTRACT (tests/test_gpu_ba_window_fast_kb8.py), that of dvm_ba_set_problem_cam: against the float64
+ *     restatement of the recipe the LM accept / reject sequence and the stop reason are identical and poses and landmarks agree within 10 x
+ *     what the restatement itself moves by when every edge's theta is one float32 ulp off (never less than 1e-6); against the tile solver
+ *     (dvm_ba_set_problem_cam + dvm_ba_optimize, the same kb8_project: only the summation order differs) the same sequence, and states as
+ *     close as the two pinhole forms are to each other.
+ * The windows are grouped by model type; each type present runs as one launch of its instantiation of the kernel, one after the other: a
+ * homogeneous fleet is ONE launch, a mixed call two.  G is chosen per launch from that launch's window count; the G = 1 repeat after a barrier
+ * time-out applies per launch.  A window's result depends neither on its batch, nor on G, nor on the other model types of the call.
+ * Limits as for dvm_ba_optimize_windows_fast: more than 30 free cameras in a window is DVM_ERR_CAPACITY, returned before anything runs -- for a
+ * fisheye agent the way out is dvm_ba_set_problem_cam + dvm_ba_optimize (dvm_ba_optimize_batch is pinhole-only).  DVM_BA_SPLIT is NOT honoured
+ * by this entry: it is always the one launch per model type.  The sequential-order dvm_ba_optimize_windows stays pinhole-only: its promise
+ * is g2o's bits, and that promise does not exist under a float atan2f (see dvm_ba_set_problem_cam).
+ * dvm_ba_pool_optimize_cam: dvm_ba_pool_optimize for one window and its model.  Calls of different model types -- and dvm_ba_pool_optimize
+ * calls -- that arrive within one commit window ride in the same call; every caller gets the bits of a solo
+ * dvm_ba_optimize_windows_fast_cam call.  batch_size: how many windows the call held, over all model types. */
+int dvm_ba_optimize_windows_fast_cam(int device, const dvm_ba_window* windows, const dvm_camera_model* models /* [K] */, int K,
+                                     const volatile uint8_t* stop_flag, dvm_ba_stats* stats);
+int dvm_ba_pool_optimize_cam(dvm_ba_pool* pool, const dvm_ba_window* w, const dvm_camera_model* model, dvm_ba_stats* stats, int* batch_size);
 /* The same K independent problems solved CONCURRENTLY on the general solver: up to `threads` (<= 0: 4) host threads of this call each
  * drive one solver handle from a process-wide pool and pull windows from a shared counter, so that the launch chains of different
  * windows interleave on the device (one window alone leaves it mostly idle).  Window k gets exactly what dvm_ba_set_problem +
