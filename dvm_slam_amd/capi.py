@@ -1530,6 +1530,292 @@ class LocalMapOut(C.Structure):
     _fields_ = [("mp_out", C.c_void_p), ("outlier", C.c_void_p), ("track_pts", C.c_void_p)]
 
 
+# ---- an agent's map points resident on the device (dvm_map_store, include/dvmslam_hip.h) and the two tracked-frame halves reading them
+class MapStore:
+    """dvm_map_store: `capacity` slots of LOCAL_POINT_DTYPE records in device memory.  update() writes records to slots (asynchronous; every
+    later call that reads the store sees it), read() returns slots.  Calls on one store are not concurrent."""
+
+    def __init__(self, capacity, device=0):
+        self.L = lib()
+        self.h = C.c_void_p()
+        f = self.L.dvm_map_store_create
+        f.restype = C.c_int32; f.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
+        check(f(int(device), int(capacity), C.byref(self.h)))
+
+    @property
+    def capacity(self):
+        f = self.L.dvm_map_store_capacity
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p]
+        return f(self.h)
+
+    def update(self, slots, records):
+        slots = np.ascontiguousarray(slots, np.int32); records = np.ascontiguousarray(records, LOCAL_POINT_DTYPE)
+        assert slots.ndim == 1 and slots.shape == records.shape
+        f = self.L.dvm_map_store_update
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        check(f(self.h, len(slots), _p(slots), _p(records)))
+
+    def read(self, slots):
+        slots = np.ascontiguousarray(slots, np.int32)
+        out = np.zeros(len(slots), LOCAL_POINT_DTYPE)
+        f = self.L.dvm_map_store_read
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        check(f(self.h, len(slots), _p(slots), _p(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            f = self.L.dvm_map_store_destroy
+            f.restype = None; f.argtypes = [C.c_void_p]
+            f(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+
+class TrackLast(C.Structure):
+    """dvm_track_last (include/dvmslam_hip.h)"""
+    _fields_ = [("store", C.c_void_p), ("n", C.c_int32), ("slot", C.c_void_p), ("octave", C.c_void_p), ("angle", C.c_void_p),
+                ("Tcw_pred", C.c_float * 7), ("th", C.c_float)]
+
+
+class TrackShared(C.Structure):
+    """dvm_track_shared (include/dvmslam_hip.h)"""
+    _fields_ = [("bounds", C.c_float * 4), ("dist", C.c_void_p), ("scale_factors", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("nlevels", C.c_int32),
+                ("cam", BaCamera), ("th_high", C.c_int32), ("check_ori", C.c_int32), ("min_matches", C.c_int32)]
+
+
+class LocalMapInResident(C.Structure):
+    """dvm_local_map_in_resident (include/dvmslam_hip.h)"""
+    _fields_ = [("store", C.c_void_p), ("slots", C.c_void_p), ("n", C.c_int32), ("frame_mp", C.c_void_p), ("th", C.c_float), ("far_points", C.c_int32),
+                ("th_far", C.c_float)]
+
+
+def entry_lists(kps_l, mp_l, outlier_l=None):
+    """LastFrame's entry lists as dvm_track_last takes them: the keypoints that hold a map point and are no outliers, in keypoint order.
+    Returns (idx, slot, octave, angle): idx = the keypoint of every entry, slot = mp_l[idx]."""
+    kps_l = np.ascontiguousarray(kps_l, KP_DTYPE); mp_l = np.ascontiguousarray(mp_l, np.int32)
+    keep = mp_l >= 0
+    if outlier_l is not None:
+        keep &= np.asarray(outlier_l) == 0
+    idx = np.nonzero(keep)[0].astype(np.int32)
+    return idx, mp_l[idx].copy(), kps_l["octave"][idx].astype(np.uint8), kps_l["angle"][idx].astype(np.float32)
+
+
+def _track_shared(K, bounds, scale_factors, inv_sigma2, check_ori=True, th_high=100, min_matches=20):
+    sf = np.ascontiguousarray(scale_factors, np.float32); s2 = np.ascontiguousarray(inv_sigma2, np.float32)
+    sh = TrackShared()
+    sh.bounds[:] = [float(v) for v in np.asarray(bounds, np.float32)]
+    sh.dist = None; sh.scale_factors = sf.ctypes.data; sh.inv_level_sigma2 = s2.ctypes.data; sh.nlevels = len(sf)
+    if K is not None:
+        sh.cam.fx, sh.cam.fy, sh.cam.cx, sh.cam.cy = [float(v) for v in np.asarray(K, np.float32)[:4]]
+    sh.th_high, sh.check_ori, sh.min_matches = int(th_high), int(bool(check_ori)), int(min_matches)
+    return sh, (sf, s2)
+
+
+def _track_lasts(lasts):
+    """lasts: per frame a dict(store (MapStore or None), slot, octave, angle, Tcw_pred (7 floats: q, t), th)"""
+    arr = (TrackLast * len(lasts))()
+    keep = []
+    for b, d in enumerate(lasts):
+        slot = np.ascontiguousarray(d["slot"], np.int32); octv = np.ascontiguousarray(d["octave"], np.uint8); ang = np.ascontiguousarray(d["angle"], np.float32)
+        assert len(slot) == len(octv) == len(ang)
+        keep.append((slot, octv, ang, d.get("store")))
+        a = arr[b]
+        a.store = None if d.get("store") is None else d["store"].h
+        a.n = len(slot); a.slot = slot.ctypes.data; a.octave = octv.ctypes.data; a.angle = ang.ctypes.data
+        a.Tcw_pred[:] = [float(v) for v in np.asarray(d["Tcw_pred"], np.float32)]
+        a.th = float(d.get("th", 15.0))
+    return arr, keep
+
+
+def build_frame_queries_host(last, K, bounds, scale_factors, records, model=None):
+    """dvmh_build_frame_queries: the host's loop header of SearchByProjection(CurrentFrame, LastFrame) on one frame's entry lists, the map
+    points given as `records` (LOCAL_POINT_DTYPE, indexed by last['slot']).  last: a dict as Tracker.debug_build_queries takes it (its
+    store is not read).  Returns a dict: nq, q_entry, qx, qy, qr, qmin, qmax, q_claims, q_angle, q_pos [nq, 3], qdesc [nq, 32]."""
+    H = host_lib()
+    slot = np.ascontiguousarray(last["slot"], np.int32); octv = np.ascontiguousarray(last["octave"], np.uint8); ang = np.ascontiguousarray(last["angle"], np.float32)
+    records = np.ascontiguousarray(records, LOCAL_POINT_DTYPE)
+    T = np.ascontiguousarray(last["Tcw_pred"], np.float32); b4 = np.ascontiguousarray(bounds, np.float32); sf = np.ascontiguousarray(scale_factors, np.float32)
+    K4 = None if K is None else np.ascontiguousarray(K, np.float32)
+    n = len(slot); m = max(n, 1)
+    o = dict(q_entry=np.zeros(m, np.int32), qx=np.zeros(m, np.float32), qy=np.zeros(m, np.float32), qr=np.zeros(m, np.float32), qmin=np.zeros(m, np.int32),
+             qmax=np.zeros(m, np.int32), q_claims=np.zeros(m, np.uint8), q_angle=np.zeros(m, np.float32), q_pos=np.zeros((m, 3), np.float32),
+             qdesc=np.zeros((m, 32), np.uint8))
+    fn = H.dvmh_build_frame_queries
+    fn.restype = C.c_int32; fn.argtypes = None
+    nq = fn(_p(T), None if K4 is None else _p(K4), None if model is None else C.byref(model), _p(b4), _p(sf), C.c_int32(len(sf)), C.c_int32(n), _p(slot),
+            _p(records), _p(octv), _p(ang), C.c_float(float(last.get("th", 15.0))), *[_p(o[k]) for k in ("q_entry", "qx", "qy", "qr", "qmin", "qmax", "q_claims",
+                                                                                                        "q_angle", "q_pos", "qdesc")])
+    if nq < 0:
+        check(nq)
+    out = {k: v[:nq] for k, v in o.items()}
+    out["nq"] = nq
+    return out
+
+
+def _debug_build_queries(trk, lasts, K, bounds, scale_factors, inv_sigma2):
+    count = len(lasts)
+    arr, keep = _track_lasts(lasts)
+    sh, keep2 = _track_shared(K, bounds, scale_factors, inv_sigma2)
+    stride = max(64, (max(len(k[0]) for k in keep) + 63) & ~63)
+    Qn = count * stride
+    nq = np.zeros(count, np.int32)
+    o = dict(q_entry=np.zeros(Qn, np.int32), qx=np.zeros(Qn, np.float32), qy=np.zeros(Qn, np.float32), qr=np.zeros(Qn, np.float32), qmin=np.zeros(Qn, np.int32),
+             qmax=np.zeros(Qn, np.int32), q_claims=np.zeros(Qn, np.uint8), q_angle=np.zeros(Qn, np.float32), q_pos=np.zeros((Qn, 3), np.float32),
+             qdesc=np.zeros((Qn, 32), np.uint8))
+    got = C.c_int32(0)
+    f = trk.L.dvm_track_debug_build_queries
+    f.restype = C.c_int32; f.argtypes = None
+    check(f(trk.t, C.c_int32(count), arr, C.byref(sh), _p(nq), *[_p(o[k]) for k in ("q_entry", "qx", "qy", "qr", "qmin", "qmax", "q_claims", "q_angle", "q_pos",
+                                                                                     "qdesc")], C.byref(got)))
+    assert got.value == stride, (got.value, stride)
+    out = []
+    for b in range(count):
+        d = {k: v[b * stride:b * stride + nq[b]].copy() for k, v in o.items()}
+        d["nq"] = int(nq[b])
+        out.append(d)
+    return out
+
+
+def _last_upload_bytes(trk):
+    a, b = C.c_int64(0), C.c_int64(0)
+    f = trk.L.dvm_tracker_last_upload_bytes
+    f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    check(f(trk.t, C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def _track_resident(trk, imgs, ins, outs, res, K, bounds, scale_factors, inv_sigma2, th, check_ori, lap):
+    imgs = np.ascontiguousarray(imgs, np.uint8)
+    count = imgs.shape[0]
+    f4 = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (K, bounds, scale_factors, inv_sigma2)]
+    fn = trk.H.dvmh_track_with_motion_model_batch_resident
+    fn.restype = C.c_int32; fn.argtypes = None
+    vp = C.c_void_p
+    check(fn(trk.t, trk.ext.h, C.c_int32(trk.device), C.c_int32(count), vp(imgs.ctypes.data), C.c_int32(imgs.shape[1]), C.c_int32(imgs.shape[2]),
+             C.c_int32(imgs.strides[1]), C.c_int64(imgs.strides[0]), C.c_int32(lap[0]), C.c_int32(lap[1]), None if f4[0] is None else _p(f4[0]), _p(f4[1]),
+             _p(f4[2]), _p(f4[3]), C.c_int32(len(f4[2])), C.c_float(float(th)), C.c_int32(int(check_ori)), ins[0] if isinstance(ins, tuple) else ins, outs, res))
+    return count
+
+
+def _prepare_resident(Tcw_preds, lasts):
+    """lasts: per agent (kps_l, mp_l as store slots, outlier_l or None, MapStore).  Returns the marshalled dvmh_track_in_resident array."""
+    n = len(lasts)
+    ins = (TrackIn * n)()      # dvmh_track_in_resident has dvmh_track_in's layout: the store's handle where mps was
+    keep = []
+    for b, (T, (kl, ml, ol, store)) in enumerate(zip(Tcw_preds, lasts)):
+        T = np.ascontiguousarray(T, np.float32); kl = np.ascontiguousarray(kl, KP_DTYPE); ml = np.ascontiguousarray(ml, np.int32)
+        ol = None if ol is None else np.ascontiguousarray(ol, np.uint8)
+        keep.append((T, kl, ml, ol, store))
+        i = ins[b]
+        i.Tcw_pred, i.Nl, i.kps_l, i.mp_l, i.outlier_l, i.mps = T.ctypes.data, len(kl), kl.ctypes.data, ml.ctypes.data, None if ol is None else ol.ctypes.data, store.h
+    return ins, keep
+
+
+def _track_local_map_resident(trk, stores, slot_lists, frame_mps, th, far_points, th_far, want_track_points):
+    count = len(slot_lists)
+    per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * count
+    ths, fars, thfs = per(th), per(far_points), per(th_far)
+    assert len(stores) == count and len(frame_mps) == count and len(ths) == count and len(fars) == count and len(thfs) == count
+    ins = (LocalMapInResident * count)(); outs = (LocalMapOut * count)(); res = (TrackLocalResult * count)(); status = np.zeros(count, np.int32)
+    keep = []
+    for b in range(count):
+        sl = np.ascontiguousarray(slot_lists[b], np.int32); fm = np.ascontiguousarray(frame_mps[b], np.int32)
+        mp = np.full(max(len(fm), 1), -1, np.int32); outl = np.zeros(max(len(fm), 1), np.uint8)
+        tp = np.zeros(max(len(sl), 1), TRACK_DTYPE) if want_track_points else None
+        keep.append((sl, fm, mp, outl, tp))
+        ins[b].store = None if stores[b] is None else stores[b].h
+        ins[b].slots, ins[b].n, ins[b].frame_mp = (sl.ctypes.data if len(sl) else None), len(sl), fm.ctypes.data
+        ins[b].th, ins[b].far_points, ins[b].th_far = float(ths[b]), int(bool(fars[b])), float(thfs[b])
+        outs[b].mp_out, outs[b].outlier, outs[b].track_pts = mp.ctypes.data, outl.ctypes.data, None if tp is None else tp.ctypes.data
+    f = trk.L.dvm_track_local_map_batch_resident
+    f.restype = C.c_int32
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    check(f(trk.t, trk.ext.h, count, ins, outs, res, _p(status)))
+    out = []
+    for b in range(count):
+        r = res[b]
+        d = {k: getattr(r, k) for k in ("n_to_match", "nmatches", "n_requeried", "n_cleared_bad", "n_edges", "n_inliers", "matches_inliers")}
+        d["status"] = int(status[b])
+        if status[b] == 0:
+            sl, fm, mp, outl, tp = keep[b]
+            d.update(mp=mp[:len(fm)], outlier=outl[:len(fm)], pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
+            if want_track_points:
+                d["track_pts"] = tp[:len(sl)]
+        out.append(d)
+    return out
+
+
+_TRACK_COUNTERS = ("n", "mono_index", "nmatches", "nmatches_search", "nmatches_map", "n_inliers", "wide_window", "replayed_on_host", "tracked", "n_requeried")
+
+
+def _tracker_track_resident(self, img, Tcw_pred, K, bounds, scale_factors, inv_sigma2, kps_l, mp_l, outlier_l, store, th=15.0, check_ori=True, lap=(0, 1000)):
+    """dvmh_track_with_motion_model_batch_resident for one frame: Tracker.track with LastFrame's map points given as slots of `store` (a
+    MapStore) in mp_l.  Under a camera model set with set_camera_model K may be None.  Returns what track() returns, mp / dropped as slots."""
+    img = np.ascontiguousarray(img, np.uint8)
+    cap = self.ext.cap
+    kps = np.empty(cap, KP_DTYPE); kun = np.empty(cap, KP_DTYPE); desc = np.empty((cap, 32), np.uint8)
+    mp = np.empty(cap, np.int32); dropped = np.empty(cap, np.int32)
+    ins, keep = _prepare_resident([Tcw_pred], [(kps_l, mp_l, outlier_l, store)])
+    outs = (TrackOut * 1)(); res = (TrackResult * 1)()
+    o = outs[0]
+    o.kps, o.desc, o.cap, o.kps_un, o.mp_c, o.dropped = kps.ctypes.data, desc.ctypes.data, cap, kun.ctypes.data, mp.ctypes.data, dropped.ctypes.data
+    _track_resident(self, img[None], ins, outs, res, K, bounds, scale_factors, inv_sigma2, th, check_ori, lap)
+    r = res[0]
+    n = r.n
+    out = {k: getattr(r, k) for k in _TRACK_COUNTERS}
+    out.update(kps=kps[:n], kps_un=kun[:n], desc=desc[:n], mp=mp[:n], dropped=dropped[:n], pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
+    return out
+
+
+def _tracker_track_local_map_resident(self, store, slots, frame_mp, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
+    """dvm_track_local_map_batch_resident for the one frame of the last track() / track_resident(): Tracker.track_local_map with the local map
+    given as slots of `store`.  Returns what track_local_map returns plus status."""
+    return _track_local_map_resident(self, [store], [slots], [frame_mp], th, far_points, th_far, want_track_points)[0]
+
+
+def _batch_track_resident(self, imgs, ins, K, bounds, scale_factors, inv_sigma2, th=15.0, check_ori=True, lap=(0, 1000)):
+    """dvmh_track_with_motion_model_batch_resident: TrackerBatch.track with every agent's map points in a MapStore.  ins: prepare_resident()'s
+    array.  Returns one dict per frame as track() does, mp / dropped as store slots."""
+    count = _track_resident(self, imgs, ins, self.outs, self.res, K, bounds, scale_factors, inv_sigma2, th, check_ori, lap)
+    out = []
+    for b in range(count):
+        r = self.res[b]
+        n = r.n
+        d = {k: getattr(r, k) for k in _TRACK_COUNTERS}
+        d.update(kps=self.kps[b, :n], kps_un=self.kun[b, :n], desc=self.desc[b, :n], mp=self.mp[b, :n], dropped=self.dropped[b, :n],
+                 pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
+        out.append(d)
+    return out
+
+
+def _batch_track_local_map_resident(self, stores, slot_lists, frame_mps, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
+    """dvm_track_local_map_batch_resident: TrackerBatch.track_local_map with every frame's table given as slots of its MapStore."""
+    return _track_local_map_resident(self, stores, slot_lists, frame_mps, th, far_points, th_far, want_track_points)
+
+
+def _debug_build_queries_method(self, lasts, K, bounds, scale_factors, inv_sigma2):
+    """dvm_track_debug_build_queries: k_track_queries alone.  lasts: per frame a dict(store, slot, octave, angle, Tcw_pred (7 floats: q, t),
+    th).  Returns one dict per frame: nq, q_entry, qx, qy, qr, qmin, qmax, q_claims, q_angle, q_pos, qdesc."""
+    return _debug_build_queries(self, lasts, K, bounds, scale_factors, inv_sigma2)
+
+
+def _last_upload_bytes_method(self):
+    """dvm_tracker_last_upload_bytes: (first half, second half) host-to-device bytes of the last finish and the last local-map call."""
+    return _last_upload_bytes(self)
+
+
+Tracker.track_resident = _tracker_track_resident
+Tracker.track_local_map_resident = _tracker_track_local_map_resident
+TrackerBatch.prepare_resident = staticmethod(_prepare_resident)
+TrackerBatch.track_resident = _batch_track_resident
+TrackerBatch.track_local_map_resident = _batch_track_local_map_resident
+for _cls in (Tracker, TrackerBatch):
+    _cls.debug_build_queries = _debug_build_queries_method
+    _cls.last_upload_bytes = _last_upload_bytes_method
+
+
 TRACKED_POINT_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
                                 ("in_view", "u1"), ("bad", "u1"), ("pad", "u1", (2,)), ("desc", "u1", (32,)), ("n_obs", "<i4")])
 

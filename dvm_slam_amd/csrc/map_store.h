@@ -1,0 +1,30 @@
+// dvm_slam_amd/csrc/map_store.h -- dvm_map_store as the chains see it (map_store.cpp), and the launchers of map_store_kernels.hip.
+//
+// A chain that reads stores checks every slot on the host (store_slots_ok), then brackets the kernels that read them:
+//   store_read_begin(st, s)   s waits for the store's last queued update
+//   ... the reading kernels on s ...
+//   store_read_end(st, s)     the store's next update waits for what s holds so far
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/dvmslam_hip.h"
+#include "track_kernels.h"   // LocalPointPod == dvm_local_point
+
+namespace dvm {
+const LocalPointPod* store_records(const dvm_map_store* st);   // device, [capacity]
+int store_device(const dvm_map_store* st);
+// every one of slots[0 .. n) lies in [0, capacity) and has been written
+bool store_slots_ok(const dvm_map_store* st, const int32_t* slots, int n);
+int store_read_begin(const dvm_map_store* st, hipStream_t s);
+int store_read_end(const dvm_map_store* st, hipStream_t s);
+
+// dst[slots[k]] = src[k], k < n (the host checked the slots: in range, each once)
+void launch_store_scatter(hipStream_t s, LocalPointPod* dst, const int32_t* slots, const LocalPointPod* src, int n);
+// one table: dst[k] = src[slots[k]], k < n
+void launch_store_read(hipStream_t s, const LocalPointPod* src, const int32_t* slots, LocalPointPod* dst, int n);
+// the tables of a dvm_track_local_map_batch_resident call: frame b's n[b] records from stores[b] by slots[qoff[b] + k] to dst[qoff[b] + k];
+// span_max: the largest table, rounded up to 64
+struct StoreGather { const LocalPointPod* const* stores; const LocalFrameArgs* per_frame; const int32_t* qoff; const int32_t* slots; };
+void launch_store_gather(hipStream_t s, const StoreGather& G, LocalPointPod* dst, int count, int span_max);
+}  // namespace dvm

@@ -15,6 +15,10 @@
 // candidates were all taken by earlier queries (the list may go on: the caller replays the epilogue from the ranked lists on the host).
 // The second half (dvm_track_local_map, dvm_track_reference_keyframe) runs as the batch of one frame: the single calls keep their own
 // checks and run the chains of dvm_track_local_map_batch / dvm_track_reference_keyframe_batch.
+// Both halves also read an agent's map points where they live on the device (dvm_map_store, map_store.cpp): dvm_track_finish_batch_resident
+// takes LastFrame's entry lists (slot, octave, angle: 9 B per entry) and k_track_queries builds the query block from the store, beside the
+// extraction; dvm_track_local_map_batch_resident takes the tables as slot lists and k_store_gather fills the chain's device table.  Every
+// slot is checked on the host against its store before anything is queued.  Behind the query block / the table the chains are the same.
 // Every reservation here is a WorkingSet carved by a Cursor<256> (chain.h, shared with the other chains): items start at multiples of 256 bytes.
 #include <algorithm>
 #include <chrono>
@@ -34,6 +38,7 @@
 #include "match_kernels.h"
 #include "orb_pipeline.h"
 #include "host_stage.h"   // HostPool
+#include "map_store.h"
 #include "track_kernels.h"
 
 using namespace dvm;
@@ -91,6 +96,10 @@ struct dvm_tracker {
   int begun = 0;                   // frames of the batch whose extraction is queued
   dvm_camera_model model{};        // dvm_tracker_set_camera_model: 0 (a fresh tracker): the cam of the query / parameter structs; 1: KannalaBrandt8 on model.p
   int rows = 0, cols = 0;
+  // ---- the resident first half (dvm_track_finish_batch_resident): the entry lists go up through rw, k_track_queries writes d_q
+  WorkingSet rw;                   // device: the upload copy; mapped: [upload staging][q_entry: max_frames x q_rcap][nq: max_frames]
+  int32_t *r_entry = nullptr, *r_nq = nullptr;   // mapped: the entry number of every query, the frames' query counts
+  int64_t up_first = 0, up_second = 0;           // dvm_tracker_last_upload_bytes: what the last finish / local-map call copied up
   // ---- the second half (dvm_track_local_map[_batch]): working set of dvm_tracker_reserve_local_map, and what the last finish left for it
   int lm_cap = 0;                  // table entries reserved (a multiple of 64; a batch: all frames' tables, each rounded up to 64)
   WorkingSet lmw;                  // device: [upload][per-entry arrays][query arrays][ranked lists][counters]; mapped: [upload staging][results]
@@ -169,6 +178,14 @@ int dvm_tracker_create_batch(int device, int max_frames, int max_keypoints, int 
   m.assign = c.carve<int32_t>(B * K); m.outlier = c.carve<uint8_t>(B * K);
   m.res = c.carve<int32_t>(B * 8); m.fin = c.carve<int32_t>(B * 4); m.nedges = c.carve<int32_t>(B); m.pose_out = c.carve<double>(B * 7);
   m.n_inl = c.carve<int32_t>(B); m.kps_un = c.carve<dvm_keypoint_pod>(K);
+  {   // the resident first half: 9 bytes per entry (every frame's list rounded up to 64), two level tables, a record per frame
+    const size_t rup = pad<256>(2 * 256 + pad<64>(B * sizeof(ResidentFrame)) + B * Q * 9);
+    if (const char* what = t->rw.alloc(rup, rup + pad<256>(B * Q * 4) + pad<256>(B * 4), rup, /*mapped*/ true, /*zeroed*/ true)) {
+      dvm_tracker_destroy(t); set_error(std::string("dvm_tracker_create: ") + what); return DVM_ERR_HIP;
+    }
+    Cursor256 rc2{t->rw.hm + rup};
+    t->r_entry = rc2.carve<int32_t>(B * Q); t->r_nq = rc2.carve<int32_t>(B);
+  }
   if (hipStreamCreateWithFlags(&t->cstream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&t->cev, hipEventDisableTiming) != hipSuccess) {
     dvm_tracker_destroy(t); set_error("dvm_tracker_create: query block"); return DVM_ERR_HIP;
@@ -187,7 +204,7 @@ void dvm_tracker_destroy(dvm_tracker* t) {
   t->lmw.free(); t->rk.ws.free(); t->rkb.ws.free();
   if (t->cev) hipEventDestroy(t->cev);
   if (t->cstream) hipStreamDestroy(t->cstream);
-  t->ws.free();
+  t->ws.free(); t->rw.free();
   delete t;
 }
 
@@ -224,18 +241,113 @@ int dvm_track_begin(dvm_tracker* t, dvm_orb* h, const uint8_t* img, int rows, in
   return dvm_track_begin_batch(t, h, img, 1, rows, cols, stride, (int64_t)rows * stride, lap0, lap1);
 }
 
-int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* qs, const dvm_track_frame_out* outs, dvm_track_result* res) {
-  if (!t || !h || !qs || !outs || !res || count < 1) return DVM_ERR_INVALID;
+namespace {
+// what the frames of a finish share: the fields of dvm_track_queries that are not per query (qs[0]'s), or dvm_track_shared
+struct FinishShared {
+  float bounds[4]; const dvm_distortion* dist; const float* inv_level_sigma2; int nlevels; dvm_ba_camera cam; int th_high, check_ori, min_matches;
+};
+// the upload block of a resident finish, carved in the mapped staging buffer of t->rw and at the same offsets in its device copy:
+// [mvScaleFactors 64][mvInvLevelSigma2 64][frames][slot, angle, octave: E entries each, frame b's at ResidentFrame::off -- every frame's
+// list rounded up to 64 entries, back to back] -- 9 bytes per entry
+struct ResidentUpload { float *scale, *inv_sigma2; ResidentFrame* fr; int32_t* slot; float* angle; uint8_t* octave; size_t bytes; };
+ResidentUpload carve_resident_upload(uint8_t* base, int count, size_t E) {
+  ResidentUpload u;
+  Cursor<64> c{base};
+  u.scale = c.carve<float>(64); u.inv_sigma2 = c.carve<float>(64); u.fr = c.carve<ResidentFrame>((size_t)count);
+  u.slot = c.carve<int32_t>(E); u.angle = c.carve<float>(E); u.octave = c.carve<uint8_t>(E);
+  u.bytes = c.used();
+  return u;
+}
+// the tracker's query block of a call of `count` frames at stride Qs, carved in the mapped buffer (t->qdev: the same item of d_q)
+size_t carve_query_block(dvm_tracker* t, int count, int Qs) {
+  auto& m = t->m;
+  Cursor256 c{t->ws.hm};
+  const size_t Qn = (size_t)count * Qs;
+  m.qdesc = c.carve<uint8_t>(Qn * 32); m.qx = c.carve<float>(Qn); m.qy = c.carve<float>(Qn); m.qr = c.carve<float>(Qn);
+  m.qmin = c.carve<int32_t>(Qn); m.qmax = c.carve<int32_t>(Qn); m.q_claims = c.carve<uint8_t>(Qn); m.q_angle = c.carve<float>(Qn);
+  m.q_pos = c.carve<float>(Qn * 3); m.pose_in = c.carve<double>((size_t)count * 7); m.nq_arr = c.carve<int32_t>(count); m.inv_sigma2 = c.carve<float>(64);
+  return c.used();
+}
+// the checks of a resident call on its entry lists and shared parameters, before anything is queued; *n_max: the largest entry count
+int resident_check(const char* fn, const dvm_tracker* t, int count, const dvm_track_last* last, const dvm_track_shared* p, int* n_max) {
+  const std::string who(fn);
+  if (p->nlevels < 1 || p->nlevels > 64 || !p->inv_level_sigma2 || !p->scale_factors) { set_error(who + ": bad shared parameters"); return DVM_ERR_INVALID; }
+  *n_max = 0;
+  for (int b = 0; b < count; b++) {
+    const dvm_track_last& L = last[b];
+    if (L.n < 0 || (L.n && (!L.store || !L.slot || !L.octave || !L.angle))) return DVM_ERR_INVALID;
+    if (L.n > t->q_cap) { set_error(who + ": more LastFrame entries than the tracker's max_queries"); return DVM_ERR_CAPACITY; }
+    if (!L.n) continue;
+    if (store_device(L.store) != t->device) { set_error(who + ": the store lives on another device"); return DVM_ERR_INVALID; }
+    if (!store_slots_ok(L.store, L.slot, L.n)) { set_error(who + ": a slot outside its store or never written"); return DVM_ERR_INVALID; }
+    for (int i = 0; i < L.n; i++)
+      if ((int)L.octave[i] >= p->nlevels) { set_error(who + ": an octave outside the level tables"); return DVM_ERR_INVALID; }
+    *n_max = std::max(*n_max, L.n);
+  }
+  return DVM_OK;
+}
+// the entry lists packed, copied up and k_track_queries queued on stream qs (the tracker's side stream: beside the extraction); the query
+// block of the call must be carved (carve_query_block).  *d_inv_sigma2: mvInvLevelSigma2 on the device; *bytes: what was copied up
+int resident_queue(dvm_tracker* t, hipStream_t qs, int count, const dvm_track_last* last, const dvm_track_shared* p, int Qs, const float** d_inv_sigma2,
+                   size_t* bytes) {
+  std::vector<int32_t> eoff((size_t)count);
+  size_t E = 0;
+  for (int b = 0; b < count; b++) { eoff[b] = (int32_t)E; E += ((size_t)last[b].n + 63) & ~(size_t)63; }
+  const ResidentUpload up = carve_resident_upload(t->rw.hm, count, E);
+  if (up.bytes > t->rw.up_bytes) { set_error("dvm_track_finish_batch_resident: the entry lists exceed what the tracker was created for"); return DVM_ERR_CAPACITY; }
+  for (int k = 0; k < 64; k++) { up.scale[k] = k < p->nlevels ? p->scale_factors[k] : 1.0f; up.inv_sigma2[k] = k < p->nlevels ? p->inv_level_sigma2[k] : 0.0f; }
+  HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {
+    const dvm_track_last& L = last[b];
+    ResidentFrame& fr = up.fr[b];
+    fr.store = L.n ? store_records(L.store) : nullptr; fr.n = L.n; fr.th = L.th; fr.off = eoff[b];
+    std::memcpy(fr.q, L.Tcw_pred.q, 16); std::memcpy(fr.t, L.Tcw_pred.t, 12);
+    const size_t o = (size_t)eoff[b], n = (size_t)L.n;
+    if (n) { std::memcpy(up.slot + o, L.slot, n * 4); std::memcpy(up.angle + o, L.angle, n * 4); std::memcpy(up.octave + o, L.octave, n); }
+  });
+  DVM_HIP(hipMemcpyAsync(t->rw.d, t->rw.hm, up.bytes, hipMemcpyHostToDevice, qs));
+  const ResidentUpload dup = carve_resident_upload(t->rw.d, count, E);
+  for (int b = 0; b < count; b++)
+    if (last[b].n) { const int rc = store_read_begin(last[b].store, qs); if (rc != DVM_OK) return rc; }
+  const dvm_camera_model& M = t->model;
+  TrackQueryArgs A{};
+  A.fx = (float)p->cam.fx; A.fy = (float)p->cam.fy; A.cx = (float)p->cam.cx; A.cy = (float)p->cam.cy;
+  A.min_x = p->bounds[0]; A.max_x = p->bounds[1]; A.min_y = p->bounds[2]; A.max_y = p->bounds[3];
+  std::memcpy(A.kb8, M.p, sizeof(A.kb8));
+  auto& m = t->m;
+  const TrackQueryOut O{t->qdev(m.qdesc), t->qdev(m.qx), t->qdev(m.qy), t->qdev(m.qr), t->qdev(m.qmin), t->qdev(m.qmax), t->qdev(m.q_claims),
+                        t->qdev(m.q_angle), t->qdev(m.q_pos), t->qdev(m.pose_in), t->qdev(m.nq_arr), t->rw.dev(t->r_entry), t->rw.dev(t->r_nq)};
+  launch_track_queries(qs, M.model, dup.fr, dup.slot, dup.octave, dup.angle, dup.scale, A, count, Qs, O);
+  { const int rc = hip_check(hipGetLastError(), "k_track_queries"); if (rc != DVM_OK) return rc; }
+  for (int b = 0; b < count; b++)
+    if (last[b].n) { const int rc = store_read_end(last[b].store, qs); if (rc != DVM_OK) return rc; }
+  *d_inv_sigma2 = dup.inv_sigma2; *bytes = up.bytes;
+  return DVM_OK;
+}
+
+// dvm_track_finish_batch (qs: the caller's queries, copied up) and dvm_track_finish_batch_resident (last / p: the queries built on the
+// device from the frames' entry lists and stores); one of qs and last is NULL.  Behind the query block the two are one chain.
+int finish_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* qs, const dvm_track_last* last, const dvm_track_shared* p,
+               const dvm_track_frame_out* outs, dvm_track_result* res) {
   t->clear_next();
   if (t->begun != count) { set_error("dvm_track_finish: no matching dvm_track_begin on this tracker"); return DVM_ERR_STATE; }
-  const dvm_track_queries& q0 = qs[0];
   const dvm_camera_model M = t->model;
   const bool kb8 = M.model == dvm_cam::kKannalaBrandt8;    // (the cam fields of the queries are then not read)
+  FinishShared S{};
+  if (qs) {
+    const dvm_track_queries& q0 = qs[0];
+    std::memcpy(S.bounds, q0.bounds, 16); S.dist = q0.dist; S.inv_level_sigma2 = q0.inv_level_sigma2; S.nlevels = q0.nlevels; S.cam = q0.cam;
+    S.th_high = q0.th_high; S.check_ori = q0.check_ori; S.min_matches = q0.min_matches;
+  } else {
+    std::memcpy(S.bounds, p->bounds, 16); S.dist = p->dist; S.inv_level_sigma2 = p->inv_level_sigma2; S.nlevels = p->nlevels; S.cam = p->cam;
+    S.th_high = p->th_high; S.check_ori = p->check_ori; S.min_matches = p->min_matches;
+  }
   int nq_max = 0;
   for (int b = 0; b < count; b++) {
-    const dvm_track_queries& q = qs[b];
     const dvm_track_frame_out& o = outs[b];
     if (!o.kps || !o.desc || !o.assign || !o.outlier) return DVM_ERR_INVALID;
+    if (!qs) continue;
+    const dvm_track_queries& q0 = qs[0];
+    const dvm_track_queries& q = qs[b];
     if (q.nq < 0 || q.nq > t->q_cap || q.nlevels < 1 || q.nlevels > 64 || !q.inv_level_sigma2) { set_error("dvm_track_finish: bad query set"); return DVM_ERR_INVALID; }
     if (q.nq && (!q.qdesc || !q.qx || !q.qy || !q.qr || !q.qmin || !q.qmax || !q.q_claims || !q.q_angle || !q.q_pos)) return DVM_ERR_INVALID;
     if (kb8_with_distortion(M, q.dist)) {
@@ -249,8 +361,17 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
     }
     if (count > 1 && q.dist && q.dist->k1 != 0.0f) { set_error("dvm_track_finish_batch: distorted keypoints take the single-frame call"); return DVM_ERR_INVALID; }
     nq_max = std::max(nq_max, q.nq);
-    std::memset(&res[b], 0, sizeof(res[b]));
   }
+  if (!qs) {
+    const int rc = resident_check("dvm_track_finish_batch_resident", t, count, last, p, &nq_max);
+    if (rc != DVM_OK) return rc;
+    if (kb8_with_distortion(M, S.dist)) {
+      set_error("dvm_track_finish_batch_resident: distortion coefficients under a KannalaBrandt8 camera model (such a frame has mvKeysUn = mvKeys, mDistCoef zero)");
+      return DVM_ERR_INVALID;
+    }
+    if (count > 1 && S.dist && S.dist->k1 != 0.0f) { set_error("dvm_track_finish_batch_resident: distorted keypoints take the single-frame call"); return DVM_ERR_INVALID; }
+  }
+  for (int b = 0; b < count; b++) std::memset(&res[b], 0, sizeof(res[b]));
   DVM_HIP(hipSetDevice(t->device));
   hipStream_t s = (hipStream_t)dvm_orb_stream(h);
   const dvm_keypoint* d_kps = nullptr; const uint8_t* d_desc = nullptr; const int32_t* d_n = nullptr; int ocap = 0;
@@ -266,45 +387,45 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
   }
   const int Qs = (std::max(nq_max, 1) + 63) & ~63;      // the per-query arrays' stride for this call
   auto& m = t->m;
-  size_t q_used = 0;
-  {   // the query block of THIS call, packed: one copy (~75 KB per frame of 1 000 queries)
-    Cursor256 c{t->ws.hm};
-    const size_t Qn = (size_t)count * Qs;
-    m.qdesc = c.carve<uint8_t>(Qn * 32); m.qx = c.carve<float>(Qn); m.qy = c.carve<float>(Qn); m.qr = c.carve<float>(Qn);
-    m.qmin = c.carve<int32_t>(Qn); m.qmax = c.carve<int32_t>(Qn); m.q_claims = c.carve<uint8_t>(Qn); m.q_angle = c.carve<float>(Qn);
-    m.q_pos = c.carve<float>(Qn * 3); m.pose_in = c.carve<double>((size_t)count * 7); m.nq_arr = c.carve<int32_t>(count); m.inv_sigma2 = c.carve<float>(64);
-    // (the block's end and the ranked lists' inside what create sized: refused before anything is written)
-    q_used = c.used();
-    if (q_used > t->q_bytes || Qn > (size_t)t->max_frames * t->q_rcap) {
-      set_error("dvm_track_finish: the query block exceeds what the tracker was created for");
-      return DVM_ERR_CAPACITY;
-    }
+  // the query block of THIS call, packed: one copy (~75 KB per frame of 1 000 queries)
+  // (the block's end and the ranked lists' inside what create sized: refused before anything is written)
+  const size_t q_used = carve_query_block(t, count, Qs);
+  if (q_used > t->q_bytes || (size_t)count * Qs > (size_t)t->max_frames * t->q_rcap) {
+    set_error("dvm_track_finish: the query block exceeds what the tracker was created for");
+    return DVM_ERR_CAPACITY;
   }
-  HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {       // (a batch's query blocks: 2.4 MB for 32 frames)
-    const dvm_track_queries& q = qs[b];
-    const size_t o = b * Qs, nq = (size_t)q.nq;
-    std::memcpy(m.qdesc + o * 32, q.qdesc, nq * 32); std::memcpy(m.qx + o, q.qx, nq * 4); std::memcpy(m.qy + o, q.qy, nq * 4);
-    std::memcpy(m.qr + o, q.qr, nq * 4); std::memcpy(m.qmin + o, q.qmin, nq * 4); std::memcpy(m.qmax + o, q.qmax, nq * 4);
-    std::memcpy(m.q_claims + o, q.q_claims, nq); std::memcpy(m.q_angle + o, q.q_angle, nq * 4); std::memcpy(m.q_pos + o * 3, q.q_pos, nq * 12);
-    std::memcpy(m.pose_in + 7 * b, q.pose_in, 56);
-    m.nq_arr[b] = q.nq;
-  });
-  std::memcpy(m.inv_sigma2, q0.inv_level_sigma2, (size_t)q0.nlevels * 4);
-  {
+  const float* d_inv_sigma2 = t->qdev(m.inv_sigma2);
+  if (qs) {
+    HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {       // (a batch's query blocks: 2.4 MB for 32 frames)
+      const dvm_track_queries& q = qs[b];
+      const size_t o = b * Qs, nq = (size_t)q.nq;
+      std::memcpy(m.qdesc + o * 32, q.qdesc, nq * 32); std::memcpy(m.qx + o, q.qx, nq * 4); std::memcpy(m.qy + o, q.qy, nq * 4);
+      std::memcpy(m.qr + o, q.qr, nq * 4); std::memcpy(m.qmin + o, q.qmin, nq * 4); std::memcpy(m.qmax + o, q.qmax, nq * 4);
+      std::memcpy(m.q_claims + o, q.q_claims, nq); std::memcpy(m.q_angle + o, q.q_angle, nq * 4); std::memcpy(m.q_pos + o * 3, q.q_pos, nq * 12);
+      std::memcpy(m.pose_in + 7 * b, q.pose_in, 56);
+      m.nq_arr[b] = q.nq;
+    });
+    std::memcpy(m.inv_sigma2, S.inv_level_sigma2, (size_t)S.nlevels * 4);
     DVM_HIP(hipMemcpyAsync(t->d_q, t->ws.hm, q_used, hipMemcpyHostToDevice, t->cstream));   // beside the extraction, not behind it
-    DVM_HIP(hipEventRecord(t->cev, t->cstream));
-    DVM_HIP(hipStreamWaitEvent(s, t->cev, 0));
+    t->up_first = (int64_t)q_used;
+  } else {
+    // the entry lists (9 B per entry) in place of the queries: k_track_queries writes the block on the device, beside the extraction
+    size_t bytes = 0;
+    if ((rc = resident_queue(t, t->cstream, count, last, p, Qs, &d_inv_sigma2, &bytes)) != DVM_OK) return rc;
+    t->up_first = (int64_t)bytes;
   }
+  DVM_HIP(hipEventRecord(t->cev, t->cstream));
+  DVM_HIP(hipStreamWaitEvent(s, t->cev, 0));
   // mvKeysUn: the extractor's keypoints themselves without distortion (Frame.cc:791-797), else undistorted on the device (:799-818)
-  const bool undist = count == 1 && q0.dist && q0.dist->k1 != 0.0f;
+  const bool undist = count == 1 && S.dist && S.dist->k1 != 0.0f;
   const dvm_keypoint* d_un = d_kps;
   if (undist) {
-    rc = dvm_undistort_keypoints(q0.dist, d_kps, reinterpret_cast<dvm_keypoint*>(t->d_kps_un), ocap, 1, s);
+    rc = dvm_undistort_keypoints(S.dist, d_kps, reinterpret_cast<dvm_keypoint*>(t->d_kps_un), ocap, 1, s);
     if (rc != DVM_OK) return rc;
     d_un = reinterpret_cast<const dvm_keypoint*>(t->d_kps_un);
     if (outs[0].kps_un) DVM_HIP(hipMemcpyAsync(m.kps_un, t->d_kps_un, (size_t)ocap * sizeof(dvm_keypoint_pod), hipMemcpyDeviceToHost, s));
   }
-  rc = dvm_frame_build_batch(t->grid, 0, count, d_un, kps_stride, d_desc, desc_stride, d_n, q0.bounds[0], q0.bounds[1], q0.bounds[2], q0.bounds[3], s);
+  rc = dvm_frame_build_batch(t->grid, 0, count, d_un, kps_stride, d_desc, desc_stride, d_n, S.bounds[0], S.bounds[1], S.bounds[2], S.bounds[3], s);
   if (rc != DVM_OK) return rc;
   const FrameView FV = frame_view_of(t->grid);    // (bounds of the build above)
   launch_match_window_ranked_batch(s, FV, 0, count, nullptr, nullptr, 0, t->qdev(m.qdesc), t->qdev(m.qx), t->qdev(m.qy), t->qdev(m.qr), t->qdev(m.qmin),
@@ -314,11 +435,11 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
   rq.F = FV;
   { static const bool no_rq = std::getenv("DVM_TRACK_NO_REQUERY") != nullptr; if (no_rq) rq.F.skp = nullptr; }   /* timing experiment only */
   rq.qdesc = t->qdev(m.qdesc); rq.qx = t->qdev(m.qx); rq.qy = t->qdev(m.qy); rq.qr = t->qdev(m.qr); rq.qmin = t->qdev(m.qmin); rq.qmax = t->qdev(m.qmax);
-  launch_track_claims(s, t->d_ranked, t->qdev(m.q_claims), t->qdev(m.q_angle), 0, rq, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, q0.th_high,
-                      q0.check_ori, t->d_assign, t->d_res, t->ws.dev(m.assign), t->ws.dev(m.res), TB);
-  launch_track_gather(s, t->d_assign, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, t->qdev(m.q_pos), t->qdev(m.inv_sigma2), q0.nlevels, t->d_Xw,
-                      t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges, t->d_res, q0.min_matches, t->ws.dev(m.nedges), TB);
-  launch_pose_optimize(s, M, q0.cam, t->qdev(m.pose_in), t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, t->ws.dev(m.pose_out), t->d_edge_out,
+  launch_track_claims(s, t->d_ranked, t->qdev(m.q_claims), t->qdev(m.q_angle), 0, rq, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, S.th_high,
+                      S.check_ori, t->d_assign, t->d_res, t->ws.dev(m.assign), t->ws.dev(m.res), TB);
+  launch_track_gather(s, t->d_assign, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, t->qdev(m.q_pos), d_inv_sigma2, S.nlevels, t->d_Xw,
+                      t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges, t->d_res, S.min_matches, t->ws.dev(m.nedges), TB);
+  launch_pose_optimize(s, M, S.cam, t->qdev(m.pose_in), t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, t->ws.dev(m.pose_out), t->d_edge_out,
                        t->ws.dev(m.n_inl), t->d_chi);
   launch_track_finish(s, t->d_assign, d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, t->qdev(m.q_claims), t->ws.dev(m.outlier), t->ws.dev(m.fin), t->d_res, TB);
   // (what the host wants back is written to mapped memory by the kernels themselves: no copy command behind the chain)
@@ -333,25 +454,30 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
   }
   static const bool debug = std::getenv("DVM_TRACK_DEBUG") != nullptr;       // per-frame counters on stderr
   for (int b = 0; b < count; b++) {
-    const dvm_track_queries& q = qs[b];
+    const int nq_b = qs ? qs[b].nq : t->r_nq[b];
+    const int min_matches = qs ? qs[b].min_matches : S.min_matches;
     const dvm_track_frame_out& o = outs[b];
     dvm_track_result& r = res[b];
     const int n = r.n;
     if (o.kps_un) std::memcpy(o.kps_un, undist ? reinterpret_cast<const dvm_keypoint*>(m.kps_un) : o.kps, (size_t)n * sizeof(dvm_keypoint));
     const size_t ko = (size_t)b * ocap;
     std::memcpy(o.assign, m.assign + ko, (size_t)n * 4);
+    if (!qs) {     // the chain's query numbers as entry numbers of last[b] (k_track_queries kept q_entry beside each query)
+      const int32_t* qe = t->r_entry + (size_t)b * Qs;
+      for (int j = 0; j < n; j++) if (o.assign[j] >= 0) o.assign[j] = qe[o.assign[j]];
+    }
     const int32_t* rs = m.res + 8 * b;
     r.nmatches = rs[0];
     r.nmatches_before_rotation = rs[2];
     r.n_requeried = rs[3];
-    if (debug) std::fprintf(stderr, "track: frame %d nq %d rounds %d requeried %d\n", b, q.nq, rs[4], rs[3]);
+    if (debug) std::fprintf(stderr, "track: frame %d nq %d rounds %d requeried %d\n", b, nq_b, rs[4], rs[3]);
     if (rs[1]) {                        // a query ran out of ranked candidates and could not be searched again on the device (DVM_TRACK_NO_REQUERY)
       r.status = DVM_TRACK_REPLAY_ON_HOST;
-      if (o.ranked && q.nq) DVM_HIP(hipMemcpy(o.ranked, t->d_ranked + (size_t)b * Qs * 4, (size_t)q.nq * 16, hipMemcpyDeviceToHost));
+      if (o.ranked && nq_b) DVM_HIP(hipMemcpy(o.ranked, t->d_ranked + (size_t)b * Qs * 4, (size_t)nq_b * 16, hipMemcpyDeviceToHost));
       std::memset(o.outlier, 0, (size_t)n);
       continue;
     }
-    if (r.nmatches < q.min_matches) { r.status = DVM_TRACK_FEW_MATCHES; std::memset(o.outlier, 0, (size_t)n); continue; }
+    if (r.nmatches < min_matches) { r.status = DVM_TRACK_FEW_MATCHES; std::memset(o.outlier, 0, (size_t)n); continue; }
     r.status = DVM_TRACK_COMPLETE;
     std::memcpy(o.outlier, m.outlier + ko, (size_t)n);
     r.n_edges = m.nedges[b]; r.n_inliers = m.n_inl[b]; r.nmatches_map = m.fin[4 * b]; r.nmatches_after = m.fin[4 * b + 1];
@@ -360,15 +486,67 @@ int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_trac
   {     // what the second half runs on: the frames' grids (slots 0..count-1) and mvKeysUn
     LocalFrame& f = t->lf;
     f.ready = count == 1 && res[0].status == DVM_TRACK_COMPLETE; f.batch_ready = 1; f.rkb_ready = 1;
-    f.h = h; f.serial = orb_result_serial(h); f.ocap = ocap; f.nlevels = q0.nlevels;
+    f.h = h; f.serial = orb_result_serial(h); f.ocap = ocap; f.nlevels = S.nlevels;
     f.d_un = reinterpret_cast<const dvm_keypoint_pod*>(d_un); f.d_n = d_n;
-    std::memcpy(f.bounds, q0.bounds, 16); std::memcpy(f.inv_sigma2, q0.inv_level_sigma2, (size_t)q0.nlevels * 4); f.cam = q0.cam; f.model = M;
+    std::memcpy(f.bounds, S.bounds, 16); std::memcpy(f.inv_sigma2, S.inv_level_sigma2, (size_t)S.nlevels * 4); f.cam = S.cam; f.model = M;
     f.count = count; f.kps_stride = kps_stride; f.ns.resize((size_t)count); f.status.resize((size_t)count);
     f.monos.resize((size_t)count); f.poses.assign(m.pose_out, m.pose_out + 7 * (size_t)count);
     for (int b = 0; b < count; b++) { f.ns[b] = res[b].n; f.status[b] = res[b].status; f.monos[b] = res[b].mono_index; }
     f.d_desc = d_desc; f.desc_stride = desc_stride;
   }
   if (count == 1 && t->max_frames == 1) { t->rk_state = 2; t->rk_h = h; t->rk_serial = orb_result_serial(h); }   // (whatever the status)
+  return DVM_OK;
+}
+}  // namespace
+
+int dvm_track_finish_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* qs, const dvm_track_frame_out* outs, dvm_track_result* res) {
+  if (!t || !h || !qs || !outs || !res || count < 1) return DVM_ERR_INVALID;
+  return finish_run(t, h, count, qs, nullptr, nullptr, outs, res);
+}
+
+int dvm_track_finish_batch_resident(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_last* last, const dvm_track_shared* p,
+                                    const dvm_track_frame_out* outs, dvm_track_result* res) {
+  if (!t || !h || !last || !p || !outs || !res || count < 1) return DVM_ERR_INVALID;
+  return finish_run(t, h, count, nullptr, last, p, outs, res);
+}
+
+int dvm_track_debug_build_queries(dvm_tracker* t, int count, const dvm_track_last* last, const dvm_track_shared* p, int32_t* nq, int32_t* q_entry,
+                                  float* qx, float* qy, float* qr, int32_t* qmin, int32_t* qmax, uint8_t* q_claims, float* q_angle, float* q_pos,
+                                  uint8_t* qdesc, int32_t* stride) {
+  if (!t || !last || !p || !nq || !q_entry || !qx || !qy || !qr || !qmin || !qmax || !q_claims || !q_angle || !q_pos || !qdesc || !stride || count < 1)
+    return DVM_ERR_INVALID;
+  if (count > t->max_frames) { set_error("dvm_track_debug_build_queries: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
+  int n_max = 0;
+  int rc = resident_check("dvm_track_debug_build_queries", t, count, last, p, &n_max);
+  if (rc != DVM_OK) return rc;
+  DVM_HIP(hipSetDevice(t->device));
+  const int Qs = (std::max(n_max, 1) + 63) & ~63;
+  const size_t Qn = (size_t)count * Qs;
+  if (carve_query_block(t, count, Qs) > t->q_bytes || Qn > (size_t)t->max_frames * t->q_rcap) {
+    set_error("dvm_track_debug_build_queries: the query block exceeds what the tracker was created for");
+    return DVM_ERR_CAPACITY;
+  }
+  const float* d_inv_sigma2 = nullptr; size_t bytes = 0;
+  if ((rc = resident_queue(t, t->cstream, count, last, p, Qs, &d_inv_sigma2, &bytes)) != DVM_OK) return rc;
+  DVM_HIP(hipStreamSynchronize(t->cstream));
+  auto& m = t->m;
+  DVM_HIP(hipMemcpy(qdesc, t->qdev(m.qdesc), Qn * 32, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(qx, t->qdev(m.qx), Qn * 4, hipMemcpyDeviceToHost));
+  DVM_HIP(hipMemcpy(qy, t->qdev(m.qy), Qn * 4, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(qr, t->qdev(m.qr), Qn * 4, hipMemcpyDeviceToHost));
+  DVM_HIP(hipMemcpy(qmin, t->qdev(m.qmin), Qn * 4, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(qmax, t->qdev(m.qmax), Qn * 4, hipMemcpyDeviceToHost));
+  DVM_HIP(hipMemcpy(q_claims, t->qdev(m.q_claims), Qn, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(q_angle, t->qdev(m.q_angle), Qn * 4, hipMemcpyDeviceToHost));
+  DVM_HIP(hipMemcpy(q_pos, t->qdev(m.q_pos), Qn * 12, hipMemcpyDeviceToHost));
+  DVM_HIP(hipMemcpy(nq, t->qdev(m.nq_arr), (size_t)count * 4, hipMemcpyDeviceToHost));
+  std::memcpy(q_entry, t->r_entry, Qn * 4);
+  for (int b = 0; b < count; b++)
+    if (nq[b] != t->r_nq[b]) { set_error("dvm_track_debug_build_queries: the device and mapped query counts differ"); return DVM_ERR_STATE; }
+  *stride = Qs;
+  return DVM_OK;
+}
+
+int dvm_tracker_last_upload_bytes(const dvm_tracker* t, int64_t* first_half, int64_t* second_half) {
+  if (!t) return DVM_ERR_INVALID;
+  if (first_half) *first_half = t->up_first;
+  if (second_half) *second_half = t->up_second;
   return DVM_OK;
 }
 
@@ -399,6 +577,27 @@ LocalMapUpload carve_local_map_upload(uint8_t* base, int count, size_t T, size_t
   u.bytes = c.used();
   return u;
 }
+// the same block where the tables are store slots (dvm_track_local_map_batch_resident): [mvScaleFactors 64][mvInvLevelSigma2 64][frame
+// block][the frames' stores: count device pointers][slots: T, frame b's at qoff[b]][frame_mp: count x kstride] -- copied up to here
+// (copy_bytes) in one copy -- then [tables: T records], device only: k_store_gather fills them from the stores
+struct LocalMapUploadResident { LocalMapUpload u; const LocalPointPod** stores; int32_t* slots; size_t copy_bytes; };
+LocalMapUploadResident carve_local_map_upload_resident(uint8_t* base, int count, size_t T, size_t kstride) {
+  LocalMapUploadResident r;
+  LocalMapUpload& u = r.u;
+  Cursor256 c{base};
+  u.scale = c.carve<float>(64); u.inv_sigma2 = c.carve<float>(64);
+  uint8_t* fb = c.carve<uint8_t>((size_t)count * kFrameRec);
+  u.pose = reinterpret_cast<double*>(fb); u.fa = reinterpret_cast<LocalFrameArgs*>(fb + (size_t)count * 56);
+  u.qoff = reinterpret_cast<int32_t*>(u.fa + count); u.skip_on = u.qoff + count;
+  Cursor<64> t{base, nullptr, c.used()};
+  r.stores = t.carve<const LocalPointPod*>((size_t)count); r.slots = t.carve<int32_t>(T);
+  u.frame_mp = reinterpret_cast<int32_t*>(base + t.used());
+  r.copy_bytes = t.used() + (size_t)count * kstride * 4;
+  c.off = pad<256>(r.copy_bytes);
+  u.pts = c.carve<LocalPointPod>(T);
+  u.bytes = c.used();
+  return r;
+}
 }  // namespace
 
 int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points) {
@@ -411,7 +610,8 @@ int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points) {
   t->lm_cap = 0; t->lf.ready = 0; t->lf.batch_ready = 0;
   // P: table entries of one call (a batch: all frames' tables, each rounded up to 64); per keypoint and per frame: max_frames frames
   const size_t P = ((size_t)max_points + 63) & ~(size_t)63, K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
-  const size_t up = pad<256>(B * kFrameRec) + 2 * pad<256>(256) + pad<256>(P * sizeof(LocalPointPod)) + pad<256>(B * K * 4);
+  // (the last two items: the slot lists and store pointers of dvm_track_local_map_batch_resident, whose tables are filled on the device)
+  const size_t up = pad<256>(B * kFrameRec) + 2 * pad<256>(256) + pad<256>(P * sizeof(LocalPointPod)) + pad<256>(B * K * 4) + pad<256>(P * 4) + pad<256>(B * 8);
   // device: upload copy, per-entry arrays (seen, pos, claims), per-keypoint arrays (frame_mp, skip), pose seeds, query arrays at any stride
   // up to P, ranked lists, counters
   const size_t dbytes = up + pad<256>(P) + pad<256>(P * 12) + pad<256>(P) + pad<256>(B * K * 4) + pad<256>(B * K) + pad<256>(B * 56) +
@@ -431,8 +631,10 @@ namespace {
 // TrackLocalMap on the `count` frames of the last finish (t->lf), behind the entry points' state checks: the tables, the frames' points,
 // poses and parameters in ONE upload, ONE chain of batched launches, a workgroup (row of workgroups) per frame on grid slots 0..count-1,
 // ONE synchronisation.  A frame the first half did not complete is skipped.
-int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_out* out, dvm_track_local_result* res,
-                  int32_t* status) {
+// in: the tables as records, copied up (dvm_track_local_map[_batch]); rin: the tables as store slots, gathered on the device
+// (dvm_track_local_map_batch_resident); one of the two is NULL
+int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_in_resident* rin, const dvm_local_map_out* out,
+                  dvm_track_local_result* res, int32_t* status) {
   LocalFrame& f = t->lf;
   static const bool timing = std::getenv("DVM_TRACK_BATCH_TIMING") != nullptr;       // host-side phase times on stderr
   using clk = std::chrono::steady_clock;
@@ -444,11 +646,19 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
   for (int b = 0; b < count; b++) {
     qoff[b] = (int32_t)std::min(T, (size_t)INT32_MAX);
     if (f.status[b] != DVM_TRACK_COMPLETE) continue;
-    const dvm_local_map_in& q = in[b];
+    struct { int32_t n; const void* tab; const int32_t* frame_mp; } q = {in ? in[b].n : rin[b].n, in ? (const void*)in[b].pts : (const void*)rin[b].slots,
+                                                                         in ? in[b].frame_mp : rin[b].frame_mp};
     const int N = f.ns[b];
-    if (q.n < 0 || (q.n && !q.pts) || (N && !q.frame_mp) || !out[b].mp_out || !out[b].outlier) return DVM_ERR_INVALID;
+    if (q.n < 0 || (q.n && !q.tab) || (N && !q.frame_mp) || !out[b].mp_out || !out[b].outlier) return DVM_ERR_INVALID;
     for (int j = 0; j < N; j++)
       if (q.frame_mp[j] < -1 || q.frame_mp[j] >= q.n) { set_error("dvm_track_local_map_batch: frame_mp names a point outside the table"); return DVM_ERR_INVALID; }
+    if (rin && q.n) {     // every slot checked here, on the host: k_store_gather indexes the store with them
+      if (!rin[b].store) return DVM_ERR_INVALID;
+      if (store_device(rin[b].store) != t->device) { set_error("dvm_track_local_map_batch_resident: the store lives on another device"); return DVM_ERR_INVALID; }
+      if (!store_slots_ok(rin[b].store, rin[b].slots, q.n)) {
+        set_error("dvm_track_local_map_batch_resident: a slot outside its store or never written"); return DVM_ERR_INVALID;
+      }
+    }
     const size_t span = ((size_t)q.n + 63) & ~(size_t)63;
     nb[b] = q.n; T += span; span_max = std::max(span_max, span); live++;
   }
@@ -457,7 +667,8 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
   if (!live) { f.ready = 0; f.batch_ready = 0; f.rkb_ready = 0; return DVM_OK; }
   const int ocap = f.ocap;
   const size_t Tc = std::max(T, (size_t)64);
-  const LocalMapUpload up = carve_local_map_upload(t->lmw.hm, count, Tc, (size_t)ocap);
+  const LocalMapUploadResident rup = rin ? carve_local_map_upload_resident(t->lmw.hm, count, Tc, (size_t)ocap) : LocalMapUploadResident{};
+  const LocalMapUpload up = rin ? rup.u : carve_local_map_upload(t->lmw.hm, count, Tc, (size_t)ocap);
   if (up.bytes > t->lmw.up_bytes) { set_error("dvm_track_local_map_batch: the upload block exceeds the reservation"); return DVM_ERR_CAPACITY; }
   DVM_HIP(hipSetDevice(t->device));
   hipStream_t s = (hipStream_t)dvm_orb_stream(h);
@@ -471,18 +682,30 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
     const bool go = f.status[b] == DVM_TRACK_COMPLETE;
     int32_t* fm = up.frame_mp + b * (size_t)ocap;
     std::memcpy(up.pose + 7 * b, f.poses.data() + 7 * b, 56);    // the finish's pose, or the reference-keyframe chain's
-    up.fa[b] = LocalFrameArgs{nb[b], go && in[b].far_points ? 1 : 0, go ? in[b].th : 1.0f, go ? in[b].th_far : 0.0f};
+    const int far_points = !go ? 0 : in ? in[b].far_points : rin[b].far_points;
+    up.fa[b] = LocalFrameArgs{nb[b], far_points ? 1 : 0, !go ? 1.0f : in ? in[b].th : rin[b].th, !go ? 0.0f : in ? in[b].th_far : rin[b].th_far};
     up.qoff[b] = qoff[b]; up.skip_on[b] = 1;
+    if (rin) rup.stores[b] = go && nb[b] ? store_records(rin[b].store) : nullptr;
     if (go) {
-      if (nb[b]) std::memcpy(up.pts + qoff[b], in[b].pts, (size_t)nb[b] * sizeof(LocalPointPod));
-      if (f.ns[b]) std::memcpy(fm, in[b].frame_mp, (size_t)f.ns[b] * 4);
+      if (nb[b] && in) std::memcpy(up.pts + qoff[b], in[b].pts, (size_t)nb[b] * sizeof(LocalPointPod));
+      if (nb[b] && rin) std::memcpy(rup.slots + qoff[b], rin[b].slots, (size_t)nb[b] * 4);
+      if (f.ns[b]) std::memcpy(fm, (in ? in[b].frame_mp : rin[b].frame_mp), (size_t)f.ns[b] * 4);
     } else {
       for (int j = 0; j < ocap; j++) fm[j] = -1;        // a skipped frame holds nothing and searches nothing
     }
   });
-  DVM_HIP(hipMemcpyAsync(t->lmw.d, t->lmw.hm, up.bytes, hipMemcpyHostToDevice, s));
+  DVM_HIP(hipMemcpyAsync(t->lmw.d, t->lmw.hm, rin ? rup.copy_bytes : up.bytes, hipMemcpyHostToDevice, s));
+  t->up_second = (int64_t)(rin ? rup.copy_bytes : up.bytes);
   const clk::time_point tp1 = clk::now();
-  const LocalMapUpload dup = carve_local_map_upload(t->lmw.d, count, Tc, (size_t)ocap);
+  const LocalMapUploadResident drup = rin ? carve_local_map_upload_resident(t->lmw.d, count, Tc, (size_t)ocap) : LocalMapUploadResident{};
+  const LocalMapUpload dup = rin ? drup.u : carve_local_map_upload(t->lmw.d, count, Tc, (size_t)ocap);
+  if (rin) {     // the device tables from the stores, behind their last updates
+    for (int b = 0; b < count; b++)
+      if (f.status[b] == DVM_TRACK_COMPLETE && nb[b]) { rc = store_read_begin(rin[b].store, s); if (rc != DVM_OK) return rc; }
+    launch_store_gather(s, StoreGather{drup.stores, dup.fa, dup.qoff, drup.slots}, dup.pts, count, (int)span_max);
+    for (int b = 0; b < count; b++)
+      if (f.status[b] == DVM_TRACK_COMPLETE && nb[b]) { rc = store_read_end(rin[b].store, s); if (rc != DVM_OK) return rc; }
+  }
   // 2. device arrays of this call: per entry at the frames' offsets, per keypoint at b * ocap
   const size_t Kb = (size_t)count * ocap;
   LocalQueries LQ;
@@ -576,7 +799,7 @@ int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, 
   const dvm_local_map_in in{pts, n, frame_mp, th, far_points, th_far};
   const dvm_local_map_out out{mp_out, outlier, track_pts};
   int32_t status = 0;
-  return local_map_run(t, h, 1, &in, &out, res, &status);
+  return local_map_run(t, h, 1, &in, nullptr, &out, res, &status);
 }
 
 int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_out* out,
@@ -588,7 +811,19 @@ int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_l
     return DVM_ERR_STATE;
   }
   if (!t->lmw.d) { set_error("dvm_track_local_map_batch: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
-  return local_map_run(t, h, count, in, out, res, status);
+  return local_map_run(t, h, count, in, nullptr, out, res, status);
+}
+
+int dvm_track_local_map_batch_resident(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in_resident* in, const dvm_local_map_out* out,
+                                       dvm_track_local_result* res, int32_t* status) {
+  if (!t || !h || !in || !out || !res || !status || count < 1) return DVM_ERR_INVALID;
+  LocalFrame& f = t->lf;
+  if (!f.batch_ready || f.h != h || orb_result_serial(h) != f.serial || f.count != count) {
+    set_error("dvm_track_local_map_batch_resident: not right after a dvm_track_finish[_batch][_resident] of `count` frames (same tracker and extractor)");
+    return DVM_ERR_STATE;
+  }
+  if (!t->lmw.d) { set_error("dvm_track_local_map_batch_resident: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
+  return local_map_run(t, h, count, nullptr, in, out, res, status);
 }
 
 // ---- the other way into the second half: Tracking::TrackReferenceKeyFrame (src/Tracking.cc:2461-2520) on the frames of a finish, or on

@@ -26,6 +26,23 @@ struct LocalPointPod {  // == dvm_local_point
   uint8_t desc[32];
   int32_t n_obs, bad;
 };
+// ---- the first half's queries built on the device from a map-point store (dvm_track_finish_batch_resident)
+struct ResidentFrame {  // one frame of the call: its store's records, its entry count, SearchByProjection's th, the predicted pose, where its entry lists begin
+  const LocalPointPod* store; int32_t n; float th; float q[4], t[3]; int32_t off;
+};                      // 48 bytes
+struct TrackQueryArgs { // the call's constants: camera (pinhole: fx fy cx cy; KannalaBrandt8: kb8 = mvParameters), image bounds
+  float fx, fy, cx, cy, min_x, max_x, min_y, max_y;
+  float kb8[8];
+};
+struct TrackQueryOut {  // the tracker's device query block at the call's stride, plus what the host reads (mapped)
+  uint8_t* qdesc; float *qx, *qy, *qr; int32_t *qmin, *qmax; uint8_t* q_claims; float *q_angle, *q_pos; double* pose_in; int32_t* nq_arr;
+  int32_t* q_entry_host;   // mapped [count][stride]: the entry number of every query
+  int32_t* nq_host;        // mapped [count]
+};
+// one workgroup per frame: frame b's entry lists (slot, octave, angle) at frames[b].off, its queries at b * stride, scale = mvScaleFactors [64];
+// model: dvm_cam::kPinhole or kKannalaBrandt8.  The host has checked every slot against its store and every octave against the tables.
+void launch_track_queries(hipStream_t s, int model, const ResidentFrame* frames, const int32_t* slot, const uint8_t* octave, const float* angle,
+                          const float* scale, const TrackQueryArgs& A, int count, int stride, const TrackQueryOut& O);
 struct LocalFrameArgs { int32_t n, far_points; float th, th_far; };   // one frame's table size and SearchByProjection's th / far-point filter
 struct LocalMapArgs {   // the call's constants: camera, bounds, level count; per frame its table size and SearchByProjection's th / far-point filter
   float fx, fy, cx, cy, min_x, max_x, min_y, max_y, log_scale_factor;

@@ -453,6 +453,90 @@ __global__ void __launch_bounds__(1024) k_track_local_prologue(const LocalPointP
   if (tid == 0) { LQ.nq[0] = base; res_host[0] = s_cnt[1]; res_host[1] = s_cnt[0]; }
 }
 
+// The loop header of SearchByProjection(CurrentFrame, LastFrame) (ORBmatcher.cc:1573-1611) on the device, from LastFrame's entry list and
+// the agent's map-point store (dvm_track_finish_batch_resident) -- what dvm_host::BuildFrameQueries and the three per-query arrays of
+// host/tracking.cpp produce on the host, operation for operation:
+//   x3Dc = Tcw * pos (dvm_pose::se3_apply: Sophus' quaternion form), invzc = (float)(1.0 / zc), the entry skipped if invzc < 0;
+//   (u, v) = mpCamera->project(x3Dc): pinhole fx * xc / zc + cx in float, KannalaBrandt8 dvm_cam::kb8_project on A.kb8;
+//   skipped if u < mnMinX || u > mnMaxX, or v < mnMinY || v > mnMaxY (written as the reference writes them: a NaN passes);
+//   radius = th * mvScaleFactors[octave], levels octave - 1 .. octave + 1.
+// One workgroup of four waves per frame, entries in rounds of 256.  The kept entries are compacted IN ENTRY ORDER (the claim replay is
+// sequential in query order): inside a wave a ballot and mbcnt give the lane's offset, the four waves' counts go through LDS, and a
+// running base carries over the rounds.  Per kept entry: qx qy qr qmin qmax, q_claims (n_obs > 0), q_angle, q_pos, the 32 descriptor
+// bytes of the store's record, and the entry number (mapped: the host turns the chain's query numbers into entry numbers with it).
+// nq goes to the device nq_arr and to mapped memory; pose_in is the predicted pose widened to double (Optimizer.cc:760).
+template <int MODEL>
+__global__ void __launch_bounds__(256) k_track_queries(const ResidentFrame* __restrict__ frames, const int32_t* __restrict__ slot,
+                                                       const uint8_t* __restrict__ octave, const float* __restrict__ angle,
+                                                       const float* __restrict__ scale, TrackQueryArgs A, int stride, TrackQueryOut O) {
+  __shared__ int s_wave[4];
+  __shared__ float s_scale[64];
+  const int b = blockIdx.x;
+  const ResidentFrame fr = frames[b];
+  {
+    const size_t o = (size_t)b * stride;
+    slot += fr.off; octave += fr.off; angle += fr.off;
+    O.qdesc += o * 32; O.qx += o; O.qy += o; O.qr += o; O.qmin += o; O.qmax += o; O.q_claims += o; O.q_angle += o; O.q_pos += o * 3;
+    O.pose_in += 7 * b; O.nq_arr += b; O.q_entry_host += o; O.nq_host += b;
+  }
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int n = fr.n;
+  if (tid < 64) s_scale[tid] = scale[tid];
+  if (tid == 0) {      // (constant indices: fr stays in registers)
+#pragma unroll
+    for (int k = 0; k < 3; k++) O.pose_in[k] = (double)fr.t[k];
+#pragma unroll
+    for (int k = 0; k < 4; k++) O.pose_in[3 + k] = (double)fr.q[k];
+  }
+  __syncthreads();
+  int base = 0;
+  for (int c = 0; c < n; c += 256) {
+    const int i = c + tid;
+    bool keep = false;
+    float u = 0.0f, v = 0.0f;
+    const LocalPointPod* P = nullptr;
+    int oct = 0;
+    if (i < n) {
+      P = fr.store + slot[i];
+      oct = octave[i];
+      const float X[3] = {P->pos[0], P->pos[1], P->pos[2]};
+      float x3Dc[3];
+      dvm_pose::se3_apply(fr.q, fr.t, X, x3Dc);
+      const float xc = x3Dc[0], yc = x3Dc[1], zc = x3Dc[2];
+      const float invzc = (float)(1.0 / zc);
+      if (MODEL == dvm_cam::kKannalaBrandt8) dvm_cam::kb8_project(A.kb8, xc, yc, zc, u, v);
+      else { u = A.fx * xc / zc + A.cx; v = A.fy * yc / zc + A.cy; }
+      keep = !(invzc < 0) && !(u < A.min_x || u > A.max_x) && !(v < A.min_y || v > A.max_y);
+    }
+    const unsigned long long m = __ballot(keep);
+    if (lane == 0) s_wave[wv] = __popcll(m);
+    __syncthreads();
+    int pos = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    int total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      const int cw = s_wave[w];
+      if (w < wv) pos += cw;
+      total += cw;
+    }
+    if (keep) {
+      O.qx[pos] = u; O.qy[pos] = v; O.qr[pos] = fr.th * s_scale[oct];
+      O.qmin[pos] = oct - 1; O.qmax[pos] = oct + 1;
+      O.q_claims[pos] = P->n_obs > 0 ? 1 : 0;
+      O.q_angle[pos] = angle[i];
+      O.q_pos[3 * (size_t)pos] = P->pos[0]; O.q_pos[3 * (size_t)pos + 1] = P->pos[1]; O.q_pos[3 * (size_t)pos + 2] = P->pos[2];
+      const uint2* sd = reinterpret_cast<const uint2*>(P->desc);
+      uint2* dd = reinterpret_cast<uint2*>(O.qdesc + (size_t)pos * 32);
+#pragma unroll
+      for (int k = 0; k < 4; k++) dd[k] = sd[k];
+      O.q_entry_host[pos] = i;
+    }
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) { O.nq_arr[0] = base; O.nq_host[0] = base; }
+}
+
 // ---- the reference-keyframe chain: Tracking::TrackReferenceKeyFrame (Tracking.cc:2461-2520) behind the extraction of the frame
 
 namespace {
@@ -707,6 +791,13 @@ void launch_track_local_prologue(hipStream_t s, int model, const LocalPointPod* 
   else
     hipLaunchKernelGGL((k_track_local_prologue<dvm_cam::kPinhole>), dim3(B.count), dim3(1024), 0, s, pts, frame_mp_in, pose_first, scale, d_n, kp_cap,
                        A, LQ, track_pts_host, res_host, B);
+}
+void launch_track_queries(hipStream_t s, int model, const ResidentFrame* frames, const int32_t* slot, const uint8_t* octave, const float* angle,
+                          const float* scale, const TrackQueryArgs& A, int count, int stride, const TrackQueryOut& O) {
+  if (model == dvm_cam::kKannalaBrandt8)
+    hipLaunchKernelGGL((k_track_queries<dvm_cam::kKannalaBrandt8>), dim3(count), dim3(256), 0, s, frames, slot, octave, angle, scale, A, stride, O);
+  else
+    hipLaunchKernelGGL((k_track_queries<dvm_cam::kPinhole>), dim3(count), dim3(256), 0, s, frames, slot, octave, angle, scale, A, stride, O);
 }
 void launch_track_gather(hipStream_t s, const int32_t* assign, const dvm_keypoint_pod* kps_un, const int32_t* d_n, int kp_cap, const float* q_pos,
                          const float* inv_sigma2, int nlevels, double* Xw, double* obs, double* info, int32_t* edge_kp, int32_t* n_edges,

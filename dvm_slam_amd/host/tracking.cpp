@@ -382,3 +382,153 @@ extern "C" int dvmh_track_with_motion_model_batch_cam(dvm_tracker* t, dvm_orb* h
   return track_with_motion_model_batch(t, h, device, count, imgs, rows, cols, stride, frame_stride, lap0, lap1, Km, cam, bounds, scale_factors,
                                        inv_level_sigma2, nlevels, th, check_ori, in, outs, res);
 }
+
+
+// ---- the agents' map points resident on the device (dvm_map_store): the batched call above with LastFrame's map points given as store
+// slots.  The host projects nothing: it packs the entry lists (slot, octave, angle of every LastFrame keypoint that holds a point and is no
+// outlier) and k_track_queries builds the queries from the store.
+extern "C" int dvmh_track_with_motion_model_batch_resident(dvm_tracker* t, dvm_orb* h, int device, int count, const uint8_t* imgs, int rows, int cols,
+                                                           int stride, int64_t frame_stride, int lap0, int lap1, const float* K, const float* bounds,
+                                                           const float* scale_factors, const float* inv_level_sigma2, int nlevels, float th, int check_ori,
+                                                           const dvmh_track_in_resident* in, const dvmh_track_out* outs, dvmh_track_result* res) {
+  if (!t || !h || !bounds || !scale_factors || !inv_level_sigma2 || !in || !outs || !res || count < 1) return DVM_ERR_INVALID;
+  for (int b = 0; b < count; b++) {
+    if (!in[b].Tcw_pred || (in[b].Nl && (!in[b].kps_l || !in[b].mp_l || !in[b].store)) || !outs[b].kps || !outs[b].desc || !outs[b].mp_c || !outs[b].dropped) return DVM_ERR_INVALID;
+    std::memset(&res[b], 0, sizeof(res[b]));
+  }
+  (void)device;
+  static const bool timing = std::getenv("DVM_TRACK_BATCH_TIMING") != nullptr;       // host-side phase times of a tick on stderr
+  using clk = std::chrono::steady_clock;
+  clk::time_point tp0 = clk::now(), tp1, tp2, tp3, tp4;
+  int rc = imgs ? dvm_track_begin_batch(t, h, imgs, count, rows, cols, stride, frame_stride, lap0, lap1) : dvm_track_begin_staged(t, h, count, rows, cols, lap0, lap1);
+  if (rc != DVM_OK) return rc;
+  tp1 = clk::now();
+  // the entry lists: 9 bytes per entry, in keypoint order
+  struct Entries { std::vector<int32_t> slot; std::vector<uint8_t> octave; std::vector<float> angle; int bad = 0; };
+  std::vector<Entries> E((size_t)count);
+  TickPool::get().run(count, 24, [&](int b) {
+    const dvmh_track_in_resident& a = in[b];
+    Entries& e = E[b];
+    e.slot.reserve((size_t)a.Nl); e.octave.reserve((size_t)a.Nl); e.angle.reserve((size_t)a.Nl);
+    for (int i = 0; i < a.Nl; i++) {
+      if (a.mp_l[i] < 0) continue;
+      if (a.outlier_l && a.outlier_l[i]) continue;
+      const int oct = a.kps_l[i].octave;
+      if (oct < 0 || oct >= nlevels) { e.bad = 1; return; }
+      e.slot.push_back(a.mp_l[i]); e.octave.push_back((uint8_t)oct); e.angle.push_back(a.kps_l[i].angle);
+    }
+  });
+  for (int b = 0; b < count; b++) if (E[b].bad) return DVM_ERR_INVALID;      // (a LastFrame octave outside the level tables)
+  tp2 = clk::now();
+  dvm_track_shared sh;
+  std::memset(&sh, 0, sizeof(sh));
+  std::memcpy(sh.bounds, bounds, 16);
+  sh.dist = nullptr; sh.scale_factors = scale_factors; sh.inv_level_sigma2 = inv_level_sigma2; sh.nlevels = nlevels;
+  if (K) { sh.cam.fx = K[0]; sh.cam.fy = K[1]; sh.cam.cx = K[2]; sh.cam.cy = K[3]; }     // (not read under a KannalaBrandt8 tracker)
+  sh.cam.huber_delta = 0.0;
+  sh.th_high = TH_HIGH; sh.check_ori = check_ori; sh.min_matches = 20;
+  std::vector<dvm_track_last> last((size_t)count);
+  std::vector<dvm_track_frame_out> fo((size_t)count);
+  std::vector<dvm_track_result> tr((size_t)count);
+  std::vector<std::vector<int32_t>> assign((size_t)count);
+  std::vector<std::vector<uint8_t>> outl((size_t)count);
+  std::vector<std::vector<dvm_keypoint>> un_local((size_t)count);
+  for (int b = 0; b < count; b++) {
+    const int cap = outs[b].cap;
+    assign[b].resize((size_t)cap); outl[b].resize((size_t)cap);
+    dvm_keypoint* un = outs[b].kps_un;
+    if (!un) { un_local[b].resize((size_t)cap); un = un_local[b].data(); }
+    fo[b] = dvm_track_frame_out{outs[b].kps, outs[b].desc, cap, un, assign[b].data(), outl[b].data(), nullptr};
+    dvm_track_last& L = last[b];
+    L.store = in[b].store; L.n = (int32_t)E[b].slot.size(); L.slot = E[b].slot.data(); L.octave = E[b].octave.data(); L.angle = E[b].angle.data();
+    L.Tcw_pred = *in[b].Tcw_pred; L.th = th;
+  }
+  std::vector<uint8_t> wide((size_t)count, 0);
+  for (int attempt = 0; attempt < 2; attempt++) {
+    if (attempt == 0) tp3 = clk::now();
+    rc = dvm_track_finish_batch_resident(t, h, count, last.data(), &sh, fo.data(), tr.data());
+    if (rc != DVM_OK) return rc;
+    if (attempt == 0) tp4 = clk::now();
+    bool any = false;
+    if (attempt == 0)
+      for (int b = 0; b < count; b++) if (tr[b].status == DVM_TRACK_FEW_MATCHES) { wide[b] = 1; any = true; last[b].th = 2.0f * th; }
+    if (!any) break;                 // Tracking.cc:2616-2624: "Not enough matches, wider window search" -- th changes, nothing is rebuilt here
+  }
+  for (int b = 0; b < count; b++) {
+    dvmh_track_result* out = &res[b];
+    const dvm_track_result& r = tr[b];
+    const int N = r.n;
+    const int32_t* slot = E[b].slot.data();
+    int32_t* mp_c = outs[b].mp_c; int32_t* dropped = outs[b].dropped;
+    out->n = r.n; out->mono_index = r.mono_index; out->n_requeried = r.n_requeried; out->wide_window = wide[b];
+    for (int j = 0; j < N; j++) { mp_c[j] = -1; dropped[j] = -1; }
+    out->nmatches_search = r.nmatches;
+    if (r.status != DVM_TRACK_COMPLETE) {     // not tracked: the matches of the (doubled) search stay as SearchByProjection left them
+      for (int j = 0; j < N; j++) if (assign[b][j] >= 0) mp_c[j] = slot[assign[b][j]];
+      out->nmatches = r.nmatches; out->tracked = 0; out->Tcw = *in[b].Tcw_pred;
+      for (int k = 0; k < 3; k++) out->pose[k] = (double)in[b].Tcw_pred->t[k];
+      for (int k = 0; k < 4; k++) out->pose[3 + k] = (double)in[b].Tcw_pred->q[k];
+      continue;
+    }
+    for (int j = 0; j < N; j++) {
+      if (assign[b][j] < 0) continue;
+      const int mp = slot[assign[b][j]];
+      if (outl[b][j]) dropped[j] = mp; else mp_c[j] = mp;
+    }
+    out->nmatches = r.nmatches_after; out->nmatches_map = r.nmatches_map; out->n_inliers = r.n_inliers; out->tracked = 1;
+    std::memcpy(out->pose, r.pose, 56);
+    for (int k = 0; k < 3; k++) out->Tcw.t[k] = (float)out->pose[k];
+    for (int k = 0; k < 4; k++) out->Tcw.q[k] = (float)out->pose[3 + k];
+  }
+  if (timing) {
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    std::fprintf(stderr, "track batch of %d (resident): begin (images in + enqueue) %.3f  entry lists %.3f  fill %.3f  finish (wait + results out) %.3f  rest %.3f ms\n", count,
+                 ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3), ms(tp3, tp4), ms(tp4, clk::now()));
+  }
+  return DVM_OK;
+}
+
+// The loop header of SearchByProjection(CurrentFrame, LastFrame) on the host for a list of entries whose map points are given as records:
+// dvm_host::BuildFrameQueries plus the three per-query arrays of the tracked-frame calls above, the counterpart of k_track_queries
+// (dvm_track_debug_build_queries).  Returns nq.
+extern "C" int dvmh_build_frame_queries(const dvm_se3f* Tcw_pred, const float* K, const dvm_camera_model* model, const float* bounds,
+                                        const float* scale_factors, int nlevels, int n, const int32_t* slot, const dvm_local_point* records,
+                                        const uint8_t* octave, const float* angle, float th, int32_t* q_entry, float* qx, float* qy, float* qr,
+                                        int32_t* qmin, int32_t* qmax, uint8_t* q_claims, float* q_angle, float* q_pos, uint8_t* qdesc) {
+  if (!Tcw_pred || !bounds || !scale_factors || n < 0 || (!K && !model) || (n && (!records || !octave || !angle || !q_entry || !qx || !qy || !qr ||
+      !qmin || !qmax || !q_claims || !q_angle || !q_pos || !qdesc)))
+    return DVM_ERR_INVALID;
+  if (model && !dvm_cam::model_ok(model->model, model->p)) return DVM_ERR_INVALID;
+  if (model) K = model->p;
+  std::vector<dvm_keypoint> kps((size_t)n);
+  std::vector<int32_t> mp_l((size_t)n);
+  std::vector<dvmh_map_point> mps((size_t)n);
+  for (int i = 0; i < n; i++) {
+    if ((int)octave[i] >= nlevels) return DVM_ERR_INVALID;
+    const dvm_local_point& r = records[slot ? slot[i] : i];
+    std::memset(&kps[i], 0, sizeof(kps[i]));
+    kps[i].octave = octave[i]; kps[i].angle = angle[i];
+    mp_l[i] = i;
+    std::memcpy(mps[i].pos, r.pos, 12); std::memcpy(mps[i].desc, r.desc, 32); mps[i].n_obs = r.n_obs;
+  }
+  FrameView C, L;
+  C.N = 0; C.Tcw = *Tcw_pred;
+  C.fx = K[0]; C.fy = K[1]; C.cx = K[2]; C.cy = K[3];
+  C.mpCamera = model && model->model == dvm_cam::kKannalaBrandt8 ? model : nullptr;
+  C.mnMinX = bounds[0]; C.mnMaxX = bounds[1]; C.mnMinY = bounds[2]; C.mnMaxY = bounds[3];
+  C.mvScaleFactors = scale_factors; C.nLevels = nlevels;
+  L = C;
+  L.N = n; L.mvKeysUn = kps.data(); L.mvpMapPoints = mp_l.data(); L.mvbOutlier = nullptr;
+  FrameQueries Q;
+  dvm_host::BuildFrameQueries(C, L, mps.data(), th, Q);
+  const int nq = (int)Q.qi.size();
+  for (int q = 0; q < nq; q++) {
+    const int i = Q.qi[q], mp = mp_l[i];
+    q_entry[q] = i; qx[q] = Q.qx[q]; qy[q] = Q.qy[q]; qr[q] = Q.qr[q]; qmin[q] = Q.qmin[q]; qmax[q] = Q.qmax[q];
+    q_claims[q] = mps[mp].n_obs > 0;
+    q_angle[q] = kps[i].angle;
+    q_pos[3 * q] = mps[mp].pos[0]; q_pos[3 * q + 1] = mps[mp].pos[1]; q_pos[3 * q + 2] = mps[mp].pos[2];
+    std::memcpy(qdesc + 32 * (size_t)q, Q.qdesc.data() + 32 * (size_t)q, 32);
+  }
+  return nq;
+}

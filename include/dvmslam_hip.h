@@ -1024,6 +1024,83 @@ typedef struct {
 int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_out* out,
                               dvm_track_local_result* res, int32_t* status);
 
+/* ---- An agent's map points resident on the device (csrc/map_store.cpp).  A map point is written rarely (LocalMapping after a local BA,
+ * a fuse or a culling step, under Map::mMutexMapUpdate) and read at camera rate by every frame that sees it: the store keeps the records
+ * in device memory, and the two halves of the tracked frame read them by slot (dvm_track_finish_batch_resident,
+ * dvm_track_local_map_batch_resident below) instead of carrying them up on every tick.
+ *   capacity  fixed at create: slots 0 .. capacity - 1, one dvm_local_point (72 B) each, device addresses stable, no growth
+ *             (DVM_ERR_INVALID for capacity < 1, DVM_ERR_CAPACITY when the memory cannot be had).
+ *   update    records[k] is written to slot slots[k].  Checked on the host before anything is queued: a NULL argument, a slot outside
+ *             [0, capacity) or a slot named twice in the call is DVM_ERR_INVALID and nothing is written.  The records are staged in
+ *             page-locked memory and scattered by a kernel on the STORE'S OWN STREAM; the call may return before the kernel has run.
+ *             Ordering is by events: every later call that reads the store makes its stream wait for the store's last update, and an
+ *             update waits for the last kernel that was queued to read the store -- it never overtakes a chain call in flight.  A second
+ *             update waits on the host until the first has left the staging block.
+ *   read      slots back, in the order asked (a slot may repeat); synchronous.  Tests and debugging.
+ *   Every call that names a slot never written (read, and the chain calls below) is DVM_ERR_INVALID, checked on the host against a
+ *   per-slot written flag before anything is queued: no kernel indexes a store with a value the host has not checked.
+ * Calls on ONE store -- update, read, and the chain calls that name it -- are not concurrent (the reference holds mMutexMapUpdate around
+ * the same writes); different stores are independent. */
+typedef struct dvm_map_store dvm_map_store;
+int dvm_map_store_create(int device, int capacity, dvm_map_store** out);
+void dvm_map_store_destroy(dvm_map_store* s);
+int dvm_map_store_capacity(const dvm_map_store* s);
+int dvm_map_store_update(dvm_map_store* s, int n, const int32_t* slots, const dvm_local_point* records);
+int dvm_map_store_read(dvm_map_store* s, int n, const int32_t* slots, dvm_local_point* out);
+
+/* ---- The first half reading a store: dvm_track_finish_batch with the projection queries built ON THE DEVICE (k_track_queries) from
+ * LastFrame's entry list -- the loop header of ORBmatcher.cc:1573-1611, what dvmh_track_with_motion_model builds on the host: x3Dc = Tcw *
+ * pos (Sophus' quaternion form), invzc = (float)(1.0 / z) with invzc < 0 skipped, the projection through the tracker's camera model, the
+ * four bound tests, radius = th * scale_factors[octave], levels octave - 1 .. octave + 1; the kept entries compacted in entry order (the
+ * claim replay is sequential in that order).  Per entry the host sends 9 bytes (slot, octave, angle) instead of a 69-byte query and
+ * projects nothing.  Behind the builder the chain is dvm_track_finish_batch's, with its state rules and statuses; count == 1 is the
+ * single frame; it may be called again after one begin (the wider attempt changes th only).
+ *   outs[b].assign[j] is the ENTRY NUMBER in last[b] matched to keypoint j, or -1: the caller's map point is slot[assign[j]].
+ *   last[b].n beyond the tracker's max_queries: DVM_ERR_CAPACITY.  A NULL array with n > 0, an octave >= p->nlevels, a store on another
+ *   device, a slot outside its store or never written: DVM_ERR_INVALID, before anything is queued (the begin stays valid).
+ *   Camera: pinhole fx * x / z + cx in float on (float)p->cam; under a KannalaBrandt8 tracker (dvm_tracker_set_camera_model)
+ *   dvm_cam::kb8_project on the tracker's model, and p->cam is not read.  Pinhole queries equal the host's bit for bit; KannalaBrandt8
+ *   queries differ where the device's atan2f and libm's differ in the last bit of theta. */
+typedef struct {
+  const dvm_map_store* store;      /* this agent's map points (may be NULL when n == 0) */
+  int32_t n;                       /* LastFrame entries that hold a map point and are not outliers, ascending keypoint index */
+  const int32_t* slot;             /* [n] store slot of the entry's map point */
+  const uint8_t* octave;           /* [n] LastFrame.mvKeys[i].octave */
+  const float* angle;              /* [n] LastFrame.mvKeysUn[i].angle */
+  dvm_se3f Tcw_pred;               /* mVelocity * mLastFrame.GetPose() */
+  float th;                        /* SearchByProjection's th of THIS call (15, or 30 on the wider attempt) */
+} dvm_track_last;                  /* 72 bytes */
+typedef struct {                   /* what the frames of a call share: the fields of dvm_track_queries that are not per query */
+  float bounds[4]; const dvm_distortion* dist; const float* scale_factors; const float* inv_level_sigma2; int32_t nlevels;
+  dvm_ba_camera cam; int32_t th_high, check_ori, min_matches;
+} dvm_track_shared;                /* 104 bytes */
+int dvm_track_finish_batch_resident(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_last* last, const dvm_track_shared* p,
+                                    const dvm_track_frame_out* outs, dvm_track_result* res);
+/* Test hook: k_track_queries alone on the tracker's own stream -- no begin, no image, the tracker's state untouched -- and the block copied
+ * back.  *stride = the call's per-query stride (the largest n rounded up to 64, at least 64); frame b's arrays begin at b * *stride
+ * elements (qdesc: x 32, q_pos: x 3), so every array holds count * stride elements; nq [count].  p->th_high / check_ori / min_matches and
+ * p->dist are not read. */
+int dvm_track_debug_build_queries(dvm_tracker* t, int count, const dvm_track_last* last, const dvm_track_shared* p, int32_t* nq,
+                                  int32_t* q_entry, float* qx, float* qy, float* qr, int32_t* qmin, int32_t* qmax, uint8_t* q_claims,
+                                  float* q_angle, float* q_pos, uint8_t* qdesc, int32_t* stride);
+/* The host-to-device bytes queued by the tracker's last finish (first_half) and last local-map call (second_half), resident or not: the
+ * query block or entry lists, tables or slot lists, with their per-frame parameters (the images are the extractor's and not counted).
+ * Either pointer may be NULL. */
+int dvm_tracker_last_upload_bytes(const dvm_tracker* t, int64_t* first_half, int64_t* second_half);
+
+/* ---- The second half reading stores: dvm_track_local_map_batch with every frame's table given as store slots (4 B per point instead of
+ * 72).  A gather kernel (k_store_gather) fills the chain's device table at the frames' offsets from the stores; everything behind it is
+ * dvm_track_local_map_batch's chain, and reservation, state rules, skipped frames, track_pts and outputs are exactly its own.  Accepted
+ * after either finish, resident or uploaded.  frame_mp and the outputs index the slot list (table positions), as they index pts there.
+ * A slot outside its store or never written, or a store on another device: DVM_ERR_INVALID before anything is queued. */
+typedef struct {
+  const dvm_map_store* store; const int32_t* slots; int32_t n;   /* mvpLocalMapPoints as store slots; n may be 0 */
+  const int32_t* frame_mp;                                       /* [N_b] index into slots (table position) or -1 */
+  float th; int32_t far_points; float th_far;
+} dvm_local_map_in_resident;                                     /* 48 bytes */
+int dvm_track_local_map_batch_resident(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in_resident* in,
+                                       const dvm_local_map_out* out, dvm_track_local_result* res, int32_t* status);
+
 /* ---- The other way into TrackLocalMap, Tracking::TrackReferenceKeyFrame (src/Tracking.cc:2461-2520), as ONE device chain: taken by
  * Tracking::Track (:1756-1765) when there is no motion model (no velocity yet, or within two frames of a relocalisation) or when
  * TrackWithMotionModel failed.  Frame::ComputeBoW (DBoW2 transform, levelsup 4) -> ORBmatcher(0.7, true).SearchByBoW(mpReferenceKF, F)

@@ -164,6 +164,30 @@ int dvmh_track_with_motion_model_batch_cam(dvm_tracker* t, dvm_orb* h, int devic
                                            const float* scale_factors, const float* inv_level_sigma2, int nlevels, float th, int check_ori,
                                            const dvmh_track_in* in, const dvmh_track_out* outs, dvmh_track_result* res);
 
+/* The batched call with every agent's map points resident on the device (dvm_map_store, include/dvmslam_hip.h): mp_l holds STORE SLOTS (or
+ * -1) in place of indices into mps, and the host projects nothing -- it packs LastFrame's entry lists from kps_l / mp_l / outlier_l (9 bytes
+ * per entry) and dvm_track_finish_batch_resident builds the queries on the device; frames below 20 matches run the wider attempt (th
+ * doubled, nothing rebuilt).  mp_c / dropped receive store slots.  Under a KannalaBrandt8 tracker the model is the one set on the tracker
+ * (dvm_tracker_set_camera_model) and K is not read (may be NULL).  Frame b's outputs equal dvmh_track_with_motion_model_batch on the same
+ * map points, with ids read as slots: bit for bit under the pinhole camera. */
+typedef struct {
+  const dvm_se3f* Tcw_pred;                  /* mVelocity * mLastFrame.GetPose() of this agent */
+  int32_t Nl; const dvm_keypoint* kps_l; const int32_t* mp_l; const uint8_t* outlier_l;   /* its LastFrame; mp_l: store slots or -1 */
+  const dvm_map_store* store;                /* its map points */
+} dvmh_track_in_resident;
+int dvmh_track_with_motion_model_batch_resident(dvm_tracker* t, dvm_orb* h, int device, int count, const uint8_t* imgs, int rows, int cols,
+                                                int stride, int64_t frame_stride, int lap0, int lap1, const float* K, const float* bounds,
+                                                const float* scale_factors, const float* inv_level_sigma2, int nlevels, float th, int check_ori,
+                                                const dvmh_track_in_resident* in, const dvmh_track_out* outs, dvmh_track_result* res);
+/* The loop header of SearchByProjection(CurrentFrame, LastFrame) (ORBmatcher.cc:1573-1611) on the host, for `n` LastFrame entries whose
+ * map points are records[slot[i]] (slot NULL: records[i]): what dvmh_track_with_motion_model builds before its finish, and the host
+ * counterpart of k_track_queries (dvm_track_debug_build_queries).  model NULL: the pinhole K; else the model's projection (K not read).
+ * Outputs hold up to n entries; q_entry[q] = the entry query q came from.  Returns nq, or a negative dvm_status. */
+int dvmh_build_frame_queries(const dvm_se3f* Tcw_pred, const float* K, const dvm_camera_model* model, const float* bounds,
+                             const float* scale_factors, int nlevels, int n, const int32_t* slot, const dvm_local_point* records,
+                             const uint8_t* octave, const float* angle, float th, int32_t* q_entry, float* qx, float* qy, float* qr,
+                             int32_t* qmin, int32_t* qmax, uint8_t* q_claims, float* q_angle, float* q_pos, uint8_t* qdesc);
+
 /* SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints), :44-205.  claimed_obs[j] != 0 <=> F.mvpMapPoints[j]->Observations() > 0 */
 int dvmh_search_by_projection_points(int device, int N, const dvm_keypoint* kps, const uint8_t* desc, int32_t* mp, const uint8_t* claimed_obs,
                                      const float* bounds, const float* scale_factors, int nlevels, const dvmh_tracked_point* pts, int npts, float th,
