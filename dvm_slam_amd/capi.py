@@ -2744,8 +2744,12 @@ class _FtPoints(C.Structure):   # == dvm_ft_points
                 ("desc", C.c_void_p), ("valid", C.c_void_p)]
 
 
+HIT_DTYPE = np.dtype([("point", "<i4"), ("idx", "<i4"), ("dist", "<i4")])   # == dvm_ft_hit
+
+
 class FuseTargets(_Chain):
     """dvm_fuse_targets: set() the target keyframes once (one upload, all grids in one launch), run() point tables against them."""
+    FORM_POINTS, FORM_SCW = 0, 1
 
     def __init__(self, device=0):
         self.n_targets = 0
@@ -2753,6 +2757,11 @@ class FuseTargets(_Chain):
         vp = C.c_void_p
         self.L.dvm_fuse_targets_set.argtypes = [vp, C.c_int32, vp]
         self.L.dvm_fuse_targets_run.argtypes = [vp, vp, vp, C.c_float, vp, vp]
+        self.L.dvm_fuse_targets_set_cam.argtypes = [vp, C.c_int32, vp, vp, vp]
+        self.L.dvm_fuse_targets_reserve_hits.argtypes = [vp, C.c_int32]
+        self.L.dvm_fuse_targets_run_hits.argtypes = [vp, vp, vp, C.c_float, vp, vp, C.c_int32, vp]
+        for f in (self.L.dvm_fuse_targets_set_cam, self.L.dvm_fuse_targets_reserve_hits, self.L.dvm_fuse_targets_run_hits):
+            f.restype = C.c_int32
 
     def reserve(self, max_points, max_targets, max_total_target_keypoints):
         self._reserve(max_points, max_targets, max_total_target_keypoints)
@@ -2780,13 +2789,54 @@ class FuseTargets(_Chain):
             s.log_scale_factor, s.n_levels = v.mfLogScaleFactor, v.nLevels
         return arr, keep
 
-    def set(self, kfs):
+    def set(self, kfs, models=None, forms=None):
+        """models: one CameraModel per target (dvm_fuse_targets_set_cam; under model 1 a keyframe's K is not read and may be absent), forms:
+        one of FORM_POINTS / FORM_SCW per target (under FORM_SCW the keyframe's "Tcw" and "Ow" are what sim3_to_se3(Scw) returns; without
+        an "Ow" key the centre is derived from Tcw); both None: dvm_fuse_targets_set."""
         arr, keep = self.targets(kfs)
-        self.set_raw(arr, len(kfs))
+        for t, kf in enumerate(kfs):
+            if kf.get("Ow") is not None:
+                arr[t].Ow = (C.c_float * 3)(*np.asarray(kf["Ow"], np.float32).reshape(3))
+        if models is None and forms is None:
+            return self.set_raw(arr, len(kfs))
+        m = None
+        if models is not None:
+            m = (CameraModel * max(len(kfs), 1))()
+            for t, x in enumerate(models):
+                m[t] = x
+        f = None if forms is None else np.ascontiguousarray(forms, np.uint8)
+        check(self.L.dvm_fuse_targets_set_cam(self.h, len(kfs), C.addressof(arr), None if m is None else C.addressof(m), _ptr(f)))
+        self.n_targets = len(kfs)
 
     def set_raw(self, arr, n):
         check(self.L.dvm_fuse_targets_set(self.h, int(n), C.addressof(arr)))
         self.n_targets = int(n)
+
+    def reserve_hits(self, max_hits):
+        check(self.L.dvm_fuse_targets_reserve_hits(self.h, int(max_hits)))
+
+    def run_hits(self, pts, th=3.0, skip=None, hit_cap=None, guard=0):
+        """dvm_fuse_targets_run_hits.  Returns (hit_off[T + 1], hits[n_hits] of HIT_DTYPE); hit_cap None: as many as there can be.  A
+        DvmError of code -3 carries hit_off and n_hits (the full counts) and, with guard > 0, `tail`: the guard entries behind hits[hit_cap]."""
+        P, keep = map_points_view(pts)
+        n, T = P.n, self.n_targets
+        s = _FtPoints()
+        s.n, s.pos, s.normal, s.min_dist, s.max_dist, s.desc = n, P.pos, P.normal, P.min_dist, P.max_dist, P.desc
+        va = None if pts.get("valid") is None else np.ascontiguousarray(pts["valid"], np.uint8)
+        s.valid = _ptr(va)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(T, n)
+        cap = T * n if hit_cap is None else int(hit_cap)
+        off = np.full(T + 1, -7, np.int32)
+        hits = np.empty(cap + guard + 1, HIT_DTYPE)
+        hits.view(np.int32)[3 * cap:] = -7
+        nh = C.c_int32(-7)
+        rc = self.L.dvm_fuse_targets_run_hits(self.h, C.addressof(s), _ptr(sk), float(th), _ptr(off), _ptr(hits), cap, C.byref(nh))
+        try:
+            check(rc)
+        except DvmError as e:
+            e.hit_off, e.n_hits, e.tail = off, nh.value, hits[cap:cap + guard].copy()
+            raise
+        return off, hits[:nh.value]
 
     def run(self, pts, th=3.0, skip=None, want_dist=True):
         """pts: dict(pos, normal, min_dist, max_dist, desc[, valid]); skip: [T, n] uint8 or None.  Returns (best_idx[T, n], best_dist[T, n])
@@ -2816,6 +2866,64 @@ def fuse_targets(kfs, P, in_kf, th, device=0):
                 C.c_void_p(_ptr(bi)))
     check(min(rc, 0))
     return rc, bi
+
+
+def _views_and_models(kfs, models):
+    T = len(kfs)
+    views = (_KeyFrameView * max(T, 1))()
+    for t, kv in enumerate(kfs):
+        views[t] = kv[0]
+    m = None
+    if models is not None:
+        m = (CameraModel * max(T, 1))()
+        for t, x in enumerate(models):
+            m[t] = x
+    return views, m
+
+
+def fuse_targets_cam(kfs, models, P, in_kf, th, device=0):
+    """dvmh_fuse_targets_cam: fuse_targets with one CameraModel per keyframe (None: fuse_targets).  Returns (count, best_idx[T, n])."""
+    T, n = len(kfs), P[0].n
+    views, m = _views_and_models(kfs, models)
+    bi = np.full((T, n), -7, np.int32)
+    ik = None if in_kf is None else np.ascontiguousarray(in_kf, np.uint8).reshape(T, n)
+    rc = _hcall("dvmh_fuse_targets_cam", C.c_int32, C.c_int32(device), C.c_int32(T), C.byref(views), None if m is None else C.byref(m), C.byref(P[0]),
+                C.c_void_p(_ptr(ik)), C.c_float(th), C.c_void_p(_ptr(bi)))
+    check(min(rc, 0))
+    return rc, bi
+
+
+def fuse_sim3_targets(kfs, Scws, P, th, models=None, hit_cap=None, device=0):
+    """dvmh_fuse_sim3_targets: the search part of Fuse(pKF, Scw, vpPoints, th, .) for all keyframes as one chain.  kfs = keyframe_view()
+    results (with their mp arrays), Scws [T, 7] Sim3f.  Returns (hit_off[T + 1], hits[n_hits] of HIT_DTYPE); a DvmError of code -3 carries
+    hit_off (the full counts)."""
+    T, n = len(kfs), P[0].n
+    views, m = _views_and_models(kfs, models)
+    S = (_Sim3View * max(T, 1))()
+    for t in range(T):
+        S[t] = _sim3_view(Scws[t])
+    cap = T * n if hit_cap is None else int(hit_cap)
+    off = np.full(T + 1, -7, np.int32)
+    hits = np.empty(cap + 1, HIT_DTYPE)
+    rc = _hcall("dvmh_fuse_sim3_targets", C.c_int32, C.c_int32(device), C.c_int32(T), C.byref(views), C.byref(S), None if m is None else C.byref(m),
+                C.byref(P[0]), C.c_float(th), C.c_void_p(_ptr(off)), C.c_void_p(_ptr(hits)), C.c_int32(cap))
+    try:
+        check(min(rc, 0))
+    except DvmError as e:
+        e.hit_off = off
+        raise
+    return off, hits[:rc]
+
+
+def fuse_sim3_apply(KF, P, hits):
+    """dvmh_fuse_sim3_apply (host code only): the apply step of Fuse(pKF, Scw, ...) from one keyframe's hits; KF's mp array is updated in
+    place.  Returns (nFused, replace)."""
+    hits = np.ascontiguousarray(hits, HIT_DTYPE)
+    rep = np.zeros(max(P[0].n, 1), np.int32)
+    n = _hcall("dvmh_fuse_sim3_apply", C.c_int32, C.byref(KF[0]), C.byref(P[0]), C.c_void_p(_ptr(hits)), C.c_int32(len(hits)), C.c_void_p(rep.ctypes.data))
+    if n < 0:
+        raise DvmError(n, "dvmh_fuse_sim3_apply: bad argument")
+    return n, rep[:P[0].n]
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -759,11 +759,18 @@ int ORBmatcher::Fuse(KeyFrameView& KF, const Sim3View& Scw, const MapPointsView&
   std::vector<dvm_projection> proj;
   int rc = project_search(KF, Tcw, Ow, P, valid.data(), nullptr, th, false, res, proj);
   if (rc != DVM_OK) return rc;
+  std::vector<dvm_ft_hit> hits;
+  for (int i = 0; i < P.n; i++)
+    if (valid[i] && res[i].best_idx >= 0 && res[i].best_dist <= TH_LOW) hits.push_back(dvm_ft_hit{i, res[i].best_idx, res[i].best_dist});
+  return FuseApply(KF, P, hits.data(), (int)hits.size(), vpReplacePoint);
+}
+
+int ORBmatcher::FuseApply(KeyFrameView& KF, const MapPointsView& P, const dvm_ft_hit* hits, int n_hits, int32_t* vpReplacePoint) {
+  for (int i = 0; i < P.n; i++) vpReplacePoint[i] = -1;
   int nFused = 0;
   std::vector<uint8_t> fresh(KF.N, 0);
-  for (int i = 0; i < P.n; i++) {
-    if (!valid[i] || res[i].best_idx < 0 || res[i].best_dist > TH_LOW) continue;
-    const int bestIdx = res[i].best_idx;
+  for (int k = 0; k < n_hits; k++) {
+    const int i = hits[k].point, bestIdx = hits[k].idx;
     const int pMPinKF = KF.mvpMapPoints[bestIdx];
     if (pMPinKF >= 0) {
       if (fresh[bestIdx] || !(KF.mpBad && KF.mpBad[bestIdx])) vpReplacePoint[i] = pMPinKF;
@@ -1143,11 +1150,15 @@ int dvmh_fuse(int device, const dvmh_keyframe_view* KF, const dvmh_map_points_vi
   dvm_host::ORBmatcher m(0.6f, true, device);
   return m.Fuse(KeyFrameView(*KF), MapPointsView(*P), inKF, th, best_idx);
 }
-int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targets, const dvmh_map_points_view* P, const uint8_t* inKF, float th,
-                      int32_t* best_idx) {
-  if (n_targets < 0 || (n_targets > 0 && !targets) || !P || P->n < 0) return DVM_ERR_INVALID;
+namespace {
+// The calling thread's Fuse chain (dvmh_fuse_targets[_cam], dvmh_fuse_sim3_targets) with the targets set: the keyframes as dvm_ft_target --
+// under an Scw (DVM_FT_FORM_SCW on every target) with the pose and centre Sim3ToSE3 derives --, the reservation grown where it has to
+// be, dvm_fuse_targets_set_cam.  *h: the handle.
+int FuseChainSet(int device, int n_targets, const dvmh_keyframe_view* targets, const dvm_sim3f* Scw, const dvm_camera_model* models, int n_points,
+                 dvm_fuse_targets** h) {
   thread_local FuseTargetsSlot slot;
   { const int rc = slot.open(device); if (rc != DVM_OK) return rc; }
+  *h = slot.h;
   std::vector<dvm_ft_target> tg((size_t)n_targets);
   int64_t total = 0;
   for (int t = 0; t < n_targets; t++) {
@@ -1155,8 +1166,12 @@ int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targe
     dvm_ft_target& k = tg[t];
     std::memset(&k, 0, sizeof(k));
     k.n = K.N; k.kps = K.mvKeysUn; k.desc = K.mDescriptors;
-    k.Tcw = K.Tcw;
-    std::memcpy(k.Ow, K.Twc.t, 12);                 // KeyFrame::GetCameraCenter() = mTwc.translation()
+    if (Scw) {
+      dvm_host::Sim3ToSE3(Scw[t], k.Tcw, k.Ow);
+    } else {
+      k.Tcw = K.Tcw;
+      std::memcpy(k.Ow, K.Twc.t, 12);               // KeyFrame::GetCameraCenter() = mTwc.translation()
+    }
     k.fx = K.fx; k.fy = K.fy; k.cx = K.cx; k.cy = K.cy;
     k.min_x = K.mnMinX; k.max_x = K.mnMaxX; k.min_y = K.mnMinY; k.max_y = K.mnMaxY;
     k.scale_factors = K.mvScaleFactors; k.inv_level_sigma2 = K.mvInvLevelSigma2;
@@ -1164,13 +1179,22 @@ int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targe
     total += std::max(K.N, 0);
   }
   // growth only, with headroom; sizes no reservation can hold are left to the calls' own checks (they name the offending target)
-  const int np = std::max(slot.cap[0], P->n), nt = std::max(slot.cap[1], n_targets);
-  if (n_targets <= 65535 && total <= (int64_t)n_targets * 8192 && (int64_t)np * nt <= ((int64_t)1 << 27) && !slot.holds(P->n, n_targets, total)) {
+  const int np = std::max(slot.cap[0], n_points), nt = std::max(slot.cap[1], n_targets);
+  if (n_targets <= 65535 && total <= (int64_t)n_targets * 8192 && (int64_t)np * nt <= ((int64_t)1 << 27) && !slot.holds(n_points, n_targets, total)) {
     const int tot = (int)std::min<int64_t>(std::max<int64_t>(slot.cap[2], total + total / 4), (int64_t)nt * 8192);
     const int rc = slot.reserve(np, nt, tot);
     if (rc != DVM_OK) return rc;
   }
-  int rc = dvm_fuse_targets_set(slot.h, n_targets, tg.data());
+  if (!Scw && !models) return dvm_fuse_targets_set(slot.h, n_targets, tg.data());
+  const std::vector<uint8_t> forms((size_t)n_targets, Scw ? DVM_FT_FORM_SCW : DVM_FT_FORM_POINTS);
+  return dvm_fuse_targets_set_cam(slot.h, n_targets, tg.data(), models, forms.data());
+}
+}  // namespace
+int dvmh_fuse_targets_cam(int device, int n_targets, const dvmh_keyframe_view* targets, const dvm_camera_model* models,
+                          const dvmh_map_points_view* P, const uint8_t* inKF, float th, int32_t* best_idx) {
+  if (n_targets < 0 || (n_targets > 0 && !targets) || !P || P->n < 0) return DVM_ERR_INVALID;
+  dvm_fuse_targets* h = nullptr;
+  int rc = FuseChainSet(device, n_targets, targets, nullptr, models, P->n, &h);
   if (rc != DVM_OK) return rc;
   const size_t n = (size_t)P->n, E = n * (size_t)n_targets;
   if (E == 0) return 0;
@@ -1180,11 +1204,50 @@ int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targe
   dvm_ft_points pts;
   pts.n = P->n; pts.pos = P->pos; pts.normal = P->normal; pts.min_dist = P->min_dist; pts.max_dist = P->max_dist; pts.desc = P->desc;
   pts.valid = valid.data();
-  rc = dvm_fuse_targets_run(slot.h, &pts, inKF, th, best_idx, nullptr);
+  rc = dvm_fuse_targets_run(h, &pts, inKF, th, best_idx, nullptr);
   if (rc != DVM_OK) return rc;
   int nFused = 0;
   for (size_t e = 0; e < E; e++) nFused += best_idx[e] >= 0 ? 1 : 0;
   return nFused;
+}
+int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targets, const dvmh_map_points_view* P, const uint8_t* inKF, float th,
+                      int32_t* best_idx) {
+  return dvmh_fuse_targets_cam(device, n_targets, targets, nullptr, P, inKF, th, best_idx);
+}
+int dvmh_fuse_sim3_targets(int device, int n_targets, const dvmh_keyframe_view* targets, const dvm_sim3f* Scw, const dvm_camera_model* models,
+                           const dvmh_map_points_view* P, float th, int32_t* hit_off, dvm_ft_hit* hits, int hit_cap) {
+  if (n_targets < 0 || (n_targets > 0 && (!targets || !Scw)) || !P || P->n < 0 || (P->n > 0 && !P->id) || !hit_off || hit_cap < 0 || (hit_cap > 0 && !hits))
+    return DVM_ERR_INVALID;
+  dvm_fuse_targets* h = nullptr;
+  int rc = FuseChainSet(device, n_targets, targets, Scw, models, P->n, &h);
+  if (rc != DVM_OK) return rc;
+  rc = dvm_fuse_targets_reserve_hits(h, hit_cap);     // (grow-only: nothing happens where the block holds hit_cap)
+  if (rc != DVM_OK) return rc;
+  // target t's mask: isBad(), or the point among spAlreadyFound = pKF->GetMapPoints() at entry (ORBmatcher.cc:1250, :1262)
+  const size_t n = (size_t)P->n;
+  std::vector<uint8_t> skip(n * (size_t)n_targets, 0);
+  std::vector<int32_t> already;
+  for (int t = 0; t < n_targets; t++) {
+    const dvmh_keyframe_view& K = targets[t];
+    already.assign(K.mvpMapPoints, K.mvpMapPoints + (K.mvpMapPoints ? std::max(K.N, 0) : 0));
+    std::sort(already.begin(), already.end());
+    uint8_t* row = skip.data() + (size_t)t * n;
+    for (size_t i = 0; i < n; i++)
+      if ((P->bad && P->bad[i]) || std::binary_search(already.begin(), already.end(), P->id[i])) row[i] = 1;
+  }
+  dvm_ft_points pts;
+  pts.n = P->n; pts.pos = P->pos; pts.normal = P->normal; pts.min_dist = P->min_dist; pts.max_dist = P->max_dist; pts.desc = P->desc;
+  pts.valid = nullptr;
+  int32_t total = 0;
+  rc = dvm_fuse_targets_run_hits(h, &pts, skip.data(), th, hit_off, hits, hit_cap, &total);
+  return rc != DVM_OK ? rc : total;
+}
+int dvmh_fuse_sim3_apply(dvmh_keyframe_view* KF, const dvmh_map_points_view* P, const dvm_ft_hit* hits, int n_hits, int32_t* replace) {
+  if (!KF || !P || P->n < 0 || n_hits < 0 || (n_hits > 0 && (!hits || !KF->mvpMapPoints || !P->id)) || (P->n > 0 && !replace)) return DVM_ERR_INVALID;
+  for (int k = 0; k < n_hits; k++)
+    if ((uint32_t)hits[k].point >= (uint32_t)P->n || (uint32_t)hits[k].idx >= (uint32_t)std::max(KF->N, 0)) return DVM_ERR_INVALID;
+  KeyFrameView K(*KF);                    // (the function writes through K.mvpMapPoints, the caller's array)
+  return dvm_host::ORBmatcher::FuseApply(K, MapPointsView(*P), hits, n_hits, replace);
 }
 int dvmh_search_by_bow_targets(int device, const dvmh_keyframe_view* KF1, int n_targets, const dvmh_keyframe_view* targets, float nnratio,
                                int check_ori, int32_t* matches12, int32_t* idx2, int32_t* nmatches) {

@@ -129,6 +129,9 @@ class ORBmatcher {
   // int Fuse(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints, float th, vector<MapPoint*>& vpReplacePoint)
   // (:1236-1345), whole function: KF.mvpMapPoints receives the added points, vpReplacePoint[i] the id to replace (-1 none).
   int Fuse(KeyFrameView& KF, const Sim3View& Scw, const MapPointsView& vpPoints, float th, int32_t* vpReplacePoint);
+  // its apply step (:1329-1341) from the hits of the search (point i, keypoint idx; ascending point): vpReplacePoint [vpPoints.n] is
+  // written whole.  Returns nFused = n_hits.  No device work.
+  static int FuseApply(KeyFrameView& KF, const MapPointsView& vpPoints, const dvm_ft_hit* hits, int n_hits, int32_t* vpReplacePoint);
   // int SearchByProjection(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched,
   //                        int th, float ratioHamming)   (:395-496), whole function.  vpMatched: KF.N ids (in/out).
   int SearchByProjection(const KeyFrameView& KF, const Sim3View& Scw, const MapPointsView& vpPoints, int32_t* vpMatched, int th,

@@ -277,7 +277,7 @@ int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const floa
  * entries that take the models of TWO keyframes want one model type for both (the parameters may differ per keyframe): a pair of a
  * pinhole and a KannalaBrandt8 keyframe is DVM_ERR_INVALID -- the reference's mixed pair is out of scope.  The tracked-frame
  * chains take the agent's model as state of the tracker (dvm_tracker_set_camera_model below).  The pools (dvm_orb_pool_*, dvm_match_pool_*,
- * dvm_pose_pool_*), the Fuse / BoW chains, the sequential-order BA windows (dvm_ba_optimize_windows), dvm_ba_optimize_batch,
+ * dvm_pose_pool_*), the BoW chain, the sequential-order BA windows (dvm_ba_optimize_windows), dvm_ba_optimize_batch,
  * dvm_ba_set_problem_sharded and OptimizeSim3 are pinhole-only. */
 typedef struct { int32_t model;   /* 0 pinhole, 1 KannalaBrandt8 */
                  float p[8];      /* fx, fy, cx, cy, k1, k2, k3, k4: mvParameters, float as the reference stores them */
@@ -559,6 +559,40 @@ int dvm_fuse_targets_run(dvm_fuse_targets* h, const dvm_ft_points* P, const uint
  * last run (read after a run) */
 int dvm_fuse_targets_profiling(dvm_fuse_targets* h, int enable);
 int dvm_fuse_targets_last_kernel_ms(dvm_fuse_targets* h, float* ms);
+/* dvm_fuse_targets_set with a camera model and a form PER TARGET (dvm_camera_model above).
+ *   models [n_targets], or NULL: every target projects with its own fx, fy, cx, cy.  models[t] is target t's pKF->mpCamera: under model 1 the
+ *          projection is dvm_cam::kb8_project on models[t].p and targets[t].fx .. cy are not read -- the rule of dvm_project_search_cam.
+ *          Targets of both model types may be mixed in one call (rows are independent; after a merge an agent's map holds keyframes of
+ *          other agents' cameras).
+ *   forms  [n_targets], or NULL: all DVM_FT_FORM_POINTS.  Under DVM_FT_FORM_SCW targets[t].Tcw and Ow are what dvm_host::Sim3ToSE3(Scw)
+ *          derives (as for dvm_project_search), inv_level_sigma2 is not read and may be NULL, and acceptance stays best_dist <= 50.
+ * Contract: row t of a run equals bit for bit what dvm_project_search_cam returns for target t alone with that target's model,
+ * gate_inv_sigma2 = forms[t] ? NULL : inv_level_sigma2, gate = 5.99 and valid[i] && !skip[t * n + i], followed by the <= 50 rule.
+ * dvm_fuse_targets_set(h, n, targets) is dvm_fuse_targets_set_cam(h, n, targets, NULL, NULL).
+ * Errors: those of dvm_fuse_targets_set, in both forms (the zero focal length of the target's own fx, fy only where no model is given; a
+ * missing inv_level_sigma2 only under DVM_FT_FORM_POINTS), and DVM_ERR_INVALID for a model outside {0, 1}, a zero focal length of a given
+ * model, or a form outside {0, 1}; each names the target, is reported before anything runs and leaves the handle and its resident
+ * targets usable. */
+#define DVM_FT_FORM_POINTS 0  /* Fuse(pKF, vpMapPoints, th): the 5.99 gate on inv_level_sigma2 */
+#define DVM_FT_FORM_SCW    1  /* Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) search part (ORBmatcher.cc:1256-1330): no chi2 gate */
+int dvm_fuse_targets_set_cam(dvm_fuse_targets* h, int n_targets, const dvm_ft_target* targets,
+                             const dvm_camera_model* models /* [n_targets], or NULL: the targets' fx, fy, cx, cy */,
+                             const uint8_t* forms /* [n_targets], or NULL: all DVM_FT_FORM_POINTS */);
+/* The hits of a run instead of its dense rows (LoopClosing::SearchAndFuse sizes: over a hundred keyframes x thousands of points, of which
+ * a few thousand entries are hits).  The search kernel writes its dense rows to device memory as dvm_fuse_targets_run does; a stable
+ * compaction (count per target, scan over the targets, write -- three launches, no workgroup waits on another) then writes hit_off and the
+ * hits into a mapped page-locked block, and ONE synchronisation follows.  Nothing of size T x n comes back to the host.
+ *   hits[hit_off[t] .. hit_off[t + 1]) are target t's entries with best_idx >= 0, in ascending point, with the idx and dist that
+ *   dvm_fuse_targets_run returns on the same inputs; *n_hits (may be NULL) is the total = hit_off[T].
+ * dvm_fuse_targets_reserve_hits: the block for up to max_hits hits (grow-only; a dvm_fuse_targets_reserve that grows keeps it).
+ * dvm_fuse_targets_run_hits before it is DVM_ERR_INVALID.  A total beyond hit_cap or the reservation: DVM_ERR_CAPACITY; *n_hits and hit_off
+ * still hold the full counts (the caller sizes a repeat from them), hits is unspecified, the device has written nothing past its block
+ * (the write kernel checks every position) and the handle stays usable.  T = 0 and P->n = 0 write hit_off (all zero) and *n_hits = 0.
+ * sizeof(dvm_ft_hit) == 12. */
+typedef struct { int32_t point, idx, dist; } dvm_ft_hit;
+int dvm_fuse_targets_reserve_hits(dvm_fuse_targets* h, int max_hits);
+int dvm_fuse_targets_run_hits(dvm_fuse_targets* h, const dvm_ft_points* P, const uint8_t* skip, float th,
+                              int32_t* hit_off /* [T + 1] */, dvm_ft_hit* hits, int hit_cap, int32_t* n_hits);
 
 /* The BoW searches of LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:722-731): ORBmatcher::SearchByBoW(mpCurrentKF, vpCovKFi[j],
  * vvpMatchedMPs[j]) (ORBmatcher.cc:709-834) once per candidate and covisible keyframe -- up to 11 per candidate, 33 per candidate list --

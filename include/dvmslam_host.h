@@ -242,6 +242,21 @@ int dvmh_fuse_targets(int device, int n_targets, const dvmh_keyframe_view* targe
                       int32_t* best_idx);
 /* Fuse(pKF, Scw, vpPoints, th, vpReplacePoint), :1236-1345: KF->mvpMapPoints receives the added points, replace[i] the id to replace */
 int dvmh_fuse_sim3(int device, dvmh_keyframe_view* KF, const dvm_sim3f* Scw, const dvmh_map_points_view* P, float th, int32_t* replace);
+/* dvmh_fuse_targets on a camera model per target (dvm_fuse_targets_set_cam; models NULL: dvmh_fuse_targets bit for bit).  Under model 1
+ * targets[t].fx .. cy are not read.  A model outside {0, 1} or with a zero focal length: DVM_ERR_INVALID. */
+int dvmh_fuse_targets_cam(int device, int n_targets, const dvmh_keyframe_view* targets, const dvm_camera_model* models,
+                          const dvmh_map_points_view* P, const uint8_t* inKF, float th, int32_t* best_idx);
+/* The search part of Fuse(pKF, Scw, vpPoints, th, .) for every keyframe of LoopClosing::SearchAndFuse (LoopClosing.cc:2132-2205) as one
+ * chain: dvm_fuse_targets_set_cam with DVM_FT_FORM_SCW on every target + dvm_fuse_targets_run_hits.  Target t's mask is dvmh_fuse_sim3's:
+ * P->bad[i], or P->id[i] among targets[t].mvpMapPoints at entry.  hit_off [n_targets + 1]; hits [hit_cap] (target t's are
+ * hits[hit_off[t] .. hit_off[t + 1]), ascending point).  Returns the number of hits; DVM_ERR_CAPACITY where they exceed hit_cap (hit_off then
+ * still holds the full counts: hit_off[n_targets] sizes the repeat).  The chain handle is dvmh_fuse_targets' (the calling thread's). */
+int dvmh_fuse_sim3_targets(int device, int n_targets, const dvmh_keyframe_view* targets, const dvm_sim3f* Scw /* [n_targets] */,
+                           const dvm_camera_model* models /* or NULL */, const dvmh_map_points_view* P, float th,
+                           int32_t* hit_off, dvm_ft_hit* hits, int hit_cap);
+/* The apply step (:1329-1341) of one keyframe from its hits (ascending point): KF->mvpMapPoints receives the added points, replace[i]
+ * (i < P->n) the id to replace (-1 none).  Returns nFused.  Pure host code.  dvmh_fuse_sim3 == its own search + this. */
+int dvmh_fuse_sim3_apply(dvmh_keyframe_view* KF, const dvmh_map_points_view* P, const dvm_ft_hit* hits, int n_hits, int32_t* replace);
 /* SearchByProjection(pKF, Scw, vpPoints, [vpPointsKFs,] vpMatched, [vpMatchedKF,] th, ratioHamming), :395-603; point_kf / matched_kf may be NULL */
 int dvmh_search_by_projection_sim3(int device, const dvmh_keyframe_view* KF, const dvm_sim3f* Scw, const dvmh_map_points_view* P, const int32_t* point_kf,
                                    int32_t* matched, int32_t* matched_kf, int th, float ratio_hamming, int* requeried);
