@@ -180,6 +180,7 @@ def lib():
     L.dvm_ba_stream.restype = vp
     L.dvm_optimize_sim3.argtypes = [i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, C.c_double, vp, vp]
     L.dvm_pose_optimize.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, C.POINTER(BaCamera), vp, vp, vp]
+    _declare(L, _TRACK_API)
     _LIB = L
     return L
 
@@ -1037,6 +1038,7 @@ def host_lib():
         _HOST.dvmh_search_by_projection_frames.restype = C.c_int32
         _HOST.dvmh_search_by_projection_frames.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int32,
                                                            C.c_int32, vp, vp, vp, vp, C.c_float, C.c_int32, vp]
+        _declare(_HOST, _TRACK_HOST_API)
     return _HOST
 
 
@@ -1112,145 +1114,6 @@ class Distortion(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
 
 
-class Tracker:
-    """dvm_tracker + dvmh_track_with_motion_model: Frame::Frame -> ExtractORB and Tracking::TrackWithMotionModel of one frame as ONE
-    device chain behind one synchronisation (reference src/Frame.cc:371-411, src/Tracking.cc:2584-2667)."""
-
-    def __init__(self, ext: "OrbExtractor", device=0, max_queries=None):
-        self.L, self.H, self.ext, self.device = lib(), host_lib(), ext, device
-        self.t = C.c_void_p()
-        f = self.L.dvm_tracker_create
-        f.restype = C.c_int32; f.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-        check(f(device, ext.cap, max_queries or ext.cap, C.byref(self.t)))
-
-    def close(self):
-        if getattr(self, "t", None) and self.t.value:
-            f = self.L.dvm_tracker_destroy
-            f.restype = None; f.argtypes = [C.c_void_p]
-            f(self.t)
-            self.t = C.c_void_p()
-
-    __del__ = close
-
-    def set_camera_model(self, model):
-        """dvm_tracker_set_camera_model: the camera of the agent this tracker serves, for every chain of the tracker.  model: a CameraModel, or
-        None for the default (the pinhole K of each call).  Drops what the last begin / finish prepared for the second half."""
-        f = self.L.dvm_tracker_set_camera_model
-        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_void_p]
-        check(f(self.t, _model_ref(model)))
-
-    def track(self, img, Tcw_pred, K, bounds, scale_factors, inv_sigma2, kps_l, mp_l, outlier_l, mps, th=15.0, check_ori=True, dist=None,
-              lap=(0, 1000), model=None):
-        """Tcw_pred: 7 floats (qx, qy, qz, qw, t).  model: a CameraModel (dvmh_track_with_motion_model_cam: the tracker is set to it and K,
-        which may then be None, is not read), or None for the pinhole K.  Returns a dict: n, kps, desc, kps_un, mp (mvpMapPoints after the
-        outlier drop), dropped, pose (7 doubles: t, q), and the counters of dvmh_track_result."""
-        if K is None:
-            if model is None:
-                raise ValueError("K is needed without a camera model")
-            K = model.p[:4]
-        img = np.ascontiguousarray(img, np.uint8)
-        cap = self.ext.cap
-        kps = np.empty(cap, KP_DTYPE); kun = np.empty(cap, KP_DTYPE); desc = np.empty((cap, 32), np.uint8)
-        mp = np.empty(cap, np.int32); dropped = np.empty(cap, np.int32)
-        kps_l = np.ascontiguousarray(kps_l, KP_DTYPE); mp_l = np.ascontiguousarray(mp_l, np.int32)
-        outl = None if outlier_l is None else np.ascontiguousarray(outlier_l, np.uint8)
-        f4 = [np.ascontiguousarray(a, np.float32) for a in (Tcw_pred, K, bounds, scale_factors, inv_sigma2)]
-        mps = np.ascontiguousarray(mps, MAP_POINT_DTYPE)
-        res = TrackResult()
-        fn = self.H.dvmh_track_with_motion_model if model is None else self.H.dvmh_track_with_motion_model_cam
-        fn.restype = C.c_int32; fn.argtypes = None
-        vp = C.c_void_p
-        cam = () if model is None else (C.byref(model),)
-        rc = fn(self.t, self.ext.h, C.c_int32(self.device), vp(img.ctypes.data), C.c_int32(img.shape[0]), C.c_int32(img.shape[1]), C.c_int32(img.strides[0]),
-                C.c_int32(lap[0]), C.c_int32(lap[1]), _p(f4[0]), _p(f4[1]), *cam, _p(f4[2]), None if dist is None else C.byref(dist), _p(f4[3]), _p(f4[4]),
-                C.c_int32(len(f4[3])), C.c_int32(len(kps_l)), _p(kps_l), _p(mp_l), None if outl is None else _p(outl), _p(mps), C.c_float(float(th)),
-                C.c_int32(int(check_ori)), _p(kps), _p(desc), C.c_int32(cap), _p(kun), _p(mp), _p(dropped), C.byref(res))
-        check(rc)
-        n = res.n
-        out = {k: getattr(res, k) for k in ("n", "mono_index", "nmatches", "nmatches_search", "nmatches_map", "n_inliers", "wide_window",
-                                            "replayed_on_host", "tracked", "n_requeried")}
-        out.update(kps=kps[:n], kps_un=kun[:n], desc=desc[:n], mp=mp[:n], dropped=dropped[:n], pose=np.array(res.pose[:], np.float64),
-                   Tcw=np.array(res.Tcw[:], np.float32))
-        return out
-
-
-    def reserve_local_map(self, n):
-        """dvm_tracker_reserve_local_map: the second half's working set for tables of up to n points (allocated once)."""
-        f = self.L.dvm_tracker_reserve_local_map
-        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32]
-        check(f(self.t, int(n)))
-
-    def track_local_map(self, pts, frame_mp, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
-        """dvm_track_local_map: Tracking::TrackLocalMap of the frame the last track() call tracked (reference src/Tracking.cc:2668-2740) as
-        ONE device chain.  pts: LOCAL_POINT_DTYPE array (the local map); frame_mp [n]: per keypoint the index into pts of the point the
-        frame holds, or -1.  Returns a dict: mp (mvpMapPoints after the search), outlier (mvbOutlier), track_pts (TRACK_DTYPE per entry,
-        if asked), the counters of dvm_track_local_result, pose (7 doubles: t, q) and Tcw (7 floats: q, t)."""
-        pts = np.ascontiguousarray(pts, LOCAL_POINT_DTYPE)
-        frame_mp = np.ascontiguousarray(frame_mp, np.int32)
-        n_kp = len(frame_mp)
-        mp = np.empty(max(n_kp, 1), np.int32); outl = np.empty(max(n_kp, 1), np.uint8)
-        tp = np.zeros(max(len(pts), 1), TRACK_DTYPE) if want_track_points else None
-        res = TrackLocalResult()
-        f = self.L.dvm_track_local_map
-        f.restype = C.c_int32
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
-                      C.c_void_p, C.POINTER(TrackLocalResult)]
-        check(f(self.t, self.ext.h, _p(pts) if len(pts) else None, len(pts), _p(frame_mp), float(th), int(bool(far_points)), float(th_far),
-                _p(mp), _p(outl), _p(tp), C.byref(res)))
-        out = {k: getattr(res, k) for k in ("n_to_match", "nmatches", "n_requeried", "n_cleared_bad", "n_edges", "n_inliers", "matches_inliers")}
-        out.update(mp=mp[:n_kp], outlier=outl[:n_kp], pose=np.array(res.pose[:], np.float64), Tcw=np.array(res.Tcw[:], np.float32))
-        if want_track_points:
-            out["track_pts"] = tp[:len(pts)]
-        return out
-
-    def reserve_reference_keyframe(self, n):
-        """dvm_tracker_reserve_reference_keyframe: the reference-keyframe chain's working set for keyframes of up to n keypoints."""
-        f = self.L.dvm_tracker_reserve_reference_keyframe
-        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32]
-        check(f(self.t, int(n)))
-
-    def track_reference_keyframe(self, voc, kf, pose_last, img=None, K=None, bounds=None, inv_sigma2=None, dist=None, nnratio=0.7, check_ori=True,
-                                 th_low=50, min_matches=15, min_map=10, levelsup=4, lap=(0, 1000), model=None):
-        """dvm_track_reference_keyframe: Tracking::TrackReferenceKeyFrame (reference src/Tracking.cc:2461-2520) as ONE device chain.
-        voc: a Vocabulary; kf: dict(kps (mvKeysUn), desc, mp (map-point ids or -1), pos [n, 3], n_obs, bad (optional), fv (mFeatVec as
-        vocab_transform_host returns it)); pose_last: mLastFrame.GetPose() as 7 floats (qx, qy, qz, qw, t).  With img: dvm_track_begin on it,
-        then the chain (form a: the no-motion-model case); without: the chain on the frame of the last track() (form b: the motion model
-        failed).  K: fx fy cx cy; bounds, dist: form (a).  model: a CameraModel -- with img the tracker is set to it before the begin (form (b)
-        runs on the model of the frame's track() call); K may then be None (it is not read under KannalaBrandt8).  Returns a dict: the counters of dvm_track_refkf_result, mp (mvpMapPoints after the
-        outlier drop), dropped, outlier, bow_ids / bow_vals / fv_nodes / fv_off / fv_feat (ComputeBoW), pose (7 doubles: t, q), Tcw (7 floats:
-        q, t) and, in form (a), kps / desc / kps_un."""
-        cap = self.ext.cap
-        vp = C.c_void_p
-        if model is not None:
-            K = model.p[:4] if K is None else K
-            if img is not None:
-                self.set_camera_model(model)
-        if img is not None:
-            img = np.ascontiguousarray(img, np.uint8)
-            fb = self.L.dvm_track_begin
-            fb.restype = C.c_int32
-            fb.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-            check(fb(self.t, self.ext.h, img.ctypes.data, img.shape[0], img.shape[1], img.strides[0], int(lap[0]), int(lap[1])))
-        rk, keep = _ref_keyframe(kf)
-        pr, s2 = _refkf_params(pose_last, K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
-        if bounds is not None:
-            pr.bounds[:] = [float(v) for v in np.asarray(bounds, np.float32)]
-        pr.dist = None if dist is None else C.cast(C.pointer(dist), vp)
-        kps = np.empty(cap, KP_DTYPE); kun = np.empty(cap, KP_DTYPE); desc = np.empty((cap, 32), np.uint8)
-        o, arrs = _refkf_out(cap)
-        o.kps, o.desc, o.cap, o.kps_un = kps.ctypes.data, desc.ctypes.data, cap, kun.ctypes.data
-        res = TrackRefKfResult()
-        f = self.L.dvm_track_reference_keyframe
-        f.restype = C.c_int32
-        f.argtypes = [vp, vp, vp, C.POINTER(RefKeyframe), C.POINTER(TrackRefKfParams), C.POINTER(TrackRefKfOut), C.POINTER(TrackRefKfResult)]
-        check(f(self.t, self.ext.h, voc.h, C.byref(rk), C.byref(pr), C.byref(o), C.byref(res)))
-        N = res.n
-        out = _refkf_result(res, arrs)
-        if img is not None:
-            out.update(kps=kps[:N], desc=desc[:N], kps_un=kun[:N])
-        return out
-
-
 # dvm_local_point (include/dvmslam_hip.h): one mvpLocalMapPoints entry -- GetWorldPos, GetNormal, mfMinDistance / mfMaxDistance,
 # GetDescriptor, Observations, isBad
 LOCAL_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_dist", "<f4"), ("max_dist", "<f4"), ("desc", "u1", (32,)),
@@ -1294,6 +1157,128 @@ class TrackRefKfResult(C.Structure):
                [("pose", C.c_double * 7), ("Tcw", C.c_float * 7), ("reserved2", C.c_int32)]
 
 
+class TrackIn(C.Structure):
+    """dvmh_track_in (include/dvmslam_host.h); dvmh_track_in_resident has the same layout: the store's handle where mps is"""
+    _fields_ = [("Tcw_pred", C.c_void_p), ("Nl", C.c_int32), ("kps_l", C.c_void_p), ("mp_l", C.c_void_p), ("outlier_l", C.c_void_p), ("mps", C.c_void_p)]
+
+
+class TrackOut(C.Structure):
+    """dvmh_track_out (include/dvmslam_host.h)"""
+    _fields_ = [("kps", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int32), ("kps_un", C.c_void_p), ("mp_c", C.c_void_p), ("dropped", C.c_void_p)]
+
+
+class LocalMapIn(C.Structure):
+    """dvm_local_map_in (include/dvmslam_hip.h)"""
+    _fields_ = [("pts", C.c_void_p), ("n", C.c_int32), ("frame_mp", C.c_void_p), ("th", C.c_float), ("far_points", C.c_int32), ("th_far", C.c_float)]
+
+
+class LocalMapOut(C.Structure):
+    """dvm_local_map_out (include/dvmslam_hip.h)"""
+    _fields_ = [("mp_out", C.c_void_p), ("outlier", C.c_void_p), ("track_pts", C.c_void_p)]
+
+
+class TrackLast(C.Structure):
+    """dvm_track_last (include/dvmslam_hip.h)"""
+    _fields_ = [("store", C.c_void_p), ("n", C.c_int32), ("slot", C.c_void_p), ("octave", C.c_void_p), ("angle", C.c_void_p),
+                ("Tcw_pred", C.c_float * 7), ("th", C.c_float)]
+
+
+class TrackShared(C.Structure):
+    """dvm_track_shared (include/dvmslam_hip.h)"""
+    _fields_ = [("bounds", C.c_float * 4), ("dist", C.c_void_p), ("scale_factors", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("nlevels", C.c_int32),
+                ("cam", BaCamera), ("th_high", C.c_int32), ("check_ori", C.c_int32), ("min_matches", C.c_int32)]
+
+
+class LocalMapInResident(C.Structure):
+    """dvm_local_map_in_resident (include/dvmslam_hip.h)"""
+    _fields_ = [("store", C.c_void_p), ("slots", C.c_void_p), ("n", C.c_int32), ("frame_mp", C.c_void_p), ("th", C.c_float), ("far_points", C.c_int32),
+                ("th_far", C.c_float)]
+
+
+# ---- the tracker entry points of both libraries, declared once: name -> argument types (restype int32 but for the destroy).  lib() and
+# host_lib() apply the tables when they load their library, so a call with a wrong count or a float where an int belongs raises.  No more
+# than that: pointers are not told apart (two of them swapped pass), an array's dtype is not looked at.
+class _Ptr:
+    """The argtype of a pointer argument: None, a C-contiguous numpy array (its data), a ctypes structure or array (its address), an
+    address, or what ctypes takes as a pointer anyway (c_void_p, byref(), pointer())."""
+
+    @classmethod
+    def from_param(cls, v):
+        if isinstance(v, np.ndarray):
+            if not v.flags.c_contiguous:
+                raise TypeError("a numpy array passed to the C ABI must be C-contiguous")
+            return C.c_void_p(v.ctypes.data)
+        if isinstance(v, (C.Structure, C.Array)):
+            return C.byref(v)
+        if isinstance(v, int) and not isinstance(v, bool):
+            return C.c_void_p(v)
+        return v
+
+
+_I, _L, _F, _P = C.c_int32, C.c_int64, C.c_float, _Ptr
+_TRACK_ONE = [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _F, _I, _P, _P, _I, _P, _P, _P, _P]
+_TRACK_BATCH = [_P, _P, _I, _I, _P, _I, _I, _I, _L, _I, _I, _P, _P, _P, _P, _I, _F, _I, _P, _P, _P]
+_TRACK_API = {            # libdvmslam_hip.so (include/dvmslam_hip.h)
+    "dvm_tracker_create": [_I, _I, _I, _P],
+    "dvm_tracker_create_batch": [_I, _I, _I, _I, _P],
+    "dvm_tracker_destroy": [_P],
+    "dvm_tracker_set_camera_model": [_P, _P],
+    "dvm_tracker_last_upload_bytes": [_P, _P, _P],
+    "dvm_tracker_reserve_local_map": [_P, _I],
+    "dvm_tracker_reserve_reference_keyframe": [_P, _I],
+    "dvm_tracker_reserve_reference_keyframe_batch": [_P, _I],
+    "dvm_track_begin": [_P, _P, _P, _I, _I, _I, _I, _I],
+    "dvm_track_begin_batch": [_P, _P, _P, _I, _I, _I, _I, _L, _I, _I],
+    "dvm_track_begin_staged": [_P, _P, _I, _I, _I, _I, _I],
+    "dvm_track_finish": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    "dvm_track_finish_batch": [_P, _P, _I, _P, _P, _P],
+    "dvm_track_finish_batch_resident": [_P, _P, _I, _P, _P, _P, _P],
+    "dvm_track_debug_build_queries": [_P, _I, _P, _P] + [_P] * 12,
+    "dvm_track_local_map": [_P, _P, _P, _I, _P, _F, _I, _F, _P, _P, _P, _P],
+    "dvm_track_local_map_batch": [_P, _P, _I, _P, _P, _P, _P],
+    "dvm_track_local_map_batch_resident": [_P, _P, _I, _P, _P, _P, _P],
+    "dvm_track_reference_keyframe": [_P] * 7,
+    "dvm_track_reference_keyframe_batch": [_P, _P, _P, _I, _P, _P, _P, _P, _P],
+}
+_TRACK_HOST_API = {       # libdvmslam_host.so (include/dvmslam_host.h); the _cam forms take the model behind K
+    "dvmh_track_with_motion_model": _TRACK_ONE,
+    "dvmh_track_with_motion_model_cam": _TRACK_ONE[:11] + [_P] + _TRACK_ONE[11:],
+    "dvmh_track_with_motion_model_batch": _TRACK_BATCH,
+    "dvmh_track_with_motion_model_batch_cam": _TRACK_BATCH[:12] + [_P] + _TRACK_BATCH[12:],
+    "dvmh_track_with_motion_model_batch_resident": _TRACK_BATCH,
+    "dvmh_build_frame_queries": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _F] + [_P] * 10,
+}
+
+
+def _declare(L, api):
+    for name, argtypes in api.items():
+        f = getattr(L, name)
+        f.restype = None if name.endswith("_destroy") else C.c_int32
+        f.argtypes = argtypes
+
+
+_TRACK_COUNTERS = ("n", "mono_index", "nmatches", "nmatches_search", "nmatches_map", "n_inliers", "wide_window", "replayed_on_host", "tracked", "n_requeried")
+_LOCAL_COUNTERS = ("n_to_match", "nmatches", "n_requeried", "n_cleared_bad", "n_edges", "n_inliers", "matches_inliers")
+_REFKF_COUNTERS = ("n", "mono_index", "status", "nmatches", "nmatches_before_rotation", "n_edges", "n_inliers", "nmatches_after", "nmatches_map", "n_bow", "n_fv")
+_QUERY_ARRAYS = ("q_entry", "qx", "qy", "qr", "qmin", "qmax", "q_claims", "q_angle", "q_pos", "qdesc")
+
+
+def _f32(*arrays):
+    return [None if a is None else np.ascontiguousarray(a, np.float32) for a in arrays]
+
+
+def _per_frame(v, count):
+    return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * count
+
+
+def _need_K(K, model):
+    if K is None:
+        if model is None:
+            raise ValueError("K is needed without a camera model")
+        K = model.p[:4]
+    return K
+
+
 def _ref_keyframe(kf):
     """dvm_ref_keyframe of a keyframe dict (Tracker.track_reference_keyframe's kf); returns it and the arrays it points into."""
     keep = [np.ascontiguousarray(kf["kps"], KP_DTYPE), np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32), np.ascontiguousarray(kf["mp"], np.int32),
@@ -1331,264 +1316,6 @@ def _refkf_out(cap):
     o.bow_ids, o.bow_vals = arrs["bow_ids"].ctypes.data, arrs["bow_vals"].ctypes.data
     o.fv_node, o.fv_off, o.fv_feat = arrs["fv_nodes"].ctypes.data, arrs["fv_off"].ctypes.data, arrs["fv_feat"].ctypes.data
     return o, arrs
-
-
-def _refkf_result(res, arrs):
-    """dvm_track_refkf_result and the outputs _refkf_out's arrays hold, as Tracker.track_reference_keyframe returns them."""
-    N, fo = res.n, arrs["fv_off"]
-    out = {k: getattr(res, k) for k in ("n", "mono_index", "status", "nmatches", "nmatches_before_rotation", "n_edges", "n_inliers",
-                                        "nmatches_after", "nmatches_map", "n_bow", "n_fv")}
-    out.update(mp=arrs["mp"][:N], dropped=arrs["dropped"][:N], outlier=arrs["outlier"][:N], bow_ids=arrs["bow_ids"][:res.n_bow],
-               bow_vals=arrs["bow_vals"][:res.n_bow], fv_nodes=arrs["fv_nodes"][:res.n_fv], fv_off=fo[:res.n_fv + 1], fv_feat=arrs["fv_feat"][:fo[res.n_fv]],
-               pose=np.array(res.pose[:], np.float64), Tcw=np.array(res.Tcw[:], np.float32))
-    return out
-
-
-class TrackIn(C.Structure):
-    """dvmh_track_in (include/dvmslam_host.h)"""
-    _fields_ = [("Tcw_pred", C.c_void_p), ("Nl", C.c_int32), ("kps_l", C.c_void_p), ("mp_l", C.c_void_p), ("outlier_l", C.c_void_p), ("mps", C.c_void_p)]
-
-
-class TrackOut(C.Structure):
-    """dvmh_track_out (include/dvmslam_host.h)"""
-    _fields_ = [("kps", C.c_void_p), ("desc", C.c_void_p), ("cap", C.c_int32), ("kps_un", C.c_void_p), ("mp_c", C.c_void_p), ("dropped", C.c_void_p)]
-
-
-class TrackerBatch:
-    """dvm_tracker_create_batch + dvmh_track_with_motion_model_batch: the tracked frames of up to max_frames agents as ONE chain of batched
-    launches.  ext: an OrbExtractor with max_batch >= max_frames."""
-
-    def __init__(self, ext: "OrbExtractor", max_frames, device=0):
-        self.L, self.H, self.ext, self.device, self.max_frames = lib(), host_lib(), ext, device, int(max_frames)
-        self.t = C.c_void_p()
-        f = self.L.dvm_tracker_create_batch
-        f.restype = C.c_int32; f.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-        check(f(device, self.max_frames, ext.cap, ext.cap, C.byref(self.t)))
-        cap, B = ext.cap, self.max_frames
-        self.kps = np.empty((B, cap), KP_DTYPE); self.kun = np.empty((B, cap), KP_DTYPE); self.desc = np.empty((B, cap, 32), np.uint8)
-        self.mp = np.empty((B, cap), np.int32); self.dropped = np.empty((B, cap), np.int32)
-        self.res = (TrackResult * B)()
-        self.outs = (TrackOut * B)()
-        for b in range(B):
-            o = self.outs[b]
-            o.kps, o.desc, o.cap, o.kps_un = self.kps[b].ctypes.data, self.desc[b].ctypes.data, cap, self.kun[b].ctypes.data
-            o.mp_c, o.dropped = self.mp[b].ctypes.data, self.dropped[b].ctypes.data
-
-    def close(self):
-        if getattr(self, "t", None) and self.t.value:
-            f = self.L.dvm_tracker_destroy
-            f.restype = None; f.argtypes = [C.c_void_p]
-            f(self.t)
-            self.t = C.c_void_p()
-
-    __del__ = close
-
-    def set_camera_model(self, model):
-        """dvm_tracker_set_camera_model: the camera of the agent this tracker serves, for every chain of the tracker.  model: a CameraModel, or
-        None for the default (the pinhole K of each call).  Drops what the last begin / finish prepared for the second half."""
-        f = self.L.dvm_tracker_set_camera_model
-        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_void_p]
-        check(f(self.t, _model_ref(model)))
-
-    def prepare(self, Tcw_preds, lasts):
-        """lasts: per agent (kps_l, mp_l, outlier_l or None, mps).  Returns the marshalled dvmh_track_in array (keep it alive with its arrays)."""
-        n = len(lasts)
-        ins = (TrackIn * n)()
-        keep = []
-        for b, (T, (kl, ml, ol, mps)) in enumerate(zip(Tcw_preds, lasts)):
-            T = np.ascontiguousarray(T, np.float32); kl = np.ascontiguousarray(kl, KP_DTYPE); ml = np.ascontiguousarray(ml, np.int32)
-            ol = None if ol is None else np.ascontiguousarray(ol, np.uint8); mps = np.ascontiguousarray(mps, MAP_POINT_DTYPE)
-            keep.append((T, kl, ml, ol, mps))
-            i = ins[b]
-            i.Tcw_pred, i.Nl, i.kps_l, i.mp_l, i.outlier_l, i.mps = T.ctypes.data, len(kl), kl.ctypes.data, ml.ctypes.data, None if ol is None else ol.ctypes.data, mps.ctypes.data
-        return ins, keep
-
-    def track(self, imgs, ins, K, bounds, scale_factors, inv_sigma2, th=15.0, check_ori=True, lap=(0, 1000), model=None):
-        """imgs [count, rows, cols] u8; ins: prepare()'s array; model: as Tracker.track takes it, one for all frames
-        (dvmh_track_with_motion_model_batch_cam).  Returns one dict per frame (views into this object's arrays)."""
-        if K is None:
-            if model is None:
-                raise ValueError("K is needed without a camera model")
-            K = model.p[:4]
-        imgs = np.ascontiguousarray(imgs, np.uint8)
-        count = imgs.shape[0]
-        f4 = [np.ascontiguousarray(a, np.float32) for a in (K, bounds, scale_factors, inv_sigma2)]
-        fn = self.H.dvmh_track_with_motion_model_batch if model is None else self.H.dvmh_track_with_motion_model_batch_cam
-        fn.restype = C.c_int32; fn.argtypes = None
-        vp = C.c_void_p
-        cam = () if model is None else (C.byref(model),)
-        rc = fn(self.t, self.ext.h, C.c_int32(self.device), C.c_int32(count), vp(imgs.ctypes.data), C.c_int32(imgs.shape[1]), C.c_int32(imgs.shape[2]),
-                C.c_int32(imgs.strides[1]), C.c_int64(imgs.strides[0]), C.c_int32(lap[0]), C.c_int32(lap[1]), _p(f4[0]), *cam, _p(f4[1]), _p(f4[2]), _p(f4[3]),
-                C.c_int32(len(f4[2])), C.c_float(float(th)), C.c_int32(int(check_ori)), ins[0] if isinstance(ins, tuple) else ins, self.outs, self.res)
-        check(rc)
-        out = []
-        for b in range(count):
-            r = self.res[b]
-            n = r.n
-            d = {k: getattr(r, k) for k in ("n", "mono_index", "nmatches", "nmatches_search", "nmatches_map", "n_inliers", "wide_window", "replayed_on_host",
-                                            "tracked", "n_requeried")}
-            d.update(kps=self.kps[b, :n], kps_un=self.kun[b, :n], desc=self.desc[b, :n], mp=self.mp[b, :n], dropped=self.dropped[b, :n],
-                     pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
-            out.append(d)
-        return out
-
-    def reserve_local_map(self, total):
-        """dvm_tracker_reserve_local_map: the batched second half's working set for `total` table entries per call (the sum over the
-        frames of each table's size rounded up to 64), per-keypoint arrays for max_frames frames."""
-        f = self.L.dvm_tracker_reserve_local_map
-        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32]
-        check(f(self.t, int(total)))
-
-    def track_local_map(self, tables, frame_mps, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
-        """dvm_track_local_map_batch: Tracking::TrackLocalMap of every frame the last track() call tracked, as ONE device chain.  tables [count]:
-        LOCAL_POINT_DTYPE arrays; frame_mps [count]: per keypoint the index into that frame's table, or -1; th / far_points / th_far: one value
-        for all frames or one per frame.  Returns one dict per frame: status (DVM_TRACK_COMPLETE = 0, else the first half's status and the
-        frame was skipped: zero counters, no arrays) and, for completed frames, what Tracker.track_local_map returns."""
-        count = len(tables)
-        per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * count
-        ths, fars, thfs = per(th), per(far_points), per(th_far)
-        assert len(frame_mps) == count and len(ths) == count and len(fars) == count and len(thfs) == count
-        ins = (LocalMapIn * count)(); outs = (LocalMapOut * count)(); res = (TrackLocalResult * count)(); status = np.zeros(count, np.int32)
-        keep = []
-        for b in range(count):
-            pts = np.ascontiguousarray(tables[b], LOCAL_POINT_DTYPE); fm = np.ascontiguousarray(frame_mps[b], np.int32)
-            mp = np.full(max(len(fm), 1), -1, np.int32); outl = np.zeros(max(len(fm), 1), np.uint8)
-            tp = np.zeros(max(len(pts), 1), TRACK_DTYPE) if want_track_points else None
-            keep.append((pts, fm, mp, outl, tp))
-            ins[b].pts, ins[b].n, ins[b].frame_mp = (pts.ctypes.data if len(pts) else None), len(pts), fm.ctypes.data
-            ins[b].th, ins[b].far_points, ins[b].th_far = float(ths[b]), int(bool(fars[b])), float(thfs[b])
-            outs[b].mp_out, outs[b].outlier, outs[b].track_pts = mp.ctypes.data, outl.ctypes.data, None if tp is None else tp.ctypes.data
-        f = self.L.dvm_track_local_map_batch
-        f.restype = C.c_int32
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        check(f(self.t, self.ext.h, count, ins, outs, res, _p(status)))
-        out = []
-        for b in range(count):
-            r = res[b]
-            d = {k: getattr(r, k) for k in ("n_to_match", "nmatches", "n_requeried", "n_cleared_bad", "n_edges", "n_inliers", "matches_inliers")}
-            d["status"] = int(status[b])
-            if status[b] == 0:
-                pts, fm, mp, outl, tp = keep[b]
-                d.update(mp=mp[:len(fm)], outlier=outl[:len(fm)], pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
-                if want_track_points:
-                    d["track_pts"] = tp[:len(pts)]
-            out.append(d)
-        return out
-
-    def reserve_reference_keyframe(self, total):
-        """dvm_tracker_reserve_reference_keyframe_batch: the batched reference-keyframe chain's working set for `total` keyframe keypoints
-        per call (the sum over its keyframes of each one's size rounded up to 64), per-frame arrays for max_frames frames."""
-        f = self.L.dvm_tracker_reserve_reference_keyframe_batch
-        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32]
-        check(f(self.t, int(total)))
-
-    def track_reference_keyframe(self, voc, kfs, poses_last, K, inv_sigma2, nnratio=0.7, check_ori=True, th_low=50, min_matches=15, min_map=10,
-                                 levelsup=4):
-        """dvm_track_reference_keyframe_batch: Tracking::TrackReferenceKeyFrame of the frames of the last track() call that need it, as ONE
-        device chain.  kfs [count]: a keyframe dict as Tracker.track_reference_keyframe takes it, or None for a frame that does not run;
-        poses_last [count]: mLastFrame.GetPose() as 7 floats (qx, qy, qz, qw, t), read where kfs[b] is not None.  Returns one dict per frame:
-        status (the chain's for a frame that ran, else the first half's: zero counters, no arrays) and, for a frame that ran, what
-        Tracker.track_reference_keyframe returns in form (b)."""
-        count = len(kfs)
-        assert len(poses_last) == count
-        cap = self.ext.cap
-        kfp = (C.POINTER(RefKeyframe) * count)(); prs = (TrackRefKfParams * count)(); outs = (TrackRefKfOut * count)()
-        res = (TrackRefKfResult * count)(); status = np.zeros(count, np.int32)
-        keep = []
-        for b in range(count):
-            if kfs[b] is None:
-                keep.append(None)
-                continue
-            rk, ka = _ref_keyframe(kfs[b])
-            pr, s2 = _refkf_params(poses_last[b], K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
-            o, arrs = _refkf_out(cap)
-            kfp[b] = C.pointer(rk); prs[b] = pr; outs[b] = o
-            keep.append((rk, ka, s2, arrs))
-        f = self.L.dvm_track_reference_keyframe_batch
-        f.restype = C.c_int32
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        check(f(self.t, self.ext.h, voc.h, count, kfp, prs, outs, res, _p(status)))
-        out = []
-        for b in range(count):
-            if keep[b] is None:
-                d = {k: getattr(res[b], k) for k in ("n", "mono_index", "nmatches", "nmatches_before_rotation", "n_edges", "n_inliers",
-                                                     "nmatches_after", "nmatches_map", "n_bow", "n_fv")}
-            else:
-                d = _refkf_result(res[b], keep[b][3])
-            d["status"] = int(status[b])
-            out.append(d)
-        return out
-
-
-class LocalMapIn(C.Structure):
-    """dvm_local_map_in (include/dvmslam_hip.h)"""
-    _fields_ = [("pts", C.c_void_p), ("n", C.c_int32), ("frame_mp", C.c_void_p), ("th", C.c_float), ("far_points", C.c_int32), ("th_far", C.c_float)]
-
-
-class LocalMapOut(C.Structure):
-    """dvm_local_map_out (include/dvmslam_hip.h)"""
-    _fields_ = [("mp_out", C.c_void_p), ("outlier", C.c_void_p), ("track_pts", C.c_void_p)]
-
-
-# ---- an agent's map points resident on the device (dvm_map_store, include/dvmslam_hip.h) and the two tracked-frame halves reading them
-class MapStore:
-    """dvm_map_store: `capacity` slots of LOCAL_POINT_DTYPE records in device memory.  update() writes records to slots (asynchronous; every
-    later call that reads the store sees it), read() returns slots.  Calls on one store are not concurrent."""
-
-    def __init__(self, capacity, device=0):
-        self.L = lib()
-        self.h = C.c_void_p()
-        f = self.L.dvm_map_store_create
-        f.restype = C.c_int32; f.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
-        check(f(int(device), int(capacity), C.byref(self.h)))
-
-    @property
-    def capacity(self):
-        f = self.L.dvm_map_store_capacity
-        f.restype = C.c_int32; f.argtypes = [C.c_void_p]
-        return f(self.h)
-
-    def update(self, slots, records):
-        slots = np.ascontiguousarray(slots, np.int32); records = np.ascontiguousarray(records, LOCAL_POINT_DTYPE)
-        assert slots.ndim == 1 and slots.shape == records.shape
-        f = self.L.dvm_map_store_update
-        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-        check(f(self.h, len(slots), _p(slots), _p(records)))
-
-    def read(self, slots):
-        slots = np.ascontiguousarray(slots, np.int32)
-        out = np.zeros(len(slots), LOCAL_POINT_DTYPE)
-        f = self.L.dvm_map_store_read
-        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-        check(f(self.h, len(slots), _p(slots), _p(out)))
-        return out
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            f = self.L.dvm_map_store_destroy
-            f.restype = None; f.argtypes = [C.c_void_p]
-            f(self.h)
-            self.h = C.c_void_p()
-
-    __del__ = close
-
-
-class TrackLast(C.Structure):
-    """dvm_track_last (include/dvmslam_hip.h)"""
-    _fields_ = [("store", C.c_void_p), ("n", C.c_int32), ("slot", C.c_void_p), ("octave", C.c_void_p), ("angle", C.c_void_p),
-                ("Tcw_pred", C.c_float * 7), ("th", C.c_float)]
-
-
-class TrackShared(C.Structure):
-    """dvm_track_shared (include/dvmslam_hip.h)"""
-    _fields_ = [("bounds", C.c_float * 4), ("dist", C.c_void_p), ("scale_factors", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("nlevels", C.c_int32),
-                ("cam", BaCamera), ("th_high", C.c_int32), ("check_ori", C.c_int32), ("min_matches", C.c_int32)]
-
-
-class LocalMapInResident(C.Structure):
-    """dvm_local_map_in_resident (include/dvmslam_hip.h)"""
-    _fields_ = [("store", C.c_void_p), ("slots", C.c_void_p), ("n", C.c_int32), ("frame_mp", C.c_void_p), ("th", C.c_float), ("far_points", C.c_int32),
-                ("th_far", C.c_float)]
 
 
 def entry_lists(kps_l, mp_l, outlier_l=None):
@@ -1629,24 +1356,23 @@ def _track_lasts(lasts):
     return arr, keep
 
 
+def _query_arrays(m):
+    """the ten per-query output arrays of the two query builders, m entries each"""
+    return dict(q_entry=np.zeros(m, np.int32), qx=np.zeros(m, np.float32), qy=np.zeros(m, np.float32), qr=np.zeros(m, np.float32), qmin=np.zeros(m, np.int32),
+                qmax=np.zeros(m, np.int32), q_claims=np.zeros(m, np.uint8), q_angle=np.zeros(m, np.float32), q_pos=np.zeros((m, 3), np.float32),
+                qdesc=np.zeros((m, 32), np.uint8))
+
+
 def build_frame_queries_host(last, K, bounds, scale_factors, records, model=None):
     """dvmh_build_frame_queries: the host's loop header of SearchByProjection(CurrentFrame, LastFrame) on one frame's entry lists, the map
     points given as `records` (LOCAL_POINT_DTYPE, indexed by last['slot']).  last: a dict as Tracker.debug_build_queries takes it (its
     store is not read).  Returns a dict: nq, q_entry, qx, qy, qr, qmin, qmax, q_claims, q_angle, q_pos [nq, 3], qdesc [nq, 32]."""
-    H = host_lib()
     slot = np.ascontiguousarray(last["slot"], np.int32); octv = np.ascontiguousarray(last["octave"], np.uint8); ang = np.ascontiguousarray(last["angle"], np.float32)
     records = np.ascontiguousarray(records, LOCAL_POINT_DTYPE)
-    T = np.ascontiguousarray(last["Tcw_pred"], np.float32); b4 = np.ascontiguousarray(bounds, np.float32); sf = np.ascontiguousarray(scale_factors, np.float32)
-    K4 = None if K is None else np.ascontiguousarray(K, np.float32)
-    n = len(slot); m = max(n, 1)
-    o = dict(q_entry=np.zeros(m, np.int32), qx=np.zeros(m, np.float32), qy=np.zeros(m, np.float32), qr=np.zeros(m, np.float32), qmin=np.zeros(m, np.int32),
-             qmax=np.zeros(m, np.int32), q_claims=np.zeros(m, np.uint8), q_angle=np.zeros(m, np.float32), q_pos=np.zeros((m, 3), np.float32),
-             qdesc=np.zeros((m, 32), np.uint8))
-    fn = H.dvmh_build_frame_queries
-    fn.restype = C.c_int32; fn.argtypes = None
-    nq = fn(_p(T), None if K4 is None else _p(K4), None if model is None else C.byref(model), _p(b4), _p(sf), C.c_int32(len(sf)), C.c_int32(n), _p(slot),
-            _p(records), _p(octv), _p(ang), C.c_float(float(last.get("th", 15.0))), *[_p(o[k]) for k in ("q_entry", "qx", "qy", "qr", "qmin", "qmax", "q_claims",
-                                                                                                        "q_angle", "q_pos", "qdesc")])
+    T, K4, b4, sf = _f32(last["Tcw_pred"], K, bounds, scale_factors)
+    n = len(slot)
+    o = _query_arrays(max(n, 1))
+    nq = host_lib().dvmh_build_frame_queries(T, K4, model, b4, sf, len(sf), n, slot, records, octv, ang, float(last.get("th", 15.0)), *[o[k] for k in _QUERY_ARRAYS])
     if nq < 0:
         check(nq)
     out = {k: v[:nq] for k, v in o.items()}
@@ -1654,166 +1380,377 @@ def build_frame_queries_host(last, K, bounds, scale_factors, records, model=None
     return out
 
 
-def _debug_build_queries(trk, lasts, K, bounds, scale_factors, inv_sigma2):
-    count = len(lasts)
-    arr, keep = _track_lasts(lasts)
-    sh, keep2 = _track_shared(K, bounds, scale_factors, inv_sigma2)
-    stride = max(64, (max(len(k[0]) for k in keep) + 63) & ~63)
-    Qn = count * stride
-    nq = np.zeros(count, np.int32)
-    o = dict(q_entry=np.zeros(Qn, np.int32), qx=np.zeros(Qn, np.float32), qy=np.zeros(Qn, np.float32), qr=np.zeros(Qn, np.float32), qmin=np.zeros(Qn, np.int32),
-             qmax=np.zeros(Qn, np.int32), q_claims=np.zeros(Qn, np.uint8), q_angle=np.zeros(Qn, np.float32), q_pos=np.zeros((Qn, 3), np.float32),
-             qdesc=np.zeros((Qn, 32), np.uint8))
-    got = C.c_int32(0)
-    f = trk.L.dvm_track_debug_build_queries
-    f.restype = C.c_int32; f.argtypes = None
-    check(f(trk.t, C.c_int32(count), arr, C.byref(sh), _p(nq), *[_p(o[k]) for k in ("q_entry", "qx", "qy", "qr", "qmin", "qmax", "q_claims", "q_angle", "q_pos",
-                                                                                     "qdesc")], C.byref(got)))
-    assert got.value == stride, (got.value, stride)
-    out = []
-    for b in range(count):
-        d = {k: v[b * stride:b * stride + nq[b]].copy() for k, v in o.items()}
-        d["nq"] = int(nq[b])
-        out.append(d)
-    return out
+class _TrackerBase:
+    """What Tracker and TrackerBatch share: the handle's life cycle, the reservations, the marshalling of a call's frames and the three
+    result builders (first half, TrackLocalMap, TrackReferenceKeyFrame), each written once."""
 
+    def _open(self, ext, device, max_frames, create, *sizes):
+        self.L, self.H, self.ext, self.device, self.max_frames = lib(), host_lib(), ext, device, int(max_frames)
+        self.t = C.c_void_p()
+        check(create(device, *sizes, C.byref(self.t)))
 
-def _last_upload_bytes(trk):
-    a, b = C.c_int64(0), C.c_int64(0)
-    f = trk.L.dvm_tracker_last_upload_bytes
-    f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    check(f(trk.t, C.byref(a), C.byref(b)))
-    return a.value, b.value
+    def close(self):
+        if getattr(self, "t", None) and self.t.value:
+            self.L.dvm_tracker_destroy(self.t)
+            self.t = C.c_void_p()
 
+    __del__ = close
 
-def _track_resident(trk, imgs, ins, outs, res, K, bounds, scale_factors, inv_sigma2, th, check_ori, lap):
-    imgs = np.ascontiguousarray(imgs, np.uint8)
-    count = imgs.shape[0]
-    f4 = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (K, bounds, scale_factors, inv_sigma2)]
-    fn = trk.H.dvmh_track_with_motion_model_batch_resident
-    fn.restype = C.c_int32; fn.argtypes = None
-    vp = C.c_void_p
-    check(fn(trk.t, trk.ext.h, C.c_int32(trk.device), C.c_int32(count), vp(imgs.ctypes.data), C.c_int32(imgs.shape[1]), C.c_int32(imgs.shape[2]),
-             C.c_int32(imgs.strides[1]), C.c_int64(imgs.strides[0]), C.c_int32(lap[0]), C.c_int32(lap[1]), None if f4[0] is None else _p(f4[0]), _p(f4[1]),
-             _p(f4[2]), _p(f4[3]), C.c_int32(len(f4[2])), C.c_float(float(th)), C.c_int32(int(check_ori)), ins[0] if isinstance(ins, tuple) else ins, outs, res))
-    return count
+    def set_camera_model(self, model):
+        """dvm_tracker_set_camera_model: the camera of the agent this tracker serves, for every chain of the tracker.  model: a CameraModel, or
+        None for the default (the pinhole K of each call).  Drops what the last begin / finish prepared for the second half."""
+        check(self.L.dvm_tracker_set_camera_model(self.t, model))
 
+    def reserve_local_map(self, n):
+        """dvm_tracker_reserve_local_map: the second half's working set (allocated once) for tables of up to n points per call -- a batch:
+        the sum over the frames of each table's size rounded up to 64; per-keypoint arrays for max_frames frames."""
+        check(self.L.dvm_tracker_reserve_local_map(self.t, int(n)))
 
-def _prepare_resident(Tcw_preds, lasts):
-    """lasts: per agent (kps_l, mp_l as store slots, outlier_l or None, MapStore).  Returns the marshalled dvmh_track_in_resident array."""
-    n = len(lasts)
-    ins = (TrackIn * n)()      # dvmh_track_in_resident has dvmh_track_in's layout: the store's handle where mps was
-    keep = []
-    for b, (T, (kl, ml, ol, store)) in enumerate(zip(Tcw_preds, lasts)):
-        T = np.ascontiguousarray(T, np.float32); kl = np.ascontiguousarray(kl, KP_DTYPE); ml = np.ascontiguousarray(ml, np.int32)
-        ol = None if ol is None else np.ascontiguousarray(ol, np.uint8)
-        keep.append((T, kl, ml, ol, store))
-        i = ins[b]
-        i.Tcw_pred, i.Nl, i.kps_l, i.mp_l, i.outlier_l, i.mps = T.ctypes.data, len(kl), kl.ctypes.data, ml.ctypes.data, None if ol is None else ol.ctypes.data, store.h
-    return ins, keep
+    def debug_build_queries(self, lasts, K, bounds, scale_factors, inv_sigma2):
+        """dvm_track_debug_build_queries: k_track_queries alone.  lasts: per frame a dict(store, slot, octave, angle, Tcw_pred (7 floats: q, t),
+        th).  Returns one dict per frame: nq, q_entry, qx, qy, qr, qmin, qmax, q_claims, q_angle, q_pos, qdesc."""
+        count = len(lasts)
+        arr, keep = _track_lasts(lasts)
+        sh, keep2 = _track_shared(K, bounds, scale_factors, inv_sigma2)
+        stride = max(64, (max(len(k[0]) for k in keep) + 63) & ~63)
+        nq = np.zeros(count, np.int32)
+        o = _query_arrays(count * stride)
+        got = C.c_int32(0)
+        check(self.L.dvm_track_debug_build_queries(self.t, count, arr, sh, nq, *[o[k] for k in _QUERY_ARRAYS], C.byref(got)))
+        assert got.value == stride, (got.value, stride)
+        out = []
+        for b in range(count):
+            d = {k: v[b * stride:b * stride + nq[b]].copy() for k, v in o.items()}
+            d["nq"] = int(nq[b])
+            out.append(d)
+        return out
 
+    def last_upload_bytes(self):
+        """dvm_tracker_last_upload_bytes: (first half, second half) host-to-device bytes of the last finish and the last local-map call."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        check(self.L.dvm_tracker_last_upload_bytes(self.t, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
-def _track_local_map_resident(trk, stores, slot_lists, frame_mps, th, far_points, th_far, want_track_points):
-    count = len(slot_lists)
-    per = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * count
-    ths, fars, thfs = per(th), per(far_points), per(th_far)
-    assert len(stores) == count and len(frame_mps) == count and len(ths) == count and len(fars) == count and len(thfs) == count
-    ins = (LocalMapInResident * count)(); outs = (LocalMapOut * count)(); res = (TrackLocalResult * count)(); status = np.zeros(count, np.int32)
-    keep = []
-    for b in range(count):
-        sl = np.ascontiguousarray(slot_lists[b], np.int32); fm = np.ascontiguousarray(frame_mps[b], np.int32)
-        mp = np.full(max(len(fm), 1), -1, np.int32); outl = np.zeros(max(len(fm), 1), np.uint8)
-        tp = np.zeros(max(len(sl), 1), TRACK_DTYPE) if want_track_points else None
-        keep.append((sl, fm, mp, outl, tp))
-        ins[b].store = None if stores[b] is None else stores[b].h
-        ins[b].slots, ins[b].n, ins[b].frame_mp = (sl.ctypes.data if len(sl) else None), len(sl), fm.ctypes.data
-        ins[b].th, ins[b].far_points, ins[b].th_far = float(ths[b]), int(bool(fars[b])), float(thfs[b])
-        outs[b].mp_out, outs[b].outlier, outs[b].track_pts = mp.ctypes.data, outl.ctypes.data, None if tp is None else tp.ctypes.data
-    f = trk.L.dvm_track_local_map_batch_resident
-    f.restype = C.c_int32
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    check(f(trk.t, trk.ext.h, count, ins, outs, res, _p(status)))
-    out = []
-    for b in range(count):
-        r = res[b]
-        d = {k: getattr(r, k) for k in ("n_to_match", "nmatches", "n_requeried", "n_cleared_bad", "n_edges", "n_inliers", "matches_inliers")}
-        d["status"] = int(status[b])
-        if status[b] == 0:
-            sl, fm, mp, outl, tp = keep[b]
-            d.update(mp=mp[:len(fm)], outlier=outl[:len(fm)], pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
-            if want_track_points:
-                d["track_pts"] = tp[:len(sl)]
-        out.append(d)
-    return out
+    # ---- the first half
+    def _track_arrays(self, B):
+        """The extraction's and the search's output arrays for B frames at the extractor's capacity"""
+        cap = self.ext.cap
+        return dict(kps=np.empty((B, cap), KP_DTYPE), kps_un=np.empty((B, cap), KP_DTYPE), desc=np.empty((B, cap, 32), np.uint8), mp=np.empty((B, cap), np.int32),
+                    dropped=np.empty((B, cap), np.int32))
 
+    def _track_outs(self, B):
+        """_track_arrays(B), the dvmh_track_out array pointing into them and the results: (arrays, outs, res)."""
+        a, cap = self._track_arrays(B), self.ext.cap
+        outs = (TrackOut * B)()
+        for b in range(B):
+            o = outs[b]
+            o.kps, o.desc, o.cap, o.kps_un = a["kps"][b].ctypes.data, a["desc"][b].ctypes.data, cap, a["kps_un"][b].ctypes.data
+            o.mp_c, o.dropped = a["mp"][b].ctypes.data, a["dropped"][b].ctypes.data
+        return a, outs, (TrackResult * B)()
 
-_TRACK_COUNTERS = ("n", "mono_index", "nmatches", "nmatches_search", "nmatches_map", "n_inliers", "wide_window", "replayed_on_host", "tracked", "n_requeried")
+    @staticmethod
+    def _track_ins(Tcw_preds, lasts, last_item):
+        """dvmh_track_in[_resident] of the agents' (kps_l, mp_l, outlier_l or None, x): last_item(x) -> (what to keep alive, the address that
+        goes where mps is).  Returns the array and what it points into."""
+        ins = (TrackIn * len(lasts))()
+        keep = []
+        for b, (T, (kl, ml, ol, x)) in enumerate(zip(Tcw_preds, lasts)):
+            T = np.ascontiguousarray(T, np.float32); kl = np.ascontiguousarray(kl, KP_DTYPE); ml = np.ascontiguousarray(ml, np.int32)
+            ol = None if ol is None else np.ascontiguousarray(ol, np.uint8)
+            x, addr = last_item(x)
+            keep.append((T, kl, ml, ol, x))
+            i = ins[b]
+            i.Tcw_pred, i.Nl, i.kps_l, i.mp_l, i.outlier_l, i.mps = T.ctypes.data, len(kl), kl.ctypes.data, ml.ctypes.data, None if ol is None else ol.ctypes.data, addr
+        return ins, keep
 
-
-def _tracker_track_resident(self, img, Tcw_pred, K, bounds, scale_factors, inv_sigma2, kps_l, mp_l, outlier_l, store, th=15.0, check_ori=True, lap=(0, 1000)):
-    """dvmh_track_with_motion_model_batch_resident for one frame: Tracker.track with LastFrame's map points given as slots of `store` (a
-    MapStore) in mp_l.  Under a camera model set with set_camera_model K may be None.  Returns what track() returns, mp / dropped as slots."""
-    img = np.ascontiguousarray(img, np.uint8)
-    cap = self.ext.cap
-    kps = np.empty(cap, KP_DTYPE); kun = np.empty(cap, KP_DTYPE); desc = np.empty((cap, 32), np.uint8)
-    mp = np.empty(cap, np.int32); dropped = np.empty(cap, np.int32)
-    ins, keep = _prepare_resident([Tcw_pred], [(kps_l, mp_l, outlier_l, store)])
-    outs = (TrackOut * 1)(); res = (TrackResult * 1)()
-    o = outs[0]
-    o.kps, o.desc, o.cap, o.kps_un, o.mp_c, o.dropped = kps.ctypes.data, desc.ctypes.data, cap, kun.ctypes.data, mp.ctypes.data, dropped.ctypes.data
-    _track_resident(self, img[None], ins, outs, res, K, bounds, scale_factors, inv_sigma2, th, check_ori, lap)
-    r = res[0]
-    n = r.n
-    out = {k: getattr(r, k) for k in _TRACK_COUNTERS}
-    out.update(kps=kps[:n], kps_un=kun[:n], desc=desc[:n], mp=mp[:n], dropped=dropped[:n], pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
-    return out
-
-
-def _tracker_track_local_map_resident(self, store, slots, frame_mp, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
-    """dvm_track_local_map_batch_resident for the one frame of the last track() / track_resident(): Tracker.track_local_map with the local map
-    given as slots of `store`.  Returns what track_local_map returns plus status."""
-    return _track_local_map_resident(self, [store], [slots], [frame_mp], th, far_points, th_far, want_track_points)[0]
-
-
-def _batch_track_resident(self, imgs, ins, K, bounds, scale_factors, inv_sigma2, th=15.0, check_ori=True, lap=(0, 1000)):
-    """dvmh_track_with_motion_model_batch_resident: TrackerBatch.track with every agent's map points in a MapStore.  ins: prepare_resident()'s
-    array.  Returns one dict per frame as track() does, mp / dropped as store slots."""
-    count = _track_resident(self, imgs, ins, self.outs, self.res, K, bounds, scale_factors, inv_sigma2, th, check_ori, lap)
-    out = []
-    for b in range(count):
-        r = self.res[b]
+    @staticmethod
+    def _track_result(r, a, b):
+        """dvmh_track_result r and frame b of _track_outs' arrays as track() returns them"""
         n = r.n
         d = {k: getattr(r, k) for k in _TRACK_COUNTERS}
-        d.update(kps=self.kps[b, :n], kps_un=self.kun[b, :n], desc=self.desc[b, :n], mp=self.mp[b, :n], dropped=self.dropped[b, :n],
+        d.update(kps=a["kps"][b, :n], kps_un=a["kps_un"][b, :n], desc=a["desc"][b, :n], mp=a["mp"][b, :n], dropped=a["dropped"][b, :n],
                  pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
-        out.append(d)
-    return out
+        return d
+
+    def _track_batch(self, io, imgs, ins, K, bounds, scale_factors, inv_sigma2, th, check_ori, lap, model=None, resident=False):
+        """dvmh_track_with_motion_model_batch[_cam | _resident] on io = _track_outs(>= count); returns one dict per frame"""
+        imgs = np.ascontiguousarray(imgs, np.uint8)
+        count = imgs.shape[0]
+        f4 = _f32(K, bounds, scale_factors, inv_sigma2)
+        fn = self.H.dvmh_track_with_motion_model_batch_resident if resident else \
+            self.H.dvmh_track_with_motion_model_batch if model is None else self.H.dvmh_track_with_motion_model_batch_cam
+        a, outs, res = io
+        check(fn(self.t, self.ext.h, self.device, count, imgs, imgs.shape[1], imgs.shape[2], imgs.strides[1], imgs.strides[0], int(lap[0]), int(lap[1]), f4[0],
+                 *(() if model is None else (model,)), f4[1], f4[2], f4[3], len(f4[2]), float(th), int(check_ori), ins[0] if isinstance(ins, tuple) else ins, outs, res))
+        return [self._track_result(res[b], a, b) for b in range(count)]
+
+    # ---- the second half
+    def _local_map_batch(self, tables, stores, frame_mps, th, far_points, th_far, want_track_points):
+        """dvm_track_local_map_batch, or with stores dvm_track_local_map_batch_resident (tables: slot lists)"""
+        count = len(tables)
+        resident = stores is not None
+        ths, fars, thfs = _per_frame(th, count), _per_frame(far_points, count), _per_frame(th_far, count)
+        assert len(frame_mps) == count and len(ths) == count and len(fars) == count and len(thfs) == count and (not resident or len(stores) == count)
+        ins = ((LocalMapInResident if resident else LocalMapIn) * count)(); outs = (LocalMapOut * count)(); res = (TrackLocalResult * count)()
+        status = np.zeros(count, np.int32)
+        keep = []
+        for b in range(count):
+            tab = np.ascontiguousarray(tables[b], np.int32 if resident else LOCAL_POINT_DTYPE)
+            k = self._local_map_arrays(tab, frame_mps[b], want_track_points)
+            keep.append(k)
+            i = ins[b]
+            if resident:
+                i.store, i.slots = None if stores[b] is None else stores[b].h, tab.ctypes.data if len(tab) else None
+            else:
+                i.pts = tab.ctypes.data if len(tab) else None
+            i.n, i.frame_mp, i.th, i.far_points, i.th_far = len(tab), k[1].ctypes.data, float(ths[b]), int(bool(fars[b])), float(thfs[b])
+            outs[b].mp_out, outs[b].outlier, outs[b].track_pts = k[2].ctypes.data, k[3].ctypes.data, None if k[4] is None else k[4].ctypes.data
+        fn = self.L.dvm_track_local_map_batch_resident if resident else self.L.dvm_track_local_map_batch
+        check(fn(self.t, self.ext.h, count, ins, outs, res, _p(status)))
+        return [self._local_result(res[b], keep[b], int(status[b])) for b in range(count)]
+
+    @staticmethod
+    def _local_map_arrays(tab, frame_mp, want_track_points):
+        """one frame's table, frame_mp and the arrays the call writes: (table, frame_mp, mp, outlier, track_pts or None)"""
+        fm = np.ascontiguousarray(frame_mp, np.int32)
+        return (tab, fm, np.full(max(len(fm), 1), -1, np.int32), np.zeros(max(len(fm), 1), np.uint8),
+                np.zeros(max(len(tab), 1), TRACK_DTYPE) if want_track_points else None)
+
+    @staticmethod
+    def _local_result(r, keep, status=None):
+        """dvm_track_local_result r and _local_map_arrays' outputs as track_local_map returns them; status: the batched calls' (a frame with
+        another status than DVM_TRACK_COMPLETE was skipped: zero counters, no arrays), None for the single call"""
+        d = {k: getattr(r, k) for k in _LOCAL_COUNTERS}
+        if status is not None:
+            d["status"] = status
+        if not status:
+            tab, fm, mp, outl, tp = keep
+            d.update(mp=mp[:len(fm)], outlier=outl[:len(fm)], pose=np.array(r.pose[:], np.float64), Tcw=np.array(r.Tcw[:], np.float32))
+            if tp is not None:
+                d["track_pts"] = tp[:len(tab)]
+        return d
+
+    @staticmethod
+    def _refkf_result(res, arrs):
+        """dvm_track_refkf_result and the outputs _refkf_out's arrays hold, as track_reference_keyframe returns them; arrs None: a frame that
+        did not run (the counters, zero, without its status)"""
+        if arrs is None:
+            return {k: getattr(res, k) for k in _REFKF_COUNTERS if k != "status"}
+        N, fo = res.n, arrs["fv_off"]
+        out = {k: getattr(res, k) for k in _REFKF_COUNTERS}
+        out.update(mp=arrs["mp"][:N], dropped=arrs["dropped"][:N], outlier=arrs["outlier"][:N], bow_ids=arrs["bow_ids"][:res.n_bow],
+                   bow_vals=arrs["bow_vals"][:res.n_bow], fv_nodes=arrs["fv_nodes"][:res.n_fv], fv_off=fo[:res.n_fv + 1], fv_feat=arrs["fv_feat"][:fo[res.n_fv]],
+                   pose=np.array(res.pose[:], np.float64), Tcw=np.array(res.Tcw[:], np.float32))
+        return out
 
 
-def _batch_track_local_map_resident(self, stores, slot_lists, frame_mps, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
-    """dvm_track_local_map_batch_resident: TrackerBatch.track_local_map with every frame's table given as slots of its MapStore."""
-    return _track_local_map_resident(self, stores, slot_lists, frame_mps, th, far_points, th_far, want_track_points)
+class Tracker(_TrackerBase):
+    """dvm_tracker + dvmh_track_with_motion_model: Frame::Frame -> ExtractORB and Tracking::TrackWithMotionModel of one frame as ONE
+    device chain behind one synchronisation (reference src/Frame.cc:371-411, src/Tracking.cc:2584-2667).  track and track_local_map call
+    the single-frame C entry points; the resident forms are the batch of one."""
+
+    def __init__(self, ext: "OrbExtractor", device=0, max_queries=None):
+        self._open(ext, device, 1, lib().dvm_tracker_create, ext.cap, max_queries or ext.cap)
+
+    def track(self, img, Tcw_pred, K, bounds, scale_factors, inv_sigma2, kps_l, mp_l, outlier_l, mps, th=15.0, check_ori=True, dist=None,
+              lap=(0, 1000), model=None):
+        """Tcw_pred: 7 floats (qx, qy, qz, qw, t).  model: a CameraModel (dvmh_track_with_motion_model_cam: the tracker is set to it and K,
+        which may then be None, is not read), or None for the pinhole K.  Returns a dict: n, kps, desc, kps_un, mp (mvpMapPoints after the
+        outlier drop), dropped, pose (7 doubles: t, q), and the counters of dvmh_track_result."""
+        K = _need_K(K, model)
+        img = np.ascontiguousarray(img, np.uint8)
+        a, res = self._track_arrays(1), TrackResult()       # (fresh per call: a result stays valid after the next call)
+        kps_l = np.ascontiguousarray(kps_l, KP_DTYPE); mp_l = np.ascontiguousarray(mp_l, np.int32)
+        outl = None if outlier_l is None else np.ascontiguousarray(outlier_l, np.uint8)
+        f4 = _f32(Tcw_pred, K, bounds, scale_factors, inv_sigma2)
+        mps = np.ascontiguousarray(mps, MAP_POINT_DTYPE)
+        fn = self.H.dvmh_track_with_motion_model if model is None else self.H.dvmh_track_with_motion_model_cam
+        check(fn(self.t, self.ext.h, self.device, img, img.shape[0], img.shape[1], img.strides[0], int(lap[0]), int(lap[1]), f4[0], f4[1],
+                 *(() if model is None else (model,)), f4[2], dist, f4[3], f4[4], len(f4[3]), len(kps_l), kps_l, mp_l, outl, mps, float(th), int(check_ori),
+                 a["kps"][0], a["desc"][0], self.ext.cap, a["kps_un"][0], a["mp"][0], a["dropped"][0], res))
+        return self._track_result(res, a, 0)
+
+    def track_resident(self, img, Tcw_pred, K, bounds, scale_factors, inv_sigma2, kps_l, mp_l, outlier_l, store, th=15.0, check_ori=True, lap=(0, 1000)):
+        """dvmh_track_with_motion_model_batch_resident for one frame: Tracker.track with LastFrame's map points given as slots of `store` (a
+        MapStore) in mp_l.  Under a camera model set with set_camera_model K may be None.  Returns what track() returns, mp / dropped as slots."""
+        ins, keep = TrackerBatch.prepare_resident([Tcw_pred], [(kps_l, mp_l, outlier_l, store)])
+        img = np.ascontiguousarray(img, np.uint8)
+        return self._track_batch(self._track_outs(1), img[None], ins, K, bounds, scale_factors, inv_sigma2, th, check_ori, lap, resident=True)[0]
+
+    def track_local_map(self, pts, frame_mp, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
+        """dvm_track_local_map: Tracking::TrackLocalMap of the frame the last track() call tracked (reference src/Tracking.cc:2668-2740) as
+        ONE device chain.  pts: LOCAL_POINT_DTYPE array (the local map); frame_mp [n]: per keypoint the index into pts of the point the
+        frame holds, or -1.  Returns a dict: mp (mvpMapPoints after the search), outlier (mvbOutlier), track_pts (TRACK_DTYPE per entry,
+        if asked), the counters of dvm_track_local_result, pose (7 doubles: t, q) and Tcw (7 floats: q, t)."""
+        keep = self._local_map_arrays(np.ascontiguousarray(pts, LOCAL_POINT_DTYPE), frame_mp, want_track_points)
+        pts, fm, mp, outl, tp = keep
+        res = TrackLocalResult()
+        check(self.L.dvm_track_local_map(self.t, self.ext.h, pts if len(pts) else None, len(pts), fm, float(th), int(bool(far_points)), float(th_far), mp, outl, tp, res))
+        return self._local_result(res, keep)
+
+    def track_local_map_resident(self, store, slots, frame_mp, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
+        """dvm_track_local_map_batch_resident for the one frame of the last track() / track_resident(): Tracker.track_local_map with the local map
+        given as slots of `store`.  Returns what track_local_map returns plus status."""
+        return self._local_map_batch([slots], [store], [frame_mp], th, far_points, th_far, want_track_points)[0]
+
+    def reserve_reference_keyframe(self, n):
+        """dvm_tracker_reserve_reference_keyframe: the reference-keyframe chain's working set for keyframes of up to n keypoints."""
+        check(self.L.dvm_tracker_reserve_reference_keyframe(self.t, int(n)))
+
+    def track_reference_keyframe(self, voc, kf, pose_last, img=None, K=None, bounds=None, inv_sigma2=None, dist=None, nnratio=0.7, check_ori=True,
+                                 th_low=50, min_matches=15, min_map=10, levelsup=4, lap=(0, 1000), model=None):
+        """dvm_track_reference_keyframe: Tracking::TrackReferenceKeyFrame (reference src/Tracking.cc:2461-2520) as ONE device chain.
+        voc: a Vocabulary; kf: dict(kps (mvKeysUn), desc, mp (map-point ids or -1), pos [n, 3], n_obs, bad (optional), fv (mFeatVec as
+        vocab_transform_host returns it)); pose_last: mLastFrame.GetPose() as 7 floats (qx, qy, qz, qw, t).  With img: dvm_track_begin on it,
+        then the chain (form a: the no-motion-model case); without: the chain on the frame of the last track() (form b: the motion model
+        failed).  K: fx fy cx cy; bounds, dist: form (a).  model: a CameraModel -- with img the tracker is set to it before the begin (form (b)
+        runs on the model of the frame's track() call); K may then be None (it is not read under KannalaBrandt8).  Returns a dict: the counters of dvm_track_refkf_result, mp (mvpMapPoints after the
+        outlier drop), dropped, outlier, bow_ids / bow_vals / fv_nodes / fv_off / fv_feat (ComputeBoW), pose (7 doubles: t, q), Tcw (7 floats:
+        q, t) and, in form (a), kps / desc / kps_un."""
+        cap = self.ext.cap
+        if model is not None:
+            K = model.p[:4] if K is None else K
+            if img is not None:
+                self.set_camera_model(model)
+        if img is not None:
+            img = np.ascontiguousarray(img, np.uint8)
+            check(self.L.dvm_track_begin(self.t, self.ext.h, img.ctypes.data, img.shape[0], img.shape[1], img.strides[0], int(lap[0]), int(lap[1])))
+        rk, keep = _ref_keyframe(kf)
+        pr, s2 = _refkf_params(pose_last, K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
+        if bounds is not None:
+            pr.bounds[:] = [float(v) for v in np.asarray(bounds, np.float32)]
+        pr.dist = None if dist is None else C.cast(C.pointer(dist), C.c_void_p)
+        kps = np.empty(cap, KP_DTYPE); kun = np.empty(cap, KP_DTYPE); desc = np.empty((cap, 32), np.uint8)
+        o, arrs = _refkf_out(cap)
+        o.kps, o.desc, o.cap, o.kps_un = kps.ctypes.data, desc.ctypes.data, cap, kun.ctypes.data
+        res = TrackRefKfResult()
+        check(self.L.dvm_track_reference_keyframe(self.t, self.ext.h, voc.h, rk, pr, o, res))
+        N = res.n
+        out = self._refkf_result(res, arrs)
+        if img is not None:
+            out.update(kps=kps[:N], desc=desc[:N], kps_un=kun[:N])
+        return out
 
 
-def _debug_build_queries_method(self, lasts, K, bounds, scale_factors, inv_sigma2):
-    """dvm_track_debug_build_queries: k_track_queries alone.  lasts: per frame a dict(store, slot, octave, angle, Tcw_pred (7 floats: q, t),
-    th).  Returns one dict per frame: nq, q_entry, qx, qy, qr, qmin, qmax, q_claims, q_angle, q_pos, qdesc."""
-    return _debug_build_queries(self, lasts, K, bounds, scale_factors, inv_sigma2)
+class TrackerBatch(_TrackerBase):
+    """dvm_tracker_create_batch + dvmh_track_with_motion_model_batch: the tracked frames of up to max_frames agents as ONE chain of batched
+    launches.  ext: an OrbExtractor with max_batch >= max_frames."""
+
+    def __init__(self, ext: "OrbExtractor", max_frames, device=0):
+        self._open(ext, device, max_frames, lib().dvm_tracker_create_batch, int(max_frames), ext.cap, ext.cap)
+        self._io = self._track_outs(self.max_frames)       # the first half's outputs: track() returns views into them
+        a, self.outs, self.res = self._io
+        self.kps, self.kun, self.desc, self.mp, self.dropped = a["kps"], a["kps_un"], a["desc"], a["mp"], a["dropped"]
+
+    def prepare(self, Tcw_preds, lasts):
+        """lasts: per agent (kps_l, mp_l, outlier_l or None, mps).  Returns the marshalled dvmh_track_in array (keep it alive with its arrays)."""
+        def mps_of(mps):
+            mps = np.ascontiguousarray(mps, MAP_POINT_DTYPE)
+            return mps, mps.ctypes.data
+        return self._track_ins(Tcw_preds, lasts, mps_of)
+
+    @staticmethod
+    def prepare_resident(Tcw_preds, lasts):
+        """lasts: per agent (kps_l, mp_l as store slots, outlier_l or None, MapStore).  Returns the marshalled dvmh_track_in_resident array."""
+        return _TrackerBase._track_ins(Tcw_preds, lasts, lambda store: (store, store.h))
+
+    def track(self, imgs, ins, K, bounds, scale_factors, inv_sigma2, th=15.0, check_ori=True, lap=(0, 1000), model=None):
+        """imgs [count, rows, cols] u8; ins: prepare()'s array; model: as Tracker.track takes it, one for all frames
+        (dvmh_track_with_motion_model_batch_cam).  Returns one dict per frame (views into this object's arrays)."""
+        return self._track_batch(self._io, imgs, ins, _need_K(K, model), bounds, scale_factors, inv_sigma2, th, check_ori, lap, model=model)
+
+    def track_resident(self, imgs, ins, K, bounds, scale_factors, inv_sigma2, th=15.0, check_ori=True, lap=(0, 1000)):
+        """dvmh_track_with_motion_model_batch_resident: TrackerBatch.track with every agent's map points in a MapStore.  ins: prepare_resident()'s
+        array.  Returns one dict per frame as track() does, mp / dropped as store slots."""
+        return self._track_batch(self._io, imgs, ins, K, bounds, scale_factors, inv_sigma2, th, check_ori, lap, resident=True)
+
+    def track_local_map(self, tables, frame_mps, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
+        """dvm_track_local_map_batch: Tracking::TrackLocalMap of every frame the last track() call tracked, as ONE device chain.  tables [count]:
+        LOCAL_POINT_DTYPE arrays; frame_mps [count]: per keypoint the index into that frame's table, or -1; th / far_points / th_far: one value
+        for all frames or one per frame.  Returns one dict per frame: status (DVM_TRACK_COMPLETE = 0, else the first half's status and the
+        frame was skipped: zero counters, no arrays) and, for completed frames, what Tracker.track_local_map returns."""
+        return self._local_map_batch(tables, None, frame_mps, th, far_points, th_far, want_track_points)
+
+    def track_local_map_resident(self, stores, slot_lists, frame_mps, th=1.0, far_points=False, th_far=0.0, want_track_points=False):
+        """dvm_track_local_map_batch_resident: TrackerBatch.track_local_map with every frame's table given as slots of its MapStore."""
+        return self._local_map_batch(slot_lists, stores, frame_mps, th, far_points, th_far, want_track_points)
+
+    def reserve_reference_keyframe(self, total):
+        """dvm_tracker_reserve_reference_keyframe_batch: the batched reference-keyframe chain's working set for `total` keyframe keypoints
+        per call (the sum over its keyframes of each one's size rounded up to 64), per-frame arrays for max_frames frames."""
+        check(self.L.dvm_tracker_reserve_reference_keyframe_batch(self.t, int(total)))
+
+    def track_reference_keyframe(self, voc, kfs, poses_last, K, inv_sigma2, nnratio=0.7, check_ori=True, th_low=50, min_matches=15, min_map=10,
+                                 levelsup=4):
+        """dvm_track_reference_keyframe_batch: Tracking::TrackReferenceKeyFrame of the frames of the last track() call that need it, as ONE
+        device chain.  kfs [count]: a keyframe dict as Tracker.track_reference_keyframe takes it, or None for a frame that does not run;
+        poses_last [count]: mLastFrame.GetPose() as 7 floats (qx, qy, qz, qw, t), read where kfs[b] is not None.  Returns one dict per frame:
+        status (the chain's for a frame that ran, else the first half's: zero counters, no arrays) and, for a frame that ran, what
+        Tracker.track_reference_keyframe returns in form (b)."""
+        count = len(kfs)
+        assert len(poses_last) == count
+        kfp = (C.POINTER(RefKeyframe) * count)(); prs = (TrackRefKfParams * count)(); outs = (TrackRefKfOut * count)()
+        res = (TrackRefKfResult * count)(); status = np.zeros(count, np.int32)
+        keep = []
+        for b in range(count):
+            if kfs[b] is None:
+                keep.append(None)
+                continue
+            rk, ka = _ref_keyframe(kfs[b])
+            pr, s2 = _refkf_params(poses_last[b], K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
+            o, arrs = _refkf_out(self.ext.cap)
+            kfp[b] = C.pointer(rk); prs[b] = pr; outs[b] = o
+            keep.append((rk, ka, s2, arrs))
+        check(self.L.dvm_track_reference_keyframe_batch(self.t, self.ext.h, voc.h, count, kfp, prs, outs, res, _p(status)))
+        out = []
+        for b in range(count):
+            d = self._refkf_result(res[b], None if keep[b] is None else keep[b][3])
+            d["status"] = int(status[b])
+            out.append(d)
+        return out
 
 
-def _last_upload_bytes_method(self):
-    """dvm_tracker_last_upload_bytes: (first half, second half) host-to-device bytes of the last finish and the last local-map call."""
-    return _last_upload_bytes(self)
+# ---- an agent's map points resident on the device (dvm_map_store, include/dvmslam_hip.h), read by the two tracked-frame halves above
+class MapStore:
+    """dvm_map_store: `capacity` slots of LOCAL_POINT_DTYPE records in device memory.  update() writes records to slots (asynchronous; every
+    later call that reads the store sees it), read() returns slots.  Calls on one store are not concurrent."""
 
+    def __init__(self, capacity, device=0):
+        self.L = lib()
+        self.h = C.c_void_p()
+        f = self.L.dvm_map_store_create
+        f.restype = C.c_int32; f.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
+        check(f(int(device), int(capacity), C.byref(self.h)))
 
-Tracker.track_resident = _tracker_track_resident
-Tracker.track_local_map_resident = _tracker_track_local_map_resident
-TrackerBatch.prepare_resident = staticmethod(_prepare_resident)
-TrackerBatch.track_resident = _batch_track_resident
-TrackerBatch.track_local_map_resident = _batch_track_local_map_resident
-for _cls in (Tracker, TrackerBatch):
-    _cls.debug_build_queries = _debug_build_queries_method
-    _cls.last_upload_bytes = _last_upload_bytes_method
+    @property
+    def capacity(self):
+        f = self.L.dvm_map_store_capacity
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p]
+        return f(self.h)
+
+    def update(self, slots, records):
+        slots = np.ascontiguousarray(slots, np.int32); records = np.ascontiguousarray(records, LOCAL_POINT_DTYPE)
+        assert slots.ndim == 1 and slots.shape == records.shape
+        f = self.L.dvm_map_store_update
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        check(f(self.h, len(slots), _p(slots), _p(records)))
+
+    def read(self, slots):
+        slots = np.ascontiguousarray(slots, np.int32)
+        out = np.zeros(len(slots), LOCAL_POINT_DTYPE)
+        f = self.L.dvm_map_store_read
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        check(f(self.h, len(slots), _p(slots), _p(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            f = self.L.dvm_map_store_destroy
+            f.restype = None; f.argtypes = [C.c_void_p]
+            f(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
 
 
 TRACKED_POINT_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),

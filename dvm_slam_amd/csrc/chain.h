@@ -71,13 +71,14 @@ struct WorkingSet {
 };
 
 // walks a block and its twin at equal offsets, every item rounded up to A bytes: carve reserves an item in `base`, put copies one into
-// `base` and returns where the twin holds it (staging block -> device block)
+// `base` and returns where the twin holds it (staging block -> device block).  On a null base carve only measures: it advances off and
+// returns null (no address is formed), so a layout is written once and used() of it at the largest arguments is the size to reserve.
 template <size_t A> struct Cursor {
   uint8_t* base;
   uint8_t* twin = nullptr;
   size_t off = 0;
   template <class T> T* carve(size_t count) {
-    T* r = reinterpret_cast<T*>(base + off);
+    T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
     off += pad<A>(count * sizeof(T));
     return r;
   }

@@ -19,7 +19,10 @@
 // takes LastFrame's entry lists (slot, octave, angle: 9 B per entry) and k_track_queries builds the query block from the store, beside the
 // extraction; dvm_track_local_map_batch_resident takes the tables as slot lists and k_store_gather fills the chain's device table.  Every
 // slot is checked on the host against its store before anything is queued.  Behind the query block / the table the chains are the same.
-// Every reservation here is a WorkingSet carved by a Cursor<256> (chain.h, shared with the other chains): items start at multiples of 256 bytes.
+// Every reservation here is a WorkingSet (chain.h, shared with the other chains) whose layout is written once, as a carve_* function of
+// track_layout.h: create / reserve_* measure it on a null base at the largest arguments, each call carves the same function at its own
+// shape.  Both first-half finishes are finish_run, the three second-half entry points fill a LocalSource per frame and run local_map_run,
+// both begins are begin_run; the entry points differ in their argument checks and in what they name in an error.
 #include <algorithm>
 #include <chrono>
 #include <climits>
@@ -40,6 +43,7 @@
 #include "host_stage.h"   // HostPool
 #include "map_store.h"
 #include "track_kernels.h"
+#include "track_layout.h"
 
 using namespace dvm;
 
@@ -63,47 +67,37 @@ struct LocalFrame {
 
 // a TrackReferenceKeyFrame working set: per-frame arrays for the tracker's max_frames frames at its keypoint capacity, keyframes of up to
 // `cap` entries per call (each keyframe's rounded up to 64)
-struct RefKfMapped {
-  int32_t *bow_ids, *fv_node, *fv_off, *fv_feat, *match, *cnt, *nedges, *n_inl, *fin; double *bow_vals, *pose; uint8_t* outlier;
-};
 struct RefKf {
   WorkingSet ws;                   // device: [upload copy][the frames' transforms, FeatureVectors and match state]; mapped: [upload staging][results]
   int cap = 0;
-  RefKfMapped r;                   // [max_frames] slices of the results (fv_off: kp_cap + 1 per frame, cnt: 8 per frame)
+  RefKfMapped r;                   // [max_frames] slices of the results
 };
 
 struct dvm_tracker {
   int device = 0, kp_cap = 0, q_cap = 0, max_frames = 1;
-  int q_rcap = 0;                  // q_cap rounded up to 64: the per-frame query capacity of d_q / d_ranked
+  int q_rcap = 0;                  // q_cap rounded up to 64: the per-frame query capacity of the query block and the ranked lists
   dvm_frame* grid = nullptr;       // max_frames slots
-  WorkingSet ws;                   // first half.  device: the arrays below; mapped: queries in (staging of the one copy), results out
-  // device, [frame][...]
-  uint32_t* d_ranked; int32_t* d_assign; int32_t* d_res; double *d_Xw, *d_obs, *d_info, *d_chi; int32_t *d_edge_kp, *d_nedges;
-  uint8_t* d_edge_out; dvm_keypoint_pod* d_kps_un;
-  // mapped (host address; device address: ws.dev(p)).  The query block is carved per call (stride = the call's largest nq).
-  struct Mapped {
-    uint8_t* qdesc; float *qx, *qy, *qr; int32_t *qmin, *qmax; uint8_t* q_claims; float *q_angle, *q_pos; double* pose_in; int32_t* nq_arr;
-    float* inv_sigma2;
-    int32_t* assign; uint8_t* outlier; int32_t* res; int32_t* fin; int32_t* nedges; double* pose_out; int32_t* n_inl;
-    dvm_keypoint_pod* kps_un;
-  } m;
-  // the query block: built in the mapped buffer (page-locked), copied to the device by ONE asynchronous copy on a side stream while the
-  // extraction runs; the kernels read the device copy (the one-wave claim replay walks it serially: a PCIe read per step would be its chain)
-  // d_q has no allocation of its own: it is the last item of ws.d (carved at create, freed with ws)
-  uint8_t* d_q = nullptr; size_t q_bytes = 0;
+  WorkingSet ws;                   // first half.  device: dv; mapped: [the query block, staging of the one copy: q_bytes][results m]
+  TrackerDevice dv{};
+  TrackerResults m{};
+  // the query block: carved per call (stride = the call's largest nq), built in the mapped buffer (page-locked), copied to the device by
+  // ONE asynchronous copy on a side stream while the extraction runs; the kernels read the device copy dv.q (the one-wave claim replay walks
+  // it serially: a PCIe read per step would be its chain).  qb: the last call's carve of the mapped buffer.
+  QueryBlock qb{};
+  size_t q_bytes = 0;              // the block at max_frames frames of q_rcap queries
   hipStream_t cstream = nullptr; hipEvent_t cev = nullptr;
-  template <class T> T* qdev(T* host_ptr) const { return rebase(host_ptr, ws.hm, d_q); }
+  template <class T> T* qdev(T* host_ptr) const { return rebase(host_ptr, ws.hm, dv.q); }
   int begun = 0;                   // frames of the batch whose extraction is queued
   dvm_camera_model model{};        // dvm_tracker_set_camera_model: 0 (a fresh tracker): the cam of the query / parameter structs; 1: KannalaBrandt8 on model.p
   int rows = 0, cols = 0;
-  // ---- the resident first half (dvm_track_finish_batch_resident): the entry lists go up through rw, k_track_queries writes d_q
-  WorkingSet rw;                   // device: the upload copy; mapped: [upload staging][q_entry: max_frames x q_rcap][nq: max_frames]
-  int32_t *r_entry = nullptr, *r_nq = nullptr;   // mapped: the entry number of every query, the frames' query counts
+  // ---- the resident first half (dvm_track_finish_batch_resident): the entry lists go up through rw, k_track_queries writes dv.q
+  WorkingSet rw;                   // device: the upload copy; mapped: rm
+  ResidentMapped rm{};             // mapped: the entry number of every query (max_frames x q_rcap), the frames' query counts
   int64_t up_first = 0, up_second = 0;           // dvm_tracker_last_upload_bytes: what the last finish / local-map call copied up
   // ---- the second half (dvm_track_local_map[_batch]): working set of dvm_tracker_reserve_local_map, and what the last finish left for it
   int lm_cap = 0;                  // table entries reserved (a multiple of 64; a batch: all frames' tables, each rounded up to 64)
-  WorkingSet lmw;                  // device: [upload][per-entry arrays][query arrays][ranked lists][counters]; mapped: [upload staging][results]
-  struct LocalMapped { int32_t* mp; uint8_t* outlier; TrackPoint* tp; int32_t* res; double* pose; int32_t *n_inl, *fin, *nedges; } lm;   // [max_frames]
+  WorkingSet lmw;                  // device: [upload region][carve_local_map_work]; mapped: [upload staging][results lm]
+  LocalMapResults lm{};            // [max_frames]
   LocalFrame lf;
   // ---- TrackReferenceKeyFrame: the working sets of dvm_tracker_reserve_reference_keyframe (rk, one frame) and of
   //      dvm_tracker_reserve_reference_keyframe_batch (rkb), and when the single call dvm_track_reference_keyframe may run
@@ -123,7 +117,6 @@ void vocab_launch_transform(const dvm_vocab* v, hipStream_t s, const uint8_t* d_
 }
 
 namespace {
-using Cursor256 = Cursor<256>;
 // a reservation that could not be allocated: "<fn>: <what failed>"
 int reserve_failed(const char* fn, const char* what) { set_error(std::string(fn) + ": " + what); return DVM_ERR_CAPACITY; }
 // PoseOptimization of a chain: k_pose_optimize on cam, or k_pose_optimize_kb8 on M.p under a KannalaBrandt8 model (cam is then not read)
@@ -154,37 +147,22 @@ int dvm_tracker_create_batch(int device, int max_frames, int max_keypoints, int 
   t->device = device; t->kp_cap = max_keypoints; t->q_cap = max_queries; t->max_frames = max_frames; t->q_rcap = (max_queries + 63) & ~63;
   int rc = dvm_frame_create(device, max_keypoints, max_frames, &t->grid);
   if (rc != DVM_OK) { delete t; return rc; }
-  // (Q rounded up to 64: dvm_track_finish_batch strides the per-query arrays by the call's largest nq rounded up to 64)
-  const size_t K = (size_t)max_keypoints, Q = ((size_t)max_queries + 63) & ~(size_t)63, B = (size_t)max_frames;
-  // device working set
-  const size_t dbytes = pad<256>(B * Q * 16) + pad<256>(B * K * 4) + pad<256>(B * 32) + pad<256>(B * K * 24) + pad<256>(B * K * 16) + 2 * pad<256>(B * K * 8) + pad<256>(B * K * 4) +
-                        pad<256>(B * 4) + pad<256>(B * K) + pad<256>(B * K * sizeof(dvm_keypoint_pod));
-  // mapped buffer: [query block: carved per call] [results]
-  t->q_bytes = pad<256>(B * Q * 32) + 3 * pad<256>(B * Q * 4) + 2 * pad<256>(B * Q * 4) + pad<256>(B * Q) + pad<256>(B * Q * 4) + pad<256>(B * Q * 12) + pad<256>(B * 56) +
-               pad<256>(B * 4) + pad<256>(64 * 4);
-  const size_t mbytes = t->q_bytes + pad<256>(B * K * 4) + pad<256>(B * K) + pad<256>(B * 32) + pad<256>(B * 16) + pad<256>(B * 4) + pad<256>(B * 56) + pad<256>(B * 4) +
-                        pad<256>(K * sizeof(dvm_keypoint_pod));
-  // (the query block's device copy d_q: the device block's last item)
-  if (const char* what = t->ws.alloc(dbytes + t->q_bytes, mbytes, t->q_bytes, /*mapped*/ true, /*zeroed*/ true)) {
+  // every size from the layouts at the largest call (Q rounded up to 64: dvm_track_finish_batch strides the per-query arrays by the
+  // call's largest nq rounded up to 64); the query block's device copy is the device block's last item
+  const size_t K = (size_t)max_keypoints, Q = (size_t)t->q_rcap, B = (size_t)max_frames;
+  t->q_bytes = carve_query_block(nullptr, B, Q).bytes;
+  if (const char* what = t->ws.alloc(carve_tracker_device(nullptr, B, K, Q, t->q_bytes).bytes, t->q_bytes + carve_tracker_results(nullptr, B, K).bytes, t->q_bytes,
+                                     /*mapped*/ true, /*zeroed*/ true)) {
     dvm_tracker_destroy(t); set_error(std::string("dvm_tracker_create: ") + what); return DVM_ERR_HIP;
   }
-  Cursor256 c{t->ws.d};
-  t->d_ranked = c.carve<uint32_t>(B * Q * 4); t->d_assign = c.carve<int32_t>(B * K); t->d_res = c.carve<int32_t>(B * 8);
-  t->d_Xw = c.carve<double>(B * K * 3); t->d_obs = c.carve<double>(B * K * 2); t->d_info = c.carve<double>(B * K); t->d_chi = c.carve<double>(B * K);
-  t->d_edge_kp = c.carve<int32_t>(B * K); t->d_nedges = c.carve<int32_t>(B); t->d_edge_out = c.carve<uint8_t>(B * K);
-  t->d_kps_un = c.carve<dvm_keypoint_pod>(B * K); t->d_q = c.carve<uint8_t>(t->q_bytes);
-  c = Cursor256{t->ws.hm + t->q_bytes};
-  auto& m = t->m;
-  m.assign = c.carve<int32_t>(B * K); m.outlier = c.carve<uint8_t>(B * K);
-  m.res = c.carve<int32_t>(B * 8); m.fin = c.carve<int32_t>(B * 4); m.nedges = c.carve<int32_t>(B); m.pose_out = c.carve<double>(B * 7);
-  m.n_inl = c.carve<int32_t>(B); m.kps_un = c.carve<dvm_keypoint_pod>(K);
+  t->dv = carve_tracker_device(t->ws.d, B, K, Q, t->q_bytes);
+  t->m = carve_tracker_results(t->ws.hm + t->q_bytes, B, K);
   {   // the resident first half: 9 bytes per entry (every frame's list rounded up to 64), two level tables, a record per frame
-    const size_t rup = pad<256>(2 * 256 + pad<64>(B * sizeof(ResidentFrame)) + B * Q * 9);
-    if (const char* what = t->rw.alloc(rup, rup + pad<256>(B * Q * 4) + pad<256>(B * 4), rup, /*mapped*/ true, /*zeroed*/ true)) {
+    const ResidentMapped sized = carve_resident_mapped(nullptr, B, Q);
+    if (const char* what = t->rw.alloc(sized.up, sized.bytes, sized.up, /*mapped*/ true, /*zeroed*/ true)) {
       dvm_tracker_destroy(t); set_error(std::string("dvm_tracker_create: ") + what); return DVM_ERR_HIP;
     }
-    Cursor256 rc2{t->rw.hm + rup};
-    t->r_entry = rc2.carve<int32_t>(B * Q); t->r_nq = rc2.carve<int32_t>(B);
+    t->rm = carve_resident_mapped(t->rw.hm, B, Q);
   }
   if (hipStreamCreateWithFlags(&t->cstream, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&t->cev, hipEventDisableTiming) != hipSuccess) {
@@ -217,56 +195,40 @@ int dvm_tracker_set_camera_model(dvm_tracker* t, const dvm_camera_model* model) 
   return DVM_OK;
 }
 
-int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1) {
+namespace {
+// dvm_track_begin_batch (the caller's frames) and dvm_track_begin_staged (the frames lie in the extractor's input buffer)
+int begin_run(const char* fn, bool staged, dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
-  if (count > t->max_frames) { set_error("dvm_track_begin_batch: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
+  if (count > t->max_frames) { set_error(std::string(fn) + ": more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
   t->begun = 0; t->clear_next();
-  const int rc = dvm_orb_extract_batch_host(h, imgs, count, rows, cols, stride, frame_stride, lap0, lap1);
+  const int rc = staged ? dvm_orb_extract_staged(h, count, rows, cols, lap0, lap1) : dvm_orb_extract_batch_host(h, imgs, count, rows, cols, stride, frame_stride, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
   if (count == 1 && t->max_frames == 1) { t->rk_state = 1; t->rk_h = h; t->rk_serial = orb_result_serial(h); }
   return DVM_OK;
 }
+}  // namespace
+int dvm_track_begin_batch(dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1) {
+  return begin_run("dvm_track_begin_batch", false, t, h, imgs, count, rows, cols, stride, frame_stride, lap0, lap1);
+}
 int dvm_track_begin_staged(dvm_tracker* t, dvm_orb* h, int count, int rows, int cols, int lap0, int lap1) {
-  if (!t || !h || count < 1) return DVM_ERR_INVALID;
-  if (count > t->max_frames) { set_error("dvm_track_begin_staged: more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0; t->clear_next();
-  const int rc = dvm_orb_extract_staged(h, count, rows, cols, lap0, lap1);
-  if (rc != DVM_OK) return rc;
-  t->begun = count; t->rows = rows; t->cols = cols;
-  if (count == 1 && t->max_frames == 1) { t->rk_state = 1; t->rk_h = h; t->rk_serial = orb_result_serial(h); }
-  return DVM_OK;
+  return begin_run("dvm_track_begin_staged", true, t, h, nullptr, count, rows, cols, 0, 0, lap0, lap1);
 }
 int dvm_track_begin(dvm_tracker* t, dvm_orb* h, const uint8_t* img, int rows, int cols, int stride, int lap0, int lap1) {
   return dvm_track_begin_batch(t, h, img, 1, rows, cols, stride, (int64_t)rows * stride, lap0, lap1);
 }
 
 namespace {
-// what the frames of a finish share: the fields of dvm_track_queries that are not per query (qs[0]'s), or dvm_track_shared
+// what the frames of a finish share: the fields of dvm_track_queries that are not per query (qs[0]'s), or dvm_track_shared -- the two
+// structs name them alike
 struct FinishShared {
   float bounds[4]; const dvm_distortion* dist; const float* inv_level_sigma2; int nlevels; dvm_ba_camera cam; int th_high, check_ori, min_matches;
 };
-// the upload block of a resident finish, carved in the mapped staging buffer of t->rw and at the same offsets in its device copy:
-// [mvScaleFactors 64][mvInvLevelSigma2 64][frames][slot, angle, octave: E entries each, frame b's at ResidentFrame::off -- every frame's
-// list rounded up to 64 entries, back to back] -- 9 bytes per entry
-struct ResidentUpload { float *scale, *inv_sigma2; ResidentFrame* fr; int32_t* slot; float* angle; uint8_t* octave; size_t bytes; };
-ResidentUpload carve_resident_upload(uint8_t* base, int count, size_t E) {
-  ResidentUpload u;
-  Cursor<64> c{base};
-  u.scale = c.carve<float>(64); u.inv_sigma2 = c.carve<float>(64); u.fr = c.carve<ResidentFrame>((size_t)count);
-  u.slot = c.carve<int32_t>(E); u.angle = c.carve<float>(E); u.octave = c.carve<uint8_t>(E);
-  u.bytes = c.used();
-  return u;
-}
-// the tracker's query block of a call of `count` frames at stride Qs, carved in the mapped buffer (t->qdev: the same item of d_q)
-size_t carve_query_block(dvm_tracker* t, int count, int Qs) {
-  auto& m = t->m;
-  Cursor256 c{t->ws.hm};
-  const size_t Qn = (size_t)count * Qs;
-  m.qdesc = c.carve<uint8_t>(Qn * 32); m.qx = c.carve<float>(Qn); m.qy = c.carve<float>(Qn); m.qr = c.carve<float>(Qn);
-  m.qmin = c.carve<int32_t>(Qn); m.qmax = c.carve<int32_t>(Qn); m.q_claims = c.carve<uint8_t>(Qn); m.q_angle = c.carve<float>(Qn);
-  m.q_pos = c.carve<float>(Qn * 3); m.pose_in = c.carve<double>((size_t)count * 7); m.nq_arr = c.carve<int32_t>(count); m.inv_sigma2 = c.carve<float>(64);
-  return c.used();
+extern "C++" template <class P> FinishShared finish_shared(const P& p) {
+  FinishShared S{};
+  std::memcpy(S.bounds, p.bounds, 16); S.dist = p.dist; S.inv_level_sigma2 = p.inv_level_sigma2; S.nlevels = p.nlevels; S.cam = p.cam;
+  S.th_high = p.th_high; S.check_ori = p.check_ori; S.min_matches = p.min_matches;
+  return S;
 }
 // the checks of a resident call on its entry lists and shared parameters, before anything is queued; *n_max: the largest entry count
 int resident_check(const char* fn, const dvm_tracker* t, int count, const dvm_track_last* last, const dvm_track_shared* p, int* n_max) {
@@ -287,7 +249,7 @@ int resident_check(const char* fn, const dvm_tracker* t, int count, const dvm_tr
   return DVM_OK;
 }
 // the entry lists packed, copied up and k_track_queries queued on stream qs (the tracker's side stream: beside the extraction); the query
-// block of the call must be carved (carve_query_block).  *d_inv_sigma2: mvInvLevelSigma2 on the device; *bytes: what was copied up
+// block of the call must be carved (t->qb).  *d_inv_sigma2: mvInvLevelSigma2 on the device; *bytes: what was copied up
 int resident_queue(dvm_tracker* t, hipStream_t qs, int count, const dvm_track_last* last, const dvm_track_shared* p, int Qs, const float** d_inv_sigma2,
                    size_t* bytes) {
   std::vector<int32_t> eoff((size_t)count);
@@ -313,9 +275,9 @@ int resident_queue(dvm_tracker* t, hipStream_t qs, int count, const dvm_track_la
   A.fx = (float)p->cam.fx; A.fy = (float)p->cam.fy; A.cx = (float)p->cam.cx; A.cy = (float)p->cam.cy;
   A.min_x = p->bounds[0]; A.max_x = p->bounds[1]; A.min_y = p->bounds[2]; A.max_y = p->bounds[3];
   std::memcpy(A.kb8, M.p, sizeof(A.kb8));
-  auto& m = t->m;
-  const TrackQueryOut O{t->qdev(m.qdesc), t->qdev(m.qx), t->qdev(m.qy), t->qdev(m.qr), t->qdev(m.qmin), t->qdev(m.qmax), t->qdev(m.q_claims),
-                        t->qdev(m.q_angle), t->qdev(m.q_pos), t->qdev(m.pose_in), t->qdev(m.nq_arr), t->rw.dev(t->r_entry), t->rw.dev(t->r_nq)};
+  const QueryBlock& qb = t->qb;
+  const TrackQueryOut O{t->qdev(qb.qdesc), t->qdev(qb.qx), t->qdev(qb.qy), t->qdev(qb.qr), t->qdev(qb.qmin), t->qdev(qb.qmax), t->qdev(qb.q_claims),
+                        t->qdev(qb.q_angle), t->qdev(qb.q_pos), t->qdev(qb.pose_in), t->qdev(qb.nq_arr), t->rw.dev(t->rm.entry), t->rw.dev(t->rm.nq)};
   launch_track_queries(qs, M.model, dup.fr, dup.slot, dup.octave, dup.angle, dup.scale, A, count, Qs, O);
   { const int rc = hip_check(hipGetLastError(), "k_track_queries"); if (rc != DVM_OK) return rc; }
   for (int b = 0; b < count; b++)
@@ -332,15 +294,7 @@ int finish_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* q
   if (t->begun != count) { set_error("dvm_track_finish: no matching dvm_track_begin on this tracker"); return DVM_ERR_STATE; }
   const dvm_camera_model M = t->model;
   const bool kb8 = M.model == dvm_cam::kKannalaBrandt8;    // (the cam fields of the queries are then not read)
-  FinishShared S{};
-  if (qs) {
-    const dvm_track_queries& q0 = qs[0];
-    std::memcpy(S.bounds, q0.bounds, 16); S.dist = q0.dist; S.inv_level_sigma2 = q0.inv_level_sigma2; S.nlevels = q0.nlevels; S.cam = q0.cam;
-    S.th_high = q0.th_high; S.check_ori = q0.check_ori; S.min_matches = q0.min_matches;
-  } else {
-    std::memcpy(S.bounds, p->bounds, 16); S.dist = p->dist; S.inv_level_sigma2 = p->inv_level_sigma2; S.nlevels = p->nlevels; S.cam = p->cam;
-    S.th_high = p->th_high; S.check_ori = p->check_ori; S.min_matches = p->min_matches;
-  }
+  const FinishShared S = qs ? finish_shared(qs[0]) : finish_shared(*p);
   int nq_max = 0;
   for (int b = 0; b < count; b++) {
     const dvm_track_frame_out& o = outs[b];
@@ -386,27 +340,29 @@ int finish_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* q
     if (n1 != d_n + 1) { set_error("dvm_track_finish_batch: unexpected result layout"); return DVM_ERR_STATE; }
   }
   const int Qs = (std::max(nq_max, 1) + 63) & ~63;      // the per-query arrays' stride for this call
-  auto& m = t->m;
+  const TrackerResults& m = t->m;
   // the query block of THIS call, packed: one copy (~75 KB per frame of 1 000 queries)
   // (the block's end and the ranked lists' inside what create sized: refused before anything is written)
-  const size_t q_used = carve_query_block(t, count, Qs);
+  const QueryBlock qb = carve_query_block(t->ws.hm, (size_t)count, (size_t)Qs);
+  const size_t q_used = qb.bytes;
   if (q_used > t->q_bytes || (size_t)count * Qs > (size_t)t->max_frames * t->q_rcap) {
     set_error("dvm_track_finish: the query block exceeds what the tracker was created for");
     return DVM_ERR_CAPACITY;
   }
-  const float* d_inv_sigma2 = t->qdev(m.inv_sigma2);
+  t->qb = qb;
+  const float* d_inv_sigma2 = t->qdev(qb.inv_sigma2);
   if (qs) {
     HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {       // (a batch's query blocks: 2.4 MB for 32 frames)
       const dvm_track_queries& q = qs[b];
       const size_t o = b * Qs, nq = (size_t)q.nq;
-      std::memcpy(m.qdesc + o * 32, q.qdesc, nq * 32); std::memcpy(m.qx + o, q.qx, nq * 4); std::memcpy(m.qy + o, q.qy, nq * 4);
-      std::memcpy(m.qr + o, q.qr, nq * 4); std::memcpy(m.qmin + o, q.qmin, nq * 4); std::memcpy(m.qmax + o, q.qmax, nq * 4);
-      std::memcpy(m.q_claims + o, q.q_claims, nq); std::memcpy(m.q_angle + o, q.q_angle, nq * 4); std::memcpy(m.q_pos + o * 3, q.q_pos, nq * 12);
-      std::memcpy(m.pose_in + 7 * b, q.pose_in, 56);
-      m.nq_arr[b] = q.nq;
+      std::memcpy(qb.qdesc + o * 32, q.qdesc, nq * 32); std::memcpy(qb.qx + o, q.qx, nq * 4); std::memcpy(qb.qy + o, q.qy, nq * 4);
+      std::memcpy(qb.qr + o, q.qr, nq * 4); std::memcpy(qb.qmin + o, q.qmin, nq * 4); std::memcpy(qb.qmax + o, q.qmax, nq * 4);
+      std::memcpy(qb.q_claims + o, q.q_claims, nq); std::memcpy(qb.q_angle + o, q.q_angle, nq * 4); std::memcpy(qb.q_pos + o * 3, q.q_pos, nq * 12);
+      std::memcpy(qb.pose_in + 7 * b, q.pose_in, 56);
+      qb.nq_arr[b] = q.nq;
     });
-    std::memcpy(m.inv_sigma2, S.inv_level_sigma2, (size_t)S.nlevels * 4);
-    DVM_HIP(hipMemcpyAsync(t->d_q, t->ws.hm, q_used, hipMemcpyHostToDevice, t->cstream));   // beside the extraction, not behind it
+    std::memcpy(qb.inv_sigma2, S.inv_level_sigma2, (size_t)S.nlevels * 4);
+    DVM_HIP(hipMemcpyAsync(t->dv.q, t->ws.hm, q_used, hipMemcpyHostToDevice, t->cstream));   // beside the extraction, not behind it
     t->up_first = (int64_t)q_used;
   } else {
     // the entry lists (9 B per entry) in place of the queries: k_track_queries writes the block on the device, beside the extraction
@@ -420,28 +376,28 @@ int finish_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* q
   const bool undist = count == 1 && S.dist && S.dist->k1 != 0.0f;
   const dvm_keypoint* d_un = d_kps;
   if (undist) {
-    rc = dvm_undistort_keypoints(S.dist, d_kps, reinterpret_cast<dvm_keypoint*>(t->d_kps_un), ocap, 1, s);
+    rc = dvm_undistort_keypoints(S.dist, d_kps, reinterpret_cast<dvm_keypoint*>(t->dv.kps_un), ocap, 1, s);
     if (rc != DVM_OK) return rc;
-    d_un = reinterpret_cast<const dvm_keypoint*>(t->d_kps_un);
-    if (outs[0].kps_un) DVM_HIP(hipMemcpyAsync(m.kps_un, t->d_kps_un, (size_t)ocap * sizeof(dvm_keypoint_pod), hipMemcpyDeviceToHost, s));
+    d_un = reinterpret_cast<const dvm_keypoint*>(t->dv.kps_un);
+    if (outs[0].kps_un) DVM_HIP(hipMemcpyAsync(m.kps_un, t->dv.kps_un, (size_t)ocap * sizeof(dvm_keypoint_pod), hipMemcpyDeviceToHost, s));
   }
   rc = dvm_frame_build_batch(t->grid, 0, count, d_un, kps_stride, d_desc, desc_stride, d_n, S.bounds[0], S.bounds[1], S.bounds[2], S.bounds[3], s);
   if (rc != DVM_OK) return rc;
   const FrameView FV = frame_view_of(t->grid);    // (bounds of the build above)
-  launch_match_window_ranked_batch(s, FV, 0, count, nullptr, nullptr, 0, t->qdev(m.qdesc), t->qdev(m.qx), t->qdev(m.qy), t->qdev(m.qr), t->qdev(m.qmin),
-                                   t->qdev(m.qmax), t->qdev(m.nq_arr), Qs, t->d_ranked);
-  TrackBatch TB{count, Qs, kps_stride, t->qdev(m.nq_arr)};
+  launch_match_window_ranked_batch(s, FV, 0, count, nullptr, nullptr, 0, t->qdev(qb.qdesc), t->qdev(qb.qx), t->qdev(qb.qy), t->qdev(qb.qr), t->qdev(qb.qmin),
+                                   t->qdev(qb.qmax), t->qdev(qb.nq_arr), Qs, t->dv.ranked);
+  TrackBatch TB{count, Qs, kps_stride, t->qdev(qb.nq_arr)};
   TrackRequery rq{};
   rq.F = FV;
   { static const bool no_rq = std::getenv("DVM_TRACK_NO_REQUERY") != nullptr; if (no_rq) rq.F.skp = nullptr; }   /* timing experiment only */
-  rq.qdesc = t->qdev(m.qdesc); rq.qx = t->qdev(m.qx); rq.qy = t->qdev(m.qy); rq.qr = t->qdev(m.qr); rq.qmin = t->qdev(m.qmin); rq.qmax = t->qdev(m.qmax);
-  launch_track_claims(s, t->d_ranked, t->qdev(m.q_claims), t->qdev(m.q_angle), 0, rq, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, S.th_high,
-                      S.check_ori, t->d_assign, t->d_res, t->ws.dev(m.assign), t->ws.dev(m.res), TB);
-  launch_track_gather(s, t->d_assign, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, t->qdev(m.q_pos), d_inv_sigma2, S.nlevels, t->d_Xw,
-                      t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges, t->d_res, S.min_matches, t->ws.dev(m.nedges), TB);
-  launch_pose_optimize(s, M, S.cam, t->qdev(m.pose_in), t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, t->ws.dev(m.pose_out), t->d_edge_out,
-                       t->ws.dev(m.n_inl), t->d_chi);
-  launch_track_finish(s, t->d_assign, d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, t->qdev(m.q_claims), t->ws.dev(m.outlier), t->ws.dev(m.fin), t->d_res, TB);
+  rq.qdesc = t->qdev(qb.qdesc); rq.qx = t->qdev(qb.qx); rq.qy = t->qdev(qb.qy); rq.qr = t->qdev(qb.qr); rq.qmin = t->qdev(qb.qmin); rq.qmax = t->qdev(qb.qmax);
+  launch_track_claims(s, t->dv.ranked, t->qdev(qb.q_claims), t->qdev(qb.q_angle), 0, rq, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, S.th_high,
+                      S.check_ori, t->dv.assign, t->dv.res, t->ws.dev(m.assign), t->ws.dev(m.res), TB);
+  launch_track_gather(s, t->dv.assign, reinterpret_cast<const dvm_keypoint_pod*>(d_un), d_n, ocap, t->qdev(qb.q_pos), d_inv_sigma2, S.nlevels, t->dv.Xw,
+                      t->dv.obs, t->dv.info, t->dv.edge_kp, t->dv.nedges, t->dv.res, S.min_matches, t->ws.dev(m.nedges), TB);
+  launch_pose_optimize(s, M, S.cam, t->qdev(qb.pose_in), t->dv.Xw, t->dv.obs, t->dv.info, t->dv.nedges, ocap, count, t->ws.dev(m.pose_out), t->dv.edge_out,
+                       t->ws.dev(m.n_inl), t->dv.chi);
+  launch_track_finish(s, t->dv.assign, d_n, ocap, t->dv.edge_kp, t->dv.nedges, t->dv.edge_out, t->qdev(qb.q_claims), t->ws.dev(m.outlier), t->ws.dev(m.fin), t->dv.res, TB);
   // (what the host wants back is written to mapped memory by the kernels themselves: no copy command behind the chain)
   rc = hip_check(hipGetLastError(), "tracking chain launch");
   if (rc != DVM_OK) return rc;
@@ -454,7 +410,7 @@ int finish_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* q
   }
   static const bool debug = std::getenv("DVM_TRACK_DEBUG") != nullptr;       // per-frame counters on stderr
   for (int b = 0; b < count; b++) {
-    const int nq_b = qs ? qs[b].nq : t->r_nq[b];
+    const int nq_b = qs ? qs[b].nq : t->rm.nq[b];
     const int min_matches = qs ? qs[b].min_matches : S.min_matches;
     const dvm_track_frame_out& o = outs[b];
     dvm_track_result& r = res[b];
@@ -463,7 +419,7 @@ int finish_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* q
     const size_t ko = (size_t)b * ocap;
     std::memcpy(o.assign, m.assign + ko, (size_t)n * 4);
     if (!qs) {     // the chain's query numbers as entry numbers of last[b] (k_track_queries kept q_entry beside each query)
-      const int32_t* qe = t->r_entry + (size_t)b * Qs;
+      const int32_t* qe = t->rm.entry + (size_t)b * Qs;
       for (int j = 0; j < n; j++) if (o.assign[j] >= 0) o.assign[j] = qe[o.assign[j]];
     }
     const int32_t* rs = m.res + 8 * b;
@@ -473,7 +429,7 @@ int finish_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* q
     if (debug) std::fprintf(stderr, "track: frame %d nq %d rounds %d requeried %d\n", b, nq_b, rs[4], rs[3]);
     if (rs[1]) {                        // a query ran out of ranked candidates and could not be searched again on the device (DVM_TRACK_NO_REQUERY)
       r.status = DVM_TRACK_REPLAY_ON_HOST;
-      if (o.ranked && nq_b) DVM_HIP(hipMemcpy(o.ranked, t->d_ranked + (size_t)b * Qs * 4, (size_t)nq_b * 16, hipMemcpyDeviceToHost));
+      if (o.ranked && nq_b) DVM_HIP(hipMemcpy(o.ranked, t->dv.ranked + (size_t)b * Qs * 4, (size_t)nq_b * 16, hipMemcpyDeviceToHost));
       std::memset(o.outlier, 0, (size_t)n);
       continue;
     }
@@ -522,23 +478,24 @@ int dvm_track_debug_build_queries(dvm_tracker* t, int count, const dvm_track_las
   DVM_HIP(hipSetDevice(t->device));
   const int Qs = (std::max(n_max, 1) + 63) & ~63;
   const size_t Qn = (size_t)count * Qs;
-  if (carve_query_block(t, count, Qs) > t->q_bytes || Qn > (size_t)t->max_frames * t->q_rcap) {
+  const QueryBlock qb = carve_query_block(t->ws.hm, (size_t)count, (size_t)Qs);
+  if (qb.bytes > t->q_bytes || Qn > (size_t)t->max_frames * t->q_rcap) {
     set_error("dvm_track_debug_build_queries: the query block exceeds what the tracker was created for");
     return DVM_ERR_CAPACITY;
   }
+  t->qb = qb;
   const float* d_inv_sigma2 = nullptr; size_t bytes = 0;
   if ((rc = resident_queue(t, t->cstream, count, last, p, Qs, &d_inv_sigma2, &bytes)) != DVM_OK) return rc;
   DVM_HIP(hipStreamSynchronize(t->cstream));
-  auto& m = t->m;
-  DVM_HIP(hipMemcpy(qdesc, t->qdev(m.qdesc), Qn * 32, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(qx, t->qdev(m.qx), Qn * 4, hipMemcpyDeviceToHost));
-  DVM_HIP(hipMemcpy(qy, t->qdev(m.qy), Qn * 4, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(qr, t->qdev(m.qr), Qn * 4, hipMemcpyDeviceToHost));
-  DVM_HIP(hipMemcpy(qmin, t->qdev(m.qmin), Qn * 4, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(qmax, t->qdev(m.qmax), Qn * 4, hipMemcpyDeviceToHost));
-  DVM_HIP(hipMemcpy(q_claims, t->qdev(m.q_claims), Qn, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(q_angle, t->qdev(m.q_angle), Qn * 4, hipMemcpyDeviceToHost));
-  DVM_HIP(hipMemcpy(q_pos, t->qdev(m.q_pos), Qn * 12, hipMemcpyDeviceToHost));
-  DVM_HIP(hipMemcpy(nq, t->qdev(m.nq_arr), (size_t)count * 4, hipMemcpyDeviceToHost));
-  std::memcpy(q_entry, t->r_entry, Qn * 4);
+  DVM_HIP(hipMemcpy(qdesc, t->qdev(qb.qdesc), Qn * 32, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(qx, t->qdev(qb.qx), Qn * 4, hipMemcpyDeviceToHost));
+  DVM_HIP(hipMemcpy(qy, t->qdev(qb.qy), Qn * 4, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(qr, t->qdev(qb.qr), Qn * 4, hipMemcpyDeviceToHost));
+  DVM_HIP(hipMemcpy(qmin, t->qdev(qb.qmin), Qn * 4, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(qmax, t->qdev(qb.qmax), Qn * 4, hipMemcpyDeviceToHost));
+  DVM_HIP(hipMemcpy(q_claims, t->qdev(qb.q_claims), Qn, hipMemcpyDeviceToHost)); DVM_HIP(hipMemcpy(q_angle, t->qdev(qb.q_angle), Qn * 4, hipMemcpyDeviceToHost));
+  DVM_HIP(hipMemcpy(q_pos, t->qdev(qb.q_pos), Qn * 12, hipMemcpyDeviceToHost));
+  DVM_HIP(hipMemcpy(nq, t->qdev(qb.nq_arr), (size_t)count * 4, hipMemcpyDeviceToHost));
+  std::memcpy(q_entry, t->rm.entry, Qn * 4);
   for (int b = 0; b < count; b++)
-    if (nq[b] != t->r_nq[b]) { set_error("dvm_track_debug_build_queries: the device and mapped query counts differ"); return DVM_ERR_STATE; }
+    if (nq[b] != t->rm.nq[b]) { set_error("dvm_track_debug_build_queries: the device and mapped query counts differ"); return DVM_ERR_STATE; }
   *stride = Qs;
   return DVM_OK;
 }
@@ -558,48 +515,6 @@ int dvm_track_finish(dvm_tracker* t, dvm_orb* h, const dvm_track_queries* q, dvm
 }
 
 // ---- the second half: Tracking::TrackLocalMap (src/Tracking.cc:2668-2740) behind the first
-namespace {
-// the upload block of one call, carved in the mapped staging buffer and at the same offsets in the device copy: [mvScaleFactors 64]
-// [mvInvLevelSigma2 64][per frame: the first half's pose 7 doubles, LocalFrameArgs, table offset, skip-flag switch][tables: T records,
-// frame b's at qoff[b]][frame_mp: count x kstride]
-struct LocalMapUpload {
-  float *scale, *inv_sigma2; double* pose; LocalFrameArgs* fa; int32_t *qoff, *skip_on; LocalPointPod* pts; int32_t* frame_mp; size_t bytes;
-};
-constexpr size_t kFrameRec = 7 * 8 + sizeof(LocalFrameArgs) + 8;     // per frame bytes of the frame block
-LocalMapUpload carve_local_map_upload(uint8_t* base, int count, size_t T, size_t kstride) {
-  LocalMapUpload u;
-  Cursor256 c{base};
-  u.scale = c.carve<float>(64); u.inv_sigma2 = c.carve<float>(64);
-  uint8_t* fb = c.carve<uint8_t>((size_t)count * kFrameRec);
-  u.pose = reinterpret_cast<double*>(fb); u.fa = reinterpret_cast<LocalFrameArgs*>(fb + (size_t)count * 56);
-  u.qoff = reinterpret_cast<int32_t*>(u.fa + count); u.skip_on = u.qoff + count;
-  u.pts = c.carve<LocalPointPod>(T); u.frame_mp = c.carve<int32_t>((size_t)count * kstride);
-  u.bytes = c.used();
-  return u;
-}
-// the same block where the tables are store slots (dvm_track_local_map_batch_resident): [mvScaleFactors 64][mvInvLevelSigma2 64][frame
-// block][the frames' stores: count device pointers][slots: T, frame b's at qoff[b]][frame_mp: count x kstride] -- copied up to here
-// (copy_bytes) in one copy -- then [tables: T records], device only: k_store_gather fills them from the stores
-struct LocalMapUploadResident { LocalMapUpload u; const LocalPointPod** stores; int32_t* slots; size_t copy_bytes; };
-LocalMapUploadResident carve_local_map_upload_resident(uint8_t* base, int count, size_t T, size_t kstride) {
-  LocalMapUploadResident r;
-  LocalMapUpload& u = r.u;
-  Cursor256 c{base};
-  u.scale = c.carve<float>(64); u.inv_sigma2 = c.carve<float>(64);
-  uint8_t* fb = c.carve<uint8_t>((size_t)count * kFrameRec);
-  u.pose = reinterpret_cast<double*>(fb); u.fa = reinterpret_cast<LocalFrameArgs*>(fb + (size_t)count * 56);
-  u.qoff = reinterpret_cast<int32_t*>(u.fa + count); u.skip_on = u.qoff + count;
-  Cursor<64> t{base, nullptr, c.used()};
-  r.stores = t.carve<const LocalPointPod*>((size_t)count); r.slots = t.carve<int32_t>(T);
-  u.frame_mp = reinterpret_cast<int32_t*>(base + t.used());
-  r.copy_bytes = t.used() + (size_t)count * kstride * 4;
-  c.off = pad<256>(r.copy_bytes);
-  u.pts = c.carve<LocalPointPod>(T);
-  u.bytes = c.used();
-  return r;
-}
-}  // namespace
-
 int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points) {
   if (!t || max_points < 1) return DVM_ERR_INVALID;
   // (the prologue is one workgroup per frame: beyond 1 << 20 points per frame it would dominate the chain, so such a table is refused)
@@ -610,31 +525,28 @@ int dvm_tracker_reserve_local_map(dvm_tracker* t, int max_points) {
   t->lm_cap = 0; t->lf.ready = 0; t->lf.batch_ready = 0;
   // P: table entries of one call (a batch: all frames' tables, each rounded up to 64); per keypoint and per frame: max_frames frames
   const size_t P = ((size_t)max_points + 63) & ~(size_t)63, K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
-  // (the last two items: the slot lists and store pointers of dvm_track_local_map_batch_resident, whose tables are filled on the device)
-  const size_t up = pad<256>(B * kFrameRec) + 2 * pad<256>(256) + pad<256>(P * sizeof(LocalPointPod)) + pad<256>(B * K * 4) + pad<256>(P * 4) + pad<256>(B * 8);
-  // device: upload copy, per-entry arrays (seen, pos, claims), per-keypoint arrays (frame_mp, skip), pose seeds, query arrays at any stride
-  // up to P, ranked lists, counters
-  const size_t dbytes = up + pad<256>(P) + pad<256>(P * 12) + pad<256>(P) + pad<256>(B * K * 4) + pad<256>(B * K) + pad<256>(B * 56) +
-                        pad<256>(P * 32) + 5 * pad<256>(P * 4) + pad<256>(P) + pad<256>(P * 4) + pad<256>(P * 16) + 2 * pad<256>(B * 32);
-  const size_t mbytes = up + pad<256>(B * K * 4) + pad<256>(B * K) + pad<256>(P * sizeof(TrackPoint)) + pad<256>(B * 64) + pad<256>(B * 56) +
-                        3 * pad<256>(B * 16);
-  if (const char* what = t->lmw.alloc(dbytes, mbytes, up, /*mapped*/ true, /*zeroed*/ true)) return reserve_failed("dvm_tracker_reserve_local_map", what);
-  Cursor256 c{t->lmw.hm + up};
-  auto& r = t->lm;
-  r.mp = c.carve<int32_t>(B * K); r.outlier = c.carve<uint8_t>(B * K); r.tp = c.carve<TrackPoint>(P); r.res = c.carve<int32_t>(B * 16);
-  r.pose = c.carve<double>(B * 7); r.n_inl = c.carve<int32_t>(B * 4); r.fin = c.carve<int32_t>(B * 4); r.nedges = c.carve<int32_t>(B * 4);
+  const size_t up = local_map_upload_capacity(B, P, K);
+  if (const char* what = t->lmw.alloc(up + carve_local_map_work(nullptr, B, P, K).bytes, up + carve_local_map_results(nullptr, B, K, P).bytes, up,
+                                      /*mapped*/ true, /*zeroed*/ true))
+    return reserve_failed("dvm_tracker_reserve_local_map", what);
+  t->lm = carve_local_map_results(t->lmw.hm + up, B, K, P);
   t->lm_cap = (int)P;
   return DVM_OK;
 }
 
 namespace {
+// one frame's local map as the three entry points hand it to local_map_run: the table as records, copied up (dvm_track_local_map[_batch]),
+// or as slots of the frame's store, gathered on the device (dvm_track_local_map_batch_resident); the frame's points; SearchByProjection's
+// th and far-point filter
+struct LocalSource {
+  int32_t n; const dvm_local_point* records; const int32_t* slots; const dvm_map_store* store;
+  const int32_t* frame_mp; float th; int far_points; float th_far;
+};
 // TrackLocalMap on the `count` frames of the last finish (t->lf), behind the entry points' state checks: the tables, the frames' points,
 // poses and parameters in ONE upload, ONE chain of batched launches, a workgroup (row of workgroups) per frame on grid slots 0..count-1,
-// ONE synchronisation.  A frame the first half did not complete is skipped.
-// in: the tables as records, copied up (dvm_track_local_map[_batch]); rin: the tables as store slots, gathered on the device
-// (dvm_track_local_map_batch_resident); one of the two is NULL
-int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_in_resident* rin, const dvm_local_map_out* out,
-                  dvm_track_local_result* res, int32_t* status) {
+// ONE synchronisation.  A frame the first half did not complete is skipped.  resident: every src[b] gives slots and a store, else records
+int local_map_run(dvm_tracker* t, dvm_orb* h, int count, bool resident, const LocalSource* src, const dvm_local_map_out* out, dvm_track_local_result* res,
+                  int32_t* status) {
   LocalFrame& f = t->lf;
   static const bool timing = std::getenv("DVM_TRACK_BATCH_TIMING") != nullptr;       // host-side phase times on stderr
   using clk = std::chrono::steady_clock;
@@ -646,16 +558,15 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
   for (int b = 0; b < count; b++) {
     qoff[b] = (int32_t)std::min(T, (size_t)INT32_MAX);
     if (f.status[b] != DVM_TRACK_COMPLETE) continue;
-    struct { int32_t n; const void* tab; const int32_t* frame_mp; } q = {in ? in[b].n : rin[b].n, in ? (const void*)in[b].pts : (const void*)rin[b].slots,
-                                                                         in ? in[b].frame_mp : rin[b].frame_mp};
+    const LocalSource& q = src[b];
     const int N = f.ns[b];
-    if (q.n < 0 || (q.n && !q.tab) || (N && !q.frame_mp) || !out[b].mp_out || !out[b].outlier) return DVM_ERR_INVALID;
+    if (q.n < 0 || (q.n && !(resident ? (const void*)q.slots : (const void*)q.records)) || (N && !q.frame_mp) || !out[b].mp_out || !out[b].outlier) return DVM_ERR_INVALID;
     for (int j = 0; j < N; j++)
       if (q.frame_mp[j] < -1 || q.frame_mp[j] >= q.n) { set_error("dvm_track_local_map_batch: frame_mp names a point outside the table"); return DVM_ERR_INVALID; }
-    if (rin && q.n) {     // every slot checked here, on the host: k_store_gather indexes the store with them
-      if (!rin[b].store) return DVM_ERR_INVALID;
-      if (store_device(rin[b].store) != t->device) { set_error("dvm_track_local_map_batch_resident: the store lives on another device"); return DVM_ERR_INVALID; }
-      if (!store_slots_ok(rin[b].store, rin[b].slots, q.n)) {
+    if (resident && q.n) {     // every slot checked here, on the host: k_store_gather indexes the store with them
+      if (!q.store) return DVM_ERR_INVALID;
+      if (store_device(q.store) != t->device) { set_error("dvm_track_local_map_batch_resident: the store lives on another device"); return DVM_ERR_INVALID; }
+      if (!store_slots_ok(q.store, q.slots, q.n)) {
         set_error("dvm_track_local_map_batch_resident: a slot outside its store or never written"); return DVM_ERR_INVALID;
       }
     }
@@ -667,8 +578,15 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
   if (!live) { f.ready = 0; f.batch_ready = 0; f.rkb_ready = 0; return DVM_OK; }
   const int ocap = f.ocap;
   const size_t Tc = std::max(T, (size_t)64);
-  const LocalMapUploadResident rup = rin ? carve_local_map_upload_resident(t->lmw.hm, count, Tc, (size_t)ocap) : LocalMapUploadResident{};
-  const LocalMapUpload up = rin ? rup.u : carve_local_map_upload(t->lmw.hm, count, Tc, (size_t)ocap);
+  // the upload block of this call in the staging buffer (hm) and, at the same offsets, in its device copy (d); copy_bytes: what goes up
+  const auto carve_upload = [&](uint8_t* base) {
+    if (resident) return carve_local_map_upload_resident(base, (size_t)count, Tc, (size_t)ocap);
+    LocalMapUploadResident r{carve_local_map_upload(base, (size_t)count, Tc, (size_t)ocap), nullptr, nullptr, 0};
+    r.copy_bytes = r.u.bytes;
+    return r;
+  };
+  const LocalMapUploadResident rup = carve_upload(t->lmw.hm), drup = carve_upload(t->lmw.d);
+  const LocalMapUpload &up = rup.u, &dup = drup.u;
   if (up.bytes > t->lmw.up_bytes) { set_error("dvm_track_local_map_batch: the upload block exceeds the reservation"); return DVM_ERR_CAPACITY; }
   DVM_HIP(hipSetDevice(t->device));
   hipStream_t s = (hipStream_t)dvm_orb_stream(h);
@@ -680,43 +598,35 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
   std::memcpy(up.inv_sigma2, f.inv_sigma2, 64 * 4);
   HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {       // (32 tables of 3 000 points: 7 MB)
     const bool go = f.status[b] == DVM_TRACK_COMPLETE;
+    const LocalSource& q = src[b];
     int32_t* fm = up.frame_mp + b * (size_t)ocap;
     std::memcpy(up.pose + 7 * b, f.poses.data() + 7 * b, 56);    // the finish's pose, or the reference-keyframe chain's
-    const int far_points = !go ? 0 : in ? in[b].far_points : rin[b].far_points;
-    up.fa[b] = LocalFrameArgs{nb[b], far_points ? 1 : 0, !go ? 1.0f : in ? in[b].th : rin[b].th, !go ? 0.0f : in ? in[b].th_far : rin[b].th_far};
+    up.fa[b] = go ? LocalFrameArgs{nb[b], q.far_points ? 1 : 0, q.th, q.th_far} : LocalFrameArgs{0, 0, 1.0f, 0.0f};
     up.qoff[b] = qoff[b]; up.skip_on[b] = 1;
-    if (rin) rup.stores[b] = go && nb[b] ? store_records(rin[b].store) : nullptr;
+    if (resident) rup.stores[b] = go && nb[b] ? store_records(q.store) : nullptr;
     if (go) {
-      if (nb[b] && in) std::memcpy(up.pts + qoff[b], in[b].pts, (size_t)nb[b] * sizeof(LocalPointPod));
-      if (nb[b] && rin) std::memcpy(rup.slots + qoff[b], rin[b].slots, (size_t)nb[b] * 4);
-      if (f.ns[b]) std::memcpy(fm, (in ? in[b].frame_mp : rin[b].frame_mp), (size_t)f.ns[b] * 4);
+      if (nb[b] && !resident) std::memcpy(up.pts + qoff[b], q.records, (size_t)nb[b] * sizeof(LocalPointPod));
+      if (nb[b] && resident) std::memcpy(rup.slots + qoff[b], q.slots, (size_t)nb[b] * 4);
+      if (f.ns[b]) std::memcpy(fm, q.frame_mp, (size_t)f.ns[b] * 4);
     } else {
       for (int j = 0; j < ocap; j++) fm[j] = -1;        // a skipped frame holds nothing and searches nothing
     }
   });
-  DVM_HIP(hipMemcpyAsync(t->lmw.d, t->lmw.hm, rin ? rup.copy_bytes : up.bytes, hipMemcpyHostToDevice, s));
-  t->up_second = (int64_t)(rin ? rup.copy_bytes : up.bytes);
+  DVM_HIP(hipMemcpyAsync(t->lmw.d, t->lmw.hm, rup.copy_bytes, hipMemcpyHostToDevice, s));
+  t->up_second = (int64_t)rup.copy_bytes;
   const clk::time_point tp1 = clk::now();
-  const LocalMapUploadResident drup = rin ? carve_local_map_upload_resident(t->lmw.d, count, Tc, (size_t)ocap) : LocalMapUploadResident{};
-  const LocalMapUpload dup = rin ? drup.u : carve_local_map_upload(t->lmw.d, count, Tc, (size_t)ocap);
-  if (rin) {     // the device tables from the stores, behind their last updates
+  if (resident) {     // the device tables from the stores, behind their last updates
     for (int b = 0; b < count; b++)
-      if (f.status[b] == DVM_TRACK_COMPLETE && nb[b]) { rc = store_read_begin(rin[b].store, s); if (rc != DVM_OK) return rc; }
+      if (f.status[b] == DVM_TRACK_COMPLETE && nb[b]) { rc = store_read_begin(src[b].store, s); if (rc != DVM_OK) return rc; }
     launch_store_gather(s, StoreGather{drup.stores, dup.fa, dup.qoff, drup.slots}, dup.pts, count, (int)span_max);
     for (int b = 0; b < count; b++)
-      if (f.status[b] == DVM_TRACK_COMPLETE && nb[b]) { rc = store_read_end(rin[b].store, s); if (rc != DVM_OK) return rc; }
+      if (f.status[b] == DVM_TRACK_COMPLETE && nb[b]) { rc = store_read_end(src[b].store, s); if (rc != DVM_OK) return rc; }
   }
   // 2. device arrays of this call: per entry at the frames' offsets, per keypoint at b * ocap
-  const size_t Kb = (size_t)count * ocap;
-  LocalQueries LQ;
-  Cursor256 c{t->lmw.d + t->lmw.up_bytes};
-  LQ.seen = c.carve<uint8_t>(Tc); LQ.pos = c.carve<float>(Tc * 3); LQ.claims = c.carve<uint8_t>(Tc);
-  LQ.frame_mp = c.carve<int32_t>(Kb); LQ.skip = c.carve<uint8_t>(Kb); LQ.pose_in = c.carve<double>((size_t)count * 7);
-  LQ.qdesc = c.carve<uint8_t>(Tc * 32); LQ.qx = c.carve<float>(Tc); LQ.qy = c.carve<float>(Tc); LQ.qr = c.carve<float>(Tc);
-  LQ.qmin = c.carve<int32_t>(Tc); LQ.qmax = c.carve<int32_t>(Tc); LQ.q_claims = c.carve<uint8_t>(Tc); LQ.q_tab = c.carve<int32_t>(Tc);
-  uint32_t* d_ranked = c.carve<uint32_t>(Tc * 4);
-  int32_t* d_lres = c.carve<int32_t>((size_t)count * 8);
-  LQ.nq = c.carve<int32_t>((size_t)count * 8);
+  const LocalMapWork W = carve_local_map_work(t->lmw.d + t->lmw.up_bytes, (size_t)count, Tc, (size_t)ocap);
+  const LocalQueries& LQ = W.LQ;
+  uint32_t* const d_ranked = W.ranked;
+  int32_t* const d_lres = W.lres;
   LocalMapArgs A;
   A.fx = (float)f.cam.fx; A.fy = (float)f.cam.fy; A.cx = (float)f.cam.cx; A.cy = (float)f.cam.cy;
   A.min_x = f.bounds[0]; A.max_x = f.bounds[1]; A.min_y = f.bounds[2]; A.max_y = f.bounds[3];
@@ -738,16 +648,16 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
   TrackRequery rq{};
   rq.F = FV;
   rq.qdesc = LQ.qdesc; rq.qx = LQ.qx; rq.qy = LQ.qy; rq.qr = LQ.qr; rq.qmin = LQ.qmin; rq.qmax = LQ.qmax;
-  launch_track_claims_local(s, d_ranked, LQ, rq, f.d_un, f.d_n, ocap, 100 /* TH_HIGH */, 0.8f, t->d_assign, d_lres, t->lmw.dev(r.mp),
+  launch_track_claims_local(s, d_ranked, LQ, rq, f.d_un, f.d_n, ocap, 100 /* TH_HIGH */, 0.8f, t->dv.assign, d_lres, t->lmw.dev(r.mp),
                             t->lmw.dev(r.res) + 8 * count, TB);
   // 6. PoseOptimization's edges in keypoint order (positions from the table; no min_matches gate: below 3 edges the pose stays), the pose
   //    seeded from the first half's float pose, the outlier flags and mnMatchesInliers
   const TrackBatch TE{count, 0, f.kps_stride, nullptr, dup.qoff};
-  launch_track_gather(s, t->d_assign, f.d_un, f.d_n, ocap, LQ.pos, dup.inv_sigma2, f.nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp,
-                      t->d_nedges, d_lres, 0, t->lmw.dev(r.nedges), TE);
-  launch_pose_optimize(s, f.model, f.cam, LQ.pose_in, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, t->lmw.dev(r.pose), t->d_edge_out,
-                       t->lmw.dev(r.n_inl), t->d_chi);
-  launch_track_finish(s, t->d_assign, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, LQ.claims, t->lmw.dev(r.outlier), t->lmw.dev(r.fin),
+  launch_track_gather(s, t->dv.assign, f.d_un, f.d_n, ocap, LQ.pos, dup.inv_sigma2, f.nlevels, t->dv.Xw, t->dv.obs, t->dv.info, t->dv.edge_kp,
+                      t->dv.nedges, d_lres, 0, t->lmw.dev(r.nedges), TE);
+  launch_pose_optimize(s, f.model, f.cam, LQ.pose_in, t->dv.Xw, t->dv.obs, t->dv.info, t->dv.nedges, ocap, count, t->lmw.dev(r.pose), t->dv.edge_out,
+                       t->lmw.dev(r.n_inl), t->dv.chi);
+  launch_track_finish(s, t->dv.assign, f.d_n, ocap, t->dv.edge_kp, t->dv.nedges, t->dv.edge_out, LQ.claims, t->lmw.dev(r.outlier), t->lmw.dev(r.fin),
                       d_lres, TE);
   t->clear_next();   // once per finish
   rc = hip_check(hipGetLastError(), "local map chain launch");
@@ -781,49 +691,53 @@ int local_map_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in*
 }
 }  // namespace
 
+// the state check the three entry points share: right after `after` on this tracker and extractor (count 0: the single call, on one
+// frame that completed), with the working set reserved
+static int local_map_state(const char* fn, const char* after, const dvm_tracker* t, const dvm_orb* h, int count) {
+  const LocalFrame& f = t->lf;
+  if (!(count ? f.batch_ready && f.count == count : f.ready) || f.h != h || orb_result_serial(h) != f.serial) {
+    set_error(std::string(fn) + ": not right after a " + after + " (same tracker and extractor)");
+    return DVM_ERR_STATE;
+  }
+  if (!t->lmw.d) { set_error(std::string(fn) + ": no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
+  return DVM_OK;
+}
+
 int dvm_track_local_map(dvm_tracker* t, dvm_orb* h, const dvm_local_point* pts, int n, const int32_t* frame_mp, float th, int far_points,
                         float th_far, int32_t* mp_out, uint8_t* outlier, dvm_track_point* track_pts, dvm_track_local_result* res) {
   if (!t || !h || !mp_out || !outlier || !res || n < 0 || (n && !pts)) return DVM_ERR_INVALID;
-  LocalFrame& f = t->lf;
-  if (!f.ready || f.h != h || orb_result_serial(h) != f.serial) {
-    set_error("dvm_track_local_map: not right after a dvm_track_finish of one frame that returned DVM_TRACK_COMPLETE (same tracker and extractor)");
-    return DVM_ERR_STATE;
-  }
-  if (!t->lmw.d) { set_error("dvm_track_local_map: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
+  const int rc = local_map_state("dvm_track_local_map", "dvm_track_finish of one frame that returned DVM_TRACK_COMPLETE", t, h, 0);
+  if (rc != DVM_OK) return rc;
   if (n > t->lm_cap) { set_error("dvm_track_local_map: more local map points than reserved"); return DVM_ERR_CAPACITY; }
-  const int N = f.ns[0];
+  const int N = t->lf.ns[0];
   if (N && !frame_mp) return DVM_ERR_INVALID;
   for (int j = 0; j < N; j++)
     if (frame_mp[j] < -1 || frame_mp[j] >= n) { set_error("dvm_track_local_map: frame_mp names a point outside the table"); return DVM_ERR_INVALID; }
   // the batch of one frame (ready: its first-half status is DVM_TRACK_COMPLETE)
-  const dvm_local_map_in in{pts, n, frame_mp, th, far_points, th_far};
+  const LocalSource src{n, pts, nullptr, nullptr, frame_mp, th, far_points, th_far};
   const dvm_local_map_out out{mp_out, outlier, track_pts};
   int32_t status = 0;
-  return local_map_run(t, h, 1, &in, nullptr, &out, res, &status);
+  return local_map_run(t, h, 1, false, &src, &out, res, &status);
 }
 
 int dvm_track_local_map_batch(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in* in, const dvm_local_map_out* out,
                               dvm_track_local_result* res, int32_t* status) {
   if (!t || !h || !in || !out || !res || !status || count < 1) return DVM_ERR_INVALID;
-  LocalFrame& f = t->lf;
-  if (!f.batch_ready || f.h != h || orb_result_serial(h) != f.serial || f.count != count) {
-    set_error("dvm_track_local_map_batch: not right after a dvm_track_finish[_batch] of `count` frames (same tracker and extractor)");
-    return DVM_ERR_STATE;
-  }
-  if (!t->lmw.d) { set_error("dvm_track_local_map_batch: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
-  return local_map_run(t, h, count, in, nullptr, out, res, status);
+  const int rc = local_map_state("dvm_track_local_map_batch", "dvm_track_finish[_batch] of `count` frames", t, h, count);
+  if (rc != DVM_OK) return rc;
+  std::vector<LocalSource> src((size_t)count);
+  for (int b = 0; b < count; b++) src[b] = LocalSource{in[b].n, in[b].pts, nullptr, nullptr, in[b].frame_mp, in[b].th, in[b].far_points, in[b].th_far};
+  return local_map_run(t, h, count, false, src.data(), out, res, status);
 }
 
 int dvm_track_local_map_batch_resident(dvm_tracker* t, dvm_orb* h, int count, const dvm_local_map_in_resident* in, const dvm_local_map_out* out,
                                        dvm_track_local_result* res, int32_t* status) {
   if (!t || !h || !in || !out || !res || !status || count < 1) return DVM_ERR_INVALID;
-  LocalFrame& f = t->lf;
-  if (!f.batch_ready || f.h != h || orb_result_serial(h) != f.serial || f.count != count) {
-    set_error("dvm_track_local_map_batch_resident: not right after a dvm_track_finish[_batch][_resident] of `count` frames (same tracker and extractor)");
-    return DVM_ERR_STATE;
-  }
-  if (!t->lmw.d) { set_error("dvm_track_local_map_batch_resident: no dvm_tracker_reserve_local_map on this tracker"); return DVM_ERR_STATE; }
-  return local_map_run(t, h, count, nullptr, in, out, res, status);
+  const int rc = local_map_state("dvm_track_local_map_batch_resident", "dvm_track_finish[_batch][_resident] of `count` frames", t, h, count);
+  if (rc != DVM_OK) return rc;
+  std::vector<LocalSource> src((size_t)count);
+  for (int b = 0; b < count; b++) src[b] = LocalSource{in[b].n, nullptr, in[b].slots, in[b].store, in[b].frame_mp, in[b].th, in[b].far_points, in[b].th_far};
+  return local_map_run(t, h, count, true, src.data(), out, res, status);
 }
 
 // ---- the other way into the second half: Tracking::TrackReferenceKeyFrame (src/Tracking.cc:2461-2520) on the frames of a finish, or on
@@ -858,55 +772,15 @@ int check_refkf_frame(const char* fn, const dvm_ref_keyframe* kf, const dvm_trac
   return DVM_OK;
 }
 
-// the upload block of one call: [mvInvLevelSigma2 64][per frame: pose_in 7 doubles, keyframe offset, node count, res 8][run list][wg_base]
-// [keyframes: T entries, frame b's at qoff[b] -- desc x 32, angle, use, claims, pos x 3, mFeatVec nodes, features][mFeatVec offsets: T + count,
-// frame b's at qoff[b] + b]
-struct KeyframeUpload {
-  float* inv_sigma2; double* pose; int32_t *qoff, *kfv_n, *res, *run, *wg_base;
-  uint8_t* desc; float* angle; uint8_t *use, *claims; float* pos; int32_t *fv_node, *fv_feat, *fv_off; size_t bytes;
-};
-KeyframeUpload carve_keyframe_upload(uint8_t* base, int count, size_t T) {
-  KeyframeUpload u;
-  Cursor256 c{base};
-  const size_t B = (size_t)count;
-  u.inv_sigma2 = c.carve<float>(64); u.pose = c.carve<double>(B * 7); u.qoff = c.carve<int32_t>(B); u.kfv_n = c.carve<int32_t>(B);
-  u.res = c.carve<int32_t>(B * 8); u.run = c.carve<int32_t>(B); u.wg_base = c.carve<int32_t>(B + 1);
-  u.desc = c.carve<uint8_t>(T * 32); u.angle = c.carve<float>(T); u.use = c.carve<uint8_t>(T); u.claims = c.carve<uint8_t>(T);
-  u.pos = c.carve<float>(T * 3); u.fv_node = c.carve<int32_t>(T); u.fv_feat = c.carve<int32_t>(T); u.fv_off = c.carve<int32_t>(T + B);
-  u.bytes = c.used();
-  return u;
-}
-// the device working set behind the upload, per frame at the call's capacity stride (cap <= kp_cap, count <= max_frames)
-struct RefKfWork { int32_t *word, *node; double* w; int32_t *fv_node, *fv_feat, *fv_off, *cnt, *match, *bin; size_t bytes; };
-RefKfWork carve_refkf_work(uint8_t* base, size_t B, size_t K) {
-  RefKfWork r;
-  Cursor256 c{base};
-  r.word = c.carve<int32_t>(B * K); r.node = c.carve<int32_t>(B * K); r.w = c.carve<double>(B * K);
-  r.fv_node = c.carve<int32_t>(B * K); r.fv_feat = c.carve<int32_t>(B * K); r.fv_off = c.carve<int32_t>(B * (K + 1));
-  r.cnt = c.carve<int32_t>(B * kRefKfCnt); r.match = c.carve<int32_t>(B * K); r.bin = c.carve<int32_t>(B * K);
-  r.bytes = c.used();
-  return r;
-}
-// the mapped results behind the upload staging: BowVector, FeatureVector, match, counters, outlier flags, edges / inliers / nmatchesMap,
-// pose, B slices each; returns their bytes
-size_t carve_refkf_results(uint8_t* base, size_t B, size_t K, RefKfMapped& r) {
-  Cursor256 c{base};
-  r.bow_ids = c.carve<int32_t>(B * K); r.bow_vals = c.carve<double>(B * K); r.fv_node = c.carve<int32_t>(B * K); r.fv_feat = c.carve<int32_t>(B * K);
-  r.fv_off = c.carve<int32_t>(B * (K + 1)); r.match = c.carve<int32_t>(B * K); r.cnt = c.carve<int32_t>(B * 8); r.outlier = c.carve<uint8_t>(B * K);
-  r.nedges = c.carve<int32_t>(B * 4); r.n_inl = c.carve<int32_t>(B * 4); r.fin = c.carve<int32_t>(B * 4); r.pose = c.carve<double>(B * 7);
-  return c.used();
-}
-
 // (re)allocates w for keyframes of R entries per call (a multiple of 64) and the tracker's max_frames frames; fn names the caller's errors
 int reserve_refkf(dvm_tracker* t, RefKf& w, size_t R, const char* fn) {
   DVM_HIP(hipSetDevice(t->device));
   w.cap = 0;
   const size_t K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
-  const size_t up = carve_keyframe_upload(nullptr, (int)B, R).bytes;
-  RefKfMapped sized;
-  if (const char* what = w.ws.alloc(up + carve_refkf_work(nullptr, B, K).bytes, up + carve_refkf_results(nullptr, B, K, sized), up, /*mapped*/ true, /*zeroed*/ true))
+  const size_t up = carve_keyframe_upload(nullptr, B, R).bytes;
+  if (const char* what = w.ws.alloc(up + carve_refkf_work(nullptr, B, K).bytes, up + carve_refkf_results(nullptr, B, K).bytes, up, /*mapped*/ true, /*zeroed*/ true))
     return reserve_failed(fn, what);
-  carve_refkf_results(w.ws.hm + up, B, K, w.r);
+  w.r = carve_refkf_results(w.ws.hm + up, B, K);
   w.cap = (int)R;
   return DVM_OK;
 }
@@ -1017,11 +891,11 @@ int refkf_enqueue(dvm_tracker* t, RefKf& w, dvm_orb* h, const dvm_vocab* voc, in
   launch_refkf_search(s, A, f.d_un, f.d_desc, f.d_n, ocap, P0.th_low, P0.nnratio);
   launch_refkf_settle(s, A, f.d_n, ocap, P0.check_ori);
   const TrackBatch TE{count, 0, f.kps_stride, nullptr, dup.qoff};
-  launch_track_gather(s, W.match, f.d_un, f.d_n, ocap, dup.pos, dup.inv_sigma2, P0.nlevels, t->d_Xw, t->d_obs, t->d_info, t->d_edge_kp, t->d_nedges,
+  launch_track_gather(s, W.match, f.d_un, f.d_n, ocap, dup.pos, dup.inv_sigma2, P0.nlevels, t->dv.Xw, t->dv.obs, t->dv.info, t->dv.edge_kp, t->dv.nedges,
                       dup.res, P0.min_matches, w.ws.dev(r.nedges), TE);
-  launch_pose_optimize(s, f.model, P0.cam, dup.pose, t->d_Xw, t->d_obs, t->d_info, t->d_nedges, ocap, count, w.ws.dev(r.pose), t->d_edge_out,
-                       w.ws.dev(r.n_inl), t->d_chi);
-  launch_track_finish(s, W.match, f.d_n, ocap, t->d_edge_kp, t->d_nedges, t->d_edge_out, dup.claims, w.ws.dev(r.outlier), w.ws.dev(r.fin), dup.res, TE);
+  launch_pose_optimize(s, f.model, P0.cam, dup.pose, t->dv.Xw, t->dv.obs, t->dv.info, t->dv.nedges, ocap, count, w.ws.dev(r.pose), t->dv.edge_out,
+                       w.ws.dev(r.n_inl), t->dv.chi);
+  launch_track_finish(s, W.match, f.d_n, ocap, t->dv.edge_kp, t->dv.nedges, t->dv.edge_out, dup.claims, w.ws.dev(r.outlier), w.ws.dev(r.fin), dup.res, TE);
   return hip_check(hipGetLastError(), "reference keyframe chain launch");
 }
 
@@ -1120,10 +994,10 @@ int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* vo
     if (ocap > t->kp_cap) { set_error("dvm_track_reference_keyframe: the extractor's keypoint capacity exceeds the tracker's"); return DVM_ERR_CAPACITY; }
     const dvm_keypoint* un = d_kps;
     if (undist) {
-      rc = dvm_undistort_keypoints(p->dist, d_kps, reinterpret_cast<dvm_keypoint*>(t->d_kps_un), ocap, 1, s);
+      rc = dvm_undistort_keypoints(p->dist, d_kps, reinterpret_cast<dvm_keypoint*>(t->dv.kps_un), ocap, 1, s);
       if (rc != DVM_OK) return rc;
-      un = reinterpret_cast<const dvm_keypoint*>(t->d_kps_un);
-      if (out->kps_un) DVM_HIP(hipMemcpyAsync(t->m.kps_un, t->d_kps_un, (size_t)ocap * sizeof(dvm_keypoint_pod), hipMemcpyDeviceToHost, s));
+      un = reinterpret_cast<const dvm_keypoint*>(t->dv.kps_un);
+      if (out->kps_un) DVM_HIP(hipMemcpyAsync(t->m.kps_un, t->dv.kps_un, (size_t)ocap * sizeof(dvm_keypoint_pod), hipMemcpyDeviceToHost, s));
     }
     rc = dvm_frame_build_batch(t->grid, 0, 1, un, ocap, d_desc, (int64_t)ocap * 32, d_n, p->bounds[0], p->bounds[1], p->bounds[2], p->bounds[3], s);
     if (rc != DVM_OK) return rc;

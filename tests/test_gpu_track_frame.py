@@ -146,6 +146,81 @@ def test_track_frame_dense_stream_requeries_on_device():
     trk.close(); ext.close()
 
 
+_NO_REQUERY_WORKER = """
+import sys, numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+from dvm_slam_amd import capi, synth
+from test_gpu_track_frame import BOUNDS, _check, _separate_calls
+frames = synth.frame_stream(4)
+ext = capi.OrbExtractor(max_batch=1)
+tab = ext.tables()
+scale, inv_s2 = tab["scale"], tab["inv_sigma2"]
+trk = capi.Tracker(ext)
+rng = np.random.default_rng(9)
+Kc = np.array([500.0, 500.0, 320.0, 240.0], np.float32)
+Tcw = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)
+replayed, singles, lasts = 0, [], []
+for t in (1, 2, 3):           # the frames of test_track_frame_dense_stream_requeries_on_device
+    n0, k0, d0, _ = ext.extract(frames[t - 1])
+    z = rng.uniform(3, 9, n0).astype(np.float32)
+    mps = np.zeros(n0, capi.MAP_POINT_DTYPE)
+    mps["pos"][:, 0] = (k0["x"] - Kc[2]) / Kc[0] * z; mps["pos"][:, 1] = (k0["y"] - Kc[3]) / Kc[1] * z; mps["pos"][:, 2] = z
+    mps["desc"] = d0; mps["n_obs"] = 1
+    mp_l = np.arange(n0, dtype=np.int32)
+    fused = trk.track(frames[t], Tcw, Kc, BOUNDS, scale, inv_s2, k0, mp_l, None, mps, th=15.0)
+    fused = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in fused.items()}
+    replayed += fused["replayed_on_host"]
+    sep = _separate_calls(lambda im: ext.extract(im),
+                          lambda k, d, m, T, kl, ml, mp_, th_: capi.search_by_projection_frames(k, d, m, T, Kc, BOUNDS, scale, kl, ml, None, mp_, th_)[:2],
+                          lambda p, X, o, w: [r[0] for r in capi.pose_optimize(p[None], X[None], o[None], w[None], [len(X)], Kc)],
+                          frames[t], Tcw, scale, inv_s2, k0, mp_l, mps, 15.0)
+    _check(fused, sep, exact_pose=True)
+    singles.append(fused); lasts.append((k0.copy(), mp_l, None, mps))
+assert replayed >= 1, "no frame was replayed on the host under DVM_TRACK_NO_REQUERY"
+if sys.argv[1] == "batch":    # two of the frames in one batched call: every key of the single calls' results, bit for bit
+    extB = capi.OrbExtractor(max_batch=2)
+    trkB = capi.TrackerBatch(extB, 2)
+    ins, keep = trkB.prepare([Tcw, Tcw], lasts[:2])
+    got = trkB.track(np.stack([frames[1], frames[2]]), ins, Kc, BOUNDS, scale, inv_s2, th=15.0)
+    assert sum(g["replayed_on_host"] for g in got) >= 1
+    for g, one in zip(got, singles[:2]):
+        assert sorted(g) == sorted(one)
+        for k in one:
+            if k in ("kps", "kps_un"):
+                assert g[k].tobytes() == one[k].tobytes(), k
+            elif isinstance(one[k], np.ndarray):
+                assert g[k].dtype == one[k].dtype and g[k].tobytes() == one[k].tobytes(), k
+            else:
+                assert g[k] == one[k], (k, g[k], one[k])
+    trkB.close(); extB.close()
+trk.close(); ext.close()
+print("replayed", replayed)
+"""
+
+
+def _run_no_requery_worker(mode):
+    import os
+    import subprocess
+    import sys
+    tests = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, "-c", _NO_REQUERY_WORKER % (os.path.dirname(tests), tests), mode], env={**os.environ, "DVM_TRACK_NO_REQUERY": "1"},
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
+    assert "replayed" in r.stdout
+
+
+def test_track_frame_replays_on_host_without_device_requery():
+    """DVM_TRACK_NO_REQUERY (read once per process: a fresh child) switches the device's second search of a window off: a query whose four
+    ranked candidates are all taken hands the frame back as DVM_TRACK_REPLAY_ON_HOST and dvmh_track_with_motion_model runs the separate
+    calls on it.  On the dense stream at least one frame takes that path, and every frame equals the separate calls bit for bit."""
+    _run_no_requery_worker("single")
+
+
+def test_track_batch_replays_on_host_without_device_requery():
+    """The same fallback per frame of a batch: two of those frames in one TrackerBatch.track equal the two single calls key for key."""
+    _run_no_requery_worker("batch")
+
+
 def test_track_batch_equals_single_frames():
     """dvmh_track_with_motion_model_batch: the frames of several agents (different streams, different maps, different numbers of queries, one
     of them with too few matches -> the doubled window) through ONE chain of batched launches: every frame's outputs equal the single call's."""

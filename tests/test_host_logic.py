@@ -63,6 +63,36 @@ def test_ba_ordering_and_level_schedule(tmp_path):
         assert levels(n, "1") <= 9, n
 
 
+def _build_and_run_tool(tmp_path, name, flags):
+    """tools/<name>.cpp as a plain program and once more with AddressSanitizer + UBSan (its own main, nothing preloaded): both runs clean"""
+    src = os.path.join(ROOT, "tools", name + ".cpp")
+    outs = []
+    for tag, extra in (("plain", ["-O2"]), ("san", ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])):
+        exe = tmp_path / f"{name}_{tag}"
+        subprocess.check_call(["g++", "-std=c++17", *extra, *flags, "-o", str(exe), src])
+        out = subprocess.run([str(exe)], capture_output=True, text=True)
+        assert out.returncode == 0, (tag, out.stdout[-3000:] + out.stderr[-3000:])
+        assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, (tag, out.stderr[-3000:])
+        outs.append(out.stdout)
+    return outs
+
+
+def test_track_working_set_layouts(tmp_path):
+    """dvm_slam_amd/csrc/track_layout.h (tools/check_track_layout.cpp): over a grid of tracker shapes every reservation is its layout
+    measured at the largest arguments and equals the formula it was summed by before, the items are aligned, inside and disjoint, and
+    every smaller call shape fits.  The layouts' element types come from the kernel headers, hence the HIP include path (host pass only)."""
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    for out in _build_and_run_tool(tmp_path, "check_track_layout", ["-w", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include")]):
+        assert "every size as reserved before" in out
+
+
+def test_track_frame_epilogue(tmp_path):
+    """dvm_slam_amd/host/track_settle.h (tools/check_track_settle.cpp): the per-frame epilogue of the tracked-frame host calls on
+    hand-written frames -- complete with an outlier, too few matches, nothing assigned, ids from the resident entry lists."""
+    for out in _build_and_run_tool(tmp_path, "check_track_settle", ["-Wall", "-I" + os.path.join(ROOT, "include")]):
+        assert "all frames as written" in out
+
+
 def test_generated_cholesky_panel_is_in_sync(tmp_path):
     """csrc/chol_panel.inc (the straight-line 16-column panel of k_chol_diag) is generated: the committed file must be what
     tools/gen_chol_panel.py writes, and the stream must hold the whole factorisation -- 16 reciprocal square roots, the 15
