@@ -1806,9 +1806,18 @@ class Vocabulary:
         self.keep = [np.ascontiguousarray(voc[k]) for k in ("child_off", "children", "desc", "weight", "word_id")]
         check(L.dvm_vocab_create(device, voc["n_nodes"], *[_p(a) for a in self.keep], voc["L"], C.byref(self.h)))
 
-    def transform(self, features, levelsup):
+    def transform(self, features, levelsup, on_device=False):
+        """(word id, node id, weight) per feature.  on_device: the form on device pointers (torch tensors, the null stream)."""
         f = np.ascontiguousarray(features, np.uint8).reshape(-1, 32)
         n = len(f)
+        if on_device and n:
+            import torch
+            df = torch.from_numpy(f).cuda()
+            dw = torch.full((n,), -7, dtype=torch.int32, device="cuda"); dn = torch.full_like(dw, -7)
+            dwt = torch.full((n,), -7.0, dtype=torch.float64, device="cuda")
+            check(self.L.dvm_vocab_transform(self.h, df.data_ptr(), n, levelsup, dw.data_ptr(), dn.data_ptr(), dwt.data_ptr(), 1, None))
+            torch.cuda.synchronize()
+            return dw.cpu().numpy(), dn.cpu().numpy(), dwt.cpu().numpy()
         word = np.zeros(max(n, 1), np.int32); node = np.zeros(max(n, 1), np.int32); w = np.zeros(max(n, 1), np.float64)
         check(self.L.dvm_vocab_transform(self.h, _p(f) if n else None, n, levelsup, _p(word), _p(node), _p(w), 0, None))
         return word[:n], node[:n], w[:n]

@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(256) k_bt_search(const BtKfDev* __restrict__ t
   const int kb = C.fv_off[a], ke = C.fv_off[a + 1];
   int fb = 0, fe = 0;
   {
-    const int at = fv_find<uint32_t>(K.fv_node, K.fv_n, C.fv_node[a]);   // the target's nodes ascend as unsigned
+    const int at = fv_find(K.fv_node, K.fv_n, C.fv_node[a]);   // the target's nodes ascend as unsigned
     if (at >= 0) { fb = K.fv_off[at]; fe = K.fv_off[at + 1]; }
   }
   if (fe <= fb) {                           // the target does not have the node: nothing of it matches

@@ -1031,6 +1031,15 @@ int dvm_vocab_create(int device, int n_nodes, const int32_t* child_off, const in
   if (child_off[0] != 0 || nch < 0) { set_error("vocabulary: bad child_off"); return DVM_ERR_INVALID; }
   for (int i = 0; i < n_nodes; i++) if (child_off[i + 1] < child_off[i]) { set_error("vocabulary: child_off not monotone"); return DVM_ERR_INVALID; }
   for (int c = 0; c < nch; c++) if (children[c] <= 0 || children[c] >= n_nodes) { set_error("vocabulary: child id out of range"); return DVM_ERR_INVALID; }
+  // a tree the walk of k_vocab_transform leaves: every child's id above its parent's (DBoW2 numbers nodes in creation order, a file read by
+  // loadFromTextFile names parents before children), every node but the root under exactly one parent.  A back edge would loop on the device.
+  std::vector<uint8_t> listed((size_t)n_nodes, 0);
+  for (int i = 0; i < n_nodes; i++)
+    for (int c = child_off[i]; c < child_off[i + 1]; c++) {
+      if (children[c] <= i) { set_error("vocabulary: child id not above its parent's (a cycle, or nodes not in creation order)"); return DVM_ERR_INVALID; }
+      if (listed[children[c]]++) { set_error("vocabulary: node listed under two parents"); return DVM_ERR_INVALID; }
+    }
+  if (nch != n_nodes - 1) { set_error("vocabulary: a node other than the root has no parent"); return DVM_ERR_INVALID; }
   DVM_HIP(hipSetDevice(device));
   dvm_vocab* v = new dvm_vocab;
   v->device = device; v->n_nodes = n_nodes; v->L = L;

@@ -169,15 +169,13 @@ __device__ __forceinline__ void block_sum4_put(int v, int* s4) {
 }
 __device__ __forceinline__ int block_sum4(const int* s4) { return s4[0] + s4[1] + s4[2] + s4[3]; }
 
-// ---- FeatureVector lookups.  fv_find: the index of `node` in the ascending list fv_node[0 .. fv_n) or -1; ORDER is the type the ids
-// ascend as -- uint32_t in the lists k_refkf_bow sorts and the BoW targets pack (node -1 last), int32_t in the new-points keyframes
-// (check_keyframe, new_points.cpp).
-template <class ORDER>
+// ---- FeatureVector lookups.  fv_find: the index of `node` in the ascending list fv_node[0 .. fv_n) or -1.  DBoW2's NodeId is
+// unsigned, so every list ascends as uint32_t: node -1 (a walk that ended above level L - levelsup) is last.
 __device__ __forceinline__ int fv_find(const int32_t* __restrict__ fv_node, int fv_n, int32_t node) {
   int lo = 0, hi = fv_n;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
-    if ((ORDER)fv_node[mid] < (ORDER)node) lo = mid + 1; else hi = mid;
+    if ((uint32_t)fv_node[mid] < (uint32_t)node) lo = mid + 1; else hi = mid;
   }
   return lo < fv_n && fv_node[lo] == node ? lo : -1;
 }

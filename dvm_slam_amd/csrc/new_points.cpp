@@ -46,7 +46,8 @@ int check_keyframe(const dvm_np_keyframe& k, const char* who, int n_levels) {
     if (k.fv_off[0] != 0) return fail(DVM_ERR_INVALID, w + ": FeatureVector offsets do not start at 0");
     for (int a = 0; a < k.fv_n; a++) {
       if (k.fv_off[a + 1] < k.fv_off[a]) return fail(DVM_ERR_INVALID, w + ": FeatureVector offsets not monotone");
-      if (a > 0 && k.fv_node[a] <= k.fv_node[a - 1]) return fail(DVM_ERR_INVALID, w + ": FeatureVector nodes not ascending");
+      if (a > 0 && (uint32_t)k.fv_node[a] <= (uint32_t)k.fv_node[a - 1])
+        return fail(DVM_ERR_INVALID, w + ": FeatureVector nodes not ascending (as unsigned: node -1 is last)");
     }
     const int nf = k.fv_off[k.fv_n];
     if (nf > k.n) return fail(DVM_ERR_INVALID, w + ": more FeatureVector features than keypoints");

@@ -20,14 +20,14 @@
 namespace dvm {
 
 // What the row of KF1 feature position k asks of neighbour N: idx1 = the keypoint, [fb, fe) = the positions of k's vocabulary node in N's
-// FeatureVector (node ids ascend as signed).  false: nothing to search -- k past the list, a keypoint with a MapPoint at entry (never
+// FeatureVector (node ids ascend as unsigned, node -1 last).  false: nothing to search -- k past the list, a keypoint with a MapPoint at entry (never
 // asked), or a node the neighbour lacks.
 __device__ __forceinline__ bool np_node_range(const NpArgs& A, const NpNbDev& N, int k, int& idx1, int& fb, int& fe) {
   const NpKfDev& C = A.cur;
   if (k >= A.nfeat1) return false;
   idx1 = C.fv_feat[k];
   if (C.mp[idx1] >= 0) return false;
-  const int at = fv_find<int32_t>(N.kf.fv_node, N.kf.fv_n, C.fv_node[fv_node_of(C.fv_off, C.fv_n, k)]);
+  const int at = fv_find(N.kf.fv_node, N.kf.fv_n, C.fv_node[fv_node_of(C.fv_off, C.fv_n, k)]);
   if (at < 0) return false;
   fb = N.kf.fv_off[at]; fe = N.kf.fv_off[at + 1];
   return true;

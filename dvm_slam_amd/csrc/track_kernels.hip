@@ -712,7 +712,7 @@ __global__ void __launch_bounds__(256) k_refkf_search(RefKfArgs A, const dvm_key
   const int a = wg * 4 + (threadIdx.x >> 6);
   if (a >= kfv_n) return;
   const int N = min(*d_n, cap), n_fv = A.cnt[1];
-  const int at = fv_find<uint32_t>(A.fv_node, n_fv, A.kfv_node[a]);     // the frame's nodes ascend as unsigned
+  const int at = fv_find(A.fv_node, n_fv, A.kfv_node[a]);     // the frame's nodes ascend as unsigned
   if (at < 0) return;                     // the frame does not have the node
   const int fb = A.fv_off[at], fe = A.fv_off[at + 1];
   for (int k = A.kfv_off[a]; k < A.kfv_off[a + 1]; k++) {

@@ -394,7 +394,9 @@ int ORBmatcher::SearchByProjection(FrameView& F, const TrackedPointPOD* MPs, int
 namespace {
 static_assert(ORBmatcher::HISTO_LENGTH == dvm::kRotHisto, "one histogram length");
 int RotBin(float a1, float a2) { return dvm::rot_bin(a1, a2); }   // (csrc/rot_bin.h: the device chains evaluate the same expression)
-int LowerBound(const FeatureVectorView& fv, int from, int key) { return (int)(std::lower_bound(fv.node + from, fv.node + fv.n, key) - fv.node); }
+// DBoW2's NodeId is unsigned: a FeatureVector's nodes ascend as uint32_t, node -1 is last (include/dvmslam_host.h)
+bool NodeLess(int32_t a, int32_t b) { return (uint32_t)a < (uint32_t)b; }
+int LowerBound(const FeatureVectorView& fv, int from, int32_t key) { return (int)(std::lower_bound(fv.node + from, fv.node + fv.n, key, NodeLess) - fv.node); }
 
 // Walk two FeatureVectors like the while loops of :232-364 / :735-818 / :890-1031 and call f(a, b) for every common node.
 template <class Fn>
@@ -402,7 +404,7 @@ void ForEachCommonNode(const FeatureVectorView& A, const FeatureVectorView& B, F
   int a = 0, b = 0;
   while (a < A.n && b < B.n) {
     if (A.node[a] == B.node[b]) { f(a, b); a++; b++; }
-    else if (A.node[a] < B.node[b]) a = LowerBound(A, a, B.node[b]);
+    else if (NodeLess(A.node[a], B.node[b])) a = LowerBound(A, a, B.node[b]);
     else b = LowerBound(B, b, A.node[a]);
   }
 }

@@ -421,7 +421,7 @@ int dvm_match_triangulation_cam(const uint8_t* desc1, const dvm_keypoint* kps1, 
  *
  * dvm_np_keyframe: what the two separate calls read of a keyframe.  mp[i] = map point id of keypoint i, -1 = none (of a neighbour: KF2
  * features with a point are no candidates).  fv_*: the flattened DBoW2::FeatureVector (dvmh_feature_vector_view): node ids strictly
- * ascending, features of node k = fv_feat[fv_off[k] .. fv_off[k+1]), fv_off[0] = 0, at most n features in all.  A neighbour also carries
+ * ascending -- FeatureVector nodes ascend as unsigned; -1 is last (dvmslam_host.h) --, features of node k = fv_feat[fv_off[k] .. fv_off[k+1]), fv_off[0] = 0, at most n features in all.  A neighbour also carries
  * median_depth = ComputeSceneMedianDepth(2) (the map points live with the caller) and the pair geometry ep / F12 as
  * dvmh_triangulation_geometry(cur, neighbour) computes it (index-free host arithmetic; dvmh_create_new_map_points fills it in).
  * PRECONDITION: the neighbours are distinct keyframes (GetBestCovisibilityKeyFrames returns each once; a data-only check cannot see it).
@@ -649,7 +649,9 @@ int dvm_distinctive_descriptors(const uint8_t* desc, const int32_t* off, int n_p
  * children[child_off[i] .. child_off[i+1]) in m_nodes[i].children order (empty = leaf); desc 32 B per node; weight and
  * word_id as in m_nodes[i] (word_id < 0 for inner nodes); L = m_L.  dvm_vocab_transform fills, for feature f,
  * word_id / weight of the leaf reached and node_id = the node on the path at level L - levelsup (0 if that level is
- * <= 0; -1 where the reference leaves *nid unset because the leaf lies above that level).  The BowVector /
+ * <= 0; -1 where the reference leaves *nid unset because the leaf lies above that level).  dvm_vocab_create refuses
+ * (DVM_ERR_INVALID) lists that are no tree the walk leaves: a child id not above its parent's (nodes are numbered in
+ * creation order, as DBoW2 and loadFromTextFile do), a node under two parents or under none.  The BowVector /
  * FeatureVector bookkeeping on top of it is host code (dvm_slam_amd/host/orb_vocabulary.cpp). */
 typedef struct dvm_vocab dvm_vocab;
 int dvm_vocab_create(int device, int n_nodes, const int32_t* child_off, const int32_t* children, const uint8_t* desc,

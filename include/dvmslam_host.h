@@ -14,7 +14,9 @@
 extern "C" {
 #endif
 
-/* DBoW2::FeatureVector flattened: node ids ascending, the features of node k are feat[off[k] .. off[k+1]) */
+/* DBoW2::FeatureVector flattened: the features of node k are feat[off[k] .. off[k+1]).  FeatureVector nodes ascend as unsigned; -1 is last
+ * (DBoW2's NodeId is unsigned int, std::map order: node -1 -- a transform whose walk ended above level L - levelsup -- is 4294967295).
+ * Every walk of this library and the device chains (dvm_np_keyframe, dvm_ref_keyframe, the BoW targets) compares node ids that way. */
 typedef struct dvmh_feature_vector_view { int32_t n; const int32_t* node; const int32_t* off; const int32_t* feat; } dvmh_feature_vector_view;
 /* the members of ORB_SLAM3::Frame the matcher touches (monocular; include/Frame.h:221-251) */
 typedef struct dvmh_frame_view {

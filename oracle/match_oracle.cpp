@@ -430,8 +430,10 @@ int rot_bin(float a1, float a2) {
   if (bin == kHisto) bin = 0;
   return bin;
 }
-// std::map::lower_bound over the CSR node list
-int fv_lower_bound(const int32_t* nodes, int n, int from, int key) { return (int)(std::lower_bound(nodes + from, nodes + n, key) - nodes); }
+// std::map<NodeId, ...>::lower_bound over the CSR node list.  NodeId is unsigned: the list ascends as uint32_t, node -1 (a walk
+// that ended above level L - levelsup) is 4294967295 and comes last
+bool fv_less(int32_t a, int32_t b) { return (uint32_t)a < (uint32_t)b; }
+int fv_lower_bound(const int32_t* nodes, int n, int from, int32_t key) { return (int)(std::lower_bound(nodes + from, nodes + n, key, fv_less) - nodes); }
 }  // namespace
 
 int orc_search_for_initialization(int N1, const orc_keypoint* kps1, const uint8_t* desc1, int N2, const orc_keypoint* kps2,
@@ -513,7 +515,7 @@ int orc_search_by_bow_kf_frame(const orc_keypoint* kps_kf, const uint8_t* desc_k
         }
       }
       a++; b++;
-    } else if (fv_nodes_kf[a] < fv_nodes_f[b]) {
+    } else if (fv_less(fv_nodes_kf[a], fv_nodes_f[b])) {
       a = fv_lower_bound(fv_nodes_kf, nn_kf, a, fv_nodes_f[b]);
     } else {
       b = fv_lower_bound(fv_nodes_f, nn_f, b, fv_nodes_kf[a]);
@@ -564,7 +566,7 @@ int orc_search_by_bow_kf_kf(int N1, const orc_keypoint* kps1, const uint8_t* des
         }
       }
       a++; b++;
-    } else if (fv_nodes1[a] < fv_nodes2[b]) {
+    } else if (fv_less(fv_nodes1[a], fv_nodes2[b])) {
       a = fv_lower_bound(fv_nodes1, nn1, a, fv_nodes2[b]);
     } else {
       b = fv_lower_bound(fv_nodes2, nn2, b, fv_nodes1[a]);
@@ -651,7 +653,7 @@ int orc_search_for_triangulation(int N1, const orc_keypoint* kps1, const uint8_t
         }
       }
       a++; b++;
-    } else if (fv_nodes1[a] < fv_nodes2[b]) {
+    } else if (fv_less(fv_nodes1[a], fv_nodes2[b])) {
       a = fv_lower_bound(fv_nodes1, nn1, a, fv_nodes2[b]);
     } else {
       b = fv_lower_bound(fv_nodes2, nn2, b, fv_nodes1[a]);

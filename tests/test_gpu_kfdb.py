@@ -120,3 +120,32 @@ def test_keyframe_database_sequences(capi, oracle, seed):
     assert hits > 20 and reloc_hits > 5
     for s in range(len(kfs)):
         assert dbo.state(s) == dbg.state(s) and dbo.reloc_state(s) == dbg.reloc_state(s)
+
+
+@pytest.mark.parametrize("erase", [(), (1,), (0, 4), (2, 5, 7)])
+def test_bowdb_query_late_first_word_and_ragged_live_count(capi, oracle, erase):
+    """Keyframes of more than 64 words whose first word shared with the query lies in their second 64-word chunk (position 70, and 64
+    exactly), one of 200 words that shares none, and live counts 9, 8, 7 and 6: a last workgroup of 1, 4, 3 and 2 keyframes."""
+    rng = np.random.default_rng(17)
+
+    def bow(ids):
+        ids = np.unique(np.asarray(ids)).astype(np.int32)
+        vals = rng.random(len(ids)); vals /= vals.sum()
+        return dict(ids=ids, vals=vals)
+    q = bow(rng.choice(np.arange(1000, 5000), 300, replace=False))
+    low = lambda n: rng.choice(1000, n, replace=False)                  # words below every query word
+    kfs = [bow(np.concatenate([low(70), rng.choice(q["ids"], 80, replace=False)])),
+           bow(np.concatenate([low(64), rng.choice(q["ids"], 3, replace=False)])),
+           bow(np.concatenate([low(100), 5000 + low(100)]))]
+    kfs += [bow(rng.choice(6000, int(n), replace=False)) for n in (5, 63, 64, 65, 129, 400)]
+    assert int(np.searchsorted(kfs[0]["ids"], q["ids"][0])) >= 64 and np.flatnonzero(np.isin(kfs[0]["ids"], q["ids"]))[0] == 70
+    assert np.flatnonzero(np.isin(kfs[1]["ids"], q["ids"]))[0] == 64 and not np.isin(kfs[2]["ids"], q["ids"]).any()
+    common, first, score = capi.bowdb_query_raw([(k["ids"], k["vals"]) for k in kfs], q["ids"], q["vals"], erase=erase)
+    for j, k in enumerate(kfs):
+        if j in erase:
+            assert common[j] == -1
+            continue
+        inter = np.intersect1d(q["ids"], k["ids"])
+        assert common[j] == len(inter) and first[j] == (inter[0] if len(inter) else -1), j
+        assert score[j] == np.float32(oracle.bow_score(q["ids"], q["vals"], k["ids"], k["vals"])), j
+    assert common[0] == 80 or 0 in erase

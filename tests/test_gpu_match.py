@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from voc_scene import write_dbow2_text as _write_dbow2_text
+
 pytestmark = pytest.mark.gpu
 
 
@@ -281,21 +283,6 @@ def test_vocab_transform(capi, oracle, k, L):
         oracle.bow_score(a["bow_ids"], a["bow_vals"], b["bow_ids"], b["bow_vals"])
 
 
-def _write_dbow2_text(voc, path, k):
-    """The vocabulary in DBoW2's text form (saveToTextFile, TemplatedVocabulary.h:1290-1315): "k L scoring weighting", then one line per
-    node in id order: parent, isLeaf, 32 descriptor bytes, weight.  synth.vocabulary numbers its nodes breadth-first, children after
-    parents, as a file read by loadFromTextFile does."""
-    parent = np.zeros(voc["n_nodes"], np.int64)
-    for n in range(voc["n_nodes"]):
-        parent[voc["children"][voc["child_off"][n]:voc["child_off"][n + 1]]] = n
-    with open(path, "w") as f:
-        f.write(f"{k} {voc['L']}  0 0\n")
-        for n in range(1, voc["n_nodes"]):
-            leaf = int(voc["word_id"][n] >= 0)
-            f.write(f"{parent[n]} {leaf} " + " ".join(str(int(b)) for b in voc["desc"][n]) + f" {float(voc['weight'][n])!r}\n")
-        f.write("\n")                                  # ORBvoc.txt ends in a newline; the loader must not turn it into a node
-
-
 def test_vocabulary_from_text_file(capi, oracle, tmp_path):
     """ORBVocabulary::loadFromTextFile: the tree read from DBoW2's text format gives the transform of the tree built from the arrays
     (word ids in leaf order, children in node order), a damaged file is refused."""
@@ -346,3 +333,25 @@ def test_frame_grid_reports_truncated_device_counts(capi):
         g.overflows()
     assert "truncated" in str(e.value)
     g.close()
+
+
+def test_distinctive_descriptors_at_the_kernel_limits(capi, oracle):
+    """Observation counts at the chunk of 64 lanes and at the 512 descriptors the kernel stages: 128, 129, 511 and 512 equal the oracle,
+    513 reports -2; 512 identical descriptors give median 0 at index 0."""
+    rng = np.random.default_rng(34)
+    sizes = [128, 129, 511, 512, 513, 512]
+    descs, off = [], [0]
+    for s, n in enumerate(sizes):
+        base = rng.integers(0, 256, (n // 5 + 1, 32), dtype=np.uint8)
+        d = base[rng.integers(0, len(base), n)]
+        d = np.where(rng.random((n, 32)) < 0.04, rng.integers(0, 256, (n, 32), dtype=np.uint8), d).astype(np.uint8)
+        if s == 5:
+            d = np.repeat(base[:1], n, axis=0)
+        descs.append(d); off.append(off[-1] + n)
+    desc = np.concatenate(descs)
+    bi_g, bm_g = capi.distinctive_descriptors(desc, off)
+    bi_o, bm_o = oracle.distinctive_descriptors(desc, off)
+    keep = np.array(sizes) <= 512
+    assert np.array_equal(bi_g[keep], bi_o[keep]) and np.array_equal(bm_g[keep], bm_o[keep])
+    assert (bi_g[4], bm_g[4]) == (-2, -2) and (bi_g[5], bm_g[5]) == (0, 0)
+    assert len(set(bi_g[:4].tolist())) > 1 and np.all(bm_g[:4] > 0)

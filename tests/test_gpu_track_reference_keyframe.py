@@ -81,13 +81,13 @@ def world(scene):
     return dict(scale=scale, inv_s2=inv_s2, pts=pts, voc=voc, kps=k0, desc=d0, mp=mp)
 
 
-def _kf(capi, w, voc, mp=None, pts=None, desc=None):
+def _kf(capi, w, voc, mp=None, pts=None, desc=None, levelsup=LEVELSUP):
     """dvm_ref_keyframe as a dict: map-point fields looked up in the table by id, mFeatVec from the host transform of its descriptors."""
     pts = w["pts"] if pts is None else pts
     mp = w["mp"] if mp is None else mp
     desc = w["desc"] if desc is None else desc
     ix = np.maximum(mp - MP_BASE, 0)
-    fv = capi.vocab_transform_host(voc, desc, LEVELSUP)
+    fv = capi.vocab_transform_host(voc, desc, levelsup)
     return dict(kps=w["kps"], desc=desc, mp=np.ascontiguousarray(mp, np.int32), pos=pts["pos"][ix], n_obs=pts["n_obs"][ix].astype(np.int32),
                 bad=pts["bad"][ix].astype(np.uint8), fv=fv)
 
@@ -128,9 +128,9 @@ def _pose_and_drop(opt, kf, kps_un, m, pose_last, inv_s2, gpu):
                 nmatches_map=nmap, nmatches_after=len(sel) - int((outl != 0).sum()), n_keep=len(keep))
 
 
-def _check_against_separate(capi, po, r, kf, voc, desc, kps_un, pose_last, inv_s2, oracle=True, check_ori=True):
+def _check_against_separate(capi, po, r, kf, voc, desc, kps_un, pose_last, inv_s2, oracle=True, check_ori=True, levelsup=LEVELSUP):
     """r: the chain's result.  Bit for bit against the library's calls; against the oracle: assignments and flags, pose within 1e-6."""
-    host = capi.vocab_transform_host(voc, desc, LEVELSUP)
+    host = capi.vocab_transform_host(voc, desc, levelsup)
     assert np.array_equal(r["bow_ids"], host["bow_ids"]) and np.array_equal(r["bow_vals"], host["bow_vals"])
     for k in ("fv_nodes", "fv_off", "fv_feat"):
         assert np.array_equal(r[k], host[k]), k
@@ -151,7 +151,7 @@ def _check_against_separate(capi, po, r, kf, voc, desc, kps_un, pose_last, inv_s
     assert r["status"] == (capi.DVM_TRACK_COMPLETE if sep["nmatches_map"] >= 10 else capi.DVM_TRACK_FEW_MAP_MATCHES)
     assert np.array_equal(r["Tcw"], np.concatenate([r["pose"][3:7], r["pose"][0:3]]).astype(np.float32))
     if oracle:
-        ov = po.vocab_transform(voc, desc, LEVELSUP)
+        ov = po.vocab_transform(voc, desc, levelsup)
         assert np.array_equal(ov["bow_ids"], host["bow_ids"]) and np.array_equal(ov["fv_feat"], host["fv_feat"])
         n_o, m_o = po.search_by_bow_kf_frame(kf["kps"], kf["desc"], kf["mp"], kf["bad"], kf["fv"], kps_un, desc, ov, 0.7, check_ori)
         assert n_o == r["nmatches"] and np.array_equal(m_o, pre)
@@ -215,6 +215,44 @@ def test_small_ragged_vocabulary_with_stopped_words(scene, world):
     assert len(r["fv_feat"]) < r["n"]                           # the stopped words' features are left out
     _check_against_separate(capi, po, r, kf, voc, r["desc"], r["kps_un"], pose_last, w["inv_s2"])
     assert r["nmatches"] >= 15
+    trk.close(); ext.close(); vocd.close()
+
+
+def early_leaf_vocabulary(w):
+    """A (10, 4) tree shaped like DBoW2's (voc_scene.dbow2_tree: leaves at levels 1..4, 1..10 children, equal siblings) whose node
+    descriptors are the scene's own, and the levelsup under which the frame's and the keyframe's FeatureVector both end in node -1."""
+    import voc_scene as vs
+    voc = vs.dbow2_tree(10, 4, **vs.TREES[(10, 4)])
+    rng = np.random.default_rng(7)
+    pool = np.concatenate([w["desc"], w["pts"]["desc"]])
+    voc["desc"] = pool[rng.integers(0, len(pool), voc["n_nodes"])]
+    return voc, 1
+
+
+def matches_in_node_minus_one(r):
+    """The final matches of a chain result whose frame feature lies in node -1 of the frame's FeatureVector."""
+    import voc_scene as vs
+    node = vs.node_of_feature(r, len(r["mp"]))
+    return int(((r["mp"] >= 0) & (node == 0xFFFFFFFF)).sum())
+
+
+@pytest.mark.parametrize("t", [1, 2])
+def test_feature_vectors_that_end_in_node_minus_one(scene, world, t):
+    """Leaves above level L - levelsup: ComputeBoW puts their features into node -1, the last node of mFeatVec as DBoW2 orders it, in
+    the frame and in the keyframe, and SearchByBoW matches inside it -- chain, separate calls and oracle alike."""
+    from dvm_slam_amd import capi
+    from oracle import pyoracle as po
+    frames, poses = scene
+    w = world
+    voc, levelsup = early_leaf_vocabulary(w)
+    vocd = capi.Vocabulary(voc)
+    ext, trk = _new(capi)
+    kf = _kf(capi, w, voc, levelsup=levelsup)
+    pose_last = _tcw7f(ps.pose7(*poses[t - 1]))
+    r = _form_a(trk, vocd, kf, pose_last, frames[t], w, levelsup=levelsup)
+    assert kf["fv"]["fv_nodes"][-1] == -1 and r["fv_nodes"][-1] == -1 and np.all(r["fv_nodes"][:-1] >= 0)
+    _check_against_separate(capi, po, r, kf, voc, r["desc"], r["kps_un"], pose_last, w["inv_s2"], levelsup=levelsup)
+    assert r["status"] == capi.DVM_TRACK_COMPLETE and matches_in_node_minus_one(r) >= 5
     trk.close(); ext.close(); vocd.close()
 
 

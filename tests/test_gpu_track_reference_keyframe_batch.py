@@ -78,14 +78,14 @@ def world(scene):
     return dict(scale=scale, inv_s2=inv_s2, pts=pts, mps=mps, voc=voc, kfs=kfs)
 
 
-def _kf(capi, w, voc, which=0, mp=None, pts=None, desc=None):
+def _kf(capi, w, voc, which=0, mp=None, pts=None, desc=None, levelsup=LEVELSUP):
     """dvm_ref_keyframe as a dict: map-point fields looked up in the table by id, mFeatVec from the host transform of its descriptors."""
     src = w["kfs"][which]
     pts = w["pts"] if pts is None else pts
     mp = src["mp"] if mp is None else mp
     desc = src["desc"] if desc is None else desc
     ix = np.maximum(mp, 0)
-    fv = capi.vocab_transform_host(voc, desc, LEVELSUP)
+    fv = capi.vocab_transform_host(voc, desc, levelsup)
     return dict(kps=src["kps"], desc=desc, mp=np.ascontiguousarray(mp, np.int32), pos=pts["pos"][ix], n_obs=pts["n_obs"][ix].astype(np.int32),
                 bad=pts["bad"][ix].astype(np.uint8), fv=fv)
 
@@ -231,6 +231,32 @@ def test_mixed_tick_then_second_half(scene, world):
                                      "outlier", "pose", "Tcw"))
         assert lb[b]["nmatches"] > 0
     S.close(); tb.close(); ext.close(); vocd.close()
+
+
+def test_feature_vectors_that_end_in_node_minus_one(scene, world):
+    """Three frames on a tree with leaves above level L - levelsup (tests/test_gpu_track_reference_keyframe.early_leaf_vocabulary): the
+    batched transform walks rows of unequal depth, every frame's and keyframe's FeatureVector ends in node -1, and each frame equals the
+    separate calls bit for bit and the oracle, with matches inside node -1."""
+    import test_gpu_track_reference_keyframe as one
+    from dvm_slam_amd import capi
+    from oracle import pyoracle as po
+    frames, poses = scene
+    w = world
+    voc, levelsup = one.early_leaf_vocabulary(dict(desc=w["kfs"][0]["desc"], pts=w["pts"]))
+    vocd = capi.Vocabulary(voc)
+    ts, which = [1, 2, 3], [0, 0, 1]
+    kfs = [_kf(capi, w, voc, which=k, levelsup=levelsup) for k in which]
+    pose_last = [_tcw7f(ps.pose7(*poses[t - 1])) for t in ts]
+    ext, tb = _new_batch(capi, 3)
+    first = _first_batch(tb, w, frames, poses, ts, ["none"] * 3)
+    firsts = [dict(kps_un=f["kps_un"].copy(), desc=f["desc"].copy()) for f in first]
+    rb = tb.track_reference_keyframe(vocd, kfs, pose_last, ps.K, w["inv_s2"], levelsup=levelsup)
+    for b in range(3):
+        r, kf = rb[b], kfs[b]
+        assert kf["fv"]["fv_nodes"][-1] == -1 and r["fv_nodes"][-1] == -1 and np.all(r["fv_nodes"][:-1] >= 0)
+        one._check_against_separate(capi, po, r, kf, voc, firsts[b]["desc"], firsts[b]["kps_un"], pose_last[b], w["inv_s2"], levelsup=levelsup)
+        assert r["status"] == capi.DVM_TRACK_COMPLETE and one.matches_in_node_minus_one(r) >= 5
+    tb.close(); ext.close(); vocd.close()
 
 
 @pytest.mark.parametrize("distorted", [False, True])
