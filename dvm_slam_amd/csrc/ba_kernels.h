@@ -1,22 +1,23 @@
-// dvm_slam_amd/csrc/ba_kernels.h -- device view + launchers of the FP64 bundle-adjustment kernels.
+// dvm_slam_amd/csrc/ba_kernels.h -- device views + launchers of the FP64 optimisers: the bundle adjustment's front end (BaView: edges,
+// accumulation, Schur complement, back substitution; ba_kernels.hip), the pose graph (PgView; pg_kernels.hip), PoseOptimization and Sim3.
+// The reduced system both write, and its solve, are tile_system.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "tile_system.h"
+
 namespace dvm {
 
-constexpr int kSchurLmLandmarks = 32, kSchurLmRows = 256, kSchurLmPairs = 1536, kSchurLmRuns = 512;   // a chunk of k_schur_lm: W rows 37 KB + Dinv + its index lists = 50 KB of LDS, three workgroups per CU (750 workgroups for the 500-keyframe problem: one round)
 constexpr int kEdgeLinStride = 16;  // doubles per edge and array (one 128-byte line each): e_lin = B[12] w wr0 wr1 + pad (what the camera
                                     // accumulation reads), e_linA = A[6] w wr0 wr1 + pad (what the landmark accumulation reads).  As ONE 192-byte row both
                                     // gathers dragged 2-3 lines per edge through the memory system: ~100 MB for 30 MB of operands
-// first row of camera i (elimination order) in the tiled reduced system: 10 whole cameras per 64-row tile
-__host__ __device__ inline int ba_row(int i) { return (i / 10) * 64 + (i % 10) * 6; }
 
 // Structure-of-arrays problem state in HBM (DESIGN.md "BA layout").  Poses are (t, q_xyzw) doubles.
 struct BaView {
-  int32_t P, L, E, nfree, nblk, ldS;
+  int32_t P, L, E, nfree, nblk;
   double fx, fy, cx, cy, delta;
   double* poses;            // [P][7]
   double* points;           // [L][3]
@@ -44,41 +45,10 @@ struct BaView {
   const int32_t *pair_k1, *pair_k2;            // per block: (edge of i1, edge of i2) sharing a landmark
   const int32_t* pair_pt;    // [npairs] landmark of the pair (= e_point[pair_k1]): spares the gather kernel a dependent load
   int32_t schur_wide;        // 1: few blocks with long pair lists (a local-BA window) -- k_schur with 8 waves per block instead of 2
-  // Landmark-chunk form of the Schur complement (k_schur_lm + k_schur_reduce; an experiment, built and used only under DVM_BA_SCHUR_LM=1):
-  // the landmarks, sorted by their first camera, in chunks of <= kSchurLmLandmarks landmarks / <= kSchurLmRows free-camera rows.
-  int32_t n_slc, n_slrun;    // chunks; runs (= partial 6x6 blocks) over all chunks
-  const int32_t* sl_desc;    // [n_slc][8]: row offset, rows, landmark offset, landmarks, pair offset, pairs, run offset, runs
-  const int32_t* sl_row_edge;   // per chunk row: the (local) edge whose W row it is
-  const int32_t* sl_row_lm;     // per chunk row: its landmark's slot in the chunk
-  const int32_t* sl_lm;         // per chunk landmark slot: the landmark
-  const int32_t* sl_pairs;      // per chunk, sorted by block: row1 | row2 << 9 | landmark slot << 18
-  const int32_t* sl_runs;       // per run: block, first pair (index inside the chunk); one sentinel per chunk
-  double* sl_part;              // [n_slrun][36] partial blocks, summed per block in chunk order by k_schur_reduce
-  const int32_t *bp_start, *bp_slots;   // per block: its runs (global run indices), ascending chunk
-  double* S;                // [ldS][ldS] dense lower triangle + augmented rhs row
-  double* Linv;             // [ldS/64][64*64] inverses of the factored diagonal blocks
-  double* ytmp;             // [n_pad + 64] doubles, used as int32 words: [0] ticket, [1 + k] hand-off flag of tile column k
-                            // of the one-launch back substitution; must be zeroed once after allocation
-  double* x;                // [6*nfree + 3*L]
   double *partial, *partial2;
-  // Reduced camera system in TILE space (ba_ordering.h): camera i (elimination order) owns rows
-  // ba_row(i) = (i / 10) * 64 + (i % 10) * 6; rows 60..63 of a tile are identity padding; n_pad = 64 * camera tiles;
-  // row n_pad carries bschur^T (augmented rhs), so ldS = n_pad + 64.
-  int32_t n_pad;
-  int32_t per_tile, dof;    // unknown blocks per 64-row tile and their size: (10, 6) cameras, (9, 7) Sim3 vertices
-  double* xrow;             // [n_pad] solution in row space (back substitution reads its ancestors here)
-  // level schedule of the tile Cholesky (columns of one elimination-tree height are independent):
-  const int32_t* cols;      // columns by level                                  (host offsets h_level_off)
-  const int32_t* strips;    // (row tile, column) pairs by level                 (h_strip_off)
-  const int32_t* targets;   // (ti, tj, c0, c1) trailing tiles by level          (h_tgt_off)
-  const int32_t* contrib;   // contributing columns of each target, ascending
-  const int32_t* contrib_strip;  // per contribution: indices (into strips) of the two strips it multiplies
-  int32_t* strip_flags;     // [4 * strips]: hand-off flag of every 16-row slice of a strip (k_chol_trsm_update); zeroed once after
-                            // allocation, compared with the solve's sequence number like the back substitution's flags
-  const int32_t* nz_tiles;  // (i, j) pairs of the structurally non-zero tiles (n_nz of them): cleared before every trial
-  int32_t n_nz;
-  const int32_t* colstrip_off;  // [ntiles+1] device
-  const int32_t* colstrips;     // per column: its strip rows
+  // The reduced camera system in TILE space (ba_ordering.h) and everything its solve needs: camera i (elimination order) owns rows
+  // ba_row(i); T.nfree = nfree.  The kernels here write T.S (k_schur, k_clear_tiles) and read T.x (k_point_backsub).
+  TileSystem T;
   // KEPT LANDMARKS ("border", round 5).  A map whose reduced camera system is ruined by a handful of landmarks -- a few dozen points seen from
   // places far apart on the trajectory couple camera tiles that nothing else couples: 0.2 % of the landmarks turn the 7-level elimination
   // tree of a 500-keyframe loop into a 37-level chain -- keeps those landmarks OUT of the Schur complement: they stay unknowns of the
@@ -86,28 +56,9 @@ struct BaView {
   //     [ S_E  W_K ] [xp  ]   [bp - sum_E W Dinv bl]        S_E: Schur complement over the ELIMINATED landmarks only,
   //     [ W_K' H_K ] [xl_K] = [bl_K                ]        H_K = Hll + lambda I of the kept ones, W_K their Hpl blocks
   // -- the same linear system as g2o's (block_solver.hpp:381-486 eliminates every landmark), another elimination order.  kept_slot[l] =
-  // position of landmark l among the kept ones or -1; kept_list the inverse; ncamt = camera tiles (the kept tiles follow).
-  const int32_t* kept_slot;     // [L] or null (nkept = 0)
-  const int32_t* kept_list;     // [nkept]
-  int32_t nkept, ncamt;
-  // FLOW form of the solve (k_chol_flow, ba_ordering.h): tile tasks taken through a ticket, factorisation + back substitution in ONE launch
-  const int32_t* flow_tasks;    // [n_flow_tasks][8]
-  const int32_t* flow_contrib;  // [..][4] flattened contributor lists (ba_ordering.h)
-  const int32_t* flow_col;      // [tiles][8] chain links and diagonal-tile modes (ba_ordering.h)
-  const int32_t* colstrip_id;   // per colstrips entry: index of that strip
-  int32_t* flow_flags;          // [2 x strips] a 32-row half of X published | [tiles] L^-1 of a column | [tiles] T' of a diagonal tile (PRE) | [2 x strips] a
-                                // half of a chain strip gathered | xrow tagged | ticket; compared with the solve's sequence number, zeroed once after allocation
-  int32_t n_flow_tasks, n_strips_total, n_tiles_total;
-  int32_t flow;                 // 1: ba_launch_cholesky_solve uses k_chol_flow (set by dvm_ba_set_problem; 0 after one of its waits timed out)
-  int32_t flow_wgs;             // persistent workgroups to launch (compute units of the device)
-  const int32_t *h_level_off, *h_strip_off, *h_tgt_off;  // HOST arrays [nlevels+1]
-  int32_t nlevels;
-  int32_t pair_a, pair_b;   // tile columns of the top pair (ba_ordering.h: BaTileSchedule::pair_a / pair_b) and pair_ok = 1, or pair_ok = 0
-  int32_t pair_ok;
-  int32_t diag_in_level;    // levels of <= 256 slice workgroups factor their diagonal tiles inside k_chol_trsm_update<true> (0: DVM_BA_NO_DIAG_IN_LEVEL)
-  int32_t n_root_raw;       // columns of the last launched level whose only strip is the rhs row: their panel solve (one 64x64
-                            // matrix-vector product each) is done by the back substitution itself, no k_chol_trsm launch (0: launch it)
-  const double* lambda;     // device scalar with the current LM damping (pose graph), or null: use lambda_v
+  // position of landmark l among the kept ones or -1; T.kept_list the inverse; T.ncamt = camera tiles (the kept tiles follow).
+  const int32_t* kept_slot;     // [L] or null (T.nkept = 0): read by the Schur kernels alone
+  const double* lambda;     // device scalar with the LM damping (a speculative trial: BaPublish::spec), or null: use lambda_v
   double lambda_v;          // LM damping by value (bundle adjustment: no H2D copy per trial)
   double damp_s;            // 1 normally.  Landmark-sharded BA (dvm_ba_set_problem_sharded): every rank builds a PARTIAL reduced
                             // system that is summed over ranks, so what is not a sum over edges -- lambda on the camera
@@ -117,9 +68,8 @@ struct BaView {
   double *poses_new, *points_new;   // trial state: k_update writes exp(dx) * poses -> poses_new, points + dx -> points_new; an
                                     // accepted trial swaps the pointers on the host, a rejected one leaves (poses, points) alone
                                     // -- g2o's push() / pop() / discardTop() without copies
-  // The camera model of the problem (camera_model.h), read by k_edge_eval alone.  Behind every older member, so that none of their offsets
-  // in the kernel argument moves.  0: pinhole, fx / fy / cx / cy above; 1: KannalaBrandt8, cam_p = mvParameters (fx .. cy above hold
-  // (double)cam_p[0..3] and are not read).
+  // The camera model of the problem (camera_model.h), read by k_edge_eval alone.  0: pinhole, fx / fy / cx / cy above; 1: KannalaBrandt8,
+  // cam_p = mvParameters (fx .. cy above hold (double)cam_p[0..3] and are not read).
   int32_t cam_model;
   float cam_p[8];
 };
@@ -150,7 +100,7 @@ struct BaPublish {
 };
 
 // Sim3 pose graph (Optimizer::OptimizeEssentialGraph numerics): vertex states + EdgeSim3 list + block structure.
-// The reduced system lives in a BaView used as a plain tile system (S, schedule, x): per_tile = 9, dof = 7.
+// The reduced system is a TileSystem of its own (tile_system.h): per_tile = 9, dof = 7, one launch per phase of the solve.
 struct PgView {
   int32_t n, E, nfree, fix_scale, nblk;
   double* S;                 // [n][8] vertex estimates Siw (q_xyzw, t, s)
@@ -165,10 +115,11 @@ struct PgView {
   const int32_t *v_start, *v_contrib;         // per free vertex: incident edges, edge << 1 | side
   double* bp;                // [7 * nfree] gradient b (compact), for computeScale
   double* partial;           // per-block partial sums
+  const double* lambda;      // device scalar with the current LM damping
 };
 void pg_launch_edge_eval(hipStream_t s, const PgView& G, bool jac, double* d_scalars, int slot);
-void pg_launch_build(hipStream_t s, const PgView& G, const BaView& T);
-void pg_launch_update(hipStream_t s, const PgView& G, const BaView& T, double* d_scalars, int slot_scale);
+void pg_launch_build(hipStream_t s, const PgView& G, const TileSystem& T);
+void pg_launch_update(hipStream_t s, const PgView& G, const TileSystem& T, double* d_scalars, int slot_scale);
 
 // jac: linearise at (poses, points); !jac: chi2 only, at the trial state (poses_new, points_new)
 void ba_launch_edge_eval(hipStream_t s, const BaView& V, bool jac, const BaPublish& pub);
@@ -182,8 +133,6 @@ void ba_launch_clear_tiles(hipStream_t s, const BaView& V);
 void ba_launch_schur_speculative(hipStream_t s, const BaView& V, int* d_fail);
 void ba_launch_max_diag(hipStream_t s, const BaView& V, const BaPublish& pub);
 void ba_launch_schur(hipStream_t s, const BaView& V, int* d_fail);
-// solve_seq: a number > 0 that differs from call to call on this BaView (the back substitution's hand-off flags compare against it)
-void ba_launch_cholesky_solve(hipStream_t s, const BaView& V, int* d_fail, int solve_seq);
 // d_fail: the Cholesky failure flag of this trial -- after a failed solve x keeps the last good solution (g2o's _x), which is applied all the same
 void ba_launch_backsub_update(hipStream_t s, const BaView& V, const BaPublish& pub, const int* d_fail);
 void ba_launch_edge_depth(hipStream_t s, const BaView& V, uint8_t* d_out);

@@ -5,7 +5,7 @@
 // with g2o's generic hyper-graph replaced by flat SoA arrays in HBM.  The Levenberg-Marquardt control
 // flow (reference Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:59-165 and
 // sparse_optimizer.cpp:349-412) runs here on the host, one scalar read-back per trial step; every
-// numerical step is a HIP kernel (ba_kernels.hip).
+// numerical step is a HIP kernel (ba_kernels.hip; the reduced solve: chol_kernels.hip).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -227,8 +227,6 @@ void dvm_ba_destroy(dvm_ba* h) {
   delete h;
 }
 
-// Graph construction ("buildStructure", block_solver.hpp:143-295): vertex ordering, CSR incidence
-// lists and the block pattern of the reduced camera matrix.  Done once per problem on the host.
 // the default choice between the level launches and the flow form of the reduced solve (k_chol_flow); DVM_BA_FLOW overrides it
 // Measured: the flow form costs ~15.5 us per level of a chain (the factorisation's own 7.7 us + the parent strip and
 // its product in the same workgroup) and ~18 us per level with two children; the level launches ~17 us per level when a level is a handful of
@@ -238,6 +236,54 @@ void dvm_ba_destroy(dvm_ba* h) {
 // tasks are a few per workgroup: a task holds its workgroup while it waits, and at 1 000 keyframes with loop closures (1 848 tasks on 256
 // workgroups) the level launches are ahead again (1 401 vs 1 313 it/s).
 static bool kFlowDefault(const BaTileSchedule& SC, int workgroups) { return SC.nlevels >= 5 && (int)(SC.flow_tasks.size() / 8) <= 4 * workgroups; }
+// The tile system of a bundle adjustment (T.nfree cameras in ncamt tiles, the kept landmarks' tiles behind them) from its schedule: dimensions,
+// the schedule's arrays, the buffers of the solve (x: x_len doubles) and the form the solve takes.  The flags (ytmp, flow_flags) and x are
+// zeroed by the caller, behind its uploads.
+static int fill_tile_system(dvm_ba* h, TileSystem& T, const BaTileSchedule& SC, int ncamt, const std::vector<int32_t>& kept_list, size_t x_len) {
+  const int nkb = SC.ntiles;    // camera tiles + kept-landmark tiles + the tile of the augmented rhs row
+  T.ncamt = ncamt; T.nkept = (int)kept_list.size();
+  T.n_pad = 64 * (nkb - 1);
+  T.per_tile = kCamsPerTile; T.dof = 6;
+  T.ldS = 64 * nkb;
+  T.nlevels = SC.nlevels;
+  T.pair_ok = SC.pair_a >= 0 && std::getenv("DVM_BA_NO_PAIR") == nullptr; T.pair_a = SC.pair_a; T.pair_b = SC.pair_b;   // (DVM_BA_NO_PAIR: A/B switch)
+  T.diag_in_level = std::getenv("DVM_BA_NO_DIAG_IN_LEVEL") == nullptr;
+  T.n_root_raw = std::getenv("DVM_BA_NO_ROOT_RAW") ? 0 : SC.n_root_raw;   // (ba_ordering.h: the last launched level's panel solve left to the back substitution; the switch: A/B and tests)
+  int rc = DVM_OK;
+  auto ok = [&](int r) { if (rc == DVM_OK) rc = r; };
+  ok(h->dalloc(&T.S, (size_t)T.ldS * T.ldS)); ok(h->dalloc(&T.Linv, (size_t)(T.ldS / 64) * 64 * 64)); ok(h->dalloc(&T.ytmp, (size_t)T.n_pad + 64 + 2 * (SC.strips.size() / 2) + 2));
+  ok(h->dalloc(&T.xrow, (size_t)T.n_pad + 64));
+  ok(h->dalloc(&T.x, x_len));
+  ok(h->upload(&T.nz_tiles, SC.nz_tiles)); T.n_nz = (int)(SC.nz_tiles.size() / 2);
+  ok(h->upload(&T.cols, SC.cols)); ok(h->upload(&T.strips, SC.strips)); ok(h->upload(&T.targets, SC.targets));
+  ok(h->upload(&T.contrib, SC.contrib)); ok(h->upload(&T.colstrip_off, SC.colstrip_off)); ok(h->upload(&T.colstrips, SC.colstrips));
+  ok(h->upload(&T.contrib_strip, SC.contrib_strip));
+  if (T.nkept) ok(h->upload(&T.kept_list, kept_list));
+  // the flow form of the solve (k_chol_flow): task list, per-tile level ranges, flags (zeroed once: they are compared with the solve's sequence number)
+  ok(h->upload(&T.flow_tasks, SC.flow_tasks)); ok(h->upload(&T.flow_contrib, SC.flow_contrib)); ok(h->upload(&T.flow_col, SC.flow_col)); ok(h->upload(&T.colstrip_id, SC.colstrip_id));
+  T.n_flow_tasks = (int)(SC.flow_tasks.size() / 8); T.n_strips_total = (int)(SC.strips.size() / 2); T.n_tiles_total = nkb;
+  ok(h->dalloc(&T.flow_flags, 4 * (size_t)T.n_strips_total + 2 * (size_t)nkb + 4));
+  {
+    // which form: the level launches pay ~17 us a level when a level is a handful of tiles and ~43 us when its trailing update is large; the flow
+    // form pays one launch and a ~19 us chain per level whatever the level's size.  DVM_BA_FLOW=0 / 1 forces the choice (A/B switch).
+    const char* e = std::getenv("DVM_BA_FLOW");
+    int cus = 256;
+    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+    T.flow_wgs = cus;
+    const bool fits = (size_t)T.ldS * T.ldS * sizeof(double) < (size_t)0x7FFFFFF0;      // 32-bit buffer offsets into S
+    // (the chains -- one per leaf of the elimination tree -- wait for tasks the OTHER workgroups draw: they must stay a minority)
+    // several roots (a disconnected reduced camera graph): one tree's back substitution could write x before a diagonal tile of another
+    // tree fails, and g2o's linear solver leaves x untouched when the factorisation fails -- such graphs keep the level launches
+    int roots = 0;
+    for (size_t k = 0; k + 1 < SC.flow_col.size() / 8; k++) roots += SC.flow_col[8 * k] < 0;
+    T.flow = (e ? std::atoi(e) != 0 : kFlowDefault(SC, cus)) && fits && 4 * SC.flow_leaves <= cus && roots <= 1 ? 1 : 0;
+  }
+  T.strip_flags = reinterpret_cast<int32_t*>(T.ytmp + (size_t)T.n_pad + 64);   // behind the back substitution's words, cleared with them
+  T.h_level_off = SC.level_off.data(); T.h_strip_off = SC.strip_off.data(); T.h_tgt_off = SC.tgt_off.data();
+  return rc;
+}
+// Graph construction ("buildStructure", block_solver.hpp:143-295): vertex ordering, CSR incidence
+// lists and the block pattern of the reduced camera matrix.  Done once per problem on the host.
 static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed, int P, const double* points, int L,
                             const dvm_ba_edge* edges, int E, const dvm_ba_camera* cam, int rank, int world,
                             const dvm_camera_model* model = nullptr) {
@@ -286,6 +332,7 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
   for (int p = 0; p < P; p++)
     if (!fixed[p] && ps_cnt[p + 1] > 0) { nat_of[p] = (int32_t)nat_pose.size(); nat_pose.push_back(p); }
   V.nfree = (int)nat_pose.size();
+  V.T.nfree = V.nfree;
   // ---- which camera pairs share a landmark.  One table over (camera, camera) in natural free-camera indices serves the
   // ordering (its adjacency lists, already free of duplicates) and, after the ordering, the block list of the reduced matrix.
   // (A std::map of vectors keyed by the block did this before: 29 of the 50 ms this function took at 500 keyframes, next to
@@ -308,15 +355,13 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
   };
   std::vector<int32_t> e_cam(E);
   for (int k = 0; k < E; k++) e_cam[k] = nat_of[e_pose[k]];
-  // KEPT LANDMARKS (ba_kernels.h, BaView::kept_*): when the elimination tree of the tile factorisation comes out deep (>= 12 levels: a
+  // KEPT LANDMARKS (ba_kernels.h, BaView::kept_slot): when the elimination tree of the tile factorisation comes out deep (>= 12 levels: a
   // chain, not a bush) and a few landmarks are to blame -- landmarks that couple camera pairs hardly anything else couples (<= 2
   // co-observed landmarks) --, those landmarks (at most 210: ten tiles) are left out of the Schur complement and stay unknowns of the
   // reduced system; the structure is then built again without their couplings.  DVM_BA_BORDER=0 switches it off (A/B, tests).
   constexpr size_t kMaxKept = 210;                               // ten tiles of 21
   std::vector<int32_t> kept_slot(L, -1), kept_list;
-  // (the landmark-chunk form of the Schur complement, DVM_BA_SCHUR_LM, has no workgroups for the kept landmarks' rows: the two do not combine)
-  const bool try_border = world == 1 && nf > 60 && !std::getenv("DVM_BA_SCHUR_LM") &&
-                          !(std::getenv("DVM_BA_BORDER") && std::atoi(std::getenv("DVM_BA_BORDER")) == 0);
+  const bool try_border = world == 1 && nf > 60 && !(std::getenv("DVM_BA_BORDER") && std::atoi(std::getenv("DVM_BA_BORDER")) == 0);
   std::vector<int> cam_pos;
   int levels_all = 0;
   for (int pass = 0;; pass++) {
@@ -471,89 +516,8 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
   }
   V.nblk = (int)blk_i1.size();
   const int n = 6 * V.nfree;
-  // ---- landmark-chunk form of the Schur complement.  The per-block form gathers W1 | W2 | Dinv per (edge, edge) pair: 360 B for a pair,
-  // 260 MB for the 720 k pairs of the 500-keyframe problem, of which 77 MB come from HBM -- every W row is fetched once per pair it
-  // is in.  Here a workgroup takes a chunk of landmarks, loads their W rows ONCE (23 MB in all) and forms every pair product of those
-  // landmarks from LDS; what a chunk contributes to a block is one partial 6x6 block (a "run"), and a second small launch adds a
-  // block's runs in chunk order (a fixed order: no atomics).  Landmarks are sorted by their first camera, so a chunk touches the few
-  // blocks of neighbouring cameras and a block collects from few chunks.
-  std::vector<int32_t> sl_desc, sl_row_edge, sl_row_lm, sl_lm, sl_pairs, sl_runs, bp_start(V.nblk + 1, 0), bp_slots;
-  V.n_slc = V.n_slrun = 0;
-  if (std::getenv("DVM_BA_SCHUR_LM")) {        // experiment switch: 54 + 7 us against the per-block form's 53 us on the 500-keyframe problem
-    std::unordered_map<uint64_t, int32_t> blk_of;
-    blk_of.reserve((size_t)V.nblk * 2);
-    for (int b = 0; b < V.nblk; b++) blk_of[((uint64_t)blk_i1[b] << 32) | (uint32_t)blk_i2[b]] = b;
-    std::vector<std::pair<int32_t, int32_t>> lms;       // (first camera position, landmark) of every landmark with a free-camera edge here
-    for (int l = 0; l < L; l++) {
-      int first = 1 << 30;
-      for (int a = pt_start[l]; a < pt_start[l + 1]; a++) { const int fi = pidx[e_pose[pt_edges[a]]]; if (fi >= 0) first = std::min(first, fi); }
-      if (first < (1 << 30)) lms.push_back({first, l});
-    }
-    std::sort(lms.begin(), lms.end());
-    std::vector<std::pair<int32_t, int32_t>> run_of_blk;   // (block, global run index), for the per-block lists
-    size_t i = 0;
-    bool chunks_ok = true;
-    while (i < lms.size() && chunks_ok) {
-      const int32_t row_off = (int32_t)sl_row_edge.size(), lm_off = (int32_t)sl_lm.size(), pair_off = (int32_t)sl_pairs.size(), run_off = (int32_t)sl_runs.size() / 2;
-      int nrows = 0, nlm = 0, nrun_bound = 0;
-      std::vector<std::pair<int32_t, int32_t>> pr;      // (block, row1 | row2 << 9 | landmark slot << 18)
-      std::vector<int32_t> seen_blk;
-      while (i < lms.size() && nlm < kSchurLmLandmarks) {
-        const int l = lms[i].second;
-        int deg = 0;
-        for (int a = pt_start[l]; a < pt_start[l + 1]; a++) deg += pidx[e_pose[pt_edges[a]]] >= 0;
-        if (deg > kSchurLmRows || deg * (deg + 1) / 2 > std::min(kSchurLmPairs, kSchurLmRuns)) { chunks_ok = false; break; }   // a landmark seen by > 44 free cameras: the per-block form takes the problem
-        // the chunk's limits: rows and pairs (LDS), and blocks -- a landmark of degree d can open d (d + 1) / 2 new runs at most
-        if (nrows + deg > kSchurLmRows || (int)pr.size() + deg * (deg + 1) / 2 > kSchurLmPairs || nrun_bound + deg * (deg + 1) / 2 > kSchurLmRuns) { if (nlm > 0) break; }
-        const int r0 = nrows;
-        for (int a = pt_start[l]; a < pt_start[l + 1]; a++) {
-          const int k = pt_edges[a];
-          if (pidx[e_pose[k]] < 0) continue;
-          sl_row_edge.push_back(k); sl_row_lm.push_back(nlm); nrows++;
-        }
-        // block_solver.hpp:381-439: edge k1 (outer) x edge k2 (inner) of the landmark, lower blocks only
-        for (int q1 = r0; q1 < nrows; q1++)
-          for (int q2 = r0; q2 < nrows; q2++) {
-            const int i1 = pidx[e_pose[sl_row_edge[row_off + q1]]], i2 = pidx[e_pose[sl_row_edge[row_off + q2]]];
-            if (i2 > i1) continue;
-            const int32_t bid = blk_of[((uint64_t)i1 << 32) | (uint32_t)i2];
-            pr.push_back({bid, q1 | (q2 << 9) | (nlm << 18)});
-            seen_blk.push_back(bid);
-          }
-        std::sort(seen_blk.begin(), seen_blk.end());
-        seen_blk.erase(std::unique(seen_blk.begin(), seen_blk.end()), seen_blk.end());
-        nrun_bound = (int)seen_blk.size();
-        sl_lm.push_back(l); nlm++; i++;
-      }
-      std::stable_sort(pr.begin(), pr.end(), [](const std::pair<int32_t, int32_t>& x, const std::pair<int32_t, int32_t>& y) { return x.first < y.first; });
-      int nruns = 0;
-      for (size_t j = 0; j < pr.size(); j++) {
-        if (j == 0 || pr[j].first != pr[j - 1].first) {
-          run_of_blk.push_back({pr[j].first, (int32_t)sl_runs.size() / 2 - (int32_t)(sl_desc.size() / 8)});   // global run index = position minus the sentinels before it
-          sl_runs.push_back(pr[j].first); sl_runs.push_back((int32_t)j); nruns++;
-        }
-        sl_pairs.push_back(pr[j].second);
-      }
-      sl_runs.push_back(-1); sl_runs.push_back((int32_t)pr.size());      // sentinel: where the chunk's last run ends
-      const int32_t d[8] = {row_off, nrows, lm_off, nlm, pair_off, (int32_t)pr.size(), run_off, nruns};
-      sl_desc.insert(sl_desc.end(), d, d + 8);
-    }
-    if (!chunks_ok) { sl_desc.clear(); sl_row_edge.clear(); sl_row_lm.clear(); sl_lm.clear(); sl_pairs.clear(); sl_runs.clear(); run_of_blk.clear(); }
-    V.n_slc = (int)sl_desc.size() / 8;
-    V.n_slrun = (int)run_of_blk.size();
-    for (const auto& rb : run_of_blk) bp_start[rb.first + 1]++;
-    for (int b = 0; b < V.nblk; b++) bp_start[b + 1] += bp_start[b];
-    bp_slots.resize(run_of_blk.size());
-    std::vector<int32_t> fillp(bp_start.begin(), bp_start.end() - 1);
-    for (const auto& rb : run_of_blk) bp_slots[fillp[rb.first]++] = rb.second;     // run_of_blk is in chunk order: so is every block's list
-  }
-  mark("landmark chunks");
   // ---- tile space: 10 whole cameras per 64-row tile, one extra tile for the augmented rhs row
   const int ncamt = (V.nfree + kCamsPerTile - 1) / kCamsPerTile, nkeptt = ((int)kept_list.size() + 20) / 21, nkb = ncamt + nkeptt + 1;
-  V.ncamt = ncamt; V.nkept = (int)kept_list.size();
-  V.n_pad = 64 * (ncamt + nkeptt);
-  V.per_tile = kCamsPerTile; V.dof = 6;
-  V.ldS = 64 * nkb;
   // ---- symbolic tile Cholesky + level schedule.  SLAM reduced camera matrices are banded along the trajectory plus
   // a few loop-closure blocks; skipping zero tiles keeps the dense-tile solver exact while doing only the work the
   // structure requires, and the nested-dissection order makes most tile columns independent of each other.
@@ -575,10 +539,6 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
   mark("tile schedule");
   const BaTileSchedule& SC = h->sched;
   h->tile_fill = SC.fill;
-  V.nlevels = SC.nlevels;
-  V.pair_ok = SC.pair_a >= 0 && std::getenv("DVM_BA_NO_PAIR") == nullptr; V.pair_a = SC.pair_a; V.pair_b = SC.pair_b;   // (DVM_BA_NO_PAIR: A/B switch)
-  V.diag_in_level = std::getenv("DVM_BA_NO_DIAG_IN_LEVEL") == nullptr;
-  V.n_root_raw = std::getenv("DVM_BA_NO_ROOT_RAW") ? 0 : SC.n_root_raw;   // (ba_ordering.h: the last launched level's panel solve left to the back substitution; the switch: A/B and tests)
 
   int rc = DVM_OK;
   auto ok = [&](int r) { if (rc == DVM_OK) rc = r; };
@@ -594,9 +554,6 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
     ok(h->upload(&V.pt_fi, pt_fi));
   }
   ok(h->upload(&V.ps_start, ps_start)); ok(h->upload(&V.ps_edges, ps_edges));
-  ok(h->upload(&V.sl_desc, sl_desc)); ok(h->upload(&V.sl_row_edge, sl_row_edge)); ok(h->upload(&V.sl_row_lm, sl_row_lm)); ok(h->upload(&V.sl_lm, sl_lm));
-  ok(h->upload(&V.sl_pairs, sl_pairs)); ok(h->upload(&V.sl_runs, sl_runs)); ok(h->upload(&V.bp_start, bp_start)); ok(h->upload(&V.bp_slots, bp_slots));
-  ok(h->dalloc(&V.sl_part, 36 * (size_t)std::max(V.n_slrun, 1)));
   ok(h->upload(&V.blk_i1, blk_i1)); ok(h->upload(&V.blk_i2, blk_i2)); ok(h->upload(&V.blk_start, blk_start));
   ok(h->upload(&V.pair_k1, pair_k1)); ok(h->upload(&V.pair_k2, pair_k2));
   V.schur_wide = (V.nblk > 0 && V.nblk <= 512 && pair_k1.size() / (size_t)V.nblk >= 192) ? 1 : 0;   // few blocks, long pair lists: see k_schur
@@ -612,39 +569,12 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
   ok(h->dalloc(&h->alt_lin, (size_t)E * kEdgeLinStride)); ok(h->dalloc(&h->alt_linA, (size_t)E * kEdgeLinStride)); ok(h->dalloc(&h->alt_W, (size_t)E * 18));
   ok(h->dalloc(&h->alt_Hpp, 36 * (size_t)V.nfree)); ok(h->dalloc(&h->alt_bp, (size_t)n));
   ok(h->dalloc(&h->alt_Hll, 9 * (size_t)L)); ok(h->dalloc(&h->alt_bl, 3 * (size_t)L));
-  ok(h->dalloc(&V.S, (size_t)V.ldS * V.ldS)); ok(h->dalloc(&V.Linv, (size_t)(V.ldS / 64) * 64 * 64)); ok(h->dalloc(&V.ytmp, (size_t)V.n_pad + 64 + 2 * (SC.strips.size() / 2) + 2));
-  ok(h->dalloc(&V.xrow, (size_t)V.n_pad + 64));
-  ok(h->dalloc(&V.x, (size_t)n + 3 * (size_t)L));
   ok(h->dalloc(&V.partial, (size_t)(E + 255) / 256)); ok(h->dalloc(&V.partial2, (size_t)(8 * (size_t)L + 255) / 256 + (size_t)(V.nfree + 255) / 256 + (size_t)(V.nfree + 3) / 4 + 2));   // block partials of k_point_backsub / k_max_diag
   ok(h->dalloc(&h->d_depth, (size_t)E));
   ok(h->dalloc(&h->d_flags, (size_t)E));
   h->h_flags = h->stage_alloc((size_t)std::max(E, 1));      // (nullptr when pinned memory is exhausted: set_edge_flags then copies synchronously)
-  ok(h->upload(&V.nz_tiles, SC.nz_tiles)); V.n_nz = (int)(SC.nz_tiles.size() / 2);
-  ok(h->upload(&V.cols, SC.cols)); ok(h->upload(&V.strips, SC.strips)); ok(h->upload(&V.targets, SC.targets));
-  ok(h->upload(&V.contrib, SC.contrib)); ok(h->upload(&V.colstrip_off, SC.colstrip_off)); ok(h->upload(&V.colstrips, SC.colstrips));
-  ok(h->upload(&V.contrib_strip, SC.contrib_strip));
-  if (V.nkept) { ok(h->upload(&V.kept_slot, kept_slot)); ok(h->upload(&V.kept_list, kept_list)); }
-  // the flow form of the solve (k_chol_flow): task list, per-tile level ranges, flags (zeroed once: they are compared with the solve's sequence number)
-  ok(h->upload(&V.flow_tasks, SC.flow_tasks)); ok(h->upload(&V.flow_contrib, SC.flow_contrib)); ok(h->upload(&V.flow_col, SC.flow_col)); ok(h->upload(&V.colstrip_id, SC.colstrip_id));
-  V.n_flow_tasks = (int)(SC.flow_tasks.size() / 8); V.n_strips_total = (int)(SC.strips.size() / 2); V.n_tiles_total = nkb;
-  ok(h->dalloc(&V.flow_flags, 4 * (size_t)V.n_strips_total + 2 * (size_t)nkb + 4));
-  {
-    // which form: the level launches pay ~17 us a level when a level is a handful of tiles and ~43 us when its trailing update is large; the flow
-    // form pays one launch and a ~19 us chain per level whatever the level's size.  DVM_BA_FLOW=0 / 1 forces the choice (A/B switch).
-    const char* e = std::getenv("DVM_BA_FLOW");
-    int cus = 256;
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-    V.flow_wgs = cus;
-    const bool fits = (size_t)V.ldS * V.ldS * sizeof(double) < (size_t)0x7FFFFFF0;      // 32-bit buffer offsets into S
-    // (the chains -- one per leaf of the elimination tree -- wait for tasks the OTHER workgroups draw: they must stay a minority)
-    // several roots (a disconnected reduced camera graph): one tree's back substitution could write x before a diagonal tile of another
-    // tree fails, and g2o's linear solver leaves x untouched when the factorisation fails -- such graphs keep the level launches
-    int roots = 0;
-    for (size_t k = 0; k + 1 < SC.flow_col.size() / 8; k++) roots += SC.flow_col[8 * k] < 0;
-    V.flow = (e ? std::atoi(e) != 0 : kFlowDefault(SC, cus)) && fits && 4 * SC.flow_leaves <= cus && roots <= 1 ? 1 : 0;
-  }
-  V.strip_flags = reinterpret_cast<int32_t*>(V.ytmp + (size_t)V.n_pad + 64);   // behind the back substitution's words, cleared with them
-  V.h_level_off = SC.level_off.data(); V.h_strip_off = SC.strip_off.data(); V.h_tgt_off = SC.tgt_off.data();
+  ok(fill_tile_system(h, V.T, SC, ncamt, kept_list, (size_t)n + 3 * (size_t)L));
+  if (V.T.nkept) ok(h->upload(&V.kept_slot, kept_slot));
   if (std::getenv("DVM_BA_DEBUG_SCHEDULE")) {
     for (size_t l = 0; l + 1 < SC.tgt_off.size(); l++) {
       int mx = 0; long sum = 0;
@@ -669,12 +599,12 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
   ok(h->copy_in(V.poses_new, pn.data(), pn.size() * sizeof(double)));
   ok(h->copy_in(V.points_new, points, 3 * (size_t)L * sizeof(double)));
   ok(h->flush_copies());                       // every array of the problem, merged into a few copies (copy_in)
-  ok(hip_check(hipMemsetAsync(V.x, 0, ((size_t)n + 3 * (size_t)L) * sizeof(double), h->stream), "memset"));
+  ok(hip_check(hipMemsetAsync(V.T.x, 0, ((size_t)n + 3 * (size_t)L) * sizeof(double), h->stream), "memset"));
   // (S is NOT cleared as a whole: every kernel touches structurally non-zero tiles only, and a trial's prologue clears exactly
   //  those.  The matrix is ldS^2 doubles -- 1.3 GB at 2 000 keyframes.)
   ok(hip_check(hipMemsetAsync(V.e_chi2, 0, (size_t)E * sizeof(double), h->stream), "memset"));
-  ok(hip_check(hipMemsetAsync(V.ytmp, 0, ((size_t)V.n_pad + 64 + 2 * (SC.strips.size() / 2) + 2) * sizeof(double), h->stream), "memset"));   // ticket + hand-off flags of the back substitution
-  ok(hip_check(hipMemsetAsync(V.flow_flags, 0, (4 * (size_t)V.n_strips_total + 2 * (size_t)nkb + 4) * sizeof(int32_t), h->stream), "memset"));
+  ok(hip_check(hipMemsetAsync(V.T.ytmp, 0, ((size_t)V.T.n_pad + 64 + 2 * (SC.strips.size() / 2) + 2) * sizeof(double), h->stream), "memset"));   // ticket + hand-off flags of the back substitution
+  ok(hip_check(hipMemsetAsync(V.T.flow_flags, 0, (4 * (size_t)V.T.n_strips_total + 2 * (size_t)nkb + 4) * sizeof(int32_t), h->stream), "memset"));
   h->solve_seq = 0; h->fuse_levels = true;
   ok(hip_check(hipStreamSynchronize(h->stream), "sync"));
   if (rc != DVM_OK) { h->free_problem(); return rc; }
@@ -766,12 +696,12 @@ int dvm_ba_schedule_info(const dvm_ba* h, int64_t* out) {
     }
   }
   out[0] = nlaunched; out[1] = ncols; out[2] = nstrips; out[3] = ntargets; out[4] = ncontrib; out[5] = ndiag_contrib;
-  out[6] = h->V.n_nz; out[7] = h->V.ldS; out[8] = h->V.nfree; out[9] = h->V.nblk; out[10] = h->V.E; out[11] = SC.ntiles;
+  out[6] = h->V.T.n_nz; out[7] = h->V.T.ldS; out[8] = h->V.nfree; out[9] = h->V.nblk; out[10] = h->V.E; out[11] = SC.ntiles;
   return DVM_OK;
 }
 int dvm_ba_solve_info(const dvm_ba* h, int64_t* out) {
   if (!h || !h->have_problem || !out) return DVM_ERR_STATE;
-  out[0] = h->V.flow && h->fuse_levels ? 1 : 0; out[1] = h->V.n_flow_tasks; out[2] = h->sched.flow_leaves; out[3] = h->V.flow_wgs; out[4] = h->V.nkept; out[5] = h->V.ncamt;
+  out[0] = h->V.T.flow && h->fuse_levels ? 1 : 0; out[1] = h->V.T.n_flow_tasks; out[2] = h->sched.flow_leaves; out[3] = h->V.T.flow_wgs; out[4] = h->V.T.nkept; out[5] = h->V.T.ncamt;
   return DVM_OK;
 }
 int dvm_ba_profile(dvm_ba* h, int enable, double* ms4, int32_t* trials, int32_t* iters) {
@@ -789,7 +719,7 @@ int dvm_ba_profile(dvm_ba* h, int enable, double* ms4, int32_t* trials, int32_t*
 }
 int64_t dvm_ba_allreduce_doubles(const dvm_ba* h) {
   if (!h || !h->have_problem) return 0;
-  return std::max<int64_t>({(int64_t)h->V.n_nz * 4096, 3 * (int64_t)h->V.L, 6 * (int64_t)h->V.nfree, 8});
+  return std::max<int64_t>({(int64_t)h->V.T.n_nz * 4096, 3 * (int64_t)h->V.L, 6 * (int64_t)h->V.nfree, 8});
 }
 
 // Wait until the device has released sequence number `seq` into the mapped host memory (BaPublish).  Spinning on host
@@ -906,7 +836,7 @@ int dvm_ba_optimize(dvm_ba* h, int iterations, const volatile uint8_t* stop_flag
   // has filled S) the next trial starts the ordinary way, after emptying S if need be.
   const bool speculate = !sharded && h->speculate && !h->prof;   // (the profiling pass times every phase of a trial on its own)
   // g2o's buildStructure (iteration 0 of every optimize()) reallocates _x: "the last successful solve" starts empty
-  DVM_HIP(hipMemsetAsync(V.x, 0, ((size_t)6 * V.nfree + 3 * (size_t)V.L) * sizeof(double), s));
+  DVM_HIP(hipMemsetAsync(V.T.x, 0, ((size_t)6 * V.nfree + 3 * (size_t)V.L) * sizeof(double), s));
   bool schur_enqueued = false;      // the NEXT trial's k_schur is already on the stream, for (V after the swap, lambda)
   bool tiles_clear = false;         // the structurally non-zero tiles of S are empty: k_accum's launch was the last to touch S
   for (int it = 0; it < iterations && !terminate(); it++) {
@@ -992,18 +922,18 @@ int dvm_ba_optimize(dvm_ba* h, int iterations, const volatile uint8_t* stop_flag
         if (h->prof) hipEventRecord(h->pev[1], s);
         if (sharded) {   // sum the partial reduced systems (non-zero tiles incl. the rhs row): ~6 MB at 500 keyframes
           ba_launch_pack_tiles(s, V, h->ar_buf, false);
-          if ((rc = ar_dev((int64_t)V.n_nz * 4096, 0)) != DVM_OK) return rc;
+          if ((rc = ar_dev((int64_t)V.T.n_nz * 4096, 0)) != DVM_OK) return rc;
           ba_launch_pack_tiles(s, V, h->ar_buf, true);
         }
         {
-          BaView VS = V;                                   // in-launch hand-offs (k_chol_trsm_update) only while they have never timed out
+          TileSystem TS = V.T;                             // in-launch hand-offs (k_chol_trsm_update) only while they have never timed out
           // (the fused level launches assume their whole grid resident: not with several ranks on one GPU, nor after a timeout;
           //  every rank of a sharded solve solves the summed system redundantly)
-          if (sharded || !h->fuse_levels) VS.strip_flags = nullptr;
+          if (sharded || !h->fuse_levels) TS.strip_flags = nullptr;
           // (a sharded solve keeps the flow form -- every rank solves the summed system redundantly, on its own GPU; a wait that
           //  gives up on ANY rank is all-reduced below and every rank repeats the trial with the level launches)
-          if (!h->fuse_levels) VS.flow = 0;
-          ba_launch_cholesky_solve(s, VS, h->d_fail, ++h->solve_seq);
+          if (!h->fuse_levels) TS.flow = 0;
+          tile_launch_cholesky_solve(s, TS, h->d_fail, ++h->solve_seq);
         }
         if (h->prof) hipEventRecord(h->pev[2], s);
         ba_launch_backsub_update(s, V, pub(S_SCALE, 2, false, false), h->d_fail);

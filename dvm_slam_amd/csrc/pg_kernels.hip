@@ -1,7 +1,7 @@
 // dvm_slam_amd/csrc/pg_kernels.hip -- Optimizer::OptimizeEssentialGraph on the device, FP64, for gfx950 (driver: pg_solver.cpp):
 //   k_pg_edge       per-edge error log(C * Si * Sj^-1), chi2 partial, numeric 7x7 Jacobians
 //   k_reduce_sum    the partials of a pass in a fixed order
-//   k_zero_tiles, k_pg_blocks, k_pg_rhs, k_pad_identity   the 7-DoF system in the tile solver's layout (solved by ba_launch_cholesky_solve)
+//   k_zero_tiles, k_pg_blocks, k_pg_rhs, k_pad_identity   the 7-DoF system in the tile solver's layout (tile_system.h; solved by tile_launch_cholesky_solve)
 //   k_pg_update     oplus and the computeScale partial
 // g2o::Sim3 is sim3_f64.h's.  Launchers: ba_kernels.h.
 #include <hip/hip_runtime.h>
@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(256) k_reduce_sum(const double* __restrict__ p
 
 // 64 threads per non-zero 7x7 block (a >= b): H_ab = sum over its contributions J_a^T J_b (+ lambda on the diagonal),
 // fixed order, written into the tile-space matrix
-__global__ void __launch_bounds__(256) k_pg_blocks(PgView G, BaView T) {
+__global__ void __launch_bounds__(256) k_pg_blocks(PgView G, TileSystem T) {
   const int blk = blockIdx.x * 4 + (threadIdx.x >> 6), t = threadIdx.x & 63;
   if (blk >= G.nblk || t >= 49) return;
   const int r = t / 7, c = t % 7;
@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(256) k_pg_blocks(PgView G, BaView T) {
     for (int k = 0; k < 7; k++) h += Ja[7 * k + r] * Jb[7 * k + c];
     acc += h;
   }
-  if (a == b && r == c) acc += *T.lambda;
+  if (a == b && r == c) acc += *G.lambda;
   const int ra = (a / T.per_tile) * 64 + (a % T.per_tile) * T.dof, rb = (b / T.per_tile) * 64 + (b % T.per_tile) * T.dof;
   T.S[(size_t)(ra + r) * T.ldS + rb + c] = acc;
 }
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(256) k_zero_tiles(double* __restrict__ S, int 
 }
 
 // identity on the padding rows of the tiled system (rows 60..63 of every tile, cameras beyond nfree in the last tile)
-__global__ void __launch_bounds__(256) k_pad_identity(BaView V) {
+__global__ void __launch_bounds__(256) k_pad_identity(TileSystem V) {
   const int r = blockIdx.x * 256 + threadIdx.x;
   if (r >= V.n_pad) return;
   const int w = r & 63;
@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(256) k_pad_identity(BaView V) {
 }
 
 // thread per free vertex: b_v = - sum J_v^T e  -> compact copy (computeScale) and the augmented rhs row
-__global__ void __launch_bounds__(256) k_pg_rhs(PgView G, BaView T) {
+__global__ void __launch_bounds__(256) k_pg_rhs(PgView G, TileSystem T) {
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= G.nfree) return;
   double b[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -141,12 +141,12 @@ __global__ void __launch_bounds__(256) k_pg_rhs(PgView G, BaView T) {
   if (p == 0) T.S[(size_t)T.n_pad * T.ldS + T.n_pad] = 1e200;
 }
 // thread per free vertex: oplus (S <- Sim3(x) * S) and the computeScale partial sum x^T (lambda x + b)
-__global__ void __launch_bounds__(256) k_pg_update(PgView G, BaView T) {
+__global__ void __launch_bounds__(256) k_pg_update(PgView G, TileSystem T) {
   __shared__ double red[256];
   const int p = blockIdx.x * 256 + threadIdx.x;
   double sc = 0;
   if (p < G.nfree) {
-    const double lambda = *T.lambda;
+    const double lambda = *G.lambda;
     double u[7];
     for (int r = 0; r < 7; r++) { u[r] = T.x[7 * (size_t)p + r]; sc += u[r] * (lambda * u[r] + G.bp[7 * (size_t)p + r]); }
     if (G.fix_scale) u[6] = 0;
@@ -174,13 +174,13 @@ void pg_launch_edge_eval(hipStream_t s, const PgView& G, bool jac, double* d_sca
   else hipLaunchKernelGGL(k_pg_edge<false>, dim3(nb), dim3(256), 0, s, G);
   hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(256), 0, s, G.partial, nb, d_scalars, slot);
 }
-void pg_launch_build(hipStream_t s, const PgView& G, const BaView& T) {
+void pg_launch_build(hipStream_t s, const PgView& G, const TileSystem& T) {
   hipLaunchKernelGGL(k_zero_tiles, dim3(T.n_nz), dim3(256), 0, s, T.S, T.ldS, T.nz_tiles);
   hipLaunchKernelGGL(k_pg_blocks, dim3(cdiv(G.nblk, 4)), dim3(256), 0, s, G, T);
   hipLaunchKernelGGL(k_pg_rhs, dim3(cdiv(G.nfree, 256)), dim3(256), 0, s, G, T);
   hipLaunchKernelGGL(k_pad_identity, dim3(cdiv(T.n_pad, 256)), dim3(256), 0, s, T);
 }
-void pg_launch_update(hipStream_t s, const PgView& G, const BaView& T, double* d_scalars, int slot_scale) {
+void pg_launch_update(hipStream_t s, const PgView& G, const TileSystem& T, double* d_scalars, int slot_scale) {
   const int nb = cdiv(G.nfree, 256);
   hipLaunchKernelGGL(k_pg_update, dim3(nb), dim3(256), 0, s, G, T);
   hipLaunchKernelGGL(k_reduce_sum, dim3(1), dim3(256), 0, s, G.partial, nb, d_scalars, slot_scale);

@@ -4,7 +4,7 @@
 // "SE3 Pose Recovering": VertexSim3Expmap / EdgeSim3 with identity information, g2o's numeric Jacobians,
 // OptimizationAlgorithmLevenberg with setUserLambdaInit(1e-16), optimize(20).  The sparse 7x7-block system goes through
 // the same tile Cholesky as the bundle adjustment (nested-dissection order, elimination-tree level schedule; 9 Sim3
-// vertices per 64-row tile); the LM control flow runs here, every numerical step is a HIP kernel (pg_kernels.hip; the factorisation and solve are the tile solver's, ba_kernels.hip).
+// vertices per 64-row tile); the LM control flow runs here, every numerical step is a HIP kernel (pg_kernels.hip; the factorisation and solve are the tile solver's, chol_kernels.hip).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -48,7 +48,7 @@ enum { S_CHI = 0, S_TMPCHI = 1, S_SCALE = 2 };
 struct PgProblem {
   DevPool D;
   PgView G{};
-  BaView T{};
+  TileSystem T{};   // members not set by pg_setup stay zero: one launch per phase, no flow form, no top pair, no kept landmarks
   BaTileSchedule SC;
   std::vector<int32_t> vidx;   // [n] position in the elimination order, -1 = fixed
   int n = 0, nfree = 0, solve_seq = 0;
@@ -72,7 +72,7 @@ struct PgProblem {
 // contribution lists, tile schedule, device buffers, normalised estimates.  P.nfree == 0 on return: nothing was allocated.
 int pg_setup(PgProblem& P, const double* S, const uint8_t* fixed, int n, const dvm_pg_edge* edges, int E, int fix_scale) {
   PgView& G = P.G;
-  BaView& T = P.T;
+  TileSystem& T = P.T;
   DevPool& D = P.D;
   BaTileSchedule& SC = P.SC;
   P.n = n;
@@ -142,7 +142,7 @@ int pg_setup(PgProblem& P, const double* S, const uint8_t* fixed, int n, const d
   T.h_level_off = SC.level_off.data(); T.h_strip_off = SC.strip_off.data(); T.h_tgt_off = SC.tgt_off.data();
   double* d_scalars = P.d_scalars = D.alloc<double>(8);
   P.d_fail = D.alloc<int>(1);
-  T.lambda = d_scalars + 7;
+  G.lambda = d_scalars + 7;
   if (D.rc != DVM_OK) return D.rc;
   DVM_HIP(hipMemset(T.S, 0, (size_t)T.ldS * T.ldS * sizeof(double)));   // once: trials clear only the non-zero tiles
   DVM_HIP(hipMemset(T.ytmp, 0, ((size_t)T.n_pad + 64) * sizeof(double)));  // ticket + hand-off flags of the back substitution
@@ -165,14 +165,14 @@ int pg_setup(PgProblem& P, const double* S, const uint8_t* fixed, int n, const d
 // the factorisation overwrites it.
 int pg_trial(PgProblem& P, double lambda, double* h_tiles) {
   PgView& G = P.G;
-  BaView& T = P.T;
+  TileSystem& T = P.T;
   hipStream_t s = P.s;
   DVM_HIP(hipMemcpy(P.d_scalars + 7, &lambda, sizeof(double), hipMemcpyHostToDevice));
   DVM_HIP(hipMemcpyAsync(P.d_bak, G.S, 8 * (size_t)P.n * sizeof(double), hipMemcpyDeviceToDevice, s));   // push()
   DVM_HIP(hipMemsetAsync(P.d_fail, 0, sizeof(int), s));
   pg_launch_build(s, G, T);
   if (h_tiles) DVM_HIP(hipMemcpy(h_tiles, T.S, (size_t)T.ldS * T.ldS * sizeof(double), hipMemcpyDeviceToHost));
-  ba_launch_cholesky_solve(s, T, P.d_fail, ++P.solve_seq);
+  tile_launch_cholesky_solve(s, T, P.d_fail, ++P.solve_seq);
   pg_launch_update(s, G, T, P.d_scalars, S_SCALE);
   pg_launch_edge_eval(s, G, false, P.d_scalars, S_TMPCHI);
   return P.read();
@@ -267,7 +267,7 @@ extern "C" int dvm_pose_graph_debug_trial(int device, double* S, const uint8_t* 
   for (int v = 0; v < n; v++) vidx[v] = P.nfree ? P.vidx[v] : -1;
   if (P.nfree == 0) return DVM_OK;
   PgView& G = P.G;
-  BaView& T = P.T;
+  TileSystem& T = P.T;
   const int nfree = P.nfree, dim = 7 * nfree;
   pg_launch_edge_eval(P.s, G, true, P.d_scalars, S_CHI);
   { const int rc = P.read(); if (rc != DVM_OK) return rc; }

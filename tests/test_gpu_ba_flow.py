@@ -1,5 +1,5 @@
 """The flow form of the reduced solve (k_chol_flow: tile factorisation + back substitution as ONE persistent launch of tile tasks,
-csrc/ba_kernels.hip) against the level launches it replaces and against the CPU oracle.
+csrc/chol_kernels.hip) against the level launches it replaces and against the CPU oracle.
 
 The flow form gathers a tile's updates level by level in the order the level launches apply them and runs the same tile factorisation,
 panel solve and back substitution arithmetic: with the top pair kernel switched off (DVM_BA_NO_PAIR: its in-LDS solve of the last two
@@ -146,7 +146,7 @@ def test_flow_concurrent_handles_make_progress():
 @pytest.mark.parametrize("name,delta", [("loop500", DELTA), ("loop500", 0.0), ("web120", DELTA)])
 def test_kept_landmarks_same_solution_shorter_tree(oracle, name, delta):
     """A few landmarks seen from far apart make the elimination tree a chain (loop500: 40 of 20 000 landmarks, 37 levels).  Left out of
-    the Schur complement and kept as unknowns of the reduced system (BaView::kept_*), the tree is a bush again -- and the solution is the
+    the Schur complement and kept as unknowns of the reduced system (BaView::kept_slot, TileSystem::kept_list), the tree is a bush again -- and the solution is the
     same: against the run with DVM_BA_BORDER=0 and against the oracle within the accuracy contract, identical LM trial sequences."""
     pr = synth.ba_problem(**PROBLEMS[name])
     iters = 4 if len(pr["poses"]) >= 500 else 8
