@@ -1021,6 +1021,24 @@ def optimize_sim3(S12, fix_scale, P1c, P2c, obs1, obs2, w1, w2, K1, K2, th2, dev
     return S, inl, nin.value
 
 
+def optimize_sim3_cam(S12, fix_scale, P1c, P2c, obs1, obs2, w1, w2, model1, model2, th2, device=0):
+    """dvm_optimize_sim3_cam: OptimizeSim3 with a CameraModel per keyframe (any pair of pinhole / KannalaBrandt8).  On a KannalaBrandt8
+    side the residual and the chi2 tests use the reference's project(Vector3d) (float theta), the numeric Jacobian the projection with the
+    double atan2.  Returns (S12[8], inlier mask, nIn); two pinhole models give optimize_sim3's outputs bit for bit."""
+    L = lib()
+    vp, i32 = C.c_void_p, C.c_int32
+    L.dvm_optimize_sim3_cam.restype = i32
+    L.dvm_optimize_sim3_cam.argtypes = [i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, C.c_double, vp, vp]
+    S = np.array(S12, np.float64, copy=True)
+    arrs = [np.ascontiguousarray(a, np.float64) for a in (P1c, P2c, obs1, obs2, w1, w2)]
+    n = len(arrs[0])
+    inl = np.zeros(n, np.uint8)
+    nin = C.c_int32(0)
+    check(L.dvm_optimize_sim3_cam(device, _p(S), int(fix_scale), *[_p(a) for a in arrs], n, C.addressof(model1), C.addressof(model2),
+                                  float(th2), _p(inl), C.addressof(nin)))
+    return S, inl, nin.value
+
+
 # ---- host C++ mirror (dvm_slam_amd/host, libdvmslam_host.so): ORBmatcher on plain structs over the C ABI
 HOST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libdvmslam_host.so")
 MAP_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("desc", "u1", (32,)), ("n_obs", "<i4")])
@@ -1900,6 +1918,22 @@ def sim3_hypotheses(P1c, P2c, max_err1, max_err2, K1, K2, triples, fix_scale=Fal
     T = np.zeros((H, 13), np.float32); nin = np.zeros(H, np.int32); mask = np.zeros((H, N), np.uint8)
     check(L.dvm_sim3_hypotheses(device, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), N, _p(a[4]), _p(a[5]), _p(tr), H, int(fix_scale),
                                 _p(T), _p(nin), _p(mask)))
+    return T, nin, mask
+
+
+def sim3_hypotheses_cam(P1c, P2c, max_err1, max_err2, model1, model2, triples, fix_scale=False, device=0):
+    """dvm_sim3_hypotheses_cam: sim3_hypotheses with a CameraModel per keyframe (any pair of pinhole / KannalaBrandt8); T12 does not
+    depend on the models.  Returns (T12[H,13]; n_inliers[H]; mask[H,N])."""
+    L = lib()
+    vp, i32 = C.c_void_p, C.c_int32
+    L.dvm_sim3_hypotheses_cam.restype = i32
+    L.dvm_sim3_hypotheses_cam.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp]
+    a = [np.ascontiguousarray(x, np.float32) for x in (P1c, P2c, max_err1, max_err2)]
+    tr = np.ascontiguousarray(triples, np.int32).reshape(-1, 3)
+    N, H = len(a[0]), len(tr)
+    T = np.zeros((H, 13), np.float32); nin = np.zeros(H, np.int32); mask = np.zeros((H, N), np.uint8)
+    check(L.dvm_sim3_hypotheses_cam(device, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), N, C.addressof(model1), C.addressof(model2), _p(tr), H,
+                                    int(fix_scale), _p(T), _p(nin), _p(mask)))
     return T, nin, mask
 
 

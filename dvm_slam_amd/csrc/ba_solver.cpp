@@ -1152,11 +1152,16 @@ int dvm_pose_optimize_cam(int device, const double* pose_in, const double* Xw, c
                             model->model == dvm_cam::kKannalaBrandt8 ? model->p : nullptr, pose_out, outlier, n_inliers);
 }
 
-int dvm_optimize_sim3(int device, double* S12, int fix_scale, const double* P1c, const double* P2c, const double* obs1,
-                      const double* obs2, const double* w1, const double* w2, int N, const double* K1, const double* K2,
-                      double th2, uint8_t* inlier, int32_t* n_inliers) {
-  if (!S12 || !P1c || !P2c || !obs1 || !obs2 || !w1 || !w2 || !K1 || !K2 || !inlier || !n_inliers || N < 1) {
-    set_error("dvm_optimize_sim3: bad arguments");
+}  // extern "C"
+
+namespace {
+// dvm_optimize_sim3 / dvm_optimize_sim3_cam: K = fx, fy, cx, cy of both cameras; camp = the 2 x 8 model parameters when a side is
+// KannalaBrandt8 (NULL: two pinhole cameras, the kernel dvm_optimize_sim3 has always launched)
+int optimize_sim3_impl(const char* who, int device, double* S12, int fix_scale, const double* P1c, const double* P2c, const double* obs1,
+                       const double* obs2, const double* w1, const double* w2, int N, const double* K, const float* camp, int model1,
+                       int model2, double th2, uint8_t* inlier, int32_t* n_inliers) {
+  if (!S12 || !P1c || !P2c || !obs1 || !obs2 || !w1 || !w2 || !K || !inlier || !n_inliers || N < 1) {
+    set_error(std::string(who) + ": bad arguments");
     return DVM_ERR_INVALID;
   }
   int ndev = 0;
@@ -1164,47 +1169,100 @@ int dvm_optimize_sim3(int device, double* S12, int fix_scale, const double* P1c,
   if (device < 0 || device >= ndev) return DVM_ERR_INVALID;
   DVM_HIP(hipSetDevice(device));
   const size_t n = (size_t)N;
-  double K[8], S_out[8];
-  std::memcpy(K, K1, 32); std::memcpy(K + 4, K2, 32);
+  double S_out[8];
   Stage st;   // S12 is refined in place on the device: staged in, fetched into S_out, handed over only if the solve succeeded
   const int ioS = st.add(S12, S_out, 64), iK = st.in(K, 64), iP1 = st.in(P1c, 24 * n), iP2 = st.in(P2c, 24 * n), iO1 = st.in(obs1, 16 * n),
             iO2 = st.in(obs2, 16 * n), iW1 = st.in(w1, 8 * n), iW2 = st.in(w2, 8 * n), oN = st.out(n_inliers, 4), oI = st.out(inlier, n),
             sChi = st.scratch(16 * n), sFl = st.scratch(2 * n);
+  const int iC = camp ? st.in(camp, 64) : -1;
   int rc = st.upload();
   if (rc != DVM_OK) return rc;
-  ba_launch_optimize_sim3(nullptr, st.ptr<double>(ioS), fix_scale, st.ptr<double>(iP1), st.ptr<double>(iP2), st.ptr<double>(iO1), st.ptr<double>(iO2),
-                          st.ptr<double>(iW1), st.ptr<double>(iW2), N, st.ptr<double>(iK), th2, st.ptr<uint8_t>(oI), st.ptr<int32_t>(oN),
-                          st.ptr<double>(sChi), st.ptr<uint8_t>(sFl));
+  ba_launch_optimize_sim3_cam(nullptr, st.ptr<double>(ioS), fix_scale, st.ptr<double>(iP1), st.ptr<double>(iP2), st.ptr<double>(iO1),
+                              st.ptr<double>(iO2), st.ptr<double>(iW1), st.ptr<double>(iW2), N, st.ptr<double>(iK),
+                              camp ? st.ptr<float>(iC) : nullptr, model1, model2, th2, st.ptr<uint8_t>(oI), st.ptr<int32_t>(oN),
+                              st.ptr<double>(sChi), st.ptr<uint8_t>(sFl));
   rc = hip_check(hipGetLastError(), "optimize_sim3 launch");
   if (rc == DVM_OK) rc = st.download();
   if (rc == DVM_OK && *n_inliers > 0) std::memcpy(S12, S_out, 64);
   return rc;
 }
 
-int dvm_sim3_hypotheses(int device, const float* P1c, const float* P2c, const float* max_err1, const float* max_err2, int N,
-                        const float* K1, const float* K2, const int32_t* triples, int H, int fix_scale, float* T12,
-                        int32_t* n_inliers, uint8_t* inlier_mask) {
-  if (!P1c || !P2c || !max_err1 || !max_err2 || !K1 || !K2 || !triples || !T12 || !n_inliers || !inlier_mask || N < 3 || H < 1) {
-    set_error("dvm_sim3_hypotheses: bad arguments");
+int sim3_hypotheses_impl(const char* who, int device, const float* P1c, const float* P2c, const float* max_err1, const float* max_err2,
+                         int N, const float* K, const float* camp, int model1, int model2, const int32_t* triples, int H, int fix_scale,
+                         float* T12, int32_t* n_inliers, uint8_t* inlier_mask) {
+  if (!P1c || !P2c || !max_err1 || !max_err2 || !K || !triples || !T12 || !n_inliers || !inlier_mask || N < 3 || H < 1) {
+    set_error(std::string(who) + ": bad arguments");
     return DVM_ERR_INVALID;
   }
-  for (int i = 0; i < 3 * H; i++) if (triples[i] < 0 || triples[i] >= N) { set_error("dvm_sim3_hypotheses: sample index out of range"); return DVM_ERR_INVALID; }
+  for (int i = 0; i < 3 * H; i++) if (triples[i] < 0 || triples[i] >= N) { set_error(std::string(who) + ": sample index out of range"); return DVM_ERR_INVALID; }
   int ndev = 0;
   { const int rc = need_any_device(&ndev); if (rc != DVM_OK) return rc; }
   if (device < 0 || device >= ndev) return DVM_ERR_INVALID;
   DVM_HIP(hipSetDevice(device));
   const size_t n = (size_t)N, hh = (size_t)H;
-  float K[8];
-  std::memcpy(K, K1, 16); std::memcpy(K + 4, K2, 16);
   Stage st;
   const int iP1 = st.in(P1c, 12 * n), iP2 = st.in(P2c, 12 * n), iE1 = st.in(max_err1, 4 * n), iE2 = st.in(max_err2, 4 * n), iK = st.in(K, 32),
             iT = st.in(triples, 12 * hh), oT = st.out(T12, 52 * hh), oN = st.out(n_inliers, 4 * hh), oM = st.out(inlier_mask, hh * n);
+  const int iC = camp ? st.in(camp, 64) : -1;
   int rc = st.upload();
   if (rc != DVM_OK) return rc;
-  ba_launch_sim3_hypotheses(nullptr, st.ptr<float>(iP1), st.ptr<float>(iP2), st.ptr<float>(iE1), st.ptr<float>(iE2), N, st.ptr<float>(iK),
-                            st.ptr<int32_t>(iT), H, fix_scale, st.ptr<float>(oT), st.ptr<int32_t>(oN), st.ptr<uint8_t>(oM));
+  ba_launch_sim3_hypotheses_cam(nullptr, st.ptr<float>(iP1), st.ptr<float>(iP2), st.ptr<float>(iE1), st.ptr<float>(iE2), N, st.ptr<float>(iK),
+                                camp ? st.ptr<float>(iC) : nullptr, model1, model2, st.ptr<int32_t>(iT), H, fix_scale, st.ptr<float>(oT),
+                                st.ptr<int32_t>(oN), st.ptr<uint8_t>(oM));
   rc = hip_check(hipGetLastError(), "sim3_hypotheses launch");
   return rc == DVM_OK ? st.download() : rc;
+}
+
+// the two models of a *_cam Sim3 entry, checked before anything runs: K <- fx, fy, cx, cy of both, camp <- the 2 x 8 parameters
+template <class T>
+bool sim3_models(const dvm_camera_model* m1, const dvm_camera_model* m2, T* K, float* camp) {
+  if (!m1 || !m2 || !dvm_cam::model_ok(m1->model, m1->p) || !dvm_cam::model_ok(m2->model, m2->p)) return false;
+  for (int i = 0; i < 4; i++) { K[i] = (T)m1->p[i]; K[4 + i] = (T)m2->p[i]; }
+  std::memcpy(camp, m1->p, 32); std::memcpy(camp + 8, m2->p, 32);
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int dvm_optimize_sim3(int device, double* S12, int fix_scale, const double* P1c, const double* P2c, const double* obs1,
+                      const double* obs2, const double* w1, const double* w2, int N, const double* K1, const double* K2,
+                      double th2, uint8_t* inlier, int32_t* n_inliers) {
+  if (!K1 || !K2) { set_error("dvm_optimize_sim3: bad arguments"); return DVM_ERR_INVALID; }
+  double K[8];
+  std::memcpy(K, K1, 32); std::memcpy(K + 4, K2, 32);
+  return optimize_sim3_impl("dvm_optimize_sim3", device, S12, fix_scale, P1c, P2c, obs1, obs2, w1, w2, N, K, nullptr, 0, 0, th2, inlier, n_inliers);
+}
+
+int dvm_optimize_sim3_cam(int device, double* S12, int fix_scale, const double* P1c, const double* P2c, const double* obs1,
+                          const double* obs2, const double* w1, const double* w2, int N, const dvm_camera_model* model1,
+                          const dvm_camera_model* model2, double th2, uint8_t* inlier, int32_t* n_inliers) {
+  double K[8];
+  float camp[16];
+  if (!sim3_models(model1, model2, K, camp)) { set_error("dvm_optimize_sim3_cam: NULL model, unknown model or zero focal length"); return DVM_ERR_INVALID; }
+  const bool fisheye = model1->model != dvm_cam::kPinhole || model2->model != dvm_cam::kPinhole;
+  return optimize_sim3_impl("dvm_optimize_sim3_cam", device, S12, fix_scale, P1c, P2c, obs1, obs2, w1, w2, N, K, fisheye ? camp : nullptr,
+                            model1->model, model2->model, th2, inlier, n_inliers);
+}
+
+int dvm_sim3_hypotheses(int device, const float* P1c, const float* P2c, const float* max_err1, const float* max_err2, int N,
+                        const float* K1, const float* K2, const int32_t* triples, int H, int fix_scale, float* T12,
+                        int32_t* n_inliers, uint8_t* inlier_mask) {
+  if (!K1 || !K2) { set_error("dvm_sim3_hypotheses: bad arguments"); return DVM_ERR_INVALID; }
+  float K[8];
+  std::memcpy(K, K1, 16); std::memcpy(K + 4, K2, 16);
+  return sim3_hypotheses_impl("dvm_sim3_hypotheses", device, P1c, P2c, max_err1, max_err2, N, K, nullptr, 0, 0, triples, H, fix_scale, T12,
+                              n_inliers, inlier_mask);
+}
+
+int dvm_sim3_hypotheses_cam(int device, const float* P1c, const float* P2c, const float* max_err1, const float* max_err2, int N,
+                            const dvm_camera_model* model1, const dvm_camera_model* model2, const int32_t* triples, int H,
+                            int fix_scale, float* T12, int32_t* n_inliers, uint8_t* inlier_mask) {
+  float K[8], camp[16];
+  if (!sim3_models(model1, model2, K, camp)) { set_error("dvm_sim3_hypotheses_cam: NULL model, unknown model or zero focal length"); return DVM_ERR_INVALID; }
+  const bool fisheye = model1->model != dvm_cam::kPinhole || model2->model != dvm_cam::kPinhole;
+  return sim3_hypotheses_impl("dvm_sim3_hypotheses_cam", device, P1c, P2c, max_err1, max_err2, N, K, fisheye ? camp : nullptr, model1->model,
+                              model2->model, triples, H, fix_scale, T12, n_inliers, inlier_mask);
 }
 
 }  // extern "C"

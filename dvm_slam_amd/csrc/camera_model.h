@@ -63,6 +63,18 @@ DVM_CAM_HD void kb8_project(const float* p, double x, double y, double z, double
   v = (double)p[1] * r * s + (double)p[3];
 }
 
+// The double projection with theta from the DOUBLE atan2 / sqrt and nothing else changed: the smooth function projectJac is the derivative
+// of.  What a numeric (central-difference) Jacobian is taken on: through the quantised theta above a step of 1e-9 sees a staircase.
+DVM_CAM_HD void kb8_project_exact(const float* p, double x, double y, double z, double& u, double& v) {
+  const double rho2 = x * x + y * y;
+  const double r = kb8_radius<double>(p + 4, atan2(sqrt(rho2), z));
+  const double rho = sqrt(rho2);
+  const bool axis = !(rho > 0.0);
+  const double c = axis ? 1.0 : x / rho, s = axis ? 0.0 : y / rho;
+  u = (double)p[0] * r * c + (double)p[2];
+  v = (double)p[1] * r * s + (double)p[3];
+}
+
 // projectJac: d(u, v) / d(x, y, z), row-major 2 x 3, double; its theta is the double atan2.  With rho = sqrt(x^2 + y^2),
 // d^2 = rho^2 + z^2, r(theta) and r'(theta) = 1 + 3 k1 theta^2 + 5 k2 theta^4 + 7 k3 theta^6 + 9 k4 theta^8:
 //   a = r' z / (rho^2 d^2)  (radial: d theta / d rho = z / d^2, along (x, y) / rho),   b = r / rho^3  (tangential),

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "camera_model.h"
 #include "se3_f64.h"
 
 namespace dvm {
@@ -75,6 +76,19 @@ __device__ __forceinline__ void sim3_proj(const Sim3M& m, const double* x, const
   const double X = m.s * rx[0] + m.t[0], Y = m.s * rx[1] + m.t[1], Z = m.s * rx[2] + m.t[2];
   u = K[0] * X / Z + K[2];
   v = K[1] * Y / Z + K[3];
+}
+// sim3_proj on a camera model (camera_model.h): M == 0 is sim3_proj itself; KannalaBrandt8 projects with p = mvParameters, through the
+// reference's project(Vector3d) (float theta: residuals and chi2 tests) or, EXACT, through the double atan2 (numeric Jacobians).
+template <int M, bool EXACT>
+__device__ __forceinline__ void sim3_proj_cam(const Sim3M& m, const double* x, const double* K, const float* p, double& u, double& v) {
+  if constexpr (M == dvm_cam::kPinhole) sim3_proj(m, x, K, u, v);
+  else {
+    double rx[3];
+    mat3_vec(m.R, x, rx);
+    const double X = m.s * rx[0] + m.t[0], Y = m.s * rx[1] + m.t[1], Z = m.s * rx[2] + m.t[2];
+    if constexpr (EXACT) dvm_cam::kb8_project_exact(p, X, Y, Z, u, v);
+    else dvm_cam::kb8_project(p, X, Y, Z, u, v);
+  }
 }
 __device__ inline void sim3_log(const Sim3d& S, double* res) {   // g2o Sim3::log, sim3.h:128-197
   const double sigma = log(S.s);

@@ -1,6 +1,7 @@
 // dvm_slam_amd/csrc/sim3_kernels.hip -- loop closing's Sim3 estimation on the device, FP64 / FP32, for gfx950:
 //   B9  k_optimize_sim3      Optimizer::OptimizeSim3: one workgroup, dense 7x7 Levenberg with g2o's numeric Jacobians
 //       k_sim3_hypotheses    Sim3Solver: one wave per RANSAC hypothesis (Horn's closed form + inlier count)
+// Both are templates over the camera models of the two keyframes (camera_model.h: 0 pinhole, 1 KannalaBrandt8), instantiated for the four pairs.
 // g2o::Sim3 itself is sim3_f64.h's, the 36-value reduction reduce_f64.h's.  Launchers: ba_kernels.h.
 #include <hip/hip_runtime.h>
 
@@ -18,18 +19,31 @@ namespace dvm {
 // analytic linearizeOplus is commented out (include/OptimizableTypes.h:186,205); dense 7x7 Levenberg,
 // optimize(5), inlier test chi2 <= th2, robust kernel off, optimize(5 or 10), final inlier count.
 // One workgroup runs everything; the 14 perturbed Sim3 states (and inverses) are shared by all edges.
+//
+// M1 / M2 = the camera model of keyframe 1 / 2 (camera_model.h; the reference's edges call pCamera1->project / pCamera2->project,
+// OptimizableTypes.h:183, 202), one instantiation per pair.  <0, 0> is the pinhole kernel: camp is not read.  A KannalaBrandt8 side
+// takes its eight parameters from camp[0..7] (camera 1) / camp[8..15] (camera 2) and splits the projection in two:
+//   residual, chi2, both inlier tests   kb8_project(double): the reference's project(Vector3d), theta from the FLOAT atan2f;
+//   the central differences             kb8_project_exact: theta from the double atan2, same 28 perturbed states, same delta.
+// Through the float theta the residual is a staircase with steps of one float ulp of theta (~3e-8 rad): a perturbation of 1e-9 crosses
+// a step in a few per cent of the evaluations and then reads ~1e-5 px / 2e-9, so g2o's numeric Jacobian of a fisheye edge is 0 almost
+// everywhere with spikes of thousands of px per unit, decided by libm's last bit of atan2f.  Nothing can be pinned to that; the smooth
+// projection is the function projectJac differentiates (bundle adjustment on a camera model splits residual and Jacobian the same way).
+template <int M1, int M2>
 __global__ void __launch_bounds__(256) k_optimize_sim3(double* __restrict__ S12io, int fix_scale, const double* __restrict__ P1c,
                                                        const double* __restrict__ P2c, const double* __restrict__ obs1,
                                                        const double* __restrict__ obs2, const double* __restrict__ w1,
                                                        const double* __restrict__ w2, int N, const double* __restrict__ Kio,
-                                                       double th2, uint8_t* __restrict__ inlier, int32_t* __restrict__ nin_out,
-                                                       double* __restrict__ chi_scratch, uint8_t* __restrict__ flag_scratch) {
+                                                       const float* __restrict__ camp, double th2, uint8_t* __restrict__ inlier,
+                                                       int32_t* __restrict__ nin_out, double* __restrict__ chi_scratch,
+                                                       uint8_t* __restrict__ flag_scratch) {
   __shared__ double s_park[256 * 37];   // the 36 sums of a Jacobian pass in ONE pass through LDS
   __shared__ double s_part[4 * 36];
   __shared__ double s_sum[36];
   __shared__ Sim3d s_S, s_bak;
   __shared__ Sim3M s_M[30];   // [0] S, [1] S^-1, [2+2d] S+d, [3+2d] (S+d)^-1, [16+2d] S-d, [17+2d] (S-d)^-1
   __shared__ double s_K[8];
+  __shared__ float s_p[16];
   __shared__ double s_lambda, s_ni, s_cur, s_ini, s_rho;
   __shared__ int s_ctl, s_qmax, s_nbad, s_cnt;
   const int tid = threadIdx.x;
@@ -38,6 +52,7 @@ __global__ void __launch_bounds__(256) k_optimize_sim3(double* __restrict__ S12i
   uint8_t* alive = flag_scratch;
   uint8_t* robust = flag_scratch + N;
   if (tid < 8) s_K[tid] = Kio[tid];
+  if constexpr (M1 != 0 || M2 != 0) { if (tid < 16) s_p[tid] = camp[tid]; }
   if (tid == 0) {
     for (int i = 0; i < 4; i++) s_S.q[i] = S12io[i];
     for (int i = 0; i < 3; i++) s_S.t[i] = S12io[4 + i];
@@ -73,9 +88,9 @@ __global__ void __launch_bounds__(256) k_optimize_sim3(double* __restrict__ S12i
       if (!alive[i]) continue;
       const double* x1 = P1c + 3 * i; const double* x2 = P2c + 3 * i;
       double u, v;
-      sim3_proj(s_M[0], x2, s_K, u, v);
+      sim3_proj_cam<M1, false>(s_M[0], x2, s_K, s_p, u, v);
       const double a0 = obs1[2 * i] - u, a1 = obs1[2 * i + 1] - v;
-      sim3_proj(s_M[1], x1, s_K + 4, u, v);
+      sim3_proj_cam<M2, false>(s_M[1], x1, s_K + 4, s_p + 8, u, v);
       const double b0 = obs2[2 * i] - u, b1 = obs2[2 * i + 1] - v;
       const double c12 = w1[i] * (a0 * a0 + a1 * a1), c21 = w2[i] * (b0 * b0 + b1 * b1);
       chi12[i] = c12; chi21[i] = c21;
@@ -90,10 +105,10 @@ __global__ void __launch_bounds__(256) k_optimize_sim3(double* __restrict__ S12i
 #pragma unroll
         for (int d = 0; d < 7; d++) {
           double up, vp, um, vm;
-          sim3_proj(s_M[2 + 2 * d], x2, s_K, up, vp); sim3_proj(s_M[16 + 2 * d], x2, s_K, um, vm);
+          sim3_proj_cam<M1, true>(s_M[2 + 2 * d], x2, s_K, s_p, up, vp); sim3_proj_cam<M1, true>(s_M[16 + 2 * d], x2, s_K, s_p, um, vm);
           // e(+d) - e(-d) = (obs - proj+) - (obs - proj-)
           J12[d] = 5e8 * ((obs1[2 * i] - up) - (obs1[2 * i] - um)); J12[7 + d] = 5e8 * ((obs1[2 * i + 1] - vp) - (obs1[2 * i + 1] - vm));
-          sim3_proj(s_M[3 + 2 * d], x1, s_K + 4, up, vp); sim3_proj(s_M[17 + 2 * d], x1, s_K + 4, um, vm);
+          sim3_proj_cam<M2, true>(s_M[3 + 2 * d], x1, s_K + 4, s_p + 8, up, vp); sim3_proj_cam<M2, true>(s_M[17 + 2 * d], x1, s_K + 4, s_p + 8, um, vm);
           J21[d] = 5e8 * ((obs2[2 * i] - up) - (obs2[2 * i] - um)); J21[7 + d] = 5e8 * ((obs2[2 * i + 1] - vp) - (obs2[2 * i + 1] - vm));
         }
 #pragma unroll
@@ -252,9 +267,9 @@ __global__ void __launch_bounds__(256) k_optimize_sim3(double* __restrict__ S12i
   for (int i = tid; i < N; i += 256) {
     if (!alive[i]) continue;
     double u, v;
-    sim3_proj(s_M[0], P2c + 3 * i, s_K, u, v);
+    sim3_proj_cam<M1, false>(s_M[0], P2c + 3 * i, s_K, s_p, u, v);
     const double a0 = obs1[2 * i] - u, a1 = obs1[2 * i + 1] - v;
-    sim3_proj(s_M[1], P1c + 3 * i, s_K + 4, u, v);
+    sim3_proj_cam<M2, false>(s_M[1], P1c + 3 * i, s_K + 4, s_p + 8, u, v);
     const double b0 = obs2[2 * i] - u, b1 = obs2[2 * i + 1] - v;
     const double c12 = w1[i] * (a0 * a0 + a1 * a1), c21 = w2[i] * (b0 * b0 + b1 * b1);
     if (!(c12 > th2 || c21 > th2)) { inlier[i] = 1; in++; }
@@ -269,11 +284,25 @@ __global__ void __launch_bounds__(256) k_optimize_sim3(double* __restrict__ S12i
   }
 }
 
+void ba_launch_optimize_sim3_cam(hipStream_t s, double* S12io, int fix_scale, const double* P1c, const double* P2c,
+                                 const double* obs1, const double* obs2, const double* w1, const double* w2, int N, const double* K,
+                                 const float* camp, int model1, int model2, double th2, uint8_t* inlier, int32_t* nin,
+                                 double* chi_scratch, uint8_t* flag_scratch) {
+#define DVM_SIM3_OPT(A, B)                                                                                                          \
+  hipLaunchKernelGGL((k_optimize_sim3<A, B>), dim3(1), dim3(256), 0, s, S12io, fix_scale, P1c, P2c, obs1, obs2, w1, w2, N, K, camp, \
+                     th2, inlier, nin, chi_scratch, flag_scratch)
+  if (model1 == 0 && model2 == 0) DVM_SIM3_OPT(0, 0);
+  else if (model1 == 0) DVM_SIM3_OPT(0, 1);
+  else if (model2 == 0) DVM_SIM3_OPT(1, 0);
+  else DVM_SIM3_OPT(1, 1);
+#undef DVM_SIM3_OPT
+}
+
 void ba_launch_optimize_sim3(hipStream_t s, double* S12io, int fix_scale, const double* P1c, const double* P2c,
                              const double* obs1, const double* obs2, const double* w1, const double* w2, int N,
                              const double* K, double th2, uint8_t* inlier, int32_t* nin, double* chi_scratch, uint8_t* flag_scratch) {
-  hipLaunchKernelGGL(k_optimize_sim3, dim3(1), dim3(256), 0, s, S12io, fix_scale, P1c, P2c, obs1, obs2, w1, w2, N, K, th2, inlier,
-                     nin, chi_scratch, flag_scratch);
+  ba_launch_optimize_sim3_cam(s, S12io, fix_scale, P1c, P2c, obs1, obs2, w1, w2, N, K, nullptr, 0, 0, th2, inlier, nin, chi_scratch,
+                              flag_scratch);
 }
 
 // ------------------------------------------------------------------------------------------ Sim3Solver
@@ -283,12 +312,25 @@ void ba_launch_optimize_sim3(hipStream_t s, double* S12io, int fix_scale, const 
 // input (the reference draws them with DUtils::Random).  float / double split as in the reference except the 4x4
 // eigen-decomposition: cyclic Jacobi in double ("Horn spec", same as the oracle) instead of Eigen::EigenSolver<float>.
 // (jacobi4_dev: jacobi4.h)
+// M1 / M2 = the camera model of keyframe 1 / 2: the four projections of CheckInliers and FromCameraToImage go through
+// pCamera1->project / pCamera2->project(Vector3f) (Sim3Solver.cc:393-394, 422-446), all float.  A KannalaBrandt8 side reads its
+// parameters from camp[0..7] / camp[8..15]; <0, 0> does not read camp.  Horn's closed form reads no camera: T12 has the same bits
+// under every pair.
 
+// pCamera->project(Vector3f) of model M: K = fx, fy, cx, cy (pinhole), p = mvParameters (KannalaBrandt8)
+template <int M>
+__device__ __forceinline__ void sim3_project_f32(const float* K, const float* p, const float* X, float& u, float& v) {
+  if constexpr (M == dvm_cam::kKannalaBrandt8) dvm_cam::kb8_project(p, X[0], X[1], X[2], u, v);
+  else { u = K[0] * X[0] / X[2] + K[2]; v = K[1] * X[1] / X[2] + K[3]; }
+}
+
+template <int M1, int M2>
 __global__ void __launch_bounds__(64) k_sim3_hypotheses(const float* __restrict__ P1c, const float* __restrict__ P2c,
                                                         const float* __restrict__ max_err1, const float* __restrict__ max_err2,
-                                                        int N, const float* __restrict__ K, const int32_t* __restrict__ triples,
-                                                        int H, int fix_scale, float* __restrict__ T12,
-                                                        int32_t* __restrict__ n_inliers, uint8_t* __restrict__ mask) {
+                                                        int N, const float* __restrict__ K, const float* __restrict__ camp,
+                                                        const int32_t* __restrict__ triples, int H, int fix_scale,
+                                                        float* __restrict__ T12, int32_t* __restrict__ n_inliers,
+                                                        uint8_t* __restrict__ mask) {
   const int h = blockIdx.x, lane = threadIdx.x;
   if (h >= H) return;
   float P1[3][3], P2[3][3];
@@ -365,7 +407,10 @@ __global__ void __launch_bounds__(64) k_sim3_hypotheses(const float* __restrict_
 #pragma unroll
     for (int r = 0; r < 3; r++) out[10 + r] = t[r];
   }
-  const float fx1 = K[0], fy1 = K[1], cx1 = K[2], cy1 = K[3], fx2 = K[4], fy2 = K[5], cx2 = K[6], cy2 = K[7];
+  const float Ka[4] = {K[0], K[1], K[2], K[3]}, Kb[4] = {K[4], K[5], K[6], K[7]};
+  float pa[8], pb[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) { pa[k] = M1 != 0 ? camp[k] : 0.0f; pb[k] = M2 != 0 ? camp[8 + k] : 0.0f; }
   int nin = 0;
   for (int base = 0; base < N; base += 64) {
     const int i = base + lane;
@@ -378,10 +423,11 @@ __global__ void __launch_bounds__(64) k_sim3_hypotheses(const float* __restrict_
         a[r] = ((sR[r][0] * X2[0] + sR[r][1] * X2[1]) + sR[r][2] * X2[2]) + t[r];
         b[r] = ((sRi[r][0] * X1[0] + sRi[r][1] * X1[1]) + sRi[r][2] * X1[2]) + ti[r];
       }
-      const float p1x = fx1 * X1[0] / X1[2] + cx1, p1y = fy1 * X1[1] / X1[2] + cy1;   // FromCameraToImage
-      const float p2x = fx2 * X2[0] / X2[2] + cx2, p2y = fy2 * X2[1] / X2[2] + cy2;
-      const float u1 = fx1 * a[0] / a[2] + cx1, v1 = fy1 * a[1] / a[2] + cy1;
-      const float u2 = fx2 * b[0] / b[2] + cx2, v2 = fy2 * b[1] / b[2] + cy2;
+      float p1x, p1y, p2x, p2y, u1, v1, u2, v2;
+      sim3_project_f32<M1>(Ka, pa, X1, p1x, p1y);   // FromCameraToImage
+      sim3_project_f32<M2>(Kb, pb, X2, p2x, p2y);
+      sim3_project_f32<M1>(Ka, pa, a, u1, v1);
+      sim3_project_f32<M2>(Kb, pb, b, u2, v2);
       const float d1x = p1x - u1, d1y = p1y - v1, d2x = u2 - p2x, d2y = v2 - p2y;
       const float err1 = d1x * d1x + d1y * d1y, err2 = d2x * d2x + d2y * d2y;
       in = err1 < max_err1[i] && err2 < max_err2[i];
@@ -392,9 +438,23 @@ __global__ void __launch_bounds__(64) k_sim3_hypotheses(const float* __restrict_
   if (lane == 0) n_inliers[h] = nin;
 }
 
+void ba_launch_sim3_hypotheses_cam(hipStream_t s, const float* P1c, const float* P2c, const float* e1, const float* e2, int N,
+                                   const float* K, const float* camp, int model1, int model2, const int32_t* triples, int H,
+                                   int fix_scale, float* T12, int32_t* nin, uint8_t* mask) {
+  if (H <= 0) return;
+#define DVM_SIM3_HYP(A, B)                                                                                                        \
+  hipLaunchKernelGGL((k_sim3_hypotheses<A, B>), dim3(H), dim3(64), 0, s, P1c, P2c, e1, e2, N, K, camp, triples, H, fix_scale, T12, \
+                     nin, mask)
+  if (model1 == 0 && model2 == 0) DVM_SIM3_HYP(0, 0);
+  else if (model1 == 0) DVM_SIM3_HYP(0, 1);
+  else if (model2 == 0) DVM_SIM3_HYP(1, 0);
+  else DVM_SIM3_HYP(1, 1);
+#undef DVM_SIM3_HYP
+}
+
 void ba_launch_sim3_hypotheses(hipStream_t s, const float* P1c, const float* P2c, const float* e1, const float* e2, int N,
                                const float* K, const int32_t* triples, int H, int fix_scale, float* T12, int32_t* nin, uint8_t* mask) {
-  if (H > 0) hipLaunchKernelGGL(k_sim3_hypotheses, dim3(H), dim3(64), 0, s, P1c, P2c, e1, e2, N, K, triples, H, fix_scale, T12, nin, mask);
+  ba_launch_sim3_hypotheses_cam(s, P1c, P2c, e1, e2, N, K, nullptr, 0, 0, triples, H, fix_scale, T12, nin, mask);
 }
 
 }  // namespace dvm

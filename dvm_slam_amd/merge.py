@@ -42,6 +42,12 @@ class GpuOps:
     def optimize_sim3(self, S12, P1c, P2c, o1, o2, w1, w2, K1, K2, th2):
         return self.capi.optimize_sim3(S12, False, P1c, P2c, o1, o2, w1, w2, K1, K2, th2, self.device)
 
+    def sim3_hypotheses_cam(self, P1c, P2c, e1, e2, model1, model2, triples):
+        return self.capi.sim3_hypotheses_cam(P1c, P2c, e1, e2, model1, model2, triples, False, self.device)
+
+    def optimize_sim3_cam(self, S12, P1c, P2c, o1, o2, w1, w2, model1, model2, th2):
+        return self.capi.optimize_sim3_cam(S12, False, P1c, P2c, o1, o2, w1, w2, model1, model2, th2, self.device)
+
     def search_by_sim3(self, a, pa, b, pb, m12, idx2, S12, th):
         c = self.capi
         return c.search_by_sim3(c.keyframe_view(dict(a)), c.keyframe_view(dict(b)), c.map_points_view(pa), c.map_points_view(pb), m12, idx2, S12, th,
@@ -67,10 +73,11 @@ def _quat_from_R(R):
     return -q if q[3] < 0 else q
 
 
-def merge_with_peer(ops, kf, kf_points, peer_kfs, peer_points, peer_db, levelsup, triples, nnratio=0.75, th_sim3=7.5):
+def merge_with_peer(ops, kf, kf_points, peer_kfs, peer_points, peer_db, levelsup, triples, nnratio=0.75, th_sim3=7.5, models=None):
     """kf: the current keyframe of this agent (keyframe dict: kps, desc, mp, bad, Tcw (7-float SE3f), K, bounds, scale tables, uuid,
     map_id ...); kf_points / peer_points[j]: map point data PER KEYPOINT (pos in the owner's world frame, min / max
-    distance, descriptor).  Returns a dict with every intermediate result (None fields when the merge is rejected)."""
+    distance, descriptor).  models: see solve_against_candidate.  Returns a dict with every intermediate result (None fields when the
+    merge is rejected)."""
     out = dict(candidate=-1)
     tr = ops.transform(kf["desc"], levelsup)
     kf = dict(kf, fv={k: tr[k] for k in ("fv_nodes", "fv_off", "fv_feat")})
@@ -78,13 +85,15 @@ def merge_with_peer(ops, kf, kf_points, peer_kfs, peer_points, peer_db, levelsup
     out.update(merge_possible=ok, candidate=best, score=score, baseline=base)
     if best < 0:
         return out
-    out.update(solve_against_candidate(ops, kf, kf_points, peer_kfs[best], peer_points[best], triples, nnratio, th_sim3))
+    out.update(solve_against_candidate(ops, kf, kf_points, peer_kfs[best], peer_points[best], triples, nnratio, th_sim3, models))
     return out
 
 
-def solve_against_candidate(ops, kf, kf_points, pk, pp, triples, nnratio=0.75, th_sim3=7.5):
+def solve_against_candidate(ops, kf, kf_points, pk, pp, triples, nnratio=0.75, th_sim3=7.5, models=None):
     """Steps 2-5 for one candidate keyframe `pk` (with per-keypoint map point data `pp`) of the peer; `kf` carries its feature
-    vector.  Returns the intermediate results (see merge_with_peer)."""
+    vector.  models = (model1, model2): the capi.CameraModel of `kf` and of `pk` (pinhole or KannalaBrandt8, in any pair); steps 3 and 4
+    then project with them (ops.sim3_hypotheses_cam / ops.optimize_sim3_cam) and kf["K"] / pk["K"] are read by step 5 only, which keeps
+    the pinhole formula as the reference writes it.  None: two pinhole cameras K.  Returns the intermediate results (see merge_with_peer)."""
     out = {}
     n12, m12 = ops.search_by_bow(kf, pk, nnratio)
     out.update(n_bow_matches=n12, bow_matches=m12)
@@ -100,7 +109,10 @@ def solve_against_candidate(ops, kf, kf_points, pk, pp, triples, nnratio=0.75, t
     P2c = (pp["pos"][i2].astype(np.float64) @ R2.T + t2).astype(np.float32)
     e1 = np.floor(9.210 * kf["level_sigma2"][kf["kps"]["octave"][sel]]).astype(np.float32)     # Sim3Solver.cc:106-107
     e2 = np.floor(9.210 * pk["level_sigma2"][pk["kps"]["octave"][i2]]).astype(np.float32)
-    T, nin, mask = ops.sim3_hypotheses(P1c, P2c, e1, e2, kf["K"], pk["K"], triples % len(sel))
+    if models is None:
+        T, nin, mask = ops.sim3_hypotheses(P1c, P2c, e1, e2, kf["K"], pk["K"], triples % len(sel))
+    else:
+        T, nin, mask = ops.sim3_hypotheses_cam(P1c, P2c, e1, e2, models[0], models[1], triples % len(sel))
     h = int(np.argmax(nin))
     out.update(hyp_T=T, hyp_inliers=nin, best_hyp=h)
     if nin[h] < 20:
@@ -111,8 +123,11 @@ def solve_against_candidate(ops, kf, kf_points, pk, pp, triples, nnratio=0.75, t
     o2 = np.stack([pk["kps"]["x"][i2], pk["kps"]["y"][i2]], 1).astype(np.float64)
     w1 = kf["inv_level_sigma2"][kf["kps"]["octave"][sel]].astype(np.float64)
     w2 = pk["inv_level_sigma2"][pk["kps"]["octave"][i2]].astype(np.float64)
-    S, inl, n_in = ops.optimize_sim3(S12, P1c.astype(np.float64), P2c.astype(np.float64), o1, o2, w1, w2, kf["K"].astype(np.float64),
-                                     pk["K"].astype(np.float64), 10.0)
+    if models is None:
+        S, inl, n_in = ops.optimize_sim3(S12, P1c.astype(np.float64), P2c.astype(np.float64), o1, o2, w1, w2, kf["K"].astype(np.float64),
+                                         pk["K"].astype(np.float64), 10.0)
+    else:
+        S, inl, n_in = ops.optimize_sim3_cam(S12, P1c.astype(np.float64), P2c.astype(np.float64), o1, o2, w1, w2, models[0], models[1], 10.0)
     out.update(S12=S, sim3_inliers=inl, n_sim3_inliers=n_in, pairs=(sel, i2))
     if n_in < 20:
         return out

@@ -272,13 +272,15 @@ int dvm_is_in_frustum(const dvm_frustum_frame* frame, const float* P, const floa
  * (projectJac, KannalaBrandt8.cpp:144-172) is 0 / 0 on the optical axis: NaN there, as in the reference.  sizeof(dvm_camera_model) == 36.
  * Every *_cam entry returns DVM_ERR_INVALID, before anything runs, for a NULL model, a model outside {0, 1} or a zero focal length.
  * What takes a model: dvm_pose_optimize_cam, dvm_is_in_frustum_cam, dvm_project_search_cam, dvm_ba_set_problem_cam,
- * dvm_ba_optimize_windows_fast_cam, dvm_ba_pool_optimize_cam, dvm_match_triangulation_cam, dvm_triangulate_matches_cam, dvm_create_new_map_points_cam (and dvmh_search_by_projection_frames_cam,
+ * dvm_ba_optimize_windows_fast_cam, dvm_ba_pool_optimize_cam, dvm_match_triangulation_cam, dvm_triangulate_matches_cam, dvm_create_new_map_points_cam,
+ * dvm_sim3_hypotheses_cam, dvm_optimize_sim3_cam (and dvmh_search_by_projection_frames_cam,
  * dvmh_triangulation_geometry_cam, dvmh_search_for_triangulation_cam, dvmh_create_new_map_points_cam, include/dvmslam_host.h).  The
  * entries that take the models of TWO keyframes want one model type for both (the parameters may differ per keyframe): a pair of a
- * pinhole and a KannalaBrandt8 keyframe is DVM_ERR_INVALID -- the reference's mixed pair is out of scope.  The tracked-frame
+ * pinhole and a KannalaBrandt8 keyframe is DVM_ERR_INVALID -- the reference's mixed pair is out of scope -- except the two Sim3 entries
+ * (dvm_sim3_hypotheses_cam, dvm_optimize_sim3_cam), which take all four pairs: a merge between a pinhole and a fisheye agent.  The tracked-frame
  * chains take the agent's model as state of the tracker (dvm_tracker_set_camera_model below).  The pools (dvm_orb_pool_*, dvm_match_pool_*,
  * dvm_pose_pool_*), the BoW chain, the sequential-order BA windows (dvm_ba_optimize_windows), dvm_ba_optimize_batch,
- * dvm_ba_set_problem_sharded and OptimizeSim3 are pinhole-only. */
+ * dvm_ba_set_problem_sharded, two-view initialisation and the Sim3Solver / Optimizer shim classes (include/dvmslam_host.h) are pinhole-only. */
 typedef struct { int32_t model;   /* 0 pinhole, 1 KannalaBrandt8 */
                  float p[8];      /* fx, fy, cx, cy, k1, k2, k3, k4: mvParameters, float as the reference stores them */
 } dvm_camera_model;
@@ -1241,6 +1243,25 @@ int dvm_optimize_sim3(int device, double* S12, int fix_scale, const double* P1c,
                       const double* obs2, const double* w1, const double* w2, int N, const double* K1, const double* K2,
                       double th2, uint8_t* inlier, int32_t* n_inliers);
 
+/* dvm_optimize_sim3 on a camera model per keyframe (EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ project with pCamera1 / pCamera2,
+ * OptimizableTypes.h:183, 202): model1 / model2 = the cameras of KF1 / KF2, their p[0..3] replace K1 / K2; all four pairs of (pinhole,
+ * KannalaBrandt8) are accepted.  For a KannalaBrandt8 keyframe obs are mvKeysUn = mvKeys.  Arguments, outputs and return values are
+ * otherwise dvm_optimize_sim3's; with model 0 on both sides the outputs are dvm_optimize_sim3's bit for bit.
+ * On a KannalaBrandt8 side the projection is split:
+ *   - the residual and every chi2 test (Huber weights, the inlier tests of both rounds, the final count) take the reference's
+ *     project(Vector3d): theta from the FLOAT atan2f / sqrtf (KannalaBrandt8.cpp:48-51), so the residual is a step function of the state
+ *     with steps of one float ulp of theta (~3e-8 rad);
+ *   - the numeric Jacobian is the same central difference at delta = 1e-9 through the same 28 perturbed states, taken on the projection
+ *     with theta from the DOUBLE atan2 (camera_model.h: kb8_project_exact), e = obs - proj in the pinhole path's operand order.
+ * g2o's own numeric Jacobian through the float theta is 0 almost everywhere -- a 1e-9 perturbation crosses a step in a few per cent of the
+ * evaluations -- with spikes of ~1e-5 px / 2e-9, several thousand px per unit, where it does: a result that hangs on libm's last bit of
+ * atan2f.  Nothing can be pinned to that and nobody wants it, so this entry departs from the reference here, as bundle adjustment on a
+ * camera model does (residual from the quantised project, Jacobian from projectJac's double atan2).  The pinhole path is untouched.
+ * DVM_ERR_INVALID, before anything runs and before the device is touched, for a NULL model, a model outside {0, 1} or a zero focal length. */
+int dvm_optimize_sim3_cam(int device, double* S12, int fix_scale, const double* P1c, const double* P2c, const double* obs1,
+                          const double* obs2, const double* w1, const double* w2, int N, const dvm_camera_model* model1,
+                          const dvm_camera_model* model2, double th2, uint8_t* inlier, int32_t* n_inliers);
+
 /* Optimizer::OptimizeEssentialGraph numerics (src/Optimizer.cc:1389-1652): Sim3 pose graph of n vertices
  * (S[n][8] = estimates Siw as (q_xyzw, t, s), in/out; fixed[v] != 0 keeps a vertex) and E EdgeSim3 (vertex 0 = vi,
  * vertex 1 = vj, measurement Sji = Sjw * Swi, information = identity).  g2o's numeric Jacobians, Levenberg-Marquardt
@@ -1282,6 +1303,14 @@ int dvm_pose_graph_debug_trial(int device, double* S, const uint8_t* fixed, int 
 int dvm_sim3_hypotheses(int device, const float* P1c, const float* P2c, const float* max_err1, const float* max_err2, int N,
                         const float* K1, const float* K2, const int32_t* triples, int H, int fix_scale, float* T12,
                         int32_t* n_inliers, uint8_t* inlier_mask);
+/* dvm_sim3_hypotheses on a camera model per keyframe: the four projections of CheckInliers and FromCameraToImage are
+ * pCamera1->project / pCamera2->project(Vector3f) (Sim3Solver.cc:393-394, 422-446) of model1 / model2, whose p[0..3] replace K1 / K2;
+ * all four pairs of (pinhole, KannalaBrandt8).  Horn's closed form reads no camera: T12 is dvm_sim3_hypotheses' bit for bit under every
+ * pair, and with model 0 on both sides so are the counts and the masks.  DVM_ERR_INVALID, before anything runs and before the device
+ * is touched, for a NULL model, a model outside {0, 1} or a zero focal length. */
+int dvm_sim3_hypotheses_cam(int device, const float* P1c, const float* P2c, const float* max_err1, const float* max_err2, int N,
+                            const dvm_camera_model* model1, const dvm_camera_model* model2, const int32_t* triples, int H,
+                            int fix_scale, float* T12, int32_t* n_inliers, uint8_t* inlier_mask);
 
 #ifdef __cplusplus
 }
