@@ -2659,6 +2659,66 @@ class NewPoints(_Chain):
             return R.result()
         return run
 
+    @staticmethod
+    def _keyframe_resident(slot, kf, keep):
+        """(dvm_np_keyframe_resident, view) of keyframe dict `kf` living in store slot `slot`: mp and the pose travel, the rest is the slot's."""
+        v, k = keyframe_view(kf)
+        keep.append(k)
+        s = _NpKeyFrameResident()
+        s.slot, s.mp = int(slot), v.mvpMapPoints
+        s.Tcw = v.Tcw; s.Twc = v.Twc
+        s.Ow = (C.c_float * 3)(*v.Twc[4:7])
+        return s, v
+
+    def prepare_resident(self, store, cur_slot, cur, nb_slots, neighbours, median_depth, cur_model=None, nb_models=None, record_cap=None, **params):
+        """prepare() for dvm_create_new_map_points_resident: `cur` / neighbours[j] are the keyframe dicts that were put to cur_slot /
+        nb_slots[j] of `store` (a KeyframeStore).  Of a dict the call sends mp and the pose; its intrinsics and poses also give the pair
+        geometry (ep, F12; with cur_model / nb_models the rules of prepare_cam).  mp is read in place at run()."""
+        keep = []
+        c, cv = self._keyframe_resident(cur_slot, cur, keep)
+        n_nb = len(neighbours)
+        assert len(nb_slots) == n_nb
+        nbs = (_NpNeighbourResident * max(n_nb, 1))()
+        poses = (PairPose * max(n_nb, 1))()
+        models = (CameraModel * max(n_nb, 1))()
+        for j, kf in enumerate(neighbours):
+            s, v = self._keyframe_resident(nb_slots[j], kf, keep)
+            nbs[j].kf = s
+            nbs[j].median_depth = float(median_depth[j])
+            if cur_model is None:
+                _, _, ep, F12 = triangulation_geometry((cv, None), (v, None))
+            else:
+                models[j] = nb_models[j]
+                R12, t12, ep, F12 = triangulation_geometry_cam((cv, None), (v, None), cur_model, nb_models[j])
+                poses[j] = pair_pose(R12, t12)
+            nbs[j].ep = (C.c_float * 2)(*ep); nbs[j].F12 = (C.c_float * 9)(*F12)
+        p = _np_params(cur, **params)
+        R = _NpResult(len(cur["kps"]), n_nb, _np_record_cap(cur, n_nb, record_cap))
+        fn = self.L.dvm_create_new_map_points_resident
+        vp = C.c_void_p
+        fn.restype = C.c_int32; fn.argtypes = [vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+
+        def run():
+            keep  # noqa: B018 (the views' arrays live as long as the closure)
+            check(fn(self.h, store.h, C.addressof(c), None if cur_model is None else C.addressof(cur_model), n_nb, C.addressof(nbs),
+                     None if cur_model is None else C.addressof(models), None if cur_model is None else C.addressof(poses), C.addressof(p),
+                     C.addressof(R.out)))
+            return R.result()
+        return run
+
+    def create_new_map_points_resident(self, store, cur_slot, cur, nb_slots, neighbours, median_depth, cur_model=None, nb_models=None, record_cap=None,
+                                       **params):
+        """dvm_create_new_map_points_resident; arguments as prepare_resident, result as create_new_map_points."""
+        return self.prepare_resident(store, cur_slot, cur, nb_slots, neighbours, median_depth, cur_model, nb_models, record_cap=record_cap, **params)()
+
+    def last_upload_bytes(self):
+        """The host-to-device bytes queued by the last call that reached the device, resident or not."""
+        a = C.c_int64(0)
+        fn = self.L.dvm_new_points_last_upload_bytes
+        fn.restype = C.c_int32; fn.argtypes = [C.c_void_p, C.c_void_p]
+        check(fn(self.h, C.byref(a)))
+        return a.value
+
     def create_new_map_points_cam(self, cur, neighbours, median_depth, cur_model, nb_models, record_cap=None, **params):
         """dvm_create_new_map_points_cam; arguments as prepare_cam, result as create_new_map_points."""
         return self.prepare_cam(cur, neighbours, median_depth, cur_model, nb_models, record_cap=record_cap, **params)()
@@ -2792,6 +2852,45 @@ class FuseTargets(_Chain):
         check(self.L.dvm_fuse_targets_set(self.h, int(n), C.addressof(arr)))
         self.n_targets = int(n)
 
+    @staticmethod
+    def resident_targets(slots, poses):
+        """(dvm_ft_target_resident array) of slots[t] under poses[t]: a 7-float Tcw (the centre is derived as KeyFrame::SetPose does, Twc's
+        translation) or a (Tcw, Ow) pair (the Scw form: what sim3_to_se3(Scw) returns)."""
+        arr = (_FtTargetResident * max(len(slots), 1))()
+        for t, (sl, pose) in enumerate(zip(slots, poses)):
+            Tcw, Ow = pose if isinstance(pose, (tuple, list)) and len(pose) == 2 else (pose, None)
+            Tcw = np.asarray(Tcw, np.float32).reshape(7)
+            Ow = se3_inverse(Tcw)[4:7] if Ow is None else np.asarray(Ow, np.float32).reshape(3)
+            arr[t].slot = int(sl); arr[t].Tcw = (C.c_float * 7)(*Tcw); arr[t].Ow = (C.c_float * 3)(*Ow)
+        return arr
+
+    def set_resident(self, store, slots, poses, models=None, forms=None):
+        """dvm_fuse_targets_set_resident: target t is slot slots[t] of `store` (a KeyframeStore) under poses[t] (resident_targets);
+        models / forms as set().  Only the target table travels; run() / run_hits() follow as after set()."""
+        assert len(slots) == len(poses)
+        arr = self.resident_targets(slots, poses)
+        self.set_resident_raw(store, arr, len(slots), models, forms)
+
+    def set_resident_raw(self, store, arr, n, models=None, forms=None):
+        m = None
+        if models is not None:
+            m = (CameraModel * max(n, 1))()
+            for t, x in enumerate(models):
+                m[t] = x
+        f = None if forms is None else np.ascontiguousarray(forms, np.uint8)
+        fn = self.L.dvm_fuse_targets_set_resident
+        fn.restype = C.c_int32; fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        check(fn(self.h, store.h, int(n), C.addressof(arr), None if m is None else C.addressof(m), _ptr(f)))
+        self.n_targets = int(n)
+
+    def last_upload_bytes(self):
+        """(set_bytes, run_bytes): the host-to-device bytes queued by the last set (uploaded or resident) and the last run."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        fn = self.L.dvm_fuse_targets_last_upload_bytes
+        fn.restype = C.c_int32; fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        check(fn(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def reserve_hits(self, max_hits):
         check(self.L.dvm_fuse_targets_reserve_hits(self.h, int(max_hits)))
 
@@ -2908,6 +3007,124 @@ def fuse_sim3_apply(KF, P, hits):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # dvm_search_by_bow_targets: the SearchByBoW calls of LoopClosing::DetectCommonRegionsFromBoW against all candidates and covisibles as one chain
+# dvm_keyframe_store: keyframes resident on the device, read by FuseTargets.set_resident and NewPoints.create_new_map_points_resident
+class _KfsKeyframe(C.Structure):   # == dvm_kfs_keyframe
+    _fields_ = [("n", C.c_int32), ("kps", C.c_void_p), ("desc", C.c_void_p), ("fv_n", C.c_int32), ("fv_node", C.c_void_p), ("fv_off", C.c_void_p),
+                ("fv_feat", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("log_scale_factor", C.c_float),
+                ("n_levels", C.c_int32)]
+
+
+class _KfsReadback(C.Structure):   # == dvm_kfs_readback
+    _fields_ = [("n", C.c_int32), ("fv_n", C.c_int32), ("n_feat", C.c_int32), ("n_levels", C.c_int32), ("n_sorted", C.c_int32), ("n_total", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("log_scale_factor", C.c_float),
+                ("generation", C.c_uint32), ("kps", C.c_void_p), ("desc", C.c_void_p), ("fv_node", C.c_void_p), ("fv_off", C.c_void_p),
+                ("fv_feat", C.c_void_p), ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("inv_level_sigma2", C.c_void_p),
+                ("skp", C.c_void_p), ("sidx", C.c_void_p), ("sdesc", C.c_void_p), ("cell_start", C.c_void_p)]
+
+
+class _FtTargetResident(C.Structure):   # == dvm_ft_target_resident
+    _fields_ = [("slot", C.c_int32), ("Tcw", C.c_float * 7), ("Ow", C.c_float * 3)]
+
+
+class _NpKeyFrameResident(C.Structure):   # == dvm_np_keyframe_resident
+    _fields_ = [("slot", C.c_int32), ("mp", C.c_void_p), ("Tcw", C.c_float * 7), ("Twc", C.c_float * 7), ("Ow", C.c_float * 3)]
+
+
+class _NpNeighbourResident(C.Structure):   # == dvm_np_neighbour_resident
+    _fields_ = [("kf", _NpKeyFrameResident), ("median_depth", C.c_float), ("ep", C.c_float * 2), ("F12", C.c_float * 9)]
+
+
+KFS_CELL_START = 64 * 48 + 4       # entries of a slot's cell_start (kCellStartStride)
+
+
+class KeyframeStore:
+    """dvm_keyframe_store: `capacity` slots of up to `slot_keypoints` keypoints in device memory, each holding what a keyframe keeps once
+    ComputeBoW has run -- keypoints, descriptors, FeatureVector, level tables, bounds -- and its feature grid.  put() writes keyframes to
+    slots (asynchronous; every later chain call that reads the store sees it), remove() empties slots, read() returns one slot (tests).
+    Calls on one store are not concurrent; the store outlives the chain handles set on it."""
+
+    def __init__(self, capacity, slot_keypoints, device=0):
+        self.L = lib()
+        self.h = C.c_void_p()
+        vp, i32 = C.c_void_p, C.c_int32
+        for name, args in (("create", [i32, i32, i32, vp]), ("capacity", [vp]), ("slot_keypoints", [vp]), ("put", [vp, i32, vp, vp]), ("remove", [vp, i32, vp]),
+                           ("debug_read", [vp, i32, vp])):
+            f = getattr(self.L, "dvm_keyframe_store_" + name)
+            f.restype = i32; f.argtypes = args
+        self.L.dvm_keyframe_store_destroy.restype = None; self.L.dvm_keyframe_store_destroy.argtypes = [vp]
+        check(self.L.dvm_keyframe_store_create(int(device), int(capacity), int(slot_keypoints), C.byref(self.h)))
+
+    @property
+    def capacity(self):
+        return self.L.dvm_keyframe_store_capacity(self.h)
+
+    @property
+    def slot_keypoints(self):
+        return self.L.dvm_keyframe_store_slot_keypoints(self.h)
+
+    @staticmethod
+    def records(kfs):
+        """Keyframe dicts (kps, desc, fv, K, bounds, scale_factors, level_sigma2, inv_level_sigma2, log_scale_factor; the keys keyframe_view
+        takes, a missing one NULL / 0) -> (dvm_kfs_keyframe array, keepalive)."""
+        keep = []
+        arr = (_KfsKeyframe * max(len(kfs), 1))()
+        for t, kf in enumerate(kfs):
+            v, k = keyframe_view(kf)
+            keep.append(k)
+            s = arr[t]
+            s.n, s.kps, s.desc = v.N, v.mvKeysUn, v.mDescriptors
+            s.fv_n, s.fv_node, s.fv_off, s.fv_feat = v.mFeatVec.n, v.mFeatVec.node, v.mFeatVec.off, v.mFeatVec.feat
+            s.fx, s.fy, s.cx, s.cy = v.fx, v.fy, v.cx, v.cy
+            s.min_x, s.max_x, s.min_y, s.max_y = v.mnMinX, v.mnMaxX, v.mnMinY, v.mnMaxY
+            s.scale_factors, s.level_sigma2, s.inv_level_sigma2 = v.mvScaleFactors, v.mvLevelSigma2, v.mvInvLevelSigma2
+            s.log_scale_factor, s.n_levels = v.mfLogScaleFactor, v.nLevels
+        return arr, keep
+
+    def put(self, slots, kfs):
+        slots = np.ascontiguousarray(slots, np.int32)
+        assert slots.ndim == 1 and len(slots) == len(kfs)
+        arr, keep = self.records(kfs)
+        self.put_raw(slots, arr)
+
+    def put_raw(self, slots, arr):
+        check(self.L.dvm_keyframe_store_put(self.h, len(slots), _p(slots), C.addressof(arr)))
+
+    def remove(self, slots):
+        slots = np.ascontiguousarray(slots, np.int32)
+        check(self.L.dvm_keyframe_store_remove(self.h, len(slots), _p(slots)))
+
+    def read(self, slot):
+        """One slot back (synchronous): dict(n, fv_n, n_feat, n_levels, n_sorted, n_total, generation, K, bounds, log_scale_factor, kps,
+        desc, fv_nodes, fv_off, fv_feat, scale_factors, level_sigma2, inv_level_sigma2, skp[n_sorted, 4], sidx, sdesc, cell_start)."""
+        K = self.slot_keypoints
+        a = dict(kps=np.zeros(K, KP_DTYPE), desc=np.zeros((K, 32), np.uint8), fv_node=np.zeros(K, np.int32), fv_off=np.zeros(K + 1, np.int32),
+                 fv_feat=np.zeros(K, np.int32), scale_factors=np.zeros(64, np.float32), level_sigma2=np.zeros(64, np.float32),
+                 inv_level_sigma2=np.zeros(64, np.float32), skp=np.zeros((K, 4), np.float32), sidx=np.zeros(K, np.int32),
+                 sdesc=np.zeros((K, 32), np.uint8), cell_start=np.zeros(KFS_CELL_START, np.int32))
+        r = _KfsReadback()
+        for k, v in a.items():
+            setattr(r, k, v.ctypes.data)
+        check(self.L.dvm_keyframe_store_debug_read(self.h, int(slot), C.addressof(r)))
+        n, ns, nl = r.n, r.n_sorted, r.n_levels
+        return dict(n=n, fv_n=r.fv_n, n_feat=r.n_feat, n_levels=nl, n_sorted=ns, n_total=r.n_total, generation=r.generation,
+                    K=np.array([r.fx, r.fy, r.cx, r.cy], np.float32), bounds=np.array([r.min_x, r.max_x, r.min_y, r.max_y], np.float32),
+                    log_scale_factor=r.log_scale_factor, kps=a["kps"][:n].copy(), desc=a["desc"][:n].copy(), fv_nodes=a["fv_node"][:r.fv_n].copy(),
+                    fv_off=a["fv_off"][:r.fv_n + 1 if r.fv_n else 0].copy(), fv_feat=a["fv_feat"][:r.n_feat].copy(),
+                    scale_factors=a["scale_factors"][:nl].copy(), level_sigma2=a["level_sigma2"][:nl].copy(),
+                    inv_level_sigma2=a["inv_level_sigma2"][:nl].copy(), skp=a["skp"][:ns].copy(), sidx=a["sidx"][:ns].copy(),
+                    sdesc=a["sdesc"][:ns].copy(), cell_start=a["cell_start"])
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L.dvm_keyframe_store_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+
 class _BtKeyFrame(C.Structure):   # == dvm_bt_keyframe
     _fields_ = [("n", C.c_int32), ("fv_n", C.c_int32), ("kps", C.c_void_p), ("desc", C.c_void_p), ("mp", C.c_void_p), ("bad", C.c_void_p),
                 ("fv_node", C.c_void_p), ("fv_off", C.c_void_p), ("fv_feat", C.c_void_p)]

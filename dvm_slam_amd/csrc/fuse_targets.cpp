@@ -6,14 +6,19 @@
 // does not wait.  run: packs the point table and the mask, ONE copy, ONE launch over (target, point) per camera model present, ONE copy
 // back, ONE synchronisation.  run_hits: the same search, then the compaction of the dense rows on the device (three launches) straight
 // into a mapped page-locked block [hit_off][hits] of its own (reserve_hits), and ONE synchronisation: nothing of size T x n comes back.
+// set_resident: the targets are slots of a dvm_keyframe_store (keyframe_store.h): the table's pointers go into the store, the table and
+// the model order list are the whole upload, and no grid is built; a run brackets its search with kfs_read_begin / kfs_read_end.
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
+#include <vector>
 
 #include "../../include/dvmslam_hip.h"
 #include "camera_model.h"
 #include "chain.h"
 #include "fuse_targets_kernels.h"
+#include "keyframe_store.h"
 #include "orb_pipeline.h"
 
 using namespace dvm;
@@ -30,6 +35,10 @@ struct dvm_fuse_targets : Chain {
   int max_hits = -1, hit_targets = 0;
   int build_timed = 0;                          // marks 0 / 1 hold a set's grid build that no run has read yet
   float last_ms[2] = {0, 0};
+  // a resident set: the store its targets live in and every named slot's generation at the set; null: the targets were uploaded
+  const dvm_keyframe_store* store = nullptr;
+  std::vector<std::pair<int32_t, uint32_t>> slot_gen;
+  int64_t set_bytes = 0, run_bytes = 0;         // host-to-device bytes queued by the last set / run
 };
 
 namespace {
@@ -87,6 +96,7 @@ int dvm_fuse_targets_reserve(dvm_fuse_targets* h, int max_points, int max_target
   if ((int64_t)np * nt > kMaxEntries) return fail("dvm_fuse_targets_reserve", DVM_ERR_INVALID, "bad sizes");
   // (the targets of an earlier set go with the block: set again; a failed allocation leaves the handle holding nothing)
   h->tgt_bytes = h->grid_bytes = h->pts_bytes = h->res_bytes = 0; h->max_points = h->max_targets = h->max_total = 0; h->n_targets = -1;
+  h->store = nullptr; h->slot_gen.clear();
   const size_t tgt = pad<64>(pad<64>((size_t)nt * sizeof(FtTargetDev)) + pad<64>((size_t)nt * 4) + (size_t)tot * kUpPerKeypoint + (size_t)nt * kUpFixed);
   const size_t grid = pad<64>((size_t)tot * kGridPerKeypoint + (size_t)nt * kGridFixed + 64);
   const size_t pts = pad<64>((size_t)np * kPointBytes + 7 * 64 + pad<64>((size_t)np * nt));
@@ -116,6 +126,12 @@ int dvm_fuse_targets_profiling(dvm_fuse_targets* h, int enable) {
 int dvm_fuse_targets_last_kernel_ms(dvm_fuse_targets* h, float* ms) {
   if (!h || !ms) return DVM_ERR_INVALID;
   ms[0] = h->last_ms[0]; ms[1] = h->last_ms[1];
+  return DVM_OK;
+}
+int dvm_fuse_targets_last_upload_bytes(const dvm_fuse_targets* h, int64_t* set_bytes, int64_t* run_bytes) {
+  if (!h) return DVM_ERR_INVALID;
+  if (set_bytes) *set_bytes = h->set_bytes;
+  if (run_bytes) *run_bytes = h->run_bytes;
   return DVM_OK;
 }
 
@@ -153,6 +169,7 @@ static int set_targets(const char* fn, dvm_fuse_targets* h, int n_targets, const
     return fail(fn, DVM_ERR_CAPACITY, "beyond the reservation (dvm_fuse_targets_reserve): " + std::to_string(n_targets) + " targets with " +
                                           std::to_string(total) + " keypoints");
   h->n_targets = n_targets;
+  h->store = nullptr; h->slot_gen.clear(); h->set_bytes = 0;
   if (n_targets == 0) return DVM_OK;
   DVM_HIP(hipSetDevice(h->device));
   DVM_HIP(hipStreamSynchronize(h->s));           // the staging region may still feed the copy of an earlier set (idle after a run: free)
@@ -201,11 +218,73 @@ static int set_targets(const char* fn, dvm_fuse_targets* h, int n_targets, const
   }
   if (up.used() > h->tgt_bytes || grid.used() > h->grid_bytes) return fail(fn, DVM_ERR_STATE, "packed targets exceed the reserved regions");   // (an internal error: the constants bound every target)
   DVM_HIP(hipMemcpyAsync(ws.d, ws.hm, up.used(), hipMemcpyHostToDevice, h->s));
+  h->set_bytes = (int64_t)up.used();
   DVM_HIP(h->timer.mark(0, h->s));
   launch_ft_build(h->s, reinterpret_cast<const FtTargetDev*>(ws.d), n_targets);
   DVM_HIP(h->timer.mark(1, h->s));
   h->build_timed = h->timer.on;
   return hip_check(hipGetLastError(), "dvm_fuse_targets_set launch");
+}
+
+// dvm_fuse_targets_set_resident: set_targets with every target's arrays and grid in a store slot
+static int set_resident(const char* fn, dvm_fuse_targets* h, const dvm_keyframe_store* st, int n_targets, const dvm_ft_target_resident* targets,
+                        const dvm_camera_model* models, const uint8_t* forms) {
+  if (!h || !st || n_targets < 0 || (n_targets > 0 && !targets)) return fail(fn, DVM_ERR_INVALID, "missing argument");
+  if (kfs_device(st) != h->device) return fail(fn, DVM_ERR_INVALID, "the store lives on another device than the handle");
+  std::vector<KfSlotView> views((size_t)n_targets);
+  int n_kb8 = 0;
+  for (int t = 0; t < n_targets; t++) {
+    const std::string w = "target " + std::to_string(t);
+    if (forms && forms[t] != DVM_FT_FORM_POINTS && forms[t] != DVM_FT_FORM_SCW) return fail(fn, DVM_ERR_INVALID, w + ": form outside {0, 1}");
+    if (models && models[t].model != dvm_cam::kPinhole && models[t].model != dvm_cam::kKannalaBrandt8)
+      return fail(fn, DVM_ERR_INVALID, w + ": camera model outside {0, 1}");
+    if (models && !dvm_cam::model_ok(models[t].model, models[t].p)) return fail(fn, DVM_ERR_INVALID, w + ": zero focal length of the camera model");
+    if (!kfs_slot_view(st, targets[t].slot, &views[t]))
+      return fail(fn, DVM_ERR_INVALID, w + ": slot " + std::to_string(targets[t].slot) + " outside the store, never written or removed");
+    if (!models && (!(views[t].fx != 0.0f) || !(views[t].fy != 0.0f))) return fail(fn, DVM_ERR_INVALID, w + ": zero focal length");
+    n_kb8 += models && models[t].model == dvm_cam::kKannalaBrandt8 ? 1 : 0;
+  }
+  if (n_targets > h->max_targets)
+    return fail(fn, DVM_ERR_CAPACITY, "beyond the reservation (dvm_fuse_targets_reserve): " + std::to_string(n_targets) + " targets");
+  h->n_targets = n_targets;
+  h->store = nullptr; h->slot_gen.clear(); h->set_bytes = 0;
+  if (n_targets == 0) return DVM_OK;
+  DVM_HIP(hipSetDevice(h->device));
+  DVM_HIP(hipStreamSynchronize(h->s));           // the staging region may still feed the copy of an earlier set (idle after a run: free)
+
+  const WorkingSet& ws = h->ws;
+  Cursor64 up{ws.hm, ws.d};
+  FtTargetDev* tab = up.carve<FtTargetDev>((size_t)n_targets);
+  int32_t* order = up.carve<int32_t>((size_t)n_targets);         // the pinhole targets' indices, then the KannalaBrandt8 targets'
+  h->order = rebase(order, ws.hm, ws.d);
+  h->n_kb8 = n_kb8; h->n_pinhole = n_targets - n_kb8;
+  for (int t = 0, at0 = 0, at1 = h->n_pinhole; t < n_targets; t++) {
+    const dvm_ft_target_resident& k = targets[t];
+    const KfSlotView& V = views[t];
+    FtTargetDev& D = tab[t];
+    std::memset(&D, 0, sizeof(D));
+    const bool kb8 = models && models[t].model == dvm_cam::kKannalaBrandt8;
+    order[kb8 ? at1++ : at0++] = t;
+    D.model = kb8 ? dvm_cam::kKannalaBrandt8 : dvm_cam::kPinhole;
+    if (kb8) std::memcpy(D.kb8, models[t].p, sizeof(D.kb8));
+    D.kps = V.kps; D.desc = V.desc; D.sf = V.sf;
+    D.inv_sigma2 = forms && forms[t] == DVM_FT_FORM_SCW ? nullptr : V.inv_sigma2;   // (null: project_row skips the gate)
+    D.n = V.n;
+    D.F = V.F;
+    ProjectCam& C = D.C;
+    std::memcpy(C.q, k.Tcw.q, 16); std::memcpy(C.t, k.Tcw.t, 12); std::memcpy(C.Ow, k.Ow, 12);
+    if (models) { C.fx = models[t].p[0]; C.fy = models[t].p[1]; C.cx = models[t].p[2]; C.cy = models[t].p[3]; }   // (a given model replaces the slot's own)
+    else { C.fx = V.fx; C.fy = V.fy; C.cx = V.cx; C.cy = V.cy; }
+    C.min_x = V.min_x; C.max_x = V.max_x; C.min_y = V.min_y; C.max_y = V.max_y;
+    C.log_scale_factor = V.log_scale_factor; C.n_levels = V.n_levels; C.sim3_pair = 0;
+    h->slot_gen.emplace_back(k.slot, V.gen);
+  }
+  if (up.used() > h->tgt_bytes) return fail(fn, DVM_ERR_STATE, "the target table exceeds the reserved region");   // (an internal error)
+  DVM_HIP(hipMemcpyAsync(ws.d, ws.hm, up.used(), hipMemcpyHostToDevice, h->s));
+  h->set_bytes = (int64_t)up.used();
+  h->store = st;
+  h->build_timed = 0; h->last_ms[0] = 0;         // (no grid was built)
+  return DVM_OK;
 }
 
 // what a run returns: the dense rows (dvm_fuse_targets_run: best_idx, best_dist) or the hits (dvm_fuse_targets_run_hits: the rest)
@@ -220,6 +299,9 @@ struct FtResult {
 static int run_points(const char* fn, dvm_fuse_targets* h, const dvm_ft_points* P, const uint8_t* skip, float th, const FtResult& out) {
   if (!h || !P) return fail(fn, DVM_ERR_INVALID, "missing argument");
   if (h->n_targets < 0) return fail(fn, DVM_ERR_INVALID, "no targets (dvm_fuse_targets_set comes first)");
+  if (h->store)                                 // a resident set: its slots still hold the keyframes it was made on
+    for (const auto& sg : h->slot_gen)
+      if (kfs_generation(h->store, sg.first) != sg.second) return fail(fn, DVM_ERR_STATE, "a target's slot was written since the set");
   if (P->n < 0) return fail(fn, DVM_ERR_INVALID, "negative point count");
   if (P->n > h->max_points) return fail(fn, DVM_ERR_CAPACITY, "beyond the reservation (dvm_fuse_targets_reserve): " + std::to_string(P->n) + " points");
   const int T = h->n_targets, n = P->n;
@@ -263,10 +345,13 @@ static int run_points(const char* fn, dvm_fuse_targets* h, const dvm_ft_points* 
   const int cap = out.want_hits ? std::min(out.hit_cap, h->max_hits) : 0;
 
   DVM_HIP(hipMemcpyAsync(dev, stage, up.used(), hipMemcpyHostToDevice, h->s));
+  h->run_bytes = (int64_t)up.used();
+  if (h->store) { const int rb = kfs_read_begin(h->store, h->s); if (rb != DVM_OK) return rb; }
   const EventTimer& tm = h->timer;
   DVM_HIP(tm.mark(2, h->s));
   launch_ft_search(h->s, reinterpret_cast<const FtTargetDev*>(ws.d), h->order, h->n_pinhole, h->n_kb8, A, th, d_idx, d_dist);
   DVM_HIP(tm.mark(3, h->s));
+  if (h->store) { const int re = kfs_read_end(h->store, h->s); if (re != DVM_OK) return re; }
   if (out.want_hits)
     launch_ft_hits(h->s, d_idx, d_dist, T, n, d_cnt, d_off, reinterpret_cast<int32_t*>(h->hit_dev), reinterpret_cast<FtHit*>(h->hit_dev + hit_at), cap);
   int rc = hip_check(hipGetLastError(), "dvm_fuse_targets_run launch");
@@ -300,6 +385,10 @@ int dvm_fuse_targets_set(dvm_fuse_targets* h, int n_targets, const dvm_ft_target
 }
 int dvm_fuse_targets_set_cam(dvm_fuse_targets* h, int n_targets, const dvm_ft_target* targets, const dvm_camera_model* models, const uint8_t* forms) {
   return set_targets("dvm_fuse_targets_set_cam", h, n_targets, targets, models, forms);
+}
+int dvm_fuse_targets_set_resident(dvm_fuse_targets* h, const dvm_keyframe_store* store, int n_targets, const dvm_ft_target_resident* targets,
+                                  const dvm_camera_model* models, const uint8_t* forms) {
+  return set_resident("dvm_fuse_targets_set_resident", h, store, n_targets, targets, models, forms);
 }
 int dvm_fuse_targets_run(dvm_fuse_targets* h, const dvm_ft_points* P, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist) {
   FtResult out;

@@ -3,6 +3,8 @@
 // The working set: a device block [packed upload][speculative results] and a mapped block [upload staging][results].  A call validates everything, packs both
 // keyframe sets back to back into the staging region, sends it with ONE copy, queues the three launches, synchronises ONCE and copies the
 // records out of the mapped block.  Host arithmetic here is index-free: the baseline test of each neighbour and the 3x4 pose matrices.
+// dvm_create_new_map_points_resident: the keyframes are slots of a dvm_keyframe_store (keyframe_store.h).  The same body runs with every
+// NpKfDev pointing into the store except mp, which is packed and sent as before; the launches are bracketed by kfs_read_begin / _end.
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -11,6 +13,7 @@
 
 #include "../../include/dvmslam_hip.h"
 #include "chain.h"
+#include "keyframe_store.h"
 #include "new_points_kernels.h"
 #include "orb_pipeline.h"
 #include "camera_model.h"
@@ -22,6 +25,7 @@ struct dvm_new_points : Chain {                 // ws: device block [up_bytes][s
   int max_n1 = 0, max_nb = 0, max_total = 0;
   size_t rec_cap = 0;                           // records the mapped block holds: max_nb * max_n1
   float last_ms[3] = {0, 0, 0};
+  int64_t up_bytes_last = 0;                    // host-to-device bytes queued by the last call that reached the device
 };
 
 namespace {
@@ -33,10 +37,16 @@ constexpr size_t kKfPerKeypoint = sizeof(dvm_keypoint_pod) + 32 + 4 * 4, kKfFixe
 
 int fail(int rc, const std::string& msg) { set_error("dvm_create_new_map_points: " + msg); return rc; }
 
-int check_keyframe(const dvm_np_keyframe& k, const char* who, int n_levels) {
+// view != null: the keyframe lives in a store slot -- its arrays, FeatureVector and tables were checked when it was put; mp travels
+int check_keyframe(const dvm_np_keyframe& k, const char* who, int n_levels, const KfSlotView* view = nullptr) {
   const std::string w(who);
   if (k.n < 0 || k.n > kFrameCap) return fail(DVM_ERR_INVALID, w + ": n outside [0, 8192]");
   if (k.n_levels != n_levels) return fail(DVM_ERR_INVALID, w + ": level tables of another length than the current keyframe's");
+  if (view) {
+    if (!(k.fx != 0.0f) || !(k.fy != 0.0f)) return fail(DVM_ERR_INVALID, w + ": zero focal length");
+    if (k.n > 0 && !k.mp) return fail(DVM_ERR_INVALID, w + ": missing keypoint array");
+    return DVM_OK;
+  }
   if (!k.scale_factors || !k.level_sigma2) return fail(DVM_ERR_INVALID, w + ": missing level table");
   if (!(k.fx != 0.0f) || !(k.fy != 0.0f)) return fail(DVM_ERR_INVALID, w + ": zero focal length");
   if (k.n > 0 && (!k.kps || !k.desc || !k.mp)) return fail(DVM_ERR_INVALID, w + ": missing keypoint array");
@@ -57,9 +67,18 @@ int check_keyframe(const dvm_np_keyframe& k, const char* who, int n_levels) {
   return DVM_OK;
 }
 
-// packs one keyframe at the cursor (staging block -> device block) and returns its device view
-NpKfDev pack_keyframe(const dvm_np_keyframe& k, Cursor64& c) {
+// packs one keyframe at the cursor (staging block -> device block) and returns its device view; of a keyframe in a store slot
+// (view != null) only mp is packed, the other arrays are the slot's
+NpKfDev pack_keyframe(const dvm_np_keyframe& k, Cursor64& c, const KfSlotView* view = nullptr) {
   NpKfDev v{};
+  if (view) {
+    v.kps = view->kps; v.desc = view->desc;
+    v.mp = reinterpret_cast<const int32_t*>(c.put(k.mp, (size_t)k.n * 4));
+    v.fv_node = view->fv_node; v.fv_off = view->fv_off; v.fv_feat = view->fv_feat;
+    v.sf = view->sf; v.sigma2 = view->sigma2;
+    v.n = k.n; v.fv_n = k.fv_n;
+    return v;
+  }
   const size_t n = (size_t)k.n, nf = k.fv_n > 0 ? (size_t)k.fv_off[k.fv_n] : 0;
   v.kps = reinterpret_cast<const dvm_keypoint_pod*>(c.put(k.kps, n * sizeof(dvm_keypoint_pod)));
   v.desc = c.put(k.desc, n * 32);
@@ -125,15 +144,23 @@ int dvm_new_points_last_kernel_ms(dvm_new_points* h, float* ms) {
   for (int i = 0; i < 3; i++) ms[i] = h->last_ms[i];
   return DVM_OK;
 }
+int dvm_new_points_last_upload_bytes(const dvm_new_points* h, int64_t* bytes) {
+  if (!h || !bytes) return DVM_ERR_INVALID;
+  *bytes = h->up_bytes_last;
+  return DVM_OK;
+}
 
 }  // extern "C"
 
 namespace {
 // dvm_create_new_map_points and dvm_create_new_map_points_cam: kb8 == false runs the pinhole kernels on the keyframes' intrinsics; otherwise
-// cur_model / nb_models / nb_poses (validated by the caller) go to the KannalaBrandt8 kernels
+// cur_model / nb_models / nb_poses (validated by the caller) go to the KannalaBrandt8 kernels.  store != null is
+// dvm_create_new_map_points_resident: cur_view / nb_views[j] are the keyframes' slots, and of cur / nbs[j].kf the array pointers other
+// than mp are not read (their counts, intrinsics and n_levels are the slots')
 int create_new_map_points_impl(dvm_new_points* h, const dvm_np_keyframe* cur, int n_neighbours, const dvm_np_neighbour* nbs, const dvm_np_params* p,
                                dvm_np_out* out, bool kb8, const dvm_camera_model* cur_model, const dvm_camera_model* nb_models,
-                               const dvm_pair_pose* nb_poses) {
+                               const dvm_pair_pose* nb_poses, const dvm_keyframe_store* store = nullptr, const KfSlotView* cur_view = nullptr,
+                               const KfSlotView* nb_views = nullptr) {
   static_assert(sizeof(dvm_keypoint) == sizeof(dvm_keypoint_pod), "layout");
   if (!h || !cur || !p || !out || n_neighbours < 0 || (n_neighbours > 0 && !nbs)) return fail(DVM_ERR_INVALID, "missing argument");
   if (p->monocular != 1) return fail(DVM_ERR_INVALID, "only monocular keyframes (the stereo branches are outside the accelerated path)");
@@ -141,11 +168,11 @@ int create_new_map_points_impl(dvm_new_points* h, const dvm_np_keyframe* cur, in
       (out->record_cap > 0 && (!out->pairs || !out->status || !out->x3D)))
     return fail(DVM_ERR_INVALID, "missing output array");
   if (cur->n_levels < 1 || cur->n_levels > 64) return fail(DVM_ERR_INVALID, "n_levels outside [1, 64]");
-  int rc = check_keyframe(*cur, "current keyframe", cur->n_levels);
+  int rc = check_keyframe(*cur, "current keyframe", cur->n_levels, cur_view);
   if (rc != DVM_OK) return rc;
   int64_t total = 0;
   for (int j = 0; j < n_neighbours; j++) {
-    rc = check_keyframe(nbs[j].kf, ("neighbour " + std::to_string(j)).c_str(), cur->n_levels);
+    rc = check_keyframe(nbs[j].kf, ("neighbour " + std::to_string(j)).c_str(), cur->n_levels, store ? &nb_views[j] : nullptr);
     if (rc != DVM_OK) return rc;
     total += nbs[j].kf.n;
   }
@@ -185,14 +212,14 @@ int create_new_map_points_impl(dvm_new_points* h, const dvm_np_keyframe* cur, in
   const size_t gk_off = up.used();
   TriGeomKB8* gk_stage = kb8 ? up.carve<TriGeomKB8>((size_t)nrun) : nullptr;
   NpArgs A{};
-  A.cur = pack_keyframe(*cur, up);
+  A.cur = pack_keyframe(*cur, up, cur_view);
   float T1w[12];
   pose_3x4(cur->Tcw, T1w);
   for (int r = 0; r < nrun; r++) {
     const dvm_np_neighbour& nb = nbs[run[r]];
     NpNbDev& D = nb_stage[r];
     std::memset(&D, 0, sizeof(D));
-    D.kf = pack_keyframe(nb.kf, up);
+    D.kf = pack_keyframe(nb.kf, up, store ? &nb_views[run[r]] : nullptr);
     TriPair& P = D.P;
     P.cos_parallax_max = p->cos_parallax_max;
     P.K1[0] = cur->fx; P.K1[1] = cur->fy; P.K1[2] = cur->cx; P.K1[3] = cur->cy;
@@ -213,7 +240,7 @@ int create_new_map_points_impl(dvm_new_points* h, const dvm_np_keyframe* cur, in
   }
   if (up.used() > ws.up_bytes) return fail(DVM_ERR_CAPACITY, "packed keyframes exceed the reserved upload region");   // (cannot happen: kKfPerKeypoint / kKfFixed bound every keyframe)
   A.nb = reinterpret_cast<const NpNbDev*>(ws.d);
-  A.nrun = nrun; A.n1 = n1; A.n1p = (int32_t)n1p; A.nfeat1 = cur->fv_n > 0 ? cur->fv_off[cur->fv_n] : 0;
+  A.nrun = nrun; A.n1 = n1; A.n1p = (int32_t)n1p; A.nfeat1 = cur_view ? cur_view->n_feat : cur->fv_n > 0 ? cur->fv_off[cur->fv_n] : 0;
   A.n_levels = cur->n_levels; A.check_ori = p->check_ori != 0;
   uint8_t* spec = ws.d + ws.up_bytes;
   A.best = reinterpret_cast<int32_t*>(spec);
@@ -231,7 +258,9 @@ int create_new_map_points_impl(dvm_new_points* h, const dvm_np_keyframe* cur, in
   A.h_new_point = ws.dev(r_new);
 
   DVM_HIP(hipMemcpyAsync(ws.d, ws.hm, up.used(), hipMemcpyHostToDevice, h->s));
+  h->up_bytes_last = (int64_t)up.used();
   DVM_HIP(hipMemsetAsync(A.best, 0xFF, (size_t)nrun * n1p * 4, h->s));
+  if (store) { rc = kfs_read_begin(store, h->s); if (rc != DVM_OK) return rc; }
   const EventTimer& tm = h->timer;
   DVM_HIP(tm.mark(0, h->s));
   if (kb8) {
@@ -249,6 +278,7 @@ int create_new_map_points_impl(dvm_new_points* h, const dvm_np_keyframe* cur, in
   DVM_HIP(tm.mark(2, h->s));
   launch_np_settle(h->s, A);
   DVM_HIP(tm.mark(3, h->s));
+  if (store) { rc = kfs_read_end(store, h->s); if (rc != DVM_OK) return rc; }
   rc = hip_check(hipGetLastError(), "dvm_create_new_map_points launch");
   const int rs = hip_check(hipStreamSynchronize(h->s), "dvm_create_new_map_points sync");
   if (rc != DVM_OK) return rc;
@@ -303,6 +333,49 @@ int dvm_create_new_map_points_cam(dvm_new_points* h, const dvm_np_keyframe* cur,
     nv[j].kf.fx = nb_models[j].p[0]; nv[j].kf.fy = nb_models[j].p[1]; nv[j].kf.cx = nb_models[j].p[2]; nv[j].kf.cy = nb_models[j].p[3];
   }
   return create_new_map_points_impl(h, &c, n_neighbours, nv.data(), p, out, kb8, cur_model, nb_models, nb_poses);
+}
+
+int dvm_create_new_map_points_resident(dvm_new_points* h, const dvm_keyframe_store* store, const dvm_np_keyframe_resident* cur,
+                                       const dvm_camera_model* cur_model, int n_neighbours, const dvm_np_neighbour_resident* nbs,
+                                       const dvm_camera_model* nb_models, const dvm_pair_pose* nb_poses, const dvm_np_params* p, dvm_np_out* out) {
+  if (!h || !store || !cur || !p || !out || n_neighbours < 0 || (n_neighbours > 0 && !nbs)) return fail(DVM_ERR_INVALID, "missing argument");
+  if (kfs_device(store) != h->device) return fail(DVM_ERR_INVALID, "the store lives on another device than the handle");
+  bool kb8 = false;
+  if (cur_model) {                               // the rules of dvm_create_new_map_points_cam
+    if (n_neighbours > 0 && !nb_models) return fail(DVM_ERR_INVALID, "NULL camera model");
+    if (!dvm_cam::model_ok(cur_model->model, cur_model->p)) return fail(DVM_ERR_INVALID, "current keyframe: unknown camera model or zero focal length");
+    for (int j = 0; j < n_neighbours; j++) {
+      if (!dvm_cam::model_ok(nb_models[j].model, nb_models[j].p))
+        return fail(DVM_ERR_INVALID, "neighbour " + std::to_string(j) + ": unknown camera model or zero focal length");
+      if (nb_models[j].model != cur_model->model)
+        return fail(DVM_ERR_INVALID, "neighbour " + std::to_string(j) + ": another camera model than the current keyframe's (a mixed pair is out of scope)");
+    }
+    kb8 = cur_model->model == dvm_cam::kKannalaBrandt8;
+    if (kb8 && n_neighbours > 0 && !nb_poses) return fail(DVM_ERR_INVALID, "missing relative poses");
+  }
+  // every slot's view, then the uploaded call's structs with the slots' counts and intrinsics (or the models' p[0..3]) and the per-call part
+  std::vector<KfSlotView> views((size_t)n_neighbours + 1);
+  auto keyframe_of = [&](const dvm_np_keyframe_resident& r, const dvm_camera_model* m, const std::string& w, KfSlotView* v, dvm_np_keyframe* k) {
+    if (!kfs_slot_view(store, r.slot, v)) return fail(DVM_ERR_INVALID, w + ": slot " + std::to_string(r.slot) + " outside the store, never written or removed");
+    std::memset(k, 0, sizeof(*k));
+    k->n = v->n; k->mp = r.mp; k->fv_n = v->fv_n;
+    k->Tcw = r.Tcw; k->Twc = r.Twc; std::memcpy(k->Ow, r.Ow, 12);
+    if (m) { k->fx = m->p[0]; k->fy = m->p[1]; k->cx = m->p[2]; k->cy = m->p[3]; }
+    else { k->fx = v->fx; k->fy = v->fy; k->cx = v->cx; k->cy = v->cy; }
+    k->n_levels = v->n_levels;
+    return (int)DVM_OK;
+  };
+  dvm_np_keyframe c;
+  int rc = keyframe_of(*cur, cur_model, "current keyframe", &views[0], &c);
+  if (rc != DVM_OK) return rc;
+  std::vector<dvm_np_neighbour> nv((size_t)n_neighbours);
+  for (int j = 0; j < n_neighbours; j++) {
+    rc = keyframe_of(nbs[j].kf, cur_model ? &nb_models[j] : nullptr, "neighbour " + std::to_string(j), &views[(size_t)j + 1], &nv[j].kf);
+    if (rc != DVM_OK) return rc;
+    nv[j].median_depth = nbs[j].median_depth;
+    std::memcpy(nv[j].ep, nbs[j].ep, sizeof(nv[j].ep)); std::memcpy(nv[j].F12, nbs[j].F12, sizeof(nv[j].F12));
+  }
+  return create_new_map_points_impl(h, &c, n_neighbours, nv.data(), p, out, kb8, cur_model, nb_models, nb_poses, store, &views[0], views.data() + 1);
 }
 
 }  // extern "C"

@@ -1086,6 +1086,104 @@ int dvm_map_store_capacity(const dvm_map_store* s);
 int dvm_map_store_update(dvm_map_store* s, int n, const int32_t* slots, const dvm_local_point* records);
 int dvm_map_store_read(dvm_map_store* s, int n, const int32_t* slots, dvm_local_point* out);
 
+/* ---- An agent's keyframes resident on the device (csrc/keyframe_store.cpp): the keyframe-side counterpart of dvm_map_store.  What a
+ * KeyFrame holds once ComputeBoW has run never changes -- mvKeysUn, mDescriptors, the level tables, the image bounds, mFeatVec and the
+ * feature grid --, LocalMapping names the same neighbours step after step and LoopClosing::SearchAndFuse the same hundred keyframes: the
+ * store keeps them, grid included, in device memory, and the LocalMapping chains read them by slot (dvm_fuse_targets_set_resident,
+ * dvm_create_new_map_points_resident below) instead of carrying 60 - 70 B per keypoint up and rebuilding every grid on every call.
+ * The pose and mvpMapPoints change between two LocalMapping steps and stay per-call arguments.
+ *   create    `capacity` slots of fixed size for up to `slot_keypoints` keypoints each (1 .. 8192), ONE device block that never moves:
+ *             a slot's device addresses are stable.  A slot holds the arrays as put, the three level tables, the FeatureVector and the
+ *             keyframe's grid (the layout: csrc/kf_store_layout.h).  DVM_ERR_INVALID for capacity < 1 or slot_keypoints outside
+ *             [1, 8192], DVM_ERR_CAPACITY when the memory cannot be had, DVM_ERR_NO_DEVICE without a GPU.
+ *   put       kfs[k] goes to slot slots[k].  Checked on the host before anything is queued, each failure naming the keyframe, nothing
+ *             written: DVM_ERR_CAPACITY -- n or fv_n beyond slot_keypoints; DVM_ERR_INVALID -- a slot outside [0, capacity) or named
+ *             twice in the call, n < 0, n_levels outside [1, 64], a keypoint's octave outside the level tables, empty image bounds,
+ *             fv_off not monotone from 0, more features than keypoints, a feature outside [0, n), nodes not ascending as unsigned, a
+ *             missing array (the three level tables are all required).  The batch is packed into a page-locked staging block, sent
+ *             with ONE copy and moved by ONE launch -- k_kfs_put, one 1 024-thread workgroup per keyframe, which also builds the grid
+ *             in the slot with the function dvm_frame_build and dvm_fuse_targets_set run, so a resident grid has the order a per-call
+ *             set produces.  On the STORE'S OWN STREAM; put does not wait.  A batch larger than the staging block goes in rounds.
+ *   remove    the slots are empty again (host state only).  A slot outside [0, capacity) or not written: DVM_ERR_INVALID, nothing changed.
+ *   Ordering is dvm_map_store's: every chain call that reads the store makes its stream wait for the store's last put, and a put
+ *   waits for the last kernel queued to read the store -- it never overtakes a reader in flight.
+ *   Every slot carries a written flag and a generation counter (put and remove bump it).  A chain call that names a slot never
+ *   written, or removed, is DVM_ERR_INVALID, checked on the host before anything is queued.
+ *   debug_read  one slot back, synchronous (tests): the counts and scalars always, every array whose pointer is not NULL -- kps, desc
+ *             [n], fv_node [fv_n], fv_off [fv_n + 1, when fv_n > 0], fv_feat [n_feat], the level tables [n_levels], the grid: skp [n_sorted][4]
+ *             (x, y, octave bits, cell bits), sidx [n_sorted], sdesc [n_sorted][32], cell_start [3076].  Buffers sized for slot_keypoints
+ *             (64 for the tables) hold any slot.
+ * Calls on ONE store are not concurrent; a store outlives every chain handle set on it.  sizeof(dvm_kfs_keyframe) == 120,
+ * sizeof(dvm_kfs_readback) == 160 (LP64). */
+typedef struct {                       /* what is immutable in a KeyFrame once ComputeBoW has run */
+  int32_t n;
+  const dvm_keypoint* kps;             /* mvKeysUn */
+  const uint8_t* desc;                 /* mDescriptors, n x 32 */
+  int32_t fv_n;                        /* mFeatVec, dvm_np_keyframe's convention; fv_n = 0 is legal */
+  const int32_t *fv_node, *fv_off, *fv_feat;
+  float fx, fy, cx, cy, min_x, max_x, min_y, max_y;
+  const float *scale_factors, *level_sigma2, *inv_level_sigma2;   /* [n_levels] each */
+  float log_scale_factor;
+  int32_t n_levels;
+} dvm_kfs_keyframe;
+typedef struct {
+  int32_t n, fv_n, n_feat, n_levels, n_sorted, n_total;
+  float fx, fy, cx, cy, min_x, max_x, min_y, max_y, log_scale_factor;
+  uint32_t generation;
+  dvm_keypoint* kps;
+  uint8_t* desc;
+  int32_t *fv_node, *fv_off, *fv_feat;
+  float *scale_factors, *level_sigma2, *inv_level_sigma2;
+  float* skp;
+  int32_t* sidx;
+  uint8_t* sdesc;
+  int32_t* cell_start;
+} dvm_kfs_readback;
+typedef struct dvm_keyframe_store dvm_keyframe_store;
+int dvm_keyframe_store_create(int device, int capacity, int slot_keypoints, dvm_keyframe_store** out);
+void dvm_keyframe_store_destroy(dvm_keyframe_store* s);
+int dvm_keyframe_store_capacity(const dvm_keyframe_store* s);
+int dvm_keyframe_store_slot_keypoints(const dvm_keyframe_store* s);
+int dvm_keyframe_store_put(dvm_keyframe_store* s, int n, const int32_t* slots, const dvm_kfs_keyframe* kfs);
+int dvm_keyframe_store_remove(dvm_keyframe_store* s, int n, const int32_t* slots);
+int dvm_keyframe_store_debug_read(dvm_keyframe_store* s, int slot, dvm_kfs_readback* out);
+
+/* ---- The Fuse chain on resident targets: dvm_fuse_targets_set_cam with every target given as a store slot plus what changes between
+ * two LocalMapping steps, its pose.  The host fills the target table with pointers into the store and uploads that table alone: no
+ * keypoint travels, no grid is built, no per-keypoint host loop runs.  dvm_fuse_targets_run / _run_hits are then used as they are.
+ *   models  [n_targets] or NULL: the slots' own fx, fy, cx, cy (a zero one is DVM_ERR_INVALID); forms [n_targets] or NULL: as set_cam.
+ *   A slot may appear in several targets of one set (rows are independent).  The set needs max_targets of dvm_fuse_targets_reserve
+ *   only: max_total_target_keypoints may be 0.
+ * Contract: for the same keyframes a run's rows equal dvm_fuse_targets_set_cam + run bit for bit -- both forms, both model types, mixed
+ * targets, masks, run_hits: the search kernels read the same arrays in the same order.
+ * The set records every named slot's generation: a run after one of them was put or removed is DVM_ERR_STATE ("a target's slot was
+ * written since the set"), checked on the host; the handle stays usable -- set again.  A put to a slot the set does not name leaves it
+ * valid.  A store on another device, a slot outside the store, never written or removed: DVM_ERR_INVALID before anything is queued. */
+typedef struct { int32_t slot; dvm_se3f Tcw; float Ow[3]; } dvm_ft_target_resident;   /* 44 bytes */
+int dvm_fuse_targets_set_resident(dvm_fuse_targets* h, const dvm_keyframe_store* store, int n_targets, const dvm_ft_target_resident* targets,
+                                  const dvm_camera_model* models /* [n_targets], or NULL: the slots' fx, fy, cx, cy */,
+                                  const uint8_t* forms /* [n_targets], or NULL: all DVM_FT_FORM_POINTS */);
+/* The host-to-device bytes queued by the last set (uploaded or resident) and the last run; either pointer may be NULL. */
+int dvm_fuse_targets_last_upload_bytes(const dvm_fuse_targets* h, int64_t* set_bytes, int64_t* run_bytes);
+
+/* ---- CreateNewMapPoints on resident keyframes: dvm_create_new_map_points[_cam] with every keyframe given as a store slot plus its
+ * per-call part -- mvpMapPoints (LocalMapping changes it between any two calls; 4 B per keypoint against about 70) and the pose.
+ * Keypoints, descriptors, FeatureVector and level tables are read in the slots; the kernels are the uploaded call's.
+ *   cur_model NULL: the pinhole chain on the slots' fx, fy, cx, cy (nb_models, nb_poses not read); otherwise the rules of
+ *   dvm_create_new_map_points_cam.  The current keyframe's and the neighbours' slots are distinct keyframes (the precondition above).
+ * Contract: the records equal dvm_create_new_map_points[_cam] on the same keyframes bit for bit; the reservation (its keypoint total
+ * included), the baseline skip and the error rules are that call's own.  A keyframe put with fv_n = 0 is legal as cur or neighbour and
+ * finds nothing, as a dvm_np_keyframe with fv_n = 0 does.  A slot outside the store, never written or removed, a NULL mp where the
+ * slot holds keypoints, or a store on another device: DVM_ERR_INVALID before anything is queued. */
+typedef struct { int32_t slot; const int32_t* mp; dvm_se3f Tcw, Twc; float Ow[3]; } dvm_np_keyframe_resident;   /* 88 bytes */
+typedef struct { dvm_np_keyframe_resident kf; float median_depth; float ep[2], F12[9]; } dvm_np_neighbour_resident;   /* 136 bytes */
+int dvm_create_new_map_points_resident(dvm_new_points* h, const dvm_keyframe_store* store, const dvm_np_keyframe_resident* cur,
+                                       const dvm_camera_model* cur_model /* NULL: pinhole from the slots */, int n_neighbours,
+                                       const dvm_np_neighbour_resident* nbs, const dvm_camera_model* nb_models, const dvm_pair_pose* nb_poses,
+                                       const dvm_np_params* p, dvm_np_out* out);
+/* The host-to-device bytes queued by the last call that reached the device, resident or not. */
+int dvm_new_points_last_upload_bytes(const dvm_new_points* h, int64_t* bytes);
+
 /* ---- The first half reading a store: dvm_track_finish_batch with the projection queries built ON THE DEVICE (k_track_queries) from
  * LastFrame's entry list -- the loop header of ORBmatcher.cc:1573-1611, what dvmh_track_with_motion_model builds on the host: x3Dc = Tcw *
  * pos (Sophus' quaternion form), invzc = (float)(1.0 / z) with invzc < 0 skipped, the projection through the tracker's camera model, the
