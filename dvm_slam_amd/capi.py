@@ -1257,6 +1257,8 @@ _TRACK_API = {            # libdvmslam_hip.so (include/dvmslam_hip.h)
     "dvm_track_local_map_batch_resident": [_P, _P, _I, _P, _P, _P, _P],
     "dvm_track_reference_keyframe": [_P] * 7,
     "dvm_track_reference_keyframe_batch": [_P, _P, _P, _I, _P, _P, _P, _P, _P],
+    "dvm_track_reference_keyframe_batch_resident": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    "dvm_tracker_last_refkf_upload_bytes": [_P, _P],
 }
 _TRACK_HOST_API = {       # libdvmslam_host.so (include/dvmslam_host.h); the _cam forms take the model behind K
     "dvmh_track_with_motion_model": _TRACK_ONE,
@@ -1270,7 +1272,9 @@ _TRACK_HOST_API = {       # libdvmslam_host.so (include/dvmslam_host.h); the _ca
 
 def _declare(L, api):
     for name, argtypes in api.items():
-        f = getattr(L, name)
+        f = getattr(L, name, None)
+        if f is None:       # an older library (DVM_HIP_LIB, the measurement tools' baseline): calling the entry raises AttributeError
+            continue
         f.restype = None if name.endswith("_destroy") else C.c_int32
         f.argtypes = argtypes
 
@@ -1448,6 +1452,44 @@ class _TrackerBase:
         a, b = C.c_int64(0), C.c_int64(0)
         check(self.L.dvm_tracker_last_upload_bytes(self.t, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def last_refkf_upload_bytes(self):
+        """dvm_tracker_last_refkf_upload_bytes: host-to-device bytes of the last reference-keyframe call that reached the device."""
+        a = C.c_int64(0)
+        check(self.L.dvm_tracker_last_refkf_upload_bytes(self.t, C.byref(a)))
+        return a.value
+
+    def _refkf_batch(self, voc, kfs, store, poses_last, K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup):
+        """Both batched reference-keyframe calls.  store None: kfs[b] a keyframe dict (uploaded); else the KeyframeStore and kfs[b] a
+        (slot, MapStore or None, mp_slots) tuple; None: the frame does not run."""
+        count = len(kfs)
+        assert len(poses_last) == count
+        kfp = (C.POINTER(RefKeyframe if store is None else KfResident) * count)(); prs = (TrackRefKfParams * count)(); outs = (TrackRefKfOut * count)()
+        res = (TrackRefKfResult * count)(); status = np.zeros(count, np.int32)
+        keep = []
+        for b in range(count):
+            if kfs[b] is None:
+                keep.append(None)
+                continue
+            if store is None:
+                rk, ka = _ref_keyframe(kfs[b])
+            else:
+                rk, ka = KfResident(), []
+                _kf_resident(kfs[b], rk, ka)
+            pr, s2 = _refkf_params(poses_last[b], K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
+            o, arrs = _refkf_out(self.ext.cap)
+            kfp[b] = C.pointer(rk); prs[b] = pr; outs[b] = o
+            keep.append((rk, ka, s2, arrs))
+        if store is None:
+            check(self.L.dvm_track_reference_keyframe_batch(self.t, self.ext.h, voc.h, count, kfp, prs, outs, res, _p(status)))
+        else:
+            check(self.L.dvm_track_reference_keyframe_batch_resident(self.t, self.ext.h, voc.h, store.h, count, kfp, prs, outs, res, _p(status)))
+        out = []
+        for b in range(count):
+            d = self._refkf_result(res[b], None if keep[b] is None else keep[b][3])
+            d["status"] = int(status[b])
+            out.append(d)
+        return out
 
     # ---- the first half
     def _track_arrays(self, B):
@@ -1650,6 +1692,19 @@ class Tracker(_TrackerBase):
         return out
 
 
+    def reserve_reference_keyframe_batch(self, total):
+        """dvm_tracker_reserve_reference_keyframe_batch on the single-frame tracker: the working set track_reference_keyframe_resident runs on."""
+        check(self.L.dvm_tracker_reserve_reference_keyframe_batch(self.t, int(total)))
+
+    def track_reference_keyframe_resident(self, voc, store, kf, pose_last, K, inv_sigma2, nnratio=0.7, check_ori=True, th_low=50, min_matches=15,
+                                          min_map=10, levelsup=4, model=None):
+        """dvm_track_reference_keyframe_batch_resident for the one frame of the last track() (form (b) of track_reference_keyframe: the motion
+        model failed): the reference keyframe as (slot, MapStore or None, mp_slots) of `store` (a KeyframeStore).  Needs
+        reserve_reference_keyframe_batch.  Returns what track_reference_keyframe returns in form (b), mp / dropped as map-store slots."""
+        K = _need_K(K, model)
+        return self._refkf_batch(voc, [kf], store, [pose_last], K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)[0]
+
+
 class TrackerBatch(_TrackerBase):
     """dvm_tracker_create_batch + dvmh_track_with_motion_model_batch: the tracked frames of up to max_frames agents as ONE chain of batched
     launches.  ext: an OrbExtractor with max_batch >= max_frames."""
@@ -1705,27 +1760,14 @@ class TrackerBatch(_TrackerBase):
         poses_last [count]: mLastFrame.GetPose() as 7 floats (qx, qy, qz, qw, t), read where kfs[b] is not None.  Returns one dict per frame:
         status (the chain's for a frame that ran, else the first half's: zero counters, no arrays) and, for a frame that ran, what
         Tracker.track_reference_keyframe returns in form (b)."""
-        count = len(kfs)
-        assert len(poses_last) == count
-        kfp = (C.POINTER(RefKeyframe) * count)(); prs = (TrackRefKfParams * count)(); outs = (TrackRefKfOut * count)()
-        res = (TrackRefKfResult * count)(); status = np.zeros(count, np.int32)
-        keep = []
-        for b in range(count):
-            if kfs[b] is None:
-                keep.append(None)
-                continue
-            rk, ka = _ref_keyframe(kfs[b])
-            pr, s2 = _refkf_params(poses_last[b], K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
-            o, arrs = _refkf_out(self.ext.cap)
-            kfp[b] = C.pointer(rk); prs[b] = pr; outs[b] = o
-            keep.append((rk, ka, s2, arrs))
-        check(self.L.dvm_track_reference_keyframe_batch(self.t, self.ext.h, voc.h, count, kfp, prs, outs, res, _p(status)))
-        out = []
-        for b in range(count):
-            d = self._refkf_result(res[b], None if keep[b] is None else keep[b][3])
-            d["status"] = int(status[b])
-            out.append(d)
-        return out
+        return self._refkf_batch(voc, kfs, None, poses_last, K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
+
+    def track_reference_keyframe_resident(self, voc, store, kfs, poses_last, K, inv_sigma2, nnratio=0.7, check_ori=True, th_low=50, min_matches=15,
+                                          min_map=10, levelsup=4):
+        """dvm_track_reference_keyframe_batch_resident: track_reference_keyframe with every reference keyframe given as a slot of `store` (a
+        KeyframeStore): kfs [count]: (slot, MapStore or None, mp_slots), or None for a frame that does not run.  Returns what
+        track_reference_keyframe returns, mp / dropped as map-store slots."""
+        return self._refkf_batch(voc, kfs, store, poses_last, K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
 
 
 # ---- an agent's map points resident on the device (dvm_map_store, include/dvmslam_hip.h), read by the two tracked-frame halves above
@@ -3130,6 +3172,20 @@ class _BtKeyFrame(C.Structure):   # == dvm_bt_keyframe
                 ("fv_node", C.c_void_p), ("fv_off", C.c_void_p), ("fv_feat", C.c_void_p)]
 
 
+class KfResident(C.Structure):   # == dvm_kf_resident
+    _fields_ = [("slot", C.c_int32), ("points", C.c_void_p), ("mp_slot", C.c_void_p)]
+
+
+def _kf_resident(kf, s, keep):
+    """(slot, MapStore or None, mp_slots or None) -> dvm_kf_resident s; the slot list is kept alive in keep."""
+    slot, store, mp = kf
+    a = None if mp is None else np.ascontiguousarray(mp, np.int32)
+    keep.append((store, a))
+    s.slot = int(slot)
+    s.points = None if store is None else store.h
+    s.mp_slot = None if a is None else a.ctypes.data
+
+
 class BowTargets(_Chain):
     """dvm_bow_targets: SearchByBoW(cur, target) (ORBmatcher.cc:709-834) for all target keyframes behind one upload and one synchronisation."""
 
@@ -3137,6 +3193,8 @@ class BowTargets(_Chain):
         super().__init__("dvm_bow_targets", 2, device)
         vp = C.c_void_p
         self.L.dvm_search_by_bow_targets.argtypes = [vp, vp, C.c_int32, vp, C.c_float, C.c_int32, vp, vp]
+        _declare(self.L, {"dvm_search_by_bow_targets_resident": [vp, vp, vp, C.c_int32, vp, C.c_float, C.c_int32, vp, vp],
+                          "dvm_bow_targets_last_upload_bytes": [vp, vp], "dvm_bow_targets_last_prologue_ms": [vp, vp]})
 
     def reserve(self, max_cur_keypoints, max_targets, max_total_target_keypoints):
         self._reserve(max_cur_keypoints, max_targets, max_total_target_keypoints)
@@ -3182,6 +3240,44 @@ class BowTargets(_Chain):
     def search(self, cur, targets, nnratio=0.9, check_ori=True):
         """cur / targets: keyframe dicts (kps, desc, mp[, bad], fv).  Returns (match_idx2[T, n], nmatches[T])."""
         return self.prepare(cur, targets, nnratio, check_ori)()
+
+
+    def prepare_resident(self, store, cur, targets, nnratio=0.9, check_ori=True):
+        """prepare() for search_resident: the slot lists are read in place at run()."""
+        keep = []
+        c = KfResident()
+        _kf_resident(cur, c, keep)
+        T = len(targets)
+        arr = (KfResident * max(T, 1))()
+        for t, kf in enumerate(targets):
+            _kf_resident(kf, arr[t], keep)
+        n1 = 0 if keep[0][1] is None else len(keep[0][1])
+        idx = np.full((T, n1), -7, np.int32); nm = np.full(T, -7, np.int32)
+
+        def run():
+            keep  # noqa: B018 (the arrays live as long as the closure)
+            check(self.L.dvm_search_by_bow_targets_resident(self.h, store.h, C.addressof(c), T, C.addressof(arr), float(nnratio), int(check_ori),
+                                                            idx.ctypes.data, nm.ctypes.data))
+            return idx, nm
+        return run
+
+    def search_resident(self, store, cur, targets, nnratio=0.9, check_ori=True):
+        """dvm_search_by_bow_targets_resident.  store: the KeyframeStore; cur / targets: (slot, MapStore or None, mp_slots) -- the keyframe's
+        slot, the map its points live in and GetMapPointMatches() as that map's slots (-1 = none; as long as the slot's keyframe).
+        Returns what search() returns."""
+        return self.prepare_resident(store, cur, targets, nnratio, check_ori)()
+
+    def last_upload_bytes(self):
+        """dvm_bow_targets_last_upload_bytes: host-to-device bytes of the last call that reached the device, either form."""
+        b = C.c_int64(0)
+        check(self.L.dvm_bow_targets_last_upload_bytes(self.h, C.byref(b)))
+        return b.value
+
+    def last_prologue_ms(self):
+        """The prologue kernel's milliseconds of the last resident call that ran with profiling on."""
+        ms = C.c_float(0)
+        check(self.L.dvm_bow_targets_last_prologue_ms(self.h, C.byref(ms)))
+        return ms.value
 
 
 def search_by_bow_targets(KF1, kfs, nnratio=0.9, check_ori=True, device=0, want_idx2=True):

@@ -22,4 +22,20 @@ void launch_bt_search(hipStream_t s, const BtKfDev* tab, int n_targets, int n1, 
 void launch_bt_settle(hipStream_t s, const BtKfDev* tab, int n_targets, int n1, int check_ori, int32_t* match, const int8_t* bin, const int32_t* cnt,
                       int32_t* nmatches);
 
+// ---- the resident call (dvm_search_by_bow_targets_resident): desc and the FeatureVector of a table entry point into a keyframe-store
+// slot; angle and use point into the handle's device block, which nothing uploads -- k_bt_prologue writes them.  What it reads per entry:
+struct BtProKf {
+  const uint8_t* recs;           // the keyframe's map store: [capacity] records of 72 bytes (dvm_local_point); not read when every mp_slot < 0
+  const int32_t* mp_slot;        // [n] uploaded, the list rounded up to 64 bytes: GetMapPointMatches() as slots of recs, -1 = none
+  const uint8_t* kps;            // the slot's keypoint records, [n] of 28 bytes (dvm_keypoint)
+  uint64_t reserved;
+};                               // 32 bytes
+constexpr int kBtProThreads = 256;                   // k_bt_prologue's workgroup
+constexpr int kBtProSpan = kBtProThreads * 4;        // keypoints of one workgroup, four per thread
+// ONE launch: for every entry k of tab [n_kf] (the current keyframe and the targets) use[i] = mp_slot[i] >= 0 && !record.bad and
+// angle[i] = kps[i].angle, written through tab[k].use / tab[k].angle; match [n_match] = -1; cnt [n_cnt] = 0.  n_max: the largest n of tab.
+// match and cnt at multiples of 16 bytes, n_cnt a multiple of 4; the host has checked every slot of every list.
+void launch_bt_prologue(hipStream_t s, const BtKfDev* tab, const BtProKf* pro, int n_kf, int n_max, int32_t* match, int64_t n_match, int32_t* cnt,
+                        int n_cnt);
+
 }  // namespace dvm

@@ -1,9 +1,12 @@
 // dvm_slam_amd/csrc/bow_targets_kernels.hip -- ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (ORBmatcher.cc:709-834) of one current
 // keyframe against many target keyframes: the searches LoopClosing::DetectCommonRegionsFromBoW runs per candidate and covisible
 // (LoopClosing.cc:722-731), all in one launch plus one launch for the rotation checks.
+#include <algorithm>
+
 #include "bow_targets_kernels.h"
 #include "match_device.h"
 #include "rot_bin.h"
+#include "track_kernels.h"   // LocalPointPod, dvm_keypoint_pod
 
 namespace dvm {
 
@@ -101,6 +104,49 @@ __global__ void __launch_bounds__(256) k_bt_settle(const BtKfDev* __restrict__ t
   block_sum4_put(nd, s_nd);
   __syncthreads();
   if (tid == 0) nmatches[t] = cnt[t * kBtCnt + 30] - block_sum4(s_nd);
+}
+
+// the resident call's prologue: what the uploaded call packs on the host, derived on the device from the keyframe-store slots and the
+// map stores.  blockIdx.x = table entry (the current keyframe, the targets), blockIdx.y walks its keypoints, kBtProSpan to a workgroup:
+// a thread takes four consecutive keypoints -- ONE 16-byte load of their map-point slots, four gathers of record.bad (72-byte records) and
+// of the keypoint's angle (28-byte records), ONE 16-byte store of the angles and ONE 4-byte store of the flags.  The slot list, the angle
+// and the flag array each begin at a multiple of 64 bytes and are rounded up to one, so the last thread's vector stays inside its item;
+// what it writes past n is zero and nothing reads it.  Then all workgroups together fill the match rows with -1 (a feature of the
+// current keyframe that no node lists keeps it: k_bt_search writes the listed ones only) and zero the counters, 16 bytes a thread.  No
+// LDS, no barrier; four waves of 64.
+__global__ void __launch_bounds__(kBtProThreads) k_bt_prologue(const BtKfDev* __restrict__ tab, const BtProKf* __restrict__ pro,
+                                                               int32_t* __restrict__ match, int64_t n_match, int32_t* __restrict__ cnt, int n_cnt) {
+  const BtKfDev K = tab[blockIdx.x];
+  const BtProKf P = pro[blockIdx.x];
+  const int i0 = ((int)blockIdx.y * kBtProThreads + (int)threadIdx.x) * 4;
+  if (i0 < K.n) {
+    const int4 sl = *reinterpret_cast<const int4*>(P.mp_slot + i0);
+    const int slot[4] = {sl.x, sl.y, sl.z, sl.w};
+    float a[4];
+    uint32_t use = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const bool in = i0 + j < K.n;
+      a[j] = in ? reinterpret_cast<const dvm_keypoint_pod*>(P.kps)[i0 + j].angle : 0.0f;
+      if (in && slot[j] >= 0 && reinterpret_cast<const LocalPointPod*>(P.recs)[slot[j]].bad == 0) use |= 1u << (8 * j);   // pMP && !pMP->isBad()
+    }
+    *reinterpret_cast<float4*>(const_cast<float*>(K.angle) + i0) = make_float4(a[0], a[1], a[2], a[3]);
+    *reinterpret_cast<uint32_t*>(const_cast<uint8_t*>(K.use) + i0) = use;
+  }
+  const int64_t stride = (int64_t)gridDim.x * gridDim.y * kBtProThreads;
+  const int64_t me = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * kBtProThreads + threadIdx.x;
+  const int64_t m16 = n_match >> 2;
+  for (int64_t i = me; i < m16; i += stride) reinterpret_cast<int4*>(match)[i] = make_int4(-1, -1, -1, -1);
+  for (int64_t i = m16 * 4 + me; i < n_match; i += stride) match[i] = -1;
+  for (int64_t i = me; i < (n_cnt >> 2); i += stride) reinterpret_cast<int4*>(cnt)[i] = make_int4(0, 0, 0, 0);
+}
+
+void launch_bt_prologue(hipStream_t s, const BtKfDev* tab, const BtProKf* pro, int n_kf, int n_max, int32_t* match, int64_t n_match, int32_t* cnt,
+                        int n_cnt) {
+  static_assert(sizeof(LocalPointPod) == 72 && sizeof(dvm_keypoint_pod) == 28 && sizeof(BtProKf) == 32, "what BtProKf's comments state");
+  if (n_kf < 1) return;
+  const unsigned by = (unsigned)std::max(1, (n_max + kBtProSpan - 1) / kBtProSpan);
+  hipLaunchKernelGGL(k_bt_prologue, dim3((unsigned)n_kf, by), dim3(kBtProThreads), 0, s, tab, pro, match, n_match, cnt, n_cnt);
 }
 
 void launch_bt_search(hipStream_t s, const BtKfDev* tab, int n_targets, int n1, int fv_n1, float nnratio, int32_t* match, int8_t* bin, int32_t* cnt) {

@@ -21,6 +21,7 @@
 
 #include "../../include/dvmslam_hip.h"
 #include "chain.h"
+#include "fv_once.h"
 #include "keyframe_store.h"
 
 using namespace dvm;
@@ -29,6 +30,7 @@ namespace {
 constexpr int kStageKeyframes = 32;              // keyframes of the largest size one round holds (smaller ones: more)
 struct SlotMeta {
   uint8_t written = 0;
+  uint8_t fv_once = 0;                             // the FeatureVector lists every feature at most once (fv_once.h): what the BoW-targets search needs
   uint32_t gen = 0;
   int32_t n = 0, fv_n = 0, n_feat = 0, n_levels = 0;
   float fx = 0, fy = 0, cx = 0, cy = 0, min_x = 0, max_x = 0, min_y = 0, max_y = 0, log_scale_factor = 0;
@@ -47,6 +49,7 @@ struct dvm_keyframe_store {
   bool write_pending = false, read_pending = false;
   std::vector<SlotMeta> meta;
   std::vector<uint32_t> stamp; uint32_t call = 0;  // per slot: the put call that named it last (a slot named twice in one call)
+  std::vector<uint8_t> seen;                       // [K] scratch of the listed-once scan
   uint8_t* slot_base(int32_t sl) const { return d + (size_t)sl * L.stride; }
   // the staging block is the host's again: the last round's copy has read it
   int staging_free() {
@@ -85,7 +88,7 @@ bool kfs_slot_view(const dvm_keyframe_store* st, int32_t slot, KfSlotView* v) {
   v->n = m.n; v->fv_n = m.fv_n; v->n_feat = m.n_feat; v->n_levels = m.n_levels;
   v->fx = m.fx; v->fy = m.fy; v->cx = m.cx; v->cy = m.cy;
   v->min_x = m.min_x; v->max_x = m.max_x; v->min_y = m.min_y; v->max_y = m.max_y; v->log_scale_factor = m.log_scale_factor;
-  v->gen = m.gen;
+  v->gen = m.gen; v->fv_once = m.fv_once != 0;
   return true;
 }
 uint32_t kfs_generation(const dvm_keyframe_store* st, int32_t slot) { return (uint32_t)slot < (uint32_t)st->capacity ? st->meta[slot].gen : 0u; }
@@ -168,7 +171,7 @@ int dvm_keyframe_store_create(int device, int capacity, int slot_keypoints, dvm_
     dvm_keyframe_store_destroy(st);
     return fail(fn, DVM_ERR_HIP, "stream, events or clearing the slots");
   }
-  st->meta.assign(C, SlotMeta()); st->stamp.assign(C, 0);
+  st->meta.assign(C, SlotMeta()); st->stamp.assign(C, 0); st->seen.assign((size_t)slot_keypoints, 0);
   *out = st;
   return DVM_OK;
 }
@@ -246,6 +249,8 @@ int dvm_keyframe_store_put(dvm_keyframe_store* st, int n, const int32_t* slots, 
       SlotMeta& M = st->meta[slots[k]];
       M.written = 1; M.gen++;
       M.n = f.n; M.fv_n = f.fv_n; M.n_feat = f.fv_n > 0 ? f.fv_off[f.fv_n] : 0; M.n_levels = f.n_levels;
+      // put accepts a feature listed in two nodes (Fuse and CreateNewMapPoints do not mind); the slot remembers it for the chain that does
+      M.fv_once = fv_first_repeat(f.fv_feat, M.n_feat, f.n, st->seen.data()) < 0;
       M.fx = f.fx; M.fy = f.fy; M.cx = f.cx; M.cy = f.cy;
       M.min_x = f.min_x; M.max_x = f.max_x; M.min_y = f.min_y; M.max_y = f.max_y; M.log_scale_factor = f.log_scale_factor;
     }

@@ -26,6 +26,7 @@ struct KfSlotView {
   int32_t n, fv_n, n_feat, n_levels;
   float fx, fy, cx, cy, min_x, max_x, min_y, max_y, log_scale_factor;
   uint32_t gen;
+  bool fv_once;                  // every feature lies in at most one node of the FeatureVector (fv_once.h)
 };
 int kfs_device(const dvm_keyframe_store* st);
 bool kfs_slot_view(const dvm_keyframe_store* st, int32_t slot, KfSlotView* v);

@@ -54,6 +54,20 @@ bool store_slots_ok(const dvm_map_store* st, const int32_t* slots, int n) {
     if ((uint32_t)slots[k] >= cap || !w[slots[k]]) return false;
   return true;
 }
+int store_kf_slots_check(const dvm_map_store* st, const int32_t* slots, int n, bool* any) {
+  bool some = false;
+  int rc = 0;
+  for (int k = 0; k < n && !rc; k++) {
+    const int32_t sl = slots[k];
+    if (sl == -1) continue;
+    some = true;
+    if (sl < 0) rc = 1;
+    else if (!st) rc = 2;
+    else if (sl >= st->capacity || !st->written[sl]) rc = 1;
+  }
+  if (any) *any = some;
+  return rc;
+}
 int store_read_begin(const dvm_map_store* cst, hipStream_t s) {
   dvm_map_store* st = const_cast<dvm_map_store*>(cst);
   if (!st->write_pending) return DVM_OK;

@@ -16,6 +16,9 @@ const LocalPointPod* store_records(const dvm_map_store* st);   // device, [capac
 int store_device(const dvm_map_store* st);
 // every one of slots[0 .. n) lies in [0, capacity) and has been written
 bool store_slots_ok(const dvm_map_store* st, const int32_t* slots, int n);
+// a keyframe's GetMapPointMatches() as slots (dvm_kf_resident): every one of slots[0 .. n) is -1 (no point) or a written slot of st.
+// 0: yes; 1: a slot below -1, outside [0, capacity) or never written; 2: st is NULL and a slot names a point.  *any (may be NULL): a slot >= 0 seen
+int store_kf_slots_check(const dvm_map_store* st, const int32_t* slots, int n, bool* any);
 int store_read_begin(const dvm_map_store* st, hipStream_t s);
 int store_read_end(const dvm_map_store* st, hipStream_t s);
 

@@ -41,6 +41,7 @@
 #include "match_kernels.h"
 #include "orb_pipeline.h"
 #include "host_stage.h"   // HostPool
+#include "keyframe_store.h"
 #include "map_store.h"
 #include "track_kernels.h"
 #include "track_layout.h"
@@ -94,6 +95,7 @@ struct dvm_tracker {
   WorkingSet rw;                   // device: the upload copy; mapped: rm
   ResidentMapped rm{};             // mapped: the entry number of every query (max_frames x q_rcap), the frames' query counts
   int64_t up_first = 0, up_second = 0;           // dvm_tracker_last_upload_bytes: what the last finish / local-map call copied up
+  int64_t up_refkf = 0;                          // dvm_tracker_last_refkf_upload_bytes: what the last reference-keyframe call copied up
   // ---- the second half (dvm_track_local_map[_batch]): working set of dvm_tracker_reserve_local_map, and what the last finish left for it
   int lm_cap = 0;                  // table entries reserved (a multiple of 64; a batch: all frames' tables, each rounded up to 64)
   WorkingSet lmw;                  // device: [upload region][carve_local_map_work]; mapped: [upload staging][results lm]
@@ -743,7 +745,8 @@ int dvm_track_local_map_batch_resident(dvm_tracker* t, dvm_orb* h, int count, co
 // ---- the other way into the second half: Tracking::TrackReferenceKeyFrame (src/Tracking.cc:2461-2520) on the frames of a finish, or on
 //      the one frame of a single-frame begin / finish
 namespace {
-// the checks of dvm_track_reference_keyframe on one frame's keyframe, parameters and outputs (form (b)); cap: keypoints per keyframe
+// the checks of dvm_track_reference_keyframe on one frame's keyframe, parameters and outputs (form (b)); cap: keypoints per keyframe.
+// kf NULL: a resident keyframe (check_refkf_resident; its FeatureVector passed these checks when it was put)
 int check_refkf_frame(const char* fn, const dvm_ref_keyframe* kf, const dvm_track_refkf_params* p, const dvm_track_refkf_out* out, int cap) {
   char msg[256];
   if (!out->mp_out || !out->dropped || !out->outlier) return DVM_ERR_INVALID;
@@ -751,6 +754,7 @@ int check_refkf_frame(const char* fn, const dvm_ref_keyframe* kf, const dvm_trac
       !(p->nnratio >= 0.0f)) {
     std::snprintf(msg, sizeof msg, "%s: bad parameters", fn); set_error(msg); return DVM_ERR_INVALID;
   }
+  if (!kf) return DVM_OK;
   const int n = kf->n, nf = kf->fv_n;
   if (n < 0 || nf < 0) return DVM_ERR_INVALID;
   if (n > cap || nf > cap) { std::snprintf(msg, sizeof msg, "%s: more keyframe keypoints than reserved", fn); set_error(msg); return DVM_ERR_CAPACITY; }
@@ -772,12 +776,37 @@ int check_refkf_frame(const char* fn, const dvm_ref_keyframe* kf, const dvm_trac
   return DVM_OK;
 }
 
+// one frame's keyframe as the entry points hand it to refkf_enqueue: uploaded whole (dvm_track_reference_keyframe[_batch]), or a
+// keyframe-store slot plus its map points as map-store slots, packed on the device (dvm_track_reference_keyframe_batch_resident);
+// neither: the frame does not run
+struct RefKfSource {
+  const dvm_ref_keyframe* kf = nullptr;
+  const dvm_kf_resident* r = nullptr; KfSlotView v{};
+  bool runs() const { return kf || r; }
+  int n() const { return kf ? kf->n : v.n; }
+  int fv_n() const { return kf ? kf->fv_n : v.fv_n; }
+  const int32_t* mp() const { return kf ? kf->mp : r->mp_slot; }   // the caller's ids of the keyframe's points
+};
+// a resident keyframe's slot and lists, checked on the host: k_refkf_gather indexes the stores with them; fills q.v
+int check_refkf_resident(const char* fn, const dvm_tracker* t, const dvm_keyframe_store* kfs, int b, RefKfSource& q, int cap) {
+  const dvm_kf_resident& r = *q.r;
+  const std::string w = std::string(fn) + ": frame " + std::to_string(b) + " (slot " + std::to_string(r.slot) + ")";
+  if (!kfs_slot_view(kfs, r.slot, &q.v)) { set_error(w + ": slot outside the store, never written or removed"); return DVM_ERR_INVALID; }
+  if (q.v.n > cap) { set_error(w + ": more keyframe keypoints than reserved"); return DVM_ERR_CAPACITY; }
+  if (q.v.n > 0 && !r.mp_slot) { set_error(w + ": missing mp_slot"); return DVM_ERR_INVALID; }
+  if (r.points && store_device(r.points) != t->device) { set_error(w + ": its map store lives on another device"); return DVM_ERR_INVALID; }
+  const int bad = store_kf_slots_check(r.points, r.mp_slot, q.v.n, nullptr);
+  if (bad == 1) { set_error(w + ": an mp_slot below -1, outside its map store or never written"); return DVM_ERR_INVALID; }
+  if (bad == 2) { set_error(w + ": an mp_slot names a point and points is NULL"); return DVM_ERR_INVALID; }
+  return DVM_OK;
+}
+
 // (re)allocates w for keyframes of R entries per call (a multiple of 64) and the tracker's max_frames frames; fn names the caller's errors
 int reserve_refkf(dvm_tracker* t, RefKf& w, size_t R, const char* fn) {
   DVM_HIP(hipSetDevice(t->device));
   w.cap = 0;
   const size_t K = (size_t)t->kp_cap, B = (size_t)t->max_frames;
-  const size_t up = carve_keyframe_upload(nullptr, B, R).bytes;
+  const size_t up = carve_keyframe_upload_resident(nullptr, B, R).u.bytes;   // (the uploaded form's block and the resident form's lists)
   if (const char* what = w.ws.alloc(up + carve_refkf_work(nullptr, B, K).bytes, up + carve_refkf_results(nullptr, B, K).bytes, up, /*mapped*/ true, /*zeroed*/ true))
     return reserve_failed(fn, what);
   w.r = carve_refkf_results(w.ws.hm + up, B, K);
@@ -790,19 +819,24 @@ int reserve_refkf(dvm_tracker* t, RefKf& w, size_t R, const char* fn) {
 // enqueued (a refused call leaves the finish for a corrected one); then the keyframes packed back to back into w's staging block by the pool
 // threads, ONE asynchronous copy, and the chain on the extractor's stream.  *nrun_out: the frames that run (none: nothing enqueued),
 // *T_out: their keyframe entries.
-int refkf_enqueue(dvm_tracker* t, RefKf& w, dvm_orb* h, const dvm_vocab* voc, int count, const dvm_ref_keyframe* const* kfs,
-                  const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status, int* nrun_out,
-                  size_t* T_out) {
+// src[b]: frame b's keyframe; the resident ones (all or none of a call) are slots of `store`, filled into the block by k_refkf_gather.
+int refkf_enqueue(const char* fn, dvm_tracker* t, RefKf& w, dvm_orb* h, const dvm_vocab* voc, int count, RefKfSource* src, const dvm_keyframe_store* store,
+                  int kf_cap, const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status,
+                  int* nrun_out, size_t* T_out) {
   LocalFrame& f = t->lf;
+  const bool resident = store != nullptr;
+  const std::string sfn = fn;
+  if (resident && kfs_device(store) != t->device) { set_error(sfn + ": the keyframe store lives on another device"); return DVM_ERR_INVALID; }
   std::vector<int32_t> qoff((size_t)count, 0), run;
   size_t T = 0;
   const dvm_track_refkf_params* p0 = nullptr;
   for (int b = 0; b < count; b++) {
     qoff[b] = (int32_t)std::min(T, (size_t)INT32_MAX);
-    const dvm_ref_keyframe* kf = kfs[b];
-    if (!kf) continue;
+    RefKfSource& q = src[b];
+    if (!q.runs()) continue;
     const dvm_track_refkf_params* p = &ps[b];
-    const int rc = check_refkf_frame("dvm_track_reference_keyframe_batch", kf, p, &outs[b], kFrameCap);
+    int rc = check_refkf_frame(fn, q.kf, p, &outs[b], kf_cap);
+    if (rc == DVM_OK && q.r) rc = check_refkf_resident(fn, t, store, b, q, kf_cap);
     if (rc != DVM_OK) return rc;
     if (!p0) {
       p0 = p;
@@ -810,20 +844,28 @@ int refkf_enqueue(dvm_tracker* t, RefKf& w, dvm_orb* h, const dvm_vocab* voc, in
                p->min_map != p0->min_map || p->levelsup != p0->levelsup || p->nlevels != p0->nlevels ||
                std::memcmp(p->inv_level_sigma2, p0->inv_level_sigma2, (size_t)p->nlevels * 4) != 0 ||
                (f.model.model != dvm_cam::kKannalaBrandt8 && std::memcmp(&p->cam, &p0->cam, sizeof(p->cam)) != 0)) {
-      set_error("dvm_track_reference_keyframe_batch: the frames that run share camera, level table and matcher thresholds");
+      set_error(sfn + ": the frames that run share camera, level table and matcher thresholds");
       return DVM_ERR_INVALID;
     }
-    T += ((size_t)std::max(kf->n, kf->fv_n) + 63) & ~(size_t)63;
+    T += ((size_t)std::max(q.n(), q.fv_n()) + 63) & ~(size_t)63;
     run.push_back(b);
   }
-  if (p0 && vocab_device(voc) != t->device) { set_error("dvm_track_reference_keyframe_batch: the vocabulary lives on another device"); return DVM_ERR_INVALID; }
+  if (p0 && vocab_device(voc) != t->device) { set_error(sfn + ": the vocabulary lives on another device"); return DVM_ERR_INVALID; }
   if (T > (size_t)w.cap) {
-    set_error("dvm_track_reference_keyframe_batch: more keyframe keypoints than reserved (each keyframe's rounded up to 64)"); return DVM_ERR_CAPACITY;
+    set_error(sfn + ": more keyframe keypoints than reserved (each keyframe's rounded up to 64)"); return DVM_ERR_CAPACITY;
   }
   const int ocap = f.ocap;
-  const KeyframeUpload up = carve_keyframe_upload(w.ws.hm, count, std::max(T, (size_t)64));
+  // the upload block of this call in the staging buffer (hm) and, at the same offsets, in its device copy (d); copy_bytes: what goes up
+  const auto carve_upload = [&](uint8_t* base) {
+    if (resident) return carve_keyframe_upload_resident(base, (size_t)count, std::max(T, (size_t)64));
+    KeyframeUploadResident r{carve_keyframe_upload(base, (size_t)count, std::max(T, (size_t)64)), nullptr, nullptr, 0};
+    r.copy_bytes = r.u.bytes;
+    return r;
+  };
+  const KeyframeUploadResident rup = carve_upload(w.ws.hm), drup = carve_upload(w.ws.d);
+  const KeyframeUpload &up = rup.u, &dup = drup.u;
   if (up.bytes > w.ws.up_bytes || ocap > t->kp_cap) {
-    set_error("dvm_track_reference_keyframe_batch: the upload block exceeds the reservation"); return DVM_ERR_CAPACITY;
+    set_error(sfn + ": the upload block exceeds the reservation"); return DVM_ERR_CAPACITY;
   }
   // accepted: once per finish, and the single call no longer runs on it
   for (int b = 0; b < count; b++) { std::memset(&res[b], 0, sizeof(res[b])); status[b] = f.status[b]; }
@@ -838,22 +880,30 @@ int refkf_enqueue(dvm_tracker* t, RefKf& w, dvm_orb* h, const dvm_vocab* voc, in
   std::memset(up.inv_sigma2, 0, 64 * 4);
   std::memcpy(up.inv_sigma2, P0.inv_level_sigma2, (size_t)P0.nlevels * 4);
   int nwg = 0;
-  for (int r = 0; r < nrun; r++) { up.run[r] = run[r]; up.wg_base[r] = nwg; nwg += (kfs[run[r]]->fv_n + 3) / 4; }
+  for (int r = 0; r < nrun; r++) { up.run[r] = run[r]; up.wg_base[r] = nwg; nwg += (src[run[r]].fv_n() + 3) / 4; }
   up.wg_base[nrun] = nwg;
   HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {
-    const dvm_ref_keyframe* kf = kfs[b];
+    const RefKfSource& q = src[b];
+    const dvm_ref_keyframe* kf = q.kf;
     const size_t o = (size_t)qoff[b];
     up.qoff[b] = qoff[b];
     int32_t* rs = up.res + 8 * b;
     for (int k = 0; k < 8; k++) rs[k] = 0;
-    if (!kf) {                            // a frame that does not run: no edges (k_track_gather reads res[1] != 0), the pose left alone
+    if (resident) std::memset(&rup.items[b], 0, sizeof(RefKfGatherItem));
+    if (!q.runs()) {                      // a frame that does not run: no edges (k_track_gather reads res[1] != 0), the pose left alone
       rs[1] = 1; up.kfv_n[b] = 0;
       std::memcpy(up.pose + 7 * b, f.poses.data() + 7 * b, 56);
       return;
     }
-    const int n = kf->n, nf = kf->fv_n, nfeat = nf ? kf->fv_off[nf] : 0;
     std::memcpy(up.pose + 7 * b, ps[b].pose_in, 56);
-    up.kfv_n[b] = nf;
+    up.kfv_n[b] = q.fv_n();
+    if (q.r) {                            // the slot list goes up; k_refkf_gather packs the rest where the loop below packs it
+      const KfSlotView& v = q.v;
+      rup.items[b] = RefKfGatherItem{q.r->points ? store_records(q.r->points) : nullptr, v.kps, v.desc, v.fv_node, v.fv_off, v.fv_feat, v.n, v.n_feat};
+      if (v.n) std::memcpy(rup.mp_slot + o, q.r->mp_slot, (size_t)v.n * 4);
+      return;
+    }
+    const int n = kf->n, nf = kf->fv_n, nfeat = nf ? kf->fv_off[nf] : 0;
     if (n) std::memcpy(up.desc + o * 32, kf->desc, (size_t)n * 32);
     for (int i = 0; i < n; i++) {
       const int id = kf->mp[i];
@@ -870,8 +920,23 @@ int refkf_enqueue(dvm_tracker* t, RefKf& w, dvm_orb* h, const dvm_vocab* voc, in
       fo[0] = 0;
     }
   });
-  DVM_HIP(hipMemcpyAsync(w.ws.d, w.ws.hm, up.bytes, hipMemcpyHostToDevice, s));
-  const KeyframeUpload dup = carve_keyframe_upload(w.ws.d, count, std::max(T, (size_t)64));
+  DVM_HIP(hipMemcpyAsync(w.ws.d, w.ws.hm, rup.copy_bytes, hipMemcpyHostToDevice, s));
+  t->up_refkf = (int64_t)rup.copy_bytes;
+  if (resident) {     // the packed keyframes from the stores, behind their last puts and updates; nothing after the gather reads a store
+    std::vector<const dvm_map_store*> maps;    // the distinct map stores of the frames that run: one wait and one event each
+    for (int r = 0; r < nrun; r++) {
+      const dvm_map_store* m = src[run[r]].r->points;
+      if (m && std::find(maps.begin(), maps.end(), m) == maps.end()) maps.push_back(m);
+    }
+    int rc = kfs_read_begin(store, s);
+    for (size_t k = 0; k < maps.size() && rc == DVM_OK; k++) rc = store_read_begin(maps[k], s);
+    if (rc != DVM_OK) return rc;
+    launch_refkf_gather(s, drup.items, drup.mp_slot, dup.run, nrun, dup.qoff, dup.kfv_n,
+                        RefKfGatherOut{dup.desc, dup.angle, dup.use, dup.claims, dup.pos, dup.fv_node, dup.fv_feat, dup.fv_off});
+    rc = kfs_read_end(store, s);
+    for (size_t k = 0; k < maps.size() && rc == DVM_OK; k++) rc = store_read_end(maps[k], s);
+    if (rc != DVM_OK) return rc;
+  }
   // 2. the chain: ComputeBoW (the transform of all frames that run in one launch, then the BowVector / FeatureVector in LDS, a workgroup per
   //    frame) -> SearchByBoW (each frame's keyframe nodes on their own workgroups) -> rotation check -> PoseOptimization's edges in keypoint
   //    order -> k_pose_optimize seeded from pose_in -> outlier flags and nmatchesMap, as the batched first half runs them (a frame that
@@ -901,14 +966,14 @@ int refkf_enqueue(dvm_tracker* t, RefKf& w, dvm_orb* h, const dvm_vocab* voc, in
 
 // after refkf_enqueue's chain is through: every frame that ran copied out of w's mapped results by the pool threads, and what the second
 // half runs on -- such a frame complete or not by this call's status, seeded from its pose
-void refkf_copy_out(dvm_tracker* t, const RefKf& w, int count, const dvm_ref_keyframe* const* kfs, const dvm_track_refkf_params* ps,
+void refkf_copy_out(dvm_tracker* t, const RefKf& w, int count, const RefKfSource* src, const dvm_track_refkf_params* ps,
                     const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status) {
   LocalFrame& f = t->lf;
   const RefKfMapped& r = w.r;
   const size_t K = (size_t)f.ocap;
   HostPool::get().run((size_t)count, count >= 4 ? 8 : 1, [&](size_t b) {
-    const dvm_ref_keyframe* kf = kfs[b];
-    if (!kf) return;
+    if (!src[b].runs()) return;
+    const int32_t* kf_mp = src[b].mp();
     const dvm_track_refkf_params* p = &ps[b];
     const dvm_track_refkf_out* out = &outs[b];
     dvm_track_refkf_result* q = &res[b];
@@ -928,7 +993,7 @@ void refkf_copy_out(dvm_tracker* t, const RefKf& w, int count, const dvm_ref_key
     const uint8_t* outl = r.outlier + b * K;
     for (int j = 0; j < N; j++) {
       const int a = match[j];
-      const int id = a >= 0 ? kf->mp[a] : -1;
+      const int id = a >= 0 ? kf_mp[a] : -1;
       const bool o = !few && id >= 0 && outl[j];
       out->mp_out[j] = o ? -1 : id; out->dropped[j] = o ? id : -1; out->outlier[j] = o ? 1 : 0;
     }
@@ -1012,7 +1077,9 @@ int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* vo
   int32_t status = 0;
   int nrun = 0;
   size_t T = 0;
-  rc = refkf_enqueue(t, t->rk, h, voc, 1, &kf, p, out, res, &status, &nrun, &T);
+  RefKfSource src;
+  src.kf = kf;
+  rc = refkf_enqueue("dvm_track_reference_keyframe", t, t->rk, h, voc, 1, &src, nullptr, t->rk_cap, p, out, res, &status, &nrun, &T);
   if (rc != DVM_OK) return rc;
   // ONE synchronisation (behind the download of the extraction in form (a))
   if (form == 1) {
@@ -1027,7 +1094,7 @@ int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* vo
   } else {
     DVM_HIP(hipStreamSynchronize(s));
   }
-  refkf_copy_out(t, t->rk, 1, &kf, p, out, res, &status);
+  refkf_copy_out(t, t->rk, 1, &src, p, out, res, &status);
   return DVM_OK;
 }
 
@@ -1039,32 +1106,57 @@ int dvm_tracker_reserve_reference_keyframe_batch(dvm_tracker* t, int max_total_k
   return reserve_refkf(t, t->rkb, ((size_t)max_total_kf_keypoints + 63) & ~(size_t)63, "dvm_tracker_reserve_reference_keyframe_batch");
 }
 
-int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, int count, const dvm_ref_keyframe* const* kfs,
-                                       const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status) {
-  if (!t || !h || !voc || !kfs || !ps || !outs || !res || !status || count < 1) return DVM_ERR_INVALID;
+namespace {
+// both batched entry points behind their argument checks: the state rules, the chain, ONE synchronisation, the results
+int refkf_batch_run(const char* fn, dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, int count, std::vector<RefKfSource>& src, const dvm_keyframe_store* store,
+                    const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status) {
   LocalFrame& f = t->lf;
+  const std::string sfn = fn;
   if (!f.rkb_ready || f.h != h || orb_result_serial(h) != f.serial || f.count != count) {
-    set_error("dvm_track_reference_keyframe_batch: not right after a dvm_track_finish[_batch] of `count` frames (same tracker and extractor), "
-              "or already run on that finish");
+    set_error(sfn + ": not right after a dvm_track_finish[_batch] of `count` frames (same tracker and extractor), or already run on that finish");
     return DVM_ERR_STATE;
   }
-  if (!t->rkb.ws.d) { set_error("dvm_track_reference_keyframe_batch: no dvm_tracker_reserve_reference_keyframe_batch on this tracker"); return DVM_ERR_STATE; }
+  if (!t->rkb.ws.d) { set_error(sfn + ": no dvm_tracker_reserve_reference_keyframe_batch on this tracker"); return DVM_ERR_STATE; }
   static const bool timing = std::getenv("DVM_TRACK_BATCH_TIMING") != nullptr;       // host-side phase times on stderr
   using clk = std::chrono::steady_clock;
   const clk::time_point tp0 = clk::now();
   int nrun = 0;
   size_t T = 0;
-  int rc = refkf_enqueue(t, t->rkb, h, voc, count, kfs, ps, outs, res, status, &nrun, &T);
+  int rc = refkf_enqueue(fn, t, t->rkb, h, voc, count, src.data(), store, kFrameCap, ps, outs, res, status, &nrun, &T);
   if (rc != DVM_OK || !nrun) return rc;
   const clk::time_point tp1 = clk::now();
   DVM_HIP(hipStreamSynchronize((hipStream_t)dvm_orb_stream(h)));
   const clk::time_point tp2 = clk::now();
-  refkf_copy_out(t, t->rkb, count, kfs, ps, outs, res, status);
+  refkf_copy_out(t, t->rkb, count, src.data(), ps, outs, res, status);
   if (timing) {
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::fprintf(stderr, "track reference keyframe batch of %d (%d run, %zu entries): pack + enqueue %.3f  wait %.3f  results out %.3f ms\n", count,
                  nrun, T, ms(tp0, tp1), ms(tp1, tp2), ms(tp2, clk::now()));
   }
+  return DVM_OK;
+}
+}  // namespace
+
+int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, int count, const dvm_ref_keyframe* const* kfs,
+                                       const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res, int32_t* status) {
+  if (!t || !h || !voc || !kfs || !ps || !outs || !res || !status || count < 1) return DVM_ERR_INVALID;
+  std::vector<RefKfSource> src((size_t)count);
+  for (int b = 0; b < count; b++) src[b].kf = kfs[b];
+  return refkf_batch_run("dvm_track_reference_keyframe_batch", t, h, voc, count, src, nullptr, ps, outs, res, status);
+}
+
+int dvm_track_reference_keyframe_batch_resident(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, const dvm_keyframe_store* kfs, int count,
+                                                const dvm_kf_resident* const* kf, const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs,
+                                                dvm_track_refkf_result* res, int32_t* status) {
+  if (!t || !h || !voc || !kfs || !kf || !ps || !outs || !res || !status || count < 1) return DVM_ERR_INVALID;
+  std::vector<RefKfSource> src((size_t)count);
+  for (int b = 0; b < count; b++) src[b].r = kf[b];
+  return refkf_batch_run("dvm_track_reference_keyframe_batch_resident", t, h, voc, count, src, kfs, ps, outs, res, status);
+}
+
+int dvm_tracker_last_refkf_upload_bytes(const dvm_tracker* t, int64_t* bytes) {
+  if (!t || !bytes) return DVM_ERR_INVALID;
+  *bytes = t->up_refkf;
   return DVM_OK;
 }
 

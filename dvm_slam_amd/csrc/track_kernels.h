@@ -113,4 +113,16 @@ void launch_refkf_bow(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int
 void launch_refkf_search(hipStream_t s, const RefKfArgs& A, const dvm_keypoint_pod* kps_un, const uint8_t* desc, const int32_t* d_n, int cap, int th_low,
                          float nnratio);
 void launch_refkf_settle(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, int cap, int check_ori);
+// ---- the packed keyframes of the chain above filled on the device (dvm_track_reference_keyframe_batch_resident): frame b's keyframe is a
+// keyframe-store slot (kps, desc, the FeatureVector) plus its map points as slots of a map store (recs)
+struct RefKfGatherItem {
+  const LocalPointPod* recs;              // the frame's map store; not read when every mp_slot < 0
+  const dvm_keypoint_pod* kps; const uint8_t* desc; const int32_t *fv_node, *fv_off, *fv_feat;   // in the slot
+  int32_t n, n_feat;                      // keypoints, features the FeatureVector lists (its node count: kfv_nb[b])
+};                                        // 56 bytes
+struct RefKfGatherOut { uint8_t* desc; float* angle; uint8_t *use, *claims; float* pos; int32_t *fv_node, *fv_feat, *fv_off; };
+// one workgroup per frame that runs (run [nrun]): frame b's keyframe written at kqoff[b] entries of O (fv_off at kqoff[b] + b) as the
+// uploaded call packs it; mp_slot: the frames' lists at kqoff[b].  The host has checked every slot of every list.
+void launch_refkf_gather(hipStream_t s, const RefKfGatherItem* items, const int32_t* mp_slot, const int32_t* run, int nrun, const int32_t* kqoff,
+                         const int32_t* kfv_nb, const RefKfGatherOut& O);
 }  // namespace dvm

@@ -828,4 +828,58 @@ void launch_refkf_settle(hipStream_t s, const RefKfArgs& A, const int32_t* d_n, 
   hipLaunchKernelGGL(k_refkf_settle, dim3(A.nrun), dim3(256), 0, s, A, d_n, cap, check_ori);
 }
 
+// ---- dvm_track_reference_keyframe_batch_resident: the packed keyframe block filled from the stores, as refkf_enqueue (track.cpp) packs
+// it on the host for the uploaded call.  One 1 024-thread workgroup per frame that runs.  Descriptors, nodes and features move 16 bytes
+// per thread and step: the slot's arrays begin at multiples of 64 bytes and kqoff[b] is a multiple of 64 entries, so both sides are
+// aligned; the offsets land at kqoff[b] + b entries, 4-byte aligned only, and move a dword at a time.  Per keypoint: the angle out of
+// the slot's 28-byte records, and out of the map point's 72-byte record the host loop's three rules.  No LDS, no barrier.
+namespace {
+// n4 dwords from src to dst, both at multiples of 16 bytes
+__device__ __forceinline__ void refkf_move(int32_t* __restrict__ dst, const int32_t* __restrict__ src, int n4) {
+  const int n16 = n4 >> 2;
+  for (int i = threadIdx.x; i < n16; i += 1024) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+  for (int i = n16 * 4 + threadIdx.x; i < n4; i += 1024) dst[i] = src[i];
+}
+}  // namespace
+__global__ void __launch_bounds__(1024) k_refkf_gather(const RefKfGatherItem* __restrict__ items, const int32_t* __restrict__ mp_slot,
+                                                       const int32_t* __restrict__ run, const int32_t* __restrict__ kqoff,
+                                                       const int32_t* __restrict__ kfv_nb, RefKfGatherOut O) {
+  const int b = run[blockIdx.x];
+  const RefKfGatherItem K = items[b];
+  const size_t o = (size_t)kqoff[b];
+  const int nf = kfv_nb[b];
+  refkf_move(reinterpret_cast<int32_t*>(O.desc + o * 32), reinterpret_cast<const int32_t*>(K.desc), K.n * 8);
+  refkf_move(O.fv_node + o, K.fv_node, nf);
+  refkf_move(O.fv_feat + o, K.fv_feat, K.n_feat);
+  int32_t* fo = O.fv_off + o + b;
+  if (nf > 0) {
+    for (int a = threadIdx.x; a <= nf; a += 1024) fo[a] = K.fv_off[a];
+  } else if (threadIdx.x == 0) {
+    fo[0] = 0;
+  }
+  const int32_t* slots = mp_slot + o;
+  for (int i = threadIdx.x; i < K.n; i += 1024) {
+    const int id = slots[i];
+    float px = 0.0f, py = 0.0f, pz = 0.0f;
+    bool use = false, claims = false;
+    if (id >= 0) {
+      const LocalPointPod& R = K.recs[id];
+      px = R.pos[0]; py = R.pos[1]; pz = R.pos[2];
+      use = R.bad == 0;                     // SearchByBoW: no map point or a bad one -> skipped (:247-252)
+      claims = R.n_obs > 0;
+    }
+    O.angle[o + i] = K.kps[i].angle;
+    O.use[o + i] = use ? 1 : 0;
+    O.claims[o + i] = claims ? 1 : 0;
+    float* p = O.pos + 3 * (o + i);
+    p[0] = px; p[1] = py; p[2] = pz;
+  }
+}
+void launch_refkf_gather(hipStream_t s, const RefKfGatherItem* items, const int32_t* mp_slot, const int32_t* run, int nrun, const int32_t* kqoff,
+                         const int32_t* kfv_nb, const RefKfGatherOut& O) {
+  static_assert(sizeof(RefKfGatherItem) == 56, "track_kernels.h states it");
+  if (nrun < 1) return;
+  hipLaunchKernelGGL(k_refkf_gather, dim3(nrun), dim3(1024), 0, s, items, mp_slot, run, kqoff, kfv_nb, O);
+}
+
 }  // namespace dvm

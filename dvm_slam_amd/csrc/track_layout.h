@@ -158,15 +158,35 @@ struct KeyframeUpload {
   float* inv_sigma2; double* pose; int32_t *qoff, *kfv_n, *res, *run, *wg_base;
   uint8_t* desc; float* angle; uint8_t *use, *claims; float* pos; int32_t *fv_node, *fv_feat, *fv_off; size_t bytes;
 };
+// the head both forms begin with, and the packed keyframes the chain's kernels read at kqoff[b]
+inline void carve_keyframe_head(Cursor<256>& c, size_t B, KeyframeUpload& u) {
+  u.inv_sigma2 = c.carve<float>(64); u.pose = c.carve<double>(B * 7); u.qoff = c.carve<int32_t>(B); u.kfv_n = c.carve<int32_t>(B);
+  u.res = c.carve<int32_t>(B * 8); u.run = c.carve<int32_t>(B); u.wg_base = c.carve<int32_t>(B + 1);
+}
+inline void carve_keyframe_block(Cursor<256>& c, size_t B, size_t T, KeyframeUpload& u) {
+  u.desc = c.carve<uint8_t>(T * 32); u.angle = c.carve<float>(T); u.use = c.carve<uint8_t>(T); u.claims = c.carve<uint8_t>(T);
+  u.pos = c.carve<float>(T * 3); u.fv_node = c.carve<int32_t>(T); u.fv_feat = c.carve<int32_t>(T); u.fv_off = c.carve<int32_t>(T + B);
+}
 inline KeyframeUpload carve_keyframe_upload(uint8_t* base, size_t B, size_t T) {
   KeyframeUpload u;
   Cursor<256> c{base};
-  u.inv_sigma2 = c.carve<float>(64); u.pose = c.carve<double>(B * 7); u.qoff = c.carve<int32_t>(B); u.kfv_n = c.carve<int32_t>(B);
-  u.res = c.carve<int32_t>(B * 8); u.run = c.carve<int32_t>(B); u.wg_base = c.carve<int32_t>(B + 1);
-  u.desc = c.carve<uint8_t>(T * 32); u.angle = c.carve<float>(T); u.use = c.carve<uint8_t>(T); u.claims = c.carve<uint8_t>(T);
-  u.pos = c.carve<float>(T * 3); u.fv_node = c.carve<int32_t>(T); u.fv_feat = c.carve<int32_t>(T); u.fv_off = c.carve<int32_t>(T + B);
+  carve_keyframe_head(c, B, u); carve_keyframe_block(c, B, T, u);
   u.bytes = c.used();
   return u;
+}
+// the same block where the keyframes are store slots (dvm_track_reference_keyframe_batch_resident): [head][per frame: where k_refkf_gather
+// reads the keyframe][mp_slot: T entries, frame b's at qoff[b]] -- copied up to here (copy_bytes) in one copy -- then [keyframes: T
+// entries][offsets], device only: k_refkf_gather fills them from the slots and the map stores
+struct KeyframeUploadResident { KeyframeUpload u; RefKfGatherItem* items; int32_t* mp_slot; size_t copy_bytes; };
+inline KeyframeUploadResident carve_keyframe_upload_resident(uint8_t* base, size_t B, size_t T) {
+  KeyframeUploadResident r;
+  Cursor<256> c{base};
+  carve_keyframe_head(c, B, r.u);
+  r.items = c.carve<RefKfGatherItem>(B); r.mp_slot = c.carve<int32_t>(T);
+  r.copy_bytes = c.used();
+  carve_keyframe_block(c, B, T, r.u);
+  r.u.bytes = c.used();
+  return r;
 }
 // the device working set behind the upload, per frame at the call's capacity stride (cap <= kp_cap, count <= max_frames)
 struct RefKfWork { int32_t *word, *node; double* w; int32_t *fv_node, *fv_feat, *fv_off, *cnt, *match, *bin; size_t bytes; };

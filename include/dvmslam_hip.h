@@ -1184,6 +1184,44 @@ int dvm_create_new_map_points_resident(dvm_new_points* h, const dvm_keyframe_sto
 /* The host-to-device bytes queued by the last call that reached the device, resident or not. */
 int dvm_new_points_last_upload_bytes(const dvm_new_points* h, int64_t* bytes);
 
+/* ---- A resident keyframe, as the place-recognition searches and TrackReferenceKeyFrame name it (below): a keyframe-store slot plus
+ * GetMapPointMatches() as map-store slots, 4 B per keypoint.  Descriptors, mvKeysUn and the FeatureVector are read in the slot; the
+ * map points' isBad(), Observations() and GetWorldPos() in the 72-byte records of `points`.  Different keyframes of one call may name
+ * different map stores (merge candidates belong to other maps); all of them, and the keyframe store, live on the handle's device.
+ * An mp_slot is -1 or a written slot of `points`; anything else is DVM_ERR_INVALID.  sizeof(dvm_kf_resident) == 24 (LP64). */
+typedef struct {
+  int32_t slot;                 /* dvm_keyframe_store slot */
+  const dvm_map_store* points;  /* the map this keyframe's points live in; may be NULL when every mp_slot is -1 */
+  const int32_t* mp_slot;       /* [n of the slot] GetMapPointMatches() as map-store slots, -1 = NULL pointer */
+} dvm_kf_resident;
+
+/* ---- dvm_search_by_bow_targets on resident keyframes.  The keyframe table's desc / fv_node / fv_off / fv_feat point into the slots;
+ * the mp_slot lists are the whole per-keypoint upload.  ONE prologue launch (k_bt_prologue) then writes into the handle's device block,
+ * for every keyframe of the call, use[i] = mp_slot[i] >= 0 && !record.bad and angle[i] = the slot's mvKeysUn[i].angle, -1 into every
+ * match row (a feature of cur that no node lists keeps it: no host pass) and zero into the per-target counters; the search and the
+ * settle kernels are the uploaded call's.  The search is ordered behind every put to `kfs` and every update of a named map store
+ * queued before the call, and a put or update queued after it waits for it.
+ * Contract: for the same keyframes match_idx2 and nmatches equal dvm_search_by_bow_targets bit for bit, where that call carries
+ * mp[i] = mp_slot[i] and bad[i] = the record's bad != 0.
+ * Upload: exactly
+ *     64 * ceil(56 * (T + 1) / 64) + 64 * ceil(32 * (T + 1) / 64) + sum over cur and the T targets of 64 * ceil(4 * n / 64)
+ * bytes (the keyframe table, the prologue's table, the lists) -- at most 4 B per keypoint, each list rounded up to 64 B, plus 256 B per
+ * keyframe.  dvm_bow_targets_last_upload_bytes reports it, for either form.
+ * dvm_bow_targets_reserve keeps its meaning: max_total_target_keypoints bounds the device block, which holds the flags and angles.
+ * The listed-once rule (a feature lies in ONE node) is checked per call by the uploaded form; dvm_keyframe_store_put accepts such a
+ * keyframe as before and records per slot whether the rule holds; this call refuses a slot where it does not.
+ * Errors, all before anything is queued, the handle stays usable, each naming the keyframe: DVM_ERR_INVALID -- a slot outside the
+ * store, never written or removed; a store on another device; an mp_slot below -1, outside its map store or never written; a NULL
+ * mp_slot where the slot holds keypoints; a NULL points with an mp_slot >= 0; a slot whose FeatureVector lists a feature twice.
+ * DVM_ERR_CAPACITY -- beyond the reservation.  Legal, as in the uploaded call: n_targets = 0, a keyframe with n = 0 or fv_n = 0, one
+ * slot as cur and as a target, one slot as several targets under different mp_slot lists. */
+int dvm_search_by_bow_targets_resident(dvm_bow_targets* h, const dvm_keyframe_store* kfs, const dvm_kf_resident* cur, int n_targets,
+                                       const dvm_kf_resident* targets, float nnratio, int check_ori, int32_t* match_idx2, int32_t* nmatches);
+/* The host-to-device bytes queued by the last call that reached the device, either form. */
+int dvm_bow_targets_last_upload_bytes(const dvm_bow_targets* h, int64_t* bytes);
+/* With dvm_bow_targets_profiling on: the prologue kernel's milliseconds of the last call (0 after an uploaded call). */
+int dvm_bow_targets_last_prologue_ms(dvm_bow_targets* h, float* ms);
+
 /* ---- The first half reading a store: dvm_track_finish_batch with the projection queries built ON THE DEVICE (k_track_queries) from
  * LastFrame's entry list -- the loop header of ORBmatcher.cc:1573-1611, what dvmh_track_with_motion_model builds on the host: x3Dc = Tcw *
  * pos (Sophus' quaternion form), invzc = (float)(1.0 / z) with invzc < 0 skipped, the projection through the tracker's camera model, the
@@ -1329,6 +1367,25 @@ int dvm_tracker_reserve_reference_keyframe_batch(dvm_tracker* t, int max_total_k
 int dvm_track_reference_keyframe_batch(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, int count, const dvm_ref_keyframe* const* kfs,
                                        const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs, dvm_track_refkf_result* res,
                                        int32_t* status);
+/* dvm_track_reference_keyframe_batch on resident keyframes: kf[b] names frame b's reference keyframe as a slot of `kfs` plus its map
+ * points as map-store slots (dvm_kf_resident above), NULL = the frame does not run.  The host uploads the mp_slot lists and the small
+ * per-frame arrays and nothing per keypoint beyond those 4 B; a gather kernel (k_refkf_gather, one workgroup per frame that runs)
+ * packs the chain's keyframe block on the device -- descriptors and the FeatureVector out of the slot, the angle out of its keypoint
+ * records, and per keypoint out of the map point's record use = id >= 0 && !bad, claims = id >= 0 && n_obs > 0, pos = id >= 0 ?
+ * record.pos : 0.  Everything behind the gather is the uploaded call's chain; it is ordered behind every put and update queued before.
+ * Contract: state rules, reservation (dvm_tracker_reserve_reference_keyframe_batch: a slot counts its n rounded up to 64), skipped
+ * frames, outputs and statuses are dvm_track_reference_keyframe_batch's, the call that follows is accepted as after it, and res, outs
+ * and status equal that call's bit for bit where it carries mp = mp_slot and mp_pos / mp_nobs / mp_bad read from the records -- under
+ * the pinhole tracker and a KannalaBrandt8 one; outs[b].mp_out / dropped hold map-store slots.  count = 1 on a single-frame tracker
+ * is legal.  DVM_ERR_INVALID before anything is queued, the finish left for a corrected call: a slot outside the store, never written
+ * or removed; a store on another device; an mp_slot below -1, outside its map store or never written; a NULL mp_slot where the slot
+ * holds keypoints; a NULL points with an mp_slot >= 0.  DVM_ERR_CAPACITY: the keyframes' total beyond the reservation. */
+int dvm_track_reference_keyframe_batch_resident(dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, const dvm_keyframe_store* kfs, int count,
+                                                const dvm_kf_resident* const* kf /* [count], NULL = frame does not run */,
+                                                const dvm_track_refkf_params* ps, const dvm_track_refkf_out* outs,
+                                                dvm_track_refkf_result* res, int32_t* status);
+/* The host-to-device bytes queued by the tracker's last reference-keyframe call that reached the device, any form. */
+int dvm_tracker_last_refkf_upload_bytes(const dvm_tracker* t, int64_t* bytes);
 
 /* Optimizer::OptimizeSim3 (Optimizer.cc:1960-2212), numerics for N correspondences gathered by the caller:
  * P1c / P2c = the matched map points in their own key frame's camera frame (R1w*P+t1w, R2w*P+t2w), obs1 / obs2 =
