@@ -3067,6 +3067,29 @@ class _KfsReadback(C.Structure):   # == dvm_kfs_readback
                 ("skp", C.c_void_p), ("sidx", C.c_void_p), ("sdesc", C.c_void_p), ("cell_start", C.c_void_p)]
 
 
+class _KfsDeviceKeyframe(C.Structure):   # == dvm_kfs_device_keyframe
+    _fields_ = [("d_kps", C.c_void_p), ("d_desc", C.c_void_p), ("d_n", C.c_void_p), ("n", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("inv_level_sigma2", C.c_void_p), ("log_scale_factor", C.c_float),
+                ("n_levels", C.c_int32)]
+
+
+class _KfsBowOut(C.Structure):   # == dvm_kfs_bow_out
+    _fields_ = [("n", C.c_int32), ("n_bow", C.c_int32), ("n_fv", C.c_int32), ("n_feat", C.c_int32), ("bow_ids", C.c_void_p), ("bow_vals", C.c_void_p),
+                ("fv_node", C.c_void_p), ("fv_off", C.c_void_p), ("fv_feat", C.c_void_p)]
+
+
+def _dev_ptr(v):
+    """A torch CUDA tensor, an int device pointer or None -> the pointer (None: NULL)."""
+    if v is None:
+        return None
+    if hasattr(v, "data_ptr"):
+        assert v.is_cuda and v.is_contiguous()
+        return v.data_ptr()
+    return int(v)
+
+
 class _FtTargetResident(C.Structure):   # == dvm_ft_target_resident
     _fields_ = [("slot", C.c_int32), ("Tcw", C.c_float * 7), ("Ow", C.c_float * 3)]
 
@@ -3093,8 +3116,12 @@ class KeyframeStore:
         self.h = C.c_void_p()
         vp, i32 = C.c_void_p, C.c_int32
         for name, args in (("create", [i32, i32, i32, vp]), ("capacity", [vp]), ("slot_keypoints", [vp]), ("put", [vp, i32, vp, vp]), ("remove", [vp, i32, vp]),
-                           ("debug_read", [vp, i32, vp])):
-            f = getattr(self.L, "dvm_keyframe_store_" + name)
+                           ("debug_read", [vp, i32, vp]), ("put_device", [vp, vp, i32, vp, i32, vp, vp, vp]),
+                           ("put_tracked", [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]), ("last_put_bytes", [vp, vp]), ("profile", [vp, i32]),
+                           ("last_put_ms", [vp, vp])):
+            f = getattr(self.L, "dvm_keyframe_store_" + name, None)
+            if f is None:       # an older library (DVM_HIP_LIB, the measurement tools' baseline): calling the entry raises AttributeError
+                continue
             f.restype = i32; f.argtypes = args
         self.L.dvm_keyframe_store_destroy.restype = None; self.L.dvm_keyframe_store_destroy.argtypes = [vp]
         check(self.L.dvm_keyframe_store_create(int(device), int(capacity), int(slot_keypoints), C.byref(self.h)))
@@ -3133,6 +3160,88 @@ class KeyframeStore:
 
     def put_raw(self, slots, arr):
         check(self.L.dvm_keyframe_store_put(self.h, len(slots), _p(slots), C.addressof(arr)))
+
+    @staticmethod
+    def device_records(kfs):
+        """Keyframe dicts -> (dvm_kfs_device_keyframe array, keepalive).  kps / desc: torch CUDA tensors or int device pointers (missing:
+        NULL); n: the device count, a tensor or an int device pointer, or None / missing; count: the host count (without n) or the
+        arrays' capacity (with n) -- missing: the length of a kps tensor.  K, bounds, scale_factors, level_sigma2, inv_level_sigma2,
+        log_scale_factor, n_levels (default: the scale table's length): as keyframe_view; a missing table is NULL."""
+        keep = []
+        arr = (_KfsDeviceKeyframe * max(len(kfs), 1))()
+        for t, kf in enumerate(kfs):
+            s = arr[t]
+            kps = kf.get("kps")
+            keep.append([kps, kf.get("desc"), kf.get("n")])
+            s.d_kps, s.d_desc, s.d_n = _dev_ptr(kps), _dev_ptr(kf.get("desc")), _dev_ptr(kf.get("n"))
+            if kf.get("count") is not None:
+                s.n = int(kf["count"])
+            else:
+                s.n = kps.numel() * kps.element_size() // KP_DTYPE.itemsize if hasattr(kps, "numel") else 0
+            s.fx, s.fy, s.cx, s.cy = (float(x) for x in kf.get("K", (0, 0, 0, 0)))
+            s.min_x, s.max_x, s.min_y, s.max_y = (float(x) for x in kf["bounds"])
+            nl = 0
+            for key in ("scale_factors", "level_sigma2", "inv_level_sigma2"):
+                if kf.get(key) is not None:
+                    a = np.ascontiguousarray(kf[key], np.float32); keep.append(a); setattr(s, key, a.ctypes.data); nl = len(a)
+            s.n_levels = int(kf.get("n_levels", nl))
+            s.log_scale_factor = float(kf.get("log_scale_factor", 0.0))
+        return arr, keep
+
+    def _bow_outs(self, n):
+        K = self.slot_keypoints
+        outs = (_KfsBowOut * max(n, 1))()
+        bufs = []
+        for k in range(n):
+            b = dict(bow_ids=np.zeros(K, np.int32), bow_vals=np.zeros(K, np.float64), fv_node=np.zeros(K, np.int32), fv_off=np.zeros(K + 1, np.int32),
+                     fv_feat=np.zeros(K, np.int32))
+            for name, a in b.items():
+                setattr(outs[k], name, a.ctypes.data)
+            bufs.append(b)
+        return outs, bufs
+
+    @staticmethod
+    def _bow_results(outs, bufs):
+        return [dict(n=o.n, bow_ids=b["bow_ids"][:o.n_bow].copy(), bow_vals=b["bow_vals"][:o.n_bow].copy(), fv_nodes=b["fv_node"][:o.n_fv].copy(),
+                     fv_off=b["fv_off"][:o.n_fv + 1].copy(), fv_feat=b["fv_feat"][:o.n_feat].copy()) for o, b in zip(outs, bufs)]
+
+    def put_device(self, voc, slots, kfs, levelsup=4, stream=None):
+        """dvm_keyframe_store_put_device: keyframes whose arrays are in device memory (device_records) go to `slots`; KeyFrame::ComputeBoW
+        runs on the device.  voc: a Vocabulary; stream: the stream that produced the arrays (an int handle; None: the null stream).
+        One synchronisation.  Returns a list of dict(n, bow_ids, bow_vals, fv_nodes, fv_off, fv_feat) as vocab_transform_host."""
+        slots = np.ascontiguousarray(slots, np.int32)
+        assert slots.ndim == 1 and len(slots) == len(kfs)
+        arr, keep = self.device_records(kfs)
+        outs, bufs = self._bow_outs(len(kfs))
+        check(self.L.dvm_keyframe_store_put_device(self.h, voc.h, int(levelsup), stream, len(slots), _p(slots), C.addressof(arr), C.addressof(outs)))
+        return self._bow_results(outs[:len(kfs)], bufs)
+
+    def put_tracked(self, tracker, ext, voc, frames, slots, tables, levelsup=4):
+        """dvm_keyframe_store_put_tracked: frames `frames` of the last finish of `tracker` (a Tracker or a TrackerBatch on extractor `ext`)
+        go to `slots`.  tables: per keyframe dict(K, bounds, scale_factors, level_sigma2, inv_level_sigma2, log_scale_factor).
+        Returns what put_device returns."""
+        frames = np.ascontiguousarray(frames, np.int32); slots = np.ascontiguousarray(slots, np.int32)
+        assert frames.ndim == 1 and slots.ndim == 1 and len(frames) == len(slots) == len(tables)
+        arr, keep = self.device_records([dict(t, kps=None, desc=None, n=None, count=0) for t in tables])
+        outs, bufs = self._bow_outs(len(tables))
+        check(self.L.dvm_keyframe_store_put_tracked(self.h, tracker.t, ext.h, voc.h, int(levelsup), len(slots), _p(frames), _p(slots), C.addressof(arr),
+                                                    C.addressof(outs)))
+        return self._bow_results(outs[:len(tables)], bufs)
+
+    def last_put_bytes(self):
+        """Host-to-device bytes of the last put or put_device that reached the device."""
+        b = C.c_int64(0)
+        check(self.L.dvm_keyframe_store_last_put_bytes(self.h, C.byref(b)))
+        return b.value
+
+    def profile(self, on=True):
+        check(self.L.dvm_keyframe_store_profile(self.h, int(on)))
+
+    def last_put_ms(self):
+        """(check, transform, bow, put) milliseconds of the last put_device that ran with profiling on (its first round)."""
+        ms = (C.c_float * 4)()
+        check(self.L.dvm_keyframe_store_last_put_ms(self.h, ms))
+        return tuple(ms)
 
     def remove(self, slots):
         slots = np.ascontiguousarray(slots, np.int32)

@@ -10,6 +10,10 @@
 //            store's stream wait for `read_ev` (the last kernel a chain queued to read the store), sends ONE copy to the staging block's
 //            device twin, launches k_kfs_put there and records `write_ev`.  It returns without waiting; the next round (or put) waits on
 //            the host for `write_ev` before it touches the staging block again.
+//   put_device  the keyframe's arrays are in device memory (kfs_put_device_run; keyframe_put_kernels.hip): the same wait for `read_ev`, an
+//            event behind the stream that produced the arrays, ONE copy of the item records and level tables, the launches, `write_ev`
+//            -- and then ONE synchronisation, because the host record of a slot (n, fv_n, n_feat) and the BowVector / FeatureVector the
+//            caller gets come from mapped memory the kernels wrote.  A call the first kernel refuses changes no slot and no record.
 //   a chain  kfs_read_begin: its stream waits for `write_ev`; kfs_read_end: `read_ev` recorded behind its reading kernels.
 // Safety: per slot the host keeps a written flag, a generation and the counts the kernels index with; every slot a call names is checked
 // BEFORE anything is queued, and every count of a put is bounded by slot_keypoints, so no kernel runs on an unchecked value.
@@ -17,6 +21,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/dvmslam_hip.h"
@@ -50,6 +55,14 @@ struct dvm_keyframe_store {
   std::vector<SlotMeta> meta;
   std::vector<uint32_t> stamp; uint32_t call = 0;  // per slot: the put call that named it last (a slot named twice in one call)
   std::vector<uint8_t> seen;                       // [K] scratch of the listed-once scan
+  int64_t last_h2d = 0;                            // dvm_keyframe_store_last_put_bytes
+  // ---- put_device (allocated by the first one): the upload ([KfsDevHead][capacity KfsDevItem], page-locked + device twin), the
+  // transform's scratch for a round of keyframes, the mapped results of every keyframe a call can name, the event behind the caller's stream
+  uint8_t *dv_hup = nullptr, *dv_dup = nullptr;
+  uint8_t* dv_scratch = nullptr; int dv_round = 0;
+  uint8_t *dv_hout = nullptr, *dv_dout = nullptr; size_t dv_out_stride = 0;
+  hipEvent_t src_ev = nullptr;
+  hipEvent_t tev[5] = {}; bool timing = false; float last_ms[4] = {0, 0, 0, 0};
   uint8_t* slot_base(int32_t sl) const { return d + (size_t)sl * L.stride; }
   // the staging block is the host's again: the last round's copy has read it
   int staging_free() {
@@ -137,7 +150,183 @@ int check_keyframe(const char* fn, const dvm_kfs_keyframe& k, const std::string&
   }
   return DVM_OK;
 }
+
+// ---- put_device
+// one keyframe's mapped results: the counts, then the BowVector and the FeatureVector, each sized for K keypoints and rounded up
+dvm::KfsDevOut carve_dev_out(uint8_t* base, size_t K, size_t* bytes) {
+  Cursor<kKfsAlign> c{base};
+  KfsDevOut o{};
+  o.res = c.carve<KfsDevRes>(1);
+  o.bow_ids = c.carve<int32_t>(K); o.bow_vals = c.carve<double>(K);
+  o.fv_node = c.carve<int32_t>(K); o.fv_off = c.carve<int32_t>(K + 1); o.fv_feat = c.carve<int32_t>(K);
+  if (bytes) *bytes = c.used();
+  return o;
+}
+KfsDevScratch carve_dev_scratch(uint8_t* base, size_t round, size_t K, size_t* bytes) {
+  Cursor<kKfsAlign> c{base};
+  KfsDevScratch w{};
+  w.w = c.carve<double>(round * K); w.word = c.carve<int32_t>(round * K); w.node = c.carve<int32_t>(round * K);
+  if (bytes) *bytes = c.used();
+  return w;
+}
+// the first put_device of a store reserves what the form needs
+int dev_reserve(const char* fn, dvm_keyframe_store* st) {
+  if (st->dv_hup) return DVM_OK;
+  const size_t C = (size_t)st->capacity, K = (size_t)st->K, up = sizeof(KfsDevHead) + C * sizeof(KfsDevItem);
+  size_t out_stride = 0, scratch = 0;
+  carve_dev_out(nullptr, K, &out_stride);
+  const int round = std::min(st->capacity, kStageKeyframes);
+  carve_dev_scratch(nullptr, (size_t)round, K, &scratch);
+  uint8_t *hup = nullptr, *dup = nullptr, *sc = nullptr, *hout = nullptr, *dout = nullptr;
+  hipEvent_t ev = nullptr;
+  const bool ok = hipHostMalloc(reinterpret_cast<void**>(&hup), up, hipHostMallocDefault) == hipSuccess &&
+                  hipMalloc(reinterpret_cast<void**>(&dup), up) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&sc), scratch) == hipSuccess &&
+                  hipHostMalloc(reinterpret_cast<void**>(&hout), C * out_stride, hipHostMallocMapped) == hipSuccess &&
+                  hipHostGetDevicePointer(reinterpret_cast<void**>(&dout), hout, 0) == hipSuccess &&
+                  hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    if (hup) (void)hipHostFree(hup);
+    if (dup) (void)hipFree(dup);
+    if (sc) (void)hipFree(sc);
+    if (hout) (void)hipHostFree(hout);
+    if (ev) (void)hipEventDestroy(ev);
+    return fail(fn, DVM_ERR_CAPACITY, "the working set of the device put (item table, transform scratch, mapped results)");
+  }
+  std::memset(hout, 0, C * out_stride);
+  st->dv_hup = hup; st->dv_dup = dup; st->dv_scratch = sc; st->dv_round = round; st->dv_hout = hout; st->dv_dout = dout; st->dv_out_stride = out_stride;
+  st->src_ev = ev;
+  return DVM_OK;
+}
 }  // namespace
+
+namespace dvm {
+int vocab_device(const dvm_vocab* v);           // capi.cpp: the vocabulary's device and its transform of device features (count on the device)
+void vocab_launch_transform(const dvm_vocab* v, hipStream_t s, const uint8_t* d_feat, int cap, const int32_t* d_n, int levelsup, int32_t* word_id,
+                            int32_t* node_id, double* weight, const int32_t* run, int nrun, int64_t feat_stride);
+
+int kfs_put_device_run(const char* fn, dvm_keyframe_store* st, const dvm_vocab* voc, int levelsup, hipStream_t src, int n, const int32_t* slots,
+                       const dvm_kfs_device_keyframe* kfs, dvm_kfs_bow_out* outs) {
+  if (!st || !voc || n < 0 || (n && (!slots || !kfs))) return fail(fn, DVM_ERR_INVALID, "missing argument");
+  if (n == 0) return DVM_OK;
+  // what the host can see of the batch is decided before anything is queued
+  if (++st->call == 0) { std::fill(st->stamp.begin(), st->stamp.end(), 0u); st->call = 1; }
+  const int K = st->K;
+  for (int k = 0; k < n; k++) {
+    const int32_t sl = slots[k];
+    const dvm_kfs_device_keyframe& f = kfs[k];
+    const std::string w = "keyframe " + std::to_string(k) + " (slot " + std::to_string(sl) + ")";
+    if (sl < 0 || sl >= st->capacity) return fail(fn, DVM_ERR_INVALID, w + ": slot outside [0, capacity)");
+    if (st->stamp[sl] == st->call) return fail(fn, DVM_ERR_INVALID, w + ": slot named twice in one call");
+    st->stamp[sl] = st->call;
+    if (f.n < 0) return fail(fn, DVM_ERR_INVALID, w + ": negative n");
+    if (!f.d_n && f.n > K) return fail(fn, DVM_ERR_CAPACITY, w + ": " + std::to_string(f.n) + " keypoints beyond slot_keypoints " + std::to_string(K));
+    if (f.n_levels < 1 || f.n_levels > 64) return fail(fn, DVM_ERR_INVALID, w + ": n_levels outside [1, 64]");
+    if (!f.scale_factors || !f.level_sigma2 || !f.inv_level_sigma2) return fail(fn, DVM_ERR_INVALID, w + ": missing level table");
+    if (!(f.max_x > f.min_x) || !(f.max_y > f.min_y)) return fail(fn, DVM_ERR_INVALID, w + ": image bounds empty");
+    if (f.n > 0 && (!f.d_kps || !f.d_desc)) return fail(fn, DVM_ERR_INVALID, w + ": missing keypoint array");
+    if (((reinterpret_cast<uintptr_t>(f.d_kps) | reinterpret_cast<uintptr_t>(f.d_desc) | reinterpret_cast<uintptr_t>(f.d_n)) & 3) != 0)
+      return fail(fn, DVM_ERR_INVALID, w + ": an array not aligned to 4 bytes");
+  }
+  if (vocab_device(voc) != st->device) return fail(fn, DVM_ERR_INVALID, "the vocabulary lives on another device");
+  DVM_HIP(hipSetDevice(st->device));
+  { const int rc = dev_reserve(fn, st); if (rc != DVM_OK) return rc; }
+  // the one upload: the flag, then per keyframe the item record and the three level tables
+  KfsDevHead* hh = reinterpret_cast<KfsDevHead*>(st->dv_hup);
+  KfsDevItem* hi = reinterpret_cast<KfsDevItem*>(st->dv_hup + sizeof(KfsDevHead));
+  KfsDevHead* dh = reinterpret_cast<KfsDevHead*>(st->dv_dup);
+  KfsDevItem* di = reinterpret_cast<KfsDevItem*>(st->dv_dup + sizeof(KfsDevHead));
+  std::memset(hh, 0, sizeof(*hh));
+  hh->flag = kKfsDevNoFlag;
+  for (int k = 0; k < n; k++) {
+    const dvm_kfs_device_keyframe& f = kfs[k];
+    KfsDevItem& it = hi[k];
+    std::memset(&it, 0, sizeof(it));
+    it.kps = reinterpret_cast<const dvm_keypoint_pod*>(f.d_kps); it.desc = f.d_desc; it.d_n = f.d_n;
+    it.slot = st->slot_base(slots[k]);
+    it.cap = f.n; it.n_levels = f.n_levels;
+    it.minX = f.min_x; it.minY = f.min_y;
+    it.wInv = static_cast<float>(64) / static_cast<float>(f.max_x - f.min_x);   // Frame.cc:443-444, as dvm_frame_build
+    it.hInv = static_cast<float>(48) / static_cast<float>(f.max_y - f.min_y);
+    std::memcpy(it.sf, f.scale_factors, (size_t)f.n_levels * 4);
+    std::memcpy(it.sigma2, f.level_sigma2, (size_t)f.n_levels * 4);
+    std::memcpy(it.inv_sigma2, f.inv_level_sigma2, (size_t)f.n_levels * 4);
+  }
+  const size_t up = sizeof(KfsDevHead) + (size_t)n * sizeof(KfsDevItem), os = st->dv_out_stride;
+  hipStream_t s = st->s;
+  if (st->read_pending) {                                          // behind the chain kernels that read the slots
+    DVM_HIP(hipStreamWaitEvent(s, st->read_ev, 0));
+    st->read_pending = false;
+  }
+  DVM_HIP(hipEventRecord(st->src_ev, src));                        // behind what produced the arrays
+  DVM_HIP(hipStreamWaitEvent(s, st->src_ev, 0));
+  DVM_HIP(hipMemcpyAsync(st->dv_dup, st->dv_hup, up, hipMemcpyHostToDevice, s));
+  st->last_h2d = (int64_t)up;
+  const bool tm = st->timing;
+  const KfsDevOut out_dev = carve_dev_out(st->dv_dout, (size_t)K, nullptr);
+  if (tm) DVM_HIP(hipEventRecord(st->tev[0], s));
+  launch_kfs_dev_check(s, dh, di, n, K, out_dev.res, os);
+  if (tm) DVM_HIP(hipEventRecord(st->tev[1], s));
+  const KfsDevScratch W = carve_dev_scratch(st->dv_scratch, (size_t)st->dv_round, (size_t)K, nullptr);
+  for (int first = 0; first < n; first += st->dv_round) {
+    const int m = std::min(st->dv_round, n - first);
+    for (int r = 0; r < m; r++) {
+      const dvm_kfs_device_keyframe& f = kfs[first + r];
+      vocab_launch_transform(voc, s, f.d_desc, std::min(f.n, K), &di[first + r].count, levelsup, W.word + (size_t)r * K, W.node + (size_t)r * K,
+                             W.w + (size_t)r * K, nullptr, 1, 0);
+    }
+    if (tm && first == 0) DVM_HIP(hipEventRecord(st->tev[2], s));
+    KfsDevOut o = out_dev;
+    const size_t ob = (size_t)first * os;
+    auto mv = [ob](auto*& p) { p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uint8_t*>(p) + ob); };
+    mv(o.res); mv(o.bow_ids); mv(o.bow_vals); mv(o.fv_node); mv(o.fv_off); mv(o.fv_feat);
+    if (!launch_kfs_dev_bow(s, dh, di, first, m, K, W, st->L, o, os)) {
+      (void)hipStreamSynchronize(s);
+      return fail(fn, DVM_ERR_CAPACITY, "the LDS of the FeatureVector sort (16 B per keypoint of the slot size rounded up to a power of two)");
+    }
+    if (tm && first == 0) DVM_HIP(hipEventRecord(st->tev[3], s));
+    launch_kfs_dev_put(s, dh, di, first, m, st->L, o.res, os);
+    if (tm && first == 0) DVM_HIP(hipEventRecord(st->tev[4], s));
+  }
+  { const int rc = hip_check(hipGetLastError(), "the device put's launches"); if (rc != DVM_OK) return rc; }
+  DVM_HIP(hipEventRecord(st->write_ev, s));
+  st->write_pending = true;
+  // the ONE synchronisation: the flag, the counts, the BowVector and the FeatureVector lie in mapped memory behind it
+  DVM_HIP(hipStreamSynchronize(s));
+  st->write_pending = false;
+  if (tm)
+    for (int i = 0; i < 4; i++) DVM_HIP(hipEventElapsedTime(&st->last_ms[i], st->tev[i], st->tev[i + 1]));
+  const KfsDevOut out_host = carve_dev_out(st->dv_hout, (size_t)K, nullptr);
+  auto host_at = [&](auto* p, int k) { return reinterpret_cast<decltype(p)>(reinterpret_cast<uint8_t*>(p) + (size_t)k * os); };
+  const int32_t flag = host_at(out_host.res, 0)->flag;
+  if (flag != kKfsDevNoFlag) {
+    const int k = flag >> 1;
+    const std::string w = "keyframe " + std::to_string(k) + " (slot " + std::to_string(k < n ? slots[k] : -1) + ")";
+    if (flag & 1) return fail(fn, DVM_ERR_INVALID, w + ": a keypoint's octave outside the level tables; no slot of the call written");
+    return fail(fn, DVM_ERR_CAPACITY, w + ": " + std::to_string(k < n ? host_at(out_host.res, k)->n : 0) + " keypoints beyond slot_keypoints " +
+                                          std::to_string(K) + "; no slot of the call written");
+  }
+  for (int k = 0; k < n; k++) {
+    const dvm_kfs_device_keyframe& f = kfs[k];
+    const KfsDevRes& R = *host_at(out_host.res, k);
+    SlotMeta& M = st->meta[slots[k]];
+    M.written = 1; M.gen++;
+    M.n = R.n; M.fv_n = R.n_fv; M.n_feat = R.n_feat; M.n_levels = f.n_levels;
+    M.fv_once = 1;                                                 // a feature lies in one node: the transform gives each feature one
+    M.fx = f.fx; M.fy = f.fy; M.cx = f.cx; M.cy = f.cy;
+    M.min_x = f.min_x; M.max_x = f.max_x; M.min_y = f.min_y; M.max_y = f.max_y; M.log_scale_factor = f.log_scale_factor;
+    if (!outs) continue;
+    dvm_kfs_bow_out& o = outs[k];
+    o.n = R.n; o.n_bow = R.n_bow; o.n_fv = R.n_fv; o.n_feat = R.n_feat;
+    if (o.bow_ids) std::memcpy(o.bow_ids, host_at(out_host.bow_ids, k), (size_t)R.n_bow * 4);
+    if (o.bow_vals) std::memcpy(o.bow_vals, host_at(out_host.bow_vals, k), (size_t)R.n_bow * 8);
+    if (o.fv_node) std::memcpy(o.fv_node, host_at(out_host.fv_node, k), (size_t)R.n_fv * 4);
+    if (o.fv_off) std::memcpy(o.fv_off, host_at(out_host.fv_off, k), ((size_t)R.n_fv + 1) * 4);
+    if (o.fv_feat) std::memcpy(o.fv_feat, host_at(out_host.fv_feat, k), (size_t)R.n_feat * 4);
+  }
+  return DVM_OK;
+}
+}  // namespace dvm
 
 extern "C" {
 
@@ -187,6 +376,12 @@ void dvm_keyframe_store_destroy(dvm_keyframe_store* st) {
   if (st->d) (void)hipFree(st->d);
   if (st->ds) (void)hipFree(st->ds);
   if (st->hs) (void)hipHostFree(st->hs);
+  if (st->dv_dup) (void)hipFree(st->dv_dup);
+  if (st->dv_scratch) (void)hipFree(st->dv_scratch);
+  if (st->dv_hup) (void)hipHostFree(st->dv_hup);
+  if (st->dv_hout) (void)hipHostFree(st->dv_hout);
+  if (st->src_ev) (void)hipEventDestroy(st->src_ev);
+  for (hipEvent_t e : st->tev) if (e) (void)hipEventDestroy(e);
   delete st;
 }
 
@@ -210,6 +405,7 @@ int dvm_keyframe_store_put(dvm_keyframe_store* st, int n, const int32_t* slots, 
   }
   DVM_HIP(hipSetDevice(st->device));
   KfsPutItem* items = reinterpret_cast<KfsPutItem*>(st->hs);
+  st->last_h2d = 0;
   for (int done = 0; done < n;) {
     { const int rc = st->staging_free(); if (rc != DVM_OK) return rc; }
     Cursor<kKfsAlign> c{st->hs, st->ds, st->item_bytes};
@@ -240,6 +436,7 @@ int dvm_keyframe_store_put(dvm_keyframe_store* st, int n, const int32_t* slots, 
     }
     // the items and the arrays in one copy (the gap between them, when the batch is smaller than the capacity, travels too: at most 48 B per slot)
     DVM_HIP(hipMemcpyAsync(st->ds, st->hs, c.used(), hipMemcpyHostToDevice, st->s));
+    st->last_h2d += (int64_t)c.used();
     launch_kfs_put(st->s, reinterpret_cast<const KfsPutItem*>(st->ds), m, st->L);
     { const int rc = hip_check(hipGetLastError(), "k_kfs_put"); if (rc != DVM_OK) return rc; }
     DVM_HIP(hipEventRecord(st->write_ev, st->s));
@@ -256,6 +453,32 @@ int dvm_keyframe_store_put(dvm_keyframe_store* st, int n, const int32_t* slots, 
     }
     done += m;
   }
+  return DVM_OK;
+}
+
+int dvm_keyframe_store_put_device(dvm_keyframe_store* st, const dvm_vocab* voc, int levelsup, void* stream, int n, const int32_t* slots,
+                                  const dvm_kfs_device_keyframe* kfs, dvm_kfs_bow_out* outs) {
+  return kfs_put_device_run("dvm_keyframe_store_put_device", st, voc, levelsup, (hipStream_t)stream, n, slots, kfs, outs);
+}
+
+int dvm_keyframe_store_last_put_bytes(const dvm_keyframe_store* st, int64_t* host_to_device) {
+  if (!st || !host_to_device) return DVM_ERR_INVALID;
+  *host_to_device = st->last_h2d;
+  return DVM_OK;
+}
+
+int dvm_keyframe_store_profile(dvm_keyframe_store* st, int enable) {
+  if (!st) return DVM_ERR_INVALID;
+  DVM_HIP(hipSetDevice(st->device));
+  if (enable)
+    for (hipEvent_t& e : st->tev) if (!e) DVM_HIP(hipEventCreate(&e));
+  st->timing = enable != 0;
+  return DVM_OK;
+}
+
+int dvm_keyframe_store_last_put_ms(const dvm_keyframe_store* st, float ms[4]) {
+  if (!st || !ms) return DVM_ERR_INVALID;
+  for (int i = 0; i < 4; i++) ms[i] = st->last_ms[i];
   return DVM_OK;
 }
 

@@ -46,4 +46,45 @@ struct KfsPutItem {
 // one workgroup per item: the staged arrays to the slot's (layout L), and the slot's grid by frame_build_block
 void launch_kfs_put(hipStream_t s, const KfsPutItem* items, int n_items, const KfSlotLayout& L);
 
+// ---- dvm_keyframe_store_put_device: the keyframe's arrays are in device memory already (keyframe_put_kernels.hip)
+// The one upload of a call: this head, then one KfsDevItem per keyframe.
+constexpr int32_t kKfsDevNoFlag = 0x7FFFFFFF;
+struct KfsDevHead {
+  int32_t flag;          // kKfsDevNoFlag, or (keyframe << 1 | what): the first keyframe of the call the device refuses; what = 0: its
+  int32_t pad[15];       // count exceeds slot_keypoints, 1: an octave outside [0, n_levels).  Raised by k_kfs_dev_check (atomicMin)
+};
+struct KfsDevItem {
+  const dvm_keypoint_pod* kps;     // the caller's arrays (4-byte aligned at least)
+  const uint8_t* desc;
+  const int32_t* d_n;              // the device count, or null: cap is the count
+  uint8_t* slot;
+  int32_t cap, n_levels;
+  float minX, minY, wInv, hInv;
+  int32_t count;                   // written by k_kfs_dev_check: the keyframe's keypoints (0 for a keyframe it refuses); the transform's d_n
+  int32_t pad;
+  float sf[kKfsLevels], sigma2[kKfsLevels], inv_sigma2[kKfsLevels];
+};                                 // 832 bytes: everything that travels up per keyframe
+// what the host reads of one keyframe after the call's one wait (mapped memory): the counts, then the BowVector and a copy of the
+// FeatureVector, each array sized for slot_keypoints
+struct KfsDevRes { int32_t n, n_bow, n_fv, n_feat, flag, pad[3]; };
+struct KfsDevOut {
+  KfsDevRes* res;                  // [1]
+  int32_t* bow_ids; double* bow_vals; int32_t *fv_node, *fv_off, *fv_feat;   // [K], [K], [K], [K + 1], [K]
+};
+// the scratch of a round of keyframes: k_vocab_transform's per-feature results, keyframe r of the round at r * K
+struct KfsDevScratch { int32_t* word; int32_t* node; double* w; };
+// one workgroup per keyframe of the call: items[k].count, res[k].n, the call's flag
+void launch_kfs_dev_check(hipStream_t s, KfsDevHead* head, KfsDevItem* items, int n_items, int K, KfsDevRes* res, size_t res_stride);
+// one 1 024-thread workgroup per keyframe of a round (items first .. first + m): ComputeBoW's bookkeeping, the FeatureVector into the
+// slot, the BowVector and a copy of the FeatureVector to out0 + r * out_stride bytes; false: the sort's LDS cannot be had
+bool launch_kfs_dev_bow(hipStream_t s, const KfsDevHead* head, const KfsDevItem* items, int first, int m, int K, const KfsDevScratch& W,
+                        const KfSlotLayout& L, const KfsDevOut& out0, size_t out_stride);
+// one 1 024-thread workgroup per keyframe of a round: keypoints, descriptors and tables into the slot, the slot's grid, res[k].flag
+void launch_kfs_dev_put(hipStream_t s, const KfsDevHead* head, const KfsDevItem* items, int first, int m, const KfSlotLayout& L,
+                        KfsDevRes* res0, size_t res_stride);
+
+// dvm_keyframe_store_put_device behind its name (track.cpp: dvm_keyframe_store_put_tracked calls it on the tracker's frames)
+int kfs_put_device_run(const char* fn, dvm_keyframe_store* st, const dvm_vocab* voc, int levelsup, hipStream_t src, int n, const int32_t* slots,
+                       const dvm_kfs_device_keyframe* kfs, dvm_kfs_bow_out* outs);
+
 }  // namespace dvm

@@ -53,6 +53,7 @@ using namespace dvm;
 // rkb_ready: any finish, until dvm_track_reference_keyframe_batch, the single call or the second half runs on it
 struct LocalFrame {
   int ready = 0, batch_ready = 0, rkb_ready = 0;
+  int kf_ready = 0;                              // the frames may be promoted (dvm_keyframe_store_put_tracked): set with the fields below, cleared by a begin ONLY
   dvm_orb* h = nullptr; uint64_t serial = 0;     // the extractor and which of its extractions the frame is
   int ocap = 0, nlevels = 0;
   const dvm_keypoint_pod* d_un = nullptr; const int32_t* d_n = nullptr;   // mvKeysUn on the device, the keypoint count
@@ -202,7 +203,7 @@ namespace {
 int begin_run(const char* fn, bool staged, dvm_tracker* t, dvm_orb* h, const uint8_t* imgs, int count, int rows, int cols, int stride, int64_t frame_stride, int lap0, int lap1) {
   if (!t || !h || count < 1) return DVM_ERR_INVALID;
   if (count > t->max_frames) { set_error(std::string(fn) + ": more frames than the tracker was created for"); return DVM_ERR_CAPACITY; }
-  t->begun = 0; t->clear_next();
+  t->begun = 0; t->clear_next(); t->lf.kf_ready = 0;
   const int rc = staged ? dvm_orb_extract_staged(h, count, rows, cols, lap0, lap1) : dvm_orb_extract_batch_host(h, imgs, count, rows, cols, stride, frame_stride, lap0, lap1);
   if (rc != DVM_OK) return rc;
   t->begun = count; t->rows = rows; t->cols = cols;
@@ -451,6 +452,7 @@ int finish_run(dvm_tracker* t, dvm_orb* h, int count, const dvm_track_queries* q
     f.monos.resize((size_t)count); f.poses.assign(m.pose_out, m.pose_out + 7 * (size_t)count);
     for (int b = 0; b < count; b++) { f.ns[b] = res[b].n; f.status[b] = res[b].status; f.monos[b] = res[b].mono_index; }
     f.d_desc = d_desc; f.desc_stride = desc_stride;
+    f.kf_ready = 1;
   }
   if (count == 1 && t->max_frames == 1) { t->rk_state = 2; t->rk_h = h; t->rk_serial = orb_result_serial(h); }   // (whatever the status)
   return DVM_OK;
@@ -1072,6 +1074,7 @@ int dvm_track_reference_keyframe(dvm_tracker* t, dvm_orb* h, const dvm_vocab* vo
     std::memcpy(f.inv_sigma2, p->inv_level_sigma2, (size_t)p->nlevels * 4); f.cam = p->cam; f.model = t->model;
     f.count = 1; f.kps_stride = ocap; f.d_desc = d_desc; f.desc_stride = (int64_t)ocap * 32;
     f.ns.assign(1, 0); f.status.assign(1, 0); f.monos.assign(1, 0); f.poses.assign(7, 0.0);
+    f.kf_ready = 1;
   }
   // the batched chain on the one frame
   int32_t status = 0;
@@ -1152,6 +1155,32 @@ int dvm_track_reference_keyframe_batch_resident(dvm_tracker* t, dvm_orb* h, cons
   std::vector<RefKfSource> src((size_t)count);
   for (int b = 0; b < count; b++) src[b].r = kf[b];
   return refkf_batch_run("dvm_track_reference_keyframe_batch_resident", t, h, voc, count, src, kfs, ps, outs, res, status);
+}
+
+// Tracking::CreateNewKeyFrame on frames of the last finish: dvm_keyframe_store_put_device (keyframe_store.cpp) on the frames' mvKeysUn and
+// descriptors where the finish left them, behind the extractor's stream.  The flag is LocalFrame::kf_ready: only a begin clears it.
+int dvm_keyframe_store_put_tracked(dvm_keyframe_store* st, dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, int levelsup, int n, const int32_t* frames,
+                                   const int32_t* slots, const dvm_kfs_device_keyframe* tables, dvm_kfs_bow_out* outs) {
+  const char* fn = "dvm_keyframe_store_put_tracked";
+  if (!st || !t || !h || !voc || n < 0 || (n && (!frames || !slots || !tables))) { set_error(std::string(fn) + ": missing argument"); return DVM_ERR_INVALID; }
+  const LocalFrame& f = t->lf;
+  if (!f.kf_ready || f.h != h || orb_result_serial(h) != f.serial) {
+    set_error(std::string(fn) + ": not after a dvm_track_finish[_batch] or form (a) of dvm_track_reference_keyframe on this tracker and extractor, "
+                                "or a begin has run since");
+    return DVM_ERR_STATE;
+  }
+  if (kfs_device(st) != t->device) { set_error(std::string(fn) + ": the store lives on another device"); return DVM_ERR_INVALID; }
+  std::vector<dvm_kfs_device_keyframe> kfs((size_t)n);
+  for (int k = 0; k < n; k++) {
+    const int b = frames[k];
+    if (b < 0 || b >= f.count) { set_error(std::string(fn) + ": keyframe " + std::to_string(k) + ": frame outside [0, count)"); return DVM_ERR_INVALID; }
+    kfs[k] = tables[k];
+    kfs[k].d_kps = reinterpret_cast<const dvm_keypoint*>(f.d_un + (size_t)b * f.kps_stride);
+    kfs[k].d_desc = f.d_desc + (size_t)b * f.desc_stride;
+    kfs[k].d_n = f.d_n + b;
+    kfs[k].n = f.ocap;
+  }
+  return kfs_put_device_run(fn, st, voc, levelsup, (hipStream_t)dvm_orb_stream(h), n, slots, kfs.data(), outs);
 }
 
 int dvm_tracker_last_refkf_upload_bytes(const dvm_tracker* t, int64_t* bytes) {

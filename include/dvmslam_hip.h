@@ -1148,6 +1148,59 @@ int dvm_keyframe_store_put(dvm_keyframe_store* s, int n, const int32_t* slots, c
 int dvm_keyframe_store_remove(dvm_keyframe_store* s, int n, const int32_t* slots);
 int dvm_keyframe_store_debug_read(dvm_keyframe_store* s, int slot, dvm_kfs_readback* out);
 
+/* ---- A put straight from device memory: when Tracking::CreateNewKeyFrame promotes the current frame, its mvKeysUn and descriptors lie
+ * in device memory (the extractor's result, the tracker's frame after a finish) and KeyFrame::ComputeBoW is device code.
+ * dvm_keyframe_store_put_device computes the BowVector and the FeatureVector on the device and fills the slot there; per keyframe the
+ * item record and the three level tables travel up (832 B, nothing per keypoint), the BowVector and the FeatureVector come down
+ * (KeyFrameDatabase::add and the host mirrors need them).
+ *   put_device  kfs[k] goes to slot slots[k].  The outcome equals dvm_keyframe_store_put of the same keyframe with fv_* set to what
+ *             dvmh_vocab_transform(features = desc, levelsup) returns: every array dvm_keyframe_store_debug_read returns is equal bit
+ *             for bit, and the slot serves every resident chain (a feature lies in ONE node by construction).  `stream` is the stream
+ *             that produced the arrays (NULL: the null stream); the work is ordered behind it by an event and runs on the STORE'S OWN
+ *             STREAM under the store's ordering rule (it waits for the last reader, readers wait for it).  Four kinds of launches:
+ *             k_kfs_dev_check (the count and the octaves of every keyframe of the call), k_vocab_transform per keyframe,
+ *             k_kfs_dev_bow (ComputeBoW's bookkeeping, the FeatureVector into the slot), k_kfs_dev_put (keypoints, descriptors,
+ *             tables, the grid).  Unlike put the call synchronises, ONCE: the host's slot record and `outs` are read from mapped
+ *             memory after that wait.  Checked on the host before anything is queued, each naming the keyframe: DVM_ERR_INVALID --
+ *             a slot outside [0, capacity) or named twice, n < 0, a NULL or not 4-byte-aligned array with n > 0, n_levels outside
+ *             [1, 64], empty bounds, a missing table, a vocabulary on another device; DVM_ERR_CAPACITY -- a host n beyond
+ *             slot_keypoints.  Seen on the device only, by the first kernel, which raises one flag for the call: a count
+ *             min(*d_n, n) beyond slot_keypoints (DVM_ERR_CAPACITY), a keypoint's octave outside [0, n_levels) (DVM_ERR_INVALID);
+ *             the later kernels of the call then return at once, the error names the first such keyframe, and NO slot of the
+ *             call is written: each keeps its content and its generation.
+ *   put_tracked  put_device on frames frames[k] of the tracker's last finish, ordered behind dvm_orb_stream(h).  Accepted after a
+ *             dvm_track_finish / dvm_track_finish_batch (any form) or after form (a) of dvm_track_reference_keyframe, until the
+ *             tracker's next begin; the second-half and reference-keyframe calls in between do not end it.  DVM_ERR_STATE otherwise,
+ *             and when h or its extraction is not the one the finish ran on; DVM_ERR_INVALID for a frame outside [0, count).  The
+ *             camera, the bounds and the level tables are tables[k]'s (its d_* and n are ignored): nothing is read silently from the tracker.
+ *   last_put_bytes  host-to-device bytes of the last put or put_device that reached the device.
+ *   profile / last_put_ms  with profiling on, put_device records events around its launches; ms[0..3] = check, transform, bow, put of
+ *             the last call's first round (a round: up to 32 keyframes).
+ * sizeof(dvm_kfs_device_keyframe) == 96, sizeof(dvm_kfs_bow_out) == 56 (LP64). */
+typedef struct {                 /* one keyframe whose arrays are in device memory */
+  const dvm_keypoint* d_kps;     /* mvKeysUn, device */
+  const uint8_t* d_desc;         /* n x 32, device */
+  const int32_t* d_n;            /* device count (as dvm_orb_result_device), or NULL: n below is used */
+  int32_t n;                     /* host count when d_n == NULL; else the capacity of the two arrays (count = min(*d_n, n)) */
+  float fx, fy, cx, cy, min_x, max_x, min_y, max_y;
+  const float *scale_factors, *level_sigma2, *inv_level_sigma2;   /* host, [n_levels] */
+  float log_scale_factor; int32_t n_levels;
+} dvm_kfs_device_keyframe;
+typedef struct {                 /* host buffers, each may be NULL; sized for slot_keypoints (+1 for fv_off) */
+  int32_t n, n_bow, n_fv, n_feat;             /* written always */
+  int32_t* bow_ids; double* bow_vals;         /* mBowVec, ascending word */
+  int32_t *fv_node, *fv_off, *fv_feat;        /* mFeatVec as dvmh_vocab_transform returns it */
+} dvm_kfs_bow_out;
+int dvm_keyframe_store_put_device(dvm_keyframe_store* s, const dvm_vocab* voc, int levelsup, void* stream,
+                                  int n, const int32_t* slots, const dvm_kfs_device_keyframe* kfs, dvm_kfs_bow_out* outs);
+int dvm_keyframe_store_put_tracked(dvm_keyframe_store* s, dvm_tracker* t, dvm_orb* h, const dvm_vocab* voc, int levelsup,
+                                   int n, const int32_t* frames, const int32_t* slots,
+                                   const dvm_kfs_device_keyframe* tables /* scalars + level tables only; d_* and n ignored */,
+                                   dvm_kfs_bow_out* outs);
+int dvm_keyframe_store_last_put_bytes(const dvm_keyframe_store* s, int64_t* host_to_device);
+int dvm_keyframe_store_profile(dvm_keyframe_store* s, int enable);
+int dvm_keyframe_store_last_put_ms(const dvm_keyframe_store* s, float ms[4]);
+
 /* ---- The Fuse chain on resident targets: dvm_fuse_targets_set_cam with every target given as a store slot plus what changes between
  * two LocalMapping steps, its pose.  The host fills the target table with pointers into the store and uploads that table alone: no
  * keypoint travels, no grid is built, no per-keypoint host loop runs.  dvm_fuse_targets_run / _run_hits are then used as they are.
