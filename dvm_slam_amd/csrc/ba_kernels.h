@@ -170,8 +170,12 @@ void ba_launch_pose_optimize_kb8(hipStream_t s, const double* pose_in, const dou
 
 }  // namespace dvm
 
-// csrc/ba_window.hip: dvm_ba_optimize_windows with the choice of normalising the input quaternions (a fresh graph: SE3Quat's
-// constructor does) or taking them as they are (the state a previous optimize() of the same graph left)
 #include "../../include/dvmslam_hip.h"
-int dvm_ba_optimize_windows_impl(int device, const dvm_ba_window* windows, int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats, bool normalize_input, bool fast, int cluster,
-                                 const dvm_camera_model* models = nullptr);
+// csrc/ba_window_seq.hip: dvm_ba_optimize_windows with the choice of normalising the input quaternions (a fresh graph: SE3Quat's
+// constructor does) or taking them as they are (the state a previous optimize() of the same graph left)
+int ba_windows_seq(int device, const dvm_ba_window* windows, int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats, bool normalize_input);
+// csrc/ba_window_cluster.hip: dvm_ba_optimize_windows_fast[_cam].  cluster > 0: that many workgroups per window, else chosen by
+// ba_cluster_size from the call's own grid; models NULL: pinhole windows, else the camera model of every window
+int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats, int cluster, const dvm_camera_model* models);
+// the largest of 8 / 4 / 2 / 1 workgroups per window for which `groups` windows' workgroups are resident at once; `forced` > 0 or DVM_BA_CLUSTER decide otherwise
+int ba_cluster_size(int device, int groups, int forced);

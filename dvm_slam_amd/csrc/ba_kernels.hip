@@ -12,7 +12,7 @@
 //   sharded solve              k_pack_tiles, k_hpp_diag, k_points_exchange
 // All accumulations are gathers with a fixed order: results are run-to-run deterministic.
 // The other FP64 optimisers live in files of their own: pose_kernels.hip (PoseOptimization), sim3_kernels.hip (OptimizeSim3, Sim3Solver),
-// pg_kernels.hip (essential graph), ba_window.hip (small windows); the small algebra they share is se3_f64.h's.
+// pg_kernels.hip (essential graph), ba_window_seq.hip / ba_window_cluster.hip (windows); the small algebra they share is se3_f64.h's.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -236,7 +236,7 @@ __global__ void __launch_bounds__(256) k_edge_eval(BaView V, BaPublish pub) {
 __device__ __forceinline__ void dinv_apply(const double* H, const double* bl, double lambda, double* __restrict__ D, double* __restrict__ db) {
   const double M[9] = {H[0] + lambda, H[1], H[2], H[3], H[4] + lambda, H[5], H[6], H[7], H[8] + lambda};
   double o[9];
-  inv3(M, o);     // (the operations of ba_window.hip's w_dinv in the same order: the same bits)
+  inv3(M, o);     // (the operations of ba_window_cluster.hip's w_dinv in the same order: the same bits)
 #pragma unroll
   for (int k = 0; k < 9; k++) D[k] = o[k];
   mat3_vec(o, bl, db);

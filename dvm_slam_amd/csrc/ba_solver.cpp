@@ -69,7 +69,7 @@ struct dvm_ba {
   uint8_t* h_flags = nullptr;               // ONE page-locked staging slot of E bytes for them, reserved with the problem and reused by every call
   bool have_problem = false;
   double ms_structure = 0;
-  // Window mode (csrc/ba_window.hip): a problem with a handful of free cameras -- the two-keyframe global BA of a monocular
+  // Window mode (csrc/ba_window_seq.hip): a problem with a handful of free cameras -- the two-keyframe global BA of a monocular
   // initialisation, the first local windows -- is solved by the sequential-order kernel, whose result is bit-identical to g2o's
   // summation order: with one or two free cameras the gauge is held by the damping alone and any other order lands 1e-3 and more
   // away.  The state then lives in these host copies between calls; the tile solver's device arrays are
@@ -616,7 +616,7 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
   h->have_problem = true;
   {
     static const int max_free = [] { const char* e = std::getenv("DVM_BA_WINDOW_MAX_FREE"); return e ? std::atoi(e) : 6; }();
-    // (the sequential-order kernels of ba_window.hip are pinhole-only: what they promise is g2o's bits, and no two atan2f share those)
+    // (the sequential-order kernels of ba_window_seq.hip are pinhole-only: what they promise is g2o's bits, and no two atan2f share those)
     h->win_mode = world == 1 && !kb8 && V.nfree <= std::min(max_free, 30) && !std::getenv("DVM_BA_NO_WINDOW");
     h->win_device_stale = false;
     if (h->win_mode) {
@@ -768,7 +768,7 @@ int dvm_ba_optimize(dvm_ba* h, int iterations, const volatile uint8_t* stop_flag
     std::vector<double> po(h->ws_poses.size()), xo(h->ws_points.size());
     w.poses_out = po.data(); w.points_out = xo.data(); w.edge_chi2_out = h->ws_chi2.data(); w.depth_positive_out = h->ws_depth.data();
     dvm_ba_stats ws;
-    const int rc = dvm_ba_optimize_windows_impl(h->device, &w, 1, stop_flag, &ws, /*normalize_input=*/false, /*fast=*/false, /*cluster=*/0);
+    const int rc = ba_windows_seq(h->device, &w, 1, stop_flag, &ws, /*normalize_input=*/false);
     if (rc == DVM_ERR_CAPACITY && !h->win_device_stale) {
       // what the sequential-order kernel cannot hold (a landmark with more rows than a chunk: duplicate observations; an index block
       // beyond its staging area) the tile solver can: this problem is its from now on (round-4 advice)

@@ -5,7 +5,7 @@
 // driver calls pow(2 rho - 1, 3) (optimization_algorithm_levenberg.cpp:131) from libm.  No device libm returns glibc's bits: glibc's
 // sin / cos / pow are faithfully (< 1 ulp) but not correctly rounded -- pow(x, 3) differs from the correctly rounded cube on 0.08 % of
 // random arguments (tools/dev note in DESIGN.md) -- and ROCm's ocml rounds differently again.  A bundle adjustment that is to be
-// BIT-IDENTICAL to its CPU restatement (csrc/ba_window.hip) cannot call either; both sides evaluate this spec instead:
+// BIT-IDENTICAL to its CPU restatement (csrc/ba_window_seq.hip) cannot call either; both sides evaluate this spec instead:
 //   * f64_sin / f64_cos: fdlibm's __kernel_sin / __kernel_cos (Sun, 1993: < 1 ulp on |x| <= pi/4) behind fdlibm's medium-size
 //     argument reduction by pi/2 in two pieces (first 33 bits + tail: exact for |x| < 2^19 pi/2), Horner form, every product and sum
 //     written out -- compiled with -ffp-contract=off on both sides;

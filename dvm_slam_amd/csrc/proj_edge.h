@@ -1,7 +1,7 @@
 // dvm_slam_amd/csrc/proj_edge.h -- the reprojection edge of the FP64 optimisers, ONE definition: the camera (PoseCamPinhole / PoseCamKB8)
 // and what EdgeSE3ProjectXYZ / EdgeSE3ProjectXYZOnlyPose compute with it (OptimizableTypes.cpp:51-63,136-155): the point in the camera
 // frame, the residual, chi2, and the Jacobians A (2x3, landmark) and B (2x6, pose).  Its users -- k_edge_eval (ba_kernels.hip),
-// pose_optimize_block (pose_kernels.hip), win_edge_pass and cl_edge_pass (ba_window.hip) -- keep only what is theirs: where the rows go,
+// pose_optimize_block (pose_kernels.hip), win_edge_pass (ba_window_seq.hip) and cl_edge_pass (ba_window_cluster.hip) -- keep only what is theirs: where the rows go,
 // which edges are active, what is accumulated.  Three of them promise g2o's bits: the expressions and their order are the oracle's.
 #pragma once
 #include <hip/hip_runtime.h>

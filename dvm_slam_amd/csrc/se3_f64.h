@@ -1,4 +1,4 @@
-// dvm_slam_amd/csrc/se3_f64.h -- the FP64 small algebra of the optimisers (ba_kernels.hip, ba_window.hip, pose_kernels.hip, sim3_f64.h):
+// dvm_slam_amd/csrc/se3_f64.h -- the FP64 small algebra of the optimisers (ba_kernels.hip, ba_window_seq.hip, ba_window_cluster.hip, pose_kernels.hip, sim3_f64.h):
 // quaternion <-> rotation, SE3 oplus, Huber, the 3x3 inverse.  ONE definition each: the sequential-order window kernels promise g2o's
 // bits, so every expression keeps the oracle's order and every libm call is f64_spec.h's (-ffp-contract=off: one IEEE rounding each).
 #pragma once

@@ -1,4 +1,4 @@
-"""dvm_ba_optimize_windows (csrc/ba_window.hip): K independent bundle adjustments in one launch, every sum in g2o's sequential order ->
+"""dvm_ba_optimize_windows (csrc/ba_window_seq.hip): K independent bundle adjustments in one launch, every sum in g2o's sequential order ->
 BIT-IDENTICAL to the CPU oracle: poses, points, per-edge chi2, the LM trial sequence, chi2 and lambda of every iteration.  The cases
 are the ones the 1e-6 tolerance cannot cover: the two-keyframe GlobalBundleAdjustemnt(map, 20) of a monocular
 initialisation (Tracking.cc:2330), local windows of 3..5 keyframes (Optimizer.cc:1030), weak-gauge toys whose result moves by 1e-3 and

@@ -1,4 +1,4 @@
-"""dvm_ba_optimize_windows_fast (csrc/ba_window.hip, k_ba_window<true>): K LocalBundleAdjustment windows in ONE launch, a workgroup per
+"""dvm_ba_optimize_windows_fast (csrc/ba_window_cluster.hip, k_ba_window_cluster): K LocalBundleAdjustment windows in ONE launch, a workgroup per
 window, the LM control on the device, every sum a tree in a fixed order (reference: Optimizer.cc:1030-1387 per window; g2o
 block_solver.hpp:381-483, optimization_algorithm_levenberg.cpp:59-165).  Contract: the general solver's -- the oracle's LM trial
 sequence, poses / landmarks within 1e-6, chi2 within 1e-9 relative -- and determinism (the same bits run to run, and for a window
@@ -196,7 +196,7 @@ def test_fast_windows_do_not_depend_on_the_placement(windows, monkeypatch):
 
 
 def test_fast_windows_with_tables_in_blocks_of_their_own(oracle, windows, monkeypatch):
-    """The windows' tables travel in one page-locked block sized from the edge counts before they are built (csrc/ba_window.hip:
+    """The windows' tables travel in one page-locked block sized from the edge counts before they are built (csrc/ba_window_cluster.hip:
     shared_tables); a window that finds it full -- its (edge, edge) pair list far beyond the estimate -- packs into a block of its own,
     sent on its own.  DVM_BA_TEST_PRIVATE_TABLES makes every second window of a call take that path: the same bits as without it."""
     pr = synth.ba_problem(n_kf=32, n_pts=260, k_obs=32, seed=0x3D1, radius=12.0)

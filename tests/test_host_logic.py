@@ -93,6 +93,17 @@ def test_track_frame_epilogue(tmp_path):
         assert "all frames as written" in out
 
 
+def test_ba_window_index_tables(tmp_path):
+    """dvm_slam_amd/csrc/ba_window_seq_tables.h and ba_window_cluster_tables.h (tools/check_ba_window_tables.cpp): the (block, row, row)
+    pairs of both forms are the direct enumeration of block_solver.hpp's Schur loop, every block's in landmark order; lpos / fpos are
+    permutations and every chunk respects C, C2 and kWinIntCap; the cluster form's sort is camera-major with the fixed cameras' edges
+    last, e_orig is a permutation and the wave schedule lists every task once -- from 1 to 30 free cameras, with a landmark seen twice
+    by one camera or only by fixed ones and with no edge at all; 31 free cameras and an out-of-range edge are refused."""
+    for out in _build_and_run_tool(tmp_path, "check_ba_window_tables", ["-Wall"]):
+        assert "window tables as the direct enumeration" in out
+        assert len(re.findall(r" ok$", out, re.M)) == 7 and out.count("refused (") == 3
+
+
 def test_generated_cholesky_panel_is_in_sync(tmp_path):
     """csrc/chol_panel.inc (the straight-line 16-column panel of k_chol_diag) is generated: the committed file must be what
     tools/gen_chol_panel.py writes, and the stream must hold the whole factorisation -- 16 reciprocal square roots, the 15

@@ -53,7 +53,7 @@ def main():
             nfree = int(((1 - fixed) & np.isin(np.arange(n_kf), pr["edge_pose"])).sum())
             same_lm = sg["iterations"] == so["iterations"] and sg["total_trials"] == so["total_trials"]
             if nfree <= 6:
-                # window mode (csrc/ba_window.hip): g2o's summation order -> the oracle's bits, whatever the conditioning
+                # window mode (csrc/ba_window_seq.hip): g2o's summation order -> the oracle's bits, whatever the conditioning
                 window_cases += 1
                 ok = (same_lm and np.array_equal(Pg.view(np.int64), Po.view(np.int64)) and np.array_equal(Xg.view(np.int64), Xo.view(np.int64)) and
                       np.array_equal(chig.view(np.int64), chio.view(np.int64)) and sg["chi2_final"] == so["chi2_final"] and sg["lambda_final"] == so["lambda_final"])
