@@ -1813,6 +1813,112 @@ class MapStore:
     __del__ = close
 
 
+BA_OBS_DTYPE = np.dtype([("pose", "<i4"), ("point", "<i4"), ("kp", "<i4")])      # == dvm_ba_obs
+
+
+class BaWindowResident(C.Structure):
+    """dvm_ba_window_resident (include/dvmslam_hip.h)"""
+    _fields_ = [("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32), ("iterations", C.c_int32),
+                ("poses", C.c_void_p), ("fixed", C.c_void_p), ("keyframes", C.c_void_p), ("kf_slot", C.c_void_p), ("ow", C.c_void_p),
+                ("points", C.c_void_p), ("mp_slot", C.c_void_p), ("obs", C.c_void_p), ("ref_edge", C.c_void_p), ("cam", BaCamera),
+                ("chi2_erase", C.c_double), ("poses_out", C.c_void_p), ("points_out", C.c_void_p), ("edge_chi2_out", C.c_void_p),
+                ("depth_positive_out", C.c_void_p), ("geometry_out", C.c_void_p), ("point_dirty_out", C.c_void_p), ("ow_out", C.c_void_p)]
+
+
+class BaResidentBatch:
+    """K resident windows marshalled once into the dvm_ba_window_resident array (BaWindowBatch's counterpart).  problems: the dicts of
+    ba_optimize_windows without points / edges, with kf_slots [P] + keyframe_store (a KeyframeStore), mp_slots [L] + map_store (a MapStore),
+    obs (BA_OBS_DTYPE), ref_edge [L] or None, ow [P, 3] or None, chi2_erase (default 5.991), model (a CameraModel) or intrinsics;
+    want_geometry=False: geometry_out and ow_out are NULL (the commit needs neither on the host) and the result arrays stay zeros."""
+
+    def __init__(self, problems):
+        K = len(problems)
+        self.K = K
+        self.wins = (BaWindowResident * max(K, 1))()
+        self.stats = (BaStats * max(K, 1))()
+        self.models = None
+        if any(pr.get("model") is not None for pr in problems):
+            self.models = (CameraModel * max(K, 1))()
+            for k, pr in enumerate(problems):
+                m = pr.get("model")
+                self.models[k] = m if m is not None else CameraModel.pinhole(*[float(v) for v in pr["intrinsics"]])
+        self.keep, self.outs = [], []
+        for k, pr in enumerate(problems):
+            poses = np.ascontiguousarray(pr["poses"], np.float64).reshape(-1, 7); fixed = np.ascontiguousarray(pr["fixed"], np.uint8)
+            kf_slots = np.ascontiguousarray(pr["kf_slots"], np.int32); mp_slots = np.ascontiguousarray(pr["mp_slots"], np.int32)
+            obs = np.ascontiguousarray(pr["obs"], BA_OBS_DTYPE)
+            assert len(kf_slots) == len(poses) == len(fixed)
+            P, L, E = len(poses), len(mp_slots), len(obs)
+            ref = None if pr.get("ref_edge") is None else np.ascontiguousarray(pr["ref_edge"], np.int32)
+            ow = None if pr.get("ow") is None else np.ascontiguousarray(pr["ow"], np.float32).reshape(-1, 3)
+            assert ref is None or len(ref) == L
+            assert ow is None or len(ow) == P
+            o = dict(poses=np.zeros((P, 7), np.float64), points=np.zeros((L, 3), np.float64), edge_chi2=np.zeros(E, np.float64),
+                     depth_positive=np.zeros(E, np.uint8), geometry=np.zeros((L, 8), np.float32), point_dirty=np.zeros(L, np.uint8),
+                     ow=np.zeros((P, 3), np.float32))
+            self.keep.append((poses, fixed, kf_slots, mp_slots, obs, ref, ow, pr.get("keyframe_store"), pr.get("map_store"))); self.outs.append(o)
+            w = self.wins[k]
+            w.n_poses, w.n_points, w.n_edges, w.iterations = P, L, E, int(pr["iterations"])
+            w.poses, w.fixed, w.kf_slot, w.mp_slot, w.obs = poses.ctypes.data, fixed.ctypes.data, kf_slots.ctypes.data, mp_slots.ctypes.data, obs.ctypes.data
+            w.keyframes = pr["keyframe_store"].h if pr.get("keyframe_store") is not None else None
+            w.points = pr["map_store"].h if pr.get("map_store") is not None else None
+            w.ref_edge = ref.ctypes.data if ref is not None else None
+            w.ow = ow.ctypes.data if ow is not None else None
+            intr = pr["intrinsics"] if pr.get("model") is None else list(pr["model"].p[:4])
+            w.cam = BaCamera(*[float(v) for v in intr], float(pr["huber_delta"]))
+            w.chi2_erase = float(pr.get("chi2_erase", 5.991))
+            w.poses_out, w.points_out, w.edge_chi2_out, w.depth_positive_out = (o["poses"].ctypes.data, o["points"].ctypes.data, o["edge_chi2"].ctypes.data,
+                                                                                o["depth_positive"].ctypes.data)
+            w.point_dirty_out = o["point_dirty"].ctypes.data
+            if pr.get("want_geometry", True):
+                w.geometry_out, w.ow_out = o["geometry"].ctypes.data, o["ow"].ctypes.data
+
+    results = BaWindowBatch.results
+
+
+class BaResident:
+    """dvm_ba_resident: LocalBundleAdjustment windows that read a KeyframeStore and a MapStore by slot and write their result back into the
+    MapStore on the device.  optimize() is ba_optimize_windows(fast=True) on what the slots hold (the same bits) plus, per window,
+    `geometry` [L, 8] (pos, normal, min_dist, max_dist of the clean, used points; zeros elsewhere), `point_dirty` [L] and `ow` [P, 3];
+    commit(k) queues the write of window k's geometry (-1: every window not yet committed) into the map store's records."""
+
+    def __init__(self, device=0):
+        self.L = lib()
+        self.h = C.c_void_p()
+        vp, i32 = C.c_void_p, C.c_int32
+        for name, args in (("create", [i32, vp]), ("optimize", [vp, vp, vp, i32, vp, vp]), ("commit", [vp, i32]), ("last_bytes", [vp, vp, vp])):
+            f = getattr(self.L, "dvm_ba_resident_" + name)
+            f.restype = i32; f.argtypes = args
+        self.L.dvm_ba_resident_destroy.restype = None; self.L.dvm_ba_resident_destroy.argtypes = [vp]
+        check(self.L.dvm_ba_resident_create(int(device), C.byref(self.h)))
+
+    def run(self, batch, stop_flag=None, collect=True):
+        """The bare library call on a BaResidentBatch."""
+        sf = _p(stop_flag) if stop_flag is not None else None
+        check(self.L.dvm_ba_resident_optimize(self.h, C.addressof(batch.wins), None if batch.models is None else C.addressof(batch.models), batch.K, sf,
+                                              C.addressof(batch.stats)))
+        return batch.results() if collect else None
+
+    def optimize(self, problems, stop_flag=None):
+        return self.run(BaResidentBatch(problems), stop_flag)
+
+    def commit(self, k=-1):
+        check(self.L.dvm_ba_resident_commit(self.h, int(k)))
+
+    def last_bytes(self):
+        """(host to device, device to host) of the last optimize."""
+        up, down = C.c_int64(0), C.c_int64(0)
+        check(self.L.dvm_ba_resident_last_bytes(self.h, C.byref(up), C.byref(down)))
+        return up.value, down.value
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L.dvm_ba_resident_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+
 TRACKED_POINT_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("depth", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
                                 ("in_view", "u1"), ("bad", "u1"), ("pad", "u1", (2,)), ("desc", "u1", (32,)), ("n_obs", "<i4")])
 

@@ -175,7 +175,10 @@ void ba_launch_pose_optimize_kb8(hipStream_t s, const double* pose_in, const dou
 // constructor does) or taking them as they are (the state a previous optimize() of the same graph left)
 int ba_windows_seq(int device, const dvm_ba_window* windows, int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats, bool normalize_input);
 // csrc/ba_window_cluster.hip: dvm_ba_optimize_windows_fast[_cam].  cluster > 0: that many workgroups per window, else chosen by
-// ba_cluster_size from the call's own grid; models NULL: pinhole windows, else the camera model of every window
-int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats, int cluster, const dvm_camera_model* models);
+// ba_cluster_size from the call's own grid; models NULL: pinhole windows, else the camera model of every window; res (ba_window_common.h):
+// the windows read resident stores (dvm_ba_resident_optimize)
+namespace dvm { struct ResidentCall; }
+int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats, int cluster, const dvm_camera_model* models,
+                       const dvm::ResidentCall* res = nullptr);
 // the largest of 8 / 4 / 2 / 1 workgroups per window for which `groups` windows' workgroups are resident at once; `forced` > 0 or DVM_BA_CLUSTER decide otherwise
 int ba_cluster_size(int device, int groups, int forced);

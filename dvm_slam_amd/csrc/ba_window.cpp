@@ -1,10 +1,12 @@
 // dvm_slam_amd/csrc/ba_window.cpp -- the C entry points of the window optimizers (dvm_ba_optimize_windows, dvm_ba_optimize_windows_fast[_cam],
-// dvm_ba_pool_*) and the host bookkeeping of a call that both launchers share (WinCall, ba_window_common.h).  The kernels and their
-// launchers: ba_window_seq.hip (g2o's summation order, the oracle's bits) and ba_window_cluster.hip (tree sums, G workgroups per window).
+// dvm_ba_pool_*, dvm_ba_resident_*) and the host bookkeeping of a call that both launchers share (WinCall, ba_window_common.h).  The kernels and their
+// launchers: ba_window_seq.hip (g2o's summation order, the oracle's bits) and ba_window_cluster.hip (tree sums, G workgroups per window);
+// ba_window_resident.hip: the gather and prepare kernels of the windows that read resident stores.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -12,8 +14,12 @@
 #include <vector>
 
 #include "ba_kernels.h"
+#include "ba_resident_lists.h"
 #include "ba_window_common.h"
+#include "chain.h"
 #include "group_commit.h"
+#include "keyframe_store.h"
+#include "map_store.h"
 
 using namespace dvm;
 
@@ -220,6 +226,188 @@ int dvm_ba_pool_optimize(dvm_ba_pool* pool, const dvm_ba_window* w, dvm_ba_stats
 int dvm_ba_pool_optimize_cam(dvm_ba_pool* pool, const dvm_ba_window* w, const dvm_camera_model* model, dvm_ba_stats* stats, int* batch_size) {
   if (!model || !dvm_cam::model_ok(model->model, model->p)) { set_error("dvm_ba_pool_optimize_cam: NULL model, unknown model or zero focal length"); return DVM_ERR_INVALID; }
   return ba_pool_optimize(pool, w, model, stats, batch_size);
+}
+
+// ---- dvm_ba_resident_*: LocalBundleAdjustment windows that read the keyframe store and the map store and commit to the map store on the
+// device (include/dvmslam_hip.h).  This file: the handle, every check -- all on the host, before anything is queued --, the commit's
+// bookkeeping.  The kernels: ba_window_resident.hip; the launcher: ba_windows_cluster with a ResidentCall; the scatter: map_store.cpp.
+struct dvm_ba_resident {
+  int device = 0;
+  uint8_t* d = nullptr; size_t dcap = 0;          // what the prepare kernels leave and a commit reads, all windows of the last optimize
+  struct Win { dvm_map_store* store; float* geom; uint8_t* state; int32_t* slot; float* ow; int32_t L; bool has_ref, committed; };
+  std::vector<Win> win;
+  bool valid = false;                             // the last optimize succeeded
+  std::vector<hipEvent_t> ev; int n_pending = 0;  // behind the queued commits' scatters: the next optimize's prepare kernels wait for them
+  int64_t h2d = 0, d2h = 0;
+  // per-call scratch, kept with the handle
+  std::vector<std::vector<ResidentKf>> kf;
+  std::vector<ResidentLists> lists;
+};
+
+int dvm_ba_resident_create(int device, dvm_ba_resident** out) {
+  if (!out) return DVM_ERR_INVALID;
+  *out = nullptr;
+  const int rc = need_device(device);
+  if (rc != DVM_OK) return rc;
+  dvm_ba_resident* h = new (std::nothrow) dvm_ba_resident();
+  if (!h) return DVM_ERR_INVALID;
+  h->device = device;
+  *out = h;
+  return DVM_OK;
+}
+void dvm_ba_resident_destroy(dvm_ba_resident* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  for (int i = 0; i < h->n_pending; i++) (void)hipEventSynchronize(h->ev[i]);     // a queued commit still reads h->d
+  for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
+  if (h->d) (void)hipFree(h->d);
+  delete h;
+}
+
+static int resident_refuse(int k, const std::string& what) {
+  set_error("dvm_ba_resident_optimize: window " + std::to_string(k) + ": " + what);
+  return DVM_ERR_INVALID;
+}
+
+int dvm_ba_resident_optimize(dvm_ba_resident* h, const dvm_ba_window_resident* windows, const dvm_camera_model* models, int K,
+                             const volatile uint8_t* stop_flag, dvm_ba_stats* stats) {
+  if (!h) return DVM_ERR_INVALID;
+  h->valid = false;
+  if (K < 0 || (K && !windows)) { set_error("dvm_ba_resident_optimize: NULL windows"); return DVM_ERR_INVALID; }
+  for (int k = 0; models && k < K; k++)
+    if (!dvm_cam::model_ok(models[k].model, models[k].p)) return resident_refuse(k, "unknown model or zero focal length");
+  // every check of every window, on the host, before the device is touched
+  if ((int)h->kf.size() < K) { h->kf.resize(K); h->lists.resize(K); }
+  std::vector<dvm_ba_window> win(K);
+  // (the windows are independent: checked by the pooled host threads that build their tables later -- 32 windows of 15 000 edges
+  //  checked one after the other cost more than a millisecond of a 5 ms call)
+  auto check = [&](int k) -> int {
+    const dvm_ba_window_resident& w = windows[k];
+    const int P = w.n_poses, L = w.n_points, E = w.n_edges;
+    if (P < 0 || L < 0 || E < 0 || w.iterations < 0) return resident_refuse(k, "a negative count");
+    if ((P && (!w.poses || !w.fixed || !w.keyframes || !w.kf_slot)) || (L && (!w.points || !w.mp_slot)) || (E && !w.obs)) return resident_refuse(k, "a NULL array");
+    if (P && kfs_device(w.keyframes) != h->device) return resident_refuse(k, "the keyframe store lies on another device");
+    if (L && store_device(w.points) != h->device) return resident_refuse(k, "the map store lies on another device");
+    std::vector<ResidentKf>& kf = h->kf[k];
+    kf.resize(P);
+    static thread_local std::vector<int32_t> n_kp, sorted;
+    n_kp.resize(P);
+    for (int p = 0; p < P; p++) {
+      KfSlotView v;
+      if (!kfs_slot_view(w.keyframes, w.kf_slot[p], &v)) return resident_refuse(k, "keyframe slot " + std::to_string(w.kf_slot[p]) + " lies outside the store, was never written or has been removed");
+      kf[p] = ResidentKf{v.kps, v.inv_sigma2, v.sf, v.n_levels, 0};
+      n_kp[p] = v.n;
+    }
+    if (resident_lists_build(w.obs, P, L, E, h->lists[k]) != 0) return resident_refuse(k, "edge index out of range");
+    for (int e = 0; e < E; e++)
+      if (w.obs[e].kp < 0 || w.obs[e].kp >= n_kp[w.obs[e].pose]) return resident_refuse(k, "edge " + std::to_string(e) + ": keypoint " + std::to_string(w.obs[e].kp) + " outside its keyframe's [0, n)");
+    if (L && !store_slots_ok(w.points, w.mp_slot, L)) return resident_refuse(k, "a map slot outside [0, capacity) or never written");
+    sorted.assign(w.mp_slot, w.mp_slot + L);
+    std::sort(sorted.begin(), sorted.end());
+    for (int l = 1; l < L; l++) if (sorted[l] == sorted[l - 1]) return resident_refuse(k, "map slot " + std::to_string(sorted[l]) + " named twice");
+    if (w.ref_edge) {
+      int at = 0;
+      const int bad = resident_ref_check(w.obs, L, E, h->lists[k], w.ref_edge, &at);
+      if (bad) return resident_refuse(k, "ref_edge of point " + std::to_string(at) + (bad == 1 ? " out of range" : bad == 2 ? " is not an edge of that point" : " is -1 on a point that has edges"));
+    }
+    dvm_ba_window& o = win[k];
+    std::memset(&o, 0, sizeof(o));
+    o.n_poses = P; o.n_points = L; o.n_edges = E; o.iterations = w.iterations;
+    o.poses = w.poses; o.fixed = w.fixed; o.cam = w.cam;
+    if (models && models[k].model == dvm_cam::kPinhole) { o.cam.fx = (double)models[k].p[0]; o.cam.fy = (double)models[k].p[1]; o.cam.cx = (double)models[k].p[2]; o.cam.cy = (double)models[k].p[3]; }
+    o.poses_out = w.poses_out; o.points_out = w.points_out; o.edge_chi2_out = w.edge_chi2_out; o.depth_positive_out = w.depth_positive_out;
+    return win_graph(o, true, nullptr, resident_obs(w));     // (the limit of 30 free cameras)
+  };
+  {
+    std::vector<int> rcs(K, DVM_OK);
+    std::vector<std::string> errs(K);
+    HostPool::get().run((size_t)K, 32, [&](size_t k) { if ((rcs[k] = check((int)k)) != DVM_OK) errs[k] = last_error_cstr(); });
+    for (int k = 0; k < K; k++) if (rcs[k] != DVM_OK) { set_error(errs[k]); return rcs[k]; }     // (the first refused window names itself)
+  }
+  std::vector<const dvm_keyframe_store*> kf_stores;
+  std::vector<const dvm_map_store*> map_stores;
+  for (int k = 0; k < K; k++) {
+    const dvm_ba_window_resident& w = windows[k];
+    if (w.n_poses && std::find(kf_stores.begin(), kf_stores.end(), w.keyframes) == kf_stores.end()) kf_stores.push_back(w.keyframes);
+    if (w.n_points && std::find(map_stores.begin(), map_stores.end(), w.points) == map_stores.end()) map_stores.push_back(w.points);
+  }
+  h->win.clear();
+  h->h2d = h->d2h = 0;
+  if (K == 0) { h->valid = true; return DVM_OK; }
+  { const int rc = hip_check(hipSetDevice(h->device), "hipSetDevice"); if (rc != DVM_OK) return rc; }
+  // the handle's block: per window geom [L][8], state [L], slot [L], ow [P][3]
+  Cursor<256> cur{nullptr};
+  for (int k = 0; k < K; k++) { cur.carve<float>(8 * (size_t)windows[k].n_points); cur.carve<uint8_t>((size_t)windows[k].n_points); cur.carve<int32_t>((size_t)windows[k].n_points); cur.carve<float>(3 * (size_t)windows[k].n_poses); }
+  if (cur.used() > h->dcap) {
+    for (int i = 0; i < h->n_pending; i++) DVM_HIP(hipEventSynchronize(h->ev[i]));     // a queued commit still reads the old block
+    h->n_pending = 0;
+    if (h->d) (void)hipFree(h->d);
+    h->d = nullptr; h->dcap = 0;
+    const size_t cap = std::max<size_t>(cur.used() * 2, (size_t)1 << 16);
+    { const int rc = hip_check(hipMalloc(reinterpret_cast<void**>(&h->d), cap), "hipMalloc(prepared windows)"); if (rc != DVM_OK) { h->d = nullptr; return rc; } }
+    h->dcap = cap;
+  }
+  std::vector<WinResident> src(K);
+  std::vector<dvm_ba_resident::Win> prepared(K);
+  cur = Cursor<256>{h->d};
+  for (int k = 0; k < K; k++) {
+    const dvm_ba_window_resident& w = windows[k];
+    WinResident& r = src[k];
+    r.w = &w; r.kf = h->kf[k].data(); r.records = w.n_points ? reinterpret_cast<const dvm_local_point*>(store_records(w.points)) : nullptr;
+    r.pe_start = h->lists[k].pe_start.data(); r.pe_edges = h->lists[k].pe_edges.data();
+    r.geom = cur.carve<float>(8 * (size_t)w.n_points); r.state = cur.carve<uint8_t>((size_t)w.n_points);
+    r.slot = cur.carve<int32_t>((size_t)w.n_points); r.ow = cur.carve<float>(3 * (size_t)w.n_poses);
+    prepared[k] = dvm_ba_resident::Win{w.points, r.geom, r.state, r.slot, r.ow, w.n_points, w.ref_edge != nullptr, false};
+  }
+  ResidentCall call;
+  call.win = src.data();
+  call.kf_stores = kf_stores.data(); call.n_kf_stores = (int)kf_stores.size();
+  call.map_stores = map_stores.data(); call.n_map_stores = (int)map_stores.size();
+  call.wait_ev = h->ev.data(); call.n_wait = h->n_pending;
+  call.h2d = &h->h2d; call.d2h = &h->d2h;
+  const int rc = ba_windows_cluster(h->device, win.data(), K, stop_flag, stats, 0, models, &call);
+  if (rc != DVM_OK) return rc;
+  h->n_pending = 0;                    // (the call's stream waited for them, and the call for its stream)
+  h->win.swap(prepared);
+  h->valid = true;
+  return DVM_OK;
+}
+
+int dvm_ba_resident_commit(dvm_ba_resident* h, int k) {
+  if (!h) return DVM_ERR_INVALID;
+  if (!h->valid) { set_error("dvm_ba_resident_commit: no optimize has run on the handle, or the last one failed"); return DVM_ERR_STATE; }
+  const int K = (int)h->win.size();
+  if (k < -1 || k >= K) { set_error("dvm_ba_resident_commit: window " + std::to_string(k) + " outside the last optimize's [0, " + std::to_string(K) + ")"); return DVM_ERR_INVALID; }
+  if (k >= 0 && h->win[k].committed) { set_error("dvm_ba_resident_commit: window " + std::to_string(k) + " has been committed"); return DVM_ERR_STATE; }
+  if (k >= 0 && !h->win[k].has_ref) { set_error("dvm_ba_resident_commit: window " + std::to_string(k) + " was given no ref_edge"); return DVM_ERR_STATE; }
+  std::vector<int> todo;
+  for (int i = (k < 0 ? 0 : k); i < (k < 0 ? K : k + 1); i++)
+    if (!h->win[i].committed && h->win[i].has_ref) todo.push_back(i);
+  std::vector<dvm_map_store*> stores;
+  for (int i : todo) if (h->win[i].L > 0 && std::find(stores.begin(), stores.end(), h->win[i].store) == stores.end()) stores.push_back(h->win[i].store);
+  { const int rc = hip_check(hipSetDevice(h->device), "hipSetDevice"); if (rc != DVM_OK) return rc; }
+  while (h->ev.size() < (size_t)h->n_pending + stores.size()) {
+    hipEvent_t e = nullptr;
+    DVM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    h->ev.push_back(e);
+  }
+  for (dvm_map_store* st : stores) {                // one scatter per distinct store
+    std::vector<StoreCommitRange> ranges;
+    for (int i : todo) if (h->win[i].store == st && h->win[i].L > 0) ranges.push_back(StoreCommitRange{h->win[i].geom, h->win[i].state, h->win[i].slot, h->win[i].L, 0});
+    const int rc = store_commit_geometry(st, ranges.data(), (int)ranges.size(), h->ev[h->n_pending]);
+    if (rc != DVM_OK) { h->valid = false; return rc; }
+    h->n_pending++;
+    for (int i : todo) if (h->win[i].store == st) h->win[i].committed = true;
+  }
+  for (int i : todo) h->win[i].committed = true;   // (windows without points)
+  return DVM_OK;
+}
+
+int dvm_ba_resident_last_bytes(const dvm_ba_resident* h, int64_t* host_to_device, int64_t* device_to_host) {
+  if (!h) return DVM_ERR_INVALID;
+  if (host_to_device) *host_to_device = h->h2d;
+  if (device_to_host) *device_to_host = h->d2h;
+  return DVM_OK;
 }
 
 }  // extern "C"

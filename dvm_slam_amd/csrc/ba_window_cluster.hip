@@ -848,7 +848,11 @@ int ba_cluster_size(int device, int groups, int forced) {
 // instantiation of k_ba_window_cluster, one after the other on the calling thread's staging stream, G chosen per launch from its own window
 // count: a homogeneous call is one launch, a mixed one two.  A window's result depends neither on its batch nor on G, hence not on the other
 // model types of the call either.
-int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats, int cluster, const dvm_camera_model* models) {
+// res (dvm_ba_resident_optimize): the windows' edges and points are not the caller's arrays (edges and points of `windows` are NULL) but
+// lie in resident stores -- a gather kernel in front of the solver fills e_obs / e_info / pts, the prepare kernels run behind it
+// (ba_window_resident.hip); tables, views and launch are the same.
+int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats, int cluster, const dvm_camera_model* models,
+                       const ResidentCall* res) {
   if (K < 0 || (K && !windows)) { set_error("dvm_ba_optimize_windows: null windows"); return DVM_ERR_INVALID; }
   if (K == 0) return DVM_OK;
   int n_kb8 = 0;
@@ -856,14 +860,17 @@ int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const vo
   const bool kb8 = n_kb8 == K;
   int rc = DVM_OK;
   if (n_kb8 > 0 && n_kb8 < K) {
-    for (int k = 0; k < K; k++) if ((rc = win_graph(windows[k], true, nullptr)) != DVM_OK) return rc;     // ALL windows are checked before the first launch
+    for (int k = 0; k < K; k++) if ((rc = win_graph(windows[k], true, nullptr, res ? resident_obs(*res->win[k].w) : nullptr)) != DVM_OK) return rc;     // ALL windows are checked before the first launch
     for (int type = 0; type < 2; type++) {
       std::vector<int> idx;
       std::vector<dvm_ba_window> gw;
       std::vector<dvm_camera_model> gm;
-      for (int k = 0; k < K; k++) if ((models[k].model == dvm_cam::kKannalaBrandt8 ? 1 : 0) == type) { idx.push_back(k); gw.push_back(windows[k]); gm.push_back(models[k]); }
+      std::vector<WinResident> gr;
+      for (int k = 0; k < K; k++) if ((models[k].model == dvm_cam::kKannalaBrandt8 ? 1 : 0) == type) { idx.push_back(k); gw.push_back(windows[k]); gm.push_back(models[k]); if (res) gr.push_back(res->win[k]); }
       std::vector<dvm_ba_stats> gs(idx.size());
-      if ((rc = ba_windows_cluster(device, gw.data(), (int)idx.size(), stop_flag, stats ? gs.data() : nullptr, cluster, gm.data())) != DVM_OK) return rc;
+      ResidentCall gres;
+      if (res) { gres = *res; gres.win = gr.data(); }
+      if ((rc = ba_windows_cluster(device, gw.data(), (int)idx.size(), stop_flag, stats ? gs.data() : nullptr, cluster, gm.data(), res ? &gres : nullptr)) != DVM_OK) return rc;
       for (size_t j = 0; stats && j < idx.size(); j++) stats[idx[j]] = gs[j];
     }
     return DVM_OK;
@@ -903,14 +910,14 @@ int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const vo
     std::vector<std::string> errs(K);
     static const int bt = std::getenv("DVM_BA_BUILD_THREADS") ? std::max(1, atoi(std::getenv("DVM_BA_BUILD_THREADS"))) : 32;
     HostPool::get().run((size_t)K, bt, [&](size_t k) {
-      rcs[k] = build_window_fast(windows[k], B[k]);
+      rcs[k] = build_window_fast(windows[k], B[k], res ? resident_obs(*res->win[k].w) : nullptr);
       if (rcs[k] == DVM_OK) { hipSetDevice(device); rcs[k] = B[k].pack_fast((private_tables && (k & 1)) ? nullptr : &shared_tables); }
       if (rcs[k] == DVM_OK) rcs[k] = send_tables((int)k);     // (a pooled thread: the device of the call, for the arena's first allocation)
       if (rcs[k] != DVM_OK) errs[k] = last_error_cstr();
     });
     for (int k = 0; k < K; k++) if (rcs[k] != DVM_OK) { set_error(errs[k]); return rcs[k]; }
   } else {
-    if ((rc = build_window_fast(windows[0], B[0])) != DVM_OK || (rc = B[0].pack_fast(&shared_tables)) != DVM_OK || (rc = send_tables(0)) != DVM_OK) return rc;
+    if ((rc = build_window_fast(windows[0], B[0], res ? resident_obs(*res->win[0].w) : nullptr)) != DVM_OK || (rc = B[0].pack_fast(&shared_tables)) != DVM_OK || (rc = send_tables(0)) != DVM_OK) return rc;
   }
   call.mark(1);
   if (std::getenv("DVM_BA_WINDOW_TIMING")) {     // (measurement only: how long the tables' copies run on behind the builds)
@@ -927,14 +934,17 @@ int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const vo
   for (int k = 0; k < K; k++) {     // inputs: the window's tables are already page-locked (pack_fast); the landmarks from the caller's array
     const ClusterBuild& b = B[k]; Slots& s = sl[k];
     s.arena = b.shared_off < 0 ? st.in_pinned(b.arena.used ? b.arena.base : nullptr, b.arena.used) : -1;
-    s.pts = st.in(b.g.L ? windows[k].points : nullptr, 24 * (size_t)b.g.L);
+    s.pts = res ? -1 : st.in(b.g.L ? windows[k].points : nullptr, 24 * (size_t)b.g.L);
   }
+  ResidentStage rstage(res ? *res : ResidentCall{}, res ? K : 0);     // (without res: nothing added, nothing launched)
+  if (res) rstage.add_inputs(st);
   std::vector<uint32_t> sync_zero(16, 0u);        // a window's arrival counter [0] and time-out word [8], zero at every launch
   std::vector<std::vector<uint32_t>> sync_back(K, std::vector<uint32_t>(16, 0u));
   for (int k = 0; k < K; k++) sl[k].cl_sync = st.add(sync_zero.data(), sync_back[k].data(), 64);
   std::vector<ClusterWin> views(K);
   const int views_slot = st.in(views.data(), sizeof(ClusterWin) * (size_t)K);   // filled in below, once layout() has placed everything
   call.add_outputs(st);
+  if (res) { rstage.add_outputs(st); rstage.add_scratch(st); }
   for (int k = 0; k < K; k++) {                     // working memory
     const ClusterBuild& b = B[k]; Slots& s = sl[k];
     const size_t E = b.g.E, Fp = (size_t)b.Fp, n = 6 * (size_t)b.g.nfree, nl = 3 * (size_t)b.g.nact;
@@ -965,7 +975,8 @@ int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const vo
     v.e_orig = A4(b.ao.e_orig); v.e_lm = A4(b.ao.e_lm); v.cam_start = A4(b.ao.cam_start); v.pt_edges = A4(b.ao.pt_edges);
     v.bp_start = A4(b.ao.bp_start); v.bp_pairs = reinterpret_cast<const int2*>(A4(b.ao.bp_pairs));
     v.sched_start = A4(b.ao.sched_start); v.sched_task = A4(b.ao.sched_task);
-    v.pts = st.ptr<double>(s.pts); v.poses_t = st.ptr<double>(s.poses_t); v.pts_t = st.ptr<double>(s.pts_t);
+    if (res) { v.e_obs = rstage.e_obs(st, k); v.e_info = rstage.e_info(st, k); }
+    v.pts = res ? rstage.pts(st, k) : st.ptr<double>(s.pts); v.poses_t = st.ptr<double>(s.poses_t); v.pts_t = st.ptr<double>(s.pts_t);
     v.rowA = st.ptr<double>(s.rowA); v.e_rho = st.ptr<double>(s.erho);
     v.Bs = st.ptr<double>(s.Bs); v.Ws = st.ptr<double>(s.Ws); v.Ts = st.ptr<double>(s.Ts); v.Cs = st.ptr<double>(s.Cs); v.chi_s = st.ptr<double>(s.chi_s);
     v.cl_ctr = st.ptr<unsigned int>(s.cl_sync); v.cl_tmo = v.cl_ctr + 8;
@@ -973,12 +984,19 @@ int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const vo
     v.Hpp = st.ptr<double>(s.Hpp); v.bp = st.ptr<double>(s.bp); v.HB = st.ptr<double>(s.HB);
     v.x = st.ptr<double>(s.x); v.terms = st.ptr<double>(s.terms);
     call.fill(st, k, v);
+    if (res) rstage.fill(st, k, v.e_orig, v.out_poses, v.out_pts, v.e_chi2, v.e_depth);
     const size_t n = 6 * (size_t)g.nfree;
     lds_doubles = std::max(lds_doubles, n * (n + 1) / 2 + 2 * n + 64 + 256 + (size_t)b.stage_doubles);
   }
   call.mark(4);
   if ((rc = st.upload()) != DVM_OK) return rc;
   for (int i = 0; i < 4; i++) DVM_HIP(hipStreamWaitEvent(st.stream(), tup.e[i], 0));     // the tables have arrived before the launch starts
+  if (res) {
+    if ((rc = rstage.gather(st)) != DVM_OK) return rc;
+    int64_t up = (int64_t)st.in_bytes;
+    for (int k = 0; k < K; k++) up += (int64_t)(B[k].shared_off >= 0 ? B[k].packed_bytes : B[k].arena.used);
+    *res->h2d += up;
+  }
   call.mark(5);
   // dynamic LDS: the packed reduced system of the largest window, rhs / diagonal, control words and the reduction buffers
   const size_t lds_bytes = sizeof(double) * lds_doubles;
@@ -995,12 +1013,18 @@ int ba_windows_cluster(int device, const dvm_ba_window* windows, int K, const vo
   hipLaunchKernelGGL(kernel, dim3(groups * G), dim3(kWinThreads), lds_bytes, st.stream(), st.ptr<ClusterWin>(views_slot), stop_dev, scatter ? -K : K, G);
   hipEventRecord(kev.b, st.stream());
   DVM_HIP(hipGetLastError());
+  if (res) {
+    if ((rc = rstage.prepare(st)) != DVM_OK) return rc;
+    size_t lo = st.total, hi = 0;      // the span Stage::download fetches
+    for (const Stage::Item& it : st.items) if (it.dst && it.bytes && !it.mapped) { lo = std::min(lo, it.off); hi = std::max(hi, it.off + it.bytes); }
+    if (hi > lo) *res->d2h += (int64_t)(hi - lo);
+  }
   if ((rc = call.wait(st, G)) != DVM_OK) return rc;
   if (G > 1) {
     bool timed_out = std::getenv("DVM_BA_TEST_TIMEOUT") != nullptr;      // (test hook: take the repeat path without a real time-out)
     for (int k = 0; k < K; k++) timed_out = timed_out || sync_back[k][8] != 0u;
     if (timed_out)     // a cluster's workgroups were not all resident (other work held compute units): solve the batch again, one workgroup per window
-      return ba_windows_cluster(device, windows, K, stop_flag, stats, 1, models);
+      return ba_windows_cluster(device, windows, K, stop_flag, stats, 1, models, res);
   }
   static const char* names[16] = {"edge pass + Jacobians", "Hll / bl, Hpp / bp", "W Dinv rows", "Schur blocks + rhs", "assemble S in LDS", "Cholesky", "substitution + x", "W^T x rows",
                                   "landmarks + oplus", "edge pass chi2 + sums", "IN BARRIERS (workgroup 0)", "decision + rest", "  chol: diagonal block", "  chol: panel", "  chol: barriers", "  chol: trailing update"};

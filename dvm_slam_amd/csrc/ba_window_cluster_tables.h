@@ -27,9 +27,10 @@ struct ClusterTables {
 // The cluster form's structure: edges sorted camera-major (free cameras in free-index order, a camera's edges by landmark, then the fixed
 // cameras' edges), per landmark its edges in that order, per block of the reduced system its (row, row) pairs in landmark order
 // (block_solver.hpp:381-439: edge k1 (outer) x edge k2 (inner), lower blocks; (k1, k1) on the diagonal).  b may have been used before.
-inline int build_window_fast(const dvm_ba_window& w, ClusterTables& b) {
+// obs: see win_graph -- the per-edge measurements are then not the host's: e_obs / e_info stay empty, the gather kernel goes through e_orig.
+inline int build_window_fast(const dvm_ba_window& w, ClusterTables& b, const dvm_ba_obs* obs = nullptr) {
   WinGraph& g = b.g;
-  const int rc = win_graph(w, /*normalize=*/true, &g);
+  const int rc = win_graph(w, /*normalize=*/true, &g, obs);
   if (rc != DVM_OK) return rc;
   b.blk_ij.clear();
   const int E = g.E, nf = g.nfree, P = g.P;
@@ -54,11 +55,12 @@ inline int build_window_fast(const dvm_ba_window& w, ClusterTables& b) {
   b.Fp = (b.F + 63) & ~63;
   std::vector<int32_t>& ep = b.t_ep; std::vector<int32_t>& ept = b.t_ept;
   std::vector<double>& eo = b.t_eo; std::vector<double>& ei = b.t_ei;
-  ep.resize(E); ept.resize(E); eo.resize(2 * (size_t)E); ei.resize(E);
+  ep.resize(E); ept.resize(E); eo.resize(obs ? 0 : 2 * (size_t)E); ei.resize(obs ? 0 : E);
   b.e_lm.resize(E);
   for (int j = 0; j < E; j++) {
     const int k = order[j];
-    ep[j] = g.e_pose[k]; ept[j] = g.e_point[k]; eo[2 * (size_t)j] = g.e_obs[2 * (size_t)k]; eo[2 * (size_t)j + 1] = g.e_obs[2 * (size_t)k + 1]; ei[j] = g.e_info[k];
+    ep[j] = g.e_pose[k]; ept[j] = g.e_point[k];
+    if (!obs) { eo[2 * (size_t)j] = g.e_obs[2 * (size_t)k]; eo[2 * (size_t)j + 1] = g.e_obs[2 * (size_t)k + 1]; ei[j] = g.e_info[k]; }
     b.e_lm[j] = g.lidx[ept[j]];
   }
   g.e_pose.swap(ep); g.e_point.swap(ept); g.e_obs.swap(eo); g.e_info.swap(ei);

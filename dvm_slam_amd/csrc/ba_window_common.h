@@ -2,6 +2,7 @@
 //   ba_window_seq.hip      k_ba_window: g2o's summation order, the oracle's bits, pinhole (dvm_ba_optimize_windows)
 //   ba_window_cluster.hip  k_ba_window_cluster<CAM>: tree sums, G workgroups per window (dvm_ba_optimize_windows_fast[_cam], dvm_ba_pool_*)
 //   ba_window.cpp          the C entry points, the pool, and the host bookkeeping of a call that both launchers use (WinCall)
+//   ba_window_resident.hip the gather / prepare kernels dvm_ba_resident_optimize puts around the cluster form (WinResident, ResidentStage)
 // Host part first (no HIP: tools/check_ba_window_tables.cpp compiles it with g++): the graph front end of a window.  Device part below.
 #pragma once
 #include <cmath>
@@ -31,12 +32,22 @@ struct WinGraph {
 };
 // validates the window's arrays, range-checks the edges, marks the used vertices, numbers them, applies the limit of 30 free cameras.
 // g == nullptr: the checks alone, nothing built (a call of two launches checks ALL its windows before the first launch).
-inline int win_graph(const dvm_ba_window& w, bool normalize, WinGraph* g) {
+// obs != nullptr: a window of dvm_ba_resident_optimize -- the edges' indices come from obs, w.edges and w.points are not read and
+// e_obs / e_info stay empty (a gather kernel fills them on the device from the resident stores).
+// the obs argument of win_graph for a resident window (never NULL: a window without edges has no array to give)
+inline const dvm_ba_obs* resident_obs(const dvm_ba_window_resident& w) { static const dvm_ba_obs none{0, 0, 0}; return w.obs ? w.obs : &none; }
+inline int win_graph(const dvm_ba_window& w, bool normalize, WinGraph* g, const dvm_ba_obs* obs = nullptr) {
   const int P = w.n_poses, L = w.n_points, E = w.n_edges;
-  if (P < 0 || L < 0 || E < 0 || (P && (!w.poses || !w.fixed)) || (L && !w.points) || (E && !w.edges)) { set_error("dvm_ba_optimize_windows: null array"); return DVM_ERR_INVALID; }
+  if (P < 0 || L < 0 || E < 0 || (P && (!w.poses || !w.fixed)) || (!obs && ((L && !w.points) || (E && !w.edges)))) { set_error("dvm_ba_optimize_windows: null array"); return DVM_ERR_INVALID; }
   std::vector<uint8_t> pose_used(P, 0), pt_used(L, 0);
-  if (g) { g->e_pose.resize(E); g->e_point.resize(E); g->e_obs.resize(2 * (size_t)E); g->e_info.resize(E); }
-  for (int k = 0; k < E; k++) {
+  if (g) { g->e_pose.resize(E); g->e_point.resize(E); g->e_obs.resize(obs ? 0 : 2 * (size_t)E); g->e_info.resize(obs ? 0 : E); }
+  for (int k = 0; obs && k < E; k++) {
+    const dvm_ba_obs& e = obs[k];
+    if (e.pose < 0 || e.pose >= P || e.point < 0 || e.point >= L) { set_error("dvm_ba_optimize_windows: edge index out of range"); return DVM_ERR_INVALID; }
+    pose_used[e.pose] = 1; pt_used[e.point] = 1;
+    if (g) { g->e_pose[k] = e.pose; g->e_point[k] = e.point; }
+  }
+  for (int k = 0; !obs && k < E; k++) {
     const dvm_ba_edge& e = w.edges[k];
     if (e.pose < 0 || e.pose >= P || e.point < 0 || e.point >= L) { set_error("dvm_ba_optimize_windows: edge index out of range"); return DVM_ERR_INVALID; }
     pose_used[e.pose] = 1; pt_used[e.point] = 1;
@@ -126,6 +137,57 @@ struct WinCall {
   int wait(Stage& st, int G);           // behind the launch: forwards the caller's stop flag until the stream is through, then downloads
   // hands out the stats (and window 0's phase clocks, if asked for); kernel_us < 0: as the kernel left it (0)
   void finish(dvm_ba_stats* stats, const char* const* phase_names, int kernel_us);
+};
+
+// ---- dvm_ba_resident_optimize (ba_window.cpp: the entry and its checks; ba_window_resident.hip: the kernels): a window whose measurements
+// and points lie in a keyframe store and a map store.  ba_windows_cluster takes one WinResident per window as the SOURCE of the solver
+// view's e_obs / e_info / pts -- filled by a gather kernel in front of the solver instead of from the caller's arrays -- and runs the
+// prepare kernels behind it; the launcher, its tables and the solver are the same.
+struct dvm_keypoint_pod;
+struct ResidentKf { const dvm_keypoint_pod* kps; const float *inv_sigma2, *sf; int32_t n_levels, pad; };   // a camera's slot (device addresses)
+struct WinResident {
+  const dvm_ba_window_resident* w;       // checked by the entry: every index the kernels form lies inside its array
+  const ResidentKf* kf;                  // [n_poses], host
+  const dvm_local_point* records;        // the window's map store (device)
+  const int32_t *pe_start, *pe_edges;    // a point's edges in the caller's order (ba_resident_lists.h), host
+  float* geom; uint8_t* state; int32_t* slot; float* ow;   // memory of the handle (device): what a commit reads
+};
+struct ResidentCall {
+  const WinResident* win;                // [K]
+  const dvm_keyframe_store* const* kf_stores; int n_kf_stores;   // the distinct stores of the call: the brackets around the reading kernels
+  const dvm_map_store* const* map_stores; int n_map_stores;
+  const hipEvent_t* wait_ev; int n_wait; // queued commits that still read the handle's memory: the prepare kernels wait for them
+  int64_t *h2d, *d2h;                    // bytes sent up / fetched, accumulated over the call's launches
+};
+// the device view of a window for the three kernels; state: 0 clean and used, 1 dirty, 2 unused
+struct ResidentWinDev {
+  int32_t P, L, E, pad;
+  const dvm_ba_obs* obs; const ResidentKf* kf; const int32_t* mp_slot; const dvm_local_point* records; const int32_t* e_orig;
+  double *e_obs, *e_info, *pts;
+  const double *in_poses, *out_poses, *out_pts, *e_chi2; const uint8_t *fixed, *e_depth; const float* ow_in;
+  const int32_t *pe_start, *pe_edges, *ref_edge; double chi2_erase;
+  float *geom, *ow, *geom_out, *ow_out; uint8_t *state, *dirty_out; int32_t* slot;
+};
+// the Stage items, views and launches a ResidentCall adds to ba_windows_cluster
+struct ResidentStage {
+  const ResidentCall rc; const int K;
+  struct Slots { int obs, kf, mp_slot, pe_start, pe_edges, ref_edge, in_poses, fixed, ow_in, e_obs, e_info, pts, geom_out, dirty_out, ow_out; };
+  std::vector<Slots> sl;
+  std::vector<ResidentWinDev> views;
+  int views_slot = -1, max_el = 0, max_p = 0, max_l = 0;
+  ResidentStage(const ResidentCall& c, int k) : rc(c), K(k), sl(k), views(k) {}
+  // before layout().  Inputs first; the host outputs right behind WinCall's (Stage::download fetches ONE span from the first output to
+  // the last: working memory between two outputs would travel down with them); then the solver's three arrays as scratch
+  void add_inputs(Stage& st);
+  void add_outputs(Stage& st);
+  void add_scratch(Stage& st);
+  double* e_obs(const Stage& st, int k) const { return st.ptr<double>(sl[k].e_obs); }
+  double* e_info(const Stage& st, int k) const { return st.ptr<double>(sl[k].e_info); }
+  double* pts(const Stage& st, int k) const { return st.ptr<double>(sl[k].pts); }
+  // behind layout(): window k's view from the solver view's pointers
+  void fill(const Stage& st, int k, const int32_t* e_orig, const double* out_poses, const double* out_pts, const double* e_chi2, const uint8_t* e_depth);
+  int gather(const Stage& st);           // read brackets of the stores open, the gather kernel, the map stores' brackets closed
+  int prepare(const Stage& st);          // the waits for queued commits, centres and points, the keyframe stores' brackets closed
 };
 
 }  // namespace dvm

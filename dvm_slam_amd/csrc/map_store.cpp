@@ -83,6 +83,26 @@ int store_read_end(const dvm_map_store* cst, hipStream_t s) {
   st->read_pending = true;
   return DVM_OK;
 }
+int store_commit_geometry(dvm_map_store* st, const StoreCommitRange* ranges, int n, hipEvent_t done) {
+  DVM_HIP(hipSetDevice(st->device));
+  if (st->read_pending) {                                        // behind the chain kernels that read the records, as an update
+    DVM_HIP(hipStreamWaitEvent(st->s, st->read_ev, 0));
+    st->read_pending = false;
+  }
+  for (int first = 0; first < n; first += kStoreCommitRanges) {
+    const int m = std::min(kStoreCommitRanges, n - first);
+    StoreCommit C;
+    std::memset(&C, 0, sizeof(C));
+    int span = 0;
+    for (int i = 0; i < m; i++) { C.r[i] = ranges[first + i]; span = std::max(span, (int)ranges[first + i].n); }
+    launch_store_commit(st->s, st->d, C, m, span);
+    { const int rc = hip_check(hipGetLastError(), "k_store_commit"); if (rc != DVM_OK) return rc; }
+  }
+  DVM_HIP(hipEventRecord(st->write_ev, st->s));
+  st->write_pending = true;
+  DVM_HIP(hipEventRecord(done, st->s));
+  return DVM_OK;
+}
 }  // namespace dvm
 
 extern "C" {

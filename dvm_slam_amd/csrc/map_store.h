@@ -30,4 +30,15 @@ void launch_store_read(hipStream_t s, const LocalPointPod* src, const int32_t* s
 // span_max: the largest table, rounded up to 64
 struct StoreGather { const LocalPointPod* const* stores; const LocalFrameArgs* per_frame; const int32_t* qoff; const int32_t* slots; };
 void launch_store_gather(hipStream_t s, const StoreGather& G, LocalPointPod* dst, int count, int span_max);
+
+// dvm_ba_resident_commit: the geometry a local BA prepared in device memory (ba_window_resident.hip) into the records.  A range is one
+// window's points: geom [n][8] = pos, normal, min_dist, max_dist -- the first eight words of a record --, state [n] (0: write it; anything
+// else: the record is not touched), slot [n] (checked by the optimize that prepared them: in range, written, each once per window).
+struct StoreCommitRange { const float* geom; const uint8_t* state; const int32_t* slot; int32_t n, pad; };
+constexpr int kStoreCommitRanges = 16;
+struct StoreCommit { StoreCommitRange r[kStoreCommitRanges]; };
+void launch_store_commit(hipStream_t s, LocalPointPod* dst, const StoreCommit& C, int n_ranges, int span_max);
+// queues the ranges as dvm_map_store_update queues its scatter: on the store's stream behind read_ev, write_ev recorded, no wait; `done`
+// (the caller's) is recorded behind the last launch: the ranges' memory may be overwritten once it has passed
+int store_commit_geometry(dvm_map_store* st, const StoreCommitRange* ranges, int n, hipEvent_t done);
 }  // namespace dvm

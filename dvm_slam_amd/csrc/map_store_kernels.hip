@@ -42,6 +42,21 @@ __global__ void __launch_bounds__(256) k_store_gather(StoreGather G, uint32_t* _
   dst[(o + k) * kRecWords + w] = src[(size_t)G.slots[o + k] * kRecWords + w];
 }
 
+// dvm_ba_resident_commit: blockIdx.y = range, a lane per word of the eight geometry words; the other ten words of a record (desc, n_obs,
+// bad) and the records of points whose state is not 0 are never written
+__global__ void __launch_bounds__(256) k_store_commit(uint32_t* __restrict__ dst, StoreCommit C) {
+  const StoreCommitRange& R = C.r[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= R.n * 8) return;
+  const int k = i >> 3, w = i & 7;
+  if (R.state[k] != 0) return;
+  dst[(size_t)R.slot[k] * kRecWords + w] = reinterpret_cast<const uint32_t*>(R.geom)[i];
+}
+
+void launch_store_commit(hipStream_t s, LocalPointPod* dst, const StoreCommit& C, int n_ranges, int span_max) {
+  if (n_ranges < 1 || span_max < 1) return;
+  hipLaunchKernelGGL(k_store_commit, dim3((unsigned)(((int64_t)span_max * 8 + 255) / 256), (unsigned)n_ranges), dim3(256), 0, s, reinterpret_cast<uint32_t*>(dst), C);
+}
 void launch_store_scatter(hipStream_t s, LocalPointPod* dst, const int32_t* slots, const LocalPointPod* src, int n) {
   if (n < 1) return;
   const unsigned blocks = (unsigned)(((int64_t)n * kRecWords + 255) / 256);

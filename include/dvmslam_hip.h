@@ -1520,6 +1520,70 @@ int dvm_sim3_hypotheses_cam(int device, const float* P1c, const float* P2c, cons
                             const dvm_camera_model* model1, const dvm_camera_model* model2, const int32_t* triples, int H,
                             int fix_scale, float* T12, int32_t* n_inliers, uint8_t* inlier_mask);
 
+/* ---- LocalBundleAdjustment on the resident stores: dvm_ba_optimize_windows_fast[_cam] whose observations and points are READ from the
+ * keyframe slots and the map slots they have been lying in since ComputeBoW, and whose result goes BACK into the map slots on the device.
+ *   optimize  the cluster form (k_ba_window_cluster<CAM>, unchanged) on K windows.  Per observation only the 12-byte dvm_ba_obs goes up,
+ *             per point its slot (and ref_edge): a gather kernel in front of the solver fills, in the tables' sorted edge order,
+ *             e_obs = (double)mvKeysUn[kp].pt, e_info = (double)mvInvLevelSigma2[octave] from the slot of the edge's camera and
+ *             pts = (double)record[mp_slot].pos (the casts of Optimizer.cc:1188, 1207-1217).  poses, points, edge_chi2, depth_positive
+ *             and the statistics are those of dvm_ba_optimize_windows_fast (models NULL) / _fast_cam on the host-gathered window, bit
+ *             for bit.  The windows of one call may name different keyframe stores and different map stores (K agents).  Behind the
+ *             solver a prepare step leaves in memory of the handle, per window: the cameras' centres as float -- a free camera's from
+ *             its optimised pose as SE3f(Quaternionf, Vector3f).inverse().translation() (Optimizer.cc:1374, SetPose's mOw), a fixed
+ *             camera's the caller's ow row or, without one, the same of its input pose without the constructor's normalisation --; per
+ *             point whether it is DIRTY (one of its edges has chi2 > chi2_erase or no positive depth, Optimizer.cc:1324) or UNUSED (no
+ *             edge); and for every clean, used point SetWorldPos + MapPoint::UpdateNormalAndDepth (MapPoint.cc:473-540) in float32:
+ *             pos = (float)points_out, normal = mean over the point's edges IN THE CALLER'S ORDER of (pos - ow) / |pos - ow|,
+ *             max_dist = |pos - ow[ref]| * scale_factors[octave of the ref keypoint], min_dist = max_dist / scale_factors[n_levels - 1]
+ *             (tables of the ref keyframe's slot).  geometry_out rows of dirty and unused points are zeros; without ref_edge
+ *             min_dist = max_dist = 0.  Runs outside the map mutex, as Optimizer.cc:1311 does; synchronous.  DVM_BA_SPLIT is not honoured.
+ *   commit    window k of the last optimize (-1: every window not yet committed): ONE scatter per distinct map store, queued as
+ *             dvm_map_store_update queues its own -- on the store's stream, behind the last kernel queued to read the store, followed by
+ *             the store's write event; it does not wait.  It writes pos, normal, min_dist, max_dist of every clean, used point into
+ *             record[mp_slot] and nothing else: desc, n_obs and bad keep their bits, and a dirty or unused point's record is not touched
+ *             (the host sends those after its EraseObservation logic with dvm_map_store_update, as before).  The caller issues it under
+ *             Map::mMutexMapUpdate, where Optimizer.cc:1357-1384 writes back.  The next optimize on the handle waits (on its stream) for
+ *             a queued commit before it overwrites what that commit reads.  The map stores must outlive the commit.
+ *   DVM_ERR_STATE: commit before any optimize, after an optimize that failed, of a window committed already (k = -1 with nothing left
+ *             is DVM_OK), of a window whose ref_edge was NULL; k outside [-1, K) is DVM_ERR_INVALID.
+ *   Refused on the host before anything is queued, no output written, the handle and a previous optimize's commits left as they were
+ *   except that a refused optimize counts as failed: DVM_ERR_INVALID -- a NULL array, a store on another device, a keyframe slot outside
+ *             its store, never written or removed, an edge index out of range, kp outside [0, n) of its slot, a map slot out of range,
+ *             never written or named twice in one window, ref_edge[l] out of range or not an edge of point l (-1 is legal only on a
+ *             point without edges), an invalid model; DVM_ERR_CAPACITY -- more than 30 free cameras in a window.
+ *   last_bytes  what the last optimize sent up (tables, observations, slot lists, views) and fetched.
+ * Calls on one handle are not concurrent; the calls on the stores it names follow the stores' rules.  sizeof(dvm_ba_obs) == 12,
+ * sizeof(dvm_ba_window_resident) == 192 (LP64). */
+typedef struct { int32_t pose, point, kp; } dvm_ba_obs;   /* camera and point of THIS window, keypoint index in that camera's keyframe */
+typedef struct {
+  int32_t n_poses, n_points, n_edges, iterations;
+  const double* poses;           /* [n_poses][7] world -> camera, as dvm_ba_window */
+  const uint8_t* fixed;          /* [n_poses] */
+  const dvm_keyframe_store* keyframes;
+  const int32_t* kf_slot;        /* [n_poses] */
+  const float* ow;               /* [n_poses][3] or NULL: GetCameraCenter() of the FIXED cameras (rows of free cameras are not read) */
+  dvm_map_store* points;
+  const int32_t* mp_slot;        /* [n_points], each slot at most once per window */
+  const dvm_ba_obs* obs;         /* [n_edges], a point's edges in MapPoint::GetObservations() order */
+  const int32_t* ref_edge;       /* [n_points] or NULL: the edge that is the point's observation by mpRefKF; NULL: the window cannot be committed */
+  dvm_ba_camera cam;             /* as dvm_ba_window (huber_delta read for every model) */
+  double chi2_erase;             /* 5.991 for the monocular edge */
+  double* poses_out;             /* as dvm_ba_window, any may be NULL */
+  double* points_out;
+  double* edge_chi2_out;
+  uint8_t* depth_positive_out;
+  float* geometry_out;           /* [n_points][8] or NULL: pos[3], normal[3], min_dist, max_dist as the commit would write them */
+  uint8_t* point_dirty_out;      /* [n_points] or NULL */
+  float* ow_out;                 /* [n_poses][3] or NULL: the camera centres the normals were taken from */
+} dvm_ba_window_resident;
+typedef struct dvm_ba_resident dvm_ba_resident;
+int dvm_ba_resident_create(int device, dvm_ba_resident** out);
+void dvm_ba_resident_destroy(dvm_ba_resident* h);
+int dvm_ba_resident_optimize(dvm_ba_resident* h, const dvm_ba_window_resident* windows, const dvm_camera_model* models /* [K] or NULL: pinhole cam */,
+                             int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats);
+int dvm_ba_resident_commit(dvm_ba_resident* h, int k /* window of the last optimize; -1: every window not yet committed */);
+int dvm_ba_resident_last_bytes(const dvm_ba_resident* h, int64_t* host_to_device, int64_t* device_to_host);
+
 #ifdef __cplusplus
 }
 #endif
