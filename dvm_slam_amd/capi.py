@@ -1770,6 +1770,18 @@ class TrackerBatch(_TrackerBase):
         return self._refkf_batch(voc, kfs, store, poses_last, K, inv_sigma2, nnratio, check_ori, th_low, min_matches, min_map, levelsup)
 
 
+MP_OBS_DTYPE = np.dtype([("kf", "<i4"), ("kp", "<i4")])                                   # == dvm_mp_obs
+MP_REFRESH_KF_DTYPE = np.dtype([("slot", "<i4"), ("flags", "<u4"), ("ow", "<f4", (3,))])    # == dvm_mp_refresh_kf
+MPR_KF_BAD, MPR_DESCRIPTOR, MPR_GEOMETRY = 1, 1, 2
+
+
+class MpRefresh(C.Structure):
+    """dvm_mp_refresh (include/dvmslam_hip.h)"""
+    _fields_ = [("n_points", C.c_int32), ("n_kfs", C.c_int32), ("n_obs", C.c_int32), ("what", C.c_uint32), ("mp_slot", C.c_void_p),
+                ("obs_off", C.c_void_p), ("obs", C.c_void_p), ("ref_obs", C.c_void_p), ("kfs", C.c_void_p), ("is_new", C.c_void_p),
+                ("new_pos", C.c_void_p), ("best_obs_out", C.c_void_p), ("best_median_out", C.c_void_p), ("geometry_out", C.c_void_p)]
+
+
 # ---- an agent's map points resident on the device (dvm_map_store, include/dvmslam_hip.h), read by the two tracked-frame halves above
 class MapStore:
     """dvm_map_store: `capacity` slots of LOCAL_POINT_DTYPE records in device memory.  update() writes records to slots (asynchronous; every
@@ -1802,6 +1814,54 @@ class MapStore:
         f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         check(f(self.h, len(slots), _p(slots), _p(out)))
         return out
+
+    def refresh(self, kf_store, mp_slots, obs_off, obs, ref_obs, kfs, is_new=None, new_pos=None, what=3, want_geometry=False, out=None):
+        """dvm_map_store_refresh: ComputeDistinctiveDescriptors + UpdateNormalAndDepth into the records of mp_slots, from the descriptor
+        rows kf_store's slots hold.  obs (MP_OBS_DTYPE) in CSR order by obs_off [n + 1]; ref_obs [n]: mpRefKF's observation inside each
+        point's list; kfs (MP_REFRESH_KF_DTYPE); is_new [n] + new_pos [n, 3]: points that enter the store with this call.  Returns
+        dict(best_obs [n] (-1: descriptor not written), best_median [n], geometry [n, 8] or None) -- `out` itself when the caller
+        brings the arrays (int32 [n], int32 [n], float32 [n, 8] or None)."""
+        mp_slots = np.ascontiguousarray(mp_slots, np.int32); obs_off = np.ascontiguousarray(obs_off, np.int32)
+        obs = np.ascontiguousarray(obs, MP_OBS_DTYPE); ref_obs = np.ascontiguousarray(ref_obs, np.int32)
+        kfs = np.ascontiguousarray(kfs, MP_REFRESH_KF_DTYPE)
+        n = len(mp_slots)
+        assert obs_off.shape == (n + 1,) and ref_obs.shape == (n,)
+        if is_new is not None:
+            is_new = np.ascontiguousarray(is_new, np.uint8); new_pos = np.ascontiguousarray(new_pos, np.float32).reshape(-1, 3)
+            assert is_new.shape == (n,) and new_pos.shape == (n, 3)
+        if out is None:
+            out = dict(best_obs=np.zeros(n, np.int32), best_median=np.zeros(n, np.int32), geometry=np.zeros((n, 8), np.float32) if want_geometry else None)
+        want_geometry = out["geometry"] is not None
+        assert out["best_obs"].shape == out["best_median"].shape == (n,) and out["best_obs"].dtype == out["best_median"].dtype == np.int32
+        assert not want_geometry or (out["geometry"].shape == (n, 8) and out["geometry"].dtype == np.float32 and out["geometry"].flags.c_contiguous)
+        a = MpRefresh(n, len(kfs), len(obs), int(what), mp_slots.ctypes.data, obs_off.ctypes.data, obs.ctypes.data, ref_obs.ctypes.data, kfs.ctypes.data,
+                      None if is_new is None else is_new.ctypes.data, None if is_new is None else new_pos.ctypes.data, out["best_obs"].ctypes.data,
+                      out["best_median"].ctypes.data, out["geometry"].ctypes.data if want_geometry else None)
+        f = self.L.dvm_map_store_refresh
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        check(f(self.h, kf_store.h, C.byref(a)))
+        return out
+
+    def last_refresh_bytes(self):
+        """(host to device, device to host) of the last refresh."""
+        up, down = C.c_int64(0), C.c_int64(0)
+        f = self.L.dvm_map_store_last_refresh_bytes
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        check(f(self.h, C.byref(up), C.byref(down)))
+        return up.value, down.value
+
+    def profile(self, enable=True):
+        """HIP-event timing of the refresh kernel on / off (measurement only)."""
+        f = self.L.dvm_map_store_profile
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_int32]
+        check(f(self.h, int(bool(enable))))
+
+    def last_refresh_ms(self):
+        ms = C.c_float(0)
+        f = self.L.dvm_map_store_last_refresh_ms
+        f.restype = C.c_int32; f.argtypes = [C.c_void_p, C.c_void_p]
+        check(f(self.h, C.byref(ms)))
+        return ms.value
 
     def close(self):
         if getattr(self, "h", None) and self.h.value:

@@ -9,6 +9,7 @@
 #include "ba_window_common.h"
 #include "keyframe_store.h"
 #include "map_store.h"
+#include "point_geometry.h"
 #include "pose_f32.h"
 
 namespace dvm {
@@ -60,10 +61,8 @@ __global__ void __launch_bounds__(64) k_ba_res_centres(const ResidentWinDev* __r
   }
 }
 
-__device__ __forceinline__ float res_norm3(const float* d) { return sqrtf(dvm_pose::sum3(d[0] * d[0], d[1] * d[1], d[2] * d[2])); }
-
 // blockIdx.y = window, a lane per point (its edges: a few tens at most).  Dirty: an edge with chi2 > chi2_erase or no positive depth
-// (Optimizer.cc:1324).  Clean and used: SetWorldPos + UpdateNormalAndDepth (MapPoint.cc:473-540) over the edges in the caller's order.
+// (Optimizer.cc:1324).  Clean and used: SetWorldPos + UpdateNormalAndDepth over the edges in the caller's order (point_geometry.h).
 __global__ void __launch_bounds__(256) k_ba_res_points(const ResidentWinDev* __restrict__ wins) {
   const ResidentWinDev& W = wins[blockIdx.y];
   const int l = blockIdx.x * 256 + threadIdx.x;
@@ -80,22 +79,15 @@ __global__ void __launch_bounds__(256) k_ba_res_points(const ResidentWinDev* __r
     const float pos[3] = {(float)W.out_pts[3 * (size_t)l], (float)W.out_pts[3 * (size_t)l + 1], (float)W.out_pts[3 * (size_t)l + 2]};
     float normal[3] = {0.f, 0.f, 0.f};
     for (int q = q0; q < q1; q++) {
-      const float* ow = W.ow + 3 * W.obs[W.pe_edges[q]].pose;
-      const float d[3] = {pos[0] - ow[0], pos[1] - ow[1], pos[2] - ow[2]};
-      const float n = res_norm3(d);
-      normal[0] = normal[0] + d[0] / n; normal[1] = normal[1] + d[1] / n; normal[2] = normal[2] + d[2] / n;
+      float t[3];
+      geo_term(pos, W.ow + 3 * W.obs[W.pe_edges[q]].pose, t);
+      geo_add(normal, t[0], t[1], t[2]);
     }
-    const float cnt = (float)(q1 - q0);
-    g[0] = pos[0]; g[1] = pos[1]; g[2] = pos[2];
-    g[3] = normal[0] / cnt; g[4] = normal[1] / cnt; g[5] = normal[2] / cnt;
+    geo_mean(pos, normal, q1 - q0, g);
     if (W.ref_edge) {
       const dvm_ba_obs ref = W.obs[W.ref_edge[l]];
       const ResidentKf kf = W.kf[ref.pose];
-      const float* ow = W.ow + 3 * ref.pose;
-      const float d[3] = {pos[0] - ow[0], pos[1] - ow[1], pos[2] - ow[2]};
-      const float max_dist = res_norm3(d) * kf.sf[kf.kps[ref.kp].octave];
-      g[7] = max_dist;
-      g[6] = max_dist / kf.sf[kf.n_levels - 1];
+      geo_distances(pos, W.ow + 3 * ref.pose, kf.sf, kf.kps[ref.kp].octave, kf.n_levels, g);
     }
   }
   for (int c = 0; c < 8; c++) {

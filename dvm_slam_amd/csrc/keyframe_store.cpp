@@ -105,6 +105,7 @@ bool kfs_slot_view(const dvm_keyframe_store* st, int32_t slot, KfSlotView* v) {
   return true;
 }
 uint32_t kfs_generation(const dvm_keyframe_store* st, int32_t slot) { return (uint32_t)slot < (uint32_t)st->capacity ? st->meta[slot].gen : 0u; }
+KfsBlockView kfs_block_view(const dvm_keyframe_store* st) { return KfsBlockView{st->d, st->L.stride, st->L.kps, st->L.desc, st->L.sf}; }
 int kfs_read_begin(const dvm_keyframe_store* cst, hipStream_t s) {
   dvm_keyframe_store* st = const_cast<dvm_keyframe_store*>(cst);
   if (!st->write_pending) return DVM_OK;

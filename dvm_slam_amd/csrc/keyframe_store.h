@@ -32,6 +32,9 @@ int kfs_device(const dvm_keyframe_store* st);
 bool kfs_slot_view(const dvm_keyframe_store* st, int32_t slot, KfSlotView* v);
 // the slot's generation now (put and remove bump it); 0 for a slot outside the store
 uint32_t kfs_generation(const dvm_keyframe_store* st, int32_t slot);
+// the store's block for a kernel that forms slot addresses itself: slot sl's arrays begin at base + sl * stride + kps / desc / sf
+struct KfsBlockView { const uint8_t* base; size_t stride, kps, desc, sf; };
+KfsBlockView kfs_block_view(const dvm_keyframe_store* st);
 int kfs_read_begin(const dvm_keyframe_store* st, hipStream_t s);
 int kfs_read_end(const dvm_keyframe_store* st, hipStream_t s);
 

@@ -11,6 +11,10 @@
 //            staging block again.
 //   a chain  store_read_begin: its stream waits for `write_ev`; store_read_end: `read_ev` recorded behind its reading kernels.
 // So a reader always sees every update queued before it, and an update never overtakes a reader in flight.
+//   refresh  (dvm_map_store_refresh) writes records in place from the keyframe store's descriptors: on the calling thread's staging stream
+//            (host_stage.h), which waits for `read_ev` AND `write_ev` -- it is a writer behind every reader and every earlier writer --,
+//            bracketed as a reader of the keyframe store; it records `write_ev` behind its launch and synchronises once, so whatever
+//            follows it, on any stream, sees its records.
 // Safety: the host keeps a written flag per slot; every slot a call names is checked against capacity and that flag BEFORE anything is
 // queued, so no kernel indexes the store with an unchecked value.
 #include <algorithm>
@@ -21,6 +25,9 @@
 
 #include "../../include/dvmslam_hip.h"
 #include "chain.h"
+#include "host_stage.h"
+#include "keyframe_store.h"
+#include "map_refresh_lists.h"
 #include "map_store.h"
 
 using namespace dvm;
@@ -42,6 +49,10 @@ struct dvm_map_store {
     if (write_pending) { DVM_HIP(hipEventSynchronize(write_ev)); write_pending = false; }
     return DVM_OK;
   }
+  // dvm_map_store_refresh: what the last one moved, its kernel's time when profiling, the call's keyframe table as the kernel takes it
+  int64_t refresh_h2d = 0, refresh_d2h = 0;
+  EventTimer timer; float refresh_ms = 0.f;
+  std::vector<MprKfMeta> kf_meta; std::vector<MprKfDev> kf_dev;
 };
 
 namespace dvm {
@@ -145,6 +156,7 @@ void dvm_map_store_destroy(dvm_map_store* st) {
   if (st->s) (void)hipStreamDestroy(st->s);
   if (st->write_ev) (void)hipEventDestroy(st->write_ev);
   if (st->read_ev) (void)hipEventDestroy(st->read_ev);
+  st->timer.destroy();
   if (st->d) (void)hipFree(st->d);
   if (st->hm) (void)hipHostFree(st->hm);
   delete st;
@@ -194,6 +206,114 @@ int dvm_map_store_read(dvm_map_store* st, int n, const int32_t* slots, dvm_local
     DVM_HIP(hipStreamSynchronize(st->s));
     std::memcpy(out + done, st->stage_recs(), (size_t)m * sizeof(LocalPointPod));
   }
+  return DVM_OK;
+}
+
+int dvm_map_store_refresh(dvm_map_store* st, const dvm_keyframe_store* ks, const dvm_mp_refresh* in) {
+  static const char* fn = "dvm_map_store_refresh: ";
+  auto refuse = [&](int rc, const std::string& msg) { set_error(fn + msg); return rc; };
+  if (!st || !ks || !in) return refuse(DVM_ERR_INVALID, "missing argument");
+  {
+    const MprVerdict v = mpr_check_args(*in);
+    if (v.fault == kMprCounts) return refuse(DVM_ERR_INVALID, "a negative count");
+    if (v.fault == kMprWhat) return refuse(DVM_ERR_INVALID, "what = " + std::to_string(in->what) + ": not DESCRIPTOR, GEOMETRY or both");
+    if (v.fault != kMprOk) return refuse(DVM_ERR_INVALID, "a required array is NULL (ref_obs with GEOMETRY; is_new and new_pos come together)");
+  }
+  if (kfs_device(ks) != st->device) return refuse(DVM_ERR_INVALID, "the keyframe store lives on another device");
+  const int L = in->n_points, K = in->n_kfs;
+  // what the keyframe store knows of every entry, then every list: decided before anything is queued
+  st->kf_meta.assign((size_t)K, MprKfMeta{-1, 0});
+  st->kf_dev.resize((size_t)K);
+  for (int k = 0; k < K; k++) {
+    const dvm_mp_refresh_kf& f = in->kfs[k];
+    KfSlotView v;
+    if (f.slot >= 0 && kfs_slot_view(ks, f.slot, &v)) st->kf_meta[k] = MprKfMeta{v.n, v.n_levels};
+    MprKfDev& d = st->kf_dev[k];
+    d.slot = f.slot; d.fl = (f.flags & DVM_MPR_KF_BAD) | ((uint32_t)st->kf_meta[k].n_levels << 8);
+    d.ow[0] = f.ow[0]; d.ow[1] = f.ow[1]; d.ow[2] = f.ow[2];
+  }
+  if (++st->gen == 0) { std::fill(st->stamp.begin(), st->stamp.end(), 0u); st->gen = 1; }
+  const MprVerdict v = mpr_check_lists(*in, st->capacity, st->written.data(), st->stamp.data(), st->gen, st->kf_meta.data());
+  if (v.fault != kMprOk) {
+    const std::string pt = v.point >= 0 ? "point " + std::to_string(v.point) + (v.point < L ? " (slot " + std::to_string(in->mp_slot[v.point]) + ")" : std::string()) : std::string();
+    const std::string kf = v.kf >= 0 ? "keyframe " + std::to_string(v.kf) + " (slot " + std::to_string(in->kfs[v.kf].slot) + ")" : std::string();
+    const std::string ob = v.obs >= 0 ? ", observation " + std::to_string(v.obs - in->obs_off[v.point]) : std::string();
+    switch (v.fault) {
+      case kMprOff: return refuse(v.rc(), "obs_off not monotone from 0 to n_obs at entry " + std::to_string(v.point));
+      case kMprKfFlags: return refuse(v.rc(), kf + ": unknown flags");
+      case kMprKfSlot: return refuse(v.rc(), kf + ": slot outside the keyframe store, never written or removed");
+      case kMprMapSlot: return refuse(v.rc(), pt + ": slot outside [0, capacity)");
+      case kMprMapTwice: return refuse(v.rc(), pt + ": slot named twice in one call");
+      case kMprUnwritten: return refuse(v.rc(), pt + ": an old point whose slot was never written");
+      case kMprNewEmpty: return refuse(v.rc(), pt + ": a new point without observations");
+      case kMprNewWhat: return refuse(v.rc(), pt + ": a new point needs what = DESCRIPTOR | GEOMETRY");
+      case kMprTooMany: return refuse(v.rc(), pt + ": more than " + std::to_string(kMprMaxObs) + " observations");
+      case kMprObsKf: return refuse(v.rc(), pt + ob + ": kf outside [0, n_kfs)");
+      case kMprKp: return refuse(v.rc(), pt + ob + ": kp outside [0, n) of " + kf);
+      case kMprRef: return refuse(v.rc(), pt + ": ref_obs outside [0, N)");
+      default: return refuse(v.rc(), pt + ": the ref observation lies on " + kf + ", a bad keyframe without a slot");
+    }
+  }
+  st->refresh_h2d = st->refresh_d2h = 0; st->refresh_ms = 0.f;
+  if (L == 0) return DVM_OK;
+  DVM_HIP(hipSetDevice(st->device));
+  // one upload; the outputs are written by the kernel into page-locked memory (each entry once: nothing but the results comes down)
+  Stage stg;
+  const size_t l = (size_t)L;
+  const int i_slot = stg.in(in->mp_slot, 4 * l), i_off = stg.in(in->obs_off, 4 * (l + 1)), i_obs = stg.in(in->obs, sizeof(dvm_mp_obs) * (size_t)in->n_obs);
+  const int i_ref = stg.in(in->ref_obs, 4 * l), i_kf = stg.in(K ? st->kf_dev.data() : nullptr, sizeof(MprKfDev) * (size_t)K);
+  const int i_new = stg.in(in->is_new, l), i_pos = stg.in(in->new_pos, 12 * l);
+  const int o_best = stg.out_mapped(in->best_obs_out, 4 * l), o_med = stg.out_mapped(in->best_median_out, 4 * l), o_geo = stg.out_mapped(in->geometry_out, 32 * l);
+  { const int rc = stg.upload(); if (rc != DVM_OK) return rc; }
+  hipStream_t s = stg.stream();
+  if (st->read_pending) {                                          // a writer: behind the chain kernels that read the records ...
+    DVM_HIP(hipStreamWaitEvent(s, st->read_ev, 0));
+    st->read_pending = false;
+  }
+  { const int rc = store_read_begin(st, s); if (rc != DVM_OK) return rc; }     // ... and behind the last update or commit
+  { const int rc = kfs_read_begin(ks, s); if (rc != DVM_OK) return rc; }       // a reader of the keyframe slots
+  const KfsBlockView B = kfs_block_view(ks);
+  MprArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.records = st->d;
+  A.kf_base = B.base; A.kf_stride = B.stride; A.kf_kps = B.kps; A.kf_desc = B.desc; A.kf_sf = B.sf;
+  A.mp_slot = stg.ptr<int32_t>(i_slot); A.obs_off = stg.ptr<int32_t>(i_off); A.obs = stg.ptr<dvm_mp_obs>(i_obs); A.ref_obs = stg.ptr<int32_t>(i_ref);
+  A.kfs = stg.ptr<MprKfDev>(i_kf); A.is_new = stg.ptr<uint8_t>(i_new); A.new_pos = stg.ptr<float>(i_pos);
+  A.best_obs_out = stg.ptr<int32_t>(o_best); A.best_median_out = stg.ptr<int32_t>(o_med); A.geometry_out = stg.ptr<float>(o_geo);
+  A.n_points = L; A.what = in->what;
+  DVM_HIP(st->timer.mark(0, s));
+  launch_mp_refresh(s, A, v.max_obs > 64);
+  { const int rc = hip_check(hipGetLastError(), "k_mp_refresh"); if (rc != DVM_OK) return rc; }
+  DVM_HIP(st->timer.mark(1, s));
+  { const int rc = kfs_read_end(ks, s); if (rc != DVM_OK) return rc; }
+  DVM_HIP(hipEventRecord(st->write_ev, s));
+  st->write_pending = true;
+  // the ONE synchronisation: the outputs lie in page-locked memory behind it
+  { const int rc = stg.download(); if (rc != DVM_OK) return rc; }
+  st->write_pending = false;
+  if (in->is_new)
+    for (int p = 0; p < L; p++) if (in->is_new[p]) st->written[in->mp_slot[p]] = 1;
+  st->refresh_h2d = (int64_t)stg.in_bytes;
+  st->refresh_d2h = (int64_t)(4 * l) * (1 + (in->best_median_out ? 1 : 0) + (in->geometry_out ? 8 : 0));
+  if (st->timer.on) DVM_HIP(st->timer.elapsed(0, 1, &st->refresh_ms));
+  return DVM_OK;
+}
+
+int dvm_map_store_last_refresh_bytes(const dvm_map_store* st, int64_t* host_to_device, int64_t* device_to_host) {
+  if (!st || !host_to_device || !device_to_host) return DVM_ERR_INVALID;
+  *host_to_device = st->refresh_h2d; *device_to_host = st->refresh_d2h;
+  return DVM_OK;
+}
+
+int dvm_map_store_profile(dvm_map_store* st, int enable) {
+  if (!st) return DVM_ERR_INVALID;
+  DVM_HIP(hipSetDevice(st->device));
+  return st->timer.enable(enable != 0);
+}
+
+int dvm_map_store_last_refresh_ms(const dvm_map_store* st, float* kernel_ms) {
+  if (!st || !kernel_ms) return DVM_ERR_INVALID;
+  *kernel_ms = st->refresh_ms;
   return DVM_OK;
 }
 

@@ -41,4 +41,20 @@ void launch_store_commit(hipStream_t s, LocalPointPod* dst, const StoreCommit& C
 // queues the ranges as dvm_map_store_update queues its scatter: on the store's stream behind read_ev, write_ev recorded, no wait; `done`
 // (the caller's) is recorded behind the last launch: the ranges' memory may be overwritten once it has passed
 int store_commit_geometry(dvm_map_store* st, const StoreCommitRange* ranges, int n, hipEvent_t done);
+
+// dvm_map_store_refresh (map_refresh_kernels.hip): ComputeDistinctiveDescriptors + UpdateNormalAndDepth into the records, a wavefront per
+// point.  What travels up per keyframe entry is the caller's 20 bytes with the slot's level count folded into the flags word; the kernel
+// forms a slot's addresses from the keyframe store's block (base + slot * stride + the layout's offsets).  The entry has checked every
+// index (map_refresh_lists.h): no kernel checks one.
+struct MprKfDev { int32_t slot; uint32_t fl; float ow[3]; };      // fl = flags & DVM_MPR_KF_BAD | n_levels << 8
+struct MprArgs {
+  LocalPointPod* records;                                          // the map store's block
+  const uint8_t* kf_base; size_t kf_stride, kf_kps, kf_desc, kf_sf;   // the keyframe store's block: slot stride, offsets of kps / desc / scale factors in a slot
+  const int32_t *mp_slot, *obs_off; const dvm_mp_obs* obs; const int32_t* ref_obs; const MprKfDev* kfs;
+  const uint8_t* is_new; const float* new_pos;                     // both null: no new point
+  int32_t *best_obs_out, *best_median_out; float* geometry_out;    // the last two may be null
+  int32_t n_points; uint32_t what;
+};
+// big: some point has more than 64 observations (the form with the LDS descriptor table); otherwise the form without LDS
+void launch_mp_refresh(hipStream_t s, const MprArgs& A, bool big);
 }  // namespace dvm

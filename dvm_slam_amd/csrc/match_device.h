@@ -212,4 +212,50 @@ __device__ __forceinline__ uint32_t bow_node_scan(const uint8_t* __restrict__ qd
   return wave_min(best);
 }
 
+// ---- MapPoint::ComputeDistinctiveDescriptors' order statistic (reference src/MapPoint.cc:384-453), shared by k_distinctive
+// (match_kernels.hip) and k_mp_refresh (map_refresh_kernels.hip).  kth_distance: the smallest v in [0, 256] with count_le(v) > k -- the
+// k-th value of a sorted row of Hamming distances -- by a binary search over the value range, nine steps, no sort; count_le(v) counts the
+// row's entries <= v (ballots) and is wave-uniform.
+constexpr int kDistinctMaxN = 512;
+template <class CountLE>
+__device__ __forceinline__ int kth_distance(int k, CountLE count_le) {
+  int lo = 0, hi = 256;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (count_le(mid) > k) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+// The LDS form, for ONE wavefront that is its whole workgroup: s_desc [N][8] holds the N <= kDistinctMaxN descriptors (written and
+// made visible by the caller: a barrier behind its stores), s_row [N] is scratch.  Row i = one distance per lane in chunks of 64, its
+// median = sorted_row[(N - 1) >> 1] with the self distance included.  Returns median << 16 | i of the first row with the strictly
+// smallest median, in every lane; s_desc is as it was and no lane is still reading s_row.
+__device__ __forceinline__ uint32_t distinctive_lds(const uint32_t* s_desc, uint16_t* s_row, int N, int lane) {
+  const int k = (N - 1) >> 1;                     // (size_t)(0.5 * (N - 1))
+  uint32_t best = 0xFFFFFFFFu;
+  for (int i = 0; i < N; i++) {
+    uint32_t di[8];
+#pragma unroll
+    for (int w = 0; w < 8; w++) di[w] = s_desc[i * 8 + w];
+    for (int j = lane; j < N; j += 64) {
+      int d = 0;
+#pragma unroll
+      for (int w = 0; w < 8; w++) d += __popc(di[w] ^ s_desc[j * 8 + w]);
+      s_row[j] = (uint16_t)d;
+    }
+    __syncthreads();
+    const int med = kth_distance(k, [&](int mid) {
+      int cnt = 0;
+      for (int base = 0; base < N; base += 64) {
+        const int j = base + lane;
+        cnt += __popcll(__ballot(j < N && (int)s_row[j] <= mid));
+      }
+      return cnt;
+    });
+    best = min(best, ((uint32_t)med << 16) | (uint32_t)i);
+    __syncthreads();
+  }
+  return best;
+}
+
 }  // namespace dvm

@@ -1086,6 +1086,65 @@ int dvm_map_store_capacity(const dvm_map_store* s);
 int dvm_map_store_update(dvm_map_store* s, int n, const int32_t* slots, const dvm_local_point* records);
 int dvm_map_store_read(dvm_map_store* s, int n, const int32_t* slots, dvm_local_point* out);
 
+/* ---- A map point's record made where it lies: MapPoint::ComputeDistinctiveDescriptors() + MapPoint::UpdateNormalAndDepth() (src/MapPoint.cc:
+ * 384-453, 473-540) -- what LocalMapping runs in ProcessNewKeyFrame, at the end of CreateNewMapPoints and at the end of SearchInNeighbors --
+ * from the descriptor rows the keyframe slots hold (dvm_keyframe_store, below) and the position the map slot holds.  The call names slots:
+ * 8 B per observation and about 25 B per point travel up, 4 B per point come down (which observation's descriptor won, so that the host
+ * MapPoint copies its own row).  No camera model is read.  N = a point's observation count, its list in GetObservations() order.
+ *   DESCRIPTOR  candidates: the observations on keyframes without DVM_MPR_KF_BAD, in list order (:406).  Winner and median are
+ *               dvm_distinctive_descriptors' on that set (median = sorted_row[(N' - 1) >> 1], self distance included, the first strictly
+ *               smaller median wins); best_obs_out = the winner's index in the point's FULL list, the record's desc = that keyframe
+ *               slot's row.  No candidate: best_obs_out = best_median_out = -1 and desc is not touched (a new point's desc: zeros).
+ *   GEOMETRY    (N >= 1) pos = the record's own, or new_pos for a new point.  All N observations count, bad keyframes too (:493-512):
+ *               normal = (((0 + t0) + t1) + ...) / (float)N, t = d / |d| per component, d = pos - ow, |d| = sqrt(d0 d0 + (d1 d1 + d2 d2));
+ *               max_dist = |pos - ow_ref| * sf_ref[octave of the ref keypoint], min_dist = max_dist / sf_ref[n_levels_ref - 1], the level
+ *               table read from the ref keyframe's slot.  float32, one rounding per operation: the bits dvm_ba_resident_commit writes.
+ *   the record  n_obs = N in every case.  Old point: pos and bad are kept, only the groups in `what` are written; N = 0: nothing but n_obs.
+ *               New point (is_new[p] != 0): the whole record -- pos = new_pos, bad = 0 --; it needs what = both and N >= 1, and its slot
+ *               counts as written from this call on.
+ *   outputs     best_obs_out -1 where the descriptor was not asked for or not written; geometry_out: pos, normal, min_dist, max_dist as
+ *               the record holds them after the call.
+ *   refusals    decided on the host before anything is queued: nothing is written, a new slot stays unwritten, dvm_last_error names the
+ *               point or keyframe.  DVM_ERR_INVALID: a NULL required array (ref_obs is required with GEOMETRY, is_new and new_pos come
+ *               together); what = 0 or unknown bits; stores on different devices; obs_off not monotone from 0 to n_obs; a map slot outside
+ *               the store or named twice; an old point's slot never written; a new point with N = 0 or what != both; obs.kf outside
+ *               [0, n_kfs); a keyframe slot outside its store, never written or removed; unknown keyframe flags; kp outside [0, n) of its
+ *               slot; ref_obs outside [0, N) when GEOMETRY and N >= 1.  An entry with DVM_MPR_KF_BAD may carry slot = -1 (the keyframe
+ *               has left the store): the kp of its observations is then not checked, and it may not be a point's ref (DVM_ERR_INVALID).
+ *               DVM_ERR_CAPACITY: a point with more than 512 observations.
+ *   ordering    the inputs go up in one copy on the calling thread's staging stream; ONE launch (k_mp_refresh, a wavefront per point)
+ *               there.  The call is a WRITER of the map store -- it waits for the last kernel queued to read it and for the last update or
+ *               commit -- and a READER of the keyframe store (it waits for the last put; the next put waits for it).  It synchronises
+ *               once; the outputs are valid and new slots are written when it returns.
+ *   last_refresh_bytes   what the last refresh sent up (its one copy) and what came down (the kernel's writes into page-locked memory).
+ *   profile / last_refresh_ms   with profiling enabled, k_mp_refresh's time by HIP events (measurement only).
+ * sizeof(dvm_mp_obs) == 8 (kf 0, kp 4); sizeof(dvm_mp_refresh_kf) == 20 (slot 0, flags 4, ow 8); sizeof(dvm_mp_refresh) == 96 (LP64:
+ * n_points 0, n_kfs 4, n_obs 8, what 12, mp_slot 16, obs_off 24, obs 32, ref_obs 40, kfs 48, is_new 56, new_pos 64, best_obs_out 72,
+ * best_median_out 80, geometry_out 88). */
+typedef struct { int32_t kf, kp; } dvm_mp_obs;                     /* 8 B: index into the call's keyframe table; keypoint index in that keyframe */
+#define DVM_MPR_KF_BAD 1u
+typedef struct { int32_t slot; uint32_t flags; float ow[3]; } dvm_mp_refresh_kf;   /* 20 B: keyframe-store slot, pKF->isBad(), GetCameraCenter() */
+#define DVM_MPR_DESCRIPTOR 1u
+#define DVM_MPR_GEOMETRY   2u
+typedef struct {
+  int32_t n_points, n_kfs, n_obs; uint32_t what;   /* what: DESCRIPTOR, GEOMETRY or both */
+  const int32_t* mp_slot;          /* [n_points] map-store slot of each point */
+  const int32_t* obs_off;          /* [n_points + 1] CSR, 0 .. n_obs */
+  const dvm_mp_obs* obs;           /* [n_obs] a point's observations in MapPoint::GetObservations() order */
+  const int32_t* ref_obs;          /* [n_points] index INSIDE the point's own list of mpRefKF's observation */
+  const dvm_mp_refresh_kf* kfs;    /* [n_kfs] */
+  const uint8_t* is_new;           /* [n_points] or NULL (none new) */
+  const float* new_pos;            /* [n_points][3] GetWorldPos() of the new points (rows of old points not read); NULL iff is_new is NULL */
+  int32_t* best_obs_out;           /* [n_points] index inside the point's list of the winning observation; -1: descriptor not written */
+  int32_t* best_median_out;        /* [n_points] or NULL */
+  float* geometry_out;             /* [n_points][8] pos, normal, min_dist, max_dist as written, or NULL */
+} dvm_mp_refresh;
+struct dvm_keyframe_store;
+int dvm_map_store_refresh(dvm_map_store* ms, const struct dvm_keyframe_store* ks, const dvm_mp_refresh* in);
+int dvm_map_store_last_refresh_bytes(const dvm_map_store* ms, int64_t* host_to_device, int64_t* device_to_host);
+int dvm_map_store_profile(dvm_map_store* ms, int enable);
+int dvm_map_store_last_refresh_ms(const dvm_map_store* ms, float* kernel_ms);
+
 /* ---- An agent's keyframes resident on the device (csrc/keyframe_store.cpp): the keyframe-side counterpart of dvm_map_store.  What a
  * KeyFrame holds once ComputeBoW has run never changes -- mvKeysUn, mDescriptors, the level tables, the image bounds, mFeatVec and the
  * feature grid --, LocalMapping names the same neighbours step after step and LoopClosing::SearchAndFuse the same hundred keyframes: the
