@@ -2992,6 +2992,15 @@ class _FtPoints(C.Structure):   # == dvm_ft_points
                 ("desc", C.c_void_p), ("valid", C.c_void_p)]
 
 
+class _FtPointsResident(C.Structure):   # == dvm_ft_points_resident
+    _fields_ = [("points", C.c_void_p), ("n", C.c_int32), ("slot", C.c_void_p), ("valid", C.c_void_p)]
+
+
+class _FtCandidates(C.Structure):   # == dvm_ft_candidates
+    _fields_ = [("points", C.c_void_p), ("n_lists", C.c_int32), ("mp_slot", C.c_void_p), ("n", C.c_void_p), ("exclude", C.c_void_p),
+                ("n_exclude", C.c_int32)]
+
+
 HIT_DTYPE = np.dtype([("point", "<i4"), ("idx", "<i4"), ("dist", "<i4")])   # == dvm_ft_hit
 
 
@@ -3138,6 +3147,77 @@ class FuseTargets(_Chain):
         bi = np.full((T, n), -7, np.int32); bd = np.full((T, n), -7, np.int32) if want_dist else None
         check(self.L.dvm_fuse_targets_run(self.h, C.addressof(s), _ptr(sk), float(th), _ptr(bi), _ptr(bd)))
         return bi, bd
+
+    def _points_resident(self, store, slots, skip, valid):
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n, T = len(slots), self.n_targets
+        va = None if valid is None else np.ascontiguousarray(valid, np.uint8).reshape(n)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(T, n)
+        s = _FtPointsResident(None if store is None else store.h, n, _ptr(slots), _ptr(va))
+        return s, sk, (slots, va)
+
+    def run_resident(self, store, slots, th=3.0, skip=None, valid=None, want_dist=True, out=None):
+        """dvm_fuse_targets_run_resident: run() on the records of `store` (a MapStore, or None when every slot is -1) under slots [n]
+        (-1: a masked row); a bad record masks its row on the device.  out: (best_idx, best_dist) arrays of the caller's to fill."""
+        s, sk, keep = self._points_resident(store, slots, skip, valid)
+        n, T = s.n, self.n_targets
+        bi, bd = out if out is not None else (np.full((T, n), -7, np.int32), np.full((T, n), -7, np.int32) if want_dist else None)
+        fn = self.L.dvm_fuse_targets_run_resident
+        fn.restype = C.c_int32; fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        check(fn(self.h, C.addressof(s), _ptr(sk), float(th), _ptr(bi), _ptr(bd)))
+        return bi, bd
+
+    def run_hits_resident(self, store, slots, th=3.0, skip=None, valid=None, hit_cap=None, guard=0):
+        """dvm_fuse_targets_run_hits_resident; arguments as run_resident, result and DvmError as run_hits."""
+        s, sk, keep = self._points_resident(store, slots, skip, valid)
+        n, T = s.n, self.n_targets
+        cap = T * n if hit_cap is None else int(hit_cap)
+        off = np.full(T + 1, -7, np.int32)
+        hits = np.empty(cap + guard + 1, HIT_DTYPE)
+        hits.view(np.int32)[3 * cap:] = -7
+        nh = C.c_int32(-7)
+        fn = self.L.dvm_fuse_targets_run_hits_resident
+        fn.restype = C.c_int32; fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        rc = fn(self.h, C.addressof(s), _ptr(sk), float(th), _ptr(off), _ptr(hits), cap, C.byref(nh))
+        try:
+            check(rc)
+        except DvmError as e:
+            e.hit_off, e.n_hits, e.tail = off, nh.value, hits[cap:cap + guard].copy()
+            raise
+        return off, hits[:nh.value]
+
+    def reserve_candidates(self, max_entries, map_capacity):
+        fn = self.L.dvm_fuse_targets_reserve_candidates
+        fn.restype = C.c_int32; fn.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        check(fn(self.h, int(max_entries), int(map_capacity)))
+
+    def run_hits_candidates(self, store, lists, th=3.0, exclude=None, cand_cap=None, hit_cap=None, guard=0):
+        """dvm_fuse_targets_run_hits_candidates: lists = the target keyframes' GetMapPointMatches() as slots of `store`, exclude = the
+        current keyframe's.  Returns (cand_slot[n_cand], hit_off[T + 1], hits[n_hits]) with hits["point"] an index into cand_slot.  A
+        DvmError of code -3 carries n_cand, hit_off, n_hits and, with guard > 0, `cand_tail`: the guard words behind cand_slot[cand_cap]."""
+        lists = [np.ascontiguousarray(a, np.int32).reshape(-1) for a in lists]
+        L, T = len(lists), self.n_targets
+        total = sum(len(a) for a in lists)
+        ptrs = (C.c_void_p * max(L, 1))(*[a.ctypes.data for a in lists])
+        lens = np.array([len(a) for a in lists], np.int32)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, np.int32).reshape(-1)
+        c = _FtCandidates(None if store is None else store.h, L, C.addressof(ptrs), _ptr(lens), _ptr(ex), 0 if ex is None else len(ex))
+        ccap = total if cand_cap is None else int(cand_cap)
+        cap = T * total if hit_cap is None else int(hit_cap)
+        cand = np.full(ccap + guard + 1, -7, np.int32)
+        off = np.full(T + 1, -7, np.int32)
+        hits = np.empty(cap + 1, HIT_DTYPE)
+        nc, nh = C.c_int32(-7), C.c_int32(-7)
+        fn = self.L.dvm_fuse_targets_run_hits_candidates
+        fn.restype = C.c_int32
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        rc = fn(self.h, C.addressof(c), float(th), _ptr(cand), ccap, C.byref(nc), _ptr(off), _ptr(hits), cap, C.byref(nh))
+        try:
+            check(rc)
+        except DvmError as e:
+            e.n_cand, e.hit_off, e.n_hits, e.cand_tail = nc.value, off, nh.value, cand[ccap:ccap + guard].copy()
+            raise
+        return cand[:nc.value], off, hits[:nh.value]
 
 
 def fuse_targets(kfs, P, in_kf, th, device=0):

@@ -147,5 +147,8 @@ void launch_ft_hits(hipStream_t s, const int32_t* best_idx, const int32_t* best_
   hipLaunchKernelGGL(k_ft_hit_scan, dim3(1), dim3(256), 0, s, cnt, n_targets, off, off_out);
   hipLaunchKernelGGL(k_ft_hit_write, dim3(n_targets), dim3(256), 0, s, best_idx, best_dist, n, off, hits_out, cap);
 }
+void launch_ft_scan(hipStream_t s, const int32_t* cnt, int n, int32_t* off, int32_t* off_out) {
+  hipLaunchKernelGGL(k_ft_hit_scan, dim3(1), dim3(256), 0, s, cnt, n, off, off_out);
+}
 
 }  // namespace dvm

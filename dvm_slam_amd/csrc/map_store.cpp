@@ -25,6 +25,7 @@
 
 #include "../../include/dvmslam_hip.h"
 #include "chain.h"
+#include "fuse_points_lists.h"
 #include "host_stage.h"
 #include "keyframe_store.h"
 #include "map_refresh_lists.h"
@@ -58,6 +59,7 @@ struct dvm_map_store {
 namespace dvm {
 const LocalPointPod* store_records(const dvm_map_store* st) { return st->d; }
 int store_device(const dvm_map_store* st) { return st->device; }
+const uint8_t* store_written(const dvm_map_store* st) { return st->written.data(); }
 bool store_slots_ok(const dvm_map_store* st, const int32_t* slots, int n) {
   const uint32_t cap = (uint32_t)st->capacity;
   const uint8_t* w = st->written.data();
@@ -66,18 +68,7 @@ bool store_slots_ok(const dvm_map_store* st, const int32_t* slots, int n) {
   return true;
 }
 int store_kf_slots_check(const dvm_map_store* st, const int32_t* slots, int n, bool* any) {
-  bool some = false;
-  int rc = 0;
-  for (int k = 0; k < n && !rc; k++) {
-    const int32_t sl = slots[k];
-    if (sl == -1) continue;
-    some = true;
-    if (sl < 0) rc = 1;
-    else if (!st) rc = 2;
-    else if (sl >= st->capacity || !st->written[sl]) rc = 1;
-  }
-  if (any) *any = some;
-  return rc;
+  return fpl_slots_check(FplStore{st ? st->capacity : -1, st ? st->written.data() : nullptr}, slots, n, any);
 }
 int store_read_begin(const dvm_map_store* cst, hipStream_t s) {
   dvm_map_store* st = const_cast<dvm_map_store*>(cst);

@@ -14,6 +14,7 @@
 namespace dvm {
 const LocalPointPod* store_records(const dvm_map_store* st);   // device, [capacity]
 int store_device(const dvm_map_store* st);
+const uint8_t* store_written(const dvm_map_store* st);         // host, [capacity]: an update has named the slot
 // every one of slots[0 .. n) lies in [0, capacity) and has been written
 bool store_slots_ok(const dvm_map_store* st, const int32_t* slots, int n);
 // a keyframe's GetMapPointMatches() as slots (dvm_kf_resident): every one of slots[0 .. n) is -1 (no point) or a written slot of st.

@@ -1278,6 +1278,62 @@ int dvm_fuse_targets_set_resident(dvm_fuse_targets* h, const dvm_keyframe_store*
 /* The host-to-device bytes queued by the last set (uploaded or resident) and the last run; either pointer may be NULL. */
 int dvm_fuse_targets_last_upload_bytes(const dvm_fuse_targets* h, int64_t* set_bytes, int64_t* run_bytes);
 
+/* ---- The Fuse run on points named as map-store slots: dvm_fuse_targets_run / _run_hits with the point table read from the 72-byte
+ * records of a dvm_map_store instead of travelling up.  ONE gather launch (k_ft_gather) fills the handle's point arrays from the records
+ * -- position, normal, distance range, descriptor, and the row's valid flag -- and the search and hit kernels run as they are.
+ *   Row i is searched iff slot[i] >= 0, (valid == NULL or valid[i]), records[slot[i]].bad == 0 and skip[t * n + i] is not set: isBad()
+ *   is read on the device; skip stays the caller's IsInKeyFrame matrix.  A slot may appear more than once (its rows are equal).
+ * Contract: for targets set by dvm_fuse_targets_set[_cam] or by dvm_fuse_targets_set_resident, the dense rows and the hits equal, bit for
+ * bit, dvm_fuse_targets_run[_hits] on the table that dvm_map_store_read of those slots yields with `valid` as above -- both forms, both
+ * model types, mixed targets.
+ * Ordering: the gather and the search are bracketed as a reader of the store on the handle's stream: a run queued behind a
+ * dvm_map_store_update, a dvm_ba_resident_commit or a dvm_map_store_refresh sees their bytes with no host synchronisation between, and a
+ * later update waits for the run.
+ * Bytes up per run: 4 n (+ n with valid) (+ T n with skip), each array rounded up to 64 (dvm_fuse_targets_last_upload_bytes).  n is
+ * bounded by max_points of dvm_fuse_targets_reserve.
+ * Errors, all decided on the host before anything is queued, the handle stays usable and no output array is written: those of
+ * dvm_fuse_targets_run[_hits]; a NULL store where a slot is >= 0, a store on another device, a slot below -1, outside the capacity or
+ * never written: DVM_ERR_INVALID.  n = 0 and T = 0 behave as in the uploaded run. */
+typedef struct {
+  const dvm_map_store* points;   /* the map the points live in; on the handle's device */
+  int32_t n;
+  const int32_t* slot;           /* [n] map-store slots; -1 = NULL pointer (the row is masked); a slot may appear more than once */
+  const uint8_t* valid;          /* [n] or NULL (all) */
+} dvm_ft_points_resident;        /* 32 bytes (LP64) */
+int dvm_fuse_targets_run_resident(dvm_fuse_targets* h, const dvm_ft_points_resident* P, const uint8_t* skip, float th, int32_t* best_idx, int32_t* best_dist);
+int dvm_fuse_targets_run_hits_resident(dvm_fuse_targets* h, const dvm_ft_points_resident* P, const uint8_t* skip, float th,
+                                       int32_t* hit_off /* [T + 1] */, dvm_ft_hit* hits, int hit_cap, int32_t* n_hits);
+
+/* ---- The second direction of SearchInNeighbors (src/LocalMapping.cc:826-846): vpFuseCandidates built and searched on the device.  The
+ * call names the target keyframes' GetMapPointMatches() as map-store slots (4 B per keypoint, as dvm_kf_resident does); the device makes
+ * the candidate list, gathers its records and searches it against the set targets in ONE chain with ONE synchronisation.
+ *   The entries are numbered flat in (list, keypoint) order.  An entry is a candidate iff its slot is >= 0, its record is not bad and no
+ *   earlier entry names the same slot; the candidates keep flat order.  A candidate whose slot is in `exclude` (the current keyframe's
+ *   own list: IsInKeyFrame(mpCurrentKeyFrame)) stays in the list and its rows are masked.
+ * Returns cand_slot[0 .. *n_cand) and the hits of the set targets against that list, hits[].point an index into cand_slot.  Both come
+ * down through a mapped page-locked block: nothing of the size of the bound does.
+ * Contract: cand_slot is the list defined above; hit_off and hits equal dvm_fuse_targets_run_hits_resident with P.slot = cand_slot and
+ * skip[t * n + i] = (cand_slot[i] is in exclude).
+ * dvm_fuse_targets_reserve_candidates: the first-index table of the dedupe (map_capacity words, idle between calls: every call puts it
+ * back through the entries it touched) and the blocks for lists of up to max_entries entries in total (grow-only).  The call before it:
+ * DVM_ERR_INVALID.  The flat length of the lists is the gather's and the search's n: beyond max_points of dvm_fuse_targets_reserve or
+ * max_entries -- or n_exclude beyond max_entries, or a store of more than map_capacity slots -- DVM_ERR_CAPACITY before anything is
+ * queued.  *n_cand > cand_cap: DVM_ERR_CAPACITY, *n_cand holds the full count and nothing is written past cand_slot[cand_cap); the hits
+ * as in dvm_fuse_targets_run_hits; the handle stays usable.  Every list, exclude included, holds -1 or written slots of `points`
+ * (otherwise DVM_ERR_INVALID before anything is queued).  sizeof(dvm_ft_candidates) == 48 (LP64). */
+typedef struct {
+  const dvm_map_store* points;
+  int32_t n_lists;
+  const int32_t* const* mp_slot;  /* [n_lists] a keyframe's GetMapPointMatches() as map-store slots, -1 = none */
+  const int32_t* n;               /* [n_lists] their lengths */
+  const int32_t* exclude;         /* [n_exclude] or NULL: the current keyframe's own mp_slot list (-1 entries ignored) */
+  int32_t n_exclude;
+} dvm_ft_candidates;
+int dvm_fuse_targets_reserve_candidates(dvm_fuse_targets* h, int max_entries, int map_capacity);
+int dvm_fuse_targets_run_hits_candidates(dvm_fuse_targets* h, const dvm_ft_candidates* C, float th,
+                                         int32_t* cand_slot, int cand_cap, int32_t* n_cand,
+                                         int32_t* hit_off /* [T + 1] */, dvm_ft_hit* hits, int hit_cap, int32_t* n_hits);
+
 /* ---- CreateNewMapPoints on resident keyframes: dvm_create_new_map_points[_cam] with every keyframe given as a store slot plus its
  * per-call part -- mvpMapPoints (LocalMapping changes it between any two calls; 4 B per keypoint against about 70) and the pose.
  * Keypoints, descriptors, FeatureVector and level tables are read in the slots; the kernels are the uploaded call's.
