@@ -3364,7 +3364,8 @@ class KeyframeStore:
         for name, args in (("create", [i32, i32, i32, vp]), ("capacity", [vp]), ("slot_keypoints", [vp]), ("put", [vp, i32, vp, vp]), ("remove", [vp, i32, vp]),
                            ("debug_read", [vp, i32, vp]), ("put_device", [vp, vp, i32, vp, i32, vp, vp, vp]),
                            ("put_tracked", [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]), ("last_put_bytes", [vp, vp]), ("profile", [vp, i32]),
-                           ("last_put_ms", [vp, vp])):
+                           ("last_put_ms", [vp, vp]), ("set_rows", [vp, i32, vp, i32, vp, vp]), ("patch_rows", [vp, i32, vp, i32, vp]),
+                           ("debug_read_rows", [vp, i32, i32, vp, i32, vp])):
             f = getattr(self.L, "dvm_keyframe_store_" + name, None)
             if f is None:       # an older library (DVM_HIP_LIB, the measurement tools' baseline): calling the entry raises AttributeError
                 continue
@@ -3514,9 +3515,140 @@ class KeyframeStore:
                     inv_level_sigma2=a["inv_level_sigma2"][:nl].copy(), skp=a["skp"][:ns].copy(), sidx=a["sidx"][:ns].copy(),
                     sdesc=a["sdesc"][:ns].copy(), cell_start=a["cell_start"])
 
+    def set_rows(self, which, points, slots, rows):
+        """dvm_keyframe_store_set_rows: rows[k] (int32, as long as the slot's n; None: a NULL row) becomes the row of kind `which`
+        (KFS_ROW_MATCHES / KFS_ROW_OBSERVED) of slot slots[k]; its values are slots of the MapStore `points` or -1.  Asynchronous."""
+        slots = np.ascontiguousarray(slots, np.int32)
+        assert slots.ndim == 1 and len(slots) == len(rows)
+        keep = [None if r is None else np.ascontiguousarray(r, np.int32) for r in rows]
+        ptrs = (C.c_void_p * max(len(keep), 1))(*[None if r is None else r.ctypes.data for r in keep])
+        check(self.L.dvm_keyframe_store_set_rows(self.h, int(which), None if points is None else points.h, len(slots), _p(slots), C.addressof(ptrs)))
+
+    def patch_rows(self, which, points, edits):
+        """dvm_keyframe_store_patch_rows: edits = KFS_ROW_EDIT_DTYPE records or (slot, kp, value) triples, applied in order."""
+        e = np.asarray(edits)
+        if e.dtype != KFS_ROW_EDIT_DTYPE:
+            e = np.ascontiguousarray(e, np.int32).reshape(-1, 3).view(KFS_ROW_EDIT_DTYPE).reshape(-1)
+        e = np.ascontiguousarray(e)
+        check(self.L.dvm_keyframe_store_patch_rows(self.h, int(which), None if points is None else points.h, len(e), _p(e)))
+
+    def read_rows(self, which, slot):
+        """One row back (synchronous, tests): int32 [n], empty for a row that is not set."""
+        out = np.full(self.slot_keypoints, -7, np.int32)
+        n = C.c_int32(-7)
+        check(self.L.dvm_keyframe_store_debug_read_rows(self.h, int(which), int(slot), _p(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
     def close(self):
         if getattr(self, "h", None) and self.h.value:
             self.L.dvm_keyframe_store_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+
+# ---- Tracking::UpdateLocalMap on the resident stores (dvm_update_local_map, include/dvmslam_hip.h)
+KFS_ROW_MATCHES, KFS_ROW_OBSERVED = 0, 1
+KFS_ROW_EDIT_DTYPE = np.dtype([("slot", "<i4"), ("kp", "<i4"), ("value", "<i4")])      # == dvm_kfs_row_edit
+
+
+class _UlmKeyframesIn(C.Structure):   # == dvm_ulm_keyframes_in
+    _fields_ = [("kfs", C.c_void_p), ("points", C.c_void_p), ("n", C.c_int32), ("mp_slot", C.c_void_p)]
+
+
+class _UlmKeyframesOut(C.Structure):   # == dvm_ulm_keyframes_out
+    _fields_ = [("votes", C.c_void_p), ("frame_bad", C.c_void_p)]
+
+
+class _UlmPointsIn(C.Structure):   # == dvm_ulm_points_in
+    _fields_ = [("kfs", C.c_void_p), ("points", C.c_void_p), ("n_kfs", C.c_int32), ("kf_slot", C.c_void_p), ("n", C.c_int32), ("mp_slot", C.c_void_p)]
+
+
+class _UlmPointsOut(C.Structure):   # == dvm_ulm_points_out
+    _fields_ = [("local_slot", C.c_void_p), ("local_cap", C.c_int32), ("n_local", C.c_int32), ("frame_mp", C.c_void_p), ("n_outside", C.c_int32)]
+
+
+class UpdateLocalMap:
+    """dvm_update_local_map: the vote loop of UpdateLocalKeyFrames and UpdateLocalPoints for the frames of one tick, read from the rows a
+    KeyframeStore keeps (set_rows / patch_rows) and the records of a MapStore.  A frame is a dict; every call is one upload, one chain of
+    launches and one synchronisation."""
+
+    GUARD = 64       # guard words behind every output array (tests look at them)
+
+    def __init__(self, device=0):
+        self.L = lib()
+        vp, i32 = C.c_void_p, C.c_int32
+        _declare(self.L, {"dvm_update_local_map_create": [i32, vp], "dvm_update_local_map_reserve": [vp, i32, i32, i32, i32, i32, i32],
+                          "dvm_update_local_map_keyframes": [vp, i32, vp, vp], "dvm_update_local_map_points": [vp, i32, vp, vp],
+                          "dvm_update_local_map_last_bytes": [vp, vp, vp], "dvm_update_local_map_profile": [vp, i32],
+                          "dvm_update_local_map_last_ms": [vp, vp]})
+        self.L.dvm_update_local_map_destroy.restype = None; self.L.dvm_update_local_map_destroy.argtypes = [vp]
+        self.h = vp()
+        check(self.L.dvm_update_local_map_create(int(device), C.byref(self.h)))
+
+    def reserve(self, max_frames, max_frame_keypoints, max_local_keyframes, map_capacity, kf_capacity, slot_keypoints):
+        check(self.L.dvm_update_local_map_reserve(self.h, int(max_frames), int(max_frame_keypoints), int(max_local_keyframes), int(map_capacity),
+                                                  int(kf_capacity), int(slot_keypoints)))
+
+    def keyframes(self, frames):
+        """frames: dict(kfs=KeyframeStore, points=MapStore, mp_slot=int32 [n]) per frame.  Returns per frame dict(votes [capacity of kfs],
+        frame_bad [n] uint8); the arrays carry GUARD untouched entries behind them under votes_guarded / frame_bad_guarded."""
+        B, G = len(frames), self.GUARD
+        ins = (_UlmKeyframesIn * max(B, 1))(); outs = (_UlmKeyframesOut * max(B, 1))()
+        keep, res = [], []
+        for b, f in enumerate(frames):
+            mp = np.ascontiguousarray(f["mp_slot"], np.int32)
+            votes = np.full(f["kfs"].capacity + G, -7, np.int32); bad = np.full(len(mp) + G, 7, np.uint8)
+            keep.append(mp)
+            ins[b].kfs, ins[b].points, ins[b].n, ins[b].mp_slot = f["kfs"].h, f["points"].h, len(mp), mp.ctypes.data
+            outs[b].votes, outs[b].frame_bad = votes.ctypes.data, bad.ctypes.data
+            res.append(dict(votes=votes[:len(votes) - G], frame_bad=bad[:len(mp)], votes_guarded=votes, frame_bad_guarded=bad))
+        check(self.L.dvm_update_local_map_keyframes(self.h, B, C.addressof(ins), C.addressof(outs)))
+        return res
+
+    def points(self, frames, local_cap=None, raise_capacity=True):
+        """frames: dict(kfs, points, kf_slot=int32 [n_kfs], mp_slot=int32 [n]) per frame; local_cap: one value or one per frame (default:
+        the map store's capacity).  Returns per frame dict(local_slot [min(n_local, local_cap)], n_local, frame_mp [n], n_outside, and
+        the guarded arrays).  With raise_capacity=False a DVM_ERR_CAPACITY call returns its (complete) results with capacity=True."""
+        B, G = len(frames), self.GUARD
+        ins = (_UlmPointsIn * max(B, 1))(); outs = (_UlmPointsOut * max(B, 1))()
+        caps = _per_frame(local_cap, B) if local_cap is not None else [f["points"].capacity for f in frames]
+        keep, arrs = [], []
+        for b, f in enumerate(frames):
+            mp = np.ascontiguousarray(f["mp_slot"], np.int32); kf = np.ascontiguousarray(f["kf_slot"], np.int32)
+            loc = np.full(int(caps[b]) + G, -7, np.int32); fmp = np.full(len(mp) + G, -7, np.int32)
+            keep.append((mp, kf)); arrs.append((loc, fmp))
+            i, o = ins[b], outs[b]
+            i.kfs, i.points, i.n_kfs, i.kf_slot, i.n, i.mp_slot = f["kfs"].h, f["points"].h, len(kf), kf.ctypes.data, len(mp), mp.ctypes.data
+            o.local_slot, o.local_cap, o.n_local, o.frame_mp, o.n_outside = loc.ctypes.data, int(caps[b]), -7, fmp.ctypes.data, -7
+        rc = self.L.dvm_update_local_map_points(self.h, B, C.addressof(ins), C.addressof(outs))
+        if rc != -3 or raise_capacity or outs[0].n_local == -7:   # (-3: DVM_ERR_CAPACITY; n_local untouched: refused before it ran)
+            check(rc)
+        res = []
+        for b in range(B):
+            loc, fmp = arrs[b]
+            o = outs[b]
+            res.append(dict(local_slot=loc[:min(o.n_local, int(caps[b]))], n_local=o.n_local, frame_mp=fmp[:len(fmp) - G], n_outside=o.n_outside,
+                            local_guarded=loc, frame_mp_guarded=fmp, capacity=rc == -3))
+        return res
+
+    def last_bytes(self):
+        """(host to device, device to host) of the last call."""
+        up, down = C.c_int64(0), C.c_int64(0)
+        check(self.L.dvm_update_local_map_last_bytes(self.h, C.byref(up), C.byref(down)))
+        return up.value, down.value
+
+    def profile(self, enable=True):
+        check(self.L.dvm_update_local_map_profile(self.h, int(bool(enable))))
+
+    def last_ms(self):
+        ms = C.c_float(0)
+        check(self.L.dvm_update_local_map_last_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.L.dvm_update_local_map_destroy(self.h)
             self.h = C.c_void_p()
 
     __del__ = close

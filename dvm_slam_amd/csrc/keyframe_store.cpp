@@ -15,6 +15,9 @@
 //            -- and then ONE synchronisation, because the host record of a slot (n, fv_n, n_feat) and the BowVector / FeatureVector the
 //            caller gets come from mapped memory the kernels wrote.  A call the first kernel refuses changes no slot and no record.
 //   a chain  kfs_read_begin: its stream waits for `write_ev`; kfs_read_end: `read_ev` recorded behind its reading kernels.
+//   rows     (set_rows / patch_rows, below) two int32 rows per slot in blocks of their own, made by the first call that sets one: staged and
+//            queued exactly as a put -- the staging block, the store's stream behind `read_ev`, `write_ev` --, and unset by every put,
+//            put_device and remove of the slot (the slot's device length goes back to 0 on the store's stream).
 // Safety: per slot the host keeps a written flag, a generation and the counts the kernels index with; every slot a call names is checked
 // BEFORE anything is queued, and every count of a put is bounded by slot_keypoints, so no kernel runs on an unchecked value.
 #include <algorithm>
@@ -26,8 +29,10 @@
 
 #include "../../include/dvmslam_hip.h"
 #include "chain.h"
+#include "fuse_points_lists.h"
 #include "fv_once.h"
 #include "keyframe_store.h"
+#include "map_store.h"
 
 using namespace dvm;
 
@@ -63,6 +68,45 @@ struct dvm_keyframe_store {
   uint8_t *dv_hout = nullptr, *dv_dout = nullptr; size_t dv_out_stride = 0;
   hipEvent_t src_ev = nullptr;
   hipEvent_t tev[5] = {}; bool timing = false; float last_ms[4] = {0, 0, 0, 0};
+  // ---- the rows (DVM_KFS_ROW_MATCHES, DVM_KFS_ROW_OBSERVED), per kind: the device block and the per-slot lengths (allocated by the first
+  // call that sets a row of the kind), per slot whether its row is set and which map store its values name, and how many set rows name
+  // each map store (a handful of stores at most: one agent, one map)
+  struct RowMeta { uint8_t set = 0; const dvm_map_store* points = nullptr; };
+  int32_t* rows_d[2] = {nullptr, nullptr}; int32_t* rowlen_d[2] = {nullptr, nullptr};
+  size_t row_words = 0;
+  std::vector<RowMeta> rowmeta[2];
+  std::vector<std::pair<const dvm_map_store*, int>> row_stores[2];
+  std::vector<int32_t> edit_order; std::vector<KfsRowEdit> edit_keep;   // patch_rows: the call's edits collapsed to one per cell
+  void row_count(int which, const dvm_map_store* p, int d) {
+    for (auto& e : row_stores[which])
+      if (e.first == p) { e.second += d; return; }
+    row_stores[which].emplace_back(p, d);
+  }
+  // the host half of unsetting slot's rows; true: a device length has to go back to 0
+  bool rows_forget(int32_t sl) {
+    bool any = false;
+    for (int w = 0; w < 2; w++) {
+      if (!rows_d[w] || !rowmeta[w][sl].set) continue;
+      row_count(w, rowmeta[w][sl].points, -1);
+      rowmeta[w][sl] = RowMeta();
+      any = true;
+    }
+    return any;
+  }
+  // the device half, on the store's stream (the caller has made it wait for `read_ev` and records `write_ev` behind it): the lengths of
+  // slots[0 .. n) back to 0, one memset per run of consecutive slots
+  int rows_unset_device(const int32_t* slots, int n) {
+    for (int w = 0; w < 2; w++) {
+      if (!rowlen_d[w]) continue;
+      for (int k = 0; k < n;) {
+        int m = 1;
+        while (k + m < n && slots[k + m] == slots[k] + m) m++;
+        DVM_HIP(hipMemsetAsync(rowlen_d[w] + slots[k], 0, (size_t)m * 4, s));
+        k += m;
+      }
+    }
+    return DVM_OK;
+  }
   uint8_t* slot_base(int32_t sl) const { return d + (size_t)sl * L.stride; }
   // the staging block is the host's again: the last round's copy has read it
   int staging_free() {
@@ -105,6 +149,18 @@ bool kfs_slot_view(const dvm_keyframe_store* st, int32_t slot, KfSlotView* v) {
   return true;
 }
 uint32_t kfs_generation(const dvm_keyframe_store* st, int32_t slot) { return (uint32_t)slot < (uint32_t)st->capacity ? st->meta[slot].gen : 0u; }
+int kfs_capacity(const dvm_keyframe_store* st) { return st->capacity; }
+KfsRowsView kfs_rows_view(const dvm_keyframe_store* st, int which) { return KfsRowsView{st->rows_d[which], st->rowlen_d[which], st->row_words}; }
+bool kfs_row_info(const dvm_keyframe_store* st, int which, int32_t slot, int32_t* n, const dvm_map_store** points) {
+  if ((uint32_t)slot >= (uint32_t)st->capacity || !st->meta[slot].written || !st->rows_d[which] || !st->rowmeta[which][slot].set) return false;
+  *n = st->meta[slot].n; *points = st->rowmeta[which][slot].points;
+  return true;
+}
+bool kfs_rows_all_name(const dvm_keyframe_store* st, int which, const dvm_map_store* points) {
+  for (const auto& e : st->row_stores[which])
+    if (e.second > 0 && e.first != points) return false;
+  return true;
+}
 KfsBlockView kfs_block_view(const dvm_keyframe_store* st) { return KfsBlockView{st->d, st->L.stride, st->L.kps, st->L.desc, st->L.sf}; }
 int kfs_read_begin(const dvm_keyframe_store* cst, hipStream_t s) {
   dvm_keyframe_store* st = const_cast<dvm_keyframe_store*>(cst);
@@ -307,6 +363,15 @@ int kfs_put_device_run(const char* fn, dvm_keyframe_store* st, const dvm_vocab* 
     return fail(fn, DVM_ERR_CAPACITY, w + ": " + std::to_string(k < n ? host_at(out_host.res, k)->n : 0) + " keypoints beyond slot_keypoints " +
                                           std::to_string(K) + "; no slot of the call written");
   }
+  {                                                                // a new keyframe holds nothing until it is told: the slots' rows are unset
+    bool any = false;
+    for (int k = 0; k < n; k++) any |= st->rows_forget(slots[k]);
+    if (any) {
+      { const int rc = st->rows_unset_device(slots, n); if (rc != DVM_OK) return rc; }
+      DVM_HIP(hipEventRecord(st->write_ev, s));
+      st->write_pending = true;
+    }
+  }
   for (int k = 0; k < n; k++) {
     const dvm_kfs_device_keyframe& f = kfs[k];
     const KfsDevRes& R = *host_at(out_host.res, k);
@@ -343,6 +408,7 @@ int dvm_keyframe_store_create(int device, int capacity, int slot_keypoints, dvm_
   if (!st) return DVM_ERR_INVALID;
   st->device = device; st->capacity = capacity; st->K = slot_keypoints;
   st->L = kf_slot_layout((size_t)slot_keypoints);
+  st->row_words = pad<16>((size_t)slot_keypoints);
   const size_t C = (size_t)capacity, block = C * st->L.stride;
   st->item_bytes = pad<256>(C * sizeof(KfsPutItem));
   st->stage_bytes = st->item_bytes + (size_t)std::min(capacity, kStageKeyframes) * kf_stage_bytes_max((size_t)slot_keypoints);
@@ -382,6 +448,10 @@ void dvm_keyframe_store_destroy(dvm_keyframe_store* st) {
   if (st->dv_hup) (void)hipHostFree(st->dv_hup);
   if (st->dv_hout) (void)hipHostFree(st->dv_hout);
   if (st->src_ev) (void)hipEventDestroy(st->src_ev);
+  for (int w = 0; w < 2; w++) {
+    if (st->rows_d[w]) (void)hipFree(st->rows_d[w]);
+    if (st->rowlen_d[w]) (void)hipFree(st->rowlen_d[w]);
+  }
   for (hipEvent_t e : st->tev) if (e) (void)hipEventDestroy(e);
   delete st;
 }
@@ -440,6 +510,11 @@ int dvm_keyframe_store_put(dvm_keyframe_store* st, int n, const int32_t* slots, 
     st->last_h2d += (int64_t)c.used();
     launch_kfs_put(st->s, reinterpret_cast<const KfsPutItem*>(st->ds), m, st->L);
     { const int rc = hip_check(hipGetLastError(), "k_kfs_put"); if (rc != DVM_OK) return rc; }
+    {                                                              // a new keyframe holds nothing until it is told: the slots' rows are unset
+      bool any = false;
+      for (int k = done; k < done + m; k++) any |= st->rows_forget(slots[k]);
+      if (any) { const int rc = st->rows_unset_device(slots + done, m); if (rc != DVM_OK) return rc; }
+    }
     DVM_HIP(hipEventRecord(st->write_ev, st->s));
     st->write_pending = true;
     for (int k = done; k < done + m; k++) {
@@ -489,9 +564,21 @@ int dvm_keyframe_store_remove(dvm_keyframe_store* st, int n, const int32_t* slot
   for (int k = 0; k < n; k++)
     if ((uint32_t)slots[k] >= (uint32_t)st->capacity || !st->meta[slots[k]].written)
       return fail(fn, DVM_ERR_INVALID, "slot " + std::to_string(slots[k]) + " outside [0, capacity) or not written");
+  bool any = false;
   for (int k = 0; k < n; k++) {
     SlotMeta& M = st->meta[slots[k]];
     if (M.written) { M.written = 0; M.gen++; }
+    any |= st->rows_forget(slots[k]);
+  }
+  if (any) {                                                       // the slots' row lengths on the device, queued as a put
+    DVM_HIP(hipSetDevice(st->device));
+    if (st->read_pending) {
+      DVM_HIP(hipStreamWaitEvent(st->s, st->read_ev, 0));
+      st->read_pending = false;
+    }
+    { const int rc = st->rows_unset_device(slots, n); if (rc != DVM_OK) return rc; }
+    DVM_HIP(hipEventRecord(st->write_ev, st->s));
+    st->write_pending = true;
   }
   return DVM_OK;
 }
@@ -529,6 +616,189 @@ int dvm_keyframe_store_debug_read(dvm_keyframe_store* st, int slot, dvm_kfs_read
   give(out->sidx, L.sidx, ns * 4);
   give(out->sdesc, L.sdesc, ns * 32);
   give(out->cell_start, L.cell_start, kKfsCellStart * 4);
+  return DVM_OK;
+}
+
+}  // extern "C"
+
+// ---- the rows beside the keyframes
+namespace {
+const char* row_name(int which) { return which == DVM_KFS_ROW_MATCHES ? "MATCHES" : "OBSERVED"; }
+// what both row calls check of their arguments before they look at a slot
+int rows_args(const char* fn, const dvm_keyframe_store* st, int which, const dvm_map_store* points) {
+  if (which != DVM_KFS_ROW_MATCHES && which != DVM_KFS_ROW_OBSERVED) return fail(fn, DVM_ERR_INVALID, "which = " + std::to_string(which) + ": not DVM_KFS_ROW_MATCHES or DVM_KFS_ROW_OBSERVED");
+  if (!points) return fail(fn, DVM_ERR_INVALID, "missing map store");
+  if (store_device(points) != st->device) return fail(fn, DVM_ERR_INVALID, "the map store lives on another device");
+  return DVM_OK;
+}
+// the first row call of a kind makes the kind's block: every word -1, every length 0
+int rows_reserve(const char* fn, dvm_keyframe_store* st, int which) {
+  if (st->rows_d[which]) return DVM_OK;
+  const size_t C = (size_t)st->capacity, bytes = C * st->row_words * 4;
+  int32_t *r = nullptr, *l = nullptr;
+  if (hipMalloc(reinterpret_cast<void**>(&r), bytes) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&l), C * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    if (r) (void)hipFree(r);
+    return fail(fn, DVM_ERR_CAPACITY, std::string("the block of the ") + row_name(which) + " rows (" + std::to_string(bytes) + " bytes)");
+  }
+  if (hipMemsetAsync(r, 0xff, bytes, st->s) != hipSuccess || hipMemsetAsync(l, 0, C * 4, st->s) != hipSuccess || hipStreamSynchronize(st->s) != hipSuccess) {
+    (void)hipFree(r); (void)hipFree(l);
+    return fail(fn, DVM_ERR_HIP, "clearing the rows");
+  }
+  st->rows_d[which] = r; st->rowlen_d[which] = l;
+  st->rowmeta[which].assign(C, dvm_keyframe_store::RowMeta());
+  return DVM_OK;
+}
+// slot's row of the kind is set and names `points` from now on (host state)
+void row_mark_set(dvm_keyframe_store* st, int which, int32_t sl, const dvm_map_store* points) {
+  dvm_keyframe_store::RowMeta& R = st->rowmeta[which][sl];
+  if (R.set) st->row_count(which, R.points, -1);
+  R.set = 1; R.points = points;
+  st->row_count(which, points, +1);
+}
+}  // namespace
+
+extern "C" {
+
+int dvm_keyframe_store_set_rows(dvm_keyframe_store* st, int which, const dvm_map_store* points, int n, const int32_t* slots, const int32_t* const* rows) {
+  const char* fn = "dvm_keyframe_store_set_rows";
+  if (!st || n < 0 || (n && (!slots || !rows))) return fail(fn, DVM_ERR_INVALID, "missing argument");
+  { const int rc = rows_args(fn, st, which, points); if (rc != DVM_OK) return rc; }
+  if (n == 0) return DVM_OK;
+  // the whole batch is decided before anything is staged or queued
+  if (++st->call == 0) { std::fill(st->stamp.begin(), st->stamp.end(), 0u); st->call = 1; }
+  const FplStore ps{dvm_map_store_capacity(points), store_written(points)};
+  for (int k = 0; k < n; k++) {
+    const int32_t sl = slots[k];
+    const std::string w = "row " + std::to_string(k) + " (slot " + std::to_string(sl) + ")";
+    if ((uint32_t)sl >= (uint32_t)st->capacity || !st->meta[sl].written) return fail(fn, DVM_ERR_INVALID, w + ": slot outside [0, capacity), never put or removed");
+    if (st->stamp[sl] == st->call) return fail(fn, DVM_ERR_INVALID, w + ": slot named twice in one call");
+    st->stamp[sl] = st->call;
+    const int32_t len = st->meta[sl].n;
+    if (len > 0 && !rows[k]) return fail(fn, DVM_ERR_INVALID, w + ": NULL row where the slot holds " + std::to_string(len) + " keypoints");
+    int at = -1;
+    if (fpl_slots_check(ps, rows[k], len, nullptr, &at))
+      return fail(fn, DVM_ERR_INVALID, w + ": entry " + std::to_string(at) + " = " + std::to_string(rows[k][at]) + " is below -1, outside the map store or never written");
+  }
+  DVM_HIP(hipSetDevice(st->device));
+  { const int rc = rows_reserve(fn, st, which); if (rc != DVM_OK) return rc; }
+  KfsRowItem* items = reinterpret_cast<KfsRowItem*>(st->hs);
+  st->last_h2d = 0;
+  for (int done = 0; done < n;) {
+    { const int rc = st->staging_free(); if (rc != DVM_OK) return rc; }
+    Cursor<kKfsAlign> c{st->hs, st->ds, st->item_bytes};
+    int m = 0;
+    for (; done + m < n; m++) {
+      const int32_t len = st->meta[slots[done + m]].n;
+      if (c.used() + pad<kKfsAlign>((size_t)len * 4) > st->stage_bytes) break;   // (the first of a round always fits: a row is smaller than a keyframe)
+      items[m] = KfsRowItem{slots[done + m], len, (int32_t)c.used(), 0};
+      c.put(rows[done + m], (size_t)len * 4);
+    }
+    if (m == 0) return fail(fn, DVM_ERR_STATE, "a row exceeds the staging block");
+    if (st->read_pending) {                                        // behind the chain kernels that read the rows
+      DVM_HIP(hipStreamWaitEvent(st->s, st->read_ev, 0));
+      st->read_pending = false;
+    }
+    DVM_HIP(hipMemcpyAsync(st->ds, st->hs, c.used(), hipMemcpyHostToDevice, st->s));
+    st->last_h2d += (int64_t)c.used();
+    launch_kfs_rows_set(st->s, reinterpret_cast<const KfsRowItem*>(st->ds), m, st->ds, st->rows_d[which], st->rowlen_d[which], st->row_words);
+    { const int rc = hip_check(hipGetLastError(), "k_kfs_rows_set"); if (rc != DVM_OK) return rc; }
+    DVM_HIP(hipEventRecord(st->write_ev, st->s));
+    st->write_pending = true;
+    for (int k = done; k < done + m; k++) row_mark_set(st, which, slots[k], points);
+    done += m;
+  }
+  return DVM_OK;
+}
+
+int dvm_keyframe_store_patch_rows(dvm_keyframe_store* st, int which, const dvm_map_store* points, int n_edits, const dvm_kfs_row_edit* edits) {
+  static_assert(sizeof(dvm_kfs_row_edit) == sizeof(KfsRowEdit) && sizeof(KfsRowEdit) == 12, "layout");
+  const char* fn = "dvm_keyframe_store_patch_rows";
+  if (!st || n_edits < 0 || (n_edits && !edits)) return fail(fn, DVM_ERR_INVALID, "missing argument");
+  { const int rc = rows_args(fn, st, which, points); if (rc != DVM_OK) return rc; }
+  if (n_edits == 0) return DVM_OK;
+  const int32_t pcap = dvm_map_store_capacity(points);
+  const uint8_t* pw = store_written(points);
+  const bool have = st->rows_d[which] != nullptr;
+  for (int i = 0; i < n_edits; i++) {
+    const dvm_kfs_row_edit& e = edits[i];
+    const std::string w = "edit " + std::to_string(i) + " (slot " + std::to_string(e.slot) + ", kp " + std::to_string(e.kp) + ")";
+    if ((uint32_t)e.slot >= (uint32_t)st->capacity || !st->meta[e.slot].written) return fail(fn, DVM_ERR_INVALID, w + ": slot outside [0, capacity), never put or removed");
+    if ((uint32_t)e.kp >= (uint32_t)st->meta[e.slot].n) return fail(fn, DVM_ERR_INVALID, w + ": kp outside [0, " + std::to_string(st->meta[e.slot].n) + ")");
+    if (e.value != -1 && ((uint32_t)e.value >= (uint32_t)pcap || !pw[e.value]))
+      return fail(fn, DVM_ERR_INVALID, w + ": value " + std::to_string(e.value) + " is below -1, outside the map store or never written");
+    if (have && st->rowmeta[which][e.slot].set && st->rowmeta[which][e.slot].points != points)
+      return fail(fn, DVM_ERR_INVALID, w + ": the slot's row names another map store");
+  }
+  // the last edit of a cell wins: one edit per cell is queued, so no two threads write one word
+  std::vector<int32_t>& ord = st->edit_order;
+  ord.resize((size_t)n_edits);
+  for (int i = 0; i < n_edits; i++) ord[i] = i;
+  std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) {
+    return edits[a].slot != edits[b].slot ? edits[a].slot < edits[b].slot : edits[a].kp < edits[b].kp;
+  });
+  std::vector<KfsRowEdit>& keep = st->edit_keep;
+  keep.clear();
+  for (int i = 0; i < n_edits; i++) {
+    const dvm_kfs_row_edit& e = edits[ord[i]];
+    if (i + 1 < n_edits && edits[ord[i + 1]].slot == e.slot && edits[ord[i + 1]].kp == e.kp) continue;
+    keep.push_back(KfsRowEdit{e.slot, e.kp, e.value});
+  }
+  DVM_HIP(hipSetDevice(st->device));
+  { const int rc = rows_reserve(fn, st, which); if (rc != DVM_OK) return rc; }
+  { const int rc = st->staging_free(); if (rc != DVM_OK) return rc; }
+  // a row not yet set opens as n entries of -1 (a new keyframe holds nothing): its items lead the first round
+  KfsRowItem* items = reinterpret_cast<KfsRowItem*>(st->hs);
+  int n_open = 0;
+  for (size_t i = 0; i < keep.size(); i++) {
+    const int32_t sl = keep[i].slot;
+    if (st->rowmeta[which][sl].set || (i > 0 && keep[i - 1].slot == sl)) continue;   // (keep is sorted by slot)
+    items[n_open++] = KfsRowItem{sl, st->meta[sl].n, -1, 0};
+  }
+  const size_t per_round = (st->stage_bytes - st->item_bytes) / sizeof(KfsRowEdit);
+  st->last_h2d = 0;
+  for (size_t done = 0; done < keep.size();) {
+    if (done) { const int rc = st->staging_free(); if (rc != DVM_OK) return rc; }
+    const size_t m = std::min(per_round, keep.size() - done), bytes = m * sizeof(KfsRowEdit);
+    std::memcpy(st->hs + st->item_bytes, keep.data() + done, bytes);
+    if (st->read_pending) {                                        // behind the chain kernels that read the rows
+      DVM_HIP(hipStreamWaitEvent(st->s, st->read_ev, 0));
+      st->read_pending = false;
+    }
+    const bool open = done == 0 && n_open > 0;
+    const size_t from = open ? 0 : st->item_bytes;                 // (the items travel only when a row opens)
+    DVM_HIP(hipMemcpyAsync(st->ds + from, st->hs + from, st->item_bytes - from + bytes, hipMemcpyHostToDevice, st->s));
+    st->last_h2d += (int64_t)(st->item_bytes - from + bytes);
+    if (open) launch_kfs_rows_set(st->s, reinterpret_cast<const KfsRowItem*>(st->ds), n_open, st->ds, st->rows_d[which], st->rowlen_d[which], st->row_words);
+    launch_kfs_rows_patch(st->s, reinterpret_cast<const KfsRowEdit*>(st->ds + st->item_bytes), (int)m, st->rows_d[which], st->row_words);
+    { const int rc = hip_check(hipGetLastError(), "k_kfs_rows_patch"); if (rc != DVM_OK) return rc; }
+    DVM_HIP(hipEventRecord(st->write_ev, st->s));
+    st->write_pending = true;
+    if (open)
+      for (int k = 0; k < n_open; k++) row_mark_set(st, which, items[k].slot, points);
+    done += m;
+  }
+  return DVM_OK;
+}
+
+int dvm_keyframe_store_debug_read_rows(dvm_keyframe_store* st, int which, int slot, int32_t* out, int cap, int32_t* n_out) {
+  const char* fn = "dvm_keyframe_store_debug_read_rows";
+  if (!st || !n_out || cap < 0 || (cap && !out)) return fail(fn, DVM_ERR_INVALID, "missing argument");
+  if (which != DVM_KFS_ROW_MATCHES && which != DVM_KFS_ROW_OBSERVED) return fail(fn, DVM_ERR_INVALID, "which = " + std::to_string(which));
+  if ((uint32_t)slot >= (uint32_t)st->capacity || !st->meta[slot].written)
+    return fail(fn, DVM_ERR_INVALID, "slot " + std::to_string(slot) + " outside [0, capacity) or not written");
+  *n_out = 0;
+  if (!st->rows_d[which]) return DVM_OK;                           // no row of the kind was ever set
+  DVM_HIP(hipSetDevice(st->device));
+  DVM_HIP(hipStreamSynchronize(st->s));
+  st->write_pending = false;
+  int32_t len = 0;
+  DVM_HIP(hipMemcpy(&len, st->rowlen_d[which] + slot, 4, hipMemcpyDeviceToHost));
+  const int32_t want = st->rowmeta[which][slot].set ? st->meta[slot].n : 0;
+  if (len != want) return fail(fn, DVM_ERR_STATE, "the slot's device row length " + std::to_string(len) + " is not the host's " + std::to_string(want));
+  *n_out = len;
+  if (len > cap) return fail(fn, DVM_ERR_CAPACITY, "the row holds " + std::to_string(len) + " entries, the buffer " + std::to_string(cap));
+  if (len > 0) DVM_HIP(hipMemcpy(out, st->rows_d[which] + (size_t)slot * st->row_words, (size_t)len * 4, hipMemcpyDeviceToHost));
   return DVM_OK;
 }
 

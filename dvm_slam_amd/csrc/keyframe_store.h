@@ -38,6 +38,28 @@ KfsBlockView kfs_block_view(const dvm_keyframe_store* st);
 int kfs_read_begin(const dvm_keyframe_store* st, hipStream_t s);
 int kfs_read_end(const dvm_keyframe_store* st, hipStream_t s);
 
+// ---- the rows beside the keyframes (dvm_keyframe_store_set_rows / _patch_rows; keyframe_rows_kernels.hip): per kind one device block of
+// [capacity] rows of row_words int32 each (slot_keypoints rounded up to 16: a row starts on 64 bytes) and one length per slot -- the
+// slot's n while the row is set, 0 otherwise -- which a kernel that walks the whole store reads instead of a host-made list.
+// rows == nullptr: no row of the kind was ever set (every length counts as 0).
+struct KfsRowsView { const int32_t* rows; const int32_t* len; size_t row_words; };
+KfsRowsView kfs_rows_view(const dvm_keyframe_store* st, int which);
+// slot's row of the kind as the host knows it: false for a slot outside the store, never put, removed, or whose row is not set;
+// *n: its length, *points: the map store its values were checked against
+bool kfs_row_info(const dvm_keyframe_store* st, int which, int32_t slot, int32_t* n, const dvm_map_store** points);
+// every row of the kind that is set names `points` (true for none set): what lets a kernel walk ALL rows against one map store's tables
+bool kfs_rows_all_name(const dvm_keyframe_store* st, int which, const dvm_map_store* points);
+int kfs_capacity(const dvm_keyframe_store* st);
+
+// one row of a set round: staged at src_off bytes of the staging block's device twin (src_off < 0: no staged row -- the row becomes n
+// entries of -1, what patch_rows does to a row not yet set)
+struct KfsRowItem { int32_t slot, n, src_off, pad; };
+struct KfsRowEdit { int32_t slot, kp, value; };   // == dvm_kfs_row_edit
+// one 256-thread workgroup per item: the staged row into rows + slot * row_words, len[slot] = n
+void launch_kfs_rows_set(hipStream_t s, const KfsRowItem* items, int n_items, const uint8_t* stage, int32_t* rows, int32_t* len, size_t row_words);
+// one thread per edit (the host left one edit per cell): rows[slot * row_words + kp] = value
+void launch_kfs_rows_patch(hipStream_t s, const KfsRowEdit* edits, int n_edits, int32_t* rows, size_t row_words);
+
 // one keyframe of a put round: its staged arrays (the device copy of the staging block: kps, desc, fv_node, fv_off, fv_feat, sf, sigma2,
 // inv_sigma2 back to back, each rounded up to 64 bytes) and its slot
 struct KfsPutItem {

@@ -1163,7 +1163,8 @@ int dvm_map_store_last_refresh_ms(const dvm_map_store* ms, float* kernel_ms);
  *             with ONE copy and moved by ONE launch -- k_kfs_put, one 1 024-thread workgroup per keyframe, which also builds the grid
  *             in the slot with the function dvm_frame_build and dvm_fuse_targets_set run, so a resident grid has the order a per-call
  *             set produces.  On the STORE'S OWN STREAM; put does not wait.  A batch larger than the staging block goes in rounds.
- *   remove    the slots are empty again (host state only).  A slot outside [0, capacity) or not written: DVM_ERR_INVALID, nothing changed.
+ *   remove    the slots are empty again (host state; with rows set -- below -- also the slots' row lengths, queued as a put).  A slot
+ *             outside [0, capacity) or not written: DVM_ERR_INVALID, nothing changed.
  *   Ordering is dvm_map_store's: every chain call that reads the store makes its stream wait for the store's last put, and a put
  *   waits for the last kernel queued to read the store -- it never overtakes a reader in flight.
  *   Every slot carries a written flag and a generation counter (put and remove bump it).  A chain call that names a slot never
@@ -1698,6 +1699,124 @@ int dvm_ba_resident_optimize(dvm_ba_resident* h, const dvm_ba_window_resident* w
                              int K, const volatile uint8_t* stop_flag, dvm_ba_stats* stats);
 int dvm_ba_resident_commit(dvm_ba_resident* h, int k /* window of the last optimize; -1: every window not yet committed */);
 int dvm_ba_resident_last_bytes(const dvm_ba_resident* h, int64_t* host_to_device, int64_t* device_to_host);
+
+/* ---- Rows beside the keyframes: which map point does keypoint kp of the keyframe in slot j hold.  Two int32 rows per keyframe-store
+ * slot, each as long as the slot's n, their values slots of a dvm_map_store:
+ *   DVM_KFS_ROW_MATCHES   GetMapPointMatches() as map-store slots, -1 for a NULL pointer (UpdateLocalPoints reads it).
+ *   DVM_KFS_ROW_OBSERVED  entry kp = the slot of the map point whose mObservations holds (this keyframe, kp), -1 otherwise: the inverse
+ *                         of GetObservations() (the votes of UpdateLocalKeyFrames read it).
+ * The two differ in the reference: a keyframe Tracking::CreateNewKeyFrame has queued has its mvpMapPoints set, and its points get their
+ * AddObservation only in LocalMapping::ProcessNewKeyFrame.  Until then it is walked by UpdateLocalPoints and receives no votes.
+ * The rows live in an allocation of their own -- capacity x (slot_keypoints rounded up to 16) x 4 B per kind, plus 4 B per slot for the
+ * row's length on the device -- made by the first call that sets a row of that kind: a store on which no row call is made behaves and
+ * allocates as before, and the slot layout (csrc/kf_store_layout.h) and every view of a slot are untouched.
+ *   set_rows    rows[k] (the slot's n entries) becomes slot slots[k]'s row of kind `which`.
+ *   patch_rows  edits[i] = {slot, kp, value}: the mirror of AddObservation / EraseObservation (OBSERVED) and AddMapPoint /
+ *               EraseMapPointMatch / ReplaceMapPointMatch (MATCHES); MapPoint::Replace is both.  The edits of one call apply in order: the
+ *               last edit of a cell wins (the host collapses duplicates before anything is queued; no two threads write one cell).  A
+ *               slot whose row is not set opens as n entries of -1 first.
+ *   points      the map store the values name.  Every value is checked on the host at set or patch time: -1 or a written slot of
+ *               `points`.  The store remembers per slot and kind which map store its row names; a map store's capacity is fixed and a
+ *               written slot stays written, so a row checked once stays valid: no kernel indexes a store with a value the host has not
+ *               checked, and no per-tick call re-checks a row.  `points` outlives the rows that name it.
+ *   ordering    that of dvm_keyframe_store_put: page-locked staging, ONE copy and a scatter kernel (k_kfs_rows_set / k_kfs_rows_patch) per
+ *               round on the STORE'S OWN STREAM; the call may return before the kernel has run, every later reader waits for it, and it
+ *               never overtakes a reader in flight.
+ *   unset       put, put_device, put_tracked and remove of a slot unset both of its rows (host state, and the slot's device length goes
+ *               back to 0 on the store's stream): a new keyframe holds nothing until it is told.  The device keeps each slot's row
+ *               length per kind -- 0 for a slot never set, unset or removed --, so a kernel walks a store without a host-made list.
+ *   refusals    DVM_ERR_INVALID before anything is queued, each naming the offender, nothing written: a slot outside the store, never
+ *               put or removed; a NULL row where the slot holds keypoints; kp outside [0, n); a value below -1, outside `points` or
+ *               never written; a `points` on another device; a slot named twice in one set_rows; `which` unknown; a patch of a row that
+ *               names another map store.
+ *   debug_read_rows  one row back, synchronous (tests): *n_out = the row's length (0 for a row not set), out [cap] its entries;
+ *               DVM_ERR_CAPACITY with *n_out set when cap is too small.
+ *   dvm_keyframe_store_last_put_bytes also reports the row calls.
+ * sizeof(dvm_kfs_row_edit) == 12. */
+#define DVM_KFS_ROW_MATCHES  0
+#define DVM_KFS_ROW_OBSERVED 1
+typedef struct { int32_t slot, kp, value; } dvm_kfs_row_edit;      /* 12 B */
+int dvm_keyframe_store_set_rows(dvm_keyframe_store* s, int which, const dvm_map_store* points, int n, const int32_t* slots,
+                                const int32_t* const* rows);
+int dvm_keyframe_store_patch_rows(dvm_keyframe_store* s, int which, const dvm_map_store* points, int n_edits, const dvm_kfs_row_edit* edits);
+int dvm_keyframe_store_debug_read_rows(dvm_keyframe_store* s, int which, int slot, int32_t* out, int cap, int32_t* n_out);
+
+/* ---- Tracking::UpdateLocalMap() on the resident stores (csrc/update_local_map.cpp): the two graph walks between the halves of a tracked
+ * frame (reference src/Tracking.cc:3108-3274) as list intersections over the rows above.  Both calls serve the `count` frames of one tick;
+ * each frame names its own keyframe store and map store (one agent each; frames may share stores).  Each call is ONE upload, ONE chain of
+ * batched launches on the handle's stream and ONE synchronisation; the results come down through a mapped page-locked block.  A call is a
+ * READER of every store it names: it sees every dvm_map_store_update / _refresh, dvm_ba_resident_commit, put and row edit queued before
+ * it with no host synchronisation between, and none of those overtakes it.  What stays host work is :3207-3251: one neighbour, one child
+ * and one parent per local keyframe and the choice of pKFmax -- index work on the votes.
+ *   reserve     grow-only: `max_frames` frames of up to `max_frame_keypoints` keypoints and `max_local_keyframes` named keyframes, on map
+ *               stores of up to `map_capacity` slots and keyframe stores of up to `kf_capacity` slots of `slot_keypoints`.  The handle
+ *               holds three tables of map_capacity words per frame (mult, first, pos).  They are idle between calls: every call puts
+ *               back the entries it touched; there is no capacity-sized memset per call.
+ *   keyframes   the vote loop of UpdateLocalKeyFrames (:3145-3181).  in[b].mp_slot [n]: the frame's mvpMapPoints as map-store slots, -1
+ *               for none (mCurrentFrame's list, or mLastFrame's in the branch of :3162; the caller chooses).
+ *               out[b].votes [capacity of in[b].kfs]: votes[j] = sum over kp of mult[OBSERVED[j][kp]], mult[s] = the number of the
+ *               frame's keypoints that hold the non-bad point s -- a point held twice votes twice, as the reference's loop does; 0 for a
+ *               slot without an OBSERVED row.  out[b].frame_bad [n]: 1 where keypoint i names a record with bad != 0 -- the entries the
+ *               reference sets to NULL at :3157 / :3177; they do not vote.
+ *               Kernels: k_ulm_mult (integer atomicAdd per frame entry), k_ulm_votes (one wavefront per (frame, keyframe slot): 16-byte
+ *               row loads, mult gathered, a wave reduction, one word written), k_ulm_mult_reset.
+ *               Upload: 64 * count + sum over frames of 4 * ceil16(n_b) bytes (ceil16: rounded up to a multiple of 16 entries, 64 B).
+ *   points      UpdateLocalPoints (:3117-3141) plus the frame_mp of dvm_local_map_in_resident.  in[b].kf_slot [n_kfs]: mvpLocalKeyFrames
+ *               in the order the loop visits them (the vector reversed); in[b].mp_slot [n]: the frame's list after the clearing above.
+ *               The entries are the named slots' MATCHES rows numbered flat in (keyframe, keypoint) order; an entry is taken iff its
+ *               value is >= 0, its record is not bad and no earlier entry names the same slot.  out[b].local_slot [local_cap]: the taken
+ *               entries in flat order -- mvpLocalMapPoints as slots, in the reference's order; n_local their count.  out[b].frame_mp [n]:
+ *               the position in local_slot of the point keypoint i holds; -1 where it holds none, the point is bad, or the point is in
+ *               no named row -- n_outside counts the last case (the second half's precondition is that it is 0; the caller decides).
+ *               n_local > local_cap: DVM_ERR_CAPACITY, n_local holds the full count, nothing is written past local_slot[local_cap) and
+ *               frame_mp and n_outside are complete for every frame of the call.
+ *               Kernels: k_ulm_mark (integer atomicMin of the key k * padded row length + kp), k_ulm_count / k_ulm_scan / k_ulm_write
+ *               (stable compaction; the write records pos[slot]), k_ulm_frame_mp, k_ulm_points_reset.
+ *               Upload: 64 * count + sum over frames of 4 * (ceil16(n_b) + ceil16(n_kfs_b)) bytes.  No row travels.
+ *   refusals    on the host before anything is queued, each naming frame and entry; the handle stays usable and its tables idle.
+ *               DVM_ERR_INVALID: a NULL argument with a non-zero count; a store on another device; a frame slot below -1, outside its
+ *               map store or never written; a kf_slot outside the store, never put, removed or without a MATCHES row; a kf_slot named
+ *               twice in one frame; a named row -- for the votes: any OBSERVED row of the store -- that names another map store than
+ *               in[b].points.  DVM_ERR_CAPACITY: anything beyond the reservation.  Legal: count = 0, n = 0, n_kfs = 0, a row of length
+ *               0, every entry -1, every point bad.
+ *   failures    a HIP error behind a call's first launch (DVM_ERR_HIP): the outputs are not valid, the stores' read brackets are closed
+ *               (a later writer waits for whatever the handle's stream still holds), and the next call on the handle writes the three
+ *               tables idle again before it runs -- a failed call never leaves entries that a later call would count.
+ *   last_bytes  the last call's one upload, and what was copied out of the mapped block.
+ *   profile / last_ms  with profiling on, the kernels' time of the last call by HIP events (measurement only).
+ * local_slot and frame_mp are what dvm_local_map_in_resident::slots and frame_mp take.  Calls on one handle are not concurrent.
+ * sizeof(dvm_ulm_keyframes_in) == 32 (kfs 0, points 8, n 16, mp_slot 24); sizeof(dvm_ulm_keyframes_out) == 16 (votes 0, frame_bad 8);
+ * sizeof(dvm_ulm_points_in) == 48 (kfs 0, points 8, n_kfs 16, kf_slot 24, n 32, mp_slot 40); sizeof(dvm_ulm_points_out) == 32
+ * (local_slot 0, local_cap 8, n_local 12, frame_mp 16, n_outside 24) (LP64). */
+typedef struct {
+  const dvm_keyframe_store* kfs; const dvm_map_store* points;
+  int32_t n; const int32_t* mp_slot;               /* [n] the frame's mvpMapPoints as slots of `points`, -1: none */
+} dvm_ulm_keyframes_in;
+typedef struct {
+  int32_t* votes;                                  /* [dvm_keyframe_store_capacity(kfs)] */
+  uint8_t* frame_bad;                              /* [n] */
+} dvm_ulm_keyframes_out;
+typedef struct {
+  const dvm_keyframe_store* kfs; const dvm_map_store* points;
+  int32_t n_kfs; const int32_t* kf_slot;           /* [n_kfs] mvpLocalKeyFrames as keyframe-store slots, in the loop's order */
+  int32_t n; const int32_t* mp_slot;               /* [n] the frame's list, bad entries cleared or not (they count as none) */
+} dvm_ulm_points_in;
+typedef struct {
+  int32_t* local_slot; int32_t local_cap;          /* [local_cap] */
+  int32_t n_local;                                 /* written: the full count */
+  int32_t* frame_mp;                               /* [n] */
+  int32_t n_outside;                               /* written */
+} dvm_ulm_points_out;
+typedef struct dvm_update_local_map dvm_update_local_map;
+int dvm_update_local_map_create(int device, dvm_update_local_map** out);
+void dvm_update_local_map_destroy(dvm_update_local_map* h);
+int dvm_update_local_map_reserve(dvm_update_local_map* h, int max_frames, int max_frame_keypoints, int max_local_keyframes, int map_capacity,
+                                 int kf_capacity, int slot_keypoints);
+int dvm_update_local_map_keyframes(dvm_update_local_map* h, int count, const dvm_ulm_keyframes_in* in, const dvm_ulm_keyframes_out* out);
+int dvm_update_local_map_points(dvm_update_local_map* h, int count, const dvm_ulm_points_in* in, dvm_ulm_points_out* out);
+int dvm_update_local_map_last_bytes(const dvm_update_local_map* h, int64_t* host_to_device, int64_t* device_to_host);
+int dvm_update_local_map_profile(dvm_update_local_map* h, int enable);
+int dvm_update_local_map_last_ms(const dvm_update_local_map* h, float* kernel_ms);
 
 #ifdef __cplusplus
 }
