@@ -2204,6 +2204,69 @@ def pose_graph_debug_trial(S, fixed, edges_v, edges_meas, fix_scale=False, lam=1
                 failed=int(st.failed), levels=int(st.levels), nfree=m)
 
 
+TILE_FORM_FLOW, TILE_FORM_NO_PAIR, TILE_FORM_NO_DIAG_IN_LEVEL, TILE_FORM_NO_ROOT_RAW, TILE_FORM_PER_PHASE = 1, 2, 4, 8, 16
+TILE_PATHS = ("none", "level_one_launch", "slices_diag_update", "diag_fused", "diag_trsm_update", "raw_root")   # DVM_TILE_PATH_*
+TILE_FLOW_REFUSED = 7     # the bits of flow_refusal that forbid the flow form (bit 8: the level launches are merely preferred)
+
+
+class TileSolveInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("n_tiles", "levels", "pair_a", "pair_b", "n_root_raw", "flow_leaves", "roots", "flow_tasks", "flow_refusal",
+                                         "traced_levels", "used_pair", "used_flow", "backsolve_cols", "reserved")] + \
+               [(k, C.c_int32 * 64) for k in ("level_nc", "level_ns", "level_nt", "level_path")]
+
+
+def _tile_info(st):
+    d = {k: int(getattr(st, k)) for k, t in TileSolveInfo._fields_ if t is C.c_int32 and k != "reserved"}
+    nl = min(d["levels"], 64)
+    for k in ("level_nc", "level_ns", "level_nt"):
+        d[k] = [int(v) for v in getattr(st, k)[:nl]]
+    d["level_path"] = [TILE_PATHS[v] for v in st.level_path[:d["traced_levels"]]]
+    return d
+
+
+def tile_schedule_debug(mask, workgroups=256):
+    """dvm_tile_schedule_debug (host only): the schedule of a tile mask [t, t] over the tiles of unknowns, as a dict (see dvm_tile_solve_info)."""
+    L = lib()
+    L.dvm_tile_schedule_debug.restype = C.c_int32
+    L.dvm_tile_schedule_debug.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(TileSolveInfo)]
+    m = np.ascontiguousarray(mask, np.uint8)
+    assert m.ndim == 2 and m.shape[0] == m.shape[1]
+    st = TileSolveInfo()
+    check(L.dvm_tile_schedule_debug(len(m), _p(m), int(workgroups), C.byref(st)))
+    return _tile_info(st)
+
+
+def tile_solve_debug(A, b, n_blocks, dof=6, per_tile=10, kept_list=(), n_landmarks=0, mask=None, x_in=None, form=0, repeats=1, A2=None, b2=None,
+                     device=0):
+    """dvm_tile_solve_debug: A x = b through the tile Cholesky in the form `form` (TILE_FORM_* bits).  A[n, n] (lower triangle read), n =
+    dof * n_blocks + 3 * len(kept_list).  Returns (x[repeats, dof * n_blocks + 3 * n_landmarks], fail[repeats], info dict); with A2 / b2 the
+    solves of that system in between the repeats come back as info["x2"], info["fail2"]."""
+    L = lib()
+    vp, i32 = C.c_void_p, C.c_int32
+    L.dvm_tile_solve_debug.restype = i32
+    L.dvm_tile_solve_debug.argtypes = [i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(TileSolveInfo)]
+    kept = np.ascontiguousarray(kept_list, np.int32)
+    n, xl = dof * n_blocks + 3 * len(kept), dof * n_blocks + 3 * n_landmarks
+    A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64)
+    assert A.shape == (n, n) and b.shape == (n,)
+    if A2 is not None:
+        A2 = np.ascontiguousarray(A2, np.float64); b2 = np.ascontiguousarray(b2, np.float64)
+        assert A2.shape == (n, n) and b2.shape == (n,)
+    xi = np.zeros(xl) if x_in is None else np.ascontiguousarray(x_in, np.float64)
+    assert xi.shape == (xl,)
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+    x = np.zeros((repeats, xl)); fail = np.zeros(repeats, np.int32)
+    st = TileSolveInfo()
+    x2 = np.zeros((max(repeats - 1, 0), xl)); fail2 = np.zeros(max(repeats - 1, 1), np.int32)[:max(repeats - 1, 0)]
+    check(L.dvm_tile_solve_debug(device, n_blocks, dof, per_tile, len(kept), _p(kept if len(kept) else None), n_landmarks, _p(A), _p(b), _p(m), _p(xi),
+                                 int(form), int(repeats), _p(A2), _p(b2), _p(x), _p(fail), _p(x2 if A2 is not None else None),
+                                 _p(fail2 if A2 is not None else None), C.byref(st)))
+    info = _tile_info(st)
+    if A2 is not None:
+        info["x2"], info["fail2"] = x2, fail2
+    return x, fail, info
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # SURVEY.md 8(a) M4-M7: the remaining whole ORBmatcher functions (host mirrors in dvm_slam_amd/host/orb_matcher.cpp over
 # dvm_hamming_matrix / dvm_match_lists / dvm_project_search / dvm_match_triangulation).  The view structs of

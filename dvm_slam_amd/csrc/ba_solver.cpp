@@ -18,6 +18,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -187,6 +188,80 @@ struct dvm_ba {
   }
 };
 
+// the default choice between the level launches and the flow form of the reduced solve (k_chol_flow); DVM_BA_FLOW overrides it
+// Measured (DESIGN.md section 10): the flow form costs ~15.5 us per level of a chain (the factorisation's own 7.7 us + the parent strip and
+// its product in the same workgroup) and ~18 us per level with two children; the level launches ~17 us per level when a level is a handful of
+// tiles and ~20 us when its trailing update is large, and they own the small problems (the top-pair kernel solves a local-BA window's whole
+// reduced system in one workgroup).  From 5 levels on the flow form wins -- 100 keyframes 6 927 -> 7 114 it/s, 200: 5 536 -> 5 739, the
+// 500-keyframe ring 4 036 -> 4 092, the same map with loop closures (13 levels after the kept landmarks) 2 404 -> 2 509 -- as long as its
+// tasks are a few per workgroup: a task holds its workgroup while it waits, and at 1 000 keyframes with loop closures (1 848 tasks on 256
+// workgroups) the level launches are ahead again (1 401 vs 1 313 it/s).
+static bool kFlowDefault(const BaTileSchedule& SC, int workgroups) { return SC.nlevels >= 5 && (int)(SC.flow_tasks.size() / 8) <= 4 * workgroups; }
+namespace dvm {
+// The admission test of the flow form (tile_system.h): 0 = the solve takes it.
+int32_t tile_flow_refusal(const BaTileSchedule& SC, int32_t ldS, int workgroups) {
+  int32_t why = 0;
+  if (!((size_t)ldS * ldS * sizeof(double) < (size_t)0x7FFFFFF0)) why |= kFlowTooLarge;      // 32-bit buffer offsets into S
+  // several roots (a disconnected reduced camera graph): one tree's back substitution could write x before a diagonal tile of another
+  // tree fails, and g2o's linear solver leaves x untouched when the factorisation fails -- such graphs keep the level launches
+  int roots = 0;
+  for (size_t k = 0; k + 1 < SC.flow_col.size() / 8; k++) roots += SC.flow_col[8 * k] < 0;
+  if (roots > 1) why |= kFlowSeveralRoots;
+  // (the chains -- one per leaf of the elimination tree -- wait for tasks the OTHER workgroups draw: they must stay a minority)
+  if (4 * SC.flow_leaves > workgroups) why |= kFlowTooManyLeaves;
+  if (!kFlowDefault(SC, workgroups)) why |= kFlowNotPreferred;
+  return why;
+}
+int tile_system_fill(TileArena& A, int device, TileSystem& T, const BaTileSchedule& SC, int nfree, int per_tile, int dof, int ncamt,
+                     const int32_t* kept_list, int nkept, size_t x_len, int32_t* flow_refusal) {
+  const int nkb = SC.ntiles;    // camera tiles + kept-landmark tiles + the tile of the augmented rhs row
+  T.nfree = nfree; T.ncamt = ncamt; T.nkept = nkept;
+  T.n_pad = 64 * (nkb - 1);
+  T.per_tile = per_tile; T.dof = dof;
+  T.ldS = 64 * nkb;
+  T.nlevels = SC.nlevels;
+  T.pair_ok = SC.pair_a >= 0; T.pair_a = SC.pair_a; T.pair_b = SC.pair_b;
+  T.diag_in_level = 1;
+  T.n_root_raw = SC.n_root_raw;   // (ba_ordering.h: the last launched level's panel solve left to the back substitution)
+  int rc = DVM_OK;
+  auto ok = [&](int r) { if (rc == DVM_OK) rc = r; };
+  auto dalloc = [&](auto** p, size_t n) { void* q = nullptr; const int r = A.alloc(&q, n * sizeof(**p)); *p = static_cast<std::remove_reference_t<decltype(*p)>>(q); return r; };
+  auto upload = [&](const int32_t** p, const int32_t* v, size_t n) { const void* q = nullptr; const int r = A.upload(&q, v, n * sizeof(int32_t)); *p = static_cast<const int32_t*>(q); return r; };
+  auto up = [&](const int32_t** p, const std::vector<int32_t>& v) { return upload(p, v.data(), v.size()); };
+  const size_t nstrips = SC.strips.size() / 2;
+  ok(dalloc(&T.S, (size_t)T.ldS * T.ldS)); ok(dalloc(&T.Linv, (size_t)(T.ldS / 64) * 64 * 64)); ok(dalloc(&T.ytmp, (size_t)T.n_pad + 64 + 2 * nstrips + 2));
+  ok(dalloc(&T.xrow, (size_t)T.n_pad + 64));
+  ok(dalloc(&T.x, x_len));
+  ok(up(&T.nz_tiles, SC.nz_tiles)); T.n_nz = (int)(SC.nz_tiles.size() / 2);
+  ok(up(&T.cols, SC.cols)); ok(up(&T.strips, SC.strips)); ok(up(&T.targets, SC.targets));
+  ok(up(&T.contrib, SC.contrib)); ok(up(&T.colstrip_off, SC.colstrip_off)); ok(up(&T.colstrips, SC.colstrips));
+  ok(up(&T.contrib_strip, SC.contrib_strip));
+  if (T.nkept) ok(upload(&T.kept_list, kept_list, (size_t)nkept));
+  // the flow form of the solve (k_chol_flow): task list, per-tile level ranges, flags (zeroed once: they are compared with the solve's sequence number)
+  ok(up(&T.flow_tasks, SC.flow_tasks)); ok(up(&T.flow_contrib, SC.flow_contrib)); ok(up(&T.flow_col, SC.flow_col)); ok(up(&T.colstrip_id, SC.colstrip_id));
+  T.n_flow_tasks = (int)(SC.flow_tasks.size() / 8); T.n_strips_total = (int)nstrips; T.n_tiles_total = nkb;
+  ok(dalloc(&T.flow_flags, 4 * (size_t)T.n_strips_total + 2 * (size_t)nkb + 4));
+  {
+    // which form: the level launches pay ~17 us a level when a level is a handful of tiles and ~43 us when its trailing update is large; the flow
+    // form pays one launch and a ~19 us chain per level whatever the level's size
+    int cus = 256;
+    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    T.flow_wgs = cus;
+    const int32_t why = tile_flow_refusal(SC, T.ldS, cus);
+    T.flow = why == 0 ? 1 : 0;
+    if (flow_refusal) *flow_refusal = why;
+  }
+  T.strip_flags = reinterpret_cast<int32_t*>(T.ytmp + (size_t)T.n_pad + 64);   // behind the back substitution's words, cleared with them
+  T.h_level_off = SC.level_off.data(); T.h_strip_off = SC.strip_off.data(); T.h_tgt_off = SC.tgt_off.data();
+  return rc;
+}
+// ticket + hand-off flags of the back substitution and of the level launches (ytmp), the flow form's flags
+hipError_t tile_system_zero_flags(hipStream_t s, const TileSystem& T) {
+  const hipError_t e = hipMemsetAsync(T.ytmp, 0, ((size_t)T.n_pad + 64 + 2 * (size_t)T.n_strips_total + 2) * sizeof(double), s);
+  return e != hipSuccess ? e : hipMemsetAsync(T.flow_flags, 0, (4 * (size_t)T.n_strips_total + 2 * (size_t)T.n_tiles_total + 4) * sizeof(int32_t), s);
+}
+}  // namespace dvm
+
 extern "C" {
 
 int dvm_ba_create(int device, dvm_ba** out) {
@@ -227,59 +302,28 @@ void dvm_ba_destroy(dvm_ba* h) {
   delete h;
 }
 
-// the default choice between the level launches and the flow form of the reduced solve (k_chol_flow); DVM_BA_FLOW overrides it
-// Measured (DESIGN.md section 10): the flow form costs ~15.5 us per level of a chain (the factorisation's own 7.7 us + the parent strip and
-// its product in the same workgroup) and ~18 us per level with two children; the level launches ~17 us per level when a level is a handful of
-// tiles and ~20 us when its trailing update is large, and they own the small problems (the top-pair kernel solves a local-BA window's whole
-// reduced system in one workgroup).  From 5 levels on the flow form wins -- 100 keyframes 6 927 -> 7 114 it/s, 200: 5 536 -> 5 739, the
-// 500-keyframe ring 4 036 -> 4 092, the same map with loop closures (13 levels after the kept landmarks) 2 404 -> 2 509 -- as long as its
-// tasks are a few per workgroup: a task holds its workgroup while it waits, and at 1 000 keyframes with loop closures (1 848 tasks on 256
-// workgroups) the level launches are ahead again (1 401 vs 1 313 it/s).
-static bool kFlowDefault(const BaTileSchedule& SC, int workgroups) { return SC.nlevels >= 5 && (int)(SC.flow_tasks.size() / 8) <= 4 * workgroups; }
-// The tile system of a bundle adjustment (T.nfree cameras in ncamt tiles, the kept landmarks' tiles behind them) from its schedule: dimensions,
-// the schedule's arrays, the buffers of the solve (x: x_len doubles) and the form the solve takes.  The flags (ytmp, flow_flags) and x are
-// zeroed by the caller, behind its uploads.
+// The tile system of a bundle adjustment (nfree cameras in ncamt tiles, the kept landmarks' tiles behind them): tile_system_fill on the handle's
+// arena, then the A/B switches of the environment on the form it chose.
 static int fill_tile_system(dvm_ba* h, TileSystem& T, const BaTileSchedule& SC, int ncamt, const std::vector<int32_t>& kept_list, size_t x_len) {
-  const int nkb = SC.ntiles;    // camera tiles + kept-landmark tiles + the tile of the augmented rhs row
-  T.ncamt = ncamt; T.nkept = (int)kept_list.size();
-  T.n_pad = 64 * (nkb - 1);
-  T.per_tile = kCamsPerTile; T.dof = 6;
-  T.ldS = 64 * nkb;
-  T.nlevels = SC.nlevels;
-  T.pair_ok = SC.pair_a >= 0 && std::getenv("DVM_BA_NO_PAIR") == nullptr; T.pair_a = SC.pair_a; T.pair_b = SC.pair_b;   // (DVM_BA_NO_PAIR: A/B switch)
-  T.diag_in_level = std::getenv("DVM_BA_NO_DIAG_IN_LEVEL") == nullptr;
-  T.n_root_raw = std::getenv("DVM_BA_NO_ROOT_RAW") ? 0 : SC.n_root_raw;   // (ba_ordering.h: the last launched level's panel solve left to the back substitution; the switch: A/B and tests)
-  int rc = DVM_OK;
-  auto ok = [&](int r) { if (rc == DVM_OK) rc = r; };
-  ok(h->dalloc(&T.S, (size_t)T.ldS * T.ldS)); ok(h->dalloc(&T.Linv, (size_t)(T.ldS / 64) * 64 * 64)); ok(h->dalloc(&T.ytmp, (size_t)T.n_pad + 64 + 2 * (SC.strips.size() / 2) + 2));
-  ok(h->dalloc(&T.xrow, (size_t)T.n_pad + 64));
-  ok(h->dalloc(&T.x, x_len));
-  ok(h->upload(&T.nz_tiles, SC.nz_tiles)); T.n_nz = (int)(SC.nz_tiles.size() / 2);
-  ok(h->upload(&T.cols, SC.cols)); ok(h->upload(&T.strips, SC.strips)); ok(h->upload(&T.targets, SC.targets));
-  ok(h->upload(&T.contrib, SC.contrib)); ok(h->upload(&T.colstrip_off, SC.colstrip_off)); ok(h->upload(&T.colstrips, SC.colstrips));
-  ok(h->upload(&T.contrib_strip, SC.contrib_strip));
-  if (T.nkept) ok(h->upload(&T.kept_list, kept_list));
-  // the flow form of the solve (k_chol_flow): task list, per-tile level ranges, flags (zeroed once: they are compared with the solve's sequence number)
-  ok(h->upload(&T.flow_tasks, SC.flow_tasks)); ok(h->upload(&T.flow_contrib, SC.flow_contrib)); ok(h->upload(&T.flow_col, SC.flow_col)); ok(h->upload(&T.colstrip_id, SC.colstrip_id));
-  T.n_flow_tasks = (int)(SC.flow_tasks.size() / 8); T.n_strips_total = (int)(SC.strips.size() / 2); T.n_tiles_total = nkb;
-  ok(h->dalloc(&T.flow_flags, 4 * (size_t)T.n_strips_total + 2 * (size_t)nkb + 4));
-  {
-    // which form: the level launches pay ~17 us a level when a level is a handful of tiles and ~43 us when its trailing update is large; the flow
-    // form pays one launch and a ~19 us chain per level whatever the level's size.  DVM_BA_FLOW=0 / 1 forces the choice (A/B switch).
-    const char* e = std::getenv("DVM_BA_FLOW");
-    int cus = 256;
-    hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
-    T.flow_wgs = cus;
-    const bool fits = (size_t)T.ldS * T.ldS * sizeof(double) < (size_t)0x7FFFFFF0;      // 32-bit buffer offsets into S
-    // (the chains -- one per leaf of the elimination tree -- wait for tasks the OTHER workgroups draw: they must stay a minority)
-    // several roots (a disconnected reduced camera graph): one tree's back substitution could write x before a diagonal tile of another
-    // tree fails, and g2o's linear solver leaves x untouched when the factorisation fails -- such graphs keep the level launches
-    int roots = 0;
-    for (size_t k = 0; k + 1 < SC.flow_col.size() / 8; k++) roots += SC.flow_col[8 * k] < 0;
-    T.flow = (e ? std::atoi(e) != 0 : kFlowDefault(SC, cus)) && fits && 4 * SC.flow_leaves <= cus && roots <= 1 ? 1 : 0;
-  }
-  T.strip_flags = reinterpret_cast<int32_t*>(T.ytmp + (size_t)T.n_pad + 64);   // behind the back substitution's words, cleared with them
-  T.h_level_off = SC.level_off.data(); T.h_strip_off = SC.strip_off.data(); T.h_tgt_off = SC.tgt_off.data();
+  struct HandleArena final : TileArena {
+    dvm_ba* h;
+    int alloc(void** p, size_t bytes) override { uint8_t* q = nullptr; const int rc = h->dalloc(&q, bytes); *p = q; return rc; }
+    int upload(const void** p, const void* src, size_t bytes) override {
+      uint8_t* q = nullptr;
+      int rc = h->dalloc(&q, bytes);
+      if (rc == DVM_OK) rc = h->copy_in(q, src, bytes);
+      *p = q;
+      return rc;
+    }
+  } A;
+  A.h = h;
+  int32_t why = 0;
+  const int rc = tile_system_fill(A, h->device, T, SC, T.nfree, kCamsPerTile, 6, ncamt, kept_list.data(), (int)kept_list.size(), x_len, &why);
+  if (std::getenv("DVM_BA_NO_PAIR")) T.pair_ok = 0;               // (A/B switch)
+  if (std::getenv("DVM_BA_NO_DIAG_IN_LEVEL")) T.diag_in_level = 0;
+  if (std::getenv("DVM_BA_NO_ROOT_RAW")) T.n_root_raw = 0;        // (the switch: A/B and tests)
+  // DVM_BA_FLOW=0 / 1 forces the choice between the level launches and the flow form (A/B switch); what forbids the flow form still does
+  if (const char* e = std::getenv("DVM_BA_FLOW")) T.flow = std::atoi(e) != 0 && !(why & (kFlowTooLarge | kFlowSeveralRoots | kFlowTooManyLeaves)) ? 1 : 0;
   return rc;
 }
 // Graph construction ("buildStructure", block_solver.hpp:143-295): vertex ordering, CSR incidence
@@ -603,8 +647,7 @@ static int set_problem_impl(dvm_ba* h, const double* poses, const uint8_t* fixed
   // (S is NOT cleared as a whole: every kernel touches structurally non-zero tiles only, and a trial's prologue clears exactly
   //  those.  The matrix is ldS^2 doubles -- 1.3 GB at 2 000 keyframes.)
   ok(hip_check(hipMemsetAsync(V.e_chi2, 0, (size_t)E * sizeof(double), h->stream), "memset"));
-  ok(hip_check(hipMemsetAsync(V.T.ytmp, 0, ((size_t)V.T.n_pad + 64 + 2 * (SC.strips.size() / 2) + 2) * sizeof(double), h->stream), "memset"));   // ticket + hand-off flags of the back substitution
-  ok(hip_check(hipMemsetAsync(V.T.flow_flags, 0, (4 * (size_t)V.T.n_strips_total + 2 * (size_t)nkb + 4) * sizeof(int32_t), h->stream), "memset"));
+  ok(hip_check(tile_system_zero_flags(h->stream, V.T), "memset"));
   h->solve_seq = 0; h->fuse_levels = true;
   ok(hip_check(hipStreamSynchronize(h->stream), "sync"));
   if (rc != DVM_OK) { h->free_problem(); return rc; }

@@ -7,7 +7,10 @@
 //   k_chol_backsolve       L^T x = y
 //   k_chol_flow            the whole factorisation and solve as one dataflow launch
 //   tile_launch_cholesky_solve   picks the form from the TileSystem's members
-// Every sum has a fixed order: results are run-to-run deterministic, and the same whichever form solves.
+// Every sum has a fixed order: results are run-to-run deterministic.  The level launches give the same bits on every path (level in one
+// launch, slices with the diagonal tiles + update, diag + fused solve/update, one launch per phase, diagonal tiles in or out of the level), and
+// so does the flow form.  Two forms sum in an order of their own and agree with those to rounding only: k_chol_pair on its two columns, and
+// the back substitution's panel solve of the raw root columns (n_root_raw) against a launched one (tests/test_gpu_tile_solve.py holds all this).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1502,9 +1505,12 @@ __global__ void __launch_bounds__(256) k_chol_flow(FlowArgs A) {
 
 constexpr int kDiagLevelMaxWGs = 256;    // k_chol_trsm_update<true>: 86 KB of LDS, one workgroup per CU
 constexpr int kFusedLevelMaxWGs = 512;   // 2 workgroups per CU on 256 CUs (3 fit: 41 KB of LDS each); the leaf level of the BASELINE problem (536) measured the same fused or not
-void tile_launch_cholesky_solve(hipStream_t s, const TileSystem& T, int* d_fail, int solve_seq) {
+void tile_launch_cholesky_solve(hipStream_t s, const TileSystem& T, int* d_fail, int solve_seq, TileSolveTrace* trace) {
+  if (trace) *trace = TileSolveTrace{};
   if (T.nfree == 0) return;
   const int n1 = T.n_pad + 1;
+  if (trace) trace->nlevels = std::min<int>(T.nlevels, TileSolveTrace::kMaxLevels);
+  auto took = [&](int h, TileLevelPath p) { if (trace && h < TileSolveTrace::kMaxLevels) trace->path[h] = p; };
   if (T.flow && T.flow_tasks && T.flow_flags) {     // the whole solve as one persistent launch of tile tasks (k_chol_flow)
     FlowArgs A;
     A.S = T.S; A.ldS = T.ldS; A.n1 = n1; A.n_pad = T.n_pad; A.Linv_all = T.Linv;
@@ -1519,6 +1525,7 @@ void tile_launch_cholesky_solve(hipStream_t s, const TileSystem& T, int* d_fail,
     A.nfree = T.nfree; A.per_tile = T.per_tile; A.dof = T.dof; A.ncamt = T.ncamt; A.nkept = T.nkept; A.kept_list = T.kept_list;
     const int wgs = std::max(1, std::min(A.n_factor + A.n_back, T.flow_wgs > 0 ? T.flow_wgs : 256));
     hipLaunchKernelGGL(k_chol_flow, dim3(wgs), dim3(256), 0, s, A);
+    if (trace) trace->flow = 1;
     return;
   }
   // test switch: the slices publish a sequence number nobody waits for, so every wait times out and the caller's retry path
@@ -1548,6 +1555,7 @@ void tile_launch_cholesky_solve(hipStream_t s, const TileSystem& T, int* d_fail,
                          T.contrib_strip, T.strip_flags, solve_seq, break_handoff ? -1 : solve_seq, d_fail, tag, T.n_pad);
       tag = nullptr;
       if (nt > 0 && !all) hipLaunchKernelGGL(k_chol_update, dim3(4 * nt), dim3(256), 0, s, T.S, T.ldS, n1, T.targets + 4 * (size_t)T.h_tgt_off[h], T.contrib);
+      took(h, all ? kPathLevelOneLaunch : kPathSlicesDiagUpdate);
       continue;
     }
     hipLaunchKernelGGL(k_chol_diag, dim3(nc), dim3(256), 0, s, T.S, T.ldS, n1, T.cols + T.h_level_off[h], d_fail, T.Linv);
@@ -1558,8 +1566,10 @@ void tile_launch_cholesky_solve(hipStream_t s, const TileSystem& T, int* d_fail,
                          T.h_strip_off[h], 4 * ns, T.targets + 4 * (size_t)T.h_tgt_off[h], T.contrib, T.contrib_strip, T.strip_flags, solve_seq,
                          break_handoff ? -1 : solve_seq, d_fail, tag, T.n_pad);
       tag = nullptr;
+      took(h, kPathDiagFused);
       continue;
     }
+    took(h, raw_root ? kPathRawRoot : kPathDiagTrsmUpdate);
     if (raw_root) continue;
     if (ns > 0) { hipLaunchKernelGGL(k_chol_trsm, dim3(4 * ns), dim3(256), 0, s, T.S, T.ldS, n1, T.Linv, T.strips + 2 * (size_t)T.h_strip_off[h], tag, T.n_pad); tag = nullptr; }
     if (nt > 0) hipLaunchKernelGGL(k_chol_update, dim3(4 * nt), dim3(256), 0, s, T.S, T.ldS, n1, T.targets + 4 * (size_t)T.h_tgt_off[h], T.contrib);
@@ -1573,7 +1583,9 @@ void tile_launch_cholesky_solve(hipStream_t s, const TileSystem& T, int* d_fail,
     hipLaunchKernelGGL(k_chol_pair, dim3(1), dim3(256), 0, s, T.S, T.ldS, T.n_pad, T.pair_a, T.pair_b, T.nfree, T.per_tile, T.dof, T.xrow, T.x, d_fail, T.ncamt, T.nkept, T.kept_list);
     ncols -= 2;          // `cols` lists the levels in order: the pair's columns are its last two entries
     n_raw = 0;
+    if (trace) trace->pair = 1;
   }
+  if (trace) trace->backsolve_cols = std::max(ncols, 0);
   if (ncols > 0)
     hipLaunchKernelGGL(k_chol_backsolve, dim3(ncols), dim3(256), 0, s, T.S, T.ldS, T.n_pad, T.nfree, T.per_tile, T.dof, T.cols, ncols,
                        T.S + (size_t)T.n_pad * T.ldS, T.xrow, T.x, T.Linv, T.colstrip_off, T.colstrips, reinterpret_cast<int32_t*>(T.ytmp),

@@ -64,9 +64,50 @@ struct TileSystem {
   const int32_t* kept_list; // [nkept]
 };
 
+// What tile_launch_cholesky_solve launched, written on the HOST for a caller that asks (the test hook dvm_tile_solve_debug): per level of the
+// schedule the path it took, and whether the top pair / the flow form solved.  Levels past kMaxLevels are not recorded.
+enum TileLevelPath : int32_t {
+  kPathNone = 0,          // nothing launched for the level: the rhs tile's level, a level of the top pair, every level of the flow form
+  kPathLevelOneLaunch,    // k_chol_trsm_update<true> over slices and quadrants: the whole level, diagonal tiles included, in one launch
+  kPathSlicesDiagUpdate,  // k_chol_trsm_update<true> over the slices (diagonal tiles inside), k_chol_update behind it when the level has targets
+  kPathDiagFused,         // k_chol_diag, then k_chol_trsm_update<false>: panel solves and trailing update in one launch
+  kPathDiagTrsmUpdate,    // k_chol_diag, k_chol_trsm, k_chol_update: one launch per phase (a phase without work is not launched)
+  kPathRawRoot,           // k_chol_diag alone: the panel solve of the root columns is left to the back substitution (n_root_raw)
+};
+struct TileSolveTrace {
+  static constexpr int kMaxLevels = 64;
+  int32_t nlevels;            // levels recorded
+  int32_t path[kMaxLevels];   // TileLevelPath per level
+  int32_t pair;               // 1: k_chol_pair solved the top two columns
+  int32_t flow;               // 1: k_chol_flow did the whole solve
+  int32_t backsolve_cols;     // columns handed to k_chol_backsolve (0: not launched)
+};
+
 // Factorisation and solve of T on stream s: x (and xrow) hold the solution afterwards, *d_fail != 0 reports a non-positive pivot (x then
 // keeps what it held) or, = 2, a hand-off wait that gave up (the caller repeats the trial with T.flow = 0 / T.strip_flags = null).
 // solve_seq: a number > 0 that differs from call to call on this system (the hand-off flags compare against it)
-void tile_launch_cholesky_solve(hipStream_t s, const TileSystem& T, int* d_fail, int solve_seq);
+// trace: null, or where the launcher notes what it launched (host memory; the launches are the same either way)
+void tile_launch_cholesky_solve(hipStream_t s, const TileSystem& T, int* d_fail, int solve_seq, TileSolveTrace* trace = nullptr);
+
+// ---- setting a system up from its schedule (ba_solver.cpp), shared by the bundle adjustment and the test hook (tile_debug.cpp)
+struct BaTileSchedule;
+// where the device arrays of a system come from: the bundle adjustment's arena, a plain hipMalloc pool
+struct TileArena {
+  virtual int alloc(void** p, size_t bytes) = 0;                            // device memory, not initialised
+  virtual int upload(const void** p, const void* src, size_t bytes) = 0;    // device memory holding a copy of src
+ protected:
+  ~TileArena() = default;
+};
+// why a schedule is kept off the flow form (tile_flow_refusal): the first three forbid it, the last is the measured preference
+enum : int32_t { kFlowTooLarge = 1, kFlowSeveralRoots = 2, kFlowTooManyLeaves = 4, kFlowNotPreferred = 8 };
+int32_t tile_flow_refusal(const BaTileSchedule& SC, int32_t ldS, int workgroups);
+// The tile system of nfree unknown blocks (per_tile of dof rows to a tile) in ncamt tiles with the kept landmarks' tiles behind them, from its
+// schedule: dimensions, the schedule's arrays, the buffers of the solve (x: x_len doubles) and the form the solve takes by default -- top pair
+// when the schedule has one, diagonal tiles inside the level launches, n_root_raw honoured, in-launch hand-offs, the flow form when
+// tile_flow_refusal is 0 (returned in *flow_refusal).  T holds pointers into SC.  The flags and x are zeroed by the caller, behind its
+// uploads: tile_system_zero_flags.
+int tile_system_fill(TileArena& A, int device, TileSystem& T, const BaTileSchedule& SC, int nfree, int per_tile, int dof, int ncamt,
+                     const int32_t* kept_list, int nkept, size_t x_len, int32_t* flow_refusal);
+hipError_t tile_system_zero_flags(hipStream_t s, const TileSystem& T);
 
 }  // namespace dvm

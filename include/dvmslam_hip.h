@@ -1618,6 +1618,50 @@ int dvm_pose_graph_debug_trial(int device, double* S, const uint8_t* fixed, int 
                                double lambda, double* e, double* J, double* H, double* b, double* x, int32_t* vidx,
                                dvm_pg_trial_stats* stats);
 
+/* Test hook (tests/test_gpu_tile_solve.py): ONE linear system through the tile Cholesky that solves the bundle adjustment's reduced system
+ * and the pose graph's normal equations, with no edge, camera or Levenberg-Marquardt step around it: the same schedule (ba_tile_schedule), the
+ * same set-up of the solver's members, the same launcher.  Host pointers, synchronous.
+ * The system, in unknown space and elimination order: n_blocks blocks of dof rows, per_tile to a 64-row tile ((dof, per_tile) = (6, 10) or
+ * (7, 9)), then n_kept blocks of 3 rows, 21 to a tile (kept landmark j = landmark kept_list[j] of n_landmarks, each listed once);
+ * n = dof * n_blocks + 3 * n_kept.  A[n][n] row-major, symmetric positive definite, lower triangle read; b[n];
+ * mask[tiles][tiles] (lower triangle read): the structurally non-zero tiles -- a tile may be present and hold zeros, a non-zero of A outside
+ * the mask is refused -- or null: the tiles where A (or A2) is not zero (either way all of A is read on the host, O(n^2), with the other
+ * argument checks and before a device is looked for).  x_in[dof * n_blocks + 3 * n_landmarks]: what x holds before each solve.
+ * form: 0 = level launches as the bundle adjustment sets them up by default (top pair when the schedule has one, diagonal tiles inside the
+ * level launches, n_root_raw honoured, in-launch hand-offs), changed by the DVM_TILE_FORM_* bits; a flow form that the admission test
+ * forbids (info->flow_refusal & 7) is an error, never a silent fall-back.
+ * repeats (1..8): the system is solved that many times on the same structure, S rewritten and x reset to x_in before each solve, the
+ * sequence number of the hand-off flags increasing; with A2 / b2 (both or neither; same mask) that second system is solved in between.
+ * Outputs: x[repeats][dof * n_blocks + 3 * n_landmarks] (unknown block i at dof * i, landmark l at dof * n_blocks + 3 * l), fail[repeats]
+ * (non-zero: a non-positive pivot, x keeps x_in), x2 / fail2 (null, or [repeats - 1] of the same): the solves of A2 in between; info: the
+ * schedule and, for the first solve, what the launcher launched. */
+#define DVM_TILE_FORM_FLOW 1              /* k_chol_flow: factorisation and back substitution in one launch */
+#define DVM_TILE_FORM_NO_PAIR 2           /* the top pair goes through the level launches, not k_chol_pair */
+#define DVM_TILE_FORM_NO_DIAG_IN_LEVEL 4  /* diagonal tiles by k_chol_diag, never inside a level launch */
+#define DVM_TILE_FORM_NO_ROOT_RAW 8       /* the root columns' panel solve is launched, not left to the back substitution */
+#define DVM_TILE_FORM_PER_PHASE 16        /* no in-launch hand-offs: one launch per phase, the pose graph's form */
+/* level_path[h]: what was launched for level h */
+#define DVM_TILE_PATH_NONE 0                /* nothing: the rhs tile's level, the top pair's levels, every level of the flow form */
+#define DVM_TILE_PATH_LEVEL_ONE_LAUNCH 1    /* the whole level, diagonal tiles included, in one launch */
+#define DVM_TILE_PATH_SLICES_DIAG_UPDATE 2  /* panel slices with the diagonal tiles in one launch, the trailing update behind it */
+#define DVM_TILE_PATH_DIAG_FUSED 3          /* diagonal tiles, then panel solves + trailing update in one launch */
+#define DVM_TILE_PATH_DIAG_TRSM_UPDATE 4    /* diagonal tiles, panel solves, trailing update: one launch each */
+#define DVM_TILE_PATH_RAW_ROOT 5            /* diagonal tiles alone; the back substitution does the panel solve */
+typedef struct {
+  int32_t n_tiles, levels, pair_a, pair_b, n_root_raw, flow_leaves, roots, flow_tasks;
+  int32_t flow_refusal;      /* 1 S too large, 2 several roots, 4 too many leaves for the workgroups, 8 the level launches are preferred */
+  int32_t traced_levels, used_pair, used_flow, backsolve_cols, reserved;
+  int32_t level_nc[64], level_ns[64], level_nt[64];   /* columns, strips and trailing targets per level (first 64) */
+  int32_t level_path[64];
+} dvm_tile_solve_info;
+int dvm_tile_solve_debug(int device, int n_blocks, int dof, int per_tile, int n_kept, const int32_t* kept_list, int n_landmarks,
+                         const double* A, const double* b, const uint8_t* mask, const double* x_in, int form, int repeats,
+                         const double* A2, const double* b2, double* x, int32_t* fail, double* x2, int32_t* fail2, dvm_tile_solve_info* info);
+/* Test hook, host only (no device needed): the schedule of a tile mask over n_tiles tiles of unknowns as dvm_tile_solve_debug would
+ * build it, with the flow form's admission test for `workgroups` compute units.  Fills the schedule part of info.  n_tiles <= 256: the
+ * symbolic factorisation keeps dense per-level maps, fine for a test and for nothing larger. */
+int dvm_tile_schedule_debug(int n_tiles, const uint8_t* mask, int workgroups, dvm_tile_solve_info* info);
+
 /* Sim3Solver::ComputeSim3 + CheckInliers (src/Sim3Solver.cc:294-408) for H RANSAC hypotheses in one launch.
  * P1c / P2c: the N matched map points in the two keyframes' camera frames (mvX3Dc1 / mvX3Dc2, float[3N]);
  * max_err1/2: mvnMaxError1/2 as the reference stores them, (float)(size_t)(9.210 * sigma2); K1 / K2: fx, fy, cx, cy;

@@ -68,6 +68,9 @@ def test_count_only_entry_points(L):
     # dvm_pose_graph_debug_trial(device, S, fixed, n, edges, E, fix_scale, lambda, e, J, H, b, x, vidx, stats)      pg_solver.cpp
     _refused(L, L.dvm_pose_graph_debug_trial(i32(0), _ptr(z), _ptr(z), i32(2), _ptr(z), i32(1), i32(1), C.c_double(1.0), _ptr(z), _ptr(z), _ptr(z),
                                              _ptr(z), _ptr(z), _ptr(z), _ptr(z)))
+    # dvm_tile_solve_debug(device, n_blocks, dof, per_tile, n_kept, kept_list, n_landmarks, A, b, mask, x_in, form, repeats, A2, b2, x, fail, x2, fail2, info)   tile_debug.cpp
+    _refused(L, L.dvm_tile_solve_debug(i32(0), i32(1), i32(6), i32(10), i32(0), vp(0), i32(0), _ptr(z), _ptr(z), vp(0), _ptr(z), i32(0), i32(1), vp(0),
+                                       vp(0), _ptr(z), _ptr(z), vp(0), vp(0), _ptr(z)))
     # dvm_wire_gather_keypoints(d_block, first_kf, count, d_kps, kps_stride, d_desc, desc_stride, stream)         wire.cpp
     _refused(L, L.dvm_wire_gather_keypoints(vp(64), i32(0), i32(1), vp(64), C.c_int64(1), vp(64), C.c_int64(32), vp(0)))
 
@@ -79,3 +82,6 @@ def test_count_only_entry_points(L):
     assert L.dvm_triangulate_matches(_ptr(pair), *tri) == INVALID
     assert L.dvm_last_error() == b"dvm_triangulate_matches: n_levels out of range"
     assert L.dvm_is_in_frustum(_ptr(z), vp(0), _ptr(z), _ptr(z), _ptr(z), i32(1), f32(0.5), _ptr(z), i32(0), vp(0)) == INVALID
+    assert L.dvm_tile_solve_debug(i32(0), i32(1), i32(6), i32(9), i32(0), vp(0), i32(0), _ptr(z), _ptr(z), vp(0), _ptr(z), i32(0), i32(1), vp(0), vp(0),
+                                  _ptr(z), _ptr(z), vp(0), vp(0), _ptr(z)) == INVALID          # (6, 9) is neither layout
+    assert L.dvm_last_error() == b"dvm_tile_solve_debug: bad arguments"
